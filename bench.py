@@ -21,13 +21,20 @@ the chip, so the events around ONE launch (`roofline.kernel_ms_bracketed`, what
 rocprofv3 --stats reports as the kernel's average duration for this command) span
 about F frame periods; `roofline.kernel_ms`, the duration `achieved` is priced on,
 is the chip time per launch: HIP events from the first timed launch's start to the
-last one's end on the launch streams, divided by K.  At N = 1 the plain
+last one's end on the launch streams, divided by K.  With --full, at N = 1 the plain
 one-stream loop (`--inflight 1`: each frame starts when the previous one has
 ended, ms_per_step = a frame's latency) is measured right after the timed region
 and reported as `extra.one_frame_in_flight`.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W --full
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, renders W warm-up frames, times exactly K frames (frames W .. W + K - 1) once and prints the line:
+ms_per_step = that stretch / K.  --full adds everything else: the timed block repeated (5 blocks and at least 8 s,
+the median block reported), frame 0 against the oracle, the CPU baseline and the untimed extras (N > 1: the gathered
+frame against the unsharded one, render-only time per rank, the other exchange forms).  --dump-outputs DIR writes the
+frame of the last timed step (DIR/image.npy, float32); the frames rendered depend on W and K only.
 
 Both lines work for every N.  Started plainly (no WORLD_SIZE in the environment) with N > 1, this process is only the
 fork/join (the one call of main.cpp:139-154, execute + waitExecutionDone): before anything that could touch the GPU is
@@ -328,7 +335,7 @@ def free_port():
 
 def other_exchange_forms(headline, world, no_extras=False):
     """the exchange forms a run measures after its timed region (extra.exchange_forms), in order: the two that are not the
-    headline form; none at N = 1 or with --no-extras"""
+    headline form; none at N = 1, without --full or with --no-extras"""
     return [] if world <= 1 or no_extras else [f for f in ("root", "all", "peer") if f != headline]
 
 
@@ -405,6 +412,26 @@ def oracle_frame(cfg, nodes, textures, cam, light, threads):
     return O.samples_to_image(acc), rays, sumc
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, image):
+    """--dump-outputs: the frame a caller of the timed path receives (RGBA8, H x W x 4) as float32 DIR/image.npy; a frame
+    over DUMP_MAX_BYTES as float32 is written as a fixed sample of its pixels (seed 0): image_sample.npy (pixels x 4) and
+    image_sample_pixels.npy (their row-major indices, float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.asarray(image, np.float32)
+    if img.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), img)
+        return
+    h, w, c = img.shape
+    n = DUMP_MAX_BYTES // (c * 4 + 8) // 2
+    pix = np.sort(np.random.default_rng(0).choice(h * w, size=n, replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), img.reshape(h * w, c)[pix])
+    np.save(os.path.join(out_dir, "image_sample_pixels.npy"), pix.astype(np.float64))
+
+
 def exchange_facts(torch, dist, backend, world):
     """What the N > 1 exchange ran on, for the bench line: RCCL's version, the GPUs of the node and which of them can reach
     which directly (hipDeviceCanAccessPeer: xGMI links between the ranks' devices), and the IPC mode of the run."""
@@ -431,10 +458,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--pitch", type=float, default=-0.5)
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of `steps` frames each (the median block is reported)")
-    ap.add_argument("--blocks-min-seconds", type=float, default=8.0,
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: repeated timed blocks (defaults 5 blocks / 8 s), the frame-0 parity "
+                         "check against the oracle, the CPU baseline, the untimed extras (N = 1: one frame in flight, the timed symbol "
+                         "alone, 2-bounce extension, walks from the root, invariant-ray reuse; N > 1: gathered frame vs unsharded, "
+                         "render-only time per rank, the other exchange forms).  Without it a run times exactly `steps` frames once")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region, write the frame its last step produced (rank 0's RGBA8 image as float32) to DIR/image.npy; "
+                         "frames above 64 MB as float32 are written as a fixed seeded pixel sample (image_sample.npy + image_sample_pixels.npy)")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="timed blocks of `steps` frames each (the median block is reported); default 1, with --full 5")
+    ap.add_argument("--blocks-min-seconds", type=float, default=None,
                     help="keep timing blocks until this much has been timed (max 4096 blocks): the timed region is one contiguous stretch of GPU "
-                         "work several seconds long, so that an outside sampler of GPU activity sees it (round-3 verdict item 5)")
+                         "work several seconds long, so that an outside sampler of GPU activity sees it (round-3 verdict item 5); "
+                         "default 0, with --full 8")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-oracle-frame", action="store_true",
                     help="skip config.frame_equals_oracle (frame 0 of the timed renderers -- at N > 1 the gathered frame 0 -- against the oracle's)")
@@ -451,7 +488,7 @@ def main():
     ap.add_argument("--fused", default="auto", choices=["auto", "0", "1"],
                     help="resolve + pack + reset inside the frame kernel (vrc_render_frame_resolved) instead of a second kernel; "
                          "auto = whenever frames overlap (whole-spp work units: the fused path then resolves from registers, "
-                         "never slower, 1 % faster on short shards; tools/shard_inflight.py, tools/resolve_cost.py)")
+                         "never slower, 1 %% faster on short shards; tools/shard_inflight.py, tools/resolve_cost.py)")
     ap.add_argument("--whole-spp", default="auto", choices=["auto", "0", "1"],
                     help="work unit of the frame kernel = a tile's WHOLE sample set (vrc_renderer_set_sample_chunk(spp)); auto = whenever "
                          "frames overlap (--inflight > 1).  `--inflight 1 --whole-spp 1 --fused 1 --lane-samples 1` runs the timed "
@@ -461,18 +498,24 @@ def main():
                          "4 = 4 x 4 pixels x 4 samples abreast, 0 = the library's choice")
     ap.add_argument("--no-quad", action="store_true",
                     help="A/B: vrc_renderer_set_quad_walks(0) -- the pinhole kernel's sample-invariant walks in the plain 8 x 8 x 1 layout")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extra measurements (2-bounce extension; N > 1: the other exchange forms)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed extra measurements (2-bounce extension; N > 1: the other exchange forms)")
     ap.add_argument("--forms-deadline-s", type=float, default=240.0,
                     help="N > 1: the untimed block that measures the other exchange forms (extra.exchange_forms) may take this long; after it "
                          "rank 0 prints the headline line it already has and every rank leaves")
     ap.add_argument("--tuning", default="", help="blocks_per_cu: workgroups of the frame kernel per CU (= which waves-per-SIMD build), 0 = the library's choice")
     args = ap.parse_args()
+    if args.blocks is None:
+        args.blocks = 5 if args.full else 1
+    if args.blocks_min_seconds is None:
+        args.blocks_min_seconds = 8.0 if args.full else 0.0
+    # the extras, checks and baselines run only with --full; a plain run is set-up, warm-up, the timed steps and the line
+    no_extras = args.no_extras or not args.full
 
     # the fork/join of main.cpp:139-154 across GPUs: plain `python bench.py --gpus N` starts its own ranks -- decided here,
     # before torch (or anything else that can touch the GPU) is imported
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], plan_extra={
-            "headline_exchange": args.gather, "exchange_forms_measured_by_the_same_ranks": other_exchange_forms(args.gather, args.gpus, args.no_extras),
+            "headline_exchange": args.gather, "exchange_forms_measured_by_the_same_ranks": other_exchange_forms(args.gather, args.gpus, no_extras),
             "forms_deadline_s": args.forms_deadline_s, "processes_started_for_them": 0}))
 
     import numpy as np
@@ -698,8 +741,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step(True)
+        for j in range(args.steps):
+            step(True, frame_override=args.warmup + j)         # every block renders the same frames: warmup .. warmup + steps - 1
         enq_us = (time.perf_counter() - t0) / args.steps * 1e6   # host time to issue a frame (no waiting on the GPU unless a slot is busy)
         t_dr = time.perf_counter()
         drain()                                                # the last frames' gathers are inside the timed region
@@ -723,6 +766,13 @@ def main():
     ev_pairs.extend(med_events)
     block_ms = [b[0] / args.steps * 1e3 for b in blocks]
     stream = tstreams[0].cuda_stream
+    if args.dump_outputs and rank == 0:
+        # the frame the last timed step produced, as a caller of the timed path receives it (N > 1: the gathered frame)
+        if not dist_on:
+            last = rcs[(state["i"] - 1) % F].readImage(stream)
+        else:
+            last = rcs[state["last_slot"]].readImage(stream) if peers is not None else full[state["last_slot"]].cpu().numpy().reshape(H, W, 4)
+        dump_outputs(args.dump_outputs, last)
 
     class _Sum:
         rays = sum(x.rays for x in sts)
@@ -751,10 +801,10 @@ def main():
         kernel_ms_max = kernel_ms
 
     verified = None
-    if dist_on and rank == 0:
+    if dist_on and rank == 0 and args.full:
         # not timed: the gathered frame must equal the unsharded render of the same samples
         ref = make_renderer()
-        ref.frame_index = (state["i"] - 1) * spp                 # the last frame rendered
+        ref.frame_index = (args.warmup + args.steps - 1) * spp   # the last frame rendered (every timed block ends on it)
         ref.renderFrame(cam, spp=spp, stream=stream)
         ref.samples_to_image(stream)
         torch.cuda.synchronize()
@@ -781,13 +831,13 @@ def main():
         return got
 
     frame0 = None
-    if dist_on and many and not args.no_oracle_frame:
+    if dist_on and many and args.full and not args.no_oracle_frame:
         frame0 = frame0_through_exchange()
 
     # N > 1: the chip time per launch above spans this rank's exchange / unpack kernels and waits as well: time the
     # frame kernel of this rank's shard on its own, untimed extra, same renderers / streams / unit policy, no exchange
     render_only_ms = None
-    if dist_on:
+    if dist_on and args.full:
         dist.barrier()                                         # rank 0 has compared the gathered frame (peer writes land in ITS framebuffers)
         n_ro = max(2 * F, min(args.steps, 30))
         evs = []
@@ -828,7 +878,7 @@ def main():
     # (RayContext::gi_bounce is never read), which is what `value` measures -- the 2-bounce EXTENSION
     # (recursive getGlobalIllumination at the GI hit, defined by the oracle) is reported beside it
     extras = {}
-    if rank == 0 and world == 1 and not dist_on and not args.no_extras and F > 1:
+    if rank == 0 and world == 1 and not dist_on and not no_extras and F > 1:
         # the same frames one at a time on one stream: a frame's latency, and the kernel's duration when it has the chip alone
         rc1 = make_renderer(whole=False)                        # the library's own unit policy for a launch alone on the chip
         ts = tstreams[0]
@@ -864,7 +914,7 @@ def main():
             "kernel": rc1.lastKernel(),
             "note": "--inflight 1: one stream, each frame starts when the previous one has ended; the library's automatic work-unit "
                     "policy, resolve as a second kernel; median block of `blocks` (min / median / max in ms_per_step_blocks)"}
-    if rank == 0 and world == 1 and not dist_on and not args.no_extras and F > 1:
+    if rank == 0 and world == 1 and not dist_on and not no_extras and F > 1:
         # the TIMED kernel symbol one launch at a time (round-4 verdict, Next 1): same unit policy, resolve and lane map as the
         # timed renderers, one stream, events around every launch -- the duration rocprofv3 --stats can reproduce
         # (`--inflight 1 --whole-spp 1 --fused 1 --lane-samples 1`, profiles/traffic.json[<config>_n1_inflight1_wholespp])
@@ -904,7 +954,7 @@ def main():
                     "median block); this is what `rocprofv3 --stats -- python3 bench.py --inflight 1 --whole-spp 1 --fused 1 --lane-samples 1` "
                     "reports as the symbol's average duration"}
 
-    if rank == 0 and world == 1 and not dist_on and not args.no_extras and args.config == "c3":
+    if rank == 0 and world == 1 and not dist_on and not no_extras and args.config == "c3":
         # the same way as the timed region: F renderers / streams round-robin, same unit policy, same resolve
         rcs2 = [make_renderer() for _ in range(F)]
         for r2 in rcs2:
@@ -939,7 +989,7 @@ def main():
                     "(oracle/vrc_oracle.c global_illumination, level 1); same frame, same frames in flight and unit policy as the timed "
                     "region, measured right after it"}
 
-    if rank == 0 and world == 1 and not dist_on and not args.no_extras and cfg["aperture"] == 0.0 and cfg.get("gi_bounces", 1) <= 1:
+    if rank == 0 and world == 1 and not dist_on and not no_extras and cfg["aperture"] == 0.0 and cfg.get("gi_bounces", 1) <= 1:
         # untimed extra, the other way round: the same frames with every ray started at the root as the reference's loop does
         # (vrc_renderer_set_walk_from_root) instead of below it, next to the previous hit / the camera -- what the start below
         # the root is worth; same image, same rays, same sum of complexities
@@ -972,7 +1022,7 @@ def main():
             "note": "measurement switch (vrc_renderer_set_walk_from_root): no ray starts below the root; same image, rays and "
                     "complexity sums as the timed region, same frames in flight and unit policy, measured right after it"}
 
-    if rank == 0 and world == 1 and not dist_on and not args.no_extras and cfg["aperture"] == 0.0:
+    if rank == 0 and world == 1 and not dist_on and not no_extras and cfg["aperture"] == 0.0:
         # untimed extra, beyond the reference: the same frames with vrc_renderer_set_invariant_ray_reuse -- a pinhole camera's
         # primary ray and the shadow ray of its hit are the same for every sample, the reference (and `value`) walk them
         # once per sample, here once per pixel and frame.  Same image bit for bit (tests/test_gpu_reuse.py); its Mrays/s
@@ -1203,7 +1253,7 @@ def main():
                 f"({sync_kernel_name}), each its own row blocks, gathered the timed way ({out['config']['sharding']}) vs oracle/vrc_oracle.c: the "
                 f"gathered RGBA8 image bit for bit, rays summed over ranks {rays0} vs {ref_rays}, loop iterations {sumc0} vs {ref_sumc}; oracle time "
                 f"{time.perf_counter() - t_or:.1f} s on rank 0")
-        if world == 1 and not args.no_cpu_baseline and not args.no_oracle_frame:
+        if world == 1 and args.full and not args.no_cpu_baseline and not args.no_oracle_frame:
             # the parity bit of THIS run (round-3 verdict item 4): frame 0 once more on a renderer set up like the timed ones
             # (same unit policy, same resolve, same lane map) against the oracle's frame 0 -- image, rays, loop iterations
             host_nodes = svo.downloadNodes()
@@ -1228,7 +1278,7 @@ def main():
                 f"frame 0 ({spp} samples of all {W * H} pixels) rendered by {chk.lastKernel()} on a renderer configured like the timed ones vs "
                 f"oracle/vrc_oracle.c: resolved RGBA8 image bit for bit, rays {got_st.rays} vs {ref_rays}, loop iterations {got_st.sum_complexity} vs "
                 f"{ref_sumc}; oracle time {time.perf_counter() - t_or:.1f} s")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, svo.downloadNodes(), textures, cam, light)
     # N > 1, untimed extra (round-5 verdict, Next 2): ONE invocation reports all three exchange forms.  After the timed region
     # (the headline form, --gather) the SAME ranks, renderers, streams and buffers run a short block of frames (3 blocks of
@@ -1237,7 +1287,7 @@ def main():
     # set up (hipIpc refused ...) records its error and the run goes on; nothing here can change `value`, and a deadline guards
     # the headline: if the extras have not finished after --forms-deadline-s seconds, rank 0 prints the line it already has
     # (with the reason in extra.exchange_forms) and every rank leaves by itself.  No process is started or replaced.
-    if dist_on and many and not args.no_extras:
+    if dist_on and many and not no_extras:
         forms = {}
         if rank == 0:
             forms[args.gather] = {

@@ -15,12 +15,12 @@ def test_parent_plans_n_ranks_and_never_imports_torch():
     env = dict(os.environ, VRC_BENCH_LAUNCH_DRYRUN="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "HSA_ENABLE_IPC_MODE_LEGACY", "VRC_KEEP_IPC_MODE"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--config", "c4"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--config", "c4", "--full"],
                          env=env, capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, out.stderr
     plan = json.loads(out.stdout.strip().splitlines()[-1])
     assert plan["torch_imported"] is False and plan["modules_touching_gpu"] == []
-    assert plan["argv"][1:] == [os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--config", "c4"]
+    assert plan["argv"][1:] == [os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--config", "c4", "--full"]
     ranks = plan["ranks"]
     assert [r["RANK"] for r in ranks] == [str(i) for i in range(8)]
     assert [r["LOCAL_RANK"] for r in ranks] == [str(i) for i in range(8)]
@@ -32,6 +32,12 @@ def test_parent_plans_n_ranks_and_never_imports_torch():
     after = plan["after_timed_region"]
     assert after["headline_exchange"] == "root" and after["exchange_forms_measured_by_the_same_ranks"] == ["all", "peer"]
     assert after["processes_started_for_them"] == 0 and after["forms_deadline_s"] > 0
+    # without --full the ranks measure the headline form only
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--config", "c4"],
+                         env=env, capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr
+    plain = json.loads(out.stdout.strip().splitlines()[-1])
+    assert plain["torch_imported"] is False and plain["after_timed_region"]["exchange_forms_measured_by_the_same_ranks"] == []
 
 
 def test_the_other_exchange_forms_follow_the_headline_form():
@@ -81,10 +87,13 @@ def test_cpu_quota_is_read_from_cgroup_v2_and_v1(tmp_path):
 
 
 def test_a_launcher_environment_is_left_alone():
-    """Under torch.distributed.run (WORLD_SIZE set) bench.py is a rank, not a launcher: it must go on to the GPU check."""
+    """Under torch.distributed.run (WORLD_SIZE set) bench.py is a rank, not a launcher: it must go on to the GPU checks (no GPU
+    here; on a one-GPU box the next one: RCCL needs a GPU per rank)."""
     env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29999", VRC_BENCH_LAUNCH_DRYRUN="1")
+    env.pop("VRC_DIST_BACKEND", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"], env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode != 0 and "needs a GPU" in out.stderr and out.stdout.strip() == ""
+    assert out.returncode != 0 and out.stdout.strip() == ""
+    assert "needs a GPU" in out.stderr or "RCCL needs one per rank" in out.stderr, out.stderr
 
 
 class FakeProc:

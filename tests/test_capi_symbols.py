@@ -117,8 +117,8 @@ def test_argument_validation_needs_no_gpu(built):
 def test_bmp_texture_readers(built, tmp_path):
     """The data format in front of the path: the reference loads its two albedo tables from 16 x 16 BMP files
     (raycaster.hpp:53-54).  The host adapter's loadBMP and the Python loader decode a 24-bpp bottom-up file (what the
-    reference ships), a 32-bpp one and a top-down one to the same top-down RGB table; where the reference is mounted,
-    its own files decode to the packaged tables."""
+    reference ships), a 32-bpp one and a top-down one to the same top-down RGB table; the reference's own files (kept under
+    tests/golden) decode to the packaged tables."""
     import struct
     import subprocess
     import cpuvoxelraycaster_amd as vrc
@@ -160,9 +160,8 @@ def test_bmp_texture_readers(built, tmp_path):
         out = subprocess.run([exe, str(tmp_path / name)], capture_output=True)
         want = odd if name == "odd.bmp" else rgb
         assert out.stderr.decode() == f"{want.shape[1]} {want.shape[0]}" and out.stdout == want.tobytes(), name
-    ref = "/root/reference/res"
-    if os.path.isdir(ref):
-        t, s = vrc.load_textures_bmp(os.path.join(ref, "grass_top_16x16.bmp"), os.path.join(ref, "grass_side_16x16.bmp"))
-        assert np.array_equal(t, top) and np.array_equal(s, side)
-        out = subprocess.run([exe, os.path.join(ref, "grass_side_16x16.bmp")], capture_output=True)
-        assert out.stdout == side.tobytes()
+    ref = os.path.join(ROOT, "tests", "golden")                  # the reference's own res/grass_{top,side}_16x16.bmp, as data
+    t, s = vrc.load_textures_bmp(os.path.join(ref, "grass_top_16x16.bmp"), os.path.join(ref, "grass_side_16x16.bmp"))
+    assert np.array_equal(t, top) and np.array_equal(s, side)
+    out = subprocess.run([exe, os.path.join(ref, "grass_side_16x16.bmp")], capture_output=True)
+    assert out.stdout == side.tobytes()

@@ -18,7 +18,7 @@ def test_plain_bench_line_launches_its_ranks(built, world, gather):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["VRC_DIST_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "5", "--warmup", "2", "--blocks", "1",
-                          "--blocks-min-seconds", "0", "--gather", gather, "--config", "c4"] + ([] if world == 4 else ["--no-extras"]),
+                          "--blocks-min-seconds", "0", "--gather", gather, "--config", "c4", "--full"] + ([] if world == 4 else ["--no-extras"]),
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
@@ -52,15 +52,15 @@ def test_plain_bench_line_launches_its_ranks(built, world, gather):
 def test_the_drivers_launch_line(built):
     """the line the driver uses for N > 1, word for word: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
     --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W` (here N = 2 ranks sharing the box's one GPU,
-    hence VRC_DIST_BACKEND=gloo).  bench.py is then a rank, not a launcher: rc 0, rank 0's JSON line is the last line of
-    stdout, it says who launched it, validates itself and carries the three exchange forms."""
+    hence VRC_DIST_BACKEND=gloo), with --full.  bench.py is then a rank, not a launcher: rc 0, rank 0's JSON line is the last
+    line of stdout, it says who launched it, validates itself and carries the three exchange forms."""
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["VRC_DIST_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                          "--blocks", "1", "--blocks-min-seconds", "0"], env=env, capture_output=True, text=True, timeout=900)
+                          "--blocks", "1", "--blocks-min-seconds", "0", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
     c = d["config"]
@@ -81,7 +81,7 @@ def test_the_extras_deadline_keeps_the_headline_line(built):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["VRC_DIST_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--blocks", "1",
-                          "--blocks-min-seconds", "0", "--config", "c4", "--forms-deadline-s", "0.05"], env=env, capture_output=True, text=True, timeout=600)
+                          "--blocks-min-seconds", "0", "--config", "c4", "--forms-deadline-s", "0.05", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
     assert d["n_gpus"] == 2 and d["config"]["frame_equals_oracle"] is True and d["value"] > 0

@@ -7,7 +7,7 @@ BARGS=$1; shift
 mkdir -p $OUT
 for v in "$@"; do
   name=${v%%=*}; flags=${v#*=}
-  VRC_EXTRA_FLAGS="$flags" python3 bench.py --no-cpu-baseline --no-extras $BARGS > $OUT/$name.log 2>&1
+  VRC_EXTRA_FLAGS="$flags" python3 bench.py --full --no-cpu-baseline --no-extras $BARGS > $OUT/$name.log 2>&1
   python3 - "$OUT/$name.log" "$name" "$flags" <<'PY'
 import json, sys
 try:
