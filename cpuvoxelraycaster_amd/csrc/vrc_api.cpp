@@ -52,7 +52,7 @@ namespace {
 // kernels, from different threads); the process-wide defaults below only seed new renderers and are read and written
 // under g_tuning_mu.
 struct Tuning {
-    uint32_t blocks_per_cu = 0;         // 0 = the library's choice of build (waves per SIMD), see sync_waves_for
+    uint32_t blocks_per_cu = 0;         // 0 = the library's choice of build (waves per SIMD), see render_impl
     bool blocks_per_cu_set = false;
     uint32_t sample_chunk = 0;   // 0 = automatic
     uint32_t tail_units_per_wave = 4;   // automatic chunking: units of half the chunk for the last tiles (0 = off); tools/chunk_time.py
@@ -612,8 +612,11 @@ int render_impl(vrc_renderer* r, const vrc_camera* cam, const vrc_frame_params* 
     // profiles/r04/pmcq_ns{1,4}.txt, and four abreast has four times the queue pops and unit prologues for a wave to sit out,
     // which a chip kept full by overlapping launches cannot hide -- DESIGN.md section 9).
     const bool caller_whole_spp = tuning.sample_chunk != 0u && tuning.sample_chunk >= a.p.spp;
-    a.lane_samples = (can_s4 && (tuning.lane_samples == 4u || (tuning.lane_samples == 0u && !caller_whole_spp))) ? 4u : 1u;
-    const uint32_t tw = a.lane_samples == 4u ? 4u : 8u;
+    // the build to launch (vrc_internal.h, FrameVariant): its lane map is final here, but for the quadrant walks (below)
+    vrc::FrameVariant v{vrc::camera_is_pinhole(a.cam), a.p.gi_bounces <= 1u, fused, tuning.walk_from_root, vrc::LaneMap::tile8x8, 0u};
+    if (can_s4 && (tuning.lane_samples == 4u || (tuning.lane_samples == 0u && !caller_whole_spp))) v.map = vrc::LaneMap::samples4;
+    const bool s4 = v.map == vrc::LaneMap::samples4;
+    const uint32_t tw = s4 ? 4u : 8u;
     const uint32_t tiles_per_row = a.checker_wide ? (r->width + 15u) / 16u : (r->width + tw - 1u) / tw;
     const uint64_t items = (uint64_t)tiles_per_row * ((rows + tw - 1u) / tw) * 64ull;
     if (items > 0xfffffff0ull) return fail(VRC_ERR_INVALID, "vrc_render_frame: frame too large");
@@ -636,38 +639,39 @@ int render_impl(vrc_renderer* r, const vrc_camera* cam, const vrc_frame_params* 
     }
     a.fused_resolve = fused ? 1u : 0u;
     a.reuse_invariant = tuning.reuse_invariant ? 1u : 0u;
-    a.walk_from_root = tuning.walk_from_root ? 1u : 0u;
     a.tile_done = r->d_tile_done;
     a.resolve_dst = (uint32_t*)dst;
     // Quadrant walks (render_sync_body's QUAD; vrc_renderer_set_quad_walks, on by default): the pinhole kernels on the 8 x 8 map
     // when every work unit has a multiple of four samples (the walks of a pixel's sample-invariant rays are laid out four
     // abreast), without invariant-ray reuse (one walk per unit: nothing to lay out) and without the primary-hit capture (which
-    // records per-lane complexities); the tree must have 8 levels or more (a walk's final state waits in stack rows 3..7).
+    // records per-lane complexities); the tree must have 8 levels or more (a walk's final state waits in stack rows 3..7); and
+    // this build of the library must have them.
     // Decided BEFORE the occupancy and the unit policy, which follow the build that is launched (its builds sit at their own
     // occupancy); the one condition that needs the policy's result -- every unit a multiple of four samples -- is checked after
     // it, and a launch that fails it is planned again for the plain build.
-    const bool quad_candidate = vrc::quad_available() && tuning.quad_walks && a.lane_samples == 1u && a.p.use_samples && a.p.spp % 4u == 0u &&
-                                !a.reuse_invariant && !a.prim && !a.walk_from_root && !a.checker_wide && vrc::camera_is_pinhole(a.cam) && s->depth >= 8u;
+    const bool quad_candidate = vrc::quad_available() && tuning.quad_walks && !s4 && a.p.use_samples && a.p.spp % 4u == 0u &&
+                                !a.reuse_invariant && !a.prim && !v.from_root && !a.checker_wide && v.pinhole && s->depth >= 8u;
+    const uint32_t lds = vrc::frame_lds_bytes(s->depth);
+    const uint32_t fit = 163840u / lds;              // workgroups whose LDS fits a CU
+    const vrc::FrameKernel* kernel = nullptr;
     uint64_t want = 0, cap = 0;
-    auto plan = [&](bool quad) -> int {
+    auto plan = [&](vrc::LaneMap map) -> int {
         want = (items + VRC_RENDER_BLOCK - 1) / VRC_RENDER_BLOCK;
         a.sample_chunk = a.sample_chunk_tail = a.tail_tiles = 0;
-        uint32_t bpc = 0;
-        {
-            const uint32_t lds = 2u * s->depth * 1024u + 1536u + 128u + 544u + 32u + (quad ? vrc::quad_lds_bytes() : 0u);  // two stacks (primary path, secondary walks), tables, counters, camera paths
-            const uint32_t fit = 163840u / lds;
-            // which build of the kernel (waves per SIMD = workgroups per CU): by the kind of launch, or the caller's choice
-            const bool whole_spp = a.p.use_samples && a.p.spp > 1 && tuning.sample_chunk >= a.p.spp;
-            uint32_t waves = vrc::sync_waves_for(vrc::camera_is_pinhole(a.cam), a.p.gi_bounces <= 1, a.p.use_gi != 0, whole_spp,
-                                                 (uint64_t)a.n_items * a.p.spp, tuning.blocks_per_cu_set ? tuning.blocks_per_cu : 0u);
-            if (a.lane_samples == 4u) waves = vrc::sync_s4_waves(vrc::camera_is_pinhole(a.cam));
-            if (quad) waves = vrc::quad_waves();
-            if (waves > fit) waves = quad ? fit : vrc::sync_max_blocks_per_cu();   // deep trees: the stacks of 8 workgroups do not fit a CU's LDS
-            a.waves = waves;
-            bpc = waves;
-            if (tuning.blocks_per_cu_set && tuning.blocks_per_cu < bpc) bpc = tuning.blocks_per_cu;
-            if (bpc > fit) bpc = fit;
-        }
+        v.map = map;
+        // waves per SIMD: the kind's standard build, or for the lens one-bounce kernel on the 8 x 8 map 7 -- by the caller's
+        // blocks_per_cu >= 7, by default for whole-spp units (tools/sweep_waves.sh, profiles/r03/sweep_waves_below.txt: 7 by
+        // 1-1.5 % with frames in flight, 6 alone on the chip).  Deep trees: the stacks of that many workgroups do not fit a CU's
+        // LDS.  A kind without a build at these waves (the from-root builds) runs its standard build on this grid.
+        v.waves = 0u;                                // (no build has 0: the kind's standard build)
+        v.waves = vrc::frame_kernel(v)->v.waves;
+        const bool whole_spp = a.p.use_samples && a.p.spp > 1 && tuning.sample_chunk >= a.p.spp;
+        if (!v.pinhole && v.one_bounce && map == vrc::LaneMap::tile8x8 && (tuning.blocks_per_cu ? tuning.blocks_per_cu >= 7u : whole_spp))
+            v.waves = 7u;
+        if (v.waves > fit) v.waves = fit;
+        kernel = vrc::frame_kernel(v);
+        // workgroups per CU on the grid: the build's waves, or fewer if the caller asks for fewer
+        const uint32_t bpc = tuning.blocks_per_cu && tuning.blocks_per_cu < v.waves ? tuning.blocks_per_cu : v.waves;
         cap = (uint64_t)s->cu_count * bpc;
         if (a.p.use_samples && a.p.spp > 1) {
             // Units should be short against the launch (its end waits for the last unit of every wave, and the oldest
@@ -678,7 +682,7 @@ int render_impl(vrc_renderer* r, const vrc_camera* cam, const vrc_frame_params* 
             const uint64_t tiles = a.n_items / 64, waves = cap * (VRC_RENDER_BLOCK / 64);
             uint32_t c = tuning.sample_chunk ? tuning.sample_chunk : a.p.spp;
             if (c > a.p.spp) c = a.p.spp;
-            if (!tuning.sample_chunk && a.lane_samples == 4u) {
+            if (!tuning.sample_chunk && s4) {
                 // four samples abreast: a unit's samples come in fours (a tile has 16 pixels, so there are four times the units)
                 while (c % 8u == 0u && tiles * (a.p.spp / c) < 48 * waves) c /= 2;
             } else if (!tuning.sample_chunk) {
@@ -688,7 +692,7 @@ int render_impl(vrc_renderer* r, const vrc_camera* cam, const vrc_frame_params* 
             a.sample_chunk = c < a.p.spp ? c : 0;
             // shorter units for the tiles handed out last (about four per wave): halves the spread of the waves' end times
             uint64_t units = tiles * ((a.p.spp + c - 1) / c);
-            if (!tuning.sample_chunk && c >= 2 && tuning.tail_units_per_wave && (a.lane_samples == 1u || c % 8u == 0u)) {
+            if (!tuning.sample_chunk && c >= 2 && tuning.tail_units_per_wave && (!s4 || c % 8u == 0u)) {
                 const uint32_t ct = c / 2, cpt_tail = (a.p.spp + ct - 1) / ct;
                 uint64_t tt = (uint64_t)tuning.tail_units_per_wave * waves / cpt_tail;
                 if (tt > tiles) tt = tiles;
@@ -699,7 +703,7 @@ int render_impl(vrc_renderer* r, const vrc_camera* cam, const vrc_frame_params* 
 #ifdef VRC_EXP_UNITS   // experiment builds only (tools/build_variant.py): "head chunk,tail chunk,tail units per wave" from the environment
             if (const char* ev = getenv("VRC_EXP_UNITS")) {
                 unsigned ec = 0, ect = 0, etpw = 0;
-                if (sscanf(ev, "%u,%u,%u", &ec, &ect, &etpw) == 3 && ec >= 1 && ect >= 1 && a.lane_samples == 1u) {
+                if (sscanf(ev, "%u,%u,%u", &ec, &ect, &etpw) == 3 && ec >= 1 && ect >= 1 && !s4) {
                     c = ec > a.p.spp ? a.p.spp : ec;
                     a.sample_chunk = c < a.p.spp ? c : 0;
                     const uint32_t cpt_tail = (a.p.spp + ect - 1) / ect;
@@ -718,15 +722,15 @@ int render_impl(vrc_renderer* r, const vrc_camera* cam, const vrc_frame_params* 
         }
         return VRC_OK;
     };
-    if (int rc = plan(quad_candidate)) return rc;
+    if (int rc = plan(quad_candidate ? vrc::LaneMap::quad : v.map)) return rc;
     if (quad_candidate) {
         const uint32_t c_head = a.sample_chunk ? a.sample_chunk : a.p.spp, c_tail = a.sample_chunk_tail ? a.sample_chunk_tail : c_head;
-        if (c_head % 4u == 0u && c_tail % 4u == 0u) a.quad_walks = 1u;
-        else if (int rc = plan(false)) return rc;
+        if (c_head % 4u != 0u || c_tail % 4u != 0u)
+            if (int rc = plan(vrc::LaneMap::tile8x8)) return rc;
     }
-    const uint64_t cap_launch = cap;
-    const uint32_t grid = (uint32_t)(want < cap_launch ? want : cap_launch);
-    HIP_TRY(vrc::launch_render(a, grid, st, &r->last_kernel));
+    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    r->last_kernel = kernel->name;
+    HIP_TRY(vrc::launch_render(*kernel, a, grid, lds, st));
     if (queue_used >= 0) r->queue_zero[1 - queue_used] = true;           // zeroed by the launch that is now in the stream
     return VRC_OK;
 }

@@ -64,16 +64,6 @@ struct FrameArgs {
     // pinhole kernels (vrc_renderer_set_invariant_ray_reuse): walk a work unit's sample-invariant rays (the primary ray
     // and the shadow ray of its hit) once instead of once per sample; same image, fewer walks executed and counted
     uint32_t reuse_invariant;
-    // host only, measurement switch (vrc_renderer_set_walk_from_root): launch the pinhole one-bounce kernel's from-root build
-    uint32_t walk_from_root;
-    // host only: which build of the stage-synchronous kernel to launch, by waves per SIMD (6, 7 or 8; see sync_waves_for)
-    uint32_t waves;
-    // which lane <-> (pixel, sample) map of the stage-synchronous kernel: 1 = 8 x 8 pixels, 4 = 4 x 4 pixels x 4 samples abreast
-    // (render_sync_body's NS); n_items then counts 64 lanes per 4 x 4 tile
-    uint32_t lane_samples;
-    // pinhole kernels: the sample-invariant walks quadrant by quadrant, four samples abreast (render_sync_body's QUAD); the host
-    // sets it only for launches whose every unit has a multiple of four samples, without reuse and without the capture
-    uint32_t quad_walks;
     uint32_t* tile_done;
     uint32_t* resolve_dst;
     vrc_camera cam;
@@ -86,11 +76,15 @@ hipError_t launch_cast_ray_chains(const void* nodes, int depth, uint64_t n, cons
                                   const float* dir_b, float coef_b, vrc_hit* out_a, vrc_hit* out_b, uint32_t* not_executed, hipStream_t st);
 hipError_t launch_grid_cast(const uint8_t* cells, int X, int Y, int Z, uint64_t n, const float* org, const float* dir,
                             vrc_hit* out, hipStream_t st);
-uint32_t sync_max_blocks_per_cu();    // register-limited workgroups per CU of k_render_sync
-uint32_t quad_lds_bytes();            // LDS a workgroup of the quadrant-walk kernels needs on top
-uint32_t quad_waves();                // waves per SIMD the quadrant-walk kernels are built for
-bool quad_available();                // false in the variant builds that leave the quadrant-walk kernels out (launch_render would fall back)
-uint32_t sync_s4_waves(bool pinhole); // waves per SIMD the samples-abreast builds were compiled for
+
+// The lane <-> (pixel, sample) map of a frame-kernel build: 8 x 8 pixels; 4 x 4 pixels x 4 samples abreast (render_sync_body's NS;
+// FrameArgs::n_items then counts 64 lanes per 4 x 4 tile); or the pinhole kernels' sample-invariant walks quadrant by quadrant,
+// four samples abreast (render_sync_body's QUAD: for launches whose every unit has a multiple of four samples, without reuse and
+// without the capture).
+enum class LaneMap : uint32_t { tile8x8, samples4, quad };
+
+// One build of the frame kernel (vrc_kernels.hip, VRC_FRAME_KERNELS): camera kind, bounces, fused resolve, every ray from the root
+// (the measurement switch vrc_renderer_set_walk_from_root), lane map, and the waves per SIMD it is built for.
 // The stage-synchronous kernels are built for 6 waves per SIMD (80 VGPRs), the lens one-bounce kernel also for 7 (72).
 // Rounds 2 and 3 shipped 7- and 8-wave builds of the pinhole kernels too, picked by a table (profiles/r03/sweep_waves.txt:
 // the 8-wave build won C3 with frames in flight by 2 %).  With walks that start below the root -- fewer iterations, two
@@ -101,11 +95,26 @@ uint32_t sync_s4_waves(bool pinhole); // waves per SIMD the samples-abreast buil
 //   lens (DOF) + GI (C4), three frames in flight                6: 1.250   7: 1.232
 //   lens (DOF) + GI (C4), one at a time                         6: 1.372   7: 1.348                 (pitch 0: 0.889 / 0.899)
 //   short launch (C2: 1280 x 720, primary + shadow, 1 spp)      6: 0.073   7: 0.079   8: 0.087
-// so they are gone (and with them their register spills: the 6-wave pinhole kernel has one).  sync_waves_for: 6, the lens
-// kernel 7 with whole-spp units; a caller's vrc_renderer_set_tuning(blocks_per_cu) >= 7 selects the lens kernel's 7-wave build.
-uint32_t sync_waves_for(bool pinhole, bool one_bounce, bool use_gi, bool whole_spp_units, uint64_t pixel_samples, uint32_t requested);
-bool camera_is_pinhole(const vrc_camera& cam);   // the host's predicate for the pinhole kernels (see launch_render)
-hipError_t launch_render(const FrameArgs& a, uint32_t grid_blocks, hipStream_t st, const char** launched);
+// so they are gone (and with them their register spills: the 6-wave pinhole kernel has one).  The planner (render_impl) takes
+// each kind's standard build, the lens kernel's 7-wave build for whole-spp units; a caller's vrc_renderer_set_tuning(blocks_per_cu)
+// >= 7 selects it.
+struct FrameVariant {
+    bool pinhole, one_bounce, fused, from_root;
+    LaneMap map;
+    uint32_t waves;
+};
+struct FrameKernel {
+    void (*fn)(const FrameArgs);
+    const char* name;
+    FrameVariant v;
+};
+// the build of this kind at v.waves, else the kind's standard build; nullptr when this build of the library has none of the kind
+// (the variant builds have no quadrant-walk kernels)
+const FrameKernel* frame_kernel(const FrameVariant& v);
+bool quad_available();                           // whether the table has quadrant-walk rows (none in the variant builds)
+uint32_t frame_lds_bytes(uint32_t depth);        // dynamic LDS of a frame-kernel workgroup on a tree of `depth` levels
+bool camera_is_pinhole(const vrc_camera& cam);   // the host's predicate for the pinhole kernels
+hipError_t launch_render(const FrameKernel& k, const FrameArgs& a, uint32_t grid_blocks, uint32_t lds, hipStream_t st);
 hipError_t launch_resolve(const void* accum, void* image, uint32_t n, hipStream_t st);
 hipError_t launch_fill_u32(void* p, uint32_t value, uint64_t n, hipStream_t st);
 hipError_t launch_sanitize_nodes(void* nodes, uint64_t n, hipStream_t st);   // leaf_mask &= child_mask

@@ -30,6 +30,15 @@ using namespace vrc;
 // T1: batch per-ray operator
 // ---------------------------------------------------------------------------
 
+// the 48-byte HitPoint record of a hit as three 16-byte stores (the per-ray operators' output, the frame kernels' capture)
+__device__ __forceinline__ void store_hit(vrc_hit* out, const Hit& h)
+{
+    uint4* o = reinterpret_cast<uint4*>(out);
+    o[0] = make_uint4(f2u(h.px), f2u(h.py), f2u(h.pz), f2u(h.nx));
+    o[1] = make_uint4(f2u(h.ny), f2u(h.nz), f2u(h.u), f2u(h.v));
+    o[2] = make_uint4(h.hit, h.node, f2u(h.distance), h.complexity);
+}
+
 // LOD = false when the caller passes neither ray_size_coef nor ray_size_bias (both 0): the LOD test
 // of lsvo.hpp:82 cannot fire then and is compiled out (see ray_step).
 template <bool LOD>
@@ -52,11 +61,7 @@ __device__ __forceinline__ void cast_rays_body(const uint2* __restrict__ nodes, 
     ray_run<256, LOD ? 2 : 0>(r, active, nodes, stk, depth, coef, bias);
     Hit h;
     ray_finish(r, depth, ox, oy, oz, dx, dy, dz, h);
-    // 48-byte record as three 16-byte stores
-    uint4* o = reinterpret_cast<uint4*>(out + i);
-    o[0] = make_uint4(f2u(h.px), f2u(h.py), f2u(h.pz), f2u(h.nx));
-    o[1] = make_uint4(f2u(h.ny), f2u(h.nz), f2u(h.u), f2u(h.v));
-    o[2] = make_uint4(h.hit, h.node, f2u(h.distance), h.complexity);
+    store_hit(out + i, h);
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -95,10 +100,7 @@ __device__ __forceinline__ void cast_ray_chains_body(const uint2* __restrict__ n
     ray_run<256, 0>(r, active, nodes, stk, depth, 0.0f, 0.0f);
     Hit h;
     ray_finish(r, depth, ox, oy, oz, dx, dy, dz, h);
-    uint4* o = reinterpret_cast<uint4*>(out_a + i);
-    o[0] = make_uint4(f2u(h.px), f2u(h.py), f2u(h.pz), f2u(h.nx));
-    o[1] = make_uint4(f2u(h.ny), f2u(h.nz), f2u(h.u), f2u(h.v));
-    o[2] = make_uint4(h.hit, h.node, f2u(h.distance), h.complexity);
+    store_hit(out_a + i, h);
     ox = org_b[3 * i + 0]; oy = org_b[3 * i + 1]; oz = org_b[3 * i + 2];
     dx = dir_b[3 * i + 0]; dy = dir_b[3 * i + 1]; dz = dir_b[3 * i + 2];
     active = ray_setup(r, root, ox, oy, oz, dx, dy, dz);
@@ -111,10 +113,7 @@ __device__ __forceinline__ void cast_ray_chains_body(const uint2* __restrict__ n
     ray_run<256, LOD ? 1 : 0, true>(r, active, nodes, stk, depth, coef_b, 0.0f);
     Hit g;
     ray_finish(r, depth, ox, oy, oz, dx, dy, dz, g);
-    o = reinterpret_cast<uint4*>(out_b + i);
-    o[0] = make_uint4(f2u(g.px), f2u(g.py), f2u(g.pz), f2u(g.nx));
-    o[1] = make_uint4(f2u(g.ny), f2u(g.nz), f2u(g.u), f2u(g.v));
-    o[2] = make_uint4(g.hit, g.node, f2u(g.distance), g.complexity);
+    store_hit(out_b + i, g);
     if (not_executed) not_executed[i] = skipped;
 }
 
@@ -247,6 +246,9 @@ __device__ __forceinline__ bool pixel_selected(const vrc_frame_params& p, uint32
 
 // entries from one row of a stack to the next: the sync kernels keep two stacks with interleaved rows (render_sync_body)
 #define VRC_SYNC_ROW (2 * VRC_RENDER_BLOCK)
+// the rest of a frame kernel's LDS after its two stacks (frame_lds_bytes): the two 16 x 16 albedo tables, 4 waves x 4 counters,
+// the camera paths (VRC_CAMERA_PATH_BYTES), 4 waves' count of iterations not executed
+constexpr uint32_t VRC_TEX_BYTES = 1536u, VRC_WAVE_CTR_BYTES = 128u, VRC_NOT_EXECUTED_BYTES = 32u;
 
 #ifndef VRC_SYNC_S4_WAVES
 #define VRC_SYNC_S4_WAVES 6          // waves per SIMD the samples-abreast kernels are built for (pinhole / lens)
@@ -269,167 +271,160 @@ __device__ __forceinline__ uint32_t probe_wave_max(uint32_t v)
 #define VRC_PROBE_WALK(r, k)
 #endif
 
-// raycaster.hpp:169-207 getGlobalIllumination for one pixel-sample (+ the nested second bounce of the extension): GI
-// ray from the point (bp, bn), cast with LOD coefficient 0.5; if it hits, a shadow ray from the GI hit towards the
-// light.  Called by all lanes of a wave whose pixel-sample has a primary hit (`in exec`); the two walks are wave-wide.
-// `stk_hit` holds the path to the point's hit (the stack its walk left); the chain's walks use the other stack (its rows lie
-// VRC_RENDER_BLOCK entries further): the GI ray starts below the root on a copy of that path, the GI shadow ray on what the
-// GI walk left (vrc_device.h, ray_start_below).
-template <bool ONE_BOUNCE>   // true: gi_bounces == 1 is known (the reference's semantics), the chain is straight-line code
-__device__ __forceinline__ float gi_chain(const uint2* __restrict__ nodes, stack_t* const stk_hit, const uint32_t base_scale, const bool from_root,
-                                          const uint2 root, const int depth,
-                                          const float n_normalizer, const float lx, const float ly, const float lz,
-                                          const uint32_t gi_bounces_rt, const uint32_t seed, const uint32_t fr, const uint32_t pix,
-                                          float base_px, float base_py, float base_pz, float base_nx, float base_ny, float base_nz,
-                                          unsigned long long* ctr)
+// raycaster.hpp:169-207 getGlobalIllumination for one pixel-sample (+ the nested second bounce of the extension): GI ray from
+// the primary hit (b*: its point and normal), cast with LOD coefficient 0.5; if it hits, a shadow ray from the GI hit towards
+// the light.  ONE_BOUNCE: the reference's one level.  Otherwise the 2-bounce extension (the kernels built for it always run
+// exactly two levels: vrc_render_frame rejects gi_bounces > 2, the planner sends gi_bounces <= 1 to the one-bounce kernels):
+// level 1 the same from the GI hit with draws 4, 5, and gi = max(0, acc0 + dot_gi0 * max(0, acc1)).
+// Called by all lanes of a wave whose pixel-sample has a primary hit (`in exec`); the walks are wave-wide.  `stk_hit` holds the
+// path to the primary hit (the stack its walk left); the walks here use the other stack (its rows lie VRC_RENDER_BLOCK entries
+// further): the GI ray starts below the root on a copy of that path, the GI shadow ray on what the GI walk left (vrc_device.h,
+// ray_start_below); a level-1 GI ray starts at the root (the GI shadow walk has used the stack since its hit).
+template <bool ONE_BOUNCE>
+__device__ __forceinline__ float gi_term(const uint2* __restrict__ nodes, stack_t* const stk_hit, const uint32_t base_scale, const bool from_root,
+                                         const uint2 root, const int depth,
+                                         const float n_normalizer, const float lx, const float ly, const float lz,
+                                         const uint32_t seed, const uint32_t fr, const uint32_t pix,
+                                         float base_px, float base_py, float base_pz, float base_nx, float base_ny, float base_nz,
+                                         unsigned long long* ctr)
 {
-    const uint32_t gi_bounces = ONE_BOUNCE ? 1u : gi_bounces_rt;
-    stack_t* const stk = stk_hit + VRC_RENDER_BLOCK;
-    Ray r;
-    bool active;
-    float ox, oy, oz, dx, dy, dz;
-    float acc[2] = {0.0f, 0.0f}, dgi[2] = {0.0f, 0.0f};
-    uint32_t draw = 2u, level = 0u;
-    bool chain = true;
-    while (chain) {
-        ox = base_px + base_nx * n_normalizer;                           // :174
-        oy = base_py + base_ny * n_normalizer;
-        oz = base_pz + base_nz * n_normalizer;
-        const float c1 = get_rand(counter_rand(seed, fr, pix, draw), -1000.0f, 1000.0f);
-        const float c2 = get_rand(counter_rand(seed, fr, pix, draw + 1u), -1000.0f, 1000.0f);
-        draw += 2u;
-        float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-        if (base_nx != 0.0f)      { qy = c1; qz = c2; }
-        else if (base_ny != 0.0f) { qx = c1; qz = c2; }
-        else if (base_nz != 0.0f) { qx = c1; qy = c2; }
-        dx = (base_nx + qx) * n_normalizer;                              // :192
-        dy = (base_ny + qy) * n_normalizer;
-        dz = (base_nz + qz) * n_normalizer;
-        normalize3(dx, dy, dz);
-        const float dot_gi = dot3(dx, dy, dz, base_nx, base_ny, base_nz);   // :193
-        if (level == 0u) dgi[0] = dot_gi; else dgi[1] = dot_gi;
-        active = ray_setup(r, root, ox, oy, oz, dx, dy, dz);
-        if (level == 0u) {     // (a deeper level starts at the root: the GI shadow walk has used the stack since its hit)
+    if constexpr (ONE_BOUNCE) {   // the reference's loop over levels; with gi_bounces == 1 known it compiles to straight-line code
+        const uint32_t gi_bounces = 1u;
+        stack_t* const stk = stk_hit + VRC_RENDER_BLOCK;
+        Ray r;
+        bool active;
+        float ox, oy, oz, dx, dy, dz;
+        float acc[2] = {0.0f, 0.0f}, dgi[2] = {0.0f, 0.0f};
+        uint32_t draw = 2u, level = 0u;
+        bool chain = true;
+        while (chain) {
+            ox = base_px + base_nx * n_normalizer;                           // :174
+            oy = base_py + base_ny * n_normalizer;
+            oz = base_pz + base_nz * n_normalizer;
+            const float c1 = get_rand(counter_rand(seed, fr, pix, draw), -1000.0f, 1000.0f);
+            const float c2 = get_rand(counter_rand(seed, fr, pix, draw + 1u), -1000.0f, 1000.0f);
+            draw += 2u;
+            float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+            if (base_nx != 0.0f)      { qy = c1; qz = c2; }
+            else if (base_ny != 0.0f) { qx = c1; qz = c2; }
+            else if (base_nz != 0.0f) { qx = c1; qy = c2; }
+            dx = (base_nx + qx) * n_normalizer;                              // :192
+            dy = (base_ny + qy) * n_normalizer;
+            dz = (base_nz + qz) * n_normalizer;
+            normalize3(dx, dy, dz);
+            const float dot_gi = dot3(dx, dy, dz, base_nx, base_ny, base_nz);   // :193
+            if (level == 0u) dgi[0] = dot_gi; else dgi[1] = dot_gi;
+            active = ray_setup(r, root, ox, oy, oz, dx, dy, dz);
+            if (level == 0u) {     // (a deeper level starts at the root: the GI shadow walk has used the stack since its hit)
+                if (!from_root) copy_stack<VRC_SYNC_ROW>(stk, stk_hit, depth);
+                ray_start_below(r, (from_root ? 22u : start_scale_next_to_lod(ox, oy, oz, base_px, base_py, base_pz, base_scale, dx, dy, dz)), ox, oy, oz);
+            }
+            ray_run_total_below<VRC_SYNC_ROW, 1>(r, active, nodes, stk, depth, 0.5f, 0.0f, ctr);   // :194
+            Hit g;
+            ray_finish(r, depth, ox, oy, oz, dx, dy, dz, g);
+            chain = false;
+            if (g.hit) {                                                     // :195-203
+                ox = g.px + g.nx * n_normalizer;
+                oy = g.py + g.ny * n_normalizer;
+                oz = g.pz + g.nz * n_normalizer;
+                dx = lx - ox; dy = ly - oy; dz = lz - oz;
+                normalize3(dx, dy, dz);
+                const float dotl = dot3(g.nx, g.ny, g.nz, dx, dy, dz);         // :200
+                const float contrib = 1000000.0f * smin(0.5f, smax(0.0f, dotl) * dot_gi);   // :201
+                active = ray_setup(r, root, ox, oy, oz, dx, dy, dz);
+                ray_start_below(r, (from_root ? 22u : start_scale_next_to_lod(ox, oy, oz, g.px, g.py, g.pz, (g.hit >> 16) & 0xffu, dx, dy, dz)), ox, oy, oz);
+                ray_run_total_below<VRC_SYNC_ROW, 1>(r, active, nodes, stk, depth, 0.5f, 0.0f, ctr);   // :198
+                if (!r.kind) { if (level == 0u) acc[0] += contrib; else acc[1] += contrib; }
+                if (level + 1u < gi_bounces) {
+                    base_px = g.px; base_py = g.py; base_pz = g.pz;
+                    base_nx = g.nx; base_ny = g.ny; base_nz = g.nz;
+                    level += 1u;
+                    chain = true;
+                }
+            }
+        }
+        // :206, innermost level first: gi = max(0, acc0 [+ dot_gi0 * max(0, acc1)])
+        if (level == 0u) return smax(0.0f, acc[0] / 1.0f);
+        acc[0] += dgi[0] * smax(0.0f, acc[1] / 1.0f);
+        return smax(0.0f, acc[0] / 1.0f);
+    } else {   // the 2-bounce extension: both levels as straight-line code
+        float acc0 = 0.0f, acc1 = 0.0f, dgi0 = 0.0f;
+        stack_t* const stk = stk_hit + VRC_RENDER_BLOCK;
+        Ray r;
+        bool active;
+        float ox, oy, oz, dx, dy, dz;
+        {   // ---- level 0
+            ox = base_px + base_nx * n_normalizer;                                 // :174
+            oy = base_py + base_ny * n_normalizer;
+            oz = base_pz + base_nz * n_normalizer;
+            const float c1 = get_rand(counter_rand(seed, fr, pix, 2u), -1000.0f, 1000.0f);
+            const float c2 = get_rand(counter_rand(seed, fr, pix, 3u), -1000.0f, 1000.0f);
+            float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+            if (base_nx != 0.0f)      { qy = c1; qz = c2; }
+            else if (base_ny != 0.0f) { qx = c1; qz = c2; }
+            else if (base_nz != 0.0f) { qx = c1; qy = c2; }
+            dx = (base_nx + qx) * n_normalizer;                                 // :192
+            dy = (base_ny + qy) * n_normalizer;
+            dz = (base_nz + qz) * n_normalizer;
+            normalize3(dx, dy, dz);
+            dgi0 = dot3(dx, dy, dz, base_nx, base_ny, base_nz);                        // :193
+            active = ray_setup(r, root, ox, oy, oz, dx, dy, dz);
             if (!from_root) copy_stack<VRC_SYNC_ROW>(stk, stk_hit, depth);
             ray_start_below(r, (from_root ? 22u : start_scale_next_to_lod(ox, oy, oz, base_px, base_py, base_pz, base_scale, dx, dy, dz)), ox, oy, oz);
+            ray_run_total_below<VRC_SYNC_ROW, 1>(r, active, nodes, stk, depth, 0.5f, 0.0f, ctr);   // :194
         }
-        ray_run_total_below<VRC_SYNC_ROW, 1>(r, active, nodes, stk, depth, 0.5f, 0.0f, ctr);   // :194
         Hit g;
         ray_finish(r, depth, ox, oy, oz, dx, dy, dz, g);
-        chain = false;
-        if (g.hit) {                                                     // :195-203
+        if (g.hit) {                                                         // :195-203
             ox = g.px + g.nx * n_normalizer;
             oy = g.py + g.ny * n_normalizer;
             oz = g.pz + g.nz * n_normalizer;
             dx = lx - ox; dy = ly - oy; dz = lz - oz;
             normalize3(dx, dy, dz);
-            const float dotl = dot3(g.nx, g.ny, g.nz, dx, dy, dz);         // :200
-            const float contrib = 1000000.0f * smin(0.5f, smax(0.0f, dotl) * dot_gi);   // :201
+            const float dotl = dot3(g.nx, g.ny, g.nz, dx, dy, dz);             // :200
+            const float contrib = 1000000.0f * smin(0.5f, smax(0.0f, dotl) * dgi0);   // :201
             active = ray_setup(r, root, ox, oy, oz, dx, dy, dz);
             ray_start_below(r, (from_root ? 22u : start_scale_next_to_lod(ox, oy, oz, g.px, g.py, g.pz, (g.hit >> 16) & 0xffu, dx, dy, dz)), ox, oy, oz);
             ray_run_total_below<VRC_SYNC_ROW, 1>(r, active, nodes, stk, depth, 0.5f, 0.0f, ctr);   // :198
-            if (!r.kind) { if (level == 0u) acc[0] += contrib; else acc[1] += contrib; }
-            if (level + 1u < gi_bounces) {
-                base_px = g.px; base_py = g.py; base_pz = g.pz;
-                base_nx = g.nx; base_ny = g.ny; base_nz = g.nz;
-                level += 1u;
-                chain = true;
-            }
-        }
-    }
-    // :206, innermost level first: gi = max(0, acc0 [+ dot_gi0 * max(0, acc1)])
-    if (level == 0u) return smax(0.0f, acc[0] / 1.0f);
-    acc[0] += dgi[0] * smax(0.0f, acc[1] / 1.0f);
-    return smax(0.0f, acc[0] / 1.0f);
-}
-
-// The 2-bounce extension as straight-line code (the kernels built for it always run exactly two levels: vrc_render_frame
-// rejects gi_bounces > 2, launch_render sends gi_bounces <= 1 to the one-bounce kernels).  Same operations in the same
-// order as gi_chain<false> with gi_bounces = 2 -- level 0 from the primary hit with draws 2, 3, level 1 from the GI hit with
-// draws 4, 5, gi = max(0, acc0 + dot_gi0 * max(0, acc1)) -- without the loop-carried level / draw / base state.
-__device__ __forceinline__ float gi_two_levels(const uint2* __restrict__ nodes, stack_t* const stk_hit, const uint32_t base_scale, const bool from_root,
-                                               const uint2 root, const int depth,
-                                               const float n_normalizer, const float lx, const float ly, const float lz,
-                                               const uint32_t seed, const uint32_t fr, const uint32_t pix,
-                                               const float b0px, const float b0py, const float b0pz,
-                                               const float b0nx, const float b0ny, const float b0nz, unsigned long long* ctr)
-{
-    float acc0 = 0.0f, acc1 = 0.0f, dgi0 = 0.0f;
-    stack_t* const stk = stk_hit + VRC_RENDER_BLOCK;
-    Ray r;
-    bool active;
-    float ox, oy, oz, dx, dy, dz;
-    {   // ---- level 0
-        ox = b0px + b0nx * n_normalizer;                                 // :174
-        oy = b0py + b0ny * n_normalizer;
-        oz = b0pz + b0nz * n_normalizer;
-        const float c1 = get_rand(counter_rand(seed, fr, pix, 2u), -1000.0f, 1000.0f);
-        const float c2 = get_rand(counter_rand(seed, fr, pix, 3u), -1000.0f, 1000.0f);
-        float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-        if (b0nx != 0.0f)      { qy = c1; qz = c2; }
-        else if (b0ny != 0.0f) { qx = c1; qz = c2; }
-        else if (b0nz != 0.0f) { qx = c1; qy = c2; }
-        dx = (b0nx + qx) * n_normalizer;                                 // :192
-        dy = (b0ny + qy) * n_normalizer;
-        dz = (b0nz + qz) * n_normalizer;
-        normalize3(dx, dy, dz);
-        dgi0 = dot3(dx, dy, dz, b0nx, b0ny, b0nz);                        // :193
-        active = ray_setup(r, root, ox, oy, oz, dx, dy, dz);
-        if (!from_root) copy_stack<VRC_SYNC_ROW>(stk, stk_hit, depth);
-        ray_start_below(r, (from_root ? 22u : start_scale_next_to_lod(ox, oy, oz, b0px, b0py, b0pz, base_scale, dx, dy, dz)), ox, oy, oz);
-        ray_run_total_below<VRC_SYNC_ROW, 1>(r, active, nodes, stk, depth, 0.5f, 0.0f, ctr);   // :194
-    }
-    Hit g;
-    ray_finish(r, depth, ox, oy, oz, dx, dy, dz, g);
-    if (g.hit) {                                                         // :195-203
-        ox = g.px + g.nx * n_normalizer;
-        oy = g.py + g.ny * n_normalizer;
-        oz = g.pz + g.nz * n_normalizer;
-        dx = lx - ox; dy = ly - oy; dz = lz - oz;
-        normalize3(dx, dy, dz);
-        const float dotl = dot3(g.nx, g.ny, g.nz, dx, dy, dz);             // :200
-        const float contrib = 1000000.0f * smin(0.5f, smax(0.0f, dotl) * dgi0);   // :201
-        active = ray_setup(r, root, ox, oy, oz, dx, dy, dz);
-        ray_start_below(r, (from_root ? 22u : start_scale_next_to_lod(ox, oy, oz, g.px, g.py, g.pz, (g.hit >> 16) & 0xffu, dx, dy, dz)), ox, oy, oz);
-        ray_run_total_below<VRC_SYNC_ROW, 1>(r, active, nodes, stk, depth, 0.5f, 0.0f, ctr);   // :198
-        if (!r.kind) acc0 += contrib;
-        // ---- level 1: the same from the GI hit
-        const float b1nx = g.nx, b1ny = g.ny, b1nz = g.nz;
-        ox = g.px + b1nx * n_normalizer;
-        oy = g.py + b1ny * n_normalizer;
-        oz = g.pz + b1nz * n_normalizer;
-        const float c1 = get_rand(counter_rand(seed, fr, pix, 4u), -1000.0f, 1000.0f);
-        const float c2 = get_rand(counter_rand(seed, fr, pix, 5u), -1000.0f, 1000.0f);
-        float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-        if (b1nx != 0.0f)      { qy = c1; qz = c2; }
-        else if (b1ny != 0.0f) { qx = c1; qz = c2; }
-        else if (b1nz != 0.0f) { qx = c1; qy = c2; }
-        dx = (b1nx + qx) * n_normalizer;
-        dy = (b1ny + qy) * n_normalizer;
-        dz = (b1nz + qz) * n_normalizer;
-        normalize3(dx, dy, dz);
-        const float dgi1 = dot3(dx, dy, dz, b1nx, b1ny, b1nz);
-        active = ray_setup(r, root, ox, oy, oz, dx, dy, dz);
-        ray_run_total<VRC_SYNC_ROW, 1>(r, active, nodes, stk, depth, 0.5f, 0.0f, ctr);
-        Hit g1;
-        ray_finish(r, depth, ox, oy, oz, dx, dy, dz, g1);
-        if (g1.hit) {
-            ox = g1.px + g1.nx * n_normalizer;
-            oy = g1.py + g1.ny * n_normalizer;
-            oz = g1.pz + g1.nz * n_normalizer;
-            dx = lx - ox; dy = ly - oy; dz = lz - oz;
+            if (!r.kind) acc0 += contrib;
+            // ---- level 1: the same from the GI hit
+            const float b1nx = g.nx, b1ny = g.ny, b1nz = g.nz;
+            ox = g.px + b1nx * n_normalizer;
+            oy = g.py + b1ny * n_normalizer;
+            oz = g.pz + b1nz * n_normalizer;
+            const float c1 = get_rand(counter_rand(seed, fr, pix, 4u), -1000.0f, 1000.0f);
+            const float c2 = get_rand(counter_rand(seed, fr, pix, 5u), -1000.0f, 1000.0f);
+            float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+            if (b1nx != 0.0f)      { qy = c1; qz = c2; }
+            else if (b1ny != 0.0f) { qx = c1; qz = c2; }
+            else if (b1nz != 0.0f) { qx = c1; qy = c2; }
+            dx = (b1nx + qx) * n_normalizer;
+            dy = (b1ny + qy) * n_normalizer;
+            dz = (b1nz + qz) * n_normalizer;
             normalize3(dx, dy, dz);
-            const float dotl1 = dot3(g1.nx, g1.ny, g1.nz, dx, dy, dz);
-            const float contrib1 = 1000000.0f * smin(0.5f, smax(0.0f, dotl1) * dgi1);
+            const float dgi1 = dot3(dx, dy, dz, b1nx, b1ny, b1nz);
             active = ray_setup(r, root, ox, oy, oz, dx, dy, dz);
-            ray_start_below(r, (from_root ? 22u : start_scale_next_to_lod(ox, oy, oz, g1.px, g1.py, g1.pz, (g1.hit >> 16) & 0xffu, dx, dy, dz)), ox, oy, oz);
-            ray_run_total_below<VRC_SYNC_ROW, 1>(r, active, nodes, stk, depth, 0.5f, 0.0f, ctr);
-            if (!r.kind) acc1 += contrib1;
+            ray_run_total<VRC_SYNC_ROW, 1>(r, active, nodes, stk, depth, 0.5f, 0.0f, ctr);
+            Hit g1;
+            ray_finish(r, depth, ox, oy, oz, dx, dy, dz, g1);
+            if (g1.hit) {
+                ox = g1.px + g1.nx * n_normalizer;
+                oy = g1.py + g1.ny * n_normalizer;
+                oz = g1.pz + g1.nz * n_normalizer;
+                dx = lx - ox; dy = ly - oy; dz = lz - oz;
+                normalize3(dx, dy, dz);
+                const float dotl1 = dot3(g1.nx, g1.ny, g1.nz, dx, dy, dz);
+                const float contrib1 = 1000000.0f * smin(0.5f, smax(0.0f, dotl1) * dgi1);
+                active = ray_setup(r, root, ox, oy, oz, dx, dy, dz);
+                ray_start_below(r, (from_root ? 22u : start_scale_next_to_lod(ox, oy, oz, g1.px, g1.py, g1.pz, (g1.hit >> 16) & 0xffu, dx, dy, dz)), ox, oy, oz);
+                ray_run_total_below<VRC_SYNC_ROW, 1>(r, active, nodes, stk, depth, 0.5f, 0.0f, ctr);
+                if (!r.kind) acc1 += contrib1;
+            }
+            acc0 += dgi0 * smax(0.0f, acc1 / 1.0f);                            // :206, innermost level first
+            return smax(0.0f, acc0 / 1.0f);
         }
-        acc0 += dgi0 * smax(0.0f, acc1 / 1.0f);                            // :206, innermost level first
         return smax(0.0f, acc0 / 1.0f);
     }
-    return smax(0.0f, acc0 / 1.0f);
 }
 
 // ---- Quadrant walks (round 5): the pinhole kernel's sample-invariant walks in a 4 x 4 pixels x 4 samples lane map -----------
@@ -444,7 +439,6 @@ __device__ __forceinline__ float gi_two_levels(const uint2* __restrict__ nodes, 
 // ds_bpermute (no VALU, no LDS storage); the four lanes of a pixel walk in step on the pixel's OWN stack column (identical
 // pushes to one address), so the path to the primary hit ends up where the GI stages, which keep the 8 x 8 map, expect it.
 
-constexpr uint32_t VRC_QUAD_LDS_BYTES = 0u;                           // (a walk's final state waits in the secondary stack: depth >= 8 rows)
 // A walk's pixels: a block of the 8 x 8 tile -- 4 x 4 (each pixel in 4 lanes), 4 x 2 (8 lanes) or 2 x 2 (16 lanes): the more walks a
 // pixel's ray needs (samples per unit, x shadow samples), the fewer distinct rays share a walk (C3 pose, VALU instructions per
 // tile-sample, primary + shadow: 8 x 8 x 1 3518, 4 x 4 x 4 2926, 2 x 2 x 16 2503; tests/tools/path_schedule.py --quad).
@@ -517,6 +511,60 @@ __device__ __forceinline__ uint32_t albedo_of(const uint8_t* tex, const Hit& h)
     return (uint32_t)img[idx * 3] | ((uint32_t)img[idx * 3 + 1] << 8) | ((uint32_t)img[idx * 3 + 2] << 16);
 }
 
+// the camera block: ONE scalar load of 16 dwords from the kernel-argument segment, where it is needed (the frame kernels are at
+// their register budget)
+typedef uint32_t cam16_t __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ cam16_t load_camera(const volatile FrameArgs* ka)
+{
+    cam16_t cw;
+    asm volatile("s_load_dwordx16 %0, %1, %2\n s_waitcnt lgkmcnt(0)" : "=s"(cw) : "s"((const void*)ka), "i"((int)__builtin_offsetof(FrameArgs, cam)));
+    return cw;
+}
+
+// R0: main.cpp:133,145-149; camera_controller.hpp:34-54 with rand_vec = +-0 (see PINHOLE at render_sync_body): a pinhole camera's
+// ray of a pixel, from the camera block.  (The general lane map computes the lens form in place, for both cameras: behind a call
+// the compiler orders the lens products differently.)
+__device__ __forceinline__ void pinhole_camera_ray(const cam16_t cw, const uint32_t W, const uint32_t H, const uint32_t px_x, const uint32_t px_y,
+                                                   const float inv_size, float& ox, float& oy, float& oz, float& dx, float& dy, float& dz)
+{
+    const float cpos0 = u2f(cw[0]), cpos1 = u2f(cw[1]), cpos2 = u2f(cw[2]);
+    const float cfov = u2f(cw[12]), cfocal = u2f(cw[14]);
+    const float aspect_ratio = (float)W / (float)H;
+    const float lens_x = (float)px_x / (float)H - aspect_ratio * 0.5f;
+    const float lens_y = (float)px_y / (float)H - 0.5f;
+    float sx = lens_x, sy = lens_y, sz = cfov;
+    normalize3(sx, sy, sz);
+    float vx = sx * cfocal, vy = sy * cfocal, vz = sz * cfocal;
+    const float m[9] = {u2f(cw[3]), u2f(cw[4]), u2f(cw[5]), u2f(cw[6]), u2f(cw[7]), u2f(cw[8]), u2f(cw[9]), u2f(cw[10]), u2f(cw[11])};
+    normalize3(vx, vy, vz);
+    dx = (m[0] * vx + m[1] * vy) + m[2] * vz;
+    dy = (m[3] * vx + m[4] * vy) + m[5] * vz;
+    dz = (m[6] * vx + m[7] * vy) + m[8] * vz;
+    ox = (cpos0 + 0.0f) * inv_size + 1.0f;
+    oy = (cpos1 + 0.0f) * inv_size + 1.0f;
+    oz = (cpos2 + 0.0f) * inv_size + 1.0f;
+}
+
+// raycaster.hpp:139,150-158: the shadow ray of a primary hit towards the light, and the light it receives if not occluded (:156)
+__device__ __forceinline__ float shadow_ray(const Hit& h, const float inv_size, const float lx, const float ly, const float lz,
+                                            float& ox, float& oy, float& oz, float& dx, float& dy, float& dz)
+{
+    ox = h.px + h.nx * inv_size * 0.001f;
+    oy = h.py + h.ny * inv_size * 0.001f;
+    oz = h.pz + h.nz * inv_size * 0.001f;
+    dx = lx - ox; dy = ly - oy; dz = lz - oz;
+    normalize3(dx, dy, dz);
+    return smax(0.0f, dot3(dx, dy, dz, h.nx, h.ny, h.nz));
+}
+
+// two 64-bit adds per pixel: (r, g) and (b, count) as pairs of u32 -- a sum never carries out of its low word (sums < 2^32, as
+// the accumulator format requires), so each half adds independently
+__device__ __forceinline__ void add_sums(unsigned long long* ap, const uint32_t r, const uint32_t g, const uint32_t b, const uint32_t count)
+{
+    atomicAdd(ap + 0, (unsigned long long)r | ((unsigned long long)g << 32));
+    atomicAdd(ap + 1, (unsigned long long)b | ((unsigned long long)count << 32));
+}
+
 // PINHOLE: the camera has aperture exactly +0 (the reference's default) -- decided by the host, see vrc_render_frame.
 // Then a pixel's camera ray is the same for every sample, and so are its primary hit, albedo and shadow ray(s): a work
 // unit sets them up ONCE and walks them once per sample of the unit (every ray the reference casts is still walked and
@@ -531,9 +579,11 @@ __device__ __forceinline__ uint32_t albedo_of(const uint8_t* tex, const Hit& h)
 // Every ray the reference casts is still walked and counted, each by its own lane.
 // QUAD (pinhole, 8 x 8 map): the sample-invariant walks run quadrant by quadrant, four samples abreast (see quad_gather above);
 // for units whose sample count is a multiple of four, without invariant-ray reuse and without the primary-hit capture.
-template <bool PINHOLE, bool ONE_BOUNCE, bool FUSED, bool FROM_ROOT = false, uint32_t NS = 1u, bool QUAD = false>
+template <bool PINHOLE, bool ONE_BOUNCE, bool FUSED, bool FROM_ROOT, LaneMap MAP>
 __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
 {
+    constexpr uint32_t NS = MAP == LaneMap::samples4 ? 4u : 1u;
+    constexpr bool QUAD = MAP == LaneMap::quad;
     static_assert(!QUAD || (PINHOLE && !FROM_ROOT && NS == 1u), "quadrant walks exist for the pinhole kernels on the 8 x 8 map");
     // [depth][2][256] two stacks, their rows interleaved | 1536 B textures | 4 waves x 4 counters | camera paths (8 x 16 entries + 8) |
     // 4 waves' count of iterations not executed
@@ -542,11 +592,11 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
     // (secondary rays use the other stack, stk + VRC_RENDER_BLOCK: a copy of that path, then their own)
     uint8_t* tex = reinterpret_cast<uint8_t*>(lds_dyn + 2u * a.depth * VRC_RENDER_BLOCK);
     const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t i = threadIdx.x; i < 1536u / 4u; i += VRC_RENDER_BLOCK)
+    for (uint32_t i = threadIdx.x; i < VRC_TEX_BYTES / 4u; i += VRC_RENDER_BLOCK)
         reinterpret_cast<uint32_t*>(tex)[i] = reinterpret_cast<const uint32_t*>(a.tex)[i];
     // this wave's {loop iterations, rays, primary hits, pixel-samples}: booked per walk / per unit by one lane with
     // no-return LDS adds, so that no per-lane counter is live across the walks (the kernel is at its register budget)
-    unsigned long long* const ctr = reinterpret_cast<unsigned long long*>(tex + 1536) + 4u * (threadIdx.x >> 6);
+    unsigned long long* const ctr = reinterpret_cast<unsigned long long*>(tex + VRC_TEX_BYTES) + 4u * (threadIdx.x >> 6);
     if (lane < 4u) ctr[lane] = 0ull;
     if (lane == 4u) ctr[VRC_CTR_NOT_EXECUTED] = 0ull;
     const uint2* __restrict__ nodes = a.nodes;
@@ -554,7 +604,7 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
     // the paths from the root to the camera's cell (vrc_device.h, camera_path): camera rays start at their ends.  One per
     // combination of direction signs (they differ only for a pinhole camera on the cube's centre planes -- the reference's
     // default pose; with a lens the lens point decides, and a camera on a centre plane starts its rays at the root)
-    stack_t* const cam_path = reinterpret_cast<stack_t*>(tex + 1536 + 128);
+    stack_t* const cam_path = reinterpret_cast<stack_t*>(tex + VRC_TEX_BYTES + VRC_WAVE_CTR_BYTES);
     if (threadIdx.x < 8u) {
         const float isz = 1.0f / (float)(1u << a.depth);
         cam_path[threadIdx.x * 16u + 15u] = camera_path(nodes, depth, (a.cam.position[0] + 0.0f) * isz + 1.0f, (a.cam.position[1] + 0.0f) * isz + 1.0f,
@@ -578,7 +628,6 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
     const float n_normalizer = inv_size * 0.0078125f * 2.0f;              // raycaster.hpp:171-172
     const float lx = a.p.light_position[0], ly = a.p.light_position[1], lz = a.p.light_position[2];
     const uint32_t shadow_samples = a.p.shadow_samples ? a.p.shadow_samples : (a.p.use_samples ? 4u : 1u);
-    const uint32_t gi_bounces = a.p.gi_bounces ? a.p.gi_bounces : 1u;
     const uint32_t spp = a.p.spp ? a.p.spp : 1u;
     // Checkerboard frames (main.cpp:137,143: every other pixel of each swarm area) use tiles of 16 x 8 pixels, of
     // which a lane takes the selected pixel of its pair, so that all 64 lanes of a wave have work
@@ -589,7 +638,7 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
     const uint32_t tiles_per_row = checker ? (W + 15u) / 16u : (W + TW - 1u) / TW;
     const uint32_t n_tiles = a.n_items >> 6;
     const bool sharded = a.p.row_block && a.p.shard_count > 1u;
-    constexpr bool pinhole = PINHOLE;     // see launch_render for the host's predicate
+    constexpr bool pinhole = PINHOLE;     // see camera_is_pinhole for the host's predicate
     // (arguments used once per launch or per work unit are read from the kernel-argument segment where they are needed
     // rather than held in SGPRs throughout: the kernel is at its register budget)
     const volatile FrameArgs* ka = (const volatile FrameArgs*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -691,12 +740,8 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
                 // ---- the same stages with the walks laid out quadrant by quadrant (the host guarantees n_samples % 4 == 0,
                 // no reuse, no capture).  8 x 8 map: generate the pixel's camera ray, once
                 stack_t* const stk_wave = stk - lane;                              // column of this wave's lane 0
-                // the camera block: ONE scalar load of 16 dwords from the kernel-argument segment, live in this prologue only
-                typedef uint32_t cam16_t __attribute__((ext_vector_type(16)));
-                cam16_t cw;
-                asm volatile("s_load_dwordx16 %0, %1, %2\n s_waitcnt lgkmcnt(0)" : "=s"(cw) : "s"((const void*)ka), "i"((int)__builtin_offsetof(FrameArgs, cam)));
-                const float cpos0 = u2f(cw[0]), cpos1 = u2f(cw[1]), cpos2 = u2f(cw[2]);
-                const float cfov = u2f(cw[12]), cfocal = u2f(cw[14]);
+                const cam16_t cw = load_camera(ka);
+                const float cpos0 = u2f(cw[0]), cpos1 = u2f(cw[1]), cpos2 = u2f(cw[2]);   // (again after the walks)
                 // (what a pixel's walks leave for the 8 x 8 map waits in the pixel's column of the SECONDARY stack: rows 3..7 after
                 // the primary walks, which do not touch that stack; row 0 after the shadow walks of its quadrant, which are done with it)
                 // lanes per pixel in the primary walks (the unit's samples) and in the shadow walks (x shadow samples): 4, 8 or 16
@@ -708,21 +753,7 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
                 r0.tcx = r0.tcy = r0.tcz = r0.tox = r0.toy = r0.toz = 0.0f; r0.px = r0.py = r0.pz = 1.0f; r0.t_min = r0.t_max = 0.0f;
                 r0.scale = SVO_MAX - 1; r0.child_offset = 0u; r0.mirror = 0u;
                 if (valid) {
-                    // R0: main.cpp:133,145-149; camera_controller.hpp:34-54 with rand_vec = +-0 (see PINHOLE above)
-                    const float aspect_ratio = (float)W / (float)H;
-                    const float lens_x = (float)px_x / (float)H - aspect_ratio * 0.5f;
-                    const float lens_y = (float)px_y / (float)H - 0.5f;
-                    float sx = lens_x, sy = lens_y, sz = cfov;
-                    normalize3(sx, sy, sz);
-                    float vx = sx * cfocal, vy = sy * cfocal, vz = sz * cfocal;
-                    const float m[9] = {u2f(cw[3]), u2f(cw[4]), u2f(cw[5]), u2f(cw[6]), u2f(cw[7]), u2f(cw[8]), u2f(cw[9]), u2f(cw[10]), u2f(cw[11])};
-                    normalize3(vx, vy, vz);
-                    dx = (m[0] * vx + m[1] * vy) + m[2] * vz;
-                    dy = (m[3] * vx + m[4] * vy) + m[5] * vz;
-                    dz = (m[6] * vx + m[7] * vy) + m[8] * vz;
-                    ox = (cpos0 + 0.0f) * inv_size + 1.0f;
-                    oy = (cpos1 + 0.0f) * inv_size + 1.0f;
-                    oz = (cpos2 + 0.0f) * inv_size + 1.0f;
+                    pinhole_camera_ray(cw, W, H, px_x, px_y, inv_size, ox, oy, oz, dx, dy, dz);
                     active = ray_setup(r0, root, ox, oy, oz, dx, dy, dz);
                     const stack_t* const my_cam_path = cam_path + (r0.mirror ^ 7u) * 16u;
                     ray_start_at_camera(r0, cam_scale < 22u ? my_cam_path[15] : 22u, ox, oy, oz);
@@ -774,13 +805,8 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
                         hit = true;
                         albedo = albedo_of(tex, h) | (h.hit >> 16 << 24);               // raycaster.hpp:141-145
                         hpx = h.px; hpy = h.py; hpz = h.pz; hnx = h.nx; hny = h.ny; hnz = h.nz;
-                        // raycaster.hpp:139,150-158 shadow ray(s): the reference re-casts the identical ray
-                        ox = h.px + h.nx * inv_size * 0.001f;
-                        oy = h.py + h.ny * inv_size * 0.001f;
-                        oz = h.pz + h.nz * inv_size * 0.001f;
-                        dx = lx - ox; dy = ly - oy; dz = lz - oz;
-                        normalize3(dx, dy, dz);
-                        light_intensity = smax(0.0f, dot3(dx, dy, dz, h.nx, h.ny, h.nz));       // :156 (taken back below if occluded)
+                        // shadow ray(s): the reference re-casts the identical ray; the light is taken back below if occluded
+                        light_intensity = shadow_ray(h, inv_size, lx, ly, lz, ox, oy, oz, dx, dy, dz);
                         active = ray_setup(r0, root, ox, oy, oz, dx, dy, dz);
                         ray_start_below(r0, start_scale_next_to(ox, oy, oz, h.px, h.py, h.pz, h.hit >> 16), ox, oy, oz);
                     }
@@ -804,24 +830,8 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
                 if (hit && stk[VRC_RENDER_BLOCK]) light_intensity = 0.0f;                // :155-157
             } else
             if (valid) {
-                typedef uint32_t cam16_t __attribute__((ext_vector_type(16)));      // (the camera block: see the quadrant-walk prologue)
-                cam16_t cw;
-                asm volatile("s_load_dwordx16 %0, %1, %2\n s_waitcnt lgkmcnt(0)" : "=s"(cw) : "s"((const void*)ka), "i"((int)__builtin_offsetof(FrameArgs, cam)));
-                // R0: main.cpp:133,145-149; camera_controller.hpp:34-54 with rand_vec = +-0 (see PINHOLE above)
-                const float aspect_ratio = (float)W / (float)H;
-                const float lens_x = (float)px_x / (float)H - aspect_ratio * 0.5f;
-                const float lens_y = (float)px_y / (float)H - 0.5f;
-                float sx = lens_x, sy = lens_y, sz = u2f(cw[12]);
-                normalize3(sx, sy, sz);
-                float vx = sx * u2f(cw[14]), vy = sy * u2f(cw[14]), vz = sz * u2f(cw[14]);
-                const float m[9] = {u2f(cw[3]), u2f(cw[4]), u2f(cw[5]), u2f(cw[6]), u2f(cw[7]), u2f(cw[8]), u2f(cw[9]), u2f(cw[10]), u2f(cw[11])};
-                normalize3(vx, vy, vz);
-                float dx = (m[0] * vx + m[1] * vy) + m[2] * vz;
-                float dy = (m[3] * vx + m[4] * vy) + m[5] * vz;
-                float dz = (m[6] * vx + m[7] * vy) + m[8] * vz;
-                float ox = (u2f(cw[0]) + 0.0f) * inv_size + 1.0f;
-                float oy = (u2f(cw[1]) + 0.0f) * inv_size + 1.0f;
-                float oz = (u2f(cw[2]) + 0.0f) * inv_size + 1.0f;
+                float ox, oy, oz, dx, dy, dz;
+                pinhole_camera_ray(load_camera(ka), W, H, px_x, px_y, inv_size, ox, oy, oz, dx, dy, dz);
                 Ray r0, r;
                 bool active = ray_setup(r0, root, ox, oy, oz, dx, dy, dz);
                 // every camera ray starts at the camera, on the path of its direction signs
@@ -842,24 +852,14 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
                 Hit h;
                 ray_finish(r, depth, ox, oy, oz, dx, dy, dz, h);
 #ifndef VRC_PROBE
-                if (a.prim && s_begin == 0u) {
-                    uint4* o = reinterpret_cast<uint4*>(a.prim + pix);
-                    o[0] = make_uint4(f2u(h.px), f2u(h.py), f2u(h.pz), f2u(h.nx));
-                    o[1] = make_uint4(f2u(h.ny), f2u(h.nz), f2u(h.u), f2u(h.v));
-                    o[2] = make_uint4(h.hit, h.node, f2u(h.distance), h.complexity);
-                }
+                if (a.prim && s_begin == 0u) store_hit(a.prim + pix, h);
 #endif
                 if (h.hit) {
                     hit = true;
                     albedo = albedo_of(tex, h) | (h.hit >> 16 << 24);               // raycaster.hpp:141-145
                     hpx = h.px; hpy = h.py; hpz = h.pz; hnx = h.nx; hny = h.ny; hnz = h.nz;
-                    // raycaster.hpp:139,150-158 shadow ray(s): the reference re-casts the identical ray
-                    ox = h.px + h.nx * inv_size * 0.001f;
-                    oy = h.py + h.ny * inv_size * 0.001f;
-                    oz = h.pz + h.nz * inv_size * 0.001f;
-                    dx = lx - ox; dy = ly - oy; dz = lz - oz;
-                    normalize3(dx, dy, dz);
-                    const float lit = smax(0.0f, dot3(dx, dy, dz, h.nx, h.ny, h.nz));           // :156
+                    // shadow ray(s): the reference re-casts the identical ray
+                    const float lit = shadow_ray(h, inv_size, lx, ly, lz, ox, oy, oz, dx, dy, dz);
                     active = ray_setup(r0, root, ox, oy, oz, dx, dy, dz);
                     ray_start_below(r0, from_root ? 22u : start_scale_next_to(ox, oy, oz, h.px, h.py, h.pz, h.hit >> 16), ox, oy, oz);
                     for (uint32_t k = n_shadow_walks; k--;) {
@@ -876,14 +876,9 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
                     uint32_t color = 0u;                                             // ColorResult: Black
                     if (hit) {
                         float gi_intensity = 0.0f;
-                        if (a.p.use_gi) {
-                            if constexpr (ONE_BOUNCE)
-                                gi_intensity = gi_chain<ONE_BOUNCE>(nodes, stk, albedo >> 24, from_root, root, depth, n_normalizer, lx, ly, lz, gi_bounces, a.p.seed,
-                                                    a.p.frame_index + sample, pix, hpx, hpy, hpz, hnx, hny, hnz, ctr);
-                            else
-                                gi_intensity = gi_two_levels(nodes, stk, albedo >> 24, from_root, root, depth, n_normalizer, lx, ly, lz, a.p.seed,
-                                                    a.p.frame_index + sample, pix, hpx, hpy, hpz, hnx, hny, hnz, ctr);
-                        }
+                        if (a.p.use_gi)
+                            gi_intensity = gi_term<ONE_BOUNCE>(nodes, stk, albedo >> 24, from_root, root, depth, n_normalizer, lx, ly, lz, a.p.seed,
+                                                               a.p.frame_index + sample, pix, hpx, hpy, hpz, hnx, hny, hnz, ctr);
                         color = color_mult(albedo, smin(1.0f, smax(0.0f, light_intensity + gi_intensity)));   // :163
                     }
                     sink_sample(a, pix, color, acc_r, acc_g, acc_b);
@@ -905,10 +900,8 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
                 uint32_t probe_c0 = 0u, probe_c1 = 0u, probe_c2 = 0u, probe_c3 = 0u;
 #endif
                 if (valid && (NS == 1u || sample < s_end)) {
-                    // the camera block: ONE scalar load of 16 dwords from the kernel-argument segment per sample, live in the ray generation only
-                    typedef uint32_t cam16_t __attribute__((ext_vector_type(16)));
-                    cam16_t cw;
-                    asm volatile("s_load_dwordx16 %0, %1, %2\n s_waitcnt lgkmcnt(0)" : "=s"(cw) : "s"((const void*)ka), "i"((int)__builtin_offsetof(FrameArgs, cam)));
+                    // the camera block, once per sample: live in the ray generation only
+                    const cam16_t cw = load_camera(ka);
                     const float cpos0 = u2f(cw[0]), cpos1 = u2f(cw[1]), cpos2 = u2f(cw[2]);
                     const float cfov = u2f(cw[12]), caperture = u2f(cw[13]), cfocal = u2f(cw[14]);
                     // R0: main.cpp:133,145-149; camera_controller.hpp:34-54
@@ -969,25 +962,15 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
                     Hit h;
                     ray_finish(r, depth, ox, oy, oz, dx, dy, dz, h);                   // raycaster.hpp:131
 #ifndef VRC_PROBE
-                    if (a.prim && sample == 0u) {
-                        uint4* o = reinterpret_cast<uint4*>(a.prim + pix);
-                        o[0] = make_uint4(f2u(h.px), f2u(h.py), f2u(h.pz), f2u(h.nx));
-                        o[1] = make_uint4(f2u(h.ny), f2u(h.nz), f2u(h.u), f2u(h.v));
-                        o[2] = make_uint4(h.hit, h.node, f2u(h.distance), h.complexity);
-                    }
+                    if (a.prim && sample == 0u) store_hit(a.prim + pix, h);
 #endif
                     if (h.hit) {
                         n_hits += 1u;
                         const uint32_t albedo = albedo_of(tex, h);                             // raycaster.hpp:141-145
-                        // raycaster.hpp:139,150-158 shadow ray(s): the reference re-casts the identical ray
+                        // shadow ray(s): the reference re-casts the identical ray
                         float light_intensity = 0.0f;
-                        ox = h.px + h.nx * inv_size * 0.001f;
-                        oy = h.py + h.ny * inv_size * 0.001f;
-                        oz = h.pz + h.nz * inv_size * 0.001f;
                         for (uint32_t i = shadow_samples; i--;) {
-                            dx = lx - ox; dy = ly - oy; dz = lz - oz;
-                            normalize3(dx, dy, dz);
-                            const float lit = smax(0.0f, dot3(dx, dy, dz, h.nx, h.ny, h.nz));       // :156
+                            const float lit = shadow_ray(h, inv_size, lx, ly, lz, ox, oy, oz, dx, dy, dz);
                             active = ray_setup(r, root, ox, oy, oz, dx, dy, dz);
                             if (!from_root) copy_stack<VRC_SYNC_ROW>(stk + VRC_RENDER_BLOCK, stk, depth);
                             ray_start_below(r, from_root ? 22u : start_scale_next_to(ox, oy, oz, h.px, h.py, h.pz, (h.hit >> 16) & 0xffu), ox, oy, oz);
@@ -995,16 +978,10 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
                             VRC_PROBE_WALK(r, 1)
                             if (!r.kind) light_intensity = lit;                                  // :155-157
                         }
-                        // raycaster.hpp:161,169-207 GI (+ the nested second bounce of the extension)
-                        float gi_intensity = 0.0f;
-                        if (a.p.use_gi) {
-                            if constexpr (ONE_BOUNCE)
-                                gi_intensity = gi_chain<ONE_BOUNCE>(nodes, stk, (h.hit >> 16) & 0xffu, from_root, root, depth, n_normalizer, lx, ly, lz, gi_bounces, a.p.seed, fr, pix,
-                                                    h.px, h.py, h.pz, h.nx, h.ny, h.nz, ctr);
-                            else
-                                gi_intensity = gi_two_levels(nodes, stk, (h.hit >> 16) & 0xffu, from_root, root, depth, n_normalizer, lx, ly, lz, a.p.seed, fr, pix,
-                                                    h.px, h.py, h.pz, h.nx, h.ny, h.nz, ctr);
-                        }
+                        float gi_intensity = 0.0f;                                             // raycaster.hpp:161
+                        if (a.p.use_gi)
+                            gi_intensity = gi_term<ONE_BOUNCE>(nodes, stk, (h.hit >> 16) & 0xffu, from_root, root, depth, n_normalizer, lx, ly, lz,
+                                                               a.p.seed, fr, pix, h.px, h.py, h.pz, h.nx, h.ny, h.nz, ctr);
                         color = color_mult(albedo, smin(1.0f, smax(0.0f, light_intensity + gi_intensity)));   // :163
                     }
                     n_pix += 1u;
@@ -1034,11 +1011,7 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
                     v.x += acc_r; v.y += acc_g; v.z += acc_b; v.w += spp;
                     *ap = v;
                 } else {
-                    // two 64-bit adds per pixel: (r, g) and (b, count) as pairs of u32 -- a sum never carries out of its
-                    // low word (sums < 2^32, as the accumulator format requires), so each half adds independently
-                    unsigned long long* ap = reinterpret_cast<unsigned long long*>(unit_accum + 4ull * pix);
-                    atomicAdd(ap + 0, (unsigned long long)acc_r | ((unsigned long long)acc_g << 32));
-                    atomicAdd(ap + 1, (unsigned long long)acc_b | ((unsigned long long)(s_end - s_begin) << 32));
+                    add_sums(reinterpret_cast<unsigned long long*>(unit_accum + 4ull * pix), acc_r, acc_g, acc_b, s_end - s_begin);
                 }
             }
         } else if (a.p.use_samples) {
@@ -1050,10 +1023,7 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
             uint32_t sum_r = acc_r, sum_g = acc_g, sum_b = acc_b, count = s_end - s_begin;
             if (chunks_per_tile != 1u) {
                 unsigned long long* ap = reinterpret_cast<unsigned long long*>(unit_accum + 4ull * pix);
-                if (writer) {
-                    atomicAdd(ap + 0, (unsigned long long)acc_r | ((unsigned long long)acc_g << 32));
-                    atomicAdd(ap + 1, (unsigned long long)acc_b | ((unsigned long long)(s_end - s_begin) << 32));
-                }
+                if (writer) add_sums(ap, acc_r, acc_g, acc_b, s_end - s_begin);
                 // Every lane's adds are performed at the memory side before this unit counts as arrived; the counter add
                 // is a device-scope atomic too, and the last arriver takes the sums with device-scope exchanges -- never
                 // with loads: the 128-byte line of a pixel's sums also holds neighbours' (of another tile when the width
@@ -1112,73 +1082,68 @@ __device__ __forceinline__ void render_sync_body(const FrameArgs& a)
     }
 }
 
+// The builds of the frame kernel, one row each: X(symbol, PINHOLE, ONE_BOUNCE, FUSED, FROM_ROOT, lane map, waves per SIMD).  The list
+// instantiates them and makes the table the planner chooses from (frame_kernel); the first row of a kind is its standard build.
 // k_render_sync: any camera, the reference's one indirect bounce (k_render_sync2: the 2-bounce extension).
 // k_render_sync_pinhole: aperture +0 and one bounce -- the configuration the reference ships with and BASELINE's metric
 // is quoted on (k_render_sync_pinhole2: with the extension).  The bounce count is a compile-time fact in the one-bounce
-// kernels: gi_chain is straight-line code there, which is worth a third of the register spills.  The ..._resolved
+// kernels: gi_term is straight-line code there, which is worth a third of the register spills.  The ..._resolved
 // kernels are the same four with the fused resolve (vrc_render_frame_resolved) compiled in; the plain ones do not
 // carry its code or its arguments' registers.
-#define VRC_SYNC_KERNEL_NS(name, PINHOLE, ONE_BOUNCE, FUSED, WAVES, NS)                            \
-    extern "C" __global__ void __launch_bounds__(VRC_RENDER_BLOCK, WAVES) name(const FrameArgs a)  \
-    {                                                                                              \
-        render_sync_body<PINHOLE, ONE_BOUNCE, FUSED, false, NS>(a);                                \
-    }
-#define VRC_SYNC_KERNEL(name, PINHOLE, ONE_BOUNCE, FUSED, WAVES) VRC_SYNC_KERNEL_NS(name, PINHOLE, ONE_BOUNCE, FUSED, WAVES, 1u)
-VRC_SYNC_KERNEL(k_render_sync, false, true, false, VRC_SYNC_MIN_WAVES)
-VRC_SYNC_KERNEL(k_render_sync2, false, false, false, VRC_SYNC_MIN_WAVES)
-VRC_SYNC_KERNEL(k_render_sync_pinhole, true, true, false, VRC_SYNC_MIN_WAVES)
-VRC_SYNC_KERNEL(k_render_sync_pinhole2, true, false, false, VRC_SYNC_MIN_WAVES)
-VRC_SYNC_KERNEL(k_render_sync_resolved, false, true, true, VRC_SYNC_MIN_WAVES)
-VRC_SYNC_KERNEL(k_render_sync2_resolved, false, false, true, VRC_SYNC_MIN_WAVES)
-VRC_SYNC_KERNEL(k_render_sync_pinhole_resolved, true, true, true, VRC_SYNC_MIN_WAVES)
-VRC_SYNC_KERNEL(k_render_sync_pinhole2_resolved, true, false, true, VRC_SYNC_MIN_WAVES)
-// the lens (DOF) one-bounce kernel also at 7 waves per SIMD (vrc_internal.h: sync_waves_for).  Rounds 2 and 3 shipped pinhole
+// _w7: the lens (DOF) one-bounce kernel also at 7 waves per SIMD (vrc_internal.h, FrameVariant).  Rounds 2 and 3 shipped pinhole
 // builds for 7 and 8 waves as well; since the walks start below the root (fewer, less coherent iterations; two stacks) the
 // 6-wave build ties or beats them on every configuration and pose (profiles/r03/sweep_waves_below.txt), without their spills.
-VRC_SYNC_KERNEL(k_render_sync_w7, false, true, false, 7)
-VRC_SYNC_KERNEL(k_render_sync_resolved_w7, false, true, true, 7)
-// four samples abreast (NS = 4, see render_sync_body): the one-bounce kernels, for sample-mode frames with spp % 4 == 0
-VRC_SYNC_KERNEL_NS(k_render_sync_s4, false, true, false, VRC_SYNC_S4_WAVES_LENS, 4u)
-VRC_SYNC_KERNEL_NS(k_render_sync_resolved_s4, false, true, true, VRC_SYNC_S4_WAVES_LENS, 4u)
-VRC_SYNC_KERNEL_NS(k_render_sync_pinhole_s4, true, true, false, VRC_SYNC_S4_WAVES, 4u)
-VRC_SYNC_KERNEL_NS(k_render_sync_pinhole_resolved_s4, true, true, true, VRC_SYNC_S4_WAVES, 4u)
-// the pinhole kernels with quadrant walks (render_sync_body's QUAD)
-// (the variant builds -- the C++ walk, the probes, every ray from the root -- have no quadrant-walk kernels: quad_available())
+// _s4: four samples abreast (see render_sync_body), the one-bounce kernels, for sample-mode frames with spp % 4 == 0.
+// _from_root: every kernel of the 8 x 8 map once more with every ray started at the root, as lsvo.hpp:60-72 does
+// (vrc_renderer_set_walk_from_root: a measurement and A/B switch -- bench.py's extra.every_ray_from_the_root says what the start
+// below the root is worth; tests/test_gpu_start_below.py renders pinhole, lens and 2-bounce frames both ways and wants them equal)
+#define VRC_FRAME_KERNELS(X)                                                                                    \
+    X(k_render_sync, false, true, false, false, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)                           \
+    X(k_render_sync2, false, false, false, false, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)                         \
+    X(k_render_sync_pinhole, true, true, false, false, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)                    \
+    X(k_render_sync_pinhole2, true, false, false, false, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)                  \
+    X(k_render_sync_resolved, false, true, true, false, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)                   \
+    X(k_render_sync2_resolved, false, false, true, false, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)                 \
+    X(k_render_sync_pinhole_resolved, true, true, true, false, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)            \
+    X(k_render_sync_pinhole2_resolved, true, false, true, false, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)          \
+    X(k_render_sync_w7, false, true, false, false, LaneMap::tile8x8, 7)                                         \
+    X(k_render_sync_resolved_w7, false, true, true, false, LaneMap::tile8x8, 7)                                 \
+    X(k_render_sync_s4, false, true, false, false, LaneMap::samples4, VRC_SYNC_S4_WAVES_LENS)                   \
+    X(k_render_sync_resolved_s4, false, true, true, false, LaneMap::samples4, VRC_SYNC_S4_WAVES_LENS)           \
+    X(k_render_sync_pinhole_s4, true, true, false, false, LaneMap::samples4, VRC_SYNC_S4_WAVES)                 \
+    X(k_render_sync_pinhole_resolved_s4, true, true, true, false, LaneMap::samples4, VRC_SYNC_S4_WAVES)         \
+    X(k_render_sync_pinhole_from_root, true, true, false, true, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)           \
+    X(k_render_sync_pinhole_resolved_from_root, true, true, true, true, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)   \
+    X(k_render_sync_pinhole2_from_root, true, false, false, true, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)         \
+    X(k_render_sync_pinhole2_resolved_from_root, true, false, true, true, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES) \
+    X(k_render_sync_from_root, false, true, false, true, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)                  \
+    X(k_render_sync_resolved_from_root, false, true, true, true, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)          \
+    X(k_render_sync2_from_root, false, false, false, true, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)                \
+    X(k_render_sync2_resolved_from_root, false, false, true, true, LaneMap::tile8x8, VRC_SYNC_MIN_WAVES)        \
+    VRC_QUAD_FRAME_KERNELS(X)
+// the pinhole kernels with quadrant walks (render_sync_body's QUAD).  The variant builds -- the C++ walk, the probes, every ray
+// from the root -- have none: no quadrant rows, so the planner cannot choose them (quad_available).
 #ifndef VRC_SYNC_Q_WAVES
 #define VRC_SYNC_Q_WAVES 6
 #endif
 #if !(defined(VRC_WALK_CPP) || defined(VRC_PROBE) || defined(VRC_NO_START_BELOW))
 #define VRC_HAVE_QUAD 1
-#define VRC_SYNC_KERNEL_Q(name, ONE_BOUNCE, FUSED)                                                         \
-    extern "C" __global__ void __launch_bounds__(VRC_RENDER_BLOCK, VRC_SYNC_Q_WAVES) name(const FrameArgs a)  \
-    {                                                                                                      \
-        render_sync_body<true, ONE_BOUNCE, FUSED, false, 1u, true>(a);                                     \
-    }
-VRC_SYNC_KERNEL_Q(k_render_sync_pinhole_q, true, false)
-VRC_SYNC_KERNEL_Q(k_render_sync_pinhole_resolved_q, true, true)
-VRC_SYNC_KERNEL_Q(k_render_sync_pinhole2_q, false, false)
-VRC_SYNC_KERNEL_Q(k_render_sync_pinhole2_resolved_q, false, true)
-#undef VRC_SYNC_KERNEL_Q
+#define VRC_QUAD_FRAME_KERNELS(X)                                                                   \
+    X(k_render_sync_pinhole_q, true, true, false, false, LaneMap::quad, VRC_SYNC_Q_WAVES)           \
+    X(k_render_sync_pinhole_resolved_q, true, true, true, false, LaneMap::quad, VRC_SYNC_Q_WAVES)   \
+    X(k_render_sync_pinhole2_q, true, false, false, false, LaneMap::quad, VRC_SYNC_Q_WAVES)         \
+    X(k_render_sync_pinhole2_resolved_q, true, false, true, false, LaneMap::quad, VRC_SYNC_Q_WAVES)
+#else
+#define VRC_QUAD_FRAME_KERNELS(X)
 #endif
-#undef VRC_SYNC_KERNEL
-#undef VRC_SYNC_KERNEL_NS
-// every kernel of the 8 x 8 map once more with every ray started at the root, as lsvo.hpp:60-72 does
-// (vrc_renderer_set_walk_from_root: a measurement and A/B switch -- bench.py's extra.every_ray_from_the_root says what the start
-// below the root is worth; tests/test_gpu_start_below.py renders pinhole, lens and 2-bounce frames both ways and wants them equal)
-#define VRC_SYNC_KERNEL_ROOT(name, PINHOLE, ONE_BOUNCE, FUSED)                                                  \
-    extern "C" __global__ void __launch_bounds__(VRC_RENDER_BLOCK, VRC_SYNC_MIN_WAVES) name(const FrameArgs a)  \
-    {                                                                                                           \
-        render_sync_body<PINHOLE, ONE_BOUNCE, FUSED, true>(a);                                                  \
+
+#define VRC_FRAME_KERNEL(name, PINHOLE, ONE_BOUNCE, FUSED, FROM_ROOT, MAP, WAVES)                    \
+    extern "C" __global__ void __launch_bounds__(VRC_RENDER_BLOCK, WAVES) name(const FrameArgs a)  \
+    {                                                                                              \
+        render_sync_body<PINHOLE, ONE_BOUNCE, FUSED, FROM_ROOT, MAP>(a);                           \
     }
-VRC_SYNC_KERNEL_ROOT(k_render_sync_pinhole_from_root, true, true, false)
-VRC_SYNC_KERNEL_ROOT(k_render_sync_pinhole_resolved_from_root, true, true, true)
-VRC_SYNC_KERNEL_ROOT(k_render_sync_pinhole2_from_root, true, false, false)
-VRC_SYNC_KERNEL_ROOT(k_render_sync_pinhole2_resolved_from_root, true, false, true)
-VRC_SYNC_KERNEL_ROOT(k_render_sync_from_root, false, true, false)
-VRC_SYNC_KERNEL_ROOT(k_render_sync_resolved_from_root, false, true, true)
-VRC_SYNC_KERNEL_ROOT(k_render_sync2_from_root, false, false, false)
-VRC_SYNC_KERNEL_ROOT(k_render_sync2_resolved_from_root, false, false, true)
-#undef VRC_SYNC_KERNEL_ROOT
+VRC_FRAME_KERNELS(VRC_FRAME_KERNEL)
+#undef VRC_FRAME_KERNEL
 
 // ---------------------------------------------------------------------------
 // S4 sink + plumbing
@@ -1367,26 +1332,34 @@ hipError_t launch_grid_cast(const uint8_t* cells, int X, int Y, int Z, uint64_t 
     return hipGetLastError();
 }
 
-uint32_t sync_max_blocks_per_cu() { return VRC_SYNC_MIN_WAVES; }
-uint32_t quad_lds_bytes() { return VRC_QUAD_LDS_BYTES; }
-uint32_t quad_waves() { return VRC_SYNC_Q_WAVES; }
+#define VRC_FRAME_ROW(name, PINHOLE, ONE_BOUNCE, FUSED, FROM_ROOT, MAP, WAVES) {name, #name, {PINHOLE, ONE_BOUNCE, FUSED, FROM_ROOT, MAP, WAVES}},
+static const FrameKernel frame_kernels[] = {VRC_FRAME_KERNELS(VRC_FRAME_ROW)};
+#undef VRC_FRAME_ROW
+
+const FrameKernel* frame_kernel(const FrameVariant& v)
+{
+    const FrameKernel* standard = nullptr;
+    for (const FrameKernel& k : frame_kernels) {
+        if (k.v.pinhole != v.pinhole || k.v.one_bounce != v.one_bounce || k.v.fused != v.fused || k.v.from_root != v.from_root ||
+            k.v.map != v.map)
+            continue;
+        if (k.v.waves == v.waves) return &k;
+        if (!standard) standard = &k;
+    }
+    return standard;
+}
+
 bool quad_available()
 {
-#ifdef VRC_HAVE_QUAD
-    return true;
-#else
+    for (const FrameKernel& k : frame_kernels)
+        if (k.v.map == LaneMap::quad) return true;
     return false;
-#endif
 }
-uint32_t sync_s4_waves(bool pinhole) { return pinhole ? VRC_SYNC_S4_WAVES : VRC_SYNC_S4_WAVES_LENS; }
-uint32_t sync_waves_for(bool pinhole, bool one_bounce, bool use_gi, bool whole_spp_units, uint64_t pixel_samples, uint32_t requested)
+
+// two stacks, textures, the waves' counters, camera paths, the waves' counts of iterations not executed (render_sync_body)
+uint32_t frame_lds_bytes(uint32_t depth)
 {
-    // the builds that exist: 6 for every kernel; the lens one-bounce kernel also 7
-    (void)use_gi; (void)pixel_samples;
-    if (pinhole || !one_bounce) return VRC_SYNC_MIN_WAVES;
-    if (requested) return requested >= 7u ? 7u : VRC_SYNC_MIN_WAVES;   // the caller's choice, rounded down to a build that exists
-    // tools/sweep_waves.sh (profiles/r03/sweep_waves_below.txt: C2..C5 x pitch 0 / -0.5 / -1.2 x frames in flight 3 / 1)
-    return whole_spp_units ? 7u : VRC_SYNC_MIN_WAVES;                  // lens: 7 by 1-1.5 % with frames in flight, 6 alone on the chip
+    return 2u * depth * VRC_RENDER_BLOCK * sizeof(stack_t) + VRC_TEX_BYTES + VRC_WAVE_CTR_BYTES + VRC_CAMERA_PATH_BYTES + VRC_NOT_EXECUTED_BYTES;
 }
 
 bool camera_is_pinhole(const vrc_camera& cam)
@@ -1404,43 +1377,9 @@ bool camera_is_pinhole(const vrc_camera& cam)
     return pinhole;
 }
 
-hipError_t launch_render(const FrameArgs& a, uint32_t grid_blocks, hipStream_t st, const char** launched)
+hipError_t launch_render(const FrameKernel& k, const FrameArgs& a, uint32_t grid_blocks, uint32_t lds, hipStream_t st)
 {
-    const char* name = "";
-    {
-        size_t lds = 2 * (size_t)a.depth * VRC_RENDER_BLOCK * sizeof(stack_t) + 1536 + 128 + VRC_CAMERA_PATH_BYTES + 32;   // two stacks, tables, the waves' counters, camera paths, iterations not executed
-        const bool pinhole = camera_is_pinhole(a.cam);
-        const bool one = a.p.gi_bounces <= 1u, fused = a.fused_resolve != 0u;
-        const uint32_t waves = a.waves;
-        struct Build { void (*fn)(const FrameArgs); const char* name; };
-#define VRC_BUILD(k) Build{k, #k}
-        const bool s4 = a.lane_samples == 4u && one;
-#ifdef VRC_HAVE_QUAD
-        const bool quad = a.quad_walks != 0u && pinhole && !s4 && !a.walk_from_root;
-        if (quad) lds += VRC_QUAD_LDS_BYTES;
-#endif
-        const Build b =
-#ifdef VRC_HAVE_QUAD
-            quad ? (one ? (fused ? VRC_BUILD(k_render_sync_pinhole_resolved_q) : VRC_BUILD(k_render_sync_pinhole_q))
-                        : (fused ? VRC_BUILD(k_render_sync_pinhole2_resolved_q) : VRC_BUILD(k_render_sync_pinhole2_q))) :
-#endif
-            s4 ? (pinhole ? (fused ? VRC_BUILD(k_render_sync_pinhole_resolved_s4) : VRC_BUILD(k_render_sync_pinhole_s4))
-                          : (fused ? VRC_BUILD(k_render_sync_resolved_s4) : VRC_BUILD(k_render_sync_s4))) :
-            a.walk_from_root ? (pinhole ? (one ? (fused ? VRC_BUILD(k_render_sync_pinhole_resolved_from_root) : VRC_BUILD(k_render_sync_pinhole_from_root))
-                                               : (fused ? VRC_BUILD(k_render_sync_pinhole2_resolved_from_root) : VRC_BUILD(k_render_sync_pinhole2_from_root)))
-                                        : (one ? (fused ? VRC_BUILD(k_render_sync_resolved_from_root) : VRC_BUILD(k_render_sync_from_root))
-                                               : (fused ? VRC_BUILD(k_render_sync2_resolved_from_root) : VRC_BUILD(k_render_sync2_from_root)))) :
-            (waves == 7u && !pinhole && one) ? (fused ? VRC_BUILD(k_render_sync_resolved_w7) : VRC_BUILD(k_render_sync_w7)) :
-            pinhole ? (one ? (fused ? VRC_BUILD(k_render_sync_pinhole_resolved) : VRC_BUILD(k_render_sync_pinhole))
-                           : (fused ? VRC_BUILD(k_render_sync_pinhole2_resolved) : VRC_BUILD(k_render_sync_pinhole2)))
-                    : (one ? (fused ? VRC_BUILD(k_render_sync_resolved) : VRC_BUILD(k_render_sync))
-                           : (fused ? VRC_BUILD(k_render_sync2_resolved) : VRC_BUILD(k_render_sync2)));
-#undef VRC_BUILD
-        void (*kernel_fn)(const FrameArgs) = b.fn;
-        name = b.name;
-        hipLaunchKernelGGL(kernel_fn, dim3(grid_blocks), dim3(VRC_RENDER_BLOCK), lds, st, a);
-    }
-    if (launched) *launched = name;
+    hipLaunchKernelGGL(k.fn, dim3(grid_blocks), dim3(VRC_RENDER_BLOCK), lds, st, a);
     return hipGetLastError();
 }
 

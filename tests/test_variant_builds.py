@@ -3,6 +3,7 @@ defined, so every -DVRC_PROBE / -DVRC_WALK_CPP / -DVRC_NO_START_BELOW build was 
 pass (hipcc -fsyntax-only: host AND gfx950 device side, inline-asm constraints included) of the two sources that carry
 switches, once per flag of cpuvoxelraycaster_amd/build.py's VARIANT_FLAGS; about a second each, no GPU."""
 import os
+import re
 import subprocess
 
 import pytest
@@ -24,13 +25,41 @@ def test_variant_flag_compiles(flag):
 
 def test_variant_builds_have_no_quadrant_kernels_and_say_so():
     """the variants that leave the quadrant-walk kernels out must report it (vrc::quad_available), so that render_impl neither
-    sets FrameArgs::quad_walks nor sizes the grid for a build launch_render would not launch"""
+    chooses a quadrant-walk build nor sizes the grid for a build it could not launch"""
     src = open(os.path.join(build.CSRC, "vrc_kernels.hip")).read()
     api = open(os.path.join(build.CSRC, "vrc_api.cpp")).read()
     assert "bool quad_available()" in src and "vrc::quad_available() &&" in api
     # the occupancy macro is defined whatever the variant
     head = src[:src.index("#define VRC_HAVE_QUAD 1")]
     assert "#define VRC_SYNC_Q_WAVES 6" in head and head.rstrip().endswith("defined(VRC_NO_START_BELOW))")
+
+
+def test_variant_builds_have_no_quadrant_rows_in_the_frame_kernel_table():
+    """the variants that leave the quadrant-walk kernels out have no quadrant rows in the frame-kernel table (vrc::frame_kernel),
+    and the planner chooses only from rows that exist, so that render_impl neither picks a quadrant build nor sizes the grid for
+    a build launch_render could not launch"""
+    src = open(os.path.join(build.CSRC, "vrc_kernels.hip")).read()
+    api = open(os.path.join(build.CSRC, "vrc_api.cpp")).read()
+    guard = "#if !(defined(VRC_WALK_CPP) || defined(VRC_PROBE) || defined(VRC_NO_START_BELOW))"
+    i = src.index(guard)
+    j = src.index("#else", i)
+    k = src.index("#endif", j)
+    # every quadrant row of the one list sits behind the guard, and the other branch has none
+    quad_rows = re.findall(r"X\((k_render_sync\w+),[^)]*LaneMap::quad", src)
+    assert len(quad_rows) == 4 and quad_rows == re.findall(r"X\((k_render_sync\w+),[^)]*LaneMap::quad", src[i:j])
+    assert src[j:k].split() == ["#else", "#define", "VRC_QUAD_FRAME_KERNELS(X)"]
+    # the kernels and the table come from that list; the planner asks the table for a quadrant build and launches what it chose
+    assert "VRC_FRAME_KERNELS(VRC_FRAME_KERNEL)" in src and "VRC_FRAME_KERNELS(VRC_FRAME_ROW)" in src
+    assert "if (k.v.map == LaneMap::quad) return true;" in src and "vrc::quad_available() &&" in api
+    assert "kernel = vrc::frame_kernel(v);" in api and "vrc::launch_render(*kernel," in api
+    # the occupancy macro is defined whatever the variant
+    assert "#define VRC_SYNC_Q_WAVES 6" in src[:i]
+    if os.path.exists(HIPCC):   # and the preprocessor agrees, per variant
+        for flag in ("", "-DVRC_WALK_CPP", "-DVRC_PROBE", "-DVRC_NO_START_BELOW"):
+            cmd = [HIPCC] + [f for f in FRONT if f != "-fsyntax-only"] + ([flag] if flag else []) + \
+                  ["--cuda-host-only", "-E", "-x", "hip", os.path.join(build.CSRC, "vrc_kernels.hip")]
+            out = subprocess.run(cmd, capture_output=True, text=True, check=True).stdout
+            assert all((name in out) == (flag == "") for name in quad_rows), flag
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")

@@ -16,7 +16,7 @@ from cpuvoxelraycaster_amd import build  # noqa: E402
 # kernel -> (VGPR spills, scratch bytes per lane) the shipped builds are accepted with (round-5 advice: the quadrant-walk
 # kernels sit at the 80-VGPR budget; a spill that creeps into the unit loop of the timed kernel is a performance regression
 # nobody would see in the parity tests).  The one spill of k_render_sync_pinhole_resolved_q is the fused resolve's tile counter
-# pointer, touched once per unit; the 2-bounce extension's five are in the second gi_chain.  Everything else of the pinhole
+# pointer, touched once per unit; the 2-bounce extension's five are in gi_term's second level.  Everything else of the pinhole
 # family has none.  The lens kernels' figures are the accepted cost of 7 waves per SIMD.
 ACCEPTED_SPILLS = {
     "k_render_sync_pinhole_q": (0, 0),

@@ -37,7 +37,7 @@ def period(N, F, whole):
         if os.environ.get("VRC_QUAD_OFF") == "1":
             rc.setQuadWalks(False)                  # A/B of the quadrant walks (round 5)
         if BLOCKS:
-            rc.setTuning(blocks_per_cu=BLOCKS)      # force the 6 / 7 / 8 waves-per-SIMD build (A/B of sync_waves_for's choice)
+            rc.setTuning(blocks_per_cu=BLOCKS)      # force the 6 / 7 / 8 waves-per-SIMD build (A/B of the planner's choice)
         rcs.append(rc)
     streams = [torch.cuda.Stream() for _ in range(F)]
     bufs = [torch.empty(L.vrc_shard_bytes(W, H, 8, N), dtype=torch.uint8, device="cuda") for _ in range(F)]
