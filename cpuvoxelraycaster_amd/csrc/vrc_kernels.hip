@@ -137,6 +137,15 @@ k_cast_ray_chains_nolod(const uint2* __restrict__ nodes, int depth, uint64_t n, 
 // G1: dense grid DDA
 // ---------------------------------------------------------------------------
 
+// grid_3d.hpp:58-60 `(int)position.x`: undefined in C++ for NaN and outside [-2^31, 2^31).  The reference as it ships (x86-64)
+// gives INT_MIN for all of them -- the loop at :70 never runs, the ray is a miss with a zero record -- and the oracle states
+// that rule (orc_grid_cell).  v_cvt_i32_f32 saturates and turns NaN into 0, a cell of the grid: hence the select.
+// |v| < 2^31 leaves out -2^31 itself, whose conversion is INT_MIN anyway.
+__device__ __forceinline__ int grid_cell(float v)
+{
+    return fabsf(v) < 0x1p31f ? (int)v : (int)0x80000000u;
+}
+
 extern "C" __global__ void __launch_bounds__(256)
 k_grid_cast(const uint8_t* __restrict__ cells, int X, int Y, int Z, uint64_t n,
             const float* __restrict__ org, const float* __restrict__ dir, vrc_hit* __restrict__ out)
@@ -149,7 +158,7 @@ k_grid_cast(const uint8_t* __restrict__ cells, int X, int Y, int Z, uint64_t n,
     const float t_dx = fabsf(1.0f / dx), t_dy = fabsf(1.0f / dy), t_dz = fabsf(1.0f / dz);
     const int step_x = dx < 0 ? -1 : 1, step_y = dy < 0 ? -1 : 1, step_z = dz < 0 ? -1 : 1;
     const int dir_x = step_x > 0 ? 1 : 0, dir_y = step_y > 0 ? 1 : 0, dir_z = step_z > 0 ? 1 : 0;
-    int cell_x = (int)ox, cell_y = (int)oy, cell_z = (int)oz;
+    int cell_x = grid_cell(ox), cell_y = grid_cell(oy), cell_z = grid_cell(oz);
     float t_max_x = ((float)(cell_x + dir_x) - ox) / dx;
     float t_max_y = ((float)(cell_y + dir_y) - oy) / dy;
     float t_max_z = ((float)(cell_z + dir_z) - oz) / dz;

@@ -160,7 +160,12 @@ int vrc_cast_ray(const vrc_scene *s, const float org[3], const float dir[3],
 /* cells[(x*Y + y)*Z + z] = Cell::Type (0 = Empty). */
 int vrc_grid_create(const uint8_t *cells, int32_t X, int32_t Y, int32_t Z, int device, vrc_grid **out);
 int vrc_grid_destroy(vrc_grid *g);
-/* Grid3D::castRay(position, direction) (grid_3d.hpp:36-132), voxel units. */
+/* Grid3D::castRay(position, direction) (grid_3d.hpp:36-132), voxel units.  The start cell is the origin truncated towards
+ * zero (:58-60: an origin in (-1, 0) starts in cell 0).  An origin coordinate that is NaN or outside [-2^31, 2^31) has no
+ * cell: the ray is a miss with an all-zero record, complexity included, as in the reference as it ships (x86-64 converts
+ * such a value to INT_MIN, and the loop at :70 never runs).  So is every ray whose start cell lies outside the grid.
+ * Non-finite and zero direction components are valid input and give what the reference's arithmetic gives; the sign and
+ * payload of a NaN in a float field are the hardware's. */
 int vrc_grid_cast_rays(const vrc_grid *g, uint64_t n, const float *org_xyz, const float *dir_xyz,
                        vrc_hit *out, int mem, void *stream);
 

@@ -496,6 +496,15 @@ void orc_cast_rays(const orc_lnode *nodes, uint32_t depth, uint64_t n,
 /* G1: Grid3D<X,Y,Z>::castRay (grid_3d.hpp:36-132)                           */
 /* ------------------------------------------------------------------------- */
 
+/* grid_3d.hpp:58-60 `(int32_t)position.x`.  C leaves the conversion undefined for NaN and for values outside
+ * [-2^31, 2^31); the reference as it ships (x86-64: cvttss2si) gives INT32_MIN for all of them, so the loop at :70 never
+ * runs and the ray is a miss with an all-zero record.  Stated here as a rule, so that neither this file nor the kernel
+ * depends on what a compiler or a GPU makes of the undefined case. */
+int32_t orc_grid_cell(float v)
+{
+    return (v >= -2147483648.0f && v < 2147483648.0f) ? (int32_t)v : INT32_MIN;
+}
+
 void orc_grid_cast_ray(const uint8_t *cells, int32_t X, int32_t Y, int32_t Z,
                        const float org[3], const float dir[3], orc_hit *point)
 {
@@ -505,8 +514,8 @@ void orc_grid_cast_ray(const uint8_t *cells, int32_t X, int32_t Y, int32_t Z,
     /* :48-55 */
     const int32_t step_x = dir[0] < 0 ? -1 : 1, step_y = dir[1] < 0 ? -1 : 1, step_z = dir[2] < 0 ? -1 : 1;
     const int32_t dir_x = step_x > 0 ? 1 : 0, dir_y = step_y > 0 ? 1 : 0, dir_z = step_z > 0 ? 1 : 0;
-    /* :58-60 float -> int32 truncation */
-    int32_t cell_x = (int32_t)org[0], cell_y = (int32_t)org[1], cell_z = (int32_t)org[2];
+    /* :58-60 float -> int32 truncation (NaN / out of range: INT32_MIN, see orc_grid_cell) */
+    int32_t cell_x = orc_grid_cell(org[0]), cell_y = orc_grid_cell(org[1]), cell_z = orc_grid_cell(org[2]);
     /* :62-64 (int + int) converted to float, minus, divide */
     float t_max_x = ((float)(cell_x + dir_x) - org[0]) / dir[0];
     float t_max_y = ((float)(cell_y + dir_y) - org[1]) / dir[1];

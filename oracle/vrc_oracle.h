@@ -91,6 +91,7 @@ void orc_cast_rays(const orc_lnode *nodes, uint32_t depth, uint64_t n,
                    orc_hit *out, int threads);
 
 /* ---- G1: Grid3D::castRay (grid_3d.hpp:36-132), cells = type bytes [x][y][z] ---- */
+int32_t orc_grid_cell(float v);   /* the start cell of one coordinate: truncation; NaN or outside [-2^31, 2^31) -> INT32_MIN */
 void orc_grid_cast_ray(const uint8_t *cells, int32_t X, int32_t Y, int32_t Z,
                        const float org[3], const float dir[3], orc_hit *out);
 void orc_grid_cast_rays(const uint8_t *cells, int32_t X, int32_t Y, int32_t Z,

@@ -259,3 +259,46 @@ def test_direction_magnitudes_across_the_shortcut_guards(terrain, exp2):
     coef = np.full(len(org), 0.5, np.float32)
     bias = np.where(np.arange(len(org)) % 3 == 0, 1e-3, 0.0).astype(np.float32)
     assert_hits_equal(svo.castRays(org, d, coef, bias), O.cast_rays(nodes, 9, org, d, coef, bias, threads=8))
+
+
+@pytest.mark.parametrize("mem", ["host", "device"])
+@pytest.mark.parametrize("form", ["both", "coef_only", "bias_only", "neither"])
+def test_coef_and_bias_argument_forms(terrain, form, mem):
+    """vrc_cast_rays takes `coef` and `bias` separately, each an array or NULL (= zeros): the host form lays its staging
+    block out from which of the two are there, and only both NULL select the kernel without the LOD test.  Every form, from
+    host memory and from device memory on a created stream, against the oracle with the missing array read as zeros."""
+    import ctypes as C
+    import torch
+    import cpuvoxelraycaster_amd as vrc
+    L = vrc.capi.load()
+    ptr = vrc.capi.ptr
+    nodes, svo = terrain[7]
+    org, d = raygen.mixed_rays(100000, seed=31)
+    n = len(org)
+    rng = np.random.default_rng(32)
+    coef = rng.choice([0.0, 0.25, 0.5, 1.5], size=n).astype(np.float32) if form in ("both", "coef_only") else None
+    bias = rng.choice([0.0, 0.0, 0.002, 0.05], size=n).astype(np.float32) if form in ("both", "bias_only") else None
+    zeros = np.zeros(n, np.float32)
+    ref = O.cast_rays(nodes, 7, org, d, coef if coef is not None else zeros, bias if bias is not None else zeros, threads=8)
+    if form == "neither":
+        assert ref.tobytes() == O.cast_rays(nodes, 7, org, d, threads=8).tobytes()
+    else:
+        assert ((ref["hit"] & 0xff) == 2).sum() > 100                      # the LOD cut-off fires
+    if mem == "host":
+        out = np.full(n * 48, 0xAB, np.uint8)
+        vrc.capi.check(L.vrc_cast_rays(svo._h, n, ptr(org), ptr(d), ptr(coef), ptr(bias), ptr(out), vrc.capi.VRC_MEM_HOST, None))
+    else:
+        st = C.c_void_p()
+        vrc.capi.check(L.vrc_stream_create(0, C.byref(st)))
+        try:
+            t = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x).reshape(-1)).cuda()
+            p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+            d_org, d_dir, d_coef, d_bias = t(org), t(d), t(coef), t(bias)
+            d_out = torch.full((n * 48,), 0xAB, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            vrc.capi.check(L.vrc_cast_rays(svo._h, n, p(d_org), p(d_dir), p(d_coef), p(d_bias), p(d_out), vrc.capi.VRC_MEM_DEVICE, st))
+            vrc.capi.check(L.vrc_stream_synchronize(0, st))
+            out = d_out.cpu().numpy()
+        finally:
+            vrc.capi.check(L.vrc_stream_destroy(0, st))
+    assert_hits_equal(np.frombuffer(out.tobytes(), dtype=vrc.HIT_DTYPE), ref)

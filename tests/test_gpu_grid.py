@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+import edge_cases as E
 import oracle_lib as O
 from test_gpu_cast import assert_hits_equal
 
@@ -46,3 +47,189 @@ def test_grid_random_rays(built):
     got = vrc.Grid3D(cells).castRays(org, d)
     ref = O.grid_cast_rays(cells, org, d)
     assert_hits_equal(got, ref)
+
+
+# ---- the edges of the operator's inputs ----------------------------------------------------------------------------------
+# Every batch goes through vrc.Grid3D(...).castRays and through the oracle; fields are compared as uint32, and a float that
+# is NaN on both sides counts as equal (edge_cases.assert_hits_equal_nan_relaxed: the hardware fixes the sign and payload of
+# inf * 0, not the algorithm).  The tests above keep the strict comparison.
+
+
+def grid_pair(vrc, cells, org, d):
+    got = vrc.Grid3D(cells).castRays(org, d)
+    ref = O.grid_cast_rays(cells, org, d, threads=8)
+    relaxed, ref_nan = E.assert_hits_equal_nan_relaxed(got, ref)
+    print(f"grid {cells.shape}: {len(org)} rays, {int((ref['hit'] != 0).sum())} hits, {relaxed} lanes compared relaxed, "
+          f"{ref_nan} lanes with a NaN in the oracle's record")
+    return got, ref
+
+
+@pytest.mark.parametrize("density", [0.5, 1.0])
+@pytest.mark.parametrize("shape", [(8, 8, 8), (3, 5, 7)])
+def test_grid_origin_nan_inf_or_outside_int32_is_a_miss(built, shape, density):
+    """(int)position of grid_3d.hpp:58-60 for NaN, +-inf, +-2^31, +-3e9, +-FLT_MAX: the reference as shipped starts such a
+    ray in cell INT_MIN, i.e. nowhere -- a miss with a zero record (orc_grid_cell states the rule).  The grids are half and
+    wholly solid, so that a walk that wrongly starts has something to hit."""
+    import cpuvoxelraycaster_amd as vrc
+    cells = E.grid_cells(shape, density, seed=11)
+    org, d = E.grid_origin_non_finite(shape, np.random.default_rng(1))
+    got, ref = grid_pair(vrc, cells, org, d)
+    assert not ref.view(np.uint8).any() and not got.view(np.uint8).any()
+
+
+@pytest.mark.parametrize("density", [0.5, 1.0])
+@pytest.mark.parametrize("shape", [(8, 8, 8), (3, 5, 7)])
+def test_grid_direction_edges(built, shape, density):
+    """NaN, +-inf, (0, 0, 0), (-0, -0, -0), denormals, +-2^-126 and +-2^127 as direction components"""
+    import cpuvoxelraycaster_amd as vrc
+    cells = E.grid_cells(shape, density, seed=12)
+    org, d = E.grid_direction_edges(shape, np.random.default_rng(2))
+    got, ref = grid_pair(vrc, cells, org, d)
+    assert (ref["hit"] != 0).any()
+
+
+@pytest.mark.parametrize("density", [0.5, 1.0])
+@pytest.mark.parametrize("shape", [(8, 8, 8), (3, 5, 7)])
+def test_grid_origins_at_and_beyond_the_boundary(built, shape, density):
+    """On every integer plane (0 and X, Y, Z included); in (-1, 0), which truncates to cell 0 and so walks; in [X, X + 1)
+    and one cell outside each face pointing inwards, which the reference misses (the loop of grid_3d.hpp:70 tests the
+    start cell's indices before anything else)."""
+    import cpuvoxelraycaster_amd as vrc
+    cells = E.grid_cells(shape, density, seed=13)
+    org, d, must_miss = E.grid_boundary_origins(shape, np.random.default_rng(3))
+    got, ref = grid_pair(vrc, cells, org, d)
+    assert must_miss.sum() > 100 and not got["hit"][must_miss].any() and not ref["hit"][must_miss].any()
+    walks = ((org < 0) & (org > -1)).any(1) & ~must_miss                        # from (-1, 0) on some axis
+    assert walks.sum() > 50 and (got["hit"][walks] != 0).any()
+
+
+def test_grid_start_cell_solid(built):
+    """Only the NEW cell is ever tested (grid_3d.hpp:102): in a full grid every ray that reaches a second cell hits it on its
+    first iteration; a lone solid cell is invisible to the rays that start in it."""
+    import cpuvoxelraycaster_amd as vrc
+    shape = (6, 7, 5)
+    rng = np.random.default_rng(4)
+    org, d = E.grid_inside_rays(shape, rng, 4096)
+    got, _ = grid_pair(vrc, np.ones(shape, np.uint8), org, d)
+    hit = got["hit"] != 0
+    assert hit.mean() > 0.5 and (got["complexity"][hit] == 1).all() and (got["complexity"][~hit] == 0).all()
+    cells = np.zeros(shape, np.uint8)
+    cells[2, 3, 1] = 1
+    org = (np.asarray([2, 3, 1], np.float32) + rng.random((4096, 3)).astype(np.float32) * np.float32(0.999)).astype(np.float32)
+    assert (np.trunc(org) == [2, 3, 1]).all()
+    got, _ = grid_pair(vrc, cells, org, d)
+    assert not got["hit"].any()
+    org2, d2 = E.grid_inside_rays(shape, rng, 4096)                  # ... and visible to rays from elsewhere
+    got, _ = grid_pair(vrc, cells, org2, d2)
+    assert (got["node"][got["hit"] != 0] == (2 * 7 + 3) * 5 + 1).all() and (got["hit"] != 0).any()
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 1), (1, 37, 1), (37, 1, 1), (1, 1, 37), (3, 5, 7)])
+@pytest.mark.parametrize("density", [0.0, 0.5, 1.0])
+def test_grid_degenerate_shapes(built, shape, density):
+    import cpuvoxelraycaster_amd as vrc
+    rng = np.random.default_rng(5)
+    cells = E.grid_cells(shape, density, seed=14) if density else np.zeros(shape, np.uint8)
+    org, d = E.grid_inside_rays(shape, rng, 2048)
+    o2, d2, _ = E.grid_boundary_origins(shape, rng)
+    got, ref = grid_pair(vrc, cells, np.concatenate([org, o2]), np.concatenate([d, d2]))
+    if density == 0.0 or shape == (1, 1, 1):
+        assert not got["hit"].any()                                 # a single cell is a start cell only
+    else:
+        assert (got["hit"] != 0).any()
+
+
+def test_grid_iteration_cap(built):
+    """The loop of grid_3d.hpp:70 runs while iter < 2048, and iteration i of a ray along +z from cell 0 tests cell i: a solid
+    cell 2048 is hit on the last iteration the cap allows (complexity 2048), cell 2049 is never tested."""
+    import cpuvoxelraycaster_amd as vrc
+    f = np.float32
+    org = np.asarray([[0.5, 0.5, 0.5], [0.25, 0.75, 0.0], [0.5, 0.5, 0.999]], f)
+    d = np.asarray([[0, 0, 1], [0, 0, 2.5], [0, 0, 1e-3]], f)
+    for z, hits in ((2047, True), (2048, True), (2049, False), (4095, False)):
+        cells = np.zeros((1, 1, 4096), np.uint8)
+        cells[0, 0, z] = 1
+        got, ref = grid_pair(vrc, cells, org, d)
+        if hits:
+            assert (got["hit"] == (1 | (2 << 8))).all() and (got["complexity"] == z).all() and (got["node"] == z).all()
+            assert got["position"][0, 2] == f(z)
+        else:
+            assert not got.view(np.uint8).any()
+    # from the far end towards -z the same count holds: cell 4095 - i on iteration i
+    cells = np.zeros((1, 1, 4096), np.uint8)
+    cells[0, 0, 4095 - 2048] = cells[0, 0, 0] = 1
+    got, _ = grid_pair(vrc, cells, np.asarray([[0.5, 0.5, 4095.5]], f), np.asarray([[0, 0, -1]], f))
+    assert got["complexity"][0] == 2048 and got["node"][0] == 4095 - 2048
+    cells[0, 0, 4095 - 2048] = 0
+    got, _ = grid_pair(vrc, cells, np.asarray([[0.5, 0.5, 4095.5]], f), np.asarray([[0, 0, -1]], f))
+    assert not got["hit"].any()
+    # an oblique ray leaves through a side face long before the cap
+    got, _ = grid_pair(vrc, np.ones((1, 1, 4096), np.uint8), np.asarray([[0.75, 0.5, 100.5]], f), np.asarray([[1, 0, 1]], f))
+    assert not got["hit"].any()
+
+
+@pytest.mark.parametrize("n", [0, 1, 257])
+def test_grid_batch_sizes_and_device_memory(built, n):
+    """n = 0, one ray, one ray more than a workgroup; VRC_MEM_DEVICE on a created stream gives the bytes of VRC_MEM_HOST"""
+    import ctypes as C
+    import torch
+    import cpuvoxelraycaster_amd as vrc
+    L = vrc.capi.load()
+    shape = (9, 4, 6)
+    cells = E.grid_cells(shape, 0.3, seed=15)
+    org, d = E.grid_inside_rays(shape, np.random.default_rng(6), max(n, 8))
+    org, d = np.ascontiguousarray(org[:n]), np.ascontiguousarray(d[:n])
+    grid = vrc.Grid3D(cells)
+    host = grid.castRays(org, d)
+    assert len(host) == n
+    assert_hits_equal(host, O.grid_cast_rays(cells, org, d))
+    st = C.c_void_p()
+    vrc.capi.check(L.vrc_stream_create(0, C.byref(st)))
+    try:
+        d_org, d_dir = torch.from_numpy(org.reshape(-1)).cuda(), torch.from_numpy(d.reshape(-1)).cuda()
+        d_out = torch.full((max(n, 1) * 48,), 0xAB, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        p = lambda t: C.c_void_p(t.data_ptr())
+        # (n = 0 with valid pointers: nothing is launched, nothing written)
+        vrc.capi.check(L.vrc_grid_cast_rays(grid._h, n, p(d_org) if n else p(d_out), p(d_dir) if n else p(d_out), p(d_out),
+                                            vrc.capi.VRC_MEM_DEVICE, st))
+        vrc.capi.check(L.vrc_stream_synchronize(0, st))
+        back = d_out.cpu().numpy()
+        if n:
+            assert back.tobytes() == host.tobytes()
+        else:
+            assert (back == 0xAB).all()
+    finally:
+        vrc.capi.check(L.vrc_stream_destroy(0, st))
+
+
+def test_grid_argument_checks(built):
+    """null grid, null buffers, a bad `mem`, X <= 0: VRC_ERR_INVALID before anything is launched; the next valid call works"""
+    import ctypes as C
+    import cpuvoxelraycaster_amd as vrc
+    L = vrc.capi.load()
+    ptr = vrc.capi.ptr
+    shape = (4, 3, 5)
+    cells = E.grid_cells(shape, 0.5, seed=16)
+    org, d = E.grid_inside_rays(shape, np.random.default_rng(7), 64)
+    out = np.zeros(64, vrc.HIT_DTYPE)
+    h = C.c_void_p()
+    for X, Y, Z in ((0, 3, 5), (4, 0, 5), (4, 3, 0), (-1, 3, 5), (4, -3, 5), (4, 3, -2 ** 31)):
+        assert L.vrc_grid_create(ptr(cells), X, Y, Z, 0, C.byref(h)) == -1 and not h
+    assert L.vrc_grid_create(None, 4, 3, 5, 0, C.byref(h)) == -1
+    assert L.vrc_grid_create(ptr(cells), 4, 3, 5, 0, None) == -1
+    assert b"vrc_grid_create" in L.vrc_last_error()
+    grid = vrc.Grid3D(cells)
+    HOST = vrc.capi.VRC_MEM_HOST
+    assert L.vrc_grid_cast_rays(None, 64, ptr(org), ptr(d), ptr(out), HOST, None) == -1
+    assert L.vrc_grid_cast_rays(grid._h, 64, None, ptr(d), ptr(out), HOST, None) == -1
+    assert L.vrc_grid_cast_rays(grid._h, 64, ptr(org), None, ptr(out), HOST, None) == -1
+    assert L.vrc_grid_cast_rays(grid._h, 64, ptr(org), ptr(d), None, HOST, None) == -1
+    for mem in (2, -1, 7):
+        assert L.vrc_grid_cast_rays(grid._h, 64, ptr(org), ptr(d), ptr(out), mem, None) == -1
+        assert b"mem" in L.vrc_last_error()
+    assert not out.view(np.uint8).any()
+    assert L.vrc_grid_cast_rays(grid._h, 0, None, None, None, HOST, None) == 0        # no rays: nothing to read or write
+    assert L.vrc_grid_cast_rays(grid._h, 64, ptr(org), ptr(d), ptr(out), HOST, None) == 0
+    assert_hits_equal(out, O.grid_cast_rays(cells, org, d))
+    assert (out["hit"] != 0).any()

@@ -319,3 +319,33 @@ def test_frame_on_the_references_own_swarm_pool(heights, textures):
     assert not acc[ch:].any() and not acc[:, cw:].any()
     assert (acc[:ch, :cw, 3] == 6).all()
     assert 0 < rays <= orays and 0 < steps <= osteps
+
+
+def test_grid_start_cell_conversion_rule():
+    """grid_3d.hpp:58-60 `(int)position.x` is undefined in C for NaN and outside [-2^31, 2^31); the reference as shipped
+    (x86-64) yields INT_MIN for all of them, so such a ray starts nowhere: a miss with a zero record.  orc_grid_cell states
+    that rule instead of leaving it to a compiler; the kernel follows the same one (tests/test_gpu_grid.py)."""
+    import ctypes as C
+    L = O.lib()
+    L.orc_grid_cell.restype = C.c_int32
+    L.orc_grid_cell.argtypes = [C.c_float]
+    INT_MIN = -2 ** 31
+    f = np.float32
+    for v, cell in ((np.nan, INT_MIN), (-np.nan, INT_MIN), (np.inf, INT_MIN), (-np.inf, INT_MIN), (2.0 ** 31, INT_MIN),
+                    (-2.0 ** 31, INT_MIN), (3e9, INT_MIN), (-3e9, INT_MIN), (np.finfo(f).max, INT_MIN),
+                    (2.0 ** 31 - 128, 2 ** 31 - 128), (-2.0 ** 31 + 128, -2 ** 31 + 128),
+                    (-0.5, 0), (-0.0, 0), (-0.999, 0), (-1.0, -1), (-1.5, -1), (0.0, 0), (0.999, 0), (7.5, 7), (8.0, 8)):
+        assert L.orc_grid_cell(f(v)) == cell, v
+    # through the cast: a solid 8^3 grid, direction +x
+    cells = np.ones((8, 8, 8), np.uint8)
+    d = np.asarray([1.0, 0.0, 0.0], f)
+    for v in (np.nan, np.inf, -np.inf, 2.0 ** 31, -2.0 ** 31, 3e9, 2.0 ** 31 - 128):
+        for a in range(3):
+            org = np.asarray([3.5, 3.5, 3.5], f)
+            org[a] = v
+            assert not O.grid_cast_rays(cells, org[None], d[None]).view(np.uint8).any(), (v, a)
+        assert not O.grid_cast_rays(cells, np.full((1, 3), v, f), d[None]).view(np.uint8).any(), v
+    # -0.5 truncates to cell 0 and so walks: the first new cell, x = 1, is the hit
+    h = O.grid_cast_rays(cells, np.asarray([[-0.5, 3.5, 3.5]], f), d[None])[0]
+    assert (h["hit"], h["node"], h["complexity"], h["distance"]) == (1, (1 * 8 + 3) * 8 + 3, 1, 1.5)
+    assert h["position"].tolist() == [1.0, 3.5, 3.5] and h["normal"].tolist() == [-1.0, 0.0, 0.0]

@@ -12,6 +12,44 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 
 
+def fuzz_chains(args):
+    """Chains of two casts against two casts of the oracle: every kind of ray B of edge_cases.CHAIN_KINDS on one scene per
+    case -- a carved random volume of 2..7 levels or the terrain at 7..9.  Reads tests/golden only."""
+    import cpuvoxelraycaster_amd as vrc
+    import edge_cases as E
+    import oracle_lib as O
+    heights = O.load_terrain_heights()
+    f = np.float32
+    t0 = time.time()
+    it = bad = chains = 0
+    while time.time() - t0 < args.seconds:
+        rng = np.random.default_rng(args.seed * 100003 + it)
+        it += 1
+        if rng.integers(0, 4) == 0:
+            depth = int(rng.integers(7, 10))
+            nodes = vrc.build_terrain_lsvo(heights, depth)
+            light = np.asarray(vrc.reference_light(depth), f)
+            cam = (np.asarray(vrc.reference_camera(depth).position, f) * (f(1.0) / f(1 << depth)) + f(1.0)).astype(f)
+        else:
+            depth = int(rng.integers(2, 8))
+            nodes = O.compile_voxels(depth, np.argwhere(E.carved_volume(depth, rng)).astype(np.int64))
+            light = rng.uniform(1.0, 2.0, 3).astype(f) if rng.integers(0, 2) else np.asarray([1.3, 1.9, 1.6], f)
+            cam = rng.uniform(1.05, 1.95, 3).astype(f)
+        svo = vrc.LSVO(nodes, depth)
+        cast_oracle = lambda o, d, coef: O.cast_rays(nodes, depth, o, d, coef, 0.0, threads=16)
+        for kind in E.CHAIN_KINDS:
+            org_a, dir_a = E.chain_rays_a(depth, max(args.rays, 1), rng, None, cam)
+            try:
+                st = E.check_chains(E.gpu_chain_caster(svo), cast_oracle, depth, kind, org_a, dir_a, light, rng)
+                chains += st["n"] * len(E.CHAIN_COEFS)
+            except AssertionError as e:
+                print("CHAIN MISMATCH", dict(seed=args.seed, case=it, depth=depth, kind=kind, rays=args.rays), str(e)[:2000])
+                bad += 1
+        svo.close()
+    print(f"fuzz --chains: {it} scenes, {chains} chains compared on whole batches, {bad} mismatches, {time.time() - t0:.0f} s")
+    return 1 if bad else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=300)
@@ -22,7 +60,13 @@ def main():
     ap.add_argument("--depth10", type=float, default=0.0,
                     help="probability that a steered terrain case runs on the 1024^3 tree (10 levels, BASELINE config 5's: the deepest stack "
                          "the frame kernels are built for; generated once and kept) instead of 256^3 / 512^3 -- no draw at 0: old seeds replay")
+    ap.add_argument("--chains", action="store_true",
+                    help="vrc_cast_ray_chains instead of frames and single casts: the generator and the checks of tests/test_gpu_chains.py "
+                         "(edge_cases.check_chains) on random volumes and the terrain, --rays chains per case, until --seconds are over")
+    ap.add_argument("--rays", type=int, default=50000, help="chains per case of --chains")
     args = ap.parse_args()
+    if args.chains:
+        sys.exit(fuzz_chains(args))
     deep = {}                                                    # the 1024^3 terrain and its 324 MB of nodes on the host, made once
     import collections
     kernels = collections.Counter()
