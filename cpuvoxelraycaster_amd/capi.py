@@ -122,6 +122,17 @@ SYMBOLS = {
     "vrc_stream_create": (_int, [_int, C.POINTER(_vp)]),
     "vrc_stream_destroy": (_int, [_int, _vp]),
     "vrc_stream_synchronize": (_int, [_int, _vp]),
+    "vrc_volume_create": (_int, [_u32, _int, C.POINTER(_vp)]),
+    "vrc_volume_from_scene": (_int, [_vp, C.POINTER(_vp)]),
+    "vrc_volume_destroy": (_int, [_vp]),
+    "vrc_volume_depth": (_u32, [_vp]),
+    "vrc_volume_set_voxels": (_int, [_vp, _u64, _vp, _int, _int, _vp]),
+    "vrc_volume_fill_boxes": (_int, [_vp, _u64, _vp, _int, _int, _vp]),
+    "vrc_volume_commit": (_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_float)]),
+    "vrc_volume_download": (_int, [_vp, _vp]),
+    "vrc_volume_solid_count": (_int, [_vp, C.POINTER(_u64)]),
+    "vrc_renderer_set_scene": (_int, [_vp, _vp]),
+    "vrc_hit_to_voxel": (_int, [_u32, _vp, _vp, _vp, C.POINTER(_int)]),
 }
 
 _lib = None

@@ -93,6 +93,7 @@ struct vrc_grid {
 struct vrc_renderer {
     const vrc_scene* scene = nullptr;   // must outlive every vrc_render_frame call; the other calls only need r->device
     int device = 0;
+    uint32_t depth = 0;                 // of the scene it was created for; vrc_renderer_set_scene takes scenes of this depth
     uint32_t width = 0, height = 0;
     void* d_image = nullptr;  // RGBA8
     void* image_target = nullptr;   // where sharded frames are resolved to instead of d_image (vrc_renderer_set_image_target): a peer's framebuffer
@@ -486,7 +487,7 @@ extern "C" int vrc_renderer_create(const vrc_scene* s, uint32_t width, uint32_t 
     HIP_TRY(hipSetDevice(s->device));
     vrc_renderer* r = new (std::nothrow) vrc_renderer();
     if (!r) return fail(VRC_ERR_OOM, "out of host memory");
-    r->scene = s; r->device = s->device; r->width = width; r->height = height;
+    r->scene = s; r->device = s->device; r->depth = s->depth; r->width = width; r->height = height;
     { std::lock_guard<std::mutex> lk(g_tuning_mu); r->tuning = g_tuning; }
     const uint64_t n = (uint64_t)width * height;
     hipError_t e = hipMalloc(&r->d_image, n * 4);
@@ -527,6 +528,46 @@ extern "C" int vrc_renderer_destroy(vrc_renderer* r)
 void vrc::renderer_info(const vrc_renderer* r, int* device, uint32_t* width, uint32_t* height)
 {
     *device = r->device; *width = r->width; *height = r->height;
+}
+
+// The rebind RayCaster's `const LSVO& svo` (raycaster.hpp:265) has no way to do: the next frame walks another scene.
+// Everything else the renderer owns is independent of the scene (the frame kernels get nodes / tex / depth per launch).
+extern "C" int vrc_renderer_set_scene(vrc_renderer* r, const vrc_scene* s)
+{
+    if (!r || !s) return fail(VRC_ERR_INVALID, "vrc_renderer_set_scene: null argument");
+    if (s->device != r->device) return fail(VRC_ERR_INVALID, "vrc_renderer_set_scene: the scene lives on device %d, the renderer on %d", s->device, r->device);
+    if (s->depth != r->depth) return fail(VRC_ERR_INVALID, "vrc_renderer_set_scene: depth %u != the renderer's %u", s->depth, r->depth);
+    r->scene = s;
+    return VRC_OK;
+}
+
+// Host arithmetic only.  position is in [1, 2)^3 and strictly inside the hit cell (lsvo.hpp:156-158), so (p - 1) * S
+// is exact in float and its floor is the cell the WALK saw; the walk sees the scene point-reflected through the cube
+// centre (child_shift = child_offset ^ mirror_mask, lsvo.hpp:79), hence S-1 - cell in setCell
+// coordinates.  The normal points out of the hit face in walk space, i.e. towards -normal in setCell space.
+extern "C" int vrc_hit_to_voxel(uint32_t depth, const vrc_hit* hit, uint32_t voxel[3], uint32_t neighbour[3], int* has_neighbour)
+{
+    if (!hit || !voxel) return fail(VRC_ERR_INVALID, "vrc_hit_to_voxel: null argument");
+    if (depth < 2 || depth > VRC_MAX_DEPTH) return fail(VRC_ERR_INVALID, "vrc_hit_to_voxel: depth %u not in [2,%d]", depth, VRC_MAX_DEPTH);
+    if ((hit->hit & 0xffu) != 1u) return fail(VRC_ERR_INVALID, "vrc_hit_to_voxel: not a unit-voxel hit (kind %u: 0 = miss, 2 = LOD cut-off)", hit->hit & 0xffu);
+    const float S = (float)(1u << depth);
+    int32_t cell[3];
+    for (int a = 0; a < 3; ++a) {
+        const float f = std::floor((hit->position[a] - 1.0f) * S);
+        if (!(f >= 0.0f && f < S)) return fail(VRC_ERR_INVALID, "vrc_hit_to_voxel: position outside [1,2)^3");
+        cell[a] = (int32_t)(1u << depth) - 1 - (int32_t)f;
+        voxel[a] = (uint32_t)cell[a];
+    }
+    int axis = -1, axes = 0;
+    for (int a = 0; a < 3; ++a) if (hit->normal[a] != 0.0f) { axis = a; ++axes; }
+    int has = 0;
+    if (axes == 1) {
+        cell[axis] -= hit->normal[axis] > 0.0f ? 1 : -1;
+        has = cell[axis] >= 0 && cell[axis] < (int32_t)(1u << depth);
+    }
+    if (neighbour) for (int a = 0; a < 3; ++a) neighbour[a] = has ? (uint32_t)cell[a] : 0u;
+    if (has_neighbour) *has_neighbour = has;
+    return VRC_OK;
 }
 
 extern "C" int vrc_renderer_set_primary_capture(vrc_renderer* r, vrc_hit* prim_dev)

@@ -7,6 +7,9 @@
 //                              setLightPosition, renderRay's per-frame batch
 //                              (renderFrame), samples_to_image, resetSamples,
 //                              public flags use_gi / use_samples, render_image
+//   vrc_host::HipVoxelVolume<- the write half of Volumetric (setCell, volumetric.hpp:59):
+//                              batched edits of a device-resident occupancy, commit()
+//                              builds a new HipLSVO, HipRayCaster::setScene shows it
 //
 // Header-only, C++14, no GLM / SFML needed.  When the reference's own headers
 // are on the include path, define VRC_WITH_REFERENCE_HEADERS before including
@@ -169,8 +172,73 @@ private:
         p.complexity = h.complexity;
         return p;
     }
+    friend class HipVoxelVolume;
     explicit HipLSVO(vrc_scene* adopted) : scene_(adopted) {}
     vrc_scene* scene_ = nullptr;
+};
+
+// What SVO::setCell + compileSVO are to the reference (svo.hpp:72, lsvo_utils.cpp:4), on the device and repeatable: the
+// occupancy of the S^3 volume stays resident, setCell() queues edits, commit() applies them and builds a NEW HipLSVO
+// (bit-identical to compileSVO of the voxel set).  A scene in use is never touched: keep the old HipLSVO until the frames
+// that walk it are done, then drop it.  Not re-entrant.  INTEGRATION.md section 2a.
+class HipVoxelVolume {
+public:
+    explicit HipVoxelVolume(uint32_t depth, int device = 0) { check(vrc_volume_create(depth, device, &v_), "vrc_volume_create"); }
+    // makes an existing scene (e.g. HipLSVO::fromFastNoiseTerrain) editable; takes over its albedo tables
+    static std::unique_ptr<HipVoxelVolume> fromScene(const HipLSVO& svo)
+    {
+        vrc_volume* v = nullptr;
+        check(vrc_volume_from_scene(svo.handle(), &v), "vrc_volume_from_scene");
+        return std::unique_ptr<HipVoxelVolume>(new HipVoxelVolume(v));
+    }
+    ~HipVoxelVolume() { vrc_volume_destroy(v_); }
+    HipVoxelVolume(const HipVoxelVolume&) = delete;
+    HipVoxelVolume& operator=(const HipVoxelVolume&) = delete;
+
+    // Volumetric::setCell (volumetric.hpp:59): Empty clears, every other type sets (the tree has one cell kind,
+    // lsvo.hpp:21-23).  Queued on the host; flush() / commit() send the queue as batches.
+    void setCell(Cell::Type type, Cell::Texture, uint32_t x, uint32_t y, uint32_t z)
+    {
+        const bool solid = type != Cell::Empty;
+        if (!queue_.empty() && solid != queue_solid_) flush();   // a batch carries one value; order between values is kept
+        queue_solid_ = solid;
+        queue_.push_back(x); queue_.push_back(y); queue_.push_back(z);
+    }
+    // [lo, hi) per axis, clipped to the volume
+    void fillBox(uint32_t x0, uint32_t y0, uint32_t z0, uint32_t x1, uint32_t y1, uint32_t z1, bool solid)
+    {
+        flush();
+        const uint32_t box[6] = {x0, y0, z0, x1, y1, z1};
+        check(vrc_volume_fill_boxes(v_, 1, box, solid ? 1 : 0, VRC_MEM_HOST, nullptr), "vrc_volume_fill_boxes");
+    }
+    void flush()
+    {
+        if (queue_.empty()) return;
+        check(vrc_volume_set_voxels(v_, queue_.size() / 3, queue_.data(), queue_solid_ ? 1 : 0, VRC_MEM_HOST, nullptr), "vrc_volume_set_voxels");
+        queue_.clear();
+    }
+    std::unique_ptr<HipLSVO> commit(float* build_ms = nullptr)
+    {
+        flush();
+        vrc_scene* s = nullptr;
+        check(vrc_volume_commit(v_, &s, build_ms), "vrc_volume_commit");
+        return std::unique_ptr<HipLSVO>(new HipLSVO(s));
+    }
+    uint64_t solidCount()
+    {
+        flush();
+        uint64_t n = 0;
+        check(vrc_volume_solid_count(v_, &n), "vrc_volume_solid_count");
+        return n;
+    }
+    uint32_t depth() const { return vrc_volume_depth(v_); }
+    vrc_volume* handle() const { return v_; }
+
+private:
+    explicit HipVoxelVolume(vrc_volume* adopted) : v_(adopted) {}
+    vrc_volume* v_ = nullptr;
+    std::vector<uint32_t> queue_;
+    bool queue_solid_ = true;
 };
 
 // Camera values Camera::getRay reads (camera_controller.hpp:16-49); the Camera /
@@ -202,6 +270,9 @@ public:
     HipRayCaster& operator=(const HipRayCaster&) = delete;
 
     void setLightPosition(const Vec3& position) { light_ = position; }   // raycaster.hpp:62
+    // the rebind `const LSVO<N>& svo` (raycaster.hpp:265) cannot do: the following frames walk `svo` (same depth, same
+    // device, e.g. HipVoxelVolume::commit()'s); image, accumulators and counters are kept
+    void setScene(const HipLSVO& svo) { check(vrc_renderer_set_scene(r_, svo.handle()), "vrc_renderer_set_scene"); }
 
     // One frame: Camera::getRay + renderRay for every selected pixel (main.cpp:139-152).
     // checker_board_offset = -1 renders every pixel; 0 / 1 as main.cpp:137,143.

@@ -6,6 +6,7 @@ over the C ABI (include/vrc.h).  Names follow the reference:
   RayCaster.renderFrame        <- the swarm lambda: getRay + renderRay per pixel (src/main.cpp:139-152)
   RayCaster.samples_to_image   <- raycaster.hpp:94
   RayCaster.resetSamples       <- raycaster.hpp:105
+  VoxelVolume.setVoxels        <- Volumetric::setCell       (include/volumetric.hpp:59), batched; commit() -> a new LSVO
   Presenter.present            <- the SFML blend / upscale chain after the frame (src/main.cpp:160-182)
 
 All compute runs in the HIP kernels of libvrc_hip.so; numpy / torch are only
@@ -132,6 +133,83 @@ class LSVO:
             pass
 
 
+def hit_to_voxel(depth, hit):
+    """The voxel a castRay record hit, in setCell coordinates, and the empty cell the ray came through (None when there is
+    none): ((x, y, z), (x, y, z) | None).  Host arithmetic (include/vrc.h: vrc_hit_to_voxel); raises for a miss / LOD cut-off."""
+    rec = np.zeros(1, HIT_DTYPE)
+    rec[0] = hit
+    voxel, neighbour, has = np.zeros(3, np.uint32), np.zeros(3, np.uint32), C.c_int()
+    check(capi.load().vrc_hit_to_voxel(depth, ptr(rec), ptr(voxel), ptr(neighbour), C.byref(has)))
+    return tuple(int(v) for v in voxel), (tuple(int(v) for v in neighbour) if has.value else None)
+
+
+class VoxelVolume:
+    """Device-resident editable occupancy of an S^3 volume (include/vrc.h: vrc_volume_*).  Edits are batched; commit()
+    builds a new immutable LSVO on the device, bit-identical to compileSVO of the current voxel set."""
+
+    def __init__(self, depth, device=0):
+        self._h = C.c_void_p()
+        check(capi.load().vrc_volume_create(depth, device, C.byref(self._h)))
+        self.depth, self.device = depth, device
+
+    @classmethod
+    def fromScene(cls, svo):
+        """Rasterise a resident scene (e.g. LSVO.fromFastNoiseTerrain) into a volume; takes over its albedo tables."""
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        check(capi.load().vrc_volume_from_scene(svo._h, C.byref(self._h)))
+        self.depth, self.device = svo.depth, svo.device
+        return self
+
+    def setVoxels(self, xyz, solid=True):
+        """xyz: (n, 3) voxel coordinates, all set or all cleared; out-of-volume ones are dropped.  Synchronous."""
+        xyz = np.ascontiguousarray(xyz, np.uint32).reshape(-1, 3)
+        check(capi.load().vrc_volume_set_voxels(self._h, xyz.shape[0], ptr(xyz), int(bool(solid)), capi.VRC_MEM_HOST, None))
+
+    def setVoxelsDevice(self, n, xyz_ptr, solid=True, stream=None):
+        """the same over n x 3 uint32 in device memory, asynchronous on `stream`"""
+        check(capi.load().vrc_volume_set_voxels(self._h, n, ptr(xyz_ptr), int(bool(solid)), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def fillBoxes(self, lo_hi, solid=True):
+        """lo_hi: (n, 6) = lo x y z (inclusive), hi x y z (exclusive); clipped to the volume.  Synchronous."""
+        lo_hi = np.ascontiguousarray(lo_hi, np.uint32).reshape(-1, 6)
+        check(capi.load().vrc_volume_fill_boxes(self._h, lo_hi.shape[0], ptr(lo_hi), int(bool(solid)), capi.VRC_MEM_HOST, None))
+
+    def fillBoxesDevice(self, n, lo_hi_ptr, solid=True, stream=None):
+        check(capi.load().vrc_volume_fill_boxes(self._h, n, ptr(lo_hi_ptr), int(bool(solid)), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def commit(self, textures=None):
+        """A NEW LSVO of the current occupancy (build_ms = device time of the sweeps); the volume stays editable."""
+        handle, ms = C.c_void_p(), C.c_float()
+        check(capi.load().vrc_volume_commit(self._h, C.byref(handle), C.byref(ms)))
+        svo = LSVO._from_handle(handle, self.depth, self.device, textures)
+        svo.build_ms = ms.value
+        return svo
+
+    def download(self):
+        """dense uint8 [x, y, z] occupancy (0 / 1)"""
+        size = 1 << self.depth
+        out = np.zeros((size, size, size), np.uint8)
+        check(capi.load().vrc_volume_download(self._h, ptr(out)))
+        return out
+
+    def solidCount(self):
+        n = C.c_uint64()
+        check(capi.load().vrc_volume_solid_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            capi.load().vrc_volume_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Grid3D:
     """Dense grid (grid_3d.hpp); cells[x, y, z] = Cell::Type (0 = Empty)."""
 
@@ -187,6 +265,11 @@ class RayCaster:
 
     def setLightPosition(self, position):
         self.light_position = tuple(float(v) for v in position)
+
+    def setScene(self, svo):
+        """The following frames walk `svo` (same depth, same device); image, accumulators and counters are kept."""
+        check(capi.load().vrc_renderer_set_scene(self._h, svo._h))
+        self.svo = svo
 
     def params(self, spp=1, checker_parity=-1, row_block=0, shard_index=0, shard_count=1):
         p = FrameParams()

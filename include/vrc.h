@@ -13,7 +13,10 @@
  *
  * Threading: a vrc_scene is immutable after creation and may be shared by
  * any number of renderers / threads (the reference calls castRay concurrently
- * from 16 workers, main.cpp:139-152).  A vrc_renderer is not re-entrant.
+ * from 16 workers, main.cpp:139-152).  A vrc_renderer is not re-entrant.  A
+ * vrc_volume (the editable occupancy scenes are committed from) is not
+ * re-entrant either: one thread at a time edits or commits it; the scenes it
+ * has committed are ordinary immutable scenes.
  *
  * Streams: `stream` arguments are hipStream_t handles passed as void*
  * (NULL = the default stream).  Calls taking a stream are asynchronous on it
@@ -72,6 +75,7 @@ typedef struct vrc_hit {
 typedef struct vrc_scene vrc_scene;        /* device-resident LSVO + albedo tables */
 typedef struct vrc_grid vrc_grid;          /* device-resident dense Grid3D */
 typedef struct vrc_renderer vrc_renderer;  /* RayCaster state: framebuffer + sample accumulators */
+typedef struct vrc_volume vrc_volume;      /* device-resident editable occupancy of an S^3 volume */
 
 const char *vrc_last_error(void);
 int vrc_device_count(void);                /* >= 0, or VRC_ERR_NO_DEVICE */
@@ -155,6 +159,48 @@ int vrc_cast_ray_chains(const vrc_scene *s, uint64_t n,
 int vrc_cast_ray(const vrc_scene *s, const float org[3], const float dir[3],
                  float ray_size_coef, float ray_size_bias, vrc_hit *out);
 
+/* ---- editable volume: Volumetric::setCell (volumetric.hpp:59; empty in LSVO, lsvo.hpp:26) ---- */
+
+/* A scene is never patched in place: frames in flight keep reading it.  What is edited is a vrc_volume, the occupancy
+ * of an S^3 volume (S = 1 << depth, depth 2..10 as for the GPU builder) resident on one device -- one byte per
+ * 2 x 2 x 2 brick, 16 MiB at 512^3, 128 MiB at 1024^3 -- and vrc_volume_commit builds a NEW scene from it with the
+ * builder's sweeps, bit-identical to compileSVO of the current voxel set.  Coordinates are SVO::setCell's
+ * (svo.hpp:72), the ones vrc_build_volume_lsvo's solid[(x*S + y)*S + z] uses. */
+int vrc_volume_create(uint32_t depth, int device, vrc_volume **out);      /* empty; albedo tables white */
+/* Rasterises a resident scene's LNode[] into a new volume on the scene's device (this is what makes a scene that was
+ * generated on the device editable) and copies its albedo tables.  A leaf above the unit-voxel level is solid throughout. */
+int vrc_volume_from_scene(const vrc_scene *s, vrc_volume **out);
+int vrc_volume_destroy(vrc_volume *v);
+uint32_t vrc_volume_depth(const vrc_volume *v);
+/* n voxels (n x 3 uint32: x, y, z), ALL set (solid != 0) or ALL cleared: one value per call, so the result does not
+ * depend on the order in which the device applies them; duplicates are legal, coordinates outside the volume are
+ * dropped (the rule for setCell).  `mem` as in vrc_cast_rays: VRC_MEM_HOST = staged,
+ * synchronous; VRC_MEM_DEVICE = read in place, asynchronous on `stream`.  Successive calls are ordered by stream
+ * order -- issue a volume's asynchronous edits on ONE stream (or order the streams yourself). */
+int vrc_volume_set_voxels(vrc_volume *v, uint64_t n, const uint32_t *xyz, int solid, int mem, void *stream);
+/* n axis-aligned boxes (n x 6 uint32: lo x y z inclusive, hi x y z exclusive), clipped to the volume; empty boxes are
+ * legal.  Cost follows the bricks inside the boxes (whole 32-bit words of bricks are stored as such), not the bounding
+ * volume of all of them. */
+int vrc_volume_fill_boxes(vrc_volume *v, uint64_t n, const uint32_t *lo_hi, int solid, int mem, void *stream);
+/* Builds a new scene from the current occupancy (after every edit issued so far, whatever its stream).  Synchronous.
+ * The volume stays valid and editable; scenes committed earlier are untouched and belong to the caller, who destroys
+ * them (vrc_scene_destroy) once no frame uses them any more.  The new scene carries the volume's albedo tables.
+ * *build_ms (optional) as for vrc_scene_build_volume.  The volume keeps the builder's per-level grids between commits
+ * (12 bytes per cell of every level: 1.8 GiB at depth 10, 230 MiB at depth 9), allocated by the first commit. */
+int vrc_volume_commit(vrc_volume *v, vrc_scene **out, float *build_ms);
+/* Dense copy for the host, solid_host[(x*S + y)*S + z] = 0 / 1 (S^3 bytes, the layout of vrc_build_volume_lsvo), and
+ * the number of solid voxels.  Synchronous, after every edit issued so far. */
+int vrc_volume_download(vrc_volume *v, uint8_t *solid_host);
+int vrc_volume_solid_count(vrc_volume *v, uint64_t *count);
+
+/* The voxel a ray hit, for "dig / build at the crosshair": pure host arithmetic, no device.  For a unit-voxel hit
+ * (hit->hit & 0xff == 1) voxel[] = the solid voxel in setCell coordinates (S-1 - floor((position - 1) * S) per axis:
+ * the walk sees the scene point-reflected) and, when exactly one component of the normal is
+ * non-zero, neighbour[] = voxel - sign(normal): the empty cell the ray came through -- *has_neighbour = 0 (and
+ * neighbour zeroed) when that cell lies outside the volume or the normal is zero (a ray that started inside a solid
+ * voxel).  neighbour / has_neighbour may be NULL.  A miss or an LOD cut-off is VRC_ERR_INVALID. */
+int vrc_hit_to_voxel(uint32_t depth, const vrc_hit *hit, uint32_t voxel[3], uint32_t neighbour[3], int *has_neighbour);
+
 /* ---- dense grid: Grid3D<X,Y,Z> (grid_3d.hpp:10-138) ------------------- */
 
 /* cells[(x*Y + y)*Z + z] = Cell::Type (0 = Empty). */
@@ -221,6 +267,10 @@ int vrc_stream_synchronize(int device, void *stream);   /* blocks the calling th
  * process-wide scheduling defaults (vrc_set_*) at creation. */
 int vrc_renderer_create(const vrc_scene *s, uint32_t width, uint32_t height, vrc_renderer **out);
 int vrc_renderer_destroy(vrc_renderer *r);
+/* Points the renderer at another scene of the same depth on the same device (e.g. the one vrc_volume_commit just
+ * built), between its frames: frames already enqueued keep the scene they were enqueued with, so the old scene must
+ * live until they are done.  Image, accumulators, counters and every setting are kept. */
+int vrc_renderer_set_scene(vrc_renderer *r, const vrc_scene *s);
 
 /* One frame = what the swarm lambda does (main.cpp:139-152): for every selected
  * pixel, Camera::getRay + RayCaster::renderRay, `spp` times.  Adds to the
