@@ -179,7 +179,7 @@ extern "C" int vrc_terrain_heights(int32_t seed, uint32_t size, int device, int3
     }
     if (e == hipSuccess) e = hipMemcpy(height_host, d_h, (size_t)size * size * 4, hipMemcpyDeviceToHost);
     (void)hipFree(d_h);
-    if (e != hipSuccess) return vrc::fail(e == hipErrorOutOfMemory ? VRC_ERR_OOM : VRC_ERR_HIP, "vrc_terrain_heights: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return vrc::fail_hip(e, "vrc_terrain_heights");
     return VRC_OK;
 }
 
@@ -197,7 +197,7 @@ extern "C" int vrc_scene_build_fastnoise_terrain(int32_t seed, uint32_t depth, i
     int32_t *d_h = nullptr, *d_lim = nullptr;
     hipError_t e = hipMalloc((void**)&d_h, (size_t)S * S * 4);
     if (e == hipSuccess) e = hipMalloc((void**)&d_lim, (size_t)S * S * 4);
-    if (e != hipSuccess) rc = vrc::fail(e == hipErrorOutOfMemory ? VRC_ERR_OOM : VRC_ERR_HIP, "vrc_scene_build_fastnoise_terrain: %s", hipGetErrorString(e));
+    if (e != hipSuccess) rc = vrc::fail_hip(e, "vrc_scene_build_fastnoise_terrain");
     else rc = build_on_device(TerrainVox{d_lim, S}, depth, device, cus, out, build_ms, [&]() {
         // inside the timed region: *build_ms covers noise -> heights -> column limits -> LSVO
         hipLaunchKernelGGL(k_terrain_heights, grid_for((uint64_t)S * S), dim3(256), 0, nullptr, tab, S, d_h);
@@ -221,7 +221,7 @@ extern "C" int vrc_scene_build_terrain(const int32_t* height, uint32_t depth, in
     hipError_t e = hipMalloc((void**)&d_h, (size_t)S * S * 4);
     if (e == hipSuccess) e = hipMalloc((void**)&d_lim, (size_t)S * S * 4);
     if (e == hipSuccess) e = hipMemcpy(d_h, height, (size_t)S * S * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = vrc::fail(e == hipErrorOutOfMemory ? VRC_ERR_OOM : VRC_ERR_HIP, "vrc_scene_build_terrain: %s", hipGetErrorString(e));
+    if (e != hipSuccess) rc = vrc::fail_hip(e, "vrc_scene_build_terrain");
     else rc = build_on_device(TerrainVox{d_lim, S}, depth, device, cus, out, build_ms, [&]() {
         hipLaunchKernelGGL(k_terrain_lim, grid_for((uint64_t)S * S), dim3(256), 0, nullptr, d_h, d_lim, S);
         return hipGetLastError();
@@ -242,7 +242,7 @@ extern "C" int vrc_scene_build_volume(const uint8_t* solid, uint32_t depth, int 
     uint8_t* d_solid = nullptr;
     hipError_t e = hipMalloc((void**)&d_solid, S * S * S);
     if (e == hipSuccess) e = hipMemcpy(d_solid, solid, S * S * S, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = vrc::fail(e == hipErrorOutOfMemory ? VRC_ERR_OOM : VRC_ERR_HIP, "vrc_scene_build_volume: %s", hipGetErrorString(e));
+    if (e != hipSuccess) rc = vrc::fail_hip(e, "vrc_scene_build_volume");
     else rc = build_on_device(VolumeVox{d_solid, (uint32_t)S}, depth, device, cus, out, build_ms, []() { return hipSuccess; });
     (void)hipFree(d_solid);
     return rc;

@@ -19,15 +19,14 @@
 #include <new>
 
 #include "../../include/vrc.h"
-#include "vrc_internal.h"
+#include "vrc_host.h"
 
 namespace {
 
 #define HIP_TRYB(expr)                                                                              \
     do {                                                                                            \
         hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) { rc = vrc::fail(e_ == hipErrorOutOfMemory ? VRC_ERR_OOM : VRC_ERR_HIP, \
-                                               "%s: %s", #expr, hipGetErrorString(e_)); goto done; } \
+        if (e_ != hipSuccess) { rc = vrc::fail_hip(e_, #expr); goto done; }                         \
     } while (0)
 
 // An occupancy source is a functor vox(x, y, z) -> bool in SVO::setCell coordinates.  The sweeps only ever ask for

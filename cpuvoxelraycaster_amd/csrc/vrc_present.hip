@@ -33,7 +33,7 @@
 #include <new>
 
 #include "../../include/vrc.h"
-#include "vrc_internal.h"
+#include "vrc_host.h"
 
 struct vrc_presenter {
     int device = 0;
@@ -47,7 +47,7 @@ namespace {
 #define HIP_TRYP(expr)                                                                              \
     do {                                                                                            \
         hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return vrc::fail(e_ == hipErrorOutOfMemory ? VRC_ERR_OOM : VRC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+        if (e_ != hipSuccess) return vrc::fail_hip(e_, #expr);                                      \
     } while (0)
 
 // round(a * b / 255): a UNORM8 product stored to a UNORM8 target (255 is odd: no ties)
@@ -159,7 +159,7 @@ extern "C" int vrc_presenter_create(int device, uint32_t width, uint32_t height,
     if (e != hipSuccess) {
         (void)hipFree(p->d_denoised); (void)hipFree(p->d_window);
         delete p;
-        return vrc::fail(e == hipErrorOutOfMemory ? VRC_ERR_OOM : VRC_ERR_HIP, "vrc_presenter_create: %s", hipGetErrorString(e));
+        return vrc::fail_hip(e, "vrc_presenter_create");
     }
     *out = p;
     return VRC_OK;

@@ -163,11 +163,6 @@ __global__ void k_count_solid(const uint32_t* __restrict__ words, uint64_t n_wor
     if (threadIdx.x == 0 && part[0]) atomicAdd(total, (unsigned long long)part[0]);
 }
 
-int hip_fail(const char* what, hipError_t e)
-{
-    return vrc::fail(e == hipErrorOutOfMemory ? VRC_ERR_OOM : VRC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
-
 void volume_free(vrc_volume* v)
 {
     if (!v) return;
@@ -196,7 +191,7 @@ int volume_new(uint32_t depth, int device, vrc_volume** out)
     if (e == hipSuccess) e = hipMalloc((void**)&v->d_count, 8);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&v->edit_done, hipEventDisableTiming);
     if (e == hipSuccess) e = hipMemset(v->d_tex, 0xff, 1536);   // sf::Color::White, as a scene without textures
-    if (e != hipSuccess) { volume_free(v); return hip_fail("vrc_volume: allocation", e); }
+    if (e != hipSuccess) { volume_free(v); return vrc::fail_hip(e, "vrc_volume: allocation"); }
     *out = v;
     return VRC_OK;
 }
@@ -215,24 +210,24 @@ template <class Launch>
 int edit(vrc_volume* v, const char* what, uint64_t count, uint32_t words_per_item, const uint32_t* items, int mem, hipStream_t st, Launch launch)
 {
     hipError_t e = hipSetDevice(v->device);
-    if (e != hipSuccess) return hip_fail(what, e);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
     const uint32_t* d_items = items;
     if (mem == VRC_MEM_HOST) {
         const size_t need = (size_t)count * words_per_item * 4u;
         if (v->stage_cap < need) {
             if (v->d_stage) (void)hipFree(v->d_stage);
             v->d_stage = nullptr; v->stage_cap = 0;
-            if ((e = hipMalloc((void**)&v->d_stage, need)) != hipSuccess) return hip_fail(what, e);
+            if ((e = hipMalloc((void**)&v->d_stage, need)) != hipSuccess) return vrc::fail_hip(e, what);
             v->stage_cap = need;
         }
-        if ((e = hipMemcpyAsync(v->d_stage, items, need, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(what, e);
+        if ((e = hipMemcpyAsync(v->d_stage, items, need, hipMemcpyHostToDevice, st)) != hipSuccess) return vrc::fail_hip(e, what);
         d_items = v->d_stage;
     }
     launch(d_items);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(what, e);
+    if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
     if (mem == VRC_MEM_HOST) e = hipStreamSynchronize(st);
     else if (st != nullptr) { e = hipEventRecord(v->edit_done, st); v->edit_pending = true; }
-    if (e != hipSuccess) return hip_fail(what, e);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
     return VRC_OK;
 }
 
@@ -246,7 +241,7 @@ extern "C" int vrc_volume_create(uint32_t depth, int device, vrc_volume** out)
     int rc = volume_new(depth, device, &v);
     if (rc) return rc;
     hipError_t e = hipMemset(v->d_bricks, 0, v->n_bricks);
-    if (e != hipSuccess) { volume_free(v); return hip_fail("vrc_volume_create", e); }
+    if (e != hipSuccess) { volume_free(v); return vrc::fail_hip(e, "vrc_volume_create"); }
     *out = v;
     return VRC_OK;
 }
@@ -262,7 +257,7 @@ extern "C" int vrc_volume_from_scene(const vrc_scene* s, vrc_volume** out)
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(v->d_tex, s->d_tex, 1536, hipMemcpyDeviceToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { volume_free(v); return hip_fail("vrc_volume_from_scene", e); }
+    if (e != hipSuccess) { volume_free(v); return vrc::fail_hip(e, "vrc_volume_from_scene"); }
     *out = v;
     return VRC_OK;
 }
@@ -316,13 +311,13 @@ extern "C" int vrc_volume_commit(vrc_volume* v, vrc_scene** out, float* build_ms
     if (!v || !out) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_commit: null argument");
     hipError_t e = hipSetDevice(v->device);
     if (e == hipSuccess) e = wait_for_edits(v);
-    if (e != hipSuccess) return hip_fail("vrc_volume_commit", e);
+    if (e != hipSuccess) return vrc::fail_hip(e, "vrc_volume_commit");
     vrc_scene* s = nullptr;
     const int rc = build_on_device(BrickVox{(const uint8_t*)v->d_bricks, 1u << (v->depth - 1u)}, v->depth, v->device, v->cu_count, &s, build_ms,
                                    []() { return hipSuccess; }, &v->grids);
     if (rc) return rc;
     e = hipMemcpy(s->d_tex, v->d_tex, 1536, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) { vrc::scene_free(s); return hip_fail("vrc_volume_commit", e); }
+    if (e != hipSuccess) { vrc::scene_free(s); return vrc::fail_hip(e, "vrc_volume_commit"); }
     *out = s;
     return VRC_OK;
 }
@@ -341,7 +336,7 @@ extern "C" int vrc_volume_download(vrc_volume* v, uint8_t* solid_host)
     }
     if (e == hipSuccess) e = hipMemcpy(solid_host, d_dense, S * S * S, hipMemcpyDeviceToHost);
     if (d_dense) (void)hipFree(d_dense);
-    if (e != hipSuccess) return hip_fail("vrc_volume_download", e);
+    if (e != hipSuccess) return vrc::fail_hip(e, "vrc_volume_download");
     return VRC_OK;
 }
 
@@ -360,7 +355,7 @@ extern "C" int vrc_volume_solid_count(vrc_volume* v, uint64_t* count)
     }
     unsigned long long total = 0;
     if (e == hipSuccess) e = hipMemcpy(&total, v->d_count, 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail("vrc_volume_solid_count", e);
+    if (e != hipSuccess) return vrc::fail_hip(e, "vrc_volume_solid_count");
     *count = total;
     return VRC_OK;
 }

@@ -417,8 +417,8 @@ int vrc_set_tuning(uint32_t blocks_per_cu);
  * automatic mode's tail policy instead: low 16 bits = units per wave with the halved chunk. */
 int vrc_set_sample_chunk(uint32_t samples_per_unit);
 /* The stage-synchronous kernel is built for 6 resident workgroups per CU (= waves per SIMD) and, for
- * cameras with a lens, also for 7; the library picks by the kind of launch (csrc/vrc_api.cpp,
- * render_impl), and blocks_per_cu >= 7 picks the 7-wave build where there is one (fewer than 6:
+ * cameras with a lens, also for 7; the library picks by the kind of launch (csrc/vrc_plan.h,
+ * plan_frame), and blocks_per_cu >= 7 picks the 7-wave build where there is one (fewer than 6:
  * the 6-wave build on fewer workgroups).
  * vrc_renderer_last_kernel: the symbol of the frame kernel the renderer's last frame launched
  * (what a profile of the run lists), "" before the first frame. */

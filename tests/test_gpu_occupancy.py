@@ -1,4 +1,5 @@
-"""The stage-synchronous frame kernel exists in builds for 6 waves per SIMD and, the lens kernel, 7 (vrc_internal.h: FrameVariant; the planner, render_impl).
+"""The stage-synchronous frame kernel exists in builds for 6 waves per SIMD and, the lens kernel, 7 (vrc_internal.h: FrameVariant; the planner, vrc_plan.h -- tests/test_frame_plan.py pins
+the same choices on the host).
 Every build renders the same frame bit for bit -- against the oracle on a small frame with the build forced through
 vrc_renderer_set_tuning(blocks_per_cu), and build against build at BASELINE size where the library picks by the kind of
 launch; vrc_renderer_last_kernel names what ran."""

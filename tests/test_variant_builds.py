@@ -1,7 +1,7 @@
 """The documented experiment builds still compile (round-5 advice: quad_waves() named a macro that only the product build
 defined, so every -DVRC_PROBE / -DVRC_WALK_CPP / -DVRC_NO_START_BELOW build was broken without anyone noticing).  A front-end
-pass (hipcc -fsyntax-only: host AND gfx950 device side, inline-asm constraints included) of the two sources that carry
-switches, once per flag of cpuvoxelraycaster_amd/build.py's VARIANT_FLAGS; about a second each, no GPU."""
+pass (hipcc -fsyntax-only: host AND gfx950 device side, inline-asm constraints included) of the sources that carry
+switches (the kernels; the renderer, through the planner in vrc_plan.h) and the rest of the C ABI, once per flag of cpuvoxelraycaster_amd/build.py's VARIANT_FLAGS; about a second each, no GPU."""
 import os
 import re
 import subprocess
@@ -17,18 +17,18 @@ FRONT = [f for f in build.FLAGS if f not in ("-shared", "-fPIC", "-O3")] + ["-fs
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
 @pytest.mark.parametrize("flag", [""] + build.VARIANT_FLAGS)
 def test_variant_flag_compiles(flag):
-    for src in ("vrc_kernels.hip", "vrc_api.cpp"):
+    for src in ("vrc_kernels.hip", "vrc_renderer.cpp", "vrc_api.cpp", "vrc_ipc.cpp"):
         cmd = [HIPCC] + FRONT + ([flag] if flag else []) + ["-x", "hip", os.path.join(build.CSRC, src)]
         r = subprocess.run(cmd, capture_output=True, text=True)
         assert r.returncode == 0, f"{' '.join(cmd)}\n{r.stderr[-3000:]}"
 
 
 def test_variant_builds_have_no_quadrant_kernels_and_say_so():
-    """the variants that leave the quadrant-walk kernels out must report it (vrc::quad_available), so that render_impl neither
+    """the variants that leave the quadrant-walk kernels out must report it (vrc::quad_available), so that the planner neither
     chooses a quadrant-walk build nor sizes the grid for a build it could not launch"""
     src = open(os.path.join(build.CSRC, "vrc_kernels.hip")).read()
-    api = open(os.path.join(build.CSRC, "vrc_api.cpp")).read()
-    assert "bool quad_available()" in src and "vrc::quad_available() &&" in api
+    plan = open(os.path.join(build.CSRC, "vrc_plan.h")).read()
+    assert "bool quad_available()" in src and "vrc::quad_available() &&" in plan
     # the occupancy macro is defined whatever the variant
     head = src[:src.index("#define VRC_HAVE_QUAD 1")]
     assert "#define VRC_SYNC_Q_WAVES 6" in head and head.rstrip().endswith("defined(VRC_NO_START_BELOW))")
@@ -36,10 +36,11 @@ def test_variant_builds_have_no_quadrant_kernels_and_say_so():
 
 def test_variant_builds_have_no_quadrant_rows_in_the_frame_kernel_table():
     """the variants that leave the quadrant-walk kernels out have no quadrant rows in the frame-kernel table (vrc::frame_kernel),
-    and the planner chooses only from rows that exist, so that render_impl neither picks a quadrant build nor sizes the grid for
-    a build launch_render could not launch"""
+    and the planner (vrc_plan.h) chooses only from rows that exist, so that render_impl (vrc_renderer.cpp) neither picks a quadrant
+    build nor sizes the grid for a build launch_render could not launch"""
     src = open(os.path.join(build.CSRC, "vrc_kernels.hip")).read()
-    api = open(os.path.join(build.CSRC, "vrc_api.cpp")).read()
+    plan = open(os.path.join(build.CSRC, "vrc_plan.h")).read()
+    renderer = open(os.path.join(build.CSRC, "vrc_renderer.cpp")).read()
     guard = "#if !(defined(VRC_WALK_CPP) || defined(VRC_PROBE) || defined(VRC_NO_START_BELOW))"
     i = src.index(guard)
     j = src.index("#else", i)
@@ -50,8 +51,8 @@ def test_variant_builds_have_no_quadrant_rows_in_the_frame_kernel_table():
     assert src[j:k].split() == ["#else", "#define", "VRC_QUAD_FRAME_KERNELS(X)"]
     # the kernels and the table come from that list; the planner asks the table for a quadrant build and launches what it chose
     assert "VRC_FRAME_KERNELS(VRC_FRAME_KERNEL)" in src and "VRC_FRAME_KERNELS(VRC_FRAME_ROW)" in src
-    assert "if (k.v.map == LaneMap::quad) return true;" in src and "vrc::quad_available() &&" in api
-    assert "kernel = vrc::frame_kernel(v);" in api and "vrc::launch_render(*kernel," in api
+    assert "if (k.v.map == LaneMap::quad) return true;" in src and "vrc::quad_available() &&" in plan
+    assert "kernel = vrc::frame_kernel(v);" in plan and "vrc::launch_render(*plan.kernel," in renderer
     # the occupancy macro is defined whatever the variant
     assert "#define VRC_SYNC_Q_WAVES 6" in src[:i]
     if os.path.exists(HIPCC):   # and the preprocessor agrees, per variant

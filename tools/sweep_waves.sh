@@ -1,6 +1,6 @@
 #!/bin/bash
 # Which build of the stage-synchronous frame kernel (6 / 7 / 8 waves per SIMD) wins for which launch: the table behind
-# the planner's waves (csrc/vrc_api.cpp, render_impl), measured off the tuning pose as well (round-2 verdict item 8).
+# the planner's waves (csrc/vrc_plan.h, plan_units), measured off the tuning pose as well (round-2 verdict item 8).
 #   usage: tools/sweep_waves.sh <outfile> [configs, default "c2 c3 c4 c5"]
 # For every config x camera pitch {0, -0.5, -1.2} x {three frames in flight (whole-spp units, fused resolve), one frame at a
 # time (automatic chunk)}: ms per frame of the library's own choice and of each forced build.
