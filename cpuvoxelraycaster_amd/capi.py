@@ -12,6 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libvrc_hip.so")
 
 VRC_MEM_HOST, VRC_MEM_DEVICE = 0, 1
+VRC_COPY_REPLACE, VRC_COPY_OR, VRC_COPY_ANDNOT = 0, 1, 2
 
 HIT_DTYPE = np.dtype([
     ("position", "<f4", 3), ("normal", "<f4", 3), ("voxel_coord", "<f4", 2),
@@ -131,6 +132,12 @@ SYMBOLS = {
     "vrc_volume_commit": (_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_float)]),
     "vrc_volume_download": (_int, [_vp, _vp]),
     "vrc_volume_solid_count": (_int, [_vp, C.POINTER(_u64)]),
+    "vrc_volume_fill_spheres": (_int, [_vp, _u64, _vp, _int, _int, _vp]),
+    "vrc_volume_fill_spheres_at_hits": (_int, [_vp, _u64, _vp, _i32, _int, _int, _vp]),
+    "vrc_volume_copy_region": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp]),
+    "vrc_volume_clone": (_int, [_vp, C.POINTER(_vp)]),
+    "vrc_volume_get_voxels": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
+    "vrc_volume_count_boxes": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
     "vrc_renderer_set_scene": (_int, [_vp, _vp]),
     "vrc_hit_to_voxel": (_int, [_u32, _vp, _vp, _vp, C.POINTER(_int)]),
 }

@@ -8,6 +8,8 @@
 // commit is the builder's count / rank / emit sweeps (vrc_build_sweeps.h) over a third occupancy source, BrickVox:
 // bit-identical to compileSVO of the voxel set, into a NEW scene.  Batched edits are 32-bit vector atomics
 // (atomicOr / atomicAnd) on the words that hold the bricks, or whole-word stores where a box covers a word.
+// Brushes (spheres, spheres at the hits of a ray batch), region copies between volumes and the two queries (single
+// voxels, solid voxels per box) walk the same rows of words as the boxes do.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -28,7 +30,9 @@ struct vrc_volume {
     // host-memory form of the edit calls: grow-only staging block
     uint32_t* d_stage = nullptr;
     size_t stage_cap = 0;
-    // the last asynchronous edit: commit / download / solid_count run on the NULL stream and wait for it first
+    // the last asynchronous edit: commit / download / solid_count run on the NULL stream and wait for it first.  The flag
+    // says that the event has been recorded at least once; it is never cleared, because a wait only orders ONE stream
+    // behind the edit and the next caller may bring another.
     hipEvent_t edit_done = nullptr;
     bool edit_pending = false;
 };
@@ -59,53 +63,298 @@ __device__ __forceinline__ uint32_t axis_pair(uint32_t c, uint32_t lo, uint32_t 
     return ((v >= lo && v < hi) ? 1u : 0u) | ((v + 1u >= lo && v + 1u < hi) ? 2u : 0u);
 }
 
+// The brick rows a clipped, non-empty voxel box [lo, hi) touches, as a list of work items.  A row = the bricks
+// (cx, cy, cz0..cz1), contiguous bytes; item = (row, k-th 32-bit word of the row).
+struct BoxWords {
+    uint32_t lo[3], hi[3];
+    uint32_t bx0, by0, cz0, cz1, nby, wpr;
+    uint64_t items;
+};
+
+__device__ __forceinline__ BoxWords box_words(const uint32_t lo[3], const uint32_t hi[3])
+{
+    BoxWords b;
+    for (int a = 0; a < 3; ++a) { b.lo[a] = lo[a]; b.hi[a] = hi[a]; }
+    b.bx0 = lo[0] >> 1; b.by0 = lo[1] >> 1; b.cz0 = lo[2] >> 1;
+    const uint32_t nbx = ((hi[0] - 1u) >> 1) - b.bx0 + 1u;
+    b.nby = ((hi[1] - 1u) >> 1) - b.by0 + 1u;
+    b.cz1 = (hi[2] - 1u) >> 1;
+    b.wpr = ((b.cz1 - b.cz0 + 3u) >> 2) + 1u;          // upper bound of the words one row touches, whatever its alignment
+    b.items = (uint64_t)nbx * b.nby * b.wpr;
+    return b;
+}
+
+// One item of a box: the word index `w`, the row's brick coordinates and the byte indices of brick (cx, cy, 0) and of
+// the row's first / last brick.  false: the row has fewer words than wpr and this item is beyond them.
+struct RowWord {
+    uint32_t cx, cy;
+    uint64_t base, first, last, w;
+};
+
+__device__ __forceinline__ bool row_word(const BoxWords& b, uint32_t n, uint64_t it, RowWord& r)
+{
+    const uint32_t k = (uint32_t)(it % b.wpr);
+    const uint32_t row = (uint32_t)(it / b.wpr);
+    r.cx = b.bx0 + row / b.nby; r.cy = b.by0 + row % b.nby;
+    r.base = ((uint64_t)r.cx * n + r.cy) * n;
+    r.first = r.base + b.cz0; r.last = r.base + b.cz1;
+    r.w = (r.first >> 2) + k;
+    return r.w <= (r.last >> 2);
+}
+
+// the voxels of word r.w that lie inside the box, as a mask of the word's bits
+__device__ __forceinline__ uint32_t box_mask(const BoxWords& b, const RowWord& r)
+{
+    const uint32_t xy = axis_pair(r.cx, b.lo[0], b.hi[0]) | (axis_pair(r.cy, b.lo[1], b.hi[1]) << 2);
+    // xy: bit 0 / 1 = x voxel 0 / 1 inside, bit 2 / 3 = y voxel 0 / 1 inside -> the 4 (y, x) bits of one z layer
+    const uint32_t layer = ((xy & 1u) ? 0x5u : 0u) | ((xy & 2u) ? 0xAu : 0u);
+    const uint32_t plane = (layer & ((xy & 4u) ? 0x3u : 0u)) | (layer & ((xy & 8u) ? 0xCu : 0u));
+    uint32_t mask = 0u;
+    for (uint32_t j = 0; j < 4u; ++j) {
+        const uint64_t byte = 4u * r.w + j;
+        if (byte < r.first || byte > r.last) continue;
+        const uint32_t zp = axis_pair((uint32_t)(byte - r.base), b.lo[2], b.hi[2]);
+        const uint32_t m8 = ((zp & 1u) ? plane : 0u) | ((zp & 2u) ? plane << 4 : 0u);
+        mask |= m8 << (8u * j);
+    }
+    return mask;
+}
+
+// lo_hi[0..5] clipped to the volume; false = empty, inverted or wholly outside
+__device__ __forceinline__ bool clip_box(const uint32_t* lo_hi, uint32_t S, uint32_t lo[3], uint32_t hi[3])
+{
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = lo_hi[a];
+        hi[a] = lo_hi[3 + a] < S ? lo_hi[3 + a] : S;
+        if (lo[a] >= hi[a]) return false;
+    }
+    return true;
+}
+
 // Boxes [lo, hi) clipped to the volume.  blockIdx.x = box, and the box's work is split over blockIdx.y x 256 threads.
-// The work of a box is the 32-bit WORDS its brick rows touch: a row = the bricks (cx, cy, cz0..cz1), contiguous bytes;
-// item = (row, k-th word of the row).  A word the box covers completely is stored as a whole (every writer of a call
-// writes the same value, so a plain store next to other lanes' atomics is safe); a partly covered one is one atomic
-// with the mask of the covered voxels.  Cost: proportional to the bricks inside the boxes, never to the bounding
-// volume of all of them.
+// The work of a box is the 32-bit WORDS its brick rows touch (BoxWords).  A word the box covers completely is stored as
+// a whole (every writer of a call writes the same value, so a plain store next to other lanes' atomics is safe); a
+// partly covered one is one atomic with the mask of the covered voxels.  Cost: proportional to the bricks inside the
+// boxes, never to the bounding volume of all of them.
 __global__ void k_fill_boxes(uint32_t* __restrict__ words, uint32_t S, const uint32_t* __restrict__ lo_hi, uint32_t solid)
 {
-    const uint32_t* b = lo_hi + 6ull * blockIdx.x;
+    uint32_t lo[3], hi[3];
+    if (!clip_box(lo_hi + 6ull * blockIdx.x, S, lo, hi)) return;      // uniform for the workgroup
+    const uint32_t n = S >> 1;
+    const BoxWords b = box_words(lo, hi);
+    for (uint64_t it = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; it < b.items; it += (uint64_t)gridDim.y * blockDim.x) {
+        RowWord r;
+        if (!row_word(b, n, it, r)) continue;
+        const uint32_t mask = box_mask(b, r);
+        if (mask == 0xffffffffu) words[r.w] = solid ? 0xffffffffu : 0u;
+        else if (mask) {
+            if (solid) atomicOr(&words[r.w], mask);
+            else atomicAnd(&words[r.w], ~mask);
+        }
+    }
+}
+
+// ---- brushes -----------------------------------------------------------------
+
+#define VRC_BRUSH_LIMIT (1 << 20)     // |centre| and radius of a sphere: squares and their sums stay far inside 64 bits
+
+// floor(sqrt(v)) for 0 <= v <= 2^42, exact: the double root is within one of it
+__device__ __forceinline__ int64_t isqrt(int64_t v)
+{
+    int64_t h = (int64_t)sqrt((double)v);
+    while (h * h > v) --h;
+    while ((h + 1) * (h + 1) <= v) ++h;
+    return h;
+}
+
+// Spheres (cx, cy, cz, r): voxel (x, y, z) belongs iff dx^2 + dy^2 + dz^2 <= r^2 in integers.  blockIdx.x = sphere, its
+// work split over blockIdx.y x blockDim.x threads and laid out as the words of its OWN bounding box clipped to the
+// volume (BoxWords), so the cost follows the bricks around each sphere, never the volume or the batch's bounding volume.
+// A voxel column (x, y) of a sphere is one z interval, cz -/+ isqrt(r^2 - dx^2 - dy^2): a word's mask follows from the
+// four intervals of its brick row.  Whole words are stored, partly covered ones take one atomic -- none at all where the
+// word already has the value (all writers of a call write the same value, so a stale read only costs the atomic; the
+// hits of neighbouring rays name the same voxels over and over).
+__global__ void k_fill_spheres(uint32_t* __restrict__ words, uint32_t S, const int32_t* __restrict__ centre_radius, uint32_t solid)
+{
+    const int32_t* s = centre_radius + 4ull * blockIdx.x;
+    const int32_t c[3] = {s[0], s[1], s[2]}, rad = s[3];
+    if (rad < 0 || rad > VRC_BRUSH_LIMIT) return;                      // uniform for the workgroup, as every return below
     uint32_t lo[3], hi[3];
     for (int a = 0; a < 3; ++a) {
-        lo[a] = b[a];
-        hi[a] = b[3 + a] < S ? b[3 + a] : S;
-        if (lo[a] >= hi[a]) return;                 // empty (or wholly outside): uniform for the workgroup
+        if (c[a] > VRC_BRUSH_LIMIT || c[a] < -VRC_BRUSH_LIMIT) return;
+        const int32_t l = c[a] - rad, h = c[a] + rad + 1;              // |.| <= 2^21 + 1
+        if (h <= 0 || l >= (int32_t)S) return;
+        lo[a] = l < 0 ? 0u : (uint32_t)l;
+        hi[a] = h > (int32_t)S ? S : (uint32_t)h;
     }
     const uint32_t n = S >> 1;
-    const uint32_t bx0 = lo[0] >> 1, by0 = lo[1] >> 1, cz0 = lo[2] >> 1;
-    const uint32_t nbx = ((hi[0] - 1u) >> 1) - bx0 + 1u, nby = ((hi[1] - 1u) >> 1) - by0 + 1u;
-    const uint32_t cz1 = (hi[2] - 1u) >> 1;
-    const uint32_t wpr = ((cz1 - cz0 + 3u) >> 2) + 1u;   // upper bound of the words one row touches, whatever its alignment
-    const uint64_t items = (uint64_t)nbx * nby * wpr;
-    for (uint64_t it = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; it < items; it += (uint64_t)gridDim.y * blockDim.x) {
-        const uint32_t k = (uint32_t)(it % wpr);
-        const uint32_t row = (uint32_t)(it / wpr);
-        const uint32_t cx = bx0 + row / nby, cy = by0 + row % nby;
-        const uint64_t base = ((uint64_t)cx * n + cy) * n;               // byte index of brick (cx, cy, 0)
-        const uint64_t first = base + cz0, last = base + cz1;
-        const uint64_t w = (first >> 2) + k;
-        if (w > (last >> 2)) continue;
-        const uint32_t xy = axis_pair(cx, lo[0], hi[0]) | (axis_pair(cy, lo[1], hi[1]) << 2);
-        // xy: bit 0 / 1 = x voxel 0 / 1 inside, bit 2 / 3 = y voxel 0 / 1 inside -> the 4 (y, x) bits of one z layer
-        const uint32_t layer = ((xy & 1u) ? 0x5u : 0u) | ((xy & 2u) ? 0xAu : 0u);
-        const uint32_t plane = (layer & ((xy & 4u) ? 0x3u : 0u)) | (layer & ((xy & 8u) ? 0xCu : 0u));
+    const int64_t r2 = (int64_t)rad * rad;
+    const BoxWords b = box_words(lo, hi);
+    for (uint64_t it = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; it < b.items; it += (uint64_t)gridDim.y * blockDim.x) {
+        RowWord r;
+        if (!row_word(b, n, it, r)) continue;
+        // the z interval [zl, zh] of each of the row's four columns, k = y * 2 + x as in a brick's bit index
+        int32_t zl[4], zh[4];
+        bool any = false;
+        for (int k = 0; k < 4; ++k) {
+            const int64_t dx = (int64_t)(2u * r.cx + (k & 1)) - c[0], dy = (int64_t)(2u * r.cy + (k >> 1)) - c[1];
+            const int64_t rem = r2 - dx * dx - dy * dy;
+            if (rem < 0) { zl[k] = 1; zh[k] = 0; continue; }
+            const int32_t h = (int32_t)isqrt(rem);
+            zl[k] = c[2] - h; zh[k] = c[2] + h;
+            any = true;
+        }
+        if (!any) continue;
         uint32_t mask = 0u;
         for (uint32_t j = 0; j < 4u; ++j) {
-            const uint64_t byte = 4u * w + j;
-            if (byte < first || byte > last) continue;
-            const uint32_t zp = axis_pair((uint32_t)(byte - base), lo[2], hi[2]);
-            const uint32_t m8 = ((zp & 1u) ? plane : 0u) | ((zp & 2u) ? plane << 4 : 0u);
+            const uint64_t byte = 4u * r.w + j;
+            if (byte < r.first || byte > r.last) continue;
+            const int32_t z0 = 2 * (int32_t)(byte - r.base);
+            uint32_t m8 = 0u;
+            for (int k = 0; k < 4; ++k)
+                m8 |= ((z0 >= zl[k] && z0 <= zh[k]) ? 1u << k : 0u) | ((z0 + 1 >= zl[k] && z0 + 1 <= zh[k]) ? 16u << k : 0u);
             mask |= m8 << (8u * j);
         }
-        if (mask == 0xffffffffu) words[w] = solid ? 0xffffffffu : 0u;
+        if (mask == 0xffffffffu) words[r.w] = solid ? 0xffffffffu : 0u;
         else if (mask) {
-            if (solid) atomicOr(&words[w], mask);
-            else atomicAnd(&words[w], ~mask);
+            const uint32_t have = words[r.w];
+            if (solid) { if ((have & mask) != mask) atomicOr(&words[r.w], mask); }
+            else if (have & mask) atomicAnd(&words[r.w], ~mask);
         }
     }
+}
+
+// vrc_hit_to_voxel (vrc_api.cpp) per record, the same float32 operations: centre = the voxel hit (dig) or the empty
+// cell the ray came through (build); records that function refuses, and a build without a neighbour, get radius -1,
+// which k_fill_spheres drops.
+__global__ void k_hits_to_centres(uint64_t count, const vrc_hit* __restrict__ hits, uint32_t depth, int32_t radius, uint32_t build,
+                                  int32_t* __restrict__ centre_radius)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const vrc_hit h = hits[i];
+    const int32_t Si = (int32_t)(1u << depth);
+    const float S = (float)Si;
+    int32_t cell[3];
+    bool ok = (h.hit & 0xffu) == 1u;
+    for (int a = 0; a < 3; ++a) {
+        const float f = floorf((h.position[a] - 1.0f) * S);
+        ok = ok && f >= 0.0f && f < S;                                  // NaN fails both
+        cell[a] = ok ? Si - 1 - (int32_t)f : 0;
+    }
+    if (ok && build) {
+        int axis = -1, axes = 0;
+        for (int a = 0; a < 3; ++a) if (h.normal[a] != 0.0f) { axis = a; ++axes; }
+        ok = axes == 1;
+        if (ok) {
+            cell[axis] -= h.normal[axis] > 0.0f ? 1 : -1;
+            ok = cell[axis] >= 0 && cell[axis] < Si;
+        }
+    }
+    int4 out;
+    out.x = cell[0]; out.y = cell[1]; out.z = cell[2]; out.w = ok ? radius : -1;
+    ((int4*)centre_radius)[i] = out;
+}
+
+// ---- region copy ---------------------------------------------------------------
+
+// bit k = voxel (x, y, z0 + k) of the source, 0 <= k < 10 where the voxel exists: the column's bits of the five bricks
+// from z0 on (z0 even, may be negative or beyond the volume)
+__device__ __forceinline__ uint32_t source_column(const uint8_t* __restrict__ src, uint32_t ns, int64_t x, int64_t y, int64_t z0)
+{
+    const int64_t Ss = 2 * (int64_t)ns;
+    if (x < 0 || y < 0 || x >= Ss || y >= Ss) return 0u;
+    const uint8_t* row = src + ((uint64_t)(x >> 1) * ns + (uint64_t)(y >> 1)) * ns;
+    const uint32_t sh = (uint32_t)(y & 1) * 2u + (uint32_t)(x & 1);
+    uint32_t bits = 0u;
+    for (int j = 0; j < 5; ++j) {
+        const int64_t bz = (z0 >> 1) + j;
+        if (bz < 0 || bz >= (int64_t)ns) continue;
+        const uint32_t v = row[bz] >> sh;
+        bits |= ((v & 1u) | ((v >> 3) & 2u)) << (2 * j);
+    }
+    return bits;
+}
+
+// dst voxel p in the box [lo, hi) takes (op) src voxel p + off.  One thread per destination WORD of the box's rows: it
+// gathers the word's 4 columns x 8 z-neighbours from the up to 2 x 2 x 5 source bricks that hold them, whatever the
+// offset's parity on any axis, and writes the word once -- a partly covered word is a masked read-modify-write, which
+// needs no atomic because a word has one owner within a call.  Volumes of 4^3 (two rows to a word) are the exception:
+// there a word's rows take atomics.
+__global__ void k_copy_region(uint32_t* __restrict__ dst, uint32_t Sd, const uint8_t* __restrict__ src, uint32_t Ss,
+                              uint32_t lx, uint32_t ly, uint32_t lz, uint32_t hx, uint32_t hy, uint32_t hz,
+                              int64_t ox, int64_t oy, int64_t oz, int op)
+{
+    const uint32_t lo[3] = {lx, ly, lz}, hi[3] = {hx, hy, hz};
+    const uint32_t n = Sd >> 1, ns = Ss >> 1;
+    const BoxWords b = box_words(lo, hi);
+    for (uint64_t it = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; it < b.items; it += (uint64_t)gridDim.x * blockDim.x) {
+        RowWord r;
+        if (!row_word(b, n, it, r)) continue;
+        const uint32_t mask = box_mask(b, r);
+        if (!mask) continue;
+        // z of the word's first voxel, relative to the row (negative where the word starts in the row before: n = 2)
+        const int64_t z0 = 2 * ((int64_t)(4u * r.w) - (int64_t)r.base);
+        const int64_t sz = z0 + oz;
+        const uint32_t odd = (uint32_t)(sz & 1);
+        uint32_t bits = 0u;
+        for (uint32_t k = 0; k < 4u; ++k) {
+            const uint32_t col = (source_column(src, ns, 2 * (int64_t)r.cx + (k & 1u) + ox, 2 * (int64_t)r.cy + (k >> 1) + oy, sz - odd) >> odd) & 0xffu;
+            // column bit z -> word bit (z >> 1) * 8 + (z & 1) * 4 + k
+            for (uint32_t z = 0; z < 8u; ++z) bits |= ((col >> z) & 1u) << ((z >> 1) * 8u + (z & 1u) * 4u + k);
+        }
+        bits &= mask;
+        if (n < 4u) {
+            if (op == VRC_COPY_REPLACE) { atomicAnd(&dst[r.w], ~mask); atomicOr(&dst[r.w], bits); }
+            else if (op == VRC_COPY_OR) atomicOr(&dst[r.w], bits);
+            else atomicAnd(&dst[r.w], ~bits);
+            continue;
+        }
+        uint32_t v;
+        if (op == VRC_COPY_REPLACE) v = mask == 0xffffffffu ? bits : ((dst[r.w] & ~mask) | bits);
+        else if (op == VRC_COPY_OR) { if (!bits) continue; v = dst[r.w] | bits; }
+        else { if (!bits) continue; v = dst[r.w] & ~bits; }
+        dst[r.w] = v;
+    }
+}
+
+// ---- queries -------------------------------------------------------------------
+
+__global__ void k_get_voxels(const uint8_t* __restrict__ bricks, uint32_t S, uint64_t count, const uint32_t* __restrict__ xyz, uint8_t* __restrict__ solid_out)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+    uint32_t v = 0u;
+    if (x < S && y < S && z < S) {
+        const uint32_t n = S >> 1;
+        v = (bricks[((uint64_t)(x >> 1) * n + (y >> 1)) * n + (z >> 1)] >> ((z & 1u) * 4u + (y & 1u) * 2u + (x & 1u))) & 1u;
+    }
+    solid_out[i] = (uint8_t)v;
+}
+
+// counts[box] (zeroed before the launch) += the solid voxels inside box: popcount of the words under k_fill_boxes' masks
+__global__ void k_count_boxes(const uint32_t* __restrict__ words, uint32_t S, const uint32_t* __restrict__ lo_hi, unsigned long long* __restrict__ counts)
+{
+    __shared__ uint32_t part[256];
+    uint32_t lo[3], hi[3];
+    if (!clip_box(lo_hi + 6ull * blockIdx.x, S, lo, hi)) return;      // uniform for the workgroup
+    const uint32_t n = S >> 1;
+    const BoxWords b = box_words(lo, hi);
+    uint32_t total = 0u;               // the largest box is 2^25 words: 2^22 voxels per thread, 2^30 per workgroup
+    for (uint64_t it = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; it < b.items; it += (uint64_t)gridDim.y * blockDim.x) {
+        RowWord r;
+        if (!row_word(b, n, it, r)) continue;
+        const uint32_t mask = box_mask(b, r);
+        if (mask) total += __popc(words[r.w] & mask);
+    }
+    part[threadIdx.x] = total;
+    __syncthreads();
+    for (uint32_t s = 128u; s; s >>= 1) {
+        if (threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && part[0]) atomicAdd(&counts[blockIdx.x], (unsigned long long)part[0]);
 }
 
 // ---- scene -> volume ---------------------------------------------------------
@@ -199,13 +448,39 @@ int volume_new(uint32_t depth, int device, vrc_volume** out)
 // orders the NULL stream behind the last asynchronous edit
 hipError_t wait_for_edits(vrc_volume* v)
 {
-    if (!v->edit_pending) return hipSuccess;
-    v->edit_pending = false;
-    return hipStreamWaitEvent(nullptr, v->edit_done, 0);
+    return v->edit_pending ? hipStreamWaitEvent(nullptr, v->edit_done, 0) : hipSuccess;
 }
 
-// Shared frame of the two edit calls: `words_per_item` u32 per item at `items`; host memory is staged and the call
-// synchronous, device memory is used in place and the call asynchronous on `st`.
+// The grow-only staging block, at least `need` bytes.  hipFree waits for everything that may still read the old block.
+hipError_t stage_reserve(vrc_volume* v, size_t need)
+{
+    if (v->stage_cap >= need) return hipSuccess;
+    if (v->d_stage) (void)hipFree(v->d_stage);
+    v->d_stage = nullptr; v->stage_cap = 0;
+    const hipError_t e = hipMalloc((void**)&v->d_stage, need);
+    if (e == hipSuccess) v->stage_cap = need;
+    return e;
+}
+
+// orders `st` behind the last asynchronous edit: for the calls that read the occupancy, and for every call that writes
+// the staging block -- the device-memory brush at hits leaves its centres there, in flight on the caller's stream
+hipError_t order_behind_edits(vrc_volume* v, hipStream_t st)
+{
+    return v->edit_pending ? hipStreamWaitEvent(st, v->edit_done, 0) : hipSuccess;
+}
+
+// the end of every call that takes `mem`: a host-memory call is synchronous, a device-memory edit is recorded as the
+// volume's last asynchronous edit
+hipError_t finish(vrc_volume* v, int mem, hipStream_t st, bool is_edit)
+{
+    if (mem == VRC_MEM_HOST) return hipStreamSynchronize(st);
+    if (!is_edit) return hipSuccess;
+    v->edit_pending = true;            // the NULL stream included: streams made by vrc_stream_create do not wait for it
+    return hipEventRecord(v->edit_done, st);
+}
+
+// Shared frame of the edit calls that read a list of items: `words_per_item` u32 per item at `items`; host memory is
+// staged and the call synchronous, device memory is used in place and the call asynchronous on `st`.
 template <class Launch>
 int edit(vrc_volume* v, const char* what, uint64_t count, uint32_t words_per_item, const uint32_t* items, int mem, hipStream_t st, Launch launch)
 {
@@ -214,21 +489,38 @@ int edit(vrc_volume* v, const char* what, uint64_t count, uint32_t words_per_ite
     const uint32_t* d_items = items;
     if (mem == VRC_MEM_HOST) {
         const size_t need = (size_t)count * words_per_item * 4u;
-        if (v->stage_cap < need) {
-            if (v->d_stage) (void)hipFree(v->d_stage);
-            v->d_stage = nullptr; v->stage_cap = 0;
-            if ((e = hipMalloc((void**)&v->d_stage, need)) != hipSuccess) return vrc::fail_hip(e, what);
-            v->stage_cap = need;
-        }
+        if ((e = order_behind_edits(v, st)) != hipSuccess) return vrc::fail_hip(e, what);
+        if ((e = stage_reserve(v, need)) != hipSuccess) return vrc::fail_hip(e, what);
         if ((e = hipMemcpyAsync(v->d_stage, items, need, hipMemcpyHostToDevice, st)) != hipSuccess) return vrc::fail_hip(e, what);
         d_items = v->d_stage;
     }
     launch(d_items);
     if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
-    if (mem == VRC_MEM_HOST) e = hipStreamSynchronize(st);
-    else if (st != nullptr) { e = hipEventRecord(v->edit_done, st); v->edit_pending = true; }
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    if ((e = finish(v, mem, st, true)) != hipSuccess) return vrc::fail_hip(e, what);
     return VRC_OK;
+}
+
+// workgroups per item for the kernels that take one item per blockIdx.x: a few items are spread over up to 1024
+// workgroups each (a whole 1024^3 volume is 2^25 words); many items: one workgroup each.  A workgroup that finds
+// nothing to do leaves at once.
+uint32_t split_for(const vrc_volume* v, uint64_t n)
+{
+    uint32_t split = (uint32_t)((4096ull + n - 1) / n);
+    const uint64_t max_words = v->n_bricks / 4u;
+    const uint32_t useful = (uint32_t)((max_words + 255u) / 256u);   // 256-thread groups that cover the largest possible box once
+    if (split > 1024u) split = 1024u;
+    if (split > useful) split = useful;
+    if (split == 0) split = 1;
+    return split;
+}
+
+// max_radius: the largest radius of the batch where the caller knows it, -1 where it does not
+void launch_fill_spheres(vrc_volume* v, uint64_t n, const int32_t* d_spheres, int32_t max_radius, int solid, hipStream_t st)
+{
+    // many small spheres (a brush at every hit of a batch: at most 6 x 6 x 3 words each): a wave each, not four
+    const bool small = n >= 4096u && max_radius >= 0 && max_radius <= 4;
+    hipLaunchKernelGGL(k_fill_spheres, dim3((uint32_t)n, split_for(v, n)), dim3(small ? 64 : 256), 0, st, v->d_bricks, 1u << v->depth,
+                       d_spheres, solid ? 1u : 0u);
 }
 
 }  // namespace
@@ -293,17 +585,162 @@ extern "C" int vrc_volume_fill_boxes(vrc_volume* v, uint64_t n, const uint32_t* 
     if (n > 0x7fffffffull) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_boxes: too many boxes for one launch");
     hipStream_t st = (hipStream_t)stream;
     const uint32_t S = 1u << v->depth;
-    // a few boxes: their words are spread over up to 1024 workgroups each (a whole 1024^3 volume is 2^25 words); many
-    // boxes: one workgroup each.  A workgroup that finds nothing to do leaves at once.
-    uint32_t split = (uint32_t)((4096ull + n - 1) / n);
-    const uint64_t max_words = v->n_bricks / 4u;
-    const uint32_t useful = (uint32_t)((max_words + 255u) / 256u);   // 256-thread groups that cover the largest possible box once
-    if (split > 1024u) split = 1024u;
-    if (split > useful) split = useful;
-    if (split == 0) split = 1;
+    const uint32_t split = split_for(v, n);
     return edit(v, "vrc_volume_fill_boxes", n, 6, lo_hi, mem, st, [&](const uint32_t* d_boxes) {
         hipLaunchKernelGGL(k_fill_boxes, dim3((uint32_t)n, split), dim3(256), 0, st, v->d_bricks, S, d_boxes, solid ? 1u : 0u);
     });
+}
+
+extern "C" int vrc_volume_fill_spheres(vrc_volume* v, uint64_t n, const int32_t* centre_radius, int solid, int mem, void* stream)
+{
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_spheres: null volume");
+    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_spheres: bad mem kind %d", mem);
+    if (n == 0) return VRC_OK;
+    if (!centre_radius) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_spheres: null buffer");
+    if (n > 0x7fffffffull) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_spheres: too many spheres for one launch");
+    hipStream_t st = (hipStream_t)stream;
+    return edit(v, "vrc_volume_fill_spheres", n, 4, (const uint32_t*)centre_radius, mem, st, [&](const uint32_t* d_spheres) {
+        launch_fill_spheres(v, n, (const int32_t*)d_spheres, -1, solid, st);
+    });
+}
+
+extern "C" int vrc_volume_fill_spheres_at_hits(vrc_volume* v, uint64_t n, const vrc_hit* hits, int32_t radius, int solid, int mem, void* stream)
+{
+    const char* what = "vrc_volume_fill_spheres_at_hits";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
+    if (radius < 0 || radius > VRC_BRUSH_LIMIT) return vrc::fail(VRC_ERR_INVALID, "%s: radius %d not in [0, 2^20]", what, radius);
+    if (n == 0) return VRC_OK;
+    if (!hits) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (n > 0x7fffffffull) return vrc::fail(VRC_ERR_INVALID, "%s: too many hits for one launch", what);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(v->device);
+    // the centres go through the staging block (n x 4 int32, then the hits themselves when they come from the host),
+    // which an earlier call on another stream may still be reading
+    if (e == hipSuccess) e = order_behind_edits(v, st);
+    if (e == hipSuccess) e = stage_reserve(v, (size_t)n * (mem == VRC_MEM_HOST ? 64u : 16u));
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    int32_t* d_centres = (int32_t*)v->d_stage;
+    const vrc_hit* d_hits = hits;
+    if (mem == VRC_MEM_HOST) {
+        d_hits = (const vrc_hit*)((uint8_t*)v->d_stage + (size_t)n * 16u);
+        if ((e = hipMemcpyAsync((void*)d_hits, hits, (size_t)n * sizeof(vrc_hit), hipMemcpyHostToDevice, st)) != hipSuccess) return vrc::fail_hip(e, what);
+    }
+    hipLaunchKernelGGL(k_hits_to_centres, grid_for(n), dim3(256), 0, st, n, d_hits, v->depth, radius, solid ? 1u : 0u, d_centres);
+    launch_fill_spheres(v, n, d_centres, radius, solid, st);
+    if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
+    if ((e = finish(v, mem, st, true)) != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+extern "C" int vrc_volume_copy_region(vrc_volume* dst, vrc_volume* src, const uint32_t src_lo[3], const uint32_t size[3], const int32_t dst_lo[3],
+                                      int op, void* stream)
+{
+    const char* what = "vrc_volume_copy_region";
+    if (!dst || !src || !src_lo || !size || !dst_lo) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (src == dst) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
+    if (op != VRC_COPY_REPLACE && op != VRC_COPY_OR && op != VRC_COPY_ANDNOT) return vrc::fail(VRC_ERR_INVALID, "%s: bad op %d", what, op);
+    if (src->device != dst->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, src->device, dst->device);
+    // the region clipped to both volumes, as the destination's voxel box [lo, hi) and the offset to the source
+    const int64_t Ss = 1ll << src->depth, Sd = 1ll << dst->depth;
+    uint32_t lo[3], hi[3];
+    int64_t off[3];
+    for (int a = 0; a < 3; ++a) {
+        int64_t d0 = 0, d1 = size[a];                                  // 0 <= d0 <= d < d1 <= size
+        if (-(int64_t)dst_lo[a] > d0) d0 = -(int64_t)dst_lo[a];
+        if (Ss - (int64_t)src_lo[a] < d1) d1 = Ss - (int64_t)src_lo[a];
+        if (Sd - (int64_t)dst_lo[a] < d1) d1 = Sd - (int64_t)dst_lo[a];
+        if (d0 >= d1) return VRC_OK;                                   // nothing of the region lies in both volumes
+        lo[a] = (uint32_t)(dst_lo[a] + d0);
+        hi[a] = (uint32_t)(dst_lo[a] + d1);
+        off[a] = (int64_t)src_lo[a] - (int64_t)dst_lo[a];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(dst->device);
+    if (e == hipSuccess) e = order_behind_edits(src, st);
+    if (e == hipSuccess) e = order_behind_edits(dst, st);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    const uint64_t words = (uint64_t)(((hi[0] - 1u) >> 1) - (lo[0] >> 1) + 1u) * (((hi[1] - 1u) >> 1) - (lo[1] >> 1) + 1u) *
+                           (((((hi[2] - 1u) >> 1) - (lo[2] >> 1) + 3u) >> 2) + 1u);
+    uint64_t groups = (words + 255u) / 256u;
+    if (groups > 16384u) groups = 16384u;
+    hipLaunchKernelGGL(k_copy_region, dim3((uint32_t)groups), dim3(256), 0, st, dst->d_bricks, (uint32_t)Sd, (const uint8_t*)src->d_bricks, (uint32_t)Ss,
+                       lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], off[0], off[1], off[2], op);
+    if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
+    if ((e = finish(dst, VRC_MEM_DEVICE, st, true)) != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+extern "C" int vrc_volume_clone(vrc_volume* src, vrc_volume** out)
+{
+    if (!src || !out) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_clone: null argument");
+    vrc_volume* v = nullptr;
+    int rc = volume_new(src->depth, src->device, &v);
+    if (rc) return rc;
+    hipError_t e = wait_for_edits(src);
+    if (e == hipSuccess) e = hipMemcpyAsync(v->d_bricks, src->d_bricks, src->n_bricks, hipMemcpyDeviceToDevice, nullptr);
+    if (e == hipSuccess) e = hipMemcpyAsync(v->d_tex, src->d_tex, 1536, hipMemcpyDeviceToDevice, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) { volume_free(v); return vrc::fail_hip(e, "vrc_volume_clone"); }
+    *out = v;
+    return VRC_OK;
+}
+
+extern "C" int vrc_volume_get_voxels(vrc_volume* v, uint64_t n, const uint32_t* xyz, uint8_t* solid_out, int mem, void* stream)
+{
+    const char* what = "vrc_volume_get_voxels";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
+    if (n == 0) return VRC_OK;
+    if (!xyz || !solid_out) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "%s: too many voxels for one launch", what);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(v->device);
+    if (e == hipSuccess) e = order_behind_edits(v, st);
+    const uint32_t* d_xyz = xyz;
+    uint8_t* d_out = solid_out;
+    if (mem == VRC_MEM_HOST) {
+        if (e == hipSuccess) e = stage_reserve(v, (size_t)n * 13u);
+        d_xyz = v->d_stage;
+        d_out = (uint8_t*)v->d_stage + (size_t)n * 12u;
+        if (e == hipSuccess) e = hipMemcpyAsync(v->d_stage, xyz, (size_t)n * 12u, hipMemcpyHostToDevice, st);
+    }
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    hipLaunchKernelGGL(k_get_voxels, grid_for(n), dim3(256), 0, st, (const uint8_t*)v->d_bricks, 1u << v->depth, n, d_xyz, d_out);
+    e = hipGetLastError();
+    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipMemcpyAsync(solid_out, d_out, n, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = finish(v, mem, st, false);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+extern "C" int vrc_volume_count_boxes(vrc_volume* v, uint64_t n, const uint32_t* lo_hi, uint64_t* counts, int mem, void* stream)
+{
+    const char* what = "vrc_volume_count_boxes";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
+    if (n == 0) return VRC_OK;
+    if (!lo_hi || !counts) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (n > 0x7fffffffull) return vrc::fail(VRC_ERR_INVALID, "%s: too many boxes for one launch", what);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(v->device);
+    if (e == hipSuccess) e = order_behind_edits(v, st);
+    const uint32_t* d_boxes = lo_hi;
+    unsigned long long* d_counts = (unsigned long long*)counts;
+    if (mem == VRC_MEM_HOST) {
+        if (e == hipSuccess) e = stage_reserve(v, (size_t)n * 32u);
+        d_counts = (unsigned long long*)v->d_stage;
+        d_boxes = (const uint32_t*)((uint8_t*)v->d_stage + (size_t)n * 8u);
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)d_boxes, lo_hi, (size_t)n * 24u, hipMemcpyHostToDevice, st);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, (size_t)n * 8u, st);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    hipLaunchKernelGGL(k_count_boxes, dim3((uint32_t)n, split_for(v, n)), dim3(256), 0, st, v->d_bricks, 1u << v->depth, d_boxes, d_counts);
+    e = hipGetLastError();
+    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipMemcpyAsync(counts, d_counts, (size_t)n * 8u, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = finish(v, mem, st, false);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
 }
 
 extern "C" int vrc_volume_commit(vrc_volume* v, vrc_scene** out, float* build_ms)

@@ -133,6 +133,17 @@ public:
         return out;
     }
 
+    // the same batch as raw records (include/vrc.h: vrc_hit), e.g. for HipVoxelVolume::fillSpheresAtHits
+    std::vector<vrc_hit> castRaysRecords(const std::vector<Vec3>& positions, const std::vector<Vec3>& directions) const
+    {
+        if (positions.size() != directions.size()) throw std::invalid_argument("castRaysRecords: size mismatch");
+        std::vector<vrc_hit> raw(positions.size());
+        if (!raw.empty())
+            check(vrc_cast_rays(scene_, raw.size(), &positions[0].x, &directions[0].x, nullptr, nullptr, raw.data(), VRC_MEM_HOST, nullptr),
+                  "vrc_cast_rays");
+        return raw;
+    }
+
     // pairs of casts as RayCaster::castRay chains them (raycaster.hpp:131 -> :153; :194 -> :198), device buffers: ray A, then
     // ray B next to A's hit, started below the root as the frame kernels start their secondary rays (vrc_cast_ray_chains);
     // hits_b[i] equals a cast of ray B alone.  Asynchronous on `stream`.
@@ -216,6 +227,64 @@ public:
         if (queue_.empty()) return;
         check(vrc_volume_set_voxels(v_, queue_.size() / 3, queue_.data(), queue_solid_ ? 1 : 0, VRC_MEM_HOST, nullptr), "vrc_volume_set_voxels");
         queue_.clear();
+    }
+    // Brushes, copies and queries (include/vrc.h).  Host-memory forms are synchronous; the *Device forms read device
+    // memory in place and are asynchronous on `stream`.  Every one of them sends the setCell queue first.
+    struct Sphere { int32_t x, y, z, radius; };
+    void fillSpheres(const std::vector<Sphere>& spheres, bool solid)
+    {
+        flush();
+        check(vrc_volume_fill_spheres(v_, spheres.size(), spheres.empty() ? nullptr : &spheres[0].x, solid ? 1 : 0, VRC_MEM_HOST, nullptr),
+              "vrc_volume_fill_spheres");
+    }
+    void fillSpheresDevice(uint64_t n, const int32_t* centre_radius_dev, bool solid, void* stream = nullptr)
+    {
+        flush();
+        check(vrc_volume_fill_spheres(v_, n, centre_radius_dev, solid ? 1 : 0, VRC_MEM_DEVICE, stream), "vrc_volume_fill_spheres");
+    }
+    // one sphere at every record: solid = false digs at the voxel hit, true builds at the empty cell in front of it
+    void fillSpheresAtHits(const std::vector<vrc_hit>& hits, int32_t radius, bool solid)
+    {
+        flush();
+        check(vrc_volume_fill_spheres_at_hits(v_, hits.size(), hits.data(), radius, solid ? 1 : 0, VRC_MEM_HOST, nullptr),
+              "vrc_volume_fill_spheres_at_hits");
+    }
+    // the records vrc_cast_rays(..., VRC_MEM_DEVICE, stream) left on the device: same stream, no host copy of a hit
+    void fillSpheresAtHitsDevice(uint64_t n, const vrc_hit* hits_dev, int32_t radius, bool solid, void* stream = nullptr)
+    {
+        flush();
+        check(vrc_volume_fill_spheres_at_hits(v_, n, hits_dev, radius, solid ? 1 : 0, VRC_MEM_DEVICE, stream), "vrc_volume_fill_spheres_at_hits");
+    }
+    // voxels src_lo + d of `src` -> dst_lo + d of this volume for 0 <= d < size, clipped to both; op = VRC_COPY_*
+    void copyRegion(HipVoxelVolume& src, const uint32_t src_lo[3], const uint32_t size[3], const int32_t dst_lo[3],
+                    int op = VRC_COPY_REPLACE, void* stream = nullptr)
+    {
+        flush();
+        src.flush();
+        check(vrc_volume_copy_region(v_, src.v_, src_lo, size, dst_lo, op, stream), "vrc_volume_copy_region");
+    }
+    std::unique_ptr<HipVoxelVolume> clone()
+    {
+        flush();
+        vrc_volume* v = nullptr;
+        check(vrc_volume_clone(v_, &v), "vrc_volume_clone");
+        return std::unique_ptr<HipVoxelVolume>(new HipVoxelVolume(v));
+    }
+    // xyz: n x 3 coordinates -> 0 / 1 each (0 outside the volume)
+    std::vector<uint8_t> getVoxels(const std::vector<uint32_t>& xyz)
+    {
+        flush();
+        std::vector<uint8_t> out(xyz.size() / 3);
+        check(vrc_volume_get_voxels(v_, out.size(), xyz.data(), out.data(), VRC_MEM_HOST, nullptr), "vrc_volume_get_voxels");
+        return out;
+    }
+    // lo_hi: n x 6 as for fillBox -> solid voxels per box
+    std::vector<uint64_t> countBoxes(const std::vector<uint32_t>& lo_hi)
+    {
+        flush();
+        std::vector<uint64_t> out(lo_hi.size() / 6);
+        check(vrc_volume_count_boxes(v_, out.size(), lo_hi.data(), out.data(), VRC_MEM_HOST, nullptr), "vrc_volume_count_boxes");
+        return out;
     }
     std::unique_ptr<HipLSVO> commit(float* build_ms = nullptr)
     {

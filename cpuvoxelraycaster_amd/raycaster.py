@@ -178,6 +178,62 @@ class VoxelVolume:
     def fillBoxesDevice(self, n, lo_hi_ptr, solid=True, stream=None):
         check(capi.load().vrc_volume_fill_boxes(self._h, n, ptr(lo_hi_ptr), int(bool(solid)), capi.VRC_MEM_DEVICE, ptr(stream)))
 
+    def fillSpheres(self, centre_radius, solid=True):
+        """centre_radius: (n, 4) int32 = centre x y z (signed, may lie outside), radius; the voxels with
+        dx^2 + dy^2 + dz^2 <= r^2 are set or cleared.  Synchronous."""
+        cr = np.ascontiguousarray(centre_radius, np.int32).reshape(-1, 4)
+        check(capi.load().vrc_volume_fill_spheres(self._h, cr.shape[0], ptr(cr), int(bool(solid)), capi.VRC_MEM_HOST, None))
+
+    def fillSpheresDevice(self, n, centre_radius_ptr, solid=True, stream=None):
+        check(capi.load().vrc_volume_fill_spheres(self._h, n, ptr(centre_radius_ptr), int(bool(solid)), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def fillSpheresAtHits(self, hits, radius, solid=True):
+        """One sphere at every castRays record: solid=False digs at the voxel hit, solid=True builds at the empty cell the
+        ray came through; misses, LOD cut-offs and records without such a cell are skipped.  Synchronous."""
+        hits = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+        check(capi.load().vrc_volume_fill_spheres_at_hits(self._h, hits.shape[0], ptr(hits), int(radius), int(bool(solid)), capi.VRC_MEM_HOST, None))
+
+    def fillSpheresAtHitsDevice(self, n, hits_ptr, radius, solid=True, stream=None):
+        """the same over the records castRaysDevice left in device memory; on the same stream no host copy and no
+        synchronisation lies between the cast and the edit"""
+        check(capi.load().vrc_volume_fill_spheres_at_hits(self._h, n, ptr(hits_ptr), int(radius), int(bool(solid)), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def copyRegion(self, src, src_lo, size, dst_lo, op=capi.VRC_COPY_REPLACE, stream=None):
+        """Voxels src_lo + d of the volume `src` (any depth, same device) go to dst_lo + d of this one for 0 <= d < size,
+        clipped to both; op = capi.VRC_COPY_REPLACE / _OR / _ANDNOT.  Asynchronous on `stream`."""
+        src_lo = np.ascontiguousarray(src_lo, np.uint32).reshape(3)
+        size = np.ascontiguousarray(size, np.uint32).reshape(3)
+        dst_lo = np.ascontiguousarray(dst_lo, np.int32).reshape(3)
+        check(capi.load().vrc_volume_copy_region(self._h, src._h, ptr(src_lo), ptr(size), ptr(dst_lo), int(op), ptr(stream)))
+
+    def clone(self):
+        """A new volume with this one's occupancy (after every edit issued so far) and albedo tables: the undo snapshot."""
+        other = VoxelVolume.__new__(VoxelVolume)
+        other._h = C.c_void_p()
+        check(capi.load().vrc_volume_clone(self._h, C.byref(other._h)))
+        other.depth, other.device = self.depth, self.device
+        return other
+
+    def getVoxels(self, xyz):
+        """uint8 0 / 1 per (n, 3) voxel coordinate, 0 outside the volume.  Synchronous."""
+        xyz = np.ascontiguousarray(xyz, np.uint32).reshape(-1, 3)
+        out = np.zeros(xyz.shape[0], np.uint8)
+        check(capi.load().vrc_volume_get_voxels(self._h, xyz.shape[0], ptr(xyz), ptr(out), capi.VRC_MEM_HOST, None))
+        return out
+
+    def getVoxelsDevice(self, n, xyz_ptr, solid_out_ptr, stream=None):
+        check(capi.load().vrc_volume_get_voxels(self._h, n, ptr(xyz_ptr), ptr(solid_out_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def countBoxes(self, lo_hi):
+        """solid voxels per (n, 6) box (lo inclusive, hi exclusive, clipped to the volume), uint64.  Synchronous."""
+        lo_hi = np.ascontiguousarray(lo_hi, np.uint32).reshape(-1, 6)
+        out = np.zeros(lo_hi.shape[0], np.uint64)
+        check(capi.load().vrc_volume_count_boxes(self._h, lo_hi.shape[0], ptr(lo_hi), ptr(out), capi.VRC_MEM_HOST, None))
+        return out
+
+    def countBoxesDevice(self, n, lo_hi_ptr, counts_ptr, stream=None):
+        check(capi.load().vrc_volume_count_boxes(self._h, n, ptr(lo_hi_ptr), ptr(counts_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
+
     def commit(self, textures=None):
         """A NEW LSVO of the current occupancy (build_ms = device time of the sweeps); the volume stays editable."""
         handle, ms = C.c_void_p(), C.c_float()

@@ -201,6 +201,43 @@ int vrc_volume_solid_count(vrc_volume *v, uint64_t *count);
  * voxel).  neighbour / has_neighbour may be NULL.  A miss or an LOD cut-off is VRC_ERR_INVALID. */
 int vrc_hit_to_voxel(uint32_t depth, const vrc_hit *hit, uint32_t voxel[3], uint32_t neighbour[3], int *has_neighbour);
 
+/* Brushes, region copies and queries: what an editor does next, without leaving the device.  `mem`, `stream`, n == 0 and
+ * the one-value-per-call rule are those of vrc_volume_set_voxels; the calls that read the occupancy are ordered behind
+ * the volume's last asynchronous edit.
+ *
+ * n spheres (n x 4 int32: centre x y z, radius r): voxel (x, y, z) is set or cleared iff
+ * (x-cx)^2 + (y-cy)^2 + (z-cz)^2 <= r^2 in integers.  Centres are signed and may lie outside the volume (the sphere is
+ * clipped); r == 0 is the centre voxel alone, r < 0 is empty; a sphere with a centre coordinate beyond +-2^20 or r > 2^20 is
+ * dropped.  Cost follows the bricks inside each sphere's own bounding box (whole 32-bit words are stored as such).  A
+ * sphere is one workgroup column: a batch of more than 4096 gets one 256-thread workgroup per sphere whatever its
+ * radius, so thousands of LARGE spheres in one call each walk their bounding box on four waves. */
+int vrc_volume_fill_spheres(vrc_volume *v, uint64_t n, const int32_t *centre_radius, int solid, int mem, void *stream);
+/* One sphere of `radius` (0 .. 2^20) at every record of a ray batch, the centres computed on the device exactly as
+ * vrc_hit_to_voxel(vrc_volume_depth(v), &hits[i], ...) computes them: solid == 0 (dig) at `voxel`, solid != 0 (build) at
+ * `neighbour`.  A record vrc_hit_to_voxel refuses (miss, LOD cut-off, position outside [1, 2)^3, NaN) is skipped, and so
+ * is a build at a record without a neighbour.  With VRC_MEM_DEVICE, vrc_cast_rays(..., VRC_MEM_DEVICE, stream) followed
+ * by this call on the same stream edits the volume with no host copy of a hit.  The centres pass through the volume's
+ * grow-only staging block (16 bytes per record). */
+int vrc_volume_fill_spheres_at_hits(vrc_volume *v, uint64_t n, const vrc_hit *hits, int32_t radius, int solid, int mem, void *stream);
+/* Voxel src_lo + d of `src` goes to dst_lo + d of `dst` for 0 <= d < size, clipped to both volumes (what falls outside
+ * either is neither read nor written).  The volumes may have different depths (a 32^3 clipboard stamped into a 512^3
+ * world) and must be two different volumes on one device; any voxel offset is legal.  Asynchronous on `stream`: ordered
+ * behind the last asynchronous edits of both volumes, recorded as dst's last edit.  Device-memory edits do not wait for
+ * that record: do not edit src OR dst on ANOTHER stream before the copy has run (a partly covered word of dst is a plain
+ * read-modify-write, so such an edit of dst can be lost, and one of src may or may not be copied). */
+#define VRC_COPY_REPLACE 0   /* dst = src inside the region */
+#define VRC_COPY_OR      1   /* dst |= src   (paste a model, keep what is there) */
+#define VRC_COPY_ANDNOT  2   /* dst &= ~src  (carve the model's shape out) */
+int vrc_volume_copy_region(vrc_volume *dst, vrc_volume *src, const uint32_t src_lo[3], const uint32_t size[3],
+                           const int32_t dst_lo[3], int op, void *stream);
+/* A new volume with src's depth, device, occupancy (after every edit issued so far) and albedo tables: the undo
+ * snapshot.  Synchronous. */
+int vrc_volume_clone(vrc_volume *src, vrc_volume **out);
+/* solid_out[i] = 0 / 1 for voxel xyz[3i..3i+2], 0 outside the volume.  counts[i] = solid voxels in box i (n x 6 uint32 as
+ * for vrc_volume_fill_boxes, clipped; empty or inverted = 0), so one whole-volume box equals vrc_volume_solid_count. */
+int vrc_volume_get_voxels(vrc_volume *v, uint64_t n, const uint32_t *xyz, uint8_t *solid_out, int mem, void *stream);
+int vrc_volume_count_boxes(vrc_volume *v, uint64_t n, const uint32_t *lo_hi, uint64_t *counts, int mem, void *stream);
+
 /* ---- dense grid: Grid3D<X,Y,Z> (grid_3d.hpp:10-138) ------------------- */
 
 /* cells[(x*Y + y)*Z + z] = Cell::Type (0 = Empty). */

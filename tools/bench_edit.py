@@ -11,6 +11,17 @@ For the 256^3, 512^3 and 1024^3 FastNoise terrain:
                    same process, alternating A B A B, `--pairs` pairs after one warm-up pair: medians, the baseline's
                    own min / max over its repetitions, and whether the commit's median lies within that spread
                    (commit_within_baseline_spread: commit median <= baseline max).
+With --brushes (written to profiles/edit/bench_brushes.json by whoever runs it), the brushes, copies and queries instead,
+at 512^3 and 1024^3, device memory, device time by events, one warm-up, A B A B in one process, `--pairs` pairs, median
+and range:
+  sphere_r{4,32,128}   one vrc_volume_fill_spheres sphere against vrc_volume_fill_boxes on that sphere's bounding box
+  spheres_10k_r3       10^4 spheres of radius 3 in one batch
+  spray_10k            cast 10^4 rays + brush at hits (radius 3) + commit on one stream, against the host round trip
+                       (cast to host memory, vrc_hit_to_voxel per record, vrc_volume_set_voxels of the enumerated voxels,
+                       commit); both end-to-end wall times
+  copy_64              a 64^3 region copy at an aligned and at an odd offset
+  clone                a whole-volume clone (wall time) and the fraction of HBM speed its bytes moved at
+  get_voxels_1m, count_boxes_1k_16
 No threshold is applied; the numbers are reported."""
 import argparse
 import json
@@ -36,6 +47,145 @@ def device_ms(fn, repeats=5):
         if i:                                        # the first run warms up
             out.append(a.elapsed_time(b))
     return statistics.median(out)
+
+
+def stat(values, digits=5):
+    return {"median": round(statistics.median(values), digits), "min": round(min(values), digits), "max": round(max(values), digits)}
+
+
+def ab_device_ms(fa, fb, pairs):
+    """A B A B: device time of each by events on the NULL stream, one warm-up pair first"""
+    import torch
+    out = ([], [])
+    for i in range(pairs + 1):
+        for k, fn in enumerate((fa, fb)):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if i:
+                out[k].append(a.elapsed_time(b))
+    return stat(out[0]), stat(out[1])
+
+
+def ab_wall_ms(fa, fb, pairs):
+    import torch
+    out = ([], [])
+    for i in range(pairs + 1):
+        for k, fn in enumerate((fa, fb)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if i:
+                out[k].append((time.perf_counter() - t0) * 1e3)
+    return stat(out[0], 3), stat(out[1], 3)
+
+
+HBM_BYTES_PER_S = 8.0e12     # MI355X peak
+
+
+def bench_brushes(vrc, depth, pairs):
+    import torch
+    S = 1 << depth
+    rng = np.random.default_rng(depth)
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    volume = vrc.VoxelVolume.fromScene(scene)
+    res = {"size": S, "pairs": pairs}
+    flip = [False]
+    m = S // 2
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).cuda()
+
+    for r in (4, 32, 128):
+        sphere = dev(np.array([(m, m, m, r)], np.int32))
+        box = dev(np.array([(m - r, m - r, m - r, m + r + 1, m + r + 1, m + r + 1)], np.uint32))
+
+        def fa():
+            flip[0] = not flip[0]
+            volume.fillSpheresDevice(1, sphere.data_ptr(), flip[0], None)
+
+        def fb():
+            volume.fillBoxesDevice(1, box.data_ptr(), flip[0], None)
+        a, b = ab_device_ms(fa, fb, pairs)
+        res[f"sphere_r{r}"] = {"sphere_ms": a, "bounding_box_ms": b, "sphere_not_slower": bool(a["median"] <= b["median"])}
+    spheres = dev(np.concatenate([rng.integers(0, S, (10000, 3)), np.full((10000, 1), 3)], axis=1).astype(np.int32))
+    res["spheres_10k_r3_ms"] = ab_device_ms(lambda: volume.fillSpheresDevice(10000, spheres.data_ptr(), True, None),
+                                            lambda: volume.fillSpheresDevice(10000, spheres.data_ptr(), False, None), pairs)[0]
+    volume.close()
+
+    # spray: 10^4 camera rays, dig radius 3 at every hit, commit -- device path against today's host round trip
+    volume = vrc.VoxelVolume.fromScene(scene)
+    other = vrc.VoxelVolume.fromScene(scene)
+    cam = np.array(vrc.reference_camera_position(depth), np.float32) / np.float32(S) + np.float32(1.0)
+    d = rng.normal(size=(10000, 3)).astype(np.float32) * np.float32(0.3) + np.array([0.0, 0.5, 0.8], np.float32)
+    d /= np.linalg.norm(d, axis=1, keepdims=True).astype(np.float32)
+    org = np.tile(cam, (10000, 1)).astype(np.float32)
+    t_org, t_dir, t_hits = dev(org), dev(d), torch.zeros(10000 * 12, dtype=torch.int32).cuda()
+    g = np.mgrid[-3:4, -3:4, -3:4].reshape(3, -1).T
+    ball = g[(g * g).sum(1) <= 9]
+    L = vrc.capi.load()
+    import ctypes as C
+    stream = C.c_void_p()
+    vrc.capi.check(L.vrc_stream_create(0, C.byref(stream)))
+    counts = {}
+
+    def device_path():
+        scene.castRaysDevice(10000, t_org.data_ptr(), t_dir.data_ptr(), t_hits.data_ptr(), stream=stream)
+        volume.fillSpheresAtHitsDevice(10000, t_hits.data_ptr(), 3, False, stream)
+        volume.commit().close()
+
+    def host_path():
+        hits = scene.castRays(org, d)
+        xyz = []
+        for h in hits[(hits["hit"] & 0xff) == 1]:
+            xyz.append(np.array(vrc.hit_to_voxel(depth, h)[0]) + ball)
+        if xyz:
+            xyz = np.concatenate(xyz)
+            xyz = xyz[np.all((xyz >= 0) & (xyz < S), axis=1)]
+            other.setVoxels(xyz.astype(np.uint32), False)
+            counts["voxels_sent"] = int(len(xyz))
+        other.commit().close()
+    a, b = ab_wall_ms(device_path, host_path, pairs)
+    assert volume.solidCount() == other.solidCount()
+    res["spray_10k"] = {"device_path_wall_ms": a, "host_round_trip_wall_ms": b, **counts}
+    L.vrc_stream_synchronize(0, stream)
+    L.vrc_stream_destroy(0, stream)
+    other.close()
+
+    # copies
+    clip = vrc.VoxelVolume(6)
+    clip.fillSpheres([(32, 32, 32, 30)], True)
+    a, b = ab_device_ms(lambda: volume.copyRegion(clip, [0, 0, 0], [64, 64, 64], [m, m, m], 0, None),
+                        lambda: volume.copyRegion(clip, [0, 0, 0], [64, 64, 64], [m + 1, m + 1, m + 3], 0, None), pairs)
+    res["copy_64_ms"] = {"aligned": a, "odd_offset": b}
+    walls = []
+    for i in range(pairs + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        c = volume.clone()
+        if i:
+            walls.append((time.perf_counter() - t0) * 1e3)
+        c.close()
+    moved = 2 * (S ** 3 // 8)                               # read + write of the brick bytes
+    res["clone"] = {"wall_ms": stat(walls, 3), "bytes_moved": moved,
+                    "fraction_of_hbm_peak": round(moved / HBM_BYTES_PER_S / (statistics.median(walls) * 1e-3), 4)}
+
+    # queries
+    xyz = dev(rng.integers(0, S, (1000000, 3)).astype(np.uint32))
+    out = torch.zeros(1000000, dtype=torch.uint8).cuda()
+    lo = rng.integers(0, S - 16, (1000, 3))
+    boxes = dev(np.concatenate([lo, lo + 16], axis=1).astype(np.uint32))
+    cnt = torch.zeros(1000, dtype=torch.int64).cuda()
+    a, b = ab_device_ms(lambda: volume.getVoxelsDevice(1000000, xyz.data_ptr(), out.data_ptr(), None),
+                        lambda: volume.countBoxesDevice(1000, boxes.data_ptr(), cnt.data_ptr(), None), pairs)
+    res["get_voxels_1m_ms"], res["count_boxes_1k_16_ms"] = a, b
+    volume.close()
+    clip.close()
+    scene.close()
+    return res
 
 
 def bench_depth(vrc, depth, pairs):
@@ -95,16 +245,19 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--depths", type=int, nargs="+", default=[8, 9, 10])
     ap.add_argument("--pairs", type=int, default=5)
+    ap.add_argument("--brushes", action="store_true", help="time the brushes, copies and queries (depths 9 and 10 unless --depths is given)")
     args = ap.parse_args()
+    if args.brushes and args.depths == [8, 9, 10]:
+        args.depths = [9, 10]
     import __graft_entry__ as g
     g.build()
     import torch
     import cpuvoxelraycaster_amd as vrc
     if not torch.cuda.is_available():
         raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-    out = {"bench": "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
+    out = {"bench": "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
     for d in args.depths:
-        out["depths"][str(d)] = bench_depth(vrc, d, max(1, args.pairs))
+        out["depths"][str(d)] = (bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
     print(json.dumps(out))
 
 
