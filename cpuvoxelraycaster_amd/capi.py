@@ -13,6 +13,8 @@ LIB_PATH = os.path.join(PKG, "libvrc_hip.so")
 
 VRC_MEM_HOST, VRC_MEM_DEVICE = 0, 1
 VRC_COPY_REPLACE, VRC_COPY_OR, VRC_COPY_ANDNOT = 0, 1, 2
+VRC_CONNECT_FACES, VRC_CONNECT_ALL = 6, 26
+VRC_FLOOD_SOLID, VRC_FLOOD_EMPTY = 0, 1
 
 HIT_DTYPE = np.dtype([
     ("position", "<f4", 3), ("normal", "<f4", 3), ("voxel_coord", "<f4", 2),
@@ -44,6 +46,10 @@ class FrameParams(C.Structure):
 class FrameStats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("sum_complexity", C.c_uint64),
                 ("primary_hits", C.c_uint64), ("pixels", C.c_uint64), ("iterations_not_executed", C.c_uint64)]
+
+
+class FloodStats(C.Structure):
+    _fields_ = [("reached", C.c_uint64), ("sweeps", C.c_uint32), ("converged", C.c_uint32)]
 
 
 # every symbol include/vrc.h declares: (restype, argtypes)
@@ -138,6 +144,7 @@ SYMBOLS = {
     "vrc_volume_clone": (_int, [_vp, C.POINTER(_vp)]),
     "vrc_volume_get_voxels": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
     "vrc_volume_count_boxes": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
+    "vrc_volume_flood": (_int, [_vp, _vp, _int, _int, _u32, C.POINTER(FloodStats)]),
     "vrc_renderer_set_scene": (_int, [_vp, _vp]),
     "vrc_hit_to_voxel": (_int, [_u32, _vp, _vp, _vp, C.POINTER(_int)]),
 }

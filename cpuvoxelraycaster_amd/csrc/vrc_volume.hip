@@ -9,7 +9,8 @@
 // bit-identical to compileSVO of the voxel set, into a NEW scene.  Batched edits are 32-bit vector atomics
 // (atomicOr / atomicAnd) on the words that hold the bricks, or whole-word stores where a box covers a word.
 // Brushes (spheres, spheres at the hits of a ray batch), region copies between volumes and the two queries (single
-// voxels, solid voxels per box) walk the same rows of words as the boxes do.
+// voxels, solid voxels per box) walk the same rows of words as the boxes do.  The flood fill by connectivity
+// (vrc_volume_flood) has its kernels in vrc_flood.hip; the entry point, its ordering and its scratch block are here.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -17,6 +18,7 @@
 
 #include "../../include/vrc.h"
 #include "vrc_build_sweeps.h"
+#include "vrc_flood.h"
 
 struct vrc_volume {
     int device = 0;
@@ -30,6 +32,9 @@ struct vrc_volume {
     // host-memory form of the edit calls: grow-only staging block
     uint32_t* d_stage = nullptr;
     size_t stage_cap = 0;
+    // vrc_volume_flood with this volume as `region`: grow-only tile flags and sweep counters
+    uint32_t* d_flood = nullptr;
+    size_t flood_cap = 0;
     // the last asynchronous edit: commit / download / solid_count run on the NULL stream and wait for it first.  The flag
     // says that the event has been recorded at least once; it is never cleared, because a wait only orders ONE stream
     // behind the edit and the next caller may bring another.
@@ -422,6 +427,7 @@ void volume_free(vrc_volume* v)
     if (v->d_tex) (void)hipFree(v->d_tex);
     if (v->d_count) (void)hipFree(v->d_count);
     if (v->d_stage) (void)hipFree(v->d_stage);
+    if (v->d_flood) (void)hipFree(v->d_flood);
     v->grids.release();
     delete v;
 }
@@ -740,6 +746,41 @@ extern "C" int vrc_volume_count_boxes(vrc_volume* v, uint64_t n, const uint32_t*
     if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipMemcpyAsync(counts, d_counts, (size_t)n * 8u, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = finish(v, mem, st, false);
     if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+extern "C" int vrc_volume_flood(vrc_volume* region, vrc_volume* medium, int connectivity, int through, uint32_t max_sweeps, vrc_flood_stats* stats)
+{
+    const char* what = "vrc_volume_flood";
+    if (!region || !medium) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (region == medium) return vrc::fail(VRC_ERR_INVALID, "%s: region and medium are the same volume", what);
+    if (connectivity != VRC_CONNECT_FACES && connectivity != VRC_CONNECT_ALL) return vrc::fail(VRC_ERR_INVALID, "%s: connectivity %d is neither 6 nor 26", what, connectivity);
+    if (through != VRC_FLOOD_SOLID && through != VRC_FLOOD_EMPTY) return vrc::fail(VRC_ERR_INVALID, "%s: bad through %d", what, through);
+    if (region->depth != medium->depth) return vrc::fail(VRC_ERR_INVALID, "%s: volumes of depths %u and %u", what, region->depth, medium->depth);
+    if (region->device != medium->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, region->device, medium->device);
+    // the NULL stream, behind the last asynchronous edit of either volume, as commit / download are
+    hipError_t e = hipSetDevice(region->device);
+    if (e == hipSuccess) e = wait_for_edits(region);
+    if (e == hipSuccess) e = wait_for_edits(medium);
+    const size_t need = vrc::flood_scratch_bytes(region->depth);
+    if (e == hipSuccess && region->flood_cap < need) {
+        if (region->d_flood) (void)hipFree(region->d_flood);
+        region->d_flood = nullptr; region->flood_cap = 0;
+        if ((e = hipMalloc((void**)&region->d_flood, need)) == hipSuccess) region->flood_cap = need;
+    }
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    uint32_t sweeps = 0, converged = 0;
+    e = vrc::flood_run(region->d_bricks, medium->d_bricks, region->depth, connectivity, through,
+                       max_sweeps ? max_sweeps : vrc::flood_sweep_bound(region->depth), region->d_flood, nullptr, &sweeps, &converged);
+    // recorded as region's last edit: edits on streams made by vrc_stream_create do not wait for the NULL stream
+    if (e == hipSuccess) e = finish(region, VRC_MEM_DEVICE, nullptr, true);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    if (stats) {
+        uint64_t reached = 0;
+        const int rc = vrc_volume_solid_count(region, &reached);
+        if (rc) return rc;
+        stats->reached = reached; stats->sweeps = sweeps; stats->converged = converged;
+    }
     return VRC_OK;
 }
 

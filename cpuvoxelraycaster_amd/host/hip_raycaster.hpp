@@ -91,7 +91,7 @@ inline std::vector<uint8_t> loadBMP(const std::string& path, uint32_t* width = n
 class HipLSVO {
 public:
     // LSVO(const SVO<N>&) + compileSVO replaced by a pre-compiled LNode array
-    HipLSVO(const vrc_lnode* lnodes, uint64_t n_nodes, uint32_t depth, int device = 0)
+    HipLSVO(const vrc_lnode* lnodes, uint64_t n_nodes, uint32_t depth, int device = 0) : device_(device)
     {
         check(vrc_scene_create(lnodes, n_nodes, depth, device, &scene_), "vrc_scene_create");
     }
@@ -100,7 +100,7 @@ public:
     {
         vrc_scene* s = nullptr;
         check(vrc_scene_build_fastnoise_terrain(seed, depth, device, &s, build_ms), "vrc_scene_build_fastnoise_terrain");
-        return std::unique_ptr<HipLSVO>(new HipLSVO(s));
+        return std::unique_ptr<HipLSVO>(new HipLSVO(s, device));
     }
     ~HipLSVO() { vrc_scene_destroy(scene_); }
     HipLSVO(const HipLSVO&) = delete;
@@ -169,6 +169,7 @@ public:
 
     vrc_scene* handle() const { return scene_; }
     uint32_t depth() const { return vrc_scene_depth(scene_); }
+    int device() const { return device_; }
     Cell cell;   // lsvo.hpp:289
 
 private:
@@ -184,8 +185,9 @@ private:
         return p;
     }
     friend class HipVoxelVolume;
-    explicit HipLSVO(vrc_scene* adopted) : scene_(adopted) {}
+    HipLSVO(vrc_scene* adopted, int device) : scene_(adopted), device_(device) {}
     vrc_scene* scene_ = nullptr;
+    int device_ = 0;
 };
 
 // What SVO::setCell + compileSVO are to the reference (svo.hpp:72, lsvo_utils.cpp:4), on the device and repeatable: the
@@ -194,13 +196,13 @@ private:
 // that walk it are done, then drop it.  Not re-entrant.  INTEGRATION.md section 2a.
 class HipVoxelVolume {
 public:
-    explicit HipVoxelVolume(uint32_t depth, int device = 0) { check(vrc_volume_create(depth, device, &v_), "vrc_volume_create"); }
+    explicit HipVoxelVolume(uint32_t depth, int device = 0) : device_(device) { check(vrc_volume_create(depth, device, &v_), "vrc_volume_create"); }
     // makes an existing scene (e.g. HipLSVO::fromFastNoiseTerrain) editable; takes over its albedo tables
     static std::unique_ptr<HipVoxelVolume> fromScene(const HipLSVO& svo)
     {
         vrc_volume* v = nullptr;
         check(vrc_volume_from_scene(svo.handle(), &v), "vrc_volume_from_scene");
-        return std::unique_ptr<HipVoxelVolume>(new HipVoxelVolume(v));
+        return std::unique_ptr<HipVoxelVolume>(new HipVoxelVolume(v, svo.device()));
     }
     ~HipVoxelVolume() { vrc_volume_destroy(v_); }
     HipVoxelVolume(const HipVoxelVolume&) = delete;
@@ -268,7 +270,7 @@ public:
         flush();
         vrc_volume* v = nullptr;
         check(vrc_volume_clone(v_, &v), "vrc_volume_clone");
-        return std::unique_ptr<HipVoxelVolume>(new HipVoxelVolume(v));
+        return std::unique_ptr<HipVoxelVolume>(new HipVoxelVolume(v, device_));
     }
     // xyz: n x 3 coordinates -> 0 / 1 each (0 outside the volume)
     std::vector<uint8_t> getVoxels(const std::vector<uint32_t>& xyz)
@@ -286,12 +288,41 @@ public:
         check(vrc_volume_count_boxes(v_, out.size(), lo_hi.data(), out.data(), VRC_MEM_HOST, nullptr), "vrc_volume_count_boxes");
         return out;
     }
+    // Flood fill by connectivity (include/vrc.h: vrc_volume_flood): this volume's solid voxels are the seeds; afterwards it
+    // holds exactly the voxels of `medium` (its solid ones, or its empty ones with through_empty) joined to a seed by face
+    // neighbours (6) or face / edge / corner neighbours (26).  max_sweeps = 0 runs to convergence; a capped call may return
+    // converged == 0 with a valid partial result, and calling again continues.  Synchronous.
+    vrc_flood_stats flood(HipVoxelVolume& medium, int connectivity = VRC_CONNECT_FACES, bool through_empty = false, uint32_t max_sweeps = 0)
+    {
+        flush();
+        medium.flush();
+        vrc_flood_stats st;
+        check(vrc_volume_flood(v_, medium.v_, connectivity, through_empty ? VRC_FLOOD_EMPTY : VRC_FLOOD_SOLID, max_sweeps, &st), "vrc_volume_flood");
+        return st;
+    }
+    // Drops what no longer holds on to the anchors (lo_hi: n x 6 as for fillBox): afterwards this volume holds only the solid
+    // voxels joined to a solid voxel inside an anchor box, and the rest -- the debris -- is returned as a new volume.
+    std::unique_ptr<HipVoxelVolume> keepConnected(const std::vector<uint32_t>& anchor_lo_hi, int connectivity = VRC_CONNECT_FACES)
+    {
+        flush();
+        const uint32_t d = depth(), S = 1u << d;
+        const uint32_t zero[3] = {0, 0, 0}, all[3] = {S, S, S};
+        const int32_t at[3] = {0, 0, 0};
+        HipVoxelVolume supported(d, device_);
+        if (!anchor_lo_hi.empty())
+            check(vrc_volume_fill_boxes(supported.v_, anchor_lo_hi.size() / 6, anchor_lo_hi.data(), 1, VRC_MEM_HOST, nullptr), "vrc_volume_fill_boxes");
+        supported.flood(*this, connectivity);
+        std::unique_ptr<HipVoxelVolume> debris = clone();
+        debris->copyRegion(supported, zero, all, at, VRC_COPY_ANDNOT);
+        copyRegion(supported, zero, all, at, VRC_COPY_REPLACE);
+        return debris;       // `supported` is destroyed behind the copies: vrc_volume_destroy waits for the device
+    }
     std::unique_ptr<HipLSVO> commit(float* build_ms = nullptr)
     {
         flush();
         vrc_scene* s = nullptr;
         check(vrc_volume_commit(v_, &s, build_ms), "vrc_volume_commit");
-        return std::unique_ptr<HipLSVO>(new HipLSVO(s));
+        return std::unique_ptr<HipLSVO>(new HipLSVO(s, device_));
     }
     uint64_t solidCount()
     {
@@ -304,8 +335,9 @@ public:
     vrc_volume* handle() const { return v_; }
 
 private:
-    explicit HipVoxelVolume(vrc_volume* adopted) : v_(adopted) {}
+    HipVoxelVolume(vrc_volume* adopted, int device) : v_(adopted), device_(device) {}
     vrc_volume* v_ = nullptr;
+    int device_ = 0;
     std::vector<uint32_t> queue_;
     bool queue_solid_ = true;
 };

@@ -234,6 +234,32 @@ class VoxelVolume:
     def countBoxesDevice(self, n, lo_hi_ptr, counts_ptr, stream=None):
         check(capi.load().vrc_volume_count_boxes(self._h, n, ptr(lo_hi_ptr), ptr(counts_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
 
+    def flood(self, medium, connectivity=6, through_empty=False, max_sweeps=0):
+        """Flood fill by connectivity (include/vrc.h: vrc_volume_flood): this volume's solid voxels are the seeds; afterwards
+        it holds exactly the voxels of `medium` (its solid ones, or its empty ones with through_empty) joined to a seed by
+        face neighbours (connectivity=6) or face / edge / corner neighbours (26).  max_sweeps=0 runs to convergence; a capped
+        call may return converged == 0 with a valid partial result, and calling again continues.  Synchronous.  Returns
+        capi.FloodStats (reached, sweeps, converged)."""
+        st = capi.FloodStats()
+        check(capi.load().vrc_volume_flood(self._h, medium._h, int(connectivity), capi.VRC_FLOOD_EMPTY if through_empty else capi.VRC_FLOOD_SOLID,
+                                           int(max_sweeps), C.byref(st)))
+        return st
+
+    def keepConnected(self, anchor_boxes, connectivity=6):
+        """Drops what no longer holds on to the anchors: afterwards this volume holds only the solid voxels joined to a
+        solid voxel inside one of the (n, 6) anchor boxes, and the rest -- the debris -- is returned as a new volume."""
+        S = 1 << self.depth
+        whole = ((0, 0, 0), (S, S, S), (0, 0, 0))
+        supported = VoxelVolume(self.depth, self.device)
+        supported.fillBoxes(anchor_boxes)
+        supported.flood(self, connectivity)
+        debris = self.clone()
+        debris.copyRegion(supported, *whole, op=capi.VRC_COPY_ANDNOT)
+        self.copyRegion(supported, *whole, op=capi.VRC_COPY_REPLACE)
+        # the copies run on the NULL stream; `supported` is destroyed behind them (vrc_volume_destroy waits for the device)
+        supported.close()
+        return debris
+
     def commit(self, textures=None):
         """A NEW LSVO of the current occupancy (build_ms = device time of the sweeps); the volume stays editable."""
         handle, ms = C.c_void_p(), C.c_float()

@@ -238,6 +238,38 @@ int vrc_volume_clone(vrc_volume *src, vrc_volume **out);
 int vrc_volume_get_voxels(vrc_volume *v, uint64_t n, const uint32_t *xyz, uint8_t *solid_out, int mem, void *stream);
 int vrc_volume_count_boxes(vrc_volume *v, uint64_t n, const uint32_t *lo_hi, uint64_t *counts, int mem, void *stream);
 
+/* Flood fill by connectivity, on the device: which voxels hold on to the ground, which cave is enclosed, which piece lies
+ * under the crosshair.  M = the voxels of `medium` that are solid (VRC_FLOOD_SOLID) or empty (VRC_FLOOD_EMPTY); the solid
+ * voxels of `region` on entry are the seeds, put there with any edit call.  On return with converged == 1, `region` is
+ * exactly the set of voxels of M joined to a seed in M by a chain of neighbours (sharing a face: VRC_CONNECT_FACES; a face,
+ * an edge or a corner: VRC_CONNECT_ALL) that lies in M.  Seeds outside M are dropped.  The volume's faces are walls: no
+ * wrap-around, and nothing beyond them counts as empty.  The result is unique: it does not depend on scheduling or on the
+ * number of sweeps.  `medium` is only read; apply the result with vrc_volume_copy_region (VRC_COPY_ANDNOT removes the
+ * region from a clone of the medium: what is NOT joined to the seeds).
+ *
+ * The device works in global sweeps over 32^3-voxel tiles, each iterated to its local fixed point; only tiles at the
+ * frontier do work.  max_sweeps caps the sweeps of this call; 0 = the library's bound, 8^depth + 1: a sweep that sets no
+ * voxel has read the final state everywhere and ends the flood, every sweep before it sets at least one voxel of M, and M
+ * has at most 8^depth (a sweep is expected to carry the frontier across a tile; no sweep count has been measured yet).
+ * If the cap comes first the call still returns VRC_OK, with converged == 0 and a valid partial result in `region`: a
+ * superset of the seeds in M and a subset of the answer.  The operation is monotone, so calling again continues from
+ * there, and any sequence of capped calls ends at the region one uncapped call gives.  Every call starts from the region
+ * alone (no frontier is kept between calls), so the first sweep of a continuing call stages every tile that already holds
+ * a region voxel before the frontier tracking takes over: a host with a frame budget pays that once per call.
+ *
+ * region and medium: two different volumes of one depth on one device.  Synchronous (the host decides convergence), on
+ * the NULL stream, ordered behind the last asynchronous edit of both volumes and recorded as region's last edit.
+ * stats (may be NULL): reached = solid voxels of region afterwards, sweeps = global sweeps issued (counters are read back
+ * every few sweeps, so a few more than needed), converged.  region keeps a grow-only scratch block (tile flags and
+ * counters, 384 KiB at depth 10). */
+#define VRC_CONNECT_FACES 6     /* neighbours share a face */
+#define VRC_CONNECT_ALL   26    /* neighbours share a face, an edge or a corner */
+#define VRC_FLOOD_SOLID 0       /* travel through the solid voxels of `medium` */
+#define VRC_FLOOD_EMPTY 1       /* travel through its empty voxels (caves, the air) */
+typedef struct vrc_flood_stats { uint64_t reached; uint32_t sweeps; uint32_t converged; } vrc_flood_stats;
+int vrc_volume_flood(vrc_volume *region, vrc_volume *medium, int connectivity, int through,
+                     uint32_t max_sweeps, vrc_flood_stats *stats);
+
 /* ---- dense grid: Grid3D<X,Y,Z> (grid_3d.hpp:10-138) ------------------- */
 
 /* cells[(x*Y + y)*Z + z] = Cell::Type (0 = Empty). */

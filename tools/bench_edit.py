@@ -22,6 +22,16 @@ and range:
   copy_64              a 64^3 region copy at an aligned and at an odd offset
   clone                a whole-volume clone (wall time) and the fraction of HBM speed its bytes moved at
   get_voxels_1m, count_boxes_1k_16
+With --flood (written to profiles/edit/bench_flood.json by whoever runs it), vrc_volume_flood at 512^3, device time by
+events around the synchronous call, one warm-up, A B A B in one process against B = reading region and medium once (two
+vrc_volume_solid_count calls, 32 MiB), `--pairs` pairs, median and range, with the sweeps issued and
+read_once x sweeps as the floor a flood without frontier tracking could not beat:
+  terrain_from_bottom      the FastNoise terrain's solid voxels from the slab its columns stand on
+  dug_terrain_from_bottom  the same after 400 sphere digs of radius 12 at ray hits
+  air_from_top             the EMPTY flood of the air above the dug terrain from the slab y = S - 1
+  serpentine               the worst case: a one-voxel path of 1024 lines through every tile, from its first voxel
+  host_round_trip          what the flood replaces, on the dug terrain: vrc_volume_download, a labelling pass in numpy
+                           (tests/flood_model.py), upload of the result as y runs through vrc_volume_fill_boxes; wall times
 No threshold is applied; the numbers are reported."""
 import argparse
 import json
@@ -188,6 +198,104 @@ def bench_brushes(vrc, depth, pairs):
     return res
 
 
+def bench_flood(vrc, depth, pairs):
+    import torch
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import flood_model
+    S = 1 << depth
+    rng = np.random.default_rng(depth)
+    res = {"size": S, "pairs": pairs, "read_once_bytes": 2 * (S ** 3 // 8)}
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    terrain = vrc.VoxelVolume.fromScene(scene)
+    region = vrc.VoxelVolume(depth)
+    whole = np.array([[0, 0, 0, S, S, S]], np.uint32)
+    bottom = np.array([[0, S // 2 + 1, 0, S, S // 2 + 2, S]], np.uint32)
+    top = np.array([[0, S - 1, 0, S, S, S]], np.uint32)
+
+    def case(medium, seed, connectivity, through_empty, seed_is_voxels=False):
+        stats = []
+
+        def fa():
+            region.fillBoxes(whole, False)
+            (region.setVoxels if seed_is_voxels else region.fillBoxes)(seed)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            st = region.flood(medium, connectivity, through_empty)
+            b.record()
+            b.synchronize()
+            assert st.converged == 1
+            stats.append((a.elapsed_time(b), st.sweeps, st.reached))
+
+        def fb():
+            region.solidCount()
+            medium.solidCount()
+        flood_ms, reads = [], []
+        for i in range(pairs + 1):
+            fa()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fb()
+            b.record()
+            b.synchronize()
+            if i:
+                flood_ms.append(stats[-1][0])
+                reads.append(a.elapsed_time(b))
+        sweeps = stats[-1][1]
+        assert all(s[2] == stats[-1][2] for s in stats)
+        floor = statistics.median(reads) * sweeps
+        return {"connectivity": connectivity, "through_empty": through_empty, "flood_ms": stat(flood_ms, 4), "sweeps": sweeps,
+                "sweeps_range": [min(s[1] for s in stats), max(s[1] for s in stats)], "reached": stats[-1][2],
+                "read_once_ms": stat(reads, 4), "read_once_x_sweeps_ms": round(floor, 4),
+                "flood_over_floor": round(statistics.median(flood_ms) / floor, 4)}
+
+    res["terrain_from_bottom"] = case(terrain, bottom, 6, False)
+    cam = np.array(vrc.reference_camera_position(depth), np.float32) / np.float32(S) + np.float32(1.0)
+    d = rng.normal(size=(400, 3)).astype(np.float32) * np.float32(0.3) + np.array([0.0, 0.5, 0.8], np.float32)
+    d /= np.linalg.norm(d, axis=1, keepdims=True).astype(np.float32)
+    hits = scene.castRays(np.tile(cam, (400, 1)).astype(np.float32), d)
+    terrain.fillSpheresAtHits(hits, 12, False)
+    res["digs"] = {"rays": 400, "unit_hits": int(((hits["hit"] & 0xff) == 1).sum()), "radius": 12}
+    res["dug_terrain_from_bottom"] = case(terrain, bottom, 6, False)
+    res["dug_terrain_from_bottom_26"] = case(terrain, bottom, 26, False)
+    res["air_from_top"] = case(terrain, top, 6, True)
+
+    # what the flood replaces: download, label on the host, upload the result as runs along y
+    walls = {}
+    t0 = time.perf_counter()
+    dug = terrain.download()
+    walls["download_ms"] = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    seeds = np.zeros_like(dug)
+    seeds[:, S // 2 + 1, :] = 1
+    want = flood_model.flood(dug, seeds, 6)
+    walls["host_labelling_ms"] = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    edge = np.diff(np.pad(want.astype(np.int8), ((0, 0), (1, 1), (0, 0))), axis=1)
+    starts, ends = np.argwhere(edge == 1), np.argwhere(edge == -1)          # sorted by (x, y, z): re-sort by (x, z, y) to pair them
+    starts = starts[np.lexsort((starts[:, 1], starts[:, 2], starts[:, 0]))]
+    ends = ends[np.lexsort((ends[:, 1], ends[:, 2], ends[:, 0]))]
+    boxes = np.stack([starts[:, 0], starts[:, 1], starts[:, 2], starts[:, 0] + 1, ends[:, 1], starts[:, 2] + 1], axis=1).astype(np.uint32)
+    other = vrc.VoxelVolume(depth)
+    other.fillBoxes(boxes)
+    torch.cuda.synchronize()
+    walls["upload_fill_boxes_ms"] = (time.perf_counter() - t0) * 1e3
+    assert other.solidCount() == int(want.sum(dtype=np.int64)) == res["dug_terrain_from_bottom"]["reached"]
+    other.close()
+    res["host_round_trip"] = {k: round(v, 1) for k, v in walls.items()}
+    res["host_round_trip"]["boxes_uploaded"] = int(len(boxes))
+    res["host_round_trip"]["total_ms"] = round(sum(walls.values()), 1)
+    del dug, seeds, want, edge
+
+    path, start = flood_model.serpentine(S, 16)
+    medium = vrc.VoxelVolume(depth)
+    medium.setVoxels(np.argwhere(path))
+    res["serpentine"] = case(medium, np.array([start], np.uint32), 6, False, seed_is_voxels=True)
+    res["serpentine"]["path_voxels"] = int(path.sum())
+    for v in (medium, region, terrain, scene):
+        v.close()
+    return res
+
+
 def bench_depth(vrc, depth, pairs):
     import torch
     S = 1 << depth
@@ -246,18 +354,21 @@ def main():
     ap.add_argument("--depths", type=int, nargs="+", default=[8, 9, 10])
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--brushes", action="store_true", help="time the brushes, copies and queries (depths 9 and 10 unless --depths is given)")
+    ap.add_argument("--flood", action="store_true", help="time vrc_volume_flood (depth 9 unless --depths is given)")
     args = ap.parse_args()
     if args.brushes and args.depths == [8, 9, 10]:
         args.depths = [9, 10]
+    if args.flood and args.depths == [8, 9, 10]:
+        args.depths = [9]
     import __graft_entry__ as g
     g.build()
     import torch
     import cpuvoxelraycaster_amd as vrc
     if not torch.cuda.is_available():
         raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-    out = {"bench": "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
+    out = {"bench": "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
     for d in args.depths:
-        out["depths"][str(d)] = (bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
+        out["depths"][str(d)] = (bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
     print(json.dumps(out))
 
 
