@@ -10,7 +10,8 @@
 // (atomicOr / atomicAnd) on the words that hold the bricks, or whole-word stores where a box covers a word.
 // Brushes (spheres, spheres at the hits of a ray batch), region copies between volumes and the two queries (single
 // voxels, solid voxels per box) walk the same rows of words as the boxes do.  The flood fill by connectivity
-// (vrc_volume_flood) has its kernels in vrc_flood.hip; the entry point, its ordering and its scratch block are here.
+// (vrc_volume_flood) has its kernels in vrc_flood.hip, the solid voxelisation of triangle meshes (vrc_volume_xor_mesh)
+// in vrc_voxelize.hip; the entry points, their ordering and their scratch blocks are here.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -19,6 +20,7 @@
 #include "../../include/vrc.h"
 #include "vrc_build_sweeps.h"
 #include "vrc_flood.h"
+#include "vrc_voxelize.h"
 
 struct vrc_volume {
     int device = 0;
@@ -35,6 +37,8 @@ struct vrc_volume {
     // vrc_volume_flood with this volume as `region`: grow-only tile flags and sweep counters
     uint32_t* d_flood = nullptr;
     size_t flood_cap = 0;
+    // vrc_volume_xor_mesh: the mark field, as large as d_bricks, allocated and zeroed by the first call, zero between calls
+    uint32_t* d_marks = nullptr;
     // the last asynchronous edit: commit / download / solid_count run on the NULL stream and wait for it first.  The flag
     // says that the event has been recorded at least once; it is never cleared, because a wait only orders ONE stream
     // behind the edit and the next caller may bring another.
@@ -428,6 +432,7 @@ void volume_free(vrc_volume* v)
     if (v->d_count) (void)hipFree(v->d_count);
     if (v->d_stage) (void)hipFree(v->d_stage);
     if (v->d_flood) (void)hipFree(v->d_flood);
+    if (v->d_marks) (void)hipFree(v->d_marks);
     v->grids.release();
     delete v;
 }
@@ -639,6 +644,30 @@ extern "C" int vrc_volume_fill_spheres_at_hits(vrc_volume* v, uint64_t n, const 
     return VRC_OK;
 }
 
+extern "C" int vrc_volume_xor_mesh(vrc_volume* v, uint64_t n, const int32_t* tris, int mem, void* stream)
+{
+    const char* what = "vrc_volume_xor_mesh";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
+    if (n == 0) return VRC_OK;
+    if (!tris) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (n > 0x7fffffffull) return vrc::fail(VRC_ERR_INVALID, "%s: too many triangles for one launch", what);
+    hipStream_t st = (hipStream_t)stream;
+    // the mark field is shared by every call and the scan's read-modify-write of the occupancy is not atomic: behind the
+    // last asynchronous edit whatever the memory kind
+    hipError_t e = hipSetDevice(v->device);
+    if (e == hipSuccess) e = order_behind_edits(v, st);
+    if (e == hipSuccess && !v->d_marks) {
+        const size_t bytes = vrc::voxelize_scratch_bytes(v->depth);
+        if ((e = hipMalloc((void**)&v->d_marks, bytes)) == hipSuccess) e = hipMemsetAsync(v->d_marks, 0, bytes, st);
+        if (e != hipSuccess && v->d_marks) { (void)hipFree(v->d_marks); v->d_marks = nullptr; }
+    }
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return edit(v, what, n, 9, (const uint32_t*)tris, mem, st, [&](const uint32_t* d_tris) {
+        vrc::voxelize_run(v->d_bricks, v->d_marks, v->depth, n, (const int32_t*)d_tris, st);
+    });
+}
+
 extern "C" int vrc_volume_copy_region(vrc_volume* dst, vrc_volume* src, const uint32_t src_lo[3], const uint32_t size[3], const int32_t dst_lo[3],
                                       int op, void* stream)
 {
@@ -815,6 +844,13 @@ extern "C" int vrc_volume_download(vrc_volume* v, uint8_t* solid_host)
     if (e == hipSuccess) e = hipMemcpy(solid_host, d_dense, S * S * S, hipMemcpyDeviceToHost);
     if (d_dense) (void)hipFree(d_dense);
     if (e != hipSuccess) return vrc::fail_hip(e, "vrc_volume_download");
+    return VRC_OK;
+}
+
+extern "C" int vrc_volume_edit_scratch_bytes(const vrc_volume* v, uint64_t* bytes)
+{
+    if (!v || !bytes) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_edit_scratch_bytes: null argument");
+    *bytes = (uint64_t)v->stage_cap + (uint64_t)v->flood_cap + (v->d_marks ? (uint64_t)vrc::voxelize_scratch_bytes(v->depth) : 0u);
     return VRC_OK;
 }
 

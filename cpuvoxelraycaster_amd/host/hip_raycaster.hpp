@@ -17,6 +17,7 @@
 // be handed to Camera::getClosestPoint and friends unchanged.
 #pragma once
 
+#include <cmath>
 #include <cstdint>
 #include <fstream>
 #include <memory>
@@ -317,6 +318,71 @@ public:
         copyRegion(supported, zero, all, at, VRC_COPY_REPLACE);
         return debris;       // `supported` is destroyed behind the copies: vrc_volume_destroy waits for the device
     }
+    // Solid voxelisation by crossing parity (include/vrc.h: vrc_volume_xor_mesh): n x 9 int32 triangles in setCell
+    // coordinates with VRC_MESH_FRAC_BITS fractional bits; every voxel whose centre lies under an odd number of them is
+    // flipped, so a closed mesh in an empty volume gives its inside.  Synchronous.
+    void xorMesh(const std::vector<int32_t>& tris_fixed)
+    {
+        flush();
+        check(vrc_volume_xor_mesh(v_, tris_fixed.size() / 9, tris_fixed.data(), VRC_MEM_HOST, nullptr), "vrc_volume_xor_mesh");
+    }
+    void xorMeshDevice(uint64_t n, const int32_t* tris_dev, void* stream = nullptr)
+    {
+        flush();
+        check(vrc_volume_xor_mesh(v_, n, tris_dev, VRC_MEM_DEVICE, stream), "vrc_volume_xor_mesh");
+    }
+    // n x 3 vertices in voxels -> fixed point, llrint((v * scale + offset) * 64), each VERTEX once: a vertex shared by
+    // several faces stays one point, so a closed mesh stays closed
+    static std::vector<int64_t> quantiseMesh(const std::vector<double>& verts, double scale = 1.0, double ox = 0.0, double oy = 0.0, double oz = 0.0)
+    {
+        const double off[3] = {ox, oy, oz}, unit = (double)(1 << VRC_MESH_FRAC_BITS);
+        std::vector<int64_t> fixed(verts.size());
+        for (size_t i = 0; i < verts.size(); ++i) {
+            const double q = std::nearbyint((verts[i] * scale + off[i % 3]) * unit);
+            if (!(std::fabs(q) <= 131072.0)) throw std::invalid_argument("quantiseMesh: a vertex lies beyond +-2048 voxels");
+            fixed[i] = (int64_t)std::llrint(q);
+        }
+        return fixed;
+    }
+    // XORs the solid of the indexed mesh (verts n x 3 in voxels, faces m x 3 indices) into the volume
+    void voxelizeMesh(const std::vector<double>& verts, const std::vector<uint32_t>& faces, double scale = 1.0,
+                      double ox = 0.0, double oy = 0.0, double oz = 0.0)
+    {
+        const int64_t zero[3] = {0, 0, 0};
+        xorMesh(meshSoup(quantiseMesh(verts, scale, ox, oy, oz), faces, zero));
+    }
+    // What an editor does with a model: voxelises it into a clipboard volume of the smallest depth that holds its bounding
+    // box and copies that box into this volume with op (VRC_COPY_OR pastes, _ANDNOT carves, _REPLACE overwrites the box)
+    void stampMesh(const std::vector<double>& verts, const std::vector<uint32_t>& faces, int op = VRC_COPY_OR, double scale = 1.0,
+                   double ox = 0.0, double oy = 0.0, double oz = 0.0)
+    {
+        flush();
+        const std::vector<int64_t> fixed = quantiseMesh(verts, scale, ox, oy, oz);
+        if (fixed.size() < 3) return;
+        int64_t lo[3], hi[3];
+        for (int a = 0; a < 3; ++a) lo[a] = hi[a] = fixed[a];
+        for (size_t i = 0; i < fixed.size(); ++i) {
+            if (fixed[i] < lo[i % 3]) lo[i % 3] = fixed[i];
+            if (fixed[i] > hi[i % 3]) hi[i % 3] = fixed[i];
+        }
+        uint32_t size[3], largest = 1;
+        int32_t at[3];
+        int64_t origin[3];
+        for (int a = 0; a < 3; ++a) {
+            const int64_t l = lo[a] >> VRC_MESH_FRAC_BITS, h = -((-hi[a]) >> VRC_MESH_FRAC_BITS);   // floor, ceil
+            size[a] = (uint32_t)(h - l > 1 ? h - l : 1);
+            if (size[a] > largest) largest = size[a];
+            at[a] = (int32_t)l;
+            origin[a] = l * (1 << VRC_MESH_FRAC_BITS);
+        }
+        uint32_t d = 2;
+        while ((1u << d) < largest) ++d;
+        if (d > 10) throw std::invalid_argument("stampMesh: the mesh's bounding box exceeds 1024 voxels");
+        HipVoxelVolume clip(d, device_);
+        clip.xorMesh(meshSoup(fixed, faces, origin));       // whole voxels: the same triangles, moved
+        const uint32_t zero[3] = {0, 0, 0};
+        copyRegion(clip, zero, size, at, op);               // `clip` is destroyed behind the copy: vrc_volume_destroy waits
+    }
     std::unique_ptr<HipLSVO> commit(float* build_ms = nullptr)
     {
         flush();
@@ -331,10 +397,25 @@ public:
         check(vrc_volume_solid_count(v_, &n), "vrc_volume_solid_count");
         return n;
     }
+    uint64_t editScratchBytes() const
+    {
+        uint64_t n = 0;
+        check(vrc_volume_edit_scratch_bytes(v_, &n), "vrc_volume_edit_scratch_bytes");
+        return n;
+    }
     uint32_t depth() const { return vrc_volume_depth(v_); }
     vrc_volume* handle() const { return v_; }
 
 private:
+    static std::vector<int32_t> meshSoup(const std::vector<int64_t>& fixed, const std::vector<uint32_t>& faces, const int64_t origin[3])
+    {
+        std::vector<int32_t> tris(faces.size() * 3);
+        for (size_t i = 0; i < faces.size(); ++i) {
+            if ((size_t)faces[i] * 3 + 2 >= fixed.size()) throw std::invalid_argument("mesh: a face names a vertex that does not exist");
+            for (int a = 0; a < 3; ++a) tris[3 * i + a] = (int32_t)(fixed[(size_t)faces[i] * 3 + a] - origin[a]);
+        }
+        return tris;
+    }
     HipVoxelVolume(vrc_volume* adopted, int device) : v_(adopted), device_(device) {}
     vrc_volume* v_ = nullptr;
     int device_ = 0;

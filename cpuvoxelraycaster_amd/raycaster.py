@@ -260,6 +260,54 @@ class VoxelVolume:
         supported.close()
         return debris
 
+    def xorMesh(self, tris_fixed, device=False, stream=None):
+        """Solid voxelisation by crossing parity (include/vrc.h: vrc_volume_xor_mesh): (n, 9) int32 triangles in setCell
+        coordinates with 6 fractional bits (64 units per voxel, voxel centres at 64 c + 32); every voxel whose centre lies
+        under an odd number of them is flipped.  A closed mesh in an empty volume gives its inside.  Synchronous; with
+        device=True tris_fixed is (n, device pointer to n x 9 int32) and the call is asynchronous on `stream`."""
+        if device:
+            n, tris_ptr = tris_fixed
+            check(capi.load().vrc_volume_xor_mesh(self._h, int(n), ptr(tris_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
+            return
+        tris = np.ascontiguousarray(tris_fixed, np.int32).reshape(-1, 9)
+        check(capi.load().vrc_volume_xor_mesh(self._h, tris.shape[0], ptr(tris), capi.VRC_MEM_HOST, None))
+
+    @staticmethod
+    def quantiseMesh(verts, scale=1.0, offset=(0.0, 0.0, 0.0)):
+        """(n, 3) float vertices -> int32 fixed point, rint((v * scale + offset) * 64) in float64.  Each VERTEX once: a
+        vertex shared by several faces stays one point, so a closed mesh stays closed."""
+        v = np.asarray(verts, np.float64).reshape(-1, 3) * float(scale) + np.asarray(offset, np.float64).reshape(1, 3)
+        q = np.rint(v * float(1 << capi.VRC_MESH_FRAC_BITS))
+        if not np.all(np.abs(q) <= float(1 << 17)):          # NaN fails too
+            raise VrcError("quantiseMesh: a vertex lies beyond +-2048 voxels (vrc_volume_xor_mesh would drop its triangles)")
+        return q.astype(np.int32)
+
+    def voxelizeMesh(self, verts, faces, scale=1.0, offset=(0.0, 0.0, 0.0)):
+        """XORs the solid of the indexed mesh (verts (n, 3) float in voxels, faces (m, 3) indices) into the volume."""
+        fixed = self.quantiseMesh(verts, scale, offset)
+        self.xorMesh(fixed[np.asarray(faces, np.int64).reshape(-1, 3)].reshape(-1, 9))
+
+    def stampMesh(self, verts, faces, op=capi.VRC_COPY_OR, scale=1.0, offset=(0.0, 0.0, 0.0)):
+        """What an editor does with a model: voxelises it into a clipboard volume of the smallest depth that holds its
+        bounding box and copies that box into this volume with op (capi.VRC_COPY_OR pastes, _ANDNOT carves, _REPLACE
+        overwrites the box).  Returns (lo, size) of the box in this volume's voxels."""
+        fixed = self.quantiseMesh(verts, scale, offset).astype(np.int64)
+        lo = fixed.min(axis=0) >> capi.VRC_MESH_FRAC_BITS
+        size = np.maximum(-((-fixed.max(axis=0)) >> capi.VRC_MESH_FRAC_BITS) - lo, 1)
+        depth = 2
+        while (1 << depth) < size.max():
+            depth += 1
+        if depth > 10:
+            raise VrcError("stampMesh: the mesh's bounding box exceeds 1024 voxels")
+        clip = VoxelVolume(depth, self.device)
+        try:
+            local = (fixed - (lo << capi.VRC_MESH_FRAC_BITS)).astype(np.int32)      # whole voxels: the same triangles, moved
+            clip.xorMesh(local[np.asarray(faces, np.int64).reshape(-1, 3)].reshape(-1, 9))
+            self.copyRegion(clip, (0, 0, 0), size, lo, op)
+        finally:
+            clip.close()        # vrc_volume_destroy waits for the copy
+        return tuple(int(q) for q in lo), tuple(int(q) for q in size)
+
     def commit(self, textures=None):
         """A NEW LSVO of the current occupancy (build_ms = device time of the sweeps); the volume stays editable."""
         handle, ms = C.c_void_p(), C.c_float()
@@ -278,6 +326,12 @@ class VoxelVolume:
     def solidCount(self):
         n = C.c_uint64()
         check(capi.load().vrc_volume_solid_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def editScratchBytes(self):
+        """device bytes in the scratch blocks of the edit calls (staging, flood, mark field); include/vrc.h"""
+        n = C.c_uint64()
+        check(capi.load().vrc_volume_edit_scratch_bytes(self._h, C.byref(n)))
         return int(n.value)
 
     def close(self):

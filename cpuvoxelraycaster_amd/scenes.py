@@ -83,3 +83,43 @@ def reference_camera(depth, pitch=-0.5, yaw=0.0, aperture=0.0, focal_length=1.0,
     from . import capi, raycaster
     rot = (make_rotation or capi.make_rotation)(yaw, pitch)
     return raycaster.make_camera(reference_camera_position(depth), rot, 1.0, aperture, focal_length)
+
+
+def icosphere(subdivisions=2):
+    """(verts (n, 3) float64 on the unit sphere, faces (m, 3) int32, outward winding) of an icosahedron subdivided 0..3
+    times: 20 * 4^subdivisions triangles (20, 80, 320, 1280).  Vertices are shared between faces, so the mesh is closed --
+    what VoxelVolume.voxelizeMesh needs to give a solid."""
+    if not 0 <= int(subdivisions) <= 3:
+        raise ValueError("icosphere: subdivisions 0..3")
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    verts = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t),
+             (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    verts = [tuple(np.asarray(v, np.float64) / np.linalg.norm(v)) for v in verts]
+    faces = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+             (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(int(subdivisions)):
+        middle = {}
+
+        def mid(i, j):
+            key = (min(i, j), max(i, j))
+            if key not in middle:
+                m = (np.asarray(verts[i]) + np.asarray(verts[j])) / 2.0
+                verts.append(tuple(m / np.linalg.norm(m)))
+                middle[key] = len(verts) - 1
+            return middle[key]
+
+        split = []
+        for a, b, c in faces:
+            ab, bc, ca = mid(a, b), mid(b, c), mid(c, a)
+            split += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        faces = split
+    return np.asarray(verts, np.float64), np.asarray(faces, np.int32)
+
+
+def box_mesh(lo, hi):
+    """(verts (8, 3) float64, faces (12, 3) int32, outward winding) of the axis-aligned box [lo, hi]"""
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    verts = np.array([[(hi if (i >> a) & 1 else lo)[a] for a in range(3)] for i in range(8)], np.float64)   # bit a of i: axis a at hi
+    quads = [(0, 2, 3, 1), (4, 5, 7, 6), (0, 1, 5, 4), (2, 6, 7, 3), (0, 4, 6, 2), (1, 3, 7, 5)]                 # -z +z -y +y -x +x
+    faces = [f for a, b, c, d in quads for f in ((a, b, c), (a, c, d))]
+    return verts, np.asarray(faces, np.int32)

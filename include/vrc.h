@@ -219,6 +219,33 @@ int vrc_volume_fill_spheres(vrc_volume *v, uint64_t n, const int32_t *centre_rad
  * by this call on the same stream edits the volume with no host copy of a hit.  The centres pass through the volume's
  * grow-only staging block (16 bytes per record). */
 int vrc_volume_fill_spheres_at_hits(vrc_volume *v, uint64_t n, const vrc_hit *hits, int32_t radius, int solid, int mem, void *stream);
+/* Solid voxelisation of a triangle mesh by crossing parity along z: bringing a model in without leaving the device.
+ * n triangles (n x 9 int32: ax ay az bx by bz cx cy cz) in setCell coordinates with VRC_MESH_FRAC_BITS fractional bits, 64
+ * units per voxel: the centre of voxel (x, y, z) is (64x + 32, 64y + 32, 64z + 32).  `mem`, `stream` and n == 0 as for
+ * vrc_volume_fill_spheres; the call is always ordered behind the volume's last asynchronous edit.  Per triangle, in
+ * 64-bit integers: n = (b - a) x (c - a), s = sign(n.z); a triangle with n.z == 0 contributes nothing.
+ *   Cover: the triangle covers voxel column (x, y) iff for its centre p = (64x + 32, 64y + 32) and every edge P -> Q of
+ *   a -> b, b -> c, c -> a, with d = s (Q - P) in xy and E = d.x (p.y - P.y) - d.y (p.x - P.x):  E > 0, or E == 0 and
+ *   (d.y > 0 or (d.y == 0 and d.x < 0)).  A centre on an edge shared by two triangles on opposite sides of it in projection
+ *   belongs to exactly one of them; on a silhouette edge to both or to neither.
+ *   Flip: in a covered column voxel z is flipped iff s n . (centre - a) < 0, its centre strictly on the -z side of the
+ *   plane: the prefix [0, k) of the column, k = clamp(ceil(N / (64 |n.z|)), 0, S) with
+ *   N = |n.z| (a.z - 32) - s (n.x (p.x - a.x) + n.y (p.y - a.y)).
+ * A voxel's state afterwards is its state on entry XOR the parity of its flips over all triangles of the call.  For a
+ * closed mesh in an empty volume that is exactly the set of voxel centres inside the mesh, whatever the triangles' order
+ * or winding; an open mesh is legal and fills everything under the sheet; the same mesh twice restores the volume.  The
+ * result is unique: integers and XOR, no dependence on scheduling.  Columns and prefixes are clipped to the volume: what
+ * lies outside is neither read nor written.  A triangle with any coordinate beyond +-2^17 units (+-2048 voxels) is
+ * dropped like an out-of-range sphere (inside that range every quantity above stays below 2^57) -- and dropping ONE
+ * triangle of a closed mesh breaks its parity: the columns under it come out inverted below the mesh, so keep a mesh
+ * inside the range as a whole.  Cost: one atomic per triangle and covered column, then one pass over the volume's words
+ * HOWEVER SMALL the mesh (a read of 16 MiB at 512^3, 128 MiB at 1024^3: voxelise a small model into a small volume and
+ * vrc_volume_copy_region it into the world);
+ * few triangles are spread over up to 1024 workgroups each, a batch of more than 4096 gets one 256-thread workgroup per
+ * triangle whatever its size.  The volume keeps a scratch block of the occupancy's own size (one byte per brick: 16 MiB
+ * at 512^3, 128 MiB at 1024^3), allocated by the first call and never grown or shrunk. */
+#define VRC_MESH_FRAC_BITS 6
+int vrc_volume_xor_mesh(vrc_volume *v, uint64_t n_tris, const int32_t *tris, int mem, void *stream);
 /* Voxel src_lo + d of `src` goes to dst_lo + d of `dst` for 0 <= d < size, clipped to both volumes (what falls outside
  * either is neither read nor written).  The volumes may have different depths (a 32^3 clipboard stamped into a 512^3
  * world) and must be two different volumes on one device; any voxel offset is legal.  Asynchronous on `stream`: ordered
@@ -237,6 +264,10 @@ int vrc_volume_clone(vrc_volume *src, vrc_volume **out);
  * for vrc_volume_fill_boxes, clipped; empty or inverted = 0), so one whole-volume box equals vrc_volume_solid_count. */
 int vrc_volume_get_voxels(vrc_volume *v, uint64_t n, const uint32_t *xyz, uint8_t *solid_out, int mem, void *stream);
 int vrc_volume_count_boxes(vrc_volume *v, uint64_t n, const uint32_t *lo_hi, uint64_t *counts, int mem, void *stream);
+/* Device bytes the volume holds at this moment in the scratch blocks of its edit calls: the grow-only staging block of the
+ * host-memory calls, vrc_volume_flood's block and vrc_volume_xor_mesh's mark field (0 before the first call of each).  The
+ * occupancy itself and vrc_volume_commit's grids are not counted.  Pure host bookkeeping, no device call. */
+int vrc_volume_edit_scratch_bytes(const vrc_volume *v, uint64_t *bytes);
 
 /* Flood fill by connectivity, on the device: which voxels hold on to the ground, which cave is enclosed, which piece lies
  * under the crosshair.  M = the voxels of `medium` that are solid (VRC_FLOOD_SOLID) or empty (VRC_FLOOD_EMPTY); the solid

@@ -32,6 +32,19 @@ read_once x sweeps as the floor a flood without frontier tracking could not beat
   serpentine               the worst case: a one-voxel path of 1024 lines through every tile, from its first voxel
   host_round_trip          what the flood replaces, on the dug terrain: vrc_volume_download, a labelling pass in numpy
                            (tests/flood_model.py), upload of the result as y runs through vrc_volume_fill_boxes; wall times
+With --voxelize (written to profiles/edit/bench_voxelize.json by whoever runs it), vrc_volume_xor_mesh at 512^3, triangles in
+device memory, device time by events, one warm-up, A B A B in one process against B = one read of a field of the
+occupancy's size (vrc_volume_solid_count, 16 MiB); the floor of the call is three such passes (read the marks, read and
+write the occupancy) and is reported as floor_ms = 3 x read_once; `--pairs` pairs (one more if even, so that every mesh is XORed an even number of
+times and the volume is empty again), median and range:
+  icosphere_20k        an icosphere of 20 480 triangles, radius 200 voxels
+  icosphere_1m         the same sphere as 1 310 720 triangles (three more subdivisions)
+  spanning_box         one box mesh spanning the volume: 12 triangles of 2^18 columns each
+  icospheres_4096      4 096 icospheres of 80 triangles, radius 6, at random places, in one call
+  host_round_trip      what the call replaces, for icosphere_20k and spanning_box: the numpy model on the host
+                       (tests/voxelize_model.py), then the upload of its result as z runs through vrc_volume_fill_boxes;
+                       wall times
+  first_call           wall time of the first call on a fresh volume (it allocates and zeroes the mark field) and of the second
 No threshold is applied; the numbers are reported."""
 import argparse
 import json
@@ -296,6 +309,90 @@ def bench_flood(vrc, depth, pairs):
     return res
 
 
+def subdivided_icosphere(vrc, subdivisions):
+    """scenes.icosphere beyond its three levels: every triangle split in four, new vertices pushed out to the unit sphere"""
+    verts, faces = vrc.icosphere(min(subdivisions, 3))
+    faces = faces.astype(np.int64)
+    for _ in range(max(0, subdivisions - 3)):
+        edges = np.sort(np.concatenate([faces[:, [0, 1]], faces[:, [1, 2]], faces[:, [2, 0]]]), axis=1)
+        unique, inverse = np.unique(edges, axis=0, return_inverse=True)
+        mid = verts[unique[:, 0]] + verts[unique[:, 1]]
+        mid /= np.linalg.norm(mid, axis=1, keepdims=True)
+        m = inverse.reshape(3, -1) + len(verts)                  # midpoints of a-b, b-c, c-a per face
+        a, b, c = faces.T
+        faces = np.concatenate([np.stack(t, axis=1) for t in ((a, m[0], m[2]), (b, m[1], m[0]), (c, m[2], m[1]), (m[0], m[1], m[2]))])
+        verts = np.concatenate([verts, mid])
+    return verts, faces
+
+
+def bench_voxelize(vrc, depth, pairs):
+    import torch
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import voxelize_model
+    S = 1 << depth
+    rng = np.random.default_rng(depth)
+    res = {"size": S, "pairs": pairs, "field_bytes": S ** 3 // 8}
+    quantise = vrc.VoxelVolume.quantiseMesh
+
+    def soup(verts, faces, scale, offset):
+        return quantise(verts, scale, offset)[np.asarray(faces, np.int64)].reshape(-1, 9)
+
+    m = S / 2
+    meshes = {"icosphere_20k": soup(*subdivided_icosphere(vrc, 5), 200.0 * S / 512, (m + 0.3, m - 0.2, m + 0.1)),
+              "icosphere_1m": soup(*subdivided_icosphere(vrc, 8), 200.0 * S / 512, (m + 0.3, m - 0.2, m + 0.1)),
+              "spanning_box": soup(*vrc.box_mesh((0, 0, 0), (S, S, S)), 1.0, (0, 0, 0))}
+    small_v, small_f = vrc.icosphere(1)
+    meshes["icospheres_4096"] = np.concatenate([soup(small_v, small_f, 6.0, c) for c in rng.uniform(8, S - 8, (4096, 3))])
+
+    # the first call allocates and zeroes the mark field
+    fresh = vrc.VoxelVolume(depth)
+    walls = []
+    for _ in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fresh.xorMesh(meshes["spanning_box"])
+        walls.append(round((time.perf_counter() - t0) * 1e3, 3))
+    res["first_call"] = {"first_wall_ms": walls[0], "second_wall_ms": walls[1]}
+    fresh.close()
+
+    # ab_device_ms calls the mesh once to warm up and once per timed pair: an odd number of pairs makes that an even number
+    # of XORs, and the volume is empty again for the next mesh
+    timed = pairs | 1
+    res["pairs"] = timed
+    volume = vrc.VoxelVolume(depth)
+    for name, tris in meshes.items():
+        t = torch.from_numpy(np.ascontiguousarray(tris, np.int32)).cuda()
+        torch.cuda.synchronize()
+        a, b = ab_device_ms(lambda: volume.xorMesh((len(tris), t.data_ptr()), device=True), lambda: volume.solidCount(), timed)
+        res[name] = {"triangles": int(len(tris)), "xor_mesh_ms": a, "read_once_ms": b, "floor_ms": round(3 * b["median"], 5),
+                     "over_floor": round(a["median"] / (3 * b["median"]), 3)}
+        assert volume.solidCount() == 0, name
+    volume.close()
+
+    for name in ("icosphere_20k", "spanning_box"):
+        walls = {}
+        t0 = time.perf_counter()
+        want = voxelize_model.xor_mesh(S, meshes[name])
+        walls["host_model_ms"] = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        edge = np.diff(np.pad(want.astype(np.int8), ((0, 0), (0, 0), (1, 1))), axis=2)
+        starts, ends = np.argwhere(edge == 1), np.argwhere(edge == -1)      # both sorted by (x, y, z): they pair up in order
+        boxes = np.concatenate([starts, ends + (1, 1, 0)], axis=1).astype(np.uint32)
+        other = vrc.VoxelVolume(depth)
+        other.fillBoxes(boxes)
+        torch.cuda.synchronize()
+        walls["upload_fill_boxes_ms"] = (time.perf_counter() - t0) * 1e3
+        check = vrc.VoxelVolume(depth)
+        check.xorMesh(meshes[name])
+        assert other.solidCount() == check.solidCount() == int(want.sum(dtype=np.int64))
+        other.close()
+        check.close()
+        res[name]["host_round_trip"] = {**{k: round(v, 1) for k, v in walls.items()}, "boxes_uploaded": int(len(boxes)),
+                                        "total_ms": round(sum(walls.values()), 1), "solid_voxels": int(want.sum(dtype=np.int64))}
+        del want, edge
+    return res
+
+
 def bench_depth(vrc, depth, pairs):
     import torch
     S = 1 << depth
@@ -355,7 +452,10 @@ def main():
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--brushes", action="store_true", help="time the brushes, copies and queries (depths 9 and 10 unless --depths is given)")
     ap.add_argument("--flood", action="store_true", help="time vrc_volume_flood (depth 9 unless --depths is given)")
+    ap.add_argument("--voxelize", action="store_true", help="time vrc_volume_xor_mesh (depth 9 unless --depths is given)")
     args = ap.parse_args()
+    if args.voxelize and args.depths == [8, 9, 10]:
+        args.depths = [9]
     if args.brushes and args.depths == [8, 9, 10]:
         args.depths = [9, 10]
     if args.flood and args.depths == [8, 9, 10]:
@@ -366,9 +466,9 @@ def main():
     import cpuvoxelraycaster_amd as vrc
     if not torch.cuda.is_available():
         raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-    out = {"bench": "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
+    out = {"bench": "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
     for d in args.depths:
-        out["depths"][str(d)] = (bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
+        out["depths"][str(d)] = (bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
     print(json.dumps(out))
 
 
