@@ -16,6 +16,8 @@ VRC_COPY_REPLACE, VRC_COPY_OR, VRC_COPY_ANDNOT = 0, 1, 2
 VRC_CONNECT_FACES, VRC_CONNECT_ALL = 6, 26
 VRC_FLOOD_SOLID, VRC_FLOOD_EMPTY = 0, 1
 VRC_MESH_FRAC_BITS = 6
+VRC_FACE_XN, VRC_FACE_XP, VRC_FACE_YN, VRC_FACE_YP, VRC_FACE_ZN, VRC_FACE_ZP = range(6)
+VRC_SURFACE_FACES, VRC_SURFACE_TRIANGLES = 0, 1
 
 HIT_DTYPE = np.dtype([
     ("position", "<f4", 3), ("normal", "<f4", 3), ("voxel_coord", "<f4", 2),
@@ -147,6 +149,8 @@ SYMBOLS = {
     "vrc_volume_count_boxes": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
     "vrc_volume_flood": (_int, [_vp, _vp, _int, _int, _u32, C.POINTER(FloodStats)]),
     "vrc_volume_xor_mesh": (_int, [_vp, _u64, _vp, _int, _vp]),
+    "vrc_volume_surface_count": (_int, [_vp, _int, _vp]),
+    "vrc_volume_extract_surface": (_int, [_vp, _int, _int, _u64, _u64, _vp, _vp, _int, _vp]),
     "vrc_volume_edit_scratch_bytes": (_int, [_vp, C.POINTER(_u64)]),
     "vrc_renderer_set_scene": (_int, [_vp, _vp]),
     "vrc_hit_to_voxel": (_int, [_u32, _vp, _vp, _vp, C.POINTER(_int)]),

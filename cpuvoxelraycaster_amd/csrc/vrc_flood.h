@@ -6,6 +6,10 @@
 
 namespace vrc {
 
+// The voxels of a word with x = 0 / x = 1 and with y = 0 / y = 1 inside their brick (the layout: top of vrc_flood.hip): a
+// one-voxel step along x is a shift by 1 under WORD_X0 / WORD_X1, along y by 2 under WORD_Y0 / WORD_Y1, along z by 4.
+constexpr uint32_t WORD_X0 = 0x55555555u, WORD_X1 = 0xAAAAAAAAu, WORD_Y0 = 0x33333333u, WORD_Y1 = 0xCCCCCCCCu;
+
 // bytes of device scratch a flood at `depth` needs (tile flags and sweep counters)
 size_t flood_scratch_bytes(uint32_t depth);
 // the library's own sweep bound for max_sweeps == 0 (include/vrc.h: vrc_volume_flood)

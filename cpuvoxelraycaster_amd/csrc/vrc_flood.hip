@@ -27,7 +27,7 @@ constexpr uint32_t TW = 16, TWZ = 4;           // words per tile along x / y, al
 constexpr uint32_t HX = TW + 2, HZ = TWZ + 2;  // with the halo
 constexpr uint32_t HZP = HZ + 1;               // padded: neighbouring columns 7 words apart fall on different LDS banks
 
-constexpr uint32_t X0 = 0x55555555u, X1 = 0xAAAAAAAAu, Y0 = 0x33333333u, Y1 = 0xCCCCCCCCu;
+constexpr uint32_t X0 = vrc::WORD_X0, X1 = vrc::WORD_X1, Y0 = vrc::WORD_Y0, Y1 = vrc::WORD_Y1;
 
 // w and what steps into it along x from itself and from the words of the bricks before (l) and after (r)
 __device__ __forceinline__ uint32_t dilate_x(uint32_t w, uint32_t l, uint32_t r)

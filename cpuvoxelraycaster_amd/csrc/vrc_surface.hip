@@ -1,0 +1,297 @@
+// vrc_surface.hip -- the exposed faces of the editable volume's bit field as a face or triangle list (include/vrc.h:
+// vrc_volume_surface_count, vrc_volume_extract_surface): the inverse of vrc_voxelize.hip.
+//
+// The layout of a word (2 x 2 x 8 voxels, bit zz*4 + yb*2 + xb) and the shifts that step one voxel along an axis are
+// described at the top of vrc_flood.hip; the masks are vrc_flood.h's.  Face d = 2*axis + side of a solid voxel is
+// exposed iff its neighbour on that side is empty, so the exposed faces of a word in one direction are
+//     w & ~(the word's neighbours shifted onto it),
+// e.g. towards +x  w & ~(((w >> 1) & WORD_X0) | ((r << 1) & WORD_X1))  with r the word of the next brick in x.  A word
+// beyond the volume reads as 0 (closed: the volume's own faces are exposed) or ~0 (open).  No voxel is expanded to a byte.
+//
+// The canonical order is (word, direction, bit).  Three passes on one stream, a workgroup = 256 consecutive words, a
+// lane = one word; no workgroup waits for another:
+//   1. count: the popcounts of the six masks, summed over the workgroup into its slot (at most 256 * 192 faces);
+//   2. scan:  one workgroup walks the slots 1024 at a time and replaces them by their 64-bit exclusive prefix; the
+//             total T goes behind the last slot;
+//   3. emit:  a workgroup whose range [slot, next slot) misses the window leaves after reading the two slots.  The
+//             others recompute their masks, prefix the per-word counts across their lanes, and every lane walks the set
+//             bits of its own word, writing the faces that fall inside the window: one 16-byte store per face record,
+//             nine 8-byte (or eighteen 4-byte) stores per pair of triangles.
+// Each pass reads every word and its six neighbours once (the neighbours come from the caches: a word is the x / y / z
+// neighbour of six others); the writes of pass 3 follow the window.  Word indices reach 2^25 and stay 32-bit, face
+// indices reach 3 * 8^10 > 2^32 and are 64-bit throughout.
+#include "vrc_surface.h"
+
+#include "../../include/vrc.h"
+#include "vrc_flood.h"
+
+namespace {
+
+using vrc::WORD_X0;
+using vrc::WORD_X1;
+using vrc::WORD_Y0;
+using vrc::WORD_Y1;
+
+constexpr uint32_t GROUP = 256;               // words per workgroup
+constexpr uint32_t SCAN_GROUP = 1024;         // slots per step of the scan
+
+struct Field {
+    const uint32_t* words;
+    uint32_t lg;                              // log2 of the bricks per axis, n = S / 2
+    uint32_t n_words;                         // n^3 / 4
+    uint32_t beyond;                          // what a word beyond the volume reads as: 0 closed, ~0 open
+};
+
+// voxel coordinates of bit `bit` of word W: brick byte B = 4 W + bit / 8 = (cx * n + cy) * n + cz
+__device__ __forceinline__ void voxel_of(const Field& f, uint32_t W, uint32_t bit, uint32_t c[3])
+{
+    const uint32_t B = 4u * W + (bit >> 3), nm = (1u << f.lg) - 1u;
+    c[0] = 2u * (B >> (2u * f.lg)) + (bit & 1u);
+    c[1] = 2u * ((B >> f.lg) & nm) + ((bit >> 1) & 1u);
+    c[2] = 2u * (B & nm) + ((bit >> 2) & 1u);
+}
+
+// the exposed faces of word W per direction, as masks of its bits
+__device__ __forceinline__ void word_masks(const Field& f, uint32_t W, uint32_t m[6])
+{
+    const uint32_t w = f.words[W];
+    if (f.lg >= 2u) {
+        // n >= 4: word (cx, cy, wz) of n / 4 words along z
+        const uint32_t lgz = f.lg - 2u, n = 1u << f.lg;
+        const uint32_t wz = W & ((1u << lgz) - 1u), cy = (W >> lgz) & (n - 1u), cx = W >> (lgz + f.lg);
+        const uint32_t sy = 1u << lgz, sx = n << lgz;
+        const uint32_t xl = cx ? f.words[W - sx] : f.beyond, xr = cx + 1u < n ? f.words[W + sx] : f.beyond;
+        const uint32_t yl = cy ? f.words[W - sy] : f.beyond, yr = cy + 1u < n ? f.words[W + sy] : f.beyond;
+        const uint32_t zl = wz ? f.words[W - 1u] : f.beyond, zr = wz + 1u < sy ? f.words[W + 1u] : f.beyond;
+        m[VRC_FACE_XN] = w & ~(((w << 1) & WORD_X1) | ((xl >> 1) & WORD_X0));
+        m[VRC_FACE_XP] = w & ~(((w >> 1) & WORD_X0) | ((xr << 1) & WORD_X1));
+        m[VRC_FACE_YN] = w & ~(((w << 2) & WORD_Y1) | ((yl >> 2) & WORD_Y0));
+        m[VRC_FACE_YP] = w & ~(((w >> 2) & WORD_Y0) | ((yr << 2) & WORD_Y1));
+        m[VRC_FACE_ZN] = w & ~((w << 4) | (zl >> 28));
+        m[VRC_FACE_ZP] = w & ~((w >> 4) | (zr << 28));
+        return;
+    }
+    // 4^3: two words, each two brick rows.  Voxel by voxel from the rule itself.
+    const uint32_t both[2] = {f.words[0], f.words[1]};
+    for (int d = 0; d < 6; ++d) m[d] = 0u;
+    for (uint32_t bit = 0; bit < 32u; ++bit) {
+        if (!((w >> bit) & 1u)) continue;
+        uint32_t c[3];
+        voxel_of(f, W, bit, c);
+#pragma unroll
+        for (int d = 0; d < 6; ++d) {
+            int32_t q[3] = {(int32_t)c[0], (int32_t)c[1], (int32_t)c[2]};
+            q[d >> 1] += (d & 1) ? 1 : -1;
+            uint32_t solid = f.beyond & 1u;
+            if (q[d >> 1] >= 0 && q[d >> 1] < 4) {
+                const uint32_t key = 8u * (uint32_t)(((q[0] >> 1) * 2 + (q[1] >> 1)) * 2 + (q[2] >> 1)) + (uint32_t)((q[2] & 1) * 4 + (q[1] & 1) * 2 + (q[0] & 1));
+                solid = (both[key >> 5] >> (key & 31u)) & 1u;
+            }
+            if (!solid) m[d] |= 1u << bit;
+        }
+    }
+}
+
+// v summed over the 256 lanes of the workgroup, on every lane.  part: 4 words of LDS, free again on return.
+__device__ __forceinline__ uint32_t group_sum(uint32_t v, uint32_t* part)
+{
+    for (int o = 32; o; o >>= 1) v += __shfl_down(v, o);
+    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const uint32_t s = part[0] + part[1] + part[2] + part[3];
+    __syncthreads();
+    return s;
+}
+
+// the sum of v over the lanes before this one, in a workgroup of WAVES waves; *total = the sum over all of them
+template <uint32_t WAVES>
+__device__ __forceinline__ uint32_t group_exclusive_scan(uint32_t v, uint32_t* part, uint32_t* total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t incl = v;
+    for (uint32_t o = 1; o < 64u; o <<= 1) {
+        const uint32_t t = __shfl_up(incl, o);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63u) part[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0u, all = 0u;
+    for (uint32_t k = 0; k < WAVES; ++k) {
+        const uint32_t p = part[k];
+        if (k < wave) before += p;
+        all += p;
+    }
+    __syncthreads();
+    *total = all;
+    return before + incl - v;
+}
+
+// DIRECTIONS: the six totals of the whole field (vrc_volume_surface_count); otherwise the workgroup's own total
+template <bool DIRECTIONS>
+__global__ __launch_bounds__(256) void k_surface_count(Field f, unsigned long long* __restrict__ slots)
+{
+    __shared__ uint32_t part[4];
+    const uint32_t W = blockIdx.x * GROUP + threadIdx.x;
+    uint32_t m[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    if (W < f.n_words) word_masks(f, W, m);
+    if (DIRECTIONS) {
+        for (int d = 0; d < 6; ++d) {
+            const uint32_t s = group_sum(__popc(m[d]), part);
+            if (threadIdx.x == 0 && s) atomicAdd(&slots[d], (unsigned long long)s);
+        }
+    } else {
+        uint32_t c = 0u;
+        for (int d = 0; d < 6; ++d) c += __popc(m[d]);
+        const uint32_t s = group_sum(c, part);
+        if (threadIdx.x == 0) slots[blockIdx.x] = s;
+    }
+}
+
+// slots[0 .. n_slots) -> their exclusive prefix, slots[n_slots] = the total.  One workgroup.
+__global__ __launch_bounds__(1024) void k_surface_scan(unsigned long long* __restrict__ slots, uint32_t n_slots, unsigned long long* __restrict__ total_out)
+{
+    __shared__ uint32_t part[SCAN_GROUP / 64u];
+    unsigned long long carry = 0ull;
+    for (uint32_t base = 0; base < n_slots; base += SCAN_GROUP) {      // uniform trip count
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < n_slots ? (uint32_t)slots[i] : 0u;      // <= 256 * 192; a step's sum stays below 2^26
+        uint32_t step = 0u;
+        const uint32_t before = group_exclusive_scan<SCAN_GROUP / 64u>(v, part, &step);
+        if (i < n_slots) slots[i] = carry + before;
+        carry += step;
+    }
+    if (threadIdx.x == 0) {
+        slots[n_slots] = carry;
+        if (total_out) *total_out = carry;
+    }
+}
+
+// the two triangles of face d of voxel c, 18 int32 in vrc_volume_xor_mesh's units (include/vrc.h: the corner rule)
+template <int D>
+__device__ __forceinline__ void face_triangles(const uint32_t c[3], int32_t t[18])
+{
+    constexpr int a = D >> 1, side = D & 1, u = (a + 1) % 3, v = (a + 2) % 3;
+    const int32_t pa = 64 * (int32_t)(c[a] + (uint32_t)side), u0 = 64 * (int32_t)c[u], v0 = 64 * (int32_t)c[v], u1 = u0 + 64, v1 = v0 + 64;
+    int32_t q[4][3];
+    q[0][a] = pa; q[0][u] = u0; q[0][v] = v0;
+    q[1][a] = pa; q[1][u] = u1; q[1][v] = v0;
+    q[2][a] = pa; q[2][u] = u1; q[2][v] = v1;
+    q[3][a] = pa; q[3][u] = u0; q[3][v] = v1;
+    constexpr int order[2][6] = {{0, 2, 1, 0, 3, 2}, {0, 1, 2, 0, 2, 3}};
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) t[3 * k + j] = q[order[side][k]][j];
+}
+
+// the faces of direction D of one word, from face index idx on; returns the index behind them
+template <int FORMAT, bool WIDE, int D>
+__device__ __forceinline__ unsigned long long emit_direction(const Field& f, uint32_t W, uint32_t m, unsigned long long idx, unsigned long long first,
+                                                             unsigned long long win_end, void* out)
+{
+    const unsigned long long end = idx + __popc(m);
+    if (end <= first || idx >= win_end) return end;
+    while (m) {
+        const uint32_t bit = (uint32_t)__ffs((int)m) - 1u;
+        m &= m - 1u;
+        if (idx >= first && idx < win_end) {
+            uint32_t c[3];
+            voxel_of(f, W, bit, c);
+            const unsigned long long at = idx - first;
+            if (FORMAT == VRC_SURFACE_FACES) {
+                ((uint4*)out)[at] = make_uint4(c[0], c[1], c[2], (uint32_t)D);
+            } else {
+                int32_t t[18];
+                face_triangles<D>(c, t);
+                if (WIDE) {
+                    int2* o = (int2*)out + 9ull * at;
+                    for (int k = 0; k < 9; ++k) o[k] = make_int2(t[2 * k], t[2 * k + 1]);
+                } else {
+                    int32_t* o = (int32_t*)out + 18ull * at;
+                    for (int k = 0; k < 18; ++k) o[k] = t[k];
+                }
+            }
+        }
+        ++idx;
+    }
+    return end;
+}
+
+// WIDE: `out` is 8-byte aligned, a triangle pair goes out as nine 8-byte stores
+template <int FORMAT, bool WIDE>
+__global__ __launch_bounds__(256) void k_surface_emit(Field f, const unsigned long long* __restrict__ slots, unsigned long long first,
+                                                      unsigned long long capacity, void* out)
+{
+    __shared__ uint32_t part[4];
+    const unsigned long long from = slots[blockIdx.x], to = slots[blockIdx.x + 1u];
+    const unsigned long long win_end = capacity > ~0ull - first ? ~0ull : first + capacity;
+    if (from == to || to <= first || from >= win_end) return;           // uniform for the workgroup
+    const uint32_t W = blockIdx.x * GROUP + threadIdx.x;
+    uint32_t m[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    if (W < f.n_words) word_masks(f, W, m);
+    uint32_t mine = 0u, all = 0u;
+    for (int d = 0; d < 6; ++d) mine += __popc(m[d]);
+    unsigned long long idx = from + group_exclusive_scan<4u>(mine, part, &all);
+    if (!mine || idx + mine <= first || idx >= win_end) return;         // no barrier follows
+    idx = emit_direction<FORMAT, WIDE, 0>(f, W, m[0], idx, first, win_end, out);
+    idx = emit_direction<FORMAT, WIDE, 1>(f, W, m[1], idx, first, win_end, out);
+    idx = emit_direction<FORMAT, WIDE, 2>(f, W, m[2], idx, first, win_end, out);
+    idx = emit_direction<FORMAT, WIDE, 3>(f, W, m[3], idx, first, win_end, out);
+    idx = emit_direction<FORMAT, WIDE, 4>(f, W, m[4], idx, first, win_end, out);
+    emit_direction<FORMAT, WIDE, 5>(f, W, m[5], idx, first, win_end, out);
+}
+
+Field field_of(const uint32_t* words, uint32_t depth, int closed)
+{
+    Field f;
+    f.words = words;
+    f.lg = depth - 1u;
+    f.n_words = 1u << (3u * (depth - 1u) - 2u);
+    f.beyond = closed ? 0u : 0xffffffffu;
+    return f;
+}
+
+uint32_t groups_of(uint32_t depth)
+{
+    const uint32_t n_words = 1u << (3u * (depth - 1u) - 2u);
+    return (n_words + GROUP - 1u) / GROUP;
+}
+
+}  // namespace
+
+namespace vrc {
+
+size_t surface_scratch_bytes(uint32_t depth) { return ((size_t)groups_of(depth) + 7u) * 8u; }
+
+unsigned long long* surface_total_slot(unsigned long long* scratch, uint32_t depth) { return scratch + groups_of(depth); }
+
+unsigned long long* surface_direction_slots(unsigned long long* scratch, uint32_t depth) { return scratch + groups_of(depth) + 1u; }
+
+void surface_count_run(const uint32_t* words, uint32_t depth, int closed, unsigned long long* scratch, hipStream_t st)
+{
+    unsigned long long* totals = surface_direction_slots(scratch, depth);
+    (void)hipMemsetAsync(totals, 0, 48, st);
+    hipLaunchKernelGGL(k_surface_count<true>, dim3(groups_of(depth)), dim3(GROUP), 0, st, field_of(words, depth, closed), totals);
+}
+
+void surface_offsets_run(const uint32_t* words, uint32_t depth, int closed, unsigned long long* scratch, unsigned long long* d_total, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_surface_count<false>, dim3(groups_of(depth)), dim3(GROUP), 0, st, field_of(words, depth, closed), scratch);
+    hipLaunchKernelGGL(k_surface_scan, dim3(1), dim3(SCAN_GROUP), 0, st, scratch, groups_of(depth), d_total);
+}
+
+void surface_emit_run(const uint32_t* words, uint32_t depth, int closed, int format, uint64_t first, uint64_t capacity, void* out,
+                      const unsigned long long* scratch, hipStream_t st)
+{
+    const Field f = field_of(words, depth, closed);
+    const dim3 grid(groups_of(depth)), block(GROUP);
+    const unsigned long long a = first, b = capacity;
+    if (format == VRC_SURFACE_FACES)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_surface_emit<VRC_SURFACE_FACES, true>), grid, block, 0, st, f, scratch, a, b, out);
+    else if (((uintptr_t)out & 7u) == 0u)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_surface_emit<VRC_SURFACE_TRIANGLES, true>), grid, block, 0, st, f, scratch, a, b, out);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_surface_emit<VRC_SURFACE_TRIANGLES, false>), grid, block, 0, st, f, scratch, a, b, out);
+}
+
+}  // namespace vrc

@@ -11,7 +11,8 @@
 // Brushes (spheres, spheres at the hits of a ray batch), region copies between volumes and the two queries (single
 // voxels, solid voxels per box) walk the same rows of words as the boxes do.  The flood fill by connectivity
 // (vrc_volume_flood) has its kernels in vrc_flood.hip, the solid voxelisation of triangle meshes (vrc_volume_xor_mesh)
-// in vrc_voxelize.hip; the entry points, their ordering and their scratch blocks are here.
+// in vrc_voxelize.hip, its inverse, the exposed faces as a mesh (vrc_volume_extract_surface), in vrc_surface.hip; the
+// entry points, their ordering and their scratch blocks are here.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -20,6 +21,7 @@
 #include "../../include/vrc.h"
 #include "vrc_build_sweeps.h"
 #include "vrc_flood.h"
+#include "vrc_surface.h"
 #include "vrc_voxelize.h"
 
 struct vrc_volume {
@@ -39,6 +41,9 @@ struct vrc_volume {
     size_t flood_cap = 0;
     // vrc_volume_xor_mesh: the mark field, as large as d_bricks, allocated and zeroed by the first call, zero between calls
     uint32_t* d_marks = nullptr;
+    // vrc_volume_surface_count / _extract_surface: the per-workgroup face offsets and the totals (vrc_surface.h), allocated
+    // by the first call, fixed in size
+    unsigned long long* d_surface = nullptr;
     // the last asynchronous edit: commit / download / solid_count run on the NULL stream and wait for it first.  The flag
     // says that the event has been recorded at least once; it is never cleared, because a wait only orders ONE stream
     // behind the edit and the next caller may bring another.
@@ -433,6 +438,7 @@ void volume_free(vrc_volume* v)
     if (v->d_stage) (void)hipFree(v->d_stage);
     if (v->d_flood) (void)hipFree(v->d_flood);
     if (v->d_marks) (void)hipFree(v->d_marks);
+    if (v->d_surface) (void)hipFree(v->d_surface);
     v->grids.release();
     delete v;
 }
@@ -778,6 +784,78 @@ extern "C" int vrc_volume_count_boxes(vrc_volume* v, uint64_t n, const uint32_t*
     return VRC_OK;
 }
 
+// the offsets block of the two surface calls, allocated by the first
+static hipError_t surface_reserve(vrc_volume* v)
+{
+    return v->d_surface ? hipSuccess : hipMalloc((void**)&v->d_surface, vrc::surface_scratch_bytes(v->depth));
+}
+
+extern "C" int vrc_volume_surface_count(vrc_volume* v, int closed, uint64_t counts[6])
+{
+    const char* what = "vrc_volume_surface_count";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (!counts) return vrc::fail(VRC_ERR_INVALID, "%s: null counts", what);
+    // the NULL stream, behind the last asynchronous edit (a device-memory extraction, which shares the block, included)
+    hipError_t e = hipSetDevice(v->device);
+    if (e == hipSuccess) e = wait_for_edits(v);
+    if (e == hipSuccess) e = surface_reserve(v);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    vrc::surface_count_run(v->d_bricks, v->depth, closed, v->d_surface, nullptr);
+    e = hipGetLastError();
+    unsigned long long host[6];
+    if (e == hipSuccess) e = hipMemcpy(host, vrc::surface_direction_slots(v->d_surface, v->depth), sizeof host, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    for (int d = 0; d < 6; ++d) counts[d] = host[d];
+    return VRC_OK;
+}
+
+extern "C" int vrc_volume_extract_surface(vrc_volume* v, int closed, int format, uint64_t first, uint64_t capacity, void* out, uint64_t* total,
+                                          int mem, void* stream)
+{
+    const char* what = "vrc_volume_extract_surface";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (format != VRC_SURFACE_FACES && format != VRC_SURFACE_TRIANGLES) return vrc::fail(VRC_ERR_INVALID, "%s: bad format %d", what, format);
+    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
+    if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
+    const size_t record = format == VRC_SURFACE_FACES ? 16u : 72u;
+    if (mem == VRC_MEM_DEVICE && capacity && ((uintptr_t)out & (format == VRC_SURFACE_FACES ? 15u : 3u)))
+        return vrc::fail(VRC_ERR_INVALID, "%s: device buffer %p is not aligned to %d bytes", what, out, format == VRC_SURFACE_FACES ? 16 : 4);
+    hipStream_t st = (hipStream_t)stream;
+    // behind the last asynchronous edit whatever the memory kind: the offsets block is shared by every call
+    hipError_t e = hipSetDevice(v->device);
+    if (e == hipSuccess) e = order_behind_edits(v, st);
+    if (e == hipSuccess) e = surface_reserve(v);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    if (mem == VRC_MEM_DEVICE) {
+        vrc::surface_offsets_run(v->d_bricks, v->depth, closed, v->d_surface, (unsigned long long*)total, st);
+        if (capacity) vrc::surface_emit_run(v->d_bricks, v->depth, closed, format, first, capacity, out, v->d_surface, st);
+        if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
+        // recorded as an edit: the next call, on whatever stream, must not rewrite the offsets under this one
+        if ((e = finish(v, mem, st, true)) != hipSuccess) return vrc::fail_hip(e, what);
+        return VRC_OK;
+    }
+    vrc::surface_offsets_run(v->d_bricks, v->depth, closed, v->d_surface, nullptr, st);
+    e = hipGetLastError();
+    unsigned long long T = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&T, vrc::surface_total_slot(v->d_surface, v->depth), 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    if (total) *total = T;
+    // the offsets stay valid for every window: the call holds the stream until it returns
+    const uint64_t want = first < T ? (capacity < T - first ? capacity : T - first) : 0u;
+    const uint64_t window = want < (1ull << 20) ? want : (1ull << 20);
+    if (want && (e = stage_reserve(v, (size_t)window * record)) != hipSuccess) return vrc::fail_hip(e, what);
+    for (uint64_t done = 0; done < want; done += window) {
+        const uint64_t now = want - done < window ? want - done : window;
+        vrc::surface_emit_run(v->d_bricks, v->depth, closed, format, first + done, now, v->d_stage, v->d_surface, st);
+        if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
+        if ((e = hipMemcpyAsync((uint8_t*)out + done * record, v->d_stage, (size_t)now * record, hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return vrc::fail_hip(e, what);
+    }
+    if ((e = finish(v, mem, st, false)) != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
 extern "C" int vrc_volume_flood(vrc_volume* region, vrc_volume* medium, int connectivity, int through, uint32_t max_sweeps, vrc_flood_stats* stats)
 {
     const char* what = "vrc_volume_flood";
@@ -850,7 +928,8 @@ extern "C" int vrc_volume_download(vrc_volume* v, uint8_t* solid_host)
 extern "C" int vrc_volume_edit_scratch_bytes(const vrc_volume* v, uint64_t* bytes)
 {
     if (!v || !bytes) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_edit_scratch_bytes: null argument");
-    *bytes = (uint64_t)v->stage_cap + (uint64_t)v->flood_cap + (v->d_marks ? (uint64_t)vrc::voxelize_scratch_bytes(v->depth) : 0u);
+    *bytes = (uint64_t)v->stage_cap + (uint64_t)v->flood_cap + (v->d_marks ? (uint64_t)vrc::voxelize_scratch_bytes(v->depth) : 0u) +
+             (v->d_surface ? (uint64_t)vrc::surface_scratch_bytes(v->depth) : 0u);
     return VRC_OK;
 }
 

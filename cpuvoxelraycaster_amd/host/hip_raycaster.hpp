@@ -17,6 +17,7 @@
 // be handed to Camera::getClosestPoint and friends unchanged.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <fstream>
@@ -383,6 +384,70 @@ public:
         const uint32_t zero[3] = {0, 0, 0};
         copyRegion(clip, zero, size, at, op);               // `clip` is destroyed behind the copy: vrc_volume_destroy waits
     }
+    // Getting the world out (include/vrc.h: vrc_volume_extract_surface): the exposed faces of the voxel set in their
+    // canonical order.  closed: the volume's own faces count as exposed, the mesh is closed and xorMesh of its triangles
+    // into an empty volume gives the voxel set back.  counts[d], d = VRC_FACE_*: faces per direction.
+    std::vector<uint64_t> surfaceCount(bool closed = true)
+    {
+        flush();
+        std::vector<uint64_t> counts(6);
+        check(vrc_volume_surface_count(v_, closed ? 1 : 0, counts.data()), "vrc_volume_surface_count");
+        return counts;
+    }
+    // n x 4: x y z d of every exposed face (first / capacity: a window of the canonical order, in faces)
+    std::vector<uint32_t> surfaceFaces(bool closed = true, uint64_t first = 0, uint64_t capacity = ~0ull)
+    {
+        return extractSurface<uint32_t>(VRC_SURFACE_FACES, 4, closed, first, capacity);
+    }
+    // 2n x 9: two triangles per face in xorMesh's fixed point, wound outwards
+    std::vector<int32_t> surfaceTriangles(bool closed = true, uint64_t first = 0, uint64_t capacity = ~0ull)
+    {
+        return extractSurface<int32_t>(VRC_SURFACE_TRIANGLES, 18, closed, first, capacity);
+    }
+    // the same into device memory, asynchronous on `stream`; total_dev (may be null): a device uint64_t that receives the
+    // number of faces in stream order
+    void extractSurfaceDevice(int format, uint64_t first, uint64_t capacity, void* out_dev, uint64_t* total_dev, bool closed = true,
+                              void* stream = nullptr)
+    {
+        flush();
+        check(vrc_volume_extract_surface(v_, closed ? 1 : 0, format, first, capacity, out_dev, total_dev, VRC_MEM_DEVICE, stream),
+              "vrc_volume_extract_surface");
+    }
+    // Wavefront OBJ of the exposed faces: one `v` line per distinct corner (voxel units), one `f` line per face with four
+    // 1-based indices, wound outwards.  Returns the number of faces.
+    uint64_t toObj(const std::string& path, bool closed = true)
+    {
+        const std::vector<uint32_t> faces = surfaceFaces(closed);
+        const uint64_t n = faces.size() / 4, side = (1ull << depth()) + 1;
+        std::vector<uint64_t> corner(4 * n);          // (x * side + y) * side + z of each face's corners, in winding order
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint32_t d = faces[4 * i + 3], a = d >> 1, s = d & 1, u = (a + 1) % 3, w = (a + 2) % 3;
+            static const uint32_t du[4] = {0, 1, 1, 0}, dw[4] = {0, 0, 1, 1};
+            for (uint32_t k = 0; k < 4; ++k) {
+                const uint32_t j = s ? k : (4 - k) % 4;      // q0 q1 q2 q3 towards +axis, q0 q3 q2 q1 towards -axis
+                uint64_t q[3];
+                q[a] = faces[4 * i + a] + s;
+                q[u] = faces[4 * i + u] + du[j];
+                q[w] = faces[4 * i + w] + dw[j];
+                corner[4 * i + k] = (q[0] * side + q[1]) * side + q[2];
+            }
+        }
+        std::vector<uint64_t> verts(corner);
+        std::sort(verts.begin(), verts.end());
+        verts.erase(std::unique(verts.begin(), verts.end()), verts.end());
+        std::ofstream f(path);
+        if (!f) throw std::runtime_error("toObj: cannot open " + path);
+        for (size_t i = 0; i < verts.size(); ++i)
+            f << "v " << verts[i] / (side * side) << ' ' << verts[i] / side % side << ' ' << verts[i] % side << '\n';
+        for (uint64_t i = 0; i < n; ++i) {
+            f << 'f';
+            for (uint32_t k = 0; k < 4; ++k)
+                f << ' ' << (std::lower_bound(verts.begin(), verts.end(), corner[4 * i + k]) - verts.begin()) + 1;
+            f << '\n';
+        }
+        if (!f.flush()) throw std::runtime_error("toObj: write to " + path + " failed");
+        return n;
+    }
     std::unique_ptr<HipLSVO> commit(float* build_ms = nullptr)
     {
         flush();
@@ -407,6 +472,17 @@ public:
     vrc_volume* handle() const { return v_; }
 
 private:
+    template <class T>
+    std::vector<T> extractSurface(int format, size_t per_face, bool closed, uint64_t first, uint64_t capacity)
+    {
+        flush();
+        uint64_t total = 0;
+        check(vrc_volume_extract_surface(v_, closed ? 1 : 0, format, 0, 0, nullptr, &total, VRC_MEM_HOST, nullptr), "vrc_volume_extract_surface");
+        const uint64_t n = first < total ? std::min(capacity, total - first) : 0;
+        std::vector<T> out((size_t)n * per_face);
+        if (n) check(vrc_volume_extract_surface(v_, closed ? 1 : 0, format, first, n, out.data(), nullptr, VRC_MEM_HOST, nullptr), "vrc_volume_extract_surface");
+        return out;
+    }
     static std::vector<int32_t> meshSoup(const std::vector<int64_t>& fixed, const std::vector<uint32_t>& faces, const int64_t origin[3])
     {
         std::vector<int32_t> tris(faces.size() * 3);

@@ -308,6 +308,73 @@ class VoxelVolume:
             clip.close()        # vrc_volume_destroy waits for the copy
         return tuple(int(q) for q in lo), tuple(int(q) for q in size)
 
+    # ---- getting the world out: the exposed faces as a mesh (include/vrc.h: vrc_volume_extract_surface) ----
+
+    SURFACE_WINDOW = 1 << 20        # faces per call of the host forms with capacity=None
+
+    def surfaceCount(self, closed=True):
+        """(6,) uint64: exposed faces per direction d = 2 * axis + side (capi.VRC_FACE_*); closed=False leaves out the
+        faces on the volume's own faces.  Synchronous."""
+        out = np.zeros(6, np.uint64)
+        check(capi.load().vrc_volume_surface_count(self._h, int(bool(closed)), ptr(out)))
+        return out
+
+    def _surface(self, fmt, dtype, per_face, closed, first, capacity):
+        L, closed = capi.load(), int(bool(closed))
+        total = C.c_uint64()
+        check(L.vrc_volume_extract_surface(self._h, closed, fmt, 0, 0, None, C.byref(total), capi.VRC_MEM_HOST, None))
+        first = int(first)
+        n = max(0, total.value - first)
+        if capacity is not None:
+            n = min(n, int(capacity))
+        out = np.zeros((n, per_face), dtype)
+        for at in range(0, n, self.SURFACE_WINDOW):
+            part = out[at:at + self.SURFACE_WINDOW]
+            check(L.vrc_volume_extract_surface(self._h, closed, fmt, first + at, part.shape[0], ptr(part), None, capi.VRC_MEM_HOST, None))
+        return out
+
+    def surfaceFaces(self, closed=True, first=0, capacity=None):
+        """(n, 4) uint32 x y z d: the exposed faces [first, first + capacity) of the canonical order (by occupancy word,
+        direction, bit), each named by its SOLID voxel and direction.  capacity=None fetches everything from `first` on in
+        bounded windows.  Synchronous."""
+        return self._surface(capi.VRC_SURFACE_FACES, np.uint32, 4, closed, first, capacity)
+
+    def surfaceTriangles(self, closed=True, first=0, capacity=None):
+        """(2n, 9) int32: two triangles per face of the same window in xorMesh's fixed point (64 units per voxel), wound
+        counter-clockwise seen from outside.  With closed=True the mesh is closed: xorMesh of it into an empty volume of the
+        same depth gives this volume's voxel set back."""
+        return self._surface(capi.VRC_SURFACE_TRIANGLES, np.int32, 18, closed, first, capacity).reshape(-1, 9)
+
+    def extractSurfaceDevice(self, format, first, capacity, out_ptr, total_ptr, closed=True, stream=None):
+        """the same window into device memory (16 bytes per face, or 72 for its two triangles), asynchronous on `stream`;
+        total_ptr (may be None): a device uint64 that receives the number of faces in stream order"""
+        check(capi.load().vrc_volume_extract_surface(self._h, int(bool(closed)), int(format), int(first), int(capacity), ptr(out_ptr), ptr(total_ptr),
+                                                     capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    @staticmethod
+    def meshFromFaces(faces):
+        """(n, 4) x y z d face records -> (verts (m, 3) int32 in voxel units, quads (n, 4) int64 indices): every distinct
+        corner once, each quad wound counter-clockwise seen from outside.  Host arithmetic."""
+        f = np.asarray(faces, np.int64).reshape(-1, 4)
+        n = f.shape[0]
+        d = f[:, 3]
+        a, s = d >> 1, d & 1
+        u, w = (a + 1) % 3, (a + 2) % 3
+        rows = np.arange(n)
+        du, dw = np.array([0, 1, 1, 0]), np.array([0, 0, 1, 1])
+        corners = np.zeros((n, 4, 3), np.int64)
+        for k in range(4):
+            j = np.where(s == 1, k, (4 - k) % 4)         # q0 q1 q2 q3 towards +axis, q0 q3 q2 q1 towards -axis
+            corners[rows, k, a] = f[rows, a] + s
+            corners[rows, k, u] = f[rows, u] + du[j]
+            corners[rows, k, w] = f[rows, w] + dw[j]
+        verts, index = np.unique(corners.reshape(-1, 3), axis=0, return_inverse=True)
+        return verts.astype(np.int32).reshape(-1, 3), np.asarray(index, np.int64).reshape(n, 4)
+
+    def toMesh(self, closed=True):
+        """The exposed faces as an indexed quad mesh (verts, quads), see meshFromFaces; scenes.write_obj writes it out."""
+        return self.meshFromFaces(self.surfaceFaces(closed))
+
     def commit(self, textures=None):
         """A NEW LSVO of the current occupancy (build_ms = device time of the sweeps); the volume stays editable."""
         handle, ms = C.c_void_p(), C.c_float()
@@ -329,7 +396,7 @@ class VoxelVolume:
         return int(n.value)
 
     def editScratchBytes(self):
-        """device bytes in the scratch blocks of the edit calls (staging, flood, mark field); include/vrc.h"""
+        """device bytes in the scratch blocks of the edit calls (staging, flood, mark field, surface offsets); include/vrc.h"""
         n = C.c_uint64()
         check(capi.load().vrc_volume_edit_scratch_bytes(self._h, C.byref(n)))
         return int(n.value)

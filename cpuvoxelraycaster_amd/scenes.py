@@ -123,3 +123,16 @@ def box_mesh(lo, hi):
     quads = [(0, 2, 3, 1), (4, 5, 7, 6), (0, 1, 5, 4), (2, 6, 7, 3), (0, 4, 6, 2), (1, 3, 7, 5)]                 # -z +z -y +y -x +x
     faces = [f for a, b, c, d in quads for f in ((a, b, c), (a, c, d))]
     return verts, np.asarray(faces, np.int32)
+
+
+def write_obj(path, verts, quads):
+    """Wavefront OBJ, plain text: one `v x y z` line per vertex, one `f a b c d` line per face with 1-based indices
+    (VoxelVolume.toMesh gives both; faces of any one arity work)."""
+    verts = np.asarray(verts).reshape(-1, 3)
+    quads = np.asarray(quads, np.int64)
+    quads = quads.reshape(-1, quads.shape[-1] if quads.ndim > 1 else 4)
+    with open(path, "w") as f:
+        for v in verts.tolist():
+            f.write("v %s %s %s\n" % tuple(v))
+        for q in (quads + 1).tolist():
+            f.write("f " + " ".join(str(i) for i in q) + "\n")

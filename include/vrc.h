@@ -246,6 +246,49 @@ int vrc_volume_fill_spheres_at_hits(vrc_volume *v, uint64_t n, const vrc_hit *hi
  * at 512^3, 128 MiB at 1024^3), allocated by the first call and never grown or shrunk. */
 #define VRC_MESH_FRAC_BITS 6
 int vrc_volume_xor_mesh(vrc_volume *v, uint64_t n_tris, const int32_t *tris, int mem, void *stream);
+/* The exposed faces of the voxel set as a mesh: getting the world out without a dense download, and the inverse of
+ * vrc_volume_xor_mesh.  In integers: face d = 2 * axis + side of the SOLID voxel c = (x, y, z) (side 0 = towards -axis,
+ * 1 = towards +axis) is exposed iff the voxel c -/+ e_axis is empty.  A neighbour outside the volume counts as empty when
+ * closed != 0 -- the mesh is then closed, and vrc_volume_xor_mesh of its triangles into an empty volume of the same depth
+ * gives the voxel set back bit for bit -- and as solid when closed == 0: no faces on the volume's own faces (a terrain
+ * export).
+ *   Order: with n = S / 2, B = ((x>>1) n + (y>>1)) n + (z>>1) the voxel's brick and key = 8 B + (z&1) 4 + (y&1) 2 + (x&1)
+ *   its bit position in the occupancy, the faces are ordered by (key >> 5, d, key & 31): by 32-bit occupancy word, then
+ *   direction, then bit.  The output is unique, and a window addresses it.
+ *   Window: with T the total number of faces, the call writes those of [first, first + capacity) that lie in [0, T), in
+ *   that order, to out[0 ..], and touches nothing beyond what it writes; *total (may be NULL) receives T.  capacity == 0 with out == NULL is
+ *   legal and gives T alone; first >= T writes nothing.  All counts are in faces.
+ *   VRC_SURFACE_FACES: one record of 4 uint32 per face, x y z d.  VRC_SURFACE_TRIANGLES: two triangles per face, 2 x 9
+ *   int32 in vrc_volume_xor_mesh's units (64 per voxel); face i is triangles 2i and 2i + 1.  With a = d >> 1, s = d & 1,
+ *   u = (a + 1) % 3, v = (a + 2) % 3 every corner has coordinate a = 64 (c_a + s), and in (u, v) the corners are
+ *   q0 = 64 (c_u, c_v), q1 = 64 (c_u + 1, c_v), q2 = 64 (c_u + 1, c_v + 1), q3 = 64 (c_u, c_v + 1); s == 1 gives
+ *   (q0 q1 q2), (q0 q2 q3), s == 0 gives (q0 q2 q1), (q0 q3 q2): counter-clockwise seen from outside, the normal points
+ *   out of the solid voxel.  Coordinates are <= 2^16, inside vrc_volume_xor_mesh's range.
+ * `mem` says where out AND total live.  VRC_MEM_HOST: synchronous, staged in internal windows of at most 2^20 faces, so
+ * the staging block never grows beyond 72 MiB on account of this call whatever the capacity.  VRC_MEM_DEVICE:
+ * asynchronous on `stream`, total is a device uint64_t written in stream order; out must be 16-byte aligned for face
+ * records and 4-byte aligned for triangles (8-byte alignment gets wider stores).  Both calls only read the occupancy and
+ * are ordered behind the volume's last asynchronous edit; a device-memory extraction is itself recorded as the last
+ * asynchronous edit, because the offsets block below is shared by every call.  vrc_volume_surface_count is synchronous:
+ * counts[d] = exposed faces of direction d, their sum is T.
+ * Cost: three passes on one stream -- count per workgroup of 256 words, a scan of the workgroup totals, emit -- each one
+ * read of the occupancy and its neighbour words, HOWEVER SMALL the window; the writes follow the window, and a
+ * workgroup whose faces miss the window leaves at once.  vrc_volume_surface_count is the first pass alone.  The volume
+ * keeps a block of one 64-bit offset per workgroup plus seven totals, 8 * (ceil(words / 256) + 7) bytes: 1/128 of the
+ * occupancy + 56 bytes from depth 5 up (1 MiB at depth 10, 128 KiB at depth 9), 64 bytes below; allocated by the first of
+ * the two calls, never grown, counted by vrc_volume_edit_scratch_bytes.  Times: profiles/edit/bench_surface.json (512^3 terrain, 0.92 M
+ * faces, MI355X: all face records in 0.09 ms, all triangles in 0.20 ms, next to 0.03 ms for vrc_volume_solid_count). */
+#define VRC_FACE_XN 0   /* d = 2*axis + side; side 0 = the face towards -axis, 1 = towards +axis */
+#define VRC_FACE_XP 1
+#define VRC_FACE_YN 2
+#define VRC_FACE_YP 3
+#define VRC_FACE_ZN 4
+#define VRC_FACE_ZP 5
+#define VRC_SURFACE_FACES     0   /* one record per face:  4 uint32  x y z d  (the SOLID voxel, setCell coordinates) */
+#define VRC_SURFACE_TRIANGLES 1   /* two triangles per face: 2 x 9 int32 in vrc_volume_xor_mesh's units (64 per voxel) */
+int vrc_volume_surface_count(vrc_volume *v, int closed, uint64_t counts[6]);
+int vrc_volume_extract_surface(vrc_volume *v, int closed, int format, uint64_t first, uint64_t capacity,
+                               void *out, uint64_t *total, int mem, void *stream);
 /* Voxel src_lo + d of `src` goes to dst_lo + d of `dst` for 0 <= d < size, clipped to both volumes (what falls outside
  * either is neither read nor written).  The volumes may have different depths (a 32^3 clipboard stamped into a 512^3
  * world) and must be two different volumes on one device; any voxel offset is legal.  Asynchronous on `stream`: ordered
@@ -265,8 +308,9 @@ int vrc_volume_clone(vrc_volume *src, vrc_volume **out);
 int vrc_volume_get_voxels(vrc_volume *v, uint64_t n, const uint32_t *xyz, uint8_t *solid_out, int mem, void *stream);
 int vrc_volume_count_boxes(vrc_volume *v, uint64_t n, const uint32_t *lo_hi, uint64_t *counts, int mem, void *stream);
 /* Device bytes the volume holds at this moment in the scratch blocks of its edit calls: the grow-only staging block of the
- * host-memory calls, vrc_volume_flood's block and vrc_volume_xor_mesh's mark field (0 before the first call of each).  The
- * occupancy itself and vrc_volume_commit's grids are not counted.  Pure host bookkeeping, no device call. */
+ * host-memory calls, vrc_volume_flood's block, vrc_volume_xor_mesh's mark field and the surface calls' offsets block (0
+ * before the first call of each).  The occupancy itself and vrc_volume_commit's grids are not counted.  Pure host
+ * bookkeeping, no device call. */
 int vrc_volume_edit_scratch_bytes(const vrc_volume *v, uint64_t *bytes);
 
 /* Flood fill by connectivity, on the device: which voxels hold on to the ground, which cave is enclosed, which piece lies

@@ -45,6 +45,14 @@ times and the volume is empty again), median and range:
                        (tests/voxelize_model.py), then the upload of its result as z runs through vrc_volume_fill_boxes;
                        wall times
   first_call           wall time of the first call on a fresh volume (it allocates and zeroes the mark field) and of the second
+With --surface (written to profiles/edit/bench_surface.json by whoever runs it), the surface extraction at 512^3, output in
+device memory, device time by events on the NULL stream, one warm-up, A B A B in one process against B =
+vrc_volume_solid_count on the same volume (it reads the same words once), `--pairs` pairs, median and range, the ratio to B:
+  terrain              the FastNoise terrain
+  dug_terrain          the same after the flood mode's digs (400 spheres of radius 12 at ray hits)
+  stamped_noise        the dug terrain with a random 128^3 field of density 0.5 stamped in
+  per volume: count (vrc_volume_surface_count), faces / triangles (vrc_volume_extract_surface of ALL faces, closed), the
+  number of faces and the bytes written
 No threshold is applied; the numbers are reported."""
 import argparse
 import json
@@ -393,6 +401,49 @@ def bench_voxelize(vrc, depth, pairs):
     return res
 
 
+def bench_surface(vrc, depth, pairs):
+    import torch
+    S = 1 << depth
+    rng = np.random.default_rng(depth)
+    res = {"size": S, "pairs": pairs, "read_once_bytes": S ** 3 // 8}
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    volume = vrc.VoxelVolume.fromScene(scene)
+
+    def case():
+        counts = volume.surfaceCount()
+        T = int(counts.sum())
+        out = {"faces": T, "per_direction": [int(c) for c in counts], "solid": volume.solidCount()}
+        count_ms, read_ms = ab_device_ms(volume.surfaceCount, volume.solidCount, pairs)
+        out["count_ms"], out["read_once_ms"] = count_ms, read_ms
+        out["count_over_read_once"] = round(count_ms["median"] / read_ms["median"], 3)
+        for name, fmt, record in (("faces", vrc.capi.VRC_SURFACE_FACES, 16), ("triangles", vrc.capi.VRC_SURFACE_TRIANGLES, 72)):
+            buf = torch.empty(max(T, 1) * record // 4, dtype=torch.int32, device="cuda")
+            total = torch.zeros(1, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
+            ms, read_ms = ab_device_ms(lambda: volume.extractSurfaceDevice(fmt, 0, T, buf.data_ptr(), total.data_ptr()), volume.solidCount, pairs)
+            assert int(total.item()) == T
+            out[name + "_ms"], out[name + "_bytes"] = ms, T * record
+            out[name + "_over_read_once"] = round(ms["median"] / read_ms["median"], 3)
+            del buf
+        return out
+
+    res["terrain"] = case()
+    cam = np.array(vrc.reference_camera_position(depth), np.float32) / np.float32(S) + np.float32(1.0)
+    d = rng.normal(size=(400, 3)).astype(np.float32) * np.float32(0.3) + np.array([0.0, 0.5, 0.8], np.float32)
+    d /= np.linalg.norm(d, axis=1, keepdims=True).astype(np.float32)
+    hits = scene.castRays(np.tile(cam, (400, 1)).astype(np.float32), d)
+    volume.fillSpheresAtHits(hits, 12, False)
+    res["digs"] = {"rays": 400, "unit_hits": int(((hits["hit"] & 0xff) == 1).sum()), "radius": 12}
+    res["dug_terrain"] = case()
+    noise = vrc.VoxelVolume(7)
+    noise.setVoxels(np.argwhere(rng.random((128, 128, 128)) < 0.5))
+    volume.copyRegion(noise, (0, 0, 0), (128, 128, 128), (S // 2 - 64, S // 2, S // 2 - 64))
+    res["stamped_noise"] = case()
+    noise.close()
+    volume.close()
+    return res
+
+
 def bench_depth(vrc, depth, pairs):
     import torch
     S = 1 << depth
@@ -453,7 +504,10 @@ def main():
     ap.add_argument("--brushes", action="store_true", help="time the brushes, copies and queries (depths 9 and 10 unless --depths is given)")
     ap.add_argument("--flood", action="store_true", help="time vrc_volume_flood (depth 9 unless --depths is given)")
     ap.add_argument("--voxelize", action="store_true", help="time vrc_volume_xor_mesh (depth 9 unless --depths is given)")
+    ap.add_argument("--surface", action="store_true", help="time vrc_volume_surface_count / vrc_volume_extract_surface (depth 9 unless --depths is given)")
     args = ap.parse_args()
+    if args.surface and args.depths == [8, 9, 10]:
+        args.depths = [9]
     if args.voxelize and args.depths == [8, 9, 10]:
         args.depths = [9]
     if args.brushes and args.depths == [8, 9, 10]:
@@ -466,9 +520,9 @@ def main():
     import cpuvoxelraycaster_amd as vrc
     if not torch.cuda.is_available():
         raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-    out = {"bench": "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
+    out = {"bench": "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
     for d in args.depths:
-        out["depths"][str(d)] = (bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
+        out["depths"][str(d)] = (bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
     print(json.dumps(out))
 
 
