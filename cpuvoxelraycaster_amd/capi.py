@@ -15,6 +15,7 @@ VRC_MEM_HOST, VRC_MEM_DEVICE = 0, 1
 VRC_COPY_REPLACE, VRC_COPY_OR, VRC_COPY_ANDNOT = 0, 1, 2
 VRC_CONNECT_FACES, VRC_CONNECT_ALL = 6, 26
 VRC_FLOOD_SOLID, VRC_FLOOD_EMPTY = 0, 1
+VRC_NO_COMPONENT = 0xffffffff
 VRC_MESH_FRAC_BITS = 6
 VRC_FACE_XN, VRC_FACE_XP, VRC_FACE_YN, VRC_FACE_YP, VRC_FACE_ZN, VRC_FACE_ZP = range(6)
 VRC_SURFACE_FACES, VRC_SURFACE_TRIANGLES = 0, 1
@@ -26,6 +27,9 @@ HIT_DTYPE = np.dtype([
 LNODE_DTYPE = np.dtype([("color", "u1"), ("child_mask", "u1"), ("leaf_mask", "u1"),
                         ("pad", "u1"), ("child_offset", "<u4")])
 assert HIT_DTYPE.itemsize == 48 and LNODE_DTYPE.itemsize == 8
+# vrc_component (include/vrc.h): one record per connected component
+COMPONENT_DTYPE = np.dtype([("first", "<u4", 3), ("lo", "<u4", 3), ("hi", "<u4", 3), ("reserved", "<u4"), ("voxels", "<u8")])
+assert COMPONENT_DTYPE.itemsize == 48
 
 
 class VrcError(RuntimeError):
@@ -148,6 +152,14 @@ SYMBOLS = {
     "vrc_volume_get_voxels": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
     "vrc_volume_count_boxes": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
     "vrc_volume_flood": (_int, [_vp, _vp, _int, _int, _u32, C.POINTER(FloodStats)]),
+    "vrc_volume_label_components": (_int, [_vp, _int, _int, C.POINTER(_vp), C.POINTER(_u64)]),
+    "vrc_labels_destroy": (_int, [_vp]),
+    "vrc_labels_count": (_u64, [_vp]),
+    "vrc_labels_depth": (_u32, [_vp]),
+    "vrc_labels_bytes": (_u64, [_vp]),
+    "vrc_labels_components": (_int, [_vp, _u64, _u64, _vp, _int, _vp]),
+    "vrc_labels_at": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
+    "vrc_labels_select": (_int, [_vp, _vp, _vp, _int, _int, _vp]),
     "vrc_volume_xor_mesh": (_int, [_vp, _u64, _vp, _int, _vp]),
     "vrc_volume_surface_count": (_int, [_vp, _int, _vp]),
     "vrc_volume_extract_surface": (_int, [_vp, _int, _int, _u64, _u64, _vp, _vp, _int, _vp]),

@@ -11,8 +11,9 @@
 // Brushes (spheres, spheres at the hits of a ray batch), region copies between volumes and the two queries (single
 // voxels, solid voxels per box) walk the same rows of words as the boxes do.  The flood fill by connectivity
 // (vrc_volume_flood) has its kernels in vrc_flood.hip, the solid voxelisation of triangle meshes (vrc_volume_xor_mesh)
-// in vrc_voxelize.hip, its inverse, the exposed faces as a mesh (vrc_volume_extract_surface), in vrc_surface.hip; the
-// entry points, their ordering and their scratch blocks are here.
+// in vrc_voxelize.hip, its inverse, the exposed faces as a mesh (vrc_volume_extract_surface), in vrc_surface.hip, the
+// labelling of connected components (vrc_volume_label_components, vrc_labels_*) in vrc_components.hip; the entry points,
+// their ordering and their scratch blocks are here.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -20,6 +21,7 @@
 
 #include "../../include/vrc.h"
 #include "vrc_build_sweeps.h"
+#include "vrc_components.h"
 #include "vrc_flood.h"
 #include "vrc_surface.h"
 #include "vrc_voxelize.h"
@@ -950,5 +952,145 @@ extern "C" int vrc_volume_solid_count(vrc_volume* v, uint64_t* count)
     if (e == hipSuccess) e = hipMemcpy(&total, v->d_count, 8, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return vrc::fail_hip(e, "vrc_volume_solid_count");
     *count = total;
+    return VRC_OK;
+}
+
+// ---- connected components --------------------------------------------------
+
+// A snapshot that owns its memory and is never written after vrc_volume_label_components returns: no event, no scratch.
+struct vrc_labels {
+    int device = 0;
+    uint32_t depth = 0;
+    uint64_t count = 0;
+    uint32_t* d_ids = nullptr;            // 8^depth ids, indexed by key
+    vrc_component* d_records = nullptr;   // count records, nullptr when count == 0
+};
+
+extern "C" int vrc_volume_label_components(vrc_volume* medium, int connectivity, int through, vrc_labels** out, uint64_t* n_components)
+{
+    const char* what = "vrc_volume_label_components";
+    if (!medium || !out) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (connectivity != VRC_CONNECT_FACES && connectivity != VRC_CONNECT_ALL) return vrc::fail(VRC_ERR_INVALID, "%s: connectivity %d is neither 6 nor 26", what, connectivity);
+    if (through != VRC_FLOOD_SOLID && through != VRC_FLOOD_EMPTY) return vrc::fail(VRC_ERR_INVALID, "%s: bad through %d", what, through);
+    vrc_labels* l = new (std::nothrow) vrc_labels();
+    if (!l) return vrc::fail(VRC_ERR_OOM, "out of host memory");
+    l->device = medium->device; l->depth = medium->depth;
+    // the NULL stream, behind the last asynchronous edit of the medium, as commit / download are
+    uint32_t* d_scratch = nullptr;
+    hipError_t e = hipSetDevice(medium->device);
+    if (e == hipSuccess) e = wait_for_edits(medium);
+    if (e == hipSuccess) e = hipMalloc((void**)&l->d_ids, (size_t)4u << (3u * l->depth));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_scratch, vrc::components_scratch_bytes(l->depth));
+    uint32_t C = 0;
+    if (e == hipSuccess) {
+        vrc::components_roots_run(medium->d_bricks, l->depth, connectivity, through, l->d_ids, d_scratch, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(&C, vrc::components_total_slot(d_scratch, l->depth), 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && C) e = hipMalloc((void**)&l->d_records, (size_t)C * sizeof(vrc_component));
+    if (e == hipSuccess && C) {
+        vrc::components_ids_run(l->depth, l->d_ids, d_scratch, l->d_records, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (d_scratch) (void)hipFree(d_scratch);
+    if (e != hipSuccess) {
+        (void)vrc_labels_destroy(l);
+        return vrc::fail_hip(e, what);
+    }
+    l->count = C;
+    *out = l;
+    if (n_components) *n_components = C;
+    return VRC_OK;
+}
+
+extern "C" int vrc_labels_destroy(vrc_labels* l)
+{
+    if (!l) return VRC_OK;
+    (void)hipSetDevice(l->device);
+    (void)hipDeviceSynchronize();       // device-memory calls may still be reading it on a caller's stream
+    if (l->d_ids) (void)hipFree(l->d_ids);
+    if (l->d_records) (void)hipFree(l->d_records);
+    delete l;
+    return VRC_OK;
+}
+
+extern "C" uint64_t vrc_labels_count(const vrc_labels* l) { return l ? l->count : 0; }
+extern "C" uint32_t vrc_labels_depth(const vrc_labels* l) { return l ? l->depth : 0; }
+extern "C" uint64_t vrc_labels_bytes(const vrc_labels* l) { return l ? ((uint64_t)4u << (3u * l->depth)) + l->count * sizeof(vrc_component) : 0; }
+
+extern "C" int vrc_labels_components(const vrc_labels* l, uint64_t first, uint64_t capacity, vrc_component* out, int mem, void* stream)
+{
+    const char* what = "vrc_labels_components";
+    if (!l) return vrc::fail(VRC_ERR_INVALID, "%s: null labels", what);
+    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
+    if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
+    const uint64_t want = first < l->count ? (capacity < l->count - first ? capacity : l->count - first) : 0u;
+    if (!want) return VRC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(l->device);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(out, l->d_records + first, (size_t)want * sizeof(vrc_component), mem == VRC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+extern "C" int vrc_labels_at(const vrc_labels* l, uint64_t n, const uint32_t* xyz, uint32_t* ids, int mem, void* stream)
+{
+    const char* what = "vrc_labels_at";
+    if (!l) return vrc::fail(VRC_ERR_INVALID, "%s: null labels", what);
+    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
+    if (n == 0) return VRC_OK;
+    if (!xyz || !ids) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "%s: too many voxels for one launch", what);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(l->device);
+    const uint32_t* d_xyz = xyz;
+    uint32_t* d_ids = ids;
+    uint32_t* d_stage = nullptr;          // the snapshot keeps no scratch: a host-memory call stages in a block of its own
+    if (mem == VRC_MEM_HOST) {
+        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, (size_t)n * 16u);
+        d_xyz = d_stage;
+        d_ids = d_stage + (size_t)n * 3u;
+        if (e == hipSuccess) e = hipMemcpyAsync(d_stage, xyz, (size_t)n * 12u, hipMemcpyHostToDevice, st);
+    }
+    if (e == hipSuccess) {
+        vrc::components_at_run(l->d_ids, l->depth, n, d_xyz, d_ids, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipMemcpyAsync(ids, d_ids, (size_t)n * 4u, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipStreamSynchronize(st);
+    if (d_stage) (void)hipFree(d_stage);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+extern "C" int vrc_labels_select(const vrc_labels* l, const uint8_t* keep, vrc_volume* dst, int op, int mem, void* stream)
+{
+    const char* what = "vrc_labels_select";
+    if (!l || !dst) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (op != VRC_COPY_REPLACE && op != VRC_COPY_OR && op != VRC_COPY_ANDNOT) return vrc::fail(VRC_ERR_INVALID, "%s: bad op %d", what, op);
+    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
+    if (dst->depth != l->depth) return vrc::fail(VRC_ERR_INVALID, "%s: labels of depth %u, volume of depth %u", what, l->depth, dst->depth);
+    if (dst->device != l->device) return vrc::fail(VRC_ERR_INVALID, "%s: labels on device %d, volume on device %d", what, l->device, dst->device);
+    if (!keep && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null keep with %llu components", what, (unsigned long long)l->count);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(l->device);
+    if (e == hipSuccess) e = order_behind_edits(dst, st);
+    const uint8_t* d_keep = keep;
+    uint8_t* d_stage = nullptr;
+    if (mem == VRC_MEM_HOST && l->count) {
+        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, (size_t)l->count);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_stage, keep, (size_t)l->count, hipMemcpyHostToDevice, st);
+        d_keep = d_stage;
+    }
+    if (e == hipSuccess) {
+        vrc::components_select_run(l->d_ids, l->depth, d_keep, dst->d_bricks, op, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = finish(dst, mem, st, true);
+    if (d_stage) (void)hipFree(d_stage);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
     return VRC_OK;
 }

@@ -192,6 +192,50 @@ private:
     int device_ = 0;
 };
 
+class HipVoxelVolume;
+
+// The pieces of a volume, named (include/vrc.h: vrc_volume_label_components): a snapshot on the device that later edits
+// of the volume do not change.  Ids run 0 .. count() - 1 by ascending key of each piece's first voxel.  Movable, RAII.
+class HipVoxelLabels {
+public:
+    ~HipVoxelLabels() { vrc_labels_destroy(l_); }
+    HipVoxelLabels(HipVoxelLabels&& o) noexcept : l_(o.l_) { o.l_ = nullptr; }
+    HipVoxelLabels& operator=(HipVoxelLabels&& o) noexcept
+    {
+        if (this != &o) { vrc_labels_destroy(l_); l_ = o.l_; o.l_ = nullptr; }
+        return *this;
+    }
+    HipVoxelLabels(const HipVoxelLabels&) = delete;
+    HipVoxelLabels& operator=(const HipVoxelLabels&) = delete;
+
+    uint64_t count() const { return vrc_labels_count(l_); }
+    uint32_t depth() const { return vrc_labels_depth(l_); }
+    uint64_t bytes() const { return vrc_labels_bytes(l_); }
+    // the records [first, first + capacity) that exist, in id order
+    std::vector<vrc_component> components(uint64_t first = 0, uint64_t capacity = ~0ull) const
+    {
+        const uint64_t C = count(), n = first < C ? std::min(capacity, C - first) : 0;
+        std::vector<vrc_component> out((size_t)n);
+        if (n) check(vrc_labels_components(l_, first, n, out.data(), VRC_MEM_HOST, nullptr), "vrc_labels_components");
+        return out;
+    }
+    // the piece of each of n voxels (xyz: n x 3), VRC_NO_COMPONENT outside M or outside the volume
+    std::vector<uint32_t> at(const uint32_t* xyz, uint64_t n) const
+    {
+        std::vector<uint32_t> ids((size_t)n);
+        check(vrc_labels_at(l_, n, xyz, ids.data(), VRC_MEM_HOST, nullptr), "vrc_labels_at");
+        return ids;
+    }
+    // dst becomes (VRC_COPY_REPLACE) / gains (_OR) / loses (_ANDNOT) the voxels of the pieces with keep[id] != 0
+    inline void select(const std::vector<uint8_t>& keep, HipVoxelVolume& dst, int op = VRC_COPY_REPLACE) const;
+    vrc_labels* handle() const { return l_; }
+
+private:
+    friend class HipVoxelVolume;
+    explicit HipVoxelLabels(vrc_labels* adopted) : l_(adopted) {}
+    vrc_labels* l_ = nullptr;
+};
+
 // What SVO::setCell + compileSVO are to the reference (svo.hpp:72, lsvo_utils.cpp:4), on the device and repeatable: the
 // occupancy of the S^3 volume stays resident, setCell() queues edits, commit() applies them and builds a NEW HipLSVO
 // (bit-identical to compileSVO of the voxel set).  A scene in use is never touched: keep the old HipLSVO until the frames
@@ -318,6 +362,25 @@ public:
         debris->copyRegion(supported, zero, all, at, VRC_COPY_ANDNOT);
         copyRegion(supported, zero, all, at, VRC_COPY_REPLACE);
         return debris;       // `supported` is destroyed behind the copies: vrc_volume_destroy waits for the device
+    }
+    // Every connected piece of the solid voxels (of the empty ones with through_empty) named in one call.  Synchronous.
+    HipVoxelLabels labelComponents(int connectivity = VRC_CONNECT_FACES, bool through_empty = false)
+    {
+        flush();
+        vrc_labels* l = nullptr;
+        check(vrc_volume_label_components(v_, connectivity, through_empty ? VRC_FLOOD_EMPTY : VRC_FLOOD_SOLID, &l, nullptr), "vrc_volume_label_components");
+        return HipVoxelLabels(l);
+    }
+    // Clears every solid piece of fewer than min_voxels voxels; returns how many pieces that were.
+    uint64_t removeSmallPieces(uint64_t min_voxels, int connectivity = VRC_CONNECT_FACES)
+    {
+        HipVoxelLabels labels = labelComponents(connectivity);
+        const std::vector<vrc_component> records = labels.components();
+        std::vector<uint8_t> small(records.size());
+        uint64_t removed = 0;
+        for (size_t i = 0; i < records.size(); ++i) removed += small[i] = records[i].voxels < min_voxels ? 1 : 0;
+        if (removed) labels.select(small, *this, VRC_COPY_ANDNOT);
+        return removed;
     }
     // Solid voxelisation by crossing parity (include/vrc.h: vrc_volume_xor_mesh): n x 9 int32 triangles in setCell
     // coordinates with VRC_MESH_FRAC_BITS fractional bits; every voxel whose centre lies under an odd number of them is
@@ -498,6 +561,13 @@ private:
     std::vector<uint32_t> queue_;
     bool queue_solid_ = true;
 };
+
+inline void HipVoxelLabels::select(const std::vector<uint8_t>& keep, HipVoxelVolume& dst, int op) const
+{
+    if (keep.size() != count()) throw std::invalid_argument("HipVoxelLabels::select: keep must have one byte per component");
+    dst.flush();
+    check(vrc_labels_select(l_, keep.empty() ? nullptr : keep.data(), dst.handle(), op, VRC_MEM_HOST, nullptr), "vrc_labels_select");
+}
 
 // Camera values Camera::getRay reads (camera_controller.hpp:16-49); the Camera /
 // FlyController classes themselves stay untouched on the host.

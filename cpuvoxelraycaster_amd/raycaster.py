@@ -260,6 +260,40 @@ class VoxelVolume:
         supported.close()
         return debris
 
+    def labelComponents(self, connectivity=6, through_empty=False):
+        """Every connected piece of the solid voxels (or, with through_empty, of the empty ones) named in one call
+        (include/vrc.h: vrc_volume_label_components): a VoxelLabels snapshot that later edits do not change.  Synchronous."""
+        handle, count = C.c_void_p(), C.c_uint64()
+        check(capi.load().vrc_volume_label_components(self._h, int(connectivity), capi.VRC_FLOOD_EMPTY if through_empty else capi.VRC_FLOOD_SOLID,
+                                                      C.byref(handle), C.byref(count)))
+        return VoxelLabels(handle, int(count.value), self.depth, self.device)
+
+    def removeSmallPieces(self, min_voxels, connectivity=6):
+        """Clears every solid piece of fewer than min_voxels voxels (the specks a dig or a leaky mesh leaves); returns
+        (pieces before, pieces removed)."""
+        labels = self.labelComponents(connectivity)
+        small = (labels.components()["voxels"] < min_voxels).astype(np.uint8)
+        if small.any():
+            labels.select(small, self, capi.VRC_COPY_ANDNOT)
+        labels.close()
+        return len(small), int(small.sum())
+
+    def splitPieces(self, connectivity=6, max_pieces=None):
+        """The solid pieces as bodies: (records in id order, [(id, VoxelVolume holding that piece alone), ...]) for the
+        max_pieces largest pieces (all of them with None), largest first, ties by id."""
+        labels = self.labelComponents(connectivity)
+        records = labels.components()
+        order = np.argsort(-records["voxels"].astype(np.int64), kind="stable")
+        if max_pieces is not None:
+            order = order[:max_pieces]
+        pieces = []
+        for i in order:
+            keep = np.zeros(len(records), np.uint8)
+            keep[i] = 1
+            pieces.append((int(i), labels.select(keep)))
+        labels.close()
+        return records, pieces
+
     def xorMesh(self, tris_fixed, device=False, stream=None):
         """Solid voxelisation by crossing parity (include/vrc.h: vrc_volume_xor_mesh): (n, 9) int32 triangles in setCell
         coordinates with 6 fractional bits (64 units per voxel, voxel centres at 64 c + 32); every voxel whose centre lies
@@ -404,6 +438,63 @@ class VoxelVolume:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             capi.load().vrc_volume_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VoxelLabels:
+    """The component id of every voxel of M, resident on the device (include/vrc.h: vrc_labels_*): a snapshot made by
+    VoxelVolume.labelComponents.  Ids run 0 .. count-1 by ascending key of each piece's first voxel."""
+
+    def __init__(self, handle, count, depth, device):
+        self._h, self.count, self.depth, self.device = handle, count, depth, device
+
+    def components(self, first=0, capacity=None):
+        """the records [first, first + capacity) that exist, as capi.COMPONENT_DTYPE (first, lo, hi, voxels)"""
+        if capacity is None:
+            capacity = max(self.count - first, 0)
+        out = np.zeros(min(capacity, max(self.count - first, 0)), capi.COMPONENT_DTYPE)
+        check(capi.load().vrc_labels_components(self._h, first, len(out), ptr(out) if len(out) else None, capi.VRC_MEM_HOST, None))
+        return out
+
+    def componentsDevice(self, first, capacity, out_ptr, stream=None):
+        check(capi.load().vrc_labels_components(self._h, first, capacity, ptr(out_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def at(self, xyz):
+        """uint32 id per (n, 3) voxel coordinate, capi.VRC_NO_COMPONENT outside M or outside the volume"""
+        xyz = np.ascontiguousarray(xyz, np.uint32).reshape(-1, 3)
+        out = np.zeros(xyz.shape[0], np.uint32)
+        check(capi.load().vrc_labels_at(self._h, xyz.shape[0], ptr(xyz), ptr(out), capi.VRC_MEM_HOST, None))
+        return out
+
+    def atDevice(self, n, xyz_ptr, ids_ptr, stream=None):
+        check(capi.load().vrc_labels_at(self._h, n, ptr(xyz_ptr), ptr(ids_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def select(self, keep, dst=None, op=capi.VRC_COPY_REPLACE):
+        """dst (a new volume with None) becomes / gains / loses the voxels of the pieces with keep[id] != 0; returns dst"""
+        keep = np.ascontiguousarray(keep, np.uint8).reshape(-1)
+        if len(keep) != self.count:
+            raise ValueError(f"keep has {len(keep)} entries for {self.count} components")
+        if dst is None:
+            dst = VoxelVolume(self.depth, self.device)
+        check(capi.load().vrc_labels_select(self._h, ptr(keep) if self.count else None, dst._h, int(op), capi.VRC_MEM_HOST, None))
+        return dst
+
+    def selectDevice(self, keep_ptr, dst, op=capi.VRC_COPY_REPLACE, stream=None):
+        """the same with `count` bytes of keep in device memory, asynchronous on `stream`"""
+        check(capi.load().vrc_labels_select(self._h, ptr(keep_ptr), dst._h, int(op), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def bytes(self):
+        return int(capi.load().vrc_labels_bytes(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            capi.load().vrc_labels_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -345,6 +345,57 @@ typedef struct vrc_flood_stats { uint64_t reached; uint32_t sweeps; uint32_t con
 int vrc_volume_flood(vrc_volume *region, vrc_volume *medium, int connectivity, int through,
                      uint32_t max_sweeps, vrc_flood_stats *stats);
 
+/* Connected components, on the device: every piece of M named in one call -- the debris of a dig as separate bodies, the
+ * floating specks a leaky model leaves behind vrc_volume_xor_mesh, every enclosed cave (through = VRC_FLOOD_EMPTY), the
+ * piece under each crosshair of a ray batch.  M is the flood's M: the solid voxels of `medium` (VRC_FLOOD_SOLID) or its
+ * empty voxels (VRC_FLOOD_EMPTY); the volume's faces are walls, there is no wrap-around and nothing beyond them counts as
+ * empty.  A component is a maximal subset of M whose voxels are joined by chains of neighbours lying in M; neighbours share
+ * a face (VRC_CONNECT_FACES) or a face, an edge or a corner (VRC_CONNECT_ALL).
+ *
+ * Order and ids.  A voxel's key is the surface order's: 8 B + (z&1) 4 + (y&1) 2 + (x&1), B its brick index
+ * ((x/2) n + y/2) n + z/2.  A component's representative is its voxel of minimum key, and components are numbered
+ * 0 .. C-1 by ascending representative key.  The labelling is therefore unique: it depends neither on scheduling nor on
+ * the number of passes, and two calls give identical bytes.
+ *
+ * vrc_volume_label_components is synchronous (the host needs C to size its buffers), on the NULL stream, ordered behind
+ * the medium's last asynchronous edit, and only reads the medium.  Depths 2..10.  The result is a SNAPSHOT: later edits of
+ * the medium do not change it, and destroying the medium leaves it valid.  It owns its memory: 4 bytes per voxel for the
+ * ids plus 48 bytes per component -- 512 MiB at 512^3, 4 GiB at 1024^3 (8^10 = 2^30 voxels: keys and ids fit 32 bits).
+ * *n_components may be NULL; an empty M gives C = 0 and a valid handle.
+ *
+ * The device labels by union-find on the id array (csrc/vrc_components.hip): a kernel per phase on one stream, labels
+ * only ever lowered with 32-bit vector atomics, no workgroup waiting for another; about eight passes over the id array.
+ * No time has been measured yet (tools/bench_edit.py --components writes profiles/edit/bench_components.json).
+ *
+ * vrc_labels_components writes the records of [first, first + capacity) that lie in [0, C), in id order, to out[0..]
+ * and touches nothing beyond what it writes; first >= C writes nothing, capacity == 0 with out == NULL is legal.
+ * vrc_labels_at: ids[i] = the component of voxel xyz[3i..3i+2], VRC_NO_COMPONENT for a voxel outside M or outside the
+ * volume (with vrc_hit_to_voxel: the piece under every crosshair of a ray batch).
+ * vrc_labels_select: keep has C bytes; with K = { v in M : keep[id(v)] != 0 } over the whole volume, dst becomes K
+ * (VRC_COPY_REPLACE), dst | K (VRC_COPY_OR) or dst & ~K (VRC_COPY_ANDNOT).  dst is a volume of the labels' depth on the
+ * labels' device and may be the medium itself; C == 0 with keep == NULL is legal.  Whole words are written once with
+ * plain stores.
+ * mem / stream as in vrc_volume_get_voxels: VRC_MEM_HOST is staged and synchronous, VRC_MEM_DEVICE works in place and is
+ * asynchronous on `stream`; a device-memory select is recorded as dst's last asynchronous edit, as vrc_volume_copy_region
+ * is.  NULL handles, a connectivity other than 6 / 26, a `through` other than 0 / 1, an unknown op, a depth or device
+ * mismatch and a bad `mem` are VRC_ERR_INVALID, refused before any device call. */
+typedef struct vrc_labels vrc_labels;    /* a snapshot: the component id of every voxel of M, resident on the volume's device */
+#define VRC_NO_COMPONENT 0xffffffffu
+typedef struct vrc_component {           /* 48 bytes */
+    uint32_t first[3];                   /* the representative: flooding `medium` from it gives this piece back */
+    uint32_t lo[3], hi[3];               /* bounding box, lo inclusive, hi exclusive (vrc_volume_fill_boxes' form) */
+    uint32_t reserved;                   /* 0 */
+    uint64_t voxels;
+} vrc_component;
+int vrc_volume_label_components(vrc_volume *medium, int connectivity, int through, vrc_labels **out, uint64_t *n_components);
+int vrc_labels_destroy(vrc_labels *l);
+uint64_t vrc_labels_count(const vrc_labels *l);
+uint32_t vrc_labels_depth(const vrc_labels *l);
+uint64_t vrc_labels_bytes(const vrc_labels *l);          /* device bytes held; pure host bookkeeping */
+int vrc_labels_components(const vrc_labels *l, uint64_t first, uint64_t capacity, vrc_component *out, int mem, void *stream);
+int vrc_labels_at(const vrc_labels *l, uint64_t n, const uint32_t *xyz, uint32_t *ids, int mem, void *stream);
+int vrc_labels_select(const vrc_labels *l, const uint8_t *keep, vrc_volume *dst, int op, int mem, void *stream);
+
 /* ---- dense grid: Grid3D<X,Y,Z> (grid_3d.hpp:10-138) ------------------- */
 
 /* cells[(x*Y + y)*Z + z] = Cell::Type (0 = Empty). */

@@ -53,6 +53,19 @@ vrc_volume_solid_count on the same volume (it reads the same words once), `--pai
   stamped_noise        the dug terrain with a random 128^3 field of density 0.5 stamped in
   per volume: count (vrc_volume_surface_count), faces / triangles (vrc_volume_extract_surface of ALL faces, closed), the
   number of faces and the bytes written
+With --components (printed and written to profiles/edit/bench_components.json), the connected-component labelling at 512^3,
+device time by events on the NULL stream around the synchronous calls, one warm-up, `--pairs` repetitions, median and range:
+  terrain / dug_terrain / dug_terrain_26 / air
+                       the FastNoise terrain, the same after the flood mode's digs (400 spheres of radius 12 at ray hits)
+                       under 6 and 26, and the air above it (through the empty voxels).  Per case: label (the whole
+                       vrc_volume_label_components call), records (all of them to host memory, wall time), select_one (the
+                       largest piece into a fresh volume, keep in device memory), select_all, remove_small (wall time of
+                       VoxelVolume.removeSmallPieces(8) on a clone), the number of pieces and the largest
+  scale                on the dug terrain, in the same run: fill_ids = a plain device fill of an array of the id array's size
+                       (4 bytes per voxel; the labelling is expected to cost a small number of such passes), solid_count,
+                       one full vrc_volume_flood from the bottom slab, and flood_per_piece = what the labelling replaces:
+                       one vrc_volume_flood from each record's `first` for at most the 16 largest pieces, and that mean
+                       times the number of pieces (EXTRAPOLATED, labelled so)
 No threshold is applied; the numbers are reported."""
 import argparse
 import json
@@ -497,6 +510,124 @@ def bench_depth(vrc, depth, pairs):
     return res
 
 
+def bench_components(vrc, depth, pairs):
+    import torch
+    S = 1 << depth
+    rng = np.random.default_rng(depth)
+    res = {"size": S, "pairs": pairs, "id_array_bytes": 4 * S ** 3}
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    terrain = vrc.VoxelVolume.fromScene(scene)
+
+    def timed(fn, repeats):
+        """device ms by events around fn, one warm-up; returns (stat, the last result)"""
+        out, last = [], None
+        for i in range(repeats + 1):
+            if last is not None and hasattr(last, "close"):
+                last.close()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            last = fn()
+            b.record()
+            b.synchronize()
+            if i:
+                out.append(a.elapsed_time(b))
+        return stat(out, 4), last
+
+    def case(medium, connectivity, through_empty):
+        r = {"connectivity": connectivity, "through_empty": through_empty}
+        r["label_ms"], labels = timed(lambda: medium.labelComponents(connectivity, through_empty), pairs)
+        walls = []
+        for i in range(pairs + 1):
+            t0 = time.perf_counter()
+            rec = labels.components()
+            if i:
+                walls.append((time.perf_counter() - t0) * 1e3)
+        r["records_wall_ms"] = stat(walls, 4)
+        r["pieces"], r["largest"], r["voxels"] = len(rec), int(rec["voxels"].max()), int(rec["voxels"].sum(dtype=np.uint64))
+        r["labels_bytes"] = labels.bytes()
+        dst = vrc.VoxelVolume(depth)
+        one = np.zeros(len(rec), np.uint8)
+        one[int(np.argmax(rec["voxels"]))] = 1
+        t_one, t_all = torch.from_numpy(one).cuda(), torch.ones(len(rec), dtype=torch.uint8).cuda()
+        torch.cuda.synchronize()
+        r["select_one_ms"], _ = timed(lambda: labels.selectDevice(t_one.data_ptr(), dst), pairs)
+        assert dst.solidCount() == r["largest"]
+        r["select_all_ms"], _ = timed(lambda: labels.selectDevice(t_all.data_ptr(), dst), pairs)
+        assert dst.solidCount() == r["voxels"]
+        dst.close()
+        if not through_empty:
+            walls = []
+            for i in range(pairs + 1):
+                clone = medium.clone()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                _, removed = clone.removeSmallPieces(8, connectivity)
+                torch.cuda.synchronize()
+                if i:
+                    walls.append((time.perf_counter() - t0) * 1e3)
+                clone.close()
+            r["remove_small_8_wall_ms"], r["remove_small_8_pieces"] = stat(walls, 3), removed
+        labels.close()
+        return r, rec
+
+    res["terrain"], _ = case(terrain, 6, False)
+    cam = np.array(vrc.reference_camera_position(depth), np.float32) / np.float32(S) + np.float32(1.0)
+    d = rng.normal(size=(400, 3)).astype(np.float32) * np.float32(0.3) + np.array([0.0, 0.5, 0.8], np.float32)
+    d /= np.linalg.norm(d, axis=1, keepdims=True).astype(np.float32)
+    hits = scene.castRays(np.tile(cam, (400, 1)).astype(np.float32), d)
+    terrain.fillSpheresAtHits(hits, 12, False)
+    res["digs"] = {"rays": 400, "unit_hits": int(((hits["hit"] & 0xff) == 1).sum()), "radius": 12}
+    res["dug_terrain"], rec = case(terrain, 6, False)
+    res["dug_terrain_26"], _ = case(terrain, 26, False)
+    res["air"], _ = case(terrain, 6, True)
+
+    # for scale, same run, same volume
+    scale = {}
+    ids = torch.empty(S ** 3, dtype=torch.int32, device="cuda")
+    scale["fill_ids_ms"], _ = timed(lambda: ids.fill_(7), pairs)
+    del ids
+    scale["solid_count_ms"], _ = timed(terrain.solidCount, pairs)
+    region = vrc.VoxelVolume(depth)
+    whole = np.array([[0, 0, 0, S, S, S]], np.uint32)
+
+    def flood_from(seed_boxes=None, seed_voxel=None):
+        region.fillBoxes(whole, False)
+        if seed_boxes is not None:
+            region.fillBoxes(seed_boxes)
+        else:
+            region.setVoxels([seed_voxel])
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        st = region.flood(terrain, 6)
+        b.record()
+        b.synchronize()
+        assert st.converged == 1
+        return a.elapsed_time(b), st
+
+    bottom = np.array([[0, S // 2 + 1, 0, S, S // 2 + 2, S]], np.uint32)
+    floods = [flood_from(seed_boxes=bottom)[0] for _ in range(pairs + 1)][1:]
+    scale["flood_from_bottom_ms"] = stat(floods, 4)
+    flood_from(seed_voxel=rec[0]["first"])                                   # warm-up
+    largest = np.argsort(-rec["voxels"].astype(np.int64), kind="stable")[:16]
+    per_piece = []
+    for i in largest:
+        ms, st = flood_from(seed_voxel=rec[int(i)]["first"])
+        assert st.reached == int(rec[int(i)]["voxels"])
+        per_piece.append(ms)
+    scale["flood_per_piece"] = {"pieces_flooded": len(per_piece), "each_ms": stat(per_piece, 4), "sum_ms": round(sum(per_piece), 4),
+                                "pieces": len(rec),
+                                "all_pieces_ms_EXTRAPOLATED": round(statistics.mean(per_piece) * len(rec), 3),
+                                "note": "extrapolated: mean of the floods made x number of pieces; host round trips to find the seeds not included"}
+    label = res["dug_terrain"]["label_ms"]["median"]
+    scale["label_over_fill_ids"] = round(label / scale["fill_ids_ms"]["median"], 2)
+    scale["flood_per_piece_EXTRAPOLATED_over_label"] = round(scale["flood_per_piece"]["all_pieces_ms_EXTRAPOLATED"] / label, 2)
+    res["scale"] = scale
+    region.close()
+    terrain.close()
+    scene.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--depths", type=int, nargs="+", default=[8, 9, 10])
@@ -505,7 +636,10 @@ def main():
     ap.add_argument("--flood", action="store_true", help="time vrc_volume_flood (depth 9 unless --depths is given)")
     ap.add_argument("--voxelize", action="store_true", help="time vrc_volume_xor_mesh (depth 9 unless --depths is given)")
     ap.add_argument("--surface", action="store_true", help="time vrc_volume_surface_count / vrc_volume_extract_surface (depth 9 unless --depths is given)")
+    ap.add_argument("--components", action="store_true", help="time vrc_volume_label_components / vrc_labels_* (depth 9 unless --depths is given)")
     args = ap.parse_args()
+    if args.components and args.depths == [8, 9, 10]:
+        args.depths = [9]
     if args.surface and args.depths == [8, 9, 10]:
         args.depths = [9]
     if args.voxelize and args.depths == [8, 9, 10]:
@@ -520,10 +654,14 @@ def main():
     import cpuvoxelraycaster_amd as vrc
     if not torch.cuda.is_available():
         raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-    out = {"bench": "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
+    out = {"bench": "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
     for d in args.depths:
-        out["depths"][str(d)] = (bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
+        out["depths"][str(d)] = (bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
     print(json.dumps(out))
+    if args.components:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_components.json")
+        with open(path, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
 
 
 if __name__ == "__main__":
