@@ -16,6 +16,7 @@ VRC_COPY_REPLACE, VRC_COPY_OR, VRC_COPY_ANDNOT = 0, 1, 2
 VRC_CONNECT_FACES, VRC_CONNECT_ALL = 6, 26
 VRC_FLOOD_SOLID, VRC_FLOOD_EMPTY = 0, 1
 VRC_NO_COMPONENT = 0xffffffff
+VRC_DISTANCE_NONE = 0xffffffff
 VRC_MESH_FRAC_BITS = 6
 VRC_FACE_XN, VRC_FACE_XP, VRC_FACE_YN, VRC_FACE_YP, VRC_FACE_ZN, VRC_FACE_ZP = range(6)
 VRC_SURFACE_FACES, VRC_SURFACE_TRIANGLES = 0, 1
@@ -57,6 +58,10 @@ class FrameStats(C.Structure):
 
 class FloodStats(C.Structure):
     _fields_ = [("reached", C.c_uint64), ("sweeps", C.c_uint32), ("converged", C.c_uint32)]
+
+
+class DistanceStats(C.Structure):
+    _fields_ = [("features", C.c_uint64), ("max_d2", C.c_uint32), ("argmax", C.c_uint32 * 3), ("reserved", C.c_uint32)]
 
 
 # every symbol include/vrc.h declares: (restype, argtypes)
@@ -160,6 +165,14 @@ SYMBOLS = {
     "vrc_labels_components": (_int, [_vp, _u64, _u64, _vp, _int, _vp]),
     "vrc_labels_at": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
     "vrc_labels_select": (_int, [_vp, _vp, _vp, _int, _int, _vp]),
+    "vrc_volume_distance_field": (_int, [_vp, _int, _int, C.POINTER(_vp), C.POINTER(DistanceStats)]),
+    "vrc_distance_destroy": (_int, [_vp]),
+    "vrc_distance_depth": (_u32, [_vp]),
+    "vrc_distance_bytes": (_u64, [_vp]),
+    "vrc_distance_data": (_vp, [_vp]),
+    "vrc_distance_at": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
+    "vrc_distance_download": (_int, [_vp, _vp]),
+    "vrc_distance_select": (_int, [_vp, _u32, _u32, _vp, _int, _vp]),
     "vrc_volume_xor_mesh": (_int, [_vp, _u64, _vp, _int, _vp]),
     "vrc_volume_surface_count": (_int, [_vp, _int, _vp]),
     "vrc_volume_extract_surface": (_int, [_vp, _int, _int, _u64, _u64, _vp, _vp, _int, _vp]),

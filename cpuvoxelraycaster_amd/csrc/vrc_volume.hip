@@ -12,8 +12,10 @@
 // voxels, solid voxels per box) walk the same rows of words as the boxes do.  The flood fill by connectivity
 // (vrc_volume_flood) has its kernels in vrc_flood.hip, the solid voxelisation of triangle meshes (vrc_volume_xor_mesh)
 // in vrc_voxelize.hip, its inverse, the exposed faces as a mesh (vrc_volume_extract_surface), in vrc_surface.hip, the
-// labelling of connected components (vrc_volume_label_components, vrc_labels_*) in vrc_components.hip; the entry points,
-// their ordering and their scratch blocks are here.
+// labelling of connected components (vrc_volume_label_components, vrc_labels_*) in vrc_components.hip, the exact squared
+// Euclidean distance field and the selection by distance that grow / shrink / hollow are made of
+// (vrc_volume_distance_field, vrc_distance_*) in vrc_distance.hip; the entry points, their ordering and their scratch blocks
+// are here.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -22,6 +24,7 @@
 #include "../../include/vrc.h"
 #include "vrc_build_sweeps.h"
 #include "vrc_components.h"
+#include "vrc_distance.h"
 #include "vrc_flood.h"
 #include "vrc_surface.h"
 #include "vrc_voxelize.h"
@@ -1091,6 +1094,129 @@ extern "C" int vrc_labels_select(const vrc_labels* l, const uint8_t* keep, vrc_v
     }
     if (e == hipSuccess) e = finish(dst, mem, st, true);
     if (d_stage) (void)hipFree(d_stage);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+// ---- distance field ----------------------------------------------------------
+
+// A snapshot like vrc_labels: it owns its memory and is never written after vrc_volume_distance_field returns.
+struct vrc_distance {
+    int device = 0;
+    uint32_t depth = 0;
+    uint32_t* d_field = nullptr;          // 8^depth squared distances, [(x*S + y)*S + z]
+};
+
+extern "C" int vrc_volume_distance_field(vrc_volume* medium, int to, int outside, vrc_distance** out, vrc_distance_stats* stats)
+{
+    const char* what = "vrc_volume_distance_field";
+    if (!medium || !out) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (to != VRC_FLOOD_SOLID && to != VRC_FLOOD_EMPTY) return vrc::fail(VRC_ERR_INVALID, "%s: bad to %d", what, to);
+    if (medium->depth < 2 || medium->depth > 10) return vrc::fail(VRC_ERR_INVALID, "%s: depth %u not in [2,10]", what, medium->depth);
+    vrc_distance* d = new (std::nothrow) vrc_distance();
+    if (!d) return vrc::fail(VRC_ERR_OOM, "out of host memory");
+    d->device = medium->device; d->depth = medium->depth;
+    // the NULL stream, behind the last asynchronous edit of the medium, as commit / download are
+    uint32_t* d_scratch = nullptr;
+    hipError_t e = hipSetDevice(medium->device);
+    if (e == hipSuccess) e = wait_for_edits(medium);
+    if (e == hipSuccess) e = hipMalloc((void**)&d->d_field, (size_t)4u << (3u * d->depth));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_scratch, vrc::distance_scratch_bytes(d->depth, medium->cu_count));
+    if (e == hipSuccess) {
+        vrc::distance_run(medium->d_bricks, d->depth, to, outside, medium->cu_count, d->d_field, d_scratch, nullptr);
+        e = hipGetLastError();
+    }
+    unsigned long long host[2] = {0ull, 0ull};
+    if (e == hipSuccess) e = hipMemcpy(host, vrc::distance_stats_slots(d_scratch), sizeof host, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (d_scratch) (void)hipFree(d_scratch);
+    if (e != hipSuccess) {
+        (void)vrc_distance_destroy(d);
+        return vrc::fail_hip(e, what);
+    }
+    if (stats) {
+        stats->features = host[0];
+        stats->max_d2 = 0u; stats->argmax[0] = stats->argmax[1] = stats->argmax[2] = 0u; stats->reserved = 0u;
+        if (host[1]) {
+            const uint32_t index = ~(uint32_t)host[1], mask = (1u << d->depth) - 1u;
+            stats->max_d2 = (uint32_t)(host[1] >> 32);
+            stats->argmax[0] = index >> (2u * d->depth); stats->argmax[1] = (index >> d->depth) & mask; stats->argmax[2] = index & mask;
+        }
+    }
+    *out = d;
+    return VRC_OK;
+}
+
+extern "C" int vrc_distance_destroy(vrc_distance* d)
+{
+    if (!d) return VRC_OK;
+    (void)hipSetDevice(d->device);
+    (void)hipDeviceSynchronize();       // device-memory calls may still be reading it on a caller's stream
+    if (d->d_field) (void)hipFree(d->d_field);
+    delete d;
+    return VRC_OK;
+}
+
+extern "C" uint32_t vrc_distance_depth(const vrc_distance* d) { return d ? d->depth : 0; }
+extern "C" uint64_t vrc_distance_bytes(const vrc_distance* d) { return d ? (uint64_t)4u << (3u * d->depth) : 0; }
+extern "C" const uint32_t* vrc_distance_data(const vrc_distance* d) { return d ? d->d_field : nullptr; }
+
+extern "C" int vrc_distance_at(const vrc_distance* d, uint64_t n, const uint32_t* xyz, uint32_t* d2, int mem, void* stream)
+{
+    const char* what = "vrc_distance_at";
+    if (!d) return vrc::fail(VRC_ERR_INVALID, "%s: null distance field", what);
+    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
+    if (n == 0) return VRC_OK;
+    if (!xyz || !d2) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "%s: too many voxels for one launch", what);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(d->device);
+    const uint32_t* d_xyz = xyz;
+    uint32_t* d_d2 = d2;
+    uint32_t* d_stage = nullptr;          // the snapshot keeps no scratch: a host-memory call stages in a block of its own
+    if (mem == VRC_MEM_HOST) {
+        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, (size_t)n * 16u);
+        d_xyz = d_stage;
+        d_d2 = d_stage + (size_t)n * 3u;
+        if (e == hipSuccess) e = hipMemcpyAsync(d_stage, xyz, (size_t)n * 12u, hipMemcpyHostToDevice, st);
+    }
+    if (e == hipSuccess) {
+        vrc::distance_at_run(d->d_field, d->depth, n, d_xyz, d_d2, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipMemcpyAsync(d2, d_d2, (size_t)n * 4u, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipStreamSynchronize(st);
+    if (d_stage) (void)hipFree(d_stage);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+extern "C" int vrc_distance_download(const vrc_distance* d, uint32_t* d2_host)
+{
+    const char* what = "vrc_distance_download";
+    if (!d || !d2_host) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    hipError_t e = hipSetDevice(d->device);
+    if (e == hipSuccess) e = hipMemcpy(d2_host, d->d_field, (size_t)4u << (3u * d->depth), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+extern "C" int vrc_distance_select(const vrc_distance* d, uint32_t lo, uint32_t hi, vrc_volume* dst, int op, void* stream)
+{
+    const char* what = "vrc_distance_select";
+    if (!d || !dst) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (op != VRC_COPY_REPLACE && op != VRC_COPY_OR && op != VRC_COPY_ANDNOT) return vrc::fail(VRC_ERR_INVALID, "%s: bad op %d", what, op);
+    if (lo > hi) return vrc::fail(VRC_ERR_INVALID, "%s: lo %u above hi %u", what, lo, hi);
+    if (dst->depth != d->depth) return vrc::fail(VRC_ERR_INVALID, "%s: field of depth %u, volume of depth %u", what, d->depth, dst->depth);
+    if (dst->device != d->device) return vrc::fail(VRC_ERR_INVALID, "%s: field on device %d, volume on device %d", what, d->device, dst->device);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(d->device);
+    if (e == hipSuccess) e = order_behind_edits(dst, st);
+    if (e == hipSuccess) {
+        vrc::distance_select_run(d->d_field, d->depth, lo, hi, dst->d_bricks, op, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
     if (e != hipSuccess) return vrc::fail_hip(e, what);
     return VRC_OK;
 }

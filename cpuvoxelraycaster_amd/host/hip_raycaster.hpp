@@ -236,6 +236,48 @@ private:
     vrc_labels* l_ = nullptr;
 };
 
+// The squared Euclidean distance of every voxel to the feature set (include/vrc.h: vrc_volume_distance_field): a snapshot
+// on the device, S^3 uint32 in [(x*S + y)*S + z] order, that later edits of the volume do not change.  Movable, RAII.
+class HipVoxelDistance {
+public:
+    ~HipVoxelDistance() { vrc_distance_destroy(d_); }
+    HipVoxelDistance(HipVoxelDistance&& o) noexcept : d_(o.d_), stats_(o.stats_) { o.d_ = nullptr; }
+    HipVoxelDistance& operator=(HipVoxelDistance&& o) noexcept
+    {
+        if (this != &o) { vrc_distance_destroy(d_); d_ = o.d_; stats_ = o.stats_; o.d_ = nullptr; }
+        return *this;
+    }
+    HipVoxelDistance(const HipVoxelDistance&) = delete;
+    HipVoxelDistance& operator=(const HipVoxelDistance&) = delete;
+
+    const vrc_distance_stats& stats() const { return stats_; }
+    uint32_t depth() const { return vrc_distance_depth(d_); }
+    uint64_t bytes() const { return vrc_distance_bytes(d_); }
+    const uint32_t* data() const { return vrc_distance_data(d_); }     // DEVICE pointer
+    // the squared distance at each of n voxels (xyz: n x 3), VRC_DISTANCE_NONE outside the volume
+    std::vector<uint32_t> at(const uint32_t* xyz, uint64_t n) const
+    {
+        std::vector<uint32_t> d2((size_t)n);
+        check(vrc_distance_at(d_, n, xyz, d2.data(), VRC_MEM_HOST, nullptr), "vrc_distance_at");
+        return d2;
+    }
+    std::vector<uint32_t> download() const
+    {
+        std::vector<uint32_t> d2((size_t)1 << (3u * depth()));
+        check(vrc_distance_download(d_, d2.data()), "vrc_distance_download");
+        return d2;
+    }
+    // dst becomes (VRC_COPY_REPLACE) / gains (_OR) / loses (_ANDNOT) the voxels with lo <= D <= hi
+    inline void select(uint32_t lo, uint32_t hi, HipVoxelVolume& dst, int op = VRC_COPY_REPLACE) const;
+    vrc_distance* handle() const { return d_; }
+
+private:
+    friend class HipVoxelVolume;
+    HipVoxelDistance(vrc_distance* adopted, const vrc_distance_stats& stats) : d_(adopted), stats_(stats) {}
+    vrc_distance* d_ = nullptr;
+    vrc_distance_stats stats_{};
+};
+
 // What SVO::setCell + compileSVO are to the reference (svo.hpp:72, lsvo_utils.cpp:4), on the device and repeatable: the
 // occupancy of the S^3 volume stays resident, setCell() queues edits, commit() applies them and builds a NEW HipLSVO
 // (bit-identical to compileSVO of the voxel set).  A scene in use is never touched: keep the old HipLSVO until the frames
@@ -381,6 +423,33 @@ public:
         for (size_t i = 0; i < records.size(); ++i) removed += small[i] = records[i].voxels < min_voxels ? 1 : 0;
         if (removed) labels.select(small, *this, VRC_COPY_ANDNOT);
         return removed;
+    }
+    // The exact squared Euclidean distance of every voxel to the nearest solid voxel (to the nearest empty one with
+    // to_empty; with outside, everything beyond the faces is a feature as well).  Synchronous.
+    HipVoxelDistance distanceField(bool to_empty = false, bool outside = false)
+    {
+        flush();
+        vrc_distance* d = nullptr;
+        vrc_distance_stats stats{};
+        check(vrc_volume_distance_field(v_, to_empty ? VRC_FLOOD_EMPTY : VRC_FLOOD_SOLID, outside ? 1 : 0, &d, &stats), "vrc_volume_distance_field");
+        return HipVoxelDistance(d, stats);
+    }
+    // Grow / shrink by r voxels, with the rule of fillSphere (d^2 <= r^2); open_border: beyond the faces counts as empty.
+    void dilate(uint32_t r)
+    {
+        r = std::min(r, 65535u);
+        distanceField().select(0u, r * r, *this, VRC_COPY_OR);
+    }
+    void erode(uint32_t r, bool open_border = false)
+    {
+        r = std::min(r, 65535u);
+        distanceField(true, open_border).select(0u, r * r, *this, VRC_COPY_ANDNOT);
+    }
+    // Clears the solid voxels farther than t from the empty ones: a shell t voxels thick is left.
+    void hollow(uint32_t t)
+    {
+        t = std::min(t, 65535u);
+        distanceField(true).select(t * t + 1u, VRC_DISTANCE_NONE, *this, VRC_COPY_ANDNOT);
     }
     // Solid voxelisation by crossing parity (include/vrc.h: vrc_volume_xor_mesh): n x 9 int32 triangles in setCell
     // coordinates with VRC_MESH_FRAC_BITS fractional bits; every voxel whose centre lies under an odd number of them is
@@ -567,6 +636,12 @@ inline void HipVoxelLabels::select(const std::vector<uint8_t>& keep, HipVoxelVol
     if (keep.size() != count()) throw std::invalid_argument("HipVoxelLabels::select: keep must have one byte per component");
     dst.flush();
     check(vrc_labels_select(l_, keep.empty() ? nullptr : keep.data(), dst.handle(), op, VRC_MEM_HOST, nullptr), "vrc_labels_select");
+}
+
+inline void HipVoxelDistance::select(uint32_t lo, uint32_t hi, HipVoxelVolume& dst, int op) const
+{
+    dst.flush();
+    check(vrc_distance_select(d_, lo, hi, dst.handle(), op, nullptr), "vrc_distance_select");
 }
 
 // Camera values Camera::getRay reads (camera_controller.hpp:16-49); the Camera /

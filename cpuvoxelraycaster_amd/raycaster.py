@@ -294,6 +294,59 @@ class VoxelVolume:
         labels.close()
         return records, pieces
 
+    def distanceField(self, to_empty=False, outside=False):
+        """The exact squared Euclidean distance of every voxel to the nearest solid voxel (to the nearest empty one with
+        to_empty; with outside, everything beyond the volume's faces counts as a feature too) -- include/vrc.h:
+        vrc_volume_distance_field.  A VoxelDistance snapshot that later edits do not change.  Synchronous."""
+        handle, stats = C.c_void_p(), capi.DistanceStats()
+        check(capi.load().vrc_volume_distance_field(self._h, capi.VRC_FLOOD_EMPTY if to_empty else capi.VRC_FLOOD_SOLID, int(bool(outside)),
+                                                    C.byref(handle), C.byref(stats)))
+        return VoxelDistance(handle, stats, self.depth, self.device)
+
+    @staticmethod
+    def _radius(r, what):
+        r = int(r)
+        if r < 0:
+            raise ValueError(f"{what}: negative radius {r}")
+        return min(r, 65535)              # finite distances are below 2^22: every larger radius selects the same voxels
+
+    def dilate(self, r):
+        """Grows the solid set by r voxels in place: every voxel within d^2 <= r^2 of a solid one becomes solid (a
+        fillSpheres of radius r at every solid voxel)."""
+        r = self._radius(r, "dilate")
+        field = self.distanceField()
+        field.select(0, r * r, self, capi.VRC_COPY_OR)
+        field.close()
+        return self
+
+    def erode(self, r, open_border=False):
+        """Shrinks the solid set by r voxels in place: every voxel within d^2 <= r^2 of an empty one is cleared.  With
+        open_border everything beyond the volume's faces counts as empty, so the erosion eats from the faces as well."""
+        r = self._radius(r, "erode")
+        field = self.distanceField(to_empty=True, outside=open_border)
+        field.select(0, r * r, self, capi.VRC_COPY_ANDNOT)
+        field.close()
+        return self
+
+    def openShape(self, r):
+        """erode(r) then dilate(r): removes specks and sheets thinner than the ball, keeps the rest's outline"""
+        r = self._radius(r, "openShape")
+        return self.erode(r).dilate(r)
+
+    def closeShape(self, r):
+        """dilate(r) then erode(r) with the faces as walls: fills holes and gaps narrower than the ball"""
+        r = self._radius(r, "closeShape")
+        return self.dilate(r).erode(r, open_border=False)
+
+    def hollow(self, t):
+        """Clears every solid voxel farther than t from the empty voxels (D_empty > t^2), which leaves a shell t voxels
+        thick; the faces of the volume are walls.  hollow(0) empties the volume."""
+        t = self._radius(t, "hollow")
+        field = self.distanceField(to_empty=True)
+        field.select(t * t + 1, capi.VRC_DISTANCE_NONE, self, capi.VRC_COPY_ANDNOT)
+        field.close()
+        return self
+
     def xorMesh(self, tris_fixed, device=False, stream=None):
         """Solid voxelisation by crossing parity (include/vrc.h: vrc_volume_xor_mesh): (n, 9) int32 triangles in setCell
         coordinates with 6 fractional bits (64 units per voxel, voxel centres at 64 c + 32); every voxel whose centre lies
@@ -495,6 +548,58 @@ class VoxelLabels:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             capi.load().vrc_labels_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VoxelDistance:
+    """The squared Euclidean distance of every voxel to the feature set, resident on the device as S^3 uint32 in
+    [(x*S + y)*S + z] order (include/vrc.h: vrc_distance_*): a snapshot made by VoxelVolume.distanceField.  `stats` is a
+    capi.DistanceStats (features, max_d2, argmax)."""
+
+    def __init__(self, handle, stats, depth, device):
+        self._h, self.stats, self.depth, self.device = handle, stats, depth, device
+
+    def bytes(self):
+        return int(capi.load().vrc_distance_bytes(self._h))
+
+    def data_ptr(self):
+        """the device address of the field: an (S, S, S) uint32 tensor for whoever wraps it"""
+        return int(capi.load().vrc_distance_data(self._h) or 0)
+
+    def at(self, xyz):
+        """uint32 squared distance per (n, 3) voxel coordinate, capi.VRC_DISTANCE_NONE outside the volume"""
+        xyz = np.ascontiguousarray(xyz, np.uint32).reshape(-1, 3)
+        out = np.zeros(xyz.shape[0], np.uint32)
+        check(capi.load().vrc_distance_at(self._h, xyz.shape[0], ptr(xyz), ptr(out), capi.VRC_MEM_HOST, None))
+        return out
+
+    def atDevice(self, n, xyz_ptr, d2_ptr, stream=None):
+        check(capi.load().vrc_distance_at(self._h, n, ptr(xyz_ptr), ptr(d2_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def download(self):
+        """the whole field as an (S, S, S) uint32 array"""
+        S = 1 << self.depth
+        out = np.empty((S, S, S), np.uint32)
+        check(capi.load().vrc_distance_download(self._h, ptr(out)))
+        return out
+
+    def select(self, lo, hi, dst=None, op=capi.VRC_COPY_REPLACE, stream=None):
+        """dst (a new volume with None) becomes / gains / loses the voxels with lo <= D <= hi; asynchronous on `stream`,
+        ordered as an edit of dst.  Returns dst."""
+        if dst is None:
+            dst = VoxelVolume(self.depth, self.device)
+        check(capi.load().vrc_distance_select(self._h, int(lo), int(hi), dst._h, int(op), ptr(stream)))
+        return dst
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            capi.load().vrc_distance_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -396,6 +396,60 @@ int vrc_labels_components(const vrc_labels *l, uint64_t first, uint64_t capacity
 int vrc_labels_at(const vrc_labels *l, uint64_t n, const uint32_t *xyz, uint32_t *ids, int mem, void *stream);
 int vrc_labels_select(const vrc_labels *l, const uint8_t *keep, vrc_volume *dst, int op, int mem, void *stream);
 
+/* The exact squared Euclidean distance field, on the device: how far every voxel is from the surface, and with it grow /
+ * shrink by r voxels (dilate, erode, open, close), hollowing a solid down to a shell, clearance queries, and a field a
+ * PyTorch caller reads in place.  The feature set F is the solid voxels of `medium` (to = VRC_FLOOD_SOLID) or its empty
+ * voxels (to = VRC_FLOOD_EMPTY).  With outside != 0 every integer lattice point beyond the volume's faces belongs to F as
+ * well -- the "closed" reading of the surface calls: an erosion then also eats from the volume's own faces; with
+ * outside == 0 the faces are walls and nothing lies beyond them.
+ *
+ * The field.  For every voxel p of the volume D(p) = min over q in F of (px-qx)^2 + (py-qy)^2 + (pz-qz)^2, in integers;
+ * D(p) = VRC_DISTANCE_NONE when F is empty (outside == 0 and no feature voxel in the volume).  Finite values are at most
+ * 3 (S-1)^2 < 2^22.  With outside != 0, D(p) = min(D_inside(p), min over the three axes a of (p_a + 1)^2 and (S - p_a)^2).
+ * The result is unique: it does not depend on scheduling, and two calls give identical bytes.  It is stored densely as
+ * [(x*S + y)*S + z], the layout of vrc_volume_download, so vrc_distance_data is directly an (S, S, S) uint32 tensor and
+ * vrc_distance_download is one copy.
+ *
+ * stats (may be NULL): features = |F inside the volume|; max_d2 = the largest finite D, 0 when there is none; argmax = the
+ * voxel that holds it with the smallest dense index, 0,0,0 when there is none; reserved = 0.
+ *
+ * vrc_volume_distance_field is synchronous, on the NULL stream, ordered behind the medium's last asynchronous edit, and
+ * only reads the medium.  Depths 2..10.  The result is a SNAPSHOT: it owns its memory (4 bytes per voxel: 512 MiB at 512^3,
+ * 4 GiB at 1024^3), is never written after creation, later edits of the medium do not change it, and destroying the medium
+ * leaves it valid.  All scratch is freed before return: 16 bytes of stats up to 128^3, where the working stacks are in
+ * LDS; from 256^3 on also min(S^2 / 64, 8 x compute units) groups x 64 lanes x S x 4 bytes of stacks for the lines in
+ * flight -- 64 MiB at 256^3, 256 MiB at 512^3 and 512 MiB at 1024^3 on 256 compute units -- never proportional to the volume.
+ *
+ * The device runs the separable transform in place on the field (csrc/vrc_distance.hip): the z pass from the occupancy
+ * bits, then a min-plus pass along y and one along x by the lower-envelope stack, exact in integers (crossovers compared
+ * by cross-multiplication, no float), 2 S steps per line whatever the input; one kernel per pass on one stream, no
+ * workgroup waiting for another, 64-bit vector atomics for the stats only.  No time has been measured yet
+ * (tools/bench_edit.py --distance writes profiles/edit/bench_distance.json).
+ *
+ * vrc_distance_at: d2[i] = D at voxel xyz[3i..3i+2], VRC_DISTANCE_NONE for a coordinate outside the volume; mem / stream as
+ * in vrc_labels_at (VRC_MEM_HOST is staged and synchronous, VRC_MEM_DEVICE works in place, asynchronous on `stream`).
+ * vrc_distance_download: all S^3 values to host memory, synchronous.
+ * vrc_distance_select: with K = { p : lo <= D(p) <= hi }, VRC_DISTANCE_NONE compared as the plain value 0xffffffff, dst
+ * becomes K (VRC_COPY_REPLACE), dst | K (VRC_COPY_OR) or dst & ~K (VRC_COPY_ANDNOT).  dst is a volume of the field's depth
+ * on the field's device and may be the medium itself.  Whole occupancy words are written once with plain stores, one
+ * thread per word.  Asynchronous on `stream`: ordered behind dst's last asynchronous edit and recorded as dst's last edit,
+ * as vrc_labels_select with device memory is.  dilate(r) = select(D_solid, 0, r^2, OR), erode(r) = select(D_empty, 0, r^2,
+ * ANDNOT), hollow(t) = select(D_empty, t^2 + 1, 0xffffffff, ANDNOT): the radius rule of vrc_volume_fill_spheres.
+ * NULL handles, a `to` other than 0 / 1, an unknown op, lo > hi, a depth or device mismatch and a bad `mem` are
+ * VRC_ERR_INVALID, refused before any device call; a NULL handle gives vrc_distance_depth = vrc_distance_bytes = 0 and
+ * vrc_distance_data = NULL. */
+#define VRC_DISTANCE_NONE 0xffffffffu
+typedef struct vrc_distance vrc_distance;    /* a snapshot: the squared distance of every voxel, resident on the volume's device */
+typedef struct vrc_distance_stats { uint64_t features; uint32_t max_d2; uint32_t argmax[3]; uint32_t reserved; } vrc_distance_stats;
+int vrc_volume_distance_field(vrc_volume *medium, int to, int outside, vrc_distance **out, vrc_distance_stats *stats);
+int vrc_distance_destroy(vrc_distance *d);
+uint32_t vrc_distance_depth(const vrc_distance *d);
+uint64_t vrc_distance_bytes(const vrc_distance *d);            /* 4 * 8^depth; pure host bookkeeping */
+const uint32_t *vrc_distance_data(const vrc_distance *d);      /* DEVICE pointer, S^3 uint32, [(x*S + y)*S + z] */
+int vrc_distance_at(const vrc_distance *d, uint64_t n, const uint32_t *xyz, uint32_t *d2, int mem, void *stream);
+int vrc_distance_download(const vrc_distance *d, uint32_t *d2_host);
+int vrc_distance_select(const vrc_distance *d, uint32_t lo, uint32_t hi, vrc_volume *dst, int op, void *stream);
+
 /* ---- dense grid: Grid3D<X,Y,Z> (grid_3d.hpp:10-138) ------------------- */
 
 /* cells[(x*Y + y)*Z + z] = Cell::Type (0 = Empty). */

@@ -66,6 +66,17 @@ device time by events on the NULL stream around the synchronous calls, one warm-
                        one full vrc_volume_flood from the bottom slab, and flood_per_piece = what the labelling replaces:
                        one vrc_volume_flood from each record's `first` for at most the 16 largest pieces, and that mean
                        times the number of pieces (EXTRAPOLATED, labelled so)
+With --distance (printed and written to profiles/edit/bench_distance.json), the exact distance field at 512^3, device time
+by events on the NULL stream around the calls, one warm-up, `--pairs` repetitions, median and range, for to = SOLID and EMPTY:
+  terrain / corner_voxel / empty
+                       the FastNoise terrain, a volume with one solid voxel in a corner (the long-parabola worst case: for
+                       to = SOLID one parabola spans every line) and an empty volume (to = SOLID: no feature at all,
+                       to = EMPTY: every voxel one).  Per case: field (the whole vrc_volume_distance_field call), select
+                       (vrc_distance_select of [0, 16] into a fresh volume), dilate_4 (VoxelVolume.dilate(4) on a clone, end
+                       to end, wall time), the stats, and field_over_copy
+  copy_field           the yardstick, in the same run: a device-to-device copy of 4 S^3 bytes (one read and one write of the
+                       field; the transform reads and writes it twice after writing it once)
+  worst_over_terrain   field time of corner_voxel over field time of terrain, per `to`: the per-line bound in practice
 No threshold is applied; the numbers are reported."""
 import argparse
 import json
@@ -628,6 +639,71 @@ def bench_components(vrc, depth, pairs):
     return res
 
 
+def bench_distance(vrc, depth, pairs):
+    import torch
+    S = 1 << depth
+    res = {"size": S, "pairs": pairs, "field_bytes": 4 * S ** 3}
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    terrain = vrc.VoxelVolume.fromScene(scene)
+    corner = vrc.VoxelVolume(depth)
+    corner.setVoxels([[0, 0, 0]])
+    empty = vrc.VoxelVolume(depth)
+
+    def timed(fn, repeats):
+        """device ms by events around fn, one warm-up; returns (stat, the last result)"""
+        out, last = [], None
+        for i in range(repeats + 1):
+            if last is not None and hasattr(last, "close"):
+                last.close()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            last = fn()
+            b.record()
+            b.synchronize()
+            if i:
+                out.append(a.elapsed_time(b))
+        return stat(out, 4), last
+
+    src = torch.empty(S ** 3, dtype=torch.int32, device="cuda")
+    dst_t = torch.empty(S ** 3, dtype=torch.int32, device="cuda")
+    res["copy_field_ms"], _ = timed(lambda: dst_t.copy_(src), pairs)
+    del src, dst_t
+    torch.cuda.empty_cache()
+    copy = res["copy_field_ms"]["median"]
+
+    for name, medium in (("terrain", terrain), ("corner_voxel", corner), ("empty", empty)):
+        res[name] = {}
+        for to_empty in (False, True):
+            r = {}
+            r["field_ms"], field = timed(lambda: medium.distanceField(to_empty), pairs)
+            r["features"], r["max_d2"], r["argmax"] = int(field.stats.features), int(field.stats.max_d2), [int(v) for v in field.stats.argmax]
+            dst = vrc.VoxelVolume(depth)
+            r["select_ms"], _ = timed(lambda: field.select(0, 16, dst) and None, pairs)      # select returns dst: not timed()'s to close
+            r["selected"] = dst.solidCount()
+            dst.close()
+            field.close()
+            walls = []
+            for i in range(pairs + 1):
+                clone = medium.clone()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                clone.dilate(4)
+                torch.cuda.synchronize()
+                if i:
+                    walls.append((time.perf_counter() - t0) * 1e3)
+                grown = clone.solidCount()
+                clone.close()
+            r["dilate_4_wall_ms"], r["dilate_4_solid"] = stat(walls, 3), grown
+            r["field_over_copy"] = round(r["field_ms"]["median"] / copy, 2)
+            res[name]["to_empty" if to_empty else "to_solid"] = r
+    res["worst_over_terrain"] = {k: round(res["corner_voxel"][k]["field_ms"]["median"] / res["terrain"][k]["field_ms"]["median"], 2)
+                                 for k in ("to_solid", "to_empty")}
+    for v in (terrain, corner, empty):
+        v.close()
+    scene.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--depths", type=int, nargs="+", default=[8, 9, 10])
@@ -637,7 +713,10 @@ def main():
     ap.add_argument("--voxelize", action="store_true", help="time vrc_volume_xor_mesh (depth 9 unless --depths is given)")
     ap.add_argument("--surface", action="store_true", help="time vrc_volume_surface_count / vrc_volume_extract_surface (depth 9 unless --depths is given)")
     ap.add_argument("--components", action="store_true", help="time vrc_volume_label_components / vrc_labels_* (depth 9 unless --depths is given)")
+    ap.add_argument("--distance", action="store_true", help="time vrc_volume_distance_field / vrc_distance_select / dilate (depth 9 unless --depths is given)")
     args = ap.parse_args()
+    if args.distance and args.depths == [8, 9, 10]:
+        args.depths = [9]
     if args.components and args.depths == [8, 9, 10]:
         args.depths = [9]
     if args.surface and args.depths == [8, 9, 10]:
@@ -654,10 +733,14 @@ def main():
     import cpuvoxelraycaster_amd as vrc
     if not torch.cuda.is_available():
         raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-    out = {"bench": "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
+    out = {"bench": "edit_distance" if args.distance else "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
     for d in args.depths:
-        out["depths"][str(d)] = (bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
+        out["depths"][str(d)] = (bench_distance if args.distance else bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
     print(json.dumps(out))
+    if args.distance:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_distance.json")
+        with open(path, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
     if args.components:
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_components.json")
         with open(path, "w") as f:
