@@ -18,6 +18,7 @@ VRC_FLOOD_SOLID, VRC_FLOOD_EMPTY = 0, 1
 VRC_NO_COMPONENT = 0xffffffff
 VRC_DISTANCE_NONE = 0xffffffff
 VRC_MESH_FRAC_BITS = 6
+VRC_AFFINE_FRAC_BITS = 16
 VRC_FACE_XN, VRC_FACE_XP, VRC_FACE_YN, VRC_FACE_YP, VRC_FACE_ZN, VRC_FACE_ZP = range(6)
 VRC_SURFACE_FACES, VRC_SURFACE_TRIANGLES = 0, 1
 
@@ -62,6 +63,11 @@ class FloodStats(C.Structure):
 
 class DistanceStats(C.Structure):
     _fields_ = [("features", C.c_uint64), ("max_d2", C.c_uint32), ("argmax", C.c_uint32 * 3), ("reserved", C.c_uint32)]
+
+
+class Affine(C.Structure):
+    """vrc_affine (include/vrc.h): the inverse map of vrc_volume_stamp_affine, m row-major with 16 fractional bits"""
+    _fields_ = [("m", C.c_int32 * 9), ("reserved", C.c_int32), ("t", C.c_int64 * 3)]
 
 
 # every symbol include/vrc.h declares: (restype, argtypes)
@@ -153,6 +159,8 @@ SYMBOLS = {
     "vrc_volume_fill_spheres": (_int, [_vp, _u64, _vp, _int, _int, _vp]),
     "vrc_volume_fill_spheres_at_hits": (_int, [_vp, _u64, _vp, _i32, _int, _int, _vp]),
     "vrc_volume_copy_region": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp]),
+    "vrc_volume_stamp_affine": (_int, [_vp, _vp, C.POINTER(Affine), _vp, _vp, _int, _vp]),
+    "vrc_affine_place": (_int, [_vp, _f32, _vp, _vp, _u32, _u32, C.POINTER(Affine), _vp, _vp]),
     "vrc_volume_clone": (_int, [_vp, C.POINTER(_vp)]),
     "vrc_volume_get_voxels": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
     "vrc_volume_count_boxes": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),

@@ -370,6 +370,59 @@ extern "C" int vrc_hit_to_voxel(uint32_t depth, const vrc_hit* hit, uint32_t vox
     return VRC_OK;
 }
 
+// Host arithmetic only, in doubles.  rot is vrc_make_rotation's layout (columns), so R[b][a] -- the entry of the INVERSE
+// rotation's row a, column b -- is rot[3a + b].
+extern "C" int vrc_affine_place(const float rot[9], float scale, const float src_pivot[3], const float dst_pivot[3], uint32_t src_depth,
+                                uint32_t dst_depth, vrc_affine* map, uint32_t dst_lo[3], uint32_t dst_hi[3])
+{
+    const char* what = "vrc_affine_place";
+    if (!rot || !src_pivot || !dst_pivot || !map || !dst_lo || !dst_hi) return fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (src_depth < 2 || src_depth > 10 || dst_depth < 2 || dst_depth > 10)
+        return fail(VRC_ERR_INVALID, "%s: depths %u and %u not in [2,10]", what, src_depth, dst_depth);
+    bool finite = std::isfinite(scale);
+    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(rot[i]);
+    for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(src_pivot[a]) && std::isfinite(dst_pivot[a]);
+    if (!finite) return fail(VRC_ERR_INVALID, "%s: NaN or infinite input", what);
+    if (!(scale > 0.0f)) return fail(VRC_ERR_INVALID, "%s: scale %g is not positive", what, (double)scale);
+    if (scale < 0.0625f) return fail(VRC_ERR_INVALID, "%s: scale %g below 1/16, the smallest scale the map's 2^20 limit admits for a rotation", what, (double)scale);
+    vrc_affine out;
+    out.reserved = 0;
+    for (int a = 0; a < 3; ++a) {
+        double sum[3];
+        for (int b = 0; b < 3; ++b) {
+            const double m = std::nearbyint(65536.0 * (double)rot[3 * a + b] / (double)scale);
+            if (!(std::fabs(m) <= 1048576.0)) return fail(VRC_ERR_INVALID, "%s: m[%d] = %g beyond +-2^20", what, 3 * a + b, m);
+            out.m[3 * a + b] = (int32_t)m;
+            sum[b] = m * 2.0 * (double)dst_pivot[b];
+        }
+        const double t = std::nearbyint(131072.0 * (double)src_pivot[a] - ((sum[0] + sum[1]) + sum[2]));
+        if (!(std::fabs(t) <= 1099511627776.0)) return fail(VRC_ERR_INVALID, "%s: t[%d] = %g beyond +-2^40", what, a, t);
+        out.t[a] = (int64_t)t;
+    }
+    // the bounding box of the forward image of the source cube [0, S]^3, two voxels wider on every side, clipped to dst
+    const double Ss = (double)(1u << src_depth), Sd = (double)(1u << dst_depth);
+    uint32_t lo[3], hi[3];
+    bool empty = false;
+    for (int r = 0; r < 3; ++r) {
+        double least = 0.0, most = 0.0;
+        for (int corner = 0; corner < 8; ++corner) {
+            double x = (double)dst_pivot[r];
+            for (int c = 0; c < 3; ++c)
+                x += (double)scale * (double)rot[3 * c + r] * (((corner >> c) & 1 ? Ss : 0.0) - (double)src_pivot[c]);
+            if (corner == 0 || x < least) least = x;
+            if (corner == 0 || x > most) most = x;
+        }
+        double l = std::floor(least) - 2.0, h = std::ceil(most) + 2.0;
+        if (l < 0.0) l = 0.0;
+        if (h > Sd) h = Sd;
+        if (!(l < h)) { empty = true; l = h = 0.0; }
+        lo[r] = (uint32_t)l; hi[r] = (uint32_t)h;
+    }
+    for (int a = 0; a < 3; ++a) { dst_lo[a] = empty ? 0u : lo[a]; dst_hi[a] = empty ? 0u : hi[a]; }
+    *map = out;
+    return VRC_OK;
+}
+
 // The kernels replace some IEEE divisions / square roots by short sequences that are proven equal on the ranges they
 // are used on; this runs that proof on the device: every float bit pattern of those ranges (~4.3 x 10^9 evaluations, a
 // fraction of a second).  mismatches[0..3]: reciprocal, square root, 1 / sqrt composition, get_rand -- all must be 0.

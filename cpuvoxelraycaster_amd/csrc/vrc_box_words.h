@@ -1,0 +1,82 @@
+// vrc_box_words.h -- a clipped voxel box as a list of the 32-bit occupancy words its brick rows touch: the work layout of
+// every kernel that edits or reads a box of a brick-byte field (vrc_volume.hip: boxes, spheres, region copy, box counts;
+// vrc_stamp.hip: the affine stamp).  A word holds four bricks along z, 2 x 2 x 8 voxels.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace {
+
+// the voxels of brick coordinate c (one axis) that lie in [lo, hi): bit 0 = voxel 2c, bit 1 = voxel 2c + 1
+__device__ __forceinline__ uint32_t axis_pair(uint32_t c, uint32_t lo, uint32_t hi)
+{
+    const uint32_t v = 2u * c;
+    return ((v >= lo && v < hi) ? 1u : 0u) | ((v + 1u >= lo && v + 1u < hi) ? 2u : 0u);
+}
+
+// The brick rows a clipped, non-empty voxel box [lo, hi) touches, as a list of work items.  A row = the bricks
+// (cx, cy, cz0..cz1), contiguous bytes; item = (row, k-th 32-bit word of the row).
+struct BoxWords {
+    uint32_t lo[3], hi[3];
+    uint32_t bx0, by0, cz0, cz1, nby, wpr;
+    uint64_t items;
+};
+
+// The number of work items of a clipped, non-empty box: for the host to size a launch by, and for box_words below, so that
+// the two agree by construction.
+__host__ __device__ __forceinline__ uint64_t box_word_items(const uint32_t lo[3], const uint32_t hi[3])
+{
+    const uint32_t nbx = ((hi[0] - 1u) >> 1) - (lo[0] >> 1) + 1u, nby = ((hi[1] - 1u) >> 1) - (lo[1] >> 1) + 1u;
+    const uint32_t wpr = (((((hi[2] - 1u) >> 1) - (lo[2] >> 1)) + 3u) >> 2) + 1u;
+    return (uint64_t)nbx * nby * wpr;
+}
+
+__device__ __forceinline__ BoxWords box_words(const uint32_t lo[3], const uint32_t hi[3])
+{
+    BoxWords b;
+    for (int a = 0; a < 3; ++a) { b.lo[a] = lo[a]; b.hi[a] = hi[a]; }
+    b.bx0 = lo[0] >> 1; b.by0 = lo[1] >> 1; b.cz0 = lo[2] >> 1;
+    b.nby = ((hi[1] - 1u) >> 1) - b.by0 + 1u;
+    b.cz1 = (hi[2] - 1u) >> 1;
+    b.wpr = ((b.cz1 - b.cz0 + 3u) >> 2) + 1u;          // upper bound of the words one row touches, whatever its alignment
+    b.items = box_word_items(lo, hi);
+    return b;
+}
+
+// One item of a box: the word index `w`, the row's brick coordinates and the byte indices of brick (cx, cy, 0) and of
+// the row's first / last brick.  false: the row has fewer words than wpr and this item is beyond them.
+struct RowWord {
+    uint32_t cx, cy;
+    uint64_t base, first, last, w;
+};
+
+__device__ __forceinline__ bool row_word(const BoxWords& b, uint32_t n, uint64_t it, RowWord& r)
+{
+    const uint32_t k = (uint32_t)(it % b.wpr);
+    const uint32_t row = (uint32_t)(it / b.wpr);
+    r.cx = b.bx0 + row / b.nby; r.cy = b.by0 + row % b.nby;
+    r.base = ((uint64_t)r.cx * n + r.cy) * n;
+    r.first = r.base + b.cz0; r.last = r.base + b.cz1;
+    r.w = (r.first >> 2) + k;
+    return r.w <= (r.last >> 2);
+}
+
+// the voxels of word r.w that lie inside the box, as a mask of the word's bits
+__device__ __forceinline__ uint32_t box_mask(const BoxWords& b, const RowWord& r)
+{
+    const uint32_t xy = axis_pair(r.cx, b.lo[0], b.hi[0]) | (axis_pair(r.cy, b.lo[1], b.hi[1]) << 2);
+    // xy: bit 0 / 1 = x voxel 0 / 1 inside, bit 2 / 3 = y voxel 0 / 1 inside -> the 4 (y, x) bits of one z layer
+    const uint32_t layer = ((xy & 1u) ? 0x5u : 0u) | ((xy & 2u) ? 0xAu : 0u);
+    const uint32_t plane = (layer & ((xy & 4u) ? 0x3u : 0u)) | (layer & ((xy & 8u) ? 0xCu : 0u));
+    uint32_t mask = 0u;
+    for (uint32_t j = 0; j < 4u; ++j) {
+        const uint64_t byte = 4u * r.w + j;
+        if (byte < r.first || byte > r.last) continue;
+        const uint32_t zp = axis_pair((uint32_t)(byte - r.base), b.lo[2], b.hi[2]);
+        const uint32_t m8 = ((zp & 1u) ? plane : 0u) | ((zp & 2u) ? plane << 4 : 0u);
+        mask |= m8 << (8u * j);
+    }
+    return mask;
+}
+
+}  // namespace

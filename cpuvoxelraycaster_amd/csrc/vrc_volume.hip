@@ -14,18 +14,21 @@
 // in vrc_voxelize.hip, its inverse, the exposed faces as a mesh (vrc_volume_extract_surface), in vrc_surface.hip, the
 // labelling of connected components (vrc_volume_label_components, vrc_labels_*) in vrc_components.hip, the exact squared
 // Euclidean distance field and the selection by distance that grow / shrink / hollow are made of
-// (vrc_volume_distance_field, vrc_distance_*) in vrc_distance.hip; the entry points, their ordering and their scratch blocks
-// are here.
+// (vrc_volume_distance_field, vrc_distance_*) in vrc_distance.hip, the stamp through an affine map -- rotated, mirrored and
+// scaled pastes (vrc_volume_stamp_affine) -- in vrc_stamp.hip, with the box-of-words layout it shares with the kernels here
+// in vrc_box_words.h; the entry points, their ordering and their scratch blocks are here.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <new>
 
 #include "../../include/vrc.h"
+#include "vrc_box_words.h"
 #include "vrc_build_sweeps.h"
 #include "vrc_components.h"
 #include "vrc_distance.h"
 #include "vrc_flood.h"
+#include "vrc_stamp.h"
 #include "vrc_surface.h"
 #include "vrc_voxelize.h"
 
@@ -73,70 +76,6 @@ __global__ void k_set_voxels(uint32_t* __restrict__ words, uint32_t S, uint64_t 
     const uint32_t bit = 1u << (((z & 1u) * 4u + (y & 1u) * 2u + (x & 1u)) + 8u * (uint32_t)(brick & 3u));
     if (solid) atomicOr(&words[brick >> 2], bit);
     else atomicAnd(&words[brick >> 2], ~bit);
-}
-
-// the voxels of brick coordinate c (one axis) that lie in [lo, hi): bit 0 = voxel 2c, bit 1 = voxel 2c + 1
-__device__ __forceinline__ uint32_t axis_pair(uint32_t c, uint32_t lo, uint32_t hi)
-{
-    const uint32_t v = 2u * c;
-    return ((v >= lo && v < hi) ? 1u : 0u) | ((v + 1u >= lo && v + 1u < hi) ? 2u : 0u);
-}
-
-// The brick rows a clipped, non-empty voxel box [lo, hi) touches, as a list of work items.  A row = the bricks
-// (cx, cy, cz0..cz1), contiguous bytes; item = (row, k-th 32-bit word of the row).
-struct BoxWords {
-    uint32_t lo[3], hi[3];
-    uint32_t bx0, by0, cz0, cz1, nby, wpr;
-    uint64_t items;
-};
-
-__device__ __forceinline__ BoxWords box_words(const uint32_t lo[3], const uint32_t hi[3])
-{
-    BoxWords b;
-    for (int a = 0; a < 3; ++a) { b.lo[a] = lo[a]; b.hi[a] = hi[a]; }
-    b.bx0 = lo[0] >> 1; b.by0 = lo[1] >> 1; b.cz0 = lo[2] >> 1;
-    const uint32_t nbx = ((hi[0] - 1u) >> 1) - b.bx0 + 1u;
-    b.nby = ((hi[1] - 1u) >> 1) - b.by0 + 1u;
-    b.cz1 = (hi[2] - 1u) >> 1;
-    b.wpr = ((b.cz1 - b.cz0 + 3u) >> 2) + 1u;          // upper bound of the words one row touches, whatever its alignment
-    b.items = (uint64_t)nbx * b.nby * b.wpr;
-    return b;
-}
-
-// One item of a box: the word index `w`, the row's brick coordinates and the byte indices of brick (cx, cy, 0) and of
-// the row's first / last brick.  false: the row has fewer words than wpr and this item is beyond them.
-struct RowWord {
-    uint32_t cx, cy;
-    uint64_t base, first, last, w;
-};
-
-__device__ __forceinline__ bool row_word(const BoxWords& b, uint32_t n, uint64_t it, RowWord& r)
-{
-    const uint32_t k = (uint32_t)(it % b.wpr);
-    const uint32_t row = (uint32_t)(it / b.wpr);
-    r.cx = b.bx0 + row / b.nby; r.cy = b.by0 + row % b.nby;
-    r.base = ((uint64_t)r.cx * n + r.cy) * n;
-    r.first = r.base + b.cz0; r.last = r.base + b.cz1;
-    r.w = (r.first >> 2) + k;
-    return r.w <= (r.last >> 2);
-}
-
-// the voxels of word r.w that lie inside the box, as a mask of the word's bits
-__device__ __forceinline__ uint32_t box_mask(const BoxWords& b, const RowWord& r)
-{
-    const uint32_t xy = axis_pair(r.cx, b.lo[0], b.hi[0]) | (axis_pair(r.cy, b.lo[1], b.hi[1]) << 2);
-    // xy: bit 0 / 1 = x voxel 0 / 1 inside, bit 2 / 3 = y voxel 0 / 1 inside -> the 4 (y, x) bits of one z layer
-    const uint32_t layer = ((xy & 1u) ? 0x5u : 0u) | ((xy & 2u) ? 0xAu : 0u);
-    const uint32_t plane = (layer & ((xy & 4u) ? 0x3u : 0u)) | (layer & ((xy & 8u) ? 0xCu : 0u));
-    uint32_t mask = 0u;
-    for (uint32_t j = 0; j < 4u; ++j) {
-        const uint64_t byte = 4u * r.w + j;
-        if (byte < r.first || byte > r.last) continue;
-        const uint32_t zp = axis_pair((uint32_t)(byte - r.base), b.lo[2], b.hi[2]);
-        const uint32_t m8 = ((zp & 1u) ? plane : 0u) | ((zp & 2u) ? plane << 4 : 0u);
-        mask |= m8 << (8u * j);
-    }
-    return mask;
 }
 
 // lo_hi[0..5] clipped to the volume; false = empty, inverted or wholly outside
@@ -712,6 +651,38 @@ extern "C" int vrc_volume_copy_region(vrc_volume* dst, vrc_volume* src, const ui
     if (groups > 16384u) groups = 16384u;
     hipLaunchKernelGGL(k_copy_region, dim3((uint32_t)groups), dim3(256), 0, st, dst->d_bricks, (uint32_t)Sd, (const uint8_t*)src->d_bricks, (uint32_t)Ss,
                        lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], off[0], off[1], off[2], op);
+    if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
+    if ((e = finish(dst, VRC_MEM_DEVICE, st, true)) != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+extern "C" int vrc_volume_stamp_affine(vrc_volume* dst, vrc_volume* src, const vrc_affine* map, const uint32_t dst_lo[3], const uint32_t dst_hi[3],
+                                       int op, void* stream)
+{
+    const char* what = "vrc_volume_stamp_affine";
+    if (!dst || !src || !map || !dst_lo || !dst_hi) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (src == dst) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
+    if (op != VRC_COPY_REPLACE && op != VRC_COPY_OR && op != VRC_COPY_ANDNOT) return vrc::fail(VRC_ERR_INVALID, "%s: bad op %d", what, op);
+    if (map->reserved != 0) return vrc::fail(VRC_ERR_INVALID, "%s: reserved is %d, not 0", what, map->reserved);
+    // the limits that keep s = m (2p + 1) + t below 2^41 and a word's deltas below 2^25
+    for (int i = 0; i < 9; ++i)
+        if (map->m[i] > (1 << 20) || map->m[i] < -(1 << 20)) return vrc::fail(VRC_ERR_INVALID, "%s: m[%d] = %d beyond +-2^20", what, i, map->m[i]);
+    for (int a = 0; a < 3; ++a)
+        if (map->t[a] > (1ll << 40) || map->t[a] < -(1ll << 40)) return vrc::fail(VRC_ERR_INVALID, "%s: t[%d] = %lld beyond +-2^40", what, a, (long long)map->t[a]);
+    if (src->device != dst->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, src->device, dst->device);
+    const uint32_t Sd = 1u << dst->depth;
+    uint32_t lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = dst_lo[a];
+        hi[a] = dst_hi[a] < Sd ? dst_hi[a] : Sd;
+        if (lo[a] >= hi[a]) return VRC_OK;                             // empty, inverted or wholly outside: nothing to write
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(dst->device);
+    if (e == hipSuccess) e = order_behind_edits(src, st);
+    if (e == hipSuccess) e = order_behind_edits(dst, st);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    vrc::stamp_affine_run(dst->d_bricks, dst->depth, src->d_bricks, src->depth, *map, lo, hi, op, st);
     if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
     if ((e = finish(dst, VRC_MEM_DEVICE, st, true)) != hipSuccess) return vrc::fail_hip(e, what);
     return VRC_OK;

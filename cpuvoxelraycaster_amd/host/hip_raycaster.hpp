@@ -353,6 +353,31 @@ public:
         src.flush();
         check(vrc_volume_copy_region(v_, src.v_, src_lo, size, dst_lo, op, stream), "vrc_volume_copy_region");
     }
+    // Stamps `src` into this volume through the inverse map (include/vrc.h: vrc_volume_stamp_affine): every voxel p of the
+    // box [dst_lo, dst_hi) -- the whole volume with nullptr -- takes (op) the src voxel (m (2p + 1) + t) >> 17.
+    void stampAffine(HipVoxelVolume& src, const vrc_affine& map, const uint32_t dst_lo[3] = nullptr, const uint32_t dst_hi[3] = nullptr,
+                     int op = VRC_COPY_REPLACE, void* stream = nullptr)
+    {
+        flush();
+        src.flush();
+        const uint32_t S = 1u << depth();
+        const uint32_t zero[3] = {0, 0, 0}, all[3] = {S, S, S};
+        check(vrc_volume_stamp_affine(v_, src.v_, &map, dst_lo ? dst_lo : zero, dst_hi ? dst_hi : all, op, stream), "vrc_volume_stamp_affine");
+    }
+    // Places `src` turned by rot (vrc_make_rotation's layout) and resized by scale about the pivots (continuous voxel
+    // coordinates; nullptr = the volume's centre): vrc_affine_place, then the stamp of the box it names.  Returns the map.
+    vrc_affine stampPlaced(HipVoxelVolume& src, const float rot[9], float scale = 1.0f, const float src_pivot[3] = nullptr,
+                           const float dst_pivot[3] = nullptr, int op = VRC_COPY_OR, void* stream = nullptr)
+    {
+        const float sc = (float)(1u << (src.depth() - 1u)), dc = (float)(1u << (depth() - 1u));
+        const float src_centre[3] = {sc, sc, sc}, dst_centre[3] = {dc, dc, dc};
+        vrc_affine map;
+        uint32_t lo[3], hi[3];
+        check(vrc_affine_place(rot, scale, src_pivot ? src_pivot : src_centre, dst_pivot ? dst_pivot : dst_centre, src.depth(), depth(), &map, lo, hi),
+              "vrc_affine_place");
+        stampAffine(src, map, lo, hi, op, stream);
+        return map;
+    }
     std::unique_ptr<HipVoxelVolume> clone()
     {
         flush();

@@ -143,6 +143,38 @@ def hit_to_voxel(depth, hit):
     return tuple(int(v) for v in voxel), (tuple(int(v) for v in neighbour) if has.value else None)
 
 
+def make_affine(m, t):
+    """capi.Affine from 9 row-major int32 (16 fractional bits) and 3 int64 (units of 2^-17 voxel)"""
+    a = capi.Affine()
+    m, t = [int(v) for v in np.asarray(m, object).reshape(9)], [int(v) for v in np.asarray(t, object).reshape(3)]
+    for i in range(9):
+        a.m[i] = m[i]
+    for i in range(3):
+        a.t[i] = t[i]
+    return a
+
+
+def affine_signed_permutation(perm, flip, size):
+    """The exact integer map of VoxelVolume.stampAffine for q_a = p[perm[a]], or size-1 - p[perm[a]] where flip[a] is set: one
+    of the 48 turns and mirrorings of a cube of `size` voxels.  It maps voxel centres to voxel centres."""
+    m, t = [0] * 9, [0] * 3
+    for a in range(3):
+        m[3 * a + int(perm[a])] = -65536 if flip[a] else 65536
+        t[a] = (int(size) << 17) if flip[a] else 0
+    return make_affine(m, t)
+
+
+def affine_place(rot, scale, src_pivot, dst_pivot, src_depth, dst_depth):
+    """(capi.Affine, lo, hi): the inverse map and the destination box of the placement
+    x_dst = dst_pivot + scale * R * (x_src - src_pivot), rot in make_rotation's layout.  Host arithmetic (include/vrc.h:
+    vrc_affine_place); raises for a scale below 1/16 or non-finite input."""
+    rot = np.ascontiguousarray(rot, np.float32).reshape(9)
+    sp, dp = np.ascontiguousarray(src_pivot, np.float32).reshape(3), np.ascontiguousarray(dst_pivot, np.float32).reshape(3)
+    a, lo, hi = capi.Affine(), np.zeros(3, np.uint32), np.zeros(3, np.uint32)
+    check(capi.load().vrc_affine_place(ptr(rot), float(scale), ptr(sp), ptr(dp), int(src_depth), int(dst_depth), C.byref(a), ptr(lo), ptr(hi)))
+    return a, tuple(int(v) for v in lo), tuple(int(v) for v in hi)
+
+
 class VoxelVolume:
     """Device-resident editable occupancy of an S^3 volume (include/vrc.h: vrc_volume_*).  Edits are batched; commit()
     builds a new immutable LSVO on the device, bit-identical to compileSVO of the current voxel set."""
@@ -205,6 +237,39 @@ class VoxelVolume:
         size = np.ascontiguousarray(size, np.uint32).reshape(3)
         dst_lo = np.ascontiguousarray(dst_lo, np.int32).reshape(3)
         check(capi.load().vrc_volume_copy_region(self._h, src._h, ptr(src_lo), ptr(size), ptr(dst_lo), int(op), ptr(stream)))
+
+    def stampAffine(self, src, affine, dst_lo=None, dst_hi=None, op=capi.VRC_COPY_REPLACE, stream=None):
+        """Stamps the volume `src` (any depth, same device) into this one through the inverse map `affine` (a capi.Affine,
+        e.g. from affine_signed_permutation / affine_place / make_affine): every voxel p of the box [dst_lo, dst_hi) -- the
+        whole volume by default -- takes (op) the source voxel (m (2p + 1) + t) >> 17, empty where that lies outside src
+        (include/vrc.h: vrc_volume_stamp_affine).  Asynchronous on `stream`."""
+        size = 1 << self.depth
+        lo = np.ascontiguousarray((0, 0, 0) if dst_lo is None else dst_lo, np.uint32).reshape(3)
+        hi = np.ascontiguousarray((size, size, size) if dst_hi is None else dst_hi, np.uint32).reshape(3)
+        check(capi.load().vrc_volume_stamp_affine(self._h, src._h, C.byref(affine), ptr(lo), ptr(hi), int(op), ptr(stream)))
+
+    def stampPlaced(self, src, rot, scale=1.0, src_pivot=None, dst_pivot=None, op=capi.VRC_COPY_OR, stream=None):
+        """Places `src` in this volume turned by rot (make_rotation's layout) and resized by scale about the pivots
+        (continuous voxel coordinates; the two volumes' centres by default): affine_place, then stampAffine of the box it
+        names.  Returns (affine, lo, hi)."""
+        if src_pivot is None:
+            src_pivot = (float(1 << (src.depth - 1)),) * 3
+        if dst_pivot is None:
+            dst_pivot = (float(1 << (self.depth - 1)),) * 3
+        affine, lo, hi = affine_place(rot, scale, src_pivot, dst_pivot, src.depth, self.depth)
+        self.stampAffine(src, affine, lo, hi, op, stream)
+        return affine, lo, hi
+
+    def transformed(self, affine, depth=None):
+        """A new volume of `depth` (this one's by default) on the same device that holds the stamp of this volume through
+        `affine`: affine_signed_permutation((1, 0, 2), (0, 1, 0), S) turns a clipboard a quarter turn."""
+        out = VoxelVolume(self.depth if depth is None else depth, self.device)
+        try:
+            out.stampAffine(self, affine)
+        except Exception:
+            out.close()
+            raise
+        return out
 
     def clone(self):
         """A new volume with this one's occupancy (after every edit issued so far) and albedo tables: the undo snapshot."""

@@ -77,6 +77,17 @@ by events on the NULL stream around the calls, one warm-up, `--pairs` repetition
   copy_field           the yardstick, in the same run: a device-to-device copy of 4 S^3 bytes (one read and one write of the
                        field; the transform reads and writes it twice after writing it once)
   worst_over_terrain   field time of corner_voxel over field time of terrain, per `to`: the per-line bound in practice
+With --stamp (printed and written to profiles/edit/bench_stamp.json), the affine stamp at 512^3 from the FastNoise terrain
+into a second volume, device time by events on the NULL stream, one warm-up, A B A B in one process, `--pairs` pairs, median
+and range:
+  identity             A = vrc_volume_copy_region of the whole volume, B = vrc_volume_stamp_affine with the identity map over
+                       the same box (the same work without and with the map: the yardstick), the two results asserted equal,
+                       and stamp_over_copy
+  quarter_turn         q = (p_y, S-1-p_x, p_z), next to the same copy
+  turn_30_30           a 30-degree turn about two axes at scale 1 about the centre (vrc_affine_place's map and box)
+  clipboard_64_x2      a 64^3 clipboard cut from the terrain's surface, stamped at scale 2 with the same turn into the world
+                       with the box from vrc_affine_place, next to a 128^3 region copy
+  per case the solid voxels of the result
 No threshold is applied; the numbers are reported."""
 import argparse
 import json
@@ -704,6 +715,54 @@ def bench_distance(vrc, depth, pairs):
     return res
 
 
+def bench_stamp(vrc, depth, pairs):
+    import math
+    S = 1 << depth
+    res = {"size": S, "pairs": pairs}
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    terrain = vrc.VoxelVolume.fromScene(scene)
+    copied, stamped = vrc.VoxelVolume(depth), vrc.VoxelVolume(depth)
+    REPLACE = vrc.capi.VRC_COPY_REPLACE
+    whole = ([0, 0, 0], [S, S, S], [0, 0, 0])
+    identity = vrc.make_affine([65536, 0, 0, 0, 65536, 0, 0, 0, 65536], [0, 0, 0])
+
+    def copy():
+        copied.copyRegion(terrain, *whole, REPLACE, None)
+
+    a, b = ab_device_ms(copy, lambda: stamped.stampAffine(terrain, identity, None, None, REPLACE, None), pairs)
+    same = bool(np.array_equal(copied.download(), stamped.download())) if depth <= 9 else copied.solidCount() == stamped.solidCount()
+    assert same and copied.solidCount() == stamped.solidCount() == terrain.solidCount(), "identity stamp differs from vrc_volume_copy_region"
+    res["identity"] = {"copy_region_ms": a, "stamp_ms": b, "stamp_over_copy": round(b["median"] / a["median"], 2), "equal": same,
+                       "solid": stamped.solidCount()}
+
+    turn = vrc.affine_signed_permutation((1, 0, 2), (0, 1, 0), S)
+    a, b = ab_device_ms(copy, lambda: stamped.stampAffine(terrain, turn, None, None, REPLACE, None), pairs)
+    res["quarter_turn"] = {"copy_region_ms": a, "stamp_ms": b, "stamp_over_copy": round(b["median"] / a["median"], 2), "solid": stamped.solidCount()}
+
+    # a rotation by 30 degrees about x, then about y, in vrc_make_rotation's layout (columns)
+    c, s = math.cos(math.radians(30)), math.sin(math.radians(30))
+    rx = np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
+    ry = np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
+    rot = np.ascontiguousarray((ry @ rx).T, np.float32).reshape(9)
+    placed, lo, hi = vrc.affine_place(rot, 1.0, (S / 2,) * 3, (S / 2,) * 3, depth, depth)
+    a, b = ab_device_ms(copy, lambda: stamped.stampAffine(terrain, placed, lo, hi, REPLACE, None), pairs)
+    res["turn_30_30"] = {"copy_region_ms": a, "stamp_ms": b, "stamp_over_copy": round(b["median"] / a["median"], 2), "box": [list(lo), list(hi)],
+                         "solid": stamped.solidCount()}
+
+    clip = vrc.VoxelVolume(6)
+    clip.copyRegion(terrain, [S // 2 - 32, S // 2 - 16, S // 2 - 32], [64, 64, 64], [0, 0, 0], REPLACE, None)
+    placed, lo, hi = vrc.affine_place(rot, 2.0, (32.0,) * 3, (S / 2,) * 3, 6, depth)
+    m = S // 2 - 64
+    a, b = ab_device_ms(lambda: copied.copyRegion(terrain, [m, m, m], [128, 128, 128], [m, m, m], REPLACE, None),
+                        lambda: stamped.stampAffine(clip, placed, lo, hi, vrc.capi.VRC_COPY_OR, None), pairs)
+    res["clipboard_64_x2"] = {"copy_128_ms": a, "stamp_ms": b, "stamp_over_copy": round(b["median"] / a["median"], 2), "box": [list(lo), list(hi)],
+                              "clipboard_solid": clip.solidCount(), "solid": stamped.solidCount()}
+    for v in (clip, stamped, copied, terrain):
+        v.close()
+    scene.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--depths", type=int, nargs="+", default=[8, 9, 10])
@@ -714,7 +773,10 @@ def main():
     ap.add_argument("--surface", action="store_true", help="time vrc_volume_surface_count / vrc_volume_extract_surface (depth 9 unless --depths is given)")
     ap.add_argument("--components", action="store_true", help="time vrc_volume_label_components / vrc_labels_* (depth 9 unless --depths is given)")
     ap.add_argument("--distance", action="store_true", help="time vrc_volume_distance_field / vrc_distance_select / dilate (depth 9 unless --depths is given)")
+    ap.add_argument("--stamp", action="store_true", help="time vrc_volume_stamp_affine next to vrc_volume_copy_region (depth 9 unless --depths is given)")
     args = ap.parse_args()
+    if args.stamp and args.depths == [8, 9, 10]:
+        args.depths = [9]
     if args.distance and args.depths == [8, 9, 10]:
         args.depths = [9]
     if args.components and args.depths == [8, 9, 10]:
@@ -733,10 +795,14 @@ def main():
     import cpuvoxelraycaster_amd as vrc
     if not torch.cuda.is_available():
         raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-    out = {"bench": "edit_distance" if args.distance else "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
+    out = {"bench": "edit_stamp" if args.stamp else "edit_distance" if args.distance else "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
     for d in args.depths:
-        out["depths"][str(d)] = (bench_distance if args.distance else bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
+        out["depths"][str(d)] = (bench_stamp if args.stamp else bench_distance if args.distance else bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
     print(json.dumps(out))
+    if args.stamp:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_stamp.json")
+        with open(path, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
     if args.distance:
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_distance.json")
         with open(path, "w") as f:
