@@ -1,11 +1,32 @@
-// vrc_box_words.h -- a clipped voxel box as a list of the 32-bit occupancy words its brick rows touch: the work layout of
-// every kernel that edits or reads a box of a brick-byte field (vrc_volume.hip: boxes, spheres, region copy, box counts;
-// vrc_stamp.hip: the affine stamp).  A word holds four bricks along z, 2 x 2 x 8 voxels.
+// vrc_box_words.h -- the brick-byte field's addressing, and a clipped voxel box as a list of the 32-bit occupancy words its
+// brick rows touch: the work layout of every kernel that edits or reads a box of the field (vrc_volume.hip: boxes, spheres,
+// region copy, box counts; vrc_stamp.hip: the affine stamp), the launch that goes with it, and the two ways a kernel writes
+// a destination word under VRC_COPY_REPLACE / OR / ANDNOT.  A word holds four bricks along z, 2 x 2 x 8 voxels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/vrc.h"
+
 namespace {
+
+// the byte index of the brick that holds voxel (x, y, z) in a field of n bricks per axis, and the voxel's bit in that byte
+__host__ __device__ __forceinline__ uint64_t brick_of(uint32_t n, uint32_t x, uint32_t y, uint32_t z)
+{
+    return ((uint64_t)(x >> 1) * n + (y >> 1)) * n + (z >> 1);
+}
+__host__ __device__ __forceinline__ uint32_t voxel_bit(uint32_t x, uint32_t y, uint32_t z) { return (z & 1u) * 4u + (y & 1u) * 2u + (x & 1u); }
+
+// lo_hi[0..5] clipped to the volume; false = empty, inverted or wholly outside
+__host__ __device__ __forceinline__ bool clip_box(const uint32_t* lo_hi, uint32_t S, uint32_t lo[3], uint32_t hi[3])
+{
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = lo_hi[a];
+        hi[a] = lo_hi[3 + a] < S ? lo_hi[3 + a] : S;
+        if (lo[a] >= hi[a]) return false;
+    }
+    return true;
+}
 
 // the voxels of brick coordinate c (one axis) that lie in [lo, hi): bit 0 = voxel 2c, bit 1 = voxel 2c + 1
 __device__ __forceinline__ uint32_t axis_pair(uint32_t c, uint32_t lo, uint32_t hi)
@@ -29,6 +50,14 @@ __host__ __device__ __forceinline__ uint64_t box_word_items(const uint32_t lo[3]
     const uint32_t nbx = ((hi[0] - 1u) >> 1) - (lo[0] >> 1) + 1u, nby = ((hi[1] - 1u) >> 1) - (lo[1] >> 1) + 1u;
     const uint32_t wpr = (((((hi[2] - 1u) >> 1) - (lo[2] >> 1)) + 3u) >> 2) + 1u;
     return (uint64_t)nbx * nby * wpr;
+}
+
+// the launch of the kernels that take ONE box: a thread per word of the box's rows, at most 16384 groups of 256, the rest by
+// grid stride
+inline uint32_t box_launch_groups(const uint32_t lo[3], const uint32_t hi[3])
+{
+    const uint64_t groups = (box_word_items(lo, hi) + 255u) / 256u;
+    return groups > 16384u ? 16384u : (uint32_t)groups;
 }
 
 __device__ __forceinline__ BoxWords box_words(const uint32_t lo[3], const uint32_t hi[3])
@@ -77,6 +106,34 @@ __device__ __forceinline__ uint32_t box_mask(const BoxWords& b, const RowWord& r
         mask |= m8 << (8u * j);
     }
     return mask;
+}
+
+// dst[w] takes (op) `bits` under `mask` (bits & ~mask == 0): the end of the kernels that gather a box's destination words.
+// A word has one owner within a call and is written once, a partly covered one as a masked read-modify-write -- unless
+// `shared`: in a volume of 4^3 (n < 4) two brick rows share a word, and its rows take 32-bit vector atomics.
+__device__ __forceinline__ void store_box_word(uint32_t* __restrict__ dst, uint64_t w, uint32_t mask, uint32_t bits, int op, bool shared)
+{
+    if (shared) {
+        if (op == VRC_COPY_REPLACE) { atomicAnd(&dst[w], ~mask); atomicOr(&dst[w], bits); }
+        else if (op == VRC_COPY_OR) atomicOr(&dst[w], bits);
+        else atomicAnd(&dst[w], ~bits);
+        return;
+    }
+    uint32_t v;
+    if (op == VRC_COPY_REPLACE) v = mask == 0xffffffffu ? bits : ((dst[w] & ~mask) | bits);
+    else if (op == VRC_COPY_OR) { if (!bits) return; v = dst[w] | bits; }
+    else { if (!bits) return; v = dst[w] & ~bits; }
+    dst[w] = v;
+}
+
+// dst[w] takes (op) the selection K of all 32 voxels of the word: the end of the kernels that select a whole field.  The
+// word has a single owner and is written whole with a plain store.
+__device__ __forceinline__ void store_selected_word(uint32_t* __restrict__ dst, uint32_t w, uint32_t K, int op)
+{
+    if (op == VRC_COPY_REPLACE) dst[w] = K;
+    else if (!K) return;
+    else if (op == VRC_COPY_OR) dst[w] |= K;
+    else dst[w] &= ~K;
 }
 
 }  // namespace

@@ -19,6 +19,7 @@
 #include <new>
 
 #include "../../include/vrc.h"
+#include "vrc_build_grids.h"
 #include "vrc_host.h"
 
 namespace {
@@ -126,41 +127,6 @@ __global__ void k_fill_blank_nodes(uint2* __restrict__ nodes, uint64_t n)
 }
 
 inline dim3 grid_for(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
-
-// The per-level count / rank / index grids of one build.  Levels 0 .. N-2 share one allocation; the bottom level (7/8
-// of all cells: 1.6 GB at depth 10) gets three of its own -- one multi-GB hipMalloc costs ~100 ms where the same bytes
-// in a few pieces cost 2 ms.  A one-shot build allocates and frees them; an editable volume keeps them between commits.
-struct BuildGrids {
-    uint32_t depth = 0;
-    uint32_t* arena = nullptr;
-    uint32_t *cnt[VRC_MAX_DEPTH] = {}, *rank[VRC_MAX_DEPTH] = {}, *index[VRC_MAX_DEPTH] = {};
-
-    hipError_t alloc(uint32_t N)
-    {
-        depth = N;
-        uint64_t total_cells = 0;
-        for (uint32_t L = 0; L + 1 < N; ++L) total_cells += 1ull << (3 * L);
-        hipError_t e = hipMalloc((void**)&arena, (total_cells ? total_cells : 1) * 12);
-        if (e != hipSuccess) return e;
-        uint64_t off = 0;
-        for (uint32_t L = 0; L + 1 < N; ++L) {
-            const uint64_t cells = 1ull << (3 * L);
-            cnt[L] = arena + off; rank[L] = arena + total_cells + off; index[L] = arena + 2 * total_cells + off;
-            off += cells;
-        }
-        const uint64_t bottom = 1ull << (3 * (N - 1));
-        if ((e = hipMalloc((void**)&cnt[N - 1], bottom * 4)) != hipSuccess) return e;
-        if ((e = hipMalloc((void**)&rank[N - 1], bottom * 4)) != hipSuccess) return e;
-        return hipMalloc((void**)&index[N - 1], bottom * 4);
-    }
-    void release()
-    {
-        if (arena) (void)hipFree(arena);
-        if (depth) { (void)hipFree(cnt[depth - 1]); (void)hipFree(rank[depth - 1]); (void)hipFree(index[depth - 1]); }
-        *this = BuildGrids();
-    }
-    bool allocated() const { return depth != 0 && index[depth - 1] != nullptr; }
-};
 
 // `pre` (optional) enqueues the kernels that produce the occupancy source (noise, column limits); it runs inside the
 // timed region.  *ms_out = device time of the build: [pre + count sweep] + [blank fill + emit sweep], two event

@@ -27,6 +27,9 @@
 // Every atomic is a 32- or 64-bit vector atomic at agent scope in plain HIP C++.
 #include "vrc_components.h"
 
+#include "vrc_box_words.h"
+#include "vrc_group.h"
+
 namespace {
 
 constexpr uint32_t NONE = VRC_NO_COMPONENT;
@@ -34,7 +37,6 @@ constexpr uint32_t ROOT_FLAG = 0x80000000u;
 constexpr uint32_t GROUP = 256;               // lanes per workgroup
 constexpr uint32_t ROUNDS = 32;               // a workgroup takes ROUNDS x GROUP consecutive keys (256 words)
 constexpr uint32_t GROUP_KEYS = GROUP * ROUNDS;
-constexpr uint32_t SCAN_GROUP = 1024;         // slots per step of the scan
 
 struct Field {
     uint32_t lg;                              // log2 of the bricks per axis, n = S / 2
@@ -125,40 +127,6 @@ __global__ __launch_bounds__(GROUP) void k_components_merge(Field f, const uint3
     }
 }
 
-// v summed over the GROUP lanes of the workgroup, on every lane.  part: 4 words of LDS, free again on return.
-__device__ __forceinline__ uint32_t group_sum(uint32_t v, uint32_t* part)
-{
-    for (int o = 32; o; o >>= 1) v += __shfl_down(v, o);
-    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const uint32_t s = part[0] + part[1] + part[2] + part[3];
-    __syncthreads();
-    return s;
-}
-
-// the sum of v over the lanes before this one, in a workgroup of WAVES waves; *total = the sum over all of them
-template <uint32_t WAVES>
-__device__ __forceinline__ uint32_t group_exclusive_scan(uint32_t v, uint32_t* part, uint32_t* total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-    for (uint32_t o = 1; o < 64u; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63u) part[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0u, all = 0u;
-    for (uint32_t k = 0; k < WAVES; ++k) {
-        const uint32_t p = part[k];
-        if (k < wave) before += p;
-        all += p;
-    }
-    __syncthreads();
-    *total = all;
-    return before + incl - v;
-}
-
 // No hook runs any more: the trees are final, and a thread that reads a label another thread has just flattened reads a
 // node of the same path.
 __global__ __launch_bounds__(GROUP) void k_components_flatten(Field f, uint32_t* L, uint32_t* __restrict__ slots)
@@ -174,24 +142,15 @@ __global__ __launch_bounds__(GROUP) void k_components_flatten(Field f, uint32_t*
         for (uint32_t p = load_label(L, a); p != a; p = load_label(L, a)) a = p;
         L[key] = a;
     }
-    const uint32_t s = group_sum(roots, part);
+    const uint32_t s = group_sum<GROUP / 64u>(roots, part);
     if (threadIdx.x == 0) slots[blockIdx.x] = s;
 }
 
 // slots[0 .. n_slots) -> their exclusive prefix, slots[n_slots] = the total (at most 2^30).  One workgroup.
 __global__ __launch_bounds__(SCAN_GROUP) void k_components_scan(uint32_t* __restrict__ slots, uint32_t n_slots)
 {
-    __shared__ uint32_t part[SCAN_GROUP / 64u];
-    uint32_t carry = 0u;
-    for (uint32_t base = 0; base < n_slots; base += SCAN_GROUP) {      // uniform trip count
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < n_slots ? slots[i] : 0u;
-        uint32_t step = 0u;
-        const uint32_t before = group_exclusive_scan<SCAN_GROUP / 64u>(v, part, &step);
-        if (i < n_slots) slots[i] = carry + before;
-        carry += step;
-    }
-    if (threadIdx.x == 0) slots[n_slots] = carry;
+    const uint32_t total = scan_slots(slots, n_slots);
+    if (threadIdx.x == 0) slots[n_slots] = total;
 }
 
 __global__ __launch_bounds__(GROUP) void k_components_roots(Field f, uint32_t* L, const uint32_t* __restrict__ slots, vrc_component* __restrict__ records)
@@ -296,11 +255,7 @@ __global__ __launch_bounds__(GROUP) void k_labels_select(Field f, const uint32_t
     const unsigned long long both = __ballot(in);
     if (key & 31u) return;
     const uint32_t K = (uint32_t)(key & 32u ? both >> 32 : both);
-    uint32_t* w = dst + (key >> 5);
-    if (op == VRC_COPY_REPLACE) *w = K;
-    else if (!K) return;
-    else if (op == VRC_COPY_OR) *w |= K;
-    else *w &= ~K;
+    store_selected_word(dst, key >> 5, K, op);
 }
 
 Field field_of(uint32_t depth, int through)

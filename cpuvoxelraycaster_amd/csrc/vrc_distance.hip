@@ -29,6 +29,8 @@
 //       workgroup give a result that does not depend on scheduling.
 #include "vrc_distance.h"
 
+#include "vrc_box_words.h"
+
 namespace {
 
 constexpr uint32_t NONE = VRC_DISTANCE_NONE;
@@ -112,6 +114,8 @@ __global__ __launch_bounds__(GROUP) void k_distance_z(const uint32_t* __restrict
         }
         __syncthreads();
     }
+    // Kept as the LDS tree it was: with group_sum (vrc_group.h) the to = SOLID field rows of tools/bench_edit.py --distance
+    // came out 0.5 - 2.4 % slower than the parent, beyond the parent's run-to-run spread (docs/NOTEBOOK.md).
     part[t] = features;                                          // at most 2^20 x 2^10 / gridDim per workgroup: fits
     __syncthreads();
     for (uint32_t s = GROUP / 2u; s; s >>= 1) {
@@ -248,10 +252,7 @@ __global__ __launch_bounds__(GROUP) void k_distance_select(const uint32_t* __res
             K |= (lo <= v && v <= hi ? 1u : 0u) << bit;
         }
     }
-    if (op == VRC_COPY_REPLACE) dst[w] = K;
-    else if (!K) return;
-    else if (op == VRC_COPY_OR) dst[w] |= K;
-    else dst[w] &= ~K;
+    store_selected_word(dst, w, K, op);
 }
 
 uint32_t minplus_groups(uint32_t depth, int cu_count)

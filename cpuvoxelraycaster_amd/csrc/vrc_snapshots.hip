@@ -1,0 +1,251 @@
+// vrc_snapshots.hip -- the snapshots taken from an editable volume (include/vrc.h): the labels of its connected components
+// (vrc_volume_label_components, vrc_labels_*; kernels in vrc_components.hip) and its exact squared Euclidean distance field
+// with the selection by distance that grow / shrink / hollow are made of (vrc_volume_distance_field, vrc_distance_*;
+// kernels in vrc_distance.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
+// event and no scratch; what it selects goes into a volume as an edit of that volume (vrc_volume_state.h).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <new>
+
+#include "../../include/vrc.h"
+#include "vrc_components.h"
+#include "vrc_distance.h"
+#include "vrc_volume_state.h"
+
+struct vrc_labels {
+    int device = 0;
+    uint32_t depth = 0;
+    uint64_t count = 0;
+    uint32_t* d_ids = nullptr;            // 8^depth ids, indexed by key
+    vrc_component* d_records = nullptr;   // count records, nullptr when count == 0
+};
+
+struct vrc_distance {
+    int device = 0;
+    uint32_t depth = 0;
+    uint32_t* d_field = nullptr;          // 8^depth squared distances, [(x*S + y)*S + z]
+};
+
+namespace {
+
+// The frame of the two creators: the NULL stream, behind the last asynchronous edit of the medium, as commit / download
+// are.  *d_array gets the snapshot's 8^depth words (its owner frees them, on failure too), a scratch block of
+// `scratch_bytes` lives for the call; run(d_scratch) enqueues the work and reads back the few words the creator needs.
+template <class Run>
+hipError_t snapshot_run(vrc_volume* medium, uint32_t** d_array, size_t scratch_bytes, Run run)
+{
+    uint32_t* d_scratch = nullptr;
+    hipError_t e = hipSetDevice(medium->device);
+    if (e == hipSuccess) e = order_behind_edits(medium, nullptr);
+    if (e == hipSuccess) e = hipMalloc((void**)d_array, (size_t)4u << (3u * medium->depth));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_scratch, scratch_bytes);
+    if (e == hipSuccess) e = run(d_scratch);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (d_scratch) (void)hipFree(d_scratch);
+    return e;
+}
+
+}  // namespace
+
+// ---- connected components --------------------------------------------------
+
+extern "C" int vrc_volume_label_components(vrc_volume* medium, int connectivity, int through, vrc_labels** out, uint64_t* n_components)
+{
+    const char* what = "vrc_volume_label_components";
+    if (!medium || !out) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_connectivity(what, connectivity)) return rc;
+    if (const int rc = check_through(what, through)) return rc;
+    vrc_labels* l = new (std::nothrow) vrc_labels();
+    if (!l) return vrc::fail(VRC_ERR_OOM, "out of host memory");
+    l->device = medium->device; l->depth = medium->depth;
+    uint32_t C = 0;
+    const hipError_t e = snapshot_run(medium, &l->d_ids, vrc::components_scratch_bytes(l->depth), [&](uint32_t* d_scratch) {
+        vrc::components_roots_run(medium->d_bricks, l->depth, connectivity, through, l->d_ids, d_scratch, nullptr);
+        hipError_t run = hipGetLastError();
+        if (run == hipSuccess) run = hipMemcpy(&C, vrc::components_total_slot(d_scratch, l->depth), 4, hipMemcpyDeviceToHost);
+        if (run == hipSuccess && C) run = hipMalloc((void**)&l->d_records, (size_t)C * sizeof(vrc_component));
+        if (run == hipSuccess && C) {
+            vrc::components_ids_run(l->depth, l->d_ids, d_scratch, l->d_records, nullptr);
+            run = hipGetLastError();
+        }
+        return run;
+    });
+    if (e != hipSuccess) {
+        (void)vrc_labels_destroy(l);
+        return vrc::fail_hip(e, what);
+    }
+    l->count = C;
+    *out = l;
+    if (n_components) *n_components = C;
+    return VRC_OK;
+}
+
+extern "C" int vrc_labels_destroy(vrc_labels* l)
+{
+    if (!l) return VRC_OK;
+    (void)hipSetDevice(l->device);
+    (void)hipDeviceSynchronize();       // device-memory calls may still be reading it on a caller's stream
+    if (l->d_ids) (void)hipFree(l->d_ids);
+    if (l->d_records) (void)hipFree(l->d_records);
+    delete l;
+    return VRC_OK;
+}
+
+extern "C" uint64_t vrc_labels_count(const vrc_labels* l) { return l ? l->count : 0; }
+extern "C" uint32_t vrc_labels_depth(const vrc_labels* l) { return l ? l->depth : 0; }
+extern "C" uint64_t vrc_labels_bytes(const vrc_labels* l) { return l ? ((uint64_t)4u << (3u * l->depth)) + l->count * sizeof(vrc_component) : 0; }
+
+extern "C" int vrc_labels_components(const vrc_labels* l, uint64_t first, uint64_t capacity, vrc_component* out, int mem, void* stream)
+{
+    const char* what = "vrc_labels_components";
+    if (!l) return vrc::fail(VRC_ERR_INVALID, "%s: null labels", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
+    const uint64_t want = first < l->count ? (capacity < l->count - first ? capacity : l->count - first) : 0u;
+    if (!want) return VRC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(l->device);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(out, l->d_records + first, (size_t)want * sizeof(vrc_component), mem == VRC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+extern "C" int vrc_labels_at(const vrc_labels* l, uint64_t n, const uint32_t* xyz, uint32_t* ids, int mem, void* stream)
+{
+    const char* what = "vrc_labels_at";
+    if (!l) return vrc::fail(VRC_ERR_INVALID, "%s: null labels", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (n == 0) return VRC_OK;
+    if (!xyz || !ids) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "%s: too many voxels for one launch", what);
+    hipStream_t st = (hipStream_t)stream;
+    return staged_call(what, l->device, nullptr, xyz, (size_t)n * 12u, ids, (size_t)n * 4u, mem, st, [&](const void* d_xyz, void* d_ids) {
+        vrc::components_at_run(l->d_ids, l->depth, n, (const uint32_t*)d_xyz, (uint32_t*)d_ids, st);
+        return hipSuccess;
+    });
+}
+
+extern "C" int vrc_labels_select(const vrc_labels* l, const uint8_t* keep, vrc_volume* dst, int op, int mem, void* stream)
+{
+    const char* what = "vrc_labels_select";
+    if (!l || !dst) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_op(what, op)) return rc;
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (dst->depth != l->depth) return vrc::fail(VRC_ERR_INVALID, "%s: labels of depth %u, volume of depth %u", what, l->depth, dst->depth);
+    if (dst->device != l->device) return vrc::fail(VRC_ERR_INVALID, "%s: labels on device %d, volume on device %d", what, l->device, dst->device);
+    if (!keep && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null keep with %llu components", what, (unsigned long long)l->count);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(l->device);
+    if (e == hipSuccess) e = order_behind_edits(dst, st);
+    const uint8_t* d_keep = keep;
+    uint8_t* d_stage = nullptr;
+    if (mem == VRC_MEM_HOST && l->count) {
+        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, (size_t)l->count);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_stage, keep, (size_t)l->count, hipMemcpyHostToDevice, st);
+        d_keep = d_stage;
+    }
+    if (e == hipSuccess) {
+        vrc::components_select_run(l->d_ids, l->depth, d_keep, dst->d_bricks, op, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = finish(dst, mem, st, true);
+    if (d_stage) (void)hipFree(d_stage);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+// ---- distance field ----------------------------------------------------------
+
+extern "C" int vrc_volume_distance_field(vrc_volume* medium, int to, int outside, vrc_distance** out, vrc_distance_stats* stats)
+{
+    const char* what = "vrc_volume_distance_field";
+    if (!medium || !out) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (to != VRC_FLOOD_SOLID && to != VRC_FLOOD_EMPTY) return vrc::fail(VRC_ERR_INVALID, "%s: bad to %d", what, to);
+    if (medium->depth < 2 || medium->depth > 10) return vrc::fail(VRC_ERR_INVALID, "%s: depth %u not in [2,10]", what, medium->depth);
+    vrc_distance* d = new (std::nothrow) vrc_distance();
+    if (!d) return vrc::fail(VRC_ERR_OOM, "out of host memory");
+    d->device = medium->device; d->depth = medium->depth;
+    unsigned long long host[2] = {0ull, 0ull};
+    const hipError_t e = snapshot_run(medium, &d->d_field, vrc::distance_scratch_bytes(d->depth, medium->cu_count), [&](uint32_t* d_scratch) {
+        vrc::distance_run(medium->d_bricks, d->depth, to, outside, medium->cu_count, d->d_field, d_scratch, nullptr);
+        const hipError_t run = hipGetLastError();
+        return run != hipSuccess ? run : hipMemcpy(host, vrc::distance_stats_slots(d_scratch), sizeof host, hipMemcpyDeviceToHost);
+    });
+    if (e != hipSuccess) {
+        (void)vrc_distance_destroy(d);
+        return vrc::fail_hip(e, what);
+    }
+    if (stats) {
+        stats->features = host[0];
+        stats->max_d2 = 0u; stats->argmax[0] = stats->argmax[1] = stats->argmax[2] = 0u; stats->reserved = 0u;
+        if (host[1]) {
+            const uint32_t index = ~(uint32_t)host[1], mask = (1u << d->depth) - 1u;
+            stats->max_d2 = (uint32_t)(host[1] >> 32);
+            stats->argmax[0] = index >> (2u * d->depth); stats->argmax[1] = (index >> d->depth) & mask; stats->argmax[2] = index & mask;
+        }
+    }
+    *out = d;
+    return VRC_OK;
+}
+
+extern "C" int vrc_distance_destroy(vrc_distance* d)
+{
+    if (!d) return VRC_OK;
+    (void)hipSetDevice(d->device);
+    (void)hipDeviceSynchronize();       // device-memory calls may still be reading it on a caller's stream
+    if (d->d_field) (void)hipFree(d->d_field);
+    delete d;
+    return VRC_OK;
+}
+
+extern "C" uint32_t vrc_distance_depth(const vrc_distance* d) { return d ? d->depth : 0; }
+extern "C" uint64_t vrc_distance_bytes(const vrc_distance* d) { return d ? (uint64_t)4u << (3u * d->depth) : 0; }
+extern "C" const uint32_t* vrc_distance_data(const vrc_distance* d) { return d ? d->d_field : nullptr; }
+
+extern "C" int vrc_distance_at(const vrc_distance* d, uint64_t n, const uint32_t* xyz, uint32_t* d2, int mem, void* stream)
+{
+    const char* what = "vrc_distance_at";
+    if (!d) return vrc::fail(VRC_ERR_INVALID, "%s: null distance field", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (n == 0) return VRC_OK;
+    if (!xyz || !d2) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "%s: too many voxels for one launch", what);
+    hipStream_t st = (hipStream_t)stream;
+    return staged_call(what, d->device, nullptr, xyz, (size_t)n * 12u, d2, (size_t)n * 4u, mem, st, [&](const void* d_xyz, void* d_d2) {
+        vrc::distance_at_run(d->d_field, d->depth, n, (const uint32_t*)d_xyz, (uint32_t*)d_d2, st);
+        return hipSuccess;
+    });
+}
+
+extern "C" int vrc_distance_download(const vrc_distance* d, uint32_t* d2_host)
+{
+    const char* what = "vrc_distance_download";
+    if (!d || !d2_host) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    hipError_t e = hipSetDevice(d->device);
+    if (e == hipSuccess) e = hipMemcpy(d2_host, d->d_field, (size_t)4u << (3u * d->depth), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+extern "C" int vrc_distance_select(const vrc_distance* d, uint32_t lo, uint32_t hi, vrc_volume* dst, int op, void* stream)
+{
+    const char* what = "vrc_distance_select";
+    if (!d || !dst) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_op(what, op)) return rc;
+    if (lo > hi) return vrc::fail(VRC_ERR_INVALID, "%s: lo %u above hi %u", what, lo, hi);
+    if (dst->depth != d->depth) return vrc::fail(VRC_ERR_INVALID, "%s: field of depth %u, volume of depth %u", what, d->depth, dst->depth);
+    if (dst->device != d->device) return vrc::fail(VRC_ERR_INVALID, "%s: field on device %d, volume on device %d", what, d->device, dst->device);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(d->device);
+    if (e == hipSuccess) e = order_behind_edits(dst, st);
+    if (e == hipSuccess) {
+        vrc::distance_select_run(d->d_field, d->depth, lo, hi, dst->d_bricks, op, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}

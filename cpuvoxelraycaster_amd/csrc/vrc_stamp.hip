@@ -42,7 +42,7 @@ __device__ __forceinline__ uint32_t gather_word(const uint8_t* __restrict__ src,
                 if (INSIDE || (x < Ss && y < Ss && z < Ss)) {          // unsigned: a negative coordinate is a large one
                     const uint32_t at = ((x >> 1) * ns + (y >> 1)) * ns + (z >> 1);     // < 2^27
                     if (at != last) { last = at; byte = src[at]; }
-                    bits |= ((byte >> ((z & 1u) * 4u + (y & 1u) * 2u + (x & 1u))) & 1u) << bit;
+                    bits |= ((byte >> voxel_bit(x, y, z)) & 1u) << bit;
                 }
             }
 #pragma unroll
@@ -90,17 +90,7 @@ __global__ void __launch_bounds__(256) k_stamp_affine(uint32_t* __restrict__ dst
         uint32_t bits = 0u;
         if (miss) { if (op != VRC_COPY_REPLACE) continue; }
         else bits = inside ? gather_word<true>(src, ns, q, frac, step, mask) : gather_word<false>(src, ns, q, frac, step, mask);
-        if (n < 4u) {
-            if (op == VRC_COPY_REPLACE) { atomicAnd(&dst[r.w], ~mask); atomicOr(&dst[r.w], bits); }
-            else if (op == VRC_COPY_OR) atomicOr(&dst[r.w], bits);
-            else atomicAnd(&dst[r.w], ~bits);
-            continue;
-        }
-        uint32_t v;
-        if (op == VRC_COPY_REPLACE) v = mask == 0xffffffffu ? bits : ((dst[r.w] & ~mask) | bits);
-        else if (op == VRC_COPY_OR) { if (!bits) continue; v = dst[r.w] | bits; }
-        else { if (!bits) continue; v = dst[r.w] & ~bits; }
-        dst[r.w] = v;
+        store_box_word(dst, r.w, mask, bits, op, n < 4u);
     }
 }
 
@@ -111,11 +101,7 @@ namespace vrc {
 void stamp_affine_run(uint32_t* dst, uint32_t dst_depth, const uint32_t* src, uint32_t src_depth, const vrc_affine& map, const uint32_t lo[3],
                       const uint32_t hi[3], int op, hipStream_t st)
 {
-    // the launch of the region copy: a thread per word of the box's rows, capped, the rest by grid stride
-    const uint64_t words = box_word_items(lo, hi);
-    uint64_t groups = (words + 255u) / 256u;
-    if (groups > 16384u) groups = 16384u;
-    hipLaunchKernelGGL(k_stamp_affine, dim3((uint32_t)groups), dim3(256), 0, st, dst, 1u << dst_depth, (const uint8_t*)src, 1u << src_depth, map,
+    hipLaunchKernelGGL(k_stamp_affine, dim3(box_launch_groups(lo, hi)), dim3(256), 0, st, dst, 1u << dst_depth, (const uint8_t*)src, 1u << src_depth, map,
                        lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], op);
 }
 

@@ -24,6 +24,7 @@
 
 #include "../../include/vrc.h"
 #include "vrc_flood.h"
+#include "vrc_group.h"
 
 namespace {
 
@@ -33,7 +34,6 @@ using vrc::WORD_Y0;
 using vrc::WORD_Y1;
 
 constexpr uint32_t GROUP = 256;               // words per workgroup
-constexpr uint32_t SCAN_GROUP = 1024;         // slots per step of the scan
 
 struct Field {
     const uint32_t* words;
@@ -92,40 +92,6 @@ __device__ __forceinline__ void word_masks(const Field& f, uint32_t W, uint32_t 
     }
 }
 
-// v summed over the 256 lanes of the workgroup, on every lane.  part: 4 words of LDS, free again on return.
-__device__ __forceinline__ uint32_t group_sum(uint32_t v, uint32_t* part)
-{
-    for (int o = 32; o; o >>= 1) v += __shfl_down(v, o);
-    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const uint32_t s = part[0] + part[1] + part[2] + part[3];
-    __syncthreads();
-    return s;
-}
-
-// the sum of v over the lanes before this one, in a workgroup of WAVES waves; *total = the sum over all of them
-template <uint32_t WAVES>
-__device__ __forceinline__ uint32_t group_exclusive_scan(uint32_t v, uint32_t* part, uint32_t* total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-    for (uint32_t o = 1; o < 64u; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63u) part[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0u, all = 0u;
-    for (uint32_t k = 0; k < WAVES; ++k) {
-        const uint32_t p = part[k];
-        if (k < wave) before += p;
-        all += p;
-    }
-    __syncthreads();
-    *total = all;
-    return before + incl - v;
-}
-
 // DIRECTIONS: the six totals of the whole field (vrc_volume_surface_count); otherwise the workgroup's own total
 template <bool DIRECTIONS>
 __global__ __launch_bounds__(256) void k_surface_count(Field f, unsigned long long* __restrict__ slots)
@@ -136,33 +102,24 @@ __global__ __launch_bounds__(256) void k_surface_count(Field f, unsigned long lo
     if (W < f.n_words) word_masks(f, W, m);
     if (DIRECTIONS) {
         for (int d = 0; d < 6; ++d) {
-            const uint32_t s = group_sum(__popc(m[d]), part);
+            const uint32_t s = group_sum<GROUP / 64u>(__popc(m[d]), part);
             if (threadIdx.x == 0 && s) atomicAdd(&slots[d], (unsigned long long)s);
         }
     } else {
         uint32_t c = 0u;
         for (int d = 0; d < 6; ++d) c += __popc(m[d]);
-        const uint32_t s = group_sum(c, part);
+        const uint32_t s = group_sum<GROUP / 64u>(c, part);
         if (threadIdx.x == 0) slots[blockIdx.x] = s;
     }
 }
 
 // slots[0 .. n_slots) -> their exclusive prefix, slots[n_slots] = the total.  One workgroup.
-__global__ __launch_bounds__(1024) void k_surface_scan(unsigned long long* __restrict__ slots, uint32_t n_slots, unsigned long long* __restrict__ total_out)
+__global__ __launch_bounds__(SCAN_GROUP) void k_surface_scan(unsigned long long* __restrict__ slots, uint32_t n_slots, unsigned long long* __restrict__ total_out)
 {
-    __shared__ uint32_t part[SCAN_GROUP / 64u];
-    unsigned long long carry = 0ull;
-    for (uint32_t base = 0; base < n_slots; base += SCAN_GROUP) {      // uniform trip count
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < n_slots ? (uint32_t)slots[i] : 0u;      // <= 256 * 192; a step's sum stays below 2^26
-        uint32_t step = 0u;
-        const uint32_t before = group_exclusive_scan<SCAN_GROUP / 64u>(v, part, &step);
-        if (i < n_slots) slots[i] = carry + before;
-        carry += step;
-    }
+    const unsigned long long total = scan_slots(slots, n_slots);      // a slot <= 256 * 192; a step's sum stays below 2^26
     if (threadIdx.x == 0) {
-        slots[n_slots] = carry;
-        if (total_out) *total_out = carry;
+        slots[n_slots] = total;
+        if (total_out) *total_out = total;
     }
 }
 

@@ -8,15 +8,12 @@
 // commit is the builder's count / rank / emit sweeps (vrc_build_sweeps.h) over a third occupancy source, BrickVox:
 // bit-identical to compileSVO of the voxel set, into a NEW scene.  Batched edits are 32-bit vector atomics
 // (atomicOr / atomicAnd) on the words that hold the bricks, or whole-word stores where a box covers a word.
-// Brushes (spheres, spheres at the hits of a ray batch), region copies between volumes and the two queries (single
-// voxels, solid voxels per box) walk the same rows of words as the boxes do.  The flood fill by connectivity
-// (vrc_volume_flood) has its kernels in vrc_flood.hip, the solid voxelisation of triangle meshes (vrc_volume_xor_mesh)
-// in vrc_voxelize.hip, its inverse, the exposed faces as a mesh (vrc_volume_extract_surface), in vrc_surface.hip, the
-// labelling of connected components (vrc_volume_label_components, vrc_labels_*) in vrc_components.hip, the exact squared
-// Euclidean distance field and the selection by distance that grow / shrink / hollow are made of
-// (vrc_volume_distance_field, vrc_distance_*) in vrc_distance.hip, the stamp through an affine map -- rotated, mirrored and
-// scaled pastes (vrc_volume_stamp_affine) -- in vrc_stamp.hip, with the box-of-words layout it shares with the kernels here
-// in vrc_box_words.h; the entry points, their ordering and their scratch blocks are here.
+//
+// Here: the volume's life cycle, the edits and queries on the occupancy with their ordering and scratch blocks, and
+// commit / download.  Boxes, spheres, spheres at the hits of a ray batch, region copies and the two queries have their
+// kernels here, over the box-of-words layout of vrc_box_words.h.  The other features keep theirs in files of their own:
+// vrc_flood.hip, vrc_voxelize.hip, vrc_surface.hip, vrc_stamp.hip.  The snapshots taken from a volume (labels, distance
+// fields) are in vrc_snapshots.hip; what the entry points of both files share is in vrc_volume_state.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -25,39 +22,12 @@
 #include "../../include/vrc.h"
 #include "vrc_box_words.h"
 #include "vrc_build_sweeps.h"
-#include "vrc_components.h"
-#include "vrc_distance.h"
 #include "vrc_flood.h"
+#include "vrc_group.h"
 #include "vrc_stamp.h"
 #include "vrc_surface.h"
+#include "vrc_volume_state.h"
 #include "vrc_voxelize.h"
-
-struct vrc_volume {
-    int device = 0;
-    int cu_count = 0;
-    uint32_t depth = 0;
-    uint32_t* d_bricks = nullptr;     // n^3 brick bytes, addressed as 32-bit words by the edit kernels (n^3 is a multiple of 8)
-    uint64_t n_bricks = 0;
-    void* d_tex = nullptr;            // 1536 bytes: the albedo tables every committed scene gets
-    unsigned long long* d_count = nullptr;
-    BuildGrids grids;                 // kept between commits, allocated by the first
-    // host-memory form of the edit calls: grow-only staging block
-    uint32_t* d_stage = nullptr;
-    size_t stage_cap = 0;
-    // vrc_volume_flood with this volume as `region`: grow-only tile flags and sweep counters
-    uint32_t* d_flood = nullptr;
-    size_t flood_cap = 0;
-    // vrc_volume_xor_mesh: the mark field, as large as d_bricks, allocated and zeroed by the first call, zero between calls
-    uint32_t* d_marks = nullptr;
-    // vrc_volume_surface_count / _extract_surface: the per-workgroup face offsets and the totals (vrc_surface.h), allocated
-    // by the first call, fixed in size
-    unsigned long long* d_surface = nullptr;
-    // the last asynchronous edit: commit / download / solid_count run on the NULL stream and wait for it first.  The flag
-    // says that the event has been recorded at least once; it is never cleared, because a wait only orders ONE stream
-    // behind the edit and the next caller may bring another.
-    hipEvent_t edit_done = nullptr;
-    bool edit_pending = false;
-};
 
 namespace {
 
@@ -71,22 +41,10 @@ __global__ void k_set_voxels(uint32_t* __restrict__ words, uint32_t S, uint64_t 
     if (i >= count) return;
     const uint32_t x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
     if (x >= S || y >= S || z >= S) return;
-    const uint32_t n = S >> 1;
-    const uint64_t brick = ((uint64_t)(x >> 1) * n + (y >> 1)) * n + (z >> 1);
-    const uint32_t bit = 1u << (((z & 1u) * 4u + (y & 1u) * 2u + (x & 1u)) + 8u * (uint32_t)(brick & 3u));
+    const uint64_t brick = brick_of(S >> 1, x, y, z);
+    const uint32_t bit = 1u << (voxel_bit(x, y, z) + 8u * (uint32_t)(brick & 3u));
     if (solid) atomicOr(&words[brick >> 2], bit);
     else atomicAnd(&words[brick >> 2], ~bit);
-}
-
-// lo_hi[0..5] clipped to the volume; false = empty, inverted or wholly outside
-__device__ __forceinline__ bool clip_box(const uint32_t* lo_hi, uint32_t S, uint32_t lo[3], uint32_t hi[3])
-{
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = lo_hi[a];
-        hi[a] = lo_hi[3 + a] < S ? lo_hi[3 + a] : S;
-        if (lo[a] >= hi[a]) return false;
-    }
-    return true;
 }
 
 // Boxes [lo, hi) clipped to the volume.  blockIdx.x = box, and the box's work is split over blockIdx.y x 256 threads.
@@ -262,17 +220,7 @@ __global__ void k_copy_region(uint32_t* __restrict__ dst, uint32_t Sd, const uin
             for (uint32_t z = 0; z < 8u; ++z) bits |= ((col >> z) & 1u) << ((z >> 1) * 8u + (z & 1u) * 4u + k);
         }
         bits &= mask;
-        if (n < 4u) {
-            if (op == VRC_COPY_REPLACE) { atomicAnd(&dst[r.w], ~mask); atomicOr(&dst[r.w], bits); }
-            else if (op == VRC_COPY_OR) atomicOr(&dst[r.w], bits);
-            else atomicAnd(&dst[r.w], ~bits);
-            continue;
-        }
-        uint32_t v;
-        if (op == VRC_COPY_REPLACE) v = mask == 0xffffffffu ? bits : ((dst[r.w] & ~mask) | bits);
-        else if (op == VRC_COPY_OR) { if (!bits) continue; v = dst[r.w] | bits; }
-        else { if (!bits) continue; v = dst[r.w] & ~bits; }
-        dst[r.w] = v;
+        store_box_word(dst, r.w, mask, bits, op, n < 4u);
     }
 }
 
@@ -284,17 +232,14 @@ __global__ void k_get_voxels(const uint8_t* __restrict__ bricks, uint32_t S, uin
     if (i >= count) return;
     const uint32_t x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
     uint32_t v = 0u;
-    if (x < S && y < S && z < S) {
-        const uint32_t n = S >> 1;
-        v = (bricks[((uint64_t)(x >> 1) * n + (y >> 1)) * n + (z >> 1)] >> ((z & 1u) * 4u + (y & 1u) * 2u + (x & 1u))) & 1u;
-    }
+    if (x < S && y < S && z < S) v = (bricks[brick_of(S >> 1, x, y, z)] >> voxel_bit(x, y, z)) & 1u;
     solid_out[i] = (uint8_t)v;
 }
 
 // counts[box] (zeroed before the launch) += the solid voxels inside box: popcount of the words under k_fill_boxes' masks
 __global__ void k_count_boxes(const uint32_t* __restrict__ words, uint32_t S, const uint32_t* __restrict__ lo_hi, unsigned long long* __restrict__ counts)
 {
-    __shared__ uint32_t part[256];
+    __shared__ uint32_t part[4];
     uint32_t lo[3], hi[3];
     if (!clip_box(lo_hi + 6ull * blockIdx.x, S, lo, hi)) return;      // uniform for the workgroup
     const uint32_t n = S >> 1;
@@ -306,13 +251,8 @@ __global__ void k_count_boxes(const uint32_t* __restrict__ words, uint32_t S, co
         const uint32_t mask = box_mask(b, r);
         if (mask) total += __popc(words[r.w] & mask);
     }
-    part[threadIdx.x] = total;
-    __syncthreads();
-    for (uint32_t s = 128u; s; s >>= 1) {
-        if (threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && part[0]) atomicAdd(&counts[blockIdx.x], (unsigned long long)part[0]);
+    const uint32_t sum = group_sum<4u>(total, part);
+    if (threadIdx.x == 0 && sum) atomicAdd(&counts[blockIdx.x], (unsigned long long)sum);
 }
 
 // ---- scene -> volume ---------------------------------------------------------
@@ -357,17 +297,12 @@ __global__ void k_expand_dense(const uint8_t* __restrict__ bricks, uint32_t S, u
 
 __global__ void k_count_solid(const uint32_t* __restrict__ words, uint64_t n_words, unsigned long long* __restrict__ total)
 {
-    __shared__ uint32_t part[256];
+    __shared__ uint32_t part[4];
     uint32_t c = 0u;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * blockDim.x)
         c += __popc(words[i]);
-    part[threadIdx.x] = c;
-    __syncthreads();
-    for (uint32_t s = 128u; s; s >>= 1) {
-        if (threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && part[0]) atomicAdd(total, (unsigned long long)part[0]);
+    const uint32_t sum = group_sum<4u>(c, part);
+    if (threadIdx.x == 0 && sum) atomicAdd(total, (unsigned long long)sum);
 }
 
 void volume_free(vrc_volume* v)
@@ -406,40 +341,6 @@ int volume_new(uint32_t depth, int device, vrc_volume** out)
     return VRC_OK;
 }
 
-// orders the NULL stream behind the last asynchronous edit
-hipError_t wait_for_edits(vrc_volume* v)
-{
-    return v->edit_pending ? hipStreamWaitEvent(nullptr, v->edit_done, 0) : hipSuccess;
-}
-
-// The grow-only staging block, at least `need` bytes.  hipFree waits for everything that may still read the old block.
-hipError_t stage_reserve(vrc_volume* v, size_t need)
-{
-    if (v->stage_cap >= need) return hipSuccess;
-    if (v->d_stage) (void)hipFree(v->d_stage);
-    v->d_stage = nullptr; v->stage_cap = 0;
-    const hipError_t e = hipMalloc((void**)&v->d_stage, need);
-    if (e == hipSuccess) v->stage_cap = need;
-    return e;
-}
-
-// orders `st` behind the last asynchronous edit: for the calls that read the occupancy, and for every call that writes
-// the staging block -- the device-memory brush at hits leaves its centres there, in flight on the caller's stream
-hipError_t order_behind_edits(vrc_volume* v, hipStream_t st)
-{
-    return v->edit_pending ? hipStreamWaitEvent(st, v->edit_done, 0) : hipSuccess;
-}
-
-// the end of every call that takes `mem`: a host-memory call is synchronous, a device-memory edit is recorded as the
-// volume's last asynchronous edit
-hipError_t finish(vrc_volume* v, int mem, hipStream_t st, bool is_edit)
-{
-    if (mem == VRC_MEM_HOST) return hipStreamSynchronize(st);
-    if (!is_edit) return hipSuccess;
-    v->edit_pending = true;            // the NULL stream included: streams made by vrc_stream_create do not wait for it
-    return hipEventRecord(v->edit_done, st);
-}
-
 // Shared frame of the edit calls that read a list of items: `words_per_item` u32 per item at `items`; host memory is
 // staged and the call synchronous, device memory is used in place and the call asynchronous on `st`.
 template <class Launch>
@@ -451,7 +352,7 @@ int edit(vrc_volume* v, const char* what, uint64_t count, uint32_t words_per_ite
     if (mem == VRC_MEM_HOST) {
         const size_t need = (size_t)count * words_per_item * 4u;
         if ((e = order_behind_edits(v, st)) != hipSuccess) return vrc::fail_hip(e, what);
-        if ((e = stage_reserve(v, need)) != hipSuccess) return vrc::fail_hip(e, what);
+        if ((e = reserve(v->d_stage, v->stage_cap, need)) != hipSuccess) return vrc::fail_hip(e, what);
         if ((e = hipMemcpyAsync(v->d_stage, items, need, hipMemcpyHostToDevice, st)) != hipSuccess) return vrc::fail_hip(e, what);
         d_items = v->d_stage;
     }
@@ -526,7 +427,7 @@ extern "C" uint32_t vrc_volume_depth(const vrc_volume* v) { return v ? v->depth 
 extern "C" int vrc_volume_set_voxels(vrc_volume* v, uint64_t n, const uint32_t* xyz, int solid, int mem, void* stream)
 {
     if (!v) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_set_voxels: null volume");
-    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_set_voxels: bad mem kind %d", mem);
+    if (const int rc = check_mem("vrc_volume_set_voxels", mem)) return rc;
     if (n == 0) return VRC_OK;
     if (!xyz) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_set_voxels: null buffer");
     if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_set_voxels: too many voxels for one launch");
@@ -540,7 +441,7 @@ extern "C" int vrc_volume_set_voxels(vrc_volume* v, uint64_t n, const uint32_t* 
 extern "C" int vrc_volume_fill_boxes(vrc_volume* v, uint64_t n, const uint32_t* lo_hi, int solid, int mem, void* stream)
 {
     if (!v) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_boxes: null volume");
-    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_boxes: bad mem kind %d", mem);
+    if (const int rc = check_mem("vrc_volume_fill_boxes", mem)) return rc;
     if (n == 0) return VRC_OK;
     if (!lo_hi) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_boxes: null buffer");
     if (n > 0x7fffffffull) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_boxes: too many boxes for one launch");
@@ -555,7 +456,7 @@ extern "C" int vrc_volume_fill_boxes(vrc_volume* v, uint64_t n, const uint32_t* 
 extern "C" int vrc_volume_fill_spheres(vrc_volume* v, uint64_t n, const int32_t* centre_radius, int solid, int mem, void* stream)
 {
     if (!v) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_spheres: null volume");
-    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_spheres: bad mem kind %d", mem);
+    if (const int rc = check_mem("vrc_volume_fill_spheres", mem)) return rc;
     if (n == 0) return VRC_OK;
     if (!centre_radius) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_spheres: null buffer");
     if (n > 0x7fffffffull) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_spheres: too many spheres for one launch");
@@ -569,7 +470,7 @@ extern "C" int vrc_volume_fill_spheres_at_hits(vrc_volume* v, uint64_t n, const 
 {
     const char* what = "vrc_volume_fill_spheres_at_hits";
     if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
-    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
+    if (const int rc = check_mem(what, mem)) return rc;
     if (radius < 0 || radius > VRC_BRUSH_LIMIT) return vrc::fail(VRC_ERR_INVALID, "%s: radius %d not in [0, 2^20]", what, radius);
     if (n == 0) return VRC_OK;
     if (!hits) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
@@ -579,7 +480,7 @@ extern "C" int vrc_volume_fill_spheres_at_hits(vrc_volume* v, uint64_t n, const 
     // the centres go through the staging block (n x 4 int32, then the hits themselves when they come from the host),
     // which an earlier call on another stream may still be reading
     if (e == hipSuccess) e = order_behind_edits(v, st);
-    if (e == hipSuccess) e = stage_reserve(v, (size_t)n * (mem == VRC_MEM_HOST ? 64u : 16u));
+    if (e == hipSuccess) e = reserve(v->d_stage, v->stage_cap, (size_t)n * (mem == VRC_MEM_HOST ? 64u : 16u));
     if (e != hipSuccess) return vrc::fail_hip(e, what);
     int32_t* d_centres = (int32_t*)v->d_stage;
     const vrc_hit* d_hits = hits;
@@ -598,7 +499,7 @@ extern "C" int vrc_volume_xor_mesh(vrc_volume* v, uint64_t n, const int32_t* tri
 {
     const char* what = "vrc_volume_xor_mesh";
     if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
-    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
+    if (const int rc = check_mem(what, mem)) return rc;
     if (n == 0) return VRC_OK;
     if (!tris) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
     if (n > 0x7fffffffull) return vrc::fail(VRC_ERR_INVALID, "%s: too many triangles for one launch", what);
@@ -624,7 +525,7 @@ extern "C" int vrc_volume_copy_region(vrc_volume* dst, vrc_volume* src, const ui
     const char* what = "vrc_volume_copy_region";
     if (!dst || !src || !src_lo || !size || !dst_lo) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
     if (src == dst) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
-    if (op != VRC_COPY_REPLACE && op != VRC_COPY_OR && op != VRC_COPY_ANDNOT) return vrc::fail(VRC_ERR_INVALID, "%s: bad op %d", what, op);
+    if (const int rc = check_op(what, op)) return rc;
     if (src->device != dst->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, src->device, dst->device);
     // the region clipped to both volumes, as the destination's voxel box [lo, hi) and the offset to the source
     const int64_t Ss = 1ll << src->depth, Sd = 1ll << dst->depth;
@@ -645,11 +546,7 @@ extern "C" int vrc_volume_copy_region(vrc_volume* dst, vrc_volume* src, const ui
     if (e == hipSuccess) e = order_behind_edits(src, st);
     if (e == hipSuccess) e = order_behind_edits(dst, st);
     if (e != hipSuccess) return vrc::fail_hip(e, what);
-    const uint64_t words = (uint64_t)(((hi[0] - 1u) >> 1) - (lo[0] >> 1) + 1u) * (((hi[1] - 1u) >> 1) - (lo[1] >> 1) + 1u) *
-                           (((((hi[2] - 1u) >> 1) - (lo[2] >> 1) + 3u) >> 2) + 1u);
-    uint64_t groups = (words + 255u) / 256u;
-    if (groups > 16384u) groups = 16384u;
-    hipLaunchKernelGGL(k_copy_region, dim3((uint32_t)groups), dim3(256), 0, st, dst->d_bricks, (uint32_t)Sd, (const uint8_t*)src->d_bricks, (uint32_t)Ss,
+    hipLaunchKernelGGL(k_copy_region, dim3(box_launch_groups(lo, hi)), dim3(256), 0, st, dst->d_bricks, (uint32_t)Sd, (const uint8_t*)src->d_bricks, (uint32_t)Ss,
                        lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], off[0], off[1], off[2], op);
     if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
     if ((e = finish(dst, VRC_MEM_DEVICE, st, true)) != hipSuccess) return vrc::fail_hip(e, what);
@@ -662,7 +559,7 @@ extern "C" int vrc_volume_stamp_affine(vrc_volume* dst, vrc_volume* src, const v
     const char* what = "vrc_volume_stamp_affine";
     if (!dst || !src || !map || !dst_lo || !dst_hi) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
     if (src == dst) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
-    if (op != VRC_COPY_REPLACE && op != VRC_COPY_OR && op != VRC_COPY_ANDNOT) return vrc::fail(VRC_ERR_INVALID, "%s: bad op %d", what, op);
+    if (const int rc = check_op(what, op)) return rc;
     if (map->reserved != 0) return vrc::fail(VRC_ERR_INVALID, "%s: reserved is %d, not 0", what, map->reserved);
     // the limits that keep s = m (2p + 1) + t below 2^41 and a word's deltas below 2^25
     for (int i = 0; i < 9; ++i)
@@ -670,13 +567,9 @@ extern "C" int vrc_volume_stamp_affine(vrc_volume* dst, vrc_volume* src, const v
     for (int a = 0; a < 3; ++a)
         if (map->t[a] > (1ll << 40) || map->t[a] < -(1ll << 40)) return vrc::fail(VRC_ERR_INVALID, "%s: t[%d] = %lld beyond +-2^40", what, a, (long long)map->t[a]);
     if (src->device != dst->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, src->device, dst->device);
-    const uint32_t Sd = 1u << dst->depth;
+    const uint32_t box[6] = {dst_lo[0], dst_lo[1], dst_lo[2], dst_hi[0], dst_hi[1], dst_hi[2]};
     uint32_t lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = dst_lo[a];
-        hi[a] = dst_hi[a] < Sd ? dst_hi[a] : Sd;
-        if (lo[a] >= hi[a]) return VRC_OK;                             // empty, inverted or wholly outside: nothing to write
-    }
+    if (!clip_box(box, 1u << dst->depth, lo, hi)) return VRC_OK;       // empty, inverted or wholly outside: nothing to write
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipSetDevice(dst->device);
     if (e == hipSuccess) e = order_behind_edits(src, st);
@@ -694,7 +587,7 @@ extern "C" int vrc_volume_clone(vrc_volume* src, vrc_volume** out)
     vrc_volume* v = nullptr;
     int rc = volume_new(src->depth, src->device, &v);
     if (rc) return rc;
-    hipError_t e = wait_for_edits(src);
+    hipError_t e = order_behind_edits(src, nullptr);
     if (e == hipSuccess) e = hipMemcpyAsync(v->d_bricks, src->d_bricks, src->n_bricks, hipMemcpyDeviceToDevice, nullptr);
     if (e == hipSuccess) e = hipMemcpyAsync(v->d_tex, src->d_tex, 1536, hipMemcpyDeviceToDevice, nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
@@ -707,57 +600,33 @@ extern "C" int vrc_volume_get_voxels(vrc_volume* v, uint64_t n, const uint32_t* 
 {
     const char* what = "vrc_volume_get_voxels";
     if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
-    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
+    if (const int rc = check_mem(what, mem)) return rc;
     if (n == 0) return VRC_OK;
     if (!xyz || !solid_out) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
     if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "%s: too many voxels for one launch", what);
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = order_behind_edits(v, st);
-    const uint32_t* d_xyz = xyz;
-    uint8_t* d_out = solid_out;
-    if (mem == VRC_MEM_HOST) {
-        if (e == hipSuccess) e = stage_reserve(v, (size_t)n * 13u);
-        d_xyz = v->d_stage;
-        d_out = (uint8_t*)v->d_stage + (size_t)n * 12u;
-        if (e == hipSuccess) e = hipMemcpyAsync(v->d_stage, xyz, (size_t)n * 12u, hipMemcpyHostToDevice, st);
-    }
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    hipLaunchKernelGGL(k_get_voxels, grid_for(n), dim3(256), 0, st, (const uint8_t*)v->d_bricks, 1u << v->depth, n, d_xyz, d_out);
-    e = hipGetLastError();
-    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipMemcpyAsync(solid_out, d_out, n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = finish(v, mem, st, false);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    return staged_call(what, v->device, v, xyz, (size_t)n * 12u, solid_out, (size_t)n, mem, st, [&](const void* d_xyz, void* d_out) {
+        hipLaunchKernelGGL(k_get_voxels, grid_for(n), dim3(256), 0, st, (const uint8_t*)v->d_bricks, 1u << v->depth, n, (const uint32_t*)d_xyz, (uint8_t*)d_out);
+        return hipSuccess;
+    });
 }
 
 extern "C" int vrc_volume_count_boxes(vrc_volume* v, uint64_t n, const uint32_t* lo_hi, uint64_t* counts, int mem, void* stream)
 {
     const char* what = "vrc_volume_count_boxes";
     if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
-    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
+    if (const int rc = check_mem(what, mem)) return rc;
     if (n == 0) return VRC_OK;
     if (!lo_hi || !counts) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
     if (n > 0x7fffffffull) return vrc::fail(VRC_ERR_INVALID, "%s: too many boxes for one launch", what);
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = order_behind_edits(v, st);
-    const uint32_t* d_boxes = lo_hi;
-    unsigned long long* d_counts = (unsigned long long*)counts;
-    if (mem == VRC_MEM_HOST) {
-        if (e == hipSuccess) e = stage_reserve(v, (size_t)n * 32u);
-        d_counts = (unsigned long long*)v->d_stage;
-        d_boxes = (const uint32_t*)((uint8_t*)v->d_stage + (size_t)n * 8u);
-        if (e == hipSuccess) e = hipMemcpyAsync((void*)d_boxes, lo_hi, (size_t)n * 24u, hipMemcpyHostToDevice, st);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, (size_t)n * 8u, st);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    hipLaunchKernelGGL(k_count_boxes, dim3((uint32_t)n, split_for(v, n)), dim3(256), 0, st, v->d_bricks, 1u << v->depth, d_boxes, d_counts);
-    e = hipGetLastError();
-    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipMemcpyAsync(counts, d_counts, (size_t)n * 8u, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = finish(v, mem, st, false);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    return staged_call(what, v->device, v, lo_hi, (size_t)n * 24u, counts, (size_t)n * 8u, mem, st, [&](const void* d_boxes, void* d_counts) {
+        const hipError_t e = hipMemsetAsync(d_counts, 0, (size_t)n * 8u, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_count_boxes, dim3((uint32_t)n, split_for(v, n)), dim3(256), 0, st, v->d_bricks, 1u << v->depth, (const uint32_t*)d_boxes,
+                           (unsigned long long*)d_counts);
+        return hipSuccess;
+    });
 }
 
 // the offsets block of the two surface calls, allocated by the first
@@ -773,7 +642,7 @@ extern "C" int vrc_volume_surface_count(vrc_volume* v, int closed, uint64_t coun
     if (!counts) return vrc::fail(VRC_ERR_INVALID, "%s: null counts", what);
     // the NULL stream, behind the last asynchronous edit (a device-memory extraction, which shares the block, included)
     hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = wait_for_edits(v);
+    if (e == hipSuccess) e = order_behind_edits(v, nullptr);
     if (e == hipSuccess) e = surface_reserve(v);
     if (e != hipSuccess) return vrc::fail_hip(e, what);
     vrc::surface_count_run(v->d_bricks, v->depth, closed, v->d_surface, nullptr);
@@ -791,7 +660,7 @@ extern "C" int vrc_volume_extract_surface(vrc_volume* v, int closed, int format,
     const char* what = "vrc_volume_extract_surface";
     if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
     if (format != VRC_SURFACE_FACES && format != VRC_SURFACE_TRIANGLES) return vrc::fail(VRC_ERR_INVALID, "%s: bad format %d", what, format);
-    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
+    if (const int rc = check_mem(what, mem)) return rc;
     if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
     const size_t record = format == VRC_SURFACE_FACES ? 16u : 72u;
     if (mem == VRC_MEM_DEVICE && capacity && ((uintptr_t)out & (format == VRC_SURFACE_FACES ? 15u : 3u)))
@@ -820,7 +689,7 @@ extern "C" int vrc_volume_extract_surface(vrc_volume* v, int closed, int format,
     // the offsets stay valid for every window: the call holds the stream until it returns
     const uint64_t want = first < T ? (capacity < T - first ? capacity : T - first) : 0u;
     const uint64_t window = want < (1ull << 20) ? want : (1ull << 20);
-    if (want && (e = stage_reserve(v, (size_t)window * record)) != hipSuccess) return vrc::fail_hip(e, what);
+    if (want && (e = reserve(v->d_stage, v->stage_cap, (size_t)window * record)) != hipSuccess) return vrc::fail_hip(e, what);
     for (uint64_t done = 0; done < want; done += window) {
         const uint64_t now = want - done < window ? want - done : window;
         vrc::surface_emit_run(v->d_bricks, v->depth, closed, format, first + done, now, v->d_stage, v->d_surface, st);
@@ -837,20 +706,15 @@ extern "C" int vrc_volume_flood(vrc_volume* region, vrc_volume* medium, int conn
     const char* what = "vrc_volume_flood";
     if (!region || !medium) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
     if (region == medium) return vrc::fail(VRC_ERR_INVALID, "%s: region and medium are the same volume", what);
-    if (connectivity != VRC_CONNECT_FACES && connectivity != VRC_CONNECT_ALL) return vrc::fail(VRC_ERR_INVALID, "%s: connectivity %d is neither 6 nor 26", what, connectivity);
-    if (through != VRC_FLOOD_SOLID && through != VRC_FLOOD_EMPTY) return vrc::fail(VRC_ERR_INVALID, "%s: bad through %d", what, through);
+    if (const int rc = check_connectivity(what, connectivity)) return rc;
+    if (const int rc = check_through(what, through)) return rc;
     if (region->depth != medium->depth) return vrc::fail(VRC_ERR_INVALID, "%s: volumes of depths %u and %u", what, region->depth, medium->depth);
     if (region->device != medium->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, region->device, medium->device);
     // the NULL stream, behind the last asynchronous edit of either volume, as commit / download are
     hipError_t e = hipSetDevice(region->device);
-    if (e == hipSuccess) e = wait_for_edits(region);
-    if (e == hipSuccess) e = wait_for_edits(medium);
-    const size_t need = vrc::flood_scratch_bytes(region->depth);
-    if (e == hipSuccess && region->flood_cap < need) {
-        if (region->d_flood) (void)hipFree(region->d_flood);
-        region->d_flood = nullptr; region->flood_cap = 0;
-        if ((e = hipMalloc((void**)&region->d_flood, need)) == hipSuccess) region->flood_cap = need;
-    }
+    if (e == hipSuccess) e = order_behind_edits(region, nullptr);
+    if (e == hipSuccess) e = order_behind_edits(medium, nullptr);
+    if (e == hipSuccess) e = reserve(region->d_flood, region->flood_cap, vrc::flood_scratch_bytes(region->depth));
     if (e != hipSuccess) return vrc::fail_hip(e, what);
     uint32_t sweeps = 0, converged = 0;
     e = vrc::flood_run(region->d_bricks, medium->d_bricks, region->depth, connectivity, through,
@@ -871,7 +735,7 @@ extern "C" int vrc_volume_commit(vrc_volume* v, vrc_scene** out, float* build_ms
 {
     if (!v || !out) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_commit: null argument");
     hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = wait_for_edits(v);
+    if (e == hipSuccess) e = order_behind_edits(v, nullptr);
     if (e != hipSuccess) return vrc::fail_hip(e, "vrc_volume_commit");
     vrc_scene* s = nullptr;
     const int rc = build_on_device(BrickVox{(const uint8_t*)v->d_bricks, 1u << (v->depth - 1u)}, v->depth, v->device, v->cu_count, &s, build_ms,
@@ -887,7 +751,7 @@ extern "C" int vrc_volume_download(vrc_volume* v, uint8_t* solid_host)
 {
     if (!v || !solid_host) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_download: null argument");
     hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = wait_for_edits(v);
+    if (e == hipSuccess) e = order_behind_edits(v, nullptr);
     const uint64_t S = 1ull << v->depth;
     uint32_t* d_dense = nullptr;
     if (e == hipSuccess) e = hipMalloc((void**)&d_dense, S * S * S);
@@ -913,7 +777,7 @@ extern "C" int vrc_volume_solid_count(vrc_volume* v, uint64_t* count)
 {
     if (!v || !count) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_solid_count: null argument");
     hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = wait_for_edits(v);
+    if (e == hipSuccess) e = order_behind_edits(v, nullptr);
     if (e == hipSuccess) e = hipMemsetAsync(v->d_count, 0, 8, nullptr);
     if (e == hipSuccess) {
         const uint64_t n_words = v->n_bricks / 4u;
@@ -926,268 +790,5 @@ extern "C" int vrc_volume_solid_count(vrc_volume* v, uint64_t* count)
     if (e == hipSuccess) e = hipMemcpy(&total, v->d_count, 8, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return vrc::fail_hip(e, "vrc_volume_solid_count");
     *count = total;
-    return VRC_OK;
-}
-
-// ---- connected components --------------------------------------------------
-
-// A snapshot that owns its memory and is never written after vrc_volume_label_components returns: no event, no scratch.
-struct vrc_labels {
-    int device = 0;
-    uint32_t depth = 0;
-    uint64_t count = 0;
-    uint32_t* d_ids = nullptr;            // 8^depth ids, indexed by key
-    vrc_component* d_records = nullptr;   // count records, nullptr when count == 0
-};
-
-extern "C" int vrc_volume_label_components(vrc_volume* medium, int connectivity, int through, vrc_labels** out, uint64_t* n_components)
-{
-    const char* what = "vrc_volume_label_components";
-    if (!medium || !out) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
-    if (connectivity != VRC_CONNECT_FACES && connectivity != VRC_CONNECT_ALL) return vrc::fail(VRC_ERR_INVALID, "%s: connectivity %d is neither 6 nor 26", what, connectivity);
-    if (through != VRC_FLOOD_SOLID && through != VRC_FLOOD_EMPTY) return vrc::fail(VRC_ERR_INVALID, "%s: bad through %d", what, through);
-    vrc_labels* l = new (std::nothrow) vrc_labels();
-    if (!l) return vrc::fail(VRC_ERR_OOM, "out of host memory");
-    l->device = medium->device; l->depth = medium->depth;
-    // the NULL stream, behind the last asynchronous edit of the medium, as commit / download are
-    uint32_t* d_scratch = nullptr;
-    hipError_t e = hipSetDevice(medium->device);
-    if (e == hipSuccess) e = wait_for_edits(medium);
-    if (e == hipSuccess) e = hipMalloc((void**)&l->d_ids, (size_t)4u << (3u * l->depth));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_scratch, vrc::components_scratch_bytes(l->depth));
-    uint32_t C = 0;
-    if (e == hipSuccess) {
-        vrc::components_roots_run(medium->d_bricks, l->depth, connectivity, through, l->d_ids, d_scratch, nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(&C, vrc::components_total_slot(d_scratch, l->depth), 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && C) e = hipMalloc((void**)&l->d_records, (size_t)C * sizeof(vrc_component));
-    if (e == hipSuccess && C) {
-        vrc::components_ids_run(l->depth, l->d_ids, d_scratch, l->d_records, nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (d_scratch) (void)hipFree(d_scratch);
-    if (e != hipSuccess) {
-        (void)vrc_labels_destroy(l);
-        return vrc::fail_hip(e, what);
-    }
-    l->count = C;
-    *out = l;
-    if (n_components) *n_components = C;
-    return VRC_OK;
-}
-
-extern "C" int vrc_labels_destroy(vrc_labels* l)
-{
-    if (!l) return VRC_OK;
-    (void)hipSetDevice(l->device);
-    (void)hipDeviceSynchronize();       // device-memory calls may still be reading it on a caller's stream
-    if (l->d_ids) (void)hipFree(l->d_ids);
-    if (l->d_records) (void)hipFree(l->d_records);
-    delete l;
-    return VRC_OK;
-}
-
-extern "C" uint64_t vrc_labels_count(const vrc_labels* l) { return l ? l->count : 0; }
-extern "C" uint32_t vrc_labels_depth(const vrc_labels* l) { return l ? l->depth : 0; }
-extern "C" uint64_t vrc_labels_bytes(const vrc_labels* l) { return l ? ((uint64_t)4u << (3u * l->depth)) + l->count * sizeof(vrc_component) : 0; }
-
-extern "C" int vrc_labels_components(const vrc_labels* l, uint64_t first, uint64_t capacity, vrc_component* out, int mem, void* stream)
-{
-    const char* what = "vrc_labels_components";
-    if (!l) return vrc::fail(VRC_ERR_INVALID, "%s: null labels", what);
-    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
-    if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
-    const uint64_t want = first < l->count ? (capacity < l->count - first ? capacity : l->count - first) : 0u;
-    if (!want) return VRC_OK;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(l->device);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(out, l->d_records + first, (size_t)want * sizeof(vrc_component), mem == VRC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
-}
-
-extern "C" int vrc_labels_at(const vrc_labels* l, uint64_t n, const uint32_t* xyz, uint32_t* ids, int mem, void* stream)
-{
-    const char* what = "vrc_labels_at";
-    if (!l) return vrc::fail(VRC_ERR_INVALID, "%s: null labels", what);
-    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
-    if (n == 0) return VRC_OK;
-    if (!xyz || !ids) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
-    if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "%s: too many voxels for one launch", what);
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(l->device);
-    const uint32_t* d_xyz = xyz;
-    uint32_t* d_ids = ids;
-    uint32_t* d_stage = nullptr;          // the snapshot keeps no scratch: a host-memory call stages in a block of its own
-    if (mem == VRC_MEM_HOST) {
-        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, (size_t)n * 16u);
-        d_xyz = d_stage;
-        d_ids = d_stage + (size_t)n * 3u;
-        if (e == hipSuccess) e = hipMemcpyAsync(d_stage, xyz, (size_t)n * 12u, hipMemcpyHostToDevice, st);
-    }
-    if (e == hipSuccess) {
-        vrc::components_at_run(l->d_ids, l->depth, n, d_xyz, d_ids, st);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipMemcpyAsync(ids, d_ids, (size_t)n * 4u, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipStreamSynchronize(st);
-    if (d_stage) (void)hipFree(d_stage);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
-}
-
-extern "C" int vrc_labels_select(const vrc_labels* l, const uint8_t* keep, vrc_volume* dst, int op, int mem, void* stream)
-{
-    const char* what = "vrc_labels_select";
-    if (!l || !dst) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
-    if (op != VRC_COPY_REPLACE && op != VRC_COPY_OR && op != VRC_COPY_ANDNOT) return vrc::fail(VRC_ERR_INVALID, "%s: bad op %d", what, op);
-    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
-    if (dst->depth != l->depth) return vrc::fail(VRC_ERR_INVALID, "%s: labels of depth %u, volume of depth %u", what, l->depth, dst->depth);
-    if (dst->device != l->device) return vrc::fail(VRC_ERR_INVALID, "%s: labels on device %d, volume on device %d", what, l->device, dst->device);
-    if (!keep && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null keep with %llu components", what, (unsigned long long)l->count);
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(l->device);
-    if (e == hipSuccess) e = order_behind_edits(dst, st);
-    const uint8_t* d_keep = keep;
-    uint8_t* d_stage = nullptr;
-    if (mem == VRC_MEM_HOST && l->count) {
-        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, (size_t)l->count);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_stage, keep, (size_t)l->count, hipMemcpyHostToDevice, st);
-        d_keep = d_stage;
-    }
-    if (e == hipSuccess) {
-        vrc::components_select_run(l->d_ids, l->depth, d_keep, dst->d_bricks, op, st);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = finish(dst, mem, st, true);
-    if (d_stage) (void)hipFree(d_stage);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
-}
-
-// ---- distance field ----------------------------------------------------------
-
-// A snapshot like vrc_labels: it owns its memory and is never written after vrc_volume_distance_field returns.
-struct vrc_distance {
-    int device = 0;
-    uint32_t depth = 0;
-    uint32_t* d_field = nullptr;          // 8^depth squared distances, [(x*S + y)*S + z]
-};
-
-extern "C" int vrc_volume_distance_field(vrc_volume* medium, int to, int outside, vrc_distance** out, vrc_distance_stats* stats)
-{
-    const char* what = "vrc_volume_distance_field";
-    if (!medium || !out) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
-    if (to != VRC_FLOOD_SOLID && to != VRC_FLOOD_EMPTY) return vrc::fail(VRC_ERR_INVALID, "%s: bad to %d", what, to);
-    if (medium->depth < 2 || medium->depth > 10) return vrc::fail(VRC_ERR_INVALID, "%s: depth %u not in [2,10]", what, medium->depth);
-    vrc_distance* d = new (std::nothrow) vrc_distance();
-    if (!d) return vrc::fail(VRC_ERR_OOM, "out of host memory");
-    d->device = medium->device; d->depth = medium->depth;
-    // the NULL stream, behind the last asynchronous edit of the medium, as commit / download are
-    uint32_t* d_scratch = nullptr;
-    hipError_t e = hipSetDevice(medium->device);
-    if (e == hipSuccess) e = wait_for_edits(medium);
-    if (e == hipSuccess) e = hipMalloc((void**)&d->d_field, (size_t)4u << (3u * d->depth));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_scratch, vrc::distance_scratch_bytes(d->depth, medium->cu_count));
-    if (e == hipSuccess) {
-        vrc::distance_run(medium->d_bricks, d->depth, to, outside, medium->cu_count, d->d_field, d_scratch, nullptr);
-        e = hipGetLastError();
-    }
-    unsigned long long host[2] = {0ull, 0ull};
-    if (e == hipSuccess) e = hipMemcpy(host, vrc::distance_stats_slots(d_scratch), sizeof host, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (d_scratch) (void)hipFree(d_scratch);
-    if (e != hipSuccess) {
-        (void)vrc_distance_destroy(d);
-        return vrc::fail_hip(e, what);
-    }
-    if (stats) {
-        stats->features = host[0];
-        stats->max_d2 = 0u; stats->argmax[0] = stats->argmax[1] = stats->argmax[2] = 0u; stats->reserved = 0u;
-        if (host[1]) {
-            const uint32_t index = ~(uint32_t)host[1], mask = (1u << d->depth) - 1u;
-            stats->max_d2 = (uint32_t)(host[1] >> 32);
-            stats->argmax[0] = index >> (2u * d->depth); stats->argmax[1] = (index >> d->depth) & mask; stats->argmax[2] = index & mask;
-        }
-    }
-    *out = d;
-    return VRC_OK;
-}
-
-extern "C" int vrc_distance_destroy(vrc_distance* d)
-{
-    if (!d) return VRC_OK;
-    (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();       // device-memory calls may still be reading it on a caller's stream
-    if (d->d_field) (void)hipFree(d->d_field);
-    delete d;
-    return VRC_OK;
-}
-
-extern "C" uint32_t vrc_distance_depth(const vrc_distance* d) { return d ? d->depth : 0; }
-extern "C" uint64_t vrc_distance_bytes(const vrc_distance* d) { return d ? (uint64_t)4u << (3u * d->depth) : 0; }
-extern "C" const uint32_t* vrc_distance_data(const vrc_distance* d) { return d ? d->d_field : nullptr; }
-
-extern "C" int vrc_distance_at(const vrc_distance* d, uint64_t n, const uint32_t* xyz, uint32_t* d2, int mem, void* stream)
-{
-    const char* what = "vrc_distance_at";
-    if (!d) return vrc::fail(VRC_ERR_INVALID, "%s: null distance field", what);
-    if (mem != VRC_MEM_HOST && mem != VRC_MEM_DEVICE) return vrc::fail(VRC_ERR_INVALID, "%s: bad mem kind %d", what, mem);
-    if (n == 0) return VRC_OK;
-    if (!xyz || !d2) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
-    if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "%s: too many voxels for one launch", what);
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(d->device);
-    const uint32_t* d_xyz = xyz;
-    uint32_t* d_d2 = d2;
-    uint32_t* d_stage = nullptr;          // the snapshot keeps no scratch: a host-memory call stages in a block of its own
-    if (mem == VRC_MEM_HOST) {
-        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, (size_t)n * 16u);
-        d_xyz = d_stage;
-        d_d2 = d_stage + (size_t)n * 3u;
-        if (e == hipSuccess) e = hipMemcpyAsync(d_stage, xyz, (size_t)n * 12u, hipMemcpyHostToDevice, st);
-    }
-    if (e == hipSuccess) {
-        vrc::distance_at_run(d->d_field, d->depth, n, d_xyz, d_d2, st);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipMemcpyAsync(d2, d_d2, (size_t)n * 4u, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipStreamSynchronize(st);
-    if (d_stage) (void)hipFree(d_stage);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
-}
-
-extern "C" int vrc_distance_download(const vrc_distance* d, uint32_t* d2_host)
-{
-    const char* what = "vrc_distance_download";
-    if (!d || !d2_host) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
-    hipError_t e = hipSetDevice(d->device);
-    if (e == hipSuccess) e = hipMemcpy(d2_host, d->d_field, (size_t)4u << (3u * d->depth), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
-}
-
-extern "C" int vrc_distance_select(const vrc_distance* d, uint32_t lo, uint32_t hi, vrc_volume* dst, int op, void* stream)
-{
-    const char* what = "vrc_distance_select";
-    if (!d || !dst) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
-    if (op != VRC_COPY_REPLACE && op != VRC_COPY_OR && op != VRC_COPY_ANDNOT) return vrc::fail(VRC_ERR_INVALID, "%s: bad op %d", what, op);
-    if (lo > hi) return vrc::fail(VRC_ERR_INVALID, "%s: lo %u above hi %u", what, lo, hi);
-    if (dst->depth != d->depth) return vrc::fail(VRC_ERR_INVALID, "%s: field of depth %u, volume of depth %u", what, d->depth, dst->depth);
-    if (dst->device != d->device) return vrc::fail(VRC_ERR_INVALID, "%s: field on device %d, volume on device %d", what, d->device, dst->device);
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(d->device);
-    if (e == hipSuccess) e = order_behind_edits(dst, st);
-    if (e == hipSuccess) {
-        vrc::distance_select_run(d->d_field, d->depth, lo, hi, dst->d_bricks, op, st);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
     return VRC_OK;
 }
