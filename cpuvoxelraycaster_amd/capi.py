@@ -184,6 +184,8 @@ SYMBOLS = {
     "vrc_volume_xor_mesh": (_int, [_vp, _u64, _vp, _int, _vp]),
     "vrc_volume_surface_count": (_int, [_vp, _int, _vp]),
     "vrc_volume_extract_surface": (_int, [_vp, _int, _int, _u64, _u64, _vp, _vp, _int, _vp]),
+    "vrc_rect_count": (_int, [_vp, _int, _vp]),
+    "vrc_extract_rects": (_int, [_vp, _int, _int, _u64, _u64, _vp, _vp, _int, _vp]),
     "vrc_volume_edit_scratch_bytes": (_int, [_vp, C.POINTER(_u64)]),
     "vrc_renderer_set_scene": (_int, [_vp, _vp]),
     "vrc_hit_to_voxel": (_int, [_u32, _vp, _vp, _vp, C.POINTER(_int)]),

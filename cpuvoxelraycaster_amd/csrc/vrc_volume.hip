@@ -12,7 +12,7 @@
 // Here: the volume's life cycle, the edits and queries on the occupancy with their ordering and scratch blocks, and
 // commit / download.  Boxes, spheres, spheres at the hits of a ray batch, region copies and the two queries have their
 // kernels here, over the box-of-words layout of vrc_box_words.h.  The other features keep theirs in files of their own:
-// vrc_flood.hip, vrc_voxelize.hip, vrc_surface.hip, vrc_stamp.hip.  The snapshots taken from a volume (labels, distance
+// vrc_flood.hip, vrc_voxelize.hip, vrc_surface.hip, vrc_rects.hip, vrc_stamp.hip.  The snapshots taken from a volume (labels, distance
 // fields) are in vrc_snapshots.hip; what the entry points of both files share is in vrc_volume_state.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,6 +25,7 @@
 #include "vrc_flood.h"
 #include "vrc_group.h"
 #include "vrc_stamp.h"
+#include "vrc_rects.h"
 #include "vrc_surface.h"
 #include "vrc_volume_state.h"
 #include "vrc_voxelize.h"
@@ -318,6 +319,7 @@ void volume_free(vrc_volume* v)
     if (v->d_flood) (void)hipFree(v->d_flood);
     if (v->d_marks) (void)hipFree(v->d_marks);
     if (v->d_surface) (void)hipFree(v->d_surface);
+    if (v->d_rects) (void)hipFree(v->d_rects);
     v->grids.release();
     delete v;
 }
@@ -701,6 +703,80 @@ extern "C" int vrc_volume_extract_surface(vrc_volume* v, int closed, int format,
     return VRC_OK;
 }
 
+// the block of the two rectangle calls (offsets, totals, row fields), allocated by the first
+static hipError_t rects_reserve(vrc_volume* v)
+{
+    return v->d_rects ? hipSuccess : hipMalloc((void**)&v->d_rects, vrc::rect_scratch_bytes(v->depth));
+}
+
+extern "C" int vrc_rect_count(vrc_volume* v, int closed, uint64_t counts[6])
+{
+    const char* what = "vrc_rect_count";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (!counts) return vrc::fail(VRC_ERR_INVALID, "%s: null counts", what);
+    // the NULL stream, behind the last asynchronous edit (a device-memory extraction, which shares the block, included)
+    hipError_t e = hipSetDevice(v->device);
+    if (e == hipSuccess) e = order_behind_edits(v, nullptr);
+    if (e == hipSuccess) e = rects_reserve(v);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    vrc::rect_rows_run(v->d_bricks, v->depth, v->d_rects, nullptr);
+    vrc::rect_count_run(v->depth, closed, v->d_rects, nullptr);
+    e = hipGetLastError();
+    unsigned long long host[6];
+    if (e == hipSuccess) e = hipMemcpy(host, vrc::rect_direction_slots(v->d_rects, v->depth), sizeof host, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    for (int d = 0; d < 6; ++d) counts[d] = host[d];
+    return VRC_OK;
+}
+
+extern "C" int vrc_extract_rects(vrc_volume* v, int closed, int format, uint64_t first, uint64_t capacity, void* out, uint64_t* total, int mem,
+                                        void* stream)
+{
+    const char* what = "vrc_extract_rects";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (format != VRC_SURFACE_FACES && format != VRC_SURFACE_TRIANGLES) return vrc::fail(VRC_ERR_INVALID, "%s: bad format %d", what, format);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
+    const size_t record = format == VRC_SURFACE_FACES ? 16u : 72u;
+    if (mem == VRC_MEM_DEVICE && capacity && ((uintptr_t)out & (format == VRC_SURFACE_FACES ? 15u : 3u)))
+        return vrc::fail(VRC_ERR_INVALID, "%s: device buffer %p is not aligned to %d bytes", what, out, format == VRC_SURFACE_FACES ? 16 : 4);
+    hipStream_t st = (hipStream_t)stream;
+    // behind the last asynchronous edit whatever the memory kind: the block is shared by every call
+    hipError_t e = hipSetDevice(v->device);
+    if (e == hipSuccess) e = order_behind_edits(v, st);
+    if (e == hipSuccess) e = rects_reserve(v);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    vrc::rect_rows_run(v->d_bricks, v->depth, v->d_rects, st);
+    if (mem == VRC_MEM_DEVICE) {
+        vrc::rect_offsets_run(v->depth, closed, v->d_rects, (unsigned long long*)total, st);
+        if (capacity) vrc::rect_emit_run(v->depth, closed, format, first, capacity, out, v->d_rects, st);
+        if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
+        // recorded as an edit: the next call, on whatever stream, must not rewrite the block under this one
+        if ((e = finish(v, mem, st, true)) != hipSuccess) return vrc::fail_hip(e, what);
+        return VRC_OK;
+    }
+    vrc::rect_offsets_run(v->depth, closed, v->d_rects, nullptr, st);
+    e = hipGetLastError();
+    unsigned long long T = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&T, vrc::rect_total_slot(v->d_rects, v->depth), 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    if (total) *total = T;
+    // the row fields and the offsets stay valid for every window: the call holds the stream until it returns
+    const uint64_t want = first < T ? (capacity < T - first ? capacity : T - first) : 0u;
+    const uint64_t window = want < (1ull << 20) ? want : (1ull << 20);
+    if (want && (e = reserve(v->d_stage, v->stage_cap, (size_t)window * record)) != hipSuccess) return vrc::fail_hip(e, what);
+    for (uint64_t done = 0; done < want; done += window) {
+        const uint64_t now = want - done < window ? want - done : window;
+        vrc::rect_emit_run(v->depth, closed, format, first + done, now, v->d_stage, v->d_rects, st);
+        if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
+        if ((e = hipMemcpyAsync((uint8_t*)out + done * record, v->d_stage, (size_t)now * record, hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return vrc::fail_hip(e, what);
+    }
+    if ((e = finish(v, mem, st, false)) != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
 extern "C" int vrc_volume_flood(vrc_volume* region, vrc_volume* medium, int connectivity, int through, uint32_t max_sweeps, vrc_flood_stats* stats)
 {
     const char* what = "vrc_volume_flood";
@@ -769,7 +845,7 @@ extern "C" int vrc_volume_edit_scratch_bytes(const vrc_volume* v, uint64_t* byte
 {
     if (!v || !bytes) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_edit_scratch_bytes: null argument");
     *bytes = (uint64_t)v->stage_cap + (uint64_t)v->flood_cap + (v->d_marks ? (uint64_t)vrc::voxelize_scratch_bytes(v->depth) : 0u) +
-             (v->d_surface ? (uint64_t)vrc::surface_scratch_bytes(v->depth) : 0u);
+             (v->d_surface ? (uint64_t)vrc::surface_scratch_bytes(v->depth) : 0u) + (v->d_rects ? (uint64_t)vrc::rect_scratch_bytes(v->depth) : 0u);
     return VRC_OK;
 }
 

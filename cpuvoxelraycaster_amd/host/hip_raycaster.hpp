@@ -570,22 +570,56 @@ public:
         check(vrc_volume_extract_surface(v_, closed ? 1 : 0, format, first, capacity, out_dev, total_dev, VRC_MEM_DEVICE, stream),
               "vrc_volume_extract_surface");
     }
-    // Wavefront OBJ of the exposed faces: one `v` line per distinct corner (voxel units), one `f` line per face with four
-    // 1-based indices, wound outwards.  Returns the number of faces.
-    uint64_t toObj(const std::string& path, bool closed = true)
+    // The same surface with coplanar faces merged into rectangles (include/vrc.h: vrc_extract_rects), in the order
+    // (d, c_a, s0, r0).  counts[d]: rectangles per direction.
+    std::vector<uint64_t> rectCount(bool closed = true)
     {
-        const std::vector<uint32_t> faces = surfaceFaces(closed);
+        flush();
+        std::vector<uint64_t> counts(6);
+        check(vrc_rect_count(v_, closed ? 1 : 0, counts.data()), "vrc_rect_count");
+        return counts;
+    }
+    // n x 4: x y z of the rectangle's voxel of smallest coordinates and d | (nr - 1) << 8 | (ns - 1) << 20
+    std::vector<uint32_t> surfaceRects(bool closed = true, uint64_t first = 0, uint64_t capacity = ~0ull)
+    {
+        return extractRects<uint32_t>(VRC_SURFACE_FACES, 4, closed, first, capacity);
+    }
+    // 2n x 9: two triangles per rectangle in xorMesh's fixed point, wound outwards
+    std::vector<int32_t> rectTriangles(bool closed = true, uint64_t first = 0, uint64_t capacity = ~0ull)
+    {
+        return extractRects<int32_t>(VRC_SURFACE_TRIANGLES, 18, closed, first, capacity);
+    }
+    // the same into device memory, asynchronous on `stream`; total_dev (may be null): a device uint64_t that receives the
+    // number of rectangles in stream order
+    void extractRectsDevice(int format, uint64_t first, uint64_t capacity, void* out_dev, uint64_t* total_dev, bool closed = true,
+                            void* stream = nullptr)
+    {
+        flush();
+        check(vrc_extract_rects(v_, closed ? 1 : 0, format, first, capacity, out_dev, total_dev, VRC_MEM_DEVICE, stream),
+              "vrc_extract_rects");
+    }
+    // Wavefront OBJ of the exposed faces: one `v` line per distinct corner (voxel units), one `f` line per face with four
+    // 1-based indices, wound outwards.  merged: one `f` line per rectangle of surfaceRects instead; rectangles share the
+    // corners they have in common.  Returns the number of `f` lines.
+    uint64_t toObj(const std::string& path, bool closed = true, bool merged = false)
+    {
+        const std::vector<uint32_t> faces = merged ? surfaceRects(closed) : surfaceFaces(closed);
         const uint64_t n = faces.size() / 4, side = (1ull << depth()) + 1;
         std::vector<uint64_t> corner(4 * n);          // (x * side + y) * side + z of each face's corners, in winding order
         for (uint64_t i = 0; i < n; ++i) {
-            const uint32_t d = faces[4 * i + 3], a = d >> 1, s = d & 1, u = (a + 1) % 3, w = (a + 2) % 3;
+            const uint32_t d = faces[4 * i + 3] & 0xffu, a = d >> 1, s = d & 1, u = (a + 1) % 3, w = (a + 2) % 3;
+            // the extents: 1 along a, nr along the run axis (z, or y for the z faces), ns along the stack axis
+            uint32_t e[3] = {1, 1, 1};
+            const uint32_t r = a == 2 ? 1 : 2;
+            e[r] = ((faces[4 * i + 3] >> 8) & 0x3ffu) + 1;
+            e[3 - a - r] = ((faces[4 * i + 3] >> 20) & 0x3ffu) + 1;
             static const uint32_t du[4] = {0, 1, 1, 0}, dw[4] = {0, 0, 1, 1};
             for (uint32_t k = 0; k < 4; ++k) {
                 const uint32_t j = s ? k : (4 - k) % 4;      // q0 q1 q2 q3 towards +axis, q0 q3 q2 q1 towards -axis
                 uint64_t q[3];
                 q[a] = faces[4 * i + a] + s;
-                q[u] = faces[4 * i + u] + du[j];
-                q[w] = faces[4 * i + w] + dw[j];
+                q[u] = faces[4 * i + u] + du[j] * e[u];
+                q[w] = faces[4 * i + w] + dw[j] * e[w];
                 corner[4 * i + k] = (q[0] * side + q[1]) * side + q[2];
             }
         }
@@ -638,6 +672,17 @@ private:
         const uint64_t n = first < total ? std::min(capacity, total - first) : 0;
         std::vector<T> out((size_t)n * per_face);
         if (n) check(vrc_volume_extract_surface(v_, closed ? 1 : 0, format, first, n, out.data(), nullptr, VRC_MEM_HOST, nullptr), "vrc_volume_extract_surface");
+        return out;
+    }
+    template <class T>
+    std::vector<T> extractRects(int format, size_t per_rect, bool closed, uint64_t first, uint64_t capacity)
+    {
+        flush();
+        uint64_t total = 0;
+        check(vrc_extract_rects(v_, closed ? 1 : 0, format, 0, 0, nullptr, &total, VRC_MEM_HOST, nullptr), "vrc_extract_rects");
+        const uint64_t n = first < total ? std::min(capacity, total - first) : 0;
+        std::vector<T> out((size_t)n * per_rect);
+        if (n) check(vrc_extract_rects(v_, closed ? 1 : 0, format, first, n, out.data(), nullptr, VRC_MEM_HOST, nullptr), "vrc_extract_rects");
         return out;
     }
     static std::vector<int32_t> meshSoup(const std::vector<int64_t>& fixed, const std::vector<uint32_t>& faces, const int64_t origin[3])

@@ -503,29 +503,86 @@ class VoxelVolume:
         check(capi.load().vrc_volume_extract_surface(self._h, int(bool(closed)), int(format), int(first), int(capacity), ptr(out_ptr), ptr(total_ptr),
                                                      capi.VRC_MEM_DEVICE, ptr(stream)))
 
+    # ---- the same surface with coplanar faces merged into rectangles (include/vrc.h: vrc_extract_rects) ----
+
+    def rectCount(self, closed=True):
+        """(6,) uint64: rectangles per direction d = 2 * axis + side: the exposed faces of surfaceCount merged by the
+        identical-run rule of include/vrc.h.  Synchronous."""
+        out = np.zeros(6, np.uint64)
+        check(capi.load().vrc_rect_count(self._h, int(bool(closed)), ptr(out)))
+        return out
+
+    def _rects(self, fmt, dtype, per_rect, closed, first, capacity):
+        L, closed = capi.load(), int(bool(closed))
+        total = C.c_uint64()
+        check(L.vrc_extract_rects(self._h, closed, fmt, 0, 0, None, C.byref(total), capi.VRC_MEM_HOST, None))
+        first = int(first)
+        n = max(0, total.value - first)
+        if capacity is not None:
+            n = min(n, int(capacity))
+        out = np.zeros((n, per_rect), dtype)
+        for at in range(0, n, self.SURFACE_WINDOW):
+            part = out[at:at + self.SURFACE_WINDOW]
+            check(L.vrc_extract_rects(self._h, closed, fmt, first + at, part.shape[0], ptr(part), None, capi.VRC_MEM_HOST, None))
+        return out
+
+    def surfaceRects(self, closed=True, first=0, capacity=None):
+        """(n, 4) uint32 x y z w: the rectangles [first, first + capacity) of the order (d, c_a, s0, r0), each named by its
+        voxel of smallest coordinates and w = d | (nr - 1) << 8 | (ns - 1) << 20 (unpackRects takes it apart).
+        capacity=None fetches everything from `first` on in bounded windows.  Synchronous."""
+        return self._rects(capi.VRC_SURFACE_FACES, np.uint32, 4, closed, first, capacity)
+
     @staticmethod
-    def meshFromFaces(faces):
+    def unpackRects(records):
+        """(n, 4) packed rectangle records -> (n, 6) int64 x y z d nr ns: nr the extent along the run axis, ns along the
+        stack axis (x faces: y stacks, z runs; y faces: x stacks, z runs; z faces: x stacks, y runs)"""
+        r = np.asarray(records, np.int64).reshape(-1, 4)
+        w = r[:, 3]
+        return np.stack([r[:, 0], r[:, 1], r[:, 2], w & 0xff, ((w >> 8) & 0x3ff) + 1, ((w >> 20) & 0x3ff) + 1], axis=1)
+
+    def rectTriangles(self, closed=True, first=0, capacity=None):
+        """(2n, 9) int32: two triangles per rectangle of the same window in xorMesh's fixed point, wound counter-clockwise
+        seen from outside.  With closed=True xorMesh of them into an empty volume of the same depth gives this volume's
+        voxel set back, as surfaceTriangles' do."""
+        return self._rects(capi.VRC_SURFACE_TRIANGLES, np.int32, 18, closed, first, capacity).reshape(-1, 9)
+
+    def extractRectsDevice(self, format, first, capacity, out_ptr, total_ptr, closed=True, stream=None):
+        """the same window into device memory (16 bytes per rectangle, or 72 for its two triangles), asynchronous on
+        `stream`; total_ptr (may be None): a device uint64 that receives the number of rectangles in stream order"""
+        check(capi.load().vrc_extract_rects(self._h, int(bool(closed)), int(format), int(first), int(capacity), ptr(out_ptr), ptr(total_ptr),
+                                                   capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    @staticmethod
+    def meshFromFaces(faces, merged=False):
         """(n, 4) x y z d face records -> (verts (m, 3) int32 in voxel units, quads (n, 4) int64 indices): every distinct
-        corner once, each quad wound counter-clockwise seen from outside.  Host arithmetic."""
+        corner once, each quad wound counter-clockwise seen from outside.  merged=True takes the packed rectangle records
+        of surfaceRects instead and gives one quad per rectangle; rectangles share the corners they have in common.  Host
+        arithmetic."""
         f = np.asarray(faces, np.int64).reshape(-1, 4)
         n = f.shape[0]
-        d = f[:, 3]
+        d = f[:, 3] & 0xff if merged else f[:, 3]
         a, s = d >> 1, d & 1
         u, w = (a + 1) % 3, (a + 2) % 3
         rows = np.arange(n)
+        extent = np.ones((n, 3), np.int64)
+        if merged:
+            r = np.where(a == 0, 2, np.where(a == 1, 2, 1))          # the run axis; the stack axis is the one left over
+            extent[rows, r] = ((f[:, 3] >> 8) & 0x3ff) + 1
+            extent[rows, 3 - a - r] = ((f[:, 3] >> 20) & 0x3ff) + 1
         du, dw = np.array([0, 1, 1, 0]), np.array([0, 0, 1, 1])
         corners = np.zeros((n, 4, 3), np.int64)
         for k in range(4):
             j = np.where(s == 1, k, (4 - k) % 4)         # q0 q1 q2 q3 towards +axis, q0 q3 q2 q1 towards -axis
             corners[rows, k, a] = f[rows, a] + s
-            corners[rows, k, u] = f[rows, u] + du[j]
-            corners[rows, k, w] = f[rows, w] + dw[j]
+            corners[rows, k, u] = f[rows, u] + du[j] * extent[rows, u]
+            corners[rows, k, w] = f[rows, w] + dw[j] * extent[rows, w]
         verts, index = np.unique(corners.reshape(-1, 3), axis=0, return_inverse=True)
         return verts.astype(np.int32).reshape(-1, 3), np.asarray(index, np.int64).reshape(n, 4)
 
-    def toMesh(self, closed=True):
-        """The exposed faces as an indexed quad mesh (verts, quads), see meshFromFaces; scenes.write_obj writes it out."""
-        return self.meshFromFaces(self.surfaceFaces(closed))
+    def toMesh(self, closed=True, merged=False):
+        """The exposed faces as an indexed quad mesh (verts, quads), see meshFromFaces; merged=True gives one quad per
+        rectangle of surfaceRects.  scenes.write_obj writes it out."""
+        return self.meshFromFaces(self.surfaceRects(closed) if merged else self.surfaceFaces(closed), merged)
 
     def commit(self, textures=None):
         """A NEW LSVO of the current occupancy (build_ms = device time of the sweeps); the volume stays editable."""
@@ -548,7 +605,7 @@ class VoxelVolume:
         return int(n.value)
 
     def editScratchBytes(self):
-        """device bytes in the scratch blocks of the edit calls (staging, flood, mark field, surface offsets); include/vrc.h"""
+        """device bytes in the scratch blocks of the edit calls (staging, flood, mark field, surface offsets, rectangle block); include/vrc.h"""
         n = C.c_uint64()
         check(capi.load().vrc_volume_edit_scratch_bytes(self._h, C.byref(n)))
         return int(n.value)

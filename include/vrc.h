@@ -289,6 +289,53 @@ int vrc_volume_xor_mesh(vrc_volume *v, uint64_t n_tris, const int32_t *tris, int
 int vrc_volume_surface_count(vrc_volume *v, int closed, uint64_t counts[6]);
 int vrc_volume_extract_surface(vrc_volume *v, int closed, int format, uint64_t first, uint64_t capacity,
                                void *out, uint64_t *total, int mem, void *stream);
+/* The same surface with coplanar faces merged into rectangles: what an exporter, an OBJ writer or a physics engine wants,
+ * fewer records than faces (3.2 times fewer on the 512^3 terrain, 1.5 times on a dense random field, 6 for any box).  The rule is exact in integers, free of any sweep order and has a unique result.
+ * The faces are vrc_volume_extract_surface's, `closed` included.  For direction d with axis a call the other two axes
+ * s < r: s the stack axis, r the run axis (a = x: s = y, r = z; a = y: s = x, r = z; a = z: s = x, r = y).  A row is the set
+ * of cells of one (d, c_a, c_s), indexed by c_r.  A run [r0, r1) is a maximal set of consecutive c_r of a row whose face d
+ * is exposed.  A rectangle is a maximal set of consecutive rows c_s = s0 .. s0 + ns - 1 of one plane (d, c_a) that all hold
+ * the IDENTICAL run [r0, r1), maximal in each of them (a row whose run contains or overlaps it does not join): a run starts
+ * a rectangle iff row c_s - 1 does not hold the identical run, and its height is the number of following rows that do.
+ * Every exposed face lies in exactly one rectangle and a rectangle holds exposed faces of one direction and plane only.
+ * This is deliberately not greedy meshing, which cuts runs and depends on the order of its sweep.
+ *   Order: by (d, c_a, s0, r0), lexicographically; it does not depend on the brick layout.  The window [first, first +
+ *   capacity) addresses it exactly as vrc_volume_extract_surface's addresses the faces, with R the total number of rectangles
+ *   in *total; all counts are in rectangles.  capacity == 0 with out == NULL is legal and gives R alone.
+ *   VRC_SURFACE_FACES: one record of 4 uint32 per rectangle, x y z and d | (nr - 1) << 8 | (ns - 1) << 20, with (x, y, z)
+ *   the rectangle's voxel of smallest coordinates, nr = r1 - r0 its extent along r and ns along s, both 1 .. 1024; the
+ *   record of a 1 x 1 rectangle is its face record.  VRC_SURFACE_TRIANGLES: two triangles per rectangle, 2 x 9 int32 in
+ *   vrc_volume_xor_mesh's units: the corner rule above with the extents e_a = 1, e_r = nr, e_s = ns, that is
+ *   q0 = 64 (c_u, c_v), q1 = 64 (c_u + e_u, c_v), q2 = 64 (c_u + e_u, c_v + e_v), q3 = 64 (c_u, c_v + e_v), the same
+ *   winding.  All corners are multiples of 64 and voxel centres lie at + 32, so the T-junctions between rectangles of
+ *   different sizes do not disturb the crossing parity: vrc_volume_xor_mesh of the closed mesh into an empty volume of the
+ *   same depth gives the voxel set back bit for bit.
+ * `mem`, `stream`, the alignment of a device buffer (16 bytes for records, 4 for triangles, 8 gets the wide stores; a
+ * misaligned buffer is refused and not written), the internal windows of 2^20 records of the host form and the ordering are
+ * vrc_volume_extract_surface's: both calls only read the occupancy, are ordered behind the volume's last asynchronous edit,
+ * and a device-memory extraction is itself recorded as the last asynchronous edit because the block below is shared.
+ * vrc_rect_count is synchronous: counts[d] = rectangles of direction d, their sum is R.  Depths 2 .. 10.
+ * Cost (csrc/vrc_rects.hip): the brick words are first turned into two dense row bit fields, Z-rows [x][y][z bits] and
+ * Y-rows [x][z][y bits], where the faces of a row are row & ~(the same row of the plane beside it); then count, scan and
+ * emit as for the faces, one lane per 32-bit word of a row: the run starts of a word are m & ~(m << 1 | carry), each is
+ * followed to its end and tested against the row before, and the emit pass walks the rows after a start for the height.
+ * Every call reads the whole occupancy and rebuilds both row fields HOWEVER SMALL the window, capacity == 0 included, and
+ * the scan of the workgroup offsets is one workgroup walking the slots 1024 at a time: 96 steps at depth 9, 768 serial
+ * steps at depth 10.  The volume keeps one block for it: with S = 2^depth,
+ * w = max(1, S / 32) and L = 6 S^2 w,  8 * (ceil(L / 256) + 7) + 8 S^2 w  bytes -- the offsets and totals, then the two
+ * row fields (S^3 / 4 bytes from depth 5 up): 32.75 MiB + 56 bytes at depth 9, 262 MiB + 56 at depth 10; allocated by the
+ * first of the two calls, never grown, counted by vrc_volume_edit_scratch_bytes from then on.
+ * Times: profiles/edit/bench_rects.json (tools/bench_edit.py --rects; 512^3, MI355X, next to the surface calls in the same
+ * run): the terrain, 0.92 M faces in 0.29 M rectangles (T / R = 3.17) -- count 0.47 ms, all records 1.97 ms, all triangles
+ * 2.11 ms, next to 0.15 / 0.09 / 0.20 ms for the faces; a dense random 128^3 field, T / R = 1.50 -- 0.36 / 0.52 / 0.58 ms
+ * next to 0.12 / 0.07 / 0.20.  Fewer records and bytes, but MORE time than the face calls, 3 to 22 times: as a
+ * faster export this first version does not deliver.  The passes have not been timed apart.  From the code the likely
+ * costs are the rebuild of the row fields by every call, six lanes per row word where the faces take one lane per
+ * occupancy word, and the emit pass, where ONE lane follows a run to its end and walks the rows after it for the height --
+ * 511 rows of 16 words under the terrain's 512 x 512 floor rectangle. */
+int vrc_rect_count(vrc_volume *v, int closed, uint64_t counts[6]);
+int vrc_extract_rects(vrc_volume *v, int closed, int format, uint64_t first, uint64_t capacity,
+                             void *out, uint64_t *total, int mem, void *stream);
 /* Voxel src_lo + d of `src` goes to dst_lo + d of `dst` for 0 <= d < size, clipped to both volumes (what falls outside
  * either is neither read nor written).  The volumes may have different depths (a 32^3 clipboard stamped into a 512^3
  * world) and must be two different volumes on one device; any voxel offset is legal.  Asynchronous on `stream`: ordered
@@ -350,7 +397,7 @@ int vrc_volume_clone(vrc_volume *src, vrc_volume **out);
 int vrc_volume_get_voxels(vrc_volume *v, uint64_t n, const uint32_t *xyz, uint8_t *solid_out, int mem, void *stream);
 int vrc_volume_count_boxes(vrc_volume *v, uint64_t n, const uint32_t *lo_hi, uint64_t *counts, int mem, void *stream);
 /* Device bytes the volume holds at this moment in the scratch blocks of its edit calls: the grow-only staging block of the
- * host-memory calls, vrc_volume_flood's block, vrc_volume_xor_mesh's mark field and the surface calls' offsets block (0
+ * host-memory calls, vrc_volume_flood's block, vrc_volume_xor_mesh's mark field, the surface calls' offsets block and the rectangle calls' block (0
  * before the first call of each).  The occupancy itself and vrc_volume_commit's grids are not counted.  Pure host
  * bookkeeping, no device call. */
 int vrc_volume_edit_scratch_bytes(const vrc_volume *v, uint64_t *bytes);

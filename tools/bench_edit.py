@@ -53,6 +53,15 @@ vrc_volume_solid_count on the same volume (it reads the same words once), `--pai
   stamped_noise        the dug terrain with a random 128^3 field of density 0.5 stamped in
   per volume: count (vrc_volume_surface_count), faces / triangles (vrc_volume_extract_surface of ALL faces, closed), the
   number of faces and the bytes written
+With --rects (printed and written to profiles/edit/bench_rects.json), the merged-rectangle extraction at 512^3 next to the
+surface extraction on the same volumes in the same run, output in device memory, device time by events on the NULL stream,
+one warm-up, A B A B in one process with A the rectangle call and B the surface call it replaces, `--pairs` pairs, median and
+range:
+  terrain              the FastNoise terrain
+  dense_noise          a random field of density 0.5 in the 128^3 corner box [0, 128)^3 of an otherwise empty volume
+  per volume: faces T and rectangles R with T / R, count (vrc_rect_count next to vrc_volume_surface_count), records
+  and triangles (vrc_extract_rects of ALL rectangles next to vrc_volume_extract_surface of ALL faces, closed) and the
+  bytes each writes
 With --components (printed and written to profiles/edit/bench_components.json), the connected-component labelling at 512^3,
 device time by events on the NULL stream around the synchronous calls, one warm-up, `--pairs` repetitions, median and range:
   terrain / dug_terrain / dug_terrain_26 / air
@@ -479,6 +488,42 @@ def bench_surface(vrc, depth, pairs):
     return res
 
 
+def bench_rects(vrc, depth, pairs):
+    import torch
+    S = 1 << depth
+    rng = np.random.default_rng(depth)
+    res = {"size": S, "pairs": pairs}
+
+    def case(volume):
+        T, R = int(volume.surfaceCount().sum()), int(volume.rectCount().sum())
+        out = {"faces": T, "rects": R, "faces_over_rects": round(T / max(R, 1), 3), "solid": volume.solidCount(),
+               "rects_per_direction": [int(c) for c in volume.rectCount()]}
+        out["rect_count_ms"], out["surface_count_ms"] = ab_device_ms(volume.rectCount, volume.surfaceCount, pairs)
+        for name, fmt, record in (("records", vrc.capi.VRC_SURFACE_FACES, 16), ("triangles", vrc.capi.VRC_SURFACE_TRIANGLES, 72)):
+            rects = torch.empty(max(R, 1) * record // 4, dtype=torch.int32, device="cuda")
+            faces = torch.empty(max(T, 1) * record // 4, dtype=torch.int32, device="cuda")
+            total = torch.zeros(2, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
+            ms, surface_ms = ab_device_ms(lambda: volume.extractRectsDevice(fmt, 0, R, rects.data_ptr(), total.data_ptr()),
+                                          lambda: volume.extractSurfaceDevice(fmt, 0, T, faces.data_ptr(), total.data_ptr() + 8), pairs)
+            assert total.tolist() == [R, T]
+            out["rect_" + name + "_ms"], out["surface_" + name + "_ms"] = ms, surface_ms
+            out["rect_" + name + "_bytes"], out["surface_" + name + "_bytes"] = R * record, T * record
+            del rects, faces
+        return out
+
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    volume = vrc.VoxelVolume.fromScene(scene)
+    res["terrain"] = case(volume)
+    volume.close()
+    volume = vrc.VoxelVolume(depth)
+    volume.setVoxels(np.argwhere(rng.random((128, 128, 128)) < 0.5))
+    res["dense_noise"] = case(volume)
+    res["scratch_bytes"] = volume.editScratchBytes()
+    volume.close()
+    return res
+
+
 def bench_depth(vrc, depth, pairs):
     import torch
     S = 1 << depth
@@ -771,11 +816,14 @@ def main():
     ap.add_argument("--flood", action="store_true", help="time vrc_volume_flood (depth 9 unless --depths is given)")
     ap.add_argument("--voxelize", action="store_true", help="time vrc_volume_xor_mesh (depth 9 unless --depths is given)")
     ap.add_argument("--surface", action="store_true", help="time vrc_volume_surface_count / vrc_volume_extract_surface (depth 9 unless --depths is given)")
+    ap.add_argument("--rects", action="store_true", help="time vrc_rect_count / vrc_extract_rects next to the surface calls (depth 9 unless --depths is given)")
     ap.add_argument("--components", action="store_true", help="time vrc_volume_label_components / vrc_labels_* (depth 9 unless --depths is given)")
     ap.add_argument("--distance", action="store_true", help="time vrc_volume_distance_field / vrc_distance_select / dilate (depth 9 unless --depths is given)")
     ap.add_argument("--stamp", action="store_true", help="time vrc_volume_stamp_affine next to vrc_volume_copy_region (depth 9 unless --depths is given)")
     args = ap.parse_args()
     if args.stamp and args.depths == [8, 9, 10]:
+        args.depths = [9]
+    if args.rects and args.depths == [8, 9, 10]:
         args.depths = [9]
     if args.distance and args.depths == [8, 9, 10]:
         args.depths = [9]
@@ -795,11 +843,15 @@ def main():
     import cpuvoxelraycaster_amd as vrc
     if not torch.cuda.is_available():
         raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-    out = {"bench": "edit_stamp" if args.stamp else "edit_distance" if args.distance else "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
+    out = {"bench": "edit_rects" if args.rects else "edit_stamp" if args.stamp else "edit_distance" if args.distance else "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
     for d in args.depths:
-        out["depths"][str(d)] = (bench_stamp if args.stamp else bench_distance if args.distance else bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
+        out["depths"][str(d)] = (bench_rects if args.rects else bench_stamp if args.stamp else bench_distance if args.distance else bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
     print(json.dumps(out))
-    if args.stamp:
+    if args.rects:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_rects.json")
+        with open(path, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+    elif args.stamp:
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_stamp.json")
         with open(path, "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
