@@ -65,6 +65,12 @@ class DistanceStats(C.Structure):
     _fields_ = [("features", C.c_uint64), ("max_d2", C.c_uint32), ("argmax", C.c_uint32 * 3), ("reserved", C.c_uint32)]
 
 
+class TravelStats(C.Structure):
+    """vrc_travel_stats (include/vrc.h): what vrc_travel_field reports"""
+    _fields_ = [("seeds", C.c_uint64), ("reached", C.c_uint64), ("max_steps", C.c_uint32), ("argmax", C.c_uint32 * 3),
+                ("sweeps", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Affine(C.Structure):
     """vrc_affine (include/vrc.h): the inverse map of vrc_volume_stamp_affine, m row-major with 16 fractional bits"""
     _fields_ = [("m", C.c_int32 * 9), ("reserved", C.c_int32), ("t", C.c_int64 * 3)]
@@ -181,6 +187,9 @@ SYMBOLS = {
     "vrc_distance_at": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
     "vrc_distance_download": (_int, [_vp, _vp]),
     "vrc_distance_select": (_int, [_vp, _u32, _u32, _vp, _int, _vp]),
+    "vrc_travel_field": (_int, [_vp, _vp, _int, _int, _u32, C.POINTER(_vp), C.POINTER(TravelStats)]),
+    "vrc_travel_connectivity": (_int, [_vp]),
+    "vrc_travel_trace_paths": (_int, [_vp, _u64, _vp, _u32, _vp, _vp, _int, _vp]),
     "vrc_volume_xor_mesh": (_int, [_vp, _u64, _vp, _int, _vp]),
     "vrc_volume_surface_count": (_int, [_vp, _int, _vp]),
     "vrc_volume_extract_surface": (_int, [_vp, _int, _int, _u64, _u64, _vp, _vp, _int, _vp]),

@@ -1,7 +1,8 @@
 // vrc_snapshots.hip -- the snapshots taken from an editable volume (include/vrc.h): the labels of its connected components
 // (vrc_volume_label_components, vrc_labels_*; kernels in vrc_components.hip) and its exact squared Euclidean distance field
 // with the selection by distance that grow / shrink / hollow are made of (vrc_volume_distance_field, vrc_distance_*;
-// kernels in vrc_distance.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
+// kernels in vrc_distance.hip), and the travel-distance field from a set of seeds, kept in the same snapshot object, with the
+// routes read off it (vrc_travel_field, vrc_travel_trace_paths; kernels in vrc_travel.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
 // event and no scratch; what it selects goes into a volume as an edit of that volume (vrc_volume_state.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +12,7 @@
 #include "../../include/vrc.h"
 #include "vrc_components.h"
 #include "vrc_distance.h"
+#include "vrc_travel.h"
 #include "vrc_volume_state.h"
 
 struct vrc_labels {
@@ -24,7 +26,8 @@ struct vrc_labels {
 struct vrc_distance {
     int device = 0;
     uint32_t depth = 0;
-    uint32_t* d_field = nullptr;          // 8^depth squared distances, [(x*S + y)*S + z]
+    int connectivity = 0;                 // 6 / 26: a travel field made with it; 0: a Euclidean field
+    uint32_t* d_field = nullptr;          // 8^depth squared distances (travel field: steps), [(x*S + y)*S + z]
 };
 
 namespace {
@@ -204,6 +207,7 @@ extern "C" int vrc_distance_destroy(vrc_distance* d)
 extern "C" uint32_t vrc_distance_depth(const vrc_distance* d) { return d ? d->depth : 0; }
 extern "C" uint64_t vrc_distance_bytes(const vrc_distance* d) { return d ? (uint64_t)4u << (3u * d->depth) : 0; }
 extern "C" const uint32_t* vrc_distance_data(const vrc_distance* d) { return d ? d->d_field : nullptr; }
+extern "C" int vrc_travel_connectivity(const vrc_distance* d) { return d ? d->connectivity : 0; }
 
 extern "C" int vrc_distance_at(const vrc_distance* d, uint64_t n, const uint32_t* xyz, uint32_t* d2, int mem, void* stream)
 {
@@ -246,6 +250,92 @@ extern "C" int vrc_distance_select(const vrc_distance* d, uint32_t lo, uint32_t 
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+// ---- travel-distance field -----------------------------------------------------
+
+extern "C" int vrc_travel_field(vrc_volume* seeds, vrc_volume* medium, int connectivity, int through, uint32_t step_limit, vrc_distance** out,
+                                       vrc_travel_stats* stats)
+{
+    const char* what = "vrc_travel_field";
+    if (!seeds || !medium) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (!out) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_connectivity(what, connectivity)) return rc;
+    if (const int rc = check_through(what, through)) return rc;
+    if (seeds->depth != medium->depth) return vrc::fail(VRC_ERR_INVALID, "%s: volumes of depths %u and %u", what, seeds->depth, medium->depth);
+    if (seeds->device != medium->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, seeds->device, medium->device);
+    if (medium->depth < 2 || medium->depth > 10) return vrc::fail(VRC_ERR_INVALID, "%s: depth %u not in [2,10]", what, medium->depth);
+    vrc_distance* d = new (std::nothrow) vrc_distance();
+    if (!d) return vrc::fail(VRC_ERR_OOM, "out of host memory");
+    d->device = medium->device; d->depth = medium->depth; d->connectivity = connectivity;
+    unsigned long long host[3] = {0ull, 0ull, 0ull};
+    uint32_t sweeps = 0, converged = 0;
+    const hipError_t e = snapshot_run(medium, &d->d_field, vrc::travel_scratch_bytes(d->depth), [&](uint32_t* d_scratch) {
+        hipError_t run = order_behind_edits(seeds, nullptr);
+        if (run == hipSuccess)
+            run = vrc::travel_run(seeds->d_bricks, medium->d_bricks, d->depth, connectivity, through, step_limit, d->d_field, d_scratch, nullptr, &sweeps,
+                                  &converged);
+        return run != hipSuccess ? run : hipMemcpy(host, vrc::travel_stats_slots(d_scratch), sizeof host, hipMemcpyDeviceToHost);
+    });
+    if (e != hipSuccess) {
+        (void)vrc_distance_destroy(d);
+        return vrc::fail_hip(e, what);
+    }
+    if (!converged) {
+        (void)vrc_distance_destroy(d);
+        return vrc::fail(VRC_ERR_HIP, "%s: internal error: no fixed point within the bound of %u sweeps", what, sweeps);
+    }
+    if (stats) {
+        stats->seeds = host[0]; stats->reached = host[1];
+        stats->max_steps = 0u; stats->argmax[0] = stats->argmax[1] = stats->argmax[2] = 0u; stats->sweeps = sweeps; stats->reserved = 0u;
+        if (host[2]) {
+            const uint32_t index = ~(uint32_t)host[2], mask = (1u << d->depth) - 1u;
+            stats->max_steps = (uint32_t)(host[2] >> 32);
+            stats->argmax[0] = index >> (2u * d->depth); stats->argmax[1] = (index >> d->depth) & mask; stats->argmax[2] = index & mask;
+        }
+    }
+    *out = d;
+    return VRC_OK;
+}
+
+extern "C" int vrc_travel_trace_paths(const vrc_distance* d, uint64_t n, const uint32_t* start_xyz, uint32_t capacity, uint32_t* paths_xyz,
+                                        uint32_t* lengths, int mem, void* stream)
+{
+    const char* what = "vrc_travel_trace_paths";
+    if (!d) return vrc::fail(VRC_ERR_INVALID, "%s: null distance field", what);
+    if (d->connectivity != VRC_CONNECT_FACES && d->connectivity != VRC_CONNECT_ALL)
+        return vrc::fail(VRC_ERR_INVALID, "%s: not a travel field (a Euclidean field has no routes)", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (n == 0) return VRC_OK;
+    if (!start_xyz || !lengths) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (!paths_xyz && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null paths with capacity %u", what, capacity);
+    if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "%s: too many starts for one launch", what);
+    if (capacity && n > (1ull << 58) / capacity) return vrc::fail(VRC_ERR_INVALID, "%s: %llu routes of capacity %u are too many", what, (unsigned long long)n, capacity);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t in_bytes = (size_t)n * 12u, len_bytes = (size_t)n * 4u, path_bytes = (size_t)n * capacity * 12u;
+    hipError_t e = hipSetDevice(d->device);
+    const uint32_t* d_in = start_xyz;
+    uint32_t *d_len = lengths, *d_paths = paths_xyz;
+    uint8_t* own = nullptr;
+    if (mem == VRC_MEM_HOST) {
+        // staged: starts, lengths, paths.  The caller's paths go up first, so that what the kernel leaves alone comes back as it was.
+        if (e == hipSuccess) e = hipMalloc((void**)&own, in_bytes + len_bytes + path_bytes);
+        d_in = (const uint32_t*)own; d_len = (uint32_t*)(own + in_bytes); d_paths = (uint32_t*)(own + in_bytes + len_bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(own, start_xyz, in_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && path_bytes) e = hipMemcpyAsync(d_paths, paths_xyz, path_bytes, hipMemcpyHostToDevice, st);
+    }
+    if (e == hipSuccess) {
+        vrc::travel_trace_run(d->d_field, d->depth, d->connectivity, n, d_in, capacity, d_paths, d_len, st);
+        e = hipGetLastError();
+    }
+    if (mem == VRC_MEM_HOST) {
+        if (e == hipSuccess) e = hipMemcpyAsync(lengths, d_len, len_bytes, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && path_bytes) e = hipMemcpyAsync(paths_xyz, d_paths, path_bytes, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (own) (void)hipFree(own);
+    }
     if (e != hipSuccess) return vrc::fail_hip(e, what);
     return VRC_OK;
 }

@@ -238,19 +238,23 @@ private:
 
 // The squared Euclidean distance of every voxel to the feature set (include/vrc.h: vrc_volume_distance_field): a snapshot
 // on the device, S^3 uint32 in [(x*S + y)*S + z] order, that later edits of the volume do not change.  Movable, RAII.
+// HipVoxelVolume::travelField makes the same object with the steps from the seeds in place of the squared distance
+// (vrc_travel_field): connectivity() is then 6 or 26, travelStats() holds what the call reported, tracePaths() reads routes.
 class HipVoxelDistance {
 public:
     ~HipVoxelDistance() { vrc_distance_destroy(d_); }
-    HipVoxelDistance(HipVoxelDistance&& o) noexcept : d_(o.d_), stats_(o.stats_) { o.d_ = nullptr; }
+    HipVoxelDistance(HipVoxelDistance&& o) noexcept : d_(o.d_), stats_(o.stats_), travel_(o.travel_) { o.d_ = nullptr; }
     HipVoxelDistance& operator=(HipVoxelDistance&& o) noexcept
     {
-        if (this != &o) { vrc_distance_destroy(d_); d_ = o.d_; stats_ = o.stats_; o.d_ = nullptr; }
+        if (this != &o) { vrc_distance_destroy(d_); d_ = o.d_; stats_ = o.stats_; travel_ = o.travel_; o.d_ = nullptr; }
         return *this;
     }
     HipVoxelDistance(const HipVoxelDistance&) = delete;
     HipVoxelDistance& operator=(const HipVoxelDistance&) = delete;
 
     const vrc_distance_stats& stats() const { return stats_; }
+    const vrc_travel_stats& travelStats() const { return travel_; }      // of a travel field; zero for a Euclidean one
+    int connectivity() const { return vrc_travel_connectivity(d_); }   // 6 / 26: a travel field; 0: a Euclidean one
     uint32_t depth() const { return vrc_distance_depth(d_); }
     uint64_t bytes() const { return vrc_distance_bytes(d_); }
     const uint32_t* data() const { return vrc_distance_data(d_); }     // DEVICE pointer
@@ -269,13 +273,26 @@ public:
     }
     // dst becomes (VRC_COPY_REPLACE) / gains (_OR) / loses (_ANDNOT) the voxels with lo <= D <= hi
     inline void select(uint32_t lo, uint32_t hi, HipVoxelVolume& dst, int op = VRC_COPY_REPLACE) const;
+    // Routes off a travel field (vrc_travel_trace_paths) from n start voxels (xyz: n x 3): lengths[i] = the field at start
+    // i, and where that is finite the route's voxels 0 .. min(length, capacity - 1) at paths[(i*capacity + k)*3 ..]; rows
+    // of starts without a value, and what lies behind a route's end, keep `fill`.
+    void tracePaths(const uint32_t* xyz, uint64_t n, uint32_t capacity, std::vector<uint32_t>& paths, std::vector<uint32_t>& lengths,
+                    uint32_t fill = VRC_DISTANCE_NONE) const
+    {
+        paths.assign((size_t)n * capacity * 3u, fill);
+        lengths.assign((size_t)n, VRC_DISTANCE_NONE);
+        check(vrc_travel_trace_paths(d_, n, xyz, capacity, capacity ? paths.data() : nullptr, lengths.data(), VRC_MEM_HOST, nullptr),
+              "vrc_travel_trace_paths");
+    }
     vrc_distance* handle() const { return d_; }
 
 private:
     friend class HipVoxelVolume;
     HipVoxelDistance(vrc_distance* adopted, const vrc_distance_stats& stats) : d_(adopted), stats_(stats) {}
+    HipVoxelDistance(vrc_distance* adopted, const vrc_travel_stats& travel) : d_(adopted), travel_(travel) {}
     vrc_distance* d_ = nullptr;
     vrc_distance_stats stats_{};
+    vrc_travel_stats travel_{};
 };
 
 // What SVO::setCell + compileSVO are to the reference (svo.hpp:72, lsvo_utils.cpp:4), on the device and repeatable: the
@@ -448,6 +465,19 @@ public:
         for (size_t i = 0; i < records.size(); ++i) removed += small[i] = records[i].voxels < min_voxels ? 1 : 0;
         if (removed) labels.select(small, *this, VRC_COPY_ANDNOT);
         return removed;
+    }
+    // The least number of steps from the solid voxels of `seeds` to every voxel through this volume's solid voxels (its
+    // empty ones with through_empty), VRC_DISTANCE_NONE where nothing arrives or, with step_limit, beyond it
+    // (include/vrc.h: vrc_travel_field).  `seeds` may be this volume.  Synchronous.
+    HipVoxelDistance travelField(HipVoxelVolume& seeds, int connectivity = VRC_CONNECT_FACES, bool through_empty = false, uint32_t step_limit = 0)
+    {
+        flush();
+        seeds.flush();
+        vrc_distance* d = nullptr;
+        vrc_travel_stats stats{};
+        check(vrc_travel_field(seeds.v_, v_, connectivity, through_empty ? VRC_FLOOD_EMPTY : VRC_FLOOD_SOLID, step_limit, &d, &stats),
+              "vrc_travel_field");
+        return HipVoxelDistance(d, stats);
     }
     // The exact squared Euclidean distance of every voxel to the nearest solid voxel (to the nearest empty one with
     // to_empty; with outside, everything beyond the faces is a feature as well).  Synchronous.

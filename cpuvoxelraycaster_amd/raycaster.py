@@ -368,6 +368,47 @@ class VoxelVolume:
                                                     C.byref(handle), C.byref(stats)))
         return VoxelDistance(handle, stats, self.depth, self.device)
 
+    def travelField(self, seeds, connectivity=6, through_empty=False, step_limit=0):
+        """The least number of steps from the solid voxels of the volume `seeds` to every voxel through this volume's solid
+        voxels (its empty ones with through_empty), a step to a face neighbour (connectivity=6) or to a face / edge / corner
+        neighbour (26) costing 1 -- include/vrc.h: vrc_travel_field.  capi.VRC_DISTANCE_NONE where nothing arrives
+        and, with step_limit, beyond step_limit steps.  A VoxelDistance snapshot with `stats` a capi.TravelStats and
+        `connectivity` 6 or 26; `seeds` may be this volume.  Synchronous."""
+        handle, stats = C.c_void_p(), capi.TravelStats()
+        check(capi.load().vrc_travel_field(seeds._h, self._h, int(connectivity), capi.VRC_FLOOD_EMPTY if through_empty else capi.VRC_FLOOD_SOLID,
+                                                  int(step_limit), C.byref(handle), C.byref(stats)))
+        return VoxelDistance(handle, stats, self.depth, self.device)
+
+    def reachableWithin(self, seeds, steps, connectivity=6, through_empty=False):
+        """A new volume holding the voxels that `steps` steps or fewer from `seeds` reach through this one (travelField
+        with step_limit, then select)."""
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError(f"reachableWithin: negative step count {steps}")
+        if steps == 0:                    # step_limit 0 would mean "no limit": the seeds themselves are what 0 steps reach
+            field = self.travelField(seeds, connectivity, through_empty, 1)
+        else:
+            field = self.travelField(seeds, connectivity, through_empty, min(steps, capi.VRC_DISTANCE_NONE - 1))
+        out = field.select(0, min(steps, capi.VRC_DISTANCE_NONE - 1))
+        field.close()
+        return out
+
+    def shortestPath(self, a, b, connectivity=6, through_empty=True):
+        """A shortest route from voxel a to voxel b through this volume's empty voxels (its solid ones with
+        through_empty=False) as a (T + 1, 3) uint32 array that starts at a and ends at b, or None when there is none: the
+        travel field seeded at b, traced from a."""
+        target = VoxelVolume(self.depth, self.device)
+        try:
+            target.setVoxels(np.asarray(b, np.uint32).reshape(1, 3))
+            field = self.travelField(target, connectivity, through_empty)
+        finally:
+            target.close()
+        try:
+            lengths, paths = field.tracePaths(np.asarray(a, np.uint32).reshape(1, 3))
+        finally:
+            field.close()
+        return None if lengths[0] == capi.VRC_DISTANCE_NONE else paths[0]
+
     @staticmethod
     def _radius(r, what):
         r = int(r)
@@ -682,10 +723,46 @@ class VoxelLabels:
 class VoxelDistance:
     """The squared Euclidean distance of every voxel to the feature set, resident on the device as S^3 uint32 in
     [(x*S + y)*S + z] order (include/vrc.h: vrc_distance_*): a snapshot made by VoxelVolume.distanceField.  `stats` is a
-    capi.DistanceStats (features, max_d2, argmax)."""
+    capi.DistanceStats (features, max_d2, argmax).  VoxelVolume.travelField makes the same object with the steps from the
+    seeds in place of the squared distance: `stats` is then a capi.TravelStats and `connectivity` 6 or 26, not 0."""
 
     def __init__(self, handle, stats, depth, device):
         self._h, self.stats, self.depth, self.device = handle, stats, depth, device
+
+    @property
+    def connectivity(self):
+        """6 or 26 for a travel field, 0 for a Euclidean one"""
+        return int(capi.load().vrc_travel_connectivity(self._h))
+
+    def tracePaths(self, starts, capacity=None):
+        """Routes off a travel field (include/vrc.h: vrc_travel_trace_paths): (lengths, routes) for (n, 3) start voxels --
+        lengths[i] = the field at start i, capi.VRC_DISTANCE_NONE outside the volume or where nothing arrives; routes[i] a
+        (k, 3) uint32 array from the start towards a seed, k = min(length, capacity - 1) + 1 voxels, empty for a start without
+        a value.  capacity=None sizes the rows by the longest route, so every route ends at a seed."""
+        starts = np.ascontiguousarray(starts, np.uint32).reshape(-1, 3)
+        n = starts.shape[0]
+        lengths = np.zeros(n, np.uint32)
+        if capacity is None:
+            if n:
+                check(capi.load().vrc_travel_trace_paths(self._h, n, ptr(starts), 0, None, ptr(lengths), capi.VRC_MEM_HOST, None))
+            finite = lengths[lengths != capi.VRC_DISTANCE_NONE]
+            capacity = int(finite.max()) + 1 if len(finite) else 0
+        capacity = int(capacity)
+        paths = np.zeros((n, capacity, 3), np.uint32)
+        if n:
+            check(capi.load().vrc_travel_trace_paths(self._h, n, ptr(starts), capacity, ptr(paths) if capacity else None, ptr(lengths),
+                                                       capi.VRC_MEM_HOST, None))
+        routes = []
+        for i in range(n):
+            k = 0 if lengths[i] == capi.VRC_DISTANCE_NONE or capacity == 0 else min(int(lengths[i]), capacity - 1) + 1
+            routes.append(paths[i, :k].copy())
+        return lengths, routes
+
+    def tracePathsDevice(self, n, starts_ptr, capacity, paths_ptr, lengths_ptr, stream=None):
+        """the same over n x 3 uint32 starts, n x capacity x 3 uint32 of routes and n uint32 lengths in device memory,
+        asynchronous on `stream`; nothing beyond the voxels of a route is written"""
+        check(capi.load().vrc_travel_trace_paths(self._h, n, ptr(starts_ptr), int(capacity), ptr(paths_ptr), ptr(lengths_ptr), capi.VRC_MEM_DEVICE,
+                                                   ptr(stream)))
 
     def bytes(self):
         return int(capi.load().vrc_distance_bytes(self._h))

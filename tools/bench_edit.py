@@ -97,6 +97,14 @@ and range:
   clipboard_64_x2      a 64^3 clipboard cut from the terrain's surface, stamped at scale 2 with the same turn into the world
                        with the box from vrc_affine_place, next to a 128^3 region copy
   per case the solid voxels of the result
+With --travel (printed and written to profiles/edit/bench_travel.json), the travel-distance field at 512^3 on the FastNoise
+terrain, device time by events on the NULL stream around the synchronous calls, one warm-up, `--pairs` repetitions, median and
+range, for 6 and 26 neighbours:
+  air_from_one_seed    through the empty voxels from the highest empty voxel of the centre column
+  solid_from_the_floor through the solid voxels from the floor layer, the slab y = S / 2 + 1 the terrain's columns stand on
+  per case: travel (the whole vrc_travel_field call) with seeds, reached, max_steps and the sweeps issued; flood
+  (vrc_volume_flood from the same seeds on the same medium, in the same run: the support of the same field) with its sweeps
+  and reached, which equals the field's; and travel_over_flood
 No threshold is applied; the numbers are reported."""
 import argparse
 import json
@@ -760,6 +768,62 @@ def bench_distance(vrc, depth, pairs):
     return res
 
 
+def bench_travel(vrc, depth, pairs):
+    """vrc_travel_field on the FastNoise terrain: through the air from one seed voxel above the ground and through
+    the solid from the floor layer (the slab y = S / 2 + 1 its columns stand on), both connectivities; device ms by events, median of `pairs`, and the sweeps
+    issued.  In the same run vrc_volume_flood from the same seeds on the same medium: it computes the support of the same
+    field (a fresh copy of the seeds per repeat, made outside the timed span)."""
+    import torch
+    S = 1 << depth
+    res = {"size": S, "pairs": pairs, "field_bytes": 4 * S ** 3}
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    terrain = vrc.VoxelVolume.fromScene(scene)
+    # the slab the terrain's columns stand on (the flood mode's `bottom`), and the highest empty voxel of the centre column
+    floor_y = S // 2 + 1
+    above = next(([S // 2, y, S // 2] for y in range(S - 2, -1, -1) if not terrain.getVoxels([[S // 2, y, S // 2]])[0]), None)
+    if above is None:
+        raise SystemExit("bench_travel: no empty voxel in the column at the centre of the terrain")
+    air_seed = vrc.VoxelVolume(depth)
+    air_seed.setVoxels([above])
+    floor = vrc.VoxelVolume(depth)
+    floor.fillBoxes([[0, floor_y, 0, S, floor_y + 1, S]])
+
+    def timed(fn, repeats, before=None):
+        out, last = [], None
+        for i in range(repeats + 1):
+            if last is not None and hasattr(last, "close"):
+                last.close()
+            arg = before() if before else None
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            last = fn(arg) if before else fn()
+            b.record()
+            b.synchronize()
+            if i:
+                out.append(a.elapsed_time(b))
+            if arg is not None:
+                last = (last, arg.solidCount())
+                arg.close()
+        return stat(out, 4), last
+
+    for name, seeds, through_empty in (("air_from_one_seed", air_seed, True), ("solid_from_the_floor", floor, False)):
+        res[name] = {"seed": above if seeds is air_seed else "layer y = %d" % floor_y}
+        for connectivity in (6, 26):
+            r = {}
+            r["travel_ms"], field = timed(lambda: terrain.travelField(seeds, connectivity, through_empty), pairs)
+            st = field.stats
+            r["seeds"], r["reached"], r["max_steps"], r["sweeps"] = int(st.seeds), int(st.reached), int(st.max_steps), int(st.sweeps)
+            field.close()
+            r["flood_ms"], (fst, flooded) = timed(lambda region: region.flood(terrain, connectivity, through_empty), pairs, before=seeds.clone)
+            r["flood_sweeps"], r["flood_reached"] = int(fst.sweeps), int(flooded)
+            r["travel_over_flood"] = round(r["travel_ms"]["median"] / r["flood_ms"]["median"], 2)
+            res[name]["connectivity_%d" % connectivity] = r
+    for v in (terrain, air_seed, floor):
+        v.close()
+    scene.close()
+    return res
+
+
 def bench_stamp(vrc, depth, pairs):
     import math
     S = 1 << depth
@@ -820,7 +884,10 @@ def main():
     ap.add_argument("--components", action="store_true", help="time vrc_volume_label_components / vrc_labels_* (depth 9 unless --depths is given)")
     ap.add_argument("--distance", action="store_true", help="time vrc_volume_distance_field / vrc_distance_select / dilate (depth 9 unless --depths is given)")
     ap.add_argument("--stamp", action="store_true", help="time vrc_volume_stamp_affine next to vrc_volume_copy_region (depth 9 unless --depths is given)")
+    ap.add_argument("--travel", action="store_true", help="time vrc_travel_field next to vrc_volume_flood from the same seeds (depth 9 unless --depths is given)")
     args = ap.parse_args()
+    if args.travel and args.depths == [8, 9, 10]:
+        args.depths = [9]
     if args.stamp and args.depths == [8, 9, 10]:
         args.depths = [9]
     if args.rects and args.depths == [8, 9, 10]:
@@ -843,11 +910,15 @@ def main():
     import cpuvoxelraycaster_amd as vrc
     if not torch.cuda.is_available():
         raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-    out = {"bench": "edit_rects" if args.rects else "edit_stamp" if args.stamp else "edit_distance" if args.distance else "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
+    out = {"bench": "edit_travel" if args.travel else "edit_rects" if args.rects else "edit_stamp" if args.stamp else "edit_distance" if args.distance else "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
     for d in args.depths:
-        out["depths"][str(d)] = (bench_rects if args.rects else bench_stamp if args.stamp else bench_distance if args.distance else bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
+        out["depths"][str(d)] = (bench_travel if args.travel else bench_rects if args.rects else bench_stamp if args.stamp else bench_distance if args.distance else bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
     print(json.dumps(out))
-    if args.rects:
+    if args.travel:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_travel.json")
+        with open(path, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+    elif args.rects:
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_rects.json")
         with open(path, "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
