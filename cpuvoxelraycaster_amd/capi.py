@@ -71,6 +71,12 @@ class TravelStats(C.Structure):
                 ("sweeps", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class FallStats(C.Structure):
+    """vrc_fall_stats (include/vrc.h): what vrc_fall_drops reports"""
+    _fields_ = [("moved_voxels", C.c_uint64), ("pieces", C.c_uint32), ("moved_pieces", C.c_uint32), ("max_drop", C.c_uint32),
+                ("rounds", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class Affine(C.Structure):
     """vrc_affine (include/vrc.h): the inverse map of vrc_volume_stamp_affine, m row-major with 16 fractional bits"""
     _fields_ = [("m", C.c_int32 * 9), ("reserved", C.c_int32), ("t", C.c_int64 * 3)]
@@ -179,6 +185,8 @@ SYMBOLS = {
     "vrc_labels_components": (_int, [_vp, _u64, _u64, _vp, _int, _vp]),
     "vrc_labels_at": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
     "vrc_labels_select": (_int, [_vp, _vp, _vp, _int, _int, _vp]),
+    "vrc_fall_drops": (_int, [_vp, _vp, _int, _u32, _vp, _int, C.POINTER(FallStats)]),
+    "vrc_fall_place": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp]),
     "vrc_volume_distance_field": (_int, [_vp, _int, _int, C.POINTER(_vp), C.POINTER(DistanceStats)]),
     "vrc_distance_destroy": (_int, [_vp]),
     "vrc_distance_depth": (_u32, [_vp]),

@@ -12,6 +12,7 @@
 #include "../../include/vrc.h"
 #include "vrc_components.h"
 #include "vrc_distance.h"
+#include "vrc_fall.h"
 #include "vrc_travel.h"
 #include "vrc_volume_state.h"
 
@@ -152,6 +153,73 @@ extern "C" int vrc_labels_select(const vrc_labels* l, const uint8_t* keep, vrc_v
     }
     if (e == hipSuccess) {
         vrc::components_select_run(l->d_ids, l->depth, d_keep, dst->d_bricks, op, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = finish(dst, mem, st, true);
+    if (d_stage) (void)hipFree(d_stage);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+// how far every piece can fall (the rule: include/vrc.h; the passes: vrc_fall.hip).  Synchronous, on the NULL stream.
+extern "C" int vrc_fall_drops(const vrc_labels* l, vrc_volume* fixed, int direction, uint32_t drop_limit, int32_t* offsets, int mem, vrc_fall_stats* stats)
+{
+    const char* what = "vrc_fall_drops";
+    if (!l) return vrc::fail(VRC_ERR_INVALID, "%s: null labels", what);
+    if (direction < VRC_FACE_XN || direction > VRC_FACE_ZP) return vrc::fail(VRC_ERR_INVALID, "%s: direction %d is not a face code 0..5", what, direction);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (fixed && fixed->depth != l->depth) return vrc::fail(VRC_ERR_INVALID, "%s: labels of depth %u, volume of depth %u", what, l->depth, fixed->depth);
+    if (fixed && fixed->device != l->device) return vrc::fail(VRC_ERR_INVALID, "%s: labels on device %d, volume on device %d", what, l->device, fixed->device);
+    if (!offsets && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null offsets with %llu components", what, (unsigned long long)l->count);
+    vrc_fall_stats none = {};
+    if (!stats) stats = &none;
+    *stats = none;
+    if (!l->count) return VRC_OK;
+    const size_t scratch_bytes = vrc::fall_scratch_bytes(l->count), offset_bytes = (size_t)l->count * 12u;
+    uint8_t* d_scratch = nullptr;
+    uint32_t converged = 0;
+    hipError_t e = hipSetDevice(l->device);
+    if (e == hipSuccess && fixed) e = order_behind_edits(fixed, nullptr);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_scratch, scratch_bytes + (mem == VRC_MEM_HOST ? offset_bytes : 0u));
+    int32_t* d_offsets = mem == VRC_MEM_HOST ? (int32_t*)(d_scratch + scratch_bytes) : offsets;
+    if (e == hipSuccess)
+        e = vrc::fall_run(l->d_ids, l->d_records, l->count, l->depth, fixed ? fixed->d_bricks : nullptr, direction, drop_limit, d_offsets, (uint32_t*)d_scratch,
+                          nullptr, stats, &converged);
+    if (e == hipSuccess && converged && mem == VRC_MEM_HOST) e = hipMemcpy(offsets, d_offsets, offset_bytes, hipMemcpyDeviceToHost);
+    if (d_scratch) (void)hipFree(d_scratch);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    if (!converged) return vrc::fail(VRC_ERR_HIP, "%s: internal error: no fixed point within the bound of %u rounds", what, stats->rounds);
+    return VRC_OK;
+}
+
+// every piece, moved by its own offset, into dst
+extern "C" int vrc_fall_place(const vrc_labels* l, const uint8_t* keep, const int32_t* offsets, vrc_volume* dst, int op, int mem, void* stream)
+{
+    const char* what = "vrc_fall_place";
+    if (!l || !dst) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_op(what, op)) return rc;
+    if (op == VRC_COPY_REPLACE) return vrc::fail(VRC_ERR_INVALID, "%s: VRC_COPY_REPLACE has no meaning for a scatter", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (dst->depth != l->depth) return vrc::fail(VRC_ERR_INVALID, "%s: labels of depth %u, volume of depth %u", what, l->depth, dst->depth);
+    if (dst->device != l->device) return vrc::fail(VRC_ERR_INVALID, "%s: labels on device %d, volume on device %d", what, l->device, dst->device);
+    if (!offsets && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null offsets with %llu components", what, (unsigned long long)l->count);
+    if (!l->count) return VRC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t offset_bytes = (size_t)l->count * 12u;
+    hipError_t e = hipSetDevice(l->device);
+    if (e == hipSuccess) e = order_behind_edits(dst, st);
+    const uint8_t* d_keep = keep;
+    const int32_t* d_offsets = offsets;
+    uint8_t* d_stage = nullptr;
+    if (mem == VRC_MEM_HOST) {                       // staged: the offsets, then the keep bytes
+        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, offset_bytes + (keep ? (size_t)l->count : 0u));
+        if (e == hipSuccess) e = hipMemcpyAsync(d_stage, offsets, offset_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && keep) e = hipMemcpyAsync(d_stage + offset_bytes, keep, (size_t)l->count, hipMemcpyHostToDevice, st);
+        d_offsets = (const int32_t*)d_stage;
+        d_keep = keep ? d_stage + offset_bytes : nullptr;
+    }
+    if (e == hipSuccess) {
+        vrc::place_run(l->d_ids, l->depth, d_keep, d_offsets, dst->d_bricks, op, st);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = finish(dst, mem, st, true);

@@ -228,6 +228,13 @@ public:
     }
     // dst becomes (VRC_COPY_REPLACE) / gains (_OR) / loses (_ANDNOT) the voxels of the pieces with keep[id] != 0
     inline void select(const std::vector<uint8_t>& keep, HipVoxelVolume& dst, int op = VRC_COPY_REPLACE) const;
+    // How far every piece can fall as a rigid body along `direction` (a VRC_FACE_* code: on the terrain generator's scenes
+    // down is VRC_FACE_YN) before it meets a solid voxel of `fixed` (nullptr: nothing), the volume's face, drop_limit
+    // (0 = none) or a piece that has come to rest (include/vrc.h: vrc_fall_drops): count() x 3 offsets D_i * g.
+    inline std::vector<int32_t> fall(HipVoxelVolume* fixed, int direction, uint32_t drop_limit = 0, vrc_fall_stats* stats = nullptr) const;
+    // dst gains (VRC_COPY_OR) or loses (VRC_COPY_ANDNOT) every voxel of the pieces with keep[id] != 0 (nullptr: all), each
+    // piece moved by its own offset; what leaves the volume is dropped
+    inline void place(const std::vector<int32_t>& offsets, HipVoxelVolume& dst, int op = VRC_COPY_OR, const std::vector<uint8_t>* keep = nullptr) const;
     vrc_labels* handle() const { return l_; }
 
 private:
@@ -454,6 +461,18 @@ public:
         vrc_labels* l = nullptr;
         check(vrc_volume_label_components(v_, connectivity, through_empty ? VRC_FLOOD_EMPTY : VRC_FLOOD_SOLID, &l, nullptr), "vrc_volume_label_components");
         return HipVoxelLabels(l);
+    }
+    // Dig, let the debris fall, commit: what no longer holds on to a solid voxel inside one of the n anchor boxes falls piece
+    // by piece along `direction` (a VRC_FACE_* code) until it lands, at most drop_limit cells (0 = no limit); afterwards the
+    // volume holds the supported part plus every loose piece where it came to rest.
+    vrc_fall_stats dropLoose(const uint32_t* anchor_lo_hi, size_t n, int direction, int connectivity = VRC_CONNECT_FACES, uint32_t drop_limit = 0)
+    {
+        std::unique_ptr<HipVoxelVolume> debris = keepConnected(std::vector<uint32_t>(anchor_lo_hi, anchor_lo_hi + 6 * n), connectivity);
+        HipVoxelLabels labels = debris->labelComponents(connectivity);
+        vrc_fall_stats stats;
+        const std::vector<int32_t> offsets = labels.fall(this, direction, drop_limit, &stats);
+        labels.place(offsets, *this, VRC_COPY_OR);
+        return stats;
     }
     // Clears every solid piece of fewer than min_voxels voxels; returns how many pieces that were.
     uint64_t removeSmallPieces(uint64_t min_voxels, int connectivity = VRC_CONNECT_FACES)
@@ -736,6 +755,24 @@ inline void HipVoxelLabels::select(const std::vector<uint8_t>& keep, HipVoxelVol
     if (keep.size() != count()) throw std::invalid_argument("HipVoxelLabels::select: keep must have one byte per component");
     dst.flush();
     check(vrc_labels_select(l_, keep.empty() ? nullptr : keep.data(), dst.handle(), op, VRC_MEM_HOST, nullptr), "vrc_labels_select");
+}
+
+inline std::vector<int32_t> HipVoxelLabels::fall(HipVoxelVolume* fixed, int direction, uint32_t drop_limit, vrc_fall_stats* stats) const
+{
+    if (fixed) fixed->flush();
+    std::vector<int32_t> offsets((size_t)count() * 3u);
+    check(vrc_fall_drops(l_, fixed ? fixed->handle() : nullptr, direction, drop_limit, offsets.empty() ? nullptr : offsets.data(), VRC_MEM_HOST, stats),
+          "vrc_fall_drops");
+    return offsets;
+}
+
+inline void HipVoxelLabels::place(const std::vector<int32_t>& offsets, HipVoxelVolume& dst, int op, const std::vector<uint8_t>* keep) const
+{
+    if (offsets.size() != count() * 3u) throw std::invalid_argument("HipVoxelLabels::place: offsets must have three entries per component");
+    if (keep && keep->size() != count()) throw std::invalid_argument("HipVoxelLabels::place: keep must have one byte per component");
+    dst.flush();
+    check(vrc_fall_place(l_, keep && !keep->empty() ? keep->data() : nullptr, offsets.empty() ? nullptr : offsets.data(), dst.handle(), op, VRC_MEM_HOST, nullptr),
+          "vrc_fall_place");
 }
 
 inline void HipVoxelDistance::select(uint32_t lo, uint32_t hi, HipVoxelVolume& dst, int op) const

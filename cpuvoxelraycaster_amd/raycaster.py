@@ -325,6 +325,24 @@ class VoxelVolume:
         supported.close()
         return debris
 
+    def dropLoose(self, anchor_boxes, direction, connectivity=6, drop_limit=0):
+        """Dig, let the debris fall, commit: what no longer holds on to a solid voxel inside one of the (n, 6) anchor boxes
+        (keepConnected) falls piece by piece as rigid bodies along `direction` (a capi.VRC_FACE_* code, no default: on the
+        terrain generator's scenes the ground lies towards -y, capi.VRC_FACE_YN) until it lands on the supported part, on
+        another piece or on the volume's face, at most drop_limit cells (0 = no limit) -- include/vrc.h: vrc_fall_drops.
+        Afterwards the volume holds the supported part plus every loose piece where it came to rest.  Returns capi.FallStats."""
+        debris = self.keepConnected(anchor_boxes, connectivity)
+        try:
+            labels = debris.labelComponents(connectivity)
+            try:
+                offsets, stats = labels.fall(self, direction, drop_limit)
+                labels.place(offsets, self, capi.VRC_COPY_OR)
+            finally:
+                labels.close()
+        finally:
+            debris.close()
+        return stats
+
     def labelComponents(self, connectivity=6, through_empty=False):
         """Every connected piece of the solid voxels (or, with through_empty, of the empty ones) named in one call
         (include/vrc.h: vrc_volume_label_components): a VoxelLabels snapshot that later edits do not change.  Synchronous."""
@@ -704,6 +722,48 @@ class VoxelLabels:
     def selectDevice(self, keep_ptr, dst, op=capi.VRC_COPY_REPLACE, stream=None):
         """the same with `count` bytes of keep in device memory, asynchronous on `stream`"""
         check(capi.load().vrc_labels_select(self._h, ptr(keep_ptr), dst._h, int(op), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def fall(self, fixed=None, direction=None, drop_limit=0):
+        """How far every piece can fall as a rigid body along `direction` (a capi.VRC_FACE_* code; on the terrain generator's
+        scenes down is capi.VRC_FACE_YN) before it meets a solid voxel of the volume `fixed` (None: nothing), the volume's
+        face, drop_limit (0 = none) or a piece that has come to rest -- include/vrc.h: vrc_fall_drops.  Returns
+        ((count, 3) int32 offsets, capi.FallStats).  Synchronous."""
+        if direction is None:
+            raise TypeError("fall: direction has no default -- which way is down is the caller's business (capi.VRC_FACE_*)")
+        offsets, stats = np.zeros((self.count, 3), np.int32), capi.FallStats()
+        check(capi.load().vrc_fall_drops(self._h, fixed._h if fixed is not None else None, int(direction), int(drop_limit),
+                                          ptr(offsets) if self.count else None, capi.VRC_MEM_HOST, C.byref(stats)))
+        return offsets, stats
+
+    def fallDevice(self, offsets_ptr, fixed=None, direction=None, drop_limit=0):
+        """the same with the count x 3 int32 offsets written to device memory, for placeDevice; still synchronous"""
+        if direction is None:
+            raise TypeError("fallDevice: direction has no default -- which way is down is the caller's business (capi.VRC_FACE_*)")
+        stats = capi.FallStats()
+        check(capi.load().vrc_fall_drops(self._h, fixed._h if fixed is not None else None, int(direction), int(drop_limit), ptr(offsets_ptr),
+                                          capi.VRC_MEM_DEVICE, C.byref(stats)))
+        return stats
+
+    def place(self, offsets, dst=None, op=capi.VRC_COPY_OR, keep=None):
+        """dst (a new volume with None) gains (VRC_COPY_OR) or loses (VRC_COPY_ANDNOT) every voxel of the pieces with
+        keep[id] != 0 (None: all), each piece moved by its own (count, 3) int32 offset; what leaves the volume is dropped.
+        Returns dst."""
+        offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1, 3)
+        if len(offsets) != self.count:
+            raise ValueError(f"offsets has {len(offsets)} rows for {self.count} components")
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, np.uint8).reshape(-1)
+            if len(keep) != self.count:
+                raise ValueError(f"keep has {len(keep)} entries for {self.count} components")
+        if dst is None:
+            dst = VoxelVolume(self.depth, self.device)
+        check(capi.load().vrc_fall_place(self._h, ptr(keep), ptr(offsets) if self.count else None, dst._h, int(op), capi.VRC_MEM_HOST, None))
+        return dst
+
+    def placeDevice(self, offsets_ptr, dst, op=capi.VRC_COPY_OR, keep_ptr=None, stream=None):
+        """the same with the offsets (and `count` bytes of keep) in device memory, asynchronous on `stream`"""
+        check(capi.load().vrc_fall_place(self._h, ptr(keep_ptr), ptr(offsets_ptr), dst._h, int(op), capi.VRC_MEM_DEVICE, ptr(stream)))
+        return dst
 
     def bytes(self):
         return int(capi.load().vrc_labels_bytes(self._h))

@@ -485,6 +485,75 @@ int vrc_labels_components(const vrc_labels *l, uint64_t first, uint64_t capacity
 int vrc_labels_at(const vrc_labels *l, uint64_t n, const uint32_t *xyz, uint32_t *ids, int mem, void *stream);
 int vrc_labels_select(const vrc_labels *l, const uint8_t *keep, vrc_volume *dst, int op, int mem, void *stream);
 
+/* Loose pieces fall as rigid bodies, on the device: the step between "this piece is loose" (vrc_volume_flood,
+ * vrc_volume_label_components of the debris) and "commit the new scene".  vrc_fall_drops says how far every piece of a
+ * labelling can fall, vrc_fall_place writes every piece, moved by its own offset, into a volume.
+ * Both work on a vrc_labels snapshot; like vrc_travel_field and vrc_travel_trace_paths on the distance snapshot they carry the
+ * name of what they compute, vrc_fall_*, as their stats record vrc_fall_stats does.
+ *
+ * The rule, exact in integers.  `direction` is a face code d = 2*axis + side (VRC_FACE_*); the unit step is g = -e_axis for
+ * side 0 and +e_axis for side 1, and "ahead of v" means v + k g, k >= 1.  Which way is down is the caller's business: the
+ * terrain generator makes a column solid for y in [S/2 + 1, S/2 + lim) in setCell coordinates, so the slab the terrain stands
+ * on lies towards -y, and down is VRC_FACE_YN there.  The pieces P_0 .. P_{C-1} are the components of the labels' set M,
+ * whatever connectivity and `through` the labels were made with.  F is the set of solid voxels of `fixed`, a volume of the
+ * labels' depth on the labels' device that is only read; NULL means empty.  The volume's faces are walls.  The drops
+ * D_i >= 0 are the GREATEST integers such that for every voxel v of P_i
+ *   1. v + D_i g lies inside the volume;
+ *   2. D_i = 0 if v itself is in F, and D_i <= k - 1 for every f = v + k g in F with k >= 1;
+ *   3. D_i <= D_j + k - 1 for every w = v + k g in P_j with j != i and k >= 1;
+ *   4. D_i <= drop_limit if drop_limit != 0.
+ * This is a shortest-path system with non-negative weights, so it has exactly one greatest solution, and that solution is
+ * what the literal simulation gives: at every tick the largest set of pieces that can all move one cell together moves, a
+ * piece being blocked if it overlaps F, touches F or the wall ahead, has reached drop_limit, or rests on a blocked piece.
+ * Order within a column is preserved, so nothing passes through anything, and after the move no voxel of a piece shares a
+ * cell with F or with another piece unless it already did on entry.
+ *
+ * vrc_fall_drops writes offsets[3i .. 3i+2] = D_i * g to host or device memory, as `mem` says; with device memory the pair
+ * fall -> place needs no host copy.  It is synchronous (the host decides convergence), runs on the NULL stream and is
+ * ordered behind the last asynchronous edit of `fixed`.  stats may be NULL; C == 0 is legal: zero stats, offsets untouched.
+ * All scratch -- one uint32 per piece, a changed flag, the union of the pieces' boxes and the stats, plus the staged offsets
+ * of a host-memory call -- is freed before return; vrc_volume_edit_scratch_bytes does not change.
+ * The device (csrc/vrc_fall.hip) relaxes in rounds, one launch each: a scan of every voxel column along the direction from
+ * the far face backwards carries the nearest non-empty voxel ahead (the wall, F or a piece, and its distance -- nothing
+ * farther ahead can bind) and lowers D[i] with a 32-bit vector atomicMin.  Every value written is an upper bound of the
+ * answer, values only decrease, and a round that lowers nothing has found every constraint satisfied: in-place relaxation
+ * ends at the greatest solution whatever the schedule, and two calls give identical bytes.  The host reads a changed flag
+ * after every round; the loop is bounded by C + 1 rounds and reaching the bound is an internal error (VRC_ERR_HIP), never
+ * a partial result.  Along z a wave takes 64 cells of a column at a time and resolves them from ballots, along x and y a
+ * lane takes a column; a wave whose lanes all lower the same piece issues one atomic; the launch covers the union of the
+ * pieces' boxes extended to the far face.
+ * Measured on an MI355X at 512^3 on the FastNoise terrain (tools/bench_edit.py --fall, profiles/edit/bench_fall.json; two
+ * bands and a grid of cuts leave 404 loose blocks of 1.9 M voxels over 5.6 M supported ones; device time by events, median
+ * of 5): the whole vrc_fall_drops call towards -y 0.57 ms in 2 rounds (largest drop 7), vrc_fall_place of all pieces
+ * 0.19 ms, next to 1.93 ms of vrc_volume_label_components and 0.20 ms of vrc_labels_select of the same labels in the same
+ * run -- a round, with the call's allocation, init pass and flag read-back shared out, costs 0.15 of the labelling.  The
+ * rounds have not been timed apart.
+ *
+ * vrc_fall_place: every voxel p of M with keep[id(p)] != 0 (keep: C bytes, NULL = all) sets (VRC_COPY_OR) or clears
+ * (VRC_COPY_ANDNOT) the voxel p + offsets[id(p)] of dst.  Targets outside the volume are dropped, the setCell rule; a piece
+ * with an offset component beyond +-2^20 is dropped whole, like an out-of-range sphere.  The offsets are arbitrary -- a
+ * fall's, or a physics engine's -- and two pieces may land on the same voxels.  VRC_COPY_REPLACE is VRC_ERR_INVALID: a
+ * scatter has no unique "replace".  dst may be the labelled medium itself, because the labels are a snapshot.  The device
+ * scatters with 32-bit vector atomic OR / AND on the occupancy words, the lanes of a wave that hit one word joining their
+ * bits first, so the result does not depend on scheduling.  mem says where keep and offsets live: VRC_MEM_HOST is staged
+ * and synchronous; VRC_MEM_DEVICE works in place and is asynchronous on `stream`, ordered behind dst's last asynchronous
+ * edit and recorded as dst's last edit, with the warning of vrc_volume_copy_region: do not edit dst on ANOTHER stream
+ * before the scatter has run.
+ *
+ * NULL `l`, `offsets` (when C > 0) or `dst`, a direction outside 0..5, a depth or device mismatch, a bad `mem` and an
+ * unknown op are VRC_ERR_INVALID, refused before any device call. */
+typedef struct vrc_fall_stats {          /* 32 bytes */
+    uint64_t moved_voxels;               /* voxels of pieces with D > 0 */
+    uint32_t pieces, moved_pieces;       /* C; pieces with D > 0 */
+    uint32_t max_drop;                   /* largest D, 0 when C == 0 */
+    uint32_t rounds;                     /* relaxation rounds issued */
+    uint32_t reserved[2];                /* 0 */
+} vrc_fall_stats;
+int vrc_fall_drops(const vrc_labels *l, vrc_volume *fixed, int direction, uint32_t drop_limit,
+                    int32_t *offsets /* C x 3: D_i * g */, int mem, vrc_fall_stats *stats);
+int vrc_fall_place(const vrc_labels *l, const uint8_t *keep /* C bytes, NULL = all */,
+                     const int32_t *offsets /* C x 3 */, vrc_volume *dst, int op, int mem, void *stream);
+
 /* The exact squared Euclidean distance field, on the device: how far every voxel is from the surface, and with it grow /
  * shrink by r voxels (dilate, erode, open, close), hollowing a solid down to a shell, clearance queries, and a field a
  * PyTorch caller reads in place.  The feature set F is the solid voxels of `medium` (to = VRC_FLOOD_SOLID) or its empty

@@ -105,6 +105,18 @@ range, for 6 and 26 neighbours:
   per case: travel (the whole vrc_travel_field call) with seeds, reached, max_steps and the sweeps issued; flood
   (vrc_volume_flood from the same seeds on the same medium, in the same run: the support of the same field) with its sweeps
   and reached, which equals the field's; and travel_over_flood
+With --fall (printed and written to profiles/edit/bench_fall.json), falling pieces at 512^3 on the FastNoise terrain: a band of
+four layers is carved out of the terrain 24 voxels above the slab its columns stand on and one of three layers 44 voxels
+above it, and everything above the lower band is cut by planes two voxels thick every 32 voxels along x and z, so that it
+hangs loose in a few hundred blocks, those above the upper band over those below it; keepConnected from the slab splits the
+supported part from the debris.  Device time by events on
+the NULL stream, one warm-up, `--pairs` repetitions, median and range:
+  label      vrc_volume_label_components of the debris (the comparison figure: a fall is a few more passes over its id array)
+  fall       vrc_fall_drops towards -y over the supported part, offsets in device memory, with rounds, pieces, moved pieces
+             and voxels and the largest drop
+  place      vrc_fall_place of every piece into a copy of the supported part (OR), offsets in device memory
+  select     vrc_labels_select of every piece of the same labels into a volume (OR)
+  fall_round_over_label = fall / rounds / label
 No threshold is applied; the numbers are reported."""
 import argparse
 import json
@@ -824,6 +836,55 @@ def bench_travel(vrc, depth, pairs):
     return res
 
 
+def bench_fall(vrc, depth, pairs):
+    """vrc_fall_drops / vrc_fall_place on the FastNoise terrain with a band carved out (see the module's text), next to
+    vrc_volume_label_components and vrc_labels_select of the same debris in the same run."""
+    import torch
+    S = 1 << depth
+    res = {"size": S, "pairs": pairs}
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    world = vrc.VoxelVolume.fromScene(scene)
+    floor_y = S // 2 + 1
+    band = [0, floor_y + 24, 0, S, floor_y + 28, S]
+    cuts = [band, [0, floor_y + 44, 0, S, floor_y + 47, S]]
+    cuts += [[c, floor_y + 24, 0, c + 2, S, S] for c in range(30, S, 32)] + [[0, floor_y + 24, c, S, S, c + 2] for c in range(30, S, 32)]
+    world.fillBoxes(cuts, False)
+    debris = world.keepConnected([[0, floor_y, 0, S, floor_y + 1, S]], 6)
+    res["band"], res["supported_voxels"], res["debris_voxels"] = band, world.solidCount(), debris.solidCount()
+    down = vrc.capi.VRC_FACE_YN
+
+    def timed(fn, repeats):
+        out, last = [], None
+        for i in range(repeats + 1):
+            if last is not None and hasattr(last, "close"):
+                last.close()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            last = fn()
+            b.record()
+            b.synchronize()
+            if i:
+                out.append(a.elapsed_time(b))
+        return stat(out, 4), last
+
+    res["label_ms"], labels = timed(lambda: debris.labelComponents(6), pairs)
+    res["pieces"] = labels.count
+    offsets = torch.zeros((max(labels.count, 1), 3), dtype=torch.int32).cuda()
+    keep = torch.ones(max(labels.count, 1), dtype=torch.uint8).cuda()
+    torch.cuda.synchronize()
+    res["fall_ms"], st = timed(lambda: labels.fallDevice(offsets.data_ptr(), world, down), pairs)
+    res["rounds"], res["moved_pieces"], res["moved_voxels"], res["max_drop"] = int(st.rounds), int(st.moved_pieces), int(st.moved_voxels), int(st.max_drop)
+    res["fall_round_over_label"] = round(res["fall_ms"]["median"] / max(st.rounds, 1) / res["label_ms"]["median"], 3)
+    target = world.clone()
+    res["place_ms"], _ = timed(lambda: labels.placeDevice(offsets.data_ptr(), target, vrc.capi.VRC_COPY_OR, None, None) and None, pairs)
+    res["placed_voxels"] = target.solidCount()
+    res["select_ms"], _ = timed(lambda: labels.selectDevice(keep.data_ptr(), target, vrc.capi.VRC_COPY_OR, None), pairs)
+    for v in (labels, target, debris, world):
+        v.close()
+    scene.close()
+    return res
+
+
 def bench_stamp(vrc, depth, pairs):
     import math
     S = 1 << depth
@@ -884,9 +945,12 @@ def main():
     ap.add_argument("--components", action="store_true", help="time vrc_volume_label_components / vrc_labels_* (depth 9 unless --depths is given)")
     ap.add_argument("--distance", action="store_true", help="time vrc_volume_distance_field / vrc_distance_select / dilate (depth 9 unless --depths is given)")
     ap.add_argument("--stamp", action="store_true", help="time vrc_volume_stamp_affine next to vrc_volume_copy_region (depth 9 unless --depths is given)")
+    ap.add_argument("--fall", action="store_true", help="time vrc_fall_drops / vrc_fall_place next to vrc_volume_label_components of the same debris (depth 9 unless --depths is given)")
     ap.add_argument("--travel", action="store_true", help="time vrc_travel_field next to vrc_volume_flood from the same seeds (depth 9 unless --depths is given)")
     args = ap.parse_args()
     if args.travel and args.depths == [8, 9, 10]:
+        args.depths = [9]
+    if args.fall and args.depths == [8, 9, 10]:
         args.depths = [9]
     if args.stamp and args.depths == [8, 9, 10]:
         args.depths = [9]
@@ -910,11 +974,15 @@ def main():
     import cpuvoxelraycaster_amd as vrc
     if not torch.cuda.is_available():
         raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-    out = {"bench": "edit_travel" if args.travel else "edit_rects" if args.rects else "edit_stamp" if args.stamp else "edit_distance" if args.distance else "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
+    out = {"bench": "edit_fall" if args.fall else "edit_travel" if args.travel else "edit_rects" if args.rects else "edit_stamp" if args.stamp else "edit_distance" if args.distance else "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
     for d in args.depths:
-        out["depths"][str(d)] = (bench_travel if args.travel else bench_rects if args.rects else bench_stamp if args.stamp else bench_distance if args.distance else bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
+        out["depths"][str(d)] = (bench_fall if args.fall else bench_travel if args.travel else bench_rects if args.rects else bench_stamp if args.stamp else bench_distance if args.distance else bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
     print(json.dumps(out))
-    if args.travel:
+    if args.fall:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_fall.json")
+        with open(path, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+    elif args.travel:
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_travel.json")
         with open(path, "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
