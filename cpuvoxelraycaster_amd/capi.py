@@ -32,6 +32,11 @@ assert HIT_DTYPE.itemsize == 48 and LNODE_DTYPE.itemsize == 8
 # vrc_component (include/vrc.h): one record per connected component
 COMPONENT_DTYPE = np.dtype([("first", "<u4", 3), ("lo", "<u4", 3), ("hi", "<u4", 3), ("reserved", "<u4"), ("voxels", "<u8")])
 assert COMPONENT_DTYPE.itemsize == 48
+# vrc_piece_moments (include/vrc.h): n, the sums of c and of the six products c_a c_b over a piece's voxels, c = 2p + 1
+MOMENTS_DTYPE = np.dtype([("voxels", "<u8"), ("s1", "<u8", 3), ("s2", "<u8", 6)])
+# vrc_affine as a numpy record, for arrays of maps (Affine below is the same 64 bytes as a ctypes structure)
+AFFINE_DTYPE = np.dtype([("m", "<i4", 9), ("reserved", "<i4"), ("t", "<i8", 3)])
+assert MOMENTS_DTYPE.itemsize == 80 and AFFINE_DTYPE.itemsize == 64
 
 
 class VrcError(RuntimeError):
@@ -173,6 +178,7 @@ SYMBOLS = {
     "vrc_volume_copy_region": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "vrc_volume_stamp_affine": (_int, [_vp, _vp, C.POINTER(Affine), _vp, _vp, _int, _vp]),
     "vrc_affine_place": (_int, [_vp, _f32, _vp, _vp, _u32, _u32, C.POINTER(Affine), _vp, _vp]),
+    "vrc_affine_place_box": (_int, [_vp, _f32, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     "vrc_volume_clone": (_int, [_vp, C.POINTER(_vp)]),
     "vrc_volume_get_voxels": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
     "vrc_volume_count_boxes": (_int, [_vp, _u64, _vp, _vp, _int, _vp]),
@@ -187,6 +193,8 @@ SYMBOLS = {
     "vrc_labels_select": (_int, [_vp, _vp, _vp, _int, _int, _vp]),
     "vrc_fall_drops": (_int, [_vp, _vp, _int, _u32, _vp, _int, C.POINTER(FallStats)]),
     "vrc_fall_place": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp]),
+    "vrc_rigid_moments": (_int, [_vp, _u64, _u64, _vp, _int, _vp]),
+    "vrc_rigid_place_affine": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     "vrc_volume_distance_field": (_int, [_vp, _int, _int, C.POINTER(_vp), C.POINTER(DistanceStats)]),
     "vrc_distance_destroy": (_int, [_vp]),
     "vrc_distance_depth": (_u32, [_vp]),

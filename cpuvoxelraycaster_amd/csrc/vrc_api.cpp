@@ -371,14 +371,12 @@ extern "C" int vrc_hit_to_voxel(uint32_t depth, const vrc_hit* hit, uint32_t vox
 }
 
 // Host arithmetic only, in doubles.  rot is vrc_make_rotation's layout (columns), so R[b][a] -- the entry of the INVERSE
-// rotation's row a, column b -- is rot[3a + b].
-extern "C" int vrc_affine_place(const float rot[9], float scale, const float src_pivot[3], const float dst_pivot[3], uint32_t src_depth,
-                                uint32_t dst_depth, vrc_affine* map, uint32_t dst_lo[3], uint32_t dst_hi[3])
+// rotation's row a, column b -- is rot[3a + b].  The one body of vrc_affine_place and vrc_affine_place_box: the map, and the
+// bounding box of the forward image of the source box [src_lo, src_hi] (continuous coordinates), two voxels wider on every
+// side, clipped to dst.  The caller has refused NULLs and bad depths.
+static int place_box(const char* what, const float rot[9], float scale, const float src_pivot[3], const float dst_pivot[3], const double src_lo[3],
+                     const double src_hi[3], uint32_t dst_depth, vrc_affine* map, uint32_t dst_lo[3], uint32_t dst_hi[3])
 {
-    const char* what = "vrc_affine_place";
-    if (!rot || !src_pivot || !dst_pivot || !map || !dst_lo || !dst_hi) return fail(VRC_ERR_INVALID, "%s: null argument", what);
-    if (src_depth < 2 || src_depth > 10 || dst_depth < 2 || dst_depth > 10)
-        return fail(VRC_ERR_INVALID, "%s: depths %u and %u not in [2,10]", what, src_depth, dst_depth);
     bool finite = std::isfinite(scale);
     for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(rot[i]);
     for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(src_pivot[a]) && std::isfinite(dst_pivot[a]);
@@ -399,8 +397,7 @@ extern "C" int vrc_affine_place(const float rot[9], float scale, const float src
         if (!(std::fabs(t) <= 1099511627776.0)) return fail(VRC_ERR_INVALID, "%s: t[%d] = %g beyond +-2^40", what, a, t);
         out.t[a] = (int64_t)t;
     }
-    // the bounding box of the forward image of the source cube [0, S]^3, two voxels wider on every side, clipped to dst
-    const double Ss = (double)(1u << src_depth), Sd = (double)(1u << dst_depth);
+    const double Sd = (double)(1u << dst_depth);
     uint32_t lo[3], hi[3];
     bool empty = false;
     for (int r = 0; r < 3; ++r) {
@@ -408,7 +405,7 @@ extern "C" int vrc_affine_place(const float rot[9], float scale, const float src
         for (int corner = 0; corner < 8; ++corner) {
             double x = (double)dst_pivot[r];
             for (int c = 0; c < 3; ++c)
-                x += (double)scale * (double)rot[3 * c + r] * (((corner >> c) & 1 ? Ss : 0.0) - (double)src_pivot[c]);
+                x += (double)scale * (double)rot[3 * c + r] * (((corner >> c) & 1 ? src_hi[c] : src_lo[c]) - (double)src_pivot[c]);
             if (corner == 0 || x < least) least = x;
             if (corner == 0 || x > most) most = x;
         }
@@ -421,6 +418,31 @@ extern "C" int vrc_affine_place(const float rot[9], float scale, const float src
     for (int a = 0; a < 3; ++a) { dst_lo[a] = empty ? 0u : lo[a]; dst_hi[a] = empty ? 0u : hi[a]; }
     *map = out;
     return VRC_OK;
+}
+
+extern "C" int vrc_affine_place(const float rot[9], float scale, const float src_pivot[3], const float dst_pivot[3], uint32_t src_depth,
+                                uint32_t dst_depth, vrc_affine* map, uint32_t dst_lo[3], uint32_t dst_hi[3])
+{
+    const char* what = "vrc_affine_place";
+    if (!rot || !src_pivot || !dst_pivot || !map || !dst_lo || !dst_hi) return fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (src_depth < 2 || src_depth > 10 || dst_depth < 2 || dst_depth > 10)
+        return fail(VRC_ERR_INVALID, "%s: depths %u and %u not in [2,10]", what, src_depth, dst_depth);
+    const double Ss = (double)(1u << src_depth), lo[3] = {0.0, 0.0, 0.0}, hi[3] = {Ss, Ss, Ss};
+    return place_box(what, rot, scale, src_pivot, dst_pivot, lo, hi, dst_depth, map, dst_lo, dst_hi);
+}
+
+extern "C" int vrc_affine_place_box(const float rot[9], float scale, const float src_pivot[3], const float dst_pivot[3], const uint32_t src_lo[3],
+                                    const uint32_t src_hi[3], uint32_t dst_depth, vrc_affine* map, uint32_t dst_lo[3], uint32_t dst_hi[3])
+{
+    const char* what = "vrc_affine_place_box";
+    if (!rot || !src_pivot || !dst_pivot || !src_lo || !src_hi || !map || !dst_lo || !dst_hi) return fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (dst_depth < 2 || dst_depth > 10) return fail(VRC_ERR_INVALID, "%s: depth %u not in [2,10]", what, dst_depth);
+    double lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) {
+        if (src_lo[a] > src_hi[a]) return fail(VRC_ERR_INVALID, "%s: source box inverted on axis %d: %u above %u", what, a, src_lo[a], src_hi[a]);
+        lo[a] = (double)src_lo[a]; hi[a] = (double)src_hi[a];
+    }
+    return place_box(what, rot, scale, src_pivot, dst_pivot, lo, hi, dst_depth, map, dst_lo, dst_hi);
 }
 
 // The kernels replace some IEEE divisions / square roots by short sequences that are proven equal on the ranges they

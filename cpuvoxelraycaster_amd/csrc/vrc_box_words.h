@@ -17,6 +17,20 @@ __host__ __device__ __forceinline__ uint64_t brick_of(uint32_t n, uint32_t x, ui
 }
 __host__ __device__ __forceinline__ uint32_t voxel_bit(uint32_t x, uint32_t y, uint32_t z) { return (z & 1u) * 4u + (y & 1u) * 2u + (x & 1u); }
 
+// A voxel's KEY is its bit index in the field, 8 B + (z&1) 4 + (y&1) 2 + (x&1) with B its brick's byte index: the index of the
+// per-voxel arrays (the labels).  lg = log2 of the bricks per axis.
+__host__ __device__ __forceinline__ uint32_t voxel_key(uint32_t lg, uint32_t x, uint32_t y, uint32_t z)
+{
+    return 8u * ((((x >> 1) << lg | (y >> 1)) << lg) | (z >> 1)) + voxel_bit(x, y, z);
+}
+__host__ __device__ __forceinline__ void key_voxel(uint32_t lg, uint32_t key, uint32_t c[3])
+{
+    const uint32_t B = key >> 3, nm = (1u << lg) - 1u;
+    c[0] = 2u * (B >> (2u * lg)) + (key & 1u);
+    c[1] = 2u * ((B >> lg) & nm) + ((key >> 1) & 1u);
+    c[2] = 2u * (B & nm) + ((key >> 2) & 1u);
+}
+
 // lo_hi[0..5] clipped to the volume; false = empty, inverted or wholly outside
 __host__ __device__ __forceinline__ bool clip_box(const uint32_t* lo_hi, uint32_t S, uint32_t lo[3], uint32_t hi[3])
 {

@@ -45,19 +45,8 @@ struct Field {
     uint32_t flip;                            // ~0: M is the complement of the words (through the empty voxels)
 };
 
-__device__ __forceinline__ uint32_t key_of(const Field& f, uint32_t x, uint32_t y, uint32_t z)
-{
-    const uint32_t B = (((x >> 1) << f.lg | (y >> 1)) << f.lg) | (z >> 1);
-    return 8u * B + (z & 1u) * 4u + (y & 1u) * 2u + (x & 1u);
-}
-
-__device__ __forceinline__ void voxel_of(const Field& f, uint32_t key, uint32_t c[3])
-{
-    const uint32_t B = key >> 3, nm = (1u << f.lg) - 1u;
-    c[0] = 2u * (B >> (2u * f.lg)) + (key & 1u);
-    c[1] = 2u * ((B >> f.lg) & nm) + ((key >> 1) & 1u);
-    c[2] = 2u * (B & nm) + ((key >> 2) & 1u);
-}
+__device__ __forceinline__ uint32_t key_of(const Field& f, uint32_t x, uint32_t y, uint32_t z) { return voxel_key(f.lg, x, y, z); }
+__device__ __forceinline__ void voxel_of(const Field& f, uint32_t key, uint32_t c[3]) { key_voxel(f.lg, key, c); }
 
 __device__ __forceinline__ uint32_t load_label(const uint32_t* L, uint32_t a)
 {

@@ -1,0 +1,30 @@
+// vrc_rigid.h -- what a physics engine needs of the pieces of a labelling, and what it hands back (vrc_rigid.hip), as
+// vrc_snapshots.hip calls them: the raw moments of every piece, and the gather that writes every piece through its own
+// inverse affine map.  Like vrc_fall.h it knows arrays only; volumes, their ordering, the staging of host memory and the
+// argument checks stay with the entry points.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/vrc.h"
+
+namespace vrc {
+
+// the limits of a map (vrc.h: vrc_volume_stamp_affine): the entry points refuse what the host can read, the kernel drops the
+// piece whose map it finds beyond them
+constexpr int32_t AFFINE_M_LIMIT = 1 << 20;
+constexpr int64_t AFFINE_T_LIMIT = 1ll << 40;
+
+// out[k] = the moments of piece first + k, k < want, of `labels` (8^depth ids by key); first + want <= the number of pieces.
+// Zeroes out[0 .. want) and accumulates into it in ONE pass over the ids; no scratch.  out is DEVICE memory.  Enqueues on `st`.
+hipError_t moments_run(const uint32_t* labels, uint32_t depth, uint64_t first, uint64_t want, vrc_piece_moments* out, hipStream_t st);
+
+// for every piece i < pieces with keep[i] != 0 (keep == nullptr: all) and every voxel p of dst in box i (boxes: pieces x 6,
+// lo then hi, clipped to dst; nullptr: all of dst): with q = (maps[i] (2p + 1)) >> 17, dst(p) is set (VRC_COPY_OR) or cleared
+// (VRC_COPY_ANDNOT) iff labels(q) == i.  `records` are the labels' own: a piece's box bounds what is loaded.  A piece whose
+// map lies beyond the limits is dropped whole.  keep, maps and boxes are DEVICE memory.  One kernel, no scratch: a 2-D grid,
+// blockIdx.y striding over the pieces and blockIdx.x over the words of a piece's box.  Enqueues on `st`.  pieces >= 1.
+void place_affine_run(const uint32_t* labels, const vrc_component* records, uint64_t pieces, uint32_t depth, const uint8_t* keep,
+                      const vrc_affine* maps, const uint32_t* boxes, uint32_t* dst, uint32_t dst_depth, int op, hipStream_t st);
+
+}  // namespace vrc

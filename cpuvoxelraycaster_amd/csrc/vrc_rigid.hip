@@ -1,0 +1,293 @@
+// vrc_rigid.hip -- the pieces of a labelling as rigid bodies with a pose (include/vrc.h: vrc_rigid_moments,
+// vrc_rigid_place_affine): the raw moments a physics engine derives mass, centre of mass and inertia tensor from, and the
+// write-back of every piece through its own inverse affine map.  The labels are vrc_components.hip's: one uint32 id per KEY
+// (vrc_box_words.h: voxel_key / key_voxel), VRC_NO_COMPONENT outside M.  Exact in integers.
+//
+// Moments.  A lane owns a key, a workgroup GROUP x ROUNDS consecutive keys (256 occupancy words), as the labelling's passes
+// do; within it every wave walks its own 64 x ROUNDS consecutive keys, a quarter of them, 8 bricks = 16 voxels along z a round.  With c = 2p + 1 a voxel adds ten terms to its piece: 1, c_x, c_y, c_z and the six products.  One 64-bit atomic per
+// voxel and term would queue every voxel of a large piece on ten words, so the terms are summed on chip first; pieces are
+// spatially coherent, so most waves see ONE id:
+//   uniform   every voxel of the wave's 64 keys carries one id: the lanes add their terms to ten 32-bit registers (a term is
+//             below 2^22, a lane adds at most ROUNDS of them) and carry them from round to round while the id stays.  When it
+//             changes, and at the end, the wave sums the registers in 64 bits; at the end the four waves meet in LDS and the
+//             waves that hold the same id issue their ten atomics once -- a workgroup wholly inside one piece costs ten;
+//   few       a wave with several ids takes a leader's id, sums the matching lanes with shuffles (32 bits: 64 terms), lets
+//             the leader issue the ten atomics and masks the lanes off, FEW times at the most;
+//   many      whatever lanes are left then (a checkerboard: every lane its own id) issue their own ten atomics.
+// An id outside the window or VRC_NO_COMPONENT costs no atomic.  Every sum is below 2^53 (vrc.h), every atomic a 64-bit vector
+// atomic add at agent scope in plain HIP C++; integer adds commute, so the bytes do not depend on the schedule.
+//
+// Placement.  vrc_stamp.hip's gather with the id array for a source: one thread per (piece, destination occupancy word), the
+// 64-bit map evaluated once per word and the other 31 voxels following in 32-bit running sums.  The source bit of q is
+// "q lies in the piece's record box and id(q) == piece": the record box stands in for the volume in the stamp's miss / inside
+// test, so a word whose source bounding box misses the piece loads nothing.  The grid is 2-D and needs neither scratch nor
+// a look at the boxes from the host: blockIdx.y strides over the pieces, blockIdx.x over the words of that piece's box.
+// Pieces may overlap in dst, so a word is written with a 32-bit vector atomic OR / AND, and not at all where its 32 bits are
+// 0.  Within a wave every lane has a word of its own -- except in a destination of 4^3, where two brick rows share a word:
+// there the lanes that hit one word join their bits first.
+//
+// Measured on an MI355X at 512^3 on the fall benchmark's scene (tools/bench_edit.py --rigid, profiles/edit/bench_rigid.json; 404
+// loose blocks of 1.9 M voxels; device time by events, median of 5): the moments of all pieces 0.44 ms next to 0.20 ms of
+// vrc_labels_select in the same run -- the waves there are uniform, and since a wave walks consecutive keys (16 voxels along
+// z a round) and a block is 30 voxels long, a run of one id lasts about two rounds, after which the 64-bit wave sums and the
+// ten atomics come.  With the rounds of a wave GROUP keys = 64 voxels apart the id changed every round: 0.66 ms.  The
+// placement with pure-translation maps (0.16 M box words) 0.075 ms next to 0.19 ms of vrc_fall_place, with a 30-degree turn
+// about two axes (0.74 M box words) 0.078 ms: the same time for 4.5 times the words, so the fixed grid and the per-piece
+// set-up seem to set it at this size; not measured apart.
+#include "vrc_rigid.h"
+
+#include "vrc_box_words.h"
+
+namespace {
+
+constexpr uint32_t NONE = VRC_NO_COMPONENT;
+constexpr uint32_t GROUP = 256;               // lanes per workgroup
+constexpr uint32_t WAVES = GROUP / 64u;
+constexpr uint32_t ROUNDS = 32;               // a workgroup of the moments pass takes ROUNDS x GROUP consecutive keys
+constexpr uint32_t GROUP_KEYS = GROUP * ROUNDS;
+constexpr uint32_t WAVE_KEYS = 64u * ROUNDS;       // the consecutive keys one wave of the moments pass walks
+constexpr uint32_t SUMS = 10;                 // vrc_piece_moments as ten uint64: voxels, s1[3], s2[6]
+constexpr uint32_t FEW = 4;                   // ids a mixed wave reduces with shuffles before its lanes go alone
+
+static_assert(sizeof(vrc_piece_moments) == SUMS * 8u, "vrc_piece_moments is ten 64-bit sums");
+static_assert(sizeof(vrc_affine) == 64, "vrc_affine is 64 bytes");
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
+{
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// the registers of a uniform run, summed over the wave and added to record `slot` by lane 0; called by whole waves
+__device__ __forceinline__ void flush_run(const uint32_t acc[SUMS], uint32_t slot, unsigned long long* out)
+{
+    for (uint32_t k = 0; k < SUMS; ++k) {
+        const unsigned long long s = wave_sum((unsigned long long)acc[k]);
+        if ((threadIdx.x & 63u) == 0u) atomicAdd(out + (size_t)SUMS * slot + k, s);
+    }
+}
+
+__global__ __launch_bounds__(GROUP) void k_moments(uint32_t lg, uint32_t n_keys, const uint32_t* __restrict__ L, uint32_t first, uint32_t want,
+                                                   unsigned long long* out)
+{
+    __shared__ unsigned long long part[WAVES][SUMS];
+    __shared__ uint32_t part_slot[WAVES];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t acc[SUMS];
+    for (uint32_t k = 0; k < SUMS; ++k) acc[k] = 0u;
+    uint32_t run = NONE;                                                // wave-uniform: the record the registers belong to
+    for (uint32_t r = 0; r < ROUNDS; ++r) {
+        // a wave walks its own WAVE_KEYS CONSECUTIVE keys, 16 voxels further along z every round, so that a run lasts as long as the
+        // piece does along z; whole waves pass or fail the bound
+        const uint32_t key = blockIdx.x * GROUP_KEYS + wave * WAVE_KEYS + r * 64u + lane;
+        if (key >= n_keys) break;
+        const uint32_t id = L[key];
+        const uint32_t slot = id - first;
+        const bool in = id != NONE && id >= first && slot < want;
+        unsigned long long todo = __ballot(in);
+        if (!todo) continue;                                            // wave-uniform
+        uint32_t c[3], t[SUMS];
+        key_voxel(lg, key, c);
+        for (int a = 0; a < 3; ++a) c[a] = in ? 2u * c[a] + 1u : 0u;
+        t[0] = in ? 1u : 0u;
+        t[1] = c[0]; t[2] = c[1]; t[3] = c[2];
+        t[4] = c[0] * c[0]; t[5] = c[1] * c[1]; t[6] = c[2] * c[2];
+        t[7] = c[0] * c[1]; t[8] = c[0] * c[2]; t[9] = c[1] * c[2];
+        const uint32_t lslot = __shfl(slot, __ffsll((long long)todo) - 1);
+        if (__ballot(in && slot != lslot) == 0ull) {                    // uniform: carried in registers
+            if (run != lslot) {
+                if (run != NONE) flush_run(acc, run, out);
+                for (uint32_t k = 0; k < SUMS; ++k) acc[k] = 0u;
+                run = lslot;
+            }
+            for (uint32_t k = 0; k < SUMS; ++k) acc[k] += t[k];
+            continue;
+        }
+        for (uint32_t pass = 0; todo && pass < FEW; ++pass) {           // few: wave-uniform
+            const int leader = __ffsll((long long)todo) - 1;
+            const uint32_t ls = __shfl(slot, leader);
+            const bool mine = in && slot == ls;
+            const unsigned long long same = __ballot(mine);
+            todo &= ~same;
+            if (same & (same - 1ull)) {
+                for (uint32_t k = 0; k < SUMS; ++k) {
+                    const uint32_t s = wave_sum(mine ? t[k] : 0u);
+                    if ((int)lane == leader) atomicAdd(out + (size_t)SUMS * ls + k, (unsigned long long)s);
+                }
+            } else if ((int)lane == leader) {
+                for (uint32_t k = 0; k < SUMS; ++k) atomicAdd(out + (size_t)SUMS * ls + k, (unsigned long long)t[k]);
+            }
+        }
+        if ((todo >> lane) & 1ull)                                      // many: the lanes that are left
+            for (uint32_t k = 0; k < SUMS; ++k) atomicAdd(out + (size_t)SUMS * slot + k, (unsigned long long)t[k]);
+    }
+    // the end of the runs: the waves of the workgroup that hold the same record add once
+    unsigned long long total[SUMS];
+    for (uint32_t k = 0; k < SUMS; ++k) total[k] = run != NONE ? wave_sum((unsigned long long)acc[k]) : 0ull;
+    if (lane == 0u) {
+        part_slot[wave] = run;
+        for (uint32_t k = 0; k < SUMS; ++k) part[wave][k] = total[k];
+    }
+    __syncthreads();
+    if (threadIdx.x >= SUMS) return;
+    const uint32_t k = threadIdx.x;
+    for (uint32_t w = 0; w < WAVES; ++w) {
+        const uint32_t slot = part_slot[w];
+        if (slot == NONE) continue;
+        bool earlier = false;
+        for (uint32_t v = 0; v < w; ++v) earlier = earlier || part_slot[v] == slot;
+        if (earlier) continue;
+        unsigned long long s = 0ull;
+        for (uint32_t v = w; v < WAVES; ++v) s += part_slot[v] == slot ? part[v][k] : 0ull;
+        atomicAdd(out + (size_t)SUMS * slot + k, s);
+    }
+}
+
+// The 32 source bits of one destination word, under `mask`: bit = 1 iff the voxel's source q lies in [rlo, rhi) and carries
+// `piece`.  q / frac / step as in vrc_stamp.hip's gather_word; ext = rhi - rlo.  INSIDE: every q of the word lies in the box.
+template <bool INSIDE>
+__device__ __forceinline__ uint32_t gather_piece(const uint32_t* __restrict__ L, uint32_t lg, uint32_t piece, const uint32_t rlo[3], const uint32_t ext[3],
+                                                 const int32_t q[3], const int32_t frac[3], const int32_t step[3][3], uint32_t mask)
+{
+    uint32_t bits = 0u;
+#pragma unroll
+    for (uint32_t col = 0; col < 4u; ++col) {          // col = y * 2 + x, as in a brick's bit index
+        int32_t d[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) d[a] = frac[a] + ((col & 1u) ? step[a][0] : 0) + ((col & 2u) ? step[a][1] : 0);
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) {
+            const uint32_t bit = (k >> 1) * 8u + (k & 1u) * 4u + col;
+            if ((mask >> bit) & 1u) {
+                const uint32_t x = (uint32_t)(q[0] + (d[0] >> 17)), y = (uint32_t)(q[1] + (d[1] >> 17)), z = (uint32_t)(q[2] + (d[2] >> 17));
+                // unsigned: a coordinate below rlo, a negative one included, is a large one
+                if (INSIDE || (x - rlo[0] < ext[0] && y - rlo[1] < ext[1] && z - rlo[2] < ext[2]))
+                    bits |= (L[voxel_key(lg, x, y, z)] == piece ? 1u : 0u) << bit;
+            }
+#pragma unroll
+            for (int a = 0; a < 3; ++a) d[a] += step[a][2];
+        }
+    }
+    return bits;
+}
+
+__global__ __launch_bounds__(GROUP) void k_place_affine(const uint32_t* __restrict__ L, uint32_t lg, const vrc_component* __restrict__ records, uint32_t C,
+                                                        const uint8_t* __restrict__ keep, const vrc_affine* __restrict__ maps, const uint32_t* __restrict__ boxes,
+                                                        uint32_t* dst, uint32_t Sd, int op)
+{
+    const uint32_t n = Sd >> 1, Ss = 2u << lg;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t piece = blockIdx.y; piece < C; piece += gridDim.y) {  // uniform for the workgroup, and so is all that skips a piece
+        if (keep && keep[piece] == 0) continue;
+        const vrc_affine map = maps[piece];
+        bool legal = map.reserved == 0;
+        for (int i = 0; i < 9; ++i) legal = legal && map.m[i] <= vrc::AFFINE_M_LIMIT && map.m[i] >= -vrc::AFFINE_M_LIMIT;
+        for (int a = 0; a < 3; ++a) legal = legal && map.t[a] <= vrc::AFFINE_T_LIMIT && map.t[a] >= -vrc::AFFINE_T_LIMIT;
+        if (!legal) continue;
+        uint32_t given[6], lo[3], hi[3];
+        for (uint32_t a = 0; a < 6u; ++a) given[a] = boxes ? boxes[6u * piece + a] : (a < 3u ? 0u : Sd);
+        if (!clip_box(given, Sd, lo, hi)) continue;
+        uint32_t rlo[3], ext[3];
+        int32_t rmin[3], rmax[3];
+        bool none = false;
+        for (int a = 0; a < 3; ++a) {
+            rlo[a] = records[piece].lo[a];
+            const uint32_t rhi = min(records[piece].hi[a], Ss);
+            none = none || rlo[a] >= rhi;
+            ext[a] = rhi - rlo[a];
+            rmin[a] = (int32_t)rlo[a]; rmax[a] = (int32_t)rhi - 1;
+        }
+        if (none) continue;
+        const BoxWords b = box_words(lo, hi);
+        // per source axis: s per destination voxel step (|.| <= 2^21), and the extremes of delta over a word's 2 x 2 x 8 voxels
+        int32_t step[3][3], dmin[3], dmax[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) step[a][c] = 2 * map.m[3 * a + c];
+            dmin[a] = min(step[a][0], 0) + min(step[a][1], 0) + 7 * min(step[a][2], 0);
+            dmax[a] = max(step[a][0], 0) + max(step[a][1], 0) + 7 * max(step[a][2], 0);
+        }
+        for (uint64_t base = (uint64_t)blockIdx.x * GROUP; base < b.items; base += (uint64_t)gridDim.x * GROUP) {      // uniform trip count
+            const uint64_t it = base + threadIdx.x;
+            uint32_t bits = 0u;
+            RowWord r;
+            r.w = 0u;
+            if (it < b.items && row_word(b, n, it, r)) {
+                const uint32_t mask = box_mask(b, r);
+                // z of the word's first voxel, relative to the row (negative where the word starts in the row before: n = 2;
+                // those voxels are outside the mask)
+                const int64_t z0 = 2 * ((int64_t)(4u * r.w) - (int64_t)r.base);
+                const int64_t c[3] = {4 * (int64_t)r.cx + 1, 4 * (int64_t)r.cy + 1, 2 * z0 + 1};   // 2p + 1: the centre in half voxels
+                int32_t q[3], frac[3];
+                bool miss = mask == 0u, inside = true;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const int64_t s = (int64_t)map.m[3 * a] * c[0] + (int64_t)map.m[3 * a + 1] * c[1] + (int64_t)map.m[3 * a + 2] * c[2] + map.t[a];
+                    q[a] = (int32_t)(s >> 17);                 // |s| < 2^41
+                    frac[a] = (int32_t)(s & 0x1ffff);
+                    const int32_t qmin = q[a] + ((frac[a] + dmin[a]) >> 17), qmax = q[a] + ((frac[a] + dmax[a]) >> 17);
+                    miss = miss || qmax < rmin[a] || qmin > rmax[a];
+                    inside = inside && qmin >= rmin[a] && qmax <= rmax[a];
+                }
+                if (!miss)
+                    bits = inside ? gather_piece<true>(L, lg, piece, rlo, ext, q, frac, step, mask) : gather_piece<false>(L, lg, piece, rlo, ext, q, frac, step, mask);
+            }
+            if (n >= 4u) {                                              // a lane, a word
+                if (bits) {
+                    if (op == VRC_COPY_OR) atomicOr(&dst[r.w], bits);
+                    else atomicAnd(&dst[r.w], ~bits);
+                }
+                continue;
+            }
+            // 4^3: two words in all, shared by the rows
+            const uint32_t word = (uint32_t)r.w;
+            unsigned long long todo = __ballot(bits != 0u);
+            while (todo) {                                              // wave-uniform
+                const int leader = __ffsll((long long)todo) - 1;
+                const uint32_t lword = __shfl(word, leader);
+                const bool mine = bits != 0u && word == lword;
+                todo &= ~__ballot(mine);
+                uint32_t joined = mine ? bits : 0u;
+                for (int o = 32; o; o >>= 1) joined |= __shfl_xor(joined, o);
+                if ((int)lane == leader) {
+                    if (op == VRC_COPY_OR) atomicOr(&dst[lword], joined);
+                    else atomicAnd(&dst[lword], ~joined);
+                }
+            }
+        }
+    }
+}
+
+}  // namespace
+
+namespace vrc {
+
+hipError_t moments_run(const uint32_t* labels, uint32_t depth, uint64_t first, uint64_t want, vrc_piece_moments* out, hipStream_t st)
+{
+    const hipError_t e = hipMemsetAsync(out, 0, (size_t)want * sizeof(vrc_piece_moments), st);
+    if (e != hipSuccess) return e;
+    const uint32_t n_keys = 1u << (3u * depth);
+    hipLaunchKernelGGL(k_moments, dim3((n_keys + GROUP_KEYS - 1u) / GROUP_KEYS), dim3(GROUP), 0, st, depth - 1u, n_keys, labels, (uint32_t)first, (uint32_t)want,
+                       (unsigned long long*)out);
+    return hipGetLastError();
+}
+
+void place_affine_run(const uint32_t* labels, const vrc_component* records, uint64_t pieces, uint32_t depth, const uint8_t* keep, const vrc_affine* maps,
+                      const uint32_t* boxes, uint32_t* dst, uint32_t dst_depth, int op, hipStream_t st)
+{
+    // about 16384 workgroups in all: the more pieces, the fewer workgroups share a piece's box; the rest is the strides
+    const uint32_t Sd = 1u << dst_depth, zero[3] = {0u, 0u, 0u}, all[3] = {Sd, Sd, Sd};
+    const uint32_t gy = pieces > 4096u ? 4096u : (uint32_t)pieces;
+    const uint64_t whole = (box_word_items(zero, all) + GROUP - 1u) / GROUP;
+    const uint32_t share = 16384u / gy;
+    const uint32_t gx = whole < share ? (uint32_t)whole : share;
+    hipLaunchKernelGGL(k_place_affine, dim3(gx, gy), dim3(GROUP), 0, st, labels, depth - 1u, records, (uint32_t)pieces, keep, maps, boxes, dst, Sd, op);
+}
+
+}  // namespace vrc

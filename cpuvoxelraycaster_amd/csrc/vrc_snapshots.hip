@@ -1,5 +1,6 @@
 // vrc_snapshots.hip -- the snapshots taken from an editable volume (include/vrc.h): the labels of its connected components
-// (vrc_volume_label_components, vrc_labels_*; kernels in vrc_components.hip) and its exact squared Euclidean distance field
+// (vrc_volume_label_components, vrc_labels_*; kernels in vrc_components.hip; the pieces' moments and posed placement,
+// vrc_rigid_*, kernels in vrc_rigid.hip) and its exact squared Euclidean distance field
 // with the selection by distance that grow / shrink / hollow are made of (vrc_volume_distance_field, vrc_distance_*;
 // kernels in vrc_distance.hip), and the travel-distance field from a set of seeds, kept in the same snapshot object, with the
 // routes read off it (vrc_travel_field, vrc_travel_trace_paths; kernels in vrc_travel.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
@@ -13,6 +14,7 @@
 #include "vrc_components.h"
 #include "vrc_distance.h"
 #include "vrc_fall.h"
+#include "vrc_rigid.h"
 #include "vrc_travel.h"
 #include "vrc_volume_state.h"
 
@@ -220,6 +222,74 @@ extern "C" int vrc_fall_place(const vrc_labels* l, const uint8_t* keep, const in
     }
     if (e == hipSuccess) {
         vrc::place_run(l->d_ids, l->depth, d_keep, d_offsets, dst->d_bricks, op, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = finish(dst, mem, st, true);
+    if (d_stage) (void)hipFree(d_stage);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+// ---- the pieces as rigid bodies with a pose (the rules: include/vrc.h; the kernels: vrc_rigid.hip) ---------------
+
+extern "C" int vrc_rigid_moments(const vrc_labels* l, uint64_t first, uint64_t capacity, vrc_piece_moments* out, int mem, void* stream)
+{
+    const char* what = "vrc_rigid_moments";
+    if (!l) return vrc::fail(VRC_ERR_INVALID, "%s: null labels", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
+    const uint64_t want = first < l->count ? (capacity < l->count - first ? capacity : l->count - first) : 0u;
+    if (!want) return VRC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = (size_t)want * sizeof(vrc_piece_moments);
+    vrc_piece_moments* d_out = out;
+    vrc_piece_moments* d_stage = nullptr;
+    hipError_t e = hipSetDevice(l->device);
+    if (mem == VRC_MEM_HOST) {
+        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, bytes);
+        d_out = d_stage;
+    }
+    if (e == hipSuccess) e = vrc::moments_run(l->d_ids, l->depth, first, want, d_out, st);
+    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipStreamSynchronize(st);
+    if (d_stage) (void)hipFree(d_stage);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+extern "C" int vrc_rigid_place_affine(const vrc_labels* l, const uint8_t* keep, const vrc_affine* maps, const uint32_t* boxes, vrc_volume* dst, int op, int mem,
+                                      void* stream)
+{
+    const char* what = "vrc_rigid_place_affine";
+    if (!l || !dst) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_op(what, op)) return rc;
+    if (op == VRC_COPY_REPLACE) return vrc::fail(VRC_ERR_INVALID, "%s: VRC_COPY_REPLACE has no meaning where pieces may overlap", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (dst->device != l->device) return vrc::fail(VRC_ERR_INVALID, "%s: labels on device %d, volume on device %d", what, l->device, dst->device);
+    if (!maps && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null maps with %llu components", what, (unsigned long long)l->count);
+    if (mem == VRC_MEM_HOST)
+        for (uint64_t i = 0; i < l->count; ++i)
+            if (const int rc = check_affine(what, maps + i, (long long)i)) return rc;
+    if (!l->count) return VRC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t C = (size_t)l->count, map_bytes = C * sizeof(vrc_affine), box_bytes = boxes ? C * 24u : 0u, keep_bytes = keep ? C : 0u;
+    hipError_t e = hipSetDevice(l->device);
+    if (e == hipSuccess) e = order_behind_edits(dst, st);
+    const uint8_t* d_keep = keep;
+    const vrc_affine* d_maps = maps;
+    const uint32_t* d_boxes = boxes;
+    uint8_t* d_stage = nullptr;
+    if (mem == VRC_MEM_HOST) {                       // staged: the maps, then the boxes, then the keep bytes
+        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, map_bytes + box_bytes + keep_bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_stage, maps, map_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && boxes) e = hipMemcpyAsync(d_stage + map_bytes, boxes, box_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && keep) e = hipMemcpyAsync(d_stage + map_bytes + box_bytes, keep, keep_bytes, hipMemcpyHostToDevice, st);
+        d_maps = (const vrc_affine*)d_stage;
+        d_boxes = boxes ? (const uint32_t*)(d_stage + map_bytes) : nullptr;
+        d_keep = keep ? d_stage + map_bytes + box_bytes : nullptr;
+    }
+    if (e == hipSuccess) {
+        vrc::place_affine_run(l->d_ids, l->d_records, l->count, l->depth, d_keep, d_maps, d_boxes, dst->d_bricks, dst->depth, op, st);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = finish(dst, mem, st, true);

@@ -562,12 +562,7 @@ extern "C" int vrc_volume_stamp_affine(vrc_volume* dst, vrc_volume* src, const v
     if (!dst || !src || !map || !dst_lo || !dst_hi) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
     if (src == dst) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
     if (const int rc = check_op(what, op)) return rc;
-    if (map->reserved != 0) return vrc::fail(VRC_ERR_INVALID, "%s: reserved is %d, not 0", what, map->reserved);
-    // the limits that keep s = m (2p + 1) + t below 2^41 and a word's deltas below 2^25
-    for (int i = 0; i < 9; ++i)
-        if (map->m[i] > (1 << 20) || map->m[i] < -(1 << 20)) return vrc::fail(VRC_ERR_INVALID, "%s: m[%d] = %d beyond +-2^20", what, i, map->m[i]);
-    for (int a = 0; a < 3; ++a)
-        if (map->t[a] > (1ll << 40) || map->t[a] < -(1ll << 40)) return vrc::fail(VRC_ERR_INVALID, "%s: t[%d] = %lld beyond +-2^40", what, a, (long long)map->t[a]);
+    if (const int rc = check_affine(what, map, -1)) return rc;
     if (src->device != dst->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, src->device, dst->device);
     const uint32_t box[6] = {dst_lo[0], dst_lo[1], dst_lo[2], dst_hi[0], dst_hi[1], dst_hi[2]};
     uint32_t lo[3], hi[3];

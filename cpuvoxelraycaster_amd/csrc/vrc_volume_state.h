@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "../../include/vrc.h"
 #include "vrc_build_grids.h"
@@ -59,6 +60,21 @@ inline int check_connectivity(const char* what, int connectivity)
 inline int check_through(const char* what, int through)
 {
     return through == VRC_FLOOD_SOLID || through == VRC_FLOOD_EMPTY ? VRC_OK : vrc::fail(VRC_ERR_INVALID, "%s: bad through %d", what, through);
+}
+
+// the limits of an affine map that keep s = m (2p + 1) + t below 2^41 and a word's deltas below 2^25 (vrc.h:
+// vrc_volume_stamp_affine); `piece` < 0: the call has one map, else the text names the piece
+inline int check_affine(const char* what, const vrc_affine* map, long long piece)
+{
+    char of[40] = "";
+    if (piece >= 0) snprintf(of, sizeof of, "piece %lld: ", piece);
+    if (map->reserved != 0) return vrc::fail(VRC_ERR_INVALID, "%s: %sreserved is %d, not 0", what, of, map->reserved);
+    for (int i = 0; i < 9; ++i)
+        if (map->m[i] > (1 << 20) || map->m[i] < -(1 << 20)) return vrc::fail(VRC_ERR_INVALID, "%s: %sm[%d] = %d beyond +-2^20", what, of, i, map->m[i]);
+    for (int a = 0; a < 3; ++a)
+        if (map->t[a] > (1ll << 40) || map->t[a] < -(1ll << 40))
+            return vrc::fail(VRC_ERR_INVALID, "%s: %st[%d] = %lld beyond +-2^40", what, of, a, (long long)map->t[a]);
+    return VRC_OK;
 }
 
 // orders `st` (nullptr: the NULL stream) behind the last asynchronous edit: for the calls that read the occupancy, and for

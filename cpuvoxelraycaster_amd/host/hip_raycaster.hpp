@@ -194,6 +194,16 @@ private:
 
 class HipVoxelVolume;
 
+// mass, centre of mass (continuous voxel coordinates) and inertia tensor about it (row-major) of one piece, a voxel being a
+// unit cube of unit mass (include/vrc.h: vrc_rigid_moments).  Mass and centre are the exact values rounded once; an inertia
+// entry goes through long double (a numerator of up to 82 bits, a division, a sum) before it is rounded to double: within one
+// unit in the last place of the exact value, not the correctly rounded one the Python layer's rationals give.
+struct HipMassProperties {
+    double mass = 0.0;
+    double centre[3] = {0.0, 0.0, 0.0};
+    double inertia[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+};
+
 // The pieces of a volume, named (include/vrc.h: vrc_volume_label_components): a snapshot on the device that later edits
 // of the volume do not change.  Ids run 0 .. count() - 1 by ascending key of each piece's first voxel.  Movable, RAII.
 class HipVoxelLabels {
@@ -235,6 +245,68 @@ public:
     // dst gains (VRC_COPY_OR) or loses (VRC_COPY_ANDNOT) every voxel of the pieces with keep[id] != 0 (nullptr: all), each
     // piece moved by its own offset; what leaves the volume is dropped
     inline void place(const std::vector<int32_t>& offsets, HipVoxelVolume& dst, int op = VRC_COPY_OR, const std::vector<uint8_t>* keep = nullptr) const;
+    // the raw moments of the pieces [first, first + capacity) that exist (include/vrc.h: vrc_rigid_moments), exact integers
+    std::vector<vrc_piece_moments> moments(uint64_t first = 0, uint64_t capacity = ~0ull) const
+    {
+        const uint64_t C = count(), n = first < C ? std::min(capacity, C - first) : 0;
+        std::vector<vrc_piece_moments> out((size_t)n);
+        if (n) check(vrc_rigid_moments(l_, first, n, out.data(), VRC_MEM_HOST, nullptr), "vrc_rigid_moments");
+        return out;
+    }
+    // what a physics engine starts from: the integer sums combined in 128-bit integers, then long double (see HipMassProperties)
+    std::vector<HipMassProperties> massProperties(uint64_t first = 0, uint64_t capacity = ~0ull) const
+    {
+        const std::vector<vrc_piece_moments> mo = moments(first, capacity);
+        std::vector<HipMassProperties> out(mo.size());
+        static const int pair[6][2] = {{0, 0}, {1, 1}, {2, 2}, {0, 1}, {0, 2}, {1, 2}};
+        for (size_t i = 0; i < mo.size(); ++i) {
+            const vrc_piece_moments& m = mo[i];
+            if (!m.voxels) continue;
+            const long double n = (long double)m.voxels;
+            long double central[6];            // sum of r_a r_b about the centre of mass: (n s2_ab - s1_a s1_b) / (4n)
+            for (int j = 0; j < 6; ++j) {
+                const __int128 num = (__int128)m.voxels * (__int128)m.s2[j] - (__int128)m.s1[pair[j][0]] * (__int128)m.s1[pair[j][1]];
+                central[j] = (long double)num / (4.0L * n);
+            }
+            HipMassProperties& o = out[i];
+            o.mass = (double)n;
+            for (int a = 0; a < 3; ++a) {
+                o.centre[a] = (double)((long double)m.s1[a] / (2.0L * n));
+                o.inertia[4 * a] = (double)(central[(a + 1) % 3] + central[(a + 2) % 3] + n / 6.0L);
+            }
+            o.inertia[1] = o.inertia[3] = (double)-central[3];
+            o.inertia[2] = o.inertia[6] = (double)-central[4];
+            o.inertia[5] = o.inertia[7] = (double)-central[5];
+        }
+        return out;
+    }
+    // The maps and boxes of placeAffine (vrc_affine_place_box of every piece's record box): every piece turned by `rot`
+    // (vrc_make_rotation's layout) and resized by `scale` about src_pivots[3i..] -- its centre of mass with nullptr -- which
+    // lands on dst_pivots[3i..], continuous voxel coordinates of a volume of dst_depth.  boxes gets count() x 6 numbers.
+    std::vector<vrc_affine> poses(const float rot[9], const std::vector<float>& dst_pivots, uint32_t dst_depth, std::vector<uint32_t>& boxes,
+                                  float scale = 1.0f, const std::vector<float>* src_pivots = nullptr) const
+    {
+        const size_t C = (size_t)count();
+        if (dst_pivots.size() != 3 * C) throw std::invalid_argument("HipVoxelLabels::poses: dst_pivots must have three entries per component");
+        if (src_pivots && src_pivots->size() != 3 * C) throw std::invalid_argument("HipVoxelLabels::poses: src_pivots must have three entries per component");
+        const std::vector<vrc_component> records = components();
+        std::vector<HipMassProperties> mass;
+        if (!src_pivots) mass = massProperties();
+        std::vector<vrc_affine> maps(C);
+        boxes.assign(6 * C, 0u);
+        for (size_t i = 0; i < C; ++i) {
+            float pivot[3];
+            for (int a = 0; a < 3; ++a) pivot[a] = src_pivots ? (*src_pivots)[3 * i + a] : (float)mass[i].centre[a];
+            check(vrc_affine_place_box(rot, scale, pivot, &dst_pivots[3 * i], records[i].lo, records[i].hi, dst_depth, &maps[i], &boxes[6 * i], &boxes[6 * i + 3]),
+                  "vrc_affine_place_box");
+        }
+        return maps;
+    }
+    // dst (any depth) gains (VRC_COPY_OR) or loses (VRC_COPY_ANDNOT) every piece with keep[id] != 0 (nullptr: all), each read
+    // through its own inverse map inside its own box of dst (count() x 6, lo then hi; nullptr: all of dst) --
+    // include/vrc.h: vrc_rigid_place_affine
+    inline void placeAffine(const std::vector<vrc_affine>& maps, HipVoxelVolume& dst, int op = VRC_COPY_OR, const std::vector<uint32_t>* boxes = nullptr,
+                            const std::vector<uint8_t>* keep = nullptr) const;
     vrc_labels* handle() const { return l_; }
 
 private:
@@ -773,6 +845,18 @@ inline void HipVoxelLabels::place(const std::vector<int32_t>& offsets, HipVoxelV
     dst.flush();
     check(vrc_fall_place(l_, keep && !keep->empty() ? keep->data() : nullptr, offsets.empty() ? nullptr : offsets.data(), dst.handle(), op, VRC_MEM_HOST, nullptr),
           "vrc_fall_place");
+}
+
+inline void HipVoxelLabels::placeAffine(const std::vector<vrc_affine>& maps, HipVoxelVolume& dst, int op, const std::vector<uint32_t>* boxes,
+                                        const std::vector<uint8_t>* keep) const
+{
+    if (maps.size() != count()) throw std::invalid_argument("HipVoxelLabels::placeAffine: maps must have one entry per component");
+    if (boxes && boxes->size() != count() * 6u) throw std::invalid_argument("HipVoxelLabels::placeAffine: boxes must have six entries per component");
+    if (keep && keep->size() != count()) throw std::invalid_argument("HipVoxelLabels::placeAffine: keep must have one byte per component");
+    dst.flush();
+    check(vrc_rigid_place_affine(l_, keep && !keep->empty() ? keep->data() : nullptr, maps.empty() ? nullptr : maps.data(),
+                                 boxes && !boxes->empty() ? boxes->data() : nullptr, dst.handle(), op, VRC_MEM_HOST, nullptr),
+          "vrc_rigid_place_affine");
 }
 
 inline void HipVoxelDistance::select(uint32_t lo, uint32_t hi, HipVoxelVolume& dst, int op) const

@@ -175,6 +175,55 @@ def affine_place(rot, scale, src_pivot, dst_pivot, src_depth, dst_depth):
     return a, tuple(int(v) for v in lo), tuple(int(v) for v in hi)
 
 
+def affine_place_box(rot, scale, src_pivot, dst_pivot, src_lo, src_hi, dst_depth):
+    """affine_place for a part of the source, the voxel box [src_lo, src_hi) -- a piece by its record box -- in place of the
+    whole cube (include/vrc.h: vrc_affine_place_box).  Returns (capi.Affine, lo, hi)."""
+    rot = np.ascontiguousarray(rot, np.float32).reshape(9)
+    sp, dp = np.ascontiguousarray(src_pivot, np.float32).reshape(3), np.ascontiguousarray(dst_pivot, np.float32).reshape(3)
+    slo, shi = np.ascontiguousarray(src_lo, np.uint32).reshape(3), np.ascontiguousarray(src_hi, np.uint32).reshape(3)
+    a, lo, hi = capi.Affine(), np.zeros(3, np.uint32), np.zeros(3, np.uint32)
+    check(capi.load().vrc_affine_place_box(ptr(rot), float(scale), ptr(sp), ptr(dp), ptr(slo), ptr(shi), int(dst_depth), C.byref(a), ptr(lo), ptr(hi)))
+    return a, tuple(int(v) for v in lo), tuple(int(v) for v in hi)
+
+
+def affine_array(maps):
+    """a sequence of capi.Affine (or an array of capi.AFFINE_DTYPE) as one contiguous capi.AFFINE_DTYPE array"""
+    if isinstance(maps, np.ndarray) and maps.dtype == capi.AFFINE_DTYPE:
+        return np.ascontiguousarray(maps).reshape(-1)
+    out = np.zeros(len(maps), capi.AFFINE_DTYPE)
+    for i, a in enumerate(maps):
+        out[i] = (list(a.m), a.reserved, list(a.t))
+    return out
+
+
+def mass_properties(moments):
+    """(mass, centre, inertia) as float64 arrays of shapes (k,), (k, 3), (k, 3, 3) from k capi.MOMENTS_DTYPE records
+    (include/vrc.h: vrc_rigid_moments).  A voxel is a unit cube of unit mass: mass n, centre of mass s1 / (2n) in continuous
+    voxel coordinates, and about it I_aa = sum(r_b^2 + r_c^2) + n/6, I_ab = -sum(r_a r_b).  Every entry is the exact rational
+    value of the integer sums, rounded once to float64."""
+    from fractions import Fraction
+    moments = np.asarray(moments, capi.MOMENTS_DTYPE).reshape(-1)
+    k = len(moments)
+    mass, centre, inertia = np.zeros(k), np.zeros((k, 3)), np.zeros((k, 3, 3))
+    pair = {(0, 0): 0, (1, 1): 1, (2, 2): 2, (0, 1): 3, (0, 2): 4, (1, 2): 5}
+    for i, rec in enumerate(moments):
+        n = int(rec["voxels"])
+        if n == 0:
+            continue
+        s1 = [int(v) for v in rec["s1"]]
+        s2 = [int(v) for v in rec["s2"]]
+        # sum of r_a r_b about the centre of mass, r = c / 2 - s1 / (2n): (n s2_ab - s1_a s1_b) / (4n)
+        central = {ab: Fraction(n * s2[j] - s1[ab[0]] * s1[ab[1]], 4 * n) for ab, j in pair.items()}
+        mass[i] = float(n)
+        for a in range(3):
+            centre[i, a] = float(Fraction(s1[a], 2 * n))
+            b, c = (a + 1) % 3, (a + 2) % 3
+            inertia[i, a, a] = float(central[(b, b)] + central[(c, c)] + Fraction(n, 6))
+        for (a, b) in ((0, 1), (0, 2), (1, 2)):
+            inertia[i, a, b] = inertia[i, b, a] = float(-central[(a, b)])
+    return mass, centre, inertia
+
+
 class VoxelVolume:
     """Device-resident editable occupancy of an S^3 volume (include/vrc.h: vrc_volume_*).  Edits are batched; commit()
     builds a new immutable LSVO on the device, bit-identical to compileSVO of the current voxel set."""
@@ -763,6 +812,73 @@ class VoxelLabels:
     def placeDevice(self, offsets_ptr, dst, op=capi.VRC_COPY_OR, keep_ptr=None, stream=None):
         """the same with the offsets (and `count` bytes of keep) in device memory, asynchronous on `stream`"""
         check(capi.load().vrc_fall_place(self._h, ptr(keep_ptr), ptr(offsets_ptr), dst._h, int(op), capi.VRC_MEM_DEVICE, ptr(stream)))
+        return dst
+
+    def moments(self, first=0, capacity=None):
+        """the raw moments of the pieces [first, first + capacity) that exist, as capi.MOMENTS_DTYPE: voxels, s1 (the sums of
+        c = 2p + 1 per axis) and s2 (the sums of c_x c_x, c_y c_y, c_z c_z, c_x c_y, c_x c_z, c_y c_z) -- include/vrc.h:
+        vrc_rigid_moments.  Exact integers."""
+        if capacity is None:
+            capacity = max(self.count - first, 0)
+        out = np.zeros(min(capacity, max(self.count - first, 0)), capi.MOMENTS_DTYPE)
+        check(capi.load().vrc_rigid_moments(self._h, first, len(out), ptr(out) if len(out) else None, capi.VRC_MEM_HOST, None))
+        return out
+
+    def momentsDevice(self, first, capacity, out_ptr, stream=None):
+        """the same into device memory (80 bytes a record), asynchronous on `stream`"""
+        check(capi.load().vrc_rigid_moments(self._h, first, capacity, ptr(out_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def massProperties(self, first=0, capacity=None):
+        """(mass, centre of mass, inertia tensor about it) of the pieces of the window, float64 arrays of shapes (k,), (k, 3)
+        and (k, 3, 3): mass_properties of moments()."""
+        return mass_properties(self.moments(first, capacity))
+
+    def poses(self, rot, dst_pivot, src_pivot=None, scale=1.0, dst_depth=None):
+        """(maps, boxes) for placeAffine: piece i turned by rot (9 floats for all, or (count, 9); make_rotation's layout) and
+        resized by `scale` (one, or one per piece) about src_pivot[i] -- its centre of mass by default -- which lands on
+        dst_pivot[i] ((count, 3), continuous voxel coordinates of a volume of dst_depth, the labels' depth by default).  maps is
+        a capi.AFFINE_DTYPE array, boxes (count, 6) uint32: vrc_affine_place_box of every piece's record box."""
+        rot = np.ascontiguousarray(rot, np.float32)
+        rot = np.broadcast_to(rot.reshape(-1, 9), (self.count, 9))
+        scale = np.broadcast_to(np.asarray(scale, np.float32).reshape(-1), (self.count,))
+        dst_pivot = np.ascontiguousarray(dst_pivot, np.float32).reshape(self.count, 3)
+        if src_pivot is None:
+            src_pivot = self.massProperties()[1]
+        src_pivot = np.ascontiguousarray(src_pivot, np.float32).reshape(self.count, 3)
+        records = self.components()
+        maps, boxes = np.zeros(self.count, capi.AFFINE_DTYPE), np.zeros((self.count, 6), np.uint32)
+        for i in range(self.count):
+            a, lo, hi = affine_place_box(rot[i], scale[i], src_pivot[i], dst_pivot[i], records["lo"][i], records["hi"][i],
+                                         self.depth if dst_depth is None else dst_depth)
+            maps[i] = (list(a.m), a.reserved, list(a.t))
+            boxes[i] = lo + hi
+        return maps, boxes
+
+    def placeAffine(self, maps, boxes=None, dst=None, op=capi.VRC_COPY_OR, keep=None):
+        """dst (a new volume of the labels' depth with None; any depth otherwise) gains (VRC_COPY_OR) or loses
+        (VRC_COPY_ANDNOT) every piece with keep[id] != 0 (None: all), each read through its OWN inverse map inside its own box
+        of dst ((count, 6) uint32 lo, hi; None: all of dst) -- include/vrc.h: vrc_rigid_place_affine.  maps: count capi.Affine
+        or a capi.AFFINE_DTYPE array, e.g. from poses().  Returns dst."""
+        maps = affine_array(maps)
+        if len(maps) != self.count:
+            raise ValueError(f"maps has {len(maps)} entries for {self.count} components")
+        if boxes is not None:
+            boxes = np.ascontiguousarray(boxes, np.uint32).reshape(-1, 6)
+            if len(boxes) != self.count:
+                raise ValueError(f"boxes has {len(boxes)} rows for {self.count} components")
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, np.uint8).reshape(-1)
+            if len(keep) != self.count:
+                raise ValueError(f"keep has {len(keep)} entries for {self.count} components")
+        if dst is None:
+            dst = VoxelVolume(self.depth, self.device)
+        check(capi.load().vrc_rigid_place_affine(self._h, ptr(keep), ptr(maps) if self.count else None, ptr(boxes), dst._h, int(op), capi.VRC_MEM_HOST, None))
+        return dst
+
+    def placeAffineDevice(self, maps_ptr, dst, boxes_ptr=None, op=capi.VRC_COPY_OR, keep_ptr=None, stream=None):
+        """the same with the maps (64 bytes each), the boxes and `count` bytes of keep in device memory, asynchronous on
+        `stream`; a piece whose map lies beyond the limits is dropped whole"""
+        check(capi.load().vrc_rigid_place_affine(self._h, ptr(keep_ptr), ptr(maps_ptr), ptr(boxes_ptr), dst._h, int(op), capi.VRC_MEM_DEVICE, ptr(stream)))
         return dst
 
     def bytes(self):

@@ -389,6 +389,14 @@ int vrc_volume_stamp_affine(vrc_volume *dst, vrc_volume *src, const vrc_affine *
                             const uint32_t dst_lo[3], const uint32_t dst_hi[3], int op, void *stream);
 int vrc_affine_place(const float rot[9], float scale, const float src_pivot[3], const float dst_pivot[3],
                      uint32_t src_depth, uint32_t dst_depth, vrc_affine *map, uint32_t dst_lo[3], uint32_t dst_hi[3]);
+/* vrc_affine_place_box: vrc_affine_place for a part of the source -- one piece of a labelling by its record box.  The same
+ * arithmetic and refusals (one body in csrc/vrc_api.cpp); the only difference is that the source cube [0, S_src]^3 is
+ * replaced by the box [src_lo, src_hi] in voxel coordinates (a vrc_component's lo / hi as they are: hi is exclusive, so the
+ * box is the continuous extent of the voxels).  With src_lo = 0 and src_hi = S_src the bytes are vrc_affine_place's.  There
+ * is no source depth to refuse; a box with src_lo above src_hi on an axis is VRC_ERR_INVALID. */
+int vrc_affine_place_box(const float rot[9], float scale, const float src_pivot[3], const float dst_pivot[3],
+                         const uint32_t src_lo[3], const uint32_t src_hi[3], uint32_t dst_depth,
+                         vrc_affine *map, uint32_t dst_lo[3], uint32_t dst_hi[3]);
 /* A new volume with src's depth, device, occupancy (after every edit issued so far) and albedo tables: the undo
  * snapshot.  Synchronous. */
 int vrc_volume_clone(vrc_volume *src, vrc_volume **out);
@@ -553,6 +561,82 @@ int vrc_fall_drops(const vrc_labels *l, vrc_volume *fixed, int direction, uint32
                     int32_t *offsets /* C x 3: D_i * g */, int mem, vrc_fall_stats *stats);
 int vrc_fall_place(const vrc_labels *l, const uint8_t *keep /* C bytes, NULL = all */,
                      const int32_t *offsets /* C x 3 */, vrc_volume *dst, int op, int mem, void *stream);
+
+/* The pieces of a labelling as rigid bodies with a pose, on the device: what a physics engine needs of every piece, and what
+ * it hands back.  vrc_rigid_moments gives the raw moments that mass, centre of mass and inertia tensor follow from, without
+ * a dense download of the ids; vrc_rigid_place_affine writes every piece through its OWN inverse affine map -- a set of
+ * debris tumbling -- in one call where vrc_labels_select and vrc_volume_stamp_affine would take a scratch volume and two
+ * calls per piece.  Both work on a vrc_labels snapshot and, like vrc_fall_*, carry the name of what they serve.  Exact in
+ * integers.
+ *
+ * vrc_rigid_moments.  With c = 2p + 1, the centre of voxel p in half voxels, the record of piece i holds n = its number of
+ * voxels, s1 = the sums of c_x, c_y, c_z over them and s2 = the sums of c_x c_x, c_y c_y, c_z c_z, c_x c_y, c_x c_z, c_y c_z.
+ * Nothing can overflow: at depth 10 c <= 2047 and n <= 2^30, so every sum is below 2^22 * 2^30 = 2^52 < 2^53 -- a double
+ * holds each exactly.  `voxels` equals the vrc_component's.  A voxel taken as a unit cube of unit mass, the mass is n, the
+ * centre of mass s1 / (2n) in continuous voxel coordinates, and with r measured from it
+ * I_aa = sum(r_b^2 + r_c^2) + n/6 and I_ab = -sum(r_a r_b), where sum(r_a r_b) = (n s2_ab - s1_a s1_b) / (4n).
+ * The window is vrc_labels_components': the records of [first, first + capacity) that lie in [0, C) are written in id order
+ * to out[0..] and nothing beyond them is touched; first >= C writes nothing, capacity == 0 with out == NULL is legal.  The
+ * call is stateless: the snapshot gains no cache and vrc_labels_bytes does not change.  VRC_MEM_HOST is staged and
+ * synchronous; VRC_MEM_DEVICE zeroes and fills `out` in place, asynchronous on `stream`, with no scratch left to free.  Sums
+ * of integers do not depend on their order: two calls give identical bytes.
+ * The device (csrc/vrc_rigid.hip) makes ONE pass over the id array, a lane per key, and adds straight into `out` with 64-bit
+ * vector atomics -- but not one per voxel and sum.  Pieces are spatially coherent, and a wave walks consecutive keys (16
+ * voxels further along z every round): a wave whose 64 keys carry one id keeps
+ * the ten sums in registers from round to round, the four waves of a workgroup meet in LDS, and a workgroup wholly inside a
+ * piece issues ten atomics for its 8192 keys.  A wave with several ids takes a leader's id, sums the matching lanes with
+ * shuffles and masks them off, four times at the most; only the lanes left after that (a checkerboard of one-voxel pieces)
+ * issue their own.  Ids outside the window and voxels outside M cost no atomic.
+ *
+ * vrc_rigid_place_affine.  The rule is vrc_volume_stamp_affine's, per piece.  For every piece i with keep[i] != 0 (keep: C
+ * bytes, NULL = all) and every voxel p of dst in box i (boxes: C x 6 uint32, lo then hi as for vrc_volume_fill_boxes,
+ * clipped to dst; an empty or inverted box skips the piece; NULL = all of dst for every piece):
+ * q = (m_i (2p + 1) + t_i) >> 17 exactly as there, the source bit is 1 iff q lies inside the labels' volume and id(q) == i
+ * -- a voxel of another piece, or one outside M, reads 0 -- and dst(p) is ORed with the bit (VRC_COPY_OR) or has it cleared
+ * (VRC_COPY_ANDNOT).  VRC_COPY_REPLACE is VRC_ERR_INVALID, as for vrc_fall_place: pieces may overlap in dst and a gather of
+ * many pieces has no unique "replace".  OR and ANDNOT commute, so the result is unique whatever the overlap and the schedule,
+ * and two calls give identical bytes; nothing outside the boxes changes.  dst may differ in depth from the labels, must be
+ * on the labels' device, and may be the labelled medium itself, because the labels are a snapshot.  vrc_affine_place_box
+ * makes map and box of a piece from a rotation, a scale and two pivots.
+ * Limits and refusals are the stamp's: an |m| entry above 2^20, a |t| entry above 2^40, reserved != 0, NULL handles, NULL
+ * `maps` when C > 0, a device mismatch, a bad `mem` and an unknown op are VRC_ERR_INVALID; with VRC_MEM_HOST every map is
+ * checked before any device call ("piece <i>: ..." names the first bad one).  With VRC_MEM_DEVICE the host cannot read the
+ * maps: a piece whose map breaks a limit is then dropped whole, like an out-of-range offset in vrc_fall_place.  C == 0 is a
+ * no-op.
+ * mem says where keep, maps and boxes live.  VRC_MEM_HOST is staged (one block, freed before return) and synchronous;
+ * VRC_MEM_DEVICE works in place and is asynchronous on `stream`, ordered behind dst's last asynchronous edit and recorded as
+ * dst's last edit, with the warning of vrc_volume_copy_region: do not edit dst on ANOTHER stream before the call has run.
+ * The device form keeps no scratch at all: the launch is a 2-D grid in which blockIdx.y strides over the pieces and
+ * blockIdx.x over the destination occupancy words of that piece's box, so the host never needs the boxes' sizes.
+ * The device (csrc/vrc_rigid.hip) takes one thread per (piece, destination word of 2 x 2 x 8 voxels), evaluates the 64-bit
+ * map once per word and lets the other 31 voxels follow in 32-bit running sums, as the stamp does.  The piece's record box
+ * [lo, hi) stands in for the source volume: a word whose source bounding box misses it costs no load of ids, one wholly
+ * inside drops the per-voxel tests.  Words are written with 32-bit vector atomic OR / AND, a word whose 32 bits are all 0
+ * issues nothing; the lanes of a wave own different words, except in a 4^3 destination, where two brick rows share a word
+ * and the lanes that hit one word join their bits first.
+ * Measured on an MI355X at 512^3 on the fall benchmark's scene (tools/bench_edit.py --rigid, profiles/edit/bench_rigid.json;
+ * 404 loose blocks of 1.9 M voxels, the largest 17644, over 5.6 M supported ones; device time by events, median of 5,
+ * everything in device memory): vrc_rigid_moments of all pieces 0.44 ms next to 0.20 ms of vrc_labels_select in the same run,
+ * 2.15 times a pass that reads the same ids and sums nothing.  The scene's waves take the uniform path, but briefly: a wave
+ * walks consecutive keys, 16 voxels further along z every round, and a block is 30 voxels long, so a run of one id lasts
+ * about two rounds before the wave sums its registers in 64 bits and issues ten atomics.  (With a wave's rounds 64 voxels
+ * apart along z, as the labelling's passes place them, the id changed every round and the same call took 0.66 ms.)  The
+ * share of the three paths has not been counted.  vrc_rigid_place_affine with pure-translation maps (the fall's offsets,
+ * boxes = the moved record boxes, 0.16 M words of dst in all; the result equal to vrc_fall_place's voxel for voxel) 0.075 ms
+ * next to 0.19 ms of vrc_fall_place, 0.39 times: it visits the words of the boxes and not the 134 M keys of the volume.
+ * With every piece turned 30 degrees about x, then y, about its own centre of mass (boxes from vrc_affine_place_box, wider
+ * by the turn and the margin: 0.74 M words) 0.078 ms.  4.5 times the words in the same time: at this size the fixed grid of
+ * 40 x 404 workgroups and each one's per-piece set-up seem to set the time, not the words; that has not been measured
+ * apart.  NULL boxes have not been timed: every piece then visits every word of dst. */
+typedef struct vrc_piece_moments {       /* 80 bytes */
+    uint64_t voxels;                     /* n */
+    uint64_t s1[3];                      /* sum of c_x, c_y, c_z             with c = 2p + 1 (centres in half voxels) */
+    uint64_t s2[6];                      /* sum of c_x c_x, c_y c_y, c_z c_z, c_x c_y, c_x c_z, c_y c_z */
+} vrc_piece_moments;
+int vrc_rigid_moments(const vrc_labels *l, uint64_t first, uint64_t capacity, vrc_piece_moments *out, int mem, void *stream);
+int vrc_rigid_place_affine(const vrc_labels *l, const uint8_t *keep /* C bytes, NULL = all */,
+                           const vrc_affine *maps /* C */, const uint32_t *boxes /* C x 6 lo,hi; NULL = all of dst */,
+                           vrc_volume *dst, int op, int mem, void *stream);
 
 /* The exact squared Euclidean distance field, on the device: how far every voxel is from the surface, and with it grow /
  * shrink by r voxels (dilate, erode, open, close), hollowing a solid down to a shell, clearance queries, and a field a

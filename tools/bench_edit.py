@@ -117,6 +117,16 @@ the NULL stream, one warm-up, `--pairs` repetitions, median and range:
   place      vrc_fall_place of every piece into a copy of the supported part (OR), offsets in device memory
   select     vrc_labels_select of every piece of the same labels into a volume (OR)
   fall_round_over_label = fall / rounds / label
+With --rigid (printed and written to profiles/edit/bench_rigid.json), the pieces as rigid bodies on the --fall scene (the same
+terrain, bands and cuts: a few hundred loose blocks), device time by events on the NULL stream, one warm-up, `--pairs`
+repetitions, median and range, everything in device memory:
+  moments          vrc_rigid_moments of all pieces              next to  select: vrc_labels_select of all pieces (one pass over
+                                                                         the same id array, no sums)
+  place_translate  vrc_rigid_place_affine with pure-translation maps (the fall's offsets; boxes = the record boxes moved by
+                   them)                                        next to  fall_place: vrc_fall_place with the same offsets; the
+                                                                         two results are compared voxel for voxel
+  place_turn       vrc_rigid_place_affine with every piece turned 30 degrees about x, then y, about its own centre of mass
+                   (maps and boxes from VoxelLabels.poses)
 No threshold is applied; the numbers are reported."""
 import argparse
 import json
@@ -885,6 +895,91 @@ def bench_fall(vrc, depth, pairs):
     return res
 
 
+def bench_rigid(vrc, depth, pairs):
+    """vrc_rigid_moments next to vrc_labels_select, vrc_rigid_place_affine next to vrc_fall_place, on bench_fall's scene"""
+    import math
+    import torch
+    S = 1 << depth
+    res = {"size": S, "pairs": pairs}
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    world = vrc.VoxelVolume.fromScene(scene)
+    floor_y = S // 2 + 1
+    band = [0, floor_y + 24, 0, S, floor_y + 28, S]
+    cuts = [band, [0, floor_y + 44, 0, S, floor_y + 47, S]]
+    cuts += [[c, floor_y + 24, 0, c + 2, S, S] for c in range(30, S, 32)] + [[0, floor_y + 24, c, S, S, c + 2] for c in range(30, S, 32)]
+    world.fillBoxes(cuts, False)
+    debris = world.keepConnected([[0, floor_y, 0, S, floor_y + 1, S]], 6)
+    labels = debris.labelComponents(6)
+    C_ = labels.count
+    res["pieces"], res["supported_voxels"], res["debris_voxels"] = C_, world.solidCount(), debris.solidCount()
+    OR = vrc.capi.VRC_COPY_OR
+
+    def timed(fn):
+        out = []
+        for i in range(pairs + 1):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if i:
+                out.append(a.elapsed_time(b))
+        return stat(out, 4)
+
+    def box_words(boxes):
+        """the (piece, destination word) work items of the placement: vrc_box_words.h's count over the non-empty boxes"""
+        return int(sum(((int(b[3]) - 1) // 2 - int(b[0]) // 2 + 1) * ((int(b[4]) - 1) // 2 - int(b[1]) // 2 + 1) * ((((int(b[5]) - 1) // 2 - int(b[2]) // 2) + 3) // 4 + 1)
+                       for b in boxes if all(b[a] < b[a + 3] for a in range(3))))
+
+    def on_device(array):
+        return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).cuda()
+
+    keep = torch.ones(max(C_, 1), dtype=torch.uint8).cuda()
+    moments = torch.zeros(max(C_, 1) * 80, dtype=torch.uint8).cuda()
+    target = world.clone()
+    torch.cuda.synchronize()
+    res["moments_ms"] = timed(lambda: labels.momentsDevice(0, C_, moments.data_ptr(), None))
+    res["select_ms"] = timed(lambda: labels.selectDevice(keep.data_ptr(), target, OR, None))
+    res["moments_over_select"] = round(res["moments_ms"]["median"] / res["select_ms"]["median"], 2)
+    got = moments.cpu().numpy().view(vrc.capi.MOMENTS_DTYPE)[:C_]
+    records = labels.components()
+    assert np.array_equal(got["voxels"], records["voxels"]) and int(got["voxels"].sum()) == res["debris_voxels"]
+    res["largest_piece_voxels"] = int(got["voxels"].max(initial=0))
+
+    offsets, st = labels.fall(world, vrc.capi.VRC_FACE_YN)
+    res["max_drop"] = int(st.max_drop)
+    maps = np.zeros(C_, vrc.capi.AFFINE_DTYPE)
+    maps["m"][:] = [65536, 0, 0, 0, 65536, 0, 0, 0, 65536]
+    maps["t"][:] = -(offsets.astype(np.int64) << 17)
+    boxes = np.concatenate([np.clip(records["lo"].astype(np.int64) + offsets, 0, S), np.clip(records["hi"].astype(np.int64) + offsets, 0, S)], axis=1).astype(np.uint32)
+    res["translate_box_words"] = box_words(boxes)
+    d_offsets, d_maps, d_boxes = on_device(offsets), on_device(maps), on_device(boxes)
+    by_fall, by_maps = world.clone(), world.clone()
+    torch.cuda.synchronize()
+    res["fall_place_ms"] = timed(lambda: labels.placeDevice(d_offsets.data_ptr(), by_fall, OR, None, None))
+    res["place_translate_ms"] = timed(lambda: labels.placeAffineDevice(d_maps.data_ptr(), by_maps, d_boxes.data_ptr(), OR, None, None))
+    res["place_translate_over_fall_place"] = round(res["place_translate_ms"]["median"] / res["fall_place_ms"]["median"], 2)
+    res["placed_voxels"] = by_maps.solidCount()
+    assert res["placed_voxels"] == by_fall.solidCount() and np.array_equal(by_maps.download(), by_fall.download()), "translation maps differ from vrc_fall_place"
+
+    c, s = math.cos(math.radians(30)), math.sin(math.radians(30))
+    rx = np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
+    ry = np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
+    rot = np.ascontiguousarray((ry @ rx).T, np.float32).reshape(9)
+    centre = labels.massProperties()[1]
+    maps, boxes = labels.poses(rot, centre)
+    d_maps, d_boxes = on_device(maps), on_device(boxes)
+    turned = world.clone()
+    torch.cuda.synchronize()
+    res["place_turn_ms"] = timed(lambda: labels.placeAffineDevice(d_maps.data_ptr(), turned, d_boxes.data_ptr(), OR, None, None))
+    res["turned_voxels"] = turned.solidCount()
+    res["turn_box_words"] = box_words(boxes)
+    for v in (turned, by_fall, by_maps, target, labels, debris, world):
+        v.close()
+    scene.close()
+    return res
+
+
 def bench_stamp(vrc, depth, pairs):
     import math
     S = 1 << depth
@@ -946,11 +1041,14 @@ def main():
     ap.add_argument("--distance", action="store_true", help="time vrc_volume_distance_field / vrc_distance_select / dilate (depth 9 unless --depths is given)")
     ap.add_argument("--stamp", action="store_true", help="time vrc_volume_stamp_affine next to vrc_volume_copy_region (depth 9 unless --depths is given)")
     ap.add_argument("--fall", action="store_true", help="time vrc_fall_drops / vrc_fall_place next to vrc_volume_label_components of the same debris (depth 9 unless --depths is given)")
+    ap.add_argument("--rigid", action="store_true", help="time vrc_rigid_moments / vrc_rigid_place_affine next to vrc_labels_select / vrc_fall_place (depth 9 unless --depths is given)")
     ap.add_argument("--travel", action="store_true", help="time vrc_travel_field next to vrc_volume_flood from the same seeds (depth 9 unless --depths is given)")
     args = ap.parse_args()
     if args.travel and args.depths == [8, 9, 10]:
         args.depths = [9]
     if args.fall and args.depths == [8, 9, 10]:
+        args.depths = [9]
+    if args.rigid and args.depths == [8, 9, 10]:
         args.depths = [9]
     if args.stamp and args.depths == [8, 9, 10]:
         args.depths = [9]
@@ -974,11 +1072,15 @@ def main():
     import cpuvoxelraycaster_amd as vrc
     if not torch.cuda.is_available():
         raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-    out = {"bench": "edit_fall" if args.fall else "edit_travel" if args.travel else "edit_rects" if args.rects else "edit_stamp" if args.stamp else "edit_distance" if args.distance else "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
+    out = {"bench": "edit_rigid" if args.rigid else "edit_fall" if args.fall else "edit_travel" if args.travel else "edit_rects" if args.rects else "edit_stamp" if args.stamp else "edit_distance" if args.distance else "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
     for d in args.depths:
-        out["depths"][str(d)] = (bench_fall if args.fall else bench_travel if args.travel else bench_rects if args.rects else bench_stamp if args.stamp else bench_distance if args.distance else bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
+        out["depths"][str(d)] = (bench_rigid if args.rigid else bench_fall if args.fall else bench_travel if args.travel else bench_rects if args.rects else bench_stamp if args.stamp else bench_distance if args.distance else bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
     print(json.dumps(out))
-    if args.fall:
+    if args.rigid:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_rigid.json")
+        with open(path, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+    elif args.fall:
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_fall.json")
         with open(path, "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
