@@ -37,6 +37,11 @@ MOMENTS_DTYPE = np.dtype([("voxels", "<u8"), ("s1", "<u8", 3), ("s2", "<u8", 6)]
 # vrc_affine as a numpy record, for arrays of maps (Affine below is the same 64 bytes as a ctypes structure)
 AFFINE_DTYPE = np.dtype([("m", "<i4", 9), ("reserved", "<i4"), ("t", "<i8", 3)])
 assert MOMENTS_DTYPE.itemsize == 80 and AFFINE_DTYPE.itemsize == 64
+# vrc_piece_contact (include/vrc.h): a posed piece against a world -- its voxel count, and count, sum of c = 2p + 1 and sum of
+# normals over the voxels inside the world's solid (overlap) and over those face to face with it (touch)
+CONTACT_DTYPE = np.dtype([("posed", "<u8"), ("overlap", "<u8"), ("overlap_s1", "<u8", 3), ("overlap_n", "<i8", 3),
+                          ("touch", "<u8"), ("touch_s1", "<u8", 3), ("touch_n", "<i8", 3), ("reserved", "<u8")])
+assert CONTACT_DTYPE.itemsize == 128
 
 
 class VrcError(RuntimeError):
@@ -85,6 +90,12 @@ class FallStats(C.Structure):
 class Affine(C.Structure):
     """vrc_affine (include/vrc.h): the inverse map of vrc_volume_stamp_affine, m row-major with 16 fractional bits"""
     _fields_ = [("m", C.c_int32 * 9), ("reserved", C.c_int32), ("t", C.c_int64 * 3)]
+
+
+class PieceContact(C.Structure):
+    """vrc_piece_contact (include/vrc.h): the same 128 bytes as CONTACT_DTYPE"""
+    _fields_ = [("posed", C.c_uint64), ("overlap", C.c_uint64), ("overlap_s1", C.c_uint64 * 3), ("overlap_n", C.c_int64 * 3),
+                ("touch", C.c_uint64), ("touch_s1", C.c_uint64 * 3), ("touch_n", C.c_int64 * 3), ("reserved", C.c_uint64)]
 
 
 # every symbol include/vrc.h declares: (restype, argtypes)
@@ -195,6 +206,7 @@ SYMBOLS = {
     "vrc_fall_place": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp]),
     "vrc_rigid_moments": (_int, [_vp, _u64, _u64, _vp, _int, _vp]),
     "vrc_rigid_place_affine": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
+    "vrc_rigid_contacts": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "vrc_volume_distance_field": (_int, [_vp, _int, _int, C.POINTER(_vp), C.POINTER(DistanceStats)]),
     "vrc_distance_destroy": (_int, [_vp]),
     "vrc_distance_depth": (_u32, [_vp]),

@@ -1,6 +1,6 @@
 // vrc_rigid.h -- what a physics engine needs of the pieces of a labelling, and what it hands back (vrc_rigid.hip), as
-// vrc_snapshots.hip calls them: the raw moments of every piece, and the gather that writes every piece through its own
-// inverse affine map.  Like vrc_fall.h it knows arrays only; volumes, their ordering, the staging of host memory and the
+// vrc_snapshots.hip calls them: the raw moments of every piece, the gather that writes every piece through its own
+// inverse affine map, and the same gather ending in the contact record of every posed piece against a world.  Like vrc_fall.h it knows arrays only; volumes, their ordering, the staging of host memory and the
 // argument checks stay with the entry points.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,5 +26,14 @@ hipError_t moments_run(const uint32_t* labels, uint32_t depth, uint64_t first, u
 // blockIdx.y striding over the pieces and blockIdx.x over the words of a piece's box.  Enqueues on `st`.  pieces >= 1.
 void place_affine_run(const uint32_t* labels, const vrc_component* records, uint64_t pieces, uint32_t depth, const uint8_t* keep,
                       const vrc_affine* maps, const uint32_t* boxes, uint32_t* dst, uint32_t dst_depth, int op, hipStream_t st);
+
+// out[i] = the contact record (vrc.h: vrc_rigid_contacts) of piece i < pieces against `world` (8^world_depth voxels as
+// occupancy words, only read): the voxels place_affine_run would set with the same keep, maps and boxes -- one copy of the
+// gather serves both -- counted, and those inside a solid voxel of the world (overlap) or face to face with one or with the
+// volume's faces (touch) summed with their centres and normals.  Zeroes out[0 .. pieces) and adds into it in ONE kernel of
+// place_affine_run's grid; a skipped piece keeps its zero record.  keep, maps, boxes and out are DEVICE memory; no scratch.
+// Enqueues on `st`.  pieces >= 1.
+hipError_t contacts_run(const uint32_t* labels, const vrc_component* records, uint64_t pieces, uint32_t depth, const uint8_t* keep,
+                        const vrc_affine* maps, const uint32_t* boxes, const uint32_t* world, uint32_t world_depth, vrc_piece_contact* out, hipStream_t st);
 
 }  // namespace vrc

@@ -1,6 +1,7 @@
 // vrc_rigid.hip -- the pieces of a labelling as rigid bodies with a pose (include/vrc.h: vrc_rigid_moments,
-// vrc_rigid_place_affine): the raw moments a physics engine derives mass, centre of mass and inertia tensor from, and the
-// write-back of every piece through its own inverse affine map.  The labels are vrc_components.hip's: one uint32 id per KEY
+// vrc_rigid_place_affine, vrc_rigid_contacts): the raw moments a physics engine derives mass, centre of mass and inertia
+// tensor from, the write-back of every piece through its own inverse affine map, and the contact record of every piece
+// under such a map against a world.  The labels are vrc_components.hip's: one uint32 id per KEY
 // (vrc_box_words.h: voxel_key / key_voxel), VRC_NO_COMPONENT outside M.  Exact in integers.
 //
 // Moments.  A lane owns a key, a workgroup GROUP x ROUNDS consecutive keys (256 occupancy words), as the labelling's passes
@@ -34,6 +35,19 @@
 // placement with pure-translation maps (0.16 M box words) 0.075 ms next to 0.19 ms of vrc_fall_place, with a 30-degree turn
 // about two axes (0.74 M box words) 0.078 ms: the same time for 4.5 times the words, so the fixed grid and the per-piece
 // set-up seem to set it at this size; not measured apart.
+//
+// Contacts.  The placement's grid, per-piece set-up (pose_piece) and per-word gather (posed_word), one copy for both kernels;
+// where the placement stores the gathered word, k_contacts reduces it.  A word with no gathered bit -- almost all of a
+// generous box -- ends there.  Another loads the world word and at most six neighbour words, builds W*(p - e_a) and
+// W*(p + e_a) for its 32 voxels by shifts under constant masks (a neighbour beyond the volume is all ones; a 4^3 world, whose
+// rows share words, is brought to the same form by world_word), and adds popcounts: the counts, the normals as differences,
+// the sums of c = 2p + 1 from the x and y parity planes and the three bit planes of the layer number.  32 bits in a lane, 64
+// from the wave sums on; the four waves meet in LDS and lanes 0..14 issue the non-zero ones of the 15 sums as 64-bit vector
+// atomic adds in plain HIP C++.  A workgroup that gathered nothing for a piece issues none.
+// Measured on the same scene (tools/bench_edit.py --contacts, profiles/edit/bench_contacts.json; the zeroing of the records
+// included): translation maps against the supported part 0.111 ms next to 0.081 ms of the placement with the same maps and
+// boxes in the same run (1.37 times), the 30-degree turn 0.118 ms next to 0.080 ms (1.48 times); against the whole medium,
+// where most gathered words meet solid, 0.110 and 0.116 ms.  The passes have not been timed apart.
 #include "vrc_rigid.h"
 
 #include "vrc_box_words.h"
@@ -49,7 +63,11 @@ constexpr uint32_t WAVE_KEYS = 64u * ROUNDS;       // the consecutive keys one w
 constexpr uint32_t SUMS = 10;                 // vrc_piece_moments as ten uint64: voxels, s1[3], s2[6]
 constexpr uint32_t FEW = 4;                   // ids a mixed wave reduces with shuffles before its lanes go alone
 
+constexpr uint32_t CONTACT_SUMS = 15;         // vrc_piece_contact: posed, overlap (count, s1[3], n[3]), touch (the same); then `reserved`
+constexpr uint32_t CONTACT_WORDS = 16;
+
 static_assert(sizeof(vrc_piece_moments) == SUMS * 8u, "vrc_piece_moments is ten 64-bit sums");
+static_assert(sizeof(vrc_piece_contact) == CONTACT_WORDS * 8u, "vrc_piece_contact is 15 64-bit sums and a reserved word");
 static_assert(sizeof(vrc_affine) == 64, "vrc_affine is 64 bytes");
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
@@ -176,6 +194,73 @@ __device__ __forceinline__ uint32_t gather_piece(const uint32_t* __restrict__ L,
     return bits;
 }
 
+// What a workgroup knows of a piece before it walks the words of the piece's box: the per-piece set-up of the two kernels
+// that gather posed pieces (k_place_affine stores the gathered bits, k_contacts reduces them).
+struct Posed {
+    vrc_affine map;
+    BoxWords b;                          // the piece's box of the destination, clipped
+    uint32_t rlo[3], ext[3];             // the piece's record box in the labels' volume: what bounds the loads of ids
+    int32_t rmin[3], rmax[3];
+    int32_t step[3][3], dmin[3], dmax[3];        // per source axis: s per destination voxel step (|.| <= 2^21), and the extremes of delta over a word's 2 x 2 x 8 voxels
+};
+
+// false: the piece is skipped whole -- keep[piece] == 0, a map beyond the limits, an empty or inverted box, an empty record.
+// Uniform for the workgroup.  Sd / Ss: the voxels per axis of the destination / of the labels' volume.
+__device__ __forceinline__ bool pose_piece(const vrc_component* __restrict__ records, uint32_t piece, const uint8_t* __restrict__ keep,
+                                           const vrc_affine* __restrict__ maps, const uint32_t* __restrict__ boxes, uint32_t Sd, uint32_t Ss, Posed& s)
+{
+    if (keep && keep[piece] == 0) return false;
+    s.map = maps[piece];
+    bool legal = s.map.reserved == 0;
+    for (int i = 0; i < 9; ++i) legal = legal && s.map.m[i] <= vrc::AFFINE_M_LIMIT && s.map.m[i] >= -vrc::AFFINE_M_LIMIT;
+    for (int a = 0; a < 3; ++a) legal = legal && s.map.t[a] <= vrc::AFFINE_T_LIMIT && s.map.t[a] >= -vrc::AFFINE_T_LIMIT;
+    if (!legal) return false;
+    uint32_t given[6], lo[3], hi[3];
+    for (uint32_t a = 0; a < 6u; ++a) given[a] = boxes ? boxes[6u * piece + a] : (a < 3u ? 0u : Sd);
+    if (!clip_box(given, Sd, lo, hi)) return false;
+    bool none = false;
+    for (int a = 0; a < 3; ++a) {
+        s.rlo[a] = records[piece].lo[a];
+        const uint32_t rhi = min(records[piece].hi[a], Ss);
+        none = none || s.rlo[a] >= rhi;
+        s.ext[a] = rhi - s.rlo[a];
+        s.rmin[a] = (int32_t)s.rlo[a]; s.rmax[a] = (int32_t)rhi - 1;
+    }
+    if (none) return false;
+    s.b = box_words(lo, hi);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s.step[a][c] = 2 * s.map.m[3 * a + c];
+        s.dmin[a] = min(s.step[a][0], 0) + min(s.step[a][1], 0) + 7 * min(s.step[a][2], 0);
+        s.dmax[a] = max(s.step[a][0], 0) + max(s.step[a][1], 0) + 7 * max(s.step[a][2], 0);
+    }
+    return true;
+}
+
+// the gathered bits of the piece in destination word r (an item of s.b): the map evaluated once in 64 bits, then gather_piece
+__device__ __forceinline__ uint32_t posed_word(const uint32_t* __restrict__ L, uint32_t lg, uint32_t piece, const Posed& s, const RowWord& r)
+{
+    const uint32_t mask = box_mask(s.b, r);
+    // z of the word's first voxel, relative to the row (negative where the word starts in the row before: n = 2;
+    // those voxels are outside the mask)
+    const int64_t z0 = 2 * ((int64_t)(4u * r.w) - (int64_t)r.base);
+    const int64_t c[3] = {4 * (int64_t)r.cx + 1, 4 * (int64_t)r.cy + 1, 2 * z0 + 1};   // 2p + 1: the centre in half voxels
+    int32_t q[3], frac[3];
+    bool miss = mask == 0u, inside = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const int64_t v = (int64_t)s.map.m[3 * a] * c[0] + (int64_t)s.map.m[3 * a + 1] * c[1] + (int64_t)s.map.m[3 * a + 2] * c[2] + s.map.t[a];
+        q[a] = (int32_t)(v >> 17);                 // |v| < 2^41
+        frac[a] = (int32_t)(v & 0x1ffff);
+        const int32_t qmin = q[a] + ((frac[a] + s.dmin[a]) >> 17), qmax = q[a] + ((frac[a] + s.dmax[a]) >> 17);
+        miss = miss || qmax < s.rmin[a] || qmin > s.rmax[a];
+        inside = inside && qmin >= s.rmin[a] && qmax <= s.rmax[a];
+    }
+    if (miss) return 0u;
+    return inside ? gather_piece<true>(L, lg, piece, s.rlo, s.ext, q, frac, s.step, mask) : gather_piece<false>(L, lg, piece, s.rlo, s.ext, q, frac, s.step, mask);
+}
+
 __global__ __launch_bounds__(GROUP) void k_place_affine(const uint32_t* __restrict__ L, uint32_t lg, const vrc_component* __restrict__ records, uint32_t C,
                                                         const uint8_t* __restrict__ keep, const vrc_affine* __restrict__ maps, const uint32_t* __restrict__ boxes,
                                                         uint32_t* dst, uint32_t Sd, int op)
@@ -183,61 +268,14 @@ __global__ __launch_bounds__(GROUP) void k_place_affine(const uint32_t* __restri
     const uint32_t n = Sd >> 1, Ss = 2u << lg;
     const uint32_t lane = threadIdx.x & 63u;
     for (uint32_t piece = blockIdx.y; piece < C; piece += gridDim.y) {  // uniform for the workgroup, and so is all that skips a piece
-        if (keep && keep[piece] == 0) continue;
-        const vrc_affine map = maps[piece];
-        bool legal = map.reserved == 0;
-        for (int i = 0; i < 9; ++i) legal = legal && map.m[i] <= vrc::AFFINE_M_LIMIT && map.m[i] >= -vrc::AFFINE_M_LIMIT;
-        for (int a = 0; a < 3; ++a) legal = legal && map.t[a] <= vrc::AFFINE_T_LIMIT && map.t[a] >= -vrc::AFFINE_T_LIMIT;
-        if (!legal) continue;
-        uint32_t given[6], lo[3], hi[3];
-        for (uint32_t a = 0; a < 6u; ++a) given[a] = boxes ? boxes[6u * piece + a] : (a < 3u ? 0u : Sd);
-        if (!clip_box(given, Sd, lo, hi)) continue;
-        uint32_t rlo[3], ext[3];
-        int32_t rmin[3], rmax[3];
-        bool none = false;
-        for (int a = 0; a < 3; ++a) {
-            rlo[a] = records[piece].lo[a];
-            const uint32_t rhi = min(records[piece].hi[a], Ss);
-            none = none || rlo[a] >= rhi;
-            ext[a] = rhi - rlo[a];
-            rmin[a] = (int32_t)rlo[a]; rmax[a] = (int32_t)rhi - 1;
-        }
-        if (none) continue;
-        const BoxWords b = box_words(lo, hi);
-        // per source axis: s per destination voxel step (|.| <= 2^21), and the extremes of delta over a word's 2 x 2 x 8 voxels
-        int32_t step[3][3], dmin[3], dmax[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) step[a][c] = 2 * map.m[3 * a + c];
-            dmin[a] = min(step[a][0], 0) + min(step[a][1], 0) + 7 * min(step[a][2], 0);
-            dmax[a] = max(step[a][0], 0) + max(step[a][1], 0) + 7 * max(step[a][2], 0);
-        }
-        for (uint64_t base = (uint64_t)blockIdx.x * GROUP; base < b.items; base += (uint64_t)gridDim.x * GROUP) {      // uniform trip count
+        Posed s;
+        if (!pose_piece(records, piece, keep, maps, boxes, Sd, Ss, s)) continue;
+        for (uint64_t base = (uint64_t)blockIdx.x * GROUP; base < s.b.items; base += (uint64_t)gridDim.x * GROUP) {      // uniform trip count
             const uint64_t it = base + threadIdx.x;
             uint32_t bits = 0u;
             RowWord r;
             r.w = 0u;
-            if (it < b.items && row_word(b, n, it, r)) {
-                const uint32_t mask = box_mask(b, r);
-                // z of the word's first voxel, relative to the row (negative where the word starts in the row before: n = 2;
-                // those voxels are outside the mask)
-                const int64_t z0 = 2 * ((int64_t)(4u * r.w) - (int64_t)r.base);
-                const int64_t c[3] = {4 * (int64_t)r.cx + 1, 4 * (int64_t)r.cy + 1, 2 * z0 + 1};   // 2p + 1: the centre in half voxels
-                int32_t q[3], frac[3];
-                bool miss = mask == 0u, inside = true;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    const int64_t s = (int64_t)map.m[3 * a] * c[0] + (int64_t)map.m[3 * a + 1] * c[1] + (int64_t)map.m[3 * a + 2] * c[2] + map.t[a];
-                    q[a] = (int32_t)(s >> 17);                 // |s| < 2^41
-                    frac[a] = (int32_t)(s & 0x1ffff);
-                    const int32_t qmin = q[a] + ((frac[a] + dmin[a]) >> 17), qmax = q[a] + ((frac[a] + dmax[a]) >> 17);
-                    miss = miss || qmax < rmin[a] || qmin > rmax[a];
-                    inside = inside && qmin >= rmin[a] && qmax <= rmax[a];
-                }
-                if (!miss)
-                    bits = inside ? gather_piece<true>(L, lg, piece, rlo, ext, q, frac, step, mask) : gather_piece<false>(L, lg, piece, rlo, ext, q, frac, step, mask);
-            }
+            if (it < s.b.items && row_word(s.b, n, it, r)) bits = posed_word(L, lg, piece, s, r);
             if (n >= 4u) {                                              // a lane, a word
                 if (bits) {
                     if (op == VRC_COPY_OR) atomicOr(&dst[r.w], bits);
@@ -264,6 +302,100 @@ __global__ __launch_bounds__(GROUP) void k_place_affine(const uint32_t* __restri
     }
 }
 
+// ---- contacts ------------------------------------------------------------------------------------------------------
+
+// A world word as the contact step sees it: word k of brick row (cx, cy), bit 4 zl + 2 y + x for the voxel (x, y) of the 2 x 2
+// column in z layer zl of the word's eight.  From 8^3 on (n >= 4) a row is n / 4 whole words and this is a load.  In a world of
+// 4^3 (n = 2) a row is two bytes and two rows share a word: there the row's 16 bits are moved down to layers 0..3 and layers
+// 4..7, which lie beyond the volume, read as ones -- a wall, as every neighbour beyond the volume does -- so that the shifts
+// below hold for it unchanged; the gathered bits are moved down by the same amount (contact_word).
+__device__ __forceinline__ uint32_t world_word(const uint32_t* __restrict__ W, uint32_t n, uint32_t cx, uint32_t cy, uint32_t k)
+{
+    if (n >= 4u) return W[((((uint64_t)cx * n + cy) * n) >> 2) + k];
+    const uint32_t b = (cx * 2u + cy) * 2u;                             // the row's first byte, 0 .. 6
+    return 0xffff0000u | ((W[b >> 2] >> (8u * (b & 3u))) & 0xffffu);
+}
+
+// one set M of voxels of a word added to its count, its sums of c = 2p + 1 and its sums of normals: popcounts only.  c0 = c of
+// the word's voxel 0; the x and y parity planes and the three bit planes of the layer number give what the other voxels add.
+__device__ __forceinline__ void add_set(uint32_t M, const uint32_t c0[3], const uint32_t lower[3], const uint32_t upper[3], uint32_t acc[7])
+{
+    const uint32_t k = __popc(M);
+    acc[0] += k;
+    acc[1] += k * c0[0] + 2u * __popc(M & 0xaaaaaaaau);
+    acc[2] += k * c0[1] + 2u * __popc(M & 0xccccccccu);
+    acc[3] += k * c0[2] + 2u * (__popc(M & 0xf0f0f0f0u) + 2u * __popc(M & 0xff00ff00u) + 4u * __popc(M & 0xffff0000u));
+#pragma unroll
+    for (int a = 0; a < 3; ++a) acc[4 + a] += (uint32_t)(__popc(M & lower[a]) - __popc(M & upper[a]));        // two's complement
+}
+
+// The contact step of one word with gathered bits != 0: the world word, the six "neighbour is solid or beyond the volume"
+// masks as whole-word operations, and the 15 sums.  acc: posed, then overlap (count, s1 x 3, n x 3), then touch.
+__device__ __forceinline__ void contact_word(const uint32_t* __restrict__ W, uint32_t n, const RowWord& r, uint32_t bits, uint32_t acc[15])
+{
+    const uint32_t rows = n >= 4u ? n >> 2 : 1u;                        // words per row
+    const uint32_t k = n >= 4u ? (uint32_t)(r.w - (r.base >> 2)) : 0u;
+    if (n < 4u) bits >>= 8u * ((uint32_t)r.base & 3u);                  // 4^3: the row's two bytes down to layers 0..3 (world_word)
+    const uint32_t cx = r.cx, cy = r.cy;
+    const uint32_t w = world_word(W, n, cx, cy, k);
+    // across the word's faces: the rows cx -+ 1 and cy -+ 1 and the words k -+ 1 of the same row; beyond the volume all ones
+    const uint32_t xm = cx ? world_word(W, n, cx - 1u, cy, k) : ~0u, xp = cx + 1u < n ? world_word(W, n, cx + 1u, cy, k) : ~0u;
+    const uint32_t ym = cy ? world_word(W, n, cx, cy - 1u, k) : ~0u, yp = cy + 1u < n ? world_word(W, n, cx, cy + 1u, k) : ~0u;
+    const uint32_t zm = k ? world_word(W, n, cx, cy, k - 1u) : ~0u, zp = k + 1u < rows ? world_word(W, n, cx, cy, k + 1u) : ~0u;
+    // W*(p - e_a) and W*(p + e_a) for the 32 voxels p of the word
+    const uint32_t lower[3] = {((w & 0x55555555u) << 1) | ((xm & 0xaaaaaaaau) >> 1), ((w & 0x33333333u) << 2) | ((ym & 0xccccccccu) >> 2), (w << 4) | (zm >> 28)};
+    const uint32_t upper[3] = {((w & 0xaaaaaaaau) >> 1) | ((xp & 0x55555555u) << 1), ((w & 0xccccccccu) >> 2) | ((yp & 0x33333333u) << 2), (w >> 4) | (zp << 28)};
+    const uint32_t c0[3] = {4u * cx + 1u, 4u * cy + 1u, 16u * k + 1u};
+    acc[0] += __popc(bits);
+    add_set(bits & w, c0, lower, upper, acc + 1);
+    add_set(bits & ~w & (lower[0] | lower[1] | lower[2] | upper[0] | upper[1] | upper[2]), c0, lower, upper, acc + 8);
+}
+
+// k_place_affine's grid and gather, ending in a reduction: the contact record of every piece against the world W (Sd^3).
+// Width of the sums.  One word adds at most 32 to a count or a normal and less than 32 * 2048 = 2^16 to a sum of c.  A lane
+// takes the words of a box by grid stride: at most 512 * 512 * 129 < 2^25.02 words (all of 1024^3) over at least 4
+// workgroups = 1024 lanes (contacts_run), so fewer than 2^15.02 words and sums below 2^31.02: the lanes add in 32 bits
+// (normals in two's complement).  Sixty-four lanes no longer fit: the wave sums, the LDS and the atomics are 64 bits wide.
+__global__ __launch_bounds__(GROUP) void k_contacts(const uint32_t* __restrict__ L, uint32_t lg, const vrc_component* __restrict__ records, uint32_t C,
+                                                    const uint8_t* __restrict__ keep, const vrc_affine* __restrict__ maps, const uint32_t* __restrict__ boxes,
+                                                    const uint32_t* __restrict__ W, uint32_t Sd, unsigned long long* out)
+{
+    __shared__ unsigned long long part[WAVES][CONTACT_SUMS];
+    const uint32_t n = Sd >> 1, Ss = 2u << lg;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t piece = blockIdx.y; piece < C; piece += gridDim.y) {  // uniform for the workgroup, and so is all that skips a piece
+        Posed s;
+        if (!pose_piece(records, piece, keep, maps, boxes, Sd, Ss, s)) continue;
+        uint32_t acc[CONTACT_SUMS];
+        for (uint32_t k = 0; k < CONTACT_SUMS; ++k) acc[k] = 0u;
+        for (uint64_t base = (uint64_t)blockIdx.x * GROUP; base < s.b.items; base += (uint64_t)gridDim.x * GROUP) {      // uniform trip count
+            const uint64_t it = base + threadIdx.x;
+            RowWord r;
+            if (it < s.b.items && row_word(s.b, n, it, r)) {
+                const uint32_t bits = posed_word(L, lg, piece, s, r);
+                if (bits) contact_word(W, n, r, bits, acc);             // almost no word of a generous box gets here
+            }
+        }
+        // a workgroup that gathered nothing (acc[0] is `posed`) issues nothing; the barrier also keeps the LDS of the piece
+        // before until its readers are done
+        if (!__syncthreads_or(acc[0] != 0u)) continue;
+        const bool some = __ballot(acc[0] != 0u) != 0ull;               // wave-uniform
+        for (uint32_t k = 0; k < CONTACT_SUMS; ++k) {
+            // the normals (k = 5..7, 12..14) are signed
+            const bool is_signed = (k >= 5u && k <= 7u) || k >= 12u;
+            const unsigned long long mine = is_signed ? (unsigned long long)(long long)(int32_t)acc[k] : (unsigned long long)acc[k];
+            const unsigned long long total = some ? wave_sum(mine) : 0ull;
+            if (lane == 0u) part[wave][k] = total;
+        }
+        __syncthreads();
+        if (threadIdx.x < CONTACT_SUMS) {                               // the non-zero sums of the workgroup: at most 15 atomics
+            unsigned long long v = 0ull;
+            for (uint32_t wv = 0; wv < WAVES; ++wv) v += part[wv][threadIdx.x];
+            if (v) atomicAdd(out + (size_t)CONTACT_WORDS * piece + threadIdx.x, v);
+        }
+    }
+}
+
 }  // namespace
 
 namespace vrc {
@@ -278,16 +410,33 @@ hipError_t moments_run(const uint32_t* labels, uint32_t depth, uint64_t first, u
     return hipGetLastError();
 }
 
-void place_affine_run(const uint32_t* labels, const vrc_component* records, uint64_t pieces, uint32_t depth, const uint8_t* keep, const vrc_affine* maps,
-                      const uint32_t* boxes, uint32_t* dst, uint32_t dst_depth, int op, hipStream_t st)
+// the grid of the two kernels that gather posed pieces: about 16384 workgroups in all: the more pieces, the fewer workgroups
+// share a piece's box; the rest is the strides.  A piece has at least 4 workgroups unless the destination has fewer words.
+static dim3 posed_grid(uint64_t pieces, uint32_t Sd)
 {
-    // about 16384 workgroups in all: the more pieces, the fewer workgroups share a piece's box; the rest is the strides
-    const uint32_t Sd = 1u << dst_depth, zero[3] = {0u, 0u, 0u}, all[3] = {Sd, Sd, Sd};
+    const uint32_t zero[3] = {0u, 0u, 0u}, all[3] = {Sd, Sd, Sd};
     const uint32_t gy = pieces > 4096u ? 4096u : (uint32_t)pieces;
     const uint64_t whole = (box_word_items(zero, all) + GROUP - 1u) / GROUP;
     const uint32_t share = 16384u / gy;
-    const uint32_t gx = whole < share ? (uint32_t)whole : share;
-    hipLaunchKernelGGL(k_place_affine, dim3(gx, gy), dim3(GROUP), 0, st, labels, depth - 1u, records, (uint32_t)pieces, keep, maps, boxes, dst, Sd, op);
+    return dim3(whole < share ? (uint32_t)whole : share, gy);
+}
+
+void place_affine_run(const uint32_t* labels, const vrc_component* records, uint64_t pieces, uint32_t depth, const uint8_t* keep, const vrc_affine* maps,
+                      const uint32_t* boxes, uint32_t* dst, uint32_t dst_depth, int op, hipStream_t st)
+{
+    const uint32_t Sd = 1u << dst_depth;
+    hipLaunchKernelGGL(k_place_affine, posed_grid(pieces, Sd), dim3(GROUP), 0, st, labels, depth - 1u, records, (uint32_t)pieces, keep, maps, boxes, dst, Sd, op);
+}
+
+hipError_t contacts_run(const uint32_t* labels, const vrc_component* records, uint64_t pieces, uint32_t depth, const uint8_t* keep, const vrc_affine* maps,
+                        const uint32_t* boxes, const uint32_t* world, uint32_t world_depth, vrc_piece_contact* out, hipStream_t st)
+{
+    const hipError_t e = hipMemsetAsync(out, 0, (size_t)pieces * sizeof(vrc_piece_contact), st);
+    if (e != hipSuccess) return e;
+    const uint32_t Sd = 1u << world_depth;
+    hipLaunchKernelGGL(k_contacts, posed_grid(pieces, Sd), dim3(GROUP), 0, st, labels, depth - 1u, records, (uint32_t)pieces, keep, maps, boxes, world, Sd,
+                       (unsigned long long*)out);
+    return hipGetLastError();
 }
 
 }  // namespace vrc

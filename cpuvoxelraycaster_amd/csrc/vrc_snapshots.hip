@@ -1,6 +1,6 @@
 // vrc_snapshots.hip -- the snapshots taken from an editable volume (include/vrc.h): the labels of its connected components
-// (vrc_volume_label_components, vrc_labels_*; kernels in vrc_components.hip; the pieces' moments and posed placement,
-// vrc_rigid_*, kernels in vrc_rigid.hip) and its exact squared Euclidean distance field
+// (vrc_volume_label_components, vrc_labels_*; kernels in vrc_components.hip; the pieces' moments, posed placement and
+// contacts, vrc_rigid_*, kernels in vrc_rigid.hip) and its exact squared Euclidean distance field
 // with the selection by distance that grow / shrink / hollow are made of (vrc_volume_distance_field, vrc_distance_*;
 // kernels in vrc_distance.hip), and the travel-distance field from a set of seeds, kept in the same snapshot object, with the
 // routes read off it (vrc_travel_field, vrc_travel_trace_paths; kernels in vrc_travel.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
@@ -293,6 +293,47 @@ extern "C" int vrc_rigid_place_affine(const vrc_labels* l, const uint8_t* keep, 
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = finish(dst, mem, st, true);
+    if (d_stage) (void)hipFree(d_stage);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    return VRC_OK;
+}
+
+extern "C" int vrc_rigid_contacts(const vrc_labels* l, const uint8_t* keep, const vrc_affine* maps, const uint32_t* boxes, vrc_volume* world,
+                                  vrc_piece_contact* out, int mem, void* stream)
+{
+    const char* what = "vrc_rigid_contacts";
+    if (!l || !world) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (world->device != l->device) return vrc::fail(VRC_ERR_INVALID, "%s: labels on device %d, volume on device %d", what, l->device, world->device);
+    if (!maps && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null maps with %llu components", what, (unsigned long long)l->count);
+    if (!out && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null records with %llu components", what, (unsigned long long)l->count);
+    if (mem == VRC_MEM_HOST)
+        for (uint64_t i = 0; i < l->count; ++i)
+            if (const int rc = check_affine(what, maps + i, (long long)i)) return rc;
+    if (!l->count) return VRC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t C = (size_t)l->count, map_bytes = C * sizeof(vrc_affine), box_bytes = boxes ? C * 24u : 0u, keep_bytes = keep ? C : 0u;
+    const size_t out_bytes = C * sizeof(vrc_piece_contact);
+    hipError_t e = hipSetDevice(l->device);
+    if (e == hipSuccess) e = order_behind_edits(world, st);          // the call reads the world's occupancy, as vrc_volume_count_boxes does
+    const uint8_t* d_keep = keep;
+    const vrc_affine* d_maps = maps;
+    const uint32_t* d_boxes = boxes;
+    vrc_piece_contact* d_out = out;
+    uint8_t* d_stage = nullptr;
+    if (mem == VRC_MEM_HOST) {                       // staged: the records, then the maps, then the boxes, then the keep bytes
+        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, out_bytes + map_bytes + box_bytes + keep_bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_stage + out_bytes, maps, map_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && boxes) e = hipMemcpyAsync(d_stage + out_bytes + map_bytes, boxes, box_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && keep) e = hipMemcpyAsync(d_stage + out_bytes + map_bytes + box_bytes, keep, keep_bytes, hipMemcpyHostToDevice, st);
+        d_out = (vrc_piece_contact*)d_stage;
+        d_maps = (const vrc_affine*)(d_stage + out_bytes);
+        d_boxes = boxes ? (const uint32_t*)(d_stage + out_bytes + map_bytes) : nullptr;
+        d_keep = keep ? d_stage + out_bytes + map_bytes + box_bytes : nullptr;
+    }
+    if (e == hipSuccess) e = vrc::contacts_run(l->d_ids, l->d_records, l->count, l->depth, d_keep, d_maps, d_boxes, world->d_bricks, world->depth, d_out, st);
+    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = finish(world, mem, st, false);           // not an edit: the world is only read
     if (d_stage) (void)hipFree(d_stage);
     if (e != hipSuccess) return vrc::fail_hip(e, what);
     return VRC_OK;

@@ -307,6 +307,13 @@ public:
     // include/vrc.h: vrc_rigid_place_affine
     inline void placeAffine(const std::vector<vrc_affine>& maps, HipVoxelVolume& dst, int op = VRC_COPY_OR, const std::vector<uint32_t>* boxes = nullptr,
                             const std::vector<uint8_t>* keep = nullptr) const;
+    // One record per piece: piece i read through its own inverse map inside its own box of `world` (count() x 6, lo then hi;
+    // nullptr: all of world), as placeAffine would write it, against the solid voxels of world and its faces: the posed voxels,
+    // those inside the solid (overlap) and those face to face with it (touch), each with the sum of c = 2p + 1 and of the voxel
+    // normals -- include/vrc.h: vrc_rigid_contacts.  A piece with keep[id] == 0 (nullptr: all kept) has an all-zero record.
+    // world is only read (its queued cells are flushed first) and nothing is excluded from it.
+    inline std::vector<vrc_piece_contact> contacts(const std::vector<vrc_affine>& maps, HipVoxelVolume& world, const std::vector<uint32_t>* boxes = nullptr,
+                                                   const std::vector<uint8_t>* keep = nullptr) const;
     vrc_labels* handle() const { return l_; }
 
 private:
@@ -857,6 +864,20 @@ inline void HipVoxelLabels::placeAffine(const std::vector<vrc_affine>& maps, Hip
     check(vrc_rigid_place_affine(l_, keep && !keep->empty() ? keep->data() : nullptr, maps.empty() ? nullptr : maps.data(),
                                  boxes && !boxes->empty() ? boxes->data() : nullptr, dst.handle(), op, VRC_MEM_HOST, nullptr),
           "vrc_rigid_place_affine");
+}
+
+inline std::vector<vrc_piece_contact> HipVoxelLabels::contacts(const std::vector<vrc_affine>& maps, HipVoxelVolume& world, const std::vector<uint32_t>* boxes,
+                                                               const std::vector<uint8_t>* keep) const
+{
+    if (maps.size() != count()) throw std::invalid_argument("HipVoxelLabels::contacts: maps must have one entry per component");
+    if (boxes && boxes->size() != count() * 6u) throw std::invalid_argument("HipVoxelLabels::contacts: boxes must have six entries per component");
+    if (keep && keep->size() != count()) throw std::invalid_argument("HipVoxelLabels::contacts: keep must have one byte per component");
+    world.flush();
+    std::vector<vrc_piece_contact> out((size_t)count());
+    check(vrc_rigid_contacts(l_, keep && !keep->empty() ? keep->data() : nullptr, maps.empty() ? nullptr : maps.data(),
+                             boxes && !boxes->empty() ? boxes->data() : nullptr, world.handle(), out.empty() ? nullptr : out.data(), VRC_MEM_HOST, nullptr),
+          "vrc_rigid_contacts");
+    return out;
 }
 
 inline void HipVoxelDistance::select(uint32_t lo, uint32_t hi, HipVoxelVolume& dst, int op) const

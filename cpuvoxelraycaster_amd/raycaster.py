@@ -224,6 +224,33 @@ def mass_properties(moments):
     return mass, centre, inertia
 
 
+def contact_properties(records):
+    """(overlap_centre, overlap_normal, touch_centre, touch_normal) as float64 arrays of shape (k, 3) from k
+    capi.CONTACT_DTYPE records (include/vrc.h: vrc_rigid_contacts).  A centre is the centroid s1 / (2 count) of the set in
+    continuous voxel coordinates, the exact rational value rounded once; a normal is the unit vector n / |n| of the summed
+    voxel normals, pointing from the solid into the open.  Zeros where the count or the vector is zero."""
+    from fractions import Fraction
+    from math import isqrt
+    records = np.asarray(records, capi.CONTACT_DTYPE).reshape(-1)
+    k = len(records)
+    out = [np.zeros((k, 3)) for _ in range(4)]
+    for i, rec in enumerate(records):
+        for j, name in enumerate(("overlap", "touch")):
+            count = int(rec[name])
+            if count:
+                out[2 * j][i] = [float(Fraction(int(v), 2 * count)) for v in rec[name + "_s1"]]
+            n = [int(v) for v in rec[name + "_n"]]
+            nn = sum(v * v for v in n)
+            if nn:
+                # |n| from the integer root of nn scaled to 54 bits or more (nn itself may exceed 2^53), rounded once; with the
+                # division the result is within one unit in the last place of n / |n|
+                shift = max(0, 54 - nn.bit_length() // 2)
+                root = isqrt(nn << (2 * shift))
+                length = float(Fraction(root, 1 << shift))
+                out[2 * j + 1][i] = [v / length for v in n]
+    return tuple(out)
+
+
 class VoxelVolume:
     """Device-resident editable occupancy of an S^3 volume (include/vrc.h: vrc_volume_*).  Edits are batched; commit()
     builds a new immutable LSVO on the device, bit-identical to compileSVO of the current voxel set."""
@@ -880,6 +907,42 @@ class VoxelLabels:
         `stream`; a piece whose map lies beyond the limits is dropped whole"""
         check(capi.load().vrc_rigid_place_affine(self._h, ptr(keep_ptr), ptr(maps_ptr), ptr(boxes_ptr), dst._h, int(op), capi.VRC_MEM_DEVICE, ptr(stream)))
         return dst
+
+    def _contact_arguments(self, maps, boxes, keep):
+        maps = affine_array(maps)
+        if len(maps) != self.count:
+            raise ValueError(f"maps has {len(maps)} entries for {self.count} components")
+        if boxes is not None:
+            boxes = np.ascontiguousarray(boxes, np.uint32).reshape(-1, 6)
+            if len(boxes) != self.count:
+                raise ValueError(f"boxes has {len(boxes)} rows for {self.count} components")
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, np.uint8).reshape(-1)
+            if len(keep) != self.count:
+                raise ValueError(f"keep has {len(keep)} entries for {self.count} components")
+        return maps, boxes, keep
+
+    def contacts(self, maps, world, boxes=None, keep=None):
+        """One capi.CONTACT_DTYPE record per piece: piece i read through its OWN inverse map inside its own box ((count, 6)
+        uint32 lo, hi; None: all of world), as placeAffine would write it into a volume of world's depth, against the solid
+        voxels of `world` and its faces -- include/vrc.h: vrc_rigid_contacts.  posed = its voxels there, overlap* = those inside
+        the world's solid (count, sum of c = 2p + 1, sum of normals), touch* = those outside it with a solid voxel or a face of
+        the volume next to them.  A piece with keep[id] == 0 (None: all kept) or an empty box has an all-zero record.  world is
+        only read; nothing is excluded from it, so against the labelled medium itself a piece at rest overlaps itself."""
+        maps, boxes, keep = self._contact_arguments(maps, boxes, keep)
+        out = np.zeros(self.count, capi.CONTACT_DTYPE)
+        check(capi.load().vrc_rigid_contacts(self._h, ptr(keep), ptr(maps) if self.count else None, ptr(boxes), world._h,
+                                              ptr(out) if self.count else None, capi.VRC_MEM_HOST, None))
+        return out
+
+    def contactsDevice(self, maps_ptr, world, out_ptr, boxes_ptr=None, keep_ptr=None, stream=None):
+        """the same with the maps (64 bytes each), the boxes, `count` bytes of keep and the records (128 bytes each) in device
+        memory, asynchronous on `stream`; a piece whose map lies beyond the limits has an all-zero record"""
+        check(capi.load().vrc_rigid_contacts(self._h, ptr(keep_ptr), ptr(maps_ptr), ptr(boxes_ptr), world._h, ptr(out_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def collides(self, maps, world, boxes=None, keep=None):
+        """bool per piece: the posed piece shares a voxel with the world's solid (contacts()["overlap"] > 0)"""
+        return self.contacts(maps, world, boxes, keep)["overlap"] > 0
 
     def bytes(self):
         return int(capi.load().vrc_labels_bytes(self._h))

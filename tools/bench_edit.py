@@ -127,6 +127,15 @@ repetitions, median and range, everything in device memory:
                                                                          two results are compared voxel for voxel
   place_turn       vrc_rigid_place_affine with every piece turned 30 degrees about x, then y, about its own centre of mass
                    (maps and boxes from VoxelLabels.poses)
+With --contacts (printed and written to profiles/edit/bench_contacts.json), the contact test of posed pieces on the same scene,
+timed the same way, everything in device memory; each contact call next to vrc_rigid_place_affine with the same maps and boxes
+in the same run (the contact time includes the zeroing of the records; the passes of a call are not timed apart):
+  contacts_translate  vrc_rigid_contacts with the fall's translation maps and the moved record boxes against the supported
+                      part                                      next to  place_translate
+  contacts_turn       the same with every piece turned 30 degrees about x, then y, about its own centre of mass
+                                                                next to  place_turn
+  contacts_*_full     the two again with world = the whole medium (supported part and debris): most gathered words are
+                      non-zero in the world
 No threshold is applied; the numbers are reported."""
 import argparse
 import json
@@ -980,6 +989,79 @@ def bench_rigid(vrc, depth, pairs):
     return res
 
 
+def bench_contacts(vrc, depth, pairs):
+    """vrc_rigid_contacts next to vrc_rigid_place_affine with the same maps and boxes, on bench_fall's scene"""
+    import math
+    import torch
+    S = 1 << depth
+    res = {"size": S, "pairs": pairs}
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    world = vrc.VoxelVolume.fromScene(scene)
+    floor_y = S // 2 + 1
+    band = [0, floor_y + 24, 0, S, floor_y + 28, S]
+    cuts = [band, [0, floor_y + 44, 0, S, floor_y + 47, S]]
+    cuts += [[c, floor_y + 24, 0, c + 2, S, S] for c in range(30, S, 32)] + [[0, floor_y + 24, c, S, S, c + 2] for c in range(30, S, 32)]
+    world.fillBoxes(cuts, False)
+    full = world.clone()                                                     # the whole medium: supported part and debris
+    debris = world.keepConnected([[0, floor_y, 0, S, floor_y + 1, S]], 6)
+    labels = debris.labelComponents(6)
+    C_ = labels.count
+    res["pieces"], res["supported_voxels"], res["debris_voxels"] = C_, world.solidCount(), debris.solidCount()
+    OR = vrc.capi.VRC_COPY_OR
+
+    def timed(fn):
+        out = []
+        for i in range(pairs + 1):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if i:
+                out.append(a.elapsed_time(b))
+        return stat(out, 4)
+
+    def box_words(boxes):
+        return int(sum(((int(b[3]) - 1) // 2 - int(b[0]) // 2 + 1) * ((int(b[4]) - 1) // 2 - int(b[1]) // 2 + 1) * ((((int(b[5]) - 1) // 2 - int(b[2]) // 2) + 3) // 4 + 1)
+                       for b in boxes if all(b[a] < b[a + 3] for a in range(3))))
+
+    def on_device(array):
+        return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).cuda()
+
+    records = labels.components()
+    offsets, st = labels.fall(world, vrc.capi.VRC_FACE_YN)
+    maps = np.zeros(C_, vrc.capi.AFFINE_DTYPE)
+    maps["m"][:] = [65536, 0, 0, 0, 65536, 0, 0, 0, 65536]
+    maps["t"][:] = -(offsets.astype(np.int64) << 17)
+    boxes = np.concatenate([np.clip(records["lo"].astype(np.int64) + offsets, 0, S), np.clip(records["hi"].astype(np.int64) + offsets, 0, S)], axis=1).astype(np.uint32)
+    c, s = math.cos(math.radians(30)), math.sin(math.radians(30))
+    rx = np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
+    ry = np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
+    rot = np.ascontiguousarray((ry @ rx).T, np.float32).reshape(9)
+    turn_maps, turn_boxes = labels.poses(rot, labels.massProperties()[1])
+    out = torch.zeros(max(C_, 1) * 128, dtype=torch.uint8).cuda()
+    for name, mp, bx in (("translate", maps, boxes), ("turn", turn_maps, turn_boxes)):
+        d_maps, d_boxes = on_device(mp), on_device(bx)
+        placed = world.clone()
+        torch.cuda.synchronize()
+        res[name + "_box_words"] = box_words(bx)
+        res["place_%s_ms" % name] = timed(lambda: labels.placeAffineDevice(d_maps.data_ptr(), placed, d_boxes.data_ptr(), OR, None, None))
+        for suffix, against in (("", world), ("_full", full)):
+            key = "contacts_%s%s" % (name, suffix)
+            res[key + "_ms"] = timed(lambda: labels.contactsDevice(d_maps.data_ptr(), against, out.data_ptr(), d_boxes.data_ptr(), None, None))
+            res[key + "_over_place"] = round(res[key + "_ms"]["median"] / res["place_%s_ms" % name]["median"], 2)
+            got = out.cpu().numpy().view(vrc.capi.CONTACT_DTYPE)[:C_]
+            assert got.tobytes() == labels.contacts(mp, against, bx).tobytes(), "device-memory records differ from the host-memory call's"
+            res[key] = {"posed_voxels": int(got["posed"].sum()), "overlap_voxels": int(got["overlap"].sum()), "touch_voxels": int(got["touch"].sum()),
+                        "pieces_overlapping": int((got["overlap"] > 0).sum()), "pieces_touching": int((got["touch"] > 0).sum())}
+        placed.close()
+    assert res["contacts_translate"]["overlap_voxels"] == 0 and res["contacts_translate"]["posed_voxels"] == res["debris_voxels"], "the fall's offsets overlap the supported part"
+    for v in (labels, debris, full, world):
+        v.close()
+    scene.close()
+    return res
+
+
 def bench_stamp(vrc, depth, pairs):
     import math
     S = 1 << depth
@@ -1042,6 +1124,7 @@ def main():
     ap.add_argument("--stamp", action="store_true", help="time vrc_volume_stamp_affine next to vrc_volume_copy_region (depth 9 unless --depths is given)")
     ap.add_argument("--fall", action="store_true", help="time vrc_fall_drops / vrc_fall_place next to vrc_volume_label_components of the same debris (depth 9 unless --depths is given)")
     ap.add_argument("--rigid", action="store_true", help="time vrc_rigid_moments / vrc_rigid_place_affine next to vrc_labels_select / vrc_fall_place (depth 9 unless --depths is given)")
+    ap.add_argument("--contacts", action="store_true", help="time vrc_rigid_contacts next to vrc_rigid_place_affine with the same maps and boxes (depth 9 unless --depths is given)")
     ap.add_argument("--travel", action="store_true", help="time vrc_travel_field next to vrc_volume_flood from the same seeds (depth 9 unless --depths is given)")
     args = ap.parse_args()
     if args.travel and args.depths == [8, 9, 10]:
@@ -1049,6 +1132,8 @@ def main():
     if args.fall and args.depths == [8, 9, 10]:
         args.depths = [9]
     if args.rigid and args.depths == [8, 9, 10]:
+        args.depths = [9]
+    if args.contacts and args.depths == [8, 9, 10]:
         args.depths = [9]
     if args.stamp and args.depths == [8, 9, 10]:
         args.depths = [9]
@@ -1072,11 +1157,15 @@ def main():
     import cpuvoxelraycaster_amd as vrc
     if not torch.cuda.is_available():
         raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-    out = {"bench": "edit_rigid" if args.rigid else "edit_fall" if args.fall else "edit_travel" if args.travel else "edit_rects" if args.rects else "edit_stamp" if args.stamp else "edit_distance" if args.distance else "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
+    out = {"bench": "edit_contacts" if args.contacts else "edit_rigid" if args.rigid else "edit_fall" if args.fall else "edit_travel" if args.travel else "edit_rects" if args.rects else "edit_stamp" if args.stamp else "edit_distance" if args.distance else "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
     for d in args.depths:
-        out["depths"][str(d)] = (bench_rigid if args.rigid else bench_fall if args.fall else bench_travel if args.travel else bench_rects if args.rects else bench_stamp if args.stamp else bench_distance if args.distance else bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
+        out["depths"][str(d)] = (bench_contacts if args.contacts else bench_rigid if args.rigid else bench_fall if args.fall else bench_travel if args.travel else bench_rects if args.rects else bench_stamp if args.stamp else bench_distance if args.distance else bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
     print(json.dumps(out))
-    if args.rigid:
+    if args.contacts:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_contacts.json")
+        with open(path, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+    elif args.rigid:
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_rigid.json")
         with open(path, "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
