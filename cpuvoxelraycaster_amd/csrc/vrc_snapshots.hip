@@ -4,7 +4,8 @@
 // with the selection by distance that grow / shrink / hollow are made of (vrc_volume_distance_field, vrc_distance_*;
 // kernels in vrc_distance.hip), and the travel-distance field from a set of seeds, kept in the same snapshot object, with the
 // routes read off it (vrc_travel_field, vrc_travel_trace_paths; kernels in vrc_travel.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
-// event and no scratch; what it selects goes into a volume as an edit of that volume (vrc_volume_state.h).
+// event and no scratch: its host-memory calls stage in a block of their own, and what it selects or places goes into a volume
+// as an edit of that volume (staged_call in vrc_volume_state.h; the ordering of every entry point: the table in DESIGN.md).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -51,6 +52,23 @@ hipError_t snapshot_run(vrc_volume* medium, uint32_t** d_array, size_t scratch_b
     if (d_scratch) (void)hipFree(d_scratch);
     return e;
 }
+
+// the packed maximum of a field's reduction, (value << 32) | ~dense index, 0 where nothing was counted: the value and
+// the x y z of the index
+void decode_argmax(unsigned long long packed, uint32_t depth, uint32_t* value, uint32_t argmax[3])
+{
+    *value = 0u; argmax[0] = argmax[1] = argmax[2] = 0u;
+    if (!packed) return;
+    const uint32_t index = ~(uint32_t)packed, mask = (1u << depth) - 1u;
+    *value = (uint32_t)(packed >> 32);
+    argmax[0] = index >> (2u * depth); argmax[1] = (index >> depth) & mask; argmax[2] = index & mask;
+}
+
+// a call on the labels / the field alone: no volume to wait for, host memory staged in a block of the call's own
+Call snapshot_call(int device, int mem, void* stream) { return Call{device, mem, (hipStream_t)stream, nullptr, false, false, false}; }
+// a call that reads the snapshot and a volume (is_edit: writes the volume): behind the volume's last asynchronous edit
+// whatever the memory kind, staged in a block of the call's own
+Call volume_call(int device, int mem, void* stream, vrc_volume* v, bool is_edit) { return Call{device, mem, (hipStream_t)stream, v, is_edit, false, true}; }
 
 }  // namespace
 
@@ -108,15 +126,15 @@ extern "C" int vrc_labels_components(const vrc_labels* l, uint64_t first, uint64
     if (!l) return vrc::fail(VRC_ERR_INVALID, "%s: null labels", what);
     if (const int rc = check_mem(what, mem)) return rc;
     if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
-    const uint64_t want = first < l->count ? (capacity < l->count - first ? capacity : l->count - first) : 0u;
+    const uint64_t want = window_of(first, capacity, l->count);
     if (!want) return VRC_OK;
+    // no list to stage: the records are copied out of the snapshot as they lie there
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipSetDevice(l->device);
     if (e == hipSuccess)
         e = hipMemcpyAsync(out, l->d_records + first, (size_t)want * sizeof(vrc_component), mem == VRC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    if (e == hipSuccess) e = finish(nullptr, mem, st, false);
+    return done(e, what);
 }
 
 extern "C" int vrc_labels_at(const vrc_labels* l, uint64_t n, const uint32_t* xyz, uint32_t* ids, int mem, void* stream)
@@ -126,10 +144,11 @@ extern "C" int vrc_labels_at(const vrc_labels* l, uint64_t n, const uint32_t* xy
     if (const int rc = check_mem(what, mem)) return rc;
     if (n == 0) return VRC_OK;
     if (!xyz || !ids) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
-    if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "%s: too many voxels for one launch", what);
-    hipStream_t st = (hipStream_t)stream;
-    return staged_call(what, l->device, nullptr, xyz, (size_t)n * 12u, ids, (size_t)n * 4u, mem, st, [&](const void* d_xyz, void* d_ids) {
-        vrc::components_at_run(l->d_ids, l->depth, n, (const uint32_t*)d_xyz, (uint32_t*)d_ids, st);
+    if (const int rc = check_count(what, n, LANE_ITEMS, "voxels")) return rc;
+    const Call call = snapshot_call(l->device, mem, stream);
+    const StagePart parts[] = {{xyz, (size_t)n * 12u, STAGE_IN}, {ids, (size_t)n * 4u, STAGE_OUT}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        vrc::components_at_run(l->d_ids, l->depth, n, (const uint32_t*)d[0], (uint32_t*)d[1], call.st);
         return hipSuccess;
     });
 }
@@ -140,38 +159,27 @@ extern "C" int vrc_labels_select(const vrc_labels* l, const uint8_t* keep, vrc_v
     if (!l || !dst) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
     if (const int rc = check_op(what, op)) return rc;
     if (const int rc = check_mem(what, mem)) return rc;
-    if (dst->depth != l->depth) return vrc::fail(VRC_ERR_INVALID, "%s: labels of depth %u, volume of depth %u", what, l->depth, dst->depth);
-    if (dst->device != l->device) return vrc::fail(VRC_ERR_INVALID, "%s: labels on device %d, volume on device %d", what, l->device, dst->device);
+    if (const int rc = check_same(what, "labels", l->depth, l->device, dst)) return rc;
     if (!keep && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null keep with %llu components", what, (unsigned long long)l->count);
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(l->device);
-    if (e == hipSuccess) e = order_behind_edits(dst, st);
-    const uint8_t* d_keep = keep;
-    uint8_t* d_stage = nullptr;
-    if (mem == VRC_MEM_HOST && l->count) {
-        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, (size_t)l->count);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_stage, keep, (size_t)l->count, hipMemcpyHostToDevice, st);
-        d_keep = d_stage;
-    }
-    if (e == hipSuccess) {
-        vrc::components_select_run(l->d_ids, l->depth, d_keep, dst->d_bricks, op, st);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = finish(dst, mem, st, true);
-    if (d_stage) (void)hipFree(d_stage);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    const Call call = volume_call(l->device, mem, stream, dst, true);
+    const StagePart parts[] = {{keep, (size_t)l->count, STAGE_IN}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        vrc::components_select_run(l->d_ids, l->depth, (const uint8_t*)d[0], dst->d_bricks, op, call.st);
+        return hipSuccess;
+    });
 }
 
 // how far every piece can fall (the rule: include/vrc.h; the passes: vrc_fall.hip).  Synchronous, on the NULL stream.
+// Not a staged_call: the scratch block is needed in both memory kinds and holds the staged offsets behind it, the rounds
+// read a flag back between launches, and the offsets come down only from a run that converged.
 extern "C" int vrc_fall_drops(const vrc_labels* l, vrc_volume* fixed, int direction, uint32_t drop_limit, int32_t* offsets, int mem, vrc_fall_stats* stats)
 {
     const char* what = "vrc_fall_drops";
     if (!l) return vrc::fail(VRC_ERR_INVALID, "%s: null labels", what);
     if (direction < VRC_FACE_XN || direction > VRC_FACE_ZP) return vrc::fail(VRC_ERR_INVALID, "%s: direction %d is not a face code 0..5", what, direction);
     if (const int rc = check_mem(what, mem)) return rc;
-    if (fixed && fixed->depth != l->depth) return vrc::fail(VRC_ERR_INVALID, "%s: labels of depth %u, volume of depth %u", what, l->depth, fixed->depth);
-    if (fixed && fixed->device != l->device) return vrc::fail(VRC_ERR_INVALID, "%s: labels on device %d, volume on device %d", what, l->device, fixed->device);
+    if (fixed)
+        if (const int rc = check_same(what, "labels", l->depth, l->device, fixed)) return rc;
     if (!offsets && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null offsets with %llu components", what, (unsigned long long)l->count);
     vrc_fall_stats none = {};
     if (!stats) stats = &none;
@@ -202,35 +210,27 @@ extern "C" int vrc_fall_place(const vrc_labels* l, const uint8_t* keep, const in
     if (const int rc = check_op(what, op)) return rc;
     if (op == VRC_COPY_REPLACE) return vrc::fail(VRC_ERR_INVALID, "%s: VRC_COPY_REPLACE has no meaning for a scatter", what);
     if (const int rc = check_mem(what, mem)) return rc;
-    if (dst->depth != l->depth) return vrc::fail(VRC_ERR_INVALID, "%s: labels of depth %u, volume of depth %u", what, l->depth, dst->depth);
-    if (dst->device != l->device) return vrc::fail(VRC_ERR_INVALID, "%s: labels on device %d, volume on device %d", what, l->device, dst->device);
+    if (const int rc = check_same(what, "labels", l->depth, l->device, dst)) return rc;
     if (!offsets && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null offsets with %llu components", what, (unsigned long long)l->count);
     if (!l->count) return VRC_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t offset_bytes = (size_t)l->count * 12u;
-    hipError_t e = hipSetDevice(l->device);
-    if (e == hipSuccess) e = order_behind_edits(dst, st);
-    const uint8_t* d_keep = keep;
-    const int32_t* d_offsets = offsets;
-    uint8_t* d_stage = nullptr;
-    if (mem == VRC_MEM_HOST) {                       // staged: the offsets, then the keep bytes
-        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, offset_bytes + (keep ? (size_t)l->count : 0u));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_stage, offsets, offset_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && keep) e = hipMemcpyAsync(d_stage + offset_bytes, keep, (size_t)l->count, hipMemcpyHostToDevice, st);
-        d_offsets = (const int32_t*)d_stage;
-        d_keep = keep ? d_stage + offset_bytes : nullptr;
-    }
-    if (e == hipSuccess) {
-        vrc::place_run(l->d_ids, l->depth, d_keep, d_offsets, dst->d_bricks, op, st);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = finish(dst, mem, st, true);
-    if (d_stage) (void)hipFree(d_stage);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    const Call call = volume_call(l->device, mem, stream, dst, true);
+    const StagePart parts[] = {{offsets, (size_t)l->count * 12u, STAGE_IN}, {keep, (size_t)l->count, STAGE_IN}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        vrc::place_run(l->d_ids, l->depth, (const uint8_t*)d[1], (const int32_t*)d[0], dst->d_bricks, op, call.st);
+        return hipSuccess;
+    });
 }
 
 // ---- the pieces as rigid bodies with a pose (the rules: include/vrc.h; the kernels: vrc_rigid.hip) ---------------
+
+// maps in host memory are held to the limits of vrc_volume_stamp_affine here, maps in device memory by the kernel
+static int check_affines(const char* what, uint64_t count, const vrc_affine* maps, int mem)
+{
+    if (mem == VRC_MEM_HOST)
+        for (uint64_t i = 0; i < count; ++i)
+            if (const int rc = check_affine(what, maps + i, (long long)i)) return rc;
+    return VRC_OK;
+}
 
 extern "C" int vrc_rigid_moments(const vrc_labels* l, uint64_t first, uint64_t capacity, vrc_piece_moments* out, int mem, void* stream)
 {
@@ -238,23 +238,11 @@ extern "C" int vrc_rigid_moments(const vrc_labels* l, uint64_t first, uint64_t c
     if (!l) return vrc::fail(VRC_ERR_INVALID, "%s: null labels", what);
     if (const int rc = check_mem(what, mem)) return rc;
     if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
-    const uint64_t want = first < l->count ? (capacity < l->count - first ? capacity : l->count - first) : 0u;
+    const uint64_t want = window_of(first, capacity, l->count);
     if (!want) return VRC_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = (size_t)want * sizeof(vrc_piece_moments);
-    vrc_piece_moments* d_out = out;
-    vrc_piece_moments* d_stage = nullptr;
-    hipError_t e = hipSetDevice(l->device);
-    if (mem == VRC_MEM_HOST) {
-        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, bytes);
-        d_out = d_stage;
-    }
-    if (e == hipSuccess) e = vrc::moments_run(l->d_ids, l->depth, first, want, d_out, st);
-    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipStreamSynchronize(st);
-    if (d_stage) (void)hipFree(d_stage);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    const Call call = snapshot_call(l->device, mem, stream);
+    const StagePart parts[] = {{out, (size_t)want * sizeof(vrc_piece_moments), STAGE_OUT}};
+    return staged_call(what, call, parts, [&](void* const* d) { return vrc::moments_run(l->d_ids, l->depth, first, want, (vrc_piece_moments*)d[0], call.st); });
 }
 
 extern "C" int vrc_rigid_place_affine(const vrc_labels* l, const uint8_t* keep, const vrc_affine* maps, const uint32_t* boxes, vrc_volume* dst, int op, int mem,
@@ -265,37 +253,18 @@ extern "C" int vrc_rigid_place_affine(const vrc_labels* l, const uint8_t* keep, 
     if (const int rc = check_op(what, op)) return rc;
     if (op == VRC_COPY_REPLACE) return vrc::fail(VRC_ERR_INVALID, "%s: VRC_COPY_REPLACE has no meaning where pieces may overlap", what);
     if (const int rc = check_mem(what, mem)) return rc;
-    if (dst->device != l->device) return vrc::fail(VRC_ERR_INVALID, "%s: labels on device %d, volume on device %d", what, l->device, dst->device);
+    if (const int rc = check_same(what, "labels", l->depth, l->device, dst, false)) return rc;      // dst may have another depth
     if (!maps && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null maps with %llu components", what, (unsigned long long)l->count);
-    if (mem == VRC_MEM_HOST)
-        for (uint64_t i = 0; i < l->count; ++i)
-            if (const int rc = check_affine(what, maps + i, (long long)i)) return rc;
+    if (const int rc = check_affines(what, l->count, maps, mem)) return rc;
     if (!l->count) return VRC_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t C = (size_t)l->count, map_bytes = C * sizeof(vrc_affine), box_bytes = boxes ? C * 24u : 0u, keep_bytes = keep ? C : 0u;
-    hipError_t e = hipSetDevice(l->device);
-    if (e == hipSuccess) e = order_behind_edits(dst, st);
-    const uint8_t* d_keep = keep;
-    const vrc_affine* d_maps = maps;
-    const uint32_t* d_boxes = boxes;
-    uint8_t* d_stage = nullptr;
-    if (mem == VRC_MEM_HOST) {                       // staged: the maps, then the boxes, then the keep bytes
-        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, map_bytes + box_bytes + keep_bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_stage, maps, map_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && boxes) e = hipMemcpyAsync(d_stage + map_bytes, boxes, box_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && keep) e = hipMemcpyAsync(d_stage + map_bytes + box_bytes, keep, keep_bytes, hipMemcpyHostToDevice, st);
-        d_maps = (const vrc_affine*)d_stage;
-        d_boxes = boxes ? (const uint32_t*)(d_stage + map_bytes) : nullptr;
-        d_keep = keep ? d_stage + map_bytes + box_bytes : nullptr;
-    }
-    if (e == hipSuccess) {
-        vrc::place_affine_run(l->d_ids, l->d_records, l->count, l->depth, d_keep, d_maps, d_boxes, dst->d_bricks, dst->depth, op, st);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = finish(dst, mem, st, true);
-    if (d_stage) (void)hipFree(d_stage);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    const size_t C = (size_t)l->count;
+    const Call call = volume_call(l->device, mem, stream, dst, true);
+    const StagePart parts[] = {{maps, C * sizeof(vrc_affine), STAGE_IN}, {boxes, C * 24u, STAGE_IN}, {keep, C, STAGE_IN}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        vrc::place_affine_run(l->d_ids, l->d_records, l->count, l->depth, (const uint8_t*)d[2], (const vrc_affine*)d[0], (const uint32_t*)d[1], dst->d_bricks,
+                              dst->depth, op, call.st);
+        return hipSuccess;
+    });
 }
 
 extern "C" int vrc_rigid_contacts(const vrc_labels* l, const uint8_t* keep, const vrc_affine* maps, const uint32_t* boxes, vrc_volume* world,
@@ -304,39 +273,19 @@ extern "C" int vrc_rigid_contacts(const vrc_labels* l, const uint8_t* keep, cons
     const char* what = "vrc_rigid_contacts";
     if (!l || !world) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
     if (const int rc = check_mem(what, mem)) return rc;
-    if (world->device != l->device) return vrc::fail(VRC_ERR_INVALID, "%s: labels on device %d, volume on device %d", what, l->device, world->device);
+    if (const int rc = check_same(what, "labels", l->depth, l->device, world, false)) return rc;    // the world may have another depth
     if (!maps && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null maps with %llu components", what, (unsigned long long)l->count);
     if (!out && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null records with %llu components", what, (unsigned long long)l->count);
-    if (mem == VRC_MEM_HOST)
-        for (uint64_t i = 0; i < l->count; ++i)
-            if (const int rc = check_affine(what, maps + i, (long long)i)) return rc;
+    if (const int rc = check_affines(what, l->count, maps, mem)) return rc;
     if (!l->count) return VRC_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t C = (size_t)l->count, map_bytes = C * sizeof(vrc_affine), box_bytes = boxes ? C * 24u : 0u, keep_bytes = keep ? C : 0u;
-    const size_t out_bytes = C * sizeof(vrc_piece_contact);
-    hipError_t e = hipSetDevice(l->device);
-    if (e == hipSuccess) e = order_behind_edits(world, st);          // the call reads the world's occupancy, as vrc_volume_count_boxes does
-    const uint8_t* d_keep = keep;
-    const vrc_affine* d_maps = maps;
-    const uint32_t* d_boxes = boxes;
-    vrc_piece_contact* d_out = out;
-    uint8_t* d_stage = nullptr;
-    if (mem == VRC_MEM_HOST) {                       // staged: the records, then the maps, then the boxes, then the keep bytes
-        if (e == hipSuccess) e = hipMalloc((void**)&d_stage, out_bytes + map_bytes + box_bytes + keep_bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_stage + out_bytes, maps, map_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && boxes) e = hipMemcpyAsync(d_stage + out_bytes + map_bytes, boxes, box_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && keep) e = hipMemcpyAsync(d_stage + out_bytes + map_bytes + box_bytes, keep, keep_bytes, hipMemcpyHostToDevice, st);
-        d_out = (vrc_piece_contact*)d_stage;
-        d_maps = (const vrc_affine*)(d_stage + out_bytes);
-        d_boxes = boxes ? (const uint32_t*)(d_stage + out_bytes + map_bytes) : nullptr;
-        d_keep = keep ? d_stage + out_bytes + map_bytes + box_bytes : nullptr;
-    }
-    if (e == hipSuccess) e = vrc::contacts_run(l->d_ids, l->d_records, l->count, l->depth, d_keep, d_maps, d_boxes, world->d_bricks, world->depth, d_out, st);
-    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = finish(world, mem, st, false);           // not an edit: the world is only read
-    if (d_stage) (void)hipFree(d_stage);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    const size_t C = (size_t)l->count;
+    // the call reads the world's occupancy, as vrc_volume_count_boxes does: behind its last edit, not an edit itself
+    const Call call = volume_call(l->device, mem, stream, world, false);
+    const StagePart parts[] = {{out, C * sizeof(vrc_piece_contact), STAGE_OUT}, {maps, C * sizeof(vrc_affine), STAGE_IN}, {boxes, C * 24u, STAGE_IN}, {keep, C, STAGE_IN}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        return vrc::contacts_run(l->d_ids, l->d_records, l->count, l->depth, (const uint8_t*)d[3], (const vrc_affine*)d[1], (const uint32_t*)d[2], world->d_bricks,
+                                 world->depth, (vrc_piece_contact*)d[0], call.st);
+    });
 }
 
 // ---- distance field ----------------------------------------------------------
@@ -361,13 +310,8 @@ extern "C" int vrc_volume_distance_field(vrc_volume* medium, int to, int outside
         return vrc::fail_hip(e, what);
     }
     if (stats) {
-        stats->features = host[0];
-        stats->max_d2 = 0u; stats->argmax[0] = stats->argmax[1] = stats->argmax[2] = 0u; stats->reserved = 0u;
-        if (host[1]) {
-            const uint32_t index = ~(uint32_t)host[1], mask = (1u << d->depth) - 1u;
-            stats->max_d2 = (uint32_t)(host[1] >> 32);
-            stats->argmax[0] = index >> (2u * d->depth); stats->argmax[1] = (index >> d->depth) & mask; stats->argmax[2] = index & mask;
-        }
+        stats->features = host[0]; stats->reserved = 0u;
+        decode_argmax(host[1], d->depth, &stats->max_d2, stats->argmax);
     }
     *out = d;
     return VRC_OK;
@@ -395,10 +339,11 @@ extern "C" int vrc_distance_at(const vrc_distance* d, uint64_t n, const uint32_t
     if (const int rc = check_mem(what, mem)) return rc;
     if (n == 0) return VRC_OK;
     if (!xyz || !d2) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
-    if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "%s: too many voxels for one launch", what);
-    hipStream_t st = (hipStream_t)stream;
-    return staged_call(what, d->device, nullptr, xyz, (size_t)n * 12u, d2, (size_t)n * 4u, mem, st, [&](const void* d_xyz, void* d_d2) {
-        vrc::distance_at_run(d->d_field, d->depth, n, (const uint32_t*)d_xyz, (uint32_t*)d_d2, st);
+    if (const int rc = check_count(what, n, LANE_ITEMS, "voxels")) return rc;
+    const Call call = snapshot_call(d->device, mem, stream);
+    const StagePart parts[] = {{xyz, (size_t)n * 12u, STAGE_IN}, {d2, (size_t)n * 4u, STAGE_OUT}};
+    return staged_call(what, call, parts, [&](void* const* p) {
+        vrc::distance_at_run(d->d_field, d->depth, n, (const uint32_t*)p[0], (uint32_t*)p[1], call.st);
         return hipSuccess;
     });
 }
@@ -409,8 +354,7 @@ extern "C" int vrc_distance_download(const vrc_distance* d, uint32_t* d2_host)
     if (!d || !d2_host) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
     hipError_t e = hipSetDevice(d->device);
     if (e == hipSuccess) e = hipMemcpy(d2_host, d->d_field, (size_t)4u << (3u * d->depth), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    return done(e, what);
 }
 
 extern "C" int vrc_distance_select(const vrc_distance* d, uint32_t lo, uint32_t hi, vrc_volume* dst, int op, void* stream)
@@ -419,8 +363,7 @@ extern "C" int vrc_distance_select(const vrc_distance* d, uint32_t lo, uint32_t 
     if (!d || !dst) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
     if (const int rc = check_op(what, op)) return rc;
     if (lo > hi) return vrc::fail(VRC_ERR_INVALID, "%s: lo %u above hi %u", what, lo, hi);
-    if (dst->depth != d->depth) return vrc::fail(VRC_ERR_INVALID, "%s: field of depth %u, volume of depth %u", what, d->depth, dst->depth);
-    if (dst->device != d->device) return vrc::fail(VRC_ERR_INVALID, "%s: field on device %d, volume on device %d", what, d->device, dst->device);
+    if (const int rc = check_same(what, "field", d->depth, d->device, dst)) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipSetDevice(d->device);
     if (e == hipSuccess) e = order_behind_edits(dst, st);
@@ -429,8 +372,7 @@ extern "C" int vrc_distance_select(const vrc_distance* d, uint32_t lo, uint32_t 
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    return done(e, what);
 }
 
 // ---- travel-distance field -----------------------------------------------------
@@ -467,13 +409,8 @@ extern "C" int vrc_travel_field(vrc_volume* seeds, vrc_volume* medium, int conne
         return vrc::fail(VRC_ERR_HIP, "%s: internal error: no fixed point within the bound of %u sweeps", what, sweeps);
     }
     if (stats) {
-        stats->seeds = host[0]; stats->reached = host[1];
-        stats->max_steps = 0u; stats->argmax[0] = stats->argmax[1] = stats->argmax[2] = 0u; stats->sweeps = sweeps; stats->reserved = 0u;
-        if (host[2]) {
-            const uint32_t index = ~(uint32_t)host[2], mask = (1u << d->depth) - 1u;
-            stats->max_steps = (uint32_t)(host[2] >> 32);
-            stats->argmax[0] = index >> (2u * d->depth); stats->argmax[1] = (index >> d->depth) & mask; stats->argmax[2] = index & mask;
-        }
+        stats->seeds = host[0]; stats->reached = host[1]; stats->sweeps = sweeps; stats->reserved = 0u;
+        decode_argmax(host[2], d->depth, &stats->max_steps, stats->argmax);
     }
     *out = d;
     return VRC_OK;
@@ -490,31 +427,13 @@ extern "C" int vrc_travel_trace_paths(const vrc_distance* d, uint64_t n, const u
     if (n == 0) return VRC_OK;
     if (!start_xyz || !lengths) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
     if (!paths_xyz && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null paths with capacity %u", what, capacity);
-    if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "%s: too many starts for one launch", what);
+    if (const int rc = check_count(what, n, LANE_ITEMS, "starts")) return rc;
     if (capacity && n > (1ull << 58) / capacity) return vrc::fail(VRC_ERR_INVALID, "%s: %llu routes of capacity %u are too many", what, (unsigned long long)n, capacity);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t in_bytes = (size_t)n * 12u, len_bytes = (size_t)n * 4u, path_bytes = (size_t)n * capacity * 12u;
-    hipError_t e = hipSetDevice(d->device);
-    const uint32_t* d_in = start_xyz;
-    uint32_t *d_len = lengths, *d_paths = paths_xyz;
-    uint8_t* own = nullptr;
-    if (mem == VRC_MEM_HOST) {
-        // staged: starts, lengths, paths.  The caller's paths go up first, so that what the kernel leaves alone comes back as it was.
-        if (e == hipSuccess) e = hipMalloc((void**)&own, in_bytes + len_bytes + path_bytes);
-        d_in = (const uint32_t*)own; d_len = (uint32_t*)(own + in_bytes); d_paths = (uint32_t*)(own + in_bytes + len_bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync(own, start_xyz, in_bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && path_bytes) e = hipMemcpyAsync(d_paths, paths_xyz, path_bytes, hipMemcpyHostToDevice, st);
-    }
-    if (e == hipSuccess) {
-        vrc::travel_trace_run(d->d_field, d->depth, d->connectivity, n, d_in, capacity, d_paths, d_len, st);
-        e = hipGetLastError();
-    }
-    if (mem == VRC_MEM_HOST) {
-        if (e == hipSuccess) e = hipMemcpyAsync(lengths, d_len, len_bytes, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && path_bytes) e = hipMemcpyAsync(paths_xyz, d_paths, path_bytes, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (own) (void)hipFree(own);
-    }
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    const Call call = snapshot_call(d->device, mem, stream);
+    // the caller's paths go up first, so that what the kernel leaves alone comes back as it was
+    const StagePart parts[] = {{start_xyz, (size_t)n * 12u, STAGE_IN}, {lengths, (size_t)n * 4u, STAGE_OUT}, {paths_xyz, (size_t)n * capacity * 12u, STAGE_INOUT}};
+    return staged_call(what, call, parts, [&](void* const* p) {
+        vrc::travel_trace_run(d->d_field, d->depth, d->connectivity, n, (const uint32_t*)p[0], capacity, (uint32_t*)p[2], (uint32_t*)p[1], call.st);
+        return hipSuccess;
+    });
 }

@@ -13,7 +13,9 @@
 // commit / download.  Boxes, spheres, spheres at the hits of a ray batch, region copies and the two queries have their
 // kernels here, over the box-of-words layout of vrc_box_words.h.  The other features keep theirs in files of their own:
 // vrc_flood.hip, vrc_voxelize.hip, vrc_surface.hip, vrc_rects.hip, vrc_stamp.hip.  The snapshots taken from a volume (labels, distance
-// fields) are in vrc_snapshots.hip; what the entry points of both files share is in vrc_volume_state.h.
+// fields) are in vrc_snapshots.hip; what the entry points of both files share -- the checks, the ordering rule and staged_call,
+// the one frame of every call that takes lists -- is in vrc_volume_state.h, and the ordering of every entry point is the
+// table in DESIGN.md.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -343,26 +345,12 @@ int volume_new(uint32_t depth, int device, vrc_volume** out)
     return VRC_OK;
 }
 
-// Shared frame of the edit calls that read a list of items: `words_per_item` u32 per item at `items`; host memory is
-// staged and the call synchronous, device memory is used in place and the call asynchronous on `st`.
-template <class Launch>
-int edit(vrc_volume* v, const char* what, uint64_t count, uint32_t words_per_item, const uint32_t* items, int mem, hipStream_t st, Launch launch)
-{
-    hipError_t e = hipSetDevice(v->device);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    const uint32_t* d_items = items;
-    if (mem == VRC_MEM_HOST) {
-        const size_t need = (size_t)count * words_per_item * 4u;
-        if ((e = order_behind_edits(v, st)) != hipSuccess) return vrc::fail_hip(e, what);
-        if ((e = reserve(v->d_stage, v->stage_cap, need)) != hipSuccess) return vrc::fail_hip(e, what);
-        if ((e = hipMemcpyAsync(v->d_stage, items, need, hipMemcpyHostToDevice, st)) != hipSuccess) return vrc::fail_hip(e, what);
-        d_items = v->d_stage;
-    }
-    launch(d_items);
-    if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
-    if ((e = finish(v, mem, st, true)) != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
-}
+// An edit that reads one list: staged in the volume's block, recorded as its last edit, and -- unlike every other call on a
+// volume -- behind the last asynchronous edit in host form only, where it writes that block; in device form it stays
+// unordered against edits on other streams, as it always was.
+Call edit_call(vrc_volume* v, int mem, void* stream) { return Call{v->device, mem, (hipStream_t)stream, v, true, true, false}; }
+// A query: a list in and a list out through the volume's block, behind the last asynchronous edit whatever the memory kind.
+Call query_call(vrc_volume* v, int mem, void* stream) { return Call{v->device, mem, (hipStream_t)stream, v, false, true, true}; }
 
 // workgroups per item for the kernels that take one item per blockIdx.x: a few items are spread over up to 1024
 // workgroups each (a whole 1024^3 volume is 2^25 words); many items: one workgroup each.  A workgroup that finds
@@ -428,43 +416,50 @@ extern "C" uint32_t vrc_volume_depth(const vrc_volume* v) { return v ? v->depth 
 
 extern "C" int vrc_volume_set_voxels(vrc_volume* v, uint64_t n, const uint32_t* xyz, int solid, int mem, void* stream)
 {
-    if (!v) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_set_voxels: null volume");
-    if (const int rc = check_mem("vrc_volume_set_voxels", mem)) return rc;
+    const char* what = "vrc_volume_set_voxels";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (const int rc = check_mem(what, mem)) return rc;
     if (n == 0) return VRC_OK;
-    if (!xyz) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_set_voxels: null buffer");
-    if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_set_voxels: too many voxels for one launch");
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t S = 1u << v->depth;
-    return edit(v, "vrc_volume_set_voxels", n, 3, xyz, mem, st, [&](const uint32_t* d_xyz) {
-        hipLaunchKernelGGL(k_set_voxels, grid_for(n), dim3(256), 0, st, v->d_bricks, S, n, d_xyz, solid ? 1u : 0u);
+    if (!xyz) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (const int rc = check_count(what, n, LANE_ITEMS, "voxels")) return rc;
+    const Call call = edit_call(v, mem, stream);
+    const StagePart parts[] = {{xyz, (size_t)n * 12u, STAGE_IN}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        hipLaunchKernelGGL(k_set_voxels, grid_for(n), dim3(256), 0, call.st, v->d_bricks, 1u << v->depth, n, (const uint32_t*)d[0], solid ? 1u : 0u);
+        return hipSuccess;
     });
 }
 
 extern "C" int vrc_volume_fill_boxes(vrc_volume* v, uint64_t n, const uint32_t* lo_hi, int solid, int mem, void* stream)
 {
-    if (!v) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_boxes: null volume");
-    if (const int rc = check_mem("vrc_volume_fill_boxes", mem)) return rc;
+    const char* what = "vrc_volume_fill_boxes";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (const int rc = check_mem(what, mem)) return rc;
     if (n == 0) return VRC_OK;
-    if (!lo_hi) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_boxes: null buffer");
-    if (n > 0x7fffffffull) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_boxes: too many boxes for one launch");
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t S = 1u << v->depth;
-    const uint32_t split = split_for(v, n);
-    return edit(v, "vrc_volume_fill_boxes", n, 6, lo_hi, mem, st, [&](const uint32_t* d_boxes) {
-        hipLaunchKernelGGL(k_fill_boxes, dim3((uint32_t)n, split), dim3(256), 0, st, v->d_bricks, S, d_boxes, solid ? 1u : 0u);
+    if (!lo_hi) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (const int rc = check_count(what, n, GROUP_ITEMS, "boxes")) return rc;
+    const Call call = edit_call(v, mem, stream);
+    const StagePart parts[] = {{lo_hi, (size_t)n * 24u, STAGE_IN}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        hipLaunchKernelGGL(k_fill_boxes, dim3((uint32_t)n, split_for(v, n)), dim3(256), 0, call.st, v->d_bricks, 1u << v->depth, (const uint32_t*)d[0],
+                           solid ? 1u : 0u);
+        return hipSuccess;
     });
 }
 
 extern "C" int vrc_volume_fill_spheres(vrc_volume* v, uint64_t n, const int32_t* centre_radius, int solid, int mem, void* stream)
 {
-    if (!v) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_spheres: null volume");
-    if (const int rc = check_mem("vrc_volume_fill_spheres", mem)) return rc;
+    const char* what = "vrc_volume_fill_spheres";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (const int rc = check_mem(what, mem)) return rc;
     if (n == 0) return VRC_OK;
-    if (!centre_radius) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_spheres: null buffer");
-    if (n > 0x7fffffffull) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_fill_spheres: too many spheres for one launch");
-    hipStream_t st = (hipStream_t)stream;
-    return edit(v, "vrc_volume_fill_spheres", n, 4, (const uint32_t*)centre_radius, mem, st, [&](const uint32_t* d_spheres) {
-        launch_fill_spheres(v, n, (const int32_t*)d_spheres, -1, solid, st);
+    if (!centre_radius) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (const int rc = check_count(what, n, GROUP_ITEMS, "spheres")) return rc;
+    const Call call = edit_call(v, mem, stream);
+    const StagePart parts[] = {{centre_radius, (size_t)n * 16u, STAGE_IN}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        launch_fill_spheres(v, n, (const int32_t*)d[0], -1, solid, call.st);
+        return hipSuccess;
     });
 }
 
@@ -476,11 +471,12 @@ extern "C" int vrc_volume_fill_spheres_at_hits(vrc_volume* v, uint64_t n, const 
     if (radius < 0 || radius > VRC_BRUSH_LIMIT) return vrc::fail(VRC_ERR_INVALID, "%s: radius %d not in [0, 2^20]", what, radius);
     if (n == 0) return VRC_OK;
     if (!hits) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
-    if (n > 0x7fffffffull) return vrc::fail(VRC_ERR_INVALID, "%s: too many hits for one launch", what);
+    if (const int rc = check_count(what, n, GROUP_ITEMS, "hits")) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipSetDevice(v->device);
-    // the centres go through the staging block (n x 4 int32, then the hits themselves when they come from the host),
-    // which an earlier call on another stream may still be reading
+    // Not a staged_call: the centres, no list of the caller's, go through the staging block in BOTH memory kinds (n x 4
+    // int32, then the hits themselves when they come from the host), which an earlier call on another stream may still
+    // be reading
     if (e == hipSuccess) e = order_behind_edits(v, st);
     if (e == hipSuccess) e = reserve(v->d_stage, v->stage_cap, (size_t)n * (mem == VRC_MEM_HOST ? 64u : 16u));
     if (e != hipSuccess) return vrc::fail_hip(e, what);
@@ -492,9 +488,8 @@ extern "C" int vrc_volume_fill_spheres_at_hits(vrc_volume* v, uint64_t n, const 
     }
     hipLaunchKernelGGL(k_hits_to_centres, grid_for(n), dim3(256), 0, st, n, d_hits, v->depth, radius, solid ? 1u : 0u, d_centres);
     launch_fill_spheres(v, n, d_centres, radius, solid, st);
-    if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
-    if ((e = finish(v, mem, st, true)) != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    if ((e = hipGetLastError()) == hipSuccess) e = finish(v, mem, st, true);
+    return done(e, what);
 }
 
 extern "C" int vrc_volume_xor_mesh(vrc_volume* v, uint64_t n, const int32_t* tris, int mem, void* stream)
@@ -504,7 +499,7 @@ extern "C" int vrc_volume_xor_mesh(vrc_volume* v, uint64_t n, const int32_t* tri
     if (const int rc = check_mem(what, mem)) return rc;
     if (n == 0) return VRC_OK;
     if (!tris) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
-    if (n > 0x7fffffffull) return vrc::fail(VRC_ERR_INVALID, "%s: too many triangles for one launch", what);
+    if (const int rc = check_count(what, n, GROUP_ITEMS, "triangles")) return rc;
     hipStream_t st = (hipStream_t)stream;
     // the mark field is shared by every call and the scan's read-modify-write of the occupancy is not atomic: behind the
     // last asynchronous edit whatever the memory kind
@@ -516,8 +511,10 @@ extern "C" int vrc_volume_xor_mesh(vrc_volume* v, uint64_t n, const int32_t* tri
         if (e != hipSuccess && v->d_marks) { (void)hipFree(v->d_marks); v->d_marks = nullptr; }
     }
     if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return edit(v, what, n, 9, (const uint32_t*)tris, mem, st, [&](const uint32_t* d_tris) {
-        vrc::voxelize_run(v->d_bricks, v->d_marks, v->depth, n, (const int32_t*)d_tris, st);
+    const StagePart parts[] = {{tris, (size_t)n * 36u, STAGE_IN}};
+    return staged_call(what, edit_call(v, mem, stream), parts, [&](void* const* d) {
+        vrc::voxelize_run(v->d_bricks, v->d_marks, v->depth, n, (const int32_t*)d[0], st);
+        return hipSuccess;
     });
 }
 
@@ -550,9 +547,8 @@ extern "C" int vrc_volume_copy_region(vrc_volume* dst, vrc_volume* src, const ui
     if (e != hipSuccess) return vrc::fail_hip(e, what);
     hipLaunchKernelGGL(k_copy_region, dim3(box_launch_groups(lo, hi)), dim3(256), 0, st, dst->d_bricks, (uint32_t)Sd, (const uint8_t*)src->d_bricks, (uint32_t)Ss,
                        lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], off[0], off[1], off[2], op);
-    if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
-    if ((e = finish(dst, VRC_MEM_DEVICE, st, true)) != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    if ((e = hipGetLastError()) == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
+    return done(e, what);
 }
 
 extern "C" int vrc_volume_stamp_affine(vrc_volume* dst, vrc_volume* src, const vrc_affine* map, const uint32_t dst_lo[3], const uint32_t dst_hi[3],
@@ -573,9 +569,8 @@ extern "C" int vrc_volume_stamp_affine(vrc_volume* dst, vrc_volume* src, const v
     if (e == hipSuccess) e = order_behind_edits(dst, st);
     if (e != hipSuccess) return vrc::fail_hip(e, what);
     vrc::stamp_affine_run(dst->d_bricks, dst->depth, src->d_bricks, src->depth, *map, lo, hi, op, st);
-    if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
-    if ((e = finish(dst, VRC_MEM_DEVICE, st, true)) != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    if ((e = hipGetLastError()) == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
+    return done(e, what);
 }
 
 extern "C" int vrc_volume_clone(vrc_volume* src, vrc_volume** out)
@@ -600,10 +595,11 @@ extern "C" int vrc_volume_get_voxels(vrc_volume* v, uint64_t n, const uint32_t* 
     if (const int rc = check_mem(what, mem)) return rc;
     if (n == 0) return VRC_OK;
     if (!xyz || !solid_out) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
-    if (n > 0x7fffffffull * 256ull) return vrc::fail(VRC_ERR_INVALID, "%s: too many voxels for one launch", what);
-    hipStream_t st = (hipStream_t)stream;
-    return staged_call(what, v->device, v, xyz, (size_t)n * 12u, solid_out, (size_t)n, mem, st, [&](const void* d_xyz, void* d_out) {
-        hipLaunchKernelGGL(k_get_voxels, grid_for(n), dim3(256), 0, st, (const uint8_t*)v->d_bricks, 1u << v->depth, n, (const uint32_t*)d_xyz, (uint8_t*)d_out);
+    if (const int rc = check_count(what, n, LANE_ITEMS, "voxels")) return rc;
+    const Call call = query_call(v, mem, stream);
+    const StagePart parts[] = {{xyz, (size_t)n * 12u, STAGE_IN}, {solid_out, (size_t)n, STAGE_OUT}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        hipLaunchKernelGGL(k_get_voxels, grid_for(n), dim3(256), 0, call.st, (const uint8_t*)v->d_bricks, 1u << v->depth, n, (const uint32_t*)d[0], (uint8_t*)d[1]);
         return hipSuccess;
     });
 }
@@ -615,161 +611,143 @@ extern "C" int vrc_volume_count_boxes(vrc_volume* v, uint64_t n, const uint32_t*
     if (const int rc = check_mem(what, mem)) return rc;
     if (n == 0) return VRC_OK;
     if (!lo_hi || !counts) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
-    if (n > 0x7fffffffull) return vrc::fail(VRC_ERR_INVALID, "%s: too many boxes for one launch", what);
-    hipStream_t st = (hipStream_t)stream;
-    return staged_call(what, v->device, v, lo_hi, (size_t)n * 24u, counts, (size_t)n * 8u, mem, st, [&](const void* d_boxes, void* d_counts) {
-        const hipError_t e = hipMemsetAsync(d_counts, 0, (size_t)n * 8u, st);
+    if (const int rc = check_count(what, n, GROUP_ITEMS, "boxes")) return rc;
+    const Call call = query_call(v, mem, stream);
+    const StagePart parts[] = {{lo_hi, (size_t)n * 24u, STAGE_IN}, {counts, (size_t)n * 8u, STAGE_OUT}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        const hipError_t e = hipMemsetAsync(d[1], 0, (size_t)n * 8u, call.st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_count_boxes, dim3((uint32_t)n, split_for(v, n)), dim3(256), 0, st, v->d_bricks, 1u << v->depth, (const uint32_t*)d_boxes,
-                           (unsigned long long*)d_counts);
+        hipLaunchKernelGGL(k_count_boxes, dim3((uint32_t)n, split_for(v, n)), dim3(256), 0, call.st, v->d_bricks, 1u << v->depth, (const uint32_t*)d[0],
+                           (unsigned long long*)d[1]);
         return hipSuccess;
     });
 }
 
-// the offsets block of the two surface calls, allocated by the first
-static hipError_t surface_reserve(vrc_volume* v)
+// ---- the two meshes: exposed faces (vrc_surface.hip) and merged rectangles (vrc_rects.hip) -------------------------
+
+// What the two extractors differ in.  Each keeps a block of its own in the volume (offsets, totals; the rectangles' row
+// fields), allocated by the first call and fixed in size.
+struct MeshRuns {
+    hipError_t (*reserve)(vrc_volume* v);
+    void (*prepare)(vrc_volume* v, hipStream_t st);                 // what every later pass reads; nullptr: nothing
+    void (*count)(vrc_volume* v, int closed, hipStream_t st);
+    void (*offsets)(vrc_volume* v, int closed, unsigned long long* d_total, hipStream_t st);
+    void (*emit)(vrc_volume* v, int closed, int format, uint64_t first, uint64_t n, void* out, hipStream_t st);
+    unsigned long long* (*total_slot)(vrc_volume* v);
+    unsigned long long* (*direction_slots)(vrc_volume* v);
+};
+
+const MeshRuns SURFACE = {
+    [](vrc_volume* v) { return v->d_surface ? hipSuccess : hipMalloc((void**)&v->d_surface, vrc::surface_scratch_bytes(v->depth)); },
+    nullptr,
+    [](vrc_volume* v, int closed, hipStream_t st) { vrc::surface_count_run(v->d_bricks, v->depth, closed, v->d_surface, st); },
+    [](vrc_volume* v, int closed, unsigned long long* d_total, hipStream_t st) { vrc::surface_offsets_run(v->d_bricks, v->depth, closed, v->d_surface, d_total, st); },
+    [](vrc_volume* v, int closed, int format, uint64_t first, uint64_t n, void* out, hipStream_t st) {
+        vrc::surface_emit_run(v->d_bricks, v->depth, closed, format, first, n, out, v->d_surface, st);
+    },
+    [](vrc_volume* v) { return vrc::surface_total_slot(v->d_surface, v->depth); },
+    [](vrc_volume* v) { return vrc::surface_direction_slots(v->d_surface, v->depth); },
+};
+
+const MeshRuns RECTS = {
+    [](vrc_volume* v) { return v->d_rects ? hipSuccess : hipMalloc((void**)&v->d_rects, vrc::rect_scratch_bytes(v->depth)); },
+    [](vrc_volume* v, hipStream_t st) { vrc::rect_rows_run(v->d_bricks, v->depth, v->d_rects, st); },
+    [](vrc_volume* v, int closed, hipStream_t st) { vrc::rect_count_run(v->depth, closed, v->d_rects, st); },
+    [](vrc_volume* v, int closed, unsigned long long* d_total, hipStream_t st) { vrc::rect_offsets_run(v->depth, closed, v->d_rects, d_total, st); },
+    [](vrc_volume* v, int closed, int format, uint64_t first, uint64_t n, void* out, hipStream_t st) {
+        vrc::rect_emit_run(v->depth, closed, format, first, n, out, v->d_rects, st);
+    },
+    [](vrc_volume* v) { return vrc::rect_total_slot(v->d_rects, v->depth); },
+    [](vrc_volume* v) { return vrc::rect_direction_slots(v->d_rects, v->depth); },
+};
+
+// the per-direction totals: synchronous on the NULL stream, behind the last asynchronous edit (a device-memory extraction,
+// which shares the block, included)
+static int mesh_count(const char* what, const MeshRuns& runs, vrc_volume* v, int closed, uint64_t counts[6])
 {
-    return v->d_surface ? hipSuccess : hipMalloc((void**)&v->d_surface, vrc::surface_scratch_bytes(v->depth));
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (!counts) return vrc::fail(VRC_ERR_INVALID, "%s: null counts", what);
+    hipError_t e = hipSetDevice(v->device);
+    if (e == hipSuccess) e = order_behind_edits(v, nullptr);
+    if (e == hipSuccess) e = runs.reserve(v);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    if (runs.prepare) runs.prepare(v, nullptr);
+    runs.count(v, closed, nullptr);
+    e = hipGetLastError();
+    unsigned long long host[6];
+    if (e == hipSuccess) e = hipMemcpy(host, runs.direction_slots(v), sizeof host, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    for (int d = 0; d < 6; ++d) counts[d] = host[d];
+    return VRC_OK;
+}
+
+// records [first, first + capacity) of the mesh and its total.  Device memory: asynchronous on the caller's stream.  Host
+// memory: synchronous; the total is read back first, then the records come through the volume's staging block in windows
+// of at most 2^20.
+static int mesh_extract(const char* what, const MeshRuns& runs, vrc_volume* v, int closed, int format, uint64_t first, uint64_t capacity, void* out,
+                        uint64_t* total, int mem, void* stream)
+{
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (format != VRC_SURFACE_FACES && format != VRC_SURFACE_TRIANGLES) return vrc::fail(VRC_ERR_INVALID, "%s: bad format %d", what, format);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
+    const size_t record = format == VRC_SURFACE_FACES ? 16u : 72u;
+    if (mem == VRC_MEM_DEVICE && capacity && ((uintptr_t)out & (format == VRC_SURFACE_FACES ? 15u : 3u)))
+        return vrc::fail(VRC_ERR_INVALID, "%s: device buffer %p is not aligned to %d bytes", what, out, format == VRC_SURFACE_FACES ? 16 : 4);
+    hipStream_t st = (hipStream_t)stream;
+    // behind the last asynchronous edit whatever the memory kind: the extractor's block is shared by every call
+    hipError_t e = hipSetDevice(v->device);
+    if (e == hipSuccess) e = order_behind_edits(v, st);
+    if (e == hipSuccess) e = runs.reserve(v);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    if (runs.prepare) runs.prepare(v, st);
+    if (mem == VRC_MEM_DEVICE) {
+        runs.offsets(v, closed, (unsigned long long*)total, st);
+        if (capacity) runs.emit(v, closed, format, first, capacity, out, st);
+        // recorded as an edit: the next call, on whatever stream, must not rewrite the block under this one
+        if ((e = hipGetLastError()) == hipSuccess) e = finish(v, mem, st, true);
+        return done(e, what);
+    }
+    runs.offsets(v, closed, nullptr, st);
+    e = hipGetLastError();
+    unsigned long long T = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&T, runs.total_slot(v), 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    if (total) *total = T;
+    // the block stays valid for every window: the call holds the stream until it returns
+    const uint64_t want = window_of(first, capacity, T);
+    const uint64_t window = want < (1ull << 20) ? want : (1ull << 20);
+    if (want) e = reserve(v->d_stage, v->stage_cap, (size_t)window * record);
+    for (uint64_t at = 0; at < want && e == hipSuccess; at += window) {
+        const uint64_t now = want - at < window ? want - at : window;
+        runs.emit(v, closed, format, first + at, now, v->d_stage, st);
+        if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpyAsync((uint8_t*)out + at * record, v->d_stage, (size_t)now * record, hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) e = finish(v, mem, st, false);
+    return done(e, what);
 }
 
 extern "C" int vrc_volume_surface_count(vrc_volume* v, int closed, uint64_t counts[6])
 {
-    const char* what = "vrc_volume_surface_count";
-    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
-    if (!counts) return vrc::fail(VRC_ERR_INVALID, "%s: null counts", what);
-    // the NULL stream, behind the last asynchronous edit (a device-memory extraction, which shares the block, included)
-    hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = order_behind_edits(v, nullptr);
-    if (e == hipSuccess) e = surface_reserve(v);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    vrc::surface_count_run(v->d_bricks, v->depth, closed, v->d_surface, nullptr);
-    e = hipGetLastError();
-    unsigned long long host[6];
-    if (e == hipSuccess) e = hipMemcpy(host, vrc::surface_direction_slots(v->d_surface, v->depth), sizeof host, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    for (int d = 0; d < 6; ++d) counts[d] = host[d];
-    return VRC_OK;
+    return mesh_count("vrc_volume_surface_count", SURFACE, v, closed, counts);
 }
 
 extern "C" int vrc_volume_extract_surface(vrc_volume* v, int closed, int format, uint64_t first, uint64_t capacity, void* out, uint64_t* total,
                                           int mem, void* stream)
 {
-    const char* what = "vrc_volume_extract_surface";
-    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
-    if (format != VRC_SURFACE_FACES && format != VRC_SURFACE_TRIANGLES) return vrc::fail(VRC_ERR_INVALID, "%s: bad format %d", what, format);
-    if (const int rc = check_mem(what, mem)) return rc;
-    if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
-    const size_t record = format == VRC_SURFACE_FACES ? 16u : 72u;
-    if (mem == VRC_MEM_DEVICE && capacity && ((uintptr_t)out & (format == VRC_SURFACE_FACES ? 15u : 3u)))
-        return vrc::fail(VRC_ERR_INVALID, "%s: device buffer %p is not aligned to %d bytes", what, out, format == VRC_SURFACE_FACES ? 16 : 4);
-    hipStream_t st = (hipStream_t)stream;
-    // behind the last asynchronous edit whatever the memory kind: the offsets block is shared by every call
-    hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = order_behind_edits(v, st);
-    if (e == hipSuccess) e = surface_reserve(v);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    if (mem == VRC_MEM_DEVICE) {
-        vrc::surface_offsets_run(v->d_bricks, v->depth, closed, v->d_surface, (unsigned long long*)total, st);
-        if (capacity) vrc::surface_emit_run(v->d_bricks, v->depth, closed, format, first, capacity, out, v->d_surface, st);
-        if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
-        // recorded as an edit: the next call, on whatever stream, must not rewrite the offsets under this one
-        if ((e = finish(v, mem, st, true)) != hipSuccess) return vrc::fail_hip(e, what);
-        return VRC_OK;
-    }
-    vrc::surface_offsets_run(v->d_bricks, v->depth, closed, v->d_surface, nullptr, st);
-    e = hipGetLastError();
-    unsigned long long T = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&T, vrc::surface_total_slot(v->d_surface, v->depth), 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    if (total) *total = T;
-    // the offsets stay valid for every window: the call holds the stream until it returns
-    const uint64_t want = first < T ? (capacity < T - first ? capacity : T - first) : 0u;
-    const uint64_t window = want < (1ull << 20) ? want : (1ull << 20);
-    if (want && (e = reserve(v->d_stage, v->stage_cap, (size_t)window * record)) != hipSuccess) return vrc::fail_hip(e, what);
-    for (uint64_t done = 0; done < want; done += window) {
-        const uint64_t now = want - done < window ? want - done : window;
-        vrc::surface_emit_run(v->d_bricks, v->depth, closed, format, first + done, now, v->d_stage, v->d_surface, st);
-        if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
-        if ((e = hipMemcpyAsync((uint8_t*)out + done * record, v->d_stage, (size_t)now * record, hipMemcpyDeviceToHost, st)) != hipSuccess)
-            return vrc::fail_hip(e, what);
-    }
-    if ((e = finish(v, mem, st, false)) != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
-}
-
-// the block of the two rectangle calls (offsets, totals, row fields), allocated by the first
-static hipError_t rects_reserve(vrc_volume* v)
-{
-    return v->d_rects ? hipSuccess : hipMalloc((void**)&v->d_rects, vrc::rect_scratch_bytes(v->depth));
+    return mesh_extract("vrc_volume_extract_surface", SURFACE, v, closed, format, first, capacity, out, total, mem, stream);
 }
 
 extern "C" int vrc_rect_count(vrc_volume* v, int closed, uint64_t counts[6])
 {
-    const char* what = "vrc_rect_count";
-    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
-    if (!counts) return vrc::fail(VRC_ERR_INVALID, "%s: null counts", what);
-    // the NULL stream, behind the last asynchronous edit (a device-memory extraction, which shares the block, included)
-    hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = order_behind_edits(v, nullptr);
-    if (e == hipSuccess) e = rects_reserve(v);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    vrc::rect_rows_run(v->d_bricks, v->depth, v->d_rects, nullptr);
-    vrc::rect_count_run(v->depth, closed, v->d_rects, nullptr);
-    e = hipGetLastError();
-    unsigned long long host[6];
-    if (e == hipSuccess) e = hipMemcpy(host, vrc::rect_direction_slots(v->d_rects, v->depth), sizeof host, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    for (int d = 0; d < 6; ++d) counts[d] = host[d];
-    return VRC_OK;
+    return mesh_count("vrc_rect_count", RECTS, v, closed, counts);
 }
 
 extern "C" int vrc_extract_rects(vrc_volume* v, int closed, int format, uint64_t first, uint64_t capacity, void* out, uint64_t* total, int mem,
                                         void* stream)
 {
-    const char* what = "vrc_extract_rects";
-    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
-    if (format != VRC_SURFACE_FACES && format != VRC_SURFACE_TRIANGLES) return vrc::fail(VRC_ERR_INVALID, "%s: bad format %d", what, format);
-    if (const int rc = check_mem(what, mem)) return rc;
-    if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
-    const size_t record = format == VRC_SURFACE_FACES ? 16u : 72u;
-    if (mem == VRC_MEM_DEVICE && capacity && ((uintptr_t)out & (format == VRC_SURFACE_FACES ? 15u : 3u)))
-        return vrc::fail(VRC_ERR_INVALID, "%s: device buffer %p is not aligned to %d bytes", what, out, format == VRC_SURFACE_FACES ? 16 : 4);
-    hipStream_t st = (hipStream_t)stream;
-    // behind the last asynchronous edit whatever the memory kind: the block is shared by every call
-    hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = order_behind_edits(v, st);
-    if (e == hipSuccess) e = rects_reserve(v);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    vrc::rect_rows_run(v->d_bricks, v->depth, v->d_rects, st);
-    if (mem == VRC_MEM_DEVICE) {
-        vrc::rect_offsets_run(v->depth, closed, v->d_rects, (unsigned long long*)total, st);
-        if (capacity) vrc::rect_emit_run(v->depth, closed, format, first, capacity, out, v->d_rects, st);
-        if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
-        // recorded as an edit: the next call, on whatever stream, must not rewrite the block under this one
-        if ((e = finish(v, mem, st, true)) != hipSuccess) return vrc::fail_hip(e, what);
-        return VRC_OK;
-    }
-    vrc::rect_offsets_run(v->depth, closed, v->d_rects, nullptr, st);
-    e = hipGetLastError();
-    unsigned long long T = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&T, vrc::rect_total_slot(v->d_rects, v->depth), 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    if (total) *total = T;
-    // the row fields and the offsets stay valid for every window: the call holds the stream until it returns
-    const uint64_t want = first < T ? (capacity < T - first ? capacity : T - first) : 0u;
-    const uint64_t window = want < (1ull << 20) ? want : (1ull << 20);
-    if (want && (e = reserve(v->d_stage, v->stage_cap, (size_t)window * record)) != hipSuccess) return vrc::fail_hip(e, what);
-    for (uint64_t done = 0; done < want; done += window) {
-        const uint64_t now = want - done < window ? want - done : window;
-        vrc::rect_emit_run(v->depth, closed, format, first + done, now, v->d_stage, v->d_rects, st);
-        if ((e = hipGetLastError()) != hipSuccess) return vrc::fail_hip(e, what);
-        if ((e = hipMemcpyAsync((uint8_t*)out + done * record, v->d_stage, (size_t)now * record, hipMemcpyDeviceToHost, st)) != hipSuccess)
-            return vrc::fail_hip(e, what);
-    }
-    if ((e = finish(v, mem, st, false)) != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    return mesh_extract("vrc_extract_rects", RECTS, v, closed, format, first, capacity, out, total, mem, stream);
 }
 
 extern "C" int vrc_volume_flood(vrc_volume* region, vrc_volume* medium, int connectivity, int through, uint32_t max_sweeps, vrc_flood_stats* stats)
@@ -832,8 +810,7 @@ extern "C" int vrc_volume_download(vrc_volume* v, uint8_t* solid_host)
     }
     if (e == hipSuccess) e = hipMemcpy(solid_host, d_dense, S * S * S, hipMemcpyDeviceToHost);
     if (d_dense) (void)hipFree(d_dense);
-    if (e != hipSuccess) return vrc::fail_hip(e, "vrc_volume_download");
-    return VRC_OK;
+    return done(e, "vrc_volume_download");
 }
 
 extern "C" int vrc_volume_edit_scratch_bytes(const vrc_volume* v, uint64_t* bytes)

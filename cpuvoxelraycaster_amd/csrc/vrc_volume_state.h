@@ -1,7 +1,8 @@
 // vrc_volume_state.h -- what the entry points of the editable volume share (vrc_volume.hip: the volume itself;
-// vrc_snapshots.hip: the labels and distance fields taken from it): the volume's record, the rule that orders a call behind
-// the volume's last asynchronous edit, the end of a call that takes a memory kind, the grow-only device block, the
-// argument checks with one text each, and the frame of a host-memory call that takes a list in and hands a list back.
+// vrc_snapshots.hip: the labels and distance fields taken from it): the volume's record, the argument checks with one text
+// each, the rule that orders a call behind the volume's last asynchronous edit, the grow-only device block, and the one
+// frame of every call that takes a memory kind and lists of arguments (staged_call).  Which stream every entry point runs
+// on, what it waits for, whether it is recorded as an edit and whether it is synchronous: the table in DESIGN.md.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,6 +63,29 @@ inline int check_through(const char* what, int through)
     return through == VRC_FLOOD_SOLID || through == VRC_FLOOD_EMPTY ? VRC_OK : vrc::fail(VRC_ERR_INVALID, "%s: bad through %d", what, through);
 }
 
+// labels / field and volume on one device and, with_depth, of one depth; `noun` is what the snapshot is called
+inline int check_same(const char* what, const char* noun, uint32_t depth, int device, const vrc_volume* v, bool with_depth = true)
+{
+    if (with_depth && v->depth != depth) return vrc::fail(VRC_ERR_INVALID, "%s: %s of depth %u, volume of depth %u", what, noun, depth, v->depth);
+    if (v->device != device) return vrc::fail(VRC_ERR_INVALID, "%s: %s on device %d, volume on device %d", what, noun, device, v->device);
+    return VRC_OK;
+}
+// what one launch takes: a lane per item in 256-lane workgroups, or a workgroup (blockIdx.x) per item
+constexpr uint64_t LANE_ITEMS = 0x7fffffffull * 256ull, GROUP_ITEMS = 0x7fffffffull;
+inline int check_count(const char* what, uint64_t n, uint64_t limit, const char* items)
+{
+    return n <= limit ? VRC_OK : vrc::fail(VRC_ERR_INVALID, "%s: too many %s for one launch", what, items);
+}
+
+// how many of `count` items the window [first, first + capacity) holds
+inline uint64_t window_of(uint64_t first, uint64_t capacity, uint64_t count)
+{
+    return first < count ? (capacity < count - first ? capacity : count - first) : 0u;
+}
+
+// the end of every entry point that called HIP
+inline int done(hipError_t e, const char* what) { return e == hipSuccess ? VRC_OK : vrc::fail_hip(e, what); }
+
 // the limits of an affine map that keep s = m (2p + 1) + t below 2^41 and a word's deltas below 2^25 (vrc.h:
 // vrc_volume_stamp_affine); `piece` < 0: the call has one map, else the text names the piece
 inline int check_affine(const char* what, const vrc_affine* map, long long piece)
@@ -107,34 +131,70 @@ hipError_t reserve(T*& block, size_t& cap, size_t need)
     return e;
 }
 
-// The frame of the calls that take a list in and hand a list back: `in_bytes` at `in`, `out_bytes` at `out`.  Device memory
-// is used in place and the call stays asynchronous on `st`.  Host memory is staged, input then output, and the call is
-// synchronous: in the grow-only block of `v`, or, for the snapshots (v == nullptr), which deliberately keep no scratch, in
-// a block of the call's own.  A call on a volume reads its occupancy and writes its staging block: behind the volume's
-// last asynchronous edit whatever the memory kind.  launch(d_in, d_out) enqueues the work on `st` and returns what its
-// HIP calls returned.
-template <class Launch>
-int staged_call(const char* what, int device, vrc_volume* v, const void* in, size_t in_bytes, void* out, size_t out_bytes, int mem, hipStream_t st, Launch launch)
+// ---- the frame of a call that takes `mem` and lists of arguments ------------------------------------------------
+
+// One list: `bytes` at the caller's `p`, read by the launch (IN), written by it (OUT) or both (INOUT: it goes up first,
+// so that what the launch leaves alone comes back as it was).  p == nullptr or bytes == 0: the part is absent and its
+// device pointer is nullptr.
+enum { STAGE_IN = 1, STAGE_OUT = 2, STAGE_INOUT = 3 };
+struct StagePart {
+    const void* p;
+    size_t bytes;
+    int dir;
+};
+
+// How the call is ordered.  `v`: the volume it reads or writes, nullptr for a call on a snapshot alone.
+struct Call {
+    int device;
+    int mem;
+    hipStream_t st;
+    vrc_volume* v;
+    bool is_edit;          // a device-memory call is recorded as v's last asynchronous edit
+    bool stage_in_v;       // host memory is staged in v's grow-only block; else in a block of the call's own, freed at the end
+    bool wait_always;      // behind v's last asynchronous edit whatever the memory kind: the call reads the occupancy or a
+                           // block the volume shares.  false: a list edit waits in host form only, where it writes v's block
+};
+
+// Device memory: launch(d) gets the caller's pointers and the call stays asynchronous on `st`.  Host memory: the parts are
+// laid out in one block in the order given, the IN parts copied up, and after the launch the OUT parts copied down and the
+// stream synchronised.  In a block of the call's own every part starts on a multiple of 16 bytes, whatever the order.  In
+// v's block the parts are packed, because the block's size is observable (vrc_volume_edit_scratch_bytes) and is exactly the
+// sum of the parts; the two calls that put more than one part there give the part with the wider items first.  launch(d)
+// enqueues the work on `st` and returns what its HIP calls returned; it does not run after a failure.
+template <size_t N, class Launch>
+int staged_call(const char* what, const Call& c, const StagePart (&parts)[N], Launch launch)
 {
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess && v) e = order_behind_edits(v, st);
-    const void* d_in = in;
-    void* d_out = out;
-    void* own = nullptr;
-    if (mem == VRC_MEM_HOST) {
-        if (e == hipSuccess) e = v ? reserve(v->d_stage, v->stage_cap, in_bytes + out_bytes) : hipMalloc(&own, in_bytes + out_bytes);
-        uint8_t* block = v ? (uint8_t*)v->d_stage : (uint8_t*)own;
-        d_in = block;
-        d_out = block + in_bytes;
-        if (e == hipSuccess) e = hipMemcpyAsync(block, in, in_bytes, hipMemcpyHostToDevice, st);
+    void* d[N];
+    size_t at[N] = {}, total = 0;
+    for (size_t i = 0; i < N; ++i) {
+        const bool present = parts[i].p && parts[i].bytes;
+        d[i] = present ? (void*)parts[i].p : nullptr;
+        if (!present) continue;
+        if (!c.stage_in_v) total = (total + 15u) & ~(size_t)15u;
+        at[i] = total;
+        total += parts[i].bytes;
     }
-    if (e == hipSuccess) e = launch(d_in, d_out);
+    const bool host = c.mem == VRC_MEM_HOST;
+    uint8_t* own = nullptr;
+    hipError_t e = hipSetDevice(c.device);
+    if (e == hipSuccess && c.v && (c.wait_always || host)) e = order_behind_edits(c.v, c.st);
+    if (host && total) {
+        if (e == hipSuccess) e = c.stage_in_v ? reserve(c.v->d_stage, c.v->stage_cap, total) : hipMalloc((void**)&own, total);
+        uint8_t* block = c.stage_in_v ? (uint8_t*)c.v->d_stage : own;
+        for (size_t i = 0; i < N; ++i) {
+            if (!d[i]) continue;
+            d[i] = block + at[i];
+            if (e == hipSuccess && (parts[i].dir & STAGE_IN)) e = hipMemcpyAsync(d[i], parts[i].p, parts[i].bytes, hipMemcpyHostToDevice, c.st);
+        }
+    }
+    if (e == hipSuccess) e = launch((void* const*)d);
     if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && mem == VRC_MEM_HOST) e = hipStreamSynchronize(st);
+    if (host && total)
+        for (size_t i = 0; i < N; ++i)
+            if (e == hipSuccess && d[i] && (parts[i].dir & STAGE_OUT)) e = hipMemcpyAsync((void*)parts[i].p, d[i], parts[i].bytes, hipMemcpyDeviceToHost, c.st);
+    if (e == hipSuccess) e = finish(c.v, c.mem, c.st, c.is_edit);
     if (own) (void)hipFree(own);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    return VRC_OK;
+    return done(e, what);
 }
 
 }  // namespace

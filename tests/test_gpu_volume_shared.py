@@ -1,16 +1,22 @@
 """The code the volume features share (vrc_group.h, vrc_box_words.h, vrc_volume_state.h), at the smallest shapes at which
 it can go wrong: the workgroup sum with idle lanes and idle waves, the two ways a destination word is written at the sizes
 on either side of the shared-word rule, and the staged call with a block that has to grow and on a stream of its own behind
-a device-memory edit.  Every expectation is NumPy's (the models of tests/*_model.py); every comparison is exact."""
+a device-memory edit, with every combination of optional parts in a block of the call's own, and with a part that goes up
+and comes back.  Every expectation is NumPy's (the models of tests/*_model.py); every comparison is exact."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
 import components_model
+import contact_model
 import distance_model
+import fall_model
+import rigid_model
 import stamp_model
 import surface_model
+import travel_model
 
 pytestmark = pytest.mark.gpu
 
@@ -218,4 +224,222 @@ def test_staged_calls_in_device_memory_behind_an_edit_on_another_stream(built):
     assert (d_big_solid.cpu().numpy() == 1).all()
     assert d_big_counts.cpu().numpy().tolist() == [B ** 3, 9 * 7 * 5, B - 1]
     for h in (labels, field, volume, big):
+        h.close()
+
+
+# ---- the calls with several parts: labels, keep bytes, offsets, maps, boxes, records -----------------------------------
+
+def scattered_blocks(extra=0):
+    """16^3: seven small blocks (and `extra` more specks) that touch nowhere, so 7 + extra pieces under 6-connectivity -- no
+    multiple of 16, so the keep bytes end off any alignment"""
+    vol = np.zeros((16, 16, 16), np.uint8)
+    for (x, y, z), (a, b, c) in [((1, 1, 1), (3, 2, 1)), ((6, 1, 2), (1, 1, 1)), ((11, 2, 1), (2, 3, 2)), ((1, 7, 6), (2, 2, 3)),
+                                 ((6, 6, 11), (3, 1, 2)), ((11, 11, 6), (1, 3, 1)), ((2, 11, 11), (2, 2, 2))]:
+        vol[x:x + a, y:y + b, z:z + c] = 1
+    for k in range(extra):
+        vol[15, 2 * (k % 8), 2 * (k // 8)] = 1
+    return vol
+
+
+@functools.lru_cache(maxsize=None)
+def piece_case():
+    """the scene of the multi-part tests and everything the model says about it, computed once and never written again"""
+    rng = np.random.default_rng(4700)
+    vol = scattered_blocks()
+    ids, records = components_model.label(vol, 6)
+    count = len(records)
+    assert count == 7
+    offsets = rng.integers(-3, 4, (count, 3)).astype(np.int32)
+    maps = rigid_model.translation_maps(offsets)
+    boxes = rigid_model.moved_boxes(records, offsets, 16)
+    keep = (np.arange(count) % 3 != 1).astype(np.uint8)
+    base = (rng.random((16, 16, 16)) < 0.3).astype(np.uint8)
+    world = (rng.random((16, 16, 16)) < 0.2).astype(np.uint8)
+    world[:, :3, :] = 1
+    want = {"moments": rigid_model.moments(ids, count)}
+    for use_keep in (False, True):
+        k = keep if use_keep else None
+        want["select", use_keep] = apply(base, components_model.select(ids, keep if use_keep else np.ones(count, np.uint8)), stamp_model.OR)
+        want["place", use_keep] = fall_model.place(ids, offsets, base, True, k)
+        for use_boxes in (False, True):
+            b = boxes if use_boxes else None
+            want["placeAffine", use_keep, use_boxes] = rigid_model.place_affine(ids, maps, b, base, rigid_model.OR, k)
+            want["contacts", use_keep, use_boxes] = contact_model.contacts(ids, maps, b, world, k)
+    for a in (vol, offsets, boxes, keep, base, world):
+        a.setflags(write=False)
+    return vol, offsets, maps, boxes, keep, base, world, want
+
+
+def affine_records(maps):
+    import cpuvoxelraycaster_amd as vrc
+    out = np.zeros(len(maps), vrc.capi.AFFINE_DTYPE)
+    for i, (m, t) in enumerate(maps):
+        out[i] = (m, 0, t)
+    return out
+
+
+def device_bytes(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+
+
+@pytest.mark.parametrize("use_boxes", [False, True])
+@pytest.mark.parametrize("use_keep", [False, True])
+def test_multi_part_calls_in_host_and_device_form(built, use_keep, use_boxes):
+    """select, place, placeAffine, contacts and moments once with their lists in host memory (staged in one block, every
+    present part at an offset of its own) and once in device memory on a created stream, keep and boxes present and absent:
+    the volumes and records of the two forms are equal and are the model's"""
+    import torch
+    import cpuvoxelraycaster_amd as vrc
+    vol, offsets, maps, boxes, keep, base, world, want = piece_case()
+    medium, d_world = volume_of(vol), volume_of(world)
+    labels = medium.labelComponents(6)
+    count = labels.count
+    assert count == 7
+    records = affine_records(maps)
+    keep_all = np.ones(count, np.uint8)
+    k, b = (keep if use_keep else None), (boxes if use_boxes else None)
+
+    host = {}
+    for name, run in (("select", lambda dst: labels.select(keep if use_keep else keep_all, dst, stamp_model.OR)),
+                      ("place", lambda dst: labels.place(offsets, dst, stamp_model.OR, k)),
+                      ("placeAffine", lambda dst: labels.placeAffine(records, b, dst, stamp_model.OR, k))):
+        dst = volume_of(base)
+        run(dst)
+        host[name] = dst.download()
+        dst.close()
+    host["contacts"] = labels.contacts(records, d_world, b, k)
+    host["moments"] = labels.moments()
+
+    t_keep, t_keep_all, t_offsets = device_bytes(keep), device_bytes(keep_all), device_bytes(offsets)
+    t_maps, t_boxes = device_bytes(records), device_bytes(boxes)
+    t_contacts = torch.full((count * 128,), 0x5A, dtype=torch.uint8).cuda()
+    t_moments = torch.full((count * 80,), 0x5A, dtype=torch.uint8).cuda()
+    p_keep = t_keep.data_ptr() if use_keep else None
+    p_boxes = t_boxes.data_ptr() if use_boxes else None
+    dsts = {name: volume_of(base) for name in ("select", "place", "placeAffine")}
+    torch.cuda.synchronize()
+    with Stream() as stream:
+        labels.selectDevice(t_keep.data_ptr() if use_keep else t_keep_all.data_ptr(), dsts["select"], stamp_model.OR, stream)
+        labels.placeDevice(t_offsets.data_ptr(), dsts["place"], stamp_model.OR, p_keep, stream)
+        labels.placeAffineDevice(t_maps.data_ptr(), dsts["placeAffine"], p_boxes, stamp_model.OR, p_keep, stream)
+        labels.contactsDevice(t_maps.data_ptr(), d_world, t_contacts.data_ptr(), p_boxes, p_keep, stream)
+        labels.momentsDevice(0, count, t_moments.data_ptr(), stream)
+    device = {name: dst.download() for name, dst in dsts.items()}
+    device["contacts"] = t_contacts.cpu().numpy().view(vrc.capi.CONTACT_DTYPE)
+    device["moments"] = t_moments.cpu().numpy().view(vrc.capi.MOMENTS_DTYPE)
+
+    for name in ("select", "place"):
+        assert np.array_equal(host[name], want[name, use_keep]), name
+        assert np.array_equal(device[name], host[name]), name
+    assert np.array_equal(host["placeAffine"], want["placeAffine", use_keep, use_boxes])
+    assert np.array_equal(device["placeAffine"], host["placeAffine"])
+    assert [contact_model.record_tuple(r) for r in host["contacts"]] == want["contacts", use_keep, use_boxes]
+    assert device["contacts"].tobytes() == host["contacts"].tobytes()
+    assert [rigid_model.moments_tuple(r) for r in host["moments"]] == want["moments"]
+    assert device["moments"].tobytes() == host["moments"].tobytes()
+    assert not np.array_equal(host["place"], base) and any(w[1] for w in want["contacts", use_keep, use_boxes])
+    assert np.array_equal(d_world.download(), world)
+    for h in list(dsts.values()) + [labels, medium, d_world]:
+        h.close()
+
+
+def test_trace_paths_in_host_form_returns_what_it_did_not_write(built):
+    """the paths are the part that goes up and comes back: lengths and routes are the model's, and every entry beyond a
+    route's length still holds what the caller left there"""
+    import cpuvoxelraycaster_amd as vrc
+    capi = vrc.capi
+    S, SENTINEL = 16, 0xA5A5A5A5
+    vol = np.zeros((S, S, S), np.uint8)
+    vol[1:15, 4, 3] = 1                                           # a corridor with a bend, seeded at one end
+    vol[14, 4:12, 3] = 1
+    vol[2, 9, 9] = 1                                              # solid, but joined to nothing: unreachable
+    seeds = np.zeros_like(vol)
+    seeds[1, 4, 3] = 1
+    T = travel_model.field(vol, seeds, 6)
+    starts = np.array([[14, 11, 3], [2, 9, 9], [5, 4, 3]], np.uint32)
+    model = [travel_model.trace(T, tuple(int(v) for v in s), 6) for s in starts]
+    assert [m[0] for m in model] == [20, travel_model.NONE, 4]
+    capacity = 24                                                 # more than the longest route's 21 voxels
+    medium, d_seeds = volume_of(vol), volume_of(seeds)
+    field = medium.travelField(d_seeds, 6)
+    lengths = np.full(3, SENTINEL, np.uint32)
+    paths = np.full((3, capacity, 3), SENTINEL, np.uint32)
+    capi.check(capi.load().vrc_travel_trace_paths(field._h, 3, capi.ptr(starts), capacity, capi.ptr(paths), capi.ptr(lengths), capi.VRC_MEM_HOST, None))
+    for i, (length, route) in enumerate(model):
+        assert int(lengths[i]) == length, i
+        assert np.array_equal(paths[i, :len(route)], route), i
+        assert (paths[i, len(route):] == SENTINEL).all(), i
+    assert [len(m[1]) for m in model] == [21, 0, 5]
+    for h in (field, medium, d_seeds):
+        h.close()
+
+
+def test_a_call_with_a_block_of_its_own_keeps_nothing_between_calls(built):
+    """host-form contacts on labels of 7 pieces, then on labels of 20: each call lays out a block for its own count"""
+    vol, offsets, maps, boxes, keep, base, world, want = piece_case()
+    d_world = volume_of(world)
+    medium = volume_of(vol)
+    labels = medium.labelComponents(6)
+    got = labels.contacts(affine_records(maps), d_world, boxes, keep)
+    assert [contact_model.record_tuple(r) for r in got] == want["contacts", True, True]
+    labels.close()
+    medium.close()
+
+    more = scattered_blocks(extra=13)
+    ids, records = components_model.label(more, 6)
+    assert len(records) == 20
+    rng = np.random.default_rng(4701)
+    offsets = rng.integers(-3, 4, (20, 3)).astype(np.int32)
+    maps, boxes = rigid_model.translation_maps(offsets), rigid_model.moved_boxes(records, offsets, 16)
+    keep = (np.arange(20) % 4 != 2).astype(np.uint8)
+    medium = volume_of(more)
+    labels = medium.labelComponents(6)
+    assert labels.count == 20
+    got = labels.contacts(affine_records(maps), d_world, boxes, keep)
+    assert [contact_model.record_tuple(r) for r in got] == contact_model.contacts(ids, maps, boxes, world, keep)
+    for h in (labels, medium, d_world):
+        h.close()
+
+
+def test_contacts_in_device_memory_behind_an_edit_of_the_world_on_another_stream(built):
+    """a device-memory fill of the world on one stream, then contactsDevice against it on another with no synchronisation:
+    the records are those of the edited world -- once at 16^3, and once behind edits that take long enough to lose a race
+    against, a 512^3 world filled and cleared sixteen times over"""
+    import torch
+    import cpuvoxelraycaster_amd as vrc
+    vol, offsets, maps, boxes, keep, base, world, _ = piece_case()
+    ids, _ = components_model.label(vol, 6)
+    medium = volume_of(vol)
+    labels = medium.labelComponents(6)
+    count = labels.count
+    box = np.array([[0, 5, 0, 16, 9, 16]], np.uint32)
+    edited = world.copy()
+    edited[0:16, 5:9, 0:16] = 1
+    want = contact_model.contacts(ids, maps, boxes, edited, keep)
+    assert want != contact_model.contacts(ids, maps, boxes, world, keep)
+    # the same pieces, unmoved, inside a 512^3 world that ends full: every posed voxel overlaps
+    big, B = vrc.VoxelVolume(9), 512
+    identity = rigid_model.translation_maps(np.zeros((count, 3), np.int32))
+    voxels = np.bincount(ids[ids != components_model.NO_COMPONENT].astype(np.int64), minlength=count)
+
+    d_world = volume_of(world)
+    t_maps, t_identity = device_bytes(affine_records(maps)), device_bytes(affine_records(identity))
+    t_boxes, t_keep, t_box = device_bytes(boxes), device_bytes(keep), device_bytes(box)
+    t_whole = device_bytes(np.array([[0, 0, 0, B, B, B]], np.uint32))
+    t_out = torch.full((count * 128,), 0x5A, dtype=torch.uint8).cuda()
+    t_big_out = torch.full((count * 128,), 0x5A, dtype=torch.uint8).cuda()
+    torch.cuda.synchronize()
+    with Stream() as first, Stream() as second:
+        d_world.fillBoxesDevice(1, t_box.data_ptr(), True, first)
+        labels.contactsDevice(t_maps.data_ptr(), d_world, t_out.data_ptr(), t_boxes.data_ptr(), t_keep.data_ptr(), second)
+        for round_ in range(16):
+            big.fillBoxesDevice(1, t_whole.data_ptr(), round_ % 2 == 1, first)
+        labels.contactsDevice(t_identity.data_ptr(), big, t_big_out.data_ptr(), None, None, second)
+    got = t_out.cpu().numpy().view(vrc.capi.CONTACT_DTYPE)
+    assert [contact_model.record_tuple(r) for r in got] == want
+    got = t_big_out.cpu().numpy().view(vrc.capi.CONTACT_DTYPE)
+    assert got["posed"].tolist() == voxels.tolist() and got["overlap"].tolist() == voxels.tolist()
+    assert np.array_equal(d_world.download(), edited)
+    for h in (labels, medium, d_world, big):
         h.close()
