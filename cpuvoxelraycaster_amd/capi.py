@@ -204,6 +204,8 @@ SYMBOLS = {
     "vrc_labels_select": (_int, [_vp, _vp, _vp, _int, _int, _vp]),
     "vrc_fall_drops": (_int, [_vp, _vp, _int, _u32, _vp, _int, C.POINTER(FallStats)]),
     "vrc_fall_place": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp]),
+    "vrc_fracture_label": (_int, [_vp, _int, _int, _u64, _vp, _u32, _int, C.POINTER(_vp), C.POINTER(_u64)]),
+    "vrc_fracture_piece_sites": (_int, [_vp, _u64, _u64, _vp, _int, _vp]),
     "vrc_rigid_moments": (_int, [_vp, _u64, _u64, _vp, _int, _vp]),
     "vrc_rigid_place_affine": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     "vrc_rigid_contacts": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),

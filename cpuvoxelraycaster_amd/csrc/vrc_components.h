@@ -14,8 +14,11 @@ size_t components_scratch_bytes(uint32_t depth);
 uint32_t* components_total_slot(uint32_t* scratch, uint32_t depth);
 // First half: labels[key] = the key of the component's representative for the voxels of M, VRC_NO_COMPONENT elsewhere
 // (M = medium for through == 0, its complement inside the volume otherwise); scratch = the exclusive prefix of the
-// representatives per workgroup and their total.  labels: 8^depth uint32.  Enqueues on `st`.
-void components_roots_run(const uint32_t* medium, uint32_t depth, int connectivity, int through, uint32_t* labels, uint32_t* scratch, hipStream_t st);
+// representatives per workgroup and their total.  labels: 8^depth uint32.  cells, optional (nullptr: none): a dense field
+// [(x*S + y)*S + z] of one uint32 per voxel; two neighbours are then joined only if they carry the same value, so the
+// components are those of M cut along the cells' borders (vrc_fracture.hip).  Enqueues on `st`.
+void components_roots_run(const uint32_t* medium, uint32_t depth, int connectivity, int through, const uint32_t* cells, uint32_t* labels, uint32_t* scratch,
+                          hipStream_t st);
 // Second half, once the host has read the total and made room for the records: labels[key] = the component's id, and
 // records[id] complete.  Enqueues on `st`.
 void components_ids_run(uint32_t depth, uint32_t* labels, const uint32_t* scratch, vrc_component* records, hipStream_t st);

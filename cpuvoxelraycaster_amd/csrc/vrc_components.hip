@@ -9,7 +9,8 @@
 // Union-find on the label array, every phase a kernel on one stream; no workgroup ever waits for another:
 //   1. init     L[key] = key for the voxels of M, VRC_NO_COMPONENT elsewhere;
 //   2. merge    a voxel of M unites itself with its neighbours of M in the earlier half of the neighbourhood (offsets that
-//               are lexicographically negative: 3 of 6, 13 of 26; beyond the volume's faces there is no neighbour).  find
+//               are lexicographically negative: 3 of 6, 13 of 26; beyond the volume's faces there is no neighbour) -- with
+//               a dense cell field (vrc_fracture_label), only with those that carry its own cell value.  find
 //               follows parents and points every node it passes at its grandparent, union hooks the larger root under the
 //               smaller with atomicMin and carries on with what the atomic returned where the node was a root no longer.
 //               A parent is always a smaller key and a label is only ever lowered, so every loop ends on its own, and a
@@ -88,8 +89,9 @@ __global__ __launch_bounds__(GROUP) void k_components_init(Field f, const uint32
     }
 }
 
-template <int CONN>
-__global__ __launch_bounds__(GROUP) void k_components_merge(Field f, const uint32_t* __restrict__ words, uint32_t* L)
+// CELLS: the voxels also carry a cell value, cells[(x*S + y)*S + z] (vrc_fracture.hip), and only neighbours of one cell unite
+template <int CONN, bool CELLS>
+__global__ __launch_bounds__(GROUP) void k_components_merge(Field f, const uint32_t* __restrict__ words, uint32_t* L, const uint32_t* __restrict__ cells)
 {
     for (uint32_t r = 0; r < ROUNDS; ++r) {
         const uint32_t key = blockIdx.x * GROUP_KEYS + r * GROUP + threadIdx.x;
@@ -98,6 +100,9 @@ __global__ __launch_bounds__(GROUP) void k_components_merge(Field f, const uint3
         if (!((w >> (key & 31u)) & 1u)) continue;
         uint32_t c[3];
         voxel_of(f, key, c);
+        const uint32_t dsh = f.lg + 1u;                                        // log2 S
+        uint32_t mine = 0u;
+        if (CELLS) mine = cells[(((size_t)c[0] << dsh | c[1]) << dsh) | c[2]];
 #pragma unroll
         for (int dx = -1; dx <= 0; ++dx)
 #pragma unroll
@@ -111,7 +116,9 @@ __global__ __launch_bounds__(GROUP) void k_components_merge(Field f, const uint3
                     if (x >= f.S || y >= f.S || z >= f.S) continue;        // below 0 wraps to above S
                     const uint32_t other = key_of(f, x, y, z);
                     const uint32_t ow = (other >> 5) == (key >> 5) ? w : words[other >> 5] ^ f.flip;
-                    if ((ow >> (other & 31u)) & 1u) unite(L, key, other);
+                    if (!((ow >> (other & 31u)) & 1u)) continue;
+                    if (CELLS && cells[(((size_t)x << dsh | y) << dsh) | z] != mine) continue;
+                    unite(L, key, other);
                 }
     }
 }
@@ -271,13 +278,19 @@ size_t components_scratch_bytes(uint32_t depth) { return ((size_t)groups_of(dept
 
 uint32_t* components_total_slot(uint32_t* scratch, uint32_t depth) { return scratch + groups_of(depth); }
 
-void components_roots_run(const uint32_t* medium, uint32_t depth, int connectivity, int through, uint32_t* labels, uint32_t* scratch, hipStream_t st)
+void components_roots_run(const uint32_t* medium, uint32_t depth, int connectivity, int through, const uint32_t* cells, uint32_t* labels, uint32_t* scratch,
+                          hipStream_t st)
 {
     const Field f = field_of(depth, through);
     const dim3 grid(groups_of(depth)), block(GROUP);
     hipLaunchKernelGGL(k_components_init, grid, block, 0, st, f, medium, labels);
-    if (connectivity == 6) hipLaunchKernelGGL(k_components_merge<6>, grid, block, 0, st, f, medium, labels);
-    else hipLaunchKernelGGL(k_components_merge<26>, grid, block, 0, st, f, medium, labels);
+    if (connectivity == 6) {
+        if (cells) hipLaunchKernelGGL((k_components_merge<6, true>), grid, block, 0, st, f, medium, labels, cells);
+        else hipLaunchKernelGGL((k_components_merge<6, false>), grid, block, 0, st, f, medium, labels, cells);
+    } else {
+        if (cells) hipLaunchKernelGGL((k_components_merge<26, true>), grid, block, 0, st, f, medium, labels, cells);
+        else hipLaunchKernelGGL((k_components_merge<26, false>), grid, block, 0, st, f, medium, labels, cells);
+    }
     hipLaunchKernelGGL(k_components_flatten, grid, block, 0, st, f, labels, scratch);
     hipLaunchKernelGGL(k_components_scan, dim3(1), dim3(SCAN_GROUP), 0, st, scratch, groups_of(depth));
 }

@@ -1,6 +1,7 @@
 // vrc_snapshots.hip -- the snapshots taken from an editable volume (include/vrc.h): the labels of its connected components
 // (vrc_volume_label_components, vrc_labels_*; kernels in vrc_components.hip; the pieces' moments, posed placement and
-// contacts, vrc_rigid_*, kernels in vrc_rigid.hip) and its exact squared Euclidean distance field
+// contacts, vrc_rigid_*, kernels in vrc_rigid.hip; the labels cut along the Voronoi cells of a list of sites,
+// vrc_fracture_*, kernels in vrc_fracture.hip) and its exact squared Euclidean distance field
 // with the selection by distance that grow / shrink / hollow are made of (vrc_volume_distance_field, vrc_distance_*;
 // kernels in vrc_distance.hip), and the travel-distance field from a set of seeds, kept in the same snapshot object, with the
 // routes read off it (vrc_travel_field, vrc_travel_trace_paths; kernels in vrc_travel.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
@@ -15,6 +16,7 @@
 #include "vrc_components.h"
 #include "vrc_distance.h"
 #include "vrc_fall.h"
+#include "vrc_fracture.h"
 #include "vrc_rigid.h"
 #include "vrc_travel.h"
 #include "vrc_volume_state.h"
@@ -25,6 +27,8 @@ struct vrc_labels {
     uint64_t count = 0;
     uint32_t* d_ids = nullptr;            // 8^depth ids, indexed by key
     vrc_component* d_records = nullptr;   // count records, nullptr when count == 0
+    bool fractured = false;               // made by vrc_fracture_label: the pieces carry a cell
+    uint32_t* d_piece_cells = nullptr;    // fractured: count cells, nullptr when count == 0
 };
 
 struct vrc_distance {
@@ -85,7 +89,7 @@ extern "C" int vrc_volume_label_components(vrc_volume* medium, int connectivity,
     l->device = medium->device; l->depth = medium->depth;
     uint32_t C = 0;
     const hipError_t e = snapshot_run(medium, &l->d_ids, vrc::components_scratch_bytes(l->depth), [&](uint32_t* d_scratch) {
-        vrc::components_roots_run(medium->d_bricks, l->depth, connectivity, through, l->d_ids, d_scratch, nullptr);
+        vrc::components_roots_run(medium->d_bricks, l->depth, connectivity, through, nullptr, l->d_ids, d_scratch, nullptr);
         hipError_t run = hipGetLastError();
         if (run == hipSuccess) run = hipMemcpy(&C, vrc::components_total_slot(d_scratch, l->depth), 4, hipMemcpyDeviceToHost);
         if (run == hipSuccess && C) run = hipMalloc((void**)&l->d_records, (size_t)C * sizeof(vrc_component));
@@ -112,13 +116,17 @@ extern "C" int vrc_labels_destroy(vrc_labels* l)
     (void)hipDeviceSynchronize();       // device-memory calls may still be reading it on a caller's stream
     if (l->d_ids) (void)hipFree(l->d_ids);
     if (l->d_records) (void)hipFree(l->d_records);
+    if (l->d_piece_cells) (void)hipFree(l->d_piece_cells);
     delete l;
     return VRC_OK;
 }
 
 extern "C" uint64_t vrc_labels_count(const vrc_labels* l) { return l ? l->count : 0; }
 extern "C" uint32_t vrc_labels_depth(const vrc_labels* l) { return l ? l->depth : 0; }
-extern "C" uint64_t vrc_labels_bytes(const vrc_labels* l) { return l ? ((uint64_t)4u << (3u * l->depth)) + l->count * sizeof(vrc_component) : 0; }
+extern "C" uint64_t vrc_labels_bytes(const vrc_labels* l)
+{
+    return l ? ((uint64_t)4u << (3u * l->depth)) + l->count * (sizeof(vrc_component) + (l->fractured ? 4u : 0u)) : 0;
+}
 
 extern "C" int vrc_labels_components(const vrc_labels* l, uint64_t first, uint64_t capacity, vrc_component* out, int mem, void* stream)
 {
@@ -285,6 +293,78 @@ extern "C" int vrc_rigid_contacts(const vrc_labels* l, const uint8_t* keep, cons
     return staged_call(what, call, parts, [&](void* const* d) {
         return vrc::contacts_run(l->d_ids, l->d_records, l->count, l->depth, (const uint8_t*)d[3], (const vrc_affine*)d[1], (const uint32_t*)d[2], world->d_bricks,
                                  world->depth, (vrc_piece_contact*)d[0], call.st);
+    });
+}
+
+// ---- Voronoi fracture (the rule: include/vrc.h; the cells: vrc_fracture.hip; the labelling: vrc_components.hip) ------
+
+// One scratch block for the call: the labelling's counts, the dense cell field, the site table and the stacks, and behind
+// them the staged sites of a host-memory call.  Not a staged_call: the host reads C back between the two halves.
+extern "C" int vrc_fracture_label(vrc_volume* medium, int connectivity, int through, uint64_t n_sites, const int32_t* sites_xyz, uint32_t max_d2, int mem,
+                                  vrc_labels** out, uint64_t* n_components)
+{
+    const char* what = "vrc_fracture_label";
+    if (!medium || !out) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_connectivity(what, connectivity)) return rc;
+    if (const int rc = check_through(what, through)) return rc;
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (n_sites == 0) return vrc::fail(VRC_ERR_INVALID, "%s: no sites", what);
+    if (!sites_xyz) return vrc::fail(VRC_ERR_INVALID, "%s: null sites", what);
+    if (n_sites >= 0xffffffffull) return vrc::fail(VRC_ERR_INVALID, "%s: %llu sites are too many (an index is below 2^32 - 1)", what, (unsigned long long)n_sites);
+    if (medium->depth < 2 || medium->depth > 10) return vrc::fail(VRC_ERR_INVALID, "%s: depth %u not in [2,10]", what, medium->depth);
+    vrc_labels* l = new (std::nothrow) vrc_labels();
+    if (!l) return vrc::fail(VRC_ERR_OOM, "out of host memory");
+    l->device = medium->device; l->depth = medium->depth; l->fractured = true;
+    const size_t label_bytes = (vrc::components_scratch_bytes(l->depth) + 15u) & ~(size_t)15u, cell_bytes = (size_t)4u << (3u * l->depth);
+    const size_t work_bytes = vrc::fracture_scratch_bytes(l->depth, medium->cu_count, n_sites), site_bytes = (size_t)n_sites * 12u;
+    uint32_t C = 0;
+    const hipError_t e = snapshot_run(medium, &l->d_ids, label_bytes + cell_bytes + work_bytes + (mem == VRC_MEM_HOST ? site_bytes : 0u), [&](uint32_t* d_scratch) {
+        uint32_t* d_cells = d_scratch + label_bytes / 4u;
+        uint32_t* d_work = d_cells + cell_bytes / 4u;
+        const int32_t* d_sites = sites_xyz;
+        hipError_t run = hipSuccess;
+        if (mem == VRC_MEM_HOST) {
+            d_sites = (const int32_t*)(d_work + work_bytes / 4u);
+            run = hipMemcpyAsync((void*)d_sites, sites_xyz, site_bytes, hipMemcpyHostToDevice, nullptr);
+        }
+        if (run == hipSuccess) {
+            vrc::fracture_cells_run(d_sites, n_sites, l->depth, max_d2, medium->cu_count, d_cells, d_work, nullptr);
+            vrc::components_roots_run(medium->d_bricks, l->depth, connectivity, through, d_cells, l->d_ids, d_scratch, nullptr);
+            run = hipGetLastError();
+        }
+        if (run == hipSuccess) run = hipMemcpy(&C, vrc::components_total_slot(d_scratch, l->depth), 4, hipMemcpyDeviceToHost);
+        if (run == hipSuccess && C) run = hipMalloc((void**)&l->d_records, (size_t)C * sizeof(vrc_component));
+        if (run == hipSuccess && C) run = hipMalloc((void**)&l->d_piece_cells, (size_t)C * 4u);
+        if (run == hipSuccess && C) {
+            vrc::components_ids_run(l->depth, l->d_ids, d_scratch, l->d_records, nullptr);
+            vrc::fracture_piece_cells_run(l->d_records, C, d_cells, l->depth, l->d_piece_cells, nullptr);
+            run = hipGetLastError();
+        }
+        return run;
+    });
+    if (e != hipSuccess) {
+        (void)vrc_labels_destroy(l);
+        return vrc::fail_hip(e, what);
+    }
+    l->count = C;
+    *out = l;
+    if (n_components) *n_components = C;
+    return VRC_OK;
+}
+
+extern "C" int vrc_fracture_piece_sites(const vrc_labels* l, uint64_t first, uint64_t capacity, uint32_t* sites, int mem, void* stream)
+{
+    const char* what = "vrc_fracture_piece_sites";
+    if (!l) return vrc::fail(VRC_ERR_INVALID, "%s: null labels", what);
+    if (!l->fractured) return vrc::fail(VRC_ERR_INVALID, "%s: not fracture labels (the pieces of vrc_volume_label_components have no cell)", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (!sites && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
+    const uint64_t want = window_of(first, capacity, l->count);
+    if (!want) return VRC_OK;
+    const Call call = snapshot_call(l->device, mem, stream);
+    const StagePart parts[] = {{sites, (size_t)want * 4u, STAGE_OUT}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        return hipMemcpyAsync(d[0], l->d_piece_cells + first, (size_t)want * 4u, hipMemcpyDeviceToDevice, call.st);
     });
 }
 

@@ -253,6 +253,15 @@ public:
         if (n) check(vrc_rigid_moments(l_, first, n, out.data(), VRC_MEM_HOST, nullptr), "vrc_rigid_moments");
         return out;
     }
+    // labels made by HipVoxelVolume::fracture: the site whose cell each piece of [first, first + capacity) lies in,
+    // VRC_NO_COMPONENT for "none" (include/vrc.h: vrc_fracture_piece_sites)
+    std::vector<uint32_t> pieceSites(uint64_t first = 0, uint64_t capacity = ~0ull) const
+    {
+        const uint64_t C = count(), n = first < C ? std::min(capacity, C - first) : 0;
+        std::vector<uint32_t> out((size_t)n);
+        check(vrc_fracture_piece_sites(l_, first, n, n ? out.data() : nullptr, VRC_MEM_HOST, nullptr), "vrc_fracture_piece_sites");
+        return out;
+    }
     // what a physics engine starts from: the integer sums combined in 128-bit integers, then long double (see HipMassProperties)
     std::vector<HipMassProperties> massProperties(uint64_t first = 0, uint64_t capacity = ~0ull) const
     {
@@ -539,6 +548,20 @@ public:
         flush();
         vrc_labels* l = nullptr;
         check(vrc_volume_label_components(v_, connectivity, through_empty ? VRC_FLOOD_EMPTY : VRC_FLOOD_SOLID, &l, nullptr), "vrc_volume_label_components");
+        return HipVoxelLabels(l);
+    }
+    // Voronoi fracture (include/vrc.h: vrc_fracture_label): the pieces of the solid voxels (the empty ones with through_empty)
+    // cut along the Voronoi cells of the sites (x y z int32 each); voxels farther than max_distance from every site (d^2 > r^2;
+    // negative: no limit) keep the cell "none" and stay whole.  Nothing is removed.  Synchronous.
+    HipVoxelLabels fracture(const std::vector<int32_t>& sites_xyz, int connectivity = VRC_CONNECT_FACES, bool through_empty = false, int64_t max_distance = -1)
+    {
+        flush();
+        vrc_labels* l = nullptr;
+        const uint64_t r = (uint64_t)std::min<int64_t>(max_distance, 65535);       // finite distances are below 2^22
+        const uint32_t max_d2 = max_distance < 0 ? VRC_DISTANCE_NONE : (uint32_t)(r * r);
+        check(vrc_fracture_label(v_, connectivity, through_empty ? VRC_FLOOD_EMPTY : VRC_FLOOD_SOLID, sites_xyz.size() / 3, sites_xyz.data(), max_d2,
+                                 VRC_MEM_HOST, &l, nullptr),
+              "vrc_fracture_label");
         return HipVoxelLabels(l);
     }
     // Dig, let the debris fall, commit: what no longer holds on to a solid voxel inside one of the n anchor boxes falls piece

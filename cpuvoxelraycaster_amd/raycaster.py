@@ -427,6 +427,43 @@ class VoxelVolume:
                                                       C.byref(handle), C.byref(count)))
         return VoxelLabels(handle, int(count.value), self.depth, self.device)
 
+    def fracture(self, sites, connectivity=6, through_empty=False, max_distance=None):
+        """Voronoi fracture (include/vrc.h: vrc_fracture_label): the pieces of the solid voxels (or, with through_empty, of the
+        empty ones) cut along the Voronoi cells of the (n, 3) int32 `sites` -- every voxel belongs to its nearest in-volume
+        site, among several nearest to the lowest index; voxels farther than max_distance from every site (d^2 > r^2, the
+        radius rule of fillSpheres; None: no limit) keep the cell "none" and stay whole.  Nothing is removed.  A VoxelLabels
+        snapshot whose pieceSites() names each piece's cell.  Synchronous."""
+        sites = np.ascontiguousarray(sites, np.int32).reshape(-1, 3)
+        max_d2 = capi.VRC_DISTANCE_NONE if max_distance is None else self._radius(max_distance, "fracture") ** 2
+        handle, count = C.c_void_p(), C.c_uint64()
+        check(capi.load().vrc_fracture_label(self._h, int(connectivity), capi.VRC_FLOOD_EMPTY if through_empty else capi.VRC_FLOOD_SOLID, sites.shape[0],
+                                             ptr(sites) if sites.shape[0] else None, max_d2, capi.VRC_MEM_HOST, C.byref(handle), C.byref(count)))
+        return VoxelLabels(handle, int(count.value), self.depth, self.device)
+
+    def fractureDevice(self, n, sites_ptr, connectivity=6, through_empty=False, max_distance=None):
+        """the same over n x 3 int32 sites in device memory; still synchronous"""
+        max_d2 = capi.VRC_DISTANCE_NONE if max_distance is None else self._radius(max_distance, "fractureDevice") ** 2
+        handle, count = C.c_void_p(), C.c_uint64()
+        check(capi.load().vrc_fracture_label(self._h, int(connectivity), capi.VRC_FLOOD_EMPTY if through_empty else capi.VRC_FLOOD_SOLID, n, ptr(sites_ptr),
+                                             max_d2, capi.VRC_MEM_DEVICE, C.byref(handle), C.byref(count)))
+        return VoxelLabels(handle, int(count.value), self.depth, self.device)
+
+    def shatter(self, sites, max_distance, direction, connectivity=6, drop_limit=0):
+        """Break, let the shards fall, ready to commit: the solid within max_distance of the `sites` is cut into Voronoi shards
+        (fracture), the shards -- the pieces whose cell is a site -- are taken out of the volume, fall as rigid bodies along
+        `direction` (a capi.VRC_FACE_* code) onto what is left, onto each other or onto the volume's face, at most drop_limit
+        cells (0 = no limit), and are put back where they come to rest.  Returns (capi.FallStats, the VoxelLabels)."""
+        labels = self.fracture(sites, connectivity, False, max_distance)
+        try:
+            shards = (labels.pieceSites() != capi.VRC_NO_COMPONENT).astype(np.uint8)
+            labels.select(shards, self, capi.VRC_COPY_ANDNOT)
+            offsets, stats = labels.fall(self, direction, drop_limit)
+            labels.place(offsets, self, capi.VRC_COPY_OR, keep=shards)
+        except Exception:
+            labels.close()
+            raise
+        return stats, labels
+
     def removeSmallPieces(self, min_voxels, connectivity=6):
         """Clears every solid piece of fewer than min_voxels voxels (the specks a dig or a leaky mesh leaves); returns
         (pieces before, pieces removed)."""
@@ -759,7 +796,7 @@ class VoxelVolume:
 
 class VoxelLabels:
     """The component id of every voxel of M, resident on the device (include/vrc.h: vrc_labels_*): a snapshot made by
-    VoxelVolume.labelComponents.  Ids run 0 .. count-1 by ascending key of each piece's first voxel."""
+    VoxelVolume.labelComponents or VoxelVolume.fracture.  Ids run 0 .. count-1 by ascending key of each piece's first voxel."""
 
     def __init__(self, handle, count, depth, device):
         self._h, self.count, self.depth, self.device = handle, count, depth, device
@@ -943,6 +980,19 @@ class VoxelLabels:
     def collides(self, maps, world, boxes=None, keep=None):
         """bool per piece: the posed piece shares a voxel with the world's solid (contacts()["overlap"] > 0)"""
         return self.contacts(maps, world, boxes, keep)["overlap"] > 0
+
+    def pieceSites(self, first=0, capacity=None):
+        """uint32 per piece of [first, first + capacity) that exists: the index of the site whose cell the piece lies in,
+        capi.VRC_NO_COMPONENT for "none" -- labels made by VoxelVolume.fracture only (include/vrc.h: vrc_fracture_piece_sites)"""
+        if capacity is None:
+            capacity = max(self.count - first, 0)
+        out = np.zeros(min(capacity, max(self.count - first, 0)), np.uint32)
+        check(capi.load().vrc_fracture_piece_sites(self._h, first, len(out), ptr(out) if len(out) else None, capi.VRC_MEM_HOST, None))
+        return out
+
+    def pieceSitesDevice(self, first, capacity, out_ptr, stream=None):
+        """the same into device memory, asynchronous on `stream`"""
+        check(capi.load().vrc_fracture_piece_sites(self._h, first, capacity, ptr(out_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
 
     def bytes(self):
         return int(capi.load().vrc_labels_bytes(self._h))

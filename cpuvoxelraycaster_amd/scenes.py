@@ -136,3 +136,19 @@ def write_obj(path, verts, quads):
             f.write("v %s %s %s\n" % tuple(v))
         for q in (quads + 1).tolist():
             f.write("f " + " ".join(str(i) for i in q) + "\n")
+
+
+def scatter_sites(centre, radius, n, seed):
+    """n integer fracture sites in the ball of `radius` voxels around `centre` (VoxelVolume.fracture / shatter), as (n, 3)
+    int32: uniform draws from numpy's default_rng(seed) over the ball's bounding cube, kept where dx^2 + dy^2 + dz^2 <= r^2
+    (the radius rule of fillSpheres).  Deterministic in its arguments; sites may coincide and may lie outside a volume."""
+    centre = np.asarray(centre, np.int64).reshape(3)
+    radius, n = int(radius), int(n)
+    if radius < 0 or n < 0:
+        raise ValueError("scatter_sites: negative radius or count")
+    rng = np.random.default_rng(seed)
+    out = np.zeros((0, 3), np.int64)
+    while len(out) < n:
+        d = rng.integers(-radius, radius + 1, size=(2 * (n - len(out)) + 8, 3))
+        out = np.concatenate([out, d[(d * d).sum(axis=1) <= radius * radius]])
+    return (centre + out[:n]).astype(np.int32)

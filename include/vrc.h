@@ -479,7 +479,7 @@ int vrc_volume_flood(vrc_volume *region, vrc_volume *medium, int connectivity, i
 typedef struct vrc_labels vrc_labels;    /* a snapshot: the component id of every voxel of M, resident on the volume's device */
 #define VRC_NO_COMPONENT 0xffffffffu
 typedef struct vrc_component {           /* 48 bytes */
-    uint32_t first[3];                   /* the representative: flooding `medium` from it gives this piece back */
+    uint32_t first[3];                   /* the representative: flooding `medium` from it gives this piece back (not for vrc_fracture_label's) */
     uint32_t lo[3], hi[3];               /* bounding box, lo inclusive, hi exclusive (vrc_volume_fill_boxes' form) */
     uint32_t reserved;                   /* 0 */
     uint64_t voxels;
@@ -701,6 +701,66 @@ typedef struct vrc_piece_contact {       /* 128 bytes */
 int vrc_rigid_contacts(const vrc_labels *l, const uint8_t *keep /* C bytes, NULL = all */,
                        const vrc_affine *maps /* C */, const uint32_t *boxes /* C x 6 lo,hi; NULL = all of world */,
                        vrc_volume *world, vrc_piece_contact *out /* C */, int mem, void *stream);
+
+/* Voronoi fracture into labelled shards, on the device: the step BEFORE "a piece is loose".  A solid body is cut along the
+ * Voronoi partition around a handful of sites (impact points), no material is removed, and the result is an ordinary
+ * vrc_labels snapshot: vrc_labels_*, vrc_fall_*, vrc_rigid_moments, vrc_rigid_place_affine and vrc_rigid_contacts work on
+ * the shards unchanged.  Like vrc_fall_* and vrc_rigid_* the calls carry the name of what they compute.
+ *
+ * The rule, exact in integers.  Sites: n sites s_0 .. s_{n-1}, three int32 voxel coordinates each.  A site outside [0, S)^3
+ * is ignored (the setCell rule) but keeps its place in the numbering; duplicates are legal.
+ * Cell of a voxel.  For every voxel p of the volume, cell(p) is the index i of an in-volume site that minimises
+ * (|p - s_i|^2, i) lexicographically: the nearest site by squared Euclidean distance, among several nearest the lowest index.
+ * cell(p) = VRC_NO_COMPONENT when no site lies in the volume, and when max_d2 != VRC_DISTANCE_NONE and that least squared
+ * distance exceeds max_d2 -- the cut-off is how a caller breaks only what lies within a radius of the impact: the rest of the
+ * world keeps the cell "none" and stays whole.
+ * Pieces.  M is the flood's M: the solid voxels of `medium` (VRC_FLOOD_SOLID) or its empty voxels (VRC_FLOOD_EMPTY); the
+ * volume's faces are walls.  A piece is a maximal subset of M whose voxels are joined by chains of neighbours (6 or 26) that
+ * lie in M and all carry the same cell value.  Representative, numbering and records are those of
+ * vrc_volume_label_components: the voxel of minimum key, ids ascending by representative key, first / lo / hi / voxels,
+ * reserved = 0.  The result is therefore unique: two calls give identical bytes.  With no in-volume site, or with max_d2
+ * below every distance, it is byte for byte that of vrc_volume_label_components.  One sentence of vrc_component does NOT hold
+ * for these labels: flooding `medium` from `first` gives the whole connected body back, not this piece -- a piece ends
+ * where its cell ends, not where the medium does.
+ *
+ * vrc_fracture_label is synchronous, on the NULL stream, ordered behind the medium's last asynchronous edit, and only reads
+ * the medium.  Depths 2..10.  mem says where sites_xyz lives, as in vrc_fall_drops: host memory is staged, device memory is
+ * read in place (and must be complete when the call is made).  The snapshot owns what a vrc_volume_label_components snapshot
+ * owns and additionally 4 bytes per piece, the piece's cell; vrc_labels_bytes counts them.  All other scratch is freed before
+ * return and vrc_volume_edit_scratch_bytes does not change: the dense cell field (4 * 8^depth bytes, as much again as the
+ * ids), the site table (4 bytes per site), the labelling's counts, the staged sites of a host-memory call (12 bytes per
+ * site) and, from 256^3 on, the envelope stacks of the lines in flight, sized as vrc_volume_distance_field's (up to 128^3 they
+ * are in LDS, 32 KiB per workgroup).
+ *
+ * The device (csrc/vrc_fracture.hip): the sites scatter their indices into the dense field with a 32-bit vector atomicMin,
+ * then three separable passes in the shape of the distance transform's carry the INDEX of the nearest site along z, y and
+ * x -- the lower-envelope stack holds site indices, one word an entry, and the partial distance is recomputed from a table
+ * of the sites' coordinates.  Ties are resolved in every pass towards the lowest index (a parabola is popped from the
+ * envelope only when it is strictly above it everywhere), which composes to the rule above; the last pass applies max_d2.
+ * The labelling is vrc_volume_label_components' union-find with one more condition in the merge -- two neighbours unite only
+ * if their cells are equal -- and a last small kernel reads every piece's cell at its representative.  Everything is integer
+ * arithmetic, every atomic a 32- or 64-bit vector atomic, no workgroup waits for another.
+ * Measured on an MI355X at 512^3 on the FastNoise terrain (tools/bench_edit.py --fracture, profiles/edit/bench_fracture.json;
+ * sites in device memory, device time by events, median of 5, A B A B in one run, next to vrc_volume_distance_field followed by
+ * vrc_volume_label_components of the same medium, the yardstick: the same traffic plus the index): 64 sites within 48 voxels of
+ * a surface point with max_d2 = 48^2 (110 pieces, 108 of them shards) 16.30 ms next to 18.18 ms, 0.90 of the yardstick; 4096
+ * sites over the whole volume, no cut-off (1386 pieces) 7.09 ms next to 18.01 ms, 0.39 of it -- the terrain is ONE piece for
+ * the plain labelling, whose union-find is dearest on one large tree, and thousands of small trees are cheaper than the
+ * index-carrying passes are dearer.  The passes have not been timed apart.
+ *
+ * vrc_fracture_piece_sites: sites[k] = the cell of piece first + k, VRC_NO_COMPONENT for "none", for the pieces of
+ * [first, first + capacity) that lie in [0, C); the window semantics, mem and stream of vrc_labels_components.  On labels made
+ * by vrc_volume_label_components it is VRC_ERR_INVALID, as vrc_travel_trace_paths is on a Euclidean field.
+ *
+ * NULL `medium` / `out`, n_sites == 0, NULL sites_xyz, n_sites >= 2^32 - 1 (an index must stay below VRC_NO_COMPONENT), a
+ * connectivity other than 6 / 26, a `through` other than 0 / 1 and a bad `mem` are VRC_ERR_INVALID, refused before any device
+ * call. */
+int vrc_fracture_label(vrc_volume *medium, int connectivity, int through,
+                       uint64_t n_sites, const int32_t *sites_xyz, uint32_t max_d2, int mem,
+                       vrc_labels **out, uint64_t *n_components);
+int vrc_fracture_piece_sites(const vrc_labels *l, uint64_t first, uint64_t capacity,
+                             uint32_t *sites /* cell of piece first+k; VRC_NO_COMPONENT for "none" */,
+                             int mem, void *stream);
 
 /* The exact squared Euclidean distance field, on the device: how far every voxel is from the surface, and with it grow /
  * shrink by r voxels (dilate, erode, open, close), hollowing a solid down to a shell, clearance queries, and a field a

@@ -117,6 +117,13 @@ the NULL stream, one warm-up, `--pairs` repetitions, median and range:
   place      vrc_fall_place of every piece into a copy of the supported part (OR), offsets in device memory
   select     vrc_labels_select of every piece of the same labels into a volume (OR)
   fall_round_over_label = fall / rounds / label
+With --fracture (printed and written to profiles/edit/bench_fracture.json), Voronoi fracture at 512^3 on the FastNoise terrain,
+sites in device memory, device time by events on the NULL stream around the synchronous calls, one warm-up pair, A B A B in one
+process, `--pairs` pairs, median and range; A = vrc_fracture_label, B = vrc_volume_distance_field followed by
+vrc_volume_label_components of the same medium (the yardstick: the same traffic plus the index):
+  impact_64_sites_radius_48   64 sites within 48 voxels of a surface point (scenes.scatter_sites), max_distance 48
+  whole_volume_4096_sites     4096 sites over the whole volume, no cut-off
+  fracture_over_distance_plus_label = A / B; the passes are not timed apart
 With --rigid (printed and written to profiles/edit/bench_rigid.json), the pieces as rigid bodies on the --fall scene (the same
 terrain, bands and cuts: a few hundred loose blocks), device time by events on the NULL stream, one warm-up, `--pairs`
 repetitions, median and range, everything in device memory:
@@ -1110,6 +1117,60 @@ def bench_stamp(vrc, depth, pairs):
     return res
 
 
+def bench_fracture(vrc, depth, pairs):
+    """vrc_fracture_label on the FastNoise terrain next to vrc_volume_distance_field plus vrc_volume_label_components of the
+    same medium (the yardstick: the same traffic plus the index), A B A B in one run; see the module's text."""
+    import torch
+    from cpuvoxelraycaster_amd import scenes
+    S = 1 << depth
+    res = {"size": S, "pairs": pairs}
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    world = vrc.VoxelVolume.fromScene(scene)
+    res["solid_voxels"] = world.solidCount()
+    x = z = S // 2
+    column = world.getVoxels(np.stack([np.full(S, x), np.arange(S), np.full(S, z)], axis=1).astype(np.uint32))
+    top = int(np.flatnonzero(column).max())
+    rng = np.random.default_rng(4096)
+    cases = {"impact_64_sites_radius_48": (scenes.scatter_sites((x, top, z), 48, 64, 64), 48),
+             "whole_volume_4096_sites": (rng.integers(0, S, (4096, 3)).astype(np.int32), None)}
+
+    def event_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b), out
+
+    def yardstick():
+        field = world.distanceField()
+        labels = world.labelComponents(6)
+        field.close()
+        return labels
+
+    for name, (sites, radius) in cases.items():
+        t_sites = torch.from_numpy(np.ascontiguousarray(sites)).cuda()
+        torch.cuda.synchronize()
+        a_ms, b_ms, pieces = [], [], 0
+        for i in range(pairs + 1):                                         # one warm-up pair, then A B A B
+            ms, labels = event_ms(lambda: world.fractureDevice(len(sites), t_sites.data_ptr(), 6, False, radius))
+            pieces, shards = labels.count, int((labels.pieceSites() != vrc.capi.VRC_NO_COMPONENT).sum())
+            labels.close()
+            if i:
+                a_ms.append(ms)
+            ms, labels = event_ms(yardstick)
+            plain = labels.count
+            labels.close()
+            if i:
+                b_ms.append(ms)
+        res[name] = {"sites": len(sites), "max_distance": radius, "pieces": pieces, "shards": shards, "plain_pieces": plain,
+                     "fracture_ms": stat(a_ms, 4), "distance_plus_label_ms": stat(b_ms, 4),
+                     "fracture_over_distance_plus_label": round(stat(a_ms, 4)["median"] / stat(b_ms, 4)["median"], 3)}
+    world.close()
+    scene.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--depths", type=int, nargs="+", default=[8, 9, 10])
@@ -1126,7 +1187,25 @@ def main():
     ap.add_argument("--rigid", action="store_true", help="time vrc_rigid_moments / vrc_rigid_place_affine next to vrc_labels_select / vrc_fall_place (depth 9 unless --depths is given)")
     ap.add_argument("--contacts", action="store_true", help="time vrc_rigid_contacts next to vrc_rigid_place_affine with the same maps and boxes (depth 9 unless --depths is given)")
     ap.add_argument("--travel", action="store_true", help="time vrc_travel_field next to vrc_volume_flood from the same seeds (depth 9 unless --depths is given)")
+    ap.add_argument("--fracture", action="store_true", help="time vrc_fracture_label next to vrc_volume_distance_field + vrc_volume_label_components (depth 9 unless --depths is given)")
     args = ap.parse_args()
+    if args.fracture:
+        if args.depths == [8, 9, 10]:
+            args.depths = [9]
+        import __graft_entry__ as g
+        g.build()
+        import torch
+        import cpuvoxelraycaster_amd as vrc
+        if not torch.cuda.is_available():
+            raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
+        out = {"bench": "edit_fracture", "device": torch.cuda.get_device_name(0), "depths": {}}
+        for d in args.depths:
+            out["depths"][str(d)] = bench_fracture(vrc, d, max(1, args.pairs))
+        print(json.dumps(out))
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_fracture.json")
+        with open(path, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+        return
     if args.travel and args.depths == [8, 9, 10]:
         args.depths = [9]
     if args.fall and args.depths == [8, 9, 10]:
