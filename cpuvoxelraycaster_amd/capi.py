@@ -209,6 +209,9 @@ SYMBOLS = {
     "vrc_rigid_moments": (_int, [_vp, _u64, _u64, _vp, _int, _vp]),
     "vrc_rigid_place_affine": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     "vrc_rigid_contacts": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
+    "vrc_rigid_pair_contacts": (_int, [_vp, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _int, _vp]),
+    "vrc_rigid_box_pair_count": (_int, [_vp, _vp, _vp, _u32, C.POINTER(_u64), _int, _vp]),
+    "vrc_rigid_box_pairs": (_int, [_vp, _vp, _vp, _u32, _u64, _u64, _vp, _int, _vp]),
     "vrc_volume_distance_field": (_int, [_vp, _int, _int, C.POINTER(_vp), C.POINTER(DistanceStats)]),
     "vrc_distance_destroy": (_int, [_vp]),
     "vrc_distance_depth": (_u32, [_vp]),

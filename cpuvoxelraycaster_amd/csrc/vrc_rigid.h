@@ -1,6 +1,7 @@
 // vrc_rigid.h -- what a physics engine needs of the pieces of a labelling, and what it hands back (vrc_rigid.hip), as
 // vrc_snapshots.hip calls them: the raw moments of every piece, the gather that writes every piece through its own
-// inverse affine map, and the same gather ending in the contact record of every posed piece against a world.  Like vrc_fall.h it knows arrays only; volumes, their ordering, the staging of host memory and the
+// inverse affine map, the same gather ending in the contact record of every posed piece against a world or, pair by pair,
+// against another posed piece, and the broad phase that lists the pairs worth asking about.  Like vrc_fall.h it knows arrays only; volumes, their ordering, the staging of host memory and the
 // argument checks stay with the entry points.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -35,5 +36,28 @@ void place_affine_run(const uint32_t* labels, const vrc_component* records, uint
 // Enqueues on `st`.  pieces >= 1.
 hipError_t contacts_run(const uint32_t* labels, const vrc_component* records, uint64_t pieces, uint32_t depth, const uint8_t* keep,
                         const vrc_affine* maps, const uint32_t* boxes, const uint32_t* world, uint32_t world_depth, vrc_piece_contact* out, hipStream_t st);
+
+// out[k] = the contact record (vrc.h: vrc_rigid_pair_contacts) of posed piece pairs[2k] against posed piece pairs[2k + 1],
+// k < n_pairs < 2^32: A_a as contacts_run gathers it, against A_b gathered the same way in place of a world and with no
+// walls -- a neighbour beyond the posed volume (8^posed_depth voxels) or beyond box b reads 0.  Zeroes out[0 .. n_pairs) and
+// adds into it in ONE kernel of contacts_run's shape with the pairs for the pieces; a pair with an index >= pieces, or whose
+// a is skipped, keeps its zero record.  keep, maps, boxes, pairs and out are DEVICE memory; no scratch.  Enqueues on `st`.
+// pieces >= 1, n_pairs >= 1.
+hipError_t pair_contacts_run(const uint32_t* labels, const vrc_component* records, uint64_t pieces, uint32_t depth, const uint8_t* keep,
+                             const vrc_affine* maps, const uint32_t* boxes, uint32_t posed_depth, uint64_t n_pairs, const uint32_t* pairs,
+                             vrc_piece_contact* out, hipStream_t st);
+
+// The broad phase (vrc.h: vrc_rigid_box_pair_count / vrc_rigid_box_pairs): the ordered pairs (a, b), a != b, of kept pieces
+// whose boxes (pieces x 6, clipped to the posed volume; required) meet when one is grown by a voxel, ascending.  A thread per
+// a walks all b -- pieces^2 box tests, hence the limit on the pieces.  `slots` is the scratch of both calls,
+// box_pair_scratch_bytes(pieces) = (pieces + 1) x 8 bytes.  box_pair_count_run fills it: the count of every a, scanned into
+// offsets, and the total in slots[pieces].  box_pairs_run, behind it on the same stream, writes the entries
+// [first, first + want) of the list to pairs[0 .. 2 want); first + want <= the total.  keep, boxes and pairs are DEVICE
+// memory.  Both enqueue on `st`.  1 <= pieces <= BOX_PAIR_PIECES.
+constexpr uint64_t BOX_PAIR_PIECES = 1ull << 20;
+size_t box_pair_scratch_bytes(uint64_t pieces);
+void box_pair_count_run(const uint8_t* keep, const uint32_t* boxes, uint64_t pieces, uint32_t posed_depth, unsigned long long* slots, hipStream_t st);
+void box_pairs_run(const uint8_t* keep, const uint32_t* boxes, uint64_t pieces, uint32_t posed_depth, unsigned long long* slots, uint64_t first, uint64_t want,
+                   uint32_t* pairs, hipStream_t st);
 
 }  // namespace vrc

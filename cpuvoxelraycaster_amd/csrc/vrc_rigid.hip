@@ -48,9 +48,22 @@
 // included): translation maps against the supported part 0.111 ms next to 0.081 ms of the placement with the same maps and
 // boxes in the same run (1.37 times), the 30-degree turn 0.118 ms next to 0.080 ms (1.48 times); against the whole medium,
 // where most gathered words meet solid, 0.110 and 0.116 ms.  The passes have not been timed apart.
+//
+// Pair contacts (vrc_rigid_pair_contacts).  k_contacts with a second posed piece for a world: blockIdx.y strides over the listed
+// pairs, the workgroup poses both pieces, and where k_contacts loads the world word and its six neighbours, k_pair_contacts
+// gathers them from piece b (piece_word) under a mask of the bits the sums will read -- up to 32 ids for the centre word, 16
+// for an x or y face, 4 for a z face -- with zeros for walls.  contact_sums, add_set and contact_flush are one copy for both.
+// The broad phase (vrc_rigid_box_pair_count / vrc_rigid_box_pairs) is k_box_pairs: a thread per a over all b, count, scan
+// (vrc_group.h), emit.
+// Measured on the same scene with the 30-degree turn (tools/bench_edit.py --pair-contacts, profiles/edit/bench_pair_contacts.json):
+// 3688 candidate pairs of the 404 pieces counted and listed in 0.33 ms (two synchronous calls, their scratch allocation
+// included), all their records in 0.81 ms (652 pairs overlap, 798 touch), next to 0.098 ms PER PAIR of clearing a scratch
+// volume, placing b and calling vrc_rigid_contacts for a (64 sampled pairs; 360 ms scaled to all, 445 times).  The passes have
+// not been timed apart.
 #include "vrc_rigid.h"
 
 #include "vrc_box_words.h"
+#include "vrc_group.h"
 
 namespace {
 
@@ -238,16 +251,19 @@ __device__ __forceinline__ bool pose_piece(const vrc_component* __restrict__ rec
     return true;
 }
 
-// the gathered bits of the piece in destination word r (an item of s.b): the map evaluated once in 64 bits, then gather_piece
-__device__ __forceinline__ uint32_t posed_word(const uint32_t* __restrict__ L, uint32_t lg, uint32_t piece, const Posed& s, const RowWord& r)
+// the gathered bits of the piece in destination word r under `want`, a mask of the word's bits the caller needs (the box's
+// own mask is ANDed to it): the map evaluated once in 64 bits, then gather_piece.  r is an item of s.b or any other word of
+// the destination made by piece_word below; a word outside the box has the mask 0 and costs no load.
+__device__ __forceinline__ uint32_t posed_word(const uint32_t* __restrict__ L, uint32_t lg, uint32_t piece, const Posed& s, const RowWord& r, uint32_t want)
 {
-    const uint32_t mask = box_mask(s.b, r);
+    const uint32_t mask = box_mask(s.b, r) & want;
+    if (!mask) return 0u;
     // z of the word's first voxel, relative to the row (negative where the word starts in the row before: n = 2;
     // those voxels are outside the mask)
     const int64_t z0 = 2 * ((int64_t)(4u * r.w) - (int64_t)r.base);
     const int64_t c[3] = {4 * (int64_t)r.cx + 1, 4 * (int64_t)r.cy + 1, 2 * z0 + 1};   // 2p + 1: the centre in half voxels
     int32_t q[3], frac[3];
-    bool miss = mask == 0u, inside = true;
+    bool miss = false, inside = true;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const int64_t v = (int64_t)s.map.m[3 * a] * c[0] + (int64_t)s.map.m[3 * a + 1] * c[1] + (int64_t)s.map.m[3 * a + 2] * c[2] + s.map.t[a];
@@ -275,7 +291,7 @@ __global__ __launch_bounds__(GROUP) void k_place_affine(const uint32_t* __restri
             uint32_t bits = 0u;
             RowWord r;
             r.w = 0u;
-            if (it < s.b.items && row_word(s.b, n, it, r)) bits = posed_word(L, lg, piece, s, r);
+            if (it < s.b.items && row_word(s.b, n, it, r)) bits = posed_word(L, lg, piece, s, r, ~0u);
             if (n >= 4u) {                                              // a lane, a word
                 if (bits) {
                     if (op == VRC_COPY_OR) atomicOr(&dst[r.w], bits);
@@ -329,8 +345,23 @@ __device__ __forceinline__ void add_set(uint32_t M, const uint32_t c0[3], const 
     for (int a = 0; a < 3; ++a) acc[4 + a] += (uint32_t)(__popc(M & lower[a]) - __popc(M & upper[a]));        // two's complement
 }
 
-// The contact step of one word with gathered bits != 0: the world word, the six "neighbour is solid or beyond the volume"
-// masks as whole-word operations, and the 15 sums.  acc: posed, then overlap (count, s1 x 3, n x 3), then touch.
+// The contact step of one word with gathered bits != 0, the seven words given as values: w = the world's word under the bits
+// and the words across its six faces, each already in the form "1 = solid, or what the caller lets a voxel beyond the
+// volume read".  The six neighbour masks are whole-word operations; then the 15 sums.  c0 = c of the word's voxel 0.
+// acc: posed, then overlap (count, s1 x 3, n x 3), then touch.  Of w only the bits under `bits` and their neighbours inside
+// the word are read, of xm / xp the odd / even x plane, of ym / yp the upper / lower y plane, of zm / zp the last / first layer.
+__device__ __forceinline__ void contact_sums(uint32_t bits, uint32_t w, uint32_t xm, uint32_t xp, uint32_t ym, uint32_t yp, uint32_t zm, uint32_t zp,
+                                             const uint32_t c0[3], uint32_t acc[15])
+{
+    // W*(p - e_a) and W*(p + e_a) for the 32 voxels p of the word
+    const uint32_t lower[3] = {((w & 0x55555555u) << 1) | ((xm & 0xaaaaaaaau) >> 1), ((w & 0x33333333u) << 2) | ((ym & 0xccccccccu) >> 2), (w << 4) | (zm >> 28)};
+    const uint32_t upper[3] = {((w & 0xaaaaaaaau) >> 1) | ((xp & 0x55555555u) << 1), ((w & 0xccccccccu) >> 2) | ((yp & 0x33333333u) << 2), (w >> 4) | (zp << 28)};
+    acc[0] += __popc(bits);
+    add_set(bits & w, c0, lower, upper, acc + 1);
+    add_set(bits & ~w & (lower[0] | lower[1] | lower[2] | upper[0] | upper[1] | upper[2]), c0, lower, upper, acc + 8);
+}
+
+// vrc_rigid_contacts' step: the world word and at most six neighbour words are loads, a neighbour beyond the volume is a wall
 __device__ __forceinline__ void contact_word(const uint32_t* __restrict__ W, uint32_t n, const RowWord& r, uint32_t bits, uint32_t acc[15])
 {
     const uint32_t rows = n >= 4u ? n >> 2 : 1u;                        // words per row
@@ -342,13 +373,32 @@ __device__ __forceinline__ void contact_word(const uint32_t* __restrict__ W, uin
     const uint32_t xm = cx ? world_word(W, n, cx - 1u, cy, k) : ~0u, xp = cx + 1u < n ? world_word(W, n, cx + 1u, cy, k) : ~0u;
     const uint32_t ym = cy ? world_word(W, n, cx, cy - 1u, k) : ~0u, yp = cy + 1u < n ? world_word(W, n, cx, cy + 1u, k) : ~0u;
     const uint32_t zm = k ? world_word(W, n, cx, cy, k - 1u) : ~0u, zp = k + 1u < rows ? world_word(W, n, cx, cy, k + 1u) : ~0u;
-    // W*(p - e_a) and W*(p + e_a) for the 32 voxels p of the word
-    const uint32_t lower[3] = {((w & 0x55555555u) << 1) | ((xm & 0xaaaaaaaau) >> 1), ((w & 0x33333333u) << 2) | ((ym & 0xccccccccu) >> 2), (w << 4) | (zm >> 28)};
-    const uint32_t upper[3] = {((w & 0xaaaaaaaau) >> 1) | ((xp & 0x55555555u) << 1), ((w & 0xccccccccu) >> 2) | ((yp & 0x33333333u) << 2), (w >> 4) | (zp << 28)};
     const uint32_t c0[3] = {4u * cx + 1u, 4u * cy + 1u, 16u * k + 1u};
-    acc[0] += __popc(bits);
-    add_set(bits & w, c0, lower, upper, acc + 1);
-    add_set(bits & ~w & (lower[0] | lower[1] | lower[2] | upper[0] | upper[1] | upper[2]), c0, lower, upper, acc + 8);
+    contact_sums(bits, w, xm, xp, ym, yp, zm, zp, c0, acc);
+}
+
+// The end of a workgroup's walk over one record's words: the lanes' 32-bit sums become 64-bit wave sums, the four waves meet
+// in LDS and lanes 0..14 add the non-zero ones of the 15 sums to `record` with 64-bit vector atomic adds.  Called by the whole
+// workgroup; one that gathered nothing (acc[0] is `posed`) issues nothing.  The first barrier also keeps the LDS of the record
+// before until its readers are done.
+__device__ __forceinline__ void contact_flush(const uint32_t acc[CONTACT_SUMS], unsigned long long (*part)[CONTACT_SUMS], unsigned long long* record)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (!__syncthreads_or(acc[0] != 0u)) return;
+    const bool some = __ballot(acc[0] != 0u) != 0ull;                   // wave-uniform
+    for (uint32_t k = 0; k < CONTACT_SUMS; ++k) {
+        // the normals (k = 5..7, 12..14) are signed
+        const bool is_signed = (k >= 5u && k <= 7u) || k >= 12u;
+        const unsigned long long mine = is_signed ? (unsigned long long)(long long)(int32_t)acc[k] : (unsigned long long)acc[k];
+        const unsigned long long total = some ? wave_sum(mine) : 0ull;
+        if (lane == 0u) part[wave][k] = total;
+    }
+    __syncthreads();
+    if (threadIdx.x < CONTACT_SUMS) {                                   // the non-zero sums of the workgroup: at most 15 atomics
+        unsigned long long v = 0ull;
+        for (uint32_t wv = 0; wv < WAVES; ++wv) v += part[wv][threadIdx.x];
+        if (v) atomicAdd(record + threadIdx.x, v);
+    }
 }
 
 // k_place_affine's grid and gather, ending in a reduction: the contact record of every piece against the world W (Sd^3).
@@ -362,7 +412,6 @@ __global__ __launch_bounds__(GROUP) void k_contacts(const uint32_t* __restrict__
 {
     __shared__ unsigned long long part[WAVES][CONTACT_SUMS];
     const uint32_t n = Sd >> 1, Ss = 2u << lg;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint32_t piece = blockIdx.y; piece < C; piece += gridDim.y) {  // uniform for the workgroup, and so is all that skips a piece
         Posed s;
         if (!pose_piece(records, piece, keep, maps, boxes, Sd, Ss, s)) continue;
@@ -372,28 +421,157 @@ __global__ __launch_bounds__(GROUP) void k_contacts(const uint32_t* __restrict__
             const uint64_t it = base + threadIdx.x;
             RowWord r;
             if (it < s.b.items && row_word(s.b, n, it, r)) {
-                const uint32_t bits = posed_word(L, lg, piece, s, r);
+                const uint32_t bits = posed_word(L, lg, piece, s, r, ~0u);
                 if (bits) contact_word(W, n, r, bits, acc);             // almost no word of a generous box gets here
             }
         }
-        // a workgroup that gathered nothing (acc[0] is `posed`) issues nothing; the barrier also keeps the LDS of the piece
-        // before until its readers are done
-        if (!__syncthreads_or(acc[0] != 0u)) continue;
-        const bool some = __ballot(acc[0] != 0u) != 0ull;               // wave-uniform
-        for (uint32_t k = 0; k < CONTACT_SUMS; ++k) {
-            // the normals (k = 5..7, 12..14) are signed
-            const bool is_signed = (k >= 5u && k <= 7u) || k >= 12u;
-            const unsigned long long mine = is_signed ? (unsigned long long)(long long)(int32_t)acc[k] : (unsigned long long)acc[k];
-            const unsigned long long total = some ? wave_sum(mine) : 0ull;
-            if (lane == 0u) part[wave][k] = total;
-        }
-        __syncthreads();
-        if (threadIdx.x < CONTACT_SUMS) {                               // the non-zero sums of the workgroup: at most 15 atomics
-            unsigned long long v = 0ull;
-            for (uint32_t wv = 0; wv < WAVES; ++wv) v += part[wv][threadIdx.x];
-            if (v) atomicAdd(out + (size_t)CONTACT_WORDS * piece + threadIdx.x, v);
-        }
+        contact_flush(acc, part, out + (size_t)CONTACT_WORDS * piece);
     }
+}
+
+// ---- contacts between posed pieces, pair by pair ---------------------------------------------------------------
+
+// Word k of brick row (cx, cy) of the posed volume as piece `piece` under s fills it, under `want`: the "world word" of the
+// pair kernel, a gather of ids where world_word loads.  The word need not be an item of s.b: outside the piece's box the box
+// mask is 0, and so the result without a load -- a voxel beyond box b is not in A_b.  From 8^3 on this is posed_word of the
+// word.  In a posed volume of 4^3 (n = 2) two rows share a word and the row's 16 bits lie in its lower or upper half: `want`
+// comes in, and the bits go out, moved DOWN to layers 0..3 -- the form contact_word brings a's bits to -- and layers 4..7,
+// which lie beyond the volume, read 0 here: there are no walls between pieces.
+__device__ __forceinline__ uint32_t piece_word(const uint32_t* __restrict__ L, uint32_t lg, uint32_t piece, const Posed& s, uint32_t n, uint32_t cx, uint32_t cy,
+                                               uint32_t k, uint32_t want)
+{
+    if (!want) return 0u;
+    RowWord r;
+    r.cx = cx; r.cy = cy;
+    r.base = ((uint64_t)cx * n + cy) * n;
+    r.first = r.base + s.b.cz0; r.last = r.base + s.b.cz1;
+    if (n >= 4u) {
+        r.w = (r.base >> 2) + k;
+        return posed_word(L, lg, piece, s, r, want);
+    }
+    const uint32_t up = 8u * ((uint32_t)r.base & 3u);
+    r.w = r.base >> 2;
+    return (posed_word(L, lg, piece, s, r, (want & 0xffffu) << up) >> up) & 0xffffu;
+}
+
+// The contact step of one word of A_a with bits != 0 against A_b: contact_word with gathers for loads and zeros for walls.
+// A gather is asked only for the bits the sums will read: under the word itself a's bits and their neighbours inside the word
+// (at most 32 ids), across an x or y face the one plane that faces a's bits there (at most 16), across a z face one layer
+// (at most 4); a face with none of a's bits on it, a word beyond the volume, one outside box b and one whose source box
+// misses b's record box cost nothing.
+// 4^3: a's bits are moved down to layers 0..3 as in contact_word, and piece_word hands b's rows over in the same form, each
+// from its own half of its own word: row (cx, cy) lies in half (2 cx + cy) & 1 of word cx, so the x neighbours come from the
+// other word and the y neighbour from the other half of the same one.  The row is the whole of z, so no word lies before or
+// after it, and with layers 4..7 reading 0 the shift (w >> 4) gives layer 3 an empty upper neighbour, as the rule wants.
+__device__ __forceinline__ void pair_word(const uint32_t* __restrict__ L, uint32_t lg, uint32_t b, const Posed& sb, uint32_t n, const RowWord& r, uint32_t bits,
+                                          uint32_t acc[15])
+{
+    const uint32_t rows = n >= 4u ? n >> 2 : 1u;                        // words per row
+    const uint32_t k = n >= 4u ? (uint32_t)(r.w - (r.base >> 2)) : 0u;
+    if (n < 4u) bits >>= 8u * ((uint32_t)r.base & 3u);
+    const uint32_t cx = r.cx, cy = r.cy;
+    const uint32_t near = bits | ((bits & 0xaaaaaaaau) >> 1) | ((bits & 0x55555555u) << 1) | ((bits & 0xccccccccu) >> 2) | ((bits & 0x33333333u) << 2) |
+                          (bits << 4) | (bits >> 4);
+    const uint32_t w = piece_word(L, lg, b, sb, n, cx, cy, k, near);
+    const uint32_t xm = cx ? piece_word(L, lg, b, sb, n, cx - 1u, cy, k, (bits & 0x55555555u) << 1) : 0u;
+    const uint32_t xp = cx + 1u < n ? piece_word(L, lg, b, sb, n, cx + 1u, cy, k, (bits & 0xaaaaaaaau) >> 1) : 0u;
+    const uint32_t ym = cy ? piece_word(L, lg, b, sb, n, cx, cy - 1u, k, (bits & 0x33333333u) << 2) : 0u;
+    const uint32_t yp = cy + 1u < n ? piece_word(L, lg, b, sb, n, cx, cy + 1u, k, (bits & 0xccccccccu) >> 2) : 0u;
+    const uint32_t zm = k ? piece_word(L, lg, b, sb, n, cx, cy, k - 1u, bits << 28) : 0u;
+    const uint32_t zp = k + 1u < rows ? piece_word(L, lg, b, sb, n, cx, cy, k + 1u, bits >> 28) : 0u;
+    const uint32_t c0[3] = {4u * cx + 1u, 4u * cy + 1u, 16u * k + 1u};
+    contact_sums(bits, w, xm, xp, ym, yp, zm, zp, c0, acc);
+}
+
+// k_contacts with a second posed piece for a world: out[pair] = the contact record of A_a against A_b without walls, for
+// every listed pair (a, b).  blockIdx.y strides over the PAIRS, blockIdx.x over the words of box a; the workgroup poses both
+// pieces.  A pair with an index >= C, or whose a is skipped, keeps its zero record; with b skipped only `posed` is counted.
+// Width of the sums.  As in k_contacts a word adds at most 32 to a count or a normal and less than 2^16 to a sum of c, and the
+// grid is posed_grid's with the pairs for the pieces: blockIdx.y takes at most 4096 rows, so a pair's box a -- at most all of
+// 1024^3, 512 * 512 * 129 < 2^25.02 words -- is shared by at least 16384 / 4096 = 4 workgroups = 1024 lanes (or every lane
+// has at most one word, where the volume has fewer).  A lane starts from zero for every pair it takes and so adds fewer than
+// 2^15.02 words and stays below 2^31.02 in 32 bits, whatever the number of pairs; wave sums, LDS and atomics are 64 bits wide.
+__global__ __launch_bounds__(GROUP) void k_pair_contacts(const uint32_t* __restrict__ L, uint32_t lg, const vrc_component* __restrict__ records, uint32_t C,
+                                                         const uint8_t* __restrict__ keep, const vrc_affine* __restrict__ maps, const uint32_t* __restrict__ boxes,
+                                                         const uint32_t* __restrict__ pairs, uint32_t n_pairs, uint32_t Sd, unsigned long long* out)
+{
+    __shared__ unsigned long long part[WAVES][CONTACT_SUMS];
+    const uint32_t n = Sd >> 1, Ss = 2u << lg;
+    for (uint32_t pair = blockIdx.y; pair < n_pairs; pair += gridDim.y) {       // uniform for the workgroup, and so is all that skips a pair
+        const uint32_t a = pairs[2u * (size_t)pair], b = pairs[2u * (size_t)pair + 1u];
+        if (a >= C || b >= C) continue;
+        Posed sa, sb;
+        if (!pose_piece(records, a, keep, maps, boxes, Sd, Ss, sa)) continue;
+        const bool other = pose_piece(records, b, keep, maps, boxes, Sd, Ss, sb);
+        uint32_t acc[CONTACT_SUMS];
+        for (uint32_t k = 0; k < CONTACT_SUMS; ++k) acc[k] = 0u;
+        for (uint64_t base = (uint64_t)blockIdx.x * GROUP; base < sa.b.items; base += (uint64_t)gridDim.x * GROUP) {     // uniform trip count
+            const uint64_t it = base + threadIdx.x;
+            RowWord r;
+            if (it < sa.b.items && row_word(sa.b, n, it, r)) {
+                const uint32_t bits = posed_word(L, lg, a, sa, r, ~0u);
+                if (bits) {                                             // almost no word of a generous box gets here
+                    if (other) pair_word(L, lg, b, sb, n, r, bits, acc);
+                    else acc[0] += __popc(bits);
+                }
+            }
+        }
+        contact_flush(acc, part, out + (size_t)CONTACT_WORDS * pair);
+    }
+}
+
+// ---- the broad phase: which boxes come near each other -----------------------------------------------------------
+
+// box i of the table clipped to the posed volume; false: the piece has no pairs (keep[i] == 0, an empty or inverted box)
+__device__ __forceinline__ bool pair_box(const uint8_t* __restrict__ keep, const uint32_t* __restrict__ boxes, uint32_t i, uint32_t Sd, uint32_t lo[3], uint32_t hi[3])
+{
+    if (keep && keep[i] == 0) return false;
+    return clip_box(boxes + 6u * (size_t)i, Sd, lo, hi);
+}
+
+// One thread per a walks all b: C^2 box tests.  b is uniform for the wave, so box b and keep[b] come through wave-uniform
+// loads and every lane compares them with a box of its own in registers.  The count pass (EMIT false) stores how many b are
+// candidates of a in slots[a]; k_scan_pair_slots turns the counts into offsets with the total in slots[C]; the emit pass runs
+// the same loop and writes entry slots[a] + j of the canonical list -- (a, b) ascending -- where it falls into
+// [first, first + want).  first + want <= the total.
+template <bool EMIT>
+__global__ __launch_bounds__(GROUP) void k_box_pairs(const uint8_t* __restrict__ keep, const uint32_t* __restrict__ boxes, uint32_t C, uint32_t Sd,
+                                                     unsigned long long* __restrict__ slots, unsigned long long first, unsigned long long want,
+                                                     uint32_t* __restrict__ pairs)
+{
+    const uint32_t a = blockIdx.x * GROUP + threadIdx.x;
+    uint32_t alo[3] = {0u, 0u, 0u}, ahi[3] = {0u, 0u, 0u};
+    bool live = a < C && pair_box(keep, boxes, a, Sd, alo, ahi);
+    unsigned long long at = 0ull;
+    if (EMIT && live) {
+        at = slots[a];
+        live = at < first + want && slots[a + 1u] > first;             // a's run meets the window
+    }
+    if (EMIT && !__syncthreads_or(live)) return;
+    uint32_t found = 0u;
+    for (uint32_t b = 0; b < C; ++b) {                                  // uniform
+        uint32_t blo[3], bhi[3];
+        if (!pair_box(keep, boxes, b, Sd, blo, bhi)) continue;
+        bool near = live && a != b;
+        for (int x = 0; x < 3; ++x) near = near && alo[x] <= bhi[x] && blo[x] <= ahi[x];        // hi exclusive: box a meets box b grown by one voxel
+        if (!near) continue;
+        if (EMIT) {
+            const unsigned long long e = at + found;
+            if (e >= first && e - first < want) {
+                pairs[2u * (e - first)] = a;
+                pairs[2u * (e - first) + 1u] = b;
+            }
+        }
+        ++found;
+    }
+    if (!EMIT && a < C) slots[a] = found;
+}
+
+// a slot is below C <= BOX_PAIR_PIECES = 2^20 and the 1024 slots of a step sum to less than 2^30, as scan_slots wants them
+__global__ __launch_bounds__(SCAN_GROUP) void k_scan_pair_slots(unsigned long long* slots, uint32_t C)
+{
+    const unsigned long long total = scan_slots(slots, C);
+    if (threadIdx.x == 0u) slots[C] = total;
 }
 
 }  // namespace
@@ -437,6 +615,34 @@ hipError_t contacts_run(const uint32_t* labels, const vrc_component* records, ui
     hipLaunchKernelGGL(k_contacts, posed_grid(pieces, Sd), dim3(GROUP), 0, st, labels, depth - 1u, records, (uint32_t)pieces, keep, maps, boxes, world, Sd,
                        (unsigned long long*)out);
     return hipGetLastError();
+}
+
+hipError_t pair_contacts_run(const uint32_t* labels, const vrc_component* records, uint64_t pieces, uint32_t depth, const uint8_t* keep, const vrc_affine* maps,
+                             const uint32_t* boxes, uint32_t posed_depth, uint64_t n_pairs, const uint32_t* pairs, vrc_piece_contact* out, hipStream_t st)
+{
+    const hipError_t e = hipMemsetAsync(out, 0, (size_t)n_pairs * sizeof(vrc_piece_contact), st);
+    if (e != hipSuccess) return e;
+    const uint32_t Sd = 1u << posed_depth;
+    hipLaunchKernelGGL(k_pair_contacts, posed_grid(n_pairs, Sd), dim3(GROUP), 0, st, labels, depth - 1u, records, (uint32_t)pieces, keep, maps, boxes, pairs,
+                       (uint32_t)n_pairs, Sd, (unsigned long long*)out);
+    return hipGetLastError();
+}
+
+size_t box_pair_scratch_bytes(uint64_t pieces) { return (size_t)(pieces + 1u) * 8u; }
+
+void box_pair_count_run(const uint8_t* keep, const uint32_t* boxes, uint64_t pieces, uint32_t posed_depth, unsigned long long* slots, hipStream_t st)
+{
+    const uint32_t C = (uint32_t)pieces;
+    hipLaunchKernelGGL(k_box_pairs<false>, dim3((C + GROUP - 1u) / GROUP), dim3(GROUP), 0, st, keep, boxes, C, 1u << posed_depth, slots, 0ull, 0ull, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(k_scan_pair_slots, dim3(1), dim3(SCAN_GROUP), 0, st, slots, C);
+}
+
+void box_pairs_run(const uint8_t* keep, const uint32_t* boxes, uint64_t pieces, uint32_t posed_depth, unsigned long long* slots, uint64_t first, uint64_t want,
+                   uint32_t* pairs, hipStream_t st)
+{
+    const uint32_t C = (uint32_t)pieces;
+    hipLaunchKernelGGL(k_box_pairs<true>, dim3((C + GROUP - 1u) / GROUP), dim3(GROUP), 0, st, keep, boxes, C, 1u << posed_depth, slots, (unsigned long long)first,
+                       (unsigned long long)want, pairs);
 }
 
 }  // namespace vrc

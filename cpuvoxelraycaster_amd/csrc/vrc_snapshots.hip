@@ -296,6 +296,116 @@ extern "C" int vrc_rigid_contacts(const vrc_labels* l, const uint8_t* keep, cons
     });
 }
 
+static int check_posed_depth(const char* what, uint32_t posed_depth)
+{
+    return posed_depth >= 2 && posed_depth <= 10 ? VRC_OK : vrc::fail(VRC_ERR_INVALID, "%s: posed depth %u not in [2,10]", what, posed_depth);
+}
+
+extern "C" int vrc_rigid_pair_contacts(const vrc_labels* l, const uint8_t* keep, const vrc_affine* maps, const uint32_t* boxes, uint32_t posed_depth,
+                                       uint64_t n_pairs, const uint32_t* pairs, vrc_piece_contact* out, int mem, void* stream)
+{
+    const char* what = "vrc_rigid_pair_contacts";
+    if (!l) return vrc::fail(VRC_ERR_INVALID, "%s: null labels", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (const int rc = check_posed_depth(what, posed_depth)) return rc;
+    if (!maps && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null maps with %llu components", what, (unsigned long long)l->count);
+    if ((!pairs || !out) && n_pairs) return vrc::fail(VRC_ERR_INVALID, "%s: null %s with %llu pairs", what, pairs ? "records" : "pairs", (unsigned long long)n_pairs);
+    if (n_pairs >= (1ull << 32)) return vrc::fail(VRC_ERR_INVALID, "%s: %llu pairs are too many (a pair's index is below 2^32)", what, (unsigned long long)n_pairs);
+    if (!n_pairs || !l->count) return VRC_OK;
+    if (const int rc = check_affines(what, l->count, maps, mem)) return rc;
+    // pairs in host memory are held to the pieces here, pairs in device memory by the kernel
+    if (mem == VRC_MEM_HOST)
+        for (uint64_t k = 0; k < n_pairs; ++k)
+            for (int side = 0; side < 2; ++side)
+                if (pairs[2u * k + side] >= l->count)
+                    return vrc::fail(VRC_ERR_INVALID, "%s: pair %llu: piece %u of %llu components", what, (unsigned long long)k, pairs[2u * k + side],
+                                     (unsigned long long)l->count);
+    const size_t C = (size_t)l->count, P = (size_t)n_pairs;
+    const Call call = snapshot_call(l->device, mem, stream);
+    const StagePart parts[] = {{out, P * sizeof(vrc_piece_contact), STAGE_OUT}, {maps, C * sizeof(vrc_affine), STAGE_IN}, {boxes, C * 24u, STAGE_IN},
+                               {pairs, P * 8u, STAGE_IN}, {keep, C, STAGE_IN}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        return vrc::pair_contacts_run(l->d_ids, l->d_records, l->count, l->depth, (const uint8_t*)d[4], (const vrc_affine*)d[1], (const uint32_t*)d[2], posed_depth,
+                                      n_pairs, (const uint32_t*)d[3], (vrc_piece_contact*)d[0], call.st);
+    });
+}
+
+// The frame of the two broad-phase calls.  Not a staged_call: the scratch block is needed in both memory kinds and holds the
+// staged boxes and keep behind it, the host reads the total back between the count and the emission, and a host-memory
+// window comes down in pieces of at most 2^20 pairs.  Synchronous either way: the block is freed before return.
+static int box_pair_call(const char* what, const vrc_labels* l, const uint8_t* keep, const uint32_t* boxes, uint32_t posed_depth, uint64_t* count, uint64_t first,
+                         uint64_t capacity, uint32_t* pairs, int mem, void* stream)
+{
+    if (!l) return vrc::fail(VRC_ERR_INVALID, "%s: null labels", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (const int rc = check_posed_depth(what, posed_depth)) return rc;
+    if (!boxes && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null boxes with %llu components", what, (unsigned long long)l->count);
+    if (l->count > vrc::BOX_PAIR_PIECES)
+        return vrc::fail(VRC_ERR_INVALID, "%s: %llu components are too many for a pass of C^2 box tests (at most 2^20)", what, (unsigned long long)l->count);
+    if (count) *count = 0;
+    if (!l->count || (!count && !capacity)) return VRC_OK;
+    const bool host = mem == VRC_MEM_HOST;
+    const size_t C = (size_t)l->count, slot_bytes = (vrc::box_pair_scratch_bytes(C) + 15u) & ~(size_t)15u, box_bytes = (C * 24u + 15u) & ~(size_t)15u;
+    const uint64_t chunk = 1ull << 20;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* block = nullptr;
+    uint32_t* d_window = nullptr;
+    hipError_t e = hipSetDevice(l->device);
+    if (e == hipSuccess) e = hipMalloc((void**)&block, slot_bytes + (host ? box_bytes + C : 0u));
+    unsigned long long* slots = (unsigned long long*)block;
+    const uint32_t* d_boxes = boxes;
+    const uint8_t* d_keep = keep;
+    if (host && e == hipSuccess) {
+        d_boxes = (const uint32_t*)(block + slot_bytes);
+        e = hipMemcpyAsync((void*)d_boxes, boxes, C * 24u, hipMemcpyHostToDevice, st);
+        if (keep && e == hipSuccess) {
+            d_keep = block + slot_bytes + box_bytes;
+            e = hipMemcpyAsync((void*)d_keep, keep, C, hipMemcpyHostToDevice, st);
+        }
+    }
+    unsigned long long total = 0;
+    if (e == hipSuccess) {
+        vrc::box_pair_count_run(d_keep, d_boxes, C, posed_depth, slots, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, slots + C, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    const uint64_t want = e == hipSuccess ? window_of(first, capacity, total) : 0u;
+    if (want && !host) {
+        vrc::box_pairs_run(d_keep, d_boxes, C, posed_depth, slots, first, want, pairs, st);
+        e = hipGetLastError();
+    } else if (want) {
+        e = hipMalloc((void**)&d_window, (size_t)(want < chunk ? want : chunk) * 8u);
+        for (uint64_t at = 0; at < want && e == hipSuccess; at += chunk) {
+            const uint64_t now = want - at < chunk ? want - at : chunk;
+            vrc::box_pairs_run(d_keep, d_boxes, C, posed_depth, slots, first + at, now, d_window, st);
+            if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpyAsync(pairs + 2u * at, d_window, (size_t)now * 8u, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+        }
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (d_window) (void)hipFree(d_window);
+    if (block) (void)hipFree(block);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    if (count) *count = total;
+    return VRC_OK;
+}
+
+extern "C" int vrc_rigid_box_pair_count(const vrc_labels* l, const uint8_t* keep, const uint32_t* boxes, uint32_t posed_depth, uint64_t* count, int mem, void* stream)
+{
+    const char* what = "vrc_rigid_box_pair_count";
+    if (!count) return vrc::fail(VRC_ERR_INVALID, "%s: null count", what);
+    return box_pair_call(what, l, keep, boxes, posed_depth, count, 0, 0, nullptr, mem, stream);
+}
+
+extern "C" int vrc_rigid_box_pairs(const vrc_labels* l, const uint8_t* keep, const uint32_t* boxes, uint32_t posed_depth, uint64_t first, uint64_t capacity,
+                                   uint32_t* pairs, int mem, void* stream)
+{
+    const char* what = "vrc_rigid_box_pairs";
+    if (!pairs && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
+    return box_pair_call(what, l, keep, boxes, posed_depth, nullptr, first, capacity, pairs, mem, stream);
+}
+
 // ---- Voronoi fracture (the rule: include/vrc.h; the cells: vrc_fracture.hip; the labelling: vrc_components.hip) ------
 
 // One scratch block for the call: the labelling's counts, the dense cell field, the site table and the stacks, and behind

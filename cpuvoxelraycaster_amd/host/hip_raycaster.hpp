@@ -323,6 +323,14 @@ public:
     // world is only read (its queued cells are flushed first) and nothing is excluded from it.
     inline std::vector<vrc_piece_contact> contacts(const std::vector<vrc_affine>& maps, HipVoxelVolume& world, const std::vector<uint32_t>* boxes = nullptr,
                                                    const std::vector<uint8_t>* keep = nullptr) const;
+    // The broad phase of pairContacts (include/vrc.h: vrc_rigid_box_pairs): the ordered pairs (a, b), a != b, of kept pieces whose
+    // boxes (count() x 6, lo then hi), clipped to a posed volume of posed_depth, meet when one is grown by a voxel; both orders,
+    // ascending, two numbers a pair.
+    inline std::vector<uint32_t> candidatePairs(const std::vector<uint32_t>& boxes, uint32_t posed_depth, const std::vector<uint8_t>* keep = nullptr) const;
+    // One record per ordered pair (a, b) of `pairs` (two numbers a pair): piece a, posed as placeAffine would write it into a
+    // volume of posed_depth, against piece b posed the same way -- no world, no walls -- include/vrc.h: vrc_rigid_pair_contacts.
+    inline std::vector<vrc_piece_contact> pairContacts(const std::vector<vrc_affine>& maps, const std::vector<uint32_t>& pairs, uint32_t posed_depth,
+                                                       const std::vector<uint32_t>* boxes = nullptr, const std::vector<uint8_t>* keep = nullptr) const;
     vrc_labels* handle() const { return l_; }
 
 private:
@@ -900,6 +908,34 @@ inline std::vector<vrc_piece_contact> HipVoxelLabels::contacts(const std::vector
     check(vrc_rigid_contacts(l_, keep && !keep->empty() ? keep->data() : nullptr, maps.empty() ? nullptr : maps.data(),
                              boxes && !boxes->empty() ? boxes->data() : nullptr, world.handle(), out.empty() ? nullptr : out.data(), VRC_MEM_HOST, nullptr),
           "vrc_rigid_contacts");
+    return out;
+}
+
+inline std::vector<uint32_t> HipVoxelLabels::candidatePairs(const std::vector<uint32_t>& boxes, uint32_t posed_depth, const std::vector<uint8_t>* keep) const
+{
+    if (boxes.size() != count() * 6u) throw std::invalid_argument("HipVoxelLabels::candidatePairs: boxes must have six entries per component");
+    if (keep && keep->size() != count()) throw std::invalid_argument("HipVoxelLabels::candidatePairs: keep must have one byte per component");
+    const uint8_t* k = keep && !keep->empty() ? keep->data() : nullptr;
+    const uint32_t* b = boxes.empty() ? nullptr : boxes.data();
+    uint64_t n = 0;
+    check(vrc_rigid_box_pair_count(l_, k, b, posed_depth, &n, VRC_MEM_HOST, nullptr), "vrc_rigid_box_pair_count");
+    std::vector<uint32_t> pairs((size_t)n * 2u);
+    if (n) check(vrc_rigid_box_pairs(l_, k, b, posed_depth, 0, n, pairs.data(), VRC_MEM_HOST, nullptr), "vrc_rigid_box_pairs");
+    return pairs;
+}
+
+inline std::vector<vrc_piece_contact> HipVoxelLabels::pairContacts(const std::vector<vrc_affine>& maps, const std::vector<uint32_t>& pairs, uint32_t posed_depth,
+                                                                   const std::vector<uint32_t>* boxes, const std::vector<uint8_t>* keep) const
+{
+    if (maps.size() != count()) throw std::invalid_argument("HipVoxelLabels::pairContacts: maps must have one entry per component");
+    if (boxes && boxes->size() != count() * 6u) throw std::invalid_argument("HipVoxelLabels::pairContacts: boxes must have six entries per component");
+    if (keep && keep->size() != count()) throw std::invalid_argument("HipVoxelLabels::pairContacts: keep must have one byte per component");
+    if (pairs.size() & 1u) throw std::invalid_argument("HipVoxelLabels::pairContacts: pairs must have two entries per pair");
+    std::vector<vrc_piece_contact> out(pairs.size() / 2u);
+    check(vrc_rigid_pair_contacts(l_, keep && !keep->empty() ? keep->data() : nullptr, maps.empty() ? nullptr : maps.data(),
+                                  boxes && !boxes->empty() ? boxes->data() : nullptr, posed_depth, out.size(), pairs.empty() ? nullptr : pairs.data(),
+                                  out.empty() ? nullptr : out.data(), VRC_MEM_HOST, nullptr),
+          "vrc_rigid_pair_contacts");
     return out;
 }
 

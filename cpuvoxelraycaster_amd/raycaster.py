@@ -452,7 +452,9 @@ class VoxelVolume:
         """Break, let the shards fall, ready to commit: the solid within max_distance of the `sites` is cut into Voronoi shards
         (fracture), the shards -- the pieces whose cell is a site -- are taken out of the volume, fall as rigid bodies along
         `direction` (a capi.VRC_FACE_* code) onto what is left, onto each other or onto the volume's face, at most drop_limit
-        cells (0 = no limit), and are put back where they come to rest.  Returns (capi.FallStats, the VoxelLabels)."""
+        cells (0 = no limit), and are put back where they come to rest.  Returns (capi.FallStats, the VoxelLabels).  The labels
+        are what a physics engine goes on with: poses() for tumbling shards, contacts() against the world, and
+        candidatePairs() / pairContacts() for shard against shard."""
         labels = self.fracture(sites, connectivity, False, max_distance)
         try:
             shards = (labels.pieceSites() != capi.VRC_NO_COMPONENT).astype(np.uint8)
@@ -976,6 +978,50 @@ class VoxelLabels:
         """the same with the maps (64 bytes each), the boxes, `count` bytes of keep and the records (128 bytes each) in device
         memory, asynchronous on `stream`; a piece whose map lies beyond the limits has an all-zero record"""
         check(capi.load().vrc_rigid_contacts(self._h, ptr(keep_ptr), ptr(maps_ptr), ptr(boxes_ptr), world._h, ptr(out_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def candidatePairs(self, boxes, depth=None, keep=None):
+        """The broad phase of pairContacts (include/vrc.h: vrc_rigid_box_pairs): the ordered pairs (a, b), a != b, of pieces with
+        keep[id] != 0 (None: all) whose (count, 6) uint32 boxes, clipped to a posed volume of `depth` (None: the labels'), meet
+        when one is grown by a voxel -- necessary for overlap or touch.  Both orders, ascending; a (P, 2) uint32 array."""
+        depth = self.depth if depth is None else int(depth)
+        boxes = np.ascontiguousarray(boxes, np.uint32).reshape(-1, 6)
+        if len(boxes) != self.count:
+            raise ValueError(f"boxes has {len(boxes)} rows for {self.count} components")
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, np.uint8).reshape(-1)
+            if len(keep) != self.count:
+                raise ValueError(f"keep has {len(keep)} entries for {self.count} components")
+        count = C.c_uint64()
+        check(capi.load().vrc_rigid_box_pair_count(self._h, ptr(keep), ptr(boxes) if self.count else None, depth, C.byref(count), capi.VRC_MEM_HOST, None))
+        pairs = np.zeros((int(count.value), 2), np.uint32)
+        if len(pairs):
+            check(capi.load().vrc_rigid_box_pairs(self._h, ptr(keep), ptr(boxes), depth, 0, len(pairs), ptr(pairs), capi.VRC_MEM_HOST, None))
+        return pairs
+
+    def pairContacts(self, maps, pairs=None, boxes=None, depth=None, keep=None):
+        """One capi.CONTACT_DTYPE record per ordered pair (a, b) of the (P, 2) uint32 `pairs`: piece a, posed as placeAffine
+        would write it into a volume of `depth` (None: the labels'), against piece b posed the same way and nothing else -- no
+        world and no walls -- include/vrc.h: vrc_rigid_pair_contacts.  posed = a's voxels there, overlap* = those inside b,
+        touch* = those outside b with a voxel of b next to them; the normals point out of b.  List (b, a) as well for b's side.
+        pairs=None: candidatePairs(boxes, depth, keep) first, which needs boxes; call that yourself to keep the list."""
+        maps, boxes, keep = self._contact_arguments(maps, boxes, keep)
+        depth = self.depth if depth is None else int(depth)
+        if pairs is None:
+            if boxes is None:
+                raise ValueError("pairContacts: pairs=None needs boxes for candidatePairs")
+            pairs = self.candidatePairs(boxes, depth, keep)
+        pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+        out = np.zeros(len(pairs), capi.CONTACT_DTYPE)
+        check(capi.load().vrc_rigid_pair_contacts(self._h, ptr(keep), ptr(maps) if self.count else None, ptr(boxes), depth, len(pairs),
+                                                   ptr(pairs) if len(pairs) else None, ptr(out) if len(pairs) else None, capi.VRC_MEM_HOST, None))
+        return out
+
+    def pairContactsDevice(self, maps_ptr, n_pairs, pairs_ptr, out_ptr, boxes_ptr=None, depth=None, keep_ptr=None, stream=None):
+        """the same with the maps, the boxes, `count` bytes of keep, the n_pairs x 2 uint32 pairs and the records (128 bytes each)
+        in device memory, asynchronous on `stream`; a pair with a piece index beyond the pieces, or whose first piece has a map
+        beyond the limits, has an all-zero record"""
+        check(capi.load().vrc_rigid_pair_contacts(self._h, ptr(keep_ptr), ptr(maps_ptr), ptr(boxes_ptr), self.depth if depth is None else int(depth),
+                                                   int(n_pairs), ptr(pairs_ptr), ptr(out_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
 
     def collides(self, maps, world, boxes=None, keep=None):
         """bool per piece: the posed piece shares a voxel with the world's solid (contacts()["overlap"] > 0)"""

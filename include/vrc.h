@@ -563,7 +563,7 @@ int vrc_fall_place(const vrc_labels *l, const uint8_t *keep /* C bytes, NULL = a
                      const int32_t *offsets /* C x 3 */, vrc_volume *dst, int op, int mem, void *stream);
 
 /* The pieces of a labelling as rigid bodies with a pose, on the device: what a physics engine needs of every piece, and what
- * it hands back (and vrc_rigid_contacts, further down, the test of a proposed pose in between).  vrc_rigid_moments gives the raw moments that mass, centre of mass and inertia tensor follow from, without
+ * it hands back (and vrc_rigid_contacts and vrc_rigid_pair_contacts, further down, the tests of a proposed pose in between).  vrc_rigid_moments gives the raw moments that mass, centre of mass and inertia tensor follow from, without
  * a dense download of the ids; vrc_rigid_place_affine writes every piece through its OWN inverse affine map -- a set of
  * debris tumbling -- in one call where vrc_labels_select and vrc_volume_stamp_affine would take a scratch volume and two
  * calls per piece.  Both work on a vrc_labels snapshot and, like vrc_fall_*, carry the name of what they serve.  Exact in
@@ -659,8 +659,8 @@ int vrc_rigid_place_affine(const vrc_labels *l, const uint8_t *keep /* C bytes, 
  * `world` is only read, may differ in depth from the labels and must be on the labels' device.  The labels are a snapshot, so
  * world may be the labelled medium itself -- but NOTHING is excluded then: a piece at its identity pose overlaps itself in
  * every voxel.  To test against "everything else", take the piece out first (vrc_labels_select with VRC_COPY_ANDNOT into a
- * clone) or pass the supported part alone, as vrc_fall_drops takes `fixed`.  Piece against piece is out of scope: place the
- * other pieces into a volume with vrc_rigid_place_affine and pass that.
+ * clone) or pass the supported part alone, as vrc_fall_drops takes `fixed`.  Piece against piece is vrc_rigid_pair_contacts, further
+ * down: the same record for every listed pair of posed pieces, with no volume in between.
  * Memory, ordering and refusals are vrc_rigid_place_affine's.  mem says where keep, maps, boxes and out live.  VRC_MEM_HOST
  * stages the four in one block, freed before return, and is synchronous; every map is checked before any device call
  * ("piece <i>: ..." names the first bad one).  VRC_MEM_DEVICE works in place and is asynchronous on `stream`: out is zeroed
@@ -701,6 +701,80 @@ typedef struct vrc_piece_contact {       /* 128 bytes */
 int vrc_rigid_contacts(const vrc_labels *l, const uint8_t *keep /* C bytes, NULL = all */,
                        const vrc_affine *maps /* C */, const uint32_t *boxes /* C x 6 lo,hi; NULL = all of world */,
                        vrc_volume *world, vrc_piece_contact *out /* C */, int mem, void *stream);
+
+/* vrc_rigid_pair_contacts: posed pieces against each other, pair by pair.  vrc_rigid_contacts tests every piece against a
+ * world; a pile of shards that tumble onto each other needs piece against piece, and through a world that is one scratch
+ * volume, one placement of the other piece and one contact call per pair -- and the record still does not say which piece
+ * was hit.  Here one call takes a list of ordered pairs and gives one vrc_piece_contact per pair.  Exact in integers.
+ *
+ * The sets.  S_d = 2^posed_depth voxels per axis, posed_depth in 2..10; it may differ from the labels' depth.  A_i is exactly
+ * the set vrc_rigid_place_affine would OR into an empty volume of depth posed_depth with the same keep, maps and boxes (NULL
+ * boxes: all of that volume).  A_i is empty for a skipped piece: keep[i] == 0, an empty or inverted box, and with
+ * VRC_MEM_DEVICE a map beyond the limits.
+ * The record.  out[k], for pair k = (a, b) = (pairs[2k], pairs[2k + 1]), is the record of A_a against the world W = A_b
+ * WITHOUT walls: W*(p) = 1 iff p is in A_b.  A neighbour beyond the volume reads 0, and so does one beyond box b, because it
+ * is not in A_b.  From that W* the fields follow as in vrc_rigid_contacts: posed = |A_a|; overlap, overlap_s1 and overlap_n
+ * over A_a and A_b; touch, touch_s1 and touch_n over the voxels of A_a outside A_b with a face neighbour in A_b;
+ * n(p)_a = W*(p - e_a) - W*(p + e_a) points out of b, the way to push a; reserved = 0.
+ * The pair is ORDERED: a caller who wants both sides lists (a, b) and (b, a); the overlap count and overlap_s1 of the two
+ * are equal, the rest is not.  a == b is legal and nothing is excluded: a piece overlaps itself in every voxel.  If a is
+ * skipped the record is all zero; if only b is skipped, posed = |A_a| and the rest is zero.  Three or more pieces in one
+ * voxel need no rule of their own: every listed pair sees its own two sets.  A pair may be listed more than once.
+ * A piece index >= C: with VRC_MEM_HOST the call is VRC_ERR_INVALID before any device call ("pair <k>: ..." names the first
+ * bad pair, next to the "piece <i>: ..." of the map check); with VRC_MEM_DEVICE that pair's record is all zero.
+ * Memory, ordering and refusals are vrc_rigid_contacts', without a world to order behind.  mem says where keep, maps, boxes,
+ * pairs and out live.  VRC_MEM_HOST stages the five in one block, freed before return, and is synchronous; VRC_MEM_DEVICE
+ * works in place, asynchronous on `stream`: out is zeroed and filled there.  NULL l, NULL maps when C > 0, NULL pairs or out
+ * when n_pairs > 0, n_pairs >= 2^32, a posed_depth outside 2..10 and a bad mem are VRC_ERR_INVALID before any device call.
+ * n_pairs == 0 or C == 0 is a no-op.  The call keeps no scratch: vrc_labels_bytes and vrc_volume_edit_scratch_bytes do not
+ * change.  Sums of integers do not depend on their order: two calls give identical bytes.
+ * The device (csrc/vrc_rigid.hip) runs ONE kernel of vrc_rigid_contacts' shape: blockIdx.y strides over the PAIRS (at most
+ * 4096 rows, the rest by stride), blockIdx.x over the occupancy words of box a, and the workgroup poses both pieces with the
+ * per-piece set-up the other two kernels use.  Per word a's bits come from the common gather; almost every word of a generous
+ * box stops there with 0.  A word with bits needs the "world word" of b and its six face neighbours, and these are not loads
+ * but gathers of piece b through its own map -- under a mask of the bits the sums will read: a's bits and their neighbours
+ * inside the word for the centre (at most 32 id loads), the facing plane of 16 for an x or y neighbour, the facing layer of 4
+ * for a z neighbour, 72 for the six faces instead of 192, and nothing for a face none of a's bits lie on.  A neighbour word
+ * outside box b, one whose source box misses b's record box and one beyond the volume read 0 without a load.  The seven words
+ * then go through the very reduction vrc_rigid_contacts uses -- shifts under constant masks, popcounts, 32-bit lane sums,
+ * 64-bit wave sums, the four waves meeting in LDS, at most 15 non-zero 64-bit vector atomic adds per workgroup and pair.  No
+ * dense field of "which piece owns this voxel" is built: posed pieces may overlap, so a voxel has no single owner, and a
+ * field per pair is the scratch volume this call replaces.
+ * Measured on an MI355X at 512^3 on the fall benchmark's scene with every piece turned 30 degrees about x, then y, about its
+ * own centre of mass (tools/bench_edit.py --pair-contacts, profiles/edit/bench_pair_contacts.json; device time by events,
+ * median of 5, everything in device memory): the 404 loose blocks of 1.9 M voxels give 3688 candidate pairs, listed by
+ * vrc_rigid_box_pair_count + vrc_rigid_box_pairs in 0.33 ms (both synchronous, the allocation of their scratch included);
+ * vrc_rigid_pair_contacts over all of them 0.81 ms, the zeroing of the records included; 652 pairs overlap (0.11 M voxels) and 798
+ * touch.  The yardstick in the same run, the documented workaround timed on a sample of 64 of the pairs -- per pair the clearing
+ * of a 512^3 scratch volume, vrc_rigid_place_affine of b alone into it and vrc_rigid_contacts of a alone against it: 0.098 ms a
+ * pair, 360 ms scaled to the 3688, 445 times the one call.  Not timed apart: the zeroing, the two gathers and the reduction of
+ * the pair kernel; the count, scan and emit passes of the broad phase; the three steps of the workaround.
+ *
+ * vrc_rigid_box_pair_count / vrc_rigid_box_pairs: the broad phase, the list the narrow phase wants, made from boxes that
+ * live on the device.  Every box (C x 6 uint32, lo then hi, REQUIRED: with "all of the volume" every pair is a candidate and
+ * the caller knows that) is clipped to [0, S_d)^3.  A piece with keep[i] == 0 or an empty or inverted box has no pairs.  The
+ * ordered pair (a, b), a != b, is a candidate iff on all three axes lo_a <= hi_b and lo_b <= hi_a (hi exclusive): box a meets
+ * box b grown by one voxel, which is necessary for overlap OR touch.  The relation is symmetric and both orders are listed,
+ * (a, b) ascending lexicographically.  vrc_rigid_box_pair_count gives the length of that list.  vrc_rigid_box_pairs has the
+ * window of vrc_labels_components: the entries of [first, first + capacity) that exist are written from pairs[0], nothing
+ * beyond them is touched, first >= count writes nothing, capacity == 0 with NULL pairs is legal.  l supplies C and the device
+ * and is not otherwise read.  mem says where keep, boxes and pairs live; `count` is the caller's host memory.  Both calls run
+ * on `stream` and are synchronous: they return when the work is done.  NULL l, NULL count, NULL boxes when C > 0, NULL pairs
+ * with capacity > 0, a posed_depth outside 2..10, a bad mem and C > 2^20 are VRC_ERR_INVALID before any device call.
+ * The device: one thread per a walks all b, so every lane of a wave reads the same box b and the table comes through
+ * wave-uniform loads; the pass stores a's count, one scan turns the counts into offsets, and a second pass of the same loop
+ * emits what falls into the window -- the project's count, scan, emit.  Scratch is (C + 1) x 8 bytes (and the staged boxes
+ * and keep of a host-memory call), freed before return.  The cost is C^2 box tests, whatever the boxes: sensible up to some
+ * ten thousand pieces (10^8 tests); beyond that a caller wants a grid or a sort, and beyond 2^20 pieces the call refuses. */
+int vrc_rigid_pair_contacts(const vrc_labels *l, const uint8_t *keep /* C bytes, NULL = all */,
+                            const vrc_affine *maps /* C */, const uint32_t *boxes /* C x 6 lo,hi; NULL = all of the posed volume */,
+                            uint32_t posed_depth,
+                            uint64_t n_pairs, const uint32_t *pairs /* n_pairs x 2: a, b */,
+                            vrc_piece_contact *out /* n_pairs */, int mem, void *stream);
+int vrc_rigid_box_pair_count(const vrc_labels *l, const uint8_t *keep, const uint32_t *boxes /* C x 6, required */,
+                             uint32_t posed_depth, uint64_t *count, int mem, void *stream);      /* synchronous */
+int vrc_rigid_box_pairs(const vrc_labels *l, const uint8_t *keep, const uint32_t *boxes, uint32_t posed_depth,
+                        uint64_t first, uint64_t capacity, uint32_t *pairs /* capacity x 2 */, int mem, void *stream);
 
 /* Voronoi fracture into labelled shards, on the device: the step BEFORE "a piece is loose".  A solid body is cut along the
  * Voronoi partition around a handful of sites (impact points), no material is removed, and the result is an ordinary
