@@ -37,7 +37,12 @@ def walled(world):
 
 def record(A, star):
     """the contact record of the posed set A (dense, or None for a skipped piece) against the world whose W* is `star`"""
-    p = np.argwhere(A).astype(np.int64) if A is not None else ()
+    return record_at(np.argwhere(A) if A is not None else (), star)
+
+
+def record_at(p, star):
+    """the same from the voxels of the posed set as an (N, 3) list: what the large cases keep in place of a dense array a piece"""
+    p = np.asarray(p, np.int64).reshape(-1, 3)
     if not len(p):
         return ZERO
     c = 2 * p + 1
