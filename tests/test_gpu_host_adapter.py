@@ -1,17 +1,15 @@
 """The C++ host adapter (HipLSVO / HipRayCaster, the reference's Volumetric /
 RayCaster interface) compiled with plain g++ against the C ABI and run on the GPU:
 autofocus ray and a GI frame must match the oracle."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
+from volume_support import run_cpp_main
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_host_adapter_matches_oracle(built, heights, textures, tmp_path):
@@ -22,15 +20,8 @@ def test_cpp_host_adapter_matches_oracle(built, heights, textures, tmp_path):
     nodes.tofile(tmp_path / "nodes.bin")
     top.tofile(tmp_path / "top.rgb")
     side.tofile(tmp_path / "side.rgb")
-    exe = str(tmp_path / "host_adapter_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "host_adapter_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe, str(tmp_path / "nodes.bin"), str(depth), str(tmp_path / "top.rgb"),
-                          str(tmp_path / "side.rgb"), str(W), str(H)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = run_cpp_main(tmp_path, "host_adapter_main", tmp_path / "nodes.bin", depth, tmp_path / "top.rgb", tmp_path / "side.rgb", W, H,
+                       flags=("-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"), libs=("-L/opt/rocm/lib", "-lamdhip64"))
     m = re.search(r"autofocus hit=(\d) distance=(\S+) complexity=(\d+) normal=(\S+),(\S+),(\S+)", out.stdout)
     f = re.search(r"frame sum=(\d+) fnv=([0-9a-f]+) rays=(\d+) steps=(\d+)", out.stdout)
     assert m and f, out.stdout

@@ -11,6 +11,8 @@ import sys
 
 import pytest
 
+from volume_support import compile_cpp_main
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
@@ -60,13 +62,9 @@ def test_peer_written_frames_equal_unsharded(built, world):
 def test_cpp_host_peer_writes(built, tmp_path, world):
     """the same exchange from a C++ host: tests/cpp/peer_write_main.cpp (vrc_host::HipFramePipeline + HipRayCaster::exportImage /
     setImageTarget + the frame flags), `world` forked processes on GPU 0"""
-    exe = str(tmp_path / "peer_write_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "peer_write_main.cpp"), "-o", exe,
-                           "-L" + libdir, "-l:libvrc_hip.so", "-L/opt/rocm/lib", "-lamdhip64", "-lpthread",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    data = os.path.join(libdir, "data")
+    exe = compile_cpp_main(tmp_path, "peer_write_main", flags=("-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"),
+                           libs=("-L/opt/rocm/lib", "-lamdhip64", "-lpthread"))
+    data = os.path.join(ROOT, "cpuvoxelraycaster_amd", "data")
     W, H = ("1920", "1080") if world == 8 else ("1280", "720")
     p = subprocess.Popen([exe, str(world), "8", W, H, "4", "9", os.path.join(data, "grass_top_16x16.rgb"),
                           os.path.join(data, "grass_side_16x16.rgb")], env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"),
@@ -121,13 +119,9 @@ def test_a_dead_writer_ends_the_run_instead_of_hanging_it(built):
 
 def test_cpp_host_dead_writer(built, tmp_path):
     """the same failure from the C++ host (HipFramePipeline::waitAllWatched): a forked rank _exit()s mid-run"""
-    exe = str(tmp_path / "peer_write_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "peer_write_main.cpp"), "-o", exe,
-                           "-L" + libdir, "-l:libvrc_hip.so", "-L/opt/rocm/lib", "-lamdhip64", "-lpthread",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    data = os.path.join(libdir, "data")
+    exe = compile_cpp_main(tmp_path, "peer_write_main", flags=("-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"),
+                           libs=("-L/opt/rocm/lib", "-lamdhip64", "-lpthread"))
+    data = os.path.join(ROOT, "cpuvoxelraycaster_amd", "data")
     p = subprocess.Popen([exe, "3", "8", "1280", "720", "4", "12", os.path.join(data, "grass_top_16x16.rgb"), os.path.join(data, "grass_side_16x16.rgb")],
                          env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PW_DIE_RANK="2", PW_DIE_AT_FRAME="5"),
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)

@@ -8,19 +8,16 @@ import subprocess
 
 import pytest
 
+from volume_support import compile_cpp_main
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("rccl") / "rccl_gather_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "rccl_gather_main.cpp"), "-o", out,
-                           "-L" + libdir, "-l:libvrc_hip.so", "-L/opt/rocm/lib", "-lrccl", "-lamdhip64", "-lpthread",
-                           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    return out
+    return compile_cpp_main(tmp_path_factory.mktemp("rccl"), "rccl_gather_main", flags=("-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"),
+                            libs=("-L/opt/rocm/lib", "-lrccl", "-lamdhip64", "-lpthread"))
 
 
 def run(exe, tmp_path, mode, world=1, frames=7):

@@ -4,24 +4,17 @@ HipRayCaster::renderFrame (a g++-built C++ program over the C ABI, like the refe
 frame's image hash, ray count and loop-iteration count must equal the oracle's frame for the same tick."""
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
+from volume_support import compile_cpp_main, fnv1a, run_cpp_main, run_program
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REPLAY = os.path.join(ROOT, "tests", "golden", "orbit.replay")
-
-
-def fnv1a(buf):
-    h = 1469598103934665603
-    for b in bytes(buf):
-        h = ((h ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return h
 
 
 def test_replay_file_through_cpp_adapter_matches_oracle(built, heights, textures, tmp_path):
@@ -36,13 +29,8 @@ def test_replay_file_through_cpp_adapter_matches_oracle(built, heights, textures
     nodes.tofile(tmp_path / "nodes.bin")
     top.tofile(tmp_path / "top.rgb")
     side.tofile(tmp_path / "side.rgb")
-    exe = str(tmp_path / "replay_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", os.path.join(ROOT, "tests", "cpp", "replay_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe, str(tmp_path / "nodes.bin"), str(depth), str(tmp_path / "top.rgb"), str(tmp_path / "side.rgb"),
-                          str(W), str(H), str(spp), REPLAY], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = run_cpp_main(tmp_path, "replay_main", tmp_path / "nodes.bin", depth, tmp_path / "top.rgb", tmp_path / "side.rgb", W, H, spp,
+                       REPLAY, timeout=300, flags=())
     assert f"{len(ticks)} ticks loaded" in out.stdout
     frames = re.findall(r"frame (\d+) t=(\S+) fnv=([0-9a-f]+) rays=(\d+) steps=(\d+) hits=(\d+)", out.stdout)
     assert len(frames) == len(ticks)
@@ -79,16 +67,12 @@ def test_replay_through_frame_pipeline_equals_tick_by_tick(built, heights, textu
     top.tofile(tmp_path / "top.rgb")
     side.tofile(tmp_path / "side.rgb")
     ticks = [ln.split() for ln in open(REPLAY).read().splitlines() if ln.strip()]
-    exe = str(tmp_path / "replay_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", os.path.join(ROOT, "tests", "cpp", "replay_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
+    exe = compile_cpp_main(tmp_path, "replay_main", flags=())
     base = [exe, str(tmp_path / "nodes.bin"), str(depth), str(tmp_path / "top.rgb"), str(tmp_path / "side.rgb"),
             str(W), str(H), str(spp), REPLAY]
 
     def frames(extra):
-        out = subprocess.run(base + extra, capture_output=True, text=True, timeout=300)
-        assert out.returncode == 0, out.stdout + out.stderr
+        out = run_program(*base, *extra, timeout=300)
         return re.findall(r"frame (\d+) t=(\S+) fnv=([0-9a-f]+) rays=(\d+) steps=(\d+) hits=(\d+)", out.stdout)
 
     want = frames([])

@@ -2,40 +2,16 @@
 array the oracle's SVO::setCell + compileSVO (small depths) or the host builder (depth 8-9, itself held to the oracle
 by tests/test_builder.py) produces for the numpy-tracked voxel set -- bit for bit -- and the frames rendered on them."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
+from volume_support import committed as committed_nodes, expected_nodes, same, terrain_volume
 
 pytestmark = pytest.mark.gpu
-
-
-def same(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
-def terrain_volume(heights, depth):
-    """main.cpp:65-74 as dense occupancy [x, y, z]: column (x, z) solid for y in [S/2 + 1, S/2 + lim)"""
-    S = 1 << depth
-    lim = np.maximum(16, np.minimum(S, heights[:S, :S].astype(np.int64)))
-    y = np.arange(S)[None, :, None]
-    return ((y >= S // 2 + 1) & (y < S // 2 + lim[:, None, :])).astype(np.uint8)
-
-
-def expected_nodes(vol, depth):
-    import cpuvoxelraycaster_amd as vrc
-    if depth <= 5:
-        return O.compile_voxels(depth, np.argwhere(vol))
-    return vrc.build_volume_lsvo(vol, depth)
-
-
-def committed(volume):
-    svo = volume.commit()
-    nodes = svo.downloadNodes()
-    assert svo.build_ms is not None and svo.build_ms > 0
-    svo.close()
-    return nodes
+committed = functools.partial(committed_nodes, timed=True)      # every commit of this file must also report its build time
 
 
 # ---- 1. round trip -------------------------------------------------------------------------------------------

@@ -9,36 +9,11 @@ import pytest
 
 import oracle_lib as O
 import raygen
+from volume_support import Stream, committed, expected_nodes, same, terrain_volume
 
 pytestmark = pytest.mark.gpu
 
 LIMIT = 1 << 20
-
-
-def same(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
-def terrain_volume(heights, depth):
-    """main.cpp:65-74 as dense occupancy [x, y, z]: column (x, z) solid for y in [S/2 + 1, S/2 + lim)"""
-    S = 1 << depth
-    lim = np.maximum(16, np.minimum(S, heights[:S, :S].astype(np.int64)))
-    y = np.arange(S)[None, :, None]
-    return ((y >= S // 2 + 1) & (y < S // 2 + lim[:, None, :])).astype(np.uint8)
-
-
-def expected_nodes(vol, depth):
-    import cpuvoxelraycaster_amd as vrc
-    if depth <= 5:
-        return O.compile_voxels(depth, np.argwhere(vol))
-    return vrc.build_volume_lsvo(vol, depth)
-
-
-def committed(volume):
-    svo = volume.commit()
-    nodes = svo.downloadNodes()
-    svo.close()
-    return nodes
 
 
 def check_volume(volume, vol, depth, what, commit=True):
@@ -56,19 +31,6 @@ def random_volume(depth, density, seed):
     volume = vrc.VoxelVolume.fromScene(scene)
     scene.close()
     return vol, volume
-
-
-class Stream:
-    def __enter__(self):
-        import cpuvoxelraycaster_amd as vrc
-        self.L = vrc.capi.load()
-        self.h = C.c_void_p()
-        vrc.capi.check(self.L.vrc_stream_create(0, C.byref(self.h)))
-        return self.h
-
-    def __exit__(self, *exc):
-        self.L.vrc_stream_synchronize(0, self.h)
-        self.L.vrc_stream_destroy(0, self.h)
 
 
 # ---- 1. spheres ------------------------------------------------------------------------------------------------

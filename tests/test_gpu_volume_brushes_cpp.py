@@ -3,22 +3,15 @@ g++ against the C ABI and run on the GPU: cast -> brush at hits -> commit -> set
 sequence renders through the Python VoxelVolume."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import raygen
+from volume_support import fnv1a, run_cpp_main
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def fnv1a(data):
-    h = 1469598103934665603
-    for b in data:
-        h = ((h ^ b) * 1099511628211) & 0xffffffffffffffff
-    return h
 
 
 def test_cpp_brush_at_hits_matches_python_path(built, tmp_path):
@@ -31,13 +24,7 @@ def test_cpp_brush_at_hits_matches_python_path(built, tmp_path):
     org[:] = np.array(vrc.reference_camera_position(depth), np.float32) / S + np.float32(1.0)   # the camera the frame is rendered from
     np.concatenate([org, d], axis=1).astype(np.float32).tofile(tmp_path / "rays.bin")
 
-    exe = str(tmp_path / "voxel_brushes_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "voxel_brushes_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe, str(depth), str(tmp_path / "rays.bin"), bmps[0], bmps[1], str(W), str(H), str(dig), str(build)],
-                         capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = run_cpp_main(tmp_path, "voxel_brushes_main", depth, tmp_path / "rays.bin", bmps[0], bmps[1], W, H, dig, build)
     m = re.search(r"rays=(\d+) unit_hits=(\d+) solid_before=(\d+) solid_dug=(\d+) solid_after=(\d+) nodes_after=(\d+) image_hash=([0-9a-f]{16})", out.stdout)
     assert m, out.stdout
     got = [int(g) for g in m.groups()[:6]] + [int(m.group(7), 16)]

@@ -2,33 +2,17 @@
 VoxelLabels).  The expected labelling is the numpy model of tests/components_model.py (held against a breadth-first search
 in tests/test_volume_components_host.py), or the analytic answer where a test says so.  Every comparison is exact: the
 number of components, every record, and the id at ALL S^3 coordinates plus a few outside the volume."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
 import components_model as model
 import flood_model
+from volume_support import Stream, all_coordinates, volume_of
 
 pytestmark = pytest.mark.gpu
 
 NONE = model.NO_COMPONENT
-
-
-def volume_of(vol, depth):
-    import cpuvoxelraycaster_amd as vrc
-    volume = vrc.VoxelVolume(depth)
-    xyz = np.argwhere(vol)
-    if len(xyz):
-        volume.setVoxels(xyz)
-    return volume
-
-
-def all_coordinates(S):
-    """(S^3 + 6, 3): every voxel in [x, y, z] order, then a few coordinates outside the volume"""
-    inside = np.indices((S, S, S)).reshape(3, -1).T
-    outside = [[S, 0, 0], [0, S, 0], [0, 0, S], [S + 7, S, S], [0xFFFFFFFF, 0, 0], [1, 0x80000000, 1]]
-    return np.concatenate([inside, np.array(outside, np.int64)]).astype(np.uint32)
 
 
 def check_labels(labels, ids, rec, what):
@@ -53,19 +37,6 @@ def check_case(vol, depth, connectivity, through_empty, what=None):
     volume.close()                                   # the snapshot outlives its medium
     check_labels(labels, ids, rec, what if what is not None else (depth, connectivity, through_empty))
     return labels, ids, rec
-
-
-class Stream:
-    def __enter__(self):
-        import cpuvoxelraycaster_amd as vrc
-        self.L = vrc.capi.load()
-        self.h = C.c_void_p()
-        vrc.capi.check(self.L.vrc_stream_create(0, C.byref(self.h)))
-        return self.h
-
-    def __exit__(self, *exc):
-        self.L.vrc_stream_synchronize(0, self.h)
-        self.L.vrc_stream_destroy(0, self.h)
 
 
 # ---- random volumes ---------------------------------------------------------------------------------------------

@@ -1,9 +1,7 @@
 """The contact mirror of the C++ host adapter (HipVoxelLabels::contacts) compiled with plain g++ against the C ABI and run on
 the GPU at 16^3: the three pieces of the rigid C++ test over a slab.  Every record the program prints must be the numpy
 model's."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,19 +9,13 @@ import pytest
 import components_model
 import contact_model as model
 import rigid_model
+from volume_support import run_cpp_main
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_contacts_match_the_model(built, tmp_path):
-    exe = str(tmp_path / "voxel_contacts_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "voxel_contacts_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    print(out.stdout.strip())
+    out = run_cpp_main(tmp_path, "voxel_contacts_main")
 
     S = 16
     debris = np.zeros((S, S, S), np.uint8)

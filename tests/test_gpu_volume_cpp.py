@@ -2,10 +2,11 @@
 C ABI and run on the GPU: setCell x N + commit + setScene must show the image the Python path renders."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
+
+from volume_support import run_cpp_main
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,13 +32,7 @@ def test_cpp_voxel_volume_matches_python_path(built, tmp_path):
                             [(S, 1, 1, 1), (1, S + 7, 1, 0)], np.c_[pit[:20], np.zeros(20, int)]]).astype(np.uint32)
     edits.tofile(tmp_path / "edits.bin")
 
-    exe = str(tmp_path / "voxel_volume_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", os.path.join(ROOT, "tests", "cpp", "voxel_volume_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe, str(depth), str(tmp_path / "edits.bin"), bmps[0], bmps[1], str(W), str(H), str(tmp_path / "out.rgba")],
-                         capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = run_cpp_main(tmp_path, "voxel_volume_main", depth, tmp_path / "edits.bin", bmps[0], bmps[1], W, H, tmp_path / "out.rgba", flags=())
     m = re.search(r"edits=(\d+) solid_before=(\d+) solid_after=(\d+) nodes_after=(\d+) changed=1 build_ms_positive=1", out.stdout)
     assert m, out.stdout
     got = np.fromfile(tmp_path / "out.rgba", np.uint8).reshape(H, W, 4)

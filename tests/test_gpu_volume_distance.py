@@ -2,32 +2,16 @@
 VoxelVolume.distanceField / VoxelDistance, dilate / erode / openShape / closeShape / hollow).  The expected field is the
 numpy model of tests/distance_model.py (held against the definition in tests/test_volume_distance_host.py), or the analytic
 answer where a test says so.  Every comparison is exact."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
 import distance_model as model
+from volume_support import Stream, all_coordinates, volume_of
 
 pytestmark = pytest.mark.gpu
 
 NONE = model.NONE
-
-
-def volume_of(vol, depth):
-    import cpuvoxelraycaster_amd as vrc
-    volume = vrc.VoxelVolume(depth)
-    xyz = np.argwhere(vol)
-    if len(xyz):
-        volume.setVoxels(xyz)
-    return volume
-
-
-def all_coordinates(S):
-    """(S^3 + 6, 3): every voxel in [x, y, z] order, then six coordinates outside the volume"""
-    inside = np.indices((S, S, S)).reshape(3, -1).T
-    outside = [[S, 0, 0], [0, S, 0], [0, 0, S], [S + 7, S, S], [0xFFFFFFFF, 0, 0], [1, 0x80000000, 1]]
-    return np.concatenate([inside, np.array(outside, np.int64)]).astype(np.uint32)
 
 
 def check_stats(field, D, features, what):
@@ -48,19 +32,6 @@ def check_field(field, D, features, what, with_at=True):
         assert (at[S ** 3:] == NONE).all(), what
     check_stats(field, D, features, what)
     assert field.bytes() == 4 * S ** 3 and field.depth == S.bit_length() - 1 and field.data_ptr() != 0
-
-
-class Stream:
-    def __enter__(self):
-        import cpuvoxelraycaster_amd as vrc
-        self.L = vrc.capi.load()
-        self.h = C.c_void_p()
-        vrc.capi.check(self.L.vrc_stream_create(0, C.byref(self.h)))
-        return self.h
-
-    def __exit__(self, *exc):
-        self.L.vrc_stream_synchronize(0, self.h)
-        self.L.vrc_stream_destroy(0, self.h)
 
 
 # ---- random volumes ---------------------------------------------------------------------------------------------

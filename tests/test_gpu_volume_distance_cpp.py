@@ -1,33 +1,25 @@
 """The distance field of the C++ host adapter (HipVoxelDistance, HipVoxelVolume::distanceField / dilate / erode / hollow)
 compiled with plain g++ against the C ABI and run on the GPU at 64^3: the two boxes, the voxel at the corner of one of them
 and the speck of the components program.  Every number the program prints must be the numpy model's."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import distance_model as model
+from volume_support import compile_cpp_main, run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def program(built, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("distance_cpp") / "voxel_distance_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "voxel_distance_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+    return compile_cpp_main(tmp_path_factory.mktemp("distance_cpp"), "voxel_distance_main")
 
 
 @pytest.mark.parametrize("to_empty,outside", [(False, False), (True, True)])
 def test_cpp_distance_matches_the_model(program, to_empty, outside):
-    out = subprocess.run([program, str(int(to_empty)), str(int(outside))], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    print(out.stdout.strip())
+    out = run_program(program, int(to_empty), int(outside))
 
     S = 64
     vol = np.zeros((S, S, S), np.uint8)

@@ -3,38 +3,16 @@ expected drops are the tick simulation of tests/fall_model.py (held against the 
 tests/test_volume_fall_host.py), the expected ids the labelling model's, or the analytic answer where a test says so.  Every
 comparison is exact: the offsets, the stats (all but `rounds`, which is bounded by 1 <= rounds <= C + 1) and every voxel of
 the placed volume."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
 import components_model
 import fall_model as model
+from volume_support import Stream, volume_of
 
 pytestmark = pytest.mark.gpu
 NONE = model.NONE
-
-
-def volume_of(vol, depth):
-    import cpuvoxelraycaster_amd as vrc
-    volume = vrc.VoxelVolume(depth)
-    xyz = np.argwhere(vol)
-    if len(xyz):
-        volume.setVoxels(xyz)
-    return volume
-
-
-class Stream:
-    def __enter__(self):
-        import cpuvoxelraycaster_amd as vrc
-        self.L = vrc.capi.load()
-        self.h = C.c_void_p()
-        vrc.capi.check(self.L.vrc_stream_create(0, C.byref(self.h)))
-        return self.h
-
-    def __exit__(self, *exc):
-        self.L.vrc_stream_synchronize(0, self.h)
-        self.L.vrc_stream_destroy(0, self.h)
 
 
 def check_fall(debris, fixed, connectivity, direction, limit=0, device_memory=False, through_empty=False, ids=None, what=None):

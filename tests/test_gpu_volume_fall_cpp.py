@@ -1,30 +1,22 @@
 """The falling pieces of the C++ host adapter (HipVoxelLabels::fall / place, HipVoxelVolume::dropLoose) compiled with plain
 g++ against the C ABI and run on the GPU at 16^3: a slab with a ledge, three loose boxes and a speck.  Every number the
 program prints must be the numpy model's."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import components_model
 import fall_model as model
+from volume_support import run_cpp_main
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DOWN = 2                                               # VRC_FACE_YN
 
 
 @pytest.mark.parametrize("connectivity,limit", [(6, 0), (26, 3)])
 def test_cpp_fall_matches_the_model(built, tmp_path, connectivity, limit):
-    exe = str(tmp_path / "voxel_fall_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "voxel_fall_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe, str(connectivity), str(limit)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    print(out.stdout.strip())
+    out = run_cpp_main(tmp_path, "voxel_fall_main", connectivity, limit)
 
     S = 16
     fixed = np.zeros((S, S, S), np.uint8)

@@ -8,37 +8,10 @@ import numpy as np
 import pytest
 
 import flood_model
-import oracle_lib as O
 import raygen
+from volume_support import Stream, committed, expected_nodes, same, volume_of
 
 pytestmark = pytest.mark.gpu
-
-
-def same(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
-def volume_of(vol, depth):
-    import cpuvoxelraycaster_amd as vrc
-    volume = vrc.VoxelVolume(depth)
-    xyz = np.argwhere(vol)
-    if len(xyz):
-        volume.setVoxels(xyz)
-    return volume
-
-
-def expected_nodes(vol, depth):
-    import cpuvoxelraycaster_amd as vrc
-    if depth <= 5:
-        return O.compile_voxels(depth, np.argwhere(vol))
-    return vrc.build_volume_lsvo(vol, depth)
-
-
-def committed(volume):
-    svo = volume.commit()
-    nodes = svo.downloadNodes()
-    svo.close()
-    return nodes
 
 
 def fill_boxes(vol, boxes):
@@ -54,19 +27,6 @@ def flood_and_check(region, medium, medium_np, seeds_np, connectivity, through_e
     assert np.array_equal(region.download(), want), what
     assert st.reached == int(want.sum(dtype=np.int64)) == region.solidCount(), what
     return want, st
-
-
-class Stream:
-    def __enter__(self):
-        import cpuvoxelraycaster_amd as vrc
-        self.L = vrc.capi.load()
-        self.h = C.c_void_p()
-        vrc.capi.check(self.L.vrc_stream_create(0, C.byref(self.h)))
-        return self.h
-
-    def __exit__(self, *exc):
-        self.L.vrc_stream_synchronize(0, self.h)
-        self.L.vrc_stream_destroy(0, self.h)
 
 
 # ---- random volumes ---------------------------------------------------------------------------------------------

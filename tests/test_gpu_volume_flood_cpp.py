@@ -1,25 +1,16 @@
 """The flood of the C++ host adapter (HipVoxelVolume::flood / keepConnected) compiled with plain g++ against the C ABI and run
 on the GPU at 128^3: cast -> dig at hits -> flood of the air -> keepConnected -> commit -> setScene -> frame must give the
 counts and the image the same sequence gives through the Python VoxelVolume, and the counts of the numpy model."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import flood_model
 import raygen
+from volume_support import fnv1a, run_cpp_main
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def fnv1a(data):
-    h = 1469598103934665603
-    for b in data:
-        h = ((h ^ b) * 1099511628211) & 0xffffffffffffffff
-    return h
 
 
 @pytest.mark.parametrize("connectivity", [6, 26])
@@ -29,13 +20,7 @@ def test_cpp_flood_matches_python_path_and_model(built, tmp_path, connectivity):
     org, d = raygen.camera_rays(depth, 48, 27, -0.5)
     np.concatenate([org, d], axis=1).astype(np.float32).tofile(tmp_path / "rays.bin")
 
-    exe = str(tmp_path / "voxel_flood_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "voxel_flood_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe, str(depth), str(tmp_path / "rays.bin"), str(W), str(H), str(dig), str(connectivity)],
-                         capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = run_cpp_main(tmp_path, "voxel_flood_main", depth, tmp_path / "rays.bin", W, H, dig, connectivity)
     m = re.search(r"rays=(\d+) solid_dug=(\d+) air=(\d+) air_converged=(\d+) supported=(\d+) debris=(\d+) nodes_after=(\d+) image_hash=([0-9a-f]{16})", out.stdout)
     assert m, out.stdout
     got = [int(g) for g in m.groups()[:7]] + [int(m.group(8), 16)]

@@ -1,26 +1,19 @@
 """The fracture mirror of the C++ host adapter (HipVoxelVolume::fracture, HipVoxelLabels::pieceSites) compiled with plain g++
 against the C ABI and run on the GPU at 64^3: a wall on a slab broken round five sites.  Every record and every piece's cell
 the program prints must be the numpy model's."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import fracture_model as model
+from volume_support import run_cpp_main
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_fracture_matches_the_model(built, tmp_path):
-    exe = str(tmp_path / "voxel_fracture_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "voxel_fracture_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = run_cpp_main(tmp_path, "voxel_fracture_main")
 
     S = 64
     world = np.zeros((S, S, S), np.uint8)

@@ -5,7 +5,6 @@ lanes take a second word; and the box and sphere lists under split_for.  The cas
 they reach are tests/large_volume_cases.py's, held to their conditions in tests/test_volume_large_cases_host.py.  The
 expected values come from numpy (components_model, stamp_model, slices), never from another GPU result, and every
 comparison is exact."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import components_model
 import large_volume_cases as cases
 import rigid_model
 import stamp_model
+from volume_support import Stream, volume_of
 
 pytestmark = pytest.mark.gpu
 NONE = cases.NONE
@@ -25,33 +25,11 @@ def apply(volume, edits):
     return volume
 
 
-def volume_of(vol):
-    import cpuvoxelraycaster_amd as vrc
-    volume = vrc.VoxelVolume(vol.shape[0].bit_length() - 1)
-    xyz = np.argwhere(vol)
-    if len(xyz):
-        volume.setVoxels(xyz)
-    return volume
-
-
 def same(got, want, what):
     """np.array_equal, with the first few differing coordinates in the message"""
     if not np.array_equal(got, want):
         where = np.argwhere(got != want)
         raise AssertionError("%s: %d voxels differ, the first at %s" % (what, len(where), where[:5].tolist()))
-
-
-class Stream:
-    def __enter__(self):
-        import cpuvoxelraycaster_amd as vrc
-        self.L = vrc.capi.load()
-        self.h = C.c_void_p()
-        vrc.capi.check(self.L.vrc_stream_create(0, C.byref(self.h)))
-        return self.h
-
-    def __exit__(self, *exc):
-        self.L.vrc_stream_synchronize(0, self.h)
-        self.L.vrc_stream_destroy(0, self.h)
 
 
 # ---- 1. the labelling at 256^3 ------------------------------------------------------------------------------------------

@@ -13,48 +13,10 @@ import contact_model
 import pair_contact_model
 import posed_cases as cases
 import rigid_model
+from volume_support import Stream, affine_records, differing, tuples, volume_of
 
 pytestmark = pytest.mark.gpu
 S = 128
-
-
-def volume_of(vol, depth=None):
-    import cpuvoxelraycaster_amd as vrc
-    volume = vrc.VoxelVolume(vol.shape[0].bit_length() - 1 if depth is None else depth)
-    xyz = np.argwhere(vol)
-    if len(xyz):
-        volume.setVoxels(xyz)
-    return volume
-
-
-class Stream:
-    def __enter__(self):
-        import cpuvoxelraycaster_amd as vrc
-        self.L = vrc.capi.load()
-        self.h = C.c_void_p()
-        vrc.capi.check(self.L.vrc_stream_create(0, C.byref(self.h)))
-        return self.h
-
-    def __exit__(self, *exc):
-        self.L.vrc_stream_synchronize(0, self.h)
-        self.L.vrc_stream_destroy(0, self.h)
-
-
-def affine_records(maps):
-    import cpuvoxelraycaster_amd as vrc
-    out = np.zeros(len(maps), vrc.capi.AFFINE_DTYPE)
-    for i, (m, t) in enumerate(maps):
-        out[i] = (m, 0, t)
-    return out
-
-
-def tuples(records):
-    return [contact_model.record_tuple(r) for r in records]
-
-
-def differing(got, want):
-    """the first few records that differ, for the assertion's message"""
-    return [(i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != w][:3]
 
 
 def labelled(case):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import rect_model as R
+from volume_support import Stream, volume_of
 
 pytestmark = pytest.mark.gpu
 SENTINEL = 0x5A5A5A5A
@@ -30,15 +31,6 @@ def model_rects(depth, density, closed):
     r = R.rects(random_field(depth, density), closed)
     r.setflags(write=False)
     return r
-
-
-def volume_of(V):
-    import cpuvoxelraycaster_amd as vrc
-    depth = int(V.shape[0]).bit_length() - 1
-    volume = vrc.VoxelVolume(depth)
-    if V.any():
-        volume.setVoxels(np.argwhere(V))
-    return volume
 
 
 def block_bytes(depth):
@@ -73,19 +65,6 @@ def check_volume(volume, V, what, rects_of=None):
         assert got.dtype == np.uint32 and got.shape == want.shape and np.array_equal(got, want), (what, closed)
         tris = volume.rectTriangles(closed)
         assert tris.dtype == np.int32 and np.array_equal(tris, R.triangles(want)), (what, closed)
-
-
-class Stream:
-    def __enter__(self):
-        import cpuvoxelraycaster_amd as vrc
-        self.L = vrc.capi.load()
-        self.h = C.c_void_p()
-        vrc.capi.check(self.L.vrc_stream_create(0, C.byref(self.h)))
-        return self.h
-
-    def __exit__(self, *exc):
-        self.L.vrc_stream_synchronize(0, self.h)
-        self.L.vrc_stream_destroy(0, self.h)
 
 
 # ---- random fields at every depth with a path of its own ------------------------------------------------------------

@@ -2,30 +2,23 @@
 toObj(merged)) compiled with plain g++ against the C ABI and run on the GPU at 32^3: a sphere, a box on two walls and a
 carved slot.  The records, the triangles and the OBJ file equal the numpy model's (tests/rect_model.py), and the triangles
 voxelised back with xorMesh give the same volume."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import rect_model as R
 import surface_model as F
+from volume_support import run_cpp_main
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_rects_round_trip_and_obj(built, tmp_path):
     import cpuvoxelraycaster_amd as vrc
     depth, S = 5, 32
-    exe = str(tmp_path / "voxel_rects_main")
     obj = tmp_path / "world.obj"
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "voxel_rects_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe, str(depth), str(obj)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = run_cpp_main(tmp_path, "voxel_rects_main", depth, obj)
     head, rect_line, tri_line = out.stdout.splitlines()
     print(head)
     m = re.search(r"solid=(\d+) back=(\d+) differ=(\d+) total=(\d+) open=(\d+) faces=(\d+) rects=(\d+) triangles=(\d+) window=(\d+) obj_faces=(\d+)", head)

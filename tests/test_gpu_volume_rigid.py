@@ -2,7 +2,6 @@
 VoxelLabels.moments / massProperties / poses / placeAffine).  The expected values are the numpy model's (tests/rigid_model.py,
 held against hand-written cases and the fall model in tests/test_volume_rigid_host.py), closed forms where a test says so,
 and the library's own vrc_fall_place / vrc_volume_stamp_affine where the calls must agree.  Every comparison is exact."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -11,46 +10,10 @@ import components_model
 import fall_model
 import rigid_model as model
 import stamp_model
+from volume_support import Stream, affine_records, labels_of, volume_of
 
 pytestmark = pytest.mark.gpu
 NONE = model.NONE
-
-
-def volume_of(vol, depth=None):
-    import cpuvoxelraycaster_amd as vrc
-    volume = vrc.VoxelVolume(vol.shape[0].bit_length() - 1 if depth is None else depth)
-    xyz = np.argwhere(vol)
-    if len(xyz):
-        volume.setVoxels(xyz)
-    return volume
-
-
-def labels_of(vol, connectivity=6, through_empty=False):
-    medium = volume_of(vol)
-    labels = medium.labelComponents(connectivity, through_empty)
-    medium.close()
-    return labels
-
-
-class Stream:
-    def __enter__(self):
-        import cpuvoxelraycaster_amd as vrc
-        self.L = vrc.capi.load()
-        self.h = C.c_void_p()
-        vrc.capi.check(self.L.vrc_stream_create(0, C.byref(self.h)))
-        return self.h
-
-    def __exit__(self, *exc):
-        self.L.vrc_stream_synchronize(0, self.h)
-        self.L.vrc_stream_destroy(0, self.h)
-
-
-def affine_records(maps):
-    import cpuvoxelraycaster_amd as vrc
-    out = np.zeros(len(maps), vrc.capi.AFFINE_DTYPE)
-    for i, (m, t) in enumerate(maps):
-        out[i] = (m, 0, t)
-    return out
 
 
 # ---- moments -----------------------------------------------------------------------------------------------------

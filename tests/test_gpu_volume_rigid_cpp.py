@@ -1,28 +1,20 @@
 """The rigid-piece mirrors of the C++ host adapter (HipVoxelLabels::moments / massProperties / poses / placeAffine) compiled
 with plain g++ against the C ABI and run on the GPU at 16^3: two boxes, one with an arm, and a speck.  Every number the
 program prints must be the numpy model's."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import components_model
 import rigid_model as model
+from volume_support import run_cpp_main
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_rigid_matches_the_model(built, tmp_path):
-    exe = str(tmp_path / "voxel_rigid_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "voxel_rigid_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    print(out.stdout.strip())
+    out = run_cpp_main(tmp_path, "voxel_rigid_main")
 
     S = 16
     debris = np.zeros((S, S, S), np.uint8)

@@ -3,7 +3,6 @@ it can go wrong: the workgroup sum with idle lanes and idle waves, the two ways 
 on either side of the shared-word rule, and the staged call with a block that has to grow and on a stream of its own behind
 a device-memory edit, with every combination of optional parts in a block of the call's own, and with a part that goes up
 and comes back.  Every expectation is NumPy's (the models of tests/*_model.py); every comparison is exact."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -17,6 +16,7 @@ import rigid_model
 import stamp_model
 import surface_model
 import travel_model
+from volume_support import Stream, affine_records, volume_of
 
 pytestmark = pytest.mark.gpu
 
@@ -28,31 +28,10 @@ def random_volume(seed, depth, density):
     return (np.random.default_rng(seed).random((S, S, S)) < density).astype(np.uint8)
 
 
-def volume_of(vol):
-    import cpuvoxelraycaster_amd as vrc
-    volume = vrc.VoxelVolume(int(vol.shape[0]).bit_length() - 1)
-    if vol.any():
-        volume.setVoxels(np.argwhere(vol))
-    return volume
-
-
 def apply(dst, K, op):
     if op == stamp_model.REPLACE:
         return (K != 0).astype(np.uint8)
     return (dst | K if op == stamp_model.OR else dst & (1 - K)).astype(np.uint8)
-
-
-class Stream:
-    def __enter__(self):
-        import cpuvoxelraycaster_amd as vrc
-        self.L = vrc.capi.load()
-        self.h = C.c_void_p()
-        vrc.capi.check(self.L.vrc_stream_create(0, C.byref(self.h)))
-        return self.h
-
-    def __exit__(self, *exc):
-        self.L.vrc_stream_synchronize(0, self.h)
-        self.L.vrc_stream_destroy(0, self.h)
 
 
 @pytest.mark.parametrize("depth", [2, 4, 5])
@@ -268,14 +247,6 @@ def piece_case():
     for a in (vol, offsets, boxes, keep, base, world):
         a.setflags(write=False)
     return vol, offsets, maps, boxes, keep, base, world, want
-
-
-def affine_records(maps):
-    import cpuvoxelraycaster_amd as vrc
-    out = np.zeros(len(maps), vrc.capi.AFFINE_DTYPE)
-    for i, (m, t) in enumerate(maps):
-        out[i] = (m, 0, t)
-    return out
 
 
 def device_bytes(a):

@@ -2,25 +2,16 @@
 volume is the numpy model of tests/stamp_model.py (held against the definition in tests/test_volume_stamp_host.py), or
 np.transpose / np.flip / vrc_volume_copy_region where a test says so.  Every comparison is np.array_equal on
 vrc_volume_download: there are no tolerances."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
 import stamp_model as model
+from volume_support import Stream, volume_of
 
 pytestmark = pytest.mark.gpu
 
 OPS = (model.REPLACE, model.OR, model.ANDNOT)
-
-
-def volume_of(vol, depth):
-    import cpuvoxelraycaster_amd as vrc
-    volume = vrc.VoxelVolume(depth)
-    xyz = np.argwhere(vol)
-    if len(xyz):
-        volume.setVoxels(xyz)
-    return volume
 
 
 def random_volume(rng, depth, density):
@@ -235,19 +226,6 @@ def test_depths_differ(built, src_depth, dst_depth):
 
 
 # ---- ordering -------------------------------------------------------------------------------------------------------
-
-class Stream:
-    def __enter__(self):
-        import cpuvoxelraycaster_amd as vrc
-        self.L = vrc.capi.load()
-        self.h = C.c_void_p()
-        vrc.capi.check(self.L.vrc_stream_create(0, C.byref(self.h)))
-        return self.h
-
-    def __exit__(self, *exc):
-        self.L.vrc_stream_synchronize(0, self.h)
-        self.L.vrc_stream_destroy(0, self.h)
-
 
 def test_stream_order_behind_device_memory_edits(built):
     """an asynchronous fill_boxes on src and one on dst, then the stamp, all on one created stream with no host

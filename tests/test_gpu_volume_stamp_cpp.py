@@ -2,26 +2,20 @@
 ABI and run on the GPU at 64^3: the two boxes, the voxel at the corner of one of them and the speck of the distance program,
 turned a quarter turn and back, then placed with a 30-degree turn about two axes at scale 1.5 in a 128^3 world.  Every
 solid count, every probe voxel and the placement's map the program prints must be the numpy model's."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import stamp_model as model
+from volume_support import compile_cpp_main, run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def program(built, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("stamp_cpp") / "voxel_stamp_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "voxel_stamp_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+    return compile_cpp_main(tmp_path_factory.mktemp("stamp_cpp"), "voxel_stamp_main")
 
 
 def bits_at(vol, probes):
@@ -29,9 +23,7 @@ def bits_at(vol, probes):
 
 
 def test_cpp_stamp_matches_the_model(program):
-    out = subprocess.run([program], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    print(out.stdout.strip())
+    out = run_program(program)
 
     S = 64
     vol = np.zeros((S, S, S), np.uint8)

@@ -2,30 +2,22 @@
 compiled with plain g++ against the C ABI and run on the GPU at 64^3: two spheres and a carved box; the triangles voxelised
 back with xorMesh give the same volume (the XOR of both counts 0 voxels), the figures equal the numpy model's and the OBJ
 file holds one `f` line per face and one `v` line per distinct corner."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import surface_model as F
+from volume_support import run_cpp_main
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_surface_round_trip_and_obj(built, tmp_path):
     import cpuvoxelraycaster_amd as vrc
     depth, S = 6, 64
-    exe = str(tmp_path / "voxel_surface_main")
     obj = tmp_path / "world.obj"
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "voxel_surface_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe, str(depth), str(obj)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    print(out.stdout.strip())
+    out = run_cpp_main(tmp_path, "voxel_surface_main", depth, obj)
     m = re.search(r"solid=(\d+) back=(\d+) differ=(\d+) total=(\d+) open=(\d+) faces=(\d+) triangles=(\d+) window=(\d+) obj_faces=(\d+)", out.stdout)
     assert m, out.stdout
     solid, back, differ, total, open_total, n_faces, n_tris, window, obj_faces = (int(g) for g in m.groups())

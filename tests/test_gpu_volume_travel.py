@@ -3,34 +3,18 @@ reachableWithin / shortestPath, VoxelDistance.tracePaths).  The expected field i
 tests/travel_model.py (held against the definition in tests/test_volume_travel_host.py), or the analytic answer where a
 test says so.  Every comparison is exact.  The device works in tiles of 16^3 voxels: depth 4 is one tile, depth 5 two per
 axis, depth 6 four per axis -- the smallest with a tile that has all 26 neighbours."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
 import travel_model as model
+from volume_support import Stream, all_coordinates, volume_of
 
 pytestmark = pytest.mark.gpu
 
 NONE = model.NONE
 TILE = 16
 TRIP_BOUND = 64          # iterations of a tile in one sweep (csrc/vrc_travel.hip: TRAVEL_TILE_ITERS)
-
-
-def volume_of(vol, depth):
-    import cpuvoxelraycaster_amd as vrc
-    volume = vrc.VoxelVolume(depth)
-    xyz = np.argwhere(vol)
-    if len(xyz):
-        volume.setVoxels(xyz)
-    return volume
-
-
-def all_coordinates(S):
-    """(S^3 + 6, 3): every voxel in [x, y, z] order, then six coordinates outside the volume"""
-    inside = np.indices((S, S, S)).reshape(3, -1).T
-    outside = [[S, 0, 0], [0, S, 0], [0, 0, S], [S + 7, S, S], [0xFFFFFFFF, 0, 0], [1, 0x80000000, 1]]
-    return np.concatenate([inside, np.array(outside, np.int64)]).astype(np.uint32)
 
 
 def check_field(field, T, n_seeds, connectivity, what, step_limit=0, with_at=True, tight=False):
@@ -76,19 +60,6 @@ def random_seeds(rng, S, count):
     for x, y, z in rng.integers(0, S, (count, 3)):
         seeds[x, y, z] = 1
     return seeds
-
-
-class Stream:
-    def __enter__(self):
-        import cpuvoxelraycaster_amd as vrc
-        self.L = vrc.capi.load()
-        self.h = C.c_void_p()
-        vrc.capi.check(self.L.vrc_stream_create(0, C.byref(self.h)))
-        return self.h
-
-    def __exit__(self, *exc):
-        self.L.vrc_stream_synchronize(0, self.h)
-        self.L.vrc_stream_destroy(0, self.h)
 
 
 # ---- random volumes ---------------------------------------------------------------------------------------------

@@ -1,33 +1,25 @@
 """The travel-distance field of the C++ host adapter (HipVoxelVolume::travelField, HipVoxelDistance::tracePaths /
 connectivity / travelStats) compiled with plain g++ against the C ABI and run on the GPU at 16^3: a corridor with a side
 room, a speck nothing reaches and a seed outside M.  Every number the program prints must be the breadth-first model's."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import travel_model as model
+from volume_support import compile_cpp_main, run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def program(built, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("travel_cpp") / "voxel_travel_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "voxel_travel_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+    return compile_cpp_main(tmp_path_factory.mktemp("travel_cpp"), "voxel_travel_main")
 
 
 @pytest.mark.parametrize("connectivity", [6, 26])
 def test_cpp_travel_matches_the_model(program, connectivity):
-    out = subprocess.run([program, str(connectivity)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    print(out.stdout.strip())
+    out = run_program(program, connectivity)
 
     S = 16
     vol = np.zeros((S, S, S), np.uint8)

@@ -3,19 +3,15 @@ The expected occupancy is the numpy model of tests/voxelize_model.py (held again
 test in tests/test_volume_voxelize_host.py); every comparison is exact: the downloaded volume equals the model's array.
 Shapes are the smallest at which the kernels take another path: 4^3 (two brick rows to a word), 8^3 (one z word per
 column), 32^3 (four), 64^3 (more than one workgroup in the scan, a triangle split over several workgroups in the mark)."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
 import voxelize_model as M
+from volume_support import Stream, same
 
 pytestmark = pytest.mark.gpu
 U = M.UNIT
-
-
-def same(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
 def voxelised(depth, tris, before=None):
@@ -60,19 +56,6 @@ def sheet(x0, y0, x1, y1, h):
     """an open horizontal rectangle [x0, x1] x [y0, y1] (voxels) at height h (units): two triangles"""
     a, b, c, d = (x0 * U, y0 * U, h), (x1 * U, y0 * U, h), (x1 * U, y1 * U, h), (x0 * U, y1 * U, h)
     return np.array([a + b + c, a + c + d], np.int32)
-
-
-class Stream:
-    def __enter__(self):
-        import cpuvoxelraycaster_amd as vrc
-        self.L = vrc.capi.load()
-        self.h = C.c_void_p()
-        vrc.capi.check(self.L.vrc_stream_create(0, C.byref(self.h)))
-        return self.h
-
-    def __exit__(self, *exc):
-        self.L.vrc_stream_synchronize(0, self.h)
-        self.L.vrc_stream_destroy(0, self.h)
 
 
 # ---- closed meshes at every depth with a path of its own -----------------------------------------------------------

@@ -1,15 +1,12 @@
 """The mesh voxelisation of the C++ host adapter (HipVoxelVolume::xorMesh / voxelizeMesh / stampMesh) compiled with plain g++
 against the C ABI and run on the GPU at 64^3: the three occupancies it writes equal the numpy model's, bit for bit."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import voxelize_model as M
+from volume_support import run_cpp_main
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_mesh_methods_match_the_model(built, tmp_path):
@@ -25,14 +22,8 @@ def test_cpp_mesh_methods_match_the_model(built, tmp_path):
     faces.astype(np.uint32).tofile(tmp_path / "faces.bin")
     tris.tofile(tmp_path / "tris.bin")
 
-    exe = str(tmp_path / "voxel_mesh_main")
-    libdir = os.path.join(ROOT, "cpuvoxelraycaster_amd")
-    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "voxel_mesh_main.cpp"),
-                           "-o", exe, "-L" + libdir, "-l:libvrc_hip.so", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe, str(depth), str(tmp_path / "verts.bin"), str(tmp_path / "faces.bin"), str(tmp_path / "tris.bin"),
-                          repr(scale), repr(off[0]), repr(off[1]), repr(off[2]), str(tmp_path / "out")], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    print(out.stdout.strip())
+    out = run_cpp_main(tmp_path, "voxel_mesh_main", depth, tmp_path / "verts.bin", tmp_path / "faces.bin", tmp_path / "tris.bin",
+                       repr(scale), repr(off[0]), repr(off[1]), repr(off[2]), tmp_path / "out")
 
     def got(name):
         return np.fromfile(tmp_path / f"out_{name}.bin", np.uint8).reshape(S, S, S)

@@ -3,9 +3,10 @@ volume is refused with VRC_ERR_INVALID before any HIP call, and the C++ host ada
 compiles under a plain C++14 compiler."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from volume_support import check_cpp_syntax
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -66,6 +67,6 @@ def test_host_adapter_with_brush_members_compiles(built):
            '    std::vector<uint64_t> counts = undo->countBoxes({0, 0, 0, 8, 8, 8});\n'
            '    (void)solid; (void)counts;\n'
            '}\nint main(){ return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src, strict=True)
     main = os.path.join(ROOT, "tests", "cpp", "voxel_brushes_main.cpp")
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", main], check=True)
+    check_cpp_syntax(main, strict=True)

@@ -3,13 +3,13 @@ adapter with HipVoxelLabels under a plain C++14 compiler, and the yardstick of t
 tests/components_model.py against a plain breadth-first search that visits the voxels in key order."""
 import ctypes as C
 import os
-import subprocess
 from collections import deque
 
 import numpy as np
 import pytest
 
 import components_model as model
+from volume_support import check_cpp_syntax
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -169,4 +169,4 @@ def test_host_adapter_with_labels_compiles(built):
            '    return world.removeSmallPieces(8) + records.size() + ids[0] + labels.bytes();\n'
            '}\n'
            'int main() { return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src, strict=True)

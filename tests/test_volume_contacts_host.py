@@ -3,7 +3,6 @@ cases written out by hand and against rigid_model.place_affine, the cases of the
 record's layout, every refusal that is decided before the first HIP call, and the arithmetic of contact_properties."""
 import ctypes as C
 import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -14,6 +13,7 @@ import contact_model as model
 import fall_model
 import rigid_model
 import stamp_model
+from volume_support import check_cpp_syntax
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NONE = model.NONE
@@ -122,7 +122,7 @@ def test_struct_layout(built):
            'static_assert(sizeof(vrc_piece_contact) == 128 && offsetof(vrc_piece_contact, overlap_s1) == 16 && offsetof(vrc_piece_contact, overlap_n) == 40 &&'
            ' offsetof(vrc_piece_contact, touch) == 64 && offsetof(vrc_piece_contact, touch_n) == 96 && offsetof(vrc_piece_contact, reserved) == 120, "contact");\n'
            ) % os.path.join(ROOT, "include", "vrc.h")
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src)
 
 
 # ---- refusals ------------------------------------------------------------------------------------------------------
@@ -198,7 +198,7 @@ def test_host_adapter_with_contacts_compiles(built):
            '    return all[0].overlap + some[0].touch;\n'
            '}\n'
            'int main() { return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src, strict=True)
 
 
 # ---- contact_properties --------------------------------------------------------------------------------------------

@@ -4,12 +4,12 @@ of tests/distance_model.py against the definition taken literally (a brute-force
 wall term)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import distance_model as model
+from volume_support import check_cpp_syntax
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -79,7 +79,7 @@ def test_distance_stats_layout(built):
     assert capi.VRC_DISTANCE_NONE == model.NONE == 0xFFFFFFFF
     hdr = os.path.join(ROOT, "include", "vrc.h")
     src = '#include "%s"\nstatic_assert(sizeof(vrc_distance_stats) == 32, "vrc_distance_stats");\nint main() { return 0; }\n' % hdr
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src)
 
 
 def test_distance_refusals_need_no_gpu(built):
@@ -161,4 +161,4 @@ def test_host_adapter_with_distance_compiles(built):
            '    return stats.features + stats.max_d2 + d2[0] + all.size() + field.bytes() + field.depth() + (field.data() != nullptr);\n'
            '}\n'
            'int main() { return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src, strict=True)

@@ -4,13 +4,13 @@ the case generators of the GPU tests under the model alone, the refusals that ne
 the C++ host adapter under a plain C++14 compiler."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import components_model
 import fall_model as model
+from volume_support import check_cpp_syntax
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NONE = model.NONE
@@ -244,4 +244,4 @@ def test_host_adapter_with_fall_compiles(built):
            '    return st.moved_voxels + dropped.moved_pieces + labels.fall(nullptr, VRC_FACE_ZP).size();\n'
            '}\n'
            'int main() { return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src, strict=True)

@@ -3,13 +3,13 @@ HipVoxelVolume::flood / keepConnected under a plain C++14 compiler, and the yard
 numpy model of tests/flood_model.py against a plain breadth-first search."""
 import ctypes as C
 import os
-import subprocess
 from collections import deque
 
 import numpy as np
 import pytest
 
 import flood_model
+from volume_support import check_cpp_syntax
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -52,9 +52,9 @@ def test_host_adapter_with_flood_compiles(built):
            '    std::unique_ptr<vrc_host::HipVoxelVolume> more = world.keepConnected({0, 0, 0, 8, 1, 8}, VRC_CONNECT_ALL);\n'
            '    return a.reached + b.sweeps + b.converged + debris->solidCount() + more->solidCount();\n'
            '}\nint main(){ return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src, strict=True)
     main = os.path.join(ROOT, "tests", "cpp", "voxel_flood_main.cpp")
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", main], check=True)
+    check_cpp_syntax(main, strict=True)
 
 
 def bfs(M, seeds, connectivity):

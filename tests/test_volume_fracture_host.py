@@ -3,7 +3,6 @@ literal per-voxel, per-site loop and against a breadth-first search --, its redu
 that need no device, scatter_sites, and the C++ host adapter under a plain C++14 compiler."""
 import ctypes as C
 import os
-import subprocess
 from collections import deque
 
 import numpy as np
@@ -11,6 +10,7 @@ import pytest
 
 import components_model
 import fracture_model as model
+from volume_support import check_cpp_syntax
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NONE = model.NONE
@@ -198,4 +198,4 @@ def test_host_adapter_with_fracture_compiles(built):
            '    return cells.size() + all.pieceSites(1, 2).size() + shards.count();\n'
            '}\n'
            'int main() { return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src, strict=True)

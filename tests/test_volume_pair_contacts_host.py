@@ -4,7 +4,6 @@ contact_model.contacts where the two rules agree, the cases of the GPU tests aga
 is decided before the first HIP call."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import contact_model
 import pair_contact_model as model
 import rigid_model
 import stamp_model
+from volume_support import check_cpp_syntax
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDENTITY = (list(stamp_model.IDENTITY[0]), [0, 0, 0])
@@ -233,4 +233,4 @@ def test_host_adapter_with_pair_contacts_compiles(built):
            '    return all[0].overlap + some[0].touch;\n'
            '}\n'
            'int main() { return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src, strict=True)

@@ -4,7 +4,6 @@ scanning outwards), the exact single cover of every face mask, and, through the 
 packing, the merged quad mesh, the refusals that need no device and the C++ host adapter under a plain C++14 compiler."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import pytest
 import rect_model as R
 import surface_model as F
 import voxelize_model as M
+from volume_support import check_cpp_syntax
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -262,6 +262,6 @@ def test_host_adapter_with_rects_compiles(built):
            '    world.extractRectsDevice(VRC_SURFACE_FACES, 0, 100, dev, nullptr, false, nullptr);\n'
            '    return counts[VRC_FACE_ZP] + rects.size() + tris.size() + world.toObj("world.obj", true, true) + world.toObj("open.obj", false);\n'
            '}\nint main(){ return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src, strict=True)
     main = os.path.join(ROOT, "tests", "cpp", "voxel_rects_main.cpp")
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", main], check=True)
+    check_cpp_syntax(main, strict=True)

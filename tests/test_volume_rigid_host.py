@@ -4,7 +4,6 @@ against vrc_affine_place and the model, every refusal that is decided before the
 mass_properties against exact fractions."""
 import ctypes as C
 import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -14,6 +13,7 @@ import components_model
 import fall_model
 import rigid_model as model
 import stamp_model
+from volume_support import check_cpp_syntax
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NONE = model.NONE
@@ -234,7 +234,7 @@ def test_struct_sizes(built):
     src = ('#include "%s"\n#include <stddef.h>\n'
            'static_assert(sizeof(vrc_piece_moments) == 80 && offsetof(vrc_piece_moments, s1) == 8 && offsetof(vrc_piece_moments, s2) == 32, "moments");\n'
            'static_assert(sizeof(vrc_affine) == 64, "affine");\n') % os.path.join(ROOT, "include", "vrc.h")
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src)
 
 
 # ---- mass properties -----------------------------------------------------------------------------------------------
@@ -297,4 +297,4 @@ def test_host_adapter_with_rigid_compiles(built):
            '    return mo.size() + (uint64_t)mp[0].mass + labels.moments(1, 2).size();\n'
            '}\n'
            'int main() { return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src, strict=True)

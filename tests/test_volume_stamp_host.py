@@ -4,13 +4,13 @@ np.transpose / np.flip on the 48 signed permutations --, the map record's size, 
 vrc_affine_place by its properties, and the C++ host adapter's new members under a plain C++14 compiler."""
 import ctypes as C
 import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
 import stamp_model as model
+from volume_support import check_cpp_syntax
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -123,7 +123,7 @@ def test_affine_layout(built):
     hdr = os.path.join(ROOT, "include", "vrc.h")
     src = ('#include "%s"\nstatic_assert(sizeof(vrc_affine) == 64, "vrc_affine");\n'
            'static_assert(VRC_AFFINE_FRAC_BITS == 16, "VRC_AFFINE_FRAC_BITS");\nint main() { return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src)
 
 
 def test_stamp_refusals_need_no_gpu(built):
@@ -292,6 +292,6 @@ def test_host_adapter_with_stamp_compiles(built):
            '    return world.stampPlaced(clipboard, rot, 1.5f, pivot, pivot, VRC_COPY_REPLACE, nullptr);\n'
            '}\n'
            'int main() { return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src, strict=True)
     main = os.path.join(ROOT, "tests", "cpp", "voxel_stamp_main.cpp")
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", main], check=True)
+    check_cpp_syntax(main, strict=True)

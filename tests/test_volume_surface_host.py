@@ -4,13 +4,13 @@ faces of a voxel set are a closed mesh whose solid voxelisation is the voxel set
 refusals that need no device and the C++ host adapter under a plain C++14 compiler."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import surface_model as F
 import voxelize_model as M
+from volume_support import check_cpp_syntax
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -192,6 +192,6 @@ def test_host_adapter_with_surface_compiles(built):
            '    world.extractSurfaceDevice(VRC_SURFACE_FACES, 0, 100, dev, nullptr, false, nullptr);\n'
            '    return counts[VRC_FACE_ZP] + faces.size() + tris.size() + world.toObj("world.obj") + world.toObj("open.obj", false);\n'
            '}\nint main(){ return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src, strict=True)
     main = os.path.join(ROOT, "tests", "cpp", "voxel_surface_main.cpp")
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", main], check=True)
+    check_cpp_syntax(main, strict=True)

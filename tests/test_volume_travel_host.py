@@ -4,12 +4,12 @@ neighbour lists, a different algorithm) --, the refusals that need no device, th
 adapter with travelField / tracePaths under a plain C++14 compiler."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import travel_model as model
+from volume_support import check_cpp_syntax
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NONE = model.NONE
@@ -112,7 +112,7 @@ def test_travel_stats_layout(built):
     assert [getattr(capi.TravelStats, f).offset for f in ("seeds", "reached", "max_steps", "argmax", "sweeps", "reserved")] == [0, 8, 16, 20, 32, 36]
     hdr = os.path.join(ROOT, "include", "vrc.h")
     src = '#include "%s"\nstatic_assert(sizeof(vrc_travel_stats) == 40, "vrc_travel_stats");\nint main() { return 0; }\n' % hdr
-    subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src)
 
 
 def test_travel_refusals_need_no_gpu(built):
@@ -192,7 +192,7 @@ def test_host_adapter_with_travel_compiles(built):
            '    return stats.seeds + stats.reached + stats.max_steps + stats.sweeps + paths.size() + lengths[0] + field.connectivity() + self.depth();\n'
            '}\n'
            'int main() { return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src, strict=True)
 
 
 def test_travel_refusal_texts(built):

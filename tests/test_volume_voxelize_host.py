@@ -4,12 +4,12 @@ tetrahedra) --, the refusals that need no device, the quantisation of VoxelVolum
 C++ host adapter under a plain C++14 compiler."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import voxelize_model as M
+from volume_support import check_cpp_syntax
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -201,6 +201,6 @@ def test_host_adapter_with_mesh_compiles(built):
            '    world.stampMesh(verts, faces, VRC_COPY_ANDNOT, 2.0, 1.0, 2.0, 3.0);\n'
            '    return world.solidCount() + vrc_host::HipVoxelVolume::quantiseMesh(verts).size();\n'
            '}\nint main(){ return 0; }\n') % hdr
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", "-"], input=src.encode(), check=True)
+    check_cpp_syntax(src, strict=True)
     main = os.path.join(ROOT, "tests", "cpp", "voxel_mesh_main.cpp")
-    subprocess.run(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", main], check=True)
+    check_cpp_syntax(main, strict=True)
