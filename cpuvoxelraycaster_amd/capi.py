@@ -42,6 +42,11 @@ assert MOMENTS_DTYPE.itemsize == 80 and AFFINE_DTYPE.itemsize == 64
 CONTACT_DTYPE = np.dtype([("posed", "<u8"), ("overlap", "<u8"), ("overlap_s1", "<u8", 3), ("overlap_n", "<i8", 3),
                           ("touch", "<u8"), ("touch_s1", "<u8", 3), ("touch_n", "<i8", 3), ("reserved", "<u8")])
 assert CONTACT_DTYPE.itemsize == 128
+# vrc_piece_clearance (include/vrc.h): a field read at the voxels of a posed piece -- their count, how many hold
+# VRC_DISTANCE_NONE, the sum of the finite values, and the least and greatest one with the voxel that holds it
+CLEARANCE_DTYPE = np.dtype([("posed", "<u8"), ("none", "<u8"), ("sum", "<u8"), ("min_value", "<u4"), ("min_at", "<u4", 3),
+                            ("max_value", "<u4"), ("max_at", "<u4", 3), ("reserved", "<u8")])
+assert CLEARANCE_DTYPE.itemsize == 64
 
 
 class VrcError(RuntimeError):
@@ -210,6 +215,7 @@ SYMBOLS = {
     "vrc_rigid_place_affine": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     "vrc_rigid_contacts": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "vrc_rigid_pair_contacts": (_int, [_vp, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _int, _vp]),
+    "vrc_rigid_clearance": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "vrc_rigid_box_pair_count": (_int, [_vp, _vp, _vp, _u32, C.POINTER(_u64), _int, _vp]),
     "vrc_rigid_box_pairs": (_int, [_vp, _vp, _vp, _u32, _u64, _u64, _vp, _int, _vp]),
     "vrc_volume_distance_field": (_int, [_vp, _int, _int, C.POINTER(_vp), C.POINTER(DistanceStats)]),

@@ -47,6 +47,16 @@ hipError_t pair_contacts_run(const uint32_t* labels, const vrc_component* record
                              const vrc_affine* maps, const uint32_t* boxes, uint32_t posed_depth, uint64_t n_pairs, const uint32_t* pairs,
                              vrc_piece_contact* out, hipStream_t st);
 
+// out[i] = the clearance record (vrc.h: vrc_rigid_clearance) of piece i < pieces over `field` (8^field_depth uint32 values as
+// [(x*S + y)*S + z], only read): the voxels contacts_run would count as `posed` with the same keep, maps and boxes -- the one
+// gather again -- counted, and the field's values there summed, with their least and greatest finite value and the voxels of
+// smallest dense index that hold them.  Three kernels on `st`: one thread per record writes the reductions' identities, the
+// gather kernel of contacts_run's grid reduces into the records with 64-bit vector atomics (add, min, max), one thread per
+// record decodes the packed minimum and maximum in place.  A skipped piece gets the record of the empty set.  keep, maps,
+// boxes and out are DEVICE memory; no scratch.  pieces >= 1, field_depth in 2..10.
+hipError_t clearance_run(const uint32_t* labels, const vrc_component* records, uint64_t pieces, uint32_t depth, const uint8_t* keep,
+                         const vrc_affine* maps, const uint32_t* boxes, const uint32_t* field, uint32_t field_depth, vrc_piece_clearance* out, hipStream_t st);
+
 // The broad phase (vrc.h: vrc_rigid_box_pair_count / vrc_rigid_box_pairs): the ordered pairs (a, b), a != b, of kept pieces
 // whose boxes (pieces x 6, clipped to the posed volume; required) meet when one is grown by a voxel, ascending.  A thread per
 // a walks all b -- pieces^2 box tests, hence the limit on the pieces.  `slots` is the scratch of both calls,

@@ -1,5 +1,5 @@
 // vrc_rigid.hip -- the pieces of a labelling as rigid bodies with a pose (include/vrc.h: vrc_rigid_moments,
-// vrc_rigid_place_affine, vrc_rigid_contacts): the raw moments a physics engine derives mass, centre of mass and inertia
+// vrc_rigid_place_affine, vrc_rigid_contacts, vrc_rigid_clearance): the raw moments a physics engine derives mass, centre of mass and inertia
 // tensor from, the write-back of every piece through its own inverse affine map, and the contact record of every piece
 // under such a map against a world.  The labels are vrc_components.hip's: one uint32 id per KEY
 // (vrc_box_words.h: voxel_key / key_voxel), VRC_NO_COMPONENT outside M.  Exact in integers.
@@ -60,7 +60,21 @@
 // included), all their records in 0.81 ms (652 pairs overlap, 798 touch), next to 0.098 ms PER PAIR of clearing a scratch
 // volume, placing b and calling vrc_rigid_contacts for a (64 sampled pairs; 360 ms scaled to all, 445 times).  The passes have
 // not been timed apart.
+//
+// Clearance (vrc_rigid_clearance).  k_contacts with a dense uint32 field (a vrc_distance snapshot) for a world: a lane with
+// gathered bits walks them and loads the field at each -- up to 32 values in four runs of eight along z -- into a count, a
+// count of VRC_DISTANCE_NONE, a 64-bit sum, and a packed minimum (value << 32 | index) and maximum (value << 32 | ~index)
+// that carry the voxel of smallest dense index with them.  clearance_flush is contact_flush for these five: shuffles, LDS,
+// at most three atomic adds, one atomicMin and one atomicMax per workgroup and piece.  The record itself holds the two
+// packed words while the kernel runs; a kernel of one thread per record before it writes the identities and one after it
+// decodes them in place, so the call keeps no scratch.
+// Measured on the same scene over the Euclidean field of the supported part (tools/bench_edit.py --clearance,
+// profiles/edit/bench_clearance.json; A B A B with vrc_rigid_contacts against the supported part, same maps and boxes, same
+// run): translation maps 0.121 ms next to 0.109 ms of the contact call (1.11 times), the 30-degree turn 0.122 ms next to
+// 0.117 ms (1.05 times).  The three kernels and their passes have not been timed apart.
 #include "vrc_rigid.h"
+
+#include <stddef.h>
 
 #include "vrc_box_words.h"
 #include "vrc_group.h"
@@ -520,6 +534,139 @@ __global__ __launch_bounds__(GROUP) void k_pair_contacts(const uint32_t* __restr
     }
 }
 
+// ---- clearance: a field read at the voxels of every posed piece ------------------------------------------------
+
+// While k_clearance runs, a record holds the packed minimum at byte 24 (min_value, min_at[0]) and the packed maximum at byte
+// 40 (max_value, max_at[0]); k_clearance_begin puts the identities there, k_clearance_end decodes them in place.
+constexpr uint32_t CLEAR_POSED = 0, CLEAR_NONE = 1, CLEAR_SUM = 2, CLEAR_MIN = 3, CLEAR_MAX = 5;     // 64-bit words of the record
+constexpr uint32_t CLEAR_PARTS = 5, CLEAR_WORDS = 8;
+constexpr unsigned long long NO_MIN = ~0ull, NO_MAX = 0ull;          // no finite value: a packed word of a real voxel is neither
+
+static_assert(sizeof(vrc_piece_clearance) == CLEAR_WORDS * 8u, "vrc_piece_clearance is eight 64-bit words");
+static_assert(offsetof(vrc_piece_clearance, min_value) == CLEAR_MIN * 8u && offsetof(vrc_piece_clearance, max_value) == CLEAR_MAX * 8u,
+              "the packed minimum and maximum lie where min_value and max_value do");
+
+// What a lane knows of the field over the voxels it gathered for one piece.  lo = (value << 32) | index: the least value, and
+// among equals the smallest dense index; hi = (value << 32) | ~index: the greatest value, and among equals the smallest
+// dense index again (decode_argmax of vrc_snapshots.hip reads the same form).  VRC_DISTANCE_NONE enters neither.
+struct Clearance {
+    uint32_t posed, none;
+    unsigned long long sum, lo, hi;
+};
+
+// the gathered bits of word r, one load of the field each.  Bit 4 zl + 2 y + x is voxel (2 cx + x, 2 cy + y, z0 + zl), z0 the
+// z of the word's first layer: in a field of 4^3 (n = 2), where two brick rows share a word, z0 is -4 for the row in the
+// word's upper half -- the set bits lie in the row's own half, so z0 + zl is 0..3 there too (posed_word takes the same z0).
+__device__ __forceinline__ void clearance_word(const uint32_t* __restrict__ field, uint32_t Sd, const RowWord& r, uint32_t bits, Clearance& c)
+{
+    const int32_t z0 = 2 * (int32_t)((int64_t)(4u * r.w) - (int64_t)r.base);
+    const uint32_t corner = (2u * r.cx * Sd + 2u * r.cy) * Sd + (uint32_t)z0;          // modulo 2^32: whole again with zl added
+    c.posed += __popc(bits);
+    while (bits) {
+        const uint32_t bit = (uint32_t)__ffs((int)bits) - 1u;
+        bits &= bits - 1u;
+        const uint32_t index = corner + ((bit & 1u) ? Sd * Sd : 0u) + ((bit & 2u) ? Sd : 0u) + (bit >> 2);
+        const uint32_t v = field[index];
+        if (v == VRC_DISTANCE_NONE) { ++c.none; continue; }
+        c.sum += v;
+        const unsigned long long lo = ((unsigned long long)v << 32) | index, hi = ((unsigned long long)v << 32) | (uint32_t)~index;
+        c.lo = lo < c.lo ? lo : c.lo;
+        c.hi = hi > c.hi ? hi : c.hi;
+    }
+}
+
+// the 64-bit minimum / maximum of a wave by shuffles of the two 32-bit halves
+template <bool MAX>
+__device__ __forceinline__ unsigned long long wave_extreme(unsigned long long v)
+{
+    for (int o = 32; o; o >>= 1) {
+        const uint32_t up = __shfl_xor((uint32_t)(v >> 32), o), down = __shfl_xor((uint32_t)v, o);
+        const unsigned long long other = ((unsigned long long)up << 32) | down;
+        v = (MAX ? other > v : other < v) ? other : v;
+    }
+    return v;
+}
+
+// contact_flush for a Clearance: wave reductions, the four waves meet in LDS, and lanes 0..4 issue what is not an identity --
+// three 64-bit vector atomic adds, one atomicMin, one atomicMax, at most.  Called by the whole workgroup; one that gathered
+// nothing for the piece issues nothing.  The first barrier also keeps the LDS of the record before until its readers are done.
+__device__ __forceinline__ void clearance_flush(const Clearance& c, unsigned long long (*part)[CLEAR_PARTS], unsigned long long* record)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (!__syncthreads_or(c.posed != 0u)) return;
+    const bool some = __ballot(c.posed != 0u) != 0ull;                  // wave-uniform
+    const unsigned long long posed = some ? wave_sum((unsigned long long)c.posed) : 0ull, none = some ? wave_sum((unsigned long long)c.none) : 0ull;
+    const unsigned long long sum = some ? wave_sum(c.sum) : 0ull;
+    const unsigned long long lo = some ? wave_extreme<false>(c.lo) : NO_MIN, hi = some ? wave_extreme<true>(c.hi) : NO_MAX;
+    if (lane == 0u) {
+        part[wave][0] = posed; part[wave][1] = none; part[wave][2] = sum; part[wave][3] = lo; part[wave][4] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x >= CLEAR_PARTS) return;
+    const uint32_t k = threadIdx.x;
+    unsigned long long v = part[0][k];
+    for (uint32_t wv = 1; wv < WAVES; ++wv) {
+        const unsigned long long o = part[wv][k];
+        v = k < 3u ? v + o : k == 3u ? (o < v ? o : v) : (o > v ? o : v);
+    }
+    if (k == 0u) { if (v) atomicAdd(record + CLEAR_POSED, v); }
+    else if (k == 1u) { if (v) atomicAdd(record + CLEAR_NONE, v); }
+    else if (k == 2u) { if (v) atomicAdd(record + CLEAR_SUM, v); }
+    else if (k == 3u) { if (v != NO_MIN) atomicMin(record + CLEAR_MIN, v); }
+    else if (v != NO_MAX) atomicMax(record + CLEAR_MAX, v);
+}
+
+// one thread per record: the identities of the five reductions, every other byte 0
+__global__ __launch_bounds__(GROUP) void k_clearance_begin(unsigned long long* out, uint32_t C)
+{
+    const uint32_t i = blockIdx.x * GROUP + threadIdx.x;
+    if (i >= C) return;
+    for (uint32_t k = 0; k < CLEAR_WORDS; ++k) out[(size_t)CLEAR_WORDS * i + k] = k == CLEAR_MIN ? NO_MIN : 0ull;
+}
+
+// one thread per record: the two packed words become min_value / min_at and max_value / max_at in place.  No finite value:
+// VRC_DISTANCE_NONE at 0,0,0 and 0 at 0,0,0.  depth: of the field.
+__global__ __launch_bounds__(GROUP) void k_clearance_end(unsigned long long* out, uint32_t C, uint32_t depth)
+{
+    const uint32_t i = blockIdx.x * GROUP + threadIdx.x;
+    if (i >= C) return;
+    unsigned long long* words = out + (size_t)CLEAR_WORDS * i;
+    const unsigned long long lo = words[CLEAR_MIN], hi = words[CLEAR_MAX];
+    const uint32_t mask = (1u << depth) - 1u;
+    const uint32_t at_lo = lo == NO_MIN ? 0u : (uint32_t)lo, at_hi = hi == NO_MAX ? 0u : ~(uint32_t)hi;
+    // value, x in one word and y, z in the next, low half first; NO_MIN gives VRC_DISTANCE_NONE, NO_MAX gives 0
+    words[CLEAR_MIN] = (lo >> 32) | ((unsigned long long)(at_lo >> (2u * depth)) << 32);
+    words[CLEAR_MIN + 1u] = ((at_lo >> depth) & mask) | ((unsigned long long)(at_lo & mask) << 32);
+    words[CLEAR_MAX] = (hi >> 32) | ((unsigned long long)(at_hi >> (2u * depth)) << 32);
+    words[CLEAR_MAX + 1u] = ((at_hi >> depth) & mask) | ((unsigned long long)(at_hi & mask) << 32);
+}
+
+// k_contacts with a field for a world: where that kernel calls contact_word, this one reads the field at the gathered bits.
+// Width of the sums.  A lane takes fewer than 2^15.02 words of a piece (k_contacts), so at most 2^20.02 voxels: the two counts
+// fit 32 bits; a finite value is below 2^30 (a travel field; below 2^22 for a Euclidean one), so the sum is 64 bits wide from
+// the lane on.  Minimum and maximum do not depend on the order they are taken in, sums of integers neither.
+__global__ __launch_bounds__(GROUP) void k_clearance(const uint32_t* __restrict__ L, uint32_t lg, const vrc_component* __restrict__ records, uint32_t C,
+                                                     const uint8_t* __restrict__ keep, const vrc_affine* __restrict__ maps, const uint32_t* __restrict__ boxes,
+                                                     const uint32_t* __restrict__ field, uint32_t Sd, unsigned long long* out)
+{
+    __shared__ unsigned long long part[WAVES][CLEAR_PARTS];
+    const uint32_t n = Sd >> 1, Ss = 2u << lg;
+    for (uint32_t piece = blockIdx.y; piece < C; piece += gridDim.y) {  // uniform for the workgroup, and so is all that skips a piece
+        Posed s;
+        if (!pose_piece(records, piece, keep, maps, boxes, Sd, Ss, s)) continue;
+        Clearance c = {0u, 0u, 0ull, NO_MIN, NO_MAX};
+        for (uint64_t base = (uint64_t)blockIdx.x * GROUP; base < s.b.items; base += (uint64_t)gridDim.x * GROUP) {      // uniform trip count
+            const uint64_t it = base + threadIdx.x;
+            RowWord r;
+            if (it < s.b.items && row_word(s.b, n, it, r)) {
+                const uint32_t bits = posed_word(L, lg, piece, s, r, ~0u);
+                if (bits) clearance_word(field, Sd, r, bits, c);        // almost no word of a generous box gets here
+            }
+        }
+        clearance_flush(c, part, out + (size_t)CLEAR_WORDS * piece);
+    }
+}
+
 // ---- the broad phase: which boxes come near each other -----------------------------------------------------------
 
 // box i of the table clipped to the posed volume; false: the piece has no pairs (keep[i] == 0, an empty or inverted box)
@@ -625,6 +772,18 @@ hipError_t pair_contacts_run(const uint32_t* labels, const vrc_component* record
     const uint32_t Sd = 1u << posed_depth;
     hipLaunchKernelGGL(k_pair_contacts, posed_grid(n_pairs, Sd), dim3(GROUP), 0, st, labels, depth - 1u, records, (uint32_t)pieces, keep, maps, boxes, pairs,
                        (uint32_t)n_pairs, Sd, (unsigned long long*)out);
+    return hipGetLastError();
+}
+
+hipError_t clearance_run(const uint32_t* labels, const vrc_component* records, uint64_t pieces, uint32_t depth, const uint8_t* keep, const vrc_affine* maps,
+                         const uint32_t* boxes, const uint32_t* field, uint32_t field_depth, vrc_piece_clearance* out, hipStream_t st)
+{
+    const uint32_t Sd = 1u << field_depth, C = (uint32_t)pieces;
+    const dim3 per_record((C + GROUP - 1u) / GROUP);
+    hipLaunchKernelGGL(k_clearance_begin, per_record, dim3(GROUP), 0, st, (unsigned long long*)out, C);
+    hipLaunchKernelGGL(k_clearance, posed_grid(pieces, Sd), dim3(GROUP), 0, st, labels, depth - 1u, records, C, keep, maps, boxes, field, Sd,
+                       (unsigned long long*)out);
+    hipLaunchKernelGGL(k_clearance_end, per_record, dim3(GROUP), 0, st, (unsigned long long*)out, C, field_depth);
     return hipGetLastError();
 }
 

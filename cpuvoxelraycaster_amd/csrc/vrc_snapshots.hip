@@ -1,6 +1,6 @@
 // vrc_snapshots.hip -- the snapshots taken from an editable volume (include/vrc.h): the labels of its connected components
 // (vrc_volume_label_components, vrc_labels_*; kernels in vrc_components.hip; the pieces' moments, posed placement and
-// contacts, vrc_rigid_*, kernels in vrc_rigid.hip; the labels cut along the Voronoi cells of a list of sites,
+// contacts and their clearance over a field, vrc_rigid_*, kernels in vrc_rigid.hip; the labels cut along the Voronoi cells of a list of sites,
 // vrc_fracture_*, kernels in vrc_fracture.hip) and its exact squared Euclidean distance field
 // with the selection by distance that grow / shrink / hollow are made of (vrc_volume_distance_field, vrc_distance_*;
 // kernels in vrc_distance.hip), and the travel-distance field from a set of seeds, kept in the same snapshot object, with the
@@ -625,5 +625,28 @@ extern "C" int vrc_travel_trace_paths(const vrc_distance* d, uint64_t n, const u
     return staged_call(what, call, parts, [&](void* const* p) {
         vrc::travel_trace_run(d->d_field, d->depth, d->connectivity, n, (const uint32_t*)p[0], capacity, (uint32_t*)p[2], (uint32_t*)p[1], call.st);
         return hipSuccess;
+    });
+}
+
+// ---- a field read at the voxels of every posed piece (the rule: include/vrc.h; the kernels: vrc_rigid.hip) ---------
+
+extern "C" int vrc_rigid_clearance(const vrc_labels* l, const uint8_t* keep, const vrc_affine* maps, const uint32_t* boxes, const vrc_distance* field,
+                                   vrc_piece_clearance* out, int mem, void* stream)
+{
+    const char* what = "vrc_rigid_clearance";
+    if (!l || !field) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (field->device != l->device) return vrc::fail(VRC_ERR_INVALID, "%s: labels on device %d, field on device %d", what, l->device, field->device);
+    if (!maps && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null maps with %llu components", what, (unsigned long long)l->count);
+    if (!out && l->count) return vrc::fail(VRC_ERR_INVALID, "%s: null records with %llu components", what, (unsigned long long)l->count);
+    if (const int rc = check_affines(what, l->count, maps, mem)) return rc;
+    if (!l->count) return VRC_OK;
+    const size_t C = (size_t)l->count;
+    // both are snapshots, never written after creation: there is no edit to wait for
+    const Call call = snapshot_call(l->device, mem, stream);
+    const StagePart parts[] = {{out, C * sizeof(vrc_piece_clearance), STAGE_OUT}, {maps, C * sizeof(vrc_affine), STAGE_IN}, {boxes, C * 24u, STAGE_IN}, {keep, C, STAGE_IN}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        return vrc::clearance_run(l->d_ids, l->d_records, l->count, l->depth, (const uint8_t*)d[3], (const vrc_affine*)d[1], (const uint32_t*)d[2], field->d_field,
+                                  field->depth, (vrc_piece_clearance*)d[0], call.st);
     });
 }

@@ -193,6 +193,7 @@ private:
 };
 
 class HipVoxelVolume;
+class HipVoxelDistance;
 
 // mass, centre of mass (continuous voxel coordinates) and inertia tensor about it (row-major) of one piece, a voxel being a
 // unit cube of unit mass (include/vrc.h: vrc_rigid_moments).  Mass and centre are the exact values rounded once; an inertia
@@ -331,6 +332,12 @@ public:
     // volume of posed_depth, against piece b posed the same way -- no world, no walls -- include/vrc.h: vrc_rigid_pair_contacts.
     inline std::vector<vrc_piece_contact> pairContacts(const std::vector<vrc_affine>& maps, const std::vector<uint32_t>& pairs, uint32_t posed_depth,
                                                        const std::vector<uint32_t>* boxes = nullptr, const std::vector<uint8_t>* keep = nullptr) const;
+    // One record per piece: `field` (Euclidean or travel, any depth) read at the voxels of piece i posed as contacts() poses it
+    // into a volume of the field's depth -- their count, how many hold VRC_DISTANCE_NONE, the sum of the finite values, and the
+    // least and greatest one with the voxel of smallest dense index that holds it -- include/vrc.h: vrc_rigid_clearance.  A
+    // piece with keep[id] == 0 (nullptr: all kept) has the record of the empty set: min_value VRC_DISTANCE_NONE, the rest 0.
+    inline std::vector<vrc_piece_clearance> clearance(const std::vector<vrc_affine>& maps, const HipVoxelDistance& field,
+                                                      const std::vector<uint32_t>* boxes = nullptr, const std::vector<uint8_t>* keep = nullptr) const;
     vrc_labels* handle() const { return l_; }
 
 private:
@@ -936,6 +943,19 @@ inline std::vector<vrc_piece_contact> HipVoxelLabels::pairContacts(const std::ve
                                   boxes && !boxes->empty() ? boxes->data() : nullptr, posed_depth, out.size(), pairs.empty() ? nullptr : pairs.data(),
                                   out.empty() ? nullptr : out.data(), VRC_MEM_HOST, nullptr),
           "vrc_rigid_pair_contacts");
+    return out;
+}
+
+inline std::vector<vrc_piece_clearance> HipVoxelLabels::clearance(const std::vector<vrc_affine>& maps, const HipVoxelDistance& field,
+                                                                  const std::vector<uint32_t>* boxes, const std::vector<uint8_t>* keep) const
+{
+    if (maps.size() != count()) throw std::invalid_argument("HipVoxelLabels::clearance: maps must have one entry per component");
+    if (boxes && boxes->size() != count() * 6u) throw std::invalid_argument("HipVoxelLabels::clearance: boxes must have six entries per component");
+    if (keep && keep->size() != count()) throw std::invalid_argument("HipVoxelLabels::clearance: keep must have one byte per component");
+    std::vector<vrc_piece_clearance> out((size_t)count());
+    check(vrc_rigid_clearance(l_, keep && !keep->empty() ? keep->data() : nullptr, maps.empty() ? nullptr : maps.data(),
+                              boxes && !boxes->empty() ? boxes->data() : nullptr, field.handle(), out.empty() ? nullptr : out.data(), VRC_MEM_HOST, nullptr),
+          "vrc_rigid_clearance");
     return out;
 }
 

@@ -251,6 +251,14 @@ def contact_properties(records):
     return tuple(out)
 
 
+def free_radius(min_value, S):
+    """VoxelLabels.freeRadius' rule on an array of vrc_piece_clearance min_value over a squared-distance field of S^3: int64
+    isqrt(min_value - 1), the largest r with r^2 < min_value; -1 where min_value is 0; S where it is capi.VRC_DISTANCE_NONE"""
+    from math import isqrt
+    values = np.asarray(min_value, np.uint32).reshape(-1)
+    return np.array([int(S) if v == capi.VRC_DISTANCE_NONE else isqrt(int(v) - 1) if v else -1 for v in values.tolist()], np.int64)
+
+
 class VoxelVolume:
     """Device-resident editable occupancy of an S^3 volume (include/vrc.h: vrc_volume_*).  Edits are batched; commit()
     builds a new immutable LSVO on the device, bit-identical to compileSVO of the current voxel set."""
@@ -1026,6 +1034,30 @@ class VoxelLabels:
     def collides(self, maps, world, boxes=None, keep=None):
         """bool per piece: the posed piece shares a voxel with the world's solid (contacts()["overlap"] > 0)"""
         return self.contacts(maps, world, boxes, keep)["overlap"] > 0
+
+    def clearance(self, maps, field, boxes=None, keep=None):
+        """One capi.CLEARANCE_DTYPE record per piece: `field` (a VoxelDistance, Euclidean or travel, of any depth) read at the
+        voxels of piece i posed as contacts() poses it into a volume of the field's depth -- include/vrc.h:
+        vrc_rigid_clearance.  posed = its voxels there, none = those whose value is capi.VRC_DISTANCE_NONE, sum = the sum of the
+        finite values, min_value / max_value = the least / greatest finite one (VRC_DISTANCE_NONE / 0 without any) and min_at /
+        max_at the voxel of smallest dense index that holds it.  A piece with keep[id] == 0 (None: all kept) or an empty box
+        has the record of the empty set: min_value VRC_DISTANCE_NONE, the rest 0."""
+        maps, boxes, keep = self._contact_arguments(maps, boxes, keep)
+        out = np.zeros(self.count, capi.CLEARANCE_DTYPE)
+        check(capi.load().vrc_rigid_clearance(self._h, ptr(keep), ptr(maps) if self.count else None, ptr(boxes), field._h,
+                                               ptr(out) if self.count else None, capi.VRC_MEM_HOST, None))
+        return out
+
+    def clearanceDevice(self, maps_ptr, field, out_ptr, boxes_ptr=None, keep_ptr=None, stream=None):
+        """the same with the maps (64 bytes each), the boxes, `count` bytes of keep and the records (64 bytes each) in device
+        memory, asynchronous on `stream`; a piece whose map lies beyond the limits has the record of the empty set"""
+        check(capi.load().vrc_rigid_clearance(self._h, ptr(keep_ptr), ptr(maps_ptr), ptr(boxes_ptr), field._h, ptr(out_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def freeRadius(self, maps, field, boxes=None, keep=None):
+        """int64 per piece, from clearance()["min_value"] over the squared distance to a feature set: the largest r such that
+        every integer translation o of the posed piece with |o| <= r stays clear of the set -- isqrt(min_value - 1); -1 where
+        min_value is 0 (the piece already overlaps the set); the field's S where there is no finite value (nothing to hit)"""
+        return free_radius(self.clearance(maps, field, boxes, keep)["min_value"], 1 << field.depth)
 
     def pieceSites(self, first=0, capacity=None):
         """uint32 per piece of [first, first + capacity) that exists: the index of the site whose cell the piece lies in,

@@ -955,6 +955,63 @@ int vrc_travel_connectivity(const vrc_distance *d);          /* 6 / 26: a travel
 int vrc_travel_trace_paths(const vrc_distance *d, uint64_t n, const uint32_t *start_xyz, uint32_t capacity,
                              uint32_t *paths_xyz, uint32_t *lengths, int mem, void *stream);
 
+/* vrc_rigid_clearance: how far a posed piece is from colliding, and how deep it is in.  vrc_rigid_contacts says whether a
+ * pose collides; a piece in free flight has the same all-zero overlap / touch whether the nearest wall is 2 voxels away or
+ * 200, and `overlap` counts voxels, not the way out.  Both answers lie in a vrc_distance snapshot: the squared distance to
+ * the solid (to = VRC_FLOOD_SOLID) is the clearance, the one to the open (to = VRC_FLOOD_EMPTY) the penetration depth, and a
+ * travel field gives "how many steps from the seeds is each piece".  This call reads such a field at the voxels of every
+ * posed piece and reduces it per piece, where the only other way is one placement into a scratch volume, one download and
+ * one vrc_distance_at per piece.  Exact in integers.
+ *
+ * The sets.  A_i is exactly the set of voxels vrc_rigid_place_affine would OR into an empty volume of the FIELD's depth with
+ * the same keep, maps and boxes -- vrc_rigid_contacts' definition, with the field's depth where that call has the world's.
+ * The record is the reduction of field(p) over p in A_i: posed = |A_i|; none = the voxels whose value is VRC_DISTANCE_NONE;
+ * sum = the sum of the finite values (below 2^60: a value is below 2^30, a set has at most 2^30 voxels); min_value / max_value
+ * = the least / greatest finite value, VRC_DISTANCE_NONE / 0 when there is none; min_at / max_at = the voxel that holds it,
+ * among several the one of smallest dense index (x*S + y)*S + z, and 0,0,0 when there is none; reserved = 0.  NONE values take
+ * part in neither minimum nor maximum.  All C records are written; a piece that is skipped -- keep[i] == 0, an empty or
+ * inverted box, and with VRC_MEM_DEVICE a map beyond the limits -- gets the record of the empty set: min_value =
+ * VRC_DISTANCE_NONE and every other byte 0.  The ties are settled, so the result is unique: two calls give identical bytes
+ * whatever the schedule.  With D the field to the solid with outside = 0, min_value = 0 says the piece overlaps, and
+ * otherwise every integer translation o of the posed set with |o|^2 < min_value stays clear of the solid (the set may leave
+ * the volume: vrc_rigid_contacts clips it): conservative advancement.
+ * Any vrc_distance snapshot is accepted, Euclidean or travel, of depth 2..10; the labels may have another depth; the field
+ * must be on the labels' device.
+ * Memory, ordering and refusals are vrc_rigid_contacts', with no volume to order behind: both arguments are snapshots.  mem
+ * says where keep, maps, boxes and out live.  VRC_MEM_HOST stages the four in one block, freed before return, and is
+ * synchronous; every map is checked before any device call ("piece <i>: ..." names the first bad one).  VRC_MEM_DEVICE works
+ * in place and is asynchronous on `stream`; while the call is in flight the records hold intermediate values.  NULL l or
+ * field, NULL maps or out when C > 0, a device mismatch and a bad mem are VRC_ERR_INVALID before any device call.  C == 0 is
+ * a no-op.  The call keeps no scratch: vrc_labels_bytes and vrc_volume_edit_scratch_bytes do not change.
+ * The device (csrc/vrc_rigid.hip) runs one kernel of vrc_rigid_contacts' shape -- the same 2-D grid, per-piece set-up and
+ * per-word gather, one copy for all -- between two small ones of one thread per record.  A lane with gathered bits walks
+ * them and loads the field at each, four runs of eight consecutive values a word, into a count, a count of NONE, a 64-bit
+ * sum and a packed minimum (value << 32 | index) and maximum (value << 32 | ~index), so that the voxel of smallest index
+ * travels with the value.  Waves reduce by shuffles, the four waves meet in LDS, and a workgroup issues at most three 64-bit
+ * vector atomic adds, one atomicMin and one atomicMax per piece, none where it gathered nothing; plain HIP C++.  The record
+ * itself holds the two packed words meanwhile: the kernel before writes the identities, the kernel after decodes them in
+ * place.  Measured on an MI355X at 512^3 on the fall benchmark's scene (tools/bench_edit.py --clearance,
+ * profiles/edit/bench_clearance.json; 404 loose blocks of 1.9 M voxels, the Euclidean field of the 5.6 M supported voxels; device
+ * time by events, median of 5, everything in device memory, A B A B with vrc_rigid_contacts against the supported part with the
+ * same maps and boxes in the same run): with the fall's translation maps and the moved record boxes (0.16 M words) 0.121 ms next
+ * to 0.109 ms of the contact call, 1.11 times; no piece overlaps, 252 are within one voxel.  With every piece turned 30 degrees
+ * about x, then y, about its own centre of mass (0.74 M words) 0.122 ms next to 0.117 ms, 1.05 times; 148 pieces overlap.  The
+ * two kernels of one thread per record, the gather, the field loads and the reduction have not been timed apart; NULL boxes,
+ * travel fields and fields of another depth than the labels have not been timed. */
+typedef struct vrc_piece_clearance {     /* 64 bytes */
+    uint64_t posed;          /* |A_i| */
+    uint64_t none;           /* voxels of A_i whose field value is VRC_DISTANCE_NONE */
+    uint64_t sum;            /* sum of the finite values over A_i (< 2^60: values < 2^30, at most 2^30 voxels) */
+    uint32_t min_value;      /* least finite value over A_i; VRC_DISTANCE_NONE when there is none */
+    uint32_t min_at[3];      /* the voxel of smallest dense index (x*S + y)*S + z that holds it; 0,0,0 when none */
+    uint32_t max_value;      /* greatest finite value over A_i; 0 when there is none */
+    uint32_t max_at[3];      /* the voxel of smallest dense index that holds it; 0,0,0 when none */
+    uint64_t reserved;       /* 0 */
+} vrc_piece_clearance;
+int vrc_rigid_clearance(const vrc_labels *l, const uint8_t *keep /* C bytes, NULL = all */,
+                        const vrc_affine *maps /* C */, const uint32_t *boxes /* C x 6 lo,hi; NULL = all of the field */,
+                        const vrc_distance *field, vrc_piece_clearance *out /* C */, int mem, void *stream);
+
 /* ---- dense grid: Grid3D<X,Y,Z> (grid_3d.hpp:10-138) ------------------- */
 
 /* cells[(x*Y + y)*Z + z] = Cell::Type (0 = Empty). */

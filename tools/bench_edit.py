@@ -156,6 +156,15 @@ Measured on an MI355X at 512^3: 404 pieces, 3688 candidate pairs listed in 0.33 
 overlap, 798 touch), next to 0.098 ms per pair of the workaround on 64 pairs, 360 ms scaled, 445 times.  Not timed apart: the
 zeroing, the two gathers and the reduction of the pair kernel; the count, scan and emit of the broad phase; the three steps
 of the workaround.
+With --clearance (printed and written to profiles/edit/bench_clearance.json), a field read at the voxels of posed pieces on the
+same scene, everything in device memory, A B A B in one run: each clearance call over the Euclidean field of the supported part
+next to vrc_rigid_contacts against the supported part with the same maps and boxes -- the same gather, reading at most 7 words
+where the clearance reads up to 32 values (the clearance time includes its two one-thread-per-record kernels, the contact time
+the zeroing of the records; the passes of a call are not timed apart):
+  clearance_translate  vrc_rigid_clearance with the fall's translation maps and the moved record boxes
+                                                                next to  contacts_translate
+  clearance_turn       the same with every piece turned 30 degrees about x, then y, about its own centre of mass
+                                                                next to  contacts_turn
 No threshold is applied; the numbers are reported."""
 import argparse
 import json
@@ -1082,6 +1091,70 @@ def bench_contacts(vrc, depth, pairs):
     return res
 
 
+def bench_clearance(vrc, depth, pairs):
+    """vrc_rigid_clearance over the Euclidean field of the supported part next to vrc_rigid_contacts against the supported part
+    with the same maps and boxes -- the same gather, reading at most 7 words where the clearance reads up to 32 values -- on
+    bench_fall's scene, A B A B in one run"""
+    import math
+    import torch
+    S = 1 << depth
+    res = {"size": S, "pairs": pairs}
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    world = vrc.VoxelVolume.fromScene(scene)
+    floor_y = S // 2 + 1
+    band = [0, floor_y + 24, 0, S, floor_y + 28, S]
+    cuts = [band, [0, floor_y + 44, 0, S, floor_y + 47, S]]
+    cuts += [[c, floor_y + 24, 0, c + 2, S, S] for c in range(30, S, 32)] + [[0, floor_y + 24, c, S, S, c + 2] for c in range(30, S, 32)]
+    world.fillBoxes(cuts, False)
+    debris = world.keepConnected([[0, floor_y, 0, S, floor_y + 1, S]], 6)       # world keeps the supported part
+    labels = debris.labelComponents(6)
+    field = world.distanceField(False, False)
+    C_ = labels.count
+    res["pieces"], res["supported_voxels"], res["debris_voxels"] = C_, world.solidCount(), debris.solidCount()
+
+    def box_words(boxes):
+        return int(sum(((int(b[3]) - 1) // 2 - int(b[0]) // 2 + 1) * ((int(b[4]) - 1) // 2 - int(b[1]) // 2 + 1) * ((((int(b[5]) - 1) // 2 - int(b[2]) // 2) + 3) // 4 + 1)
+                       for b in boxes if all(b[a] < b[a + 3] for a in range(3))))
+
+    def on_device(array):
+        return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).cuda()
+
+    records = labels.components()
+    offsets, st = labels.fall(world, vrc.capi.VRC_FACE_YN)
+    maps = np.zeros(C_, vrc.capi.AFFINE_DTYPE)
+    maps["m"][:] = [65536, 0, 0, 0, 65536, 0, 0, 0, 65536]
+    maps["t"][:] = -(offsets.astype(np.int64) << 17)
+    boxes = np.concatenate([np.clip(records["lo"].astype(np.int64) + offsets, 0, S), np.clip(records["hi"].astype(np.int64) + offsets, 0, S)], axis=1).astype(np.uint32)
+    c, s = math.cos(math.radians(30)), math.sin(math.radians(30))
+    rx = np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
+    ry = np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
+    rot = np.ascontiguousarray((ry @ rx).T, np.float32).reshape(9)
+    turn_maps, turn_boxes = labels.poses(rot, labels.massProperties()[1])
+    out = torch.zeros(max(C_, 1) * 64, dtype=torch.uint8).cuda()
+    contact_out = torch.zeros(max(C_, 1) * 128, dtype=torch.uint8).cuda()
+    for name, mp, bx in (("translate", maps, boxes), ("turn", turn_maps, turn_boxes)):
+        d_maps, d_boxes = on_device(mp), on_device(bx)
+        torch.cuda.synchronize()
+        res[name + "_box_words"] = box_words(bx)
+        res["clearance_%s_ms" % name], res["contacts_%s_ms" % name] = ab_device_ms(
+            lambda: labels.clearanceDevice(d_maps.data_ptr(), field, out.data_ptr(), d_boxes.data_ptr(), None, None),
+            lambda: labels.contactsDevice(d_maps.data_ptr(), world, contact_out.data_ptr(), d_boxes.data_ptr(), None, None), pairs)
+        res["clearance_%s_over_contacts" % name] = round(res["clearance_%s_ms" % name]["median"] / res["contacts_%s_ms" % name]["median"], 2)
+        got = out.cpu().numpy().view(vrc.capi.CLEARANCE_DTYPE)[:C_]
+        assert got.tobytes() == labels.clearance(mp, field, bx).tobytes(), "device-memory records differ from the host-memory call's"
+        hit = contact_out.cpu().numpy().view(vrc.capi.CONTACT_DTYPE)[:C_]
+        assert np.array_equal(got["posed"], hit["posed"]) and np.array_equal(got["min_value"] == 0, hit["overlap"] > 0), "clearance and contacts disagree"
+        finite = got["min_value"] != vrc.capi.VRC_DISTANCE_NONE
+        res["clearance_" + name] = {"posed_voxels": int(got["posed"].sum()), "pieces_posed": int((got["posed"] > 0).sum()),
+                                    "pieces_overlapping": int((got["min_value"] == 0).sum()), "pieces_within_one_voxel": int((got["min_value"] == 1).sum()),
+                                    "largest_min_value": int(got["min_value"][finite].max(initial=0)), "largest_max_value": int(got["max_value"].max(initial=0))}
+    assert res["clearance_translate"]["pieces_overlapping"] == 0 and res["clearance_translate"]["posed_voxels"] == res["debris_voxels"], "the fall's offsets overlap the supported part"
+    for v in (field, labels, debris, world):
+        v.close()
+    scene.close()
+    return res
+
+
 def bench_pair_contacts(vrc, depth, pairs):
     """vrc_rigid_box_pairs + vrc_rigid_pair_contacts on bench_fall's scene with bench_contacts' turned poses, next to the
     documented workaround on a sample of the pairs: vrc_rigid_place_affine of b alone into a cleared scratch volume, then
@@ -1296,6 +1369,7 @@ def main():
     ap.add_argument("--rigid", action="store_true", help="time vrc_rigid_moments / vrc_rigid_place_affine next to vrc_labels_select / vrc_fall_place (depth 9 unless --depths is given)")
     ap.add_argument("--contacts", action="store_true", help="time vrc_rigid_contacts next to vrc_rigid_place_affine with the same maps and boxes (depth 9 unless --depths is given)")
     ap.add_argument("--pair-contacts", action="store_true", help="time vrc_rigid_box_pairs and vrc_rigid_pair_contacts next to placement + contacts per pair (depth 9 unless --depths is given)")
+    ap.add_argument("--clearance", action="store_true", help="time vrc_rigid_clearance next to vrc_rigid_contacts with the same maps and boxes (depth 9 unless --depths is given)")
     ap.add_argument("--travel", action="store_true", help="time vrc_travel_field next to vrc_volume_flood from the same seeds (depth 9 unless --depths is given)")
     ap.add_argument("--fracture", action="store_true", help="time vrc_fracture_label next to vrc_volume_distance_field + vrc_volume_label_components (depth 9 unless --depths is given)")
     args = ap.parse_args()
@@ -1313,6 +1387,23 @@ def main():
             out["depths"][str(d)] = bench_fracture(vrc, d, max(1, args.pairs))
         print(json.dumps(out))
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_fracture.json")
+        with open(path, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+        return
+    if args.clearance:
+        if args.depths == [8, 9, 10]:
+            args.depths = [9]
+        import __graft_entry__ as g
+        g.build()
+        import torch
+        import cpuvoxelraycaster_amd as vrc
+        if not torch.cuda.is_available():
+            raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
+        out = {"bench": "edit_clearance", "device": torch.cuda.get_device_name(0), "depths": {}}
+        for d in args.depths:
+            out["depths"][str(d)] = bench_clearance(vrc, d, max(1, args.pairs))
+        print(json.dumps(out))
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_clearance.json")
         with open(path, "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
         return
