@@ -47,6 +47,9 @@ assert CONTACT_DTYPE.itemsize == 128
 CLEARANCE_DTYPE = np.dtype([("posed", "<u8"), ("none", "<u8"), ("sum", "<u8"), ("min_value", "<u4"), ("min_at", "<u4", 3),
                             ("max_value", "<u4"), ("max_at", "<u4", 3), ("reserved", "<u8")])
 assert CLEARANCE_DTYPE.itemsize == 64
+# a record of a delta (include/vrc.h: vrc_delta_diff): bits = before[word] ^ after[word] != 0, word strictly ascending
+DELTA_RECORD_DTYPE = np.dtype([("word", "<u4"), ("bits", "<u4")])
+assert DELTA_RECORD_DTYPE.itemsize == 8
 
 
 class VrcError(RuntimeError):
@@ -90,6 +93,11 @@ class FallStats(C.Structure):
     """vrc_fall_stats (include/vrc.h): what vrc_fall_drops reports"""
     _fields_ = [("moved_voxels", C.c_uint64), ("pieces", C.c_uint32), ("moved_pieces", C.c_uint32), ("max_drop", C.c_uint32),
                 ("rounds", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class DeltaStats(C.Structure):
+    """vrc_delta_stats (include/vrc.h): the records, the changed voxels and their box (hi exclusive) of a delta"""
+    _fields_ = [("words", C.c_uint64), ("voxels", C.c_uint64), ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("reserved", C.c_uint32 * 2)]
 
 
 class Affine(C.Structure):
@@ -229,6 +237,15 @@ SYMBOLS = {
     "vrc_travel_field": (_int, [_vp, _vp, _int, _int, _u32, C.POINTER(_vp), C.POINTER(TravelStats)]),
     "vrc_travel_connectivity": (_int, [_vp]),
     "vrc_travel_trace_paths": (_int, [_vp, _u64, _vp, _u32, _vp, _vp, _int, _vp]),
+    "vrc_delta_diff": (_int, [_vp, _vp, C.POINTER(_vp), C.POINTER(DeltaStats)]),
+    "vrc_delta_create": (_int, [_u32, _int, _u64, _vp, _int, C.POINTER(_vp), C.POINTER(DeltaStats)]),
+    "vrc_delta_destroy": (_int, [_vp]),
+    "vrc_delta_count": (_u64, [_vp]),
+    "vrc_delta_depth": (_u32, [_vp]),
+    "vrc_delta_bytes": (_u64, [_vp]),
+    "vrc_delta_get_stats": (_int, [_vp, C.POINTER(DeltaStats)]),
+    "vrc_delta_records": (_int, [_vp, _u64, _u64, _vp, _int, _vp]),
+    "vrc_delta_apply": (_int, [_vp, _vp, _vp]),
     "vrc_volume_xor_mesh": (_int, [_vp, _u64, _vp, _int, _vp]),
     "vrc_volume_surface_count": (_int, [_vp, _int, _vp]),
     "vrc_volume_extract_surface": (_int, [_vp, _int, _int, _u64, _u64, _vp, _vp, _int, _vp]),

@@ -4,7 +4,8 @@
 // vrc_fracture_*, kernels in vrc_fracture.hip) and its exact squared Euclidean distance field
 // with the selection by distance that grow / shrink / hollow are made of (vrc_volume_distance_field, vrc_distance_*;
 // kernels in vrc_distance.hip), and the travel-distance field from a set of seeds, kept in the same snapshot object, with the
-// routes read off it (vrc_travel_field, vrc_travel_trace_paths; kernels in vrc_travel.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
+// routes read off it (vrc_travel_field, vrc_travel_trace_paths; kernels in vrc_travel.hip), and the difference of two volumes as a list of
+// changed words (vrc_delta_diff, vrc_delta_*; kernels in vrc_delta.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
 // event and no scratch: its host-memory calls stage in a block of their own, and what it selects or places goes into a volume
 // as an edit of that volume (staged_call in vrc_volume_state.h; the ordering of every entry point: the table in DESIGN.md).
 #include <hip/hip_runtime.h>
@@ -14,6 +15,7 @@
 
 #include "../../include/vrc.h"
 #include "vrc_components.h"
+#include "vrc_delta.h"
 #include "vrc_distance.h"
 #include "vrc_fall.h"
 #include "vrc_fracture.h"
@@ -649,4 +651,165 @@ extern "C" int vrc_rigid_clearance(const vrc_labels* l, const uint8_t* keep, con
         return vrc::clearance_run(l->d_ids, l->d_records, l->count, l->depth, (const uint8_t*)d[3], (const vrc_affine*)d[1], (const uint32_t*)d[2], field->d_field,
                                   field->depth, (vrc_piece_clearance*)d[0], call.st);
     });
+}
+
+// ---- deltas: the changed words of two volumes (the rule: include/vrc.h; the kernels: vrc_delta.hip) -----------------
+
+struct vrc_delta {
+    int device = 0;
+    uint32_t depth = 0;
+    uint64_t count = 0;
+    uint2* d_records = nullptr;           // count records {word, bits}, nullptr when count == 0
+    vrc_delta_stats stats = {};
+};
+
+// what the passes reduced, as the stats of a list of `words` records
+static vrc_delta_stats delta_stats_of(const vrc::DeltaTotals& t, uint64_t words)
+{
+    vrc_delta_stats s = {};
+    s.words = words;
+    s.voxels = t.voxels;
+    for (int a = 0; a < 3 && words; ++a) { s.lo[a] = t.lo[a]; s.hi[a] = t.hi[a]; }
+    return s;
+}
+
+// Not a snapshot_run: two volumes to wait for, and the array is sized by what the host reads back between scan and emit.
+extern "C" int vrc_delta_diff(vrc_volume* before, vrc_volume* after, vrc_delta** out, vrc_delta_stats* stats)
+{
+    const char* what = "vrc_delta_diff";
+    if (!before || !after || !out) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (before == after) return vrc::fail(VRC_ERR_INVALID, "%s: before and after are the same volume", what);
+    if (before->depth != after->depth) return vrc::fail(VRC_ERR_INVALID, "%s: volumes of depths %u and %u", what, before->depth, after->depth);
+    if (before->device != after->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, before->device, after->device);
+    vrc_delta* d = new (std::nothrow) vrc_delta();
+    if (!d) return vrc::fail(VRC_ERR_OOM, "out of host memory");
+    d->device = before->device; d->depth = before->depth;
+    void* d_scratch = nullptr;
+    vrc::DeltaTotals totals = {};
+    hipError_t e = hipSetDevice(d->device);
+    if (e == hipSuccess) e = order_behind_edits(before, nullptr);
+    if (e == hipSuccess) e = order_behind_edits(after, nullptr);
+    if (e == hipSuccess) e = hipMalloc(&d_scratch, vrc::delta_scratch_bytes(d->depth));
+    if (e == hipSuccess) {
+        vrc::delta_offsets_run(before->d_bricks, after->d_bricks, d->depth, d_scratch, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(&totals, d_scratch, sizeof totals, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && totals.words) e = hipMalloc((void**)&d->d_records, (size_t)totals.words * 8u);
+    if (e == hipSuccess && totals.words) {
+        vrc::delta_emit_run(before->d_bricks, after->d_bricks, d->depth, d_scratch, d->d_records, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (d_scratch) (void)hipFree(d_scratch);
+    if (e != hipSuccess) {
+        (void)vrc_delta_destroy(d);
+        return vrc::fail_hip(e, what);
+    }
+    d->count = totals.words;
+    d->stats = delta_stats_of(totals, d->count);
+    if (stats) *stats = d->stats;
+    *out = d;
+    return VRC_OK;
+}
+
+extern "C" int vrc_delta_create(uint32_t depth, int device, uint64_t n, const uint32_t* records, int mem, vrc_delta** out, vrc_delta_stats* stats)
+{
+    const char* what = "vrc_delta_create";
+    if (!out) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (depth < 2 || depth > 10) return vrc::fail(VRC_ERR_INVALID, "%s: depth %u not in [2,10]", what, depth);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (!records && n) return vrc::fail(VRC_ERR_INVALID, "%s: null records with n = %llu", what, (unsigned long long)n);
+    if (const int rc = vrc::require_device(device, nullptr)) return rc;
+    vrc_delta* d = new (std::nothrow) vrc_delta();
+    if (!d) return vrc::fail(VRC_ERR_OOM, "out of host memory");
+    d->device = device; d->depth = depth;
+    // a list longer than the field has words breaks the rule within its first n_words + 1 records: those are looked at
+    const uint32_t n_words = vrc::delta_words(depth), n_check = (uint32_t)(n <= n_words ? n : n_words + 1u);
+    vrc::DeltaTotals* d_totals = nullptr;
+    vrc::DeltaTotals totals = {};
+    uint2 bad[2] = {};
+    hipError_t e = hipMalloc((void**)&d_totals, sizeof totals);
+    if (e == hipSuccess && n_check) e = hipMalloc((void**)&d->d_records, (size_t)n_check * 8u);
+    if (e == hipSuccess && n_check)
+        e = hipMemcpyAsync(d->d_records, records, (size_t)n_check * 8u, mem == VRC_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, nullptr);
+    if (e == hipSuccess) {
+        vrc::delta_check_run(d->d_records, n_check, depth, d_totals, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(&totals, d_totals, sizeof totals, hipMemcpyDeviceToHost);
+    const bool refused = e == hipSuccess && (totals.first_bad != 0xffffffffu || n > n_words);
+    if (refused && totals.first_bad < n_check) {
+        const uint32_t from = totals.first_bad ? totals.first_bad - 1u : 0u;
+        e = hipMemcpy(bad, d->d_records + from, totals.first_bad ? 16u : 8u, hipMemcpyDeviceToHost);
+        if (!totals.first_bad) bad[1] = bad[0];
+    }
+    if (d_totals) (void)hipFree(d_totals);
+    if (e != hipSuccess || refused) (void)vrc_delta_destroy(d);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    if (refused) {
+        const unsigned long long i = totals.first_bad;
+        if (totals.first_bad >= n_check) return vrc::fail(VRC_ERR_INVALID, "%s: %llu records for the %u words of depth %u", what, (unsigned long long)n, n_words, depth);
+        if (bad[1].y == 0u) return vrc::fail(VRC_ERR_INVALID, "%s: record %llu (word %u): bits are 0", what, i, bad[1].x);
+        if (bad[1].x >= n_words) return vrc::fail(VRC_ERR_INVALID, "%s: record %llu: word %u beyond the %u words of depth %u", what, i, bad[1].x, n_words, depth);
+        return vrc::fail(VRC_ERR_INVALID, "%s: record %llu: word %u is not above word %u of the record before it", what, i, bad[1].x, bad[0].x);
+    }
+    d->count = n;
+    d->stats = delta_stats_of(totals, n);
+    if (stats) *stats = d->stats;
+    *out = d;
+    return VRC_OK;
+}
+
+extern "C" int vrc_delta_destroy(vrc_delta* d)
+{
+    if (!d) return VRC_OK;
+    (void)hipSetDevice(d->device);
+    (void)hipDeviceSynchronize();       // an apply or a device-memory window may still be reading it on a caller's stream
+    if (d->d_records) (void)hipFree(d->d_records);
+    delete d;
+    return VRC_OK;
+}
+
+extern "C" uint64_t vrc_delta_count(const vrc_delta* d) { return d ? d->count : 0; }
+extern "C" uint32_t vrc_delta_depth(const vrc_delta* d) { return d ? d->depth : 0; }
+extern "C" uint64_t vrc_delta_bytes(const vrc_delta* d) { return d ? d->count * 8u : 0; }
+
+extern "C" int vrc_delta_get_stats(const vrc_delta* d, vrc_delta_stats* out)
+{
+    if (!d || !out) return vrc::fail(VRC_ERR_INVALID, "vrc_delta_get_stats: null argument");
+    *out = d->stats;
+    return VRC_OK;
+}
+
+extern "C" int vrc_delta_records(const vrc_delta* d, uint64_t first, uint64_t capacity, uint32_t* out, int mem, void* stream)
+{
+    const char* what = "vrc_delta_records";
+    if (!d) return vrc::fail(VRC_ERR_INVALID, "%s: null delta", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
+    const uint64_t want = window_of(first, capacity, d->count);
+    if (!want) return VRC_OK;
+    const Call call = snapshot_call(d->device, mem, stream);
+    const StagePart parts[] = {{out, (size_t)want * 8u, STAGE_OUT}};
+    return staged_call(what, call, parts, [&](void* const* p) {
+        return hipMemcpyAsync(p[0], d->d_records + first, (size_t)want * 8u, hipMemcpyDeviceToDevice, call.st);
+    });
+}
+
+extern "C" int vrc_delta_apply(const vrc_delta* d, vrc_volume* dst, void* stream)
+{
+    const char* what = "vrc_delta_apply";
+    if (!d || !dst) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_same(what, "delta", d->depth, d->device, dst)) return rc;
+    if (!d->count) return VRC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(d->device);
+    if (e == hipSuccess) e = order_behind_edits(dst, st);
+    if (e == hipSuccess) {
+        vrc::delta_apply_run(d->d_records, (uint32_t)d->count, dst->d_bricks, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
+    return done(e, what);
 }

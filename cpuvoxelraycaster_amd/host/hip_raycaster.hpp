@@ -194,6 +194,7 @@ private:
 
 class HipVoxelVolume;
 class HipVoxelDistance;
+class HipVoxelDelta;
 
 // mass, centre of mass (continuous voxel coordinates) and inertia tensor about it (row-major) of one piece, a voxel being a
 // unit cube of unit mass (include/vrc.h: vrc_rigid_moments).  Mass and centre are the exact values rounded once; an inertia
@@ -405,6 +406,55 @@ private:
     vrc_travel_stats travel_{};
 };
 
+// The difference of two volumes (include/vrc.h: vrc_delta_diff): a snapshot on the device, one record {word, bits} per
+// occupancy word that differs, in ascending word order.  HipVoxelVolume::applyDelta flips the changed voxels, so one delta
+// serves undo and redo.  Movable, RAII.
+class HipVoxelDelta {
+public:
+    // from caller records (n x 2 uint32: word, bits; another rank's, a saved history's), held to the rule on the device
+    static HipVoxelDelta fromRecords(uint32_t depth, const std::vector<uint32_t>& records, int device = 0)
+    {
+        if (records.size() & 1u) throw std::invalid_argument("HipVoxelDelta::fromRecords: records must have two entries per record");
+        vrc_delta* d = nullptr;
+        check(vrc_delta_create(depth, device, records.size() / 2, records.empty() ? nullptr : records.data(), VRC_MEM_HOST, &d, nullptr), "vrc_delta_create");
+        return HipVoxelDelta(d);
+    }
+    ~HipVoxelDelta() { vrc_delta_destroy(d_); }
+    HipVoxelDelta(HipVoxelDelta&& o) noexcept : d_(o.d_) { o.d_ = nullptr; }
+    HipVoxelDelta& operator=(HipVoxelDelta&& o) noexcept
+    {
+        if (this != &o) { vrc_delta_destroy(d_); d_ = o.d_; o.d_ = nullptr; }
+        return *this;
+    }
+    HipVoxelDelta(const HipVoxelDelta&) = delete;
+    HipVoxelDelta& operator=(const HipVoxelDelta&) = delete;
+
+    uint64_t count() const { return vrc_delta_count(d_); }
+    uint32_t depth() const { return vrc_delta_depth(d_); }
+    uint64_t bytes() const { return vrc_delta_bytes(d_); }
+    // records, changed voxels and their box (hi exclusive); the host copy kept in the object
+    vrc_delta_stats stats() const
+    {
+        vrc_delta_stats s{};
+        check(vrc_delta_get_stats(d_, &s), "vrc_delta_get_stats");
+        return s;
+    }
+    // the records [first, first + capacity) that exist: word, bits, word, bits, ...
+    std::vector<uint32_t> records(uint64_t first = 0, uint64_t capacity = ~0ull) const
+    {
+        const uint64_t C = count(), n = first < C ? std::min(capacity, C - first) : 0;
+        std::vector<uint32_t> out((size_t)n * 2u);
+        if (n) check(vrc_delta_records(d_, first, n, out.data(), VRC_MEM_HOST, nullptr), "vrc_delta_records");
+        return out;
+    }
+    vrc_delta* handle() const { return d_; }
+
+private:
+    friend class HipVoxelVolume;
+    explicit HipVoxelDelta(vrc_delta* adopted) : d_(adopted) {}
+    vrc_delta* d_ = nullptr;
+};
+
 // What SVO::setCell + compileSVO are to the reference (svo.hpp:72, lsvo_utils.cpp:4), on the device and repeatable: the
 // occupancy of the S^3 volume stays resident, setCell() queues edits, commit() applies them and builds a NEW HipLSVO
 // (bit-identical to compileSVO of the voxel set).  A scene in use is never touched: keep the old HipLSVO until the frames
@@ -511,6 +561,21 @@ public:
         vrc_volume* v = nullptr;
         check(vrc_volume_clone(v_, &v), "vrc_volume_clone");
         return std::unique_ptr<HipVoxelVolume>(new HipVoxelVolume(v, device_));
+    }
+    // what changed from this volume to `after` (same depth and device); both are only read.  Synchronous.
+    HipVoxelDelta diff(HipVoxelVolume& after)
+    {
+        flush();
+        after.flush();
+        vrc_delta* d = nullptr;
+        check(vrc_delta_diff(v_, after.v_, &d, nullptr), "vrc_delta_diff");
+        return HipVoxelDelta(d);
+    }
+    // word ^= bits for every record: on the `before` of a diff it gives `after`, on `after` it gives `before`
+    void applyDelta(const HipVoxelDelta& delta, void* stream = nullptr)
+    {
+        flush();
+        check(vrc_delta_apply(delta.handle(), v_, stream), "vrc_delta_apply");
     }
     // xyz: n x 3 coordinates -> 0 / 1 each (0 outside the volume)
     std::vector<uint8_t> getVoxels(const std::vector<uint32_t>& xyz)
@@ -865,6 +930,54 @@ private:
     int device_ = 0;
     std::vector<uint32_t> queue_;
     bool queue_solid_ = true;
+};
+
+// Undo and redo for a HipVoxelVolume at the cost of what each step changed: one shadow clone and two stacks of deltas.  Edit
+// the volume with any call, then record(); only record() reads the two occupancies.  max_bytes (0: no limit) bounds the
+// record bytes of both stacks: record() drops the oldest undo steps beyond it, never the one it has just taken.  The volume
+// must outlive the history.  The pointers returned stay owned by the history and hold until its next call.
+class HipVoxelHistory {
+public:
+    explicit HipVoxelHistory(HipVoxelVolume& volume, uint64_t max_bytes = 0) : volume_(volume), shadow_(volume.clone()), max_bytes_(max_bytes) {}
+    // the step from the state at the last record / undo / redo to the volume as it is now, or nullptr when nothing changed
+    const HipVoxelDelta* record()
+    {
+        HipVoxelDelta delta = shadow_->diff(volume_);
+        if (!delta.count()) return nullptr;
+        shadow_->applyDelta(delta);
+        undo_.push_back(std::move(delta));
+        redo_.clear();
+        while (max_bytes_ && undo_.size() > 1 && bytes() > max_bytes_) undo_.erase(undo_.begin());
+        return &undo_.back();
+    }
+    // takes the last recorded step back (its stats name the box to redraw); nullptr with nothing to undo
+    const HipVoxelDelta* undo() { return move(undo_, redo_); }
+    const HipVoxelDelta* redo() { return move(redo_, undo_); }
+    size_t undoCount() const { return undo_.size(); }
+    size_t redoCount() const { return redo_.size(); }
+    // record bytes held by both stacks (the shadow clone's occupancy is not counted)
+    uint64_t bytes() const
+    {
+        uint64_t n = 0;
+        for (const HipVoxelDelta& d : undo_) n += d.bytes();
+        for (const HipVoxelDelta& d : redo_) n += d.bytes();
+        return n;
+    }
+
+private:
+    const HipVoxelDelta* move(std::vector<HipVoxelDelta>& source, std::vector<HipVoxelDelta>& sink)
+    {
+        if (source.empty()) return nullptr;
+        volume_.applyDelta(source.back());
+        shadow_->applyDelta(source.back());
+        sink.push_back(std::move(source.back()));
+        source.pop_back();
+        return &sink.back();
+    }
+    HipVoxelVolume& volume_;
+    std::unique_ptr<HipVoxelVolume> shadow_;
+    uint64_t max_bytes_ = 0;
+    std::vector<HipVoxelDelta> undo_, redo_;
 };
 
 inline void HipVoxelLabels::select(const std::vector<uint8_t>& keep, HipVoxelVolume& dst, int op) const

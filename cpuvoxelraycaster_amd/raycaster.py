@@ -363,6 +363,25 @@ class VoxelVolume:
         other.depth, other.device = self.depth, self.device
         return other
 
+    def diff(self, after):
+        """What changed from this volume to `after` (same depth and device), as a VoxelDelta: one record per occupancy word
+        that differs (include/vrc.h: vrc_delta_diff).  Both volumes are only read.  Synchronous."""
+        handle, stats = C.c_void_p(), capi.DeltaStats()
+        check(capi.load().vrc_delta_diff(self._h, after._h, C.byref(handle), C.byref(stats)))
+        return VoxelDelta(handle, stats, self.depth, self.device)
+
+    def applyDelta(self, delta, stream=None):
+        """word ^= bits for every record of the delta: on the `before` of a diff it gives `after`, on `after` it gives
+        `before` (undo and redo are one call), on an empty volume the set of changed voxels.  Asynchronous on `stream`."""
+        check(capi.load().vrc_delta_apply(delta._h, self._h, ptr(stream)))
+
+    def deltaFromRecords(self, records):
+        """a VoxelDelta for this volume's depth and device from caller records (VoxelDelta.fromRecords)"""
+        return VoxelDelta.fromRecords(self.depth, records, self.device)
+
+    def deltaFromRecordsDevice(self, n, records_ptr):
+        return VoxelDelta.fromRecordsDevice(self.depth, n, records_ptr, self.device)
+
     def getVoxels(self, xyz):
         """uint8 0 / 1 per (n, 3) voxel coordinate, 0 outside the volume.  Synchronous."""
         xyz = np.ascontiguousarray(xyz, np.uint32).reshape(-1, 3)
@@ -1167,6 +1186,140 @@ class VoxelDistance:
         if getattr(self, "_h", None) is not None and self._h:
             capi.load().vrc_distance_destroy(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VoxelDelta:
+    """The difference of two volumes, resident on the device as records {word, bits} in ascending word order
+    (include/vrc.h: vrc_delta_*): a snapshot made by VoxelVolume.diff or from caller records.  `stats` is a capi.DeltaStats
+    (words, voxels, lo, hi -- the box of the changed voxels, hi exclusive), `count` the number of records.  Applying it
+    (VoxelVolume.applyDelta) flips the changed voxels: it is its own inverse."""
+
+    def __init__(self, handle, stats, depth, device):
+        self._h, self.stats, self.depth, self.device = handle, stats, depth, device
+        self.count = int(stats.words)
+
+    @classmethod
+    def fromRecords(cls, depth, records, device=0):
+        """from capi.DELTA_RECORD_DTYPE records (or anything that reshapes to (n, 2) uint32: word, bits) in host memory --
+        another rank's, a saved history's; a list that is not strictly ascending in word, names a word beyond the volume or
+        holds bits == 0 raises VrcError with the first offending index"""
+        records = np.asarray(records)
+        if records.dtype != capi.DELTA_RECORD_DTYPE:
+            records = np.ascontiguousarray(records, np.uint32).reshape(-1, 2)
+        records = np.ascontiguousarray(records)
+        return cls._create(depth, records.shape[0], ptr(records) if records.shape[0] else None, capi.VRC_MEM_HOST, device)
+
+    @classmethod
+    def fromRecordsDevice(cls, depth, n, records_ptr, device=0):
+        """the same over n x 2 uint32 in device memory, copied into the object device to device; synchronous"""
+        return cls._create(depth, n, ptr(records_ptr), capi.VRC_MEM_DEVICE, device)
+
+    @classmethod
+    def _create(cls, depth, n, records, mem, device):
+        handle, stats = C.c_void_p(), capi.DeltaStats()
+        check(capi.load().vrc_delta_create(int(depth), int(device), int(n), records, mem, C.byref(handle), C.byref(stats)))
+        return cls(handle, stats, depth, device)
+
+    def records(self, first=0, capacity=None):
+        """the records [first, first + capacity) that exist, as capi.DELTA_RECORD_DTYPE (word, bits)"""
+        if capacity is None:
+            capacity = max(self.count - first, 0)
+        out = np.zeros(min(capacity, max(self.count - first, 0)), capi.DELTA_RECORD_DTYPE)
+        check(capi.load().vrc_delta_records(self._h, first, len(out), ptr(out) if len(out) else None, capi.VRC_MEM_HOST, None))
+        return out
+
+    def recordsDevice(self, first, capacity, out_ptr, stream=None):
+        """the same into device memory, asynchronous on `stream`"""
+        check(capi.load().vrc_delta_records(self._h, first, capacity, ptr(out_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def bytes(self):
+        return int(capi.load().vrc_delta_bytes(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            capi.load().vrc_delta_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VoxelHistory:
+    """Undo and redo for a VoxelVolume at the cost of what each step changed: one shadow clone of the volume and two stacks of
+    VoxelDelta.  Edit the volume with any call, then record(); only record() reads the two occupancies, undo() and redo()
+    cost what their delta holds.  max_bytes (None: no limit) bounds the record bytes of both stacks: record() drops the
+    oldest undo steps beyond it, never the one it has just taken.  The deltas returned stay owned by the history."""
+
+    def __init__(self, volume, max_bytes=None):
+        self.volume, self.max_bytes = volume, max_bytes
+        self._shadow = volume.clone()
+        self._undo, self._redo = [], []
+
+    def record(self):
+        """the step from the state at the last record / undo / redo to the volume as it is now: its VoxelDelta, pushed on
+        the undo stack (the redo stack is cleared), or None when nothing changed"""
+        delta = self._shadow.diff(self.volume)
+        if not delta.count:
+            delta.close()
+            return None
+        self._shadow.applyDelta(delta)
+        self._undo.append(delta)
+        self._drop(self._redo, 0)
+        if self.max_bytes is not None:
+            while len(self._undo) > 1 and self.bytes() > self.max_bytes:
+                self._drop(self._undo, len(self._undo) - 1)
+        return delta
+
+    def undo(self):
+        """takes the last recorded step back; returns its VoxelDelta (stats.lo / hi: what to redraw), None with nothing to undo"""
+        return self._move(self._undo, self._redo)
+
+    def redo(self):
+        """the mirror of undo()"""
+        return self._move(self._redo, self._undo)
+
+    def _move(self, source, sink):
+        if not source:
+            return None
+        delta = source.pop()
+        self.volume.applyDelta(delta)
+        self._shadow.applyDelta(delta)
+        sink.append(delta)
+        return delta
+
+    @staticmethod
+    def _drop(stack, keep):
+        """closes all but the newest `keep` entries"""
+        while len(stack) > keep:
+            stack.pop(0).close()
+
+    @property
+    def undoCount(self):
+        return len(self._undo)
+
+    @property
+    def redoCount(self):
+        return len(self._redo)
+
+    def bytes(self):
+        """record bytes held by both stacks (the shadow clone's occupancy is not counted)"""
+        return sum(d.bytes() for d in self._undo + self._redo)
+
+    def close(self):
+        self._drop(self._undo, 0)
+        self._drop(self._redo, 0)
+        if self._shadow is not None:
+            self._shadow.close()
+            self._shadow = None
 
     def __del__(self):
         try:

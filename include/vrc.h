@@ -398,7 +398,7 @@ int vrc_affine_place_box(const float rot[9], float scale, const float src_pivot[
                          const uint32_t src_lo[3], const uint32_t src_hi[3], uint32_t dst_depth,
                          vrc_affine *map, uint32_t dst_lo[3], uint32_t dst_hi[3]);
 /* A new volume with src's depth, device, occupancy (after every edit issued so far) and albedo tables: the undo
- * snapshot.  Synchronous. */
+ * snapshot.  Synchronous.  The cheaper undo step is vrc_delta_diff against one shadow clone: 8 bytes per changed word. */
 int vrc_volume_clone(vrc_volume *src, vrc_volume **out);
 /* solid_out[i] = 0 / 1 for voxel xyz[3i..3i+2], 0 outside the volume.  counts[i] = solid voxels in box i (n x 6 uint32 as
  * for vrc_volume_fill_boxes, clipped; empty or inverted = 0), so one whole-volume box equals vrc_volume_solid_count. */
@@ -1011,6 +1011,74 @@ typedef struct vrc_piece_clearance {     /* 64 bytes */
 int vrc_rigid_clearance(const vrc_labels *l, const uint8_t *keep /* C bytes, NULL = all */,
                         const vrc_affine *maps /* C */, const uint32_t *boxes /* C x 6 lo,hi; NULL = all of the field */,
                         const vrc_distance *field, vrc_piece_clearance *out /* C */, int mem, void *stream);
+
+/* Deltas: the difference of two volumes as a compact list of changed occupancy words, on the device -- the undo / redo step
+ * (an undo stack of clones costs a whole occupancy per step, 16 MiB at 512^3 and 128 MiB at 1024^3, where an edit changes a
+ * few hundred words), what carries an edit from the rank that made it to the replicas of the other ranks, and the answer to
+ * "what did that edit change".
+ *
+ * Key, word, bit.  A voxel's key is the one of the components above: with n = S/2 and B = ((x>>1) n + (y>>1)) n + (z>>1),
+ * key = 8 B + (z&1) 4 + (y&1) 2 + (x&1).  Its occupancy word is W = key >> 5 and its bit is key & 31.  A volume of depth d
+ * has 8^d / 32 words: 2 at 4^3 and 2^25 at 1024^3.
+ * Delta.  For two volumes `before` and `after` of one depth on one device, the delta is the list of records
+ * { uint32 word, uint32 bits } (8 bytes each) that holds one record for every W with bits = before[W] ^ after[W] != 0, in
+ * strictly ascending W.  It is unique and does not depend on scheduling; in numpy, W = flatnonzero(a ^ b), bits = (a ^ b)[W].
+ * Apply.  dst[W] ^= bits for every record.  Applied to `before` it gives `after`, applied to `after` it gives `before`: one
+ * object serves undo and redo.  Applied to an empty volume it gives the set of changed voxels as a volume, which
+ * vrc_volume_copy_region intersects with either state.
+ * Stats.  words = the number of records, voxels = the sum of popcount(bits), lo / hi = the bounding box of the changed voxels
+ * in setCell coordinates, hi exclusive as in vrc_component; an empty delta has words = voxels = 0 and lo = hi = 0.
+ *
+ * A vrc_delta is a snapshot as vrc_labels is: it owns its memory (8 bytes per record, nothing for an empty one), is never
+ * written after its creator returns, and stays valid when the volumes change or are destroyed.
+ *
+ * vrc_delta_diff is synchronous (the host reads the record count to allocate exactly 8 * words bytes), on the NULL stream,
+ * ordered behind the last asynchronous edit of both volumes; it only reads them and is not recorded as an edit of either.
+ * Its scratch (1/256 of an occupancy) belongs to the call and is freed before it returns: vrc_volume_edit_scratch_bytes of both
+ * volumes is unchanged.  NULLs (stats may be NULL), before == after, different depths and different devices are
+ * VRC_ERR_INVALID, refused before any device call.  The device (csrc/vrc_delta.hip) counts the changed words per workgroup of
+ * 256 words -- reducing the voxel count and the box on the way --, scans the counts, and emits; each of the two passes over
+ * the fields reads both once, four consecutive words per lane.
+ * vrc_delta_create builds a delta from caller records (n x 2 uint32: word, bits) -- another rank's, a saved history's, made by
+ * hand.  Synchronous.  With VRC_MEM_DEVICE the records are read in place by a device-to-device copy into the object, so a
+ * broadcast can land in the buffer handed to it; they must be complete when the call is made.  One kernel holds the list to
+ * the rule -- word strictly ascending, word < 8^depth / 32, bits != 0 -- and reduces the stats.  A list that breaks it is
+ * VRC_ERR_INVALID, vrc_last_error names the FIRST offending record index, and no object is returned.  Depth 2..10; n == 0
+ * with records == NULL is legal.  stats may be NULL.
+ * vrc_delta_get_stats copies the stats kept in the object, vrc_delta_bytes is 8 * count: no device call.
+ * vrc_delta_records has the window of vrc_labels_components: the records of [first, first + capacity) that exist go to
+ * out[0..] (two uint32 each), nothing beyond them is touched, first >= count writes nothing, capacity == 0 with out == NULL is
+ * legal.  VRC_MEM_HOST is staged and synchronous, VRC_MEM_DEVICE is one copy, asynchronous on `stream`.
+ * vrc_delta_apply is asynchronous on `stream`, ordered behind dst's last asynchronous edit and recorded as dst's last edit.
+ * One lane takes one record; its word is that lane's alone because the words of a list are distinct, so it is a plain load,
+ * XOR and store.  The warning of vrc_volume_copy_region holds: do not edit dst on ANOTHER stream before the apply has run.
+ * A depth or device mismatch and NULLs are VRC_ERR_INVALID; an empty delta is a no-op that returns VRC_OK.
+ * Times: profiles/edit/bench_delta.json (tools/bench_edit.py --delta; 512^3 FastNoise terrain, MI355X, whole calls, device time by
+ * events, median of 5, A B A B next to vrc_volume_clone and to a device-to-device copy of one 16 MiB occupancy, 0.008 ms).
+ * vrc_delta_diff: 0.072 ms after a radius-8 sphere dig (70 records, 560 bytes), 0.113 ms after dropLoose on the fall benchmark's
+ * scene (74877 records, 0.57 MiB), 0.151 ms terrain against empty (300737 records, 2.3 MiB, 14 % of a clone's bytes: the terrain
+ * fills less than the half of the words one might expect), next to 0.037 ms for vrc_volume_clone.  vrc_delta_apply: 0.009 ms in
+ * all three cases.  So an undo step costs 2 to 4 times a clone's TIME and a 1/30000 to 1/7 of its memory.  The diff is far above
+ * the floor of its traffic (two reads of both occupancies, 64 MiB: two of those copies, about 0.02 ms): the call allocates and
+ * frees its scratch and its records and reads the count back between scan and emit, and the passes have not been timed apart, so
+ * how the rest divides between that host work, the three launches and the kernels is not known. */
+typedef struct vrc_delta vrc_delta;      /* a snapshot: the records of a difference, resident on the volumes' device */
+typedef struct vrc_delta_stats {         /* 48 bytes */
+    uint64_t words;
+    uint64_t voxels;
+    uint32_t lo[3], hi[3];
+    uint32_t reserved[2];                /* 0 */
+} vrc_delta_stats;
+int vrc_delta_diff(vrc_volume *before, vrc_volume *after, vrc_delta **out, vrc_delta_stats *stats);
+int vrc_delta_create(uint32_t depth, int device, uint64_t n, const uint32_t *records /* n x 2 */, int mem,
+                     vrc_delta **out, vrc_delta_stats *stats);
+int vrc_delta_destroy(vrc_delta *d);
+uint64_t vrc_delta_count(const vrc_delta *d);
+uint32_t vrc_delta_depth(const vrc_delta *d);
+uint64_t vrc_delta_bytes(const vrc_delta *d);      /* 8 * count; pure host bookkeeping */
+int vrc_delta_get_stats(const vrc_delta *d, vrc_delta_stats *out);   /* host copy kept in the object, no device call */
+int vrc_delta_records(const vrc_delta *d, uint64_t first, uint64_t capacity, uint32_t *out, int mem, void *stream);
+int vrc_delta_apply(const vrc_delta *d, vrc_volume *dst, void *stream);
 
 /* ---- dense grid: Grid3D<X,Y,Z> (grid_3d.hpp:10-138) ------------------- */
 
