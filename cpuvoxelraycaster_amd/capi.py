@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(PKG, "libvrc_hip.so")
 VRC_MEM_HOST, VRC_MEM_DEVICE = 0, 1
 VRC_COPY_REPLACE, VRC_COPY_OR, VRC_COPY_ANDNOT = 0, 1, 2
 VRC_CONNECT_FACES, VRC_CONNECT_ALL = 6, 26
+VRC_CELLS_FACES, VRC_CELLS_ALL = 6, 26
 VRC_FLOOD_SOLID, VRC_FLOOD_EMPTY = 0, 1
 VRC_NO_COMPONENT = 0xffffffff
 VRC_DISTANCE_NONE = 0xffffffff
@@ -246,6 +247,8 @@ SYMBOLS = {
     "vrc_delta_get_stats": (_int, [_vp, C.POINTER(DeltaStats)]),
     "vrc_delta_records": (_int, [_vp, _u64, _u64, _vp, _int, _vp]),
     "vrc_delta_apply": (_int, [_vp, _vp, _vp]),
+    "vrc_cells_step": (_int, [_vp, _vp, _int, _u32, _u32, _int, _vp, _int, _vp]),
+    "vrc_cells_fill_random": (_int, [_vp, _u32, _u64, _vp, _int, _vp]),
     "vrc_volume_xor_mesh": (_int, [_vp, _u64, _vp, _int, _vp]),
     "vrc_volume_surface_count": (_int, [_vp, _int, _vp]),
     "vrc_volume_extract_surface": (_int, [_vp, _int, _int, _u64, _u64, _vp, _vp, _int, _vp]),

@@ -5,7 +5,8 @@
 // with the selection by distance that grow / shrink / hollow are made of (vrc_volume_distance_field, vrc_distance_*;
 // kernels in vrc_distance.hip), and the travel-distance field from a set of seeds, kept in the same snapshot object, with the
 // routes read off it (vrc_travel_field, vrc_travel_trace_paths; kernels in vrc_travel.hip), and the difference of two volumes as a list of
-// changed words (vrc_delta_diff, vrc_delta_*; kernels in vrc_delta.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
+// changed words (vrc_delta_diff, vrc_delta_*; kernels in vrc_delta.hip).  Beside them, because they take two volumes under the same ordering
+// rule, the automaton step and the seeded fill (vrc_cells_*; kernels in vrc_cells.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
 // event and no scratch: its host-memory calls stage in a block of their own, and what it selects or places goes into a volume
 // as an edit of that volume (staged_call in vrc_volume_state.h; the ordering of every entry point: the table in DESIGN.md).
 #include <hip/hip_runtime.h>
@@ -14,6 +15,8 @@
 #include <new>
 
 #include "../../include/vrc.h"
+#include "vrc_box_words.h"
+#include "vrc_cells.h"
 #include "vrc_components.h"
 #include "vrc_delta.h"
 #include "vrc_distance.h"
@@ -811,5 +814,54 @@ extern "C" int vrc_delta_apply(const vrc_delta* d, vrc_volume* dst, void* stream
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
+    return done(e, what);
+}
+
+// ---- cells: a neighbour-count step between two volumes and the seeded fill (the rules: include/vrc.h; the kernels: vrc_cells.hip) ----
+
+extern "C" int vrc_cells_step(vrc_volume* dst, vrc_volume* src, int neighbours, uint32_t birth_mask, uint32_t survive_mask, int outside,
+                              uint64_t* changed, int mem, void* stream)
+{
+    const char* what = "vrc_cells_step";
+    if (!dst || !src) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (dst == src) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
+    if (dst->depth != src->depth) return vrc::fail(VRC_ERR_INVALID, "%s: volumes of depths %u and %u", what, dst->depth, src->depth);
+    if (dst->device != src->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, dst->device, src->device);
+    if (neighbours != VRC_CELLS_FACES && neighbours != VRC_CELLS_ALL) return vrc::fail(VRC_ERR_INVALID, "%s: neighbours %d is neither 6 nor 26", what, neighbours);
+    const uint32_t counts = (2u << neighbours) - 1u;                    // bits 0 .. neighbours
+    if (birth_mask & ~counts) return vrc::fail(VRC_ERR_INVALID, "%s: birth_mask 0x%x has a bit above bit %d", what, birth_mask, neighbours);
+    if (survive_mask & ~counts) return vrc::fail(VRC_ERR_INVALID, "%s: survive_mask 0x%x has a bit above bit %d", what, survive_mask, neighbours);
+    if (outside != 0 && outside != 1) return vrc::fail(VRC_ERR_INVALID, "%s: outside %d is neither 0 nor 1", what, outside);
+    if (changed)
+        if (const int rc = check_mem(what, mem)) return rc;
+    hipError_t e = hipSetDevice(dst->device);
+    if (e == hipSuccess) e = order_behind_edits(src, (hipStream_t)stream);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    // the counter is the call's one list: in host form it is staged in 8 bytes of the call's own and the call is synchronous
+    const Call call = volume_call(dst->device, changed ? mem : VRC_MEM_DEVICE, stream, dst, true);
+    const StagePart parts[] = {{changed, 8u, STAGE_OUT}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        const hipError_t zeroed = d[0] ? hipMemsetAsync(d[0], 0, 8u, call.st) : hipSuccess;
+        if (zeroed == hipSuccess)
+            vrc::cells_step_run(dst->d_bricks, src->d_bricks, dst->depth, neighbours, birth_mask, survive_mask, outside, (unsigned long long*)d[0], call.st);
+        return zeroed;
+    });
+}
+
+extern "C" int vrc_cells_fill_random(vrc_volume* v, uint32_t seed, uint64_t threshold, const uint32_t* lo_hi, int op, void* stream)
+{
+    const char* what = "vrc_cells_fill_random";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (threshold > (1ull << 32)) return vrc::fail(VRC_ERR_INVALID, "%s: threshold %llu above 2^32", what, (unsigned long long)threshold);
+    if (const int rc = check_op(what, op)) return rc;
+    const uint32_t S = 1u << v->depth, whole[6] = {0u, 0u, 0u, S, S, S};
+    uint32_t lo[3], hi[3];
+    if (!clip_box(lo_hi ? lo_hi : whole, S, lo, hi)) return VRC_OK;      // empty, inverted or wholly outside: nothing to write
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(v->device);
+    if (e == hipSuccess) e = order_behind_edits(v, st);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    vrc::cells_fill_random_run(v->d_bricks, v->depth, seed, threshold, lo, hi, op, st);
+    if ((e = hipGetLastError()) == hipSuccess) e = finish(v, VRC_MEM_DEVICE, st, true);
     return done(e, what);
 }

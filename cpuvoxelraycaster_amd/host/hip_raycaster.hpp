@@ -577,6 +577,58 @@ public:
         flush();
         check(vrc_delta_apply(delta.handle(), v_, stream), "vrc_delta_apply");
     }
+    // One step of the neighbour-count automaton (include/vrc.h: vrc_cells_step) from this volume into dst, which is written
+    // whole: with c the solid ones among a voxel's 6 or 26 neighbours (those beyond the faces solid with `outside`), a
+    // solid voxel stays if bit c of survive_mask is set and an empty one becomes solid if bit c of birth_mask is.
+    // changed = nullptr: asynchronous on `stream`; else *changed = the voxels that differ, and the call is synchronous.
+    void cellStep(HipVoxelVolume& dst, uint32_t birth_mask, uint32_t survive_mask, int neighbours = VRC_CELLS_ALL, bool outside = false,
+                  uint64_t* changed = nullptr, void* stream = nullptr)
+    {
+        flush();
+        dst.flush();
+        check(vrc_cells_step(dst.v_, v_, neighbours, birth_mask, survive_mask, outside ? 1 : 0, changed, VRC_MEM_HOST, stream), "vrc_cells_step");
+    }
+    // Up to `steps` steps in place, ping-pong with one scratch volume; ends early at a step that changes nothing.  Returns
+    // the number of steps that changed a voxel.
+    uint32_t automaton(uint32_t steps, uint32_t birth_mask, uint32_t survive_mask, int neighbours = VRC_CELLS_ALL, bool outside = false)
+    {
+        if (!steps) return 0;
+        HipVoxelVolume scratch(depth(), device_);
+        HipVoxelVolume *src = this, *dst = &scratch;
+        uint32_t taken = 0;
+        while (taken < steps) {
+            uint64_t changed = 0;
+            src->cellStep(*dst, birth_mask, survive_mask, neighbours, outside, &changed);
+            if (!changed) break;                 // dst equals src
+            std::swap(src, dst);
+            ++taken;
+        }
+        if (src != this) {
+            const uint32_t S = 1u << depth();
+            const uint32_t zero[3] = {0, 0, 0}, all[3] = {S, S, S};
+            const int32_t at[3] = {0, 0, 0};
+            copyRegion(scratch, zero, all, at);  // the scratch volume's destructor waits for it
+        }
+        return taken;
+    }
+    // the majority of the 27 cells around every voxel, itself included, `iterations` times in place
+    void smooth(uint32_t iterations = 1, bool outside = false) { automaton(iterations, 0x7FFC000u, 0x7FFE000u, VRC_CELLS_ALL, outside); }
+    // clears the solid voxels without a solid face neighbour
+    void removeSpecks() { automaton(1, 0u, 0x7Eu, VRC_CELLS_FACES, false); }
+    // A seeded random voxel set R, the hash of (seed, x, y, z) below round(density 2^32) (include/vrc.h:
+    // vrc_cells_fill_random): inside box (lo x y z, hi x y z exclusive; nullptr = the whole volume) this volume takes (op) R.
+    void fillRandom(uint32_t seed, double density, const uint32_t box[6] = nullptr, int op = VRC_COPY_OR, void* stream = nullptr)
+    {
+        flush();
+        if (!(density >= 0.0 && density <= 1.0)) throw std::invalid_argument("HipVoxelVolume::fillRandom: density not in [0, 1]");
+        check(vrc_cells_fill_random(v_, seed, (uint64_t)std::llround(density * 4294967296.0), box, op, stream), "vrc_cells_fill_random");
+    }
+    // caves from a seed: the fill of the whole volume, then `steps` rounds of smooth with everything beyond the faces solid
+    void caves(uint32_t seed, double density, uint32_t steps)
+    {
+        fillRandom(seed, density, nullptr, VRC_COPY_REPLACE);
+        smooth(steps, true);
+    }
     // xyz: n x 3 coordinates -> 0 / 1 each (0 outside the volume)
     std::vector<uint8_t> getVoxels(const std::vector<uint32_t>& xyz)
     {

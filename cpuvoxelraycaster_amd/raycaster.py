@@ -259,6 +259,17 @@ def free_radius(min_value, S):
     return np.array([int(S) if v == capi.VRC_DISTANCE_NONE else isqrt(int(v) - 1) if v else -1 for v in values.tolist()], np.int64)
 
 
+def count_mask(counts):
+    """the bit mask of a cell rule (VoxelVolume.cellStep): an int as it is, an iterable of neighbour counts as the OR of
+    1 << count"""
+    if isinstance(counts, (int, np.integer)):
+        return int(counts)
+    mask = 0
+    for c in counts:
+        mask |= 1 << int(c)
+    return mask
+
+
 class VoxelVolume:
     """Device-resident editable occupancy of an S^3 volume (include/vrc.h: vrc_volume_*).  Edits are batched; commit()
     builds a new immutable LSVO on the device, bit-identical to compileSVO of the current voxel set."""
@@ -381,6 +392,84 @@ class VoxelVolume:
 
     def deltaFromRecordsDevice(self, n, records_ptr):
         return VoxelDelta.fromRecordsDevice(self.depth, n, records_ptr, self.device)
+
+    countMask = staticmethod(count_mask)
+
+    def cellStep(self, birth, survive, neighbours=26, outside=False, dst=None, count_changed=False, stream=None):
+        """One step of the neighbour-count automaton (include/vrc.h: vrc_cells_step): with c the number of solid voxels among
+        a voxel's 6 or 26 neighbours (those beyond the faces solid with `outside`), a solid voxel stays if bit c of `survive`
+        is set and an empty one becomes solid if bit c of `birth` is; both are bit masks or iterables of counts.  This
+        volume is only read; the result is written whole into `dst`, a new volume by default.  Returns dst -- or, with
+        count_changed, (dst, the number of voxels that differ), which makes the call synchronous; else it is asynchronous on
+        `stream`."""
+        made = dst is None
+        if made:
+            dst = VoxelVolume(self.depth, self.device)
+        changed = C.c_uint64()
+        try:
+            check(capi.load().vrc_cells_step(dst._h, self._h, int(neighbours), self.countMask(birth), self.countMask(survive), int(outside),
+                                             C.cast(C.byref(changed), C.c_void_p) if count_changed else None, capi.VRC_MEM_HOST, ptr(stream)))
+        except Exception:
+            if made:
+                dst.close()
+            raise
+        return (dst, int(changed.value)) if count_changed else dst
+
+    def cellStepDevice(self, dst, birth, survive, changed_ptr, neighbours=26, outside=False, stream=None):
+        """the same with the count in one device uint64 (or None), zeroed and written in stream order: asynchronous"""
+        check(capi.load().vrc_cells_step(dst._h, self._h, int(neighbours), self.countMask(birth), self.countMask(survive), int(outside),
+                                         ptr(changed_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def automaton(self, steps, birth, survive, neighbours=26, outside=False):
+        """Up to `steps` steps of cellStep in place, ping-pong with one scratch volume that lives for the call.  It ends
+        early at a fixed point, a step that changes nothing; the result is left in this volume.  Returns the steps taken:
+        the number of steps that changed a voxel, at most `steps`."""
+        taken = 0
+        if steps <= 0:
+            return taken
+        src, dst = self, VoxelVolume(self.depth, self.device)
+        scratch = dst
+        try:
+            while taken < steps:
+                _, changed = src.cellStep(birth, survive, neighbours, outside, dst, count_changed=True)
+                if not changed:
+                    break                                     # dst equals src: whichever of the two this volume is, it holds the result
+                src, dst = dst, src
+                taken += 1
+            if src is not self and taken:
+                size = 1 << self.depth
+                self.copyRegion(src, (0, 0, 0), (size, size, size), (0, 0, 0))
+        finally:
+            scratch.close()                                   # waits for the copy
+        return taken
+
+    def smooth(self, iterations=1, outside=False):
+        """The majority vote of the 27 cells around every voxel, itself included, `iterations` times in place (ending early
+        at a fixed point): solid where at least 14 of the 27 are.  Rounds a voxelised model, fills pin-holes, removes
+        specks.  With `outside` everything beyond the faces votes solid."""
+        self.automaton(iterations, range(14, 27), range(13, 27), capi.VRC_CELLS_ALL, outside)
+        return self
+
+    def removeSpecks(self):
+        """Clears every solid voxel none of whose six face neighbours is solid (the faces of the volume are empty); in place"""
+        self.automaton(1, 0, range(1, 7), capi.VRC_CELLS_FACES, False)
+        return self
+
+    def fillRandom(self, seed, density, box=None, op=capi.VRC_COPY_OR, stream=None):
+        """A seeded random voxel set R (include/vrc.h: vrc_cells_fill_random): a hash of (seed, x, y, z) below
+        round(density 2^32), the same field at every depth and in every box.  Inside `box` (lo x y z, hi x y z exclusive,
+        clipped; the whole volume by default) the volume takes (op) R.  Asynchronous on `stream`."""
+        if not 0.0 <= density <= 1.0:
+            raise ValueError(f"fillRandom: density {density} not in [0, 1]")
+        lo_hi = None if box is None else np.ascontiguousarray(box, np.uint32).reshape(6)
+        check(capi.load().vrc_cells_fill_random(self._h, int(seed) & 0xFFFFFFFF, int(np.floor(density * 4294967296.0 + 0.5)), ptr(lo_hi), int(op), ptr(stream)))
+        return self
+
+    def caves(self, seed, density, steps):
+        """Procedural caves in place: the random fill of the whole volume (REPLACE), then `steps` rounds of smooth with
+        everything beyond the faces solid, so that the caves close towards the faces"""
+        self.fillRandom(seed, density, None, capi.VRC_COPY_REPLACE)
+        return self.smooth(steps, outside=True)
 
     def getVoxels(self, xyz):
         """uint8 0 / 1 per (n, 3) voxel coordinate, 0 outside the volume.  Synchronous."""

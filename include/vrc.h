@@ -1080,6 +1080,53 @@ int vrc_delta_get_stats(const vrc_delta *d, vrc_delta_stats *out);   /* host cop
 int vrc_delta_records(const vrc_delta *d, uint64_t first, uint64_t capacity, uint32_t *out, int mem, void *stream);
 int vrc_delta_apply(const vrc_delta *d, vrc_volume *dst, void *stream);
 
+/* Cells: the local question -- how many of a voxel's neighbours are solid -- as one step of a neighbour-count automaton,
+ * and a voxel set from a seed.  Clean-up (specks a brush or a fracture leaves, pin-holes), rounding by a majority vote,
+ * caves from a random fill and a few rounds of a rule, 3-D Life: all are one stencil.  (vrc_distance_select's grow / shrink is
+ * another operator: it moves the whole surface by r and costs a distance transform.)
+ *
+ * vrc_cells_step.  For every voxel p of src, c(p) is the number of solid voxels among its `neighbours` neighbours: the six
+ * that share a face (VRC_CELLS_FACES), or the 26 that share a face, an edge or a corner (VRC_CELLS_ALL).  A neighbour outside
+ * the volume counts as empty when outside == 0 and as solid when outside == 1.  Then
+ *     dst(p) = (survive_mask >> c(p)) & 1  if src(p) is solid,  (birth_mask >> c(p)) & 1  if it is empty.
+ * dst is written whole, whatever it held; src is only read.  The result is unique and does not depend on scheduling.
+ * `changed` may be NULL; otherwise it receives the number of voxels with dst(p) != src(p), and `mem` says where it lives:
+ * VRC_MEM_HOST makes the call synchronous, VRC_MEM_DEVICE is one device uint64_t, zeroed and written in stream order -- a
+ * caller that iterates to a fixed point reads it once every few steps.  The ordering is vrc_volume_copy_region's: the call is
+ * asynchronous on `stream`, runs behind the last asynchronous edits of both volumes and is recorded as dst's last edit.
+ * VRC_ERR_INVALID with the function's name, before any device call: NULL volumes, dst == src, different depths or devices,
+ * neighbours not 6 or 26, a mask bit above bit `neighbours` (no count reaches it: a typo, not a rule), outside not 0 or 1,
+ * and a bad `mem` when changed is given.  No scratch: vrc_volume_edit_scratch_bytes of both volumes is unchanged.
+ * The device (csrc/vrc_cells.hip): one lane owns one destination word (2 x 2 x 8 voxels) and writes it once.  It counts all 32
+ * voxels at a time on bit-planes: the nine brick rows around the word are shifted to the word's bit positions with the
+ * flood's shifts, a full adder along x gives 2 planes, along y 4, along z 5 -- the count of the 27 cells with the centre,
+ * which is folded into the rule (a solid centre reads survive_mask << 1) -- and the rule is a select tree over the planes with
+ * the masks' bits as leaves.  The six-neighbour count is a direct sum of six planes.
+ *
+ * vrc_cells_fill_random.  With L(u), the 32-bit finaliser
+ *     u ^= u >> 16;  u *= 0x7feb352d;  u ^= u >> 15;  u *= 0x846ca68b;  u ^= u >> 16      (all mod 2^32),
+ * h(x, y, z) = L(L(L(L(seed) ^ x) ^ y) ^ z) and R(p) = (h(p) < threshold), compared in 64 bits: threshold 0 selects nothing,
+ * 2^32 everything, a density d is threshold = round(d 2^32); above 2^32 is VRC_ERR_INVALID.  Inside the box lo_hi (6 uint32:
+ * lo inclusive, hi exclusive, clipped to the volume; NULL = the whole volume) v becomes R (VRC_COPY_REPLACE), v | R
+ * (VRC_COPY_OR) or v & ~R (VRC_COPY_ANDNOT); nothing outside the box is touched, and an empty or inverted box is a legal
+ * no-op.  The hash takes coordinates, not keys, so the field is the same at every depth and in every box.  The nesting
+ * order is deliberate: an occupancy word is 2 x 2 x 8 voxels, so it needs L(seed) once (the host computes it), 2 values for
+ * its x, 4 for its (x, y) and 32 for its z -- 38 evaluations of L for 32 voxels.  Asynchronous on `stream`, behind v's last
+ * asynchronous edit, recorded as v's last edit.  A NULL volume, a threshold above 2^32 and an unknown op are
+ * VRC_ERR_INVALID before any device call.
+ * Times: profiles/edit/bench_cells.json (tools/bench_edit.py --cells; 512^3 on the MI355X, device time by events around 20 calls in
+ * a row, median of 5, A B A B next to a whole-volume vrc_volume_copy_region, 0.060 ms, and vrc_volume_clone, 0.036 ms), alike on
+ * the FastNoise terrain and on a 0.5 random fill: a step with 6 neighbours 0.031 ms, with 26 neighbours 0.066 ms, the fill of the
+ * whole volume 0.060 ms.  With `changed` in device memory a step costs 0.038 / 0.076 ms on the terrain, where few workgroups
+ * change anything, and 0.21 ms on the random fill, where every one of 16384 workgroups adds to the same counter: ask for the
+ * count once every few steps. */
+#define VRC_CELLS_FACES 6      /* the six face neighbours  */
+#define VRC_CELLS_ALL   26     /* faces, edges and corners */
+int vrc_cells_step(vrc_volume *dst, vrc_volume *src, int neighbours, uint32_t birth_mask, uint32_t survive_mask, int outside,
+                   uint64_t *changed, int mem, void *stream);
+int vrc_cells_fill_random(vrc_volume *v, uint32_t seed, uint64_t threshold, const uint32_t *lo_hi /* 6, NULL = whole volume */,
+                          int op, void *stream);
+
 /* ---- dense grid: Grid3D<X,Y,Z> (grid_3d.hpp:10-138) ------------------- */
 
 /* cells[(x*Y + y)*Z + z] = Cell::Type (0 = Empty). */

@@ -178,6 +178,14 @@ over the occupancy a clone holds.
 Measured on an MI355X at 512^3: the diff 0.072 / 0.113 / 0.151 ms for 70 / 74877 / 300737 records next to 0.037 ms for the clone,
 the apply 0.009 ms in all three next to 0.008 ms for the copy.  Not timed apart: the allocations, the read-back and the three
 kernels of the diff.
+With --cells (printed and written to profiles/edit/bench_cells.json), the cell calls at 512^3, device time by events on the
+NULL stream, a sample = 20 calls in a row between two events, divided; one warm-up pair, A B A B in one process, `--pairs` pairs,
+median and range, on two inputs -- the FastNoise terrain and a fillRandom of density 0.5 -- each entry next to one of the library's existing read-once / write-once passes over the same
+16 MiB, timed in the same pair:
+  step_6 / step_26                   vrc_cells_step into a second volume, no counter       next to  copy_region (whole volume, REPLACE)
+  step_6_changed / step_26_changed   the same with `changed` in device memory              next to  clone (vrc_volume_clone, closed outside the events)
+  fill_random                        vrc_cells_fill_random of the whole volume, REPLACE    next to  copy_region
+and step_over_copy, the ratio of the medians.  The smoothing rule (majority of 27) and, with six neighbours, survive = 1 .. 6.
 No threshold is applied; the numbers are reported."""
 import argparse
 import json
@@ -1444,6 +1452,69 @@ def bench_delta(vrc, depth, pairs):
     return res
 
 
+def bench_cells(vrc, depth, pairs):
+    """vrc_cells_step and vrc_cells_fill_random next to vrc_volume_copy_region and vrc_volume_clone; see the module's text."""
+    import torch
+    S = 1 << depth
+    CALLS = 20                           # a single call is tens of microseconds: a sample times twenty in a row
+    res = {"size": S, "pairs": pairs, "calls_per_sample": CALLS, "occupancy_bytes": S ** 3 // 8}
+    counter = torch.zeros(1, dtype=torch.int64).cuda()
+    torch.cuda.synchronize()
+    birth26, survive26 = vrc.count_mask(range(14, 27)), vrc.count_mask(range(13, 27))
+    rules = {6: (0, vrc.count_mask(range(1, 7))), 26: (birth26, survive26)}
+
+    def timed_ab(fa, fb):
+        """A B A B, a sample = CALLS calls in a row between two events, divided; what a call returns is closed outside them"""
+        out = ([], [])
+        for i in range(pairs + 1):
+            for k, fn in enumerate((fa, fb)):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                made = [fn() for _ in range(CALLS)]
+                b.record()
+                b.synchronize()
+                for thing in made:
+                    if thing is not None:
+                        thing.close()
+                if i:
+                    out[k].append(a.elapsed_time(b) / CALLS)
+        return stat(out[0], 5), stat(out[1], 5)
+
+    def case(src):
+        dst, other = vrc.VoxelVolume(depth), vrc.VoxelVolume(depth)
+        one = {"solid_voxels": src.solidCount()}
+
+        def copy():
+            other.copyRegion(src, (0, 0, 0), (S, S, S), (0, 0, 0))
+
+        for neighbours, (birth, survive) in rules.items():
+            key = "step_%d" % neighbours
+            one[key] = {}
+            one[key]["ms"], one[key]["copy_region_ms"] = timed_ab(lambda: src.cellStepDevice(dst, birth, survive, None, neighbours), copy)
+            one[key]["step_over_copy"] = round(one[key]["ms"]["median"] / one[key]["copy_region_ms"]["median"], 3)
+            key += "_changed"
+            one[key] = {}
+            one[key]["ms"], one[key]["clone_ms"] = timed_ab(lambda: src.cellStepDevice(dst, birth, survive, counter.data_ptr(), neighbours), src.clone)
+            one[key]["changed"] = int(counter.cpu()[0])
+            one[key]["step_over_clone"] = round(one[key]["ms"]["median"] / one[key]["clone_ms"]["median"], 3)
+        one["fill_random"] = {}
+        one["fill_random"]["ms"], one["fill_random"]["copy_region_ms"] = timed_ab(lambda: dst.fillRandom(7, 0.5, None, vrc.capi.VRC_COPY_REPLACE) and None, copy)
+        one["fill_random"]["fill_over_copy"] = round(one["fill_random"]["ms"]["median"] / one["fill_random"]["copy_region_ms"]["median"], 3)
+        for v in (dst, other):
+            v.close()
+        return one
+
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    terrain = vrc.VoxelVolume.fromScene(scene)
+    res["terrain"] = case(terrain)
+    terrain.close()
+    scene.close()
+    noise = vrc.VoxelVolume(depth).fillRandom(1337, 0.5, None, vrc.capi.VRC_COPY_REPLACE)
+    res["random_0.5"] = case(noise)
+    noise.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--depths", type=int, nargs="+", default=[8, 9, 10])
@@ -1464,7 +1535,25 @@ def main():
     ap.add_argument("--travel", action="store_true", help="time vrc_travel_field next to vrc_volume_flood from the same seeds (depth 9 unless --depths is given)")
     ap.add_argument("--fracture", action="store_true", help="time vrc_fracture_label next to vrc_volume_distance_field + vrc_volume_label_components (depth 9 unless --depths is given)")
     ap.add_argument("--delta", action="store_true", help="time vrc_delta_diff / vrc_delta_apply next to vrc_volume_clone and a copy of one occupancy (depth 9 unless --depths is given)")
+    ap.add_argument("--cells", action="store_true", help="time vrc_cells_step / vrc_cells_fill_random next to vrc_volume_copy_region and vrc_volume_clone (depth 9 unless --depths is given)")
     args = ap.parse_args()
+    if args.cells:
+        if args.depths == [8, 9, 10]:
+            args.depths = [9]
+        import __graft_entry__ as g
+        g.build()
+        import torch
+        import cpuvoxelraycaster_amd as vrc
+        if not torch.cuda.is_available():
+            raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
+        out = {"bench": "edit_cells", "device": torch.cuda.get_device_name(0), "depths": {}}
+        for d in args.depths:
+            out["depths"][str(d)] = bench_cells(vrc, d, max(1, args.pairs))
+        print(json.dumps(out))
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_cells.json")
+        with open(path, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+        return
     if args.delta:
         if args.depths == [8, 9, 10]:
             args.depths = [9]
