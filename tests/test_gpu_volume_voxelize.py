@@ -2,7 +2,8 @@
 The expected occupancy is the numpy model of tests/voxelize_model.py (held against boxes, a fan and an exact orientation
 test in tests/test_volume_voxelize_host.py); every comparison is exact: the downloaded volume equals the model's array.
 Shapes are the smallest at which the kernels take another path: 4^3 (two brick rows to a word), 8^3 (one z word per
-column), 32^3 (four), 64^3 (more than one workgroup in the scan, a triangle split over several workgroups in the mark)."""
+column), 32^3 (four), 64^3 (more than one workgroup in the scan, a triangle split over several workgroups in the mark).
+The scan's other lane counts (2, 16, 32, 64 and two words a lane) and the stride of the mark loop: test_gpu_volume_voxelize_large.py."""
 
 import numpy as np
 import pytest
