@@ -101,6 +101,12 @@ class DeltaStats(C.Structure):
     _fields_ = [("words", C.c_uint64), ("voxels", C.c_uint64), ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("reserved", C.c_uint32 * 2)]
 
 
+class PackInfo(C.Structure):
+    """vrc_pack_info (include/vrc.h): the header fields of a sparse tile stream -- what vrc_pack_volume wrote or would write"""
+    _fields_ = [("depth", C.c_uint32), ("tiles", C.c_uint32), ("mixed_tiles", C.c_uint32), ("full_tiles", C.c_uint32),
+                ("partial_bricks", C.c_uint32), ("reserved", C.c_uint32), ("bytes", C.c_uint64), ("solid", C.c_uint64)]
+
+
 class Affine(C.Structure):
     """vrc_affine (include/vrc.h): the inverse map of vrc_volume_stamp_affine, m row-major with 16 fractional bits"""
     _fields_ = [("m", C.c_int32 * 9), ("reserved", C.c_int32), ("t", C.c_int64 * 3)]
@@ -247,6 +253,10 @@ SYMBOLS = {
     "vrc_delta_get_stats": (_int, [_vp, C.POINTER(DeltaStats)]),
     "vrc_delta_records": (_int, [_vp, _u64, _u64, _vp, _int, _vp]),
     "vrc_delta_apply": (_int, [_vp, _vp, _vp]),
+    "vrc_pack_bound": (_u64, [_u32]),
+    "vrc_pack_header": (_int, [_vp, _u64, C.POINTER(PackInfo)]),
+    "vrc_pack_volume": (_int, [_vp, _vp, _u64, C.POINTER(PackInfo), _int]),
+    "vrc_unpack_volume": (_int, [_vp, _vp, _u64, _int]),
     "vrc_cells_step": (_int, [_vp, _vp, _int, _u32, _u32, _int, _vp, _int, _vp]),
     "vrc_cells_fill_random": (_int, [_vp, _u32, _u64, _vp, _int, _vp]),
     "vrc_volume_xor_mesh": (_int, [_vp, _u64, _vp, _int, _vp]),

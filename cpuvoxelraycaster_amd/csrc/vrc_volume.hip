@@ -12,12 +12,13 @@
 // Here: the volume's life cycle, the edits and queries on the occupancy with their ordering and scratch blocks, and
 // commit / download.  Boxes, spheres, spheres at the hits of a ray batch, region copies and the two queries have their
 // kernels here, over the box-of-words layout of vrc_box_words.h.  The other features keep theirs in files of their own:
-// vrc_flood.hip, vrc_voxelize.hip, vrc_surface.hip, vrc_rects.hip, vrc_stamp.hip.  The snapshots taken from a volume (labels, distance
+// vrc_flood.hip, vrc_voxelize.hip, vrc_surface.hip, vrc_rects.hip, vrc_stamp.hip, vrc_pack.hip.  The snapshots taken from a volume (labels, distance
 // fields) are in vrc_snapshots.hip; what the entry points of both files share -- the checks, the ordering rule and staged_call,
 // the one frame of every call that takes lists -- is in vrc_volume_state.h, and the ordering of every entry point is the
 // table in DESIGN.md.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <new>
 
@@ -26,6 +27,7 @@
 #include "vrc_build_sweeps.h"
 #include "vrc_flood.h"
 #include "vrc_group.h"
+#include "vrc_pack.h"
 #include "vrc_stamp.h"
 #include "vrc_rects.h"
 #include "vrc_surface.h"
@@ -322,6 +324,7 @@ void volume_free(vrc_volume* v)
     if (v->d_marks) (void)hipFree(v->d_marks);
     if (v->d_surface) (void)hipFree(v->d_surface);
     if (v->d_rects) (void)hipFree(v->d_rects);
+    if (v->d_pack) (void)hipFree(v->d_pack);
     v->grids.release();
     delete v;
 }
@@ -817,7 +820,8 @@ extern "C" int vrc_volume_edit_scratch_bytes(const vrc_volume* v, uint64_t* byte
 {
     if (!v || !bytes) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_edit_scratch_bytes: null argument");
     *bytes = (uint64_t)v->stage_cap + (uint64_t)v->flood_cap + (v->d_marks ? (uint64_t)vrc::voxelize_scratch_bytes(v->depth) : 0u) +
-             (v->d_surface ? (uint64_t)vrc::surface_scratch_bytes(v->depth) : 0u) + (v->d_rects ? (uint64_t)vrc::rect_scratch_bytes(v->depth) : 0u);
+             (v->d_surface ? (uint64_t)vrc::surface_scratch_bytes(v->depth) : 0u) + (v->d_rects ? (uint64_t)vrc::rect_scratch_bytes(v->depth) : 0u) +
+             (v->d_pack ? (uint64_t)vrc::pack_scratch_bytes(v->depth) : 0u);
     return VRC_OK;
 }
 
@@ -838,5 +842,155 @@ extern "C" int vrc_volume_solid_count(vrc_volume* v, uint64_t* count)
     if (e == hipSuccess) e = hipMemcpy(&total, v->d_count, 8, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return vrc::fail_hip(e, "vrc_volume_solid_count");
     *count = total;
+    return VRC_OK;
+}
+
+// ---- the sparse tile stream (vrc.h: vrc_pack_*; kernels and format arithmetic: vrc_pack.hip, vrc_pack.h) ------------
+
+namespace {
+
+// The header rules, in the order of include/vrc.h, over the 16 header words h (nullptr when bytes < 64): nullptr, or the
+// name of the first rule that does not hold.  expect_depth == 0: any depth in 2..10 passes the depth rule.
+const char* pack_header_rule(const uint32_t* h, uint64_t bytes, uint32_t expect_depth)
+{
+    if (bytes < vrc::PACK_HEADER_BYTES || !h) return "header-short";
+    if (h[0] != vrc::PACK_MAGIC || h[1] != vrc::PACK_VERSION) return "magic-version";
+    const uint32_t depth = h[2];
+    if (depth < 2u || depth > 10u || (expect_depth && depth != expect_depth)) return "depth";
+    const uint32_t nt = vrc::pack_tiles(depth), M = h[4], P = h[5], full = h[10];
+    if (h[3] != nt) return "tiles";
+    for (int k = 11; k < 16; ++k)
+        if (h[k]) return "reserved";
+    const uint64_t length = (uint64_t)h[6] | ((uint64_t)h[7] << 32);
+    if (length != bytes) return "length-argument";
+    if (length != vrc::pack_layout(depth, M, P).length) return "length-formula";
+    if (M > nt || (uint64_t)P > (uint64_t)vrc::pack_tile_bricks(depth) * M || (uint64_t)full + M > nt) return "count-limits";
+    return nullptr;
+}
+
+void pack_info_of(const uint32_t* h, vrc_pack_info* info)
+{
+    info->depth = h[2]; info->tiles = h[3]; info->mixed_tiles = h[4]; info->full_tiles = h[10]; info->partial_bricks = h[5]; info->reserved = 0;
+    info->bytes = (uint64_t)h[6] | ((uint64_t)h[7] << 32);
+    info->solid = (uint64_t)h[8] | ((uint64_t)h[9] << 32);
+}
+
+hipError_t pack_scratch(vrc_volume* v)
+{
+    return v->d_pack ? hipSuccess : hipMalloc(&v->d_pack, vrc::pack_scratch_bytes(v->depth));
+}
+
+}  // namespace
+
+extern "C" uint64_t vrc_pack_bound(uint32_t depth) { return depth < 2u || depth > 10u ? 0u : vrc::pack_bound_bytes(depth); }
+
+extern "C" int vrc_pack_header(const void* data, uint64_t bytes, vrc_pack_info* out)
+{
+    const char* what = "vrc_pack_header";
+    if (!data || !out) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    uint32_t h[16];
+    if (bytes >= vrc::PACK_HEADER_BYTES) memcpy(h, data, sizeof h);
+    if (const char* rule = pack_header_rule(bytes >= vrc::PACK_HEADER_BYTES ? h : nullptr, bytes, 0u)) return vrc::fail(VRC_ERR_INVALID, "%s: rule %s", what, rule);
+    pack_info_of(h, out);
+    return VRC_OK;
+}
+
+extern "C" int vrc_pack_volume(vrc_volume* v, void* out, uint64_t capacity, vrc_pack_info* info, int mem)
+{
+    const char* what = "vrc_pack_volume";
+    if (!v || !info) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
+    if (out && mem == VRC_MEM_DEVICE && ((uintptr_t)out & 3u)) return vrc::fail(VRC_ERR_INVALID, "%s: device buffer %p is not aligned to 4 bytes", what, out);
+    hipError_t e = hipSetDevice(v->device);
+    if (e == hipSuccess) e = order_behind_edits(v, nullptr);
+    if (e == hipSuccess) e = pack_scratch(v);
+    vrc::PackTotals totals;
+    if (e == hipSuccess) {
+        vrc::pack_offsets_run(v->d_bricks, v->depth, v->d_pack, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(&totals, v->d_pack, sizeof totals, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    const uint64_t bytes = vrc::pack_layout(v->depth, totals.mixed, totals.partial).length;
+    info->depth = v->depth; info->tiles = vrc::pack_tiles(v->depth); info->mixed_tiles = totals.mixed; info->full_tiles = totals.full;
+    info->partial_bricks = totals.partial; info->reserved = 0; info->bytes = bytes; info->solid = totals.solid;
+    if (!out) return VRC_OK;
+    if (capacity < bytes)
+        return vrc::fail(VRC_ERR_INVALID, "%s: capacity %llu below the stream's %llu bytes", what, (unsigned long long)capacity, (unsigned long long)bytes);
+    uint8_t* own = nullptr;
+    if (mem == VRC_MEM_HOST) e = hipMalloc((void**)&own, bytes);
+    if (e == hipSuccess) {
+        vrc::pack_emit_run(v->d_bricks, v->depth, v->d_pack, totals, own ? own : (uint8_t*)out, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = own ? hipMemcpy(out, own, bytes, hipMemcpyDeviceToHost) : hipStreamSynchronize(nullptr);
+    if (own) (void)hipFree(own);
+    return done(e, what);
+}
+
+extern "C" int vrc_unpack_volume(vrc_volume* v, const void* data, uint64_t bytes, int mem)
+{
+    const char* what = "vrc_unpack_volume";
+    if (!v || !data) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (mem == VRC_MEM_DEVICE && ((uintptr_t)data & 3u)) return vrc::fail(VRC_ERR_INVALID, "%s: device buffer %p is not aligned to 4 bytes", what, data);
+    if (bytes < vrc::PACK_HEADER_BYTES) return vrc::fail(VRC_ERR_INVALID, "%s: rule %s", what, pack_header_rule(nullptr, bytes, v->depth));
+    uint32_t h[16];
+    hipError_t e = hipSuccess;
+    if (mem == VRC_MEM_HOST) memcpy(h, data, sizeof h);
+    else {
+        e = hipSetDevice(v->device);
+        if (e == hipSuccess) e = hipMemcpy(h, data, sizeof h, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return vrc::fail_hip(e, what);
+    }
+    if (const char* rule = pack_header_rule(h, bytes, v->depth)) return vrc::fail(VRC_ERR_INVALID, "%s: rule %s", what, rule);
+    const uint32_t M = h[4], P = h[5];
+    e = hipSetDevice(v->device);
+    if (e == hipSuccess) e = order_behind_edits(v, nullptr);
+    if (e == hipSuccess) e = pack_scratch(v);
+    uint8_t* own = nullptr;
+    if (e == hipSuccess && mem == VRC_MEM_HOST) {
+        e = hipMalloc((void**)&own, bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(own, data, bytes, hipMemcpyHostToDevice, nullptr);
+    }
+    const uint8_t* d = own ? own : (const uint8_t*)data;
+    vrc::PackTotals t;
+    if (e == hipSuccess) {
+        vrc::unpack_check_run(d, v->depth, M, P, v->d_pack, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(&t, v->d_pack, sizeof t, hipMemcpyDeviceToHost);
+    // the device-side rules in the order of include/vrc.h: the first that broke, with the least tile or byte where it has one
+    const char* rule = nullptr;
+    const char* unit = nullptr;
+    uint32_t at = 0u;
+    if (e == hipSuccess) {
+        const uint64_t solid = t.solid + 8ull * vrc::pack_tile_bricks(v->depth) * t.full, claimed = (uint64_t)h[8] | ((uint64_t)h[9] << 32);
+        const struct { const char* name; bool broken; const char* unit; uint32_t at; } rules[] = {
+            {"class-map", t.first_class != ~0u, "tile", t.first_class},
+            {"mixed-count", t.mixed != M, nullptr, 0u},
+            {"full-count", t.full != h[10], nullptr, 0u},
+            {"full-in-some", t.first_subset != ~0u, "tile", t.first_subset},
+            {"mask-range", t.first_range != ~0u, "tile", t.first_range},
+            {"some-empty", t.first_empty != ~0u, "tile", t.first_empty},
+            {"full-whole", t.first_whole != ~0u, "tile", t.first_whole},
+            {"partial-count", t.first_count != ~0u, "tile", t.first_count},
+            {"partial-sum", t.partial != P, nullptr, 0u},
+            {"partial-byte", t.first_byte != ~0u, "byte", t.first_byte},
+            {"padding", t.first_padding != ~0u, "byte", t.first_padding},
+            {"solid-count", solid != claimed, nullptr, 0u}};
+        for (const auto& r : rules)
+            if (r.broken) { rule = r.name; unit = r.unit; at = r.at; break; }
+    }
+    if (e == hipSuccess && !rule) {
+        vrc::unpack_write_run(d, v->depth, M, P, v->d_pack, v->d_bricks, nullptr);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    }
+    if (own) (void)hipFree(own);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    if (rule && unit) return vrc::fail(VRC_ERR_INVALID, "%s: rule %s at %s %u", what, rule, unit, at);
+    if (rule) return vrc::fail(VRC_ERR_INVALID, "%s: rule %s", what, rule);
     return VRC_OK;
 }

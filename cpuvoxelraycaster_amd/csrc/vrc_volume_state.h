@@ -35,6 +35,9 @@ struct vrc_volume {
     // vrc_rect_count / _extract_rects: the per-workgroup rectangle offsets, the totals and the two row bit fields
     // (vrc_rects.h), allocated by the first call, fixed in size
     unsigned long long* d_rects = nullptr;
+    // vrc_pack_volume / vrc_unpack_volume: the totals and the two slot arrays (vrc_pack.h), allocated by the first call, fixed
+    // in size
+    void* d_pack = nullptr;
     // the last asynchronous edit: commit / download / solid_count run on the NULL stream and wait for it first.  The flag
     // says that the event has been recorded at least once; it is never cleared, because a wait only orders ONE stream
     // behind the edit and the next caller may bring another.

@@ -21,6 +21,7 @@
 #include <cmath>
 #include <cstdint>
 #include <fstream>
+#include <iterator>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -935,6 +936,50 @@ public:
         uint64_t n = 0;
         check(vrc_volume_solid_count(v_, &n), "vrc_volume_solid_count");
         return n;
+    }
+    // The volume as its sparse tile stream (include/vrc.h: vrc_pack_volume; format version 1) and back.  packInfo: what pack
+    // would write, the count and scan passes alone.  unpack replaces the whole occupancy; a stream that breaks a canonical
+    // rule throws with the rule's name and leaves the volume as it was.  All synchronous.
+    vrc_pack_info packInfo()
+    {
+        flush();
+        vrc_pack_info info;
+        check(vrc_pack_volume(v_, nullptr, 0, &info, VRC_MEM_HOST), "vrc_pack_volume");
+        return info;
+    }
+    std::vector<uint8_t> pack()
+    {
+        vrc_pack_info info = packInfo();
+        std::vector<uint8_t> out((size_t)info.bytes);
+        check(vrc_pack_volume(v_, out.data(), out.size(), &info, VRC_MEM_HOST), "vrc_pack_volume");
+        return out;
+    }
+    void unpack(const uint8_t* data, uint64_t bytes)
+    {
+        flush();
+        check(vrc_unpack_volume(v_, data, bytes, VRC_MEM_HOST), "vrc_unpack_volume");
+    }
+    void unpack(const std::vector<uint8_t>& stream) { unpack(stream.data(), stream.size()); }
+    void save(const std::string& path)
+    {
+        const std::vector<uint8_t> stream = pack();
+        std::ofstream f(path, std::ios::binary);
+        f.write((const char*)stream.data(), (std::streamsize)stream.size());
+        if (!f.flush()) throw std::runtime_error("save: write to " + path + " failed");
+    }
+    // a new volume from a file written by save(); the depth is the header's (vrc_pack_header)
+    static std::unique_ptr<HipVoxelVolume> load(const std::string& path, int device = 0)
+    {
+        std::ifstream f(path, std::ios::binary);
+        if (!f) throw std::runtime_error("load: cannot open " + path);
+        const std::vector<uint8_t> stream((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        vrc_pack_info info;
+        uint8_t head[64] = {0};
+        std::copy(stream.begin(), stream.begin() + std::min<size_t>(64, stream.size()), head);
+        check(vrc_pack_header(head, stream.size(), &info), "vrc_pack_header");
+        std::unique_ptr<HipVoxelVolume> volume(new HipVoxelVolume(info.depth, device));
+        volume->unpack(stream);
+        return volume;
     }
     uint64_t editScratchBytes() const
     {

@@ -270,6 +270,22 @@ def count_mask(counts):
     return mask
 
 
+def packed_info(data):
+    """The header of a sparse tile stream (bytes, a uint8 numpy array or a uint8 torch tensor) as a capi.PackInfo, held to
+    the header rules of include/vrc.h (vrc_pack_header): pure host, only the first 64 bytes are read."""
+    if hasattr(data, "data_ptr"):
+        total, head = int(data.numel()), data.reshape(-1)[:64].cpu().numpy()
+    elif isinstance(data, (bytes, bytearray, memoryview)):
+        total, head = len(data), np.frombuffer(data, np.uint8, min(64, len(data)))
+    else:
+        flat = np.asarray(data, np.uint8).reshape(-1)
+        total, head = flat.size, flat[:64]
+    head = np.concatenate([np.ascontiguousarray(head, np.uint8), np.zeros(64 - len(head), np.uint8)])    # a short stream is refused by its length
+    info = capi.PackInfo()
+    check(capi.load().vrc_pack_header(ptr(head), total, C.byref(info)))
+    return info
+
+
 class VoxelVolume:
     """Device-resident editable occupancy of an S^3 volume (include/vrc.h: vrc_volume_*).  Edits are batched; commit()
     builds a new immutable LSVO on the device, bit-identical to compileSVO of the current voxel set."""
@@ -894,8 +910,68 @@ class VoxelVolume:
         check(capi.load().vrc_volume_solid_count(self._h, C.byref(n)))
         return int(n.value)
 
+    def packInfo(self):
+        """What pack() would write, as a capi.PackInfo (bytes, mixed_tiles, full_tiles, partial_bricks, solid, ...): the
+        count and scan passes alone (include/vrc.h: vrc_pack_volume with no buffer).  Synchronous."""
+        info = capi.PackInfo()
+        check(capi.load().vrc_pack_volume(self._h, None, 0, C.byref(info), capi.VRC_MEM_HOST))
+        return info
+
+    def pack(self, device=False):
+        """The volume as its sparse tile stream (include/vrc.h: the format, version 1): a uint8 numpy array, or with
+        device=True a uint8 torch tensor on the volume's device that the stream never leaves.  Equal occupancies give equal
+        bytes.  Synchronous."""
+        info = self.packInfo()
+        n = int(info.bytes)
+        if device:
+            import torch
+            out = torch.empty(n, dtype=torch.uint8, device="cuda:%d" % self.device)
+            check(capi.load().vrc_pack_volume(self._h, ptr(out.data_ptr()), n, C.byref(info), capi.VRC_MEM_DEVICE))
+            return out
+        out = np.empty(n, np.uint8)
+        check(capi.load().vrc_pack_volume(self._h, ptr(out), n, C.byref(info), capi.VRC_MEM_HOST))
+        return out
+
+    def unpack(self, data):
+        """Replaces the whole occupancy by the one of a stream made by pack(): bytes, a uint8 numpy array, or a uint8 torch
+        tensor on the volume's device (read in place).  A stream that breaks a canonical rule raises VrcError naming the rule
+        and leaves the volume as it was.  Synchronous."""
+        if hasattr(data, "data_ptr"):
+            if not data.is_cuda:
+                data = data.numpy()
+            else:
+                data = data.contiguous()
+                check(capi.load().vrc_unpack_volume(self._h, ptr(data.data_ptr()), int(data.numel()), capi.VRC_MEM_DEVICE))
+                return
+        data = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data, np.uint8).reshape(-1)
+        check(capi.load().vrc_unpack_volume(self._h, ptr(data), data.size, capi.VRC_MEM_HOST))
+
+    def save(self, path):
+        """writes pack() to a file; returns its capi.PackInfo"""
+        stream = self.pack()
+        with open(path, "wb") as f:
+            f.write(stream.tobytes())
+        return packed_info(stream)
+
+    @classmethod
+    def fromPacked(cls, data, device=0):
+        """A new volume from a stream (bytes, numpy array or device tensor as for unpack); the depth is the header's."""
+        volume = cls(int(packed_info(data).depth), device)
+        try:
+            volume.unpack(data)
+        except Exception:
+            volume.close()
+            raise
+        return volume
+
+    @classmethod
+    def load(cls, path, device=0):
+        """A new volume from a file written by save()."""
+        with open(path, "rb") as f:
+            return cls.fromPacked(f.read(), device)
+
     def editScratchBytes(self):
-        """device bytes in the scratch blocks of the edit calls (staging, flood, mark field, surface offsets, rectangle block); include/vrc.h"""
+        """device bytes in the scratch blocks of the edit calls (staging, flood, mark field, surface offsets, rectangle block, pack slots); include/vrc.h"""
         n = C.c_uint64()
         check(capi.load().vrc_volume_edit_scratch_bytes(self._h, C.byref(n)))
         return int(n.value)

@@ -405,8 +405,8 @@ int vrc_volume_clone(vrc_volume *src, vrc_volume **out);
 int vrc_volume_get_voxels(vrc_volume *v, uint64_t n, const uint32_t *xyz, uint8_t *solid_out, int mem, void *stream);
 int vrc_volume_count_boxes(vrc_volume *v, uint64_t n, const uint32_t *lo_hi, uint64_t *counts, int mem, void *stream);
 /* Device bytes the volume holds at this moment in the scratch blocks of its edit calls: the grow-only staging block of the
- * host-memory calls, vrc_volume_flood's block, vrc_volume_xor_mesh's mark field, the surface calls' offsets block and the rectangle calls' block (0
- * before the first call of each).  The occupancy itself and vrc_volume_commit's grids are not counted.  Pure host
+ * host-memory calls, vrc_volume_flood's block, vrc_volume_xor_mesh's mark field, the surface calls' offsets block, the rectangle calls' block and
+ * the slots of vrc_pack_volume / vrc_unpack_volume (0 before the first call of each).  The occupancy itself and vrc_volume_commit's grids are not counted.  Pure host
  * bookkeeping, no device call. */
 int vrc_volume_edit_scratch_bytes(const vrc_volume *v, uint64_t *bytes);
 
@@ -1079,6 +1079,90 @@ uint64_t vrc_delta_bytes(const vrc_delta *d);      /* 8 * count; pure host bookk
 int vrc_delta_get_stats(const vrc_delta *d, vrc_delta_stats *out);   /* host copy kept in the object, no device call */
 int vrc_delta_records(const vrc_delta *d, uint64_t first, uint64_t capacity, uint32_t *out, int mem, void *stream);
 int vrc_delta_apply(const vrc_delta *d, vrc_volume *dst, void *stream);
+
+/* Sparse tile stream: a volume as a byte stream that is small where the world is solid rock or air, packed and unpacked on
+ * the device -- the saved game, the level file, the first sync of a replica, the base that deltas apply to.  (vrc_volume_download
+ * is one byte per voxel, 128 MiB at 512^3; there was no direct way back in.)
+ *
+ * Format, version 1.  Little-endian; every section starts on a multiple of 4 bytes.  With S = 1 << depth (depth 2..10):
+ *   n = S/2 bricks per axis, E = min(8, n) the tile edge in bricks, T = n/E tiles per axis, NT = T^3 tiles, K = E^3 bricks per
+ *   tile (8, 64 or 512), MW = max(1, K/32) words per mask (1, 2 or 16).
+ * Brick: the 2 x 2 x 2 voxels with brick coordinates (x>>1, y>>1, z>>1); its byte has bit (z&1) 4 + (y&1) 2 + (x&1), the
+ * occupancy's own bits (key & 7 above).  Tile (tx, ty, tz) holds the bricks (E tx + i, E ty + j, E tz + k); its index is
+ * t = (tx T + ty) T + tz and a brick's local index q = (i E + j) E + k.  Tile class: 0 = every brick byte 0, 1 = every brick
+ * byte 0xff, 2 = mixed; 3 is illegal.  Mixed tiles are numbered by rank r in ascending t.  A partial brick is a brick of a
+ * mixed tile whose byte is neither 0 nor 0xff.
+ *   Header, 64 bytes = 16 uint32: 0 magic 0x50435256 (the bytes V R C P), 1 version 1, 2 depth, 3 NT, 4 M = mixed tiles,
+ *     5 P = partial bricks, 6..7 the stream's length in bytes (uint64, low word first), 8..9 solid voxels (uint64),
+ *     10 class-1 (full) tiles, 11..15 zero.
+ *   A, class map: ceil(NT/16) uint32; the class of tile t in bits 2(t%16), 2(t%16)+1 of word t/16, unused bits 0.
+ *   B, counts: M uint32; entry r = the partial bricks of mixed tile r.
+ *   C, masks: M x 2 MW uint32; per mixed tile first `some` (bit q%32 of word q/32 set iff the brick byte is not 0), then
+ *     `full` (set iff it is 0xff); bits at q >= K are 0 (depth 2 alone has them).
+ *   D, partial bytes: P bytes, tiles in ascending rank and within a tile in ascending q; then 0..3 zero bytes.
+ * Length = 64 + 4 ceil(NT/16) + 4 M + 8 MW M + 4 ceil(P/4); vrc_pack_bound(depth) is this with M = NT and P = n^3 (0 for a
+ * depth outside 2..10): 712 bytes at 16^3 and about 1.26 x the occupancy from 32^3 up (20.1 MiB at 512^3).  A volume has
+ * exactly one stream: equal occupancies give equal bytes, and pack(unpack(s)) == s for every s that unpack accepts.
+ *
+ * Canonical rules.  A stream is accepted only if all hold; vrc_last_error names the first that does not, in this order, as
+ * "rule <name>", for the rules marked (tile) / (byte) followed by " at tile <t>" / " at byte <offset into the stream>" with the
+ * LEAST offender.  From the 64 header bytes, on the host, before any kernel reads a section:
+ *   header-short     at least 64 bytes;
+ *   magic-version    magic and version match;
+ *   depth            the depth is 2..10 and, for vrc_unpack_volume, the volume's;
+ *   tiles            the NT word is right;
+ *   reserved         words 11..15 are 0;
+ *   length-argument  the length word equals the `bytes` argument;
+ *   length-formula   the length word equals the formula with the header's M and P;
+ *   count-limits     M <= NT, P <= K M, full + M <= NT.
+ * On the device:
+ *   class-map (tile)      no class 3, no unused bit set (reported as the tile index the field would have);
+ *   mixed-count           the class-2 tiles are M;
+ *   full-count            the class-1 tiles are header word 10;
+ *   full-in-some (tile)   full is a subset of some;
+ *   mask-range (tile)     no mask bit at q >= K;
+ *   some-empty (tile)     some != 0;
+ *   full-whole (tile)     full does not have all K bits;
+ *   partial-count (tile)  popcount(some & ~full) equals the tile's B entry;
+ *   partial-sum           the sum of B equals P;
+ *   partial-byte (byte)   no D byte is 0x00 or 0xff;
+ *   padding (byte)        the padding is zero;
+ *   solid-count           the solid voxels counted from the stream equal header words 8, 9.
+ * The mask rules are evaluated for the mixed tiles of rank < M.  A refused stream is VRC_ERR_INVALID and the volume keeps its
+ * occupancy bit for bit: no kernel reads outside [data, data + bytes) or writes the occupancy before every check has passed,
+ * and an offset into D stays below P whatever B claims.
+ *
+ * vrc_pack_header is pure host: the header rules (any depth in 2..10) over the first 64 bytes, and the header's fields.
+ * vrc_pack_volume and vrc_unpack_volume are synchronous like vrc_volume_commit and vrc_volume_clone: on the NULL stream, behind
+ * the volume's last asynchronous edit.  `mem` says where out / data live; info is always host memory.  Host memory is staged
+ * through a device block of the stream's length that belongs to the call and is freed before it returns.
+ * vrc_pack_volume: out == NULL with capacity == 0 runs the count and scan passes only and fills info.  capacity < info->bytes
+ * is VRC_ERR_INVALID with info filled and nothing written; otherwise exactly info->bytes bytes are written and nothing beyond
+ * them is touched.  A device `out` must be 4-byte aligned; a misaligned one is refused and not written.
+ * vrc_unpack_volume replaces the whole occupancy.  With device `data` the 64 header bytes are copied to the host first; device
+ * `data` must be 4-byte aligned and complete when the call is made.
+ * NULLs, a bad `mem`, out == NULL with capacity > 0 and a misaligned device buffer are VRC_ERR_INVALID before any device call.
+ * Scratch: the per-tile slots and the totals, 8 (NT + 1) + 64 bytes (2 MiB at 1024^3, 256 KiB at 512^3), one block of the
+ * volume, allocated by the first of the two calls, never grown, counted by vrc_volume_edit_scratch_bytes from then on.
+ * The device (csrc/vrc_pack.hip): pack is count -> scan -> emit with one 64-lane wave per tile, a lane per row of 8 brick bytes,
+ * no workgroup waiting for another; unpack is class count and rank scan, mask checks and offset scan, the D check, and only then
+ * the write, a wave per tile.  The two calls are named vrc_pack_volume / vrc_unpack_volume, not vrc_volume_*.
+ * Times: profiles/edit/bench_pack.json (tools/bench_edit.py --pack; 512^3 on the MI355X, whole calls, device time by events,
+ * median of 5, in one run next to vrc_volume_clone, 0.05 to 0.06 ms, and vrc_volume_download, 2.7 to 2.9 ms for 128 MiB).
+ * FastNoise terrain: 517316 bytes (M = 2849 of 32768 tiles, P = 132990; 3.1 % of the 16 MiB occupancy), size-only call 0.150 ms,
+ * pack to device memory 0.166 ms, unpack from device memory 0.175 ms.  A 0.5-density random field, the format's worst case:
+ * 20979956 bytes (M = 32768, P = 16646321; 1.25 x the occupancy: LARGER than what it stands for), size-only 0.484 ms, pack
+ * 0.542 ms, unpack 0.246 ms.  A pack or unpack costs 3 to 10 clones in time.  The size-only call is nearly the whole pack, and
+ * the count pass is three times slower on the random field over the same 16 MiB: every one of its 32768 waves adds to the one
+ * solid counter there.  The passes have not been timed apart. */
+typedef struct vrc_pack_info {           /* 40 bytes */
+    uint32_t depth, tiles, mixed_tiles, full_tiles, partial_bricks, reserved;
+    uint64_t bytes, solid;
+} vrc_pack_info;
+uint64_t vrc_pack_bound(uint32_t depth);                                   /* pure host; 0 for a bad depth */
+int vrc_pack_header(const void *data, uint64_t bytes, vrc_pack_info *out); /* pure host */
+int vrc_pack_volume(vrc_volume *v, void *out, uint64_t capacity, vrc_pack_info *info, int mem);
+int vrc_unpack_volume(vrc_volume *v, const void *data, uint64_t bytes, int mem);
 
 /* Cells: the local question -- how many of a voxel's neighbours are solid -- as one step of a neighbour-count automaton,
  * and a voxel set from a seed.  Clean-up (specks a brush or a fracture leaves, pin-holes), rounding by a majority vote,

@@ -186,7 +186,15 @@ median and range, on two inputs -- the FastNoise terrain and a fillRandom of den
   step_6_changed / step_26_changed   the same with `changed` in device memory              next to  clone (vrc_volume_clone, closed outside the events)
   fill_random                        vrc_cells_fill_random of the whole volume, REPLACE    next to  copy_region
 and step_over_copy, the ratio of the medians.  The smoothing rule (majority of 27) and, with six neighbours, survive = 1 .. 6.
-No threshold is applied; the numbers are reported."""
+With --pack (printed and written to profiles/edit/bench_pack.json), the sparse tile stream at 512^3, device time by events on
+the NULL stream, one warm-up round, median of `--pairs` rounds, every call of a round in the same process, on two inputs -- the
+FastNoise terrain and a fillRandom of density 0.5, the format's worst case.  Per input the stream's bytes, M and P, and
+  size_ms      vrc_pack_volume without a buffer: the count and scan passes and the read-back of the totals
+  pack_ms      vrc_pack_volume into device memory: the same, then the emit
+  unpack_ms    vrc_unpack_volume from device memory: the header copy, the checks, the read-back of the totals, the write
+  clone_ms     vrc_volume_clone (closed outside the events)
+  download_ms  vrc_volume_download, one byte per voxel to the host
+No ratio is promised and no threshold is applied; the numbers are reported."""
 import argparse
 import json
 import os
@@ -1452,6 +1460,65 @@ def bench_delta(vrc, depth, pairs):
     return res
 
 
+def bench_pack(vrc, depth, pairs):
+    """vrc_pack_volume / vrc_unpack_volume next to vrc_volume_clone and vrc_volume_download; see the module's text."""
+    import ctypes as C
+    import torch
+    capi = vrc.capi
+    L = capi.load()
+    S = 1 << depth
+    res = {"size": S, "rounds": pairs, "occupancy_bytes": S ** 3 // 8, "dense_bytes": S ** 3, "bound_bytes": int(L.vrc_pack_bound(depth))}
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    terrain = vrc.VoxelVolume.fromScene(scene)
+    noise = vrc.VoxelVolume(depth)
+    noise.fillRandom(1, 0.5)
+    dense = np.zeros((S, S, S), np.uint8)
+    for name, volume in (("terrain", terrain), ("random_half", noise)):
+        info = volume.packInfo()
+        n = int(info.bytes)
+        one = {"stream_bytes": n, "mixed_tiles": int(info.mixed_tiles), "full_tiles": int(info.full_tiles), "tiles": int(info.tiles),
+               "partial_bricks": int(info.partial_bricks), "solid": int(info.solid), "stream_over_occupancy": round(n / (S ** 3 // 8), 4),
+               "stream_over_dense": round(n / S ** 3, 5)}
+        buf = torch.empty(n, dtype=torch.uint8, device="cuda")
+        target = vrc.VoxelVolume(depth)
+        scratch = capi.PackInfo()
+
+        def size_only():
+            capi.check(L.vrc_pack_volume(volume._h, None, 0, C.byref(scratch), capi.VRC_MEM_DEVICE))
+
+        def pack():
+            capi.check(L.vrc_pack_volume(volume._h, capi.ptr(buf.data_ptr()), n, C.byref(scratch), capi.VRC_MEM_DEVICE))
+
+        def unpack():
+            capi.check(L.vrc_unpack_volume(target._h, capi.ptr(buf.data_ptr()), n, capi.VRC_MEM_DEVICE))
+
+        def download():
+            capi.check(L.vrc_volume_download(volume._h, capi.ptr(dense)))
+
+        calls = [("size_ms", size_only), ("pack_ms", pack), ("unpack_ms", unpack), ("clone_ms", volume.clone), ("download_ms", download)]
+        times = {k: [] for k, _ in calls}
+        for i in range(pairs + 1):
+            for key, fn in calls:
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                made = fn()
+                b.record()
+                b.synchronize()
+                if made is not None:
+                    made.close()
+                if i:
+                    times[key].append(a.elapsed_time(b))
+        for key, _ in calls:
+            one[key] = stat(times[key], 4)
+        assert target.pack().tobytes() == volume.pack().tobytes(), "the unpacked volume does not pack to the same stream"
+        target.close()
+        res[name] = one
+    for v in (noise, terrain):
+        v.close()
+    scene.close()
+    return res
+
+
 def bench_cells(vrc, depth, pairs):
     """vrc_cells_step and vrc_cells_fill_random next to vrc_volume_copy_region and vrc_volume_clone; see the module's text."""
     import torch
@@ -1536,7 +1603,25 @@ def main():
     ap.add_argument("--fracture", action="store_true", help="time vrc_fracture_label next to vrc_volume_distance_field + vrc_volume_label_components (depth 9 unless --depths is given)")
     ap.add_argument("--delta", action="store_true", help="time vrc_delta_diff / vrc_delta_apply next to vrc_volume_clone and a copy of one occupancy (depth 9 unless --depths is given)")
     ap.add_argument("--cells", action="store_true", help="time vrc_cells_step / vrc_cells_fill_random next to vrc_volume_copy_region and vrc_volume_clone (depth 9 unless --depths is given)")
+    ap.add_argument("--pack", action="store_true", help="time vrc_pack_volume / vrc_unpack_volume next to vrc_volume_clone and vrc_volume_download (depth 9 unless --depths is given)")
     args = ap.parse_args()
+    if args.pack:
+        if args.depths == [8, 9, 10]:
+            args.depths = [9]
+        import __graft_entry__ as g
+        g.build()
+        import torch
+        import cpuvoxelraycaster_amd as vrc
+        if not torch.cuda.is_available():
+            raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
+        out = {"bench": "edit_pack", "device": torch.cuda.get_device_name(0), "depths": {}}
+        for d in args.depths:
+            out["depths"][str(d)] = bench_pack(vrc, d, max(1, args.pairs))
+        print(json.dumps(out))
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_pack.json")
+        with open(path, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+        return
     if args.cells:
         if args.depths == [8, 9, 10]:
             args.depths = [9]
