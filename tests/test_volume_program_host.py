@@ -1,0 +1,307 @@
+"""Holds the seeded programs of tests/volume_program.py to what they are for, on the CPU alone: the mirror is the models,
+the committed seeds cover the step pairs that share a persistent block, no program idles, and each modelled hazard (a
+Mirror fault switch) changes what at least one step of every depth-5 program observes."""
+import numpy as np
+import pytest
+
+import cells_model
+import components_model
+import delta_model
+import distance_model
+import fall_model
+import flood_model
+import pack_model
+import rect_model
+import stamp_model
+import surface_model
+import volume_program as P
+import voxelize_model
+
+
+def field(S, seed, density=0.4):
+    return (np.random.default_rng(seed).random((S, S, S)) < density).astype(np.uint8)
+
+
+def primed(depth):
+    """a mirror whose two volumes hold random fields and whose snapshots exist"""
+    S = 1 << depth
+    m = P.Mirror(depth)
+    m.s["v"], m.s["w"] = field(S, 1), field(S, 2)
+    m.apply(("snapshotLabels", "host", dict(connectivity=6)))
+    m.apply(("snapshotClone", "host", {}))
+    m.s["v"] = field(S, 3)
+    m.apply(("diff", "host", {}))
+    m.apply(("pack", "host", {}))
+    m.s["v"] = field(S, 4)
+    return m
+
+
+def test_one_step_is_the_family_model():
+    depth, S = 3, 8
+    rng = np.random.default_rng(5)
+    for family in P.EDITS + P.QUERIES:
+        for form in P._FORMS_OF.get(family, ("host",)):
+            for op in (0, 1, 2):
+                m = primed(depth)
+                a = P._arguments(rng, family, form, m)
+                if "op" in a:
+                    a["op"] = op if family != "place" else (P.OR, P.ANDNOT)[op % 2]
+                v, w, ids = m.s["v"], m.s["w"], m.s["ids"]
+                out = m.apply((family, form, a))
+                value = 1 if a.get("solid") else 0
+                want_v, want_w, want = v, w, None
+                if family == "setVoxels":
+                    want_v = v.copy()
+                    for x, y, z in a["items"]:
+                        if max(x, y, z) < S:
+                            want_v[x, y, z] = value
+                elif family == "fillBoxes":
+                    want_v = v.copy()
+                    for b in a["items"]:
+                        want_v[b[0]:b[3], b[1]:b[4], b[2]:b[5]] = value
+                elif family == "fillSpheres":
+                    g = np.indices((S, S, S)).astype(np.int64)
+                    want_v = v.copy()
+                    for cx, cy, cz, r in a["items"].astype(np.int64):
+                        want_v[(g[0] - cx) ** 2 + (g[1] - cy) ** 2 + (g[2] - cz) ** 2 <= r * r] = value
+                elif family == "fillSpheresAtHits":
+                    continue                                   # held by test_hits_name_their_cells below
+                elif family == "xorMesh":
+                    want_v = voxelize_model.xor_mesh(S, a["tris"], v.copy())
+                elif family == "copyRegion":
+                    m_, t_ = stamp_model.IDENTITY
+                    t_ = [(a["src_lo"][k] - a["dst_lo"][k]) << 17 for k in range(3)]
+                    want_v = stamp_model.stamp(v, w, m_, t_, a["dst_lo"], [a["dst_lo"][k] + a["size"][k] for k in range(3)], a["op"])
+                elif family == "stampAffine":
+                    want_v = stamp_model.stamp(v, w, a["m"], a["t"], a["lo"], a["hi"], a["op"])
+                elif family == "fillRandom":
+                    want_v = cells_model.fill_random(v, a["seed"], a["threshold"], a["box"], a["op"])
+                elif family == "applyDelta":
+                    want_v = delta_model.dense_of(delta_model.apply(delta_model.words_of(v), m.s["delta"]), depth)
+                elif family == "unpack":
+                    want_v = field(S, 3)
+                elif family == "cellStepDst":
+                    want_v = cells_model.step(w, a["birth"], a["survive"], a["neighbours"], a["outside"])[0]
+                elif family == "cellStepSrc":
+                    want_w = cells_model.step(v, a["birth"], a["survive"], a["neighbours"], a["outside"])[0]
+                elif family == "floodRegion":
+                    want_v = flood_model.flood_plain(w, v, a["connectivity"], a["through_empty"])
+                    want = int(want_v.sum())
+                elif family == "floodMedium":
+                    want_w = flood_model.flood_plain(v, w, a["connectivity"], a["through_empty"])
+                    want = int(want_w.sum())
+                elif family == "keepConnected":
+                    b = a["anchors"][0]
+                    seeds = np.zeros_like(v)
+                    seeds[b[0]:b[3], b[1]:b[4], b[2]:b[5]] = 1
+                    want_v = flood_model.flood_plain(v, seeds, a["connectivity"])
+                    want = v & (1 - want_v)
+                elif family == "dilate":
+                    want_v = distance_model.dilate(v, a["r"]).astype(np.uint8)
+                elif family == "erode":
+                    want_v = distance_model.erode(v, a["r"], a["open_border"]).astype(np.uint8)
+                elif family == "select":
+                    want_v = cells_model.apply_op(v, components_model.select(ids, a["keep"]), a["op"])
+                elif family == "place":
+                    want_v = fall_model.place(ids, a["offsets"], v, a["op"] == P.OR, a["keep"])
+                elif family == "solidCount":
+                    want = int(v.sum())
+                elif family == "getVoxels":
+                    want = np.array([v[x, y, z] if max(x, y, z) < S else 0 for x, y, z in a["items"]], np.uint8)
+                elif family == "countBoxes":
+                    want = np.array([v[b[0]:b[3], b[1]:b[4], b[2]:b[5]].sum() for b in a["items"]], np.uint64)
+                elif family == "surface":
+                    f = surface_model.faces(v, a["closed"])
+                    other = form != "host" and a["order"] == "extract_first"        # the count of the other `closed` in between
+                    want = (surface_model.direction_counts(surface_model.faces(v, not a["closed"]) if other else f),
+                            f[a["first"]:a["first"] + a["capacity"]]) + (() if form == "host" else (len(f),))
+                elif family == "rects":
+                    r = rect_model.rects(v, a["closed"])
+                    other = form != "host" and a["order"] == "extract_first"
+                    want = (rect_model.direction_counts(rect_model.rects(v, not a["closed"]) if other else r),
+                            r[a["first"]:a["first"] + a["capacity"]]) + (() if form == "host" else (len(r),))
+                elif family == "pack":
+                    want = pack_model.pack(v, depth)
+                elif family == "diff":
+                    records, stats = delta_model.diff(delta_model.words_of(field(S, 1)), delta_model.words_of(v), depth)
+                    want = (records, delta_model.stats_tuple(stats))
+                elif family == "components":
+                    want = components_model.label(v, a["connectivity"])[1]
+                elif family == "distanceAt":
+                    D = distance_model.field(v, a["to_empty"], a["outside"])
+                    want = np.array([D[x, y, z] for x, y, z in a["items"]], np.uint32)
+                elif family == "commit":
+                    want = v
+                assert np.array_equal(m.s["v"], want_v) and np.array_equal(m.s["w"], want_w), (family, form, op)
+                assert P.same_value(out, want), (family, form, op)
+                if "op" not in a:
+                    break
+
+
+def test_hits_name_their_cells():
+    for S in (4, 8, 32, 64):
+        cells = np.indices((S, S, S)).reshape(3, -1).T
+        rec = P.hits_of(cells, S, miss_every=7)
+        hit = np.ones(len(cells), bool)
+        hit[::7] = False
+        assert np.array_equal(P.hit_centres(rec, S, False), cells[hit])
+        build = cells[hit] + [0, 1, 0]
+        assert np.array_equal(P.hit_centres(rec, S, True), build[build[:, 1] < S])
+    m = P.Mirror(3)
+    m.s["v"] = field(8, 9)
+    rec = P.hits_of([[1, 2, 3], [4, 7, 4], [5, 5, 5]], 8, miss_every=3)             # record 0 is a miss
+    m.apply(("fillSpheresAtHits", "devA", dict(hits=rec, radius=1, solid=True, then=None)))
+    assert np.array_equal(m.s["v"], P.spheres(field(8, 9), [[5, 6, 5, 1]], 1))      # (4, 8, 4) lies outside: no neighbour
+
+
+def test_one_step_refusals_lifetime_and_the_call_behind_a_brush():
+    depth, S = 3, 8
+    rng = np.random.default_rng(6)
+    for family in P.REFUSALS:
+        m = primed(depth)
+        before = m.save()
+        scratch = (m.scratch_bytes("v"), m.scratch_bytes("w"))
+        assert m.apply((family, "host", P._arguments(rng, family, "host", m))) == "refused" and not m.changed
+        assert all(m.s[k] is before[k] for k in before if k != "before_edit")          # nothing at all moved
+        assert (m.scratch_bytes("v"), m.scratch_bytes("w")) == scratch
+        if family == "refuseUnpack":
+            a = P._arguments(rng, family, "host", m)
+            assert pack_model.unpack(a["data"], depth)[0] == a["rule"]                 # the model refuses it, by that rule
+    m = primed(depth)
+    v, w = m.s["v"], m.s["w"]
+    m.apply(("floodMedium", "host", dict(connectivity=6, through_empty=False)))        # w gains a flood block
+    assert m.scratch_bytes("w") == P.flood_bytes(depth)
+    m.apply(("cloneSecond", "host", {}))
+    assert m.s["w"] is v and m.scratch_bytes("w") == 0                                 # a clone starts without scratch
+    m.apply(("recreateSecond", "host", dict(seed=3, threshold=cells_model.threshold_of(0.4))))
+    assert np.array_equal(m.s["w"], cells_model.random_set(3, cells_model.threshold_of(0.4), S)) and m.scratch_bytes("w") == 0
+    m.s["v"] = field(S, 11)
+    ids, records = components_model.label(m.s["v"], 26)
+    assert m.apply(("snapshotLabels", "host", dict(connectivity=26))) == len(records) and np.array_equal(m.s["ids"], ids)
+    m.apply(("snapshotClone", "host", {}))
+    held = m.s["v"]
+    m.apply(("fillBoxes", "host", dict(items=np.array([[0, 0, 0, S, S, S]], np.uint32), solid=False)))
+    assert m.s["clone"] is held and np.array_equal(m.s["ids"], ids)                    # snapshots do not follow later edits
+    # the call a brush carries behind it
+    start = field(S, 12)
+    cells = np.argwhere(start)[:5]
+    for kind in ("setVoxels", "getVoxels"):
+        m = P.Mirror(depth)
+        m.s["v"] = start
+        items = cells[1:].astype(np.uint32)
+        out = m.apply(("fillSpheresAtHits", "devB", dict(hits=P.hits_of(cells, S, miss_every=10), radius=0, solid=False, then=(kind, items))))
+        dug = P.voxels(start, cells[1:], 0)                                            # record 0 is a miss
+        if kind == "setVoxels":
+            assert out is None and np.array_equal(m.s["v"], start)                     # dug, then set again
+        else:
+            assert np.array_equal(out, np.zeros(4, np.uint8)) and np.array_equal(m.s["v"], dug)
+        assert m.scratch_bytes() == max(16 * 5, (12 if kind == "setVoxels" else 13) * 4)
+
+
+def test_programs_are_deterministic_and_replay_rebuilds_the_prefix():
+    seed, depth = P.COMMITTED[0]
+    P._program.cache_clear()
+    first = P.program(seed, depth)
+    P._program.cache_clear()
+    again = P.program(seed, depth)
+    assert len(first) == P.STEPS[depth] and all(a[:2] == b[:2] and P.same_value(tuple(a[2].values()), tuple(b[2].values())) for a, b in zip(first, again))
+    # what the generator's own mirror saw, which the other tests read, is what a fresh mirror sees
+    assert P.same_value(tuple(o[:5] for o in P.run_committed(seed, depth)), tuple(o[:5] for o in P.run(first, depth)))
+    m, prefix = P.replay(seed, depth, 40)
+    assert len(prefix) == 40 and np.array_equal(m.s["v"], P.run(first[:40], depth)[-1][1])
+
+
+def adjacent(steps):
+    return list(zip(steps, steps[1:]))
+
+
+def test_coverage_of_the_committed_seeds():
+    covered, used = set(), set()
+    for seed, depth in P.COMMITTED:
+        steps = P.program(seed, depth)
+        seen = P.run_committed(seed, depth)
+        used |= {s[0] for s in steps} | {(s[0], s[1]) for s in steps}
+        for a, b in adjacent(steps):
+            covered |= P.covers(a, b)
+        names = [s[0] for s in steps]
+        counts = [int(o[1].sum()) for o in seen]
+        # d_stage: larger list then smaller list; device-memory brush at hits on a stream, then a host-memory list call
+        assert any(a[0] == b[0] == "setVoxels" and a[1] == b[1] == "host" and len(a[2]["items"]) > len(b[2]["items"]) for a, b in adjacent(steps)), (seed, depth)
+        assert any(a[0] == "fillSpheresAtHits" and a[1] in ("devA", "devB") and P.stages(b) and b[1] == "host" for a, b in adjacent(steps)), (seed, depth)
+        # a commit follows an edit that lowered the solid count
+        assert any(names[i] == "commit" and names[i - 1] in P.EDITS and counts[i - 1] < counts[i - 2] for i in range(2, len(steps))), (seed, depth)
+        # a rectCount and a surfaceCount each follow an edit, with an earlier call of their family and none between
+        for family in ("rects", "surface"):
+            at = [i for i, n in enumerate(names) if n == family]
+            assert any(any(n in P.EDITS and seen[k][5] for k, n in enumerate(names[i + 1:j], i + 1)) for i, j in zip(at, at[1:])), (seed, depth, family)
+        # an xorMesh follows a refused xorMesh and one whose triangles were all clipped
+        meshes = [s for s in steps if s[0] in ("xorMesh", "refuseMesh")]
+        assert any(a[0] == "refuseMesh" and b[0] == "xorMesh" for a, b in adjacent(meshes)), (seed, depth)
+        assert any(a[0] == "xorMesh" and a[2]["kind"] == "clipped" and b[0] == "xorMesh" and b[2]["kind"] != "clipped" for a, b in adjacent(meshes)), (seed, depth)
+        # a flood with v as region follows an edit of the other volume used as medium
+        assert any(a[0] in ("floodMedium", "cellStepSrc", "recreateSecond", "cloneSecond") and seen[i][5] and b[0] == "floodRegion"
+                   for i, (a, b) in enumerate(adjacent(steps))), (seed, depth)
+        # inside one step: a brush on a stream of the test's own with a host list edit behind it, and one with a host query
+        # of voxels the brush changes; an extraction on a stream with the count behind it, for both meshes
+        brushes = [s for s in steps if s[0] == "fillSpheresAtHits" and s[1] in ("devA", "devB") and s[2]["then"] is not None]
+        assert any(s[2]["then"][0] == "setVoxels" for s in brushes), (seed, depth)
+        good = False
+        for i, s in enumerate(steps):
+            if any(s is b for b in brushes) and s[2]["then"][0] == "getVoxels":
+                before = P.get_voxels(seen[i - 1][1], s[2]["then"][1])
+                good = good or not np.array_equal(before, seen[i][0])
+        assert good, (seed, depth)
+        for family in ("surface", "rects"):
+            assert any(s[0] == family and s[1] in ("devA", "devB") and s[2].get("order") == "extract_first" for s in steps), (seed, depth, family)
+    assert set(P.shared_pairs()) <= covered, sorted(set(P.shared_pairs()) - covered)
+    for form in P.FORMS[1:]:                                    # the stream-only edits: each stream occurs among them
+        assert any((family, form) in used for family in P.STREAM_EDITS), form
+    # every family, every op of the families that take one and every form of the list calls: at EVERY depth
+    for depth in P.DEPTHS:
+        steps = [s for seed in P.SEEDS[depth] for s in P.program(seed, depth)]
+        ran = {(s[0], s[2].get("op"), form) for s in steps for form in (s[1], None)}
+        assert set(P.TOUR) <= ran, (depth, sorted(set(P.TOUR) - ran, key=str))
+        assert {(family, None, form) for family in P.ALL_FORMS for form in P.FORMS} <= ran, depth
+        changed = {(s[0], s[2].get("op")) for seed in P.SEEDS[depth] for s, o in zip(P.program(seed, depth), P.run_committed(seed, depth)) if o[5]}
+        idle = {(f, op) for f, op, _ in P.TOUR if f in P.EDITS} - changed
+        assert not idle, (depth, idle)                          # and each edit, with each op, changes a voxel there at least once
+
+
+@pytest.mark.parametrize("seed,depth", P.COMMITTED)
+def test_no_idle_program(seed, depth):
+    steps = P.program(seed, depth)
+    seen = P.run_committed(seed, depth)
+    edits = [o[5] for s, o in zip(steps, seen) if s[0] in P.EDITS]
+    queries = [P.is_empty(o[0]) for s, o in zip(steps, seen) if s[0] in P.QUERIES]
+    assert len(edits) >= len(steps) // 4 and len(queries) >= len(steps) // 5
+    assert sum(edits) >= 0.8 * len(edits), (sum(edits), len(edits))
+    assert sum(queries) <= 0.1 * len(queries), (sum(queries), len(queries))
+    for s, o in zip(steps, seen):
+        if s[0] in P.REFUSALS:
+            assert not o[5]                                     # a refusal leaves both volumes as they were
+
+
+@pytest.mark.parametrize("fault", P.FAULTS)
+@pytest.mark.parametrize("seed", P.SEEDS[5])
+def test_every_fault_is_visible(seed, fault):
+    # zip: where the faulty mirror could not go on (run() stops there) only the steps it did observe count
+    good, bad = P.run_committed(seed, 5), P.run_committed(seed, 5, fault)
+    assert any(not P.same_value(g[:5], b[:5]) for g, b in zip(good, bad)), (seed, fault)
+    if fault == "unordered":
+        # not through the download alone: the query behind a brush and the extraction under a count see it themselves
+        own = {s[0] for s, g, b in zip(P.program(seed, 5), good, bad) if not P.same_value(g[0], b[0])}
+        assert {"fillSpheresAtHits", "surface", "rects"} <= own, (seed, own)
+
+
+def test_scratch_sizes_restate_the_per_family_tests():
+    # tests/test_gpu_volume_surface.py: offsets_bytes; test_gpu_volume_rects.py: block_bytes and :313; test_gpu_volume_pack.py:48
+    assert P.surface_bytes(6) == 8 * (8 ** 6 // 32 // 256 + 7) and P.rects_bytes(6) == 8 * (192 + 7) + 8 * 64 * 64 * 2
+    assert P.pack_bytes(5) == 8 * (pack_model.Shape(5).NT + 1) + 64 and P.marks_bytes(10) == 1 << 27
+    assert P.flood_bytes(5) == 4 * (3 + 8) and P.flood_bytes(6) == 4 * (24 + 8)
+    m = P.Mirror(5)
+    m.apply(("setVoxels", "host", dict(items=np.zeros((10, 3), np.uint32), solid=True)))
+    m.apply(("getVoxels", "host", dict(items=np.zeros((3, 3), np.uint32))))
+    m.apply(("surface", "devA", dict(closed=True, first=0, capacity=5)))
+    assert m.scratch_bytes() == 120 + P.surface_bytes(5)
+    m.apply(("cloneSecond", "host", {}))
+    assert m.scratch_bytes("w") == 0

@@ -1,0 +1,796 @@
+"""Seeded programs of mixed calls on ONE long-lived pair of volumes, and their numpy mirror: what
+tests/test_gpu_volume_program.py runs on the device and tests/test_volume_program_host.py holds to its purpose on the CPU.
+numpy and Python integers only; every expected value comes from the model the family's own tests use (stamp_model,
+flood_model, cells_model, delta_model, pack_model, voxelize_model, surface_model, rect_model, components_model,
+distance_model, fall_model); the sphere predicate is vrc.h:208-210 taken literally, as the brushes' tests take it.
+
+A step is (family, form, arguments): a plain record.  `v` is the program's volume, `w` the second one.
+
+Forms: "host" = host memory (synchronous); "dev0" = device memory on the NULL stream; "devA" / "devB" = device memory on
+the first / second stream of the test's own.  A family without a memory kind (copyRegion, stampAffine, fillRandom,
+applyDelta, cellStep) takes only the stream from its form.
+
+ORDERING says, per combination of a call with what may still be in flight, who orders it.  The GPU test downloads both
+volumes after EVERY step, and vrc_volume_download is "synchronous, after every edit issued so far" (vrc.h:191-192), so
+between two steps nothing is in flight: every two-stream combination between steps is synchronised by the program, as
+vrc.h:178-179 asks of a caller ("issue a volume's asynchronous edits on ONE stream (or order the streams yourself)").  The
+combinations INSIDE a step are the library's to order: the download right behind a device-memory edit (vrc.h:191-192), the
+host-memory list call or query that a brush at hits carries in its `then` argument (vrc.h:205-206, 219-220: the centres lie
+in the staging block, in flight on the caller's stream), and the synchronous surface / rectangle count issued while a
+device-memory extraction of the same step is still on its stream (order "extract_first"; vrc.h:271-272, 315-316).
+
+Sizes of the per-volume scratch blocks (Mirror.scratch_bytes), each restated with the line it was read off:
+  staging, host form   12 n set_voxels (vrc_volume.hip:429), 24 n fill_boxes (:445), 16 n fill_spheres (:462),
+                       64 n brush at hits, 16 n in device form (:484), 36 n xor_mesh (:517), 13 n get_voxels (:603),
+                       32 n count_boxes (:619), 16 per face / rectangle of a host window (:697, :724)
+  mark field           8^(depth-1) (vrc_voxelize.hip:145)
+  surface offsets      8 (ceil(8^depth / 32 / 256) + 7) (vrc_surface.hip:211-221)
+  rectangle block      8 (ceil(6 S^2 w / 256) + 7) + 8 S^2 w, w = max(1, S / 32) (vrc_rects.hip:258-282)
+  pack slots           64 + 8 (tiles + 1) (vrc_pack.hip:354)
+  flood block          4 (3 T^3 + 8), T = max(1, S / 32) (vrc_flood.hip:186-190), on the REGION
+"""
+import functools
+
+import numpy as np
+
+import cells_model
+import components_model
+import delta_model
+import distance_model
+import fall_model
+import flood_model
+import pack_model
+import rect_model
+import stamp_model
+import surface_model
+import voxelize_model
+
+REPLACE, OR, ANDNOT = 0, 1, 2
+FORMS = ("host", "dev0", "devA", "devB")
+HIT_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("voxel_coord", "<f4", 2), ("hit", "<u4"), ("node", "<u4"),
+                      ("distance", "<f4"), ("complexity", "<u4")])                  # vrc_hit, 48 bytes (include/vrc.h)
+
+DEPTHS = (2, 3, 5, 6)
+SEEDS = {2: (21, 22, 23), 3: (31, 32, 33), 5: (51, 52, 53), 6: (61, 62, 63)}
+STEPS = {2: 150, 3: 150, 5: 150, 6: 64}
+COMMITTED = [(seed, depth) for depth in DEPTHS for seed in SEEDS[depth]]
+
+ORDERING = {
+    # (what runs, what may be in flight): (who orders it, where it says so)
+    ("download", "device-memory edit of the same step"): ("library", "vrc.h:191-192"),
+    ("then: host list call / query", "brush at hits of the same step"): ("library", "vrc.h:205-206, 219-220"),
+    ("surface / rect count", "device-memory extraction of the same step (order extract_first)"): ("library", "vrc.h:271-272, 315-316"),
+    ("any call", "an edit of an earlier step, on any stream"): ("program: the download between the steps", "vrc.h:178-179, 191-192"),
+}
+
+LIST_EDITS = ("setVoxels", "fillBoxes", "fillSpheres", "fillSpheresAtHits", "xorMesh")
+STREAM_EDITS = ("copyRegion", "stampAffine", "fillRandom", "applyDelta", "cellStepDst", "cellStepSrc")
+OTHER_EDITS = ("unpack", "floodRegion", "floodMedium", "keepConnected", "dilate", "erode", "select", "place")
+EDITS = LIST_EDITS + STREAM_EDITS + OTHER_EDITS
+QUERIES = ("solidCount", "getVoxels", "countBoxes", "surface", "rects", "pack", "diff", "components", "distanceAt", "commit")
+REFUSALS = ("refuseOp", "refusePack", "refuseUnpack", "refuseDelta", "refuseDepth", "refuseMesh")
+LIFETIME = ("cloneSecond", "recreateSecond", "snapshotLabels", "snapshotClone")
+FAMILIES = EDITS + QUERIES + REFUSALS + LIFETIME
+
+# the families that share a persistent block of `v` (vrc_volume_state.h:15-46); d_stage: in a form that stages
+BLOCKS = {
+    "d_stage": ("setVoxels", "fillBoxes", "fillSpheres", "fillSpheresAtHits", "xorMesh", "getVoxels", "countBoxes", "surface", "rects"),
+    "d_marks": ("xorMesh",),
+    "d_flood": ("floodRegion",),
+    "d_surface": ("surface",),
+    "d_rects": ("rects",),
+    "d_pack": ("pack", "unpack", "refusePack", "refuseUnpack"),
+    "grids": ("commit",),
+    "d_count": ("solidCount", "floodRegion"),
+}
+FAULTS = ("marks", "stage_tail", "rows", "commit", "unordered")
+
+
+def stages(step):
+    """the step writes v's staging block"""
+    family, form, _ = step
+    return family in BLOCKS["d_stage"] and (form == "host" or family == "fillSpheresAtHits")
+
+
+def shared_pairs():
+    """every (block, A, B): an ordered pair of families that share the block"""
+    return sorted((block, a, b) for block, users in BLOCKS.items() for a in users for b in users)
+
+
+def covers(previous, step):
+    """the (block, A, B) that two adjacent steps cover; for d_stage both must be in a form that writes the block"""
+    return {(block, previous[0], step[0]) for block, users in BLOCKS.items()
+            if previous[0] in users and step[0] in users and (block != "d_stage" or (stages(previous) and stages(step)))}
+
+
+# ---- the sizes ---------------------------------------------------------------------------------------------------
+
+def marks_bytes(depth):
+    return 8 ** (depth - 1)
+
+
+def surface_bytes(depth):
+    return 8 * ((8 ** depth // 32 + 255) // 256 + 7)
+
+
+def rects_bytes(depth):
+    S = 1 << depth
+    w = max(1, S // 32)
+    return 8 * ((6 * S * S * w + 255) // 256 + 7) + 8 * S * S * w
+
+
+def pack_bytes(depth):
+    return 64 + 8 * (pack_model.Shape(depth).NT + 1)
+
+
+def flood_bytes(depth):
+    T = max(1, (1 << depth) // 32)
+    return 4 * (3 * T ** 3 + 8)
+
+
+ITEM_BYTES = {"setVoxels": 12, "fillBoxes": 24, "fillSpheres": 16, "xorMesh": 36, "getVoxels": 13, "countBoxes": 32}
+
+
+# ---- small models ------------------------------------------------------------------------------------------------
+
+def spheres(vol, items, value):
+    """vrc.h:208-210: (x-cx)^2 + (y-cy)^2 + (z-cz)^2 <= r^2 in integers, clipped; r < 0 is empty"""
+    S = vol.shape[0]
+    out = vol.copy()
+    for cx, cy, cz, r in np.asarray(items, np.int64).reshape(-1, 4):
+        if r < 0:
+            continue
+        lo = [max(0, c - r) for c in (cx, cy, cz)]
+        hi = [min(S, c + r + 1) for c in (cx, cy, cz)]
+        if any(l >= h for l, h in zip(lo, hi)):
+            continue
+        x, y, z = np.ogrid[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]]
+        out[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]][(x - cx) ** 2 + (y - cy) ** 2 + (z - cz) ** 2 <= r * r] = value
+    return out
+
+
+def boxes(vol, items, value):
+    S = vol.shape[0]
+    out = vol.copy()
+    for b in np.asarray(items, np.int64).reshape(-1, 6):
+        hi = np.minimum(b[3:], S)
+        out[b[0]:hi[0], b[1]:hi[1], b[2]:hi[2]] = value
+    return out
+
+
+def voxels(vol, items, value):
+    S = vol.shape[0]
+    out = vol.copy()
+    p = np.asarray(items, np.int64).reshape(-1, 3)
+    p = p[np.all(p < S, axis=1)]
+    out[p[:, 0], p[:, 1], p[:, 2]] = value
+    return out
+
+
+def count_boxes(vol, items):
+    S = vol.shape[0]
+    out = []
+    for b in np.asarray(items, np.int64).reshape(-1, 6):
+        hi = np.minimum(b[3:], S)
+        out.append(int(vol[b[0]:hi[0], b[1]:hi[1], b[2]:hi[2]].sum()) if np.all(b[:3] < hi) else 0)
+    return np.array(out, np.uint64)
+
+
+def get_voxels(vol, items):
+    S = vol.shape[0]
+    p = np.asarray(items, np.int64).reshape(-1, 3)
+    ok = np.all(p < S, axis=1)
+    out = np.zeros(len(p), np.uint8)
+    out[ok] = vol[p[ok, 0], p[ok, 1], p[ok, 2]]
+    return out
+
+
+def hits_of(cells, S, miss_every=5):
+    """unit-voxel hit records whose vrc_hit_to_voxel voxel is `cells` (vrc.h:196-201: S-1 - floor((position - 1) S); the
+    centre of the reflected cell is exact in float32 for S <= 64), normal (0, -2, 0): the neighbour is y + 1; every
+    miss_every-th record is a miss"""
+    cells = np.asarray(cells, np.int64).reshape(-1, 3)
+    rec = np.zeros(len(cells), HIT_DTYPE)
+    rec["hit"] = 1
+    rec["hit"][::miss_every] = 0
+    rec["position"] = (1.0 + (S - 1 - cells + 0.5) / S).astype(np.float32)
+    rec["normal"][:, 1] = -2
+    return rec
+
+
+def hit_centres(rec, S, solid):
+    """the centres of the brush: dig at the voxel, build at the neighbour where it lies inside"""
+    ok = (rec["hit"] & 0xff) == 1
+    cells = (S - 1 - np.floor((rec["position"][ok].astype(np.float64) - 1.0) * S)).astype(np.int64)
+    if solid:
+        cells = cells + [0, 1, 0]
+        cells = cells[cells[:, 1] < S]
+    return cells
+
+
+def box_mesh(lo, hi):
+    """the 12 triangles of the box [lo, hi) in voxels, as surface_model.triangles winds them: a closed mesh"""
+    q = []
+    for d in range(6):
+        a, s = d >> 1, d & 1
+        u, v = (a + 1) % 3, (a + 2) % 3
+        c = [[0, 0, 0] for _ in range(4)]
+        for k, (du, dv) in enumerate(((0, 0), (1, 0), (1, 1), (0, 1))):
+            c[k][a] = hi[a] if s else lo[a]
+            c[k][u] = hi[u] if du else lo[u]
+            c[k][v] = hi[v] if dv else lo[v]
+        order = (0, 1, 2, 0, 2, 3) if s else (0, 2, 1, 0, 3, 2)
+        q += [c[i] for i in order]
+    return (np.array(q, np.int64).reshape(12, 9) * voxelize_model.UNIT).astype(np.int32)
+
+
+def clipped_triangles(S):
+    """a degenerate triangle (n.z == 0) inside the volume and one wholly outside it in x: neither flips anything"""
+    U = voxelize_model.UNIT
+    return np.array([[U, U, U, U, U, 3 * U, U, U, 2 * U],
+                     [(S + 2) * U, U, U, (S + 5) * U, U, U, (S + 2) * U, 4 * U, U]], np.int32)
+
+
+# ---- the mirror --------------------------------------------------------------------------------------------------
+
+class Mirror:
+    """The dense occupancy of both volumes, the snapshots and the expected scratch.  apply(step) returns what the step's
+    own query must observe (None for an edit) and sets .changed.  Arrays are replaced, never written in place, so that
+    save() / restore() are shallow.  `fault`: one of FAULTS, the model of a library that has that hazard."""
+
+    def __init__(self, depth, fault=None):
+        self.depth, self.S, self.fault = depth, 1 << depth, fault
+        S = self.S
+        self.s = dict(v=np.zeros((S, S, S), np.uint8), w=np.zeros((S, S, S), np.uint8), clone=None, delta=None, stream=None, ids=None,
+                      stage_v=0, blocks_v=frozenset(), stage_w=0, blocks_w=frozenset(),
+                      marks_left=False, stage_tail=b"", rows_of=None, committed=None, before_edit=None)
+        self.changed = False
+
+    def save(self):
+        return dict(self.s)
+
+    def restore(self, saved):
+        self.s = dict(saved)
+
+    def scratch_bytes(self, which="v"):
+        sizes = dict(d_marks=marks_bytes, d_surface=surface_bytes, d_rects=rects_bytes, d_pack=pack_bytes, d_flood=flood_bytes)
+        return self.s["stage_" + which] + sum(sizes[b](self.depth) for b in self.s["blocks_" + which])
+
+    def seen_download(self, which="v"):
+        """what download() right behind the step shows"""
+        if self.fault == "unordered" and which == "v" and self.s["before_edit"] is not None:
+            return self.s["before_edit"]
+        return self.s[which]
+
+    def _stage(self, n_bytes, which="v"):
+        self.s["stage_" + which] = max(self.s["stage_" + which], n_bytes)
+
+    def _block(self, name, which="v"):
+        self.s["blocks_" + which] = self.s["blocks_" + which] | {name}
+
+    def _list_items(self, family, items, host):
+        """the items a host-memory list edit reads: its own -- and, under the stage_tail fault, whatever whole items the
+        block holds behind them"""
+        raw = np.ascontiguousarray(items).tobytes()
+        if host:
+            tail = self.s["stage_tail"]
+            if self.fault == "stage_tail" and len(tail) > len(raw):
+                width = ITEM_BYTES[family]
+                whole = (len(tail) - len(raw)) // width * width
+                items = np.frombuffer(raw + tail[len(raw):len(raw) + whole], items.dtype).reshape(-1, items.shape[1])
+            self.s["stage_tail"] = raw + tail[len(raw):]
+        return items
+
+    def _op(self, dst, bits, op):
+        return cells_model.apply_op(dst, bits, op).astype(np.uint8)
+
+    def apply(self, step):
+        family, form, a = step
+        s, S, depth = self.s, self.S, self.depth
+        v0, w0 = s["v"], s["w"]
+        host = form == "host"
+        out = None
+        s["before_edit"] = None
+        if family in ("setVoxels", "fillBoxes", "fillSpheres"):
+            items = self._list_items(family, a["items"], host)
+            s["v"] = {"setVoxels": voxels, "fillBoxes": boxes, "fillSpheres": spheres}[family](v0, items, 1 if a["solid"] else 0)
+            if host:
+                self._stage(ITEM_BYTES[family] * len(a["items"]))
+        elif family == "fillSpheresAtHits":
+            centres = hit_centres(a["hits"], S, a["solid"])
+            items = np.concatenate([centres, np.full((len(centres), 1), a["radius"], np.int64)], axis=1)
+            s["v"] = spheres(v0, items, 1 if a["solid"] else 0)
+            self._stage((64 if host else 16) * len(a["hits"]))
+            if host:
+                s["stage_tail"] = np.ascontiguousarray(a["hits"]).tobytes() + s["stage_tail"][48 * len(a["hits"]):]
+            if a.get("then") is not None:
+                kind, items = a["then"]
+                if kind == "setVoxels":
+                    s["v"] = voxels(s["v"], self._list_items(kind, items, True), 1)
+                    self._stage(12 * len(items))
+                else:
+                    out = get_voxels(s["v"] if self.fault != "unordered" else v0, items)
+                    self._stage(13 * len(items))
+        elif family == "xorMesh":
+            field = s["v"].copy()
+            if s["marks_left"]:                                   # a stale mark: the scan flips a column it should not
+                field[1, 1, :max(1, S // 2)] ^= 1
+                s["marks_left"] = False
+            s["v"] = voxelize_model.xor_mesh(S, a["tris"], field)
+            if self.fault == "marks" and a["kind"] != "box":
+                s["marks_left"] = True
+            self._block("d_marks")
+            if host:
+                self._stage(36 * len(a["tris"]))
+                s["stage_tail"] = np.ascontiguousarray(a["tris"]).tobytes() + s["stage_tail"][36 * len(a["tris"]):]
+        elif family == "copyRegion":
+            lo, size, dst = a["src_lo"], a["size"], a["dst_lo"]
+            view = tuple(slice(dst[k], dst[k] + size[k]) for k in range(3))
+            bits = w0[tuple(slice(lo[k], lo[k] + size[k]) for k in range(3))]
+            new = v0.copy()
+            new[view] = self._op(new[view], bits, a["op"])
+            s["v"] = new
+        elif family == "stampAffine":
+            s["v"] = stamp_model.stamp(v0, w0, a["m"], a["t"], a["lo"], a["hi"], a["op"])
+        elif family == "fillRandom":
+            s["v"] = cells_model.fill_random(v0, a["seed"], a["threshold"], a["box"], a["op"])
+        elif family == "applyDelta":
+            words = delta_model.apply(delta_model.words_of(v0), s["delta"])
+            s["v"] = delta_model.dense_of(words, depth)
+        elif family == "unpack":
+            s["v"] = pack_model.unpack(s["stream"], depth)
+            self._block("d_pack")
+        elif family == "cellStepDst":
+            s["v"] = cells_model.step(w0, a["birth"], a["survive"], a["neighbours"], a["outside"])[0]
+        elif family == "cellStepSrc":
+            s["w"] = cells_model.step(v0, a["birth"], a["survive"], a["neighbours"], a["outside"])[0]
+        elif family == "floodRegion":
+            s["v"] = flood_model.flood(w0, v0, a["connectivity"], a["through_empty"])
+            self._block("d_flood")
+            out = int(s["v"].sum())
+        elif family == "floodMedium":
+            s["w"] = flood_model.flood(v0, w0, a["connectivity"], a["through_empty"])
+            self._block("d_flood", "w")
+            out = int(s["w"].sum())
+        elif family == "keepConnected":
+            anchors = boxes(np.zeros_like(v0), a["anchors"], 1)
+            s["v"] = flood_model.flood(v0, anchors, a["connectivity"])
+            out = v0 & (1 - s["v"])                               # the debris
+        elif family == "dilate":
+            s["v"] = distance_model.dilate(v0, a["r"]).astype(np.uint8)
+        elif family == "erode":
+            s["v"] = distance_model.erode(v0, a["r"], a["open_border"]).astype(np.uint8)
+        elif family == "select":
+            s["v"] = self._op(v0, components_model.select(s["ids"], a["keep"]), a["op"])
+        elif family == "place":
+            s["v"] = fall_model.place(s["ids"], a["offsets"], v0, a["op"] == OR, a["keep"])
+        elif family == "solidCount":
+            out = int(v0.sum())
+        elif family == "getVoxels":
+            out = get_voxels(v0, a["items"])
+            if host:
+                self._stage(13 * len(a["items"]))
+        elif family == "countBoxes":
+            out = count_boxes(v0, a["items"])
+            if host:
+                self._stage(32 * len(a["items"]))
+        elif family in ("surface", "rects"):
+            # host form: the count, then the window.  Device forms: (counts, window, total); with order "extract_first" the
+            # extraction is still on its stream when the synchronous count of the OTHER `closed` rewrites the shared block
+            # (vrc.h:271-272: the extraction is recorded as the last asynchronous edit, so the count waits for it)
+            seen = v0
+            if family == "rects":
+                seen = s["rows_of"] if self.fault == "rows" and s["rows_of"] is not None else v0
+                s["rows_of"] = seen
+            model = (lambda closed: surface_model.faces(seen, closed)) if family == "surface" else (lambda closed: rect_model.rects(seen, closed))
+            tally = surface_model.direction_counts if family == "surface" else rect_model.direction_counts
+            records = model(a["closed"])
+            first_extract = not host and a.get("order") == "extract_first"
+            counted = model(not a["closed"]) if first_extract else records
+            if first_extract and self.fault == "unordered":
+                records = counted                                 # the extraction reads the offsets the count left
+            window = records[a["first"]:a["first"] + a["capacity"]]
+            out = (tally(counted), window) if host else (tally(counted), window, len(records))
+            self._block("d_" + family)
+            if host and len(window):
+                self._stage(16 * len(window))
+        elif family == "pack":
+            s["stream"] = pack_model.pack(v0, depth)
+            out = s["stream"]
+            self._block("d_pack")
+        elif family == "diff":
+            s["delta"], stats = delta_model.diff(delta_model.words_of(s["clone"]), delta_model.words_of(v0), depth)
+            out = (s["delta"], delta_model.stats_tuple(stats))
+        elif family == "components":
+            out = components_model.label(v0, a["connectivity"])[1]
+        elif family == "distanceAt":
+            D = distance_model.field(v0, a["to_empty"], a["outside"])
+            p = np.asarray(a["items"], np.int64)
+            out = D[p[:, 0], p[:, 1], p[:, 2]].astype(np.uint32)
+        elif family == "commit":
+            out = v0 if self.fault != "commit" or s["committed"] is None else (v0 | s["committed"])
+            s["committed"] = v0
+        elif family in REFUSALS:
+            out = "refused"
+        elif family == "cloneSecond":
+            s["w"], s["stage_w"], s["blocks_w"] = v0, 0, frozenset()
+        elif family == "recreateSecond":
+            s["w"] = cells_model.fill_random(np.zeros_like(v0), a["seed"], a["threshold"])
+            s["stage_w"], s["blocks_w"] = 0, frozenset()
+        elif family == "snapshotLabels":
+            s["ids"], records = components_model.label(v0, a["connectivity"])
+            out = len(records)
+        elif family == "snapshotClone":
+            s["clone"] = v0
+        else:
+            raise ValueError(family)
+        self.changed = not (np.array_equal(s["v"], v0) and np.array_equal(s["w"], w0))
+        if family in EDITS and not host and family not in ("floodMedium", "cellStepSrc"):
+            s["before_edit"] = v0
+        return out
+
+
+@functools.lru_cache(maxsize=None)
+def empty_stream_bytes(depth):
+    S = 1 << depth
+    return len(pack_model.pack(np.zeros((S, S, S), np.uint8), depth))
+
+
+def is_empty(out):
+    """a query's result that shows nothing: None, zero, or all parts empty / all zero"""
+    if out is None:
+        return True
+    if isinstance(out, (tuple, list)):
+        return all(is_empty(o) for o in out)
+    if isinstance(out, (bytes, bytearray)):
+        return len(out) == empty_stream_bytes(pack_model.header_of(out)[2])       # as long as an empty volume's stream
+    if isinstance(out, np.ndarray):
+        return out.size == 0 or (out.dtype.names is None and not out.any())
+    return out == 0
+
+
+# ---- the generator -----------------------------------------------------------------------------------------------
+
+def _box(rng, S, least=1):
+    lo = rng.integers(0, S - least + 1, 3)
+    size = np.array([rng.integers(least, S - l + 1) for l in lo])
+    size = np.minimum(size, max(least, S // 2 + 1))
+    return [int(q) for q in lo], [int(q) for q in size]
+
+
+def _arguments(rng, family, form, m, op=None):
+    """the arguments of one step on the mirror's present state, or None where the family cannot run yet"""
+    S, depth, s = m.S, m.depth, m.s
+    a = {}
+    if family in ("setVoxels", "fillBoxes", "fillSpheres", "fillSpheresAtHits"):
+        a["solid"] = bool(rng.integers(0, 2))
+    if family in ("setVoxels", "getVoxels"):
+        n = int(rng.integers(1, 40)) if rng.random() < 0.7 else int(rng.integers(60, 200))
+        a["items"] = rng.integers(0, S + 1, (n, 3)).astype(np.uint32)
+        if family == "getVoxels" and s["v"].any():
+            solid = np.argwhere(s["v"])
+            a["items"][::2] = solid[rng.integers(0, len(solid), len(a["items"][::2]))]
+    elif family in ("fillBoxes", "countBoxes"):
+        n = int(rng.integers(1, 4)) if rng.random() < 0.7 else int(rng.integers(20, 60))
+        rows = []
+        for _ in range(n):
+            lo, size = _box(rng, S)
+            size = [min(q, max(1, S // 4)) for q in size] if family == "fillBoxes" else size
+            rows.append(lo + [l + q for l, q in zip(lo, size)])
+        a["items"] = np.array(rows, np.uint32)
+    elif family == "fillSpheres":
+        n = int(rng.integers(1, 4)) if rng.random() < 0.7 else int(rng.integers(30, 80))
+        a["items"] = np.concatenate([rng.integers(-1, S + 1, (n, 3)), rng.integers(0, max(2, S // 8) + 1, (n, 1))], axis=1).astype(np.int32)
+    elif family == "fillSpheresAtHits":
+        n = int(rng.integers(3, 30))
+        a["hits"] = hits_of(rng.integers(0, S, (n, 3)), S)
+        a["radius"] = int(rng.integers(0, max(1, S // 16) + 1))
+        a["then"] = None
+        if form in ("devA", "devB") and rng.random() < 0.7:
+            items = rng.integers(0, S, (int(rng.integers(1, 5)), 3)).astype(np.uint32)
+            a["then"] = ("setVoxels" if rng.random() < 0.5 else "getVoxels", items)
+    elif family == "xorMesh":
+        a["kind"] = ("box", "box", "mixed", "clipped")[int(rng.integers(0, 4))]
+        lo, size = _box(rng, S)
+        mesh = box_mesh(lo, [l + q for l, q in zip(lo, size)])
+        a["tris"] = {"box": mesh, "mixed": np.concatenate([clipped_triangles(S), mesh]), "clipped": clipped_triangles(S)}[a["kind"]]
+    elif family == "copyRegion":
+        a["src_lo"], a["size"] = _box(rng, S)
+        a["dst_lo"] = [int(rng.integers(0, S - q + 1)) for q in a["size"]]
+        a["op"] = int(rng.integers(0, 3))
+    elif family == "stampAffine":
+        perms = stamp_model.all_signed_permutations()
+        perm, flip = perms[int(rng.integers(0, len(perms)))]
+        a["m"], a["t"] = stamp_model.signed_permutation(perm, flip, S)
+        lo, size = _box(rng, S)
+        a["lo"], a["hi"], a["op"] = lo, [l + q for l, q in zip(lo, size)], int(rng.integers(0, 3))
+    elif family == "fillRandom":
+        lo, size = _box(rng, S)
+        a["seed"], a["threshold"] = int(rng.integers(0, 1 << 32)), cells_model.threshold_of(float(rng.choice([0.1, 0.3, 0.6])))
+        a["box"], a["op"] = lo + [l + q for l, q in zip(lo, size)], int(rng.integers(0, 3))
+    elif family == "applyDelta":
+        if s["delta"] is None:
+            return None
+    elif family == "unpack":
+        if s["stream"] is None:
+            return None
+        a["device"] = form != "host"
+    elif family in ("cellStepDst", "cellStepSrc"):
+        a["neighbours"] = int(rng.choice([6, 26]))
+        top = a["neighbours"]
+        a["birth"] = cells_model.SMOOTH_BIRTH if top == 26 else sum(1 << c for c in range(3, 7))
+        a["survive"] = cells_model.SMOOTH_SURVIVE if top == 26 else sum(1 << c for c in range(2, 7))
+        a["outside"] = int(rng.integers(0, 2))
+    elif family in ("floodRegion", "floodMedium"):
+        a["connectivity"], a["through_empty"] = int(rng.choice([6, 26])), bool(rng.integers(0, 2))
+    elif family == "keepConnected":
+        lo, size = _box(rng, S, max(1, S // 4))
+        a["anchors"], a["connectivity"] = np.array([lo + [l + q for l, q in zip(lo, size)]], np.uint32), int(rng.choice([6, 26]))
+    elif family in ("dilate", "erode"):
+        a["r"] = int(rng.integers(1, 3))
+        a["open_border"] = bool(rng.integers(0, 2))
+    elif family in ("select", "place"):
+        if s["ids"] is None:
+            return None
+        count = int(s["ids"][s["ids"] != components_model.NO_COMPONENT].max()) + 1 if (s["ids"] != components_model.NO_COMPONENT).any() else 0
+        if count == 0:
+            return None
+        a["keep"] = (rng.random(count) < 0.6).astype(np.uint8)
+        a["keep"][int(rng.integers(0, count))] = 1
+        a["op"] = int(rng.integers(0, 3)) if family == "select" else int(rng.choice([OR, ANDNOT]))
+        if family == "place":
+            a["offsets"] = rng.integers(-2, 3, (count, 3)).astype(np.int32)
+    elif family in ("surface", "rects"):
+        a["closed"], a["first"], a["capacity"] = bool(rng.integers(0, 2)), int(rng.integers(0, 8)), int(rng.integers(1, 400))
+        a["order"] = ("count_first", "extract_first")[int(rng.integers(0, 2))]
+    elif family in ("components", "snapshotLabels"):
+        a["connectivity"] = int(rng.choice([6, 26]))
+    elif family == "distanceAt":
+        a["to_empty"], a["outside"] = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
+        a["items"] = rng.integers(0, S, (int(rng.integers(1, 30)), 3)).astype(np.uint32)
+    elif family == "diff":
+        if s["clone"] is None:
+            return None
+    elif family == "recreateSecond":
+        a["seed"], a["threshold"] = int(rng.integers(0, 1 << 32)), cells_model.threshold_of(0.4)
+    elif family in ("refusePack", "refuseUnpack"):
+        if s["stream"] is None or "d_pack" not in s["blocks_v"]:
+            return None
+        if family == "refuseUnpack":
+            made = pack_model.corruptions(s["stream"])
+            rule, variant, data, _ = made[int(rng.integers(0, len(made)))]
+            a["rule"], a["data"] = rule, bytes(data)
+    elif family == "refuseDelta":
+        a["records"] = np.array([[5, 1], [3, 2]], np.uint32)                  # word 3 behind word 5: not ascending
+    if op is not None and "op" in a:
+        a["op"] = op
+    return a
+
+
+_FORMS_OF = {
+    **{f: FORMS for f in LIST_EDITS + ("getVoxels", "countBoxes", "surface", "rects")},
+    **{f: FORMS[1:] for f in STREAM_EDITS},
+    "unpack": ("host", "dev0"), "pack": ("host", "dev0"), "select": FORMS,
+}
+
+
+OPS_OF = {"copyRegion": (REPLACE, OR, ANDNOT), "stampAffine": (REPLACE, OR, ANDNOT), "fillRandom": (REPLACE, OR, ANDNOT),
+          "select": (REPLACE, OR, ANDNOT), "place": (OR, ANDNOT)}
+ALL_FORMS = LIST_EDITS + ("getVoxels", "countBoxes", "surface", "rects")
+# (family, op, form) for every family, every op of the families that take one and every form of the list calls (None: any
+# form): the tour that every depth's programs run in full
+TOUR = tuple((family, op, form) for family in FAMILIES for op in OPS_OF.get(family, (None,)) for form in (FORMS if family in ALL_FORMS else (None,)))
+
+
+def _circuit(nodes):
+    """a closed walk that takes every ordered pair of `nodes` (a node with itself included) exactly once: Hierholzer on
+    the complete directed graph with loops, edges taken in the order of `nodes`"""
+    left = {a: list(nodes) for a in nodes}
+    stack, walk = [nodes[0]], []
+    while stack:
+        if left[stack[-1]]:
+            stack.append(left[stack[-1]].pop(0))
+        else:
+            walk.append(stack.pop())
+    return tuple(reversed(walk))
+
+
+STAGE_WALK = _circuit(BLOCKS["d_stage"])          # 81 pairs
+PACK_WALK = _circuit(BLOCKS["d_pack"])            # 16 pairs
+
+
+def _share(walk, index, of):
+    """the index-th of `of` stretches of a walk, overlapping by one node so that no pair is lost"""
+    edges = len(walk) - 1
+    per = -(-edges // of)
+    return walk[index * per:min(index * per + per, edges) + 1] if index * per < edges else ()
+
+
+PROLOGUE = (
+    # what the coverage conditions name, once each in every program, before the seeded part
+    ("fillRandom", "dev0", dict(seed=7, threshold=cells_model.threshold_of(0.5), box=None, op=OR)),
+    ("cellStepSrc", "dev0", dict(neighbours=26, birth=cells_model.SMOOTH_BIRTH, survive=cells_model.SMOOTH_SURVIVE, outside=1)),
+    ("snapshotClone", "host", {}),
+    ("snapshotLabels", "host", dict(connectivity=6)),
+    ("commit", "host", {}),
+    ("rects", "host", dict(closed=True, first=0, capacity=50)),
+    ("surface", "host", dict(closed=True, first=0, capacity=50)),
+)
+
+
+class _Writer:
+    """a program being written: the steps so far and the mirror after them"""
+
+    def __init__(self, seed, depth):
+        self.rng, self.m, self.out, self.seen = np.random.default_rng(seed), Mirror(depth), [], []
+
+    def emit(self, step):
+        seen = self.m.apply(step)
+        self.record(step, seen)
+        return seen
+
+    def record(self, step, own):
+        m = self.m
+        self.out.append(step)
+        self.seen.append((own, m.seen_download("v"), m.s["w"], m.scratch_bytes("v"), m.scratch_bytes("w"), m.changed))
+
+    def solid(self, n):
+        """n solid voxels of v (fewer where it holds fewer; one is set first where it holds none)"""
+        if not self.m.s["v"].any():
+            self.emit(("setVoxels", "host", dict(items=np.array([[1, 1, 1]], np.uint32), solid=True)))
+        at = np.argwhere(self.m.s["v"])
+        return at[self.rng.permutation(len(at))[:n]].astype(np.uint32)
+
+    def ready(self, family, pad=True):
+        """what the family needs before it can run: a delta, a stream, a labelling with pieces"""
+        s = self.m.s
+        if pad and family in EDITS and not s["v"].any():                  # an emptied volume shows nothing of a clearing op
+            self.emit(("fillRandom", "dev0", dict(seed=int(self.rng.integers(0, 1 << 32)), threshold=cells_model.threshold_of(0.4), box=None, op=OR)))
+        if pad and family in ("copyRegion", "stampAffine", "cellStepDst", "floodRegion") and not s["w"].any():
+            self.emit(("recreateSecond", "host", dict(seed=int(self.rng.integers(0, 1 << 32)), threshold=cells_model.threshold_of(0.4))))
+        if family in ("select", "place") and (s["ids"] is None or not (s["ids"] != components_model.NO_COMPONENT).any()):
+            self.solid(1)
+            self.emit(("snapshotLabels", "host", dict(connectivity=6)))
+        if family == "diff" and s["clone"] is None:
+            self.emit(("snapshotClone", "host", {}))
+        if family == "applyDelta" and s["delta"] is None:
+            self.ready("diff")
+            self.emit(("diff", "host", {}))
+        if family in ("unpack", "refusePack", "refuseUnpack") and (s["stream"] is None or "d_pack" not in s["blocks_v"]):
+            self.emit(("pack", "host", {}))
+        if pad and family == "unpack" and np.array_equal(pack_model.unpack(self.m.s["stream"], self.m.depth), self.m.s["v"]):
+            self.one("fillBoxes")                                 # so that the stream holds something else than the volume
+
+    def one(self, family, form=None, op=None, tries=8, pad=True):
+        """one step of the family with seeded arguments; an edit that changes nothing or a query that shows nothing is drawn
+        again, up to `tries` times"""
+        self.ready(family, pad)           # pad=False: nothing but the prerequisites, so that a walk's pairs stay adjacent
+        for attempt in range(tries):
+            forms = _FORMS_OF.get(family, ("host",))
+            chosen = form if form is not None else forms[int(self.rng.integers(0, len(forms)))]
+            step = (family, chosen, _arguments(self.rng, family, chosen, self.m, op))
+            saved = self.m.save()
+            seen = self.m.apply(step)
+            idle = (family in EDITS and not self.m.changed) or (family in QUERIES and is_empty(seen))
+            if idle and attempt < tries - 1:
+                self.m.restore(saved)
+                continue
+            self.record(step, seen)
+            return
+
+
+def _scripted(w):
+    """the step sequences that the coverage conditions and the fault switches need, on the mirror's state after PROLOGUE"""
+    S = w.m.S
+    U = S // 2
+    many = np.array([[x, y, z] for x in range(min(S, 6)) for y in range(min(S, 6)) for z in range(2)], np.uint32)
+    few = np.array([[S - 1, S - 1, S - 1]], np.uint32)
+    for step in (
+        ("fillBoxes", "host", dict(items=np.array([[0, 0, 0, U, S, S]], np.uint32), solid=False)),        # lowers the solid count
+        ("commit", "host", {}),
+        ("commit", "host", {}),
+        ("rects", "host", dict(closed=True, first=0, capacity=50)),
+        ("surface", "host", dict(closed=True, first=0, capacity=50)),
+        ("setVoxels", "host", dict(items=many, solid=True)),                                              # larger list ...
+        ("setVoxels", "host", dict(items=few, solid=False)),                                              # ... then smaller
+        ("fillSpheresAtHits", "devA", dict(hits=hits_of(many[:7] + [0, 1, 0], S), radius=0, solid=False, then=None)),
+        ("setVoxels", "host", dict(items=few, solid=True)),
+        ("refuseMesh", "host", {}),
+        ("xorMesh", "host", dict(kind="box", tris=box_mesh([0, 0, 0], [1, 1, 1]))),
+        ("xorMesh", "devA", dict(kind="clipped", tris=clipped_triangles(S))),
+        ("xorMesh", "host", dict(kind="box", tris=box_mesh([S - 1, 0, 0], [S, 1, 1]))),
+        ("recreateSecond", "host", dict(seed=3, threshold=cells_model.threshold_of(0.4))),
+        ("floodMedium", "host", dict(connectivity=26, through_empty=False)),                              # an edit of w ...
+        ("floodRegion", "host", dict(connectivity=6, through_empty=False)),                               # ... then w as the medium of v
+        ("floodRegion", "host", dict(connectivity=26, through_empty=False)),
+        ("solidCount", "host", {}),
+        ("solidCount", "host", {}),
+        ("floodRegion", "host", dict(connectivity=26, through_empty=False)),
+    ):
+        w.emit(step)
+    # inside ONE step, with no download between: a brush on a stream of the test's own, its centres in flight in the staging
+    # block, and right behind it a host-memory list edit -- then a host-memory query of exactly the voxels the brush digs,
+    # which sees them solid unless it waits for the brush
+    w.emit(("fillSpheresAtHits", "devA", dict(hits=hits_of(w.solid(9), S, miss_every=10), radius=0, solid=False, then=("setVoxels", few))))
+    dug = w.solid(9)
+    w.emit(("fillSpheresAtHits", "devB", dict(hits=hits_of(dug, S, miss_every=10), radius=0, solid=False, then=("getVoxels", dug[1:]))))
+    # inside ONE step: an extraction still on its stream while the synchronous count of the other `closed` uses the block;
+    # the corner box makes the two meshes differ in the first records
+    w.emit(("fillBoxes", "dev0", dict(items=np.array([[0, 0, 0, 2, 2, 2]], np.uint32), solid=True)))
+    w.emit(("surface", "devA", dict(closed=True, first=0, capacity=60, order="extract_first")))
+    w.emit(("surface", "devB", dict(closed=False, first=2, capacity=60, order="count_first")))
+    w.emit(("rects", "devB", dict(closed=True, first=0, capacity=60, order="extract_first")))
+    w.emit(("rects", "devA", dict(closed=False, first=2, capacity=60, order="count_first")))
+
+
+def _generate(seed, depth, steps):
+    """PROLOGUE, the scripted conditions, this program's stretch of the two pair walks, its share of TOUR, then seeded steps"""
+    w = _Writer(seed, depth)
+    index = COMMITTED.index((seed, depth)) if (seed, depth) in COMMITTED else 0
+    for step in PROLOGUE:
+        w.emit(step)
+    _scripted(w)
+    for family in _share(STAGE_WALK, index, len(COMMITTED)):
+        w.one(family, "host", tries=3, pad=False)
+    for family in _share(PACK_WALK, index, len(COMMITTED)):
+        w.one(family, "host", tries=1, pad=False)
+    # depths 2 .. 5 run the whole tour in every program; at 64^3, where a program is short, the three seeds share it
+    share = 3 if depth >= 6 else 1
+    tour = [TOUR[i] for i in w.rng.permutation(len(TOUR)) if i % share == index % share]
+    for family, op, form in tour:
+        w.one(family, form, op)
+    names = list(FAMILIES)
+    while len(w.out) < steps:
+        w.one(names[int(w.rng.integers(0, len(names)))])
+    return w.out, w.seen
+
+
+@functools.lru_cache(maxsize=None)
+def _program(seed, depth, steps):
+    steps, seen = _generate(seed, depth, steps)
+    return tuple(steps), tuple(seen)
+
+
+def program(seed, depth, steps=None):
+    """the deterministic list of steps of a seed: the same on every machine (np.random.default_rng, no hashing)"""
+    return list(_program(seed, depth, STEPS[depth] if steps is None else steps)[0])
+
+
+def replay(seed, depth, upto, fault=None):
+    """(the mirror after the steps [0, upto) of the committed program, those steps): where the next person starts"""
+    prefix = program(seed, depth)[:upto]
+    m = Mirror(depth, fault)
+    for step in prefix:
+        m.apply(step)
+    return m, prefix
+
+
+def run(steps, depth, fault=None):
+    """what every step of a program observes on the mirror: [(own observable, download of v, of w, scratch of v, of w)]"""
+    m = Mirror(depth, fault)
+    seen = []
+    for step in steps:
+        try:
+            own = m.apply(step)
+        except (IndexError, ValueError):
+            if fault is None:
+                raise
+            break            # the faulty volume no longer fits the step's arguments: what was seen up to here is all there is
+        seen.append((own, m.seen_download("v"), m.s["w"], m.scratch_bytes("v"), m.scratch_bytes("w"), m.changed))
+    return seen
+
+
+@functools.lru_cache(maxsize=None)
+def run_committed(seed, depth, fault=None):
+    """run() of a committed program, computed once; the arrays in it are shared: read only"""
+    if fault is None:
+        return _program(seed, depth, STEPS[depth])[1]            # what the generator's own mirror saw: run() gives the same
+    return tuple(run(program(seed, depth), depth, fault))
+
+
+def same_value(a, b):
+    if isinstance(a, (tuple, list)):
+        return isinstance(b, (tuple, list)) and len(a) == len(b) and all(same_value(x, y) for x, y in zip(a, b))
+    if isinstance(a, np.ndarray):
+        return isinstance(b, np.ndarray) and a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+    return a == b
