@@ -16,6 +16,8 @@ VRC_COPY_REPLACE, VRC_COPY_OR, VRC_COPY_ANDNOT = 0, 1, 2
 VRC_CONNECT_FACES, VRC_CONNECT_ALL = 6, 26
 VRC_CELLS_FACES, VRC_CELLS_ALL = 6, 26
 VRC_FLOOD_SOLID, VRC_FLOOD_EMPTY = 0, 1
+VRC_COLUMNS_SOLID, VRC_COLUMNS_EMPTY = 1, 2
+VRC_COLUMN_NONE = 0xffffffff
 VRC_NO_COMPONENT = 0xffffffff
 VRC_DISTANCE_NONE = 0xffffffff
 VRC_MESH_FRAC_BITS = 6
@@ -51,6 +53,10 @@ assert CLEARANCE_DTYPE.itemsize == 64
 # a record of a delta (include/vrc.h: vrc_delta_diff): bits = before[word] ^ after[word] != 0, word strictly ascending
 DELTA_RECORD_DTYPE = np.dtype([("word", "<u4"), ("bits", "<u4")])
 assert DELTA_RECORD_DTYPE.itemsize == 8
+# vrc_column (include/vrc.h: vrc_columns_profile): a column met along a direction -- the coordinate of its first and last solid
+# voxel (VRC_COLUMN_NONE in an empty one), its solid voxels and its runs of consecutive solid voxels
+COLUMN_DTYPE = np.dtype([("first", "<u4"), ("last", "<u4"), ("count", "<u4"), ("runs", "<u4")])
+assert COLUMN_DTYPE.itemsize == 16
 
 
 class VrcError(RuntimeError):
@@ -259,6 +265,9 @@ SYMBOLS = {
     "vrc_unpack_volume": (_int, [_vp, _vp, _u64, _int]),
     "vrc_cells_step": (_int, [_vp, _vp, _int, _u32, _u32, _int, _vp, _int, _vp]),
     "vrc_cells_fill_random": (_int, [_vp, _u32, _u64, _vp, _int, _vp]),
+    "vrc_columns_profile": (_int, [_vp, _int, _vp, _vp, _int, _vp]),
+    "vrc_columns_fill": (_int, [_vp, _int, _vp, _vp, _i32, _vp, _i32, _int, _int, _vp]),
+    "vrc_columns_select": (_int, [_vp, _vp, _int, _u32, _u32, _int, _int, _vp]),
     "vrc_volume_xor_mesh": (_int, [_vp, _u64, _vp, _int, _vp]),
     "vrc_volume_surface_count": (_int, [_vp, _int, _vp]),
     "vrc_volume_extract_surface": (_int, [_vp, _int, _int, _u64, _u64, _vp, _vp, _int, _vp]),

@@ -6,7 +6,8 @@
 // kernels in vrc_distance.hip), and the travel-distance field from a set of seeds, kept in the same snapshot object, with the
 // routes read off it (vrc_travel_field, vrc_travel_trace_paths; kernels in vrc_travel.hip), and the difference of two volumes as a list of
 // changed words (vrc_delta_diff, vrc_delta_*; kernels in vrc_delta.hip).  Beside them, because they take two volumes under the same ordering
-// rule, the automaton step and the seeded fill (vrc_cells_*; kernels in vrc_cells.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
+// rule, the automaton step and the seeded fill (vrc_cells_*; kernels in vrc_cells.hip), and the calls that look and write along an
+// axis (vrc_columns_*; kernels in vrc_columns.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
 // event and no scratch: its host-memory calls stage in a block of their own, and what it selects or places goes into a volume
 // as an edit of that volume (staged_call in vrc_volume_state.h; the ordering of every entry point: the table in DESIGN.md).
 #include <hip/hip_runtime.h>
@@ -17,6 +18,7 @@
 #include "../../include/vrc.h"
 #include "vrc_box_words.h"
 #include "vrc_cells.h"
+#include "vrc_columns.h"
 #include "vrc_components.h"
 #include "vrc_delta.h"
 #include "vrc_distance.h"
@@ -863,5 +865,79 @@ extern "C" int vrc_cells_fill_random(vrc_volume* v, uint32_t seed, uint64_t thre
     if (e != hipSuccess) return vrc::fail_hip(e, what);
     vrc::cells_fill_random_run(v->d_bricks, v->depth, seed, threshold, lo, hi, op, st);
     if ((e = hipGetLastError()) == hipSuccess) e = finish(v, VRC_MEM_DEVICE, st, true);
+    return done(e, what);
+}
+
+// ---- columns: the profile of every column, spans from height maps, selection by the solid voxels met (the rules: include/vrc.h; the kernels: vrc_columns.hip) ----
+
+namespace {
+
+// rect (NULL: the whole face) into out[4]: non-empty and inside [0, S]^2, not clipped
+int check_rect(const char* what, const uint32_t* rect, uint32_t S, uint32_t out[4])
+{
+    const uint32_t whole[4] = {0u, 0u, S, S};
+    for (int i = 0; i < 4; ++i) out[i] = (rect ? rect : whole)[i];
+    if (out[0] < out[2] && out[1] < out[3] && out[2] <= S && out[3] <= S) return VRC_OK;
+    return vrc::fail(VRC_ERR_INVALID, "%s: rect (%u, %u, %u, %u) is empty or outside the %u x %u face", what, out[0], out[1], out[2], out[3], S, S);
+}
+
+}  // namespace
+
+extern "C" int vrc_columns_profile(vrc_volume* v, int direction, const uint32_t* rect, vrc_column* out, int mem, void* stream)
+{
+    const char* what = "vrc_columns_profile";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (!out) return vrc::fail(VRC_ERR_INVALID, "%s: null out", what);
+    if (direction < 0 || direction > 5) return vrc::fail(VRC_ERR_INVALID, "%s: bad direction %d", what, direction);
+    uint32_t r[4];
+    if (const int rc = check_rect(what, rect, 1u << v->depth, r)) return rc;
+    if (const int rc = check_mem(what, mem)) return rc;
+    const Call call = volume_call(v->device, mem, stream, v, false);
+    const StagePart parts[] = {{out, (size_t)(r[2] - r[0]) * (r[3] - r[1]) * sizeof(vrc_column), STAGE_OUT}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        vrc::columns_profile_run(v->d_bricks, v->depth, direction, r, (vrc_column*)d[0], call.st);
+        return hipSuccess;
+    });
+}
+
+extern "C" int vrc_columns_fill(vrc_volume* v, int axis, const uint32_t* rect, const int32_t* lo_map, int32_t lo_const, const int32_t* hi_map,
+                                int32_t hi_const, int op, int mem, void* stream)
+{
+    const char* what = "vrc_columns_fill";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (axis < 0 || axis > 2) return vrc::fail(VRC_ERR_INVALID, "%s: bad axis %d", what, axis);
+    uint32_t r[4];
+    if (const int rc = check_rect(what, rect, 1u << v->depth, r)) return rc;
+    if (const int rc = check_op(what, op)) return rc;
+    if (const int rc = check_mem(what, mem)) return rc;
+    const Call call = volume_call(v->device, mem, stream, v, true);
+    const size_t map_bytes = (size_t)(r[2] - r[0]) * (r[3] - r[1]) * 4u;
+    const StagePart parts[] = {{lo_map, map_bytes, STAGE_IN}, {hi_map, map_bytes, STAGE_IN}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        vrc::columns_fill_run(v->d_bricks, v->depth, axis, r, (const int32_t*)d[0], lo_const, (const int32_t*)d[1], hi_const, op, call.st);
+        return hipSuccess;
+    });
+}
+
+extern "C" int vrc_columns_select(vrc_volume* dst, vrc_volume* src, int direction, uint32_t lo, uint32_t hi, int of, int op, void* stream)
+{
+    const char* what = "vrc_columns_select";
+    if (!dst || !src) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (dst == src) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
+    if (dst->depth != src->depth) return vrc::fail(VRC_ERR_INVALID, "%s: volumes of depths %u and %u", what, dst->depth, src->depth);
+    if (dst->device != src->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, dst->device, src->device);
+    if (direction < 0 || direction > 5) return vrc::fail(VRC_ERR_INVALID, "%s: bad direction %d", what, direction);
+    if (lo > hi) return vrc::fail(VRC_ERR_INVALID, "%s: lo %u above hi %u", what, lo, hi);
+    if (of < VRC_COLUMNS_SOLID || of > (VRC_COLUMNS_SOLID | VRC_COLUMNS_EMPTY)) return vrc::fail(VRC_ERR_INVALID, "%s: bad of %d", what, of);
+    if (const int rc = check_op(what, op)) return rc;
+    // no count reaches S: a bound above S + 1 selects what S + 1 selects
+    const uint32_t top = (1u << src->depth) + 1u, band_lo = lo < top ? lo : top, band_hi = hi < top ? hi : top;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(dst->device);
+    if (e == hipSuccess) e = order_behind_edits(src, st);
+    if (e == hipSuccess) e = order_behind_edits(dst, st);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    vrc::columns_select_run(dst->d_bricks, src->d_bricks, dst->depth, direction, band_lo, band_hi, of, op, st);
+    if ((e = hipGetLastError()) == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
     return done(e, what);
 }

@@ -630,6 +630,81 @@ public:
         fillRandom(seed, density, nullptr, VRC_COPY_REPLACE);
         smooth(steps, true);
     }
+    // Along an axis (include/vrc.h: vrc_columns_*).  direction = 2 * axis + side, side 0 travels towards smaller coordinates;
+    // rect = (u_lo, v_lo, u_hi, v_hi) over the other two axes in x < y < z order, nullptr = the whole face; maps are dense
+    // U x V arrays, column (u, v) at (u - u_lo) * V + (v - v_lo).
+    // what every column of the rect holds: first / last solid voxel met, solid voxels, runs.  Synchronous.
+    std::vector<vrc_column> columnProfile(int direction, const uint32_t rect[4] = nullptr)
+    {
+        flush();
+        const uint32_t S = 1u << depth();
+        const uint64_t U = rect ? (rect[2] > rect[0] ? rect[2] - rect[0] : 0u) : S, V = rect ? (rect[3] > rect[1] ? rect[3] - rect[1] : 0u) : S;
+        std::vector<vrc_column> out(std::max<uint64_t>(U * V, 1u));          // an empty rect is refused by the library, by its text
+        check(vrc_columns_profile(v_, direction, rect, out.data(), VRC_MEM_HOST, nullptr), "vrc_columns_profile");
+        return out;
+    }
+    // the coordinate of the first solid voxel met in every column of the whole face, `none` in an empty one
+    std::vector<int32_t> heightMap(int direction, int32_t none = -1)
+    {
+        const std::vector<vrc_column> p = columnProfile(direction);
+        std::vector<int32_t> out(p.size());
+        for (size_t i = 0; i < p.size(); ++i) out[i] = p[i].count ? (int32_t)p[i].first : none;
+        return out;
+    }
+    // the solid voxels of every column along `axis`: the X-ray image
+    std::vector<uint32_t> thicknessMap(int axis)
+    {
+        const std::vector<vrc_column> p = columnProfile(2 * axis);
+        std::vector<uint32_t> out(p.size());
+        for (size_t i = 0; i < p.size(); ++i) out[i] = p[i].count;
+        return out;
+    }
+    // no column has a second run met along `direction`; grounded: and every run reaches the exit face
+    bool isHeightField(int direction, bool grounded = false)
+    {
+        const uint32_t exit_at = (direction & 1) ? (1u << depth()) - 1u : 0u;
+        for (const vrc_column& c : columnProfile(direction))
+            if (c.runs > 1u || (grounded && c.runs == 1u && c.last != exit_at)) return false;
+        return true;
+    }
+    // every column of the rect takes (op) its span [lo, hi) along `axis`: lo from lo_map (nullptr: lo_const), hi likewise,
+    // clamped to [0, S]; under VRC_COPY_REPLACE the rest of the column is cleared.  Synchronous.
+    void fillColumns(int axis, const int32_t* lo_map, int32_t lo_const, const int32_t* hi_map, int32_t hi_const, const uint32_t rect[4] = nullptr,
+                     int op = VRC_COPY_OR)
+    {
+        flush();
+        check(vrc_columns_fill(v_, axis, rect, lo_map, lo_const, hi_map, hi_const, op, VRC_MEM_HOST, nullptr), "vrc_columns_fill");
+    }
+    // the same with the maps in device memory, asynchronous on `stream`
+    void fillColumnsDevice(int axis, const int32_t* lo_map_dev, int32_t lo_const, const int32_t* hi_map_dev, int32_t hi_const,
+                           const uint32_t rect[4] = nullptr, int op = VRC_COPY_OR, void* stream = nullptr)
+    {
+        flush();
+        check(vrc_columns_fill(v_, axis, rect, lo_map_dev, lo_const, hi_map_dev, hi_const, op, VRC_MEM_DEVICE, stream), "vrc_columns_fill");
+    }
+    // main.cpp:65-72 as an editable volume: column (x, z) solid for S/2 + 1 <= y < S/2 + clamp(heights[x * S + z], 16, S), the
+    // rest cleared.  heights: S x S.
+    void raiseTerrain(const std::vector<int32_t>& heights)
+    {
+        const int32_t S = (int32_t)(1u << depth());
+        if (heights.size() != (size_t)S * (size_t)S) throw std::invalid_argument("HipVoxelVolume::raiseTerrain: heights are not S x S");
+        std::vector<int32_t> hi(heights.size());
+        for (size_t i = 0; i < hi.size(); ++i) hi[i] = S / 2 + std::max(16, std::min(S, heights[i]));
+        fillColumns(1, nullptr, S / 2 + 1, hi.data(), 0, nullptr, VRC_COPY_REPLACE);
+    }
+    // dst takes (op) the voxels with lo <= P < hi, P the solid voxels met before the voxel along `direction`, that are solid
+    // (VRC_COLUMNS_SOLID), empty (VRC_COLUMNS_EMPTY) or either (both bits).  This volume is only read.  Asynchronous on `stream`.
+    void selectColumns(HipVoxelVolume& dst, int direction, uint32_t lo, uint32_t hi, int of, int op = VRC_COPY_REPLACE, void* stream = nullptr)
+    {
+        flush();
+        dst.flush();
+        check(vrc_columns_select(dst.v_, v_, direction, lo, hi, of, op, stream), "vrc_columns_select");
+    }
+    // the solid voxels a parallel light along `direction` reaches; the first k solid voxels of every column; the empty
+    // voxels behind a solid one.  Each replaces what dst held.
+    void skyLit(HipVoxelVolume& dst, int direction) { selectColumns(dst, direction, 0u, 1u, VRC_COLUMNS_SOLID); }
+    void topLayers(HipVoxelVolume& dst, int direction, uint32_t k) { selectColumns(dst, direction, 0u, k, VRC_COLUMNS_SOLID); }
+    void sheltered(HipVoxelVolume& dst, int direction) { selectColumns(dst, direction, 1u, (1u << depth()) + 1u, VRC_COLUMNS_EMPTY); }
     // xyz: n x 3 coordinates -> 0 / 1 each (0 outside the volume)
     std::vector<uint8_t> getVoxels(const std::vector<uint32_t>& xyz)
     {

@@ -487,6 +487,116 @@ class VoxelVolume:
         self.fillRandom(seed, density, None, capi.VRC_COPY_REPLACE)
         return self.smooth(steps, outside=True)
 
+    def _rect(self, rect):
+        """(the 4 uint32 of a rect or None, its shape (U, V))"""
+        S = 1 << self.depth
+        if rect is None:
+            return None, (S, S)
+        r = np.ascontiguousarray(rect, np.uint32).reshape(4)
+        return r, (max(int(r[2]) - int(r[0]), 0), max(int(r[3]) - int(r[1]), 0))
+
+    def columnProfile(self, direction, rect=None, device=False):
+        """What every column holds, met along direction = 2 * axis + side (side 0 travels towards smaller coordinates, as for
+        dropLoose): a (U, V) array of capi.COLUMN_DTYPE with the coordinate of the `first` and `last` solid voxel met
+        (capi.VRC_COLUMN_NONE in an empty column), the `count` of solid voxels and the `runs` of consecutive ones (include/vrc.h:
+        vrc_columns_profile).  (U, V) are the other two axes in x < y < z order; rect = (u_lo, v_lo, u_hi, v_hi), the whole
+        face by default.  device: the records stay on the device, as a torch tensor of shape (U, V, 4) int32.  Synchronous."""
+        r, shape = self._rect(rect)
+        if device:
+            import torch
+            out = torch.empty(shape + (4,), dtype=torch.int32, device=f"cuda:{self.device}")
+            check(capi.load().vrc_columns_profile(self._h, int(direction), ptr(r), ptr(out.data_ptr()), capi.VRC_MEM_DEVICE, None))
+            check(capi.load().vrc_stream_synchronize(self.device, None))
+            return out
+        out = np.empty(shape, capi.COLUMN_DTYPE)
+        check(capi.load().vrc_columns_profile(self._h, int(direction), ptr(r), ptr(out), capi.VRC_MEM_HOST, None))
+        return out
+
+    def columnProfileDevice(self, direction, out_ptr, rect=None, stream=None):
+        """the same into U x V records of 16 bytes in device memory, asynchronous on `stream`"""
+        check(capi.load().vrc_columns_profile(self._h, int(direction), ptr(self._rect(rect)[0]), ptr(out_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def heightMap(self, direction, none=-1):
+        """int32 (S, S): the coordinate of the first solid voxel met along `direction` in every column, `none` where there is
+        none.  heightMap(2) is the top-down map of a y-up world."""
+        p = self.columnProfile(direction)
+        return np.where(p["count"] > 0, p["first"].astype(np.int64), none).astype(np.int32)
+
+    def thicknessMap(self, axis):
+        """uint32 (S, S): the solid voxels of every column along `axis`, the X-ray image; it sums to solidCount()"""
+        return self.columnProfile(2 * int(axis))["count"].copy()
+
+    def isHeightField(self, direction, grounded=False):
+        """True if no column has a second run met along `direction`: no overhang and no cave under the surface that the
+        direction sees.  grounded: every run must also reach the exit face."""
+        p = self.columnProfile(direction)
+        exit_at = (1 << self.depth) - 1 if int(direction) & 1 else 0
+        return bool((p["runs"] <= 1).all() and (not grounded or (p["last"][p["runs"] == 1] == exit_at).all()))
+
+    def fillColumns(self, axis, lo, hi, rect=None, op=capi.VRC_COPY_OR, stream=None):
+        """Every column of the rect takes (op) its span [lo, hi) along `axis` (include/vrc.h: vrc_columns_fill): lo and hi are
+        integers or int32 maps of the rect's shape (U, V), clamped to [0, S]; under capi.VRC_COPY_REPLACE the rest of the
+        column is cleared.  Synchronous when a map is given, else asynchronous on `stream`."""
+        r, shape = self._rect(rect)
+        maps, consts = [], []
+        for bound in (lo, hi):
+            if np.ndim(bound) == 0:
+                maps.append(None)
+                consts.append(int(max(-(1 << 31), min((1 << 31) - 1, int(bound)))))
+            else:
+                m = np.ascontiguousarray(bound, np.int32)
+                if m.shape != shape:
+                    raise ValueError(f"fillColumns: a map of shape {m.shape} for a rect of {shape}")
+                maps.append(m)
+                consts.append(0)
+        mem = capi.VRC_MEM_DEVICE if maps[0] is None and maps[1] is None else capi.VRC_MEM_HOST
+        check(capi.load().vrc_columns_fill(self._h, int(axis), ptr(r), ptr(maps[0]), consts[0], ptr(maps[1]), consts[1], int(op), mem, ptr(stream)))
+        return self
+
+    def fillColumnsDevice(self, axis, lo_ptr, lo_const, hi_ptr, hi_const, rect=None, op=capi.VRC_COPY_OR, stream=None):
+        """the same with the maps (or None) in device memory, asynchronous on `stream`"""
+        check(capi.load().vrc_columns_fill(self._h, int(axis), ptr(self._rect(rect)[0]), ptr(lo_ptr), int(lo_const), ptr(hi_ptr), int(hi_const), int(op),
+                                           capi.VRC_MEM_DEVICE, ptr(stream)))
+        return self
+
+    def raiseTerrain(self, heights):
+        """The reference's terrain rule (main.cpp:65-72) as an editable volume: column (x, z) becomes solid for
+        S/2 + 1 <= y < S/2 + clamp(heights[x, z], 16, S), everything else is cleared.  Committed, it is the scene that
+        LSVO.fromTerrain builds from the same heights."""
+        S = 1 << self.depth
+        h = np.asarray(heights)[:S, :S]
+        if h.shape != (S, S):
+            raise ValueError(f"raiseTerrain: heights of shape {np.asarray(heights).shape} for a volume of {S}")
+        hi = S // 2 + np.clip(h.astype(np.int64), 16, S)
+        return self.fillColumns(1, S // 2 + 1, hi.astype(np.int32), None, capi.VRC_COPY_REPLACE)
+
+    def selectColumns(self, direction, lo, hi, of, dst=None, op=capi.VRC_COPY_REPLACE, stream=None):
+        """dst (a new volume with None) takes (op) the voxels with lo <= P < hi, P the solid voxels met before the voxel along
+        `direction`, that are solid (of = capi.VRC_COLUMNS_SOLID), empty (capi.VRC_COLUMNS_EMPTY) or either (3) (include/vrc.h:
+        vrc_columns_select).  This volume is only read.  Asynchronous on `stream`; returns dst."""
+        made = dst is None
+        if made:
+            dst = VoxelVolume(self.depth, self.device)
+        try:
+            check(capi.load().vrc_columns_select(dst._h, self._h, int(direction), int(lo), int(hi), int(of), int(op), ptr(stream)))
+        except Exception:
+            if made:
+                dst.close()
+            raise
+        return dst
+
+    def skyLit(self, direction):
+        """a new volume: the solid voxels a parallel light along `direction` reaches, one per non-empty column"""
+        return self.selectColumns(direction, 0, 1, capi.VRC_COLUMNS_SOLID)
+
+    def topLayers(self, direction, k):
+        """a new volume: the first k solid voxels of every column met along `direction`, the topsoil"""
+        return self.selectColumns(direction, 0, int(k), capi.VRC_COLUMNS_SOLID)
+
+    def sheltered(self, direction):
+        """a new volume: the empty voxels behind a solid one along `direction`, overhangs and caves alike"""
+        return self.selectColumns(direction, 1, (1 << self.depth) + 1, capi.VRC_COLUMNS_EMPTY)
+
     def getVoxels(self, xyz):
         """uint8 0 / 1 per (n, 3) voxel coordinate, 0 outside the volume.  Synchronous."""
         xyz = np.ascontiguousarray(xyz, np.uint32).reshape(-1, 3)

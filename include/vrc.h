@@ -1211,6 +1211,73 @@ int vrc_cells_step(vrc_volume *dst, vrc_volume *src, int neighbours, uint32_t bi
 int vrc_cells_fill_random(vrc_volume *v, uint32_t seed, uint64_t threshold, const uint32_t *lo_hi /* 6, NULL = whole volume */,
                           int op, void *stream);
 
+/* Columns: the volume looked at, and written, along an axis -- a height map out of a volume, a volume out of height maps, and
+ * the voxels a parallel light reaches.  `axis` is 0, 1, 2 for x, y, z and direction = 2 * axis + side as for vrc_fall_drops:
+ * side 0 travels towards smaller coordinates (it enters at the high face), side 1 towards larger ones.  A COLUMN is the S
+ * voxels that differ only in the axis coordinate.  The other two axes in x < y < z order are (u, v): a map of the whole face
+ * has S x S entries, column (u, v) at u * S + v -- for axis 1 this is height[x * S + z] of vrc_scene_build_terrain.  `rect` is
+ * 4 uint32 (u_lo, v_lo, u_hi, v_hi), lo inclusive, hi exclusive, NULL = the whole face; it must be non-empty and lie inside
+ * [0, S]^2 and is NOT clipped (a clipped rect would change the stride of the caller's arrays): the maps of a rect are dense
+ * (u_hi - u_lo) x (v_hi - v_lo) arrays, column (u, v) at (u - u_lo) * (v_hi - v_lo) + (v - v_lo).
+ *
+ * vrc_columns_profile.  Per column of the rect, travelling along the direction from the entry face: `first` is the axis
+ * coordinate of the first solid voxel met, `last` that of the last one, `count` the number of solid voxels and `runs` the
+ * number of maximal runs of consecutive solid voxels; an empty column is (VRC_COLUMN_NONE, VRC_COLUMN_NONE, 0, 0).  A column
+ * with runs == 1 whose run touches the exit face is a height-field column: no overhang, no cave.  `first` is the height map,
+ * `count` the thickness (X-ray) image, count != 0 the silhouette.  The call reads the occupancy: it runs on `stream` behind
+ * the volume's last asynchronous edit and is not an edit; `mem` says where out lives, and VRC_MEM_HOST makes the call
+ * synchronous.  Every record of the rect is written once and nothing else is.
+ *
+ * vrc_columns_fill.  Per column of the rect the span is [lo, hi) along `axis`: lo is the column's entry of lo_map, or lo_const
+ * when lo_map is NULL, and hi likewise; both are int32 and clamped to [0, S], and lo >= hi is an empty span.  Under
+ * VRC_COPY_REPLACE the column becomes exactly its span (the rest of the column is cleared), under VRC_COPY_OR the span is set,
+ * under VRC_COPY_ANDNOT it is cleared; nothing outside the rect's columns is touched.  Both maps NULL is a box fill.  With
+ * axis 1, lo_const = S/2 + 1, hi = S/2 + clamp(height, 16, S) and REPLACE on an empty volume this is the terrain of
+ * vrc_scene_build_terrain, as a volume one can dig in.  `mem` says where the maps live.  The call is an edit on `stream`,
+ * behind the volume's last asynchronous edit and recorded as its last edit; VRC_MEM_HOST makes it synchronous.
+ *
+ * vrc_columns_select.  For a voxel p of src, P(p) is the number of solid voxels met before p (p not counted) when travelling
+ * along the direction through p's column.  K = { p : lo <= P(p) < hi, and p is solid (of = VRC_COLUMNS_SOLID), empty
+ * (VRC_COLUMNS_EMPTY) or either (both bits) }, and dst becomes K (VRC_COPY_REPLACE), dst | K or dst & ~K over the whole volume.
+ * (0, 1, SOLID) is the lit surface, one voxel per non-empty column, at the profile's `first`; (0, 1, EMPTY) the open sky;
+ * (0, k, SOLID) the top k solid voxels of every column; (1, S + 1, EMPTY) everything under a roof, overhangs and caves alike.
+ * No count reaches S, so a bound above S + 1 means S + 1; lo > hi as given is refused, lo == hi selects nothing.  The ordering
+ * is vrc_cells_step's: asynchronous on `stream`, behind the last asynchronous edits of both volumes, recorded as dst's last
+ * edit; src is only read.  dst == src is refused as vrc_cells_step refuses it: clone first.
+ *
+ * VRC_ERR_INVALID as "<function>: <reason>", before any device call: NULL volumes, a NULL out, a direction outside 0..5, an
+ * axis outside 0..2, a rect that is empty or reaches beyond S, an unknown op, `of` or `mem`, lo > hi, dst == src, volumes of
+ * different depths or devices.  Host-memory lists (out, the maps) are staged in a block of the call's own, freed before it
+ * returns: vrc_volume_edit_scratch_bytes is unchanged by all three calls.
+ * The device (csrc/vrc_columns.hip): a word is 2 x 2 x 8 voxels, so 16 columns cross it along x or y, two levels each, and 4
+ * along z, eight levels each.  Profile and select give the columns that cross one word to ONE lane, which walks the words
+ * they cross from face to face -- a stride of a brick plane along x, of a brick row along y, consecutive words along z; along
+ * x and y adjacent lanes take adjacent words -- and carries the columns' state as bit masks and bit-planes over a level's
+ * column positions: seen / previous masks, first and last as planes of the level's coordinate, count and runs by a ripple add
+ * of one bit; select keeps P - lo and P - hi in two's complement and reads the band off the two sign planes.  No atomics, no
+ * cross-lane step, every word read once, every record and every dst word written once.  Fill is one lane per destination
+ * word of the box  rect x the whole axis, which reads the spans of the word's 4 (z) or 16 (x, y) columns and stores the word
+ * once under the box's mask (4^3: two brick rows share a word and its halves take atomics).
+ * Times: profiles/edit/bench_columns.json (tools/bench_edit.py --columns; 512^3 on the MI355X, every list in device memory, device
+ * time by events around 20 calls in a row, median of 5, A B A B next to the yardstick named), alike on the FastNoise terrain and
+ * on a 0.5 random fill.  The profile of the whole face, 4 MiB of records: 0.078 ms along x, 0.080 ms along y, 0.069 ms along z,
+ * next to vrc_volume_clone, 0.037 ms (2.1, 2.2 and 1.9 clones), and vrc_volume_solid_count, 0.025 ms on the terrain (3.1, 3.3, 2.7
+ * counts) and 0.067 ms on the random fill (1.1, 1.2, 1.1).  The fill along y from the 512^2 FastNoise heights (the terrain,
+ * REPLACE): 0.113 ms next to 0.023 ms for a whole-volume vrc_volume_fill_boxes, 4.9 of them: each of the 4 Mi lanes reads the
+ * spans of its word's 16 columns, so the 1 MiB map goes through the caches 256 times -- what the code suggests, not measured
+ * apart.  The select (0, 1, SOLID): 0.077 ms along x and y, 0.066 ms along z, next to 0.031 to 0.032 ms for a 6-neighbour
+ * vrc_cells_step (2.4, 2.4 and 2.1 steps).  No axis stands out; the walks are one lane per bundle, 16384 lanes along x and y
+ * and 65536 along z at this size, each with 512 levels of bit-plane arithmetic behind its loads. */
+typedef struct vrc_column { uint32_t first, last, count, runs; } vrc_column;   /* 16 bytes */
+#define VRC_COLUMN_NONE   0xffffffffu
+#define VRC_COLUMNS_SOLID 1
+#define VRC_COLUMNS_EMPTY 2      /* 3 = both */
+int vrc_columns_profile(vrc_volume *v, int direction, const uint32_t *rect /* 4, NULL = whole face */, vrc_column *out, int mem,
+                        void *stream);
+int vrc_columns_fill(vrc_volume *v, int axis, const uint32_t *rect /* 4, NULL = whole face */, const int32_t *lo_map, int32_t lo_const,
+                     const int32_t *hi_map, int32_t hi_const, int op, int mem, void *stream);
+int vrc_columns_select(vrc_volume *dst, vrc_volume *src, int direction, uint32_t lo, uint32_t hi, int of, int op, void *stream);
+
 /* ---- dense grid: Grid3D<X,Y,Z> (grid_3d.hpp:10-138) ------------------- */
 
 /* cells[(x*Y + y)*Z + z] = Cell::Type (0 = Empty). */

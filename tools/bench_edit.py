@@ -194,6 +194,14 @@ FastNoise terrain and a fillRandom of density 0.5, the format's worst case.  Per
   unpack_ms    vrc_unpack_volume from device memory: the header copy, the checks, the read-back of the totals, the write
   clone_ms     vrc_volume_clone (closed outside the events)
   download_ms  vrc_volume_download, one byte per voxel to the host
+With --columns (printed and written to profiles/edit/bench_columns.json), the column calls at 512^3, device time by events on
+the NULL stream, a sample = 20 calls in a row between two events, divided; one warm-up pair, A B A B in one process, `--pairs`
+pairs, median and range, on two inputs -- the FastNoise terrain and a fillRandom of density 0.5 -- every list in device memory,
+each entry next to an existing pass over the same 16 MiB, timed in the same pair:
+  profile_x / _y / _z    vrc_columns_profile of the whole face (4 MiB of records)          next to  solid_count and clone
+  raise_terrain          vrc_columns_fill along y from the 512^2 FastNoise heights, REPLACE  next to  fill_boxes (one box, the whole volume)
+  select_x / _y / _z     vrc_columns_select (0, 1, SOLID) into a second volume               next to  cells_step with 6 neighbours
+and the ratios of the medians.
 No ratio is promised and no threshold is applied; the numbers are reported."""
 import argparse
 import json
@@ -1582,6 +1590,74 @@ def bench_cells(vrc, depth, pairs):
     return res
 
 
+def bench_columns(vrc, depth, pairs):
+    """vrc_columns_profile / _fill / _select next to vrc_volume_solid_count, vrc_volume_clone, vrc_volume_fill_boxes and
+    vrc_cells_step; see the module's text."""
+    import torch
+    from cpuvoxelraycaster_amd import scenes
+    capi = vrc.capi
+    S = 1 << depth
+    CALLS = 20                           # a single call is tens of microseconds: a sample times twenty in a row
+    res = {"size": S, "pairs": pairs, "calls_per_sample": CALLS, "occupancy_bytes": S ** 3 // 8, "record_bytes": S * S * 16, "map_bytes": S * S * 4}
+    records = torch.empty((S * S, 4), dtype=torch.int32, device="cuda")
+    lim = np.clip(scenes.terrain_heights(S).astype(np.int64), 16, S)
+    hi_map = torch.from_numpy((S // 2 + lim).astype(np.int32)).cuda()
+    whole = torch.tensor([0, 0, 0, S, S, S], dtype=torch.int32).cuda()
+    torch.cuda.synchronize()
+
+    def timed(fns):
+        """A B (C) A B (C), a sample = CALLS calls in a row between two events, divided; what a call returns is closed outside them"""
+        out = [[] for _ in fns]
+        for i in range(pairs + 1):
+            for k, fn in enumerate(fns):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                made = [fn() for _ in range(CALLS)]
+                b.record()
+                b.synchronize()
+                for thing in made:
+                    if isinstance(thing, vrc.VoxelVolume):
+                        thing.close()
+                if i:
+                    out[k].append(a.elapsed_time(b) / CALLS)
+        return [stat(o, 5) for o in out]
+
+    def case(src):
+        dst, other, work = vrc.VoxelVolume(depth), vrc.VoxelVolume(depth), vrc.VoxelVolume(depth)
+        one = {"solid_voxels": src.solidCount()}
+        for axis, name in enumerate("xyz"):
+            e = one["profile_" + name] = {}
+            e["ms"], e["solid_count_ms"], e["clone_ms"] = timed([lambda: src.columnProfileDevice(2 * axis, records.data_ptr()), src.solidCount, src.clone])
+            e["profile_over_solid_count"] = round(e["ms"]["median"] / e["solid_count_ms"]["median"], 3)
+            e["profile_over_clone"] = round(e["ms"]["median"] / e["clone_ms"]["median"], 3)
+        e = one["raise_terrain"] = {}
+        e["ms"], e["fill_boxes_ms"] = timed([lambda: work.fillColumnsDevice(1, None, S // 2 + 1, hi_map.data_ptr(), 0, None, capi.VRC_COPY_REPLACE) and None,
+                                             lambda: other.fillBoxesDevice(1, whole.data_ptr(), True)])
+        e["fill_over_fill_boxes"] = round(e["ms"]["median"] / e["fill_boxes_ms"]["median"], 3)
+        survive = vrc.count_mask(range(1, 7))
+        for axis, name in enumerate("xyz"):
+            e = one["select_" + name] = {}
+            e["ms"], e["cells_step_6_ms"] = timed([lambda: src.selectColumns(2 * axis, 0, 1, capi.VRC_COLUMNS_SOLID, dst) and None,
+                                                   lambda: src.cellStepDevice(other, 0, survive, None, 6)])
+            e["select_over_cells_step"] = round(e["ms"]["median"] / e["cells_step_6_ms"]["median"], 3)
+        one["selected_voxels"] = dst.solidCount()
+        for v in (dst, other, work):
+            v.close()
+        return one
+
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    terrain = vrc.VoxelVolume.fromScene(scene)
+    res["terrain"] = case(terrain)
+    raised = vrc.VoxelVolume(depth).fillColumnsDevice(1, None, S // 2 + 1, hi_map.data_ptr(), 0, None, capi.VRC_COPY_REPLACE)
+    res["raise_terrain_is_the_scene"] = bool(raised.diff(terrain).stats.words == 0)
+    for thing in (raised, terrain, scene):
+        thing.close()
+    noise = vrc.VoxelVolume(depth).fillRandom(1337, 0.5, None, capi.VRC_COPY_REPLACE)
+    res["random_0.5"] = case(noise)
+    noise.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--depths", type=int, nargs="+", default=[8, 9, 10])
@@ -1604,7 +1680,25 @@ def main():
     ap.add_argument("--delta", action="store_true", help="time vrc_delta_diff / vrc_delta_apply next to vrc_volume_clone and a copy of one occupancy (depth 9 unless --depths is given)")
     ap.add_argument("--cells", action="store_true", help="time vrc_cells_step / vrc_cells_fill_random next to vrc_volume_copy_region and vrc_volume_clone (depth 9 unless --depths is given)")
     ap.add_argument("--pack", action="store_true", help="time vrc_pack_volume / vrc_unpack_volume next to vrc_volume_clone and vrc_volume_download (depth 9 unless --depths is given)")
+    ap.add_argument("--columns", action="store_true", help="time vrc_columns_profile / _fill / _select next to vrc_volume_solid_count, vrc_volume_clone, vrc_volume_fill_boxes and vrc_cells_step (depth 9 unless --depths is given)")
     args = ap.parse_args()
+    if args.columns:
+        if args.depths == [8, 9, 10]:
+            args.depths = [9]
+        import __graft_entry__ as g
+        g.build()
+        import torch
+        import cpuvoxelraycaster_amd as vrc
+        if not torch.cuda.is_available():
+            raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
+        out = {"bench": "edit_columns", "device": torch.cuda.get_device_name(0), "depths": {}}
+        for d in args.depths:
+            out["depths"][str(d)] = bench_columns(vrc, d, max(1, args.pairs))
+        print(json.dumps(out))
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_columns.json")
+        with open(path, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+        return
     if args.pack:
         if args.depths == [8, 9, 10]:
             args.depths = [9]
