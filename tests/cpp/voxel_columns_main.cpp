@@ -1,7 +1,8 @@
 // Exercises the column methods of the C++ host adapter (cpuvoxelraycaster_amd/host/hip_raycaster.hpp) at 32^3: the profile of
 // a seeded fill along every direction and in a rect, the maps made from it, fillColumns with maps and constants under the
 // three ops, raiseTerrain, selectColumns and its one-liners.  FNV-1a hashes of the records and downloads are printed, and the
-// pytest wrapper compares them with the numpy model's.
+// pytest wrapper compares them with the numpy model's.  Then one column of 512^3 that holds 256 runs of one voxel, whose record
+// is printed field by field for both sides: beyond the 128 runs that 32^3 .. 128^3 can hold.
 #include <cstdio>
 #include <vector>
 
@@ -62,6 +63,16 @@ int main()
         std::printf("top=%llu\n", hash_of(other));
         world.sheltered(other, 4);
         std::printf("sheltered=%llu\n", hash_of(other));
+
+        // the column (x, z) = (301, 77) of 512^3 along y: solid at y = 1, 3, .. 511
+        vrc_host::HipVoxelVolume tall(9);
+        for (uint32_t y = 1; y < 512; y += 2) tall.fillBox(301, y, 77, 302, y + 1, 78, true);
+        const uint32_t one[4] = {301, 77, 302, 78};
+        for (int side = 0; side < 2; ++side) {
+            const std::vector<vrc_column> c = tall.columnProfile(2 + side, one);
+            std::printf("comb%d=%u,%u,%u,%u size=%zu\n", side, c[0].first, c[0].last, c[0].count, c[0].runs, c.size());
+        }
+        std::printf("comb_solid=%llu\n", (unsigned long long)tall.solidCount());
     } catch (const std::exception& e) {
         std::printf("error %s\n", e.what());
         return 1;

@@ -10,7 +10,10 @@ model of columns_model.py, bit for bit.  The sizes are the smallest at which eac
 A lane takes one bundle and the launches are not capped, so no size makes a lane take a second item, and no state crosses
 lanes.  What still grows with the size is the counters: plane b of a count first holds a one at a count of 2^b.  A full
 volume at 256^3 reaches plane 8; planes 9 and 10 are reached at 512^3 and 1024^3 only, so one case runs there on a full
-volume and checks records of a small rect and counts of boxes -- nothing dense comes down at that size."""
+volume and checks records of a small rect and counts of boxes -- nothing dense comes down at that size.  "Reached" is all a
+full volume does: its first and last are 0 or S - 1, its count S or S - 1 and its runs 1 or 2, so every plane is all ones or
+all zeros.  tests/test_gpu_volume_columns_planes.py runs columns with mixed patterns in the high planes of all four
+numbers and of the select's two, at the depths 7 .. 10 (the cases are tests/columns_cases.py's)."""
 import numpy as np
 import pytest
 

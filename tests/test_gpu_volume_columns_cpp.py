@@ -1,13 +1,14 @@
 """The column methods through the C++ host adapter (HipVoxelVolume::columnProfile / heightMap / thicknessMap / isHeightField /
 fillColumns / raiseTerrain / selectColumns / skyLit / topLayers / sheltered) against the numpy model:
 tests/cpp/voxel_columns_main.cpp prints FNV-1a hashes of its records and downloads, this file computes the same from
-columns_model.py."""
+columns_model.py.  Its last lines are the record of one comb column of 512^3 (256 runs), expected from columns_cases.py."""
 import re
 
 import numpy as np
 import pytest
 
 import cells_model
+import columns_cases
 import columns_model as model
 from volume_support import fnv1a, run_cpp_main
 
@@ -55,3 +56,11 @@ def test_cpp_columns_match_the_model(built, tmp_path):
     assert value("lit") == digest(model.selection(world, 2, 0, 1, model.SOLID))
     assert value("top") == digest(model.selection(world, 1, 0, 3, model.SOLID))
     assert value("sheltered") == digest(model.selection(world, 4, 1, S + 1, model.EMPTY))
+
+    comb = tuple((y, y + 1) for y in range(1, 512, 2))
+    assert comb in [runs for _, runs in columns_cases.catalogue(512)]            # "comb 256 from 1"
+    for side in (0, 1):
+        want = columns_cases.record_tuple(comb, 512, side)
+        assert want == ((1, 511, 256, 256) if side else (511, 1, 256, 256))
+        assert re.search(r"\bcomb%d=%d,%d,%d,%d size=1\b" % ((side,) + want), out), (side, want)
+    assert value("comb_solid") == 256
