@@ -204,7 +204,9 @@ each entry next to an existing pass over the same 16 MiB, timed in the same pair
 and the ratios of the medians.
 No ratio is promised and no threshold is applied; the numbers are reported."""
 import argparse
+import collections
 import json
+import math
 import os
 import statistics
 import sys
@@ -212,41 +214,64 @@ import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def device_ms(fn, repeats=5):
-    import torch
-    out = []
-    for i in range(repeats + 1):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        if i:                                        # the first run warms up
-            out.append(a.elapsed_time(b))
-    return statistics.median(out)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 
 
 def stat(values, digits=5):
     return {"median": round(statistics.median(values), digits), "min": round(min(values), digits), "max": round(max(values), digits)}
 
 
+def event_ms(fn):
+    """(device ms between two events on the NULL stream around fn(), what fn returned)"""
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b), out
+
+
+def device_ms(fn, repeats=5):
+    return statistics.median([event_ms(fn)[0] for _ in range(repeats + 1)][1:])          # the first run warms up
+
+
+def timed(fn, repeats, digits=4, before=None, after=None):
+    """One call over `repeats` samples after one warm-up: returns (stat, the last result).  The previous result is closed, if
+    it can be, before the next pair of events.  With `before`, fn takes what before() made outside the events, and
+    after(result, that) -- outside them too -- gives what is kept as the result."""
+    out, last = [], None
+    for i in range(repeats + 1):
+        if last is not None and hasattr(last, "close"):
+            last.close()
+        arg = before() if before else None
+        ms, last = event_ms((lambda: fn(arg)) if before else fn)
+        if i:
+            out.append(ms)
+        if after:
+            last = after(last, arg)
+    return stat(out, digits), last
+
+
+def timed_ab(fns, pairs, calls=1, digits=5):
+    """A B (C ...) A B (C ...) after one warm-up round: a sample is `calls` calls in a row between two events, divided.  What a
+    call returns is closed, if it can be, after the events.  One stat per function."""
+    out = [[] for _ in fns]
+    for i in range(pairs + 1):
+        for k, fn in enumerate(fns):
+            ms, made = event_ms(lambda: [fn() for _ in range(calls)])
+            for thing in made:
+                if hasattr(thing, "close"):
+                    thing.close()
+            if i:
+                out[k].append(ms / calls)
+    return [stat(o, digits) for o in out]
+
+
 def ab_device_ms(fa, fb, pairs):
     """A B A B: device time of each by events on the NULL stream, one warm-up pair first"""
-    import torch
-    out = ([], [])
-    for i in range(pairs + 1):
-        for k, fn in enumerate((fa, fb)):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if i:
-                out[k].append(a.elapsed_time(b))
-    return stat(out[0]), stat(out[1])
+    return timed_ab((fa, fb), pairs)
 
 
 def ab_wall_ms(fa, fb, pairs):
@@ -264,6 +289,63 @@ def ab_wall_ms(fa, fb, pairs):
 
 
 HBM_BYTES_PER_S = 8.0e12     # MI355X peak
+
+
+def fall_cuts(S):
+    """(the boxes the fall benchmark clears from the terrain, the slab its columns stand on): a band of four layers 24 voxels
+    above the slab (the first box), one of three layers 44 above it, and from the lower band up planes two voxels thick every
+    32 voxels along x and z"""
+    floor_y = S // 2 + 1
+    cuts = [[0, floor_y + 24, 0, S, floor_y + 28, S], [0, floor_y + 44, 0, S, floor_y + 47, S]]
+    cuts += [[c, floor_y + 24, 0, c + 2, S, S] for c in range(30, S, 32)] + [[0, floor_y + 24, c, S, S, c + 2] for c in range(30, S, 32)]
+    return cuts, [[0, floor_y, 0, S, floor_y + 1, S]]
+
+
+def fall_scene(vrc, depth, label=True, whole=False):
+    """The fall benchmark's scene (the module's text, --fall): the FastNoise terrain with fall_cuts cleared, split by
+    keepConnected from the slab.  Returns (scene, world = the supported part, debris, the debris' labels or None without
+    `label`, and with `whole` a clone of the medium taken before the split, else None)."""
+    cuts, slab = fall_cuts(1 << depth)
+    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
+    world = vrc.VoxelVolume.fromScene(scene)
+    world.fillBoxes(cuts, False)
+    full = world.clone() if whole else None
+    debris = world.keepConnected(slab, 6)
+    return scene, world, debris, debris.labelComponents(6) if label else None, full
+
+
+def turn_30_30():
+    """a rotation by 30 degrees about x, then about y, in vrc_make_rotation's layout (columns)"""
+    c, s = math.cos(math.radians(30)), math.sin(math.radians(30))
+    rx = np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
+    ry = np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
+    return np.ascontiguousarray((ry @ rx).T, np.float32).reshape(9)
+
+
+def turn_poses(labels):
+    """(maps, boxes) of every piece turned by turn_30_30 about its own centre of mass"""
+    return labels.poses(turn_30_30(), labels.massProperties()[1])
+
+
+def translate_poses(labels, records, offsets, S):
+    """(maps, boxes) of every piece moved by its row of `offsets` (the fall's): pure-translation maps, the record boxes moved"""
+    from cpuvoxelraycaster_amd import capi
+    maps = np.zeros(labels.count, capi.AFFINE_DTYPE)
+    maps["m"][:] = [65536, 0, 0, 0, 65536, 0, 0, 0, 65536]
+    maps["t"][:] = -(offsets.astype(np.int64) << 17)
+    boxes = np.concatenate([np.clip(records["lo"].astype(np.int64) + offsets, 0, S), np.clip(records["hi"].astype(np.int64) + offsets, 0, S)], axis=1).astype(np.uint32)
+    return maps, boxes
+
+
+def box_words(boxes):
+    """the (piece, destination word) work items of the placement: vrc_box_words.h's count over the non-empty boxes"""
+    return int(sum(((int(b[3]) - 1) // 2 - int(b[0]) // 2 + 1) * ((int(b[4]) - 1) // 2 - int(b[1]) // 2 + 1) * ((((int(b[5]) - 1) // 2 - int(b[2]) // 2) + 3) // 4 + 1)
+                   for b in boxes if all(b[a] < b[a + 3] for a in range(3))))
+
+
+def on_device(array):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).cuda()
 
 
 def bench_brushes(vrc, depth, pairs):
@@ -370,7 +452,7 @@ def bench_brushes(vrc, depth, pairs):
 
 def bench_flood(vrc, depth, pairs):
     import torch
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
     import flood_model
     S = 1 << depth
     rng = np.random.default_rng(depth)
@@ -388,13 +470,9 @@ def bench_flood(vrc, depth, pairs):
         def fa():
             region.fillBoxes(whole, False)
             (region.setVoxels if seed_is_voxels else region.fillBoxes)(seed)
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            st = region.flood(medium, connectivity, through_empty)
-            b.record()
-            b.synchronize()
+            ms, st = event_ms(lambda: region.flood(medium, connectivity, through_empty))
             assert st.converged == 1
-            stats.append((a.elapsed_time(b), st.sweeps, st.reached))
+            stats.append((ms, st.sweeps, st.reached))
 
         def fb():
             region.solidCount()
@@ -402,14 +480,10 @@ def bench_flood(vrc, depth, pairs):
         flood_ms, reads = [], []
         for i in range(pairs + 1):
             fa()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fb()
-            b.record()
-            b.synchronize()
+            ms, _ = event_ms(fb)
             if i:
                 flood_ms.append(stats[-1][0])
-                reads.append(a.elapsed_time(b))
+                reads.append(ms)
         sweeps = stats[-1][1]
         assert all(s[2] == stats[-1][2] for s in stats)
         floor = statistics.median(reads) * sweeps
@@ -484,7 +558,7 @@ def subdivided_icosphere(vrc, subdivisions):
 
 def bench_voxelize(vrc, depth, pairs):
     import torch
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
     import voxelize_model
     S = 1 << depth
     rng = np.random.default_rng(depth)
@@ -659,8 +733,7 @@ def bench_depth(vrc, depth, pairs):
             build.append(b.build_ms)
         a.close()
         b.close()
-    res["commit_ms"] = {"median": round(statistics.median(commit), 4), "min": round(min(commit), 4), "max": round(max(commit), 4)}
-    res["build_volume_ms"] = {"median": round(statistics.median(build), 4), "min": round(min(build), 4), "max": round(max(build), 4)}
+    res["commit_ms"], res["build_volume_ms"] = stat(commit, 4), stat(build, 4)
     res["commit_within_baseline_spread"] = bool(statistics.median(commit) <= max(build))
     res["pairs"] = pairs
 
@@ -689,21 +762,6 @@ def bench_components(vrc, depth, pairs):
     res = {"size": S, "pairs": pairs, "id_array_bytes": 4 * S ** 3}
     scene = vrc.LSVO.fromFastNoiseTerrain(depth)
     terrain = vrc.VoxelVolume.fromScene(scene)
-
-    def timed(fn, repeats):
-        """device ms by events around fn, one warm-up; returns (stat, the last result)"""
-        out, last = [], None
-        for i in range(repeats + 1):
-            if last is not None and hasattr(last, "close"):
-                last.close()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            last = fn()
-            b.record()
-            b.synchronize()
-            if i:
-                out.append(a.elapsed_time(b))
-        return stat(out, 4), last
 
     def case(medium, connectivity, through_empty):
         r = {"connectivity": connectivity, "through_empty": through_empty}
@@ -768,13 +826,9 @@ def bench_components(vrc, depth, pairs):
             region.fillBoxes(seed_boxes)
         else:
             region.setVoxels([seed_voxel])
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        st = region.flood(terrain, 6)
-        b.record()
-        b.synchronize()
+        ms, st = event_ms(lambda: region.flood(terrain, 6))
         assert st.converged == 1
-        return a.elapsed_time(b), st
+        return ms, st
 
     bottom = np.array([[0, S // 2 + 1, 0, S, S // 2 + 2, S]], np.uint32)
     floods = [flood_from(seed_boxes=bottom)[0] for _ in range(pairs + 1)][1:]
@@ -809,21 +863,6 @@ def bench_distance(vrc, depth, pairs):
     corner = vrc.VoxelVolume(depth)
     corner.setVoxels([[0, 0, 0]])
     empty = vrc.VoxelVolume(depth)
-
-    def timed(fn, repeats):
-        """device ms by events around fn, one warm-up; returns (stat, the last result)"""
-        out, last = [], None
-        for i in range(repeats + 1):
-            if last is not None and hasattr(last, "close"):
-                last.close()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            last = fn()
-            b.record()
-            b.synchronize()
-            if i:
-                out.append(a.elapsed_time(b))
-        return stat(out, 4), last
 
     src = torch.empty(S ** 3, dtype=torch.int32, device="cuda")
     dst_t = torch.empty(S ** 3, dtype=torch.int32, device="cuda")
@@ -870,7 +909,6 @@ def bench_travel(vrc, depth, pairs):
     the solid from the floor layer (the slab y = S / 2 + 1 its columns stand on), both connectivities; device ms by events, median of `pairs`, and the sweeps
     issued.  In the same run vrc_volume_flood from the same seeds on the same medium: it computes the support of the same
     field (a fresh copy of the seeds per repeat, made outside the timed span)."""
-    import torch
     S = 1 << depth
     res = {"size": S, "pairs": pairs, "field_bytes": 4 * S ** 3}
     scene = vrc.LSVO.fromFastNoiseTerrain(depth)
@@ -885,23 +923,10 @@ def bench_travel(vrc, depth, pairs):
     floor = vrc.VoxelVolume(depth)
     floor.fillBoxes([[0, floor_y, 0, S, floor_y + 1, S]])
 
-    def timed(fn, repeats, before=None):
-        out, last = [], None
-        for i in range(repeats + 1):
-            if last is not None and hasattr(last, "close"):
-                last.close()
-            arg = before() if before else None
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            last = fn(arg) if before else fn()
-            b.record()
-            b.synchronize()
-            if i:
-                out.append(a.elapsed_time(b))
-            if arg is not None:
-                last = (last, arg.solidCount())
-                arg.close()
-        return stat(out, 4), last
+    def count_reached(stats, region):
+        reached = region.solidCount()
+        region.close()
+        return stats, reached
 
     for name, seeds, through_empty in (("air_from_one_seed", air_seed, True), ("solid_from_the_floor", floor, False)):
         res[name] = {"seed": above if seeds is air_seed else "layer y = %d" % floor_y}
@@ -911,7 +936,7 @@ def bench_travel(vrc, depth, pairs):
             st = field.stats
             r["seeds"], r["reached"], r["max_steps"], r["sweeps"] = int(st.seeds), int(st.reached), int(st.max_steps), int(st.sweeps)
             field.close()
-            r["flood_ms"], (fst, flooded) = timed(lambda region: region.flood(terrain, connectivity, through_empty), pairs, before=seeds.clone)
+            r["flood_ms"], (fst, flooded) = timed(lambda region: region.flood(terrain, connectivity, through_empty), pairs, before=seeds.clone, after=count_reached)
             r["flood_sweeps"], r["flood_reached"] = int(fst.sweeps), int(flooded)
             r["travel_over_flood"] = round(r["travel_ms"]["median"] / r["flood_ms"]["median"], 2)
             res[name]["connectivity_%d" % connectivity] = r
@@ -927,31 +952,9 @@ def bench_fall(vrc, depth, pairs):
     import torch
     S = 1 << depth
     res = {"size": S, "pairs": pairs}
-    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
-    world = vrc.VoxelVolume.fromScene(scene)
-    floor_y = S // 2 + 1
-    band = [0, floor_y + 24, 0, S, floor_y + 28, S]
-    cuts = [band, [0, floor_y + 44, 0, S, floor_y + 47, S]]
-    cuts += [[c, floor_y + 24, 0, c + 2, S, S] for c in range(30, S, 32)] + [[0, floor_y + 24, c, S, S, c + 2] for c in range(30, S, 32)]
-    world.fillBoxes(cuts, False)
-    debris = world.keepConnected([[0, floor_y, 0, S, floor_y + 1, S]], 6)
-    res["band"], res["supported_voxels"], res["debris_voxels"] = band, world.solidCount(), debris.solidCount()
+    scene, world, debris, _, _ = fall_scene(vrc, depth, label=False)           # the labelling is timed below
+    res["band"], res["supported_voxels"], res["debris_voxels"] = fall_cuts(S)[0][0], world.solidCount(), debris.solidCount()
     down = vrc.capi.VRC_FACE_YN
-
-    def timed(fn, repeats):
-        out, last = [], None
-        for i in range(repeats + 1):
-            if last is not None and hasattr(last, "close"):
-                last.close()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            last = fn()
-            b.record()
-            b.synchronize()
-            if i:
-                out.append(a.elapsed_time(b))
-        return stat(out, 4), last
-
     res["label_ms"], labels = timed(lambda: debris.labelComponents(6), pairs)
     res["pieces"] = labels.count
     offsets = torch.zeros((max(labels.count, 1), 3), dtype=torch.int32).cuda()
@@ -971,50 +974,21 @@ def bench_fall(vrc, depth, pairs):
 
 
 def bench_rigid(vrc, depth, pairs):
-    """vrc_rigid_moments next to vrc_labels_select, vrc_rigid_place_affine next to vrc_fall_place, on bench_fall's scene"""
-    import math
+    """vrc_rigid_moments next to vrc_labels_select, vrc_rigid_place_affine next to vrc_fall_place, on fall_scene"""
     import torch
     S = 1 << depth
     res = {"size": S, "pairs": pairs}
-    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
-    world = vrc.VoxelVolume.fromScene(scene)
-    floor_y = S // 2 + 1
-    band = [0, floor_y + 24, 0, S, floor_y + 28, S]
-    cuts = [band, [0, floor_y + 44, 0, S, floor_y + 47, S]]
-    cuts += [[c, floor_y + 24, 0, c + 2, S, S] for c in range(30, S, 32)] + [[0, floor_y + 24, c, S, S, c + 2] for c in range(30, S, 32)]
-    world.fillBoxes(cuts, False)
-    debris = world.keepConnected([[0, floor_y, 0, S, floor_y + 1, S]], 6)
-    labels = debris.labelComponents(6)
+    scene, world, debris, labels, _ = fall_scene(vrc, depth)
     C_ = labels.count
     res["pieces"], res["supported_voxels"], res["debris_voxels"] = C_, world.solidCount(), debris.solidCount()
     OR = vrc.capi.VRC_COPY_OR
-
-    def timed(fn):
-        out = []
-        for i in range(pairs + 1):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if i:
-                out.append(a.elapsed_time(b))
-        return stat(out, 4)
-
-    def box_words(boxes):
-        """the (piece, destination word) work items of the placement: vrc_box_words.h's count over the non-empty boxes"""
-        return int(sum(((int(b[3]) - 1) // 2 - int(b[0]) // 2 + 1) * ((int(b[4]) - 1) // 2 - int(b[1]) // 2 + 1) * ((((int(b[5]) - 1) // 2 - int(b[2]) // 2) + 3) // 4 + 1)
-                       for b in boxes if all(b[a] < b[a + 3] for a in range(3))))
-
-    def on_device(array):
-        return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).cuda()
 
     keep = torch.ones(max(C_, 1), dtype=torch.uint8).cuda()
     moments = torch.zeros(max(C_, 1) * 80, dtype=torch.uint8).cuda()
     target = world.clone()
     torch.cuda.synchronize()
-    res["moments_ms"] = timed(lambda: labels.momentsDevice(0, C_, moments.data_ptr(), None))
-    res["select_ms"] = timed(lambda: labels.selectDevice(keep.data_ptr(), target, OR, None))
+    res["moments_ms"], _ = timed(lambda: labels.momentsDevice(0, C_, moments.data_ptr(), None), pairs)
+    res["select_ms"], _ = timed(lambda: labels.selectDevice(keep.data_ptr(), target, OR, None), pairs)
     res["moments_over_select"] = round(res["moments_ms"]["median"] / res["select_ms"]["median"], 2)
     got = moments.cpu().numpy().view(vrc.capi.MOMENTS_DTYPE)[:C_]
     records = labels.components()
@@ -1023,30 +997,23 @@ def bench_rigid(vrc, depth, pairs):
 
     offsets, st = labels.fall(world, vrc.capi.VRC_FACE_YN)
     res["max_drop"] = int(st.max_drop)
-    maps = np.zeros(C_, vrc.capi.AFFINE_DTYPE)
-    maps["m"][:] = [65536, 0, 0, 0, 65536, 0, 0, 0, 65536]
-    maps["t"][:] = -(offsets.astype(np.int64) << 17)
-    boxes = np.concatenate([np.clip(records["lo"].astype(np.int64) + offsets, 0, S), np.clip(records["hi"].astype(np.int64) + offsets, 0, S)], axis=1).astype(np.uint32)
+    maps, boxes = translate_poses(labels, records, offsets, S)
     res["translate_box_words"] = box_words(boxes)
     d_offsets, d_maps, d_boxes = on_device(offsets), on_device(maps), on_device(boxes)
     by_fall, by_maps = world.clone(), world.clone()
     torch.cuda.synchronize()
-    res["fall_place_ms"] = timed(lambda: labels.placeDevice(d_offsets.data_ptr(), by_fall, OR, None, None))
-    res["place_translate_ms"] = timed(lambda: labels.placeAffineDevice(d_maps.data_ptr(), by_maps, d_boxes.data_ptr(), OR, None, None))
+    # the place calls return their destination: `and None` keeps timed() from closing it
+    res["fall_place_ms"], _ = timed(lambda: labels.placeDevice(d_offsets.data_ptr(), by_fall, OR, None, None) and None, pairs)
+    res["place_translate_ms"], _ = timed(lambda: labels.placeAffineDevice(d_maps.data_ptr(), by_maps, d_boxes.data_ptr(), OR, None, None) and None, pairs)
     res["place_translate_over_fall_place"] = round(res["place_translate_ms"]["median"] / res["fall_place_ms"]["median"], 2)
     res["placed_voxels"] = by_maps.solidCount()
     assert res["placed_voxels"] == by_fall.solidCount() and np.array_equal(by_maps.download(), by_fall.download()), "translation maps differ from vrc_fall_place"
 
-    c, s = math.cos(math.radians(30)), math.sin(math.radians(30))
-    rx = np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
-    ry = np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
-    rot = np.ascontiguousarray((ry @ rx).T, np.float32).reshape(9)
-    centre = labels.massProperties()[1]
-    maps, boxes = labels.poses(rot, centre)
+    maps, boxes = turn_poses(labels)
     d_maps, d_boxes = on_device(maps), on_device(boxes)
     turned = world.clone()
     torch.cuda.synchronize()
-    res["place_turn_ms"] = timed(lambda: labels.placeAffineDevice(d_maps.data_ptr(), turned, d_boxes.data_ptr(), OR, None, None))
+    res["place_turn_ms"], _ = timed(lambda: labels.placeAffineDevice(d_maps.data_ptr(), turned, d_boxes.data_ptr(), OR, None, None) and None, pairs)
     res["turned_voxels"] = turned.solidCount()
     res["turn_box_words"] = box_words(boxes)
     for v in (turned, by_fall, by_maps, target, labels, debris, world):
@@ -1056,65 +1023,30 @@ def bench_rigid(vrc, depth, pairs):
 
 
 def bench_contacts(vrc, depth, pairs):
-    """vrc_rigid_contacts next to vrc_rigid_place_affine with the same maps and boxes, on bench_fall's scene"""
-    import math
+    """vrc_rigid_contacts next to vrc_rigid_place_affine with the same maps and boxes, on fall_scene"""
     import torch
     S = 1 << depth
     res = {"size": S, "pairs": pairs}
-    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
-    world = vrc.VoxelVolume.fromScene(scene)
-    floor_y = S // 2 + 1
-    band = [0, floor_y + 24, 0, S, floor_y + 28, S]
-    cuts = [band, [0, floor_y + 44, 0, S, floor_y + 47, S]]
-    cuts += [[c, floor_y + 24, 0, c + 2, S, S] for c in range(30, S, 32)] + [[0, floor_y + 24, c, S, S, c + 2] for c in range(30, S, 32)]
-    world.fillBoxes(cuts, False)
-    full = world.clone()                                                     # the whole medium: supported part and debris
-    debris = world.keepConnected([[0, floor_y, 0, S, floor_y + 1, S]], 6)
-    labels = debris.labelComponents(6)
+    scene, world, debris, labels, full = fall_scene(vrc, depth, whole=True)       # full: the supported part and the debris
     C_ = labels.count
     res["pieces"], res["supported_voxels"], res["debris_voxels"] = C_, world.solidCount(), debris.solidCount()
     OR = vrc.capi.VRC_COPY_OR
 
-    def timed(fn):
-        out = []
-        for i in range(pairs + 1):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if i:
-                out.append(a.elapsed_time(b))
-        return stat(out, 4)
-
-    def box_words(boxes):
-        return int(sum(((int(b[3]) - 1) // 2 - int(b[0]) // 2 + 1) * ((int(b[4]) - 1) // 2 - int(b[1]) // 2 + 1) * ((((int(b[5]) - 1) // 2 - int(b[2]) // 2) + 3) // 4 + 1)
-                       for b in boxes if all(b[a] < b[a + 3] for a in range(3))))
-
-    def on_device(array):
-        return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).cuda()
-
     records = labels.components()
     offsets, st = labels.fall(world, vrc.capi.VRC_FACE_YN)
-    maps = np.zeros(C_, vrc.capi.AFFINE_DTYPE)
-    maps["m"][:] = [65536, 0, 0, 0, 65536, 0, 0, 0, 65536]
-    maps["t"][:] = -(offsets.astype(np.int64) << 17)
-    boxes = np.concatenate([np.clip(records["lo"].astype(np.int64) + offsets, 0, S), np.clip(records["hi"].astype(np.int64) + offsets, 0, S)], axis=1).astype(np.uint32)
-    c, s = math.cos(math.radians(30)), math.sin(math.radians(30))
-    rx = np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
-    ry = np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
-    rot = np.ascontiguousarray((ry @ rx).T, np.float32).reshape(9)
-    turn_maps, turn_boxes = labels.poses(rot, labels.massProperties()[1])
+    maps, boxes = translate_poses(labels, records, offsets, S)
+    turn_maps, turn_boxes = turn_poses(labels)
     out = torch.zeros(max(C_, 1) * 128, dtype=torch.uint8).cuda()
     for name, mp, bx in (("translate", maps, boxes), ("turn", turn_maps, turn_boxes)):
         d_maps, d_boxes = on_device(mp), on_device(bx)
         placed = world.clone()
         torch.cuda.synchronize()
         res[name + "_box_words"] = box_words(bx)
-        res["place_%s_ms" % name] = timed(lambda: labels.placeAffineDevice(d_maps.data_ptr(), placed, d_boxes.data_ptr(), OR, None, None))
+        # the place call returns its destination: `and None` keeps timed() from closing it
+        res["place_%s_ms" % name], _ = timed(lambda: labels.placeAffineDevice(d_maps.data_ptr(), placed, d_boxes.data_ptr(), OR, None, None) and None, pairs)
         for suffix, against in (("", world), ("_full", full)):
             key = "contacts_%s%s" % (name, suffix)
-            res[key + "_ms"] = timed(lambda: labels.contactsDevice(d_maps.data_ptr(), against, out.data_ptr(), d_boxes.data_ptr(), None, None))
+            res[key + "_ms"], _ = timed(lambda: labels.contactsDevice(d_maps.data_ptr(), against, out.data_ptr(), d_boxes.data_ptr(), None, None), pairs)
             res[key + "_over_place"] = round(res[key + "_ms"]["median"] / res["place_%s_ms" % name]["median"], 2)
             got = out.cpu().numpy().view(vrc.capi.CONTACT_DTYPE)[:C_]
             assert got.tobytes() == labels.contacts(mp, against, bx).tobytes(), "device-memory records differ from the host-memory call's"
@@ -1131,42 +1063,19 @@ def bench_contacts(vrc, depth, pairs):
 def bench_clearance(vrc, depth, pairs):
     """vrc_rigid_clearance over the Euclidean field of the supported part next to vrc_rigid_contacts against the supported part
     with the same maps and boxes -- the same gather, reading at most 7 words where the clearance reads up to 32 values -- on
-    bench_fall's scene, A B A B in one run"""
-    import math
+    fall_scene, A B A B in one run"""
     import torch
     S = 1 << depth
     res = {"size": S, "pairs": pairs}
-    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
-    world = vrc.VoxelVolume.fromScene(scene)
-    floor_y = S // 2 + 1
-    band = [0, floor_y + 24, 0, S, floor_y + 28, S]
-    cuts = [band, [0, floor_y + 44, 0, S, floor_y + 47, S]]
-    cuts += [[c, floor_y + 24, 0, c + 2, S, S] for c in range(30, S, 32)] + [[0, floor_y + 24, c, S, S, c + 2] for c in range(30, S, 32)]
-    world.fillBoxes(cuts, False)
-    debris = world.keepConnected([[0, floor_y, 0, S, floor_y + 1, S]], 6)       # world keeps the supported part
-    labels = debris.labelComponents(6)
+    scene, world, debris, labels, _ = fall_scene(vrc, depth)
     field = world.distanceField(False, False)
     C_ = labels.count
     res["pieces"], res["supported_voxels"], res["debris_voxels"] = C_, world.solidCount(), debris.solidCount()
 
-    def box_words(boxes):
-        return int(sum(((int(b[3]) - 1) // 2 - int(b[0]) // 2 + 1) * ((int(b[4]) - 1) // 2 - int(b[1]) // 2 + 1) * ((((int(b[5]) - 1) // 2 - int(b[2]) // 2) + 3) // 4 + 1)
-                       for b in boxes if all(b[a] < b[a + 3] for a in range(3))))
-
-    def on_device(array):
-        return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).cuda()
-
     records = labels.components()
     offsets, st = labels.fall(world, vrc.capi.VRC_FACE_YN)
-    maps = np.zeros(C_, vrc.capi.AFFINE_DTYPE)
-    maps["m"][:] = [65536, 0, 0, 0, 65536, 0, 0, 0, 65536]
-    maps["t"][:] = -(offsets.astype(np.int64) << 17)
-    boxes = np.concatenate([np.clip(records["lo"].astype(np.int64) + offsets, 0, S), np.clip(records["hi"].astype(np.int64) + offsets, 0, S)], axis=1).astype(np.uint32)
-    c, s = math.cos(math.radians(30)), math.sin(math.radians(30))
-    rx = np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
-    ry = np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
-    rot = np.ascontiguousarray((ry @ rx).T, np.float32).reshape(9)
-    turn_maps, turn_boxes = labels.poses(rot, labels.massProperties()[1])
+    maps, boxes = translate_poses(labels, records, offsets, S)
+    turn_maps, turn_boxes = turn_poses(labels)
     out = torch.zeros(max(C_, 1) * 64, dtype=torch.uint8).cuda()
     contact_out = torch.zeros(max(C_, 1) * 128, dtype=torch.uint8).cuda()
     for name, mp, bx in (("translate", maps, boxes), ("turn", turn_maps, turn_boxes)):
@@ -1193,47 +1102,19 @@ def bench_clearance(vrc, depth, pairs):
 
 
 def bench_pair_contacts(vrc, depth, pairs):
-    """vrc_rigid_box_pairs + vrc_rigid_pair_contacts on bench_fall's scene with bench_contacts' turned poses, next to the
+    """vrc_rigid_box_pairs + vrc_rigid_pair_contacts on fall_scene with turn_poses (bench_contacts' turned poses), next to the
     documented workaround on a sample of the pairs: vrc_rigid_place_affine of b alone into a cleared scratch volume, then
     vrc_rigid_contacts of a alone against it"""
     import ctypes as C
-    import math
     import torch
     S = 1 << depth
     res = {"size": S, "pairs": pairs}
-    scene = vrc.LSVO.fromFastNoiseTerrain(depth)
-    world = vrc.VoxelVolume.fromScene(scene)
-    floor_y = S // 2 + 1
-    band = [0, floor_y + 24, 0, S, floor_y + 28, S]
-    cuts = [band, [0, floor_y + 44, 0, S, floor_y + 47, S]]
-    cuts += [[c, floor_y + 24, 0, c + 2, S, S] for c in range(30, S, 32)] + [[0, floor_y + 24, c, S, S, c + 2] for c in range(30, S, 32)]
-    world.fillBoxes(cuts, False)
-    debris = world.keepConnected([[0, floor_y, 0, S, floor_y + 1, S]], 6)
-    labels = debris.labelComponents(6)
+    scene, world, debris, labels, _ = fall_scene(vrc, depth)
     C_ = labels.count
     res["pieces"], res["debris_voxels"] = C_, debris.solidCount()
     L, DEV, OR = vrc.capi.load(), vrc.capi.VRC_MEM_DEVICE, vrc.capi.VRC_COPY_OR
 
-    def timed(fn):
-        out = []
-        for i in range(pairs + 1):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if i:
-                out.append(a.elapsed_time(b))
-        return stat(out, 4)
-
-    def on_device(array):
-        return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).cuda()
-
-    c, s = math.cos(math.radians(30)), math.sin(math.radians(30))
-    rx = np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
-    ry = np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
-    rot = np.ascontiguousarray((ry @ rx).T, np.float32).reshape(9)
-    maps, boxes = labels.poses(rot, labels.massProperties()[1])
+    maps, boxes = turn_poses(labels)
     d_maps, d_boxes = on_device(maps), on_device(boxes)
     listed = labels.candidatePairs(boxes)
     P = len(listed)
@@ -1248,9 +1129,9 @@ def bench_pair_contacts(vrc, depth, pairs):
         vrc.capi.check(L.vrc_rigid_box_pairs(labels._h, None, vrc.capi.ptr(d_boxes.data_ptr()), depth, 0, P, vrc.capi.ptr(d_pairs.data_ptr()), DEV, None))
 
     # both calls are synchronous and allocate their scratch: the events span that too
-    res["box_pairs_count_and_list_ms"] = timed(broad)
+    res["box_pairs_count_and_list_ms"], _ = timed(broad, pairs)
     assert count.value == P and d_pairs.cpu().numpy().view(np.uint32).reshape(-1, 2)[:P].tobytes() == listed.tobytes()
-    res["pair_contacts_ms"] = timed(lambda: labels.pairContactsDevice(d_maps.data_ptr(), P, d_pairs.data_ptr(), out.data_ptr(), d_boxes.data_ptr(), depth, None, None))
+    res["pair_contacts_ms"], _ = timed(lambda: labels.pairContactsDevice(d_maps.data_ptr(), P, d_pairs.data_ptr(), out.data_ptr(), d_boxes.data_ptr(), depth, None, None), pairs)
     got = out.cpu().numpy().view(vrc.capi.CONTACT_DTYPE)[:P]
     assert got.tobytes() == labels.pairContacts(maps, listed, boxes).tobytes(), "device-memory records differ from the host-memory call's"
     res["pairs_overlapping"], res["pairs_touching"] = int((got["overlap"] > 0).sum()), int((got["touch"] > 0).sum())
@@ -1272,7 +1153,7 @@ def bench_pair_contacts(vrc, depth, pairs):
             scratch.fillBoxes(whole, False)
             labels.placeAffineDevice(d_maps.data_ptr(), scratch, d_boxes.data_ptr(), OR, keeps[0].data_ptr(), None)
             labels.contactsDevice(d_maps.data_ptr(), scratch, one.data_ptr(), d_boxes.data_ptr(), keeps[1].data_ptr(), None)
-        times.append(timed(workaround)["median"])
+        times.append(timed(workaround, pairs)[0]["median"])
         # away from the volume's faces the workaround's record is the pair's; at the faces it also counts the walls
         rec = one.cpu().numpy().view(vrc.capi.CONTACT_DTYPE)[a]
         k = int(np.flatnonzero((listed[:, 0] == a) & (listed[:, 1] == b))[0])
@@ -1289,7 +1170,6 @@ def bench_pair_contacts(vrc, depth, pairs):
 
 
 def bench_stamp(vrc, depth, pairs):
-    import math
     S = 1 << depth
     res = {"size": S, "pairs": pairs}
     scene = vrc.LSVO.fromFastNoiseTerrain(depth)
@@ -1312,11 +1192,7 @@ def bench_stamp(vrc, depth, pairs):
     a, b = ab_device_ms(copy, lambda: stamped.stampAffine(terrain, turn, None, None, REPLACE, None), pairs)
     res["quarter_turn"] = {"copy_region_ms": a, "stamp_ms": b, "stamp_over_copy": round(b["median"] / a["median"], 2), "solid": stamped.solidCount()}
 
-    # a rotation by 30 degrees about x, then about y, in vrc_make_rotation's layout (columns)
-    c, s = math.cos(math.radians(30)), math.sin(math.radians(30))
-    rx = np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
-    ry = np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
-    rot = np.ascontiguousarray((ry @ rx).T, np.float32).reshape(9)
+    rot = turn_30_30()
     placed, lo, hi = vrc.affine_place(rot, 1.0, (S / 2,) * 3, (S / 2,) * 3, depth, depth)
     a, b = ab_device_ms(copy, lambda: stamped.stampAffine(terrain, placed, lo, hi, REPLACE, None), pairs)
     res["turn_30_30"] = {"copy_region_ms": a, "stamp_ms": b, "stamp_over_copy": round(b["median"] / a["median"], 2), "box": [list(lo), list(hi)],
@@ -1352,14 +1228,6 @@ def bench_fracture(vrc, depth, pairs):
     rng = np.random.default_rng(4096)
     cases = {"impact_64_sites_radius_48": (scenes.scatter_sites((x, top, z), 48, 64, 64), 48),
              "whole_volume_4096_sites": (rng.integers(0, S, (4096, 3)).astype(np.int32), None)}
-
-    def event_ms(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        out = fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b), out
 
     def yardstick():
         field = world.distanceField()
@@ -1404,28 +1272,12 @@ def bench_delta(vrc, depth, pairs):
     t_src, t_dst = torch.zeros(occupancy, dtype=torch.uint8).cuda(), torch.zeros(occupancy, dtype=torch.uint8).cuda()
     torch.cuda.synchronize()
 
-    def timed_ab(fa, fb):
-        """A B A B; what a call returns is closed outside its events"""
-        out = ([], [])
-        for i in range(pairs + 1):
-            for k, fn in enumerate((fa, fb)):
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                made = fn()
-                b.record()
-                b.synchronize()
-                if made is not None:
-                    made.close()
-                if i:
-                    out[k].append(a.elapsed_time(b))
-        return stat(out[0], 4), stat(out[1], 4)
-
     def case(before, after):
         delta = before.diff(after)
         st = delta.stats
         one = {"records": delta.count, "record_bytes": delta.bytes(), "record_bytes_over_occupancy": round(delta.bytes() / occupancy, 6),
                "changed_voxels": int(st.voxels), "box": [list(st.lo), list(st.hi)]}
-        one["diff_ms"], one["clone_ms"] = timed_ab(lambda: before.diff(after), before.clone)
+        one["diff_ms"], one["clone_ms"] = timed_ab([lambda: before.diff(after), before.clone], pairs, digits=4)
         one["diff_over_clone"] = round(one["diff_ms"]["median"] / one["clone_ms"]["median"], 3)
 
         def apply_twice():
@@ -1435,7 +1287,7 @@ def bench_delta(vrc, depth, pairs):
         def copy():
             t_dst.copy_(t_src)
 
-        twice, one["copy_ms"] = timed_ab(apply_twice, copy)
+        twice, one["copy_ms"] = timed_ab([apply_twice, copy], pairs, digits=4)
         one["apply_ms"] = {k: round(v / 2, 5) for k, v in twice.items()}
         one["diff_over_copy"] = round(one["diff_ms"]["median"] / one["copy_ms"]["median"], 3)
         check = before.diff(after)
@@ -1449,13 +1301,11 @@ def bench_delta(vrc, depth, pairs):
     res["sphere_dig_r8"] = case(terrain, dug)
     dug.close()
 
-    world = terrain.clone()
-    floor_y = S // 2 + 1
-    cuts = [[0, floor_y + 24, 0, S, floor_y + 28, S], [0, floor_y + 44, 0, S, floor_y + 47, S]]
-    cuts += [[c, floor_y + 24, 0, c + 2, S, S] for c in range(30, S, 32)] + [[0, floor_y + 24, c, S, S, c + 2] for c in range(30, S, 32)]
+    world = terrain.clone()                                  # fall_scene's medium, from the terrain already here
+    cuts, slab = fall_cuts(S)
     world.fillBoxes(cuts, False)
     carved = world.clone()
-    fall = world.dropLoose([[0, floor_y, 0, S, floor_y + 1, S]], vrc.capi.VRC_FACE_YN)
+    fall = world.dropLoose(slab, vrc.capi.VRC_FACE_YN)
     res["drop_loose"] = dict(case(carved, world), moved_pieces=int(fall.moved_pieces), moved_voxels=int(fall.moved_voxels))
     for v in (carved, world):
         v.close()
@@ -1504,20 +1354,7 @@ def bench_pack(vrc, depth, pairs):
             capi.check(L.vrc_volume_download(volume._h, capi.ptr(dense)))
 
         calls = [("size_ms", size_only), ("pack_ms", pack), ("unpack_ms", unpack), ("clone_ms", volume.clone), ("download_ms", download)]
-        times = {k: [] for k, _ in calls}
-        for i in range(pairs + 1):
-            for key, fn in calls:
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                made = fn()
-                b.record()
-                b.synchronize()
-                if made is not None:
-                    made.close()
-                if i:
-                    times[key].append(a.elapsed_time(b))
-        for key, _ in calls:
-            one[key] = stat(times[key], 4)
+        one.update(zip([key for key, _ in calls], timed_ab([fn for _, fn in calls], pairs, digits=4)))
         assert target.pack().tobytes() == volume.pack().tobytes(), "the unpacked volume does not pack to the same stream"
         target.close()
         res[name] = one
@@ -1538,23 +1375,6 @@ def bench_cells(vrc, depth, pairs):
     birth26, survive26 = vrc.count_mask(range(14, 27)), vrc.count_mask(range(13, 27))
     rules = {6: (0, vrc.count_mask(range(1, 7))), 26: (birth26, survive26)}
 
-    def timed_ab(fa, fb):
-        """A B A B, a sample = CALLS calls in a row between two events, divided; what a call returns is closed outside them"""
-        out = ([], [])
-        for i in range(pairs + 1):
-            for k, fn in enumerate((fa, fb)):
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                made = [fn() for _ in range(CALLS)]
-                b.record()
-                b.synchronize()
-                for thing in made:
-                    if thing is not None:
-                        thing.close()
-                if i:
-                    out[k].append(a.elapsed_time(b) / CALLS)
-        return stat(out[0], 5), stat(out[1], 5)
-
     def case(src):
         dst, other = vrc.VoxelVolume(depth), vrc.VoxelVolume(depth)
         one = {"solid_voxels": src.solidCount()}
@@ -1565,15 +1385,15 @@ def bench_cells(vrc, depth, pairs):
         for neighbours, (birth, survive) in rules.items():
             key = "step_%d" % neighbours
             one[key] = {}
-            one[key]["ms"], one[key]["copy_region_ms"] = timed_ab(lambda: src.cellStepDevice(dst, birth, survive, None, neighbours), copy)
+            one[key]["ms"], one[key]["copy_region_ms"] = timed_ab([lambda: src.cellStepDevice(dst, birth, survive, None, neighbours), copy], pairs, CALLS)
             one[key]["step_over_copy"] = round(one[key]["ms"]["median"] / one[key]["copy_region_ms"]["median"], 3)
             key += "_changed"
             one[key] = {}
-            one[key]["ms"], one[key]["clone_ms"] = timed_ab(lambda: src.cellStepDevice(dst, birth, survive, counter.data_ptr(), neighbours), src.clone)
+            one[key]["ms"], one[key]["clone_ms"] = timed_ab([lambda: src.cellStepDevice(dst, birth, survive, counter.data_ptr(), neighbours), src.clone], pairs, CALLS)
             one[key]["changed"] = int(counter.cpu()[0])
             one[key]["step_over_clone"] = round(one[key]["ms"]["median"] / one[key]["clone_ms"]["median"], 3)
         one["fill_random"] = {}
-        one["fill_random"]["ms"], one["fill_random"]["copy_region_ms"] = timed_ab(lambda: dst.fillRandom(7, 0.5, None, vrc.capi.VRC_COPY_REPLACE) and None, copy)
+        one["fill_random"]["ms"], one["fill_random"]["copy_region_ms"] = timed_ab([lambda: dst.fillRandom(7, 0.5, None, vrc.capi.VRC_COPY_REPLACE) and None, copy], pairs, CALLS)
         one["fill_random"]["fill_over_copy"] = round(one["fill_random"]["ms"]["median"] / one["fill_random"]["copy_region_ms"]["median"], 3)
         for v in (dst, other):
             v.close()
@@ -1605,40 +1425,23 @@ def bench_columns(vrc, depth, pairs):
     whole = torch.tensor([0, 0, 0, S, S, S], dtype=torch.int32).cuda()
     torch.cuda.synchronize()
 
-    def timed(fns):
-        """A B (C) A B (C), a sample = CALLS calls in a row between two events, divided; what a call returns is closed outside them"""
-        out = [[] for _ in fns]
-        for i in range(pairs + 1):
-            for k, fn in enumerate(fns):
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                made = [fn() for _ in range(CALLS)]
-                b.record()
-                b.synchronize()
-                for thing in made:
-                    if isinstance(thing, vrc.VoxelVolume):
-                        thing.close()
-                if i:
-                    out[k].append(a.elapsed_time(b) / CALLS)
-        return [stat(o, 5) for o in out]
-
     def case(src):
         dst, other, work = vrc.VoxelVolume(depth), vrc.VoxelVolume(depth), vrc.VoxelVolume(depth)
         one = {"solid_voxels": src.solidCount()}
         for axis, name in enumerate("xyz"):
             e = one["profile_" + name] = {}
-            e["ms"], e["solid_count_ms"], e["clone_ms"] = timed([lambda: src.columnProfileDevice(2 * axis, records.data_ptr()), src.solidCount, src.clone])
+            e["ms"], e["solid_count_ms"], e["clone_ms"] = timed_ab([lambda: src.columnProfileDevice(2 * axis, records.data_ptr()), src.solidCount, src.clone], pairs, CALLS)
             e["profile_over_solid_count"] = round(e["ms"]["median"] / e["solid_count_ms"]["median"], 3)
             e["profile_over_clone"] = round(e["ms"]["median"] / e["clone_ms"]["median"], 3)
         e = one["raise_terrain"] = {}
-        e["ms"], e["fill_boxes_ms"] = timed([lambda: work.fillColumnsDevice(1, None, S // 2 + 1, hi_map.data_ptr(), 0, None, capi.VRC_COPY_REPLACE) and None,
-                                             lambda: other.fillBoxesDevice(1, whole.data_ptr(), True)])
+        e["ms"], e["fill_boxes_ms"] = timed_ab([lambda: work.fillColumnsDevice(1, None, S // 2 + 1, hi_map.data_ptr(), 0, None, capi.VRC_COPY_REPLACE) and None,
+                                                lambda: other.fillBoxesDevice(1, whole.data_ptr(), True)], pairs, CALLS)
         e["fill_over_fill_boxes"] = round(e["ms"]["median"] / e["fill_boxes_ms"]["median"], 3)
         survive = vrc.count_mask(range(1, 7))
         for axis, name in enumerate("xyz"):
             e = one["select_" + name] = {}
-            e["ms"], e["cells_step_6_ms"] = timed([lambda: src.selectColumns(2 * axis, 0, 1, capi.VRC_COLUMNS_SOLID, dst) and None,
-                                                   lambda: src.cellStepDevice(other, 0, survive, None, 6)])
+            e["ms"], e["cells_step_6_ms"] = timed_ab([lambda: src.selectColumns(2 * axis, 0, 1, capi.VRC_COLUMNS_SOLID, dst) and None,
+                                                      lambda: src.cellStepDevice(other, 0, survive, None, 6)], pairs, CALLS)
             e["select_over_cells_step"] = round(e["ms"]["median"] / e["cells_step_6_ms"]["median"], 3)
         one["selected_voxels"] = dst.solidCount()
         for v in (dst, other, work):
@@ -1658,215 +1461,82 @@ def bench_columns(vrc, depth, pairs):
     return res
 
 
-def main():
+class Mode(collections.namedtuple("Mode", "name flag help bench depths writes")):
+    """One mode of the tool.  depths: what runs when --depths is not given; writes: the result also goes to
+    profiles/edit/bench_<name>.json (the line of the others is put there by hand, see profiles/README.md)."""
+
+    @property
+    def label(self):
+        return "edit_" + self.name if self.flag else "edit"
+
+    @property
+    def file(self):
+        return "bench_%s.json" % self.name
+
+
+# in order of precedence: the first mode whose flag is given runs, the last one without any
+MODES = [
+    Mode("columns", "--columns", "time vrc_columns_profile / _fill / _select next to vrc_volume_solid_count, vrc_volume_clone, vrc_volume_fill_boxes and vrc_cells_step", bench_columns, [9], True),
+    Mode("pack", "--pack", "time vrc_pack_volume / vrc_unpack_volume next to vrc_volume_clone and vrc_volume_download", bench_pack, [9], True),
+    Mode("cells", "--cells", "time vrc_cells_step / vrc_cells_fill_random next to vrc_volume_copy_region and vrc_volume_clone", bench_cells, [9], True),
+    Mode("delta", "--delta", "time vrc_delta_diff / vrc_delta_apply next to vrc_volume_clone and a copy of one occupancy", bench_delta, [9], True),
+    Mode("fracture", "--fracture", "time vrc_fracture_label next to vrc_volume_distance_field + vrc_volume_label_components", bench_fracture, [9], True),
+    Mode("clearance", "--clearance", "time vrc_rigid_clearance next to vrc_rigid_contacts with the same maps and boxes", bench_clearance, [9], True),
+    Mode("pair_contacts", "--pair-contacts", "time vrc_rigid_box_pairs and vrc_rigid_pair_contacts next to placement + contacts per pair", bench_pair_contacts, [9], True),
+    Mode("contacts", "--contacts", "time vrc_rigid_contacts next to vrc_rigid_place_affine with the same maps and boxes", bench_contacts, [9], True),
+    Mode("rigid", "--rigid", "time vrc_rigid_moments / vrc_rigid_place_affine next to vrc_labels_select / vrc_fall_place", bench_rigid, [9], True),
+    Mode("fall", "--fall", "time vrc_fall_drops / vrc_fall_place next to vrc_volume_label_components of the same debris", bench_fall, [9], True),
+    Mode("travel", "--travel", "time vrc_travel_field next to vrc_volume_flood from the same seeds", bench_travel, [9], True),
+    Mode("rects", "--rects", "time vrc_rect_count / vrc_extract_rects next to the surface calls", bench_rects, [9], True),
+    Mode("stamp", "--stamp", "time vrc_volume_stamp_affine next to vrc_volume_copy_region", bench_stamp, [9], True),
+    Mode("distance", "--distance", "time vrc_volume_distance_field / vrc_distance_select / dilate", bench_distance, [9], True),
+    Mode("components", "--components", "time vrc_volume_label_components / vrc_labels_*", bench_components, [9], True),
+    Mode("surface", "--surface", "time vrc_volume_surface_count / vrc_volume_extract_surface", bench_surface, [9], False),
+    Mode("voxelize", "--voxelize", "time vrc_volume_xor_mesh", bench_voxelize, [9], False),
+    Mode("flood", "--flood", "time vrc_volume_flood", bench_flood, [9], False),
+    Mode("brushes", "--brushes", "time the brushes, copies and queries", bench_brushes, [9, 10], False),
+    Mode("edit", None, None, bench_depth, [8, 9, 10], False),
+]
+
+
+def make_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--depths", type=int, nargs="+", default=[8, 9, 10])
+    ap.add_argument("--depths", type=int, nargs="+")
     ap.add_argument("--pairs", type=int, default=5)
-    ap.add_argument("--brushes", action="store_true", help="time the brushes, copies and queries (depths 9 and 10 unless --depths is given)")
-    ap.add_argument("--flood", action="store_true", help="time vrc_volume_flood (depth 9 unless --depths is given)")
-    ap.add_argument("--voxelize", action="store_true", help="time vrc_volume_xor_mesh (depth 9 unless --depths is given)")
-    ap.add_argument("--surface", action="store_true", help="time vrc_volume_surface_count / vrc_volume_extract_surface (depth 9 unless --depths is given)")
-    ap.add_argument("--rects", action="store_true", help="time vrc_rect_count / vrc_extract_rects next to the surface calls (depth 9 unless --depths is given)")
-    ap.add_argument("--components", action="store_true", help="time vrc_volume_label_components / vrc_labels_* (depth 9 unless --depths is given)")
-    ap.add_argument("--distance", action="store_true", help="time vrc_volume_distance_field / vrc_distance_select / dilate (depth 9 unless --depths is given)")
-    ap.add_argument("--stamp", action="store_true", help="time vrc_volume_stamp_affine next to vrc_volume_copy_region (depth 9 unless --depths is given)")
-    ap.add_argument("--fall", action="store_true", help="time vrc_fall_drops / vrc_fall_place next to vrc_volume_label_components of the same debris (depth 9 unless --depths is given)")
-    ap.add_argument("--rigid", action="store_true", help="time vrc_rigid_moments / vrc_rigid_place_affine next to vrc_labels_select / vrc_fall_place (depth 9 unless --depths is given)")
-    ap.add_argument("--contacts", action="store_true", help="time vrc_rigid_contacts next to vrc_rigid_place_affine with the same maps and boxes (depth 9 unless --depths is given)")
-    ap.add_argument("--pair-contacts", action="store_true", help="time vrc_rigid_box_pairs and vrc_rigid_pair_contacts next to placement + contacts per pair (depth 9 unless --depths is given)")
-    ap.add_argument("--clearance", action="store_true", help="time vrc_rigid_clearance next to vrc_rigid_contacts with the same maps and boxes (depth 9 unless --depths is given)")
-    ap.add_argument("--travel", action="store_true", help="time vrc_travel_field next to vrc_volume_flood from the same seeds (depth 9 unless --depths is given)")
-    ap.add_argument("--fracture", action="store_true", help="time vrc_fracture_label next to vrc_volume_distance_field + vrc_volume_label_components (depth 9 unless --depths is given)")
-    ap.add_argument("--delta", action="store_true", help="time vrc_delta_diff / vrc_delta_apply next to vrc_volume_clone and a copy of one occupancy (depth 9 unless --depths is given)")
-    ap.add_argument("--cells", action="store_true", help="time vrc_cells_step / vrc_cells_fill_random next to vrc_volume_copy_region and vrc_volume_clone (depth 9 unless --depths is given)")
-    ap.add_argument("--pack", action="store_true", help="time vrc_pack_volume / vrc_unpack_volume next to vrc_volume_clone and vrc_volume_download (depth 9 unless --depths is given)")
-    ap.add_argument("--columns", action="store_true", help="time vrc_columns_profile / _fill / _select next to vrc_volume_solid_count, vrc_volume_clone, vrc_volume_fill_boxes and vrc_cells_step (depth 9 unless --depths is given)")
-    args = ap.parse_args()
-    if args.columns:
-        if args.depths == [8, 9, 10]:
-            args.depths = [9]
-        import __graft_entry__ as g
-        g.build()
-        import torch
-        import cpuvoxelraycaster_amd as vrc
-        if not torch.cuda.is_available():
-            raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-        out = {"bench": "edit_columns", "device": torch.cuda.get_device_name(0), "depths": {}}
-        for d in args.depths:
-            out["depths"][str(d)] = bench_columns(vrc, d, max(1, args.pairs))
-        print(json.dumps(out))
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_columns.json")
-        with open(path, "w") as f:
+    for mode in MODES:
+        if mode.flag:
+            default = ("depth %d" if len(mode.depths) == 1 else "depths %d and %d") % tuple(mode.depths)
+            ap.add_argument(mode.flag, action="store_true", help="%s (%s unless --depths is given)" % (mode.help, default))
+    return ap
+
+
+def select(args):
+    """(the first mode of MODES whose flag is given, else the last; --depths, else that mode's own)"""
+    mode = next(m for m in MODES if not m.flag or getattr(args, m.flag[2:].replace("-", "_")))
+    return mode, list(mode.depths) if args.depths is None else args.depths
+
+
+def run(mode, depths, pairs, vrc, device_name, out_dir):
+    out = {"bench": mode.label, "device": device_name, "depths": {}}
+    for d in depths:
+        out["depths"][str(d)] = mode.bench(vrc, d, max(1, pairs))
+    print(json.dumps(out))
+    if mode.writes:
+        with open(os.path.join(out_dir, mode.file), "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
-        return
-    if args.pack:
-        if args.depths == [8, 9, 10]:
-            args.depths = [9]
-        import __graft_entry__ as g
-        g.build()
-        import torch
-        import cpuvoxelraycaster_amd as vrc
-        if not torch.cuda.is_available():
-            raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-        out = {"bench": "edit_pack", "device": torch.cuda.get_device_name(0), "depths": {}}
-        for d in args.depths:
-            out["depths"][str(d)] = bench_pack(vrc, d, max(1, args.pairs))
-        print(json.dumps(out))
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_pack.json")
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-        return
-    if args.cells:
-        if args.depths == [8, 9, 10]:
-            args.depths = [9]
-        import __graft_entry__ as g
-        g.build()
-        import torch
-        import cpuvoxelraycaster_amd as vrc
-        if not torch.cuda.is_available():
-            raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-        out = {"bench": "edit_cells", "device": torch.cuda.get_device_name(0), "depths": {}}
-        for d in args.depths:
-            out["depths"][str(d)] = bench_cells(vrc, d, max(1, args.pairs))
-        print(json.dumps(out))
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_cells.json")
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-        return
-    if args.delta:
-        if args.depths == [8, 9, 10]:
-            args.depths = [9]
-        import __graft_entry__ as g
-        g.build()
-        import torch
-        import cpuvoxelraycaster_amd as vrc
-        if not torch.cuda.is_available():
-            raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-        out = {"bench": "edit_delta", "device": torch.cuda.get_device_name(0), "depths": {}}
-        for d in args.depths:
-            out["depths"][str(d)] = bench_delta(vrc, d, max(1, args.pairs))
-        print(json.dumps(out))
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_delta.json")
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-        return
-    if args.fracture:
-        if args.depths == [8, 9, 10]:
-            args.depths = [9]
-        import __graft_entry__ as g
-        g.build()
-        import torch
-        import cpuvoxelraycaster_amd as vrc
-        if not torch.cuda.is_available():
-            raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-        out = {"bench": "edit_fracture", "device": torch.cuda.get_device_name(0), "depths": {}}
-        for d in args.depths:
-            out["depths"][str(d)] = bench_fracture(vrc, d, max(1, args.pairs))
-        print(json.dumps(out))
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_fracture.json")
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-        return
-    if args.clearance:
-        if args.depths == [8, 9, 10]:
-            args.depths = [9]
-        import __graft_entry__ as g
-        g.build()
-        import torch
-        import cpuvoxelraycaster_amd as vrc
-        if not torch.cuda.is_available():
-            raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-        out = {"bench": "edit_clearance", "device": torch.cuda.get_device_name(0), "depths": {}}
-        for d in args.depths:
-            out["depths"][str(d)] = bench_clearance(vrc, d, max(1, args.pairs))
-        print(json.dumps(out))
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_clearance.json")
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-        return
-    if args.pair_contacts:
-        if args.depths == [8, 9, 10]:
-            args.depths = [9]
-        import __graft_entry__ as g
-        g.build()
-        import torch
-        import cpuvoxelraycaster_amd as vrc
-        if not torch.cuda.is_available():
-            raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-        out = {"bench": "edit_pair_contacts", "device": torch.cuda.get_device_name(0), "depths": {}}
-        for d in args.depths:
-            out["depths"][str(d)] = bench_pair_contacts(vrc, d, max(1, args.pairs))
-        print(json.dumps(out))
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_pair_contacts.json")
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-        return
-    if args.travel and args.depths == [8, 9, 10]:
-        args.depths = [9]
-    if args.fall and args.depths == [8, 9, 10]:
-        args.depths = [9]
-    if args.rigid and args.depths == [8, 9, 10]:
-        args.depths = [9]
-    if args.contacts and args.depths == [8, 9, 10]:
-        args.depths = [9]
-    if args.stamp and args.depths == [8, 9, 10]:
-        args.depths = [9]
-    if args.rects and args.depths == [8, 9, 10]:
-        args.depths = [9]
-    if args.distance and args.depths == [8, 9, 10]:
-        args.depths = [9]
-    if args.components and args.depths == [8, 9, 10]:
-        args.depths = [9]
-    if args.surface and args.depths == [8, 9, 10]:
-        args.depths = [9]
-    if args.voxelize and args.depths == [8, 9, 10]:
-        args.depths = [9]
-    if args.brushes and args.depths == [8, 9, 10]:
-        args.depths = [9, 10]
-    if args.flood and args.depths == [8, 9, 10]:
-        args.depths = [9]
+    return out
+
+
+def main():
+    args = make_parser().parse_args()
+    mode, depths = select(args)
     import __graft_entry__ as g
     g.build()
     import torch
     import cpuvoxelraycaster_amd as vrc
     if not torch.cuda.is_available():
         raise SystemExit("bench_edit.py needs a GPU (the library has no CPU fallback)")
-    out = {"bench": "edit_contacts" if args.contacts else "edit_rigid" if args.rigid else "edit_fall" if args.fall else "edit_travel" if args.travel else "edit_rects" if args.rects else "edit_stamp" if args.stamp else "edit_distance" if args.distance else "edit_components" if args.components else "edit_surface" if args.surface else "edit_voxelize" if args.voxelize else "edit_flood" if args.flood else "edit_brushes" if args.brushes else "edit", "device": torch.cuda.get_device_name(0), "depths": {}}
-    for d in args.depths:
-        out["depths"][str(d)] = (bench_contacts if args.contacts else bench_rigid if args.rigid else bench_fall if args.fall else bench_travel if args.travel else bench_rects if args.rects else bench_stamp if args.stamp else bench_distance if args.distance else bench_components if args.components else bench_surface if args.surface else bench_voxelize if args.voxelize else bench_flood if args.flood else bench_brushes if args.brushes else bench_depth)(vrc, d, max(1, args.pairs))
-    print(json.dumps(out))
-    if args.contacts:
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_contacts.json")
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-    elif args.rigid:
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_rigid.json")
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-    elif args.fall:
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_fall.json")
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-    elif args.travel:
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_travel.json")
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-    elif args.rects:
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_rects.json")
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-    elif args.stamp:
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_stamp.json")
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-    if args.distance:
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_distance.json")
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
-    if args.components:
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edit", "bench_components.json")
-        with open(path, "w") as f:
-            f.write(json.dumps(out, indent=1) + "\n")
+    run(mode, depths, args.pairs, vrc, torch.cuda.get_device_name(0), os.path.join(ROOT, "profiles", "edit"))
 
 
 if __name__ == "__main__":
