@@ -20,6 +20,7 @@ VRC_COLUMNS_SOLID, VRC_COLUMNS_EMPTY = 1, 2
 VRC_COLUMN_NONE = 0xffffffff
 VRC_NO_COMPONENT = 0xffffffff
 VRC_DISTANCE_NONE = 0xffffffff
+VRC_STROKE_LIMIT = 8192
 VRC_MESH_FRAC_BITS = 6
 VRC_AFFINE_FRAC_BITS = 16
 VRC_FACE_XN, VRC_FACE_XP, VRC_FACE_YN, VRC_FACE_YP, VRC_FACE_ZN, VRC_FACE_ZP = range(6)
@@ -212,6 +213,8 @@ SYMBOLS = {
     "vrc_volume_solid_count": (_int, [_vp, C.POINTER(_u64)]),
     "vrc_volume_fill_spheres": (_int, [_vp, _u64, _vp, _int, _int, _vp]),
     "vrc_volume_fill_spheres_at_hits": (_int, [_vp, _u64, _vp, _i32, _int, _int, _vp]),
+    "vrc_stroke_fill_capsules": (_int, [_vp, _u64, _vp, _int, _int, _vp]),
+    "vrc_stroke_fill_at_hits": (_int, [_vp, _u64, _vp, _i32, _u32, _int, _int, _vp]),
     "vrc_volume_copy_region": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "vrc_volume_stamp_affine": (_int, [_vp, _vp, C.POINTER(Affine), _vp, _vp, _int, _vp]),
     "vrc_affine_place": (_int, [_vp, _f32, _vp, _vp, _u32, _u32, C.POINTER(Affine), _vp, _vp]),

@@ -12,7 +12,7 @@
 // Here: the volume's life cycle, the edits and queries on the occupancy with their ordering and scratch blocks, and
 // commit / download.  Boxes, spheres, spheres at the hits of a ray batch, region copies and the two queries have their
 // kernels here, over the box-of-words layout of vrc_box_words.h.  The other features keep theirs in files of their own:
-// vrc_flood.hip, vrc_voxelize.hip, vrc_surface.hip, vrc_rects.hip, vrc_stamp.hip, vrc_pack.hip.  The snapshots taken from a volume (labels, distance
+// vrc_flood.hip, vrc_voxelize.hip, vrc_surface.hip, vrc_rects.hip, vrc_stamp.hip, vrc_pack.hip, vrc_stroke.hip.  The snapshots taken from a volume (labels, distance
 // fields) are in vrc_snapshots.hip; what the entry points of both files share -- the checks, the ordering rule and staged_call,
 // the one frame of every call that takes lists -- is in vrc_volume_state.h, and the ordering of every entry point is the
 // table in DESIGN.md.
@@ -29,6 +29,7 @@
 #include "vrc_group.h"
 #include "vrc_pack.h"
 #include "vrc_stamp.h"
+#include "vrc_stroke.h"
 #include "vrc_rects.h"
 #include "vrc_surface.h"
 #include "vrc_volume_state.h"
@@ -491,6 +492,54 @@ extern "C" int vrc_volume_fill_spheres_at_hits(vrc_volume* v, uint64_t n, const 
     }
     hipLaunchKernelGGL(k_hits_to_centres, grid_for(n), dim3(256), 0, st, n, d_hits, v->depth, radius, solid ? 1u : 0u, d_centres);
     launch_fill_spheres(v, n, d_centres, radius, solid, st);
+    if ((e = hipGetLastError()) == hipSuccess) e = finish(v, mem, st, true);
+    return done(e, what);
+}
+
+// ---- capsules (kernels: vrc_stroke.hip) ----------------------------------------------------------------------------
+
+extern "C" int vrc_stroke_fill_capsules(vrc_volume* v, uint64_t n, const int32_t* items, int solid, int mem, void* stream)
+{
+    const char* what = "vrc_stroke_fill_capsules";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (n == 0) return VRC_OK;
+    if (!items) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (const int rc = check_count(what, n, GROUP_ITEMS, "capsules")) return rc;
+    const Call call = edit_call(v, mem, stream);
+    const StagePart parts[] = {{items, (size_t)n * 32u, STAGE_IN}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        vrc::stroke_capsules_run(v->d_bricks, v->depth, n, (const int32_t*)d[0], split_for(v, n), 256u, solid, call.st);
+        return hipSuccess;
+    });
+}
+
+extern "C" int vrc_stroke_fill_at_hits(vrc_volume* v, uint64_t n, const vrc_hit* hits, int32_t radius, uint32_t max_gap, int solid, int mem,
+                                       void* stream)
+{
+    const char* what = "vrc_stroke_fill_at_hits";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (radius < 0 || radius > VRC_STROKE_LIMIT) return vrc::fail(VRC_ERR_INVALID, "%s: radius %d not in [0, 2^13]", what, radius);
+    if (n == 0) return VRC_OK;
+    if (!hits) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (const int rc = check_count(what, n, GROUP_ITEMS, "hits")) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(v->device);
+    // Not a staged_call, as vrc_volume_fill_spheres_at_hits is none: the centres go through the staging block in both memory
+    // kinds.  The links are read off neighbouring centres by the kernel, so the block holds no list of capsules.
+    if (e == hipSuccess) e = order_behind_edits(v, st);
+    if (e == hipSuccess) e = reserve(v->d_stage, v->stage_cap, (size_t)n * (mem == VRC_MEM_HOST ? 64u : 16u));
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    int32_t* d_centres = (int32_t*)v->d_stage;
+    const vrc_hit* d_hits = hits;
+    if (mem == VRC_MEM_HOST) {
+        d_hits = (const vrc_hit*)((uint8_t*)v->d_stage + (size_t)n * 16u);
+        if ((e = hipMemcpyAsync((void*)d_hits, hits, (size_t)n * sizeof(vrc_hit), hipMemcpyHostToDevice, st)) != hipSuccess) return vrc::fail_hip(e, what);
+    }
+    hipLaunchKernelGGL(k_hits_to_centres, grid_for(n), dim3(256), 0, st, n, d_hits, v->depth, radius, solid ? 1u : 0u, d_centres);
+    // many thin strokes between neighbouring hits: a wave each, as launch_fill_spheres
+    vrc::stroke_links_run(v->d_bricks, v->depth, n, d_centres, radius, max_gap, split_for(v, n), n >= 4096u && radius <= 4 ? 64u : 256u, solid, st);
     if ((e = hipGetLastError()) == hipSuccess) e = finish(v, mem, st, true);
     return done(e, what);
 }

@@ -523,6 +523,53 @@ public:
         flush();
         check(vrc_volume_fill_spheres_at_hits(v_, n, hits_dev, radius, solid ? 1 : 0, VRC_MEM_DEVICE, stream), "vrc_volume_fill_spheres_at_hits");
     }
+    // Capsules (include/vrc.h: vrc_stroke_*): the voxels within `radius` of the segment a-b by the exact integer rule;
+    // reserved stays 0
+    struct Capsule { int32_t ax, ay, az, bx, by, bz, radius, reserved; };
+    void fillCapsules(const std::vector<Capsule>& items, bool solid)
+    {
+        flush();
+        check(vrc_stroke_fill_capsules(v_, items.size(), items.empty() ? nullptr : &items[0].ax, solid ? 1 : 0, VRC_MEM_HOST, nullptr),
+              "vrc_stroke_fill_capsules");
+    }
+    void fillCapsulesDevice(uint64_t n, const int32_t* items_dev, bool solid, void* stream = nullptr)
+    {
+        flush();
+        check(vrc_stroke_fill_capsules(v_, n, items_dev, solid ? 1 : 0, VRC_MEM_DEVICE, stream), "vrc_stroke_fill_capsules");
+    }
+    void fillLine(const int32_t a[3], const int32_t b[3], int32_t radius, bool solid)
+    {
+        const Capsule c = {a[0], a[1], a[2], b[0], b[1], b[2], radius, 0};
+        fillCapsules(std::vector<Capsule>(1, c), solid);
+    }
+    // points: x y z per point; one capsule per pair of successive points (and from the last back to the first when closed) in
+    // one call; a single point is its ball
+    void fillPolyline(const std::vector<int32_t>& points, int32_t radius, bool solid, bool closed = false)
+    {
+        const size_t n = points.size() / 3;
+        if (n == 0) return;
+        const size_t links = n == 1 ? 1 : (closed ? n : n - 1);
+        std::vector<Capsule> items(links);
+        for (size_t i = 0; i < links; ++i) {
+            const int32_t* a = &points[3 * i];
+            const int32_t* b = &points[3 * ((i + 1) % n)];
+            const Capsule c = {a[0], a[1], a[2], b[0], b[1], b[2], radius, 0};
+            items[i] = c;
+        }
+        fillCapsules(items, solid);
+    }
+    // the gapless stroke through the records: the centres of fillSpheresAtHits, each joined to the next by a capsule; a record
+    // without a centre breaks the stroke, and so does a step of more than max_gap voxels (0: no limit)
+    void strokeAtHits(const std::vector<vrc_hit>& hits, int32_t radius, bool solid, uint32_t max_gap = 0)
+    {
+        flush();
+        check(vrc_stroke_fill_at_hits(v_, hits.size(), hits.data(), radius, max_gap, solid ? 1 : 0, VRC_MEM_HOST, nullptr), "vrc_stroke_fill_at_hits");
+    }
+    void strokeAtHitsDevice(uint64_t n, const vrc_hit* hits_dev, int32_t radius, bool solid, uint32_t max_gap = 0, void* stream = nullptr)
+    {
+        flush();
+        check(vrc_stroke_fill_at_hits(v_, n, hits_dev, radius, max_gap, solid ? 1 : 0, VRC_MEM_DEVICE, stream), "vrc_stroke_fill_at_hits");
+    }
     // voxels src_lo + d of `src` -> dst_lo + d of this volume for 0 <= d < size, clipped to both; op = VRC_COPY_*
     void copyRegion(HipVoxelVolume& src, const uint32_t src_lo[3], const uint32_t size[3], const int32_t dst_lo[3],
                     int op = VRC_COPY_REPLACE, void* stream = nullptr)

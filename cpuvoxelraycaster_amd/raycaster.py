@@ -341,6 +341,48 @@ class VoxelVolume:
         synchronisation lies between the cast and the edit"""
         check(capi.load().vrc_volume_fill_spheres_at_hits(self._h, n, ptr(hits_ptr), int(radius), int(bool(solid)), capi.VRC_MEM_DEVICE, ptr(stream)))
 
+    def fillCapsules(self, items, solid=True):
+        """items: (n, 8) int32 = a x y z, b x y z, radius, 0 (signed, may lie outside): the voxels within `radius` of the
+        segment a-b, by the exact integer rule of include/vrc.h (vrc_stroke_fill_capsules), are set or cleared.  Synchronous."""
+        items = np.ascontiguousarray(items, np.int32).reshape(-1, 8)
+        check(capi.load().vrc_stroke_fill_capsules(self._h, items.shape[0], ptr(items), int(bool(solid)), capi.VRC_MEM_HOST, None))
+
+    def fillCapsulesDevice(self, n, items_ptr, solid=True, stream=None):
+        check(capi.load().vrc_stroke_fill_capsules(self._h, n, ptr(items_ptr), int(bool(solid)), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def strokeAtHits(self, hits, radius, solid=True, max_gap=0):
+        """The gapless stroke through castRays records: the centres of fillSpheresAtHits, each joined to the next by a capsule
+        of `radius`; a record without a centre breaks the stroke, and so does a step of more than max_gap voxels (0: no
+        limit).  Synchronous."""
+        hits = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+        check(capi.load().vrc_stroke_fill_at_hits(self._h, hits.shape[0], ptr(hits), int(radius), int(max_gap), int(bool(solid)),
+                                                  capi.VRC_MEM_HOST, None))
+
+    def strokeAtHitsDevice(self, n, hits_ptr, radius, solid=True, max_gap=0, stream=None):
+        """the same over the records castRaysDevice left in device memory, on the same stream with no host copy"""
+        check(capi.load().vrc_stroke_fill_at_hits(self._h, n, ptr(hits_ptr), int(radius), int(max_gap), int(bool(solid)),
+                                                  capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def fillLine(self, a, b, r=0, solid=True):
+        """one capsule from voxel a to voxel b; r = 0 is the lattice points on the segment"""
+        self.fillCapsules([tuple(a) + tuple(b) + (r, 0)], solid)
+
+    def fillPolyline(self, points, r=0, solid=True, closed=False):
+        """one capsule per pair of successive points (and from the last back to the first when closed), in one call; a single
+        point is its ball"""
+        pts = np.asarray(points, np.int64).reshape(-1, 3)
+        if len(pts) == 0:
+            return
+        if len(pts) == 1:
+            first = nxt = pts
+        elif closed:
+            first, nxt = pts, np.roll(pts, -1, axis=0)
+        else:
+            first, nxt = pts[:-1], pts[1:]
+        items = np.zeros((len(first), 8), np.int32)
+        items[:, 0:3], items[:, 3:6], items[:, 6] = first, nxt, r
+        self.fillCapsules(items, solid)
+
     def copyRegion(self, src, src_lo, size, dst_lo, op=capi.VRC_COPY_REPLACE, stream=None):
         """Voxels src_lo + d of the volume `src` (any depth, same device) go to dst_lo + d of this one for 0 <= d < size,
         clipped to both; op = capi.VRC_COPY_REPLACE / _OR / _ANDNOT.  Asynchronous on `stream`."""

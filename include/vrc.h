@@ -219,6 +219,38 @@ int vrc_volume_fill_spheres(vrc_volume *v, uint64_t n, const int32_t *centre_rad
  * by this call on the same stream edits the volume with no host copy of a hit.  The centres pass through the volume's
  * grow-only staging block (16 bytes per record). */
 int vrc_volume_fill_spheres_at_hits(vrc_volume *v, uint64_t n, const vrc_hit *hits, int32_t radius, int solid, int mem, void *stream);
+
+/* Capsules: the ball swept along a segment -- a line, a beam, a pipe, and the gapless stroke through the hits of a ray batch.
+ * The largest coordinate and radius of a capsule.  With a voxel p inside a volume of at most 1024^3, |a|, |b| <= 2^13 and
+ * r <= 2^13, every component of q = p - a is below 2^13 + 2^10 and of d = b - a at most 2^14, so q.q < 3 (2^13 + 2^10)^2
+ * < 2^28, L2 = d.d <= 3 * 2^28 < 2^30, |t| = |q.d| <= sqrt(q.q L2) < 2^29, and each product of the rule below -- (q.q) L2,
+ * t^2, r^2 L2 -- stays below 2^58: the rule is exact in 64-bit integers. */
+#define VRC_STROKE_LIMIT 8192
+/* n capsules (n x 8 int32: ax ay az bx by bz r reserved), in setCell coordinates, signed, possibly outside the volume (the
+ * capsule is clipped).  With d = b - a, L2 = d.d, q = p - a and t = q.d, voxel p = (x, y, z) is set or cleared iff, in
+ * 64-bit integers,
+ *   L2 == 0 or t <= 0:   q.q <= r^2                  (the ball at a)
+ *   t >= L2:             |p - b|^2 <= r^2            (the ball at b)
+ *   otherwise:           (q.q) L2 - t^2 <= r^2 L2    (within r of the line, between the ends)
+ * The set is the same with a and b swapped, and convex.  a == b is the sphere of vrc_volume_fill_spheres; r == 0 is the
+ * lattice points on the segment; r < 0 is empty.  An item with a coordinate beyond +-VRC_STROKE_LIMIT, with
+ * r > VRC_STROKE_LIMIT or with reserved != 0 is dropped.  `mem`, `stream`, n == 0, the one-value-per-call rule and the
+ * ordering are those of vrc_volume_fill_spheres.  Cost follows the capsule, not its bounding box: it is cut into pieces of
+ * 16 voxels along the axis in which it is longest and only the box around each piece is visited (a radius-3 diagonal of
+ * 512^3 visits 1/243 of the words of its bounding box).  A capsule is one workgroup column, as a sphere is. */
+int vrc_stroke_fill_capsules(vrc_volume *v, uint64_t n, const int32_t *items, int solid, int mem, void *stream);
+/* The stroke through the records of a ray batch: the centres c_i exactly as vrc_volume_fill_spheres_at_hits computes them
+ * (dig at `voxel`, build at `neighbour`; a record vrc_hit_to_voxel refuses, and a build without a neighbour, is no centre).
+ * Item i is the capsule (c_i, c_i+1, radius) where records i and i + 1 both give a centre and max_gap == 0 or
+ * |c_i+1 - c_i|^2 <= max_gap^2; the ball at c_i where record i gives a centre but that link does not hold; nothing
+ * otherwise.  The result is the union of the balls at all centres and of all links: successive hits further apart than the
+ * radius leave one tunnel, not a string of cavities.  A miss, an LOD cut-off or a build without a neighbour breaks the
+ * stroke there, and so does a step longer than max_gap voxels (the crosshair went from a near hill to a far one).  `radius`
+ * 0 .. 2^13.  Staging and ordering are those of vrc_volume_fill_spheres_at_hits (16 bytes per record in the volume's
+ * staging block; no list of capsules is written): with VRC_MEM_DEVICE, vrc_cast_rays(..., VRC_MEM_DEVICE, stream) followed
+ * by this call on the same stream makes no host copy. */
+int vrc_stroke_fill_at_hits(vrc_volume *v, uint64_t n, const vrc_hit *hits, int32_t radius, uint32_t max_gap, int solid, int mem,
+                            void *stream);
 /* Solid voxelisation of a triangle mesh by crossing parity along z: bringing a model in without leaving the device.
  * n triangles (n x 9 int32: ax ay az bx by bz cx cy cz) in setCell coordinates with VRC_MESH_FRAC_BITS fractional bits, 64
  * units per voxel: the centre of voxel (x, y, z) is (64x + 32, 64y + 32, 64z + 32).  `mem`, `stream` and n == 0 as for
