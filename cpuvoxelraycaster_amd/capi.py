@@ -22,6 +22,7 @@ VRC_NO_COMPONENT = 0xffffffff
 VRC_DISTANCE_NONE = 0xffffffff
 VRC_STROKE_LIMIT = 8192
 VRC_MESH_FRAC_BITS = 6
+VRC_RASTER_TOUCHED, VRC_RASTER_THIN = 0, 1
 VRC_AFFINE_FRAC_BITS = 16
 VRC_FACE_XN, VRC_FACE_XP, VRC_FACE_YN, VRC_FACE_YP, VRC_FACE_ZN, VRC_FACE_ZP = range(6)
 VRC_SURFACE_FACES, VRC_SURFACE_TRIANGLES = 0, 1
@@ -272,6 +273,7 @@ SYMBOLS = {
     "vrc_columns_fill": (_int, [_vp, _int, _vp, _vp, _i32, _vp, _i32, _int, _int, _vp]),
     "vrc_columns_select": (_int, [_vp, _vp, _int, _u32, _u32, _int, _int, _vp]),
     "vrc_volume_xor_mesh": (_int, [_vp, _u64, _vp, _int, _vp]),
+    "vrc_raster_mesh": (_int, [_vp, _u64, _vp, _int, _int, _int, _vp]),
     "vrc_volume_surface_count": (_int, [_vp, _int, _vp]),
     "vrc_volume_extract_surface": (_int, [_vp, _int, _int, _u64, _u64, _vp, _vp, _int, _vp]),
     "vrc_rect_count": (_int, [_vp, _int, _vp]),

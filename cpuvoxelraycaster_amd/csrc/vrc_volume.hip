@@ -12,7 +12,7 @@
 // Here: the volume's life cycle, the edits and queries on the occupancy with their ordering and scratch blocks, and
 // commit / download.  Boxes, spheres, spheres at the hits of a ray batch, region copies and the two queries have their
 // kernels here, over the box-of-words layout of vrc_box_words.h.  The other features keep theirs in files of their own:
-// vrc_flood.hip, vrc_voxelize.hip, vrc_surface.hip, vrc_rects.hip, vrc_stamp.hip, vrc_pack.hip, vrc_stroke.hip.  The snapshots taken from a volume (labels, distance
+// vrc_flood.hip, vrc_voxelize.hip, vrc_surface.hip, vrc_rects.hip, vrc_stamp.hip, vrc_pack.hip, vrc_stroke.hip, vrc_raster.hip.  The snapshots taken from a volume (labels, distance
 // fields) are in vrc_snapshots.hip; what the entry points of both files share -- the checks, the ordering rule and staged_call,
 // the one frame of every call that takes lists -- is in vrc_volume_state.h, and the ordering of every entry point is the
 // table in DESIGN.md.
@@ -28,6 +28,7 @@
 #include "vrc_flood.h"
 #include "vrc_group.h"
 #include "vrc_pack.h"
+#include "vrc_raster.h"
 #include "vrc_stamp.h"
 #include "vrc_stroke.h"
 #include "vrc_rects.h"
@@ -542,6 +543,25 @@ extern "C" int vrc_stroke_fill_at_hits(vrc_volume* v, uint64_t n, const vrc_hit*
     vrc::stroke_links_run(v->d_bricks, v->depth, n, d_centres, radius, max_gap, split_for(v, n), n >= 4096u && radius <= 4 ? 64u : 256u, solid, st);
     if ((e = hipGetLastError()) == hipSuccess) e = finish(v, mem, st, true);
     return done(e, what);
+}
+
+// ---- surface voxelisation (kernels: vrc_raster.hip) ------------------------------------------------------------------
+
+extern "C" int vrc_raster_mesh(vrc_volume* v, uint64_t n, const int32_t* tris, int mode, int solid, int mem, void* stream)
+{
+    const char* what = "vrc_raster_mesh";
+    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (mode != VRC_RASTER_TOUCHED && mode != VRC_RASTER_THIN) return vrc::fail(VRC_ERR_INVALID, "%s: unknown mode %d", what, mode);
+    if (n == 0) return VRC_OK;
+    if (!tris) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (const int rc = check_count(what, n, GROUP_ITEMS, "triangles")) return rc;
+    const Call call = edit_call(v, mem, stream);
+    const StagePart parts[] = {{tris, (size_t)n * 36u, STAGE_IN}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        vrc::raster_run(v->d_bricks, v->depth, n, (const int32_t*)d[0], mode, solid, call.st);
+        return hipSuccess;
+    });
 }
 
 extern "C" int vrc_volume_xor_mesh(vrc_volume* v, uint64_t n, const int32_t* tris, int mem, void* stream)

@@ -915,6 +915,26 @@ public:
         const int64_t zero[3] = {0, 0, 0};
         xorMesh(meshSoup(quantiseMesh(verts, scale, ox, oy, oz), faces, zero));
     }
+    // Surface voxelisation (include/vrc.h: vrc_raster_mesh): n x 9 int32 triangles in xorMesh's fixed point.  mode
+    // VRC_RASTER_TOUCHED selects every voxel whose closed cube meets a triangle, VRC_RASTER_THIN the voxel that holds each
+    // crossing of a voxel-centre line; the selected voxels are all set or all cleared.  Synchronous.
+    void rasterMesh(const std::vector<int32_t>& tris_fixed, int mode = VRC_RASTER_TOUCHED, bool solid = true)
+    {
+        flush();
+        check(vrc_raster_mesh(v_, tris_fixed.size() / 9, tris_fixed.data(), mode, solid ? 1 : 0, VRC_MEM_HOST, nullptr), "vrc_raster_mesh");
+    }
+    void rasterMeshDevice(uint64_t n, const int32_t* tris_dev, int mode = VRC_RASTER_TOUCHED, bool solid = true, void* stream = nullptr)
+    {
+        flush();
+        check(vrc_raster_mesh(v_, n, tris_dev, mode, solid ? 1 : 0, VRC_MEM_DEVICE, stream), "vrc_raster_mesh");
+    }
+    // Sets (or clears) the voxels the indexed mesh touches, or with thin its thin shell; the mesh need not be closed
+    void shellMesh(const std::vector<double>& verts, const std::vector<uint32_t>& faces, bool thin = false, bool solid = true, double scale = 1.0,
+                   double ox = 0.0, double oy = 0.0, double oz = 0.0)
+    {
+        const int64_t zero[3] = {0, 0, 0};
+        rasterMesh(meshSoup(quantiseMesh(verts, scale, ox, oy, oz), faces, zero), thin ? VRC_RASTER_THIN : VRC_RASTER_TOUCHED, solid);
+    }
     // What an editor does with a model: voxelises it into a clipboard volume of the smallest depth that holds its bounding
     // box and copies that box into this volume with op (VRC_COPY_OR pastes, _ANDNOT carves, _REPLACE overwrites the box)
     void stampMesh(const std::vector<double>& verts, const std::vector<uint32_t>& faces, int op = VRC_COPY_OR, double scale = 1.0,

@@ -882,6 +882,48 @@ class VoxelVolume:
         tris = np.ascontiguousarray(tris_fixed, np.int32).reshape(-1, 9)
         check(capi.load().vrc_volume_xor_mesh(self._h, tris.shape[0], ptr(tris), capi.VRC_MEM_HOST, None))
 
+    def rasterMesh(self, tris_fixed, mode=capi.VRC_RASTER_TOUCHED, solid=True, device=False, stream=None):
+        """Surface voxelisation (include/vrc.h: vrc_raster_mesh): (n, 9) int32 triangles in xorMesh's fixed point.
+        mode capi.VRC_RASTER_TOUCHED selects every voxel whose closed cube meets a triangle, capi.VRC_RASTER_THIN the voxel
+        that holds each crossing of a voxel-centre line; the selected voxels are all set or all cleared.  Synchronous; with
+        device=True tris_fixed is (n, device pointer to n x 9 int32) and the call is asynchronous on `stream`."""
+        if device:
+            n, tris_ptr = tris_fixed
+            check(capi.load().vrc_raster_mesh(self._h, int(n), ptr(tris_ptr), int(mode), int(bool(solid)), capi.VRC_MEM_DEVICE, ptr(stream)))
+            return
+        tris = np.ascontiguousarray(tris_fixed, np.int32).reshape(-1, 9)
+        check(capi.load().vrc_raster_mesh(self._h, tris.shape[0], ptr(tris), int(mode), int(bool(solid)), capi.VRC_MEM_HOST, None))
+
+    def shellMesh(self, verts, faces, thin=False, solid=True, scale=1.0, offset=(0.0, 0.0, 0.0)):
+        """Sets (or clears) the voxels the indexed mesh touches (verts (n, 3) float in voxels, faces (m, 3) indices), or with
+        thin=True its thin shell; the mesh need not be closed."""
+        fixed = self.quantiseMesh(verts, scale, offset)
+        self.rasterMesh(fixed[np.asarray(faces, np.int64).reshape(-1, 3)].reshape(-1, 9),
+                        capi.VRC_RASTER_THIN if thin else capi.VRC_RASTER_TOUCHED, solid)
+
+    def solidFromShell(self, verts, faces, scale=1.0, offset=(0.0, 0.0, 0.0)):
+        """The robust solid voxelisation: ORs into this volume the thin shell of the mesh plus every voxel that a
+        face-connected flood of the empty medium, started on the volume's six faces, does not reach around that shell.  A
+        doubled triangle or a self-intersection changes nothing, where xorMesh inverts columns; a mesh with a hole lets the
+        flood in and leaves its shell alone.  Composition only: rasterMesh, fillBoxes, flood, copyRegion."""
+        S = 1 << self.depth
+        whole = ((0, 0, 0), (S, S, S), (0, 0, 0))
+        shell = VoxelVolume(self.depth, self.device)
+        outside = VoxelVolume(self.depth, self.device)
+        try:
+            shell.shellMesh(verts, faces, True, True, scale, offset)
+            outside.fillBoxes([(0, 0, 0, S, S, 1), (0, 0, S - 1, S, S, S), (0, 0, 0, S, 1, S), (0, S - 1, 0, S, S, S),
+                               (0, 0, 0, 1, S, S), (S - 1, 0, 0, S, S, S)])
+            outside.copyRegion(shell, *whole, op=capi.VRC_COPY_ANDNOT)      # seeds: the empty voxels of the six faces
+            outside.flood(shell, 6, through_empty=True)
+            # unreached plus shell = everything the flood did not reach: the complement of `outside`
+            shell.fillBoxes([(0, 0, 0, S, S, S)])
+            shell.copyRegion(outside, *whole, op=capi.VRC_COPY_ANDNOT)
+            self.copyRegion(shell, *whole, op=capi.VRC_COPY_OR)
+        finally:
+            shell.close()           # vrc_volume_destroy waits for the copies
+            outside.close()
+
     @staticmethod
     def quantiseMesh(verts, scale=1.0, offset=(0.0, 0.0, 0.0)):
         """(n, 3) float vertices -> int32 fixed point, rint((v * scale + offset) * 64) in float64.  Each VERTEX once: a

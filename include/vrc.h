@@ -278,6 +278,53 @@ int vrc_stroke_fill_at_hits(vrc_volume *v, uint64_t n, const vrc_hit *hits, int3
  * at 512^3, 128 MiB at 1024^3), allocated by the first call and never grown or shrunk. */
 #define VRC_MESH_FRAC_BITS 6
 int vrc_volume_xor_mesh(vrc_volume *v, uint64_t n_tris, const int32_t *tris, int mem, void *stream);
+/* Surface voxelisation of a triangle mesh (the surface half of Schwarz & Seidel 2010): the voxels a mesh TOUCHES, for a mesh
+ * that has no inside -- a sail, a terrain sheet, a wall quad, a collision proxy, a model's skin -- or whose parity is broken (a
+ * dropped or doubled triangle, self-intersection).  `tris` in vrc_volume_xor_mesh's format and units: n x 9 int32, 64 units per
+ * voxel; voxel p occupies the closed cube [64p, 64p + 64]^3 and its centre is 64p + 32.  A triangle with a coordinate beyond
+ * +-2^17 is dropped, as there.  `solid`, `mem`, `stream`, n == 0, the count limit and the ordering are those of
+ * vrc_volume_fill_spheres.  One value per call -- all selected voxels are set, or all are cleared -- so the result does not
+ * depend on scheduling, on the triangles' order or on duplicates.  Everything is clipped to the volume.  The call needs no scratch
+ * block (vrc_volume_edit_scratch_bytes is unchanged by it).  All quantities are 64-bit integers; with |coordinate| <= 2^17 each
+ * stays below 2^57.  Write A, B, C for the vertices and n = (B - A) x (C - A).
+ *
+ * VRC_RASTER_TOUCHED: voxel p is selected iff its closed cube and the closed triangle share a point.  Both sets are convex, so
+ * that is the separating-axis test over 13 axes with non-strict inequalities: with o = 64p, for an axis L the cube's interval is
+ * L.o + [64 sum_i min(L_i, 0), 64 sum_i max(L_i, 0)] and the triangle's is [min, max] of L.A, L.B, L.C, and p is selected iff the
+ * two overlap (touching counts) for every L among the three unit axes, n, and the nine axes e_a x (Q - P) for the edges P -> Q of
+ * A -> B, B -> C, C -> A and the unit axes e_a.  A zero axis separates nothing.  Without special cases: a triangle with n = 0 is
+ * a segment or a point and selects exactly the voxels it touches (a supercover line); a triangle that lies in a voxel-boundary
+ * plane selects the voxels on both sides of it.  The set is the same for any permutation of the vertices.
+ *
+ * VRC_RASTER_THIN: the union over the three axes a and all triangles of the following.  With (u, v) = ((a + 1) % 3, (a + 2) % 3),
+ * a triangle with n_a == 0 contributes nothing on axis a; otherwise s = sign(n_a), and
+ *   Cover: the triangle covers voxel column (p_u, p_v) iff its projection along a covers the centre (64 p_u + 32, 64 p_v + 32),
+ *   by exactly vrc_volume_xor_mesh's Cover rule with (x, y, z) replaced by (u, v, a): the same edge functions with d = s (Q - P)
+ *   and the same tie rule.
+ *   Select: in a covered column, with c the centre, M = |n_a| A_a - s (n_u (c_u - A_u) + n_v (c_v - A_v)), the voxel
+ *   p_a = floor(M / (64 |n_a|)) is selected if it lies in the volume: the voxel that holds the point where the column's centre
+ *   line meets the plane, a crossing on a voxel boundary going to the upper voxel.  For a = z, M is xor_mesh's N + 32 |n_z|.
+ * Theorem: take a triangle and a column it covers along axis a, and let c and c + 1 be the two voxels along a between which
+ * vrc_volume_xor_mesh (read along a) changes state on account of that triangle: the THIN voxel of that column is c or c + 1
+ * (xor_mesh's k = ceil((t - 32) / 64) for the crossing at t = M / |n_a|, the THIN voxel is floor(t / 64): k where t mod 64 <= 32,
+ * k - 1 otherwise).  So two face-adjacent voxels on opposite sides of a closed mesh are never both unselected: the thin shell
+ * stops a face-connected flood, and flooding the empty medium from outside it gives a solid that no doubled triangle inverts
+ * (VoxelVolume.solidFromShell).  THIN is a subset of TOUCHED.
+ *
+ * Cost follows the surface, not the triangle's bounding box.  THIN walks, per axis, the columns of the projected bounding box:
+ * one atomic per covered column.  TOUCHED walks the columns of the projection along the axis in which |n| is largest; a column
+ * leaves on the three edge axes of that projection, and the plane leaves it an interval of at most five voxels, each held to the
+ * 13 axes.  One triangle corner to corner of 512^3, (0,0,0) (S,S,0) (S,0,S) in voxels: the predicate is applied to 524 287
+ * voxels, 524 287 are selected, the bounding box holds 134 217 728 (256 times as many).  Few triangles are spread over up to 1024 workgroups each, a
+ * batch of more than 4096 gets one 256-thread workgroup per triangle whatever its size.  Measured at 512^3 on the MI355X
+ * (tools/bench_raster.py, device time, the call that sets plus the call that clears, median of 5): the terrain's closed
+ * merged-rectangle mesh, 583 244 triangles, TOUCHED 37.6 ms and THIN 2.02 ms next to 1.02 ms for vrc_volume_xor_mesh twice; the
+ * corner-to-corner triangle TOUCHED 0.272 ms and THIN 0.044 ms next to 0.052 ms for vrc_volume_fill_boxes of its bounding box;
+ * 100 000 unit-face triangles TOUCHED 5.46 ms and THIN 0.49 ms next to 0.184 ms for vrc_volume_xor_mesh twice.  TOUCHED costs
+ * about 30 ns per triangle of a large batch however small the triangle: 5 to 37 times its yardsticks. */
+#define VRC_RASTER_TOUCHED 0   /* every voxel whose closed cube meets the closed triangle */
+#define VRC_RASTER_THIN    1   /* the voxel that holds each crossing of a voxel-centre line */
+int vrc_raster_mesh(vrc_volume *v, uint64_t n_tris, const int32_t *tris, int mode, int solid, int mem, void *stream);
 /* The exposed faces of the voxel set as a mesh: getting the world out without a dense download, and the inverse of
  * vrc_volume_xor_mesh.  In integers: face d = 2 * axis + side of the SOLID voxel c = (x, y, z) (side 0 = towards -axis,
  * 1 = towards +axis) is exposed iff the voxel c -/+ e_axis is empty.  A neighbour outside the volume counts as empty when
