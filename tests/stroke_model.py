@@ -118,6 +118,31 @@ def stroke_items(centres, valid, radius, max_gap):
     return np.array(out, np.int64).reshape(-1, 8).astype(np.int32)
 
 
+def mixed_items(rng, S, count):
+    """axis-aligned, diagonal and degenerate capsules with r in {0, 1, 2, 5} and -1, ends far outside the volume, items over the
+    limit and items with reserved != 0"""
+    a = rng.integers(-4, S + 4, (count, 3))
+    b = rng.integers(-4, S + 4, (count, 3))
+    kind = rng.integers(0, 8, count)
+    b[kind == 0] = a[kind == 0]                                               # degenerate
+    for i in np.flatnonzero(kind == 1):                                        # axis-aligned
+        keep = rng.integers(0, 3)
+        b[i] = a[i]
+        b[i, keep] = rng.integers(-4, S + 4)
+    for i in np.flatnonzero(kind == 2):                                        # an exact diagonal: ties of the major axis
+        b[i] = a[i] + rng.integers(1, S) * rng.choice([-1, 1], 3)
+    far = np.flatnonzero(kind == 3)                                            # ends far outside
+    a[far, rng.integers(0, 3, len(far))] = -rng.integers(S, LIMIT + 1, len(far))
+    b[far, rng.integers(0, 3, len(far))] = rng.integers(S, LIMIT + 1, len(far))
+    r = rng.choice([0, 1, 2, 5, 0, 1, 2, 5, -1], (count, 1))
+    items = np.concatenate([a, b, r, np.zeros((count, 1), np.int64)], axis=1)
+    over = np.flatnonzero(kind == 4)
+    items[over[0::3], 0] = LIMIT + 1                                           # dropped: a coordinate, the radius, reserved
+    items[over[1::3], 6] = LIMIT + 1
+    items[over[2::3], 7] = rng.choice([1, -1, 1 << 30], len(over[2::3]))
+    return items.astype(np.int32)
+
+
 def triangle(v, lo, hi):
     """v folded into [lo, hi]: a path that turns round at the walls keeps its step length"""
     span = hi - lo

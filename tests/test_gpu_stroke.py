@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import stroke_model as model
-from stroke_model import gaps_of, scan_rays
+from stroke_model import gaps_of, mixed_items, scan_rays
 from volume_support import Stream, committed, expected_nodes, same, volume_of
 
 pytestmark = pytest.mark.gpu
@@ -27,31 +27,6 @@ def both_forms(volume, other, items, solid, stream):
     t = on_device(items)
     other.fillCapsulesDevice(len(items), t.data_ptr(), solid, stream)
     return t                                               # kept alive by the caller until the download has waited for the edit
-
-
-def mixed_items(rng, S, count):
-    """axis-aligned, diagonal and degenerate capsules with r in {0, 1, 2, 5} and -1, ends far outside the volume, items over the
-    limit and items with reserved != 0"""
-    a = rng.integers(-4, S + 4, (count, 3))
-    b = rng.integers(-4, S + 4, (count, 3))
-    kind = rng.integers(0, 8, count)
-    b[kind == 0] = a[kind == 0]                                               # degenerate
-    for i in np.flatnonzero(kind == 1):                                        # axis-aligned
-        keep = rng.integers(0, 3)
-        b[i] = a[i]
-        b[i, keep] = rng.integers(-4, S + 4)
-    for i in np.flatnonzero(kind == 2):                                        # an exact diagonal: ties of the major axis
-        b[i] = a[i] + rng.integers(1, S) * rng.choice([-1, 1], 3)
-    far = np.flatnonzero(kind == 3)                                            # ends far outside
-    a[far, rng.integers(0, 3, len(far))] = -rng.integers(S, LIMIT + 1, len(far))
-    b[far, rng.integers(0, 3, len(far))] = rng.integers(S, LIMIT + 1, len(far))
-    r = rng.choice([0, 1, 2, 5, 0, 1, 2, 5, -1], (count, 1))
-    items = np.concatenate([a, b, r, np.zeros((count, 1), np.int64)], axis=1)
-    over = np.flatnonzero(kind == 4)
-    items[over[0::3], 0] = LIMIT + 1                                           # dropped: a coordinate, the radius, reserved
-    items[over[1::3], 6] = LIMIT + 1
-    items[over[2::3], 7] = rng.choice([1, -1, 1 << 30], len(over[2::3]))
-    return items.astype(np.int32)
 
 
 # ---- 1. batches of mixed capsules ------------------------------------------------------------------------------------
@@ -297,3 +272,135 @@ def test_stroke_leaves_one_tunnel_where_balls_leave_cavities(built, heights):
         volume.close()
     print("pieces dug:", pieces)
     assert pieces["stroke"] == 1 and pieces["balls"] >= 10
+
+
+# ---- 7. at the limits of the 32-bit claims ---------------------------------------------------------------------------
+# vrc_stroke.hip takes q.q, L2 and t as 32-bit values and multiplies 32 x 32 -> 64: right for items inside LIMIT in a volume
+# of at most 1024^3.  The yardstick is the int64 model: q.q L2 < 2.6e8 * 8.1e8 and r^2 L2 < 6.8e7 * 8.1e8, both inside
+# int64; each case also holds a sample of the model's voxels next to its surface to rule_int, which has no width at all.
+
+def limit_cases(S):
+    """{group: [item]} for a volume of S^3 = 64^3"""
+    L = LIMIT
+    signs = [(1, 1, 1), (1, -1, 1), (1, 1, -1), (1, -1, -1)]
+    diagonals = [[-L * s[0], -L * s[1], -L * s[2], L * s[0], L * s[1], L * s[2], r, 0] for s in signs for r in (0, 3, 40)]
+    # the same lines moved k = S + 2 voxels along x: they pass through (k, 0, 0), two voxels outside the volume, so the
+    # lattice points themselves (r = 0) miss it; both ends stay inside the limit
+    k = S + 2
+    shifted = [[-L + k, -L * s[1], -L * s[2], L, (L - k) * s[1], (L - k) * s[2], r, 0] for s in signs for r in (3, 40)]
+    huge = []
+    for r in (8000, L):
+        # the unit vector (2, 3, 6) / 7: a centre r away from the volume's middle along it, so the surface crosses the volume as
+        # a nearly flat slanted sheet; u = (-3, 2, 0) is square to it
+        c = [S // 2 + (r * n + 3) // 7 for n in (2, 3, 6)]
+        huge.append(c + c + [r, 0])                                            # the ball
+        huge.append(c + [c[0] - 3 * 2300, c[1] + 2 * 2300, c[2], r, 0])        # the volume at the cap of end a (t <= 0 and t > 0 meet there)
+        huge.append([c[0] + 3 * 1000, c[1] - 2 * 1000, c[2], c[0] - 3 * 2300, c[1] + 2 * 2300, c[2], r, 0])      # ... and beside the cylinder
+        fore, back = (L - c[0]) // 3, (L - c[1]) // 2                          # the same axis as long as the limit lets it be: r^2 L2 > 2^53
+        huge.append([c[0] + 3 * fore, c[1] - 2 * fore, c[2], c[0] - 3 * back, c[1] + 2 * back, c[2], r, 0])
+    medium = [[-20, 10, 5, 90, 50, 70, 30, 0], [70, 60, -8, -9, 3, 66, 31, 0]]      # most words pass the pre-test `near`, many are whole
+    return dict(diagonals=diagonals, shifted=shifted, huge=huge, medium=medium)
+
+
+def surface_sample(want, rng, count=200):
+    """about `count` voxels next to the surface of the model's set: both sides of it"""
+    edge = np.zeros(want.shape, bool)
+    for axis in range(3):
+        step = np.diff(want.astype(np.int8), axis=axis) != 0
+        lo = [slice(None)] * 3
+        hi = [slice(None)] * 3
+        lo[axis], hi[axis] = slice(0, -1), slice(1, None)
+        edge[tuple(lo)] |= step
+        edge[tuple(hi)] |= step
+    at = np.argwhere(edge)
+    return at[rng.permutation(len(at))[:count]]
+
+
+@pytest.mark.parametrize("group", ["diagonals", "shifted", "huge", "medium"])
+def test_capsules_at_the_arithmetic_limits(built, group):
+    depth, S = 6, 64
+    rng = np.random.default_rng(64)
+    empty_h, empty_d, full_h, full_d = (volume_of(np.zeros((S, S, S), np.uint8)) for _ in range(4))
+    for volume in (full_h, full_d):
+        volume.fillBoxes([(0, 0, 0, S, S, S)], True)
+    with Stream() as stream:
+        for item in limit_cases(S)[group]:
+            assert model.kept(item), item
+            want = model.fill_capsules(np.zeros((S, S, S), np.uint8), [item], 1)
+            count = int(want.sum())
+            print(group, item, count)
+            assert 0 < count < S ** 3, item                                    # some, not all
+            sample = surface_sample(want, rng)
+            assert len(sample) >= min(200, count) and all(model.rule_int(p, item) == bool(want[tuple(p)]) for p in sample), item
+            items = np.array([item], np.int32)
+            keep = both_forms(empty_h, empty_d, items, True, stream)
+            assert np.array_equal(empty_h.download(), want), (item, "set, host form")
+            assert np.array_equal(empty_d.download(), want), (item, "set, device form")
+            keep = both_forms(full_h, full_d, items, False, stream)
+            assert np.array_equal(full_h.download(), 1 - want), (item, "cleared, host form")
+            assert np.array_equal(full_d.download(), 1 - want), (item, "cleared, device form")
+            keep = both_forms(empty_h, empty_d, items, False, stream)          # back to empty and full for the next
+            keep = both_forms(full_h, full_d, items, True, stream)
+            assert empty_h.solidCount() == empty_d.solidCount() == 0 and full_h.solidCount() == full_d.solidCount() == S ** 3, item
+            del keep
+
+
+def test_corner_to_corner_of_the_limit_at_the_largest_depth(built):
+    """depth 10, the largest VoxelVolume accepts and the one the kernel's comment assumes: the only place where |q| on an axis
+    exceeds 8192 + 64.  No download: the count, every voxel of the model and every 6-neighbour outside it"""
+    import cpuvoxelraycaster_amd as vrc
+    depth, S = 10, 1024
+    L = LIMIT
+    items = np.array([[-L, -L, -L, L, L, L, 2, 0], [L, -L, -L, -L, L, L, 2, 0]], np.int32)          # the second: mirrored in x
+    cells = [model.capsule_voxels_sparse(S, item.tolist()) for item in items]
+    assert len(cells[0]) > 5 * S and 0 < len(cells[1]) < 100                  # the mirrored one meets the volume at its corner alone
+    field = np.unique(np.concatenate(cells), axis=0)
+    key = lambda p: (p[:, 0] * S + p[:, 1]) * S + p[:, 2]
+    around = np.concatenate([field + step for step in ((1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1))])
+    around = around[np.all((around >= 0) & (around < S), axis=1)]
+    around = np.unique(around[~np.isin(key(around), key(field))], axis=0)
+    assert len(around) > len(field) // 2
+    volume = vrc.VoxelVolume(depth)
+    volume.fillCapsules(items, True)
+    assert volume.solidCount() == len(field)
+    assert volume.getVoxels(field.astype(np.uint32)).all() and not volume.getVoxels(around.astype(np.uint32)).any()
+    t = on_device(items)
+    with Stream() as stream:
+        volume.fillCapsulesDevice(len(items), t.data_ptr(), False, stream)
+        assert volume.solidCount() == 0
+    volume.close()
+
+
+def spanning(rng, S, count, radii):
+    """capsules from one face of the volume, or beyond it, to the opposite one, along a seeded major axis"""
+    a, b = rng.integers(0, S, (count, 3)), rng.integers(0, S, (count, 3))
+    major = rng.integers(0, 3, count)
+    a[np.arange(count), major] = -rng.integers(0, 20, count)
+    b[np.arange(count), major] = S - 1 + rng.integers(0, 20, count)
+    flip = rng.random(count) < 0.5
+    a[flip], b[flip] = b[flip], a[flip].copy()
+    return np.concatenate([a, b, rng.choice(radii, (count, 1)), np.zeros((count, 1), np.int64)], axis=1).astype(np.int32)
+
+
+@pytest.mark.parametrize("depth,count,long", [(7, 5000, 300), (8, 300, 40)])
+def test_long_capsules_in_a_large_batch(built, depth, count, long):
+    """5000 at 128^3: split_for gives each capsule ONE workgroup, and a spanning one has 8 pieces or 9 -- the k += k_step loop
+    runs that many rounds.  300 at 256^3: 14 workgroups for the 16 to 18 pieces of a spanning one, which do not divide"""
+    S = 1 << depth
+    rng = np.random.default_rng(depth * 1000 + count)
+    a = rng.integers(-2, S + 2, (count, 3))
+    items = np.concatenate([a, a + rng.integers(-3, 4, (count, 3)), rng.integers(0, 4, (count, 1)), np.zeros((count, 1), np.int64)], axis=1).astype(np.int32)
+    where = rng.permutation(count)[:long]
+    items[where] = spanning(rng, S, long, [0, 1, 3])
+    vol = (rng.random((S, S, S)) < 0.2).astype(np.uint8)
+    volume = volume_of(vol)
+    other = volume.clone()
+    with Stream() as stream:
+        for solid in (True, False):
+            keep = both_forms(volume, other, items, solid, stream)
+            model.fill_capsules(vol, items, 1 if solid else 0, sparse=True)
+            assert np.array_equal(volume.download(), vol), (depth, solid, "host form")
+            assert np.array_equal(other.download(), vol), (depth, solid, "device form")
+            del keep
+            items = items[rng.permutation(len(items))[:len(items) // 2]]      # the clearing call: half of them, so that something stays
+    assert volume.solidCount() == int(vol.sum(dtype=np.int64))

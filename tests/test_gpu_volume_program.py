@@ -48,6 +48,16 @@ class Machine:
             torch.cuda.synchronize()
         return t.cpu().numpy()[:n * np.dtype(dtype).itemsize].view(dtype).copy()
 
+    def columns(self, records):
+        """the records of a profile, from either memory kind, in the model's terms"""
+        import columns_model
+        if records.dtype.names is None:
+            records = np.ascontiguousarray(records, np.uint32).view(self.capi.COLUMN_DTYPE)[..., 0]
+        out = np.zeros(records.shape, columns_model.COLUMN_DTYPE)
+        for name in columns_model.COLUMN_DTYPE.names:
+            out[name] = records[name]
+        return out
+
     def refused(self, call):
         with pytest.raises(self.vrc.VrcError):
             call()
@@ -62,12 +72,27 @@ class Machine:
                 getattr(v, family)(a["items"], a["solid"])
             else:
                 getattr(v, family + "Device")(len(a["items"]), self.up(a["items"]).data_ptr(), a["solid"], st)
-        elif family == "fillSpheresAtHits":
-            out = None
+        elif family == "fillCapsules":
             if host:
-                v.fillSpheresAtHits(a["hits"], a["radius"], a["solid"])
+                v.fillCapsules(a["items"], a["solid"])
             else:
-                v.fillSpheresAtHitsDevice(len(a["hits"]), self.up(a["hits"]).data_ptr(), a["radius"], a["solid"], st)
+                v.fillCapsulesDevice(len(a["items"]), self.up(a["items"]).data_ptr(), a["solid"], st)
+        elif family == "rasterMesh":
+            if host:
+                v.rasterMesh(a["items"], a["op"], a["solid"])
+            else:
+                v.rasterMesh((len(a["items"]), self.up(a["items"]).data_ptr()), a["op"], a["solid"], device=True, stream=st)
+        elif family in P.AT_HITS:
+            out = None
+            if family == "fillSpheresAtHits":
+                if host:
+                    v.fillSpheresAtHits(a["hits"], a["radius"], a["solid"])
+                else:
+                    v.fillSpheresAtHitsDevice(len(a["hits"]), self.up(a["hits"]).data_ptr(), a["radius"], a["solid"], st)
+            elif host:
+                v.strokeAtHits(a["hits"], a["radius"], a["solid"], a["max_gap"])
+            else:
+                v.strokeAtHitsDevice(len(a["hits"]), self.up(a["hits"]).data_ptr(), a["radius"], a["solid"], a["max_gap"], st)
             if a["then"] is not None:                                 # host memory, NULL stream, right behind the brush
                 kind, items = a["then"]
                 out = v.setVoxels(items, True) if kind == "setVoxels" else v.getVoxels(items)
@@ -91,6 +116,26 @@ class Machine:
         elif family in ("cellStepDst", "cellStepSrc"):
             src, dst = (w, v) if family == "cellStepDst" else (v, w)
             src.cellStep(a["birth"], a["survive"], a["neighbours"], bool(a["outside"]), dst, stream=st)
+        elif family == "columnProfile":
+            U, V = P.rect_shape(a["rect"], self.S)
+            if U * V == 0:                                            # an empty rect is refused, in either memory kind
+                t = self.out(16)
+                return self.refused(lambda: v.columnProfile(a["direction"], a["rect"]) if host else v.columnProfileDevice(a["direction"], t.data_ptr(), a["rect"], st))
+            if host:
+                return self.columns(v.columnProfile(a["direction"], a["rect"]))
+            t = self.out(16 * U * V)                                  # a buffer of the test's own
+            v.columnProfileDevice(a["direction"], t.data_ptr(), a["rect"], st)
+            return self.columns(self.down(t, form, np.uint32, 4 * U * V).reshape(U, V, 4))
+        elif family == "fillColumns":
+            if host:
+                v.fillColumns(a["axis"], a["lo"], a["hi"], a["rect"], a["op"])
+            else:
+                maps = [self.up(q).data_ptr() if np.ndim(q) else None for q in (a["lo"], a["hi"])]
+                consts = [0 if np.ndim(q) else int(q) for q in (a["lo"], a["hi"])]
+                v.fillColumnsDevice(a["axis"], maps[0], consts[0], maps[1], consts[1], a["rect"], a["op"], st)
+        elif family in ("selectColumnsDst", "selectColumnsSrc"):
+            src, dst = (w, v) if family == "selectColumnsDst" else (v, w)
+            src.selectColumns(a["direction"], a["lo"], a["hi"], a["of"], dst, a["op"], st)
         elif family == "floodRegion":
             return int(v.flood(w, a["connectivity"], a["through_empty"]).reached)
         elif family == "floodMedium":
@@ -185,6 +230,20 @@ class Machine:
         elif family == "refuseMesh":
             tris = P.box_mesh([0, 0, 0], [1, 1, 1])
             return self.refused(lambda: capi.check(self.L.vrc_volume_xor_mesh(v._h, len(tris), capi.ptr(tris), 7, None)))
+        elif family == "refuseRaster":
+            return self.refused(lambda: v.rasterMesh(P.clipped_raster_triangles(self.S), 2, True))
+        elif family == "refuseStroke":
+            return self.refused(lambda: v.strokeAtHits(P.hits_of([[0, 0, 0]], self.S, miss_every=2), (1 << 13) + 1, True))
+        elif family == "refuseProfile":
+            return self.refused(lambda: v.columnProfile(6))
+        elif family == "refuseFillAxis":
+            return self.refused(lambda: v.fillColumns(3, 0, self.S))
+        elif family == "refuseSelect":
+            return self.refused(lambda: w.selectColumns(-1, 0, 1, 1, v))
+        elif family == "refuseSelectSame":
+            return self.refused(lambda: v.selectColumns(0, 0, 1, 1, v))
+        elif family == "refuseSelectDepth":
+            return self.refused(lambda: self.other.selectColumns(0, 0, 1, 1, v))
         elif family == "cloneSecond":
             w.close()
             self.w = v.clone()

@@ -5,14 +5,17 @@ import numpy as np
 import pytest
 
 import cells_model
+import columns_model
 import components_model
 import delta_model
 import distance_model
 import fall_model
 import flood_model
 import pack_model
+import raster_model
 import rect_model
 import stamp_model
+import stroke_model
 import surface_model
 import volume_program as P
 import voxelize_model
@@ -45,7 +48,9 @@ def test_one_step_is_the_family_model():
                 m = primed(depth)
                 a = P._arguments(rng, family, form, m)
                 if "op" in a:
-                    a["op"] = op if family != "place" else (P.OR, P.ANDNOT)[op % 2]
+                    a["op"] = (P.OR, P.ANDNOT)[op % 2] if family == "place" else op % 2 if family == "rasterMesh" else op
+                if family == "strokeAtHits":
+                    a["then"] = None                           # the call behind a stroke: test_one_step_refusals_lifetime_...
                 v, w, ids = m.s["v"], m.s["w"], m.s["ids"]
                 out = m.apply((family, form, a))
                 value = 1 if a.get("solid") else 0
@@ -68,6 +73,30 @@ def test_one_step_is_the_family_model():
                     continue                                   # held by test_hits_name_their_cells below
                 elif family == "xorMesh":
                     want_v = voxelize_model.xor_mesh(S, a["tris"], v.copy())
+                elif family == "fillCapsules":
+                    g = np.indices((S, S, S)).astype(np.int64)          # the rule over the whole volume, no bounding box
+                    want_v = v.copy()
+                    for item in a["items"].tolist():
+                        if stroke_model.kept(item) and item[6] >= 0:
+                            want_v[stroke_model.rule(g[0], g[1], g[2], item)] = value
+                    assert any(stroke_model.kept(i) and abs(i[3 + k] - i[k]) == 12 for i in a["items"].tolist() for k in range(3))       # the crossing one
+                elif family == "strokeAtHits":
+                    rec = a["hits"]
+                    centres = S - 1 - np.floor((rec["position"].astype(np.float64) - 1.0) * S).astype(np.int64) + ([0, 1, 0] if a["solid"] else [0, 0, 0])
+                    valid = (rec["hit"] == 1) & (centres[:, 1] < S)
+                    want_v = stroke_model.fill_capsules(v.copy(), stroke_model.stroke_items(centres, valid, a["radius"], a["max_gap"]), value)
+                elif family == "rasterMesh":
+                    want_v = raster_model.raster_mesh(S, a["items"], a["op"], a["solid"], v.copy())
+                elif family == "fillColumns":
+                    want_v = columns_model.fill(v, a["axis"], a["lo"], a["hi"], a["rect"], a["op"])
+                    assert a["maps"] == sum(np.ndim(q) == 2 for q in (a["lo"], a["hi"])) and (form != "host" or a["maps"] >= 1)
+                elif family == "selectColumnsDst":
+                    want_v = columns_model.select(v, w, a["direction"], a["lo"], a["hi"], a["of"], a["op"])
+                elif family == "selectColumnsSrc":
+                    want_w = columns_model.select(w, v, a["direction"], a["lo"], a["hi"], a["of"], a["op"])
+                elif family == "columnProfile":
+                    empty = a["rect"] is not None and (a["rect"][0] >= a["rect"][2] or a["rect"][1] >= a["rect"][3])
+                    want = "refused" if empty else columns_model.profile(v, a["direction"], a["rect"])
                 elif family == "copyRegion":
                     m_, t_ = stamp_model.IDENTITY
                     t_ = [(a["src_lo"][k] - a["dst_lo"][k]) << 17 for k in range(3)]
@@ -253,13 +282,35 @@ def test_coverage_of_the_committed_seeds():
         assert good, (seed, depth)
         for family in ("surface", "rects"):
             assert any(s[0] == family and s[1] in ("devA", "devB") and s[2].get("order") == "extract_first" for s in steps), (seed, depth, family)
+        # the stroke at hits, whose kernel reads centre i and i + 1 in the staging block: on a stream of the test's own with a host
+        # staging call as the next step; and inside one step with a host list edit behind it, and with a host query of voxels it changes
+        assert any(a[0] == "strokeAtHits" and a[1] in ("devA", "devB") and P.stages(b) and b[1] == "host" for a, b in adjacent(steps)), (seed, depth)
+        strokes = [(i, s) for i, s in enumerate(steps) if s[0] == "strokeAtHits" and s[1] in ("devA", "devB") and s[2]["then"] is not None]
+        assert any(s[2]["then"][0] == "setVoxels" and len(s[2]["then"][1]) >= 4 for _, s in strokes), (seed, depth)
+        assert any(s[2]["then"][0] == "getVoxels" and not np.array_equal(P.get_voxels(seen[i - 1][1], s[2]["then"][1]), seen[i][0]) for i, s in strokes), (seed, depth)
+        # a host columnProfile directly after a larger host list edit: the records come down through a block of the call's own
+        # and the volume's scratch does not move; a fillColumns with two host maps directly after one with one
+        assert any(a[0] in P.ITEM_BYTES and a[1] == b[1] == "host" and b[0] == "columnProfile" and seen[i + 1][3] == seen[i][3] and
+                   0 < 16 * int(np.prod(P.rect_shape(b[2]["rect"], 1 << depth))) < P.ITEM_BYTES[a[0]] * len(a[2]["items" if "items" in a[2] else "tris"])
+                   for i, (a, b) in enumerate(adjacent(steps))), (seed, depth)
+        assert any(a[0] == b[0] == "fillColumns" and a[1] == b[1] == "host" and (a[2]["maps"], b[2]["maps"]) == (1, 2) for a, b in adjacent(steps)), (seed, depth)
+        # a rasterMesh follows a refused one and one whose triangles were all clipped
+        rasters = [s for s in steps if s[0] in ("rasterMesh", "refuseRaster")]
+        assert any(a[0] == "refuseRaster" and b[0] == "rasterMesh" for a, b in adjacent(rasters)), (seed, depth)
+        assert any(a[0] == "rasterMesh" and a[2]["kind"] == "clipped" and b[0] == "rasterMesh" and b[2]["kind"] != "clipped" for a, b in adjacent(rasters)), (seed, depth)
+        # no column call moves the scratch of either volume
+        for i, s in enumerate(steps):
+            if s[0] in P.OWN_BLOCK + ("selectColumnsDst", "selectColumnsSrc") and i:
+                assert seen[i][3:5] == seen[i - 1][3:5], (seed, depth, i)
     assert set(P.shared_pairs()) <= covered, sorted(set(P.shared_pairs()) - covered)
+    assert {("d_stage", a, b) for a in ("fillCapsules", "strokeAtHits", "rasterMesh") for b in P.BLOCKS["d_stage"]} <= covered
     for form in P.FORMS[1:]:                                    # the stream-only edits: each stream occurs among them
         assert any((family, form) in used for family in P.STREAM_EDITS), form
     # every family, every op of the families that take one and every form of the list calls: at EVERY depth
     for depth in P.DEPTHS:
         steps = [s for seed in P.SEEDS[depth] for s in P.program(seed, depth)]
-        ran = {(s[0], s[2].get("op"), form) for s in steps for form in (s[1], None)}
+        # a family that takes an op (rasterMesh: a mode) and has all four forms also counts under (family, None, form)
+        ran = {(s[0], op, form) for s in steps for op in (s[2].get("op"), None) for form in (s[1], None)}
         assert set(P.TOUR) <= ran, (depth, sorted(set(P.TOUR) - ran, key=str))
         assert {(family, None, form) for family in P.ALL_FORMS for form in P.FORMS} <= ran, depth
         changed = {(s[0], s[2].get("op")) for seed in P.SEEDS[depth] for s, o in zip(P.program(seed, depth), P.run_committed(seed, depth)) if o[5]}
@@ -290,7 +341,48 @@ def test_every_fault_is_visible(seed, fault):
     if fault == "unordered":
         # not through the download alone: the query behind a brush and the extraction under a count see it themselves
         own = {s[0] for s, g, b in zip(P.program(seed, 5), good, bad) if not P.same_value(g[0], b[0])}
-        assert {"fillSpheresAtHits", "surface", "rects"} <= own, (seed, own)
+        assert {"fillSpheresAtHits", "strokeAtHits", "surface", "rects"} <= own, (seed, own)
+    if fault == "links":
+        # the stroke itself went wrong, not a call behind it: the first step that differs is a stroke with a list edit behind it
+        first = next(s for s, g, b in zip(P.program(seed, 5), good, bad) if not P.same_value(g[:5], b[:5]))
+        assert first[0] == "strokeAtHits" and first[1] in ("devA", "devB") and first[2]["then"][0] == "setVoxels", (seed, first[:2])
+
+
+def test_faults_show_through_the_new_families():
+    """stage_tail, unordered and links on mirrors of a few steps: each new family that writes the staging block, or edits on a
+    stream, shows the hazard by itself"""
+    depth, S = 5, 32
+    start = field(S, 21)
+    caps = np.array([[i, 2, 3, i, 20, 9, 1, 0] for i in range(10)], np.int32)
+    tris = raster_model.box_mesh([70, 70, 70], [900, 1000, 1100]).astype(np.int32)
+
+    def seen(steps, fault):
+        m = P.Mirror(depth, fault)
+        m.s["v"], m.s["w"] = start, field(S, 22)
+        return [(m.apply(step), m.seen_download("v"), m.scratch_bytes("v")) for step in steps]
+
+    def visible(steps, fault):
+        return not P.same_value(tuple(seen(steps, None)), tuple(seen(steps, fault)))
+
+    # a longer host list, then a shorter one: the call reads the items the block still holds behind its own
+    assert visible([("fillCapsules", "host", dict(items=caps, solid=False)), ("fillCapsules", "host", dict(items=caps[:2], solid=True))], "stage_tail")
+    assert visible([("rasterMesh", "host", dict(items=tris, op=P.TOUCHED, solid=False)), ("rasterMesh", "host", dict(items=tris[:1], op=P.TOUCHED, solid=True))], "stage_tail")
+    # the download, and the query a stroke carries, right behind an edit on a stream
+    one = np.full((4, 4), 9, np.int32)
+    for step in (("fillCapsules", "devA", dict(items=caps, solid=False)), ("rasterMesh", "devB", dict(items=tris, op=P.THIN, solid=False)),
+                 ("fillColumns", "devA", dict(axis=0, rect=[1, 1, 5, 5], op=P.REPLACE, lo=one - 4, hi=one, maps=2)),
+                 ("selectColumnsDst", "devB", dict(direction=3, lo=0, hi=2, of=columns_model.SOLID, op=P.REPLACE))):
+        assert visible([step], "unordered"), step[0]
+    cells = np.argwhere(start)[:40:5]
+    stroke = dict(hits=P.hits_of(cells, S, miss_every=10), radius=0, max_gap=0, solid=False)
+    query = [("strokeAtHits", "devA", dict(stroke, then=("getVoxels", cells[1:].astype(np.uint32))))]
+    assert not P.same_value(seen(query, None)[0][0], seen(query, "unordered")[0][0]) and not seen(query, None)[0][0].any()
+    # k_stroke_links reads centre i + 1 after the list edit behind it has rewritten the block: another stroke altogether
+    far = np.array([[0, 0, 0], [S - 1, 0, 0], [0, S - 1, 0], [0, 0, S - 1]], np.uint32)
+    edit = [("strokeAtHits", "devB", dict(stroke, then=("setVoxels", far)))]
+    assert visible(edit, "links") and not visible([("strokeAtHits", "host", dict(stroke, then=None))], "links")
+    good, bad = seen(edit, None)[0][1], seen(edit, "links")[0][1]
+    assert (bad & (1 - good)).any()                                       # the first centres, rewritten, were never dug
 
 
 def test_scratch_sizes_restate_the_per_family_tests():
@@ -305,3 +397,23 @@ def test_scratch_sizes_restate_the_per_family_tests():
     assert m.scratch_bytes() == 120 + P.surface_bytes(5)
     m.apply(("cloneSecond", "host", {}))
     assert m.scratch_bytes("w") == 0
+    # tests/test_gpu_stroke.py and test_gpu_volume_raster.py:154-166 (32 and 36 bytes an item), test_gpu_volume_columns.py:75, 183
+    # (the records and the maps of the column calls: a block of the call's own, the volume's scratch does not move)
+    m = P.Mirror(5)
+    m.apply(("columnProfile", "host", dict(direction=2, rect=[0, 0, 3, 5])))
+    m.apply(("fillColumns", "host", dict(axis=1, rect=[0, 0, 3, 5], op=P.OR, lo=np.zeros((3, 5), np.int32), hi=np.ones((3, 5), np.int32), maps=2)))
+    assert m.scratch_bytes() == 0
+    m.apply(("fillCapsules", "host", dict(items=np.zeros((10, 8), np.int32), solid=True)))
+    m.apply(("columnProfile", "host", dict(direction=2, rect=[0, 0, 3, 5])))
+    assert m.scratch_bytes() == 320
+    m.apply(("rasterMesh", "host", dict(items=np.zeros((9, 9), np.int32), op=P.THIN, solid=True)))
+    assert m.scratch_bytes() == 324
+    m.apply(("fillCapsules", "devA", dict(items=np.zeros((99, 8), np.int32), solid=True)))
+    m.apply(("rasterMesh", "dev0", dict(items=np.zeros((99, 9), np.int32), op=P.THIN, solid=True)))
+    m.apply(("selectColumnsDst", "devA", dict(direction=0, lo=0, hi=1, of=1, op=P.OR)))
+    assert m.scratch_bytes() == 324 and m.scratch_bytes("w") == 0
+    hits = P.hits_of(np.zeros((21, 3), np.int64), 32)
+    m.apply(("strokeAtHits", "devB", dict(hits=hits, radius=1, max_gap=0, solid=True, then=None)))
+    assert m.scratch_bytes() == 16 * 21
+    m.apply(("strokeAtHits", "host", dict(hits=hits, radius=1, max_gap=0, solid=True, then=None)))
+    assert m.scratch_bytes() == 64 * 21

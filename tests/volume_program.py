@@ -2,27 +2,35 @@
 tests/test_gpu_volume_program.py runs on the device and tests/test_volume_program_host.py holds to its purpose on the CPU.
 numpy and Python integers only; every expected value comes from the model the family's own tests use (stamp_model,
 flood_model, cells_model, delta_model, pack_model, voxelize_model, surface_model, rect_model, components_model,
-distance_model, fall_model); the sphere predicate is vrc.h:208-210 taken literally, as the brushes' tests take it.
+distance_model, fall_model, stroke_model, raster_model, columns_model); the sphere predicate is vrc.h:208-210 taken literally,
+as the brushes' tests take it.
 
 A step is (family, form, arguments): a plain record.  `v` is the program's volume, `w` the second one.
 
 Forms: "host" = host memory (synchronous); "dev0" = device memory on the NULL stream; "devA" / "devB" = device memory on
 the first / second stream of the test's own.  A family without a memory kind (copyRegion, stampAffine, fillRandom,
-applyDelta, cellStep) takes only the stream from its form.
+applyDelta, cellStep, selectColumns) takes only the stream from its form.  rasterMesh keeps its mode under the key "op", so
+that the tour takes both modes as it takes every op.
 
 ORDERING says, per combination of a call with what may still be in flight, who orders it.  The GPU test downloads both
 volumes after EVERY step, and vrc_volume_download is "synchronous, after every edit issued so far" (vrc.h:191-192), so
 between two steps nothing is in flight: every two-stream combination between steps is synchronised by the program, as
 vrc.h:178-179 asks of a caller ("issue a volume's asynchronous edits on ONE stream (or order the streams yourself)").  The
 combinations INSIDE a step are the library's to order: the download right behind a device-memory edit (vrc.h:191-192), the
-host-memory list call or query that a brush at hits carries in its `then` argument (vrc.h:205-206, 219-220: the centres lie
-in the staging block, in flight on the caller's stream), and the synchronous surface / rectangle count issued while a
+host-memory list call or query that a brush or a stroke at hits carries in its `then` argument (vrc.h:205-206, 219-220 and,
+for the stroke, 249-250: the centres lie in the staging block, in flight on the caller's stream, and the stroke's kernel
+reads centre i and i + 1 there), and the synchronous surface / rectangle count issued while a
 device-memory extraction of the same step is still on its stream (order "extract_first"; vrc.h:271-272, 315-316).
 
 Sizes of the per-volume scratch blocks (Mirror.scratch_bytes), each restated with the line it was read off:
   staging, host form   12 n set_voxels (vrc_volume.hip:429), 24 n fill_boxes (:445), 16 n fill_spheres (:462),
                        64 n brush at hits, 16 n in device form (:484), 36 n xor_mesh (:517), 13 n get_voxels (:603),
-                       32 n count_boxes (:619), 16 per face / rectangle of a host window (:697, :724)
+                       32 n count_boxes (:619), 16 per face / rectangle of a host window (:697, :724),
+                       32 n fill_capsules (vrc_volume.hip:511), 64 n stroke at hits, 16 n in device form (:533),
+                       36 n raster_mesh (:560)
+  column calls         nothing: the 16 U V records of a host profile and the 4 U V bytes of each host map of a fill are
+                       staged in a block of the call's own (vrc.h:1329-1330; vrc_snapshots.hip:82 gives these calls
+                       stage_in_v = false, :896 and :915 size the parts), and select stages nothing (:937-941)
   mark field           8^(depth-1) (vrc_voxelize.hip:145)
   surface offsets      8 (ceil(8^depth / 32 / 256) + 7) (vrc_surface.hip:211-221)
   rectangle block      8 (ceil(6 S^2 w / 256) + 7) + 8 S^2 w, w = max(1, S / 32) (vrc_rects.hip:258-282)
@@ -34,47 +42,55 @@ import functools
 import numpy as np
 
 import cells_model
+import columns_model
 import components_model
 import delta_model
 import distance_model
 import fall_model
 import flood_model
 import pack_model
+import raster_model
 import rect_model
 import stamp_model
+import stroke_model
 import surface_model
 import voxelize_model
 
 REPLACE, OR, ANDNOT = 0, 1, 2
+TOUCHED, THIN = raster_model.TOUCHED, raster_model.THIN
 FORMS = ("host", "dev0", "devA", "devB")
 HIT_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("voxel_coord", "<f4", 2), ("hit", "<u4"), ("node", "<u4"),
                       ("distance", "<f4"), ("complexity", "<u4")])                  # vrc_hit, 48 bytes (include/vrc.h)
 
 DEPTHS = (2, 3, 5, 6)
 SEEDS = {2: (21, 22, 23), 3: (31, 32, 33), 5: (51, 52, 53), 6: (61, 62, 63)}
-STEPS = {2: 150, 3: 150, 5: 150, 6: 64}
+STEPS = {2: 200, 3: 200, 5: 200, 6: 110}
 COMMITTED = [(seed, depth) for depth in DEPTHS for seed in SEEDS[depth]]
 
 ORDERING = {
     # (what runs, what may be in flight): (who orders it, where it says so)
     ("download", "device-memory edit of the same step"): ("library", "vrc.h:191-192"),
     ("then: host list call / query", "brush at hits of the same step"): ("library", "vrc.h:205-206, 219-220"),
+    ("then: host list call / query", "stroke at hits of the same step, its kernel reading centres i and i + 1"): ("library", "vrc.h:249-250"),
     ("surface / rect count", "device-memory extraction of the same step (order extract_first)"): ("library", "vrc.h:271-272, 315-316"),
     ("any call", "an edit of an earlier step, on any stream"): ("program: the download between the steps", "vrc.h:178-179, 191-192"),
 }
 
-LIST_EDITS = ("setVoxels", "fillBoxes", "fillSpheres", "fillSpheresAtHits", "xorMesh")
-STREAM_EDITS = ("copyRegion", "stampAffine", "fillRandom", "applyDelta", "cellStepDst", "cellStepSrc")
-OTHER_EDITS = ("unpack", "floodRegion", "floodMedium", "keepConnected", "dilate", "erode", "select", "place")
+LIST_EDITS = ("setVoxels", "fillBoxes", "fillSpheres", "fillSpheresAtHits", "xorMesh", "fillCapsules", "strokeAtHits", "rasterMesh")
+STREAM_EDITS = ("copyRegion", "stampAffine", "fillRandom", "applyDelta", "cellStepDst", "cellStepSrc", "selectColumnsDst", "selectColumnsSrc")
+OTHER_EDITS = ("unpack", "floodRegion", "floodMedium", "keepConnected", "dilate", "erode", "select", "place", "fillColumns")
 EDITS = LIST_EDITS + STREAM_EDITS + OTHER_EDITS
-QUERIES = ("solidCount", "getVoxels", "countBoxes", "surface", "rects", "pack", "diff", "components", "distanceAt", "commit")
-REFUSALS = ("refuseOp", "refusePack", "refuseUnpack", "refuseDelta", "refuseDepth", "refuseMesh")
+QUERIES = ("solidCount", "getVoxels", "countBoxes", "surface", "rects", "pack", "diff", "components", "distanceAt", "commit", "columnProfile")
+REFUSALS = ("refuseOp", "refusePack", "refuseUnpack", "refuseDelta", "refuseDepth", "refuseMesh", "refuseRaster", "refuseStroke", "refuseProfile",
+            "refuseFillAxis", "refuseSelect", "refuseSelectSame", "refuseSelectDepth")
+AT_HITS = ("fillSpheresAtHits", "strokeAtHits")                       # the centres pass through the staging block in every form
 LIFETIME = ("cloneSecond", "recreateSecond", "snapshotLabels", "snapshotClone")
 FAMILIES = EDITS + QUERIES + REFUSALS + LIFETIME
 
 # the families that share a persistent block of `v` (vrc_volume_state.h:15-46); d_stage: in a form that stages
 BLOCKS = {
-    "d_stage": ("setVoxels", "fillBoxes", "fillSpheres", "fillSpheresAtHits", "xorMesh", "getVoxels", "countBoxes", "surface", "rects"),
+    "d_stage": ("setVoxels", "fillBoxes", "fillSpheres", "fillSpheresAtHits", "xorMesh", "getVoxels", "countBoxes", "surface", "rects",
+                "fillCapsules", "strokeAtHits", "rasterMesh"),
     "d_marks": ("xorMesh",),
     "d_flood": ("floodRegion",),
     "d_surface": ("surface",),
@@ -83,13 +99,15 @@ BLOCKS = {
     "grids": ("commit",),
     "d_count": ("solidCount", "floodRegion"),
 }
-FAULTS = ("marks", "stage_tail", "rows", "commit", "unordered")
+# the host forms of these stage in a block of the call's own (vrc.h:1329-1330): they sit next to the users of d_stage, and leave it alone
+OWN_BLOCK = ("columnProfile", "fillColumns")
+FAULTS = ("marks", "stage_tail", "rows", "commit", "unordered", "links")
 
 
 def stages(step):
     """the step writes v's staging block"""
     family, form, _ = step
-    return family in BLOCKS["d_stage"] and (form == "host" or family == "fillSpheresAtHits")
+    return family in BLOCKS["d_stage"] and (form == "host" or family in AT_HITS)
 
 
 def shared_pairs():
@@ -128,7 +146,8 @@ def flood_bytes(depth):
     return 4 * (3 * T ** 3 + 8)
 
 
-ITEM_BYTES = {"setVoxels": 12, "fillBoxes": 24, "fillSpheres": 16, "xorMesh": 36, "getVoxels": 13, "countBoxes": 32}
+ITEM_BYTES = {"setVoxels": 12, "fillBoxes": 24, "fillSpheres": 16, "xorMesh": 36, "getVoxels": 13, "countBoxes": 32, "fillCapsules": 32,
+              "rasterMesh": 36}
 
 
 # ---- small models ------------------------------------------------------------------------------------------------
@@ -206,6 +225,44 @@ def hit_centres(rec, S, solid):
         cells = cells + [0, 1, 0]
         cells = cells[cells[:, 1] < S]
     return cells
+
+
+def stroke_centres(rec, S, solid):
+    """(centres (n, 3) int64, valid (n,) bool), one per RECORD as the stroke needs them: a miss, and a build without a
+    neighbour, is no centre and breaks the stroke"""
+    valid = ((rec["hit"] & 0xff) == 1) & np.all((rec["position"] >= 1) & (rec["position"] < 2), axis=1)        # vrc.h:217
+    cells = (S - 1 - np.floor((rec["position"].astype(np.float64) - 1.0) * S)).astype(np.int64)
+    if solid:
+        cells = cells + [0, 1, 0]
+        valid = valid & (cells[:, 1] < S)
+    cells[~valid] = 0
+    return cells, valid
+
+
+def walk_cells(rng, S, n, reach=2):
+    """n cells of a random walk with steps of at most `reach` a coordinate: the hits of a dragged crosshair"""
+    return np.clip(rng.integers(0, S, 3) + np.cumsum(rng.integers(-reach, reach + 1, (n, 3)), axis=0), 0, S - 1)
+
+
+def crossing_capsule(rng, S):
+    """an item whose major axis crosses a multiple of 16 (at S > 16 inside the volume: the capsule has two pieces)"""
+    m = 16 * int(rng.integers(1, S // 16)) if S > 16 else 0
+    axis = int(rng.integers(0, 3))
+    a, b = rng.integers(0, S, 3), rng.integers(0, S, 3)
+    b = a + np.clip(b - a, -5, 5)
+    a[axis], b[axis] = m - 6, m + 6
+    return np.concatenate([a, b, [int(rng.integers(0, 3)), 0]]).astype(np.int32)
+
+
+def clipped_raster_triangles(S):
+    """a triangle wholly outside the volume in x and one with a coordinate over raster_model.LIMIT (dropped): nothing is selected"""
+    U = raster_model.UNIT
+    return np.array([[(S + 2) * U, U, U, (S + 5) * U, U, U, (S + 2) * U, 4 * U, U],
+                     [U, U, U, raster_model.LIMIT + 1, U, U, U, 3 * U, 2 * U]], np.int32)
+
+
+def rect_shape(rect, S):
+    return (S, S) if rect is None else (max(0, int(rect[2]) - int(rect[0])), max(0, int(rect[3]) - int(rect[1])))
 
 
 def box_mesh(lo, hi):
@@ -296,10 +353,32 @@ class Mirror:
             s["v"] = {"setVoxels": voxels, "fillBoxes": boxes, "fillSpheres": spheres}[family](v0, items, 1 if a["solid"] else 0)
             if host:
                 self._stage(ITEM_BYTES[family] * len(a["items"]))
-        elif family == "fillSpheresAtHits":
-            centres = hit_centres(a["hits"], S, a["solid"])
-            items = np.concatenate([centres, np.full((len(centres), 1), a["radius"], np.int64)], axis=1)
-            s["v"] = spheres(v0, items, 1 if a["solid"] else 0)
+        elif family in ("fillCapsules", "rasterMesh"):
+            items = self._list_items(family, a["items"], host)
+            if family == "fillCapsules":
+                s["v"] = stroke_model.fill_capsules(v0.copy(), items, 1 if a["solid"] else 0)
+            else:
+                s["v"] = raster_model.raster_mesh(S, items, a["op"], a["solid"], v0.copy())
+            if host:
+                self._stage(ITEM_BYTES[family] * len(a["items"]))
+        elif family in AT_HITS:
+            if family == "fillSpheresAtHits":
+                centres = hit_centres(a["hits"], S, a["solid"])
+                items = np.concatenate([centres, np.full((len(centres), 1), a["radius"], np.int64)], axis=1)
+                s["v"] = spheres(v0, items, 1 if a["solid"] else 0)
+            else:
+                centres, valid = stroke_centres(a["hits"], S, a["solid"])
+                if self.fault == "links" and not host and a.get("then") is not None:
+                    # the host-memory call behind the stroke has rewritten the head of the block (its coordinates, 12 bytes
+                    # an item) before k_stroke_links read it: n x (x, y, z, radius or -1) int32 as k_hits_to_centres left them
+                    block = np.concatenate([centres, np.where(valid, a["radius"], -1)[:, None]], axis=1).astype(np.int32)
+                    raw = bytearray(block.tobytes())
+                    over = np.ascontiguousarray(a["then"][1], np.uint32).tobytes()[:len(raw)]
+                    raw[:len(over)] = over
+                    block = np.frombuffer(bytes(raw), np.int32).reshape(-1, 4).astype(np.int64)
+                    centres, valid = block[:, :3], block[:, 3] >= 0
+                items = stroke_model.stroke_items(centres, valid, a["radius"], a["max_gap"])
+                s["v"] = stroke_model.fill_capsules(v0.copy(), items, 1 if a["solid"] else 0)
             self._stage((64 if host else 16) * len(a["hits"]))
             if host:
                 s["stage_tail"] = np.ascontiguousarray(a["hits"]).tobytes() + s["stage_tail"][48 * len(a["hits"]):]
@@ -344,6 +423,15 @@ class Mirror:
             s["v"] = cells_model.step(w0, a["birth"], a["survive"], a["neighbours"], a["outside"])[0]
         elif family == "cellStepSrc":
             s["w"] = cells_model.step(v0, a["birth"], a["survive"], a["neighbours"], a["outside"])[0]
+        elif family == "fillColumns":
+            s["v"] = columns_model.fill(v0, a["axis"], a["lo"], a["hi"], a["rect"], a["op"])        # no staging in v: OWN_BLOCK
+        elif family == "selectColumnsDst":
+            s["v"] = columns_model.select(v0, w0, a["direction"], a["lo"], a["hi"], a["of"], a["op"])
+        elif family == "selectColumnsSrc":
+            s["w"] = columns_model.select(w0, v0, a["direction"], a["lo"], a["hi"], a["of"], a["op"])
+        elif family == "columnProfile":
+            # a rect must be non-empty (vrc.h:1298): an empty one is refused and nothing moves
+            out = "refused" if 0 in rect_shape(a["rect"], S) else columns_model.profile(v0, a["direction"], a["rect"])
         elif family == "floodRegion":
             s["v"] = flood_model.flood(w0, v0, a["connectivity"], a["through_empty"])
             self._block("d_flood")
@@ -425,7 +513,7 @@ class Mirror:
         else:
             raise ValueError(family)
         self.changed = not (np.array_equal(s["v"], v0) and np.array_equal(s["w"], w0))
-        if family in EDITS and not host and family not in ("floodMedium", "cellStepSrc"):
+        if family in EDITS and not host and family not in ("floodMedium", "cellStepSrc", "selectColumnsSrc"):
             s["before_edit"] = v0
         return out
 
@@ -458,11 +546,17 @@ def _box(rng, S, least=1):
     return [int(q) for q in lo], [int(q) for q in size]
 
 
+def _rect(rng, S):
+    """a non-empty rect of columns (u_lo, v_lo, u_hi, v_hi) inside the face"""
+    u_lo, v_lo = int(rng.integers(0, S)), int(rng.integers(0, S))
+    return [u_lo, v_lo, int(rng.integers(u_lo + 1, S + 1)), int(rng.integers(v_lo + 1, S + 1))]
+
+
 def _arguments(rng, family, form, m, op=None):
     """the arguments of one step on the mirror's present state, or None where the family cannot run yet"""
     S, depth, s = m.S, m.depth, m.s
     a = {}
-    if family in ("setVoxels", "fillBoxes", "fillSpheres", "fillSpheresAtHits"):
+    if family in ("setVoxels", "fillBoxes", "fillSpheres", "fillSpheresAtHits", "fillCapsules", "strokeAtHits", "rasterMesh"):
         a["solid"] = bool(rng.integers(0, 2))
     if family in ("setVoxels", "getVoxels"):
         n = int(rng.integers(1, 40)) if rng.random() < 0.7 else int(rng.integers(60, 200))
@@ -489,6 +583,45 @@ def _arguments(rng, family, form, m, op=None):
         if form in ("devA", "devB") and rng.random() < 0.7:
             items = rng.integers(0, S, (int(rng.integers(1, 5)), 3)).astype(np.uint32)
             a["then"] = ("setVoxels" if rng.random() < 0.5 else "getVoxels", items)
+    elif family == "fillCapsules":
+        # degenerate, axis-aligned, exact diagonals, ends far outside, r = -1 and dropped items, as the brush's own test draws
+        # them, and one capsule of more than one piece
+        n = int(rng.integers(1, 6)) if rng.random() < 0.7 else int(rng.integers(20, 50))
+        a["items"] = np.concatenate([stroke_model.mixed_items(rng, S, n), crossing_capsule(rng, S)[None, :]])
+    elif family == "strokeAtHits":
+        n = int(rng.integers(3, 30))
+        a["hits"] = hits_of(walk_cells(rng, S, n), S)
+        a["radius"], a["max_gap"] = int(rng.choice([0, 1, 3])), int(rng.choice([0, 2]))
+        a["then"] = None
+        if form in ("devA", "devB") and rng.random() < 0.7:
+            items = rng.integers(0, S, (int(rng.integers(1, 5)), 3)).astype(np.uint32)
+            a["then"] = ("setVoxels" if rng.random() < 0.5 else "getVoxels", items)
+    elif family == "rasterMesh":
+        a["op"] = int(rng.integers(0, 2))                                     # the mode
+        a["kind"] = ("small", "small", "small", "mixed", "span", "clipped")[int(rng.integers(0, 6))]
+        n = int(rng.integers(1, 6)) if rng.random() < 0.7 else int(rng.integers(20, 50))
+        small = raster_model.small_triangles(rng, S, n).astype(np.int32)
+        a["items"] = {"small": small, "mixed": np.concatenate([clipped_raster_triangles(S), small]), "clipped": clipped_raster_triangles(S),
+                      "span": raster_model.corner_triangle(S).astype(np.int32)}[a["kind"]]
+    elif family == "columnProfile":
+        a["direction"] = int(rng.integers(0, 6))
+        pick = rng.random()
+        a["rect"] = None if pick < 0.4 else _rect(rng, S)
+        if pick > 0.92:
+            a["rect"][2] = a["rect"][0]                                       # empty: refused
+    elif family == "fillColumns":
+        a["axis"], a["rect"], a["op"] = int(rng.integers(0, 3)), _rect(rng, S), int(rng.integers(0, 3))
+        shape = rect_shape(a["rect"], S)
+        # host memory: one map or two; device memory: constants alone, or maps there
+        maps = int(rng.integers(1, 3)) if form == "host" else int(rng.integers(0, 3))
+        which = (0, 1) if maps == 2 else (int(rng.integers(0, 2)),) if maps == 1 else ()
+        lo, hi = int(rng.integers(-2, S // 2 + 1)), int(rng.integers(S // 2, S + 3))
+        bounds = [rng.integers(-3, S + 4, shape).astype(np.int32) if k in which else c for k, c in enumerate((lo, hi))]
+        a["lo"], a["hi"], a["maps"] = bounds[0], bounds[1], maps
+    elif family in ("selectColumnsDst", "selectColumnsSrc"):
+        a["direction"], a["of"], a["op"] = int(rng.integers(0, 6)), int(rng.choice([columns_model.SOLID, columns_model.EMPTY, columns_model.BOTH])), int(rng.integers(0, 3))
+        a["lo"] = int(rng.integers(0, max(2, S // 4)))
+        a["hi"] = (a["lo"], a["lo"] + 1, a["lo"] + int(rng.integers(1, S)), S + 1 + int(rng.integers(1, 9)))[int(rng.integers(0, 4))]
     elif family == "xorMesh":
         a["kind"] = ("box", "box", "mixed", "clipped")[int(rng.integers(0, 4))]
         lo, size = _box(rng, S)
@@ -568,15 +701,16 @@ def _arguments(rng, family, form, m, op=None):
 
 
 _FORMS_OF = {
-    **{f: FORMS for f in LIST_EDITS + ("getVoxels", "countBoxes", "surface", "rects")},
+    **{f: FORMS for f in LIST_EDITS + ("getVoxels", "countBoxes", "surface", "rects", "columnProfile", "fillColumns")},
     **{f: FORMS[1:] for f in STREAM_EDITS},
     "unpack": ("host", "dev0"), "pack": ("host", "dev0"), "select": FORMS,
 }
 
 
 OPS_OF = {"copyRegion": (REPLACE, OR, ANDNOT), "stampAffine": (REPLACE, OR, ANDNOT), "fillRandom": (REPLACE, OR, ANDNOT),
-          "select": (REPLACE, OR, ANDNOT), "place": (OR, ANDNOT)}
-ALL_FORMS = LIST_EDITS + ("getVoxels", "countBoxes", "surface", "rects")
+          "select": (REPLACE, OR, ANDNOT), "place": (OR, ANDNOT), "rasterMesh": (TOUCHED, THIN), "fillColumns": (REPLACE, OR, ANDNOT),
+          "selectColumnsDst": (REPLACE, OR, ANDNOT), "selectColumnsSrc": (REPLACE, OR, ANDNOT)}
+ALL_FORMS = LIST_EDITS + ("getVoxels", "countBoxes", "surface", "rects", "columnProfile", "fillColumns")
 # (family, op, form) for every family, every op of the families that take one and every form of the list calls (None: any
 # form): the tour that every depth's programs run in full
 TOUR = tuple((family, op, form) for family in FAMILIES for op in OPS_OF.get(family, (None,)) for form in (FORMS if family in ALL_FORMS else (None,)))
@@ -595,7 +729,7 @@ def _circuit(nodes):
     return tuple(reversed(walk))
 
 
-STAGE_WALK = _circuit(BLOCKS["d_stage"])          # 81 pairs
+STAGE_WALK = _circuit(BLOCKS["d_stage"])          # 144 pairs
 PACK_WALK = _circuit(BLOCKS["d_pack"])            # 16 pairs
 
 
@@ -646,7 +780,8 @@ class _Writer:
         s = self.m.s
         if pad and family in EDITS and not s["v"].any():                  # an emptied volume shows nothing of a clearing op
             self.emit(("fillRandom", "dev0", dict(seed=int(self.rng.integers(0, 1 << 32)), threshold=cells_model.threshold_of(0.4), box=None, op=OR)))
-        if pad and family in ("copyRegion", "stampAffine", "cellStepDst", "floodRegion") and not s["w"].any():
+        if pad and family in ("copyRegion", "stampAffine", "cellStepDst", "floodRegion", "selectColumnsDst") and s["w"].mean() < 1 / 16:
+            # (nearly) empty, as a narrow selectColumnsSrc band leaves it: nothing to copy, stamp or select from
             self.emit(("recreateSecond", "host", dict(seed=int(self.rng.integers(0, 1 << 32)), threshold=cells_model.threshold_of(0.4))))
         if family in ("select", "place") and (s["ids"] is None or not (s["ids"] != components_model.NO_COMPONENT).any()):
             self.solid(1)
@@ -721,6 +856,34 @@ def _scripted(w):
     w.emit(("surface", "devB", dict(closed=False, first=2, capacity=60, order="count_first")))
     w.emit(("rects", "devB", dict(closed=True, first=0, capacity=60, order="extract_first")))
     w.emit(("rects", "devA", dict(closed=False, first=2, capacity=60, order="count_first")))
+    # the capsule brush, the surface voxelisation and the column calls on the same long-lived pair
+    Q = min(S, 5)
+    capsules = np.array([[i % S, 0, 0, i % S, S - 1, i % Q, i % 2, 0] for i in range(10)], np.int32)
+    U64 = raster_model.UNIT
+    sheet = np.array([[0, 0, U64 + 7, S * U64, 0, U64 + 7, 0, S * U64, U64 + 7]], np.int32)           # half of the plane z = 1 + 7/64
+    one = np.full((3, Q), S // 2, np.int32)
+    for step in (
+        ("fillCapsules", "host", dict(items=capsules, solid=True)),                                       # 320 bytes of staging ...
+        ("columnProfile", "host", dict(direction=5, rect=[0, 0, 3, Q])),                                  # ... then 16 x 3 x Q of records out
+        ("fillColumns", "host", dict(axis=1, rect=[0, 0, 3, Q], op=REPLACE, lo=0, hi=one, maps=1)),       # one map ...
+        ("fillColumns", "host", dict(axis=1, rect=[0, 0, 3, Q], op=OR, lo=one - 1, hi=one + 1, maps=2)),  # ... then two
+        ("refuseRaster", "host", {}),
+        ("rasterMesh", "host", dict(kind="small", op=TOUCHED, items=sheet, solid=False)),
+        ("rasterMesh", "devB", dict(kind="clipped", op=THIN, items=clipped_raster_triangles(S), solid=True)),
+        ("rasterMesh", "host", dict(kind="small", op=THIN, items=sheet, solid=True)),
+        ("refuseStroke", "host", {}),
+        ("strokeAtHits", "devA", dict(hits=hits_of(many[:6] + [0, 1, 0], S), radius=1, max_gap=0, solid=False, then=None)),
+        ("fillCapsules", "host", dict(items=capsules[:2], solid=True)),                                   # a host staging call behind the stroke
+    ):
+        w.emit(step)
+    # inside ONE step: the stroke's kernel reads centre i and i + 1 in the staging block while, right behind it, a host-memory
+    # list edit comes to rewrite the block's head -- with four far corners, which as centres would join up along the edges --
+    # and a host-memory query of exactly the voxels the stroke digs
+    corners = np.array([[0, 0, 0], [S - 1, S - 1, 0], [0, S - 1, S - 1], [S - 1, 0, S - 1]], np.uint32)
+    w.emit(("fillBoxes", "host", dict(items=np.array([[0, 0, 0, S, S, 1], [0, S - 1, 0, S, S, S]], np.uint32), solid=False)))
+    w.emit(("strokeAtHits", "devB", dict(hits=hits_of(w.solid(9), S, miss_every=10), radius=0, max_gap=0, solid=True, then=("setVoxels", corners))))
+    dug = w.solid(9)
+    w.emit(("strokeAtHits", "devA", dict(hits=hits_of(dug, S, miss_every=10), radius=0, max_gap=0, solid=False, then=("getVoxels", dug[1:]))))
 
 
 def _generate(seed, depth, steps):
