@@ -40,6 +40,21 @@ class Machine:
         self.kept.append(t)
         return t
 
+    def guarded(self, n_words):
+        """an output buffer of the test's own, every 32-bit word of it the guard"""
+        import torch
+        t = torch.full((n_words,), P.GUARD, dtype=torch.int32, device="cuda").view(torch.uint8)
+        torch.cuda.synchronize()
+        self.kept.append(t)
+        return t
+
+    def window(self, t, form, skew, per, n):
+        """the n records of `per` words that begin `skew` bytes into a guarded buffer; every word around them is still the guard"""
+        words = self.down(t, form, np.uint32, t.numel() // 4)
+        at = skew // 4
+        assert np.all(words[:at] == P.GUARD) and np.all(words[at + per * n:] == P.GUARD), "the guard around the window was written"
+        return words[at:at + per * n].reshape(n, per).copy()
+
     def down(self, t, form, dtype, n):
         if self.streams[form] is not None:
             self.L.vrc_stream_synchronize(0, self.streams[form])
@@ -178,7 +193,12 @@ class Machine:
             if host:
                 return count(a["closed"]), window(a["closed"], a["first"], a["capacity"])
             t, total = self.out(16 * a["capacity"]), self.out(8)
-            if a.get("order") == "extract_first":
+            if a.get("order") == "voxels_behind":
+                # the same, with a voxelCount behind the extraction: it rewrites the offsets block the two families share
+                q = a["behind"]
+                extract(capi.VRC_SURFACE_FACES, a["first"], a["capacity"], t.data_ptr(), total.data_ptr(), a["closed"], st)
+                counts = v.voxelCount(q["op"], q["box"], q["closed"])
+            elif a.get("order") == "extract_first":
                 # nothing between the two calls: the extraction is still on its stream when the count of the OTHER `closed`,
                 # synchronous on the NULL stream, comes to rewrite the block they share
                 extract(capi.VRC_SURFACE_FACES, a["first"], a["capacity"], t.data_ptr(), total.data_ptr(), a["closed"], st)
@@ -189,6 +209,29 @@ class Machine:
             T = int(self.down(total, form, np.uint64, 1)[0])
             n = max(0, min(a["capacity"], T - a["first"]))
             return counts, self.down(t, form, np.uint32, 4 * n).reshape(n, 4), T
+        elif family == "voxels":
+            if host:
+                return v.voxelCount(a["op"], a["box"], a["closed"]), v.voxels(a["op"], a["box"], a["neighbours"], a["closed"], a["first"], a["capacity"])
+            fmt, per = (capi.VRC_VOXELS_NEIGHBOURS, 4) if a["neighbours"] else (capi.VRC_VOXELS_XYZ, 3)
+            t, total = self.guarded(a["skew"] // 4 + per * a["capacity"] + 8), self.out(8)
+            args = (a["op"], fmt, a["first"], a["capacity"], t.data_ptr() + a["skew"], total.data_ptr(), a["box"], a["closed"], st)
+            if a["order"] == "count_first":
+                counts = v.voxelCount(a["op"], a["box"], a["closed"])
+                v.extractVoxelsDevice(*args)
+            else:
+                # nothing between the two calls: the extraction is still on its stream when a synchronous count on the NULL stream
+                # -- of another `which`, or the surface calls' -- comes to the block they all share
+                v.extractVoxelsDevice(*args)
+                counts = v.voxelCount((a["op"] + a["shift"]) % 3, a["box"], a["closed"]) if a["order"] == "extract_first" else v.surfaceCount(a["closed"])
+            T = int(self.down(total, form, np.uint64, 1)[0])
+            return counts, self.window(t, form, a["skew"], per, P.window_of(a["first"], a["capacity"], T)), T
+        elif family == "listToSecond":
+            # extraction and setVoxelsDevice on ONE stream; the list never visits the host, its length is the mirror's
+            n = a["n"]
+            t = self.guarded(3 * n + 8)
+            v.extractVoxelsDevice(a["which"], capi.VRC_VOXELS_XYZ, 0, n, t.data_ptr(), None, a["box"], a["closed"], st)
+            w.setVoxelsDevice(n, t.data_ptr(), a["solid"], st)
+            self.window(t, form, 0, 3, n)
         elif family == "pack":
             packed = v.pack(device=not host)
             self.stream = bytes(packed.tobytes() if host else packed.cpu().numpy().tobytes())
@@ -244,6 +287,13 @@ class Machine:
             return self.refused(lambda: v.selectColumns(0, 0, 1, 1, v))
         elif family == "refuseSelectDepth":
             return self.refused(lambda: self.other.selectColumns(0, 0, 1, 1, v))
+        elif family == "refuseVoxels":
+            return self.refused(lambda: v.voxelCount(3))
+        elif family == "refuseVoxelsAligned":
+            t = self.guarded(16)
+            out = self.refused(lambda: v.extractVoxelsDevice(0, capi.VRC_VOXELS_NEIGHBOURS, 0, 2, t.data_ptr() + 8, None))
+            self.window(t, "dev0", 0, 4, 0)                           # refused, and not written
+            return out
         elif family == "cloneSecond":
             w.close()
             self.w = v.clone()

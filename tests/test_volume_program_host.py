@@ -19,6 +19,7 @@ import stroke_model
 import surface_model
 import volume_program as P
 import voxelize_model
+import voxels_model
 
 
 def field(S, seed, density=0.4):
@@ -144,11 +145,33 @@ def test_one_step_is_the_family_model():
                     other = form != "host" and a["order"] == "extract_first"        # the count of the other `closed` in between
                     want = (surface_model.direction_counts(surface_model.faces(v, not a["closed"]) if other else f),
                             f[a["first"]:a["first"] + a["capacity"]]) + (() if form == "host" else (len(f),))
+                    if form != "host" and a["order"] == "voxels_behind":            # or a voxelCount, whose result the step carries
+                        q = a["behind"]
+                        want = (len(voxels_model.brute(v.tolist(), q["op"], q["box"], q["closed"])),) + want[1:]
                 elif family == "rects":
                     r = rect_model.rects(v, a["closed"])
                     other = form != "host" and a["order"] == "extract_first"
                     want = (rect_model.direction_counts(rect_model.rects(v, not a["closed"]) if other else r),
                             r[a["first"]:a["first"] + a["capacity"]]) + (() if form == "host" else (len(r),))
+                elif family == "voxels":
+                    # the triple loop, not the dense model the mirror uses; the six surface totals are the cleared face bits
+                    # of the SURFACE masks of the whole volume (vrc.h:428-429), from the same loop
+                    b = voxels_model.brute(v.tolist(), a["op"], a["box"], a["closed"])
+                    listed = np.ascontiguousarray(b if a["neighbours"] else b[:, :3])
+                    window = listed[a["first"]:a["first"] + a["capacity"]]
+                    if form == "host":
+                        want = (len(b), window)
+                    else:
+                        assert a["skew"] in (0, 4) and not (a["skew"] and a["neighbours"])
+                        behind = {"count_first": lambda: len(b),
+                                  "extract_first": lambda: len(voxels_model.brute(v.tolist(), (a["op"] + a["shift"]) % 3, a["box"], a["closed"])),
+                                  "surface_behind": lambda: voxels_model.cleared_face_bits(voxels_model.brute(v.tolist(), voxels_model.SURFACE, None, a["closed"]))}
+                        want = (behind[a["order"]](), window, len(b))
+                elif family == "listToSecond":
+                    want_w = w.copy()
+                    for x, y, z, _ in voxels_model.brute(v.tolist(), a["which"], a["box"], a["closed"]).tolist():
+                        want_w[x, y, z] = value
+                    assert a["n"] == len(voxels_model.brute(v.tolist(), a["which"], a["box"], a["closed"]))
                 elif family == "pack":
                     want = pack_model.pack(v, depth)
                 elif family == "diff":
@@ -196,6 +219,16 @@ def test_one_step_refusals_lifetime_and_the_call_behind_a_brush():
         if family == "refuseUnpack":
             a = P._arguments(rng, family, "host", m)
             assert pack_model.unpack(a["data"], depth)[0] == a["rule"]                 # the model refuses it, by that rule
+    # a refused voxel call on a volume that has seen no surface or voxel call reserves no offsets block; the first real one does
+    m = P.Mirror(depth)
+    for family in ("refuseVoxels", "refuseVoxelsAligned"):
+        assert m.apply((family, "host", {})) == "refused" and m.scratch_bytes() == 0 and not m.s["blocks_v"]
+    m.apply(("voxels", "dev0", dict(op=0, box=None, closed=True, neighbours=False, first=0, capacity=4, skew=0, order="count_first", shift=1)))
+    assert m.scratch_bytes() == P.surface_bytes(depth)
+    for seed, deep in P.COMMITTED:
+        steps = P.program(seed, deep)
+        first = min(i for i, s in enumerate(steps) if s[0] in P.BLOCKS["d_surface"])
+        assert {"refuseVoxels", "refuseVoxelsAligned"} <= {s[0] for s in steps[:first]}, (seed, deep)
     m = primed(depth)
     v, w = m.s["v"], m.s["w"]
     m.apply(("floodMedium", "host", dict(connectivity=6, through_empty=False)))        # w gains a flood block
@@ -302,6 +335,36 @@ def test_coverage_of_the_committed_seeds():
         for i, s in enumerate(steps):
             if s[0] in P.OWN_BLOCK + ("selectColumnsDst", "selectColumnsSrc") and i:
                 assert seen[i][3:5] == seen[i - 1][3:5], (seed, depth, i)
+        # inside one step, in the offsets block the voxel lists share with the surface calls: a voxel extraction on a stream
+        # with the voxelCount of another `which` behind it, one with a surfaceCount behind it, and a surface extraction with a
+        # voxelCount behind it -- each count another number than the total of the extraction it follows, so that offsets gone
+        # stale show in the step's own result
+        streams = [(s, o[0]) for s, o in zip(steps, seen) if s[1] in ("devA", "devB") and s[0] in ("voxels", "surface")]
+        assert any(s[0] == "voxels" and s[2]["order"] == "extract_first" and own[0] != own[2] for s, own in streams), (seed, depth)
+        assert any(s[0] == "voxels" and s[2]["order"] == "surface_behind" and int(own[0].sum()) != own[2] > 0 for s, own in streams), (seed, depth)
+        assert any(s[0] == "surface" and s[2]["order"] == "voxels_behind" and own[0] != own[2] and own[0] > 0 for s, own in streams), (seed, depth)
+        # the host windows of the lists in the staging block: one directly behind a larger host list edit, one that grows the
+        # block to exactly record * window, and an empty window (of a list that is not empty) that leaves the block alone
+        def window_bytes(i):
+            a, own = steps[i][2], seen[i][0]
+            return (16 if a["neighbours"] else 12) * P.window_of(a["first"], a["capacity"], own[0])
+        def prev_bytes(i):                                       # what a host list edit staged as the step before, else 0
+            family, form, a = steps[i - 1]
+            if family not in P.ITEM_BYTES or family not in P.EDITS or form != "host":
+                return 0
+            return P.ITEM_BYTES[family] * len(a["items" if "items" in a else "tris"])
+        lists = [i for i, s in enumerate(steps) if s[0] == "voxels" and s[1] == "host" and i]
+        for i in lists:
+            assert window_bytes(i) == seen[i][0][1].nbytes, (seed, depth, i)
+        assert any(0 < window_bytes(i) < prev_bytes(i) for i in lists), (seed, depth)
+        grew = [i for i in lists if seen[i][6] == window_bytes(i) > seen[i - 1][6]]               # the block is now exactly the window
+        assert any(seen[i][3] - seen[i - 1][3] == window_bytes(i) - seen[i - 1][6] for i in grew), (seed, depth)
+        empty = [i for i in lists if window_bytes(i) == 0 < seen[i][0][0]]
+        assert any(seen[i][6] == seen[i - 1][6] > 0 and seen[i][3] == seen[i - 1][3] for i in empty), (seed, depth)
+        # the list of v into w on a stream, directly behind an edit of v on the other stream, and directly behind a surface step
+        assert any(a[0] in P.EDITS and a[0] not in P.EDITS_OF_W and {a[1], b[1]} == {"devA", "devB"} and b[0] == "listToSecond" and seen[i][5]
+                   for i, (a, b) in enumerate(adjacent(steps))), (seed, depth)
+        assert any(a[0] == "surface" and b[0] == "listToSecond" for a, b in adjacent(steps)), (seed, depth)
     assert set(P.shared_pairs()) <= covered, sorted(set(P.shared_pairs()) - covered)
     assert {("d_stage", a, b) for a in ("fillCapsules", "strokeAtHits", "rasterMesh") for b in P.BLOCKS["d_stage"]} <= covered
     for form in P.FORMS[1:]:                                    # the stream-only edits: each stream occurs among them
@@ -316,6 +379,20 @@ def test_coverage_of_the_committed_seeds():
         changed = {(s[0], s[2].get("op")) for seed in P.SEEDS[depth] for s, o in zip(P.program(seed, depth), P.run_committed(seed, depth)) if o[5]}
         idle = {(f, op) for f, op, _ in P.TOUR if f in P.EDITS} - changed
         assert not idle, (depth, idle)                          # and each edit, with each op, changes a voxel there at least once
+        # the voxel lists: both record formats for each `which`, every kind of box, an output that is 4- but not 8-byte aligned
+        lists = [s for s in steps if s[0] == "voxels"]
+        assert {(which, nb) for which in range(3) for nb in (False, True)} <= {(s[2]["op"], s[2]["neighbours"]) for s in lists}, depth
+        assert set(P.BOX_KINDS) <= {s[2]["kind"] for s in lists}, depth
+        assert any(s[1] != "host" and s[2]["skew"] == 4 for s in lists), depth
+        for s in lists:
+            box, S = s[2]["box"], 1 << depth
+            if s[2]["kind"] == "cut":                           # words cut on all three axes
+                assert all(q % 2 == 1 for q in box[0:2] + box[3:5]) and box[2] % 8 and box[5] % 8 and all(0 < l < h < S for l, h in zip(box[:3], box[3:])), box
+            assert s[2]["kind"] != "beyond" or all(h > S for h in box[3:])
+            assert s[2]["kind"] != "empty" or voxels_model.clipped(box, S) is None
+            assert s[2]["kind"] != "whole" or box in (None, [0, 0, 0, S, S, S])
+    assert {("d_surface", a, b) for a in P.BLOCKS["d_surface"] for b in P.BLOCKS["d_surface"]} <= covered
+    assert {("d_stage", a, b) for a in P.BLOCKS["d_stage"] for b in P.BLOCKS["d_stage"] if "voxels" in (a, b)} <= covered
 
 
 @pytest.mark.parametrize("seed,depth", P.COMMITTED)
@@ -341,7 +418,14 @@ def test_every_fault_is_visible(seed, fault):
     if fault == "unordered":
         # not through the download alone: the query behind a brush and the extraction under a count see it themselves
         own = {s[0] for s, g, b in zip(P.program(seed, 5), good, bad) if not P.same_value(g[0], b[0])}
-        assert {"fillSpheresAtHits", "strokeAtHits", "surface", "rects"} <= own, (seed, own)
+        assert {"fillSpheresAtHits", "strokeAtHits", "surface", "rects", "voxels"} <= own, (seed, own)
+        # the surface extraction by both counts that may come behind it: its own family's, and the voxel lists'
+        orders = {s[2].get("order") for s, g, b in zip(P.program(seed, 5), good, bad) if s[0] == "surface" and not P.same_value(g[0], b[0])}
+        assert {"extract_first", "voxels_behind"} <= orders, (seed, orders)
+    if fault == "totals":
+        # a host window of the lists, by itself, and nothing before it
+        first = next(s for s, g, b in zip(P.program(seed, 5), good, bad) if not P.same_value(g[:5], b[:5]))
+        assert first[0] == "voxels" and first[1] == "host", (seed, first[:2])
     if fault == "links":
         # the stroke itself went wrong, not a call behind it: the first step that differs is a stroke with a list edit behind it
         first = next(s for s, g, b in zip(P.program(seed, 5), good, bad) if not P.same_value(g[:5], b[:5]))
@@ -383,6 +467,24 @@ def test_faults_show_through_the_new_families():
     assert visible(edit, "links") and not visible([("strokeAtHits", "host", dict(stroke, then=None))], "links")
     good, bad = seen(edit, None)[0][1], seen(edit, "links")[0][1]
     assert (bad & (1 - good)).any()                                       # the first centres, rewritten, were never dug
+    # the offsets block of the lists and the surface calls.  A count behind an extraction that did not wait: the extraction
+    # emits by the count's offsets -- the step's own records differ; only the surfaceCount, which writes six slots that no
+    # list reads, cannot show
+    def lists(form, op, box, capacity=300, neighbours=False, first=0, **more):
+        return ("voxels", form, dict(op=op, box=box, closed=True, neighbours=neighbours, first=first, capacity=capacity, skew=0, shift=1, **more))
+    # (32^3 is four workgroups of x: the first window spans the end of the first, the second lies in one the count left empty)
+    for step in (lists("devA", P.voxels_model.ALL, None, first=int(start[:8].sum()) - 150, order="extract_first"),
+                 ("surface", "devB", dict(closed=True, first=0, capacity=300, order="voxels_behind", behind=dict(op=1, box=[9, 1, 1, 31, 31, 17], closed=True)))):
+        good, bad = seen([step], None)[0][0], seen([step], "unordered")[0][0]
+        assert good[0] == bad[0] and good[2] == bad[2] and good[1].shape == bad[1].shape and not np.array_equal(good[1], bad[1]), step[:2]
+    assert not visible([lists("devA", P.voxels_model.ALL, None, order="count_first")], "unordered")
+    assert not visible([lists("devA", P.voxels_model.ALL, None, order="surface_behind")], "unordered")
+    # a host window sized by the total the block still held: a list with a large total, then one of a small box
+    pair = [lists("host", P.voxels_model.ALL, None), lists("host", P.voxels_model.SURFACE, [3, 5, 3, 6, 8, 5], neighbours=True)]
+    good, bad = seen(pair, None), seen(pair, "totals")
+    assert P.same_value(good[0], bad[0]) and good[1][0][0] == bad[1][0][0] < 300
+    assert len(bad[1][0][1]) == 300 > len(good[1][0][1]) and bad[1][2] - good[1][2] == 16 * 300 - 12 * 300       # and the staging block with it
+    assert not visible(pair[:1], "totals") and not visible([pair[1], pair[1]], "totals")
 
 
 def test_scratch_sizes_restate_the_per_family_tests():
@@ -417,3 +519,15 @@ def test_scratch_sizes_restate_the_per_family_tests():
     assert m.scratch_bytes() == 16 * 21
     m.apply(("strokeAtHits", "host", dict(hits=hits, radius=1, max_gap=0, solid=True, then=None)))
     assert m.scratch_bytes() == 64 * 21
+    # tests/test_gpu_volume_voxels.py: offsets_bytes (the surface calls' block, counted once) and :250 (record * window, bounded by
+    # 2^20 records); a device-form list and the list into w stage nothing, an empty window reserves nothing
+    m = P.Mirror(5)
+    m.s["v"] = field(32, 5)
+    T = int(m.s["v"].sum())
+    for form, a in (("devA", dict(first=0, capacity=T)), ("host", dict(first=T, capacity=9)), ("host", dict(first=T - 7, capacity=9)), ("host", dict(first=0, capacity=5))):
+        m.apply(("voxels", form, dict(a, op=0, box=None, closed=True, neighbours=form == "host", skew=0, order="count_first", shift=1)))
+        assert m.scratch_bytes() == P.surface_bytes(5) + (16 * 7 if a["first"] == T - 7 or a["capacity"] == 5 else 0)
+    m.apply(("listToSecond", "devB", dict(which=0, box=None, closed=True, solid=True, n=T)))
+    m.apply(("surface", "host", dict(closed=True, first=0, capacity=0)))
+    assert m.scratch_bytes() == P.surface_bytes(5) + 16 * 7 and m.scratch_bytes("w") == 0
+    assert P.surface_bytes(5) == 8 * (4 + 7) and P.window_of(3, 1 << 40, 10) == 7 and P.window_of(11, 5, 10) == 0

@@ -2,7 +2,7 @@
 tests/test_gpu_volume_program.py runs on the device and tests/test_volume_program_host.py holds to its purpose on the CPU.
 numpy and Python integers only; every expected value comes from the model the family's own tests use (stamp_model,
 flood_model, cells_model, delta_model, pack_model, voxelize_model, surface_model, rect_model, components_model,
-distance_model, fall_model, stroke_model, raster_model, columns_model); the sphere predicate is vrc.h:208-210 taken literally,
+distance_model, fall_model, stroke_model, raster_model, columns_model, voxels_model); the sphere predicate is vrc.h:208-210 taken literally,
 as the brushes' tests take it.
 
 A step is (family, form, arguments): a plain record.  `v` is the program's volume, `w` the second one.
@@ -10,7 +10,8 @@ A step is (family, form, arguments): a plain record.  `v` is the program's volum
 Forms: "host" = host memory (synchronous); "dev0" = device memory on the NULL stream; "devA" / "devB" = device memory on
 the first / second stream of the test's own.  A family without a memory kind (copyRegion, stampAffine, fillRandom,
 applyDelta, cellStep, selectColumns) takes only the stream from its form.  rasterMesh keeps its mode under the key "op", so
-that the tour takes both modes as it takes every op.
+that the tour takes both modes as it takes every op; voxels keeps its `which` there for the same reason.  listToSecond (the
+x y z list of `v` extracted into device memory and set in `w` from there, on one stream) has no host form at all.
 
 ORDERING says, per combination of a call with what may still be in flight, who orders it.  The GPU test downloads both
 volumes after EVERY step, and vrc_volume_download is "synchronous, after every edit issued so far" (vrc.h:191-192), so
@@ -19,20 +20,25 @@ vrc.h:178-179 asks of a caller ("issue a volume's asynchronous edits on ONE stre
 combinations INSIDE a step are the library's to order: the download right behind a device-memory edit (vrc.h:191-192), the
 host-memory list call or query that a brush or a stroke at hits carries in its `then` argument (vrc.h:205-206, 219-220 and,
 for the stroke, 249-250: the centres lie in the staging block, in flight on the caller's stream, and the stroke's kernel
-reads centre i and i + 1 there), and the synchronous surface / rectangle count issued while a
-device-memory extraction of the same step is still on its stream (order "extract_first"; vrc.h:271-272, 315-316).
+reads centre i and i + 1 there), and the synchronous surface / rectangle / voxel count issued while a
+device-memory extraction of the same step is still on its stream (order "extract_first"; vrc.h:350-351, 394-395, 444-447).
+The voxel lists keep no block of their own: they use the surface calls' offsets block (vrc.h:454-455), so a count of EITHER
+family behind an extraction of the other is the library's to order as well (orders "surface_behind", "voxels_behind").
 
 Sizes of the per-volume scratch blocks (Mirror.scratch_bytes), each restated with the line it was read off:
   staging, host form   12 n set_voxels (vrc_volume.hip:429), 24 n fill_boxes (:445), 16 n fill_spheres (:462),
                        64 n brush at hits, 16 n in device form (:484), 36 n xor_mesh (:517), 13 n get_voxels (:603),
                        32 n count_boxes (:619), 16 per face / rectangle of a host window (:697, :724),
                        32 n fill_capsules (vrc_volume.hip:511), 64 n stroke at hits, 16 n in device form (:533),
-                       36 n raster_mesh (:560)
+                       36 n raster_mesh (:560),
+                       record * min(window, 2^20) of a host voxel list, record = 12 (x y z) or 16 (x y z m) and
+                       window = window_of(first, capacity, T); nothing where the window is empty (vrc_volume.hip:786-788)
   column calls         nothing: the 16 U V records of a host profile and the 4 U V bytes of each host map of a fill are
                        staged in a block of the call's own (vrc.h:1329-1330; vrc_snapshots.hip:82 gives these calls
                        stage_in_v = false, :896 and :915 size the parts), and select stages nothing (:937-941)
   mark field           8^(depth-1) (vrc_voxelize.hip:145)
-  surface offsets      8 (ceil(8^depth / 32 / 256) + 7) (vrc_surface.hip:211-221)
+  surface offsets      8 (ceil(8^depth / 32 / 256) + 7) (vrc_surface.hip:145); the voxel lists use the same block and add
+                       nothing (vrc_volume.hip:838-841); a refused voxel call reserves nothing (:871-873 come before :875)
   rectangle block      8 (ceil(6 S^2 w / 256) + 7) + 8 S^2 w, w = max(1, S / 32) (vrc_rects.hip:258-282)
   pack slots           64 + 8 (tiles + 1) (vrc_pack.hip:354)
   flood block          4 (3 T^3 + 8), T = max(1, S / 32) (vrc_flood.hip:186-190), on the REGION
@@ -55,6 +61,7 @@ import stamp_model
 import stroke_model
 import surface_model
 import voxelize_model
+import voxels_model
 
 REPLACE, OR, ANDNOT = 0, 1, 2
 TOUCHED, THIN = raster_model.TOUCHED, raster_model.THIN
@@ -64,7 +71,8 @@ HIT_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("voxel_coor
 
 DEPTHS = (2, 3, 5, 6)
 SEEDS = {2: (21, 22, 23), 3: (31, 32, 33), 5: (51, 52, 53), 6: (61, 62, 63)}
-STEPS = {2: 200, 3: 200, 5: 200, 6: 110}
+STEPS = {2: 232, 3: 232, 5: 232, 6: 130}
+GUARD = 0x5A5A5A5A                                                     # what a device buffer of the test's own holds where nothing was written
 COMMITTED = [(seed, depth) for depth in DEPTHS for seed in SEEDS[depth]]
 
 ORDERING = {
@@ -72,17 +80,22 @@ ORDERING = {
     ("download", "device-memory edit of the same step"): ("library", "vrc.h:191-192"),
     ("then: host list call / query", "brush at hits of the same step"): ("library", "vrc.h:205-206, 219-220"),
     ("then: host list call / query", "stroke at hits of the same step, its kernel reading centres i and i + 1"): ("library", "vrc.h:249-250"),
-    ("surface / rect count", "device-memory extraction of the same step (order extract_first)"): ("library", "vrc.h:271-272, 315-316"),
+    ("surface / rect count", "device-memory extraction of the same step (order extract_first)"): ("library", "vrc.h:350-351, 394-395"),
+    ("voxel count of another which", "device-memory voxel extraction of the same step (order extract_first)"): ("library", "vrc.h:444-447"),
+    ("surface count", "device-memory voxel extraction of the same step, in the block they share (order surface_behind)"): ("library", "vrc.h:350-351, 444-447, 454-455"),
+    ("voxel count", "device-memory surface extraction of the same step, in the block they share (order voxels_behind)"): ("library", "vrc.h:350-351, 444-447, 454-455"),
+    ("setVoxelsDevice into w", "device-memory voxel extraction from v of the same step, on the same stream (listToSecond)"): ("caller: one stream", "vrc.h:439-440"),
+    ("listToSecond on one stream", "an edit of v of the step before, on the other stream"): ("program: the download between the steps", "vrc.h:178-179, 191-192"),
     ("any call", "an edit of an earlier step, on any stream"): ("program: the download between the steps", "vrc.h:178-179, 191-192"),
 }
 
 LIST_EDITS = ("setVoxels", "fillBoxes", "fillSpheres", "fillSpheresAtHits", "xorMesh", "fillCapsules", "strokeAtHits", "rasterMesh")
 STREAM_EDITS = ("copyRegion", "stampAffine", "fillRandom", "applyDelta", "cellStepDst", "cellStepSrc", "selectColumnsDst", "selectColumnsSrc")
-OTHER_EDITS = ("unpack", "floodRegion", "floodMedium", "keepConnected", "dilate", "erode", "select", "place", "fillColumns")
+OTHER_EDITS = ("unpack", "floodRegion", "floodMedium", "keepConnected", "dilate", "erode", "select", "place", "fillColumns", "listToSecond")
 EDITS = LIST_EDITS + STREAM_EDITS + OTHER_EDITS
-QUERIES = ("solidCount", "getVoxels", "countBoxes", "surface", "rects", "pack", "diff", "components", "distanceAt", "commit", "columnProfile")
+QUERIES = ("solidCount", "getVoxels", "countBoxes", "surface", "rects", "pack", "diff", "components", "distanceAt", "commit", "columnProfile", "voxels")
 REFUSALS = ("refuseOp", "refusePack", "refuseUnpack", "refuseDelta", "refuseDepth", "refuseMesh", "refuseRaster", "refuseStroke", "refuseProfile",
-            "refuseFillAxis", "refuseSelect", "refuseSelectSame", "refuseSelectDepth")
+            "refuseFillAxis", "refuseSelect", "refuseSelectSame", "refuseSelectDepth", "refuseVoxels", "refuseVoxelsAligned")
 AT_HITS = ("fillSpheresAtHits", "strokeAtHits")                       # the centres pass through the staging block in every form
 LIFETIME = ("cloneSecond", "recreateSecond", "snapshotLabels", "snapshotClone")
 FAMILIES = EDITS + QUERIES + REFUSALS + LIFETIME
@@ -90,10 +103,10 @@ FAMILIES = EDITS + QUERIES + REFUSALS + LIFETIME
 # the families that share a persistent block of `v` (vrc_volume_state.h:15-46); d_stage: in a form that stages
 BLOCKS = {
     "d_stage": ("setVoxels", "fillBoxes", "fillSpheres", "fillSpheresAtHits", "xorMesh", "getVoxels", "countBoxes", "surface", "rects",
-                "fillCapsules", "strokeAtHits", "rasterMesh"),
+                "fillCapsules", "strokeAtHits", "rasterMesh", "voxels"),
     "d_marks": ("xorMesh",),
     "d_flood": ("floodRegion",),
-    "d_surface": ("surface",),
+    "d_surface": ("surface", "voxels", "listToSecond"),
     "d_rects": ("rects",),
     "d_pack": ("pack", "unpack", "refusePack", "refuseUnpack"),
     "grids": ("commit",),
@@ -101,7 +114,8 @@ BLOCKS = {
 }
 # the host forms of these stage in a block of the call's own (vrc.h:1329-1330): they sit next to the users of d_stage, and leave it alone
 OWN_BLOCK = ("columnProfile", "fillColumns")
-FAULTS = ("marks", "stage_tail", "rows", "commit", "unordered", "links")
+FAULTS = ("marks", "stage_tail", "rows", "commit", "unordered", "links", "totals")
+EDITS_OF_W = ("floodMedium", "cellStepSrc", "selectColumnsSrc", "listToSecond")
 
 
 def stages(step):
@@ -204,6 +218,50 @@ def get_voxels(vol, items):
     return out
 
 
+def window_of(first, capacity, T):
+    """how many records of a list of T the window [first, first + capacity) holds"""
+    return max(0, min(int(capacity), int(T) - int(first)))
+
+
+@functools.lru_cache(maxsize=256)
+def _records(model, shape, content, args):
+    out = model(np.frombuffer(content, np.uint8).reshape(shape), *args)
+    out.setflags(write=False)
+    return out
+
+
+def once(model, vol, *args):
+    """model(vol, *args) of a family's model that lists records, computed once per content of the volume: a test runs a mirror
+    of its own over the steps that the generator's mirror has just been through, and at 64^3 these lists are most of a
+    program's time.  The records are shared: read only"""
+    return _records(model, vol.shape, np.ascontiguousarray(vol, np.uint8).tobytes(), args)
+
+
+def voxel_list(vol, a, which=None, neighbours=False):
+    """the list a voxels / listToSecond step names, or that of another `which` over the same box"""
+    box = None if a["box"] is None else tuple(int(q) for q in a["box"])
+    return once(voxels_model.voxels_dense, vol, a.get("op", a.get("which")) if which is None else which, box, a["closed"], neighbours)
+
+
+def stale_emit(records, offsets_of, S, first, capacity, n):
+    """the first n records of the caller's buffer after an emit pass that found ANOTHER list's offsets in the block: a
+    workgroup (256 occupancy words, key >> 13) starts where `offsets_of`'s voxels before it end, and returns early where those
+    offsets show it nothing inside the window (vrc_voxels.hip:183-185, vrc_surface.hip:117-119); what no workgroup writes keeps
+    the guard"""
+    groups = max(1, S ** 3 // 32 // 256)
+    mine = surface_model.key_of(records[:, :3], S) >> 13
+    start = np.concatenate([[0], np.cumsum(np.bincount(surface_model.key_of(offsets_of[:, :3], S) >> 13, minlength=groups))])
+    out = np.full((n, records.shape[1]), GUARD, np.uint32)
+    for g in range(groups):
+        if start[g] == start[g + 1] or start[g + 1] <= first or start[g] >= first + capacity:
+            continue
+        rows = records[mine == g]
+        at = start[g] + np.arange(len(rows)) - first
+        ok = (at >= 0) & (at < n)
+        out[at[ok]] = rows[ok]
+    return out
+
+
 def hits_of(cells, S, miss_every=5):
     """unit-voxel hit records whose vrc_hit_to_voxel voxel is `cells` (vrc.h:196-201: S-1 - floor((position - 1) S); the
     centre of the reflected cell is exact in float32 for S <= 64), normal (0, -2, 0): the neighbour is y + 1; every
@@ -300,7 +358,7 @@ class Mirror:
         S = self.S
         self.s = dict(v=np.zeros((S, S, S), np.uint8), w=np.zeros((S, S, S), np.uint8), clone=None, delta=None, stream=None, ids=None,
                       stage_v=0, blocks_v=frozenset(), stage_w=0, blocks_w=frozenset(),
-                      marks_left=False, stage_tail=b"", rows_of=None, committed=None, before_edit=None)
+                      marks_left=False, stage_tail=b"", rows_of=None, committed=None, before_edit=None, block_total=None)
         self.changed = False
 
     def save(self):
@@ -470,7 +528,7 @@ class Mirror:
             if family == "rects":
                 seen = s["rows_of"] if self.fault == "rows" and s["rows_of"] is not None else v0
                 s["rows_of"] = seen
-            model = (lambda closed: surface_model.faces(seen, closed)) if family == "surface" else (lambda closed: rect_model.rects(seen, closed))
+            model = (lambda closed: once(surface_model.faces, seen, closed)) if family == "surface" else (lambda closed: once(rect_model.rects, seen, closed))
             tally = surface_model.direction_counts if family == "surface" else rect_model.direction_counts
             records = model(a["closed"])
             first_extract = not host and a.get("order") == "extract_first"
@@ -478,10 +536,58 @@ class Mirror:
             if first_extract and self.fault == "unordered":
                 records = counted                                 # the extraction reads the offsets the count left
             window = records[a["first"]:a["first"] + a["capacity"]]
-            out = (tally(counted), window) if host else (tally(counted), window, len(records))
+            counts = tally(counted)
+            if family == "surface":
+                s["block_total"] = len(records)
+                if not host and a.get("order") == "voxels_behind":
+                    # the extraction is still on its stream when a synchronous voxelCount rewrites the offsets block, the total
+                    # behind the last slot included (vrc.h:444-447, 454-455: the count waits for the extraction)
+                    behind = voxel_list(v0, a["behind"])
+                    counts = s["block_total"] = len(behind)
+                    if self.fault == "unordered":
+                        window = stale_emit(records, behind, S, a["first"], a["capacity"], len(window))
+            out = (counts, window) if host else (counts, window, len(records))
             self._block("d_" + family)
             if host and len(window):
                 self._stage(16 * len(window))
+        elif family == "voxels":
+            # host form: voxelCount, then the window.  Device forms: (counts, window, total) with the records in a buffer of the
+            # test's own; `counts` is the step's own voxelCount issued first ("count_first"), or, issued right behind the
+            # extraction still on its stream, the voxelCount of another `which` ("extract_first") or the six totals of
+            # surfaceCount ("surface_behind"), which keeps its direction totals in the same block
+            records = voxel_list(v0, a, neighbours=a["neighbours"])
+            T = len(records)
+            n = window_of(a["first"], a["capacity"], T)
+            window = records[a["first"]:a["first"] + n]
+            total_left = T
+            if host:
+                if self.fault == "totals" and s["block_total"] is not None:
+                    # the window is sized by the total the block held on entry; what the pass does not emit stays zero
+                    n = window_of(a["first"], a["capacity"], s["block_total"])
+                    window = np.concatenate([window, np.zeros((n, window.shape[1]), np.uint32)])[:n]
+                out = (T, window)
+                if n:
+                    self._stage((16 if a["neighbours"] else 12) * min(n, 1 << 20))
+            elif a["order"] == "extract_first":
+                other = voxel_list(v0, a, (a["op"] + a["shift"]) % 3)
+                if self.fault == "unordered":
+                    window = stale_emit(records, other, S, a["first"], a["capacity"], n)
+                out = (len(other), window, T)
+                total_left = len(other)
+            elif a["order"] == "surface_behind":
+                # surfaceCount writes the six direction totals alone, behind the slot of the total (vrc_surface.hip:149-156):
+                # slots that no pass of the lists reads, so even unordered it leaves the extraction what it was
+                out = (surface_model.direction_counts(once(surface_model.faces, v0, a["closed"])), window, T)
+            else:
+                out = (T, window, T)
+            s["block_total"] = total_left
+            self._block("d_surface")
+        elif family == "listToSecond":
+            items = voxel_list(v0, a)
+            assert self.fault is not None or a["n"] == len(items)     # the length the step hands to setVoxelsDevice is the mirror's
+            s["w"] = voxels(w0, items, 1 if a["solid"] else 0)
+            s["block_total"] = len(items)
+            self._block("d_surface")
         elif family == "pack":
             s["stream"] = pack_model.pack(v0, depth)
             out = s["stream"]
@@ -513,7 +619,7 @@ class Mirror:
         else:
             raise ValueError(family)
         self.changed = not (np.array_equal(s["v"], v0) and np.array_equal(s["w"], w0))
-        if family in EDITS and not host and family not in ("floodMedium", "cellStepSrc", "selectColumnsSrc"):
+        if family in EDITS and not host and family not in EDITS_OF_W:
             s["before_edit"] = v0
         return out
 
@@ -550,6 +656,32 @@ def _rect(rng, S):
     """a non-empty rect of columns (u_lo, v_lo, u_hi, v_hi) inside the face"""
     u_lo, v_lo = int(rng.integers(0, S)), int(rng.integers(0, S))
     return [u_lo, v_lo, int(rng.integers(u_lo + 1, S + 1)), int(rng.integers(v_lo + 1, S + 1))]
+
+
+BOX_KINDS = ("whole", "cut", "beyond", "empty")
+
+
+def _voxel_box(rng, S, kind):
+    """the box of a voxel list: the whole volume (None or spelled out); one that cuts occupancy words on all three axes (odd
+    bounds in x and y, z bounds that are no multiples of 8); one reaching beyond the volume; an empty one"""
+    if kind == "whole":
+        return None if rng.random() < 0.5 else [0, 0, 0, S, S, S]
+    if kind == "cut":
+        lo = [1 + 2 * int(rng.integers(0, S // 4)), 1 + 2 * int(rng.integers(0, S // 4)), int(rng.integers(1, S // 2))]
+        hi = [S // 2 + 1 + 2 * int(rng.integers(0, S // 4)), S // 2 + 1 + 2 * int(rng.integers(0, S // 4)), int(rng.integers(S // 2 + 1, S))]
+        lo[2] += lo[2] % 8 == 0
+        hi[2] -= hi[2] % 8 == 0
+        return lo + hi
+    lo = [int(q) for q in rng.integers(0, S // 2, 3)]
+    if kind == "beyond":
+        return lo + [int(rng.choice([S + 1, S + 100, 0xFFFFFFFF])) for _ in range(3)]
+    hi = [q + 1 + int(rng.integers(0, S // 2)) for q in lo]
+    axis = int(rng.integers(0, 3))
+    if rng.random() < 0.5:
+        hi[axis] = lo[axis]                                                   # nothing between lo and hi
+    else:
+        lo[axis], hi[axis] = S + 2, S + 5                                     # wholly outside
+    return lo + hi
 
 
 def _arguments(rng, family, form, m, op=None):
@@ -676,6 +808,24 @@ def _arguments(rng, family, form, m, op=None):
     elif family in ("surface", "rects"):
         a["closed"], a["first"], a["capacity"] = bool(rng.integers(0, 2)), int(rng.integers(0, 8)), int(rng.integers(1, 400))
         a["order"] = ("count_first", "extract_first")[int(rng.integers(0, 2))]
+        if family == "surface" and rng.random() < 1 / 3:
+            # the voxelCount that rewrites the shared block right behind the extraction
+            a["order"] = "voxels_behind"
+            a["behind"] = dict(op=int(rng.integers(0, 3)), box=_voxel_box(rng, S, ("whole", "cut", "beyond")[int(rng.integers(0, 3))]), closed=bool(rng.integers(0, 2)))
+    elif family in ("voxels", "listToSecond"):
+        a["kind"] = ("whole", "whole", "cut", "cut", "beyond", "empty")[int(rng.integers(0, 6))]
+        a["box"], a["closed"] = _voxel_box(rng, S, a["kind"]), bool(rng.integers(0, 2))
+        if family == "voxels":
+            a["op"], a["neighbours"] = int(rng.integers(0, 3)), bool(rng.integers(0, 2))
+            a["first"], a["capacity"] = int(rng.integers(0, 8)), int(rng.integers(1, 400))
+            # device forms: the output 4- but not 8-byte aligned (x y z alone); what runs around the extraction; `shift`: which
+            # other `which` the count behind the extraction takes
+            a["skew"] = 0 if a["neighbours"] else 4 * int(rng.integers(0, 2))
+            a["order"] = ("count_first", "extract_first", "surface_behind")[int(rng.integers(0, 3))]
+            a["shift"] = int(rng.integers(1, 3))
+        else:
+            a["which"], a["solid"] = int(rng.integers(0, 3)), bool(rng.integers(0, 2))
+            a["n"] = len(voxel_list(s["v"], a))                               # the list's length, which the caller of setVoxelsDevice must know
     elif family in ("components", "snapshotLabels"):
         a["connectivity"] = int(rng.choice([6, 26]))
     elif family == "distanceAt":
@@ -701,16 +851,17 @@ def _arguments(rng, family, form, m, op=None):
 
 
 _FORMS_OF = {
-    **{f: FORMS for f in LIST_EDITS + ("getVoxels", "countBoxes", "surface", "rects", "columnProfile", "fillColumns")},
-    **{f: FORMS[1:] for f in STREAM_EDITS},
+    **{f: FORMS for f in LIST_EDITS + ("getVoxels", "countBoxes", "surface", "rects", "columnProfile", "fillColumns", "voxels")},
+    **{f: FORMS[1:] for f in STREAM_EDITS + ("listToSecond",)},
     "unpack": ("host", "dev0"), "pack": ("host", "dev0"), "select": FORMS,
 }
 
 
 OPS_OF = {"copyRegion": (REPLACE, OR, ANDNOT), "stampAffine": (REPLACE, OR, ANDNOT), "fillRandom": (REPLACE, OR, ANDNOT),
           "select": (REPLACE, OR, ANDNOT), "place": (OR, ANDNOT), "rasterMesh": (TOUCHED, THIN), "fillColumns": (REPLACE, OR, ANDNOT),
-          "selectColumnsDst": (REPLACE, OR, ANDNOT), "selectColumnsSrc": (REPLACE, OR, ANDNOT)}
-ALL_FORMS = LIST_EDITS + ("getVoxels", "countBoxes", "surface", "rects", "columnProfile", "fillColumns")
+          "selectColumnsDst": (REPLACE, OR, ANDNOT), "selectColumnsSrc": (REPLACE, OR, ANDNOT),
+          "voxels": (voxels_model.ALL, voxels_model.SURFACE, voxels_model.INTERIOR)}
+ALL_FORMS = LIST_EDITS + ("getVoxels", "countBoxes", "surface", "rects", "columnProfile", "fillColumns", "voxels")
 # (family, op, form) for every family, every op of the families that take one and every form of the list calls (None: any
 # form): the tour that every depth's programs run in full
 TOUR = tuple((family, op, form) for family in FAMILIES for op in OPS_OF.get(family, (None,)) for form in (FORMS if family in ALL_FORMS else (None,)))
@@ -729,8 +880,9 @@ def _circuit(nodes):
     return tuple(reversed(walk))
 
 
-STAGE_WALK = _circuit(BLOCKS["d_stage"])          # 144 pairs
+STAGE_WALK = _circuit(BLOCKS["d_stage"])          # 169 pairs
 PACK_WALK = _circuit(BLOCKS["d_pack"])            # 16 pairs
+SURFACE_WALK = _circuit(BLOCKS["d_surface"])      # 9 pairs
 
 
 def _share(walk, index, of):
@@ -747,6 +899,8 @@ PROLOGUE = (
     ("snapshotClone", "host", {}),
     ("snapshotLabels", "host", dict(connectivity=6)),
     ("commit", "host", {}),
+    ("refuseVoxels", "host", {}),                      # before any surface or voxel call: a refusal reserves no offsets block
+    ("refuseVoxelsAligned", "host", {}),
     ("rects", "host", dict(closed=True, first=0, capacity=50)),
     ("surface", "host", dict(closed=True, first=0, capacity=50)),
 )
@@ -766,7 +920,7 @@ class _Writer:
     def record(self, step, own):
         m = self.m
         self.out.append(step)
-        self.seen.append((own, m.seen_download("v"), m.s["w"], m.scratch_bytes("v"), m.scratch_bytes("w"), m.changed))
+        self.seen.append((own, m.seen_download("v"), m.s["w"], m.scratch_bytes("v"), m.scratch_bytes("w"), m.changed, m.s["stage_v"]))
 
     def solid(self, n):
         """n solid voxels of v (fewer where it holds fewer; one is set first where it holds none)"""
@@ -884,6 +1038,52 @@ def _scripted(w):
     w.emit(("strokeAtHits", "devB", dict(hits=hits_of(w.solid(9), S, miss_every=10), radius=0, max_gap=0, solid=True, then=("setVoxels", corners))))
     dug = w.solid(9)
     w.emit(("strokeAtHits", "devA", dict(hits=hits_of(dug, S, miss_every=10), radius=0, max_gap=0, solid=False, then=("getVoxels", dug[1:]))))
+    _scripted_lists(w, many)
+
+
+def _scripted_lists(w, many):
+    """the voxel lists: their host windows in the staging block, and their passes in the offsets block of the surface calls"""
+    m, S = w.m, w.m.S
+    ALL, SURFACE, INTERIOR = voxels_model.ALL, voxels_model.SURFACE, voxels_model.INTERIOR
+    cut = [1, 1, 1, S - 1, S - 1, S // 2 + 1]                                 # odd in x and y, no multiple of 8 in z
+    beyond = [0, 0, 0, S + 1, 0xFFFFFFFF, S + 100]
+
+    def lists(form, op, box, kind, neighbours, first, capacity, closed=True, **device):
+        return ("voxels", form, dict(op=op, box=box, kind=kind, closed=closed, neighbours=neighbours, first=first, capacity=capacity, **device))
+
+    # a slab four voxels thick: at least 64 voxels, some of them interior, at every depth
+    w.emit(("fillBoxes", "dev0", dict(items=np.array([[0, 0, 0, S, S, min(S, 4)]], np.uint32), solid=True)))
+    # a host window directly behind a larger host list edit; one that grows the staging block to exactly its own size; an empty
+    # one, behind the end of a list that is not empty, which leaves the block alone
+    w.emit(("setVoxels", "host", dict(items=many, solid=True)))
+    w.emit(lists("host", SURFACE, None, "whole", False, 1, 3))
+    grow = m.s["stage_v"] // 16 + 1
+    assert len(voxel_list(m.s["v"], dict(op=ALL, box=None, closed=False))) >= grow
+    w.emit(lists("host", ALL, [0, 0, 0, S, S, S], "whole", True, 0, grow, closed=False))
+    assert m.s["stage_v"] == 16 * grow
+    assert w.emit(lists("host", INTERIOR, None, "whole", True, 8 ** m.depth, 10))[0] > 0
+    # inside ONE step: a voxel extraction still on its stream while a synchronous count -- of another `which`, then of the
+    # surface calls, which keep their totals in the same block -- comes on the NULL stream; and a surface extraction with a
+    # voxelCount behind it.  Each count differs from the total of the extraction it follows, and the windows begin where the
+    # count's list ends: by the count's offsets no workgroup has a record in them.
+    inner = len(voxel_list(m.s["v"], dict(op=INTERIOR, box=beyond, closed=True)))
+    own = w.emit(lists("devA", ALL, beyond, "beyond", False, inner, 60, skew=4, order="extract_first", shift=2))
+    assert own[0] == inner < own[2]
+    w.emit(lists("devB", SURFACE, [2, 2, 2, 2, 3, 3], "empty", True, 0, 5, skew=0, order="surface_behind", shift=1))
+    own = w.emit(lists("devB", INTERIOR, cut, "cut", False, 0, 60, skew=0, order="surface_behind", shift=1))
+    assert own[2] > 0 and int(own[0].sum()) != own[2]
+    own = w.emit(("surface", "devA", dict(closed=True, first=8, capacity=60, order="voxels_behind", behind=dict(op=ALL, box=[1, 1, 1, 3, 3, 3], closed=True))))
+    assert 0 < own[0] <= 8 < own[2]
+    # the list of v into w without a visit to the host: directly behind a surface step, and on the other stream than the edit
+    # of v of the step before (the download between the steps orders that pair)
+    for form, edit, a in (("devB", None, dict(which=SURFACE, box=None, kind="whole", closed=True, solid=True)),
+                          ("devB", "devA", dict(which=ALL, box=cut, kind="cut", closed=False, solid=False))):
+        if edit:
+            w.emit(("fillBoxes", edit, dict(items=np.array([[1, 1, 1, 2, 2, 2]], np.uint32), solid=False)))
+        w.emit(("listToSecond", form, dict(a, n=len(voxel_list(m.s["v"], a)))))
+    # a list with a large total, then one of a small box: the second window is the second pass's
+    w.emit(lists("host", ALL, None, "whole", False, 0, 399))
+    w.emit(lists("host", SURFACE, [1, 1, 1, 3, 3, 3], "cut", True, 0, 399, closed=False))
 
 
 def _generate(seed, depth, steps):
@@ -897,6 +1097,8 @@ def _generate(seed, depth, steps):
         w.one(family, "host", tries=3, pad=False)
     for family in _share(PACK_WALK, index, len(COMMITTED)):
         w.one(family, "host", tries=1, pad=False)
+    for family in _share(SURFACE_WALK, index, len(COMMITTED)):
+        w.one(family, None, tries=3, pad=False)
     # depths 2 .. 5 run the whole tour in every program; at 64^3, where a program is short, the three seeds share it
     share = 3 if depth >= 6 else 1
     tour = [TOUR[i] for i in w.rng.permutation(len(TOUR)) if i % share == index % share]
@@ -929,7 +1131,8 @@ def replay(seed, depth, upto, fault=None):
 
 
 def run(steps, depth, fault=None):
-    """what every step of a program observes on the mirror: [(own observable, download of v, of w, scratch of v, of w)]"""
+    """what every step of a program observes on the mirror: [(own observable, download of v, of w, scratch of v, of w, whether a
+    voxel changed, the staging block of v alone)]"""
     m = Mirror(depth, fault)
     seen = []
     for step in steps:
@@ -939,7 +1142,7 @@ def run(steps, depth, fault=None):
             if fault is None:
                 raise
             break            # the faulty volume no longer fits the step's arguments: what was seen up to here is all there is
-        seen.append((own, m.seen_download("v"), m.s["w"], m.scratch_bytes("v"), m.scratch_bytes("w"), m.changed))
+        seen.append((own, m.seen_download("v"), m.s["w"], m.scratch_bytes("v"), m.scratch_bytes("w"), m.changed, m.s["stage_v"]))
     return seen
 
 
