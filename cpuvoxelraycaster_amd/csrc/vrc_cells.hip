@@ -7,9 +7,8 @@
 // row next in x, along y by 2 under WORD_Y0 / WORD_Y1, along z by 4 with a nibble of the z-neighbour word.
 //
 // The step.  One lane owns one destination word and writes it once; the source is only read.  The lane brings the nine
-// brick rows (cx + a, cy + b) around its word in as COLUMNS: 40-bit values  top nibble of word wz - 1 | word wz | bottom
-// nibble of word wz + 1  in a 64-bit register, so that bit 4 + i is bit i of the word and the two z layers beyond it sit
-// below and above.  Rows and nibbles beyond the volume's faces are all `outside`.  27 loads, of which every neighbouring
+// brick rows (cx + a, cy + b) around its word in as COLUMNS (vrc_word_columns.h): 40-bit values with the word at bit 4 and
+// the two z layers beyond it below and above.  Rows and nibbles beyond the volume's faces are all `outside`.  27 loads, of which every neighbouring
 // lane wants the same words: they are left to the caches.  The 26-count is separable, and every adder works on bit-planes,
 // 32 voxels (40 with the nibbles) at a time:
 //   x: per brick row, voxel x - 1, x and x + 1 at x's bit position (two shifts and the neighbour row's other half) go
@@ -33,45 +32,10 @@
 #include "vrc_cells.h"
 
 #include "vrc_box_words.h"
-#include "vrc_flood.h"
 #include "vrc_group.h"
+#include "vrc_word_columns.h"
 
 namespace {
-
-constexpr uint64_t X0 = ((uint64_t)vrc::WORD_X0 << 32) | vrc::WORD_X0, X1 = ~X0;
-constexpr uint64_t Y0 = ((uint64_t)vrc::WORD_Y0 << 32) | vrc::WORD_Y0, Y1 = ~Y0;
-
-// the source field: n brick rows per axis, nwz words per row, edge = all ones where `outside` is solid
-struct Field {
-    const uint32_t* __restrict__ words;
-    uint32_t n, nwz, edge;
-};
-
-// The column of brick row (cx, cy) at word wz.  SMALL (4^3): the half cy of word cx between two nibbles of `outside`, 24
-// bits.  WITH_Z = false leaves the z-neighbour words alone, for the rows of which only the word itself is used.
-template <bool SMALL, bool WITH_Z>
-__device__ __forceinline__ uint64_t column(const Field& f, int32_t cx, int32_t cy, uint32_t wz)
-{
-    const uint64_t edge4 = f.edge & 0xFu;
-    if (cx < 0 || cy < 0 || cx >= (int32_t)f.n || cy >= (int32_t)f.n) return f.edge ? ~0ull : 0ull;
-    if (SMALL) {
-        const uint64_t half = (f.words[cx] >> (16u * (uint32_t)cy)) & 0xffffu;
-        return edge4 | (half << 4) | (edge4 << 20);
-    }
-    const uint32_t* row = f.words + ((uint32_t)cx * f.n + (uint32_t)cy) * f.nwz;       // below 2^25
-    uint64_t below = edge4, above = edge4;
-    if (WITH_Z) {
-        if (wz > 0u) below = row[wz - 1u] >> 28;
-        if (wz + 1u < f.nwz) above = row[wz + 1u] & 0xFu;
-    }
-    return below | ((uint64_t)row[wz] << 4) | (above << 36);
-}
-
-// the voxel one step before / after along x or y, at this voxel's bit position: c = this row, o = the row that way
-__device__ __forceinline__ uint64_t x_before(uint64_t c, uint64_t o) { return ((c & X0) << 1) | ((o & X1) >> 1); }
-__device__ __forceinline__ uint64_t x_after(uint64_t c, uint64_t o) { return ((c & X1) >> 1) | ((o & X0) << 1); }
-__device__ __forceinline__ uint64_t y_before(uint64_t c, uint64_t o) { return ((c & Y0) << 2) | ((o & Y1) >> 2); }
-__device__ __forceinline__ uint64_t y_after(uint64_t c, uint64_t o) { return ((c & Y1) >> 2) | ((o & Y0) << 2); }
 
 template <class T>
 __device__ __forceinline__ void full_add(T a, T b, T c, T& sum, T& carry)
@@ -99,7 +63,7 @@ __device__ __forceinline__ uint32_t look_up(uint32_t table, const uint32_t* plan
 // The new bits of the word wz of brick row (cx, cy) -- SMALL: of the half cy of word cx, in the low 16 bits -- and the
 // word's (half's) source bits in *centre.
 template <int NEIGH, bool SMALL>
-__device__ __forceinline__ uint32_t rule(const Field& f, int32_t cx, int32_t cy, uint32_t wz, uint32_t birth, uint32_t survive, uint32_t* centre)
+__device__ __forceinline__ uint32_t rule(const WordColumns& f, int32_t cx, int32_t cy, uint32_t wz, uint32_t birth, uint32_t survive, uint32_t* centre)
 {
     if (NEIGH == 6) {
         const uint64_t c = column<SMALL, true>(f, cx, cy, wz);
@@ -161,7 +125,7 @@ __global__ __launch_bounds__(256) void k_cells_step(uint32_t* __restrict__ dst, 
         // word (cx, cy, wz) of n / 4 words along z
         const uint32_t lgz = lg - 2u, n = 1u << lg;
         if (W < (1u << (2u * lg + lgz))) {
-            const Field f = {src, n, 1u << lgz, edge};
+            const WordColumns f = {src, lg, edge};
             uint32_t centre;
             const uint32_t out = rule<NEIGH, false>(f, (int32_t)(W >> (lgz + lg)), (int32_t)((W >> lgz) & (n - 1u)), W & ((1u << lgz) - 1u), birth, survive, &centre);
             dst[W] = out;
@@ -169,7 +133,7 @@ __global__ __launch_bounds__(256) void k_cells_step(uint32_t* __restrict__ dst, 
         }
     } else if (W < 2u) {
         // 4^3: word cx, its low half the brick row cy = 0 and its high half cy = 1
-        const Field f = {src, 2u, 0u, edge};
+        const WordColumns f = {src, 1u, edge};
         uint32_t c0, c1;
         const uint32_t h0 = rule<NEIGH, true>(f, (int32_t)W, 0, 0u, birth, survive, &c0);
         const uint32_t h1 = rule<NEIGH, true>(f, (int32_t)W, 1, 0u, birth, survive, &c1);

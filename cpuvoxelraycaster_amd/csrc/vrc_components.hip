@@ -142,13 +142,6 @@ __global__ __launch_bounds__(GROUP) void k_components_flatten(Field f, uint32_t*
     if (threadIdx.x == 0) slots[blockIdx.x] = s;
 }
 
-// slots[0 .. n_slots) -> their exclusive prefix, slots[n_slots] = the total (at most 2^30).  One workgroup.
-__global__ __launch_bounds__(SCAN_GROUP) void k_components_scan(uint32_t* __restrict__ slots, uint32_t n_slots)
-{
-    const uint32_t total = scan_slots(slots, n_slots);
-    if (threadIdx.x == 0) slots[n_slots] = total;
-}
-
 __global__ __launch_bounds__(GROUP) void k_components_roots(Field f, uint32_t* L, const uint32_t* __restrict__ slots, vrc_component* __restrict__ records)
 {
     __shared__ uint32_t part[4];
@@ -170,17 +163,6 @@ __global__ __launch_bounds__(GROUP) void k_components_roots(Field f, uint32_t* L
         rec[9] = 0u; rec[10] = 0u; rec[11] = 0u;
         L[key] = id | ROOT_FLAG;
     }
-}
-
-__device__ __forceinline__ uint32_t wave_min(uint32_t v)
-{
-    for (int o = 32; o; o >>= 1) { const uint32_t t = __shfl_xor(v, o); v = t < v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-    for (int o = 32; o; o >>= 1) { const uint32_t t = __shfl_xor(v, o); v = t > v ? t : v; }
-    return v;
 }
 
 // Reads the roots' entries (flagged, written by no one here) and writes the others'.
@@ -292,7 +274,8 @@ void components_roots_run(const uint32_t* medium, uint32_t depth, int connectivi
         else hipLaunchKernelGGL((k_components_merge<26, false>), grid, block, 0, st, f, medium, labels, cells);
     }
     hipLaunchKernelGGL(k_components_flatten, grid, block, 0, st, f, labels, scratch);
-    hipLaunchKernelGGL(k_components_scan, dim3(1), dim3(SCAN_GROUP), 0, st, scratch, groups_of(depth));
+    // a slot <= the keys of a workgroup, the total at most 2^30
+    hipLaunchKernelGGL(k_scan_slots<uint32_t>, dim3(1), dim3(SCAN_GROUP), 0, st, scratch, groups_of(depth), (uint32_t*)nullptr);
 }
 
 void components_ids_run(uint32_t depth, uint32_t* labels, const uint32_t* scratch, vrc_component* records, hipStream_t st)

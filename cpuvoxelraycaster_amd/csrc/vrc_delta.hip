@@ -130,16 +130,6 @@ __global__ __launch_bounds__(LANES) void k_delta_count(const uint32_t* __restric
     publish(e, totals);
 }
 
-// slots[0 .. n_slots) -> their exclusive prefix, slots[n_slots] = the total, also into totals->words.  One workgroup.
-__global__ __launch_bounds__(SCAN_GROUP) void k_delta_scan(uint32_t* __restrict__ slots, uint32_t n_slots, DeltaTotals* __restrict__ totals)
-{
-    const uint32_t total = scan_slots(slots, n_slots);                  // a slot <= 256, the total <= 2^25
-    if (threadIdx.x == 0) {
-        slots[n_slots] = total;
-        totals->words = total;
-    }
-}
-
 __global__ __launch_bounds__(LANES) void k_delta_emit(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t n_words,
                                                       const uint32_t* __restrict__ slots, uint2* __restrict__ records)
 {
@@ -204,7 +194,8 @@ void delta_offsets_run(const uint32_t* before, const uint32_t* after, uint32_t d
     DeltaTotals* totals = (DeltaTotals*)scratch;
     delta_totals_reset(totals, st);
     hipLaunchKernelGGL(k_delta_count, dim3(groups_of(depth)), dim3(LANES), 0, st, before, after, delta_words(depth), depth - 1u, slots_of(scratch), totals);
-    hipLaunchKernelGGL(k_delta_scan, dim3(1), dim3(SCAN_GROUP), 0, st, slots_of(scratch), groups_of(depth), totals);
+    // a slot <= 256, the total <= 2^25; the total also goes into totals->words
+    hipLaunchKernelGGL(k_scan_slots<uint32_t>, dim3(1), dim3(SCAN_GROUP), 0, st, slots_of(scratch), groups_of(depth), &totals->words);
 }
 
 void delta_emit_run(const uint32_t* before, const uint32_t* after, uint32_t depth, const void* scratch, uint2* records, hipStream_t st)

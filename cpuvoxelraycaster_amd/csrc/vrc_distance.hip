@@ -30,6 +30,7 @@
 #include "vrc_distance.h"
 
 #include "vrc_box_words.h"
+#include "vrc_word_columns.h"
 
 namespace {
 
@@ -42,15 +43,6 @@ constexpr uint32_t WAVES_PER_CU = 8;          // lines in flight = compute units
 // columns a workgroup of the z pass takes per step: a lane per voxel up to 128^3, above that as many columns as the 64
 // words of bits in LDS hold (8, 4, 2 at 256^3, 512^3, 1024^3), a lane looping over their voxels
 __host__ __device__ inline uint32_t z_columns_per_step(uint32_t S) { return S >= GROUP ? 2048u / S : GROUP / S; }
-
-// the 8 voxels (x&1, y&1 = sh) of 4 brick bytes, z ascending
-__device__ __forceinline__ uint32_t column_bits_of_word(uint32_t w, uint32_t sh)
-{
-    uint32_t t = (w >> sh) & 0x11111111u;     // bit 0 / 4 of every byte: z even / odd
-    t = (t | (t >> 3)) & 0x03030303u;
-    t = (t | (t >> 6)) & 0x000f000fu;
-    return (t | (t >> 12)) & 0xffu;
-}
 
 __global__ __launch_bounds__(GROUP) void k_distance_z(const uint32_t* __restrict__ words, uint32_t depth, uint32_t flip, uint32_t* __restrict__ D,
                                                       unsigned long long* __restrict__ stats)

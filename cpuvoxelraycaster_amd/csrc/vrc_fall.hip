@@ -35,6 +35,7 @@
 #include "vrc_fall.h"
 
 #include "vrc_box_words.h"
+#include "vrc_group.h"
 
 namespace {
 
@@ -68,17 +69,6 @@ __device__ __forceinline__ uint32_t key_of(uint32_t n, uint32_t x, uint32_t y, u
 __device__ __forceinline__ uint32_t load_drop(const uint32_t* D, uint32_t i)
 {
     return __hip_atomic_load(D + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ uint32_t wave_min(uint32_t v)
-{
-    for (int o = 32; o; o >>= 1) { const uint32_t t = __shfl_xor(v, o); v = t < v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-    for (int o = 32; o; o >>= 1) { const uint32_t t = __shfl_xor(v, o); v = t > v ? t : v; }
-    return v;
 }
 
 // The constraint of one voxel: of piece `id` (NONE: no voxel), in F or not, q cells from the far face, with the nearest
@@ -197,8 +187,7 @@ __global__ __launch_bounds__(GROUP) void k_fall_finish(uint32_t C, uint32_t axis
         for (uint32_t a = 0; a < 3u; ++a) offsets[3u * i + a] = a == axis ? sign * (int32_t)d : 0;
     const unsigned long long moved = __ballot(d != 0u);
     if (!moved) return;                                                 // wave-uniform
-    unsigned long long voxels = d ? (unsigned long long)records[i].voxels : 0ull;
-    for (int o = 32; o; o >>= 1) voxels += __shfl_xor(voxels, o);
+    const unsigned long long voxels = wave_sum(d ? (unsigned long long)records[i].voxels : 0ull);
     const uint32_t most = wave_max(d);
     if ((threadIdx.x & 63u) == 0u) {
         atomicAdd((unsigned long long*)(block + B_MOVED_VOXELS), voxels);

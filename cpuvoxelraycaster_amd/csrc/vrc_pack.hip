@@ -46,23 +46,6 @@ __device__ __forceinline__ uint32_t nonzero_bytes(uint32_t w)
 // bit k set iff byte k of w is 0xff
 __device__ __forceinline__ uint32_t full_bytes(uint32_t w) { return ~nonzero_bytes(~w) & 0xfu; }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-// the sum of v over the lanes before this one
-__device__ __forceinline__ uint32_t wave_exclusive(uint32_t v)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t incl = v;
-    for (uint32_t o = 1; o < 64u; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    return incl - v;
-}
-
 // the geometry of a lane's row in tile t: R bricks with local indices [R lane, R lane + R), at occupancy word `word`
 template <bool E8>
 struct Row {
@@ -133,16 +116,6 @@ __global__ __launch_bounds__(SCAN_GROUP) void k_pack_scan(uint32_t* __restrict__
     }
 }
 
-// the offsets scan alone (unpack, behind the mask checks) and the rank scan alone (unpack, behind the class pass)
-__global__ __launch_bounds__(SCAN_GROUP) void k_scan_one(uint32_t* __restrict__ slots, uint32_t n_tiles, uint32_t* __restrict__ total_out)
-{
-    const uint32_t total = scan_slots(slots, n_tiles);
-    if (threadIdx.x == 0) {
-        slots[n_tiles] = total;
-        if (total_out) *total_out = total;
-    }
-}
-
 struct PackHead {
     uint32_t depth, mixed, partial, full;
     unsigned long long length, solid;
@@ -202,7 +175,7 @@ __global__ __launch_bounds__(LANES) void k_pack_emit(const uint32_t* __restrict_
         if (sub == 1u) mine[mw + mask_word] = vf;
     }
     // partial bytes, held to `to`: an edit between the passes cannot make the wave write beyond its tile's share
-    uint32_t at = from + wave_exclusive((uint32_t)__popc(ps));
+    uint32_t at = from + wave_exclusive_scan((uint32_t)__popc(ps));
 #pragma unroll
     for (uint32_t k = 0; k < R; ++k)
         if (((ps >> k) & 1u) && at < to) d_bytes[at++] = (uint8_t)((k < 4u ? w.x : w.y) >> (8u * (k & 3u)));
@@ -319,7 +292,7 @@ __global__ __launch_bounds__(LANES) void k_unpack_write(const uint32_t* __restri
             fl = (mine[mw + at / 32u] >> (at & 31u)) & ((1u << R) - 1u);
         }
         const uint32_t ps = sm & ~fl;
-        uint32_t at = slot_partial[t] + wave_exclusive((uint32_t)__popc(ps));
+        uint32_t at = slot_partial[t] + wave_exclusive_scan((uint32_t)__popc(ps));
 #pragma unroll
         for (uint32_t k = 0; k < R; ++k) {
             uint32_t byte = ((fl >> k) & 1u) ? 0xffu : 0u;
@@ -390,10 +363,10 @@ void unpack_check_run(const uint8_t* data, uint32_t depth, uint32_t M, uint32_t 
     uint32_t *sm = slot_mixed_of(scratch), *sp = slot_partial_of(scratch, depth);
     totals_reset(totals, st);
     hipLaunchKernelGGL(k_unpack_classes, dim3(field_groups(depth)), dim3(256), 0, st, (const uint32_t*)(data + l.a), depth, sm, totals);
-    hipLaunchKernelGGL(k_scan_one, dim3(1), dim3(SCAN_GROUP), 0, st, sm, nt, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(k_scan_slots<uint32_t>, dim3(1), dim3(SCAN_GROUP), 0, st, sm, nt, (uint32_t*)nullptr);           // a slot <= 1
     hipLaunchKernelGGL(k_unpack_masks, dim3((uint32_t)(((uint64_t)nt * mw + 255u) / 256u)), dim3(256), 0, st, (const uint32_t*)(data + l.b),
                        (const uint32_t*)(data + l.c), depth, M, sm, sp, totals);
-    hipLaunchKernelGGL(k_scan_one, dim3(1), dim3(SCAN_GROUP), 0, st, sp, nt, &totals->partial);
+    hipLaunchKernelGGL(k_scan_slots<uint32_t>, dim3(1), dim3(SCAN_GROUP), 0, st, sp, nt, &totals->partial);             // a slot <= 512
     const uint32_t d_words = (P + 3u) / 4u;
     if (d_words) {
         uint32_t groups = (d_words + 255u) / 256u;

@@ -13,26 +13,23 @@
 // the axis z.  The faces of a row are then  row & ~(the same row of the plane c_a -/+ 1),  0 (closed) or ~0 (open) beyond the
 // volume; bits past S of a row shorter than a word are 0.
 //
-// Four passes on one stream, a workgroup = 256 consecutive lanes, a lane = one word of one row in the canonical order
-// (d, c_a, c_s, word) -- so a lane's rectangle starts in bit order continue the order (d, c_a, s0, r0); no workgroup waits
-// for another:
-//   0. rows:  one lane per word of the two fields gathers its 32 bits from the brick words;
-//   1. count: the run starts of the word are m & ~(m << 1 | carry); a start whose row before starts no run there is a
-//             rectangle start at once, the others follow their run to its end (across words) and test the row before for
-//             the identical run; summed over the workgroup into its slot (at most 256 * 16);
-//   2. scan:  vrc_group.h's scan_slots; the total R goes behind the last slot;
-//   3. emit:  a workgroup whose range [slot, next slot) misses the window leaves after reading the two slots.  The others
-//             recompute, prefix across their lanes, and a lane walks the rows after each of its starts inside the window to
-//             find the height, then writes one 16-byte record, or nine 8-byte (or eighteen 4-byte) stores.
+// A pass over the rows, then the three passes of vrc_list.h, a lane = one word of one row in the canonical order
+// (d, c_a, c_s, word) -- so a lane's rectangle starts in bit order continue the order (d, c_a, s0, r0):
+//   rows:  one lane per word of the two fields gathers its 32 bits from the brick words;
+//   count: the run starts of the word are m & ~(m << 1 | carry); a start whose row before starts no run there is a
+//          rectangle start at once, the others follow their run to its end (across words) and test the row before for the
+//          identical run.  A slot is at most 256 * 16;
+//   emit:  a lane walks the rows after each of its starts inside the window to find the height, then writes one 16-byte
+//          record, or nine 8-byte (or eighteen 4-byte) stores.
 // Lane and word indices reach 6 * 2^25 and stay 32-bit; rectangle indices are 64-bit as the face indices are.
 #include "vrc_rects.h"
 
 #include "../../include/vrc.h"
-#include "vrc_group.h"
+#include "vrc_list.h"
 
 namespace {
 
-constexpr uint32_t GROUP = 256;               // lanes per workgroup
+constexpr uint32_t GROUP = LIST_GROUP;        // lanes per workgroup
 
 struct Rows {
     const uint32_t* zrows;                    // [x][y][z bits]
@@ -187,31 +184,21 @@ __global__ __launch_bounds__(256) void k_rect_count(Rows f, unsigned long long* 
     }
 }
 
-// slots[0 .. n_slots) -> their exclusive prefix, slots[n_slots] = the total.  One workgroup.
-__global__ __launch_bounds__(SCAN_GROUP) void k_rect_scan(unsigned long long* __restrict__ slots, uint32_t n_slots, unsigned long long* __restrict__ total_out)
-{
-    const unsigned long long total = scan_slots(slots, n_slots);      // a slot <= 256 * 16; a step's sum stays below 2^22
-    if (threadIdx.x == 0) {
-        slots[n_slots] = total;
-        if (total_out) *total_out = total;
-    }
-}
-
 // WIDE: `out` is 8-byte aligned, a triangle pair goes out as nine 8-byte stores
 template <int FORMAT, bool WIDE>
 __global__ __launch_bounds__(256) void k_rect_emit(Rows f, const unsigned long long* __restrict__ slots, unsigned long long first,
                                                    unsigned long long capacity, void* out)
 {
-    __shared__ uint32_t part[4];
-    const unsigned long long from = slots[blockIdx.x], to = slots[blockIdx.x + 1u];
-    const unsigned long long win_end = capacity > ~0ull - first ? ~0ull : first + capacity;
-    if (from == to || to <= first || from >= win_end) return;           // uniform for the workgroup
+    __shared__ uint32_t part[GROUP / 64u];
     const uint32_t L = blockIdx.x * GROUP + threadIdx.x;
     Lane at;
-    uint32_t rs = L < f.n_lanes ? rect_starts(f, L, at) : 0u;
-    uint32_t all = 0u;
-    unsigned long long idx = from + group_exclusive_scan<4u>((uint32_t)__popc(rs), part, &all);
-    if (!rs || idx + __popc(rs) <= first || idx >= win_end) return;     // no barrier follows
+    uint32_t rs = 0u;
+    const auto count = [&]() {
+        if (L < f.n_lanes) rs = rect_starts(f, L, at);
+        return (uint32_t)__popc(rs);
+    };
+    unsigned long long idx, win_end;
+    if (!list_window<GROUP / 64u>(slots, first, capacity, count, part, &idx, &win_end)) return;
     const uint32_t S = 1u << f.depth, a = at.d >> 1, side = at.d & 1u;
     for (; rs; rs &= rs - 1u, ++idx) {
         if (idx < first) continue;
@@ -241,15 +228,7 @@ __global__ __launch_bounds__(256) void k_rect_emit(Rows f, const unsigned long l
         // side 1: (q0 q1 q2), (q0 q2 q3); side 0: (q0 q2 q1), (q0 q3 q2)
         const int32_t t[18] = {q0x, q0y, q0z, side ? q1x : q2x, side ? q1y : q2y, side ? q1z : q2z, side ? q2x : q1x, side ? q2y : q1y, side ? q2z : q1z,
                                q0x, q0y, q0z, side ? q2x : q3x, side ? q2y : q3y, side ? q2z : q3z, side ? q3x : q2x, side ? q3y : q2y, side ? q3z : q2z};
-        if (WIDE) {
-            int2* w = (int2*)out + 9ull * o;
-#pragma unroll
-            for (int i = 0; i < 9; ++i) w[i] = make_int2(t[2 * i], t[2 * i + 1]);
-        } else {
-            int32_t* w = (int32_t*)out + 18ull * o;
-#pragma unroll
-            for (int i = 0; i < 18; ++i) w[i] = t[i];
-        }
+        store_triangle_pair<WIDE>(out, o, t);
     }
 }
 
@@ -259,9 +238,10 @@ uint32_t field_words(uint32_t depth) { return 1u << (2u * depth + words_lg(depth
 
 uint32_t lanes_of(uint32_t depth) { return 6u * field_words(depth); }
 
-uint32_t groups_of(uint32_t depth) { return (lanes_of(depth) + GROUP - 1u) / GROUP; }
+uint32_t groups_of(uint32_t depth) { return list_groups(lanes_of(depth)); }
 
-uint32_t* fields_of(const unsigned long long* scratch, uint32_t depth) { return (uint32_t*)(scratch + groups_of(depth) + 7u); }
+// the two row fields lie behind the slots
+uint32_t* fields_of(const unsigned long long* scratch, uint32_t depth) { return (uint32_t*)((const uint8_t*)scratch + list_slot_bytes(groups_of(depth), true)); }
 
 Rows rows_of(const unsigned long long* scratch, uint32_t depth, int closed)
 {
@@ -279,11 +259,11 @@ Rows rows_of(const unsigned long long* scratch, uint32_t depth, int closed)
 
 namespace vrc {
 
-size_t rect_scratch_bytes(uint32_t depth) { return ((size_t)groups_of(depth) + 7u) * 8u + (size_t)field_words(depth) * 8u; }
+size_t rect_scratch_bytes(uint32_t depth) { return list_slot_bytes(groups_of(depth), true) + (size_t)field_words(depth) * 8u; }
 
-unsigned long long* rect_total_slot(unsigned long long* scratch, uint32_t depth) { return scratch + groups_of(depth); }
+unsigned long long* rect_total_slot(unsigned long long* scratch, uint32_t depth) { return list_total_slot(scratch, groups_of(depth)); }
 
-unsigned long long* rect_direction_slots(unsigned long long* scratch, uint32_t depth) { return scratch + groups_of(depth) + 1u; }
+unsigned long long* rect_direction_slots(unsigned long long* scratch, uint32_t depth) { return list_direction_slots(scratch, groups_of(depth)); }
 
 void rect_rows_run(const uint32_t* words, uint32_t depth, unsigned long long* scratch, hipStream_t st)
 {
@@ -302,21 +282,17 @@ void rect_count_run(uint32_t depth, int closed, unsigned long long* scratch, hip
 void rect_offsets_run(uint32_t depth, int closed, unsigned long long* scratch, unsigned long long* d_total, hipStream_t st)
 {
     hipLaunchKernelGGL(k_rect_count<false>, dim3(groups_of(depth)), dim3(GROUP), 0, st, rows_of(scratch, depth, closed), scratch);
-    hipLaunchKernelGGL(k_rect_scan, dim3(1), dim3(SCAN_GROUP), 0, st, scratch, groups_of(depth), d_total);
+    // a slot <= 256 * 16; a step's sum stays below 2^22
+    hipLaunchKernelGGL(k_scan_slots<unsigned long long>, dim3(1), dim3(SCAN_GROUP), 0, st, scratch, groups_of(depth), d_total);
 }
 
 void rect_emit_run(uint32_t depth, int closed, int format, uint64_t first, uint64_t capacity, void* out, const unsigned long long* scratch,
                    hipStream_t st)
 {
-    const Rows f = rows_of(scratch, depth, closed);
-    const dim3 grid(groups_of(depth)), block(GROUP);
-    const unsigned long long a = first, b = capacity;
-    if (format == VRC_SURFACE_FACES)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rect_emit<VRC_SURFACE_FACES, true>), grid, block, 0, st, f, scratch, a, b, out);
-    else if (((uintptr_t)out & 7u) == 0u)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rect_emit<VRC_SURFACE_TRIANGLES, true>), grid, block, 0, st, f, scratch, a, b, out);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rect_emit<VRC_SURFACE_TRIANGLES, false>), grid, block, 0, st, f, scratch, a, b, out);
+    const auto kernel = emit_kernel_for(format, out, k_rect_emit<VRC_SURFACE_FACES, true>, k_rect_emit<VRC_SURFACE_TRIANGLES, true>,
+                                        k_rect_emit<VRC_SURFACE_TRIANGLES, false>);
+    hipLaunchKernelGGL(kernel, dim3(groups_of(depth)), dim3(GROUP), 0, st, rows_of(scratch, depth, closed), scratch, (unsigned long long)first,
+                       (unsigned long long)capacity, out);
 }
 
 }  // namespace vrc

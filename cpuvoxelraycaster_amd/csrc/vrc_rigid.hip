@@ -97,17 +97,6 @@ static_assert(sizeof(vrc_piece_moments) == SUMS * 8u, "vrc_piece_moments is ten 
 static_assert(sizeof(vrc_piece_contact) == CONTACT_WORDS * 8u, "vrc_piece_contact is 15 64-bit sums and a reserved word");
 static_assert(sizeof(vrc_affine) == 64, "vrc_affine is 64 bytes");
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // the registers of a uniform run, summed over the wave and added to record `slot` by lane 0; called by whole waves
 __device__ __forceinline__ void flush_run(const uint32_t acc[SUMS], uint32_t slot, unsigned long long* out)
 {
@@ -678,7 +667,7 @@ __device__ __forceinline__ bool pair_box(const uint8_t* __restrict__ keep, const
 
 // One thread per a walks all b: C^2 box tests.  b is uniform for the wave, so box b and keep[b] come through wave-uniform
 // loads and every lane compares them with a box of its own in registers.  The count pass (EMIT false) stores how many b are
-// candidates of a in slots[a]; k_scan_pair_slots turns the counts into offsets with the total in slots[C]; the emit pass runs
+// candidates of a in slots[a]; k_scan_slots turns the counts into offsets with the total in slots[C]; the emit pass runs
 // the same loop and writes entry slots[a] + j of the canonical list -- (a, b) ascending -- where it falls into
 // [first, first + want).  first + want <= the total.
 template <bool EMIT>
@@ -712,13 +701,6 @@ __global__ __launch_bounds__(GROUP) void k_box_pairs(const uint8_t* __restrict__
         ++found;
     }
     if (!EMIT && a < C) slots[a] = found;
-}
-
-// a slot is below C <= BOX_PAIR_PIECES = 2^20 and the 1024 slots of a step sum to less than 2^30, as scan_slots wants them
-__global__ __launch_bounds__(SCAN_GROUP) void k_scan_pair_slots(unsigned long long* slots, uint32_t C)
-{
-    const unsigned long long total = scan_slots(slots, C);
-    if (threadIdx.x == 0u) slots[C] = total;
 }
 
 }  // namespace
@@ -793,7 +775,8 @@ void box_pair_count_run(const uint8_t* keep, const uint32_t* boxes, uint64_t pie
 {
     const uint32_t C = (uint32_t)pieces;
     hipLaunchKernelGGL(k_box_pairs<false>, dim3((C + GROUP - 1u) / GROUP), dim3(GROUP), 0, st, keep, boxes, C, 1u << posed_depth, slots, 0ull, 0ull, (uint32_t*)nullptr);
-    hipLaunchKernelGGL(k_scan_pair_slots, dim3(1), dim3(SCAN_GROUP), 0, st, slots, C);
+    // a slot is below C <= BOX_PAIR_PIECES = 2^20 and the 1024 slots of a step sum to less than 2^30, as scan_slots wants them
+    hipLaunchKernelGGL(k_scan_slots<unsigned long long>, dim3(1), dim3(SCAN_GROUP), 0, st, slots, C, (unsigned long long*)nullptr);
 }
 
 void box_pairs_run(const uint8_t* keep, const uint32_t* boxes, uint64_t pieces, uint32_t posed_depth, unsigned long long* slots, uint64_t first, uint64_t want,

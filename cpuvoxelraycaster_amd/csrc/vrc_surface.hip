@@ -4,27 +4,20 @@
 // The exposed faces of a word in one direction are a mask of its bits, w & ~(the word's neighbours shifted onto it):
 // word_masks in vrc_word_faces.h, which the voxel lists (vrc_voxels.hip) share.  No voxel is expanded to a byte.
 //
-// The canonical order is (word, direction, bit).  Three passes on one stream, a workgroup = 256 consecutive words, a
-// lane = one word; no workgroup waits for another:
-//   1. count: the popcounts of the six masks, summed over the workgroup into its slot (at most 256 * 192 faces);
-//   2. scan:  one workgroup walks the slots 1024 at a time and replaces them by their 64-bit exclusive prefix; the
-//             total T goes behind the last slot;
-//   3. emit:  a workgroup whose range [slot, next slot) misses the window leaves after reading the two slots.  The
-//             others recompute their masks, prefix the per-word counts across their lanes, and every lane walks the set
-//             bits of its own word, writing the faces that fall inside the window: one 16-byte store per face record,
-//             nine 8-byte (or eighteen 4-byte) stores per pair of triangles.
+// The canonical order is (word, direction, bit), the three passes are vrc_list.h's with a lane = one word: a lane counts
+// the popcounts of its six masks (a slot is at most 256 * 192 faces), and in the emit pass walks the set bits of its own
+// word: one 16-byte store per face record, nine 8-byte (or eighteen 4-byte) stores per pair of triangles.
 // Each pass reads every word and its six neighbours once (the neighbours come from the caches: a word is the x / y / z
-// neighbour of six others); the writes of pass 3 follow the window.  Word indices reach 2^25 and stay 32-bit, face
-// indices reach 3 * 8^10 > 2^32 and are 64-bit throughout.
+// neighbour of six others).  Word indices reach 2^25 and stay 32-bit, face indices reach 3 * 8^10 > 2^32.
 #include "vrc_surface.h"
 
 #include "../../include/vrc.h"
-#include "vrc_group.h"
+#include "vrc_list.h"
 #include "vrc_word_faces.h"
 
 namespace {
 
-constexpr uint32_t GROUP = 256;               // words per workgroup
+constexpr uint32_t GROUP = LIST_GROUP;        // words per workgroup
 
 // DIRECTIONS: the six totals of the whole field (vrc_volume_surface_count); otherwise the workgroup's own total
 template <bool DIRECTIONS>
@@ -44,16 +37,6 @@ __global__ __launch_bounds__(256) void k_surface_count(Field f, unsigned long lo
         for (int d = 0; d < 6; ++d) c += __popc(m[d]);
         const uint32_t s = group_sum<GROUP / 64u>(c, part);
         if (threadIdx.x == 0) slots[blockIdx.x] = s;
-    }
-}
-
-// slots[0 .. n_slots) -> their exclusive prefix, slots[n_slots] = the total.  One workgroup.
-__global__ __launch_bounds__(SCAN_GROUP) void k_surface_scan(unsigned long long* __restrict__ slots, uint32_t n_slots, unsigned long long* __restrict__ total_out)
-{
-    const unsigned long long total = scan_slots(slots, n_slots);      // a slot <= 256 * 192; a step's sum stays below 2^26
-    if (threadIdx.x == 0) {
-        slots[n_slots] = total;
-        if (total_out) *total_out = total;
     }
 }
 
@@ -94,13 +77,7 @@ __device__ __forceinline__ unsigned long long emit_direction(const Field& f, uin
             } else {
                 int32_t t[18];
                 face_triangles<D>(c, t);
-                if (WIDE) {
-                    int2* o = (int2*)out + 9ull * at;
-                    for (int k = 0; k < 9; ++k) o[k] = make_int2(t[2 * k], t[2 * k + 1]);
-                } else {
-                    int32_t* o = (int32_t*)out + 18ull * at;
-                    for (int k = 0; k < 18; ++k) o[k] = t[k];
-                }
+                store_triangle_pair<WIDE>(out, at, t);
             }
         }
         ++idx;
@@ -113,17 +90,17 @@ template <int FORMAT, bool WIDE>
 __global__ __launch_bounds__(256) void k_surface_emit(Field f, const unsigned long long* __restrict__ slots, unsigned long long first,
                                                       unsigned long long capacity, void* out)
 {
-    __shared__ uint32_t part[4];
-    const unsigned long long from = slots[blockIdx.x], to = slots[blockIdx.x + 1u];
-    const unsigned long long win_end = capacity > ~0ull - first ? ~0ull : first + capacity;
-    if (from == to || to <= first || from >= win_end) return;           // uniform for the workgroup
+    __shared__ uint32_t part[GROUP / 64u];
     const uint32_t W = blockIdx.x * GROUP + threadIdx.x;
     uint32_t m[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-    if (W < f.n_words) word_masks(f, W, m);
-    uint32_t mine = 0u, all = 0u;
-    for (int d = 0; d < 6; ++d) mine += __popc(m[d]);
-    unsigned long long idx = from + group_exclusive_scan<4u>(mine, part, &all);
-    if (!mine || idx + mine <= first || idx >= win_end) return;         // no barrier follows
+    const auto count = [&]() {
+        if (W < f.n_words) word_masks(f, W, m);
+        uint32_t mine = 0u;
+        for (int d = 0; d < 6; ++d) mine += __popc(m[d]);
+        return mine;
+    };
+    unsigned long long idx, win_end;
+    if (!list_window<GROUP / 64u>(slots, first, capacity, count, part, &idx, &win_end)) return;
     idx = emit_direction<FORMAT, WIDE, 0>(f, W, m[0], idx, first, win_end, out);
     idx = emit_direction<FORMAT, WIDE, 1>(f, W, m[1], idx, first, win_end, out);
     idx = emit_direction<FORMAT, WIDE, 2>(f, W, m[2], idx, first, win_end, out);
@@ -132,21 +109,17 @@ __global__ __launch_bounds__(256) void k_surface_emit(Field f, const unsigned lo
     emit_direction<FORMAT, WIDE, 5>(f, W, m[5], idx, first, win_end, out);
 }
 
-uint32_t groups_of(uint32_t depth)
-{
-    const uint32_t n_words = 1u << (3u * (depth - 1u) - 2u);
-    return (n_words + GROUP - 1u) / GROUP;
-}
+uint32_t groups_of(uint32_t depth) { return list_groups(1u << (3u * (depth - 1u) - 2u)); }
 
 }  // namespace
 
 namespace vrc {
 
-size_t surface_scratch_bytes(uint32_t depth) { return ((size_t)groups_of(depth) + 7u) * 8u; }
+size_t surface_scratch_bytes(uint32_t depth) { return list_slot_bytes(groups_of(depth), true); }
 
-unsigned long long* surface_total_slot(unsigned long long* scratch, uint32_t depth) { return scratch + groups_of(depth); }
+unsigned long long* surface_total_slot(unsigned long long* scratch, uint32_t depth) { return list_total_slot(scratch, groups_of(depth)); }
 
-unsigned long long* surface_direction_slots(unsigned long long* scratch, uint32_t depth) { return scratch + groups_of(depth) + 1u; }
+unsigned long long* surface_direction_slots(unsigned long long* scratch, uint32_t depth) { return list_direction_slots(scratch, groups_of(depth)); }
 
 void surface_count_run(const uint32_t* words, uint32_t depth, int closed, unsigned long long* scratch, hipStream_t st)
 {
@@ -158,21 +131,17 @@ void surface_count_run(const uint32_t* words, uint32_t depth, int closed, unsign
 void surface_offsets_run(const uint32_t* words, uint32_t depth, int closed, unsigned long long* scratch, unsigned long long* d_total, hipStream_t st)
 {
     hipLaunchKernelGGL(k_surface_count<false>, dim3(groups_of(depth)), dim3(GROUP), 0, st, field_of(words, depth, closed), scratch);
-    hipLaunchKernelGGL(k_surface_scan, dim3(1), dim3(SCAN_GROUP), 0, st, scratch, groups_of(depth), d_total);
+    // a slot <= 256 * 192; a step's sum stays below 2^26
+    hipLaunchKernelGGL(k_scan_slots<unsigned long long>, dim3(1), dim3(SCAN_GROUP), 0, st, scratch, groups_of(depth), d_total);
 }
 
 void surface_emit_run(const uint32_t* words, uint32_t depth, int closed, int format, uint64_t first, uint64_t capacity, void* out,
                       const unsigned long long* scratch, hipStream_t st)
 {
-    const Field f = field_of(words, depth, closed);
-    const dim3 grid(groups_of(depth)), block(GROUP);
-    const unsigned long long a = first, b = capacity;
-    if (format == VRC_SURFACE_FACES)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_surface_emit<VRC_SURFACE_FACES, true>), grid, block, 0, st, f, scratch, a, b, out);
-    else if (((uintptr_t)out & 7u) == 0u)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_surface_emit<VRC_SURFACE_TRIANGLES, true>), grid, block, 0, st, f, scratch, a, b, out);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_surface_emit<VRC_SURFACE_TRIANGLES, false>), grid, block, 0, st, f, scratch, a, b, out);
+    const auto kernel = emit_kernel_for(format, out, k_surface_emit<VRC_SURFACE_FACES, true>, k_surface_emit<VRC_SURFACE_TRIANGLES, true>,
+                                        k_surface_emit<VRC_SURFACE_TRIANGLES, false>);
+    hipLaunchKernelGGL(kernel, dim3(groups_of(depth)), dim3(GROUP), 0, st, field_of(words, depth, closed), scratch, (unsigned long long)first,
+                       (unsigned long long)capacity, out);
 }
 
 }  // namespace vrc

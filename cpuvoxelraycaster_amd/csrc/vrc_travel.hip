@@ -56,6 +56,7 @@
 #include "vrc_travel.h"
 
 #include "vrc_group.h"
+#include "vrc_word_columns.h"
 
 namespace {
 
@@ -68,15 +69,6 @@ constexpr uint32_t HZP = HV + 1;               // padded: neighbouring columns 1
 constexpr uint32_t GROUP = 256;
 
 __host__ __device__ inline uint32_t tiles_per_axis(uint32_t S) { return S >= TV ? S / TV : 1u; }
-
-// the 8 voxels (x&1, y&1 = sh) of the 4 brick bytes of a word, z ascending
-__device__ __forceinline__ uint32_t column_bits_of_word(uint32_t w, uint32_t sh)
-{
-    uint32_t t = (w >> sh) & 0x11111111u;     // bit 0 / 4 of every byte: z even / odd
-    t = (t | (t >> 3)) & 0x03030303u;
-    t = (t | (t >> 6)) & 0x000f000fu;
-    return (t | (t >> 12)) & 0xffu;
-}
 
 // Bit k = voxel (x, y, 8*zseg + k) of the brick field `words` (n bricks per axis), XORed with `flip` (0 or ~0) inside the
 // volume; 0 for everything outside it.  From 8^3 on a run of eight voxels along z is one aligned word; 4^3 (two brick rows to

@@ -3,20 +3,14 @@
 // vrc_volume_set_voxels.
 //
 // The layout of a word (2 x 2 x 8 voxels, bit zz*4 + yb*2 + xb) is described at the top of vrc_flood.hip.  A voxel's key
-// is 32 W + bit, so the key order is (word, bit).  Three passes on one stream, as in vrc_surface.hip: a workgroup = 256
-// consecutive words, a lane = one word, no workgroup waits for another:
-//   1. count: a lane's selection is  w & box mask & select(which)  -- for SURFACE / INTERIOR the union of the six face
-//             masks of vrc_word_faces.h and its complement in w.  A lane whose word lies outside the box loads nothing,
-//             so a workgroup wholly outside it writes 0 without touching the occupancy.  The popcounts are summed over
-//             the workgroup into its slot (at most 256 * 32 = 8192);
-//   2. scan:  one workgroup walks the slots 1024 at a time (scan_slots), the total T goes behind the last slot;
-//   3. emit:  a workgroup whose range [slot, next slot) misses the window leaves after reading the two slots.  The
-//             others recompute their selections, prefix the per-word counts across their lanes, and every lane walks the
-//             set bits of its own mask.  x y z is one 8-byte and one 4-byte store, in the order the record's address
-//             allows; x y z m is one 16-byte store.
+// is 32 W + bit, so the key order is (word, bit).  The three passes are vrc_list.h's with a lane = one word:
+//   count: a lane's selection is  w & box mask & select(which)  -- for SURFACE / INTERIOR the union of the six face masks
+//          of vrc_word_faces.h and its complement in w.  A lane whose word lies outside the box loads nothing, so a
+//          workgroup wholly outside it writes 0 without touching the occupancy.  A slot is at most 256 * 32 = 8192;
+//   emit:  every lane walks the set bits of its own mask.  x y z is one 8-byte and one 4-byte store, in the order the
+//          record's address allows; x y z m is one 16-byte store.
 // The neighbourhood.  A lane loads the 27 words around its word ONCE, as the nine brick rows (cx + a, cy + b) in the
-// column form of vrc_cells.hip: top nibble of word wz - 1 | word wz | bottom nibble of word wz + 1 in 40 bits, so that
-// bit 4 + i is bit i of the word.  Rows and nibbles beyond the volume are all `beyond`.  The x and y steps are the
+// column form of vrc_word_columns.h.  Rows and nibbles beyond the volume are all `beyond`.  The x and y steps are the
 // flood's shifts under WORD_X0 / X1 / Y0 / Y1, the z steps read the column at bit 0 / 4 / 8: 27 planes of 32 bits, plane
 // k = 9 (dx + 1) + 3 (dy + 1) + (dz + 1) holding voxel c + (dx, dy, dz) at c's bit.  A voxel's m is bit b of each
 // plane, and the six face planes (4, 22, 10, 16, 12, 14) give SURFACE / INTERIOR without the face masks.  4^3 (two
@@ -27,14 +21,13 @@
 
 #include "../../include/vrc.h"
 #include "vrc_box_words.h"
-#include "vrc_group.h"
+#include "vrc_list.h"
+#include "vrc_word_columns.h"
 #include "vrc_word_faces.h"
 
 namespace {
 
-constexpr uint32_t GROUP = 256;               // words per workgroup
-constexpr uint64_t X0 = ((uint64_t)vrc::WORD_X0 << 32) | vrc::WORD_X0, X1 = ~X0;
-constexpr uint64_t Y0 = ((uint64_t)vrc::WORD_Y0 << 32) | vrc::WORD_Y0, Y1 = ~Y0;
+constexpr uint32_t GROUP = LIST_GROUP;        // words per workgroup
 
 using vrc::VoxelQuery;
 
@@ -75,37 +68,20 @@ __device__ __forceinline__ uint32_t selection(const Field& f, const VoxelQuery& 
     return (q.which == VRC_VOXELS_SURFACE ? exposed : f.words[W] & ~exposed) & box;
 }
 
-// The column of brick row (cx, cy) at word wz, lg >= 2: 40 bits, bit 4 + i = bit i of the word
-__device__ __forceinline__ uint64_t column(const Field& f, int32_t cx, int32_t cy, uint32_t wz)
-{
-    const uint32_t lgz = f.lg - 2u;
-    const int32_t n = 1 << f.lg;
-    if (cx < 0 || cy < 0 || cx >= n || cy >= n) return f.beyond ? ~0ull : 0ull;
-    const uint32_t* row = f.words + ((((uint32_t)cx << f.lg) | (uint32_t)cy) << lgz);      // below 2^25
-    const uint64_t edge4 = f.beyond & 0xFu;
-    const uint64_t below = wz ? row[wz - 1u] >> 28 : edge4, above = wz + 1u < (1u << lgz) ? row[wz + 1u] & 0xFu : edge4;
-    return below | ((uint64_t)row[wz] << 4) | (above << 36);
-}
-
-// the voxel one step before / after along x or y, at this voxel's bit position: c = this row, o = the row that way
-__device__ __forceinline__ uint64_t x_before(uint64_t c, uint64_t o) { return ((c & X0) << 1) | ((o & X1) >> 1); }
-__device__ __forceinline__ uint64_t x_after(uint64_t c, uint64_t o) { return ((c & X1) >> 1) | ((o & X0) << 1); }
-__device__ __forceinline__ uint64_t y_before(uint64_t c, uint64_t o) { return ((c & Y0) << 2) | ((o & Y1) >> 2); }
-__device__ __forceinline__ uint64_t y_after(uint64_t c, uint64_t o) { return ((c & Y1) >> 2) | ((o & Y0) << 2); }
-
 // the 27 planes of word W, lg >= 2: p[9 (dx+1) + 3 (dy+1) + (dz+1)] bit i = voxel (bit i of W) + (dx, dy, dz)
 __device__ __forceinline__ void word_planes(const Field& f, uint32_t W, uint32_t p[27])
 {
     const uint32_t lgz = f.lg - 2u, n = 1u << f.lg;
     const uint32_t wz = W & ((1u << lgz) - 1u);
     const int32_t cy = (int32_t)((W >> lgz) & (n - 1u)), cx = (int32_t)(W >> (lgz + f.lg));
+    const WordColumns wc = {f.words, f.lg, f.beyond};
     uint64_t x[3][3];                          // [dx + 1][row cy + b - 1], at x's position
 #pragma unroll
     for (int b = 0; b < 3; ++b) {
-        const uint64_t c = column(f, cx, cy + b - 1, wz);
-        x[0][b] = x_before(c, column(f, cx - 1, cy + b - 1, wz));
+        const uint64_t c = column<false, true>(wc, cx, cy + b - 1, wz);
+        x[0][b] = x_before(c, column<false, true>(wc, cx - 1, cy + b - 1, wz));
         x[1][b] = c;
-        x[2][b] = x_after(c, column(f, cx + 1, cy + b - 1, wz));
+        x[2][b] = x_after(c, column<false, true>(wc, cx + 1, cy + b - 1, wz));
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -152,16 +128,6 @@ __global__ __launch_bounds__(256) void k_voxels_count(Field f, VoxelQuery q, uns
     if (threadIdx.x == 0) slots[blockIdx.x] = s;
 }
 
-// slots[0 .. n_slots) -> their exclusive prefix, slots[n_slots] = the total.  One workgroup.
-__global__ __launch_bounds__(SCAN_GROUP) void k_voxels_scan(unsigned long long* __restrict__ slots, uint32_t n_slots, unsigned long long* __restrict__ total_out)
-{
-    const unsigned long long total = scan_slots(slots, n_slots);      // a slot <= 8192; a step's sum stays below 2^24
-    if (threadIdx.x == 0) {
-        slots[n_slots] = total;
-        if (total_out) *total_out = total;
-    }
-}
-
 // x y z at record `at` of a 4-byte aligned list: the 8-byte store goes where the record's address allows it
 __device__ __forceinline__ void store_xyz(void* out, unsigned long long at, const uint32_t c[3])
 {
@@ -179,18 +145,16 @@ template <int FORMAT>
 __global__ __launch_bounds__(256) void k_voxels_emit(Field f, VoxelQuery q, const unsigned long long* __restrict__ slots, unsigned long long first,
                                                      unsigned long long capacity, void* out)
 {
-    __shared__ uint32_t part[4];
-    const unsigned long long from = slots[blockIdx.x], to = slots[blockIdx.x + 1u];
-    const unsigned long long win_end = capacity > ~0ull - first ? ~0ull : first + capacity;
-    if (from == to || to <= first || from >= win_end) return;           // uniform for the workgroup
+    __shared__ uint32_t part[GROUP / 64u];
     const uint32_t W = blockIdx.x * GROUP + threadIdx.x;
     const bool planes = FORMAT == VRC_VOXELS_NEIGHBOURS && f.lg >= 2u;   // uniform for the launch
     uint32_t p[27], sel = 0u;
-    if (W < f.n_words) sel = planes ? selection_planes(f, q, W, p) : selection(f, q, W);
-    uint32_t all = 0u;
-    const uint32_t mine = __popc(sel);
-    unsigned long long idx = from + group_exclusive_scan<GROUP / 64u>(mine, part, &all);
-    if (!mine || idx + mine <= first || idx >= win_end) return;         // no barrier follows
+    const auto count = [&]() {
+        if (W < f.n_words) sel = planes ? selection_planes(f, q, W, p) : selection(f, q, W);
+        return (uint32_t)__popc(sel);
+    };
+    unsigned long long idx, win_end;
+    if (!list_window<GROUP / 64u>(slots, first, capacity, count, part, &idx, &win_end)) return;
     for (; sel; sel &= sel - 1u, ++idx) {
         if (idx < first || idx >= win_end) continue;
         const uint32_t bit = (uint32_t)__ffs((int)sel) - 1u;
@@ -211,24 +175,21 @@ __global__ __launch_bounds__(256) void k_voxels_emit(Field f, VoxelQuery q, cons
     }
 }
 
-uint32_t groups_of(uint32_t depth)
-{
-    const uint32_t n_words = 1u << (3u * (depth - 1u) - 2u);
-    return (n_words + GROUP - 1u) / GROUP;
-}
+uint32_t groups_of(uint32_t depth) { return list_groups(1u << (3u * (depth - 1u) - 2u)); }
 
 }  // namespace
 
 namespace vrc {
 
-size_t voxels_scratch_bytes(uint32_t depth) { return ((size_t)groups_of(depth) + 1u) * 8u; }
+size_t voxels_scratch_bytes(uint32_t depth) { return list_slot_bytes(groups_of(depth), false); }
 
-unsigned long long* voxels_total_slot(unsigned long long* scratch, uint32_t depth) { return scratch + groups_of(depth); }
+unsigned long long* voxels_total_slot(unsigned long long* scratch, uint32_t depth) { return list_total_slot(scratch, groups_of(depth)); }
 
 void voxels_offsets_run(const uint32_t* words, uint32_t depth, const VoxelQuery& q, unsigned long long* scratch, unsigned long long* d_total, hipStream_t st)
 {
     hipLaunchKernelGGL(k_voxels_count, dim3(groups_of(depth)), dim3(GROUP), 0, st, field_of(words, depth, q.closed), q, scratch);
-    hipLaunchKernelGGL(k_voxels_scan, dim3(1), dim3(SCAN_GROUP), 0, st, scratch, groups_of(depth), d_total);
+    // a slot <= 8192; a step's sum stays below 2^24
+    hipLaunchKernelGGL(k_scan_slots<unsigned long long>, dim3(1), dim3(SCAN_GROUP), 0, st, scratch, groups_of(depth), d_total);
 }
 
 void voxels_emit_run(const uint32_t* words, uint32_t depth, const VoxelQuery& q, int format, uint64_t first, uint64_t capacity, void* out,

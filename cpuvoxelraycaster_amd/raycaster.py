@@ -1018,17 +1018,8 @@ class VoxelVolume:
 
     def _surface(self, fmt, dtype, per_face, closed, first, capacity):
         L, closed = capi.load(), int(bool(closed))
-        total = C.c_uint64()
-        check(L.vrc_volume_extract_surface(self._h, closed, fmt, 0, 0, None, C.byref(total), capi.VRC_MEM_HOST, None))
-        first = int(first)
-        n = max(0, total.value - first)
-        if capacity is not None:
-            n = min(n, int(capacity))
-        out = np.zeros((n, per_face), dtype)
-        for at in range(0, n, self.SURFACE_WINDOW):
-            part = out[at:at + self.SURFACE_WINDOW]
-            check(L.vrc_volume_extract_surface(self._h, closed, fmt, first + at, part.shape[0], ptr(part), None, capi.VRC_MEM_HOST, None))
-        return out
+        return _fetch_all(lambda at, n, out, total: check(L.vrc_volume_extract_surface(self._h, closed, fmt, at, n, out, total, capi.VRC_MEM_HOST, None)),
+                          first, capacity, per_face, dtype, self.SURFACE_WINDOW)
 
     def surfaceFaces(self, closed=True, first=0, capacity=None):
         """(n, 4) uint32 x y z d: the exposed faces [first, first + capacity) of the canonical order (by occupancy word,
@@ -1073,17 +1064,8 @@ class VoxelVolume:
         volume read solid.  capacity=None fetches everything from `first` on in bounded windows.  Synchronous."""
         L, closed, which, box = capi.load(), int(bool(closed)), int(which), self._box(box)
         fmt, per = (capi.VRC_VOXELS_NEIGHBOURS, 4) if neighbours else (capi.VRC_VOXELS_XYZ, 3)
-        total = C.c_uint64()
-        check(L.vrc_voxels_extract(self._h, which, closed, ptr(box), fmt, 0, 0, None, C.byref(total), capi.VRC_MEM_HOST, None))
-        first = int(first)
-        n = max(0, total.value - first)
-        if capacity is not None:
-            n = min(n, int(capacity))
-        out = np.zeros((n, per), np.uint32)
-        for at in range(0, n, self.SURFACE_WINDOW):
-            part = out[at:at + self.SURFACE_WINDOW]
-            check(L.vrc_voxels_extract(self._h, which, closed, ptr(box), fmt, first + at, part.shape[0], ptr(part), None, capi.VRC_MEM_HOST, None))
-        return out
+        return _fetch_all(lambda at, n, out, total: check(L.vrc_voxels_extract(self._h, which, closed, ptr(box), fmt, at, n, out, total, capi.VRC_MEM_HOST, None)),
+                          first, capacity, per, np.uint32, self.SURFACE_WINDOW)
 
     def surfaceVoxels(self, box=None, neighbours=False, closed=True, first=0, capacity=None):
         """voxels() of the solid voxels with at least one exposed face"""
@@ -1107,17 +1089,8 @@ class VoxelVolume:
 
     def _rects(self, fmt, dtype, per_rect, closed, first, capacity):
         L, closed = capi.load(), int(bool(closed))
-        total = C.c_uint64()
-        check(L.vrc_extract_rects(self._h, closed, fmt, 0, 0, None, C.byref(total), capi.VRC_MEM_HOST, None))
-        first = int(first)
-        n = max(0, total.value - first)
-        if capacity is not None:
-            n = min(n, int(capacity))
-        out = np.zeros((n, per_rect), dtype)
-        for at in range(0, n, self.SURFACE_WINDOW):
-            part = out[at:at + self.SURFACE_WINDOW]
-            check(L.vrc_extract_rects(self._h, closed, fmt, first + at, part.shape[0], ptr(part), None, capi.VRC_MEM_HOST, None))
-        return out
+        return _fetch_all(lambda at, n, out, total: check(L.vrc_extract_rects(self._h, closed, fmt, at, n, out, total, capi.VRC_MEM_HOST, None)),
+                          first, capacity, per_rect, dtype, self.SURFACE_WINDOW)
 
     def surfaceRects(self, closed=True, first=0, capacity=None):
         """(n, 4) uint32 x y z w: the rectangles [first, first + capacity) of the order (d, c_a, s0, r0), each named by its
@@ -1284,11 +1257,8 @@ class VoxelLabels:
 
     def components(self, first=0, capacity=None):
         """the records [first, first + capacity) that exist, as capi.COMPONENT_DTYPE (first, lo, hi, voxels)"""
-        if capacity is None:
-            capacity = max(self.count - first, 0)
-        out = np.zeros(min(capacity, max(self.count - first, 0)), capi.COMPONENT_DTYPE)
-        check(capi.load().vrc_labels_components(self._h, first, len(out), ptr(out) if len(out) else None, capi.VRC_MEM_HOST, None))
-        return out
+        return _fetch_known(lambda at, n, out: check(capi.load().vrc_labels_components(self._h, at, n, out, capi.VRC_MEM_HOST, None)),
+                            self.count, first, capacity, capi.COMPONENT_DTYPE)
 
     def componentsDevice(self, first, capacity, out_ptr, stream=None):
         check(capi.load().vrc_labels_components(self._h, first, capacity, ptr(out_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
@@ -1363,11 +1333,8 @@ class VoxelLabels:
         """the raw moments of the pieces [first, first + capacity) that exist, as capi.MOMENTS_DTYPE: voxels, s1 (the sums of
         c = 2p + 1 per axis) and s2 (the sums of c_x c_x, c_y c_y, c_z c_z, c_x c_y, c_x c_z, c_y c_z) -- include/vrc.h:
         vrc_rigid_moments.  Exact integers."""
-        if capacity is None:
-            capacity = max(self.count - first, 0)
-        out = np.zeros(min(capacity, max(self.count - first, 0)), capi.MOMENTS_DTYPE)
-        check(capi.load().vrc_rigid_moments(self._h, first, len(out), ptr(out) if len(out) else None, capi.VRC_MEM_HOST, None))
-        return out
+        return _fetch_known(lambda at, n, out: check(capi.load().vrc_rigid_moments(self._h, at, n, out, capi.VRC_MEM_HOST, None)),
+                            self.count, first, capacity, capi.MOMENTS_DTYPE)
 
     def momentsDevice(self, first, capacity, out_ptr, stream=None):
         """the same into device memory (80 bytes a record), asynchronous on `stream`"""
@@ -1533,11 +1500,8 @@ class VoxelLabels:
     def pieceSites(self, first=0, capacity=None):
         """uint32 per piece of [first, first + capacity) that exists: the index of the site whose cell the piece lies in,
         capi.VRC_NO_COMPONENT for "none" -- labels made by VoxelVolume.fracture only (include/vrc.h: vrc_fracture_piece_sites)"""
-        if capacity is None:
-            capacity = max(self.count - first, 0)
-        out = np.zeros(min(capacity, max(self.count - first, 0)), np.uint32)
-        check(capi.load().vrc_fracture_piece_sites(self._h, first, len(out), ptr(out) if len(out) else None, capi.VRC_MEM_HOST, None))
-        return out
+        return _fetch_known(lambda at, n, out: check(capi.load().vrc_fracture_piece_sites(self._h, at, n, out, capi.VRC_MEM_HOST, None)),
+                            self.count, first, capacity, np.uint32)
 
     def pieceSitesDevice(self, first, capacity, out_ptr, stream=None):
         """the same into device memory, asynchronous on `stream`"""
@@ -1680,11 +1644,8 @@ class VoxelDelta:
 
     def records(self, first=0, capacity=None):
         """the records [first, first + capacity) that exist, as capi.DELTA_RECORD_DTYPE (word, bits)"""
-        if capacity is None:
-            capacity = max(self.count - first, 0)
-        out = np.zeros(min(capacity, max(self.count - first, 0)), capi.DELTA_RECORD_DTYPE)
-        check(capi.load().vrc_delta_records(self._h, first, len(out), ptr(out) if len(out) else None, capi.VRC_MEM_HOST, None))
-        return out
+        return _fetch_known(lambda at, n, out: check(capi.load().vrc_delta_records(self._h, at, n, out, capi.VRC_MEM_HOST, None)),
+                            self.count, first, capacity, capi.DELTA_RECORD_DTYPE)
 
     def recordsDevice(self, first, capacity, out_ptr, stream=None):
         """the same into device memory, asynchronous on `stream`"""
@@ -1807,6 +1768,33 @@ class Grid3D:
             self.close()
         except Exception:
             pass
+
+
+def _fetch_all(call, first, capacity, per, dtype, window):
+    """(n, per) records [first, first + capacity) of a windowed list whose total only the library knows (capacity=None:
+    everything from `first` on).  call(first, n, out_ptr, total_ref) wraps the C entry point: one call with capacity 0 asks
+    the total, then the records come in windows of at most `window`."""
+    total = C.c_uint64()
+    call(0, 0, None, C.byref(total))
+    first = int(first)
+    n = max(0, total.value - first)
+    if capacity is not None:
+        n = min(n, int(capacity))
+    out = np.zeros((n, per), dtype)
+    for at in range(0, n, window):
+        part = out[at:at + window]
+        call(first + at, part.shape[0], ptr(part), None)
+    return out
+
+
+def _fetch_known(call, count, first, capacity, dtype):
+    """the records [first, first + capacity) that exist of a list of `count` records, in one call(first, n, out_ptr); an
+    empty window still makes the call, with no buffer"""
+    if capacity is None:
+        capacity = max(count - first, 0)
+    out = np.zeros(min(capacity, max(count - first, 0)), dtype)
+    call(first, len(out), ptr(out) if len(out) else None)
+    return out
 
 
 def make_camera(position, rot, fov=1.0, aperture=0.0, focal_length=1.0):

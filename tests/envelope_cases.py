@@ -17,21 +17,21 @@ SCENES = ("slant", "ball", "products")
 
 # ---- the launch geometry --------------------------------------------------------------------------------------------
 
-GROUP = 256                          # vrc_distance.hip:37, vrc_fracture.hip:54: lanes of the z passes
-LANES = 64                           # vrc_distance.hip:38, vrc_fracture.hip:55: lines per workgroup of the min-plus passes
-LDS_STACK_MAX_DEPTH = 7              # vrc_distance.hip:39, vrc_fracture.hip:56
-WAVES_PER_CU = 8                     # vrc_distance.hip:40, vrc_fracture.hip:57
-Z_GROUPS_PER_CU = 16                 # vrc_distance.hip:284, vrc_fracture.hip:255: z_cap = cu_count * 16
+GROUP = 256                          # vrc_distance.hip:38, vrc_fracture.hip:54: lanes of the z passes
+LANES = 64                           # vrc_distance.hip:39, vrc_fracture.hip:55: lines per workgroup of the min-plus passes
+LDS_STACK_MAX_DEPTH = 7              # vrc_distance.hip:40, vrc_fracture.hip:56
+WAVES_PER_CU = 8                     # vrc_distance.hip:41, vrc_fracture.hip:57
+Z_GROUPS_PER_CU = 16                 # vrc_distance.hip:276, vrc_fracture.hip:255: z_cap = cu_count * 16
 CU_COUNT = 256                       # an MI355X
 
 
 def z_columns_per_step(S):
-    """vrc_distance.hip:44"""
+    """vrc_distance.hip:45"""
     return 2048 // S if S >= GROUP else GROUP // S
 
 
 def distance_z_groups(depth, cu_count=CU_COUNT):
-    """vrc_distance.hip:282-285: (workgroups wanted, workgroups launched) of k_distance_z"""
+    """vrc_distance.hip:274-277: (workgroups wanted, workgroups launched) of k_distance_z"""
     S = 1 << depth
     cpi = z_columns_per_step(S)
     want = (S * S + cpi - 1) // cpi
@@ -39,25 +39,25 @@ def distance_z_groups(depth, cu_count=CU_COUNT):
 
 
 def words_per_column(S):
-    """vrc_distance.hip:60"""
+    """vrc_distance.hip:52"""
     return S >> 5 if S >= 32 else 1
 
 
 def minplus_groups(depth, cu_count=CU_COUNT):
-    """vrc_distance.hip:258-263, vrc_fracture.hip:227-232"""
+    """vrc_distance.hip:250-255, vrc_fracture.hip:227-232"""
     want = ((1 << (2 * depth)) + LANES - 1) // LANES
     return min(want, max(cu_count, 1) * WAVES_PER_CU)
 
 
 def line_steps(depth, cu_count=CU_COUNT):
-    """vrc_distance.hip:140, vrc_fracture.hip:157: the steps of for (l0 = blockIdx.x * LANES; l0 < lines; l0 += gridDim.x * LANES)
+    """vrc_distance.hip:132, vrc_fracture.hip:157: the steps of for (l0 = blockIdx.x * LANES; l0 < lines; l0 += gridDim.x * LANES)
     that the first workgroup takes"""
     want = ((1 << (2 * depth)) + LANES - 1) // LANES
     return -(-want // minplus_groups(depth, cu_count))
 
 
 def stacks_in_lds(depth):
-    """vrc_distance.hip:288, vrc_fracture.hip:259"""
+    """vrc_distance.hip:280, vrc_fracture.hip:259"""
     return depth <= LDS_STACK_MAX_DEPTH
 
 
@@ -73,7 +73,7 @@ def fracture_z_geometry(depth, cu_count=CU_COUNT):
 # ---- the first walk, restated ---------------------------------------------------------------------------------------
 
 def first_walk(f, strict, reload_offset=2):
-    """vrc_distance.hip:147-170 (strict=False: a parabola is popped on >=) and vrc_fracture.hip:165-190 (strict=True: on >
+    """vrc_distance.hip:139-162 (strict=False: a parabola is popped on >=) and vrc_fracture.hip:165-190 (strict=True: on >
     alone) over one line of partial squared distances f (NONE: no entry): (the stack as a list of positions, the greatest
     top, the longest pop cascade of one push, the pops).  Python integers.  reload_offset is for experiments with a wrong
     walk: the entry read back after a pop, top - 2 in the kernels."""
@@ -107,7 +107,7 @@ def first_walk(f, strict, reload_offset=2):
 
 
 def second_walk(f, stack):
-    """vrc_distance.hip:172-195: the envelope's value at every i off the stack of first_walk; NONE for an empty stack"""
+    """vrc_distance.hip:164-187: the envelope's value at every i off the stack of first_walk; NONE for an empty stack"""
     S = len(f)
     if not stack:
         return [NONE] * S
@@ -299,7 +299,7 @@ def as_entries(lines):
 
 
 def y_lines(g0, picks):
-    """the lines the y pass reads, l = x * S + z (vrc_distance.hip:143): (n, S) over j"""
+    """the lines the y pass reads, l = x * S + z (vrc_distance.hip:135): (n, S) over j"""
     S = g0.shape[0]
     return as_entries(np.stack([g0[l // S, :, l % S] for l in picks]))
 

@@ -27,21 +27,21 @@ def apply_op(dst, bits, op):
 # ---- the labelling's geometry ---------------------------------------------------------------------------------------
 
 GROUP_KEYS = GROUP * 32              # vrc_components.hip:38-40: GROUP = 256, ROUNDS = 32, GROUP_KEYS = GROUP * ROUNDS
-SCAN_GROUP = 1024                    # vrc_group.h:10: the slots scan_slots takes in one step
+SCAN_GROUP = 1024                    # vrc_group.h, SCAN_GROUP: the slots scan_slots takes in one step
 
 
 def groups_of(depth):
-    """vrc_components.hip:267-271: workgroups of the labelling's kernels = slots of its scan"""
+    """vrc_components.hip:249-253: workgroups of the labelling's kernels = slots of its scan"""
     return ((1 << (3 * depth)) + GROUP_KEYS - 1) // GROUP_KEYS
 
 
 def scan_steps(n_slots):
-    """vrc_group.h:55: for (base = 0; base < n_slots; base += SCAN_GROUP)"""
+    """vrc_group.h, the loop of scan_slots: for (base = 0; base < n_slots; base += SCAN_GROUP)"""
     return -(-n_slots // SCAN_GROUP)
 
 
 def scan_slots(counts, carry=True):
-    """vrc_group.h:51-64 on an array of counts: (the exclusive prefix, the total).  carry=False is for experiments with a
+    """vrc_group.h, scan_slots, on an array of counts: (the exclusive prefix, the total).  carry=False is for experiments with a
     wrong scan: one whose steps each start from zero"""
     counts = np.asarray(counts, np.int64)
     out = np.zeros_like(counts)

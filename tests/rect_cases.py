@@ -12,9 +12,9 @@ import functools
 import numpy as np
 
 import rect_model as R
-from large_volume_cases import SCAN_GROUP, scan_slots, scan_steps          # vrc_group.h:10, 51-64, 55, restated once
+from large_volume_cases import SCAN_GROUP, scan_slots, scan_steps          # vrc_group.h: SCAN_GROUP, scan_slots and its loop, restated once
 
-GROUP = 256                          # vrc_rects.hip:35: lanes per workgroup
+GROUP = 256                          # vrc_list.h, LIST_GROUP: lanes per workgroup
 M32 = 0xFFFFFFFF
 UNWRITTEN = 0xEEEEEEEE               # what a record no lane wrote reads as in Emulation.records
 
@@ -22,27 +22,27 @@ UNWRITTEN = 0xEEEEEEEE               # what a record no lane wrote reads as in E
 # ---- a. the geometry ---------------------------------------------------------------------------------------------------
 
 def words_lg(depth):
-    """vrc_rects.hip:256: log2 of the words of a row"""
+    """vrc_rects.hip:235: log2 of the words of a row"""
     return depth - 5 if depth > 5 else 0
 
 
 def field_words(depth):
-    """vrc_rects.hip:258: words of one row field"""
+    """vrc_rects.hip:237: words of one row field"""
     return 1 << (2 * depth + words_lg(depth))
 
 
 def lanes_of(depth):
-    """vrc_rects.hip:260"""
+    """vrc_rects.hip:239"""
     return 6 * field_words(depth)
 
 
 def groups_of(depth):
-    """vrc_rects.hip:262: workgroups of the count and emit passes = slots of the scan"""
+    """vrc_rects.hip, groups_of: workgroups of the count and emit passes = slots of the scan"""
     return (lanes_of(depth) + GROUP - 1) // GROUP
 
 
 def lane_parts(L, depth):
-    """vrc_rects.hip:146-152: lane -> (d, c_a, c_s, k)"""
+    """vrc_rects.hip:143-149: lane -> (d, c_a, c_s, k)"""
     lgw, S1 = words_lg(depth), (1 << depth) - 1
     k = L & ((1 << lgw) - 1)
     t = L >> lgw
@@ -67,7 +67,7 @@ def lane_of(records, S):
 # ---- b. the kernels, word by word ----------------------------------------------------------------------------------------
 
 def row_fields(V):
-    """what k_rect_rows leaves (vrc_rects.hip:57-92, 264-270): the Z-rows [x][y][z bits] and behind them the Y-rows
+    """what k_rect_rows leaves (vrc_rects.hip: k_rect_rows, fields_of and rows_of): the Z-rows [x][y][z bits] and behind them the Y-rows
     [x][z][y bits], w = max(1, S / 32) words a row, bits past S zero; one flat uint32 array"""
     B = np.asarray(V) != 0
     S = B.shape[0]
@@ -81,7 +81,7 @@ def row_fields(V):
 
 
 def face_word(fields, depth, beyond, d, ca, cs, k):
-    """vrc_rects.hip:97-107 on the flat fields, index for index; k may lie beyond the row, as a wrong kernel's does.  A word
+    """vrc_rects.hip:94-104 on the flat fields, index for index; k may lie beyond the row, as a wrong kernel's does.  A word
     behind the fields reads as 0"""
     a, S, lgw = d >> 1, 1 << depth, words_lg(depth)
     base = field_words(depth) if a == 2 else 0
@@ -132,7 +132,7 @@ WRONG = {
 
 
 class Emulation:
-    """k_rect_count<false>, k_rect_scan and k_rect_emit<FACES> on row fields; wrong: one of WRONG.  The counters say which
+    """k_rect_count<false>, k_scan_slots and k_rect_emit<FACES> on row fields; wrong: one of WRONG.  The counters say which
     paths the field took: run_end calls by the words they went on to (loops), holds_run's visits of a word strictly between
     k0 and k1 and the calls decided there, the reads of the bit beside a word-aligned end, and the calls with r1 == S"""
 
@@ -155,7 +155,7 @@ class Emulation:
         return face_word(self.fields, self.depth, self.beyond, d, ca, cs, k)
 
     def run_end(self, base, k, m, b):
-        """vrc_rects.hip:110-118"""
+        """vrc_rects.hip:107-115"""
         inv = ~m & (M32 << b) & M32
         loops = 0
         while not inv:
@@ -171,7 +171,7 @@ class Emulation:
         return 32 * k + ctz(inv) if inv else 32 * (k + 1)
 
     def holds_run(self, base, r0, r1):
-        """vrc_rects.hip:121-136; base: the lane of word 0 of the row asked"""
+        """vrc_rects.hip:118-133; base: the lane of word 0 of the row asked"""
         k0, k1 = r0 >> 5, (r1 - 1) >> 5
         self.holds_calls += 1
         self.row_end_calls += r1 == self.S and not r1 & 31
@@ -204,7 +204,7 @@ class Emulation:
         return True
 
     def rect_starts(self, L):
-        """vrc_rects.hip:144-167 for a lane whose word has faces"""
+        """vrc_rects.hip:141-164 for a lane whose word has faces"""
         f, w = self.f, self.w
         m = f[L]
         k = L & (w - 1)
@@ -231,7 +231,7 @@ class Emulation:
         return self._starts
 
     def slots(self):
-        """(the slots after k_rect_scan, the total it reports)"""
+        """(the slots after k_scan_slots, the total it reports)"""
         counts = np.zeros(groups_of(self.depth), np.int64)
         for L, rs in self.starts():
             counts[L // GROUP] += bin(rs).count("1")
@@ -251,7 +251,7 @@ class Emulation:
             g = L // GROUP
             if g != group:
                 group, idx = g, int(edges[g])
-                leaves = edges[g] == edges[g + 1] or edges[g + 1] <= first or edges[g] >= win_end     # vrc_rects.hip:208
+                leaves = edges[g] == edges[g + 1] or edges[g + 1] <= first or edges[g] >= win_end     # vrc_list.h, list_window
             if leaves:
                 continue
             d, ca, cs, k = lane_parts(L, self.depth)

@@ -14,18 +14,18 @@ import flood_model
 import travel_model
 
 NONE = travel_model.NONE
-GROUP = 256                          # vrc_travel.hip:68: lanes per workgroup of every kernel of the travel field
-TV = 16                              # vrc_travel.hip:65: voxels per travel tile along an axis
+GROUP = 256                          # vrc_travel.hip:69: lanes per workgroup of every kernel of the travel field
+TV = 16                              # vrc_travel.hip:66: voxels per travel tile along an axis
 FV = 32                              # vrc_flood.hip:26: a flood tile is 16 x 16 x 4 words of 2 x 2 x 8 voxels
-STATS_GROUPS_MAX = 4096              # vrc_travel.hip:365
-BATCH_MAX = 8                        # vrc_travel.hip:64, vrc_flood.hip:25: sweeps between two reads of the counters
-TILE_ITERS = 64                      # vrc_travel.hip:63
+STATS_GROUPS_MAX = 4096              # vrc_travel.hip:357
+BATCH_MAX = 8                        # vrc_travel.hip:65, vrc_flood.hip:25: sweeps between two reads of the counters
+TILE_ITERS = 64                      # vrc_travel.hip:64
 
 
 # ---- the restated geometry --------------------------------------------------------------------------------------------
 
 def travel_tiles_per_axis(S):
-    """vrc_travel.hip:70"""
+    """vrc_travel.hip:71"""
     return S // TV if S >= TV else 1
 
 
@@ -35,7 +35,7 @@ def flood_tiles_per_axis(S):
 
 
 def travel_tile_of(xyz, S):
-    """vrc_travel.hip:119 (the init pass raises this flag) and :141 (the sweep splits it again): ((x / 16) T + y / 16) T + z / 16"""
+    """vrc_travel.hip:111 (the init pass raises this flag) and :133 (the sweep splits it again): ((x / 16) T + y / 16) T + z / 16"""
     xyz = np.asarray(xyz, np.int64)
     T = travel_tiles_per_axis(S)
     return ((xyz[..., 0] // TV) * T + xyz[..., 1] // TV) * T + xyz[..., 2] // TV
@@ -50,13 +50,13 @@ def flood_tile_of(xyz, S):
 
 
 def tile_split(tile, T):
-    """vrc_travel.hip:141, vrc_flood.hip:73: (tx, ty, tz) = (tile / (T T), (tile / T) % T, tile % T)"""
+    """vrc_travel.hip:133, vrc_flood.hip:73: (tx, ty, tz) = (tile / (T T), (tile / T) % T, tile % T)"""
     tile = np.asarray(tile, np.int64)
     return tile // (T * T), (tile // T) % T, tile % T
 
 
 def travel_scratch_bytes(depth):
-    """vrc_travel.hip:297-301"""
+    """vrc_travel.hip:289-293"""
     T = travel_tiles_per_axis(1 << depth)
     return 24 + (3 * T ** 3 + BATCH_MAX) * 4
 
@@ -68,21 +68,21 @@ def flood_scratch_bytes(depth):
 
 
 def stats_launch(depth):
-    """vrc_travel.hip:363-365: (quads, workgroups of k_travel_stats)"""
+    """vrc_travel.hip:355-357: (quads, workgroups of k_travel_stats)"""
     quads = 1 << (3 * depth - 2)
     want = (quads + GROUP - 1) // GROUP
     return quads, min(want, STATS_GROUPS_MAX)
 
 
 def quads_per_lane(depth):
-    """the iterations of the loop at vrc_travel.hip:239 that the lanes of the launch take (the same for all: a power of two)"""
+    """the iterations of the loop at vrc_travel.hip:231 that the lanes of the launch take (the same for all: a power of two)"""
     quads, groups = stats_launch(depth)
     return -(-quads // (groups * GROUP))
 
 
 def stats_lane(xyz, S, groups):
     """(iteration, workgroup, thread) of k_travel_stats that sees voxel xyz: qi = dense index / 4 = blockIdx GROUP + thread
-    + iteration gridDim GROUP (vrc_travel.hip:239-245)"""
+    + iteration gridDim GROUP (vrc_travel.hip:231-237)"""
     x, y, z = (int(v) for v in xyz)
     qi = ((x * S + y) * S + z) // 4
     lanes = groups * GROUP
@@ -90,10 +90,10 @@ def stats_lane(xyz, S, groups):
 
 
 def stats_pass(T, groups, drop_later=False, tie="index"):
-    """k_travel_stats (vrc_travel.hip:233-260) on a field T under `groups` workgroups: (reached, max, argmax) as the kernel
+    """k_travel_stats (vrc_travel.hip:225-252) on a field T under `groups` workgroups: (reached, max, argmax) as the kernel
     combines them -- a lane counts the values of its quads in 32 bits and keeps the largest (value << 32) | ~dense index
-    (:245-246), the workgroup takes the largest of its lanes (:249-254) and the sum of their counts (:255), and a 64-bit
-    atomic each joins the workgroups (:257-258); decode as vrc_snapshots.hip does: no value -> (0, 0, (0, 0, 0)).
+    (:237-238), the workgroup takes the largest of its lanes (:241-246) and the sum of their counts (:247), and a 64-bit
+    atomic each joins the workgroups (:249-250); decode as vrc_snapshots.hip does: no value -> (0, 0, (0, 0, 0)).
     For experiments with a wrong kernel: drop_later=True takes only each lane's first quad (a loop that never strides);
     tie="lane" breaks a tie of values by the lower thread, then the lower workgroup, then the earlier iteration -- by who saw
     it, not by where it lies."""
@@ -130,9 +130,9 @@ def stats_pass(T, groups, drop_later=False, tie="index"):
 
 
 def batches(n_sweeps, max_sweeps=None):
-    """the batch sizes of the host loop (vrc_travel.hip:336-358, vrc_flood.hip:225-248) when sweep `n_sweeps` is the first
+    """the batch sizes of the host loop (vrc_travel.hip:328-350, vrc_flood.hip:225-248) when sweep `n_sweeps` is the first
     to count 0: 2, 4, 8, 8, ... cut at max_sweeps; their sum is the `sweeps` the call reports, and every batch but the first
-    is preceded by a reset of the counters (:340)"""
+    is preceded by a reset of the counters (:332)"""
     out, issued, batch = [], 0, 2
     while True:
         b = batch if max_sweeps is None else min(batch, max_sweeps - issued)
@@ -268,7 +268,7 @@ def ties(which):
     """Two or three corridors of equal length whose ends lie in different quarters of x: the smallest dense index must win,
     whichever iteration or lane sees it.  The winners lie beyond the first quarter, so that a loop without later iterations
     loses them.  "lanes": a smaller index is never seen in a LATER iteration than a larger one (qi = index / 4 is monotone in
-    the index, vrc_travel.hip:239-245), so the pair that can tell a tie broken by who saw it from one broken by the index is
+    the index, vrc_travel.hip:231-237), so the pair that can tell a tie broken by who saw it from one broken by the index is
     the winner under the HIGHEST thread of a workgroup in an earlier iteration and the loser under thread 0 of the same
     workgroup in a later one: a combine that prefers the lower thread takes the loser."""
     s = Scene("ties_" + which, 8, quarter=min(TIE_PATHS[n][3] for n in TIES[which]) // 64)

@@ -2,7 +2,8 @@
 it can go wrong: the workgroup sum with idle lanes and idle waves, the two ways a destination word is written at the sizes
 on either side of the shared-word rule, and the staged call with a block that has to grow and on a stream of its own behind
 a device-memory edit, with every combination of optional parts in a block of the call's own, and with a part that goes up
-and comes back.  Every expectation is NumPy's (the models of tests/*_model.py); every comparison is exact."""
+and comes back; the window of the emit prologue the three lists share (vrc_list.h) and the paged fetch of the Python
+wrapper.  Every expectation is NumPy's (the models of tests/*_model.py); every comparison is exact."""
 import functools
 
 import numpy as np
@@ -10,12 +11,17 @@ import pytest
 
 import components_model
 import contact_model
+import delta_model
 import distance_model
 import fall_model
+import fracture_model
+import rect_cases
+import rect_model
 import rigid_model
 import stamp_model
 import surface_model
 import travel_model
+import voxels_model
 from volume_support import Stream, affine_records, volume_of
 
 pytestmark = pytest.mark.gpu
@@ -413,4 +419,128 @@ def test_contacts_in_device_memory_behind_an_edit_of_the_world_on_another_stream
     assert got["posed"].tolist() == voxels.tolist() and got["overlap"].tolist() == voxels.tolist()
     assert np.array_equal(d_world.download(), edited)
     for h in (labels, medium, d_world, big):
+        h.close()
+
+
+# ---- the windowed lists: the prologue of the emit pass (vrc_list.h: list_window) and the wrapper's paged fetch ------------
+#
+# The list tests (test_gpu_volume_surface / _voxels / _rects: test_windows) put window edges inside a lane, on a workgroup
+# edge and at first >= T, on 64^3 and 32^3 fields at 50 %; none of them has capacity 0 with a buffer, first = T + 1, a
+# capacity that overflows first + capacity, or both cuts inside lanes of different workgroups, and none uses these fields.
+
+SENTINEL = 0x5A5A5A5A
+LIST_KINDS = ("faces", "voxels_xyz", "voxels_neighbours", "rects")
+
+
+@functools.lru_cache(maxsize=None)
+def list_case(kind):
+    """(the field, the model's full list, records per lane of the emit pass), computed once and never written again"""
+    if kind == "rects":
+        vol = random_volume(4800, 4, 0.37)                      # 16^3: 6 * 256 lanes, 6 workgroups
+        want = rect_model.rects(vol, True)
+        lanes = np.bincount(rect_cases.lane_of(want, 16), minlength=rect_cases.lanes_of(4))
+    else:
+        vol = random_volume(4801, 5, 0.37)                      # 32^3: 1024 words, 4 workgroups
+        if kind == "faces":
+            want = surface_model.faces(vol, True)
+            lanes = surface_model.word_direction_counts(want, 32).sum(axis=1)
+        else:
+            want = voxels_model.voxels_dense(vol, voxels_model.SURFACE, None, True, kind == "voxels_neighbours")
+            lanes = np.bincount(surface_model.key_of(want[:, :3], 32) >> 5, minlength=1024)
+    assert lanes.sum() == len(want)
+    for a in (vol, want, lanes):
+        a.setflags(write=False)
+    return vol, want, lanes
+
+
+@pytest.mark.parametrize("kind", LIST_KINDS)
+def test_list_windows_through_the_shared_prologue(built, kind):
+    """every window into device memory pre-filled with a sentinel: the records are the slice of the model's list, and
+    everything beyond min(capacity, T - first) records is untouched"""
+    import torch
+    import cpuvoxelraycaster_amd as vrc
+    capi = vrc.capi
+    vol, want, lanes = list_case(kind)
+    T, per = want.shape
+    start = np.concatenate([[0], np.cumsum(lanes)])
+    groups = len(lanes) // 256
+    busy = np.flatnonzero(lanes >= 3)
+    a, b = int(busy[busy // 256 == 1][0]), int(busy[busy // 256 == groups - 2][-1])
+    first_cut, last_cut = int(start[a]) + 1, int(start[b]) + 2   # both inside a lane's run of records, workgroups apart
+    assert start[a] < first_cut < start[a + 1] and start[b] < last_cut < start[b + 1] and a // 256 < b // 256
+    windows = [(first_cut, last_cut - first_cut), (first_cut, 1), (5, 0), (T, 4), (T + 1, 4), (3, 2 ** 64 - 1)]
+    assert first_cut + 1 < start[a + 1]                          # the second window lies wholly inside lane a
+    volume = volume_of(vol)
+    fetch = {"faces": lambda *w: volume.extractSurfaceDevice(capi.VRC_SURFACE_FACES, *w),
+             "voxels_xyz": lambda *w: volume.extractVoxelsDevice(capi.VRC_VOXELS_SURFACE, capi.VRC_VOXELS_XYZ, *w),
+             "voxels_neighbours": lambda *w: volume.extractVoxelsDevice(capi.VRC_VOXELS_SURFACE, capi.VRC_VOXELS_NEIGHBOURS, *w),
+             "rects": lambda *w: volume.extractRectsDevice(capi.VRC_SURFACE_FACES, *w)}[kind]
+    for first, capacity in windows:
+        n = max(0, min(capacity, T - first))
+        dev = torch.full((n + 4, per), SENTINEL, dtype=torch.int32, device="cuda")
+        total = torch.zeros(1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        fetch(first, capacity, dev.data_ptr(), total.data_ptr())
+        torch.cuda.synchronize()
+        got = dev.cpu().numpy().view(np.uint32)
+        assert int(total.item()) == T, (first, capacity)
+        assert np.array_equal(got[:n], want[first:first + n]), (first, capacity)
+        assert (got[n:] == SENTINEL).all(), (first, capacity)
+    volume.close()
+
+
+def test_paged_fetch_is_the_same_at_any_window(built, monkeypatch):
+    """the six host-form list calls with SURFACE_WINDOW = 7 against the default window, whole and from 5 for 23; beyond the
+    total they are empty arrays of the right shape and dtype"""
+    import cpuvoxelraycaster_amd as vrc
+    volume = volume_of(random_volume(4802, 4, 0.37))
+    calls = {"surfaceFaces": (lambda **w: volume.surfaceFaces(**w), (0, 4), np.uint32),
+             "surfaceTriangles": (lambda **w: volume.surfaceTriangles(**w), (0, 9), np.int32),
+             "voxels": (lambda **w: volume.voxels(**w), (0, 3), np.uint32),
+             "voxels(neighbours)": (lambda **w: volume.voxels(neighbours=True, **w), (0, 4), np.uint32),
+             "surfaceRects": (lambda **w: volume.surfaceRects(**w), (0, 4), np.uint32),
+             "rectTriangles": (lambda **w: volume.rectTriangles(**w), (0, 9), np.int32)}
+    whole = {name: call() for name, (call, _, _) in calls.items()}
+    part = {name: call(first=5, capacity=23) for name, (call, _, _) in calls.items()}
+    assert vrc.VoxelVolume.SURFACE_WINDOW > 7
+    monkeypatch.setattr(vrc.VoxelVolume, "SURFACE_WINDOW", 7)
+    for name, (call, empty, dtype) in calls.items():
+        rows = empty[1] // 9 + 1                                  # two triangles a record
+        assert len(whole[name]) > 7 * rows * 3, name              # several windows
+        assert np.array_equal(whole[name][5 * rows:28 * rows], part[name]) and len(part[name]) == 23 * rows, name
+        assert np.array_equal(call(), whole[name]), name
+        assert np.array_equal(call(first=5, capacity=23), part[name]), name
+        for first in (len(whole[name]) // rows, len(whole[name]) // rows + 1):
+            for capacity in (None, 4):
+                got = call(first=first, capacity=capacity)
+                assert got.shape == empty and got.dtype == dtype, (name, first, capacity)
+    volume.close()
+
+
+def test_fetch_of_a_known_count(built):
+    """components, moments, pieceSites and records from 0, from 3 for 2, from count and from count + 1"""
+    vol = scattered_blocks()
+    sites = np.array([[2, 2, 2], [13, 13, 13]], np.int32)          # no block straddles the two cells
+    ids, rec, piece_sites = fracture_model.label(vol, sites, 6)
+    assert len(rec) == 7 and len(set(piece_sites.tolist())) == 2
+    moments = rigid_model.moments(ids, 7)
+    medium, empty = volume_of(vol), volume_of(np.zeros_like(vol))
+    labels, delta = medium.fracture(sites, 6), empty.diff(medium)
+    records, _ = delta_model.diff(delta_model.words_of(np.zeros_like(vol)), delta_model.words_of(vol), 4)
+    assert labels.count == 7 and delta.count == len(records) >= 5
+    for count, first, capacity in [(7, 0, None), (7, 3, 2), (7, 7, None), (7, 7, 3), (7, 8, None), (7, 8, 3)]:
+        k = slice(first, count if capacity is None else min(count, first + capacity))
+        got = labels.components(first, capacity)
+        assert got.dtype == labels.components().dtype and got.shape == (max(0, k.stop - first),)
+        for field in ("first", "lo", "hi", "voxels"):
+            assert np.array_equal(got[field], rec[k][field]), (first, capacity, field)
+        assert [rigid_model.moments_tuple(r) for r in labels.moments(first, capacity)] == moments[k], (first, capacity)
+        got = labels.pieceSites(first, capacity)
+        assert got.dtype == np.uint32 and np.array_equal(got, piece_sites[k]), (first, capacity)
+    n = delta.count
+    for first, capacity in [(0, None), (3, 2), (n, None), (n, 3), (n + 1, None), (n + 1, 3)]:
+        got = delta.records(first, capacity)
+        want = records[first:n if capacity is None else first + capacity]
+        assert got.dtype == delta.records().dtype and got.tobytes() == want.tobytes(), (first, capacity)
+    for h in (labels, delta, medium, empty):
         h.close()

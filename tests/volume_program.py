@@ -37,10 +37,10 @@ Sizes of the per-volume scratch blocks (Mirror.scratch_bytes), each restated wit
                        staged in a block of the call's own (vrc.h:1329-1330; vrc_snapshots.hip:82 gives these calls
                        stage_in_v = false, :896 and :915 size the parts), and select stages nothing (:937-941)
   mark field           8^(depth-1) (vrc_voxelize.hip:145)
-  surface offsets      8 (ceil(8^depth / 32 / 256) + 7) (vrc_surface.hip:145); the voxel lists use the same block and add
+  surface offsets      8 (ceil(8^depth / 32 / 256) + 7) (vrc_surface.hip, surface_scratch_bytes); the voxel lists use the same block and add
                        nothing (vrc_volume.hip:838-841); a refused voxel call reserves nothing (:871-873 come before :875)
-  rectangle block      8 (ceil(6 S^2 w / 256) + 7) + 8 S^2 w, w = max(1, S / 32) (vrc_rects.hip:258-282)
-  pack slots           64 + 8 (tiles + 1) (vrc_pack.hip:354)
+  rectangle block      8 (ceil(6 S^2 w / 256) + 7) + 8 S^2 w, w = max(1, S / 32) (vrc_rects.hip, rect_scratch_bytes)
+  pack slots           64 + 8 (tiles + 1) (vrc_pack.hip:327)
   flood block          4 (3 T^3 + 8), T = max(1, S / 32) (vrc_flood.hip:186-190), on the REGION
 """
 import functools
@@ -246,7 +246,7 @@ def voxel_list(vol, a, which=None, neighbours=False):
 def stale_emit(records, offsets_of, S, first, capacity, n):
     """the first n records of the caller's buffer after an emit pass that found ANOTHER list's offsets in the block: a
     workgroup (256 occupancy words, key >> 13) starts where `offsets_of`'s voxels before it end, and returns early where those
-    offsets show it nothing inside the window (vrc_voxels.hip:183-185, vrc_surface.hip:117-119); what no workgroup writes keeps
+    offsets show it nothing inside the window (vrc_list.h, list_window: the uniform return); what no workgroup writes keeps
     the guard"""
     groups = max(1, S ** 3 // 32 // 256)
     mine = surface_model.key_of(records[:, :3], S) >> 13
@@ -575,7 +575,7 @@ class Mirror:
                 out = (len(other), window, T)
                 total_left = len(other)
             elif a["order"] == "surface_behind":
-                # surfaceCount writes the six direction totals alone, behind the slot of the total (vrc_surface.hip:149-156):
+                # surfaceCount writes the six direction totals alone, behind the slot of the total (vrc_surface.hip, surface_direction_slots and surface_count_run):
                 # slots that no pass of the lists reads, so even unordered it leaves the extraction what it was
                 out = (surface_model.direction_counts(once(surface_model.faces, v0, a["closed"])), window, T)
             else:
