@@ -274,6 +274,9 @@ SYMBOLS = {
     "vrc_columns_profile": (_int, [_vp, _int, _vp, _vp, _int, _vp]),
     "vrc_columns_fill": (_int, [_vp, _int, _vp, _vp, _i32, _vp, _i32, _int, _int, _vp]),
     "vrc_columns_select": (_int, [_vp, _vp, _int, _u32, _u32, _int, _int, _vp]),
+    "vrc_levels_counts": (_int, [_vp, _u32, _vp, _int, _vp]),
+    "vrc_levels_reduce": (_int, [_vp, _vp, _u32, _u32, _int, _vp]),
+    "vrc_levels_expand": (_int, [_vp, _vp, _int, _vp]),
     "vrc_volume_xor_mesh": (_int, [_vp, _u64, _vp, _int, _vp]),
     "vrc_raster_mesh": (_int, [_vp, _u64, _vp, _int, _int, _int, _vp]),
     "vrc_volume_surface_count": (_int, [_vp, _int, _vp]),

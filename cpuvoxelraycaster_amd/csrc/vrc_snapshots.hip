@@ -7,7 +7,8 @@
 // routes read off it (vrc_travel_field, vrc_travel_trace_paths; kernels in vrc_travel.hip), and the difference of two volumes as a list of
 // changed words (vrc_delta_diff, vrc_delta_*; kernels in vrc_delta.hip).  Beside them, because they take two volumes under the same ordering
 // rule, the automaton step and the seeded fill (vrc_cells_*; kernels in vrc_cells.hip), and the calls that look and write along an
-// axis (vrc_columns_*; kernels in vrc_columns.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
+// axis (vrc_columns_*; kernels in vrc_columns.hip), and the calls between volumes of two depths (vrc_levels_*; kernels in
+// vrc_levels.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
 // event and no scratch: its host-memory calls stage in a block of their own, and what it selects or places goes into a volume
 // as an edit of that volume (staged_call in vrc_volume_state.h; the ordering of every entry point: the table in DESIGN.md).
 #include <hip/hip_runtime.h>
@@ -24,6 +25,7 @@
 #include "vrc_distance.h"
 #include "vrc_fall.h"
 #include "vrc_fracture.h"
+#include "vrc_levels.h"
 #include "vrc_rigid.h"
 #include "vrc_travel.h"
 #include "vrc_volume_state.h"
@@ -938,6 +940,59 @@ extern "C" int vrc_columns_select(vrc_volume* dst, vrc_volume* src, int directio
     if (e == hipSuccess) e = order_behind_edits(dst, st);
     if (e != hipSuccess) return vrc::fail_hip(e, what);
     vrc::columns_select_run(dst->d_bricks, src->d_bricks, dst->depth, direction, band_lo, band_hi, of, op, st);
+    if ((e = hipGetLastError()) == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
+    return done(e, what);
+}
+
+// ---- levels: the counts of the 2^k cubes, and volumes of two depths made from one another (the rules: include/vrc.h; the kernels: vrc_levels.hip) ----
+
+extern "C" int vrc_levels_counts(vrc_volume* src, uint32_t k, uint32_t* counts, int mem, void* stream)
+{
+    const char* what = "vrc_levels_counts";
+    if (!src) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
+    if (!counts) return vrc::fail(VRC_ERR_INVALID, "%s: null counts", what);
+    if (k == 0u || k > src->depth) return vrc::fail(VRC_ERR_INVALID, "%s: k %u not in [1, %u], the volume's depth", what, k, src->depth);
+    if (const int rc = check_mem(what, mem)) return rc;
+    const Call call = volume_call(src->device, mem, stream, src, false);
+    const StagePart parts[] = {{counts, (size_t)4u << (3u * (src->depth - k)), STAGE_OUT}};
+    return staged_call(what, call, parts, [&](void* const* d) { return vrc::levels_counts_run(src->d_bricks, src->depth, k, (uint32_t*)d[0], call.st); });
+}
+
+extern "C" int vrc_levels_reduce(vrc_volume* dst, vrc_volume* src, uint32_t lo, uint32_t hi, int op, void* stream)
+{
+    const char* what = "vrc_levels_reduce";
+    if (!dst || !src) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (dst == src) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
+    if (dst->device != src->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, dst->device, src->device);
+    if (dst->depth >= src->depth) return vrc::fail(VRC_ERR_INVALID, "%s: destination of depth %u is not below the source's %u", what, dst->depth, src->depth);
+    if (const int rc = check_op(what, op)) return rc;
+    // no count is above 8^k: a bound above 8^k + 1 selects what 8^k + 1 selects
+    const uint32_t k = src->depth - dst->depth, top = (1u << (3u * k)) + 1u, band_lo = lo < top ? lo : top, band_hi = hi < top ? hi : top;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(dst->device);
+    if (e == hipSuccess) e = order_behind_edits(src, st);
+    if (e == hipSuccess) e = order_behind_edits(dst, st);
+    if (e == hipSuccess) e = reserve(dst->d_levels, dst->levels_cap, vrc::levels_scratch_bytes(src->depth, k));
+    if (e == hipSuccess) e = vrc::levels_reduce_run(dst->d_bricks, src->d_bricks, src->depth, k, band_lo, band_hi, op, dst->d_levels, st);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    if ((e = hipGetLastError()) == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
+    return done(e, what);
+}
+
+extern "C" int vrc_levels_expand(vrc_volume* dst, vrc_volume* src, int op, void* stream)
+{
+    const char* what = "vrc_levels_expand";
+    if (!dst || !src) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (dst == src) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
+    if (dst->device != src->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, dst->device, src->device);
+    if (dst->depth <= src->depth) return vrc::fail(VRC_ERR_INVALID, "%s: destination of depth %u is not above the source's %u", what, dst->depth, src->depth);
+    if (const int rc = check_op(what, op)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipSetDevice(dst->device);
+    if (e == hipSuccess) e = order_behind_edits(src, st);
+    if (e == hipSuccess) e = order_behind_edits(dst, st);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    vrc::levels_expand_run(dst->d_bricks, dst->depth, src->d_bricks, dst->depth - src->depth, op, st);
     if ((e = hipGetLastError()) == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
     return done(e, what);
 }

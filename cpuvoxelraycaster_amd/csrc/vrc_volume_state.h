@@ -43,6 +43,10 @@ struct vrc_volume {
     // behind the edit and the next caller may bring another.
     hipEvent_t edit_done = nullptr;
     bool edit_pending = false;
+    // vrc_levels_reduce with this volume as dst and a level difference of 4 and more: the counts of its voxels' cells, grow-only,
+    // at most 64^3 of them (vrc_levels.h)
+    uint32_t* d_levels = nullptr;
+    size_t levels_cap = 0;
 };
 
 namespace {

@@ -752,6 +752,55 @@ public:
     void skyLit(HipVoxelVolume& dst, int direction) { selectColumns(dst, direction, 0u, 1u, VRC_COLUMNS_SOLID); }
     void topLayers(HipVoxelVolume& dst, int direction, uint32_t k) { selectColumns(dst, direction, 0u, k, VRC_COLUMNS_SOLID); }
     void sheltered(HipVoxelVolume& dst, int direction) { selectColumns(dst, direction, 1u, (1u << depth()) + 1u, VRC_COLUMNS_EMPTY); }
+    // Between depths (include/vrc.h: vrc_levels_*).  A cell of level k is the cube of 2^k voxels per axis at a multiple of 2^k.
+    // the density grid: the solid voxels of every cell of level k, 1 <= k <= depth, (S >> k)^3 counts with cell (X, Y, Z) at
+    // (X * Sc + Y) * Sc + Z.  Synchronous.
+    std::vector<uint32_t> cellCounts(uint32_t k)
+    {
+        flush();
+        const uint32_t d = depth();
+        std::vector<uint32_t> out((size_t)1u << (3u * (k <= d ? d - k : 0u)));          // a k beyond the depth is refused by the library, by its text
+        check(vrc_levels_counts(v_, k, out.data(), VRC_MEM_HOST, nullptr), "vrc_levels_counts");
+        return out;
+    }
+    // the band [lo, hi) of counts that a rule keeps at level k: at least one voxel of the cell, every one, at least half
+    enum class LevelRule { Any, All, Majority };
+    static void countRange(LevelRule rule, uint32_t k, uint32_t* lo, uint32_t* hi)
+    {
+        const uint32_t full = 1u << (3u * k);
+        *lo = rule == LevelRule::Any ? 1u : rule == LevelRule::All ? full : full / 2u;
+        *hi = full + 1u;
+    }
+    // dst, of a smaller depth, takes (op) the voxels whose cell of this volume holds lo <= count < hi solid voxels.  This
+    // volume is only read.  Asynchronous on `stream`.
+    void reduceInto(HipVoxelVolume& dst, uint32_t lo, uint32_t hi, int op = VRC_COPY_REPLACE, void* stream = nullptr)
+    {
+        flush();
+        dst.flush();
+        check(vrc_levels_reduce(dst.v_, v_, lo, hi, op, stream), "vrc_levels_reduce");
+    }
+    // a new volume of the smaller `depth` reduced by the rule
+    std::unique_ptr<HipVoxelVolume> reduced(uint32_t depth, LevelRule rule = LevelRule::Any)
+    {
+        std::unique_ptr<HipVoxelVolume> out(new HipVoxelVolume(depth, device_));
+        uint32_t lo = 0, hi = 0;
+        countRange(rule, this->depth() > depth ? this->depth() - depth : 0u, &lo, &hi);
+        reduceInto(*out, lo, hi);
+        return out;
+    }
+    // dst, of a greater depth, takes (op) this volume with every voxel repeated 2^k times per axis.  Asynchronous on `stream`.
+    void expandInto(HipVoxelVolume& dst, int op = VRC_COPY_REPLACE, void* stream = nullptr)
+    {
+        flush();
+        dst.flush();
+        check(vrc_levels_expand(dst.v_, v_, op, stream), "vrc_levels_expand");
+    }
+    std::unique_ptr<HipVoxelVolume> expanded(uint32_t depth)
+    {
+        std::unique_ptr<HipVoxelVolume> out(new HipVoxelVolume(depth, device_));
+        expandInto(*out);
+        return out;
+    }
     // xyz: n x 3 coordinates -> 0 / 1 each (0 outside the volume)
     std::vector<uint8_t> getVoxels(const std::vector<uint32_t>& xyz)
     {

@@ -270,6 +270,19 @@ def count_mask(counts):
     return mask
 
 
+def count_range(rule, k):
+    """the band (lo, hi) of cell counts of level k that a reduction rule keeps (VoxelVolume.reduceInto): "any" is at least one
+    of the cell's 8^k voxels, "all" every one, "majority" at least half, "empty" none; a pair (lo, hi) as it is"""
+    full = 8 ** int(k)
+    if isinstance(rule, str):
+        named = {"any": (1, full + 1), "all": (full, full + 1), "majority": (full // 2, full + 1), "empty": (0, 1)}
+        if rule not in named:
+            raise ValueError(f"count_range: rule {rule!r} is none of {sorted(named)}")
+        return named[rule]
+    lo, hi = rule
+    return int(lo), int(hi)
+
+
 def packed_info(data):
     """The header of a sparse tile stream (bytes, a uint8 numpy array or a uint8 torch tensor) as a capi.PackInfo, held to
     the header rules of include/vrc.h (vrc_pack_header): pure host, only the first 64 bytes are read."""
@@ -683,6 +696,74 @@ class VoxelVolume:
     def sheltered(self, direction):
         """a new volume: the empty voxels behind a solid one along `direction`, overhangs and caves alike"""
         return self.selectColumns(direction, 1, (1 << self.depth) + 1, capi.VRC_COLUMNS_EMPTY)
+
+    countRange = staticmethod(count_range)
+
+    def cellCounts(self, k, device=False):
+        """The density grid: uint32 (Sc, Sc, Sc) with Sc = S >> k, the number of solid voxels in every cube of 2^k voxels per
+        axis, 1 <= k <= depth (include/vrc.h: vrc_levels_counts); cellCounts(depth)[0, 0, 0] is solidCount().  device: the counts
+        stay on the device, as a torch tensor of dtype int32 (the same bits).  Synchronous."""
+        sc = 1 << max(self.depth - int(k), 0)
+        if device:
+            import torch
+            out = torch.empty((sc, sc, sc), dtype=torch.int32, device=f"cuda:{self.device}")
+            check(capi.load().vrc_levels_counts(self._h, int(k), ptr(out.data_ptr()), capi.VRC_MEM_DEVICE, None))
+            check(capi.load().vrc_stream_synchronize(self.device, None))
+            return out
+        out = np.empty((sc, sc, sc), np.uint32)
+        check(capi.load().vrc_levels_counts(self._h, int(k), ptr(out), capi.VRC_MEM_HOST, None))
+        return out
+
+    def cellCountsDevice(self, k, out_ptr, stream=None):
+        """the same into (S >> k)^3 uint32 in device memory, asynchronous on `stream`"""
+        check(capi.load().vrc_levels_counts(self._h, int(k), ptr(out_ptr), capi.VRC_MEM_DEVICE, ptr(stream)))
+
+    def reduceInto(self, dst, lo, hi, op=capi.VRC_COPY_REPLACE, stream=None):
+        """The volume `dst` of a smaller depth (same device) takes (op) the voxels whose cell of this volume -- the cube of 2^k
+        voxels per axis, k the difference of the depths -- holds lo <= count < hi solid voxels (include/vrc.h:
+        vrc_levels_reduce; count_range names the usual bands).  This volume is only read.  Asynchronous on `stream`; returns
+        dst."""
+        check(capi.load().vrc_levels_reduce(dst._h, self._h, min(int(lo), 0xFFFFFFFF), min(int(hi), 0xFFFFFFFF), int(op), ptr(stream)))
+        return dst
+
+    def expandInto(self, dst, op=capi.VRC_COPY_REPLACE, stream=None):
+        """The volume `dst` of a greater depth (same device) takes (op) this volume with every voxel repeated 2^k times per
+        axis: voxel p of dst is voxel p >> k of this one (include/vrc.h: vrc_levels_expand).  Asynchronous on `stream`; returns
+        dst."""
+        check(capi.load().vrc_levels_expand(dst._h, self._h, int(op), ptr(stream)))
+        return dst
+
+    def _made(self, depth, fill):
+        out = VoxelVolume(int(depth), self.device)
+        try:
+            fill(out)
+        except Exception:
+            out.close()
+            raise
+        return out
+
+    def reduced(self, depth, rule="any"):
+        """a new volume of the smaller `depth`: reduceInto with the band of count_range(rule, self.depth - depth) -- "any" is the
+        conservative proxy, "all" the interior, "majority" keeps the volume, or a pair (lo, hi)"""
+        lo, hi = count_range(rule, self.depth - int(depth))
+        return self._made(depth, lambda out: self.reduceInto(out, lo, hi))
+
+    def expanded(self, depth):
+        """a new volume of the greater `depth` that holds this one blown up"""
+        return self._made(depth, lambda out: self.expandInto(out))
+
+    def levels(self, rule="any"):
+        """the reductions of this volume to every depth from depth - 1 down to 2, finest first, each reduced directly from this
+        volume: count thresholds do not compose from level to level"""
+        out = []
+        try:
+            for depth in range(self.depth - 1, 1, -1):
+                out.append(self.reduced(depth, rule))
+        except Exception:
+            for v in out:
+                v.close()
+            raise
+        return out
 
     def getVoxels(self, xyz):
         """uint8 0 / 1 per (n, 3) voxel coordinate, 0 outside the volume.  Synchronous."""

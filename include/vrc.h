@@ -1416,6 +1416,58 @@ int vrc_columns_fill(vrc_volume *v, int axis, const uint32_t *rect /* 4, NULL = 
                      const int32_t *hi_map, int32_t hi_const, int op, int mem, void *stream);
 int vrc_columns_select(vrc_volume *dst, vrc_volume *src, int direction, uint32_t lo, uint32_t hi, int of, int op, void *stream);
 
+/* Levels: voxels between volumes of two depths -- the density grid of a volume, the coarse volume selected by it, and a coarse
+ * volume blown up again.  k >= 1 is a level difference.  A CELL of level k is the cube of 2^k voxels per axis whose low corner
+ * is a multiple of 2^k on every axis: cell (X, Y, Z) of a volume of size S holds the voxels p with p >> k == (X, Y, Z), there
+ * are S_c = S >> k cells per axis, and count(X, Y, Z) is the number of solid voxels in the cell, 0 .. 8^k.  The calls that cross
+ * depths otherwise (vrc_volume_stamp_affine, the posed pieces) point-sample: a stamp with scale 1/2 keeps one voxel of eight.
+ *
+ * vrc_levels_counts.  k is in 1 .. depth(src).  counts has S_c^3 entries in the dense order counts[(X * S_c + Y) * S_c + Z], the
+ * order of vrc_volume_download's solid[(x * S + y) * S + z]; every entry is written exactly once with the exact count (the
+ * largest, 8^10 = 2^30, fits), and k = depth gives one entry, the volume's solid count.  `mem` says where counts lives:
+ * VRC_MEM_HOST is staged in a block of the call's own and makes the call synchronous, VRC_MEM_DEVICE works in place and is
+ * asynchronous on `stream`.  Either way the call runs behind src's last asynchronous edit and is not an edit itself.  Two calls
+ * give identical bytes.
+ *
+ * vrc_levels_reduce.  depth(dst) < depth(src), and k is their difference: voxel P of dst is cell P of src.  With
+ * K = { P in dst : lo <= count(P) < hi }, dst becomes K (VRC_COPY_REPLACE), dst | K (VRC_COPY_OR) or dst & ~K (VRC_COPY_ANDNOT)
+ * over the whole of dst, as vrc_columns_select does it.  "Any voxel solid", the conservative proxy, is (1, 8^k + 1); "all solid",
+ * the interior, is (8^k, 8^k + 1); "at least half", which keeps the volume, is (8^k / 2, 8^k + 1); the empty cells are (0, 1).
+ * lo >= hi is a legal empty K, and an hi above 8^k + 1 means 8^k + 1.  Thresholds do not compose: reduce every level from the
+ * finest volume, not from the level before, unless the rule is "any" or "all".
+ *
+ * vrc_levels_expand.  depth(dst) > depth(src), k their difference.  With E = { p in dst : src(p >> k) solid }, dst becomes E,
+ * dst | E or dst & ~E over the whole of dst.  It is vrc_volume_stamp_affine with m = diag(65536 >> k), t = 0, bit for bit.
+ *
+ * Reduce and expand take two different volumes on one device, are asynchronous on `stream`, run behind the last asynchronous
+ * edits of both volumes and are recorded as dst's last edit; src is only read.  As for vrc_volume_copy_region, an edit of
+ * either volume that is still in flight on ANOTHER stream and was issued after the call is not ordered against it.
+ * VRC_ERR_INVALID as "<function>: <reason>", before any device call: a NULL volume, NULL counts, dst == src, volumes on
+ * different devices, k == 0 or k > depth, depth(dst) >= depth(src) for reduce and depth(dst) <= depth(src) for expand, an
+ * unknown op or mem.  vrc_volume_edit_scratch_bytes is unchanged by all three calls.
+ * The device (csrc/vrc_levels.hip, the switches: csrc/vrc_levels.h): a brick byte is a cell of level 1 and its count a
+ * popcount.  counts: k = 1 a lane per source word, four counts each; k = 2, 3 a lane per cell, 4 loads of two bytes or 16 of a
+ * word; k >= 4 a workgroup per 2048 words of a cell, summed over the group, and from k = 6, where a cell has several
+ * workgroups, added with 32-bit vector atomics onto counts zeroed on the stream -- integer sums, so the bytes are the same
+ * every time.  reduce: k = 1 a lane per dst word, which is four rows of eight contiguous source bytes; else a lane per dst
+ * voxel that counts its cell (k = 2, 3) or reads the count from a grow-only block of dst's, at most 1 MiB (k >= 4: dst has depth
+ * 6 at the most), the word being one ballot of its 32 lanes.  expand: a lane per dst word, at most four source bytes read.
+ * Every dst word has one owner and is stored whole, 4^3 included.
+ * Times: profiles/edit/levels_timing.json (tools/bench_levels.py; 512^3 on the MI355X, the counts in device memory, device time
+ * by events around 10 calls in a row, median of 5, the yardsticks in the same rounds; the 16 MiB source stays in the last-level
+ * cache from call to call, for the yardsticks alike), FastNoise terrain / 0.5 random field.  counts: k = 1 0.012 / 0.014 ms (64 MiB
+ * of counts written), k = 3 0.005 / 0.005 ms, k = 5 0.021 / 0.021 ms, k = 9 0.010 / 0.028 ms, next to vrc_volume_clone of the source,
+ * 0.052 / 0.049 ms -- a weak yardstick, it allocates and synchronises, so the expectation "k = 1 costs a clone" is not what was
+ * measured: 0.24 / 0.27 of one -- and vrc_volume_solid_count, 0.026 / 0.068 ms, of which k = 9, the same number, is 0.38 / 0.42.
+ * k = 5 is the slowest form, four times k = 3: a cell's rows reach its workgroup in pieces of 16 bytes; k = 9 on the random
+ * field adds 2048 workgroup sums onto one word, where the terrain's empty workgroups add nothing -- what the code suggests,
+ * not measured apart.  reduce "any": to 256^3 0.008 ms, to 64^3 0.007 ms, to 4^3 (counts into the block,
+ * then the select) 0.015 / 0.023 ms.  expand 256^3 to 512^3: 0.013 / 0.014 ms next to 0.114 / 0.115 ms for
+ * vrc_volume_stamp_affine with m = diag(32768), 8.5 and 8.4 times faster.  No form is slower than its yardstick. */
+int vrc_levels_counts(vrc_volume *src, uint32_t k, uint32_t *counts, int mem, void *stream);
+int vrc_levels_reduce(vrc_volume *dst, vrc_volume *src, uint32_t lo, uint32_t hi, int op, void *stream);
+int vrc_levels_expand(vrc_volume *dst, vrc_volume *src, int op, void *stream);
+
 /* ---- dense grid: Grid3D<X,Y,Z> (grid_3d.hpp:10-138) ------------------- */
 
 /* cells[(x*Y + y)*Z + z] = Cell::Type (0 = Empty). */
