@@ -9,8 +9,8 @@ The switches of csrc/vrc_levels.hip (vrc_levels.h), and the (source depth, k) pa
            k = 2, 3 counted in the lane (4 -> 2, 5 -> 3, 5 -> 2, 6 -> 3, ...) | k >= 4 counts in the scratch block first
            (6 -> 2, 7 -> 3, 7 -> 2; 8 -> 2 is k = 6, where the scratch counts take atomics).
   dst      4^3 keeps two brick rows in a word: every source depth reduces down to depth 2.
-No launch below 512^3 reaches the cap of 16384 workgroups, so no lane takes a second item at these sizes; the strides are the
-same loops."""
+No launch below 512^3 reaches the cap of 16384 workgroups, so no lane takes a second item at these sizes; the second and later
+trips of every grid-stride loop run in test_gpu_volume_levels_large.py, at 512^3 and 1024^3 (the cases: levels_cases.py)."""
 import functools
 
 import numpy as np
@@ -285,6 +285,65 @@ def test_reduce_sees_an_edit_in_flight(built, dst_depth):
         dst.close()
 
 
+def edit_in_flight(S, seed, density=0.3):
+    """(base, edited, the 200000 points between them as a device tensor): edited differs from base"""
+    import torch
+    rng = np.random.default_rng(seed)
+    base = (rng.random((S, S, S)) < density).astype(np.uint8)
+    extra = rng.integers(0, S, (200000, 3)).astype(np.uint32)
+    edited = base.copy()
+    edited[tuple(extra.T.astype(np.int64))] = 1
+    assert not np.array_equal(base, edited)
+    t_extra = torch.from_numpy(extra.view(np.int32)).cuda()
+    torch.cuda.synchronize()
+    return base, edited, t_extra
+
+
+def test_counts_see_an_edit_in_flight(built):
+    """the counts run behind src's last asynchronous edit, on its stream and on another one"""
+    import torch
+    base, edited, t_extra = edit_in_flight(64, 65)
+    for k in (1, 3, 4):
+        want = model.counts(edited, k)
+        assert not np.array_equal(want, model.counts(base, k))
+        for other_stream in (False, True):
+            src = volume_of(base, 6)
+            out = torch.full(want.shape, -1, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            with Stream() as stream, Stream() as second:
+                src.setVoxelsDevice(len(t_extra), t_extra.data_ptr(), True, stream)
+                src.cellCountsDevice(k, out.data_ptr(), second if other_stream else stream)
+            got = out.cpu().numpy().view(np.uint32)
+            assert np.array_equal(got, want), (k, other_stream, differing(got, want))
+            src.close()
+
+
+@pytest.mark.parametrize("edit_of", ["src", "dst"])
+def test_expand_sees_an_edit_in_flight(built, edit_of):
+    """64^3 into 128^3 behind a device-memory setVoxels on a stream -- of the source, and of the destination (OR, so that the
+    destination's edit stays to be seen) -- on the same stream and on another one"""
+    import cpuvoxelraycaster_amd as vrc
+    src_vol = field(6, seed=41, density=0.3)
+    if edit_of == "src":
+        base, edited, t_extra = edit_in_flight(64, 66)
+        want, op = model.expand(np.zeros((128, 128, 128), np.uint8), edited), REPLACE
+        assert not np.array_equal(want, model.expand(np.zeros((128, 128, 128), np.uint8), base))
+    else:
+        base, edited, t_extra = edit_in_flight(128, 67, density=0.05)
+        want, op = model.expand(edited, src_vol, OR), OR
+        assert not np.array_equal(want, model.expand(base, src_vol, OR))
+    for other_stream in (False, True):
+        src = volume_of(base, 6) if edit_of == "src" else random_volume(6, seed=41, density=0.3)
+        dst = vrc.VoxelVolume(7) if edit_of == "src" else volume_of(base, 7)
+        with Stream() as stream, Stream() as second:
+            (src if edit_of == "src" else dst).setVoxelsDevice(len(t_extra), t_extra.data_ptr(), True, stream)
+            src.expandInto(dst, op, second if other_stream else stream)
+            got = dst.download()                                   # behind dst's last edit, the expand
+        assert np.array_equal(got, want), (edit_of, other_stream, differing(got, want))
+        src.close()
+        dst.close()
+
+
 def test_reduced_volume_commits(built):
     vol = field(6, seed=37, density=0.45)
     src = random_volume(6, seed=37, density=0.45)
@@ -314,3 +373,65 @@ def test_terrain_256(built, heights):
             assert np.array_equal(got, want), (dst_depth, rule, differing(got, want))
             coarse.close()
     src.close()
+
+
+# ---- 9. the smallest sources: 4^3 is two words and one cell of level 2 ---------------------------------------------------
+
+def test_depth_2_and_3_sources(built):
+    import cpuvoxelraycaster_amd as vrc
+    single = np.zeros((4, 4, 4), np.uint8)
+    single[3, 2, 1] = 1
+    for vol in (field(2), field(2, seed=3, density=0.8), np.ones((4, 4, 4), np.uint8), np.zeros((4, 4, 4), np.uint8), single):
+        src = volume_of(vol, 2)
+        for k in (1, 2):
+            got, want = src.cellCounts(k), model.counts(vol, k)
+            assert got.dtype == np.uint32 and got.shape == want.shape == (4 >> k,) * 3 and np.array_equal(got, want), (k, got.tolist(), want.tolist())
+        assert int(src.cellCounts(2)[0, 0, 0]) == src.solidCount() == vol.sum()
+        assert np.array_equal(src.download(), vol)
+        src.close()
+    for seed in (11, 12):
+        vol = field(3, seed=seed)
+        src = random_volume(3, seed=seed)
+        got = src.cellCounts(3)
+        assert got.shape == (1, 1, 1) and int(got[0, 0, 0]) == vol.sum() == src.solidCount()
+        small = vrc.VoxelVolume(2)
+        for rule in ("majority", "any", "all"):
+            src.reduceInto(small, *model.count_range(rule, 1))
+            assert np.array_equal(small.download(), model.reduced(vol, 2, rule)), (seed, rule)
+        small.close()
+        src.close()
+
+
+# ---- 10. one destination for its whole life, under level differences that take the scratch block, leave it and come back ---
+
+def test_one_destination_under_alternating_level_differences(built, heights):
+    """into 4^3: k = 4 (counts stored), 6 (atomics on a block zeroed on the stream), 5 (stored), 6 again from other content,
+    3 (no block); into 8^3 the same sources are k = 3, 5, 4, 5, 2.  A kernel that counted on finding the block clean, or on an
+    earlier call's memset, leaves an earlier source's counts in the result.  vrc_volume_edit_scratch_bytes of neither volume
+    moves"""
+    import cpuvoxelraycaster_amd as vrc
+    terrain = terrain_volume(heights, 8)
+    sources = [(field(6), lambda: random_volume(6)), (field(8, seed=23), lambda: random_volume(8, seed=23)), (field(7), lambda: random_volume(7)),
+               (terrain, lambda: vrc.VoxelVolume(8).raiseTerrain(heights)), (field(5), lambda: random_volume(5))]
+    dsts = {2: vrc.VoxelVolume(2), 3: vrc.VoxelVolume(3)}
+    scratch = {d: v.editScratchBytes() for d, v in dsts.items()}
+    for step, (vol, make) in enumerate(sources):
+        src = make()
+        src_scratch = src.editScratchBytes()
+        depth = vol.shape[0].bit_length() - 1
+        for dst_depth, dst in dsts.items():
+            k = depth - dst_depth
+            c = np.sort(model.counts(vol, k).reshape(-1).astype(np.int64))
+            lo = int(c[c > 0][(c > 0).sum() // 2])                             # a band that splits the cells
+            assert 0 < (c >= lo).sum() < len(c)
+            for band, op in (((lo, 8 ** k + 1), REPLACE), ((1, lo), OR), ((lo, 8 ** k + 1), ANDNOT)):
+                before = dst.download()
+                src.reduceInto(dst, *band, op)
+                got, want = dst.download(), model.reduce(before, vol, *band, op)
+                assert np.array_equal(got, want), (step, depth, dst_depth, band, op, differing(got, want))
+            assert dst.editScratchBytes() == scratch[dst_depth], (step, dst_depth)
+        assert np.array_equal(src.cellCounts(depth), [[[vol.sum()]]])
+        assert src.editScratchBytes() == src_scratch, step
+        src.close()
+    for dst in dsts.values():
+        dst.close()
