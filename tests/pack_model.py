@@ -77,17 +77,30 @@ def mask_words(bits, s):
     return np.packbits(padded, axis=-1, bitorder="little").view("<u4")
 
 
+def solid_of(bricks):
+    """the solid voxels of an array of brick bytes, a slice at a time: no array eight times the bricks' size"""
+    flat = np.ascontiguousarray(bricks).reshape(-1)
+    return sum(int(np.bincount(flat[at:at + (1 << 24)], minlength=256) @ POPCOUNT) for at in range(0, flat.size, 1 << 24))
+
+
 def pack(solid, depth):
+    assert np.asarray(solid).shape == (1 << depth,) * 3
+    return pack_bricks(bricks_of(solid), depth)
+
+
+def pack_bricks(bricks, depth):
+    """the stream of the [cx, cy, cz] brick bytes of bricks_of: what the large volumes are packed from, which need no dense
+    array then"""
     s = Shape(depth)
-    assert np.asarray(solid).shape == (s.S,) * 3
-    tiles = tiles_of(bricks_of(solid), s)
+    assert np.asarray(bricks).shape == (s.n,) * 3 and bricks.dtype == np.uint8
+    tiles = tiles_of(bricks, s)
     some, full = tiles != 0, tiles == 0xFF
     cls = np.where(~some.any(1), 0, np.where(full.all(1), 1, 2)).astype(np.uint32)
     mixed = np.flatnonzero(cls == 2)
     partial = some[mixed] & ~full[mixed]
     M, P = len(mixed), int(partial.sum())
     length = s.offsets(M, P)[4]
-    solid_count = int(POPCOUNT[tiles].sum())
+    solid_count = solid_of(tiles)
     head = struct.pack("<6IQQ6I", MAGIC, VERSION, depth, s.NT, M, P, length, solid_count, int((cls == 1).sum()), 0, 0, 0, 0, 0)
     fields = np.zeros(16 * s.CW, np.uint32)
     fields[:s.NT] = cls
@@ -134,6 +147,12 @@ def header_rule(stream, depth=None, n_bytes=None):
 def unpack(stream, depth):
     """the dense [x, y, z] occupancy, or (rule, where): the first canonical rule the stream breaks, in the header's order, and
     "tile <t>" / "byte <offset>" of its least offender (None for the rules that have none)"""
+    out = unpack_bricks(stream, depth)
+    return out if isinstance(out, tuple) else dense_of(out)
+
+
+def unpack_bricks(stream, depth):
+    """unpack, with the [cx, cy, cz] brick bytes in the dense array's place"""
     stream = bytes(stream)
     rule = header_rule(stream, depth)
     if rule:
@@ -183,7 +202,7 @@ def unpack(stream, depth):
     at = np.flatnonzero(D[P:] != 0)
     if len(at):
         broken["padding"] = "byte %d" % (d + P + at[0])
-    counted = 8 * s.K * n_full + 8 * int(full.sum()) + int(POPCOUNT[D[:P]].sum())
+    counted = 8 * s.K * n_full + 8 * int(full.sum()) + solid_of(D[:P])
     if counted != solid_claimed:
         broken["solid-count"] = None
     for rule in DEVICE_RULES:
@@ -194,7 +213,7 @@ def unpack(stream, depth):
     mixed_tiles = np.where(full[:, :s.K], 0xFF, 0).astype(np.uint8)
     mixed_tiles[(some & ~full)[:, :s.K]] = D[:P]
     tiles[mixed] = mixed_tiles
-    return dense_of(bricks_from_tiles(tiles, s))
+    return bricks_from_tiles(tiles, s)
 
 
 def set_words(stream, at, *values):
