@@ -18,6 +18,10 @@ VRC_CELLS_FACES, VRC_CELLS_ALL = 6, 26
 VRC_FLOOD_SOLID, VRC_FLOOD_EMPTY = 0, 1
 VRC_COLUMNS_SOLID, VRC_COLUMNS_EMPTY = 1, 2
 VRC_COLUMN_NONE = 0xffffffff
+VRC_MORPH_DILATE, VRC_MORPH_ERODE = 0, 1
+VRC_MORPH_SOLID, VRC_MORPH_EMPTY = 1, 2
+VRC_MORPH_REACH = 16
+VRC_MORPH_MAX_OFFSETS = 1 << 20
 VRC_NO_COMPONENT = 0xffffffff
 VRC_DISTANCE_NONE = 0xffffffff
 VRC_STROKE_LIMIT = 8192
@@ -277,6 +281,7 @@ SYMBOLS = {
     "vrc_levels_counts": (_int, [_vp, _u32, _vp, _int, _vp]),
     "vrc_levels_reduce": (_int, [_vp, _vp, _u32, _u32, _int, _vp]),
     "vrc_levels_expand": (_int, [_vp, _vp, _int, _vp]),
+    "vrc_morph_apply": (_int, [_vp, _vp, _int, _int, _u64, _vp, _vp, _int, _int, _int, _vp]),
     "vrc_volume_xor_mesh": (_int, [_vp, _u64, _vp, _int, _vp]),
     "vrc_raster_mesh": (_int, [_vp, _u64, _vp, _int, _int, _int, _vp]),
     "vrc_volume_surface_count": (_int, [_vp, _int, _vp]),

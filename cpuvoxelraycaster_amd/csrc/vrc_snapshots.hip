@@ -8,7 +8,7 @@
 // changed words (vrc_delta_diff, vrc_delta_*; kernels in vrc_delta.hip).  Beside them, because they take two volumes under the same ordering
 // rule, the automaton step and the seeded fill (vrc_cells_*; kernels in vrc_cells.hip), and the calls that look and write along an
 // axis (vrc_columns_*; kernels in vrc_columns.hip), and the calls between volumes of two depths (vrc_levels_*; kernels in
-// vrc_levels.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
+// vrc_levels.hip), and the dilation and erosion by a list of offsets (vrc_morph_apply; kernels in vrc_morph.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
 // event and no scratch: its host-memory calls stage in a block of their own, and what it selects or places goes into a volume
 // as an edit of that volume (staged_call in vrc_volume_state.h; the ordering of every entry point: the table in DESIGN.md).
 #include <hip/hip_runtime.h>
@@ -26,6 +26,7 @@
 #include "vrc_fall.h"
 #include "vrc_fracture.h"
 #include "vrc_levels.h"
+#include "vrc_morph.h"
 #include "vrc_rigid.h"
 #include "vrc_travel.h"
 #include "vrc_volume_state.h"
@@ -995,4 +996,44 @@ extern "C" int vrc_levels_expand(vrc_volume* dst, vrc_volume* src, int op, void*
     vrc::levels_expand_run(dst->d_bricks, dst->depth, src->d_bricks, dst->depth - src->depth, op, st);
     if ((e = hipGetLastError()) == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
     return done(e, what);
+}
+
+// ---- morphology: dilation and erosion by a list of offsets (the rule: include/vrc.h; the kernels: vrc_morph.hip) ----
+
+extern "C" int vrc_morph_apply(vrc_volume* dst, vrc_volume* src, int what_op, int of, uint64_t n, const int32_t* offsets, const int32_t* origin, int outside,
+                               int op, int mem, void* stream)
+{
+    const char* what = "vrc_morph_apply";
+    if (!dst || !src) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (dst == src) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
+    if (dst->depth != src->depth) return vrc::fail(VRC_ERR_INVALID, "%s: volumes of depths %u and %u", what, dst->depth, src->depth);
+    if (dst->device != src->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, dst->device, src->device);
+    if (what_op != VRC_MORPH_DILATE && what_op != VRC_MORPH_ERODE) return vrc::fail(VRC_ERR_INVALID, "%s: bad what %d", what, what_op);
+    if (of != VRC_MORPH_SOLID && of != VRC_MORPH_EMPTY) return vrc::fail(VRC_ERR_INVALID, "%s: bad of %d", what, of);
+    if (outside != 0 && outside != 1) return vrc::fail(VRC_ERR_INVALID, "%s: outside %d is neither 0 nor 1", what, outside);
+    if (const int rc = check_op(what, op)) return rc;
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (n > VRC_MORPH_MAX_OFFSETS) return vrc::fail(VRC_ERR_INVALID, "%s: %llu offsets, more than %u", what, (unsigned long long)n, VRC_MORPH_MAX_OFFSETS);
+    if (n && !offsets) return vrc::fail(VRC_ERR_INVALID, "%s: null offsets", what);
+    const int32_t pivot[3] = {origin ? origin[0] : 0, origin ? origin[1] : 0, origin ? origin[2] : 0};
+    if (mem == VRC_MEM_HOST)
+        for (uint64_t i = 0; i < n; ++i) {
+            const long long e[3] = {(long long)offsets[3u * i] - pivot[0], (long long)offsets[3u * i + 1u] - pivot[1], (long long)offsets[3u * i + 2u] - pivot[2]};
+            for (int a = 0; a < 3; ++a)
+                if (e[a] < -VRC_MORPH_REACH || e[a] > VRC_MORPH_REACH)
+                    return vrc::fail(VRC_ERR_INVALID, "%s: offset %llu is (%lld, %lld, %lld) after the origin, beyond +-%d", what, (unsigned long long)i, e[0], e[1],
+                                     e[2], VRC_MORPH_REACH);
+        }
+    hipError_t e = hipSetDevice(dst->device);
+    if (e == hipSuccess) e = order_behind_edits(src, (hipStream_t)stream);
+    // the prepared element: a block of dst's own, fixed in size; the calls that write it are dst's edits, one behind the other
+    if (e == hipSuccess && !dst->d_morph) e = hipMalloc(&dst->d_morph, vrc::MORPH_BLOCK_BYTES);
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    // the list is the call's one part: in host form it is staged in a block of the call's own and the call is synchronous
+    const Call call = volume_call(dst->device, mem, stream, dst, true);
+    const StagePart parts[] = {{offsets, (size_t)n * 12u, STAGE_IN}};
+    return staged_call(what, call, parts, [&](void* const* d) {
+        return vrc::morph_run(dst->d_bricks, src->d_bricks, dst->depth, what_op == VRC_MORPH_ERODE, of == VRC_MORPH_EMPTY, outside, n, (const int32_t*)d[0], pivot,
+                              op, dst->d_morph, call.st);
+    });
 }

@@ -329,6 +329,7 @@ void volume_free(vrc_volume* v)
     if (v->d_rects) (void)hipFree(v->d_rects);
     if (v->d_pack) (void)hipFree(v->d_pack);
     if (v->d_levels) (void)hipFree(v->d_levels);
+    if (v->d_morph) (void)hipFree(v->d_morph);
     v->grids.release();
     delete v;
 }

@@ -47,6 +47,8 @@ struct vrc_volume {
     // at most 64^3 of them (vrc_levels.h)
     uint32_t* d_levels = nullptr;
     size_t levels_cap = 0;
+    // vrc_morph_apply with this volume as dst: the prepared element (vrc_morph.h), allocated by the first call, fixed in size
+    void* d_morph = nullptr;
 };
 
 namespace {

@@ -752,6 +752,92 @@ public:
     void skyLit(HipVoxelVolume& dst, int direction) { selectColumns(dst, direction, 0u, 1u, VRC_COLUMNS_SOLID); }
     void topLayers(HipVoxelVolume& dst, int direction, uint32_t k) { selectColumns(dst, direction, 0u, k, VRC_COLUMNS_SOLID); }
     void sheltered(HipVoxelVolume& dst, int direction) { selectColumns(dst, direction, 1u, (1u << depth()) + 1u, VRC_COLUMNS_EMPTY); }
+    // Morphology by a structuring element (include/vrc.h: vrc_morph_apply).  An element is x y z per offset, every component
+    // within +-VRC_MORPH_REACH.
+    typedef std::vector<int32_t> Element;
+    // the offsets with d^2 <= r^2: the ball of dilate(r)
+    static Element elementBall(int32_t r)
+    {
+        Element e;
+        for (int32_t x = -r; x <= r; ++x)
+            for (int32_t y = -r; y <= r; ++y)
+                for (int32_t z = -r; z <= r; ++z)
+                    if (x * x + y * y + z * z <= r * r) { e.push_back(x); e.push_back(y); e.push_back(z); }
+        return e;
+    }
+    // the a x b x c box whose voxel `anchor` is the pivot (nullptr: a / 2, b / 2, c / 2)
+    static Element elementBox(int32_t a, int32_t b, int32_t c, const int32_t anchor[3] = nullptr)
+    {
+        const int32_t at[3] = {anchor ? anchor[0] : a / 2, anchor ? anchor[1] : b / 2, anchor ? anchor[2] : c / 2};
+        Element e;
+        for (int32_t x = 0; x < a; ++x)
+            for (int32_t y = 0; y < b; ++y)
+                for (int32_t z = 0; z < c; ++z) { e.push_back(x - at[0]); e.push_back(y - at[1]); e.push_back(z - at[2]); }
+        return e;
+    }
+    // the pivot and its six face neighbours
+    static Element elementCross()
+    {
+        const int32_t o[21] = {0, 0, 0, -1, 0, 0, 1, 0, 0, 0, -1, 0, 0, 1, 0, 0, 0, -1, 0, 0, 1};
+        return Element(o, o + 21);
+    }
+    // the offsets lo .. hi (both included) along `axis`
+    static Element elementLine(int axis, int32_t lo, int32_t hi)
+    {
+        Element e;
+        for (int32_t t = lo; t <= hi; ++t)
+            for (int a = 0; a < 3; ++a) e.push_back(a == axis ? t : 0);
+        return e;
+    }
+    static Element reflect(const Element& element)
+    {
+        Element e(element);
+        for (size_t i = 0; i < e.size(); ++i) e[i] = -e[i];
+        return e;
+    }
+    // dst takes (op) K = A (+) E (what = VRC_MORPH_DILATE) or A (-) E (VRC_MORPH_ERODE), A the solid voxels of this volume
+    // (its empty ones with of_empty) and, with `outside`, everything beyond the faces.  This volume is only read.  Synchronous.
+    void morph(HipVoxelVolume& dst, int what, const Element& element, bool of_empty = false, bool outside = false, int op = VRC_COPY_REPLACE,
+               const int32_t origin[3] = nullptr)
+    {
+        flush();
+        dst.flush();
+        check(vrc_morph_apply(dst.v_, v_, what, of_empty ? VRC_MORPH_EMPTY : VRC_MORPH_SOLID, element.size() / 3, element.data(), origin, outside ? 1 : 0, op,
+                              VRC_MEM_HOST, nullptr),
+              "vrc_morph_apply");
+    }
+    // the same with n offsets in device memory (a list of vrc_voxels_extract as it is, origin its pivot), asynchronous on `stream`
+    void morphDevice(HipVoxelVolume& dst, int what, uint64_t n, const int32_t* offsets_dev, const int32_t origin[3] = nullptr, bool of_empty = false,
+                     bool outside = false, int op = VRC_COPY_REPLACE, void* stream = nullptr)
+    {
+        flush();
+        dst.flush();
+        check(vrc_morph_apply(dst.v_, v_, what, of_empty ? VRC_MORPH_EMPTY : VRC_MORPH_SOLID, n, offsets_dev, origin, outside ? 1 : 0, op, VRC_MEM_DEVICE, stream),
+              "vrc_morph_apply");
+    }
+    void morphInPlace(int what, const Element& element, bool outside)
+    {
+        HipVoxelVolume scratch(depth(), device_);
+        morph(scratch, what, element, false, outside);
+        const uint32_t S = 1u << depth();
+        const uint32_t zero[3] = {0, 0, 0}, all[3] = {S, S, S};
+        const int32_t at[3] = {0, 0, 0};
+        copyRegion(scratch, zero, all, at);      // the scratch volume's destructor waits for it
+    }
+    // In place through a scratch volume.  Minkowski sums compose: a box is three lines in a row, a + b + c offsets for a b c.
+    void dilateBy(const Element& element) { morphInPlace(VRC_MORPH_DILATE, element, false); }
+    // open_border: everything beyond the faces counts as empty, so the erosion eats from the faces as well
+    void erodeBy(const Element& element, bool open_border = false) { morphInPlace(VRC_MORPH_ERODE, element, !open_border); }
+    void openBy(const Element& element) { erodeBy(element); dilateBy(element); }
+    void closeBy(const Element& element) { dilateBy(element); erodeBy(element); }
+    // dst becomes the pivots at which the shape stands free of the solid voxels and inside the volume
+    void fitsAt(HipVoxelVolume& dst, const Element& element) { morph(dst, VRC_MORPH_ERODE, element, true, false); }
+    // hit-or-miss: dst becomes the p with p + s solid for every s of solid_offsets and p + t empty for every t of empty_offsets
+    void match(HipVoxelVolume& dst, const Element& solid_offsets, const Element& empty_offsets, bool outside = false)
+    {
+        morph(dst, VRC_MORPH_ERODE, solid_offsets, false, outside);
+        morph(dst, VRC_MORPH_DILATE, reflect(empty_offsets), false, outside, VRC_COPY_ANDNOT);
+    }
     // Between depths (include/vrc.h: vrc_levels_*).  A cell of level k is the cube of 2^k voxels per axis at a multiple of 2^k.
     // the density grid: the solid voxels of every cell of level k, 1 <= k <= depth, (S >> k)^3 counts with cell (X, Y, Z) at
     // (X * Sc + Y) * Sc + Z.  Synchronous.

@@ -283,6 +283,48 @@ def count_range(rule, k):
     return int(lo), int(hi)
 
 
+def _element(offsets):
+    return np.ascontiguousarray(offsets, np.int32).reshape(-1, 3)
+
+
+def element_ball(r):
+    """(n, 3) int32: the offsets with d^2 <= r^2, the structuring element of VoxelVolume.dilate(r); r <= 16"""
+    r = int(r)
+    if r < 0:
+        raise ValueError(f"element_ball: negative radius {r}")
+    g = np.indices((2 * r + 1,) * 3).reshape(3, -1).T - r
+    return _element(g[(g.astype(np.int64) ** 2).sum(axis=1) <= r * r])
+
+
+def element_box(a, b, c, anchor=None):
+    """(a b c, 3) int32: the a x b x c box whose voxel `anchor` is the pivot (a // 2, b // 2, c // 2 by default)"""
+    at = (int(a) // 2, int(b) // 2, int(c) // 2) if anchor is None else tuple(int(v) for v in anchor)
+    return _element(np.indices((int(a), int(b), int(c))).reshape(3, -1).T - np.array(at))
+
+
+def element_cross():
+    """(7, 3) int32: the pivot and its six face neighbours"""
+    return _element([(0, 0, 0), (-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1)])
+
+
+def element_line(axis, lo, hi):
+    """(hi - lo + 1, 3) int32: the offsets lo .. hi (both included) along `axis`; element_line(0, 0, 6) smears 6 voxels along +x"""
+    e = np.zeros((max(int(hi) - int(lo) + 1, 0), 3), np.int32)
+    e[:, int(axis)] = np.arange(int(lo), int(hi) + 1)
+    return e
+
+
+def element_of(shape, pivot=(0, 0, 0)):
+    """(n, 3) int32: the solid voxels of a dense [x, y, z] array or of a VoxelVolume, relative to `pivot`"""
+    voxels = shape.voxels() if isinstance(shape, VoxelVolume) else np.argwhere(np.asarray(shape))
+    return _element(voxels.astype(np.int64) - np.asarray(pivot, np.int64).reshape(1, 3))
+
+
+def reflect(element):
+    """-E: the element of the dual operation (include/vrc.h: vrc_morph_apply)"""
+    return _element(-_element(element))
+
+
 def packed_info(data):
     """The header of a sparse tile stream (bytes, a uint8 numpy array or a uint8 torch tensor) as a capi.PackInfo, held to
     the header rules of include/vrc.h (vrc_pack_header): pure host, only the first 64 bytes are read."""
@@ -995,6 +1037,81 @@ class VoxelVolume:
         field.select(t * t + 1, capi.VRC_DISTANCE_NONE, self, capi.VRC_COPY_ANDNOT)
         field.close()
         return self
+
+    # ---- morphology by a structuring element of the caller's choice (include/vrc.h: vrc_morph_apply) ----
+
+    def morph(self, what, offsets, dst=None, of_empty=False, outside=False, op=capi.VRC_COPY_REPLACE, origin=None, stream=None):
+        """dst (a new volume with None) takes (op) K = A (+) E for what = capi.VRC_MORPH_DILATE, the p with some p - e in A, or
+        K = A (-) E for capi.VRC_MORPH_ERODE, the p with every p + e in A.  A is this volume's solid voxels (its empty ones with
+        of_empty) and, with `outside`, everything beyond the faces; E is the (n, 3) int32 `offsets` minus `origin`, every
+        component within +-16 (element_ball, element_box, element_cross, element_line, element_of make them).  This volume is
+        only read.  Synchronous; returns dst."""
+        e = _element(offsets)
+        o = None if origin is None else np.ascontiguousarray(origin, np.int32).reshape(3)
+        made = dst is None
+        if made:
+            dst = VoxelVolume(self.depth, self.device)
+        try:
+            check(capi.load().vrc_morph_apply(dst._h, self._h, int(what), capi.VRC_MORPH_EMPTY if of_empty else capi.VRC_MORPH_SOLID, e.shape[0], ptr(e), ptr(o),
+                                              int(bool(outside)), int(op), capi.VRC_MEM_HOST, ptr(stream)))
+        except Exception:
+            if made:
+                dst.close()
+            raise
+        return dst
+
+    def morphDevice(self, dst, what, n, offsets_ptr, origin=None, of_empty=False, outside=False, op=capi.VRC_COPY_REPLACE, stream=None):
+        """the same with n x 3 int32 in device memory, asynchronous on `stream`: a uint32 x y z list of extractVoxelsDevice goes in
+        as it is, with `origin` as the pivot.  An offset out of reach is dropped.  Returns dst."""
+        o = None if origin is None else np.ascontiguousarray(origin, np.int32).reshape(3)
+        check(capi.load().vrc_morph_apply(dst._h, self._h, int(what), capi.VRC_MORPH_EMPTY if of_empty else capi.VRC_MORPH_SOLID, int(n), ptr(offsets_ptr), ptr(o),
+                                          int(bool(outside)), int(op), capi.VRC_MEM_DEVICE, ptr(stream)))
+        return dst
+
+    def _morphInPlace(self, what, element, outside):
+        scratch = self.morph(what, element, outside=outside)
+        try:
+            size = 1 << self.depth
+            self.copyRegion(scratch, (0, 0, 0), (size, size, size), (0, 0, 0))
+        finally:
+            scratch.close()                                   # waits for the copy
+        return self
+
+    def dilateBy(self, element):
+        """Grows the solid set by the element in place (through a scratch volume that lives for the call): a voxel becomes
+        solid when p - e is solid for some e.  Minkowski sums compose, so a box is three line elements in a row --
+        dilateBy(element_line(0, -4, 4)).dilateBy(element_line(1, -4, 4)).dilateBy(element_line(2, -4, 4)) is the 9 x 9 x 9 box with
+        27 offsets for 729, the way to do large boxes cheaply."""
+        return self._morphInPlace(capi.VRC_MORPH_DILATE, element, False)
+
+    def erodeBy(self, element, open_border=False):
+        """Shrinks the solid set by the element in place: a voxel stays when p + e is solid for every e.  With open_border
+        everything beyond the faces counts as empty, so the erosion eats from the faces as well (as erode does)."""
+        return self._morphInPlace(capi.VRC_MORPH_ERODE, element, not open_border)
+
+    def openBy(self, element):
+        """erodeBy then dilateBy: keeps exactly the voxels that some copy of the element inside the solid set covers"""
+        return self.erodeBy(element).dilateBy(element)
+
+    def closeBy(self, element):
+        """dilateBy then erodeBy with the faces as walls: fills what no copy of the element in the empty set reaches"""
+        return self.dilateBy(element).erodeBy(element)
+
+    def fitsAt(self, element):
+        """A new volume: the pivots at which the shape stands free of the solid voxels and inside the volume -- the empty set
+        eroded by the element.  travelField through it (seeds and medium) is the shortest path of an agent of that shape."""
+        return self.morph(capi.VRC_MORPH_ERODE, element, of_empty=True, outside=False)
+
+    def match(self, solid_offsets, empty_offsets, outside=False):
+        """Hit-or-miss, a new volume: the p with p + s solid for every s of solid_offsets and p + t empty for every t of
+        empty_offsets; beyond the faces everything is solid with `outside`, else empty."""
+        out = self.morph(capi.VRC_MORPH_ERODE, solid_offsets, outside=outside)
+        try:
+            self.morph(capi.VRC_MORPH_DILATE, reflect(empty_offsets), out, outside=outside, op=capi.VRC_COPY_ANDNOT)
+        except Exception:
+            out.close()
+            raise
+        return out
 
     def xorMesh(self, tris_fixed, device=False, stream=None):
         """Solid voxelisation by crossing parity (include/vrc.h: vrc_volume_xor_mesh): (n, 9) int32 triangles in setCell

@@ -1468,6 +1468,63 @@ int vrc_levels_counts(vrc_volume *src, uint32_t k, uint32_t *counts, int mem, vo
 int vrc_levels_reduce(vrc_volume *dst, vrc_volume *src, uint32_t lo, uint32_t hi, int op, void *stream);
 int vrc_levels_expand(vrc_volume *dst, vrc_volume *src, int op, void *stream);
 
+/* Morphology with a structuring element of the caller's choice: the Minkowski sum and difference of a voxel set with a box, a
+ * line, a cross, a ball or the voxels of a piece.  (vrc_distance_select's grow / shrink knows the ball alone and builds a field of
+ * 4 bytes a voxel for it; vrc_cells_step reaches one voxel.)  "Grow by 3 x 5 x 3", "smear 6 voxels along +x", "where does THIS
+ * shape fit" -- erode the empty voxels by the shape, and vrc_travel_field through the result is the shortest path of a shaped
+ * agent -- and pattern search (hit-or-miss) are this one call.
+ *
+ * vrc_morph_apply.  The rule:
+ *   The set A.  Inside the volume, A holds the voxels of src that are solid (of == VRC_MORPH_SOLID) or empty (VRC_MORPH_EMPTY).
+ *     Beyond the faces, every lattice point belongs to A iff outside != 0.
+ *   The element E.  E = { offsets[i] - origin : 0 <= i < n } as a set; duplicates are legal.  Subtracting `origin` lets a
+ *     uint32 x y z list from vrc_voxels_extract (values below 2^31) be passed unchanged, with `origin` as the pivot: a piece
+ *     becomes an element without a host copy.
+ *   DILATE.  K = { p in the volume : some e in E has p - e in A }, that is A (+) E.
+ *   ERODE.   K = { p in the volume : every e in E has p + e in A }, that is A (-) E.
+ *   n == 0.  DILATE gives K empty, ERODE gives K the whole volume: the formulas taken literally, and legal.
+ *   dst becomes K (VRC_COPY_REPLACE), dst | K (VRC_COPY_OR) or dst & ~K (VRC_COPY_ANDNOT) over the whole of dst, as
+ *     vrc_columns_select does it.  src is only read.  The result is unique and does not depend on scheduling.
+ *   Duality.  ERODE(of, E, outside) is the complement of DILATE(the other `of`, -E, !outside).
+ * Minkowski sums compose: the dilation by a box a x b x c is three dilations by lines in a row, a + b + c offsets for a b c.
+ * The call is vrc_cells_step's kind: two different volumes of one depth on one device, asynchronous on `stream`, behind the last
+ * asynchronous edits of both volumes, recorded as dst's last edit.  `mem` says where `offsets` (n x 3 int32) lives:
+ * VRC_MEM_HOST stages the list in a block of the call's own and makes the call synchronous, VRC_MEM_DEVICE reads it in place.
+ * `origin` is three host ints (NULL = 0 0 0), read before the call returns.  vrc_volume_edit_scratch_bytes of both volumes is
+ * unchanged: the prepared element lives in a block of dst's own, 13312 bytes, allocated by the first call and fixed in size.
+ * VRC_ERR_INVALID as "vrc_morph_apply: <reason>", before any device call: NULL volumes, dst == src, different depths or devices,
+ * an unknown what, of, op or mem, outside not 0 or 1, n above VRC_MORPH_MAX_OFFSETS, NULL offsets with n != 0 and, in host
+ * memory, an offset with a component beyond +-VRC_MORPH_REACH after the origin is subtracted (in 64 bits; the text names the
+ * least such index).  In device memory the host cannot look: such an offset is DROPPED, which is vrc_volume_set_voxels's rule
+ * for coordinates outside.
+ * The device (csrc/vrc_morph.hip): a lane per offset ORs bit ez + 16 into the 64-bit z mask of column (ex, ey) of a 33 x 33 table
+ * (8712 bytes) -- duplicates fall together, what is out of reach falls out -- and one workgroup lists the non-empty columns and
+ * the element's box.  ERODE and `of` EMPTY are the same loop by the duality: complement on load, the list read negated,
+ * complement on store.  A workgroup owns 32 x 32 voxel columns and 32 voxels of z.  It brings the source in with the halo of the
+ * element's own box as PILLARS in LDS, per voxel column the 64 z bits from 16 below the tile, where a step along x or y is an
+ * index and a step along z a shift; a lane owns a brick column of the tile, four words along z, and per listed column ORs one
+ * shifted copy of its four pillars per set bit of the mask.  The cost follows the element's non-empty columns and the bits of
+ * their masks, not n and not the 33^3 cube.  Every dst word has one owner and is stored whole and once, without atomics, 4^3
+ * included.
+ * Times: profiles/edit/morph_timing.json (tools/bench_morph.py; 512^3 on the MI355X, the list in device memory, DILATE into a second volume, device
+ * time by events around 10 calls in a row, median of 5, A B A B with the yardstick in the same rounds and giving the same bits), FastNoise
+ * terrain / 0.5 random field.  The 3 x 3 x 3 cube 0.066 / 0.070 ms next to 0.069 / 0.071 ms for a 26-neighbour vrc_cells_step, 0.96 / 0.99 of it.
+ * The cross 0.058 / 0.059 ms next to 0.031 / 0.032 ms for the 6-neighbour step: 1.9 times SLOWER, the staging of the pillars is the floor
+ * of every call.  element_ball(r): r = 2 0.069 ms, r = 4 0.161 / 0.168 ms, r = 8 0.783 / 0.811 ms, next to 2.9 / 5.1 ms for
+ * vrc_volume_distance_field + vrc_distance_select whatever r, 42 / 74, 18 / 31 and 3.7 / 6.3 times faster, holding 13312 bytes where the field
+ * holds 512 MiB.  The cost follows the mask bits (33, 257, 2109 offsets: x 4.9 from r = 4 to r = 8), so no crossover was measured up to
+ * r = 8; at that growth the ball of r = 16 would cost 4 to 6 ms, about the field's time: the crossover lies near the reach, not
+ * measured.  The 9 x 9 x 9 box as one call 0.312 / 0.321 ms next to 0.154 / 0.155 ms for three line calls, 2.0 times SLOWER: compose boxes from
+ * lines.  The 33-voxel line 0.090 / 0.092 ms along x, 0.088 / 0.089 ms along y, 0.056 ms along z, where it is one column of 33 bits. */
+#define VRC_MORPH_DILATE 0
+#define VRC_MORPH_ERODE  1
+#define VRC_MORPH_SOLID  1      /* the set A is src's solid voxels */
+#define VRC_MORPH_EMPTY  2      /* ... src's empty voxels          */
+#define VRC_MORPH_REACH  16     /* |component of an offset| <= 16  */
+#define VRC_MORPH_MAX_OFFSETS (1u << 20)
+int vrc_morph_apply(vrc_volume *dst, vrc_volume *src, int what, int of, uint64_t n, const int32_t *offsets /* n x 3 */,
+                    const int32_t *origin /* 3, NULL = 0 */, int outside, int op, int mem, void *stream);
+
 /* ---- dense grid: Grid3D<X,Y,Z> (grid_3d.hpp:10-138) ------------------- */
 
 /* cells[(x*Y + y)*Z + z] = Cell::Type (0 = Empty). */
