@@ -1,6 +1,6 @@
 // vrc_cells.h -- one step of a neighbour-count automaton over a brick-word field and the seeded random fill of a box
-// (vrc_cells.hip), as vrc_snapshots.hip calls them.  The kernels know word arrays only; volumes and their ordering stay
-// with vrc_snapshots.hip.
+// (vrc_cells.hip), as vrc_volume_ops.hip calls them.  The kernels know word arrays only; volumes and their ordering stay
+// with vrc_volume_ops.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

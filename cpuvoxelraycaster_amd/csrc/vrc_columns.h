@@ -1,6 +1,6 @@
 // vrc_columns.h -- the occupancy looked at and written along an axis (vrc_columns.hip): the profile of every column of a
 // rectangle of a face, the fill of every column's span from two height maps, and the selection by the count of solid voxels
-// met before a voxel, as vrc_snapshots.hip calls them.  Like vrc_fall.h it knows arrays only; volumes, their ordering and
+// met before a voxel, as vrc_volume_ops.hip calls them.  Like vrc_fall.h it knows arrays only; volumes, their ordering and
 // the staging of the caller's lists stay with the entry points.
 #pragma once
 #include <hip/hip_runtime.h>

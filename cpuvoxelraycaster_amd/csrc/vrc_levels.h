@@ -1,6 +1,6 @@
 // vrc_levels.h -- the counts of the 2^k cubes of a brick-word field, the field of a smaller depth selected by those counts
-// and the field of a greater depth that repeats every voxel (vrc_levels.hip), as vrc_snapshots.hip calls them.  The kernels
-// know word arrays only; volumes and their ordering stay with vrc_snapshots.hip.
+// and the field of a greater depth that repeats every voxel (vrc_levels.hip), as vrc_volume_ops.hip calls them.  The kernels
+// know word arrays only; volumes and their ordering stay with vrc_volume_ops.hip.
 //
 // A CELL of level k is the cube of 2^k voxels per axis at a multiple of 2^k, 8^k / 8 brick bytes: c = 2^(k-1) bricks per axis,
 // c x c brick rows of c contiguous bytes.  Which kernel counts a cell goes by its size, and the switches are where the next

@@ -1,6 +1,6 @@
 // vrc_morph.h -- dilation and erosion of a brick-word field by a structuring element given as a list of offsets
-// (vrc_morph.hip), as vrc_snapshots.hip calls them.  The kernels know word arrays only; volumes, their ordering and the
-// block's owner stay with vrc_snapshots.hip.
+// (vrc_morph.hip), as vrc_volume_ops.hip calls them.  The kernels know word arrays only; volumes, their ordering and the
+// block's owner stay with vrc_volume_ops.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,32 +1,20 @@
-// vrc_snapshots.hip -- the snapshots taken from an editable volume (include/vrc.h): the labels of its connected components
-// (vrc_volume_label_components, vrc_labels_*; kernels in vrc_components.hip; the pieces' moments, posed placement and
-// contacts and their clearance over a field, vrc_rigid_*, kernels in vrc_rigid.hip; the labels cut along the Voronoi cells of a list of sites,
-// vrc_fracture_*, kernels in vrc_fracture.hip) and its exact squared Euclidean distance field
-// with the selection by distance that grow / shrink / hollow are made of (vrc_volume_distance_field, vrc_distance_*;
-// kernels in vrc_distance.hip), and the travel-distance field from a set of seeds, kept in the same snapshot object, with the
-// routes read off it (vrc_travel_field, vrc_travel_trace_paths; kernels in vrc_travel.hip), and the difference of two volumes as a list of
-// changed words (vrc_delta_diff, vrc_delta_*; kernels in vrc_delta.hip).  Beside them, because they take two volumes under the same ordering
-// rule, the automaton step and the seeded fill (vrc_cells_*; kernels in vrc_cells.hip), and the calls that look and write along an
-// axis (vrc_columns_*; kernels in vrc_columns.hip), and the calls between volumes of two depths (vrc_levels_*; kernels in
-// vrc_levels.hip), and the dilation and erosion by a list of offsets (vrc_morph_apply; kernels in vrc_morph.hip).  A snapshot owns its memory, is never written after its creator returns, and keeps no
-// event and no scratch: its host-memory calls stage in a block of their own, and what it selects or places goes into a volume
-// as an edit of that volume (staged_call in vrc_volume_state.h; the ordering of every entry point: the table in DESIGN.md).
+// vrc_snapshots.hip -- the snapshots taken from an editable volume (include/vrc.h) and their calls: the labels of its connected
+// components (vrc_labels_*, vrc_fall_*, vrc_rigid_*, vrc_fracture_*), its distance and travel fields (vrc_distance_*, vrc_travel_*)
+// and the difference of two volumes as a list of changed words (vrc_delta_*).  Kernels: vrc_components.hip, vrc_fall.hip,
+// vrc_rigid.hip, vrc_fracture.hip, vrc_distance.hip, vrc_travel.hip, vrc_delta.hip.  A snapshot owns its memory, is never written
+// after its creator returns, and keeps no event and no scratch: its host-memory calls stage in a block of their own, and what it
+// selects or places goes into a volume as an edit of that volume (staged_call in vrc_volume_state.h; ordering: DESIGN.md).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <new>
 
 #include "../../include/vrc.h"
-#include "vrc_box_words.h"
-#include "vrc_cells.h"
-#include "vrc_columns.h"
 #include "vrc_components.h"
 #include "vrc_delta.h"
 #include "vrc_distance.h"
 #include "vrc_fall.h"
 #include "vrc_fracture.h"
-#include "vrc_levels.h"
-#include "vrc_morph.h"
 #include "vrc_rigid.h"
 #include "vrc_travel.h"
 #include "vrc_volume_state.h"
@@ -50,21 +38,20 @@ struct vrc_distance {
 
 namespace {
 
-// The frame of the two creators: the NULL stream, behind the last asynchronous edit of the medium, as commit / download
-// are.  *d_array gets the snapshot's 8^depth words (its owner frees them, on failure too), a scratch block of
-// `scratch_bytes` lives for the call; run(d_scratch) enqueues the work and reads back the few words the creator needs.
+// The frame of the creators: the NULL stream, behind the last asynchronous edit of the medium (and of `seeds`, where given),
+// as commit / download are.  *d_array gets the snapshot's 8^depth words (its owner frees them, on failure too), a scratch
+// block of `scratch_bytes` lives for the call; run(d_scratch) enqueues the work and reads back the few words the creator needs.
 template <class Run>
-hipError_t snapshot_run(vrc_volume* medium, uint32_t** d_array, size_t scratch_bytes, Run run)
+int snapshot_run(const char* what, vrc_volume* medium, vrc_volume* seeds, uint32_t** d_array, size_t scratch_bytes, Run run)
 {
     uint32_t* d_scratch = nullptr;
-    hipError_t e = hipSetDevice(medium->device);
-    if (e == hipSuccess) e = order_behind_edits(medium, nullptr);
-    if (e == hipSuccess) e = hipMalloc((void**)d_array, (size_t)4u << (3u * medium->depth));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_scratch, scratch_bytes);
-    if (e == hipSuccess) e = run(d_scratch);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    const int rc = staged_call(what, null_stream_call(medium, seeds, false, true), [&]() {
+        hipError_t e = hipMalloc((void**)d_array, (size_t)4u << (3u * medium->depth));
+        if (e == hipSuccess) e = hipMalloc((void**)&d_scratch, scratch_bytes);
+        return e == hipSuccess ? run(d_scratch) : e;
+    });
     if (d_scratch) (void)hipFree(d_scratch);
-    return e;
+    return rc;
 }
 
 // the packed maximum of a field's reduction, (value << 32) | ~dense index, 0 where nothing was counted: the value and
@@ -77,12 +64,6 @@ void decode_argmax(unsigned long long packed, uint32_t depth, uint32_t* value, u
     *value = (uint32_t)(packed >> 32);
     argmax[0] = index >> (2u * depth); argmax[1] = (index >> depth) & mask; argmax[2] = index & mask;
 }
-
-// a call on the labels / the field alone: no volume to wait for, host memory staged in a block of the call's own
-Call snapshot_call(int device, int mem, void* stream) { return Call{device, mem, (hipStream_t)stream, nullptr, false, false, false}; }
-// a call that reads the snapshot and a volume (is_edit: writes the volume): behind the volume's last asynchronous edit
-// whatever the memory kind, staged in a block of the call's own
-Call volume_call(int device, int mem, void* stream, vrc_volume* v, bool is_edit) { return Call{device, mem, (hipStream_t)stream, v, is_edit, false, true}; }
 
 }  // namespace
 
@@ -98,7 +79,7 @@ extern "C" int vrc_volume_label_components(vrc_volume* medium, int connectivity,
     if (!l) return vrc::fail(VRC_ERR_OOM, "out of host memory");
     l->device = medium->device; l->depth = medium->depth;
     uint32_t C = 0;
-    const hipError_t e = snapshot_run(medium, &l->d_ids, vrc::components_scratch_bytes(l->depth), [&](uint32_t* d_scratch) {
+    const int rc = snapshot_run(what, medium, nullptr, &l->d_ids, vrc::components_scratch_bytes(l->depth), [&](uint32_t* d_scratch) {
         vrc::components_roots_run(medium->d_bricks, l->depth, connectivity, through, nullptr, l->d_ids, d_scratch, nullptr);
         hipError_t run = hipGetLastError();
         if (run == hipSuccess) run = hipMemcpy(&C, vrc::components_total_slot(d_scratch, l->depth), 4, hipMemcpyDeviceToHost);
@@ -109,9 +90,9 @@ extern "C" int vrc_volume_label_components(vrc_volume* medium, int connectivity,
         }
         return run;
     });
-    if (e != hipSuccess) {
+    if (rc) {
         (void)vrc_labels_destroy(l);
-        return vrc::fail_hip(e, what);
+        return rc;
     }
     l->count = C;
     *out = l;
@@ -147,12 +128,11 @@ extern "C" int vrc_labels_components(const vrc_labels* l, uint64_t first, uint64
     const uint64_t want = window_of(first, capacity, l->count);
     if (!want) return VRC_OK;
     // no list to stage: the records are copied out of the snapshot as they lie there
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(l->device);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(out, l->d_records + first, (size_t)want * sizeof(vrc_component), mem == VRC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = finish(nullptr, mem, st, false);
-    return done(e, what);
+    const Call call = snapshot_call(l->device, mem, stream);
+    return staged_call(what, call, [&]() {
+        return hipMemcpyAsync(out, l->d_records + first, (size_t)want * sizeof(vrc_component), mem == VRC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                              call.st);
+    });
 }
 
 extern "C" int vrc_labels_at(const vrc_labels* l, uint64_t n, const uint32_t* xyz, uint32_t* ids, int mem, void* stream)
@@ -438,7 +418,7 @@ extern "C" int vrc_fracture_label(vrc_volume* medium, int connectivity, int thro
     const size_t label_bytes = (vrc::components_scratch_bytes(l->depth) + 15u) & ~(size_t)15u, cell_bytes = (size_t)4u << (3u * l->depth);
     const size_t work_bytes = vrc::fracture_scratch_bytes(l->depth, medium->cu_count, n_sites), site_bytes = (size_t)n_sites * 12u;
     uint32_t C = 0;
-    const hipError_t e = snapshot_run(medium, &l->d_ids, label_bytes + cell_bytes + work_bytes + (mem == VRC_MEM_HOST ? site_bytes : 0u), [&](uint32_t* d_scratch) {
+    const int rc = snapshot_run(what, medium, nullptr, &l->d_ids, label_bytes + cell_bytes + work_bytes + (mem == VRC_MEM_HOST ? site_bytes : 0u), [&](uint32_t* d_scratch) {
         uint32_t* d_cells = d_scratch + label_bytes / 4u;
         uint32_t* d_work = d_cells + cell_bytes / 4u;
         const int32_t* d_sites = sites_xyz;
@@ -462,9 +442,9 @@ extern "C" int vrc_fracture_label(vrc_volume* medium, int connectivity, int thro
         }
         return run;
     });
-    if (e != hipSuccess) {
+    if (rc) {
         (void)vrc_labels_destroy(l);
-        return vrc::fail_hip(e, what);
+        return rc;
     }
     l->count = C;
     *out = l;
@@ -500,14 +480,14 @@ extern "C" int vrc_volume_distance_field(vrc_volume* medium, int to, int outside
     if (!d) return vrc::fail(VRC_ERR_OOM, "out of host memory");
     d->device = medium->device; d->depth = medium->depth;
     unsigned long long host[2] = {0ull, 0ull};
-    const hipError_t e = snapshot_run(medium, &d->d_field, vrc::distance_scratch_bytes(d->depth, medium->cu_count), [&](uint32_t* d_scratch) {
+    const int rc = snapshot_run(what, medium, nullptr, &d->d_field, vrc::distance_scratch_bytes(d->depth, medium->cu_count), [&](uint32_t* d_scratch) {
         vrc::distance_run(medium->d_bricks, d->depth, to, outside, medium->cu_count, d->d_field, d_scratch, nullptr);
         const hipError_t run = hipGetLastError();
         return run != hipSuccess ? run : hipMemcpy(host, vrc::distance_stats_slots(d_scratch), sizeof host, hipMemcpyDeviceToHost);
     });
-    if (e != hipSuccess) {
+    if (rc) {
         (void)vrc_distance_destroy(d);
-        return vrc::fail_hip(e, what);
+        return rc;
     }
     if (stats) {
         stats->features = host[0]; stats->reserved = 0u;
@@ -564,15 +544,11 @@ extern "C" int vrc_distance_select(const vrc_distance* d, uint32_t lo, uint32_t 
     if (const int rc = check_op(what, op)) return rc;
     if (lo > hi) return vrc::fail(VRC_ERR_INVALID, "%s: lo %u above hi %u", what, lo, hi);
     if (const int rc = check_same(what, "field", d->depth, d->device, dst)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(d->device);
-    if (e == hipSuccess) e = order_behind_edits(dst, st);
-    if (e == hipSuccess) {
-        vrc::distance_select_run(d->d_field, d->depth, lo, hi, dst->d_bricks, op, st);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
-    return done(e, what);
+    const Call call = volume_call(d->device, VRC_MEM_DEVICE, stream, dst, true);
+    return staged_call(what, call, [&]() {
+        vrc::distance_select_run(d->d_field, d->depth, lo, hi, dst->d_bricks, op, call.st);
+        return hipSuccess;
+    });
 }
 
 // ---- travel-distance field -----------------------------------------------------
@@ -585,24 +561,22 @@ extern "C" int vrc_travel_field(vrc_volume* seeds, vrc_volume* medium, int conne
     if (!out) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
     if (const int rc = check_connectivity(what, connectivity)) return rc;
     if (const int rc = check_through(what, through)) return rc;
-    if (seeds->depth != medium->depth) return vrc::fail(VRC_ERR_INVALID, "%s: volumes of depths %u and %u", what, seeds->depth, medium->depth);
-    if (seeds->device != medium->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, seeds->device, medium->device);
+    if (seeds != medium)                                                // one volume twice is allowed: seeds within their own medium
+        if (const int rc = check_pair(what, seeds, medium, true)) return rc;
     if (medium->depth < 2 || medium->depth > 10) return vrc::fail(VRC_ERR_INVALID, "%s: depth %u not in [2,10]", what, medium->depth);
     vrc_distance* d = new (std::nothrow) vrc_distance();
     if (!d) return vrc::fail(VRC_ERR_OOM, "out of host memory");
     d->device = medium->device; d->depth = medium->depth; d->connectivity = connectivity;
     unsigned long long host[3] = {0ull, 0ull, 0ull};
     uint32_t sweeps = 0, converged = 0;
-    const hipError_t e = snapshot_run(medium, &d->d_field, vrc::travel_scratch_bytes(d->depth), [&](uint32_t* d_scratch) {
-        hipError_t run = order_behind_edits(seeds, nullptr);
-        if (run == hipSuccess)
-            run = vrc::travel_run(seeds->d_bricks, medium->d_bricks, d->depth, connectivity, through, step_limit, d->d_field, d_scratch, nullptr, &sweeps,
-                                  &converged);
+    const int rc = snapshot_run(what, medium, seeds, &d->d_field, vrc::travel_scratch_bytes(d->depth), [&](uint32_t* d_scratch) {
+        const hipError_t run = vrc::travel_run(seeds->d_bricks, medium->d_bricks, d->depth, connectivity, through, step_limit, d->d_field, d_scratch, nullptr,
+                                               &sweeps, &converged);
         return run != hipSuccess ? run : hipMemcpy(host, vrc::travel_stats_slots(d_scratch), sizeof host, hipMemcpyDeviceToHost);
     });
-    if (e != hipSuccess) {
+    if (rc) {
         (void)vrc_distance_destroy(d);
-        return vrc::fail_hip(e, what);
+        return rc;
     }
     if (!converged) {
         (void)vrc_distance_destroy(d);
@@ -681,38 +655,33 @@ static vrc_delta_stats delta_stats_of(const vrc::DeltaTotals& t, uint64_t words)
     return s;
 }
 
-// Not a snapshot_run: two volumes to wait for, and the array is sized by what the host reads back between scan and emit.
+// Not a snapshot_run: the array is sized by what the host reads back between scan and emit.
 extern "C" int vrc_delta_diff(vrc_volume* before, vrc_volume* after, vrc_delta** out, vrc_delta_stats* stats)
 {
     const char* what = "vrc_delta_diff";
     if (!before || !after || !out) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
     if (before == after) return vrc::fail(VRC_ERR_INVALID, "%s: before and after are the same volume", what);
-    if (before->depth != after->depth) return vrc::fail(VRC_ERR_INVALID, "%s: volumes of depths %u and %u", what, before->depth, after->depth);
-    if (before->device != after->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, before->device, after->device);
+    if (const int rc = check_pair(what, before, after, true)) return rc;
     vrc_delta* d = new (std::nothrow) vrc_delta();
     if (!d) return vrc::fail(VRC_ERR_OOM, "out of host memory");
     d->device = before->device; d->depth = before->depth;
     void* d_scratch = nullptr;
     vrc::DeltaTotals totals = {};
-    hipError_t e = hipSetDevice(d->device);
-    if (e == hipSuccess) e = order_behind_edits(before, nullptr);
-    if (e == hipSuccess) e = order_behind_edits(after, nullptr);
-    if (e == hipSuccess) e = hipMalloc(&d_scratch, vrc::delta_scratch_bytes(d->depth));
-    if (e == hipSuccess) {
-        vrc::delta_offsets_run(before->d_bricks, after->d_bricks, d->depth, d_scratch, nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(&totals, d_scratch, sizeof totals, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && totals.words) e = hipMalloc((void**)&d->d_records, (size_t)totals.words * 8u);
-    if (e == hipSuccess && totals.words) {
-        vrc::delta_emit_run(before->d_bricks, after->d_bricks, d->depth, d_scratch, d->d_records, nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    const int rc = staged_call(what, null_stream_call(after, before, false, true), [&]() {
+        hipError_t e = hipMalloc(&d_scratch, vrc::delta_scratch_bytes(d->depth));
+        if (e == hipSuccess) {
+            vrc::delta_offsets_run(before->d_bricks, after->d_bricks, d->depth, d_scratch, nullptr);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpy(&totals, d_scratch, sizeof totals, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && totals.words) e = hipMalloc((void**)&d->d_records, (size_t)totals.words * 8u);
+        if (e == hipSuccess && totals.words) vrc::delta_emit_run(before->d_bricks, after->d_bricks, d->depth, d_scratch, d->d_records, nullptr);
+        return e;
+    });
     if (d_scratch) (void)hipFree(d_scratch);
-    if (e != hipSuccess) {
+    if (rc) {
         (void)vrc_delta_destroy(d);
-        return vrc::fail_hip(e, what);
+        return rc;
     }
     d->count = totals.words;
     d->stats = delta_stats_of(totals, d->count);
@@ -811,229 +780,9 @@ extern "C" int vrc_delta_apply(const vrc_delta* d, vrc_volume* dst, void* stream
     if (!d || !dst) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
     if (const int rc = check_same(what, "delta", d->depth, d->device, dst)) return rc;
     if (!d->count) return VRC_OK;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(d->device);
-    if (e == hipSuccess) e = order_behind_edits(dst, st);
-    if (e == hipSuccess) {
-        vrc::delta_apply_run(d->d_records, (uint32_t)d->count, dst->d_bricks, st);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
-    return done(e, what);
-}
-
-// ---- cells: a neighbour-count step between two volumes and the seeded fill (the rules: include/vrc.h; the kernels: vrc_cells.hip) ----
-
-extern "C" int vrc_cells_step(vrc_volume* dst, vrc_volume* src, int neighbours, uint32_t birth_mask, uint32_t survive_mask, int outside,
-                              uint64_t* changed, int mem, void* stream)
-{
-    const char* what = "vrc_cells_step";
-    if (!dst || !src) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
-    if (dst == src) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
-    if (dst->depth != src->depth) return vrc::fail(VRC_ERR_INVALID, "%s: volumes of depths %u and %u", what, dst->depth, src->depth);
-    if (dst->device != src->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, dst->device, src->device);
-    if (neighbours != VRC_CELLS_FACES && neighbours != VRC_CELLS_ALL) return vrc::fail(VRC_ERR_INVALID, "%s: neighbours %d is neither 6 nor 26", what, neighbours);
-    const uint32_t counts = (2u << neighbours) - 1u;                    // bits 0 .. neighbours
-    if (birth_mask & ~counts) return vrc::fail(VRC_ERR_INVALID, "%s: birth_mask 0x%x has a bit above bit %d", what, birth_mask, neighbours);
-    if (survive_mask & ~counts) return vrc::fail(VRC_ERR_INVALID, "%s: survive_mask 0x%x has a bit above bit %d", what, survive_mask, neighbours);
-    if (outside != 0 && outside != 1) return vrc::fail(VRC_ERR_INVALID, "%s: outside %d is neither 0 nor 1", what, outside);
-    if (changed)
-        if (const int rc = check_mem(what, mem)) return rc;
-    hipError_t e = hipSetDevice(dst->device);
-    if (e == hipSuccess) e = order_behind_edits(src, (hipStream_t)stream);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    // the counter is the call's one list: in host form it is staged in 8 bytes of the call's own and the call is synchronous
-    const Call call = volume_call(dst->device, changed ? mem : VRC_MEM_DEVICE, stream, dst, true);
-    const StagePart parts[] = {{changed, 8u, STAGE_OUT}};
-    return staged_call(what, call, parts, [&](void* const* d) {
-        const hipError_t zeroed = d[0] ? hipMemsetAsync(d[0], 0, 8u, call.st) : hipSuccess;
-        if (zeroed == hipSuccess)
-            vrc::cells_step_run(dst->d_bricks, src->d_bricks, dst->depth, neighbours, birth_mask, survive_mask, outside, (unsigned long long*)d[0], call.st);
-        return zeroed;
-    });
-}
-
-extern "C" int vrc_cells_fill_random(vrc_volume* v, uint32_t seed, uint64_t threshold, const uint32_t* lo_hi, int op, void* stream)
-{
-    const char* what = "vrc_cells_fill_random";
-    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
-    if (threshold > (1ull << 32)) return vrc::fail(VRC_ERR_INVALID, "%s: threshold %llu above 2^32", what, (unsigned long long)threshold);
-    if (const int rc = check_op(what, op)) return rc;
-    const uint32_t S = 1u << v->depth, whole[6] = {0u, 0u, 0u, S, S, S};
-    uint32_t lo[3], hi[3];
-    if (!clip_box(lo_hi ? lo_hi : whole, S, lo, hi)) return VRC_OK;      // empty, inverted or wholly outside: nothing to write
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = order_behind_edits(v, st);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    vrc::cells_fill_random_run(v->d_bricks, v->depth, seed, threshold, lo, hi, op, st);
-    if ((e = hipGetLastError()) == hipSuccess) e = finish(v, VRC_MEM_DEVICE, st, true);
-    return done(e, what);
-}
-
-// ---- columns: the profile of every column, spans from height maps, selection by the solid voxels met (the rules: include/vrc.h; the kernels: vrc_columns.hip) ----
-
-namespace {
-
-// rect (NULL: the whole face) into out[4]: non-empty and inside [0, S]^2, not clipped
-int check_rect(const char* what, const uint32_t* rect, uint32_t S, uint32_t out[4])
-{
-    const uint32_t whole[4] = {0u, 0u, S, S};
-    for (int i = 0; i < 4; ++i) out[i] = (rect ? rect : whole)[i];
-    if (out[0] < out[2] && out[1] < out[3] && out[2] <= S && out[3] <= S) return VRC_OK;
-    return vrc::fail(VRC_ERR_INVALID, "%s: rect (%u, %u, %u, %u) is empty or outside the %u x %u face", what, out[0], out[1], out[2], out[3], S, S);
-}
-
-}  // namespace
-
-extern "C" int vrc_columns_profile(vrc_volume* v, int direction, const uint32_t* rect, vrc_column* out, int mem, void* stream)
-{
-    const char* what = "vrc_columns_profile";
-    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
-    if (!out) return vrc::fail(VRC_ERR_INVALID, "%s: null out", what);
-    if (direction < 0 || direction > 5) return vrc::fail(VRC_ERR_INVALID, "%s: bad direction %d", what, direction);
-    uint32_t r[4];
-    if (const int rc = check_rect(what, rect, 1u << v->depth, r)) return rc;
-    if (const int rc = check_mem(what, mem)) return rc;
-    const Call call = volume_call(v->device, mem, stream, v, false);
-    const StagePart parts[] = {{out, (size_t)(r[2] - r[0]) * (r[3] - r[1]) * sizeof(vrc_column), STAGE_OUT}};
-    return staged_call(what, call, parts, [&](void* const* d) {
-        vrc::columns_profile_run(v->d_bricks, v->depth, direction, r, (vrc_column*)d[0], call.st);
+    const Call call = volume_call(d->device, VRC_MEM_DEVICE, stream, dst, true);
+    return staged_call(what, call, [&]() {
+        vrc::delta_apply_run(d->d_records, (uint32_t)d->count, dst->d_bricks, call.st);
         return hipSuccess;
-    });
-}
-
-extern "C" int vrc_columns_fill(vrc_volume* v, int axis, const uint32_t* rect, const int32_t* lo_map, int32_t lo_const, const int32_t* hi_map,
-                                int32_t hi_const, int op, int mem, void* stream)
-{
-    const char* what = "vrc_columns_fill";
-    if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
-    if (axis < 0 || axis > 2) return vrc::fail(VRC_ERR_INVALID, "%s: bad axis %d", what, axis);
-    uint32_t r[4];
-    if (const int rc = check_rect(what, rect, 1u << v->depth, r)) return rc;
-    if (const int rc = check_op(what, op)) return rc;
-    if (const int rc = check_mem(what, mem)) return rc;
-    const Call call = volume_call(v->device, mem, stream, v, true);
-    const size_t map_bytes = (size_t)(r[2] - r[0]) * (r[3] - r[1]) * 4u;
-    const StagePart parts[] = {{lo_map, map_bytes, STAGE_IN}, {hi_map, map_bytes, STAGE_IN}};
-    return staged_call(what, call, parts, [&](void* const* d) {
-        vrc::columns_fill_run(v->d_bricks, v->depth, axis, r, (const int32_t*)d[0], lo_const, (const int32_t*)d[1], hi_const, op, call.st);
-        return hipSuccess;
-    });
-}
-
-extern "C" int vrc_columns_select(vrc_volume* dst, vrc_volume* src, int direction, uint32_t lo, uint32_t hi, int of, int op, void* stream)
-{
-    const char* what = "vrc_columns_select";
-    if (!dst || !src) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
-    if (dst == src) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
-    if (dst->depth != src->depth) return vrc::fail(VRC_ERR_INVALID, "%s: volumes of depths %u and %u", what, dst->depth, src->depth);
-    if (dst->device != src->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, dst->device, src->device);
-    if (direction < 0 || direction > 5) return vrc::fail(VRC_ERR_INVALID, "%s: bad direction %d", what, direction);
-    if (lo > hi) return vrc::fail(VRC_ERR_INVALID, "%s: lo %u above hi %u", what, lo, hi);
-    if (of < VRC_COLUMNS_SOLID || of > (VRC_COLUMNS_SOLID | VRC_COLUMNS_EMPTY)) return vrc::fail(VRC_ERR_INVALID, "%s: bad of %d", what, of);
-    if (const int rc = check_op(what, op)) return rc;
-    // no count reaches S: a bound above S + 1 selects what S + 1 selects
-    const uint32_t top = (1u << src->depth) + 1u, band_lo = lo < top ? lo : top, band_hi = hi < top ? hi : top;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(dst->device);
-    if (e == hipSuccess) e = order_behind_edits(src, st);
-    if (e == hipSuccess) e = order_behind_edits(dst, st);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    vrc::columns_select_run(dst->d_bricks, src->d_bricks, dst->depth, direction, band_lo, band_hi, of, op, st);
-    if ((e = hipGetLastError()) == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
-    return done(e, what);
-}
-
-// ---- levels: the counts of the 2^k cubes, and volumes of two depths made from one another (the rules: include/vrc.h; the kernels: vrc_levels.hip) ----
-
-extern "C" int vrc_levels_counts(vrc_volume* src, uint32_t k, uint32_t* counts, int mem, void* stream)
-{
-    const char* what = "vrc_levels_counts";
-    if (!src) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
-    if (!counts) return vrc::fail(VRC_ERR_INVALID, "%s: null counts", what);
-    if (k == 0u || k > src->depth) return vrc::fail(VRC_ERR_INVALID, "%s: k %u not in [1, %u], the volume's depth", what, k, src->depth);
-    if (const int rc = check_mem(what, mem)) return rc;
-    const Call call = volume_call(src->device, mem, stream, src, false);
-    const StagePart parts[] = {{counts, (size_t)4u << (3u * (src->depth - k)), STAGE_OUT}};
-    return staged_call(what, call, parts, [&](void* const* d) { return vrc::levels_counts_run(src->d_bricks, src->depth, k, (uint32_t*)d[0], call.st); });
-}
-
-extern "C" int vrc_levels_reduce(vrc_volume* dst, vrc_volume* src, uint32_t lo, uint32_t hi, int op, void* stream)
-{
-    const char* what = "vrc_levels_reduce";
-    if (!dst || !src) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
-    if (dst == src) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
-    if (dst->device != src->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, dst->device, src->device);
-    if (dst->depth >= src->depth) return vrc::fail(VRC_ERR_INVALID, "%s: destination of depth %u is not below the source's %u", what, dst->depth, src->depth);
-    if (const int rc = check_op(what, op)) return rc;
-    // no count is above 8^k: a bound above 8^k + 1 selects what 8^k + 1 selects
-    const uint32_t k = src->depth - dst->depth, top = (1u << (3u * k)) + 1u, band_lo = lo < top ? lo : top, band_hi = hi < top ? hi : top;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(dst->device);
-    if (e == hipSuccess) e = order_behind_edits(src, st);
-    if (e == hipSuccess) e = order_behind_edits(dst, st);
-    if (e == hipSuccess) e = reserve(dst->d_levels, dst->levels_cap, vrc::levels_scratch_bytes(src->depth, k));
-    if (e == hipSuccess) e = vrc::levels_reduce_run(dst->d_bricks, src->d_bricks, src->depth, k, band_lo, band_hi, op, dst->d_levels, st);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    if ((e = hipGetLastError()) == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
-    return done(e, what);
-}
-
-extern "C" int vrc_levels_expand(vrc_volume* dst, vrc_volume* src, int op, void* stream)
-{
-    const char* what = "vrc_levels_expand";
-    if (!dst || !src) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
-    if (dst == src) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
-    if (dst->device != src->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, dst->device, src->device);
-    if (dst->depth <= src->depth) return vrc::fail(VRC_ERR_INVALID, "%s: destination of depth %u is not above the source's %u", what, dst->depth, src->depth);
-    if (const int rc = check_op(what, op)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(dst->device);
-    if (e == hipSuccess) e = order_behind_edits(src, st);
-    if (e == hipSuccess) e = order_behind_edits(dst, st);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    vrc::levels_expand_run(dst->d_bricks, dst->depth, src->d_bricks, dst->depth - src->depth, op, st);
-    if ((e = hipGetLastError()) == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
-    return done(e, what);
-}
-
-// ---- morphology: dilation and erosion by a list of offsets (the rule: include/vrc.h; the kernels: vrc_morph.hip) ----
-
-extern "C" int vrc_morph_apply(vrc_volume* dst, vrc_volume* src, int what_op, int of, uint64_t n, const int32_t* offsets, const int32_t* origin, int outside,
-                               int op, int mem, void* stream)
-{
-    const char* what = "vrc_morph_apply";
-    if (!dst || !src) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
-    if (dst == src) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
-    if (dst->depth != src->depth) return vrc::fail(VRC_ERR_INVALID, "%s: volumes of depths %u and %u", what, dst->depth, src->depth);
-    if (dst->device != src->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, dst->device, src->device);
-    if (what_op != VRC_MORPH_DILATE && what_op != VRC_MORPH_ERODE) return vrc::fail(VRC_ERR_INVALID, "%s: bad what %d", what, what_op);
-    if (of != VRC_MORPH_SOLID && of != VRC_MORPH_EMPTY) return vrc::fail(VRC_ERR_INVALID, "%s: bad of %d", what, of);
-    if (outside != 0 && outside != 1) return vrc::fail(VRC_ERR_INVALID, "%s: outside %d is neither 0 nor 1", what, outside);
-    if (const int rc = check_op(what, op)) return rc;
-    if (const int rc = check_mem(what, mem)) return rc;
-    if (n > VRC_MORPH_MAX_OFFSETS) return vrc::fail(VRC_ERR_INVALID, "%s: %llu offsets, more than %u", what, (unsigned long long)n, VRC_MORPH_MAX_OFFSETS);
-    if (n && !offsets) return vrc::fail(VRC_ERR_INVALID, "%s: null offsets", what);
-    const int32_t pivot[3] = {origin ? origin[0] : 0, origin ? origin[1] : 0, origin ? origin[2] : 0};
-    if (mem == VRC_MEM_HOST)
-        for (uint64_t i = 0; i < n; ++i) {
-            const long long e[3] = {(long long)offsets[3u * i] - pivot[0], (long long)offsets[3u * i + 1u] - pivot[1], (long long)offsets[3u * i + 2u] - pivot[2]};
-            for (int a = 0; a < 3; ++a)
-                if (e[a] < -VRC_MORPH_REACH || e[a] > VRC_MORPH_REACH)
-                    return vrc::fail(VRC_ERR_INVALID, "%s: offset %llu is (%lld, %lld, %lld) after the origin, beyond +-%d", what, (unsigned long long)i, e[0], e[1],
-                                     e[2], VRC_MORPH_REACH);
-        }
-    hipError_t e = hipSetDevice(dst->device);
-    if (e == hipSuccess) e = order_behind_edits(src, (hipStream_t)stream);
-    // the prepared element: a block of dst's own, fixed in size; the calls that write it are dst's edits, one behind the other
-    if (e == hipSuccess && !dst->d_morph) e = hipMalloc(&dst->d_morph, vrc::MORPH_BLOCK_BYTES);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    // the list is the call's one part: in host form it is staged in a block of the call's own and the call is synchronous
-    const Call call = volume_call(dst->device, mem, stream, dst, true);
-    const StagePart parts[] = {{offsets, (size_t)n * 12u, STAGE_IN}};
-    return staged_call(what, call, parts, [&](void* const* d) {
-        return vrc::morph_run(dst->d_bricks, src->d_bricks, dst->depth, what_op == VRC_MORPH_ERODE, of == VRC_MORPH_EMPTY, outside, n, (const int32_t*)d[0], pivot,
-                              op, dst->d_morph, call.st);
     });
 }

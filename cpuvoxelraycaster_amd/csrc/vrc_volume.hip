@@ -12,10 +12,11 @@
 // Here: the volume's life cycle, the edits and queries on the occupancy with their ordering and scratch blocks, and
 // commit / download.  Boxes, spheres, spheres at the hits of a ray batch, region copies and the two queries have their
 // kernels here, over the box-of-words layout of vrc_box_words.h.  The other features keep theirs in files of their own:
-// vrc_flood.hip, vrc_voxelize.hip, vrc_surface.hip, vrc_voxels.hip, vrc_rects.hip, vrc_stamp.hip, vrc_pack.hip, vrc_stroke.hip, vrc_raster.hip.  The snapshots taken from a volume (labels, distance
-// fields) are in vrc_snapshots.hip; what the entry points of both files share -- the checks, the ordering rule and staged_call,
-// the one frame of every call that takes lists -- is in vrc_volume_state.h, and the ordering of every entry point is the
-// table in DESIGN.md.
+// vrc_flood.hip, vrc_voxelize.hip, vrc_surface.hip, vrc_voxels.hip, vrc_rects.hip, vrc_stamp.hip, vrc_pack.hip, vrc_stroke.hip,
+// vrc_raster.hip.  The calls between two volumes and along their axes (cells, columns, levels, morphology) are in
+// vrc_volume_ops.hip, the snapshots taken from a volume (labels, fields, deltas) in vrc_snapshots.hip; what the entry points of
+// the three files share -- the checks, the ordering rule and staged_call, the one frame of every call -- is in
+// vrc_volume_state.h, and the ordering of every entry point is the table in DESIGN.md.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -353,13 +354,6 @@ int volume_new(uint32_t depth, int device, vrc_volume** out)
     return VRC_OK;
 }
 
-// An edit that reads one list: staged in the volume's block, recorded as its last edit, and -- unlike every other call on a
-// volume -- behind the last asynchronous edit in host form only, where it writes that block; in device form it stays
-// unordered against edits on other streams, as it always was.
-Call edit_call(vrc_volume* v, int mem, void* stream) { return Call{v->device, mem, (hipStream_t)stream, v, true, true, false}; }
-// A query: a list in and a list out through the volume's block, behind the last asynchronous edit whatever the memory kind.
-Call query_call(vrc_volume* v, int mem, void* stream) { return Call{v->device, mem, (hipStream_t)stream, v, false, true, true}; }
-
 // workgroups per item for the kernels that take one item per blockIdx.x: a few items are spread over up to 1024
 // workgroups each (a whole 1024^3 volume is 2^25 words); many items: one workgroup each.  A workgroup that finds
 // nothing to do leaves at once.
@@ -381,6 +375,29 @@ void launch_fill_spheres(vrc_volume* v, uint64_t n, const int32_t* d_spheres, in
     const bool small = n >= 4096u && max_radius >= 0 && max_radius <= 4;
     hipLaunchKernelGGL(k_fill_spheres, dim3((uint32_t)n, split_for(v, n)), dim3(small ? 64 : 256), 0, st, v->d_bricks, 1u << v->depth,
                        d_spheres, solid ? 1u : 0u);
+}
+
+// The frame of the two brushes at hits: the n centres (x, y, z, radius) go into v's staging block, then fill(d_centres) enqueues
+// the brush's own kernel.  Not a staged_call: the centres, no list of the caller's, go through the staging block in BOTH memory
+// kinds (n x 4 int32, then the hits themselves when they come from the host), which an earlier call on another stream may still
+// be reading -- so the call orders itself behind the volume's last edit and ends as an edit by hand.
+template <class Fill>
+int hits_call(const char* what, vrc_volume* v, uint64_t n, const vrc_hit* hits, int32_t radius, int solid, int mem, hipStream_t st, Fill fill)
+{
+    hipError_t e = hipSetDevice(v->device);
+    if (e == hipSuccess) e = order_behind_edits(v, st);
+    if (e == hipSuccess) e = reserve(v->d_stage, v->stage_cap, (size_t)n * (mem == VRC_MEM_HOST ? 64u : 16u));
+    int32_t* d_centres = (int32_t*)v->d_stage;
+    const vrc_hit* d_hits = hits;
+    if (e == hipSuccess && mem == VRC_MEM_HOST) {
+        d_hits = (const vrc_hit*)((uint8_t*)v->d_stage + (size_t)n * 16u);
+        e = hipMemcpyAsync((void*)d_hits, hits, (size_t)n * sizeof(vrc_hit), hipMemcpyHostToDevice, st);
+    }
+    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    hipLaunchKernelGGL(k_hits_to_centres, grid_for(n), dim3(256), 0, st, n, d_hits, v->depth, radius, solid ? 1u : 0u, d_centres);
+    fill(d_centres);
+    if ((e = hipGetLastError()) == hipSuccess) e = finish(v, mem, st, true);
+    return done(e, what);
 }
 
 }  // namespace
@@ -481,23 +498,7 @@ extern "C" int vrc_volume_fill_spheres_at_hits(vrc_volume* v, uint64_t n, const 
     if (!hits) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
     if (const int rc = check_count(what, n, GROUP_ITEMS, "hits")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(v->device);
-    // Not a staged_call: the centres, no list of the caller's, go through the staging block in BOTH memory kinds (n x 4
-    // int32, then the hits themselves when they come from the host), which an earlier call on another stream may still
-    // be reading
-    if (e == hipSuccess) e = order_behind_edits(v, st);
-    if (e == hipSuccess) e = reserve(v->d_stage, v->stage_cap, (size_t)n * (mem == VRC_MEM_HOST ? 64u : 16u));
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    int32_t* d_centres = (int32_t*)v->d_stage;
-    const vrc_hit* d_hits = hits;
-    if (mem == VRC_MEM_HOST) {
-        d_hits = (const vrc_hit*)((uint8_t*)v->d_stage + (size_t)n * 16u);
-        if ((e = hipMemcpyAsync((void*)d_hits, hits, (size_t)n * sizeof(vrc_hit), hipMemcpyHostToDevice, st)) != hipSuccess) return vrc::fail_hip(e, what);
-    }
-    hipLaunchKernelGGL(k_hits_to_centres, grid_for(n), dim3(256), 0, st, n, d_hits, v->depth, radius, solid ? 1u : 0u, d_centres);
-    launch_fill_spheres(v, n, d_centres, radius, solid, st);
-    if ((e = hipGetLastError()) == hipSuccess) e = finish(v, mem, st, true);
-    return done(e, what);
+    return hits_call(what, v, n, hits, radius, solid, mem, st, [&](const int32_t* d_centres) { launch_fill_spheres(v, n, d_centres, radius, solid, st); });
 }
 
 // ---- capsules (kernels: vrc_stroke.hip) ----------------------------------------------------------------------------
@@ -529,23 +530,11 @@ extern "C" int vrc_stroke_fill_at_hits(vrc_volume* v, uint64_t n, const vrc_hit*
     if (!hits) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
     if (const int rc = check_count(what, n, GROUP_ITEMS, "hits")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(v->device);
-    // Not a staged_call, as vrc_volume_fill_spheres_at_hits is none: the centres go through the staging block in both memory
-    // kinds.  The links are read off neighbouring centres by the kernel, so the block holds no list of capsules.
-    if (e == hipSuccess) e = order_behind_edits(v, st);
-    if (e == hipSuccess) e = reserve(v->d_stage, v->stage_cap, (size_t)n * (mem == VRC_MEM_HOST ? 64u : 16u));
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    int32_t* d_centres = (int32_t*)v->d_stage;
-    const vrc_hit* d_hits = hits;
-    if (mem == VRC_MEM_HOST) {
-        d_hits = (const vrc_hit*)((uint8_t*)v->d_stage + (size_t)n * 16u);
-        if ((e = hipMemcpyAsync((void*)d_hits, hits, (size_t)n * sizeof(vrc_hit), hipMemcpyHostToDevice, st)) != hipSuccess) return vrc::fail_hip(e, what);
-    }
-    hipLaunchKernelGGL(k_hits_to_centres, grid_for(n), dim3(256), 0, st, n, d_hits, v->depth, radius, solid ? 1u : 0u, d_centres);
-    // many thin strokes between neighbouring hits: a wave each, as launch_fill_spheres
-    vrc::stroke_links_run(v->d_bricks, v->depth, n, d_centres, radius, max_gap, split_for(v, n), n >= 4096u && radius <= 4 ? 64u : 256u, solid, st);
-    if ((e = hipGetLastError()) == hipSuccess) e = finish(v, mem, st, true);
-    return done(e, what);
+    // the links are read off neighbouring centres by the kernel, so the block holds no list of capsules; many thin strokes
+    // between neighbouring hits: a wave each, as launch_fill_spheres
+    return hits_call(what, v, n, hits, radius, solid, mem, st, [&](const int32_t* d_centres) {
+        vrc::stroke_links_run(v->d_bricks, v->depth, n, d_centres, radius, max_gap, split_for(v, n), n >= 4096u && radius <= 4 ? 64u : 256u, solid, st);
+    });
 }
 
 // ---- surface voxelisation (kernels: vrc_raster.hip) ------------------------------------------------------------------
@@ -575,21 +564,19 @@ extern "C" int vrc_volume_xor_mesh(vrc_volume* v, uint64_t n, const int32_t* tri
     if (n == 0) return VRC_OK;
     if (!tris) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
     if (const int rc = check_count(what, n, GROUP_ITEMS, "triangles")) return rc;
-    hipStream_t st = (hipStream_t)stream;
     // the mark field is shared by every call and the scan's read-modify-write of the occupancy is not atomic: behind the
     // last asynchronous edit whatever the memory kind
-    hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = order_behind_edits(v, st);
-    if (e == hipSuccess && !v->d_marks) {
-        const size_t bytes = vrc::voxelize_scratch_bytes(v->depth);
-        if ((e = hipMalloc((void**)&v->d_marks, bytes)) == hipSuccess) e = hipMemsetAsync(v->d_marks, 0, bytes, st);
-        if (e != hipSuccess && v->d_marks) { (void)hipFree(v->d_marks); v->d_marks = nullptr; }
-    }
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    const Call call = shared_edit_call(v, mem, stream);
     const StagePart parts[] = {{tris, (size_t)n * 36u, STAGE_IN}};
-    return staged_call(what, edit_call(v, mem, stream), parts, [&](void* const* d) {
-        vrc::voxelize_run(v->d_bricks, v->d_marks, v->depth, n, (const int32_t*)d[0], st);
-        return hipSuccess;
+    return staged_call(what, call, parts, [&](void* const* d) {
+        hipError_t e = hipSuccess;
+        if (!v->d_marks) {
+            const size_t bytes = vrc::voxelize_scratch_bytes(v->depth);
+            if ((e = hipMalloc((void**)&v->d_marks, bytes)) == hipSuccess) e = hipMemsetAsync(v->d_marks, 0, bytes, call.st);
+            if (e != hipSuccess && v->d_marks) { (void)hipFree(v->d_marks); v->d_marks = nullptr; }
+        }
+        if (e == hipSuccess) vrc::voxelize_run(v->d_bricks, v->d_marks, v->depth, n, (const int32_t*)d[0], call.st);
+        return e;
     });
 }
 
@@ -598,9 +585,9 @@ extern "C" int vrc_volume_copy_region(vrc_volume* dst, vrc_volume* src, const ui
 {
     const char* what = "vrc_volume_copy_region";
     if (!dst || !src || !src_lo || !size || !dst_lo) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
-    if (src == dst) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
+    if (const int rc = check_distinct(what, src, dst)) return rc;      // ahead of the op, the devices behind it: the order the refusals always had
     if (const int rc = check_op(what, op)) return rc;
-    if (src->device != dst->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, src->device, dst->device);
+    if (const int rc = check_pair(what, src, dst, false)) return rc;
     // the region clipped to both volumes, as the destination's voxel box [lo, hi) and the offset to the source
     const int64_t Ss = 1ll << src->depth, Sd = 1ll << dst->depth;
     uint32_t lo[3], hi[3];
@@ -615,15 +602,12 @@ extern "C" int vrc_volume_copy_region(vrc_volume* dst, vrc_volume* src, const ui
         hi[a] = (uint32_t)(dst_lo[a] + d1);
         off[a] = (int64_t)src_lo[a] - (int64_t)dst_lo[a];
     }
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(dst->device);
-    if (e == hipSuccess) e = order_behind_edits(src, st);
-    if (e == hipSuccess) e = order_behind_edits(dst, st);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    hipLaunchKernelGGL(k_copy_region, dim3(box_launch_groups(lo, hi)), dim3(256), 0, st, dst->d_bricks, (uint32_t)Sd, (const uint8_t*)src->d_bricks, (uint32_t)Ss,
-                       lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], off[0], off[1], off[2], op);
-    if ((e = hipGetLastError()) == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
-    return done(e, what);
+    const Call call = pair_call(dst, src, VRC_MEM_DEVICE, stream);
+    return staged_call(what, call, [&]() {
+        hipLaunchKernelGGL(k_copy_region, dim3(box_launch_groups(lo, hi)), dim3(256), 0, call.st, dst->d_bricks, (uint32_t)Sd, (const uint8_t*)src->d_bricks,
+                           (uint32_t)Ss, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], off[0], off[1], off[2], op);
+        return hipSuccess;
+    });
 }
 
 extern "C" int vrc_volume_stamp_affine(vrc_volume* dst, vrc_volume* src, const vrc_affine* map, const uint32_t dst_lo[3], const uint32_t dst_hi[3],
@@ -631,21 +615,18 @@ extern "C" int vrc_volume_stamp_affine(vrc_volume* dst, vrc_volume* src, const v
 {
     const char* what = "vrc_volume_stamp_affine";
     if (!dst || !src || !map || !dst_lo || !dst_hi) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
-    if (src == dst) return vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
+    if (const int rc = check_distinct(what, src, dst)) return rc;      // as vrc_volume_copy_region
     if (const int rc = check_op(what, op)) return rc;
     if (const int rc = check_affine(what, map, -1)) return rc;
-    if (src->device != dst->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, src->device, dst->device);
+    if (const int rc = check_pair(what, src, dst, false)) return rc;
     const uint32_t box[6] = {dst_lo[0], dst_lo[1], dst_lo[2], dst_hi[0], dst_hi[1], dst_hi[2]};
     uint32_t lo[3], hi[3];
     if (!clip_box(box, 1u << dst->depth, lo, hi)) return VRC_OK;       // empty, inverted or wholly outside: nothing to write
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(dst->device);
-    if (e == hipSuccess) e = order_behind_edits(src, st);
-    if (e == hipSuccess) e = order_behind_edits(dst, st);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    vrc::stamp_affine_run(dst->d_bricks, dst->depth, src->d_bricks, src->depth, *map, lo, hi, op, st);
-    if ((e = hipGetLastError()) == hipSuccess) e = finish(dst, VRC_MEM_DEVICE, st, true);
-    return done(e, what);
+    const Call call = pair_call(dst, src, VRC_MEM_DEVICE, stream);
+    return staged_call(what, call, [&]() {
+        vrc::stamp_affine_run(dst->d_bricks, dst->depth, src->d_bricks, src->depth, *map, lo, hi, op, call.st);
+        return hipSuccess;
+    });
 }
 
 extern "C" int vrc_volume_clone(vrc_volume* src, vrc_volume** out)
@@ -654,11 +635,11 @@ extern "C" int vrc_volume_clone(vrc_volume* src, vrc_volume** out)
     vrc_volume* v = nullptr;
     int rc = volume_new(src->depth, src->device, &v);
     if (rc) return rc;
-    hipError_t e = order_behind_edits(src, nullptr);
-    if (e == hipSuccess) e = hipMemcpyAsync(v->d_bricks, src->d_bricks, src->n_bricks, hipMemcpyDeviceToDevice, nullptr);
-    if (e == hipSuccess) e = hipMemcpyAsync(v->d_tex, src->d_tex, 1536, hipMemcpyDeviceToDevice, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) { volume_free(v); return vrc::fail_hip(e, "vrc_volume_clone"); }
+    rc = staged_call("vrc_volume_clone", null_stream_call(src, nullptr, false, true), [&]() {
+        const hipError_t e = hipMemcpyAsync(v->d_bricks, src->d_bricks, src->n_bricks, hipMemcpyDeviceToDevice, nullptr);
+        return e != hipSuccess ? e : hipMemcpyAsync(v->d_tex, src->d_tex, 1536, hipMemcpyDeviceToDevice, nullptr);
+    });
+    if (rc) { volume_free(v); return rc; }
     *out = v;
     return VRC_OK;
 }
@@ -742,18 +723,17 @@ static int mesh_count(const char* what, const MeshRuns& runs, vrc_volume* v, int
 {
     if (!v) return vrc::fail(VRC_ERR_INVALID, "%s: null volume", what);
     if (!counts) return vrc::fail(VRC_ERR_INVALID, "%s: null counts", what);
-    hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = order_behind_edits(v, nullptr);
-    if (e == hipSuccess) e = runs.reserve(v);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    if (runs.prepare) runs.prepare(v, nullptr);
-    runs.count(v, closed, nullptr);
-    e = hipGetLastError();
     unsigned long long host[6];
-    if (e == hipSuccess) e = hipMemcpy(host, runs.direction_slots(v), sizeof host, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    for (int d = 0; d < 6; ++d) counts[d] = host[d];
-    return VRC_OK;
+    const int rc = staged_call(what, null_stream_call(v, nullptr, false, false), [&]() {
+        hipError_t e = runs.reserve(v);
+        if (e != hipSuccess) return e;
+        if (runs.prepare) runs.prepare(v, nullptr);
+        runs.count(v, closed, nullptr);
+        if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpy(host, runs.direction_slots(v), sizeof host, hipMemcpyDeviceToHost);
+        return e;
+    });
+    for (int d = 0; d < 6 && !rc; ++d) counts[d] = host[d];
+    return rc;
 }
 
 // Records [first, first + capacity) of a list in its canonical order, and its total: the frame of the face, rectangle and
@@ -765,7 +745,8 @@ template <class Reserve, class Offsets, class Emit, class TotalSlot>
 static int windowed_extract(const char* what, vrc_volume* v, size_t record, uint64_t first, uint64_t capacity, void* out, uint64_t* total, int mem,
                             hipStream_t st, Reserve reserve_block, Offsets offsets, Emit emit, TotalSlot total_slot)
 {
-    // behind the last asynchronous edit whatever the memory kind: the extractor's block is shared by every call
+    // behind the last asynchronous edit whatever the memory kind: the extractor's block is shared by every call.  Not a
+    // staged_call: the host form reads the total back before it knows its windows, and synchronises between them
     hipError_t e = hipSetDevice(v->device);
     if (e == hipSuccess) e = order_behind_edits(v, st);
     if (e == hipSuccess) e = reserve_block();
@@ -851,17 +832,16 @@ extern "C" int vrc_voxels_count(vrc_volume* v, int which, int closed, const uint
     if (const int rc = voxel_query(what, v, which, closed, lo_hi, &q)) return rc;
     // synchronous on the NULL stream, behind the last asynchronous edit (a device-memory extraction, which shares the
     // block, included)
-    hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = order_behind_edits(v, nullptr);
-    if (e == hipSuccess) e = reserve_voxel_slots(v);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    vrc::voxels_offsets_run(v->d_bricks, v->depth, q, v->d_surface, nullptr, nullptr);
-    e = hipGetLastError();
     unsigned long long T = 0;
-    if (e == hipSuccess) e = hipMemcpy(&T, vrc::voxels_total_slot(v->d_surface, v->depth), 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
-    *count = T;
-    return VRC_OK;
+    const int rc = staged_call(what, null_stream_call(v, nullptr, false, false), [&]() {
+        hipError_t e = reserve_voxel_slots(v);
+        if (e != hipSuccess) return e;
+        vrc::voxels_offsets_run(v->d_bricks, v->depth, q, v->d_surface, nullptr, nullptr);
+        if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpy(&T, vrc::voxels_total_slot(v->d_surface, v->depth), 8, hipMemcpyDeviceToHost);
+        return e;
+    });
+    if (!rc) *count = T;
+    return rc;
 }
 
 extern "C" int vrc_voxels_extract(vrc_volume* v, int which, int closed, const uint32_t* lo_hi, int format, uint64_t first, uint64_t capacity, void* out,
@@ -909,20 +889,16 @@ extern "C" int vrc_volume_flood(vrc_volume* region, vrc_volume* medium, int conn
     if (region == medium) return vrc::fail(VRC_ERR_INVALID, "%s: region and medium are the same volume", what);
     if (const int rc = check_connectivity(what, connectivity)) return rc;
     if (const int rc = check_through(what, through)) return rc;
-    if (region->depth != medium->depth) return vrc::fail(VRC_ERR_INVALID, "%s: volumes of depths %u and %u", what, region->depth, medium->depth);
-    if (region->device != medium->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, region->device, medium->device);
-    // the NULL stream, behind the last asynchronous edit of either volume, as commit / download are
-    hipError_t e = hipSetDevice(region->device);
-    if (e == hipSuccess) e = order_behind_edits(region, nullptr);
-    if (e == hipSuccess) e = order_behind_edits(medium, nullptr);
-    if (e == hipSuccess) e = reserve(region->d_flood, region->flood_cap, vrc::flood_scratch_bytes(region->depth));
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    if (const int rc = check_pair(what, region, medium, true)) return rc;
+    // the NULL stream, behind the last asynchronous edit of either volume, as commit / download are; recorded as region's last
+    // edit: edits on streams made by vrc_stream_create do not wait for the NULL stream
     uint32_t sweeps = 0, converged = 0;
-    e = vrc::flood_run(region->d_bricks, medium->d_bricks, region->depth, connectivity, through,
-                       max_sweeps ? max_sweeps : vrc::flood_sweep_bound(region->depth), region->d_flood, nullptr, &sweeps, &converged);
-    // recorded as region's last edit: edits on streams made by vrc_stream_create do not wait for the NULL stream
-    if (e == hipSuccess) e = finish(region, VRC_MEM_DEVICE, nullptr, true);
-    if (e != hipSuccess) return vrc::fail_hip(e, what);
+    const int flooded = staged_call(what, null_stream_call(region, medium, true, false), [&]() {
+        const hipError_t e = reserve(region->d_flood, region->flood_cap, vrc::flood_scratch_bytes(region->depth));
+        return e != hipSuccess ? e : vrc::flood_run(region->d_bricks, medium->d_bricks, region->depth, connectivity, through,
+                                                    max_sweeps ? max_sweeps : vrc::flood_sweep_bound(region->depth), region->d_flood, nullptr, &sweeps, &converged);
+    });
+    if (flooded) return flooded;
     if (stats) {
         uint64_t reached = 0;
         const int rc = vrc_volume_solid_count(region, &reached);
@@ -935,6 +911,7 @@ extern "C" int vrc_volume_flood(vrc_volume* region, vrc_volume* medium, int conn
 extern "C" int vrc_volume_commit(vrc_volume* v, vrc_scene** out, float* build_ms)
 {
     if (!v || !out) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_commit: null argument");
+    // not a staged_call: the builder is a frame of its own, with its own texts, timing and synchronisation; only the wait is the volume's
     hipError_t e = hipSetDevice(v->device);
     if (e == hipSuccess) e = order_behind_edits(v, nullptr);
     if (e != hipSuccess) return vrc::fail_hip(e, "vrc_volume_commit");
@@ -951,18 +928,13 @@ extern "C" int vrc_volume_commit(vrc_volume* v, vrc_scene** out, float* build_ms
 extern "C" int vrc_volume_download(vrc_volume* v, uint8_t* solid_host)
 {
     if (!v || !solid_host) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_download: null argument");
-    hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = order_behind_edits(v, nullptr);
+    // the dense bytes are the call's one list, in host memory: staged in a block of the call's own, on the NULL stream
     const uint64_t S = 1ull << v->depth;
-    uint32_t* d_dense = nullptr;
-    if (e == hipSuccess) e = hipMalloc((void**)&d_dense, S * S * S);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_expand_dense, grid_for(S * S * S / 4u), dim3(256), 0, nullptr, (const uint8_t*)v->d_bricks, (uint32_t)S, d_dense);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(solid_host, d_dense, S * S * S, hipMemcpyDeviceToHost);
-    if (d_dense) (void)hipFree(d_dense);
-    return done(e, "vrc_volume_download");
+    const StagePart parts[] = {{solid_host, (size_t)(S * S * S), STAGE_OUT}};
+    return staged_call("vrc_volume_download", volume_call(v->device, VRC_MEM_HOST, nullptr, v, false), parts, [&](void* const* d) {
+        hipLaunchKernelGGL(k_expand_dense, grid_for(S * S * S / 4u), dim3(256), 0, nullptr, (const uint8_t*)v->d_bricks, (uint32_t)S, (uint32_t*)d[0]);
+        return hipSuccess;
+    });
 }
 
 extern "C" int vrc_volume_edit_scratch_bytes(const vrc_volume* v, uint64_t* bytes)
@@ -977,21 +949,19 @@ extern "C" int vrc_volume_edit_scratch_bytes(const vrc_volume* v, uint64_t* byte
 extern "C" int vrc_volume_solid_count(vrc_volume* v, uint64_t* count)
 {
     if (!v || !count) return vrc::fail(VRC_ERR_INVALID, "vrc_volume_solid_count: null argument");
-    hipError_t e = hipSetDevice(v->device);
-    if (e == hipSuccess) e = order_behind_edits(v, nullptr);
-    if (e == hipSuccess) e = hipMemsetAsync(v->d_count, 0, 8, nullptr);
-    if (e == hipSuccess) {
+    unsigned long long total = 0;
+    const int rc = staged_call("vrc_volume_solid_count", null_stream_call(v, nullptr, false, false), [&]() {
+        hipError_t e = hipMemsetAsync(v->d_count, 0, 8, nullptr);
+        if (e != hipSuccess) return e;
         const uint64_t n_words = v->n_bricks / 4u;
         uint64_t groups = (n_words + 255u) / 256u;
         if (groups > 4096u) groups = 4096u;
         hipLaunchKernelGGL(k_count_solid, dim3((uint32_t)groups), dim3(256), 0, nullptr, v->d_bricks, n_words, v->d_count);
-        e = hipGetLastError();
-    }
-    unsigned long long total = 0;
-    if (e == hipSuccess) e = hipMemcpy(&total, v->d_count, 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return vrc::fail_hip(e, "vrc_volume_solid_count");
-    *count = total;
-    return VRC_OK;
+        if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpy(&total, v->d_count, 8, hipMemcpyDeviceToHost);
+        return e;
+    });
+    if (!rc) *count = total;
+    return rc;
 }
 
 // ---- the sparse tile stream (vrc.h: vrc_pack_*; kernels and format arithmetic: vrc_pack.hip, vrc_pack.h) ------------
@@ -1051,6 +1021,7 @@ extern "C" int vrc_pack_volume(vrc_volume* v, void* out, uint64_t capacity, vrc_
     if (const int rc = check_mem(what, mem)) return rc;
     if (!out && capacity) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer with capacity %llu", what, (unsigned long long)capacity);
     if (out && mem == VRC_MEM_DEVICE && ((uintptr_t)out & 3u)) return vrc::fail(VRC_ERR_INVALID, "%s: device buffer %p is not aligned to 4 bytes", what, out);
+    // not a staged_call: the host reads the totals back, sizes and refuses by them, and only then emits
     hipError_t e = hipSetDevice(v->device);
     if (e == hipSuccess) e = order_behind_edits(v, nullptr);
     if (e == hipSuccess) e = pack_scratch(v);
@@ -1095,6 +1066,7 @@ extern "C" int vrc_unpack_volume(vrc_volume* v, const void* data, uint64_t bytes
     }
     if (const char* rule = pack_header_rule(h, bytes, v->depth)) return vrc::fail(VRC_ERR_INVALID, "%s: rule %s", what, rule);
     const uint32_t M = h[4], P = h[5];
+    // not a staged_call: the host reads the check's findings back and writes only a stream that broke no rule
     e = hipSetDevice(v->device);
     if (e == hipSuccess) e = order_behind_edits(v, nullptr);
     if (e == hipSuccess) e = pack_scratch(v);

@@ -1,8 +1,9 @@
 // vrc_volume_state.h -- what the entry points of the editable volume share (vrc_volume.hip: the volume itself;
-// vrc_snapshots.hip: the labels and distance fields taken from it): the volume's record, the argument checks with one text
-// each, the rule that orders a call behind the volume's last asynchronous edit, the grow-only device block, and the one
-// frame of every call that takes a memory kind and lists of arguments (staged_call).  Which stream every entry point runs
-// on, what it waits for, whether it is recorded as an edit and whether it is synchronous: the table in DESIGN.md.
+// vrc_volume_ops.hip: the calls between two volumes and along their axes; vrc_snapshots.hip: the labels, fields and deltas
+// taken from it): the volume's record, the argument checks with one text each, the rule that orders a call behind the last
+// asynchronous edit of the volumes it names, the grow-only device block, and the one frame of every call (staged_call, with
+// lists of arguments or without).  Which stream every entry point runs on, what it waits for, whether it is recorded as an
+// edit and whether it is synchronous: the table in DESIGN.md.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -79,6 +80,19 @@ inline int check_same(const char* what, const char* noun, uint32_t depth, int de
     if (v->device != device) return vrc::fail(VRC_ERR_INVALID, "%s: %s on device %d, volume on device %d", what, noun, device, v->device);
     return VRC_OK;
 }
+// Two volumes of one call: not one volume twice, on one device and, same_depth, of one depth.  `a` is printed before `b`;
+// vrc_volume_copy_region and vrc_volume_stamp_affine print src first, every other call dst.
+inline int check_distinct(const char* what, const vrc_volume* a, const vrc_volume* b)
+{
+    return a != b ? VRC_OK : vrc::fail(VRC_ERR_INVALID, "%s: source and destination are the same volume", what);
+}
+inline int check_pair(const char* what, const vrc_volume* a, const vrc_volume* b, bool same_depth)
+{
+    if (const int rc = check_distinct(what, a, b)) return rc;
+    if (same_depth && a->depth != b->depth) return vrc::fail(VRC_ERR_INVALID, "%s: volumes of depths %u and %u", what, a->depth, b->depth);
+    if (a->device != b->device) return vrc::fail(VRC_ERR_INVALID, "%s: volumes on devices %d and %d", what, a->device, b->device);
+    return VRC_OK;
+}
 // what one launch takes: a lane per item in 256-lane workgroups, or a workgroup (blockIdx.x) per item
 constexpr uint64_t LANE_ITEMS = 0x7fffffffull * 256ull, GROUP_ITEMS = 0x7fffffffull;
 inline int check_count(const char* what, uint64_t n, uint64_t limit, const char* items)
@@ -118,8 +132,8 @@ inline hipError_t order_behind_edits(vrc_volume* v, hipStream_t st)
     return v->edit_pending ? hipStreamWaitEvent(st, v->edit_done, 0) : hipSuccess;
 }
 
-// the end of every call that takes `mem`: a host-memory call is synchronous, a device-memory edit is recorded as the
-// volume's last asynchronous edit
+// the end of every call: a host-memory call is synchronous, a device-memory edit is recorded as the volume's last
+// asynchronous edit
 inline hipError_t finish(vrc_volume* v, int mem, hipStream_t st, bool is_edit)
 {
     if (mem == VRC_MEM_HOST) return hipStreamSynchronize(st);
@@ -140,7 +154,7 @@ hipError_t reserve(T*& block, size_t& cap, size_t need)
     return e;
 }
 
-// ---- the frame of a call that takes `mem` and lists of arguments ------------------------------------------------
+// ---- the frame of every call: with lists of arguments in `mem`, or without ----------------------------------------------
 
 // One list: `bytes` at the caller's `p`, read by the launch (IN), written by it (OUT) or both (INOUT: it goes up first,
 // so that what the launch leaves alone comes back as it was).  p == nullptr or bytes == 0: the part is absent and its
@@ -152,7 +166,8 @@ struct StagePart {
     int dir;
 };
 
-// How the call is ordered.  `v`: the volume it reads or writes, nullptr for a call on a snapshot alone.
+// How the call is ordered.  `v`: the volume it reads or writes, nullptr for a call on a snapshot alone.  Only the
+// constructors below spell out the flags.
 struct Call {
     int device;
     int mem;
@@ -162,7 +177,33 @@ struct Call {
     bool stage_in_v;       // host memory is staged in v's grow-only block; else in a block of the call's own, freed at the end
     bool wait_always;      // behind v's last asynchronous edit whatever the memory kind: the call reads the occupancy or a
                            // block the volume shares.  false: a list edit waits in host form only, where it writes v's block
+    vrc_volume* read;      // a second volume, only read (src, medium, ...): behind its last asynchronous edit in both memory
+                           // kinds; nullptr: none
+    bool synchronous;      // the stream is synchronised at the end in device form too
 };
+
+// An edit that reads one list: staged in the volume's block, recorded as its last edit, and -- unlike every other call on a
+// volume -- behind the last asynchronous edit in host form only, where it writes that block; in device form it stays
+// unordered against edits on other streams, as it always was.
+inline Call edit_call(vrc_volume* v, int mem, void* stream) { return Call{v->device, mem, (hipStream_t)stream, v, true, true, false, nullptr, false}; }
+// edit_call through a block the volume shares between calls (vrc_volume_xor_mesh's marks): behind the last edit in both kinds
+inline Call shared_edit_call(vrc_volume* v, int mem, void* stream) { return Call{v->device, mem, (hipStream_t)stream, v, true, true, true, nullptr, false}; }
+// A query: a list in and a list out through the volume's block, behind the last asynchronous edit whatever the memory kind.
+inline Call query_call(vrc_volume* v, int mem, void* stream) { return Call{v->device, mem, (hipStream_t)stream, v, false, true, true, nullptr, false}; }
+// a call on a snapshot alone: no volume to wait for, host memory staged in a block of the call's own
+inline Call snapshot_call(int device, int mem, void* stream) { return Call{device, mem, (hipStream_t)stream, nullptr, false, false, false, nullptr, false}; }
+// a call that reads (is_edit: writes) a volume beside a snapshot or a block the volume shares: behind the volume's last
+// asynchronous edit whatever the memory kind, staged in a block of the call's own
+inline Call volume_call(int device, int mem, void* stream, vrc_volume* v, bool is_edit) { return Call{device, mem, (hipStream_t)stream, v, is_edit, false, true, nullptr, false}; }
+// an edit of dst that reads src: behind the last asynchronous edit of both
+inline Call pair_call(vrc_volume* dst, vrc_volume* src, int mem, void* stream) { return Call{dst->device, mem, (hipStream_t)stream, dst, true, false, true, src, false}; }
+// A call on the NULL stream whose results the host reads: behind the last asynchronous edit of v and of `read` (nullptr:
+// none).  synchronous: the frame synchronises at the end; false where the launch's own blocking read-back has done so.
+// is_edit: recorded as v's edit too, because streams made by vrc_stream_create do not wait for the NULL stream.
+inline Call null_stream_call(vrc_volume* v, vrc_volume* read, bool is_edit, bool synchronous)
+{
+    return Call{v->device, VRC_MEM_DEVICE, nullptr, v, is_edit, false, true, read, synchronous};
+}
 
 // Device memory: launch(d) gets the caller's pointers and the call stays asynchronous on `st`.  Host memory: the parts are
 // laid out in one block in the order given, the IN parts copied up, and after the launch the OUT parts copied down and the
@@ -186,6 +227,7 @@ int staged_call(const char* what, const Call& c, const StagePart (&parts)[N], La
     const bool host = c.mem == VRC_MEM_HOST;
     uint8_t* own = nullptr;
     hipError_t e = hipSetDevice(c.device);
+    if (e == hipSuccess && c.read) e = order_behind_edits(c.read, c.st);
     if (e == hipSuccess && c.v && (c.wait_always || host)) e = order_behind_edits(c.v, c.st);
     if (host && total) {
         if (e == hipSuccess) e = c.stage_in_v ? reserve(c.v->d_stage, c.v->stage_cap, total) : hipMalloc((void**)&own, total);
@@ -202,8 +244,18 @@ int staged_call(const char* what, const Call& c, const StagePart (&parts)[N], La
         for (size_t i = 0; i < N; ++i)
             if (e == hipSuccess && d[i] && (parts[i].dir & STAGE_OUT)) e = hipMemcpyAsync((void*)parts[i].p, d[i], parts[i].bytes, hipMemcpyDeviceToHost, c.st);
     if (e == hipSuccess) e = finish(c.v, c.mem, c.st, c.is_edit);
+    if (e == hipSuccess && c.synchronous && !host) e = hipStreamSynchronize(c.st);
     if (own) (void)hipFree(own);
     return done(e, what);
+}
+
+// The frame of a call without lists: set the device, order, launch(), hipGetLastError, finish.  What the call allocates between
+// ordering and launch goes into launch(), which returns what its HIP calls returned.
+template <class Launch>
+int staged_call(const char* what, const Call& c, Launch launch)
+{
+    const StagePart none[] = {{nullptr, 0u, STAGE_IN}};
+    return staged_call(what, c, none, [&](void* const*) { return launch(); });
 }
 
 }  // namespace

@@ -483,7 +483,7 @@ def emulate_profile(words, axis, side, a, b, wrong=0):
 
 def emulate_select(words, axis, side, lo, hi, of, a, b, wrong=0):
     """k_columns_select (vrc_columns.hip:175-211) for the bundles (a, b): (K as uint32 [bundles, steps] in the order of the
-    words' indices, those indices).  lo and hi as vrc_columns_select hands them on (vrc_snapshots.hip:934: at most S + 1)"""
+    words' indices, those indices).  lo and hi as vrc_columns_select hands them on (its band_lo, band_hi: at most S + 1)"""
     S = words.S
     lg = S.bit_length() - 2
     lo, hi = min(lo, S + 1), min(hi, S + 1)

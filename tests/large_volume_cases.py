@@ -72,7 +72,7 @@ def box_launch_groups(lo, hi):
 
 def later_items(items, lanes):
     """the items a launch of `lanes` lanes takes after every lane's first, in the order of the loop
-    for (it = lane; it < items; it += lanes) (vrc_volume.hip:64, 112, 210, 251; vrc_stamp.hip:70): walk's rows with iteration >= 1"""
+    for (it = lane; it < items; it += lanes) (k_fill_boxes, k_fill_spheres, k_copy_region, k_count_boxes of vrc_volume.hip; vrc_stamp.hip:70): walk's rows with iteration >= 1"""
     return np.arange(min(lanes, items), items, dtype=np.int64)
 
 
@@ -107,7 +107,7 @@ def differing_in(words, a, b):
 # ---- the many-box launch --------------------------------------------------------------------------------------------
 
 def split_for(depth, n):
-    """vrc_volume.hip:358-367: workgroups (gridDim.y) per box or sphere of a list of n in a volume of `depth`"""
+    """split_for of vrc_volume.hip: workgroups (gridDim.y) per box or sphere of a list of n in a volume of `depth`"""
     split = (4096 + n - 1) // n
     max_words = ((1 << (3 * depth)) // 8) // 4
     useful = (max_words + 255) // 256
@@ -149,7 +149,7 @@ def fill_spheres(vol, spheres, value):
 
 
 def sphere_box(S, sphere):
-    """k_fill_spheres' clipped bounding box of (cx, cy, cz, r), or None (vrc_volume.hip:101-108)"""
+    """k_fill_spheres' clipped bounding box of (cx, cy, cz, r), or None (the head of the kernel in vrc_volume.hip)"""
     c, r = sphere[:3], sphere[3]
     lo = [max(0, int(v) - int(r)) for v in c]
     hi = [min(S, int(v) + int(r) + 1) for v in c]
@@ -372,7 +372,7 @@ def big_scene(which):
 
 
 def copy_box(src_lo, size, dst_lo, Ss, Sd):
-    """vrc_volume_copy_region's clipping (vrc_volume.hip:533-542): (lo, hi, offset) of the destination box, or None"""
+    """vrc_volume_copy_region's clipping (its loop over the axes in vrc_volume.hip): (lo, hi, offset) of the destination box, or None"""
     lo, hi, off = [], [], []
     for a in range(3):
         d0 = max(0, -dst_lo[a])

@@ -93,7 +93,7 @@ def stats_pass(T, groups, drop_later=False, tie="index"):
     """k_travel_stats (vrc_travel.hip:225-252) on a field T under `groups` workgroups: (reached, max, argmax) as the kernel
     combines them -- a lane counts the values of its quads in 32 bits and keeps the largest (value << 32) | ~dense index
     (:237-238), the workgroup takes the largest of its lanes (:241-246) and the sum of their counts (:247), and a 64-bit
-    atomic each joins the workgroups (:249-250); decode as vrc_snapshots.hip does: no value -> (0, 0, (0, 0, 0)).
+    atomic each joins the workgroups (:249-250); decode as decode_argmax of vrc_snapshots.hip does: no value -> (0, 0, (0, 0, 0)).
     For experiments with a wrong kernel: drop_later=True takes only each lane's first quad (a loop that never strides);
     tie="lane" breaks a tie of values by the lower thread, then the lower workgroup, then the earlier iteration -- by who saw
     it, not by where it lies."""

@@ -149,7 +149,7 @@ def handle(fill=0, **words):
 
 
 # `device` is the first 32-bit word of a vrc_volume and `depth` its third
-ZERO, OTHER, DEPTH_3, DEVICE_1 = handle(), handle(), handle(w2=3), handle(w0=1)
+ZERO, OTHER, DEPTH_3, DEVICE_1, DEPTH_1_DEVICE_1 = handle(), handle(), handle(w2=3), handle(w0=1), handle(w0=1, w2=1)
 OUT, MAP = (C.c_uint32 * 4)(7, 7, 7, 7), (C.c_int32 * 4)(1, 2, 3, 4)
 
 
@@ -208,12 +208,18 @@ REFUSALS = [
     ("vrc_columns_select", select_args(of=4), "bad of 4"),
     ("vrc_columns_select", select_args(op=3), "bad op 3"),
     ("vrc_columns_select", select_args(op=-1), "bad op -1"),
+    # two refusals at once: the one that wins
+    ("vrc_columns_select", select_args(src=ZERO, direction=6), "source and destination are the same volume"),
+    ("vrc_columns_select", select_args(src=DEPTH_1_DEVICE_1), "volumes of depths 0 and 1"),
+    ("vrc_columns_select", select_args(src=DEPTH_3, op=3), "volumes of depths 0 and 3"),
+    ("vrc_columns_select", select_args(src=DEVICE_1, direction=-2), "volumes on devices 0 and 1"),
+    ("vrc_columns_select", select_args(src=DEVICE_1, lo=5, hi=4), "volumes on devices 0 and 1"),
 ]
 
 
 def untouched():
     return (not any(ZERO) and not any(OTHER) and list(DEPTH_3) == [0, 0, 3] + [0] * 125 and list(DEVICE_1) == [1] + [0] * 127
-            and list(OUT) == [7] * 4 and list(MAP) == [1, 2, 3, 4])
+            and list(DEPTH_1_DEVICE_1) == [1, 0, 1] + [0] * 125 and list(OUT) == [7] * 4 and list(MAP) == [1, 2, 3, 4])
 
 
 @pytest.mark.parametrize("index", range(len(REFUSALS)), ids=["%s-%d" % (c[0], i) for i, c in enumerate(REFUSALS)])

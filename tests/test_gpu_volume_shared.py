@@ -1,20 +1,24 @@
 """The code the volume features share (vrc_group.h, vrc_box_words.h, vrc_volume_state.h), at the smallest shapes at which
 it can go wrong: the workgroup sum with idle lanes and idle waves, the two ways a destination word is written at the sizes
 on either side of the shared-word rule, and the staged call with a block that has to grow and on a stream of its own behind
-a device-memory edit, with every combination of optional parts in a block of the call's own, and with a part that goes up
-and comes back; the window of the emit prologue the three lists share (vrc_list.h) and the paged fetch of the Python
+a device-memory edit -- of the volume it writes, and of the second volume it only reads --, with every combination of
+optional parts in a block of the call's own, and with a part that goes up and comes back; the window of the emit prologue the three lists share (vrc_list.h) and the paged fetch of the Python
 wrapper.  Every expectation is NumPy's (the models of tests/*_model.py); every comparison is exact."""
 import functools
 
 import numpy as np
 import pytest
 
+import cells_model
+import columns_model
 import components_model
 import contact_model
 import delta_model
 import distance_model
 import fall_model
 import fracture_model
+import levels_model
+import morph_model
 import rect_cases
 import rect_model
 import rigid_model
@@ -209,6 +213,56 @@ def test_staged_calls_in_device_memory_behind_an_edit_on_another_stream(built):
     assert (d_big_solid.cpu().numpy() == 1).all()
     assert d_big_counts.cpu().numpy().tolist() == [B ** 3, 9 * 7 * 5, B - 1]
     for h in (labels, field, volume, big):
+        h.close()
+
+
+def test_two_volume_calls_behind_an_edit_of_the_source_on_another_stream(built):
+    """The second volume of the call frame: a device-memory fill of src on one stream -- behind eight fills of a 512^3 volume
+    on that stream, so that it is late -- then, with no synchronisation, every call that only reads src on another stream,
+    each into a destination of its own: all of them see the fill.  16^3 is the smallest size with more than one word per row
+    and a brick that is not shared.  Such a test can show a missing wait; it cannot prove a present one."""
+    import torch
+    import cpuvoxelraycaster_amd as vrc
+    depth, S = 4, 16
+    vol, base = random_volume(4700, depth, 0.37), random_volume(4701, depth, 0.5)
+    base_up, base_down = random_volume(4702, depth + 1, 0.5), random_volume(4703, depth - 2, 0.5)
+    edited = vol.copy()
+    edited[1:15, 3:12, 5:11] = 1
+    assert not np.array_equal(edited, vol)
+    element = morph_model.box(3, 3, 3)
+    birth, survive = sum(1 << c for c in range(9, 27)), sum(1 << c for c in range(6, 27))
+    any_lo, any_hi = levels_model.count_range("any", 2)
+    whole = ((0, 0, 0), (S, S, S))
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.int32).copy()).cuda()
+
+    src, big = volume_of(vol), vrc.VoxelVolume(9)
+    copied, stamped, selected, stepped, morphed = (volume_of(base) for _ in range(5))
+    up, down = volume_of(base_up), volume_of(base_down)
+    d_box, d_whole, d_element = dev(np.array([[1, 3, 5, 15, 12, 11]], np.uint32)), dev(np.array([[0, 0, 0, 512, 512, 512]], np.uint32)), dev(element)
+    torch.cuda.synchronize()
+    with Stream() as first, Stream() as second:
+        for round_ in range(8):
+            big.fillBoxesDevice(1, d_whole.data_ptr(), round_ % 2 == 0, first)
+        src.fillBoxesDevice(1, d_box.data_ptr(), True, first)
+        copied.copyRegion(src, whole[0], whole[1], whole[0], stamp_model.OR, second)
+        stamped.stampAffine(src, vrc.make_affine(*stamp_model.IDENTITY), None, None, stamp_model.REPLACE, second)
+        src.selectColumns(4, 1, 3, columns_model.SOLID, selected, stamp_model.ANDNOT, second)
+        src.cellStep(birth, survive, 26, False, stepped, False, second)
+        src.morphDevice(morphed, morph_model.DILATE, len(element), d_element.data_ptr(), stream=second)
+        src.expandInto(up, stamp_model.OR, second)
+        src.reduceInto(down, any_lo, any_hi, stamp_model.REPLACE, second)
+    assert np.array_equal(src.download(), edited)
+    assert np.array_equal(copied.download(), stamp_model.stamp(base, edited, *stamp_model.IDENTITY, *whole, stamp_model.OR))
+    assert np.array_equal(stamped.download(), stamp_model.stamp(base, edited, *stamp_model.IDENTITY, *whole, stamp_model.REPLACE))
+    assert np.array_equal(selected.download(), columns_model.select(base, edited, 4, 1, 3, columns_model.SOLID, stamp_model.ANDNOT))
+    assert np.array_equal(stepped.download(), cells_model.step(edited, birth, survive, 26, 0)[0])
+    assert np.array_equal(morphed.download(), morph_model.apply(base, edited, morph_model.DILATE, element))
+    assert np.array_equal(up.download(), levels_model.expand(base_up, edited, stamp_model.OR))
+    assert np.array_equal(down.download(), levels_model.reduce(base_down, edited, any_lo, any_hi, stamp_model.REPLACE))
+    assert int(big.solidCount()) == 0                            # the eighth fill cleared it
+    for h in (src, big, copied, stamped, selected, stepped, morphed, up, down):
         h.close()
 
 

@@ -68,6 +68,15 @@ REFUSALS = [
     ("vrc_levels_expand", expand_args(dst=ZERO), "destination of depth 0 is not above the source's 3"),
     ("vrc_levels_expand", expand_args(op=3), "bad op 3"),
     ("vrc_levels_expand", expand_args(op=-2), "bad op -2"),
+    # two refusals at once: the one that wins
+    ("vrc_levels_reduce", reduce_args(dst=DEPTH_5, op=3), "source and destination are the same volume"),
+    ("vrc_levels_reduce", reduce_args(dst=DEVICE_1, src=DEPTH_3), "volumes on devices 1 and 0"),
+    ("vrc_levels_reduce", reduce_args(src=DEVICE_1, op=3), "volumes on devices 0 and 1"),
+    ("vrc_levels_reduce", reduce_args(src=ALSO_3, op=-1), "destination of depth 3 is not below the source's 3"),
+    ("vrc_levels_expand", expand_args(src=DEPTH_5, op=3), "source and destination are the same volume"),
+    ("vrc_levels_expand", expand_args(dst=DEVICE_1, src=DEPTH_5), "volumes on devices 1 and 0"),
+    ("vrc_levels_expand", expand_args(dst=DEVICE_1, op=3), "volumes on devices 1 and 0"),
+    ("vrc_levels_expand", expand_args(dst=ALSO_3, op=3), "destination of depth 3 is not above the source's 3"),
 ]
 
 

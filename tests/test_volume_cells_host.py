@@ -160,6 +160,12 @@ REFUSALS = [
     ("vrc_cells_fill_random", (p(ZERO), 1, M32 << 32, p(BOX), 0, None), "threshold 18446744069414584320 above 2^32"),
     ("vrc_cells_fill_random", (p(ZERO), 1, 1 << 32, None, 3, None), "bad op 3"),
     ("vrc_cells_fill_random", (p(ZERO), 1, 0, p(BOX), -1, None), "bad op -1"),
+    # two refusals at once: the one that wins
+    ("vrc_cells_step", step_args(src=ZERO, neighbours=18), "source and destination are the same volume"),
+    ("vrc_cells_step", step_args(src=DEPTH_3, dst=DEVICE_1), "volumes of depths 0 and 3"),
+    ("vrc_cells_step", step_args(src=DEPTH_3, outside=2), "volumes of depths 0 and 3"),
+    ("vrc_cells_step", step_args(src=DEVICE_1, neighbours=0), "volumes on devices 0 and 1"),
+    ("vrc_cells_step", step_args(dst=DEVICE_1, changed=C.byref(CHANGED), mem=2), "volumes on devices 1 and 0"),
 ]
 
 

@@ -173,6 +173,10 @@ REFUSALS = [
     ("vrc_delta_apply", (p(ZERO), None, None), "null argument"),
     ("vrc_delta_apply", (p(ZERO), p(ONES), None), "delta of depth 0, volume of depth 16843009"),
     ("vrc_delta_apply", (p(ZERO), p(DEVICE_1), None), "delta on device 0, volume on device 1"),
+    # two refusals at once: the one that wins
+    ("vrc_delta_diff", (p(ZERO), p(ZERO), None, None), "null argument"),
+    ("vrc_delta_diff", (p(ONES), p(DEVICE_1), C.byref(OUT), None), "volumes of depths 16843009 and 0"),
+    ("vrc_delta_diff", (p(DEVICE_1), p(ONES), C.byref(OUT), None), "volumes of depths 0 and 16843009"),
 ]
 
 

@@ -164,7 +164,7 @@ def test_the_slice_models_are_stamp_models():
 # ---- 3. many boxes ------------------------------------------------------------------------------------------------------
 
 def test_many_box_launches_stride():
-    """split_for (vrc_volume.hip:358-367) caps gridDim.y at `useful` = the groups that cover the volume's WORDS once, but a box
+    """split_for (vrc_volume.hip) caps gridDim.y at `useful` = the groups that cover the volume's WORDS once, but a box
     has up to one item more per brick row than its row has words (wpr, vrc_box_words.h:84): a whole-volume box strides
     whenever split_for reaches `useful`, from 32^3 on, and any box of more than 256 items strides in a list of 4096 or more.
     The suite had such launches already -- fillBoxes of one whole-volume box at 64^3 in test_gpu_volume_components.py, a

@@ -182,6 +182,26 @@ def cases():
             (name, (p(ZERO), 5, 4, p(OTHER), 1, None), "lo 5 above hi 4"),
             (name, (p(ZERO), 0, 4, p(ONES), 2, None), "field of depth 0, volume of depth 16843009"),
             (name, (p(ZERO), 0, 4, p(DEVICE_1), 2, None), "field on device 0, volume on device 1")]
+
+    # two refusals at once: the one that wins (at the end, so that the cases above keep their numbers)
+    name = "vrc_volume_copy_region"
+    out += [(name, (p(ZERO), p(ZERO), *good, 3, None), "source and destination are the same volume"),
+            (name, (p(ZERO), p(ONES), *good, 3, None), "bad op 3"),
+            (name, (p(DEVICE_1), p(ZERO), *good, -1, None), "bad op -1"),
+            (name, (p(DEVICE_1), p(ZERO), *good, 2, None), "volumes on devices 0 and 1")]
+    name = "vrc_volume_stamp_affine"
+    out += [(name, (p(ZERO), p(ZERO), C.byref(ident), *box, 3, None), "source and destination are the same volume"),
+            (name, (p(ZERO), p(ZERO), C.byref(affine(reserved=1)), *box, 0, None), "source and destination are the same volume"),
+            (name, (p(ZERO), p(ONES), C.byref(ident), *box, 3, None), "bad op 3"),
+            (name, (p(ZERO), p(OTHER), C.byref(affine(reserved=1)), *box, 3, None), "bad op 3"),
+            (name, (p(DEVICE_1), p(ZERO), C.byref(affine(reserved=2)), *box, 0, None), "reserved is 2, not 0"),
+            (name, (p(DEVICE_1), p(ZERO), C.byref(ident), *box, 2, None), "volumes on devices 0 and 1")]
+    name = "vrc_volume_flood"
+    out += [(name, (p(ZERO), p(ZERO), 18, 0, 0, None), "region and medium are the same volume"),
+            (name, (p(ZERO), p(ONES), 18, 0, 0, None), "connectivity 18 is neither 6 nor 26"),
+            (name, (p(ZERO), p(DEVICE_1), 6, 2, 0, None), "bad through 2"),
+            (name, (p(ONES), p(DEVICE_1), 26, 0, 0, None), "volumes of depths 16843009 and 0"),
+            (name, (p(DEVICE_1), p(ZERO), 26, 0, 0, None), "volumes on devices 1 and 0")]
     return out
 
 

@@ -169,6 +169,12 @@ REFUSALS = [
     (args(n=3, offsets=FAR, origin=NEAR), "offset 0 is (-19, 0, 4) after the origin, beyond +-16"),
     (args(n=2, offsets=WIDE, origin=ORIGIN), "offset 0 is (4294967295, -1, -2147483647) after the origin, beyond +-16"),
     (args(n=2, offsets=GOOD, origin=ORIGIN), "offset 0 is (2147483664, -17, -2147483647) after the origin, beyond +-16"),
+    # two refusals at once: the one that wins
+    (args(src=ZERO, what=2), "source and destination are the same volume"),
+    (args(src=DEPTH_3, dst=DEVICE_1), "volumes of depths 0 and 3"),
+    (args(src=DEPTH_3, op=3), "volumes of depths 0 and 3"),
+    (args(dst=DEVICE_1, of=0), "volumes on devices 1 and 0"),
+    (args(src=DEVICE_1, mem=2), "volumes on devices 0 and 1"),
 ]
 
 

@@ -219,7 +219,13 @@ def test_travel_refusal_texts(built):
              (name, (p(zero), p(other), 26, 2, 0, C.byref(out), None), "bad through 2"),
              (name, (p(zero), p(ones), 6, 1, 7, C.byref(out), None), "volumes of depths 0 and 16843009"),
              (name, (p(zero), p(device_1), 6, 1, 0, C.byref(out), None), "volumes on devices 0 and 1"),
-             (name, (p(zero), p(zero), 26, 0, 0, C.byref(out), None), "depth 0 not in [2,10]")]
+             (name, (p(zero), p(zero), 26, 0, 0, C.byref(out), None), "depth 0 not in [2,10]"),
+             # two refusals at once: the one that wins
+             (name, (p(zero), p(ones), 18, 0, 0, C.byref(out), None), "connectivity 18 is neither 6 nor 26"),
+             (name, (p(zero), p(device_1), 26, 2, 0, C.byref(out), None), "bad through 2"),
+             (name, (p(ones), p(device_1), 6, 1, 0, C.byref(out), None), "volumes of depths 16843009 and 0"),
+             (name, (p(device_1), p(zero), 6, 0, 0, C.byref(out), None), "volumes on devices 1 and 0"),
+             (name, (p(zero), p(zero), 7, 0, 0, C.byref(out), None), "connectivity 7 is neither 6 nor 26")]
     name = "vrc_travel_trace_paths"
     too_many = 0x7FFFFFFF * 256 + 1
     cases += [(name, (None, 1, capi.ptr(u32), 4, capi.ptr(u32), capi.ptr(u64), 0, None), "null distance field"),

@@ -25,20 +25,20 @@ device-memory extraction of the same step is still on its stream (order "extract
 The voxel lists keep no block of their own: they use the surface calls' offsets block (vrc.h:454-455), so a count of EITHER
 family behind an extraction of the other is the library's to order as well (orders "surface_behind", "voxels_behind").
 
-Sizes of the per-volume scratch blocks (Mirror.scratch_bytes), each restated with the line it was read off:
-  staging, host form   12 n set_voxels (vrc_volume.hip:429), 24 n fill_boxes (:445), 16 n fill_spheres (:462),
-                       64 n brush at hits, 16 n in device form (:484), 36 n xor_mesh (:517), 13 n get_voxels (:603),
-                       32 n count_boxes (:619), 16 per face / rectangle of a host window (:697, :724),
-                       32 n fill_capsules (vrc_volume.hip:511), 64 n stroke at hits, 16 n in device form (:533),
-                       36 n raster_mesh (:560),
+Sizes of the per-volume scratch blocks (Mirror.scratch_bytes), each restated with the place it was read off (the StagePart
+lists of the entry points in vrc_volume.hip, by function):
+  staging, host form   12 n set_voxels, 24 n fill_boxes, 16 n fill_spheres, 64 n brush at hits, 16 n in device form (hits_call),
+                       36 n xor_mesh, 13 n get_voxels, 32 n count_boxes, 16 per face / rectangle of a host window
+                       (mesh_extract), 32 n fill_capsules, 64 n stroke at hits, 16 n in device form (hits_call), 36 n raster_mesh,
                        record * min(window, 2^20) of a host voxel list, record = 12 (x y z) or 16 (x y z m) and
-                       window = window_of(first, capacity, T); nothing where the window is empty (vrc_volume.hip:786-788)
+                       window = window_of(first, capacity, T); nothing where the window is empty (windowed_extract)
   column calls         nothing: the 16 U V records of a host profile and the 4 U V bytes of each host map of a fill are
-                       staged in a block of the call's own (vrc.h:1329-1330; vrc_snapshots.hip:82 gives these calls
-                       stage_in_v = false, :896 and :915 size the parts), and select stages nothing (:937-941)
+                       staged in a block of the call's own (vrc.h:1329-1330; volume_call in vrc_volume_state.h gives these
+                       calls stage_in_v = false, vrc_columns_profile and vrc_columns_fill size the parts), and
+                       vrc_columns_select stages nothing
   mark field           8^(depth-1) (vrc_voxelize.hip:145)
   surface offsets      8 (ceil(8^depth / 32 / 256) + 7) (vrc_surface.hip, surface_scratch_bytes); the voxel lists use the same block and add
-                       nothing (vrc_volume.hip:838-841); a refused voxel call reserves nothing (:871-873 come before :875)
+                       nothing (reserve_voxel_slots in vrc_volume.hip); a refused voxel call reserves nothing (vrc_voxels_extract checks first)
   rectangle block      8 (ceil(6 S^2 w / 256) + 7) + 8 S^2 w, w = max(1, S / 32) (vrc_rects.hip, rect_scratch_bytes)
   pack slots           64 + 8 (tiles + 1) (vrc_pack.hip:327)
   flood block          4 (3 T^3 + 8), T = max(1, S / 32) (vrc_flood.hip:186-190), on the REGION
@@ -100,7 +100,7 @@ AT_HITS = ("fillSpheresAtHits", "strokeAtHits")                       # the cent
 LIFETIME = ("cloneSecond", "recreateSecond", "snapshotLabels", "snapshotClone")
 FAMILIES = EDITS + QUERIES + REFUSALS + LIFETIME
 
-# the families that share a persistent block of `v` (vrc_volume_state.h:15-46); d_stage: in a form that stages
+# the families that share a persistent block of `v` (struct vrc_volume in vrc_volume_state.h); d_stage: in a form that stages
 BLOCKS = {
     "d_stage": ("setVoxels", "fillBoxes", "fillSpheres", "fillSpheresAtHits", "xorMesh", "getVoxels", "countBoxes", "surface", "rects",
                 "fillCapsules", "strokeAtHits", "rasterMesh", "voxels"),
