@@ -26,7 +26,7 @@ import stamp_model
 import surface_model
 import travel_model
 import voxels_model
-from volume_support import Stream, affine_records, volume_of
+from volume_support import Ballast, Stream, affine_records, device_words, event_on, volume_of
 
 pytestmark = pytest.mark.gpu
 
@@ -217,8 +217,9 @@ def test_staged_calls_in_device_memory_behind_an_edit_on_another_stream(built):
 
 
 def test_two_volume_calls_behind_an_edit_of_the_source_on_another_stream(built):
-    """The second volume of the call frame: a device-memory fill of src on one stream -- behind eight fills of a 512^3 volume
-    on that stream, so that it is late -- then, with no synchronisation, every call that only reads src on another stream,
+    """The second volume of the call frame: a device-memory fill of src on one stream -- behind the ballast (volume_support:
+    whole-volume fills of a 512^3 volume) on that stream, so that it is late, which is asserted -- then, with no
+    synchronisation, every call that only reads src on another stream,
     each into a destination of its own: all of them see the fill.  16^3 is the smallest size with more than one word per row
     and a brick that is not shared.  Such a test can show a missing wait; it cannot prove a present one."""
     import torch
@@ -234,18 +235,15 @@ def test_two_volume_calls_behind_an_edit_of_the_source_on_another_stream(built):
     any_lo, any_hi = levels_model.count_range("any", 2)
     whole = ((0, 0, 0), (S, S, S))
 
-    def dev(a):
-        return torch.from_numpy(np.ascontiguousarray(a).view(np.int32).copy()).cuda()
-
-    src, big = volume_of(vol), vrc.VoxelVolume(9)
+    src, ballast = volume_of(vol), Ballast()
     copied, stamped, selected, stepped, morphed = (volume_of(base) for _ in range(5))
     up, down = volume_of(base_up), volume_of(base_down)
-    d_box, d_whole, d_element = dev(np.array([[1, 3, 5, 15, 12, 11]], np.uint32)), dev(np.array([[0, 0, 0, 512, 512, 512]], np.uint32)), dev(element)
+    d_box, d_element = device_words(np.array([[1, 3, 5, 15, 12, 11]], np.uint32)), device_words(element)
     torch.cuda.synchronize()
     with Stream() as first, Stream() as second:
-        for round_ in range(8):
-            big.fillBoxesDevice(1, d_whole.data_ptr(), round_ % 2 == 0, first)
+        ballast.enqueue(first)
         src.fillBoxesDevice(1, d_box.data_ptr(), True, first)
+        late = event_on(first)
         copied.copyRegion(src, whole[0], whole[1], whole[0], stamp_model.OR, second)
         stamped.stampAffine(src, vrc.make_affine(*stamp_model.IDENTITY), None, None, stamp_model.REPLACE, second)
         src.selectColumns(4, 1, 3, columns_model.SOLID, selected, stamp_model.ANDNOT, second)
@@ -253,6 +251,7 @@ def test_two_volume_calls_behind_an_edit_of_the_source_on_another_stream(built):
         src.morphDevice(morphed, morph_model.DILATE, len(element), d_element.data_ptr(), stream=second)
         src.expandInto(up, stamp_model.OR, second)
         src.reduceInto(down, any_lo, any_hi, stamp_model.REPLACE, second)
+        assert not late.query(), "the fill of src was not late: it had landed before the last call was enqueued"
     assert np.array_equal(src.download(), edited)
     assert np.array_equal(copied.download(), stamp_model.stamp(base, edited, *stamp_model.IDENTITY, *whole, stamp_model.OR))
     assert np.array_equal(stamped.download(), stamp_model.stamp(base, edited, *stamp_model.IDENTITY, *whole, stamp_model.REPLACE))
@@ -261,8 +260,8 @@ def test_two_volume_calls_behind_an_edit_of_the_source_on_another_stream(built):
     assert np.array_equal(morphed.download(), morph_model.apply(base, edited, morph_model.DILATE, element))
     assert np.array_equal(up.download(), levels_model.expand(base_up, edited, stamp_model.OR))
     assert np.array_equal(down.download(), levels_model.reduce(base_down, edited, any_lo, any_hi, stamp_model.REPLACE))
-    assert int(big.solidCount()) == 0                            # the eighth fill cleared it
-    for h in (src, big, copied, stamped, selected, stepped, morphed, up, down):
+    assert int(ballast.big.solidCount()) == 0                    # the ballast's last fill cleared it
+    for h in (src, ballast, copied, stamped, selected, stepped, morphed, up, down):
         h.close()
 
 

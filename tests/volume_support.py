@@ -50,6 +50,47 @@ class Stream:
         self.L.vrc_stream_destroy(0, self.h)
 
 
+# ---- a stream kept busy, so that what is enqueued behind it is late ------------------------------------------------
+
+def device_words(a):
+    """a numpy array of 32-bit items as an int32 tensor in device memory"""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.int32).copy()).cuda()
+
+
+# How many times the ballast fills its 512^3 volume.  Sized on the MI355X so that the ballast lasts at least four times the
+# longest host-side enqueue of any call of test_gpu_volume_ordering.py (its docstring and docs/NOTEBOOK.md have the figures).
+BALLAST_FILLS = 2048
+
+
+class Ballast:
+    """One 512^3 volume and BALLAST_FILLS whole-volume device-memory fills of it: enqueue(stream) keeps the stream busy
+    for milliseconds, so that the next call enqueued on it lands late -- an edit to lose a race against.  The fills are
+    the items of ONE vrc_volume_fill_boxes list, so that the backlog stands as soon as the call returns, however slow the
+    host is at enqueuing; a second call clears the volume again."""
+
+    def __init__(self, fills=BALLAST_FILLS):
+        import cpuvoxelraycaster_amd as vrc
+        self.big, self.fills = vrc.VoxelVolume(9), fills
+        self.whole = device_words(np.tile(np.array([[0, 0, 0, 512, 512, 512]], np.uint32), (fills, 1)))
+
+    def enqueue(self, stream):
+        self.big.fillBoxesDevice(self.fills - 1, self.whole.data_ptr(), True, stream)
+        self.big.fillBoxesDevice(1, self.whole.data_ptr(), False, stream)
+
+    def close(self):
+        self.big.close()
+
+
+def event_on(stream):
+    """a torch event recorded on a vrc_stream_create stream right now: event.query() is False while the work enqueued on
+    the stream so far is still running"""
+    import torch
+    event = torch.cuda.Event()
+    event.record(torch.cuda.ExternalStream(stream.value))
+    return event
+
+
 # ---- records of posed pieces -------------------------------------------------------------------------------------
 
 def affine_records(maps):
