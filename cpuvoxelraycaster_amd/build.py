@@ -5,8 +5,8 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libvrc_hip.so")
-SOURCES = ["vrc_kernels.hip", "vrc_build_gpu.hip", "vrc_volume.hip", "vrc_volume_ops.hip", "vrc_snapshots.hip", "vrc_flood.hip", "vrc_components.hip", "vrc_cells.hip", "vrc_columns.hip", "vrc_levels.hip", "vrc_morph.hip", "vrc_delta.hip", "vrc_pack.hip", "vrc_distance.hip", "vrc_travel.hip", "vrc_fall.hip", "vrc_fracture.hip", "vrc_rigid.hip", "vrc_stamp.hip", "vrc_stroke.hip", "vrc_raster.hip", "vrc_voxelize.hip", "vrc_surface.hip", "vrc_voxels.hip", "vrc_rects.hip", "vrc_present.hip", "vrc_api.cpp", "vrc_renderer.cpp", "vrc_ipc.cpp", "vrc_builder.cpp"]
-HEADERS = ["vrc_device.h", "vrc_walk.h", "vrc_internal.h", "vrc_host.h", "vrc_plan.h", "vrc_build_sweeps.h", "vrc_build_grids.h", "vrc_flood.h", "vrc_components.h", "vrc_cells.h", "vrc_columns.h", "vrc_levels.h", "vrc_morph.h", "vrc_delta.h", "vrc_pack.h", "vrc_distance.h", "vrc_travel.h", "vrc_fall.h", "vrc_fracture.h", "vrc_rigid.h", "vrc_stamp.h", "vrc_stroke.h", "vrc_raster.h", "vrc_box_words.h", "vrc_group.h", "vrc_list.h", "vrc_word_columns.h", "vrc_volume_state.h", "vrc_voxelize.h", "vrc_surface.h", "vrc_word_faces.h", "vrc_voxels.h", "vrc_rects.h", os.path.join("..", "..", "include", "vrc.h")]
+SOURCES = ["vrc_kernels.hip", "vrc_build_gpu.hip", "vrc_volume.hip", "vrc_volume_ops.hip", "vrc_snapshots.hip", "vrc_flood.hip", "vrc_components.hip", "vrc_cells.hip", "vrc_columns.hip", "vrc_levels.hip", "vrc_morph.hip", "vrc_delta.hip", "vrc_pack.hip", "vrc_distance.hip", "vrc_travel.hip", "vrc_sight.hip", "vrc_fall.hip", "vrc_fracture.hip", "vrc_rigid.hip", "vrc_stamp.hip", "vrc_stroke.hip", "vrc_raster.hip", "vrc_voxelize.hip", "vrc_surface.hip", "vrc_voxels.hip", "vrc_rects.hip", "vrc_present.hip", "vrc_api.cpp", "vrc_renderer.cpp", "vrc_ipc.cpp", "vrc_builder.cpp"]
+HEADERS = ["vrc_device.h", "vrc_walk.h", "vrc_internal.h", "vrc_host.h", "vrc_plan.h", "vrc_build_sweeps.h", "vrc_build_grids.h", "vrc_flood.h", "vrc_components.h", "vrc_cells.h", "vrc_columns.h", "vrc_levels.h", "vrc_morph.h", "vrc_delta.h", "vrc_pack.h", "vrc_distance.h", "vrc_travel.h", "vrc_sight.h", "vrc_fall.h", "vrc_fracture.h", "vrc_rigid.h", "vrc_stamp.h", "vrc_stroke.h", "vrc_raster.h", "vrc_box_words.h", "vrc_group.h", "vrc_list.h", "vrc_word_columns.h", "vrc_volume_state.h", "vrc_voxelize.h", "vrc_surface.h", "vrc_word_faces.h", "vrc_voxels.h", "vrc_rects.h", os.path.join("..", "..", "include", "vrc.h")]
 
 # -ffp-contract=off: hipcc fuses a*b+c into v_fma_f32 by default, which changes
 # which voxel a ray hits.  Correctly rounded f32 divide and

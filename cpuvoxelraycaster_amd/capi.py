@@ -24,6 +24,8 @@ VRC_MORPH_REACH = 16
 VRC_MORPH_MAX_OFFSETS = 1 << 20
 VRC_NO_COMPONENT = 0xffffffff
 VRC_DISTANCE_NONE = 0xffffffff
+VRC_SIGHT_THIN, VRC_SIGHT_TOUCH, VRC_SIGHT_PLAIN = 0, 1, 2
+VRC_SIGHT_CLEAR, VRC_SIGHT_BLOCKED, VRC_SIGHT_OUTSIDE = 0, 1, 2
 VRC_STROKE_LIMIT = 8192
 VRC_MESH_FRAC_BITS = 6
 VRC_RASTER_TOUCHED, VRC_RASTER_THIN = 0, 1
@@ -58,6 +60,10 @@ assert CONTACT_DTYPE.itemsize == 128
 CLEARANCE_DTYPE = np.dtype([("posed", "<u8"), ("none", "<u8"), ("sum", "<u8"), ("min_value", "<u4"), ("min_at", "<u4", 3),
                             ("max_value", "<u4"), ("max_at", "<u4", 3), ("reserved", "<u8")])
 assert CLEARANCE_DTYPE.itemsize == 64
+# vrc_sight (include/vrc.h: vrc_sight_segments): a straight walk over a field -- whether it was clear, blocked or had an endpoint
+# outside, the first voxel that was not clear (the end of a clear walk) and the voxel visited just before it
+SIGHT_DTYPE = np.dtype([("status", "<u4"), ("at", "<u4", 3), ("before", "<u4", 3), ("reserved", "<u4")])
+assert SIGHT_DTYPE.itemsize == 32
 # a record of a delta (include/vrc.h: vrc_delta_diff): bits = before[word] ^ after[word] != 0, word strictly ascending
 DELTA_RECORD_DTYPE = np.dtype([("word", "<u4"), ("bits", "<u4")])
 assert DELTA_RECORD_DTYPE.itemsize == 8
@@ -102,6 +108,11 @@ class TravelStats(C.Structure):
     """vrc_travel_stats (include/vrc.h): what vrc_travel_field reports"""
     _fields_ = [("seeds", C.c_uint64), ("reached", C.c_uint64), ("max_steps", C.c_uint32), ("argmax", C.c_uint32 * 3),
                 ("sweeps", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SightStats(C.Structure):
+    """vrc_sight_stats (include/vrc.h): what vrc_sight_field reports"""
+    _fields_ = [("visible", C.c_uint64), ("max_d2", C.c_uint32), ("argmax", C.c_uint32 * 3), ("reserved", C.c_uint32)]
 
 
 class FallStats(C.Structure):
@@ -260,6 +271,8 @@ SYMBOLS = {
     "vrc_travel_field": (_int, [_vp, _vp, _int, _int, _u32, C.POINTER(_vp), C.POINTER(TravelStats)]),
     "vrc_travel_connectivity": (_int, [_vp]),
     "vrc_travel_trace_paths": (_int, [_vp, _u64, _vp, _u32, _vp, _vp, _int, _vp]),
+    "vrc_sight_segments": (_int, [_vp, _u64, _vp, _u32, _u32, _int, _vp, _int, _vp]),
+    "vrc_sight_field": (_int, [_vp, _vp, _u32, _u32, _u32, _int, C.POINTER(_vp), C.POINTER(SightStats)]),
     "vrc_delta_diff": (_int, [_vp, _vp, C.POINTER(_vp), C.POINTER(DeltaStats)]),
     "vrc_delta_create": (_int, [_u32, _int, _u64, _vp, _int, C.POINTER(_vp), C.POINTER(DeltaStats)]),
     "vrc_delta_destroy": (_int, [_vp]),

@@ -1,9 +1,10 @@
 // vrc_snapshots.hip -- the snapshots taken from an editable volume (include/vrc.h) and their calls: the labels of its connected
 // components (vrc_labels_*, vrc_fall_*, vrc_rigid_*, vrc_fracture_*), its distance and travel fields (vrc_distance_*, vrc_travel_*)
-// and the difference of two volumes as a list of changed words (vrc_delta_*).  Kernels: vrc_components.hip, vrc_fall.hip,
-// vrc_rigid.hip, vrc_fracture.hip, vrc_distance.hip, vrc_travel.hip, vrc_delta.hip.  A snapshot owns its memory, is never written
-// after its creator returns, and keeps no event and no scratch: its host-memory calls stage in a block of their own, and what it
-// selects or places goes into a volume as an edit of that volume (staged_call in vrc_volume_state.h; ordering: DESIGN.md).
+// with the straight-line walks over them (vrc_sight_*), and the difference of two volumes as a list of changed words
+// (vrc_delta_*).  Kernels: vrc_components.hip, vrc_fall.hip, vrc_rigid.hip, vrc_fracture.hip, vrc_distance.hip, vrc_travel.hip,
+// vrc_sight.hip, vrc_delta.hip.  A snapshot owns its memory, is never written after its creator returns, and keeps no event and
+// no scratch: its host-memory calls stage in a block of their own, and what it selects or places goes into a volume as an edit
+// of that volume (staged_call in vrc_volume_state.h; ordering: DESIGN.md).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -16,6 +17,7 @@
 #include "vrc_fall.h"
 #include "vrc_fracture.h"
 #include "vrc_rigid.h"
+#include "vrc_sight.h"
 #include "vrc_travel.h"
 #include "vrc_volume_state.h"
 
@@ -32,7 +34,8 @@ struct vrc_labels {
 struct vrc_distance {
     int device = 0;
     uint32_t depth = 0;
-    int connectivity = 0;                 // 6 / 26: a travel field made with it; 0: a Euclidean field
+    int connectivity = 0;                 // 6 / 26: a travel field made with it; 0: a Euclidean field or a sight field
+    bool euclidean = false;               // made by vrc_volume_distance_field: the squared distance to a set, so sqrt is 1-Lipschitz
     uint32_t* d_field = nullptr;          // 8^depth squared distances (travel field: steps), [(x*S + y)*S + z]
 };
 
@@ -478,7 +481,7 @@ extern "C" int vrc_volume_distance_field(vrc_volume* medium, int to, int outside
     if (medium->depth < 2 || medium->depth > 10) return vrc::fail(VRC_ERR_INVALID, "%s: depth %u not in [2,10]", what, medium->depth);
     vrc_distance* d = new (std::nothrow) vrc_distance();
     if (!d) return vrc::fail(VRC_ERR_OOM, "out of host memory");
-    d->device = medium->device; d->depth = medium->depth;
+    d->device = medium->device; d->depth = medium->depth; d->euclidean = true;
     unsigned long long host[2] = {0ull, 0ull};
     const int rc = snapshot_run(what, medium, nullptr, &d->d_field, vrc::distance_scratch_bytes(d->depth, medium->cu_count), [&](uint32_t* d_scratch) {
         vrc::distance_run(medium->d_bricks, d->depth, to, outside, medium->cu_count, d->d_field, d_scratch, nullptr);
@@ -610,6 +613,76 @@ extern "C" int vrc_travel_trace_paths(const vrc_distance* d, uint64_t n, const u
         vrc::travel_trace_run(d->d_field, d->depth, d->connectivity, n, (const uint32_t*)p[0], capacity, (uint32_t*)p[2], (uint32_t*)p[1], call.st);
         return hipSuccess;
     });
+}
+
+// ---- straight-line walks over a field (the rule: include/vrc.h; the kernels: vrc_sight.hip) ---------------------------
+
+// what both sight calls refuse alike
+static int check_sight(const char* what, uint32_t lo, uint32_t hi, int flags)
+{
+    if (lo > hi) return vrc::fail(VRC_ERR_INVALID, "%s: lo %u above hi %u", what, lo, hi);
+    if (flags & ~(VRC_SIGHT_TOUCH | VRC_SIGHT_PLAIN)) return vrc::fail(VRC_ERR_INVALID, "%s: unknown flag bits in %d", what, flags);
+    return VRC_OK;
+}
+
+// The stride needs the free radius that only a distance to a set holds, and a band without an upper end.  A sight field has
+// connectivity 0 as well, but its values are no such distance (NONE in every shadow, small next to the eye): it walks plainly.
+static bool sight_strides(const vrc_distance* d, uint32_t hi, int flags) { return d->euclidean && hi == 0xffffffffu && !(flags & VRC_SIGHT_PLAIN); }
+
+extern "C" int vrc_sight_segments(const vrc_distance* d, uint64_t n, const int32_t* segments, uint32_t lo, uint32_t hi, int flags, vrc_sight* out, int mem,
+                                  void* stream)
+{
+    const char* what = "vrc_sight_segments";
+    if (!d) return vrc::fail(VRC_ERR_INVALID, "%s: null distance field", what);
+    if (const int rc = check_mem(what, mem)) return rc;
+    if (const int rc = check_sight(what, lo, hi, flags)) return rc;
+    if (n == 0) return VRC_OK;
+    if (!segments || !out) return vrc::fail(VRC_ERR_INVALID, "%s: null buffer", what);
+    if (const int rc = check_count(what, n, LANE_ITEMS, "segments")) return rc;
+    const Call call = snapshot_call(d->device, mem, stream);
+    const StagePart parts[] = {{out, (size_t)n * sizeof(vrc_sight), STAGE_OUT}, {segments, (size_t)n * 24u, STAGE_IN}};
+    return staged_call(what, call, parts, [&](void* const* p) {
+        vrc::sight_segments_run(d->d_field, d->depth, n, (const int32_t*)p[1], lo, hi, (flags & VRC_SIGHT_TOUCH) != 0, sight_strides(d, hi, flags),
+                                (vrc_sight*)p[0], call.st);
+        return hipSuccess;
+    });
+}
+
+// A creator without a volume: the NULL stream, nothing to order behind.  The field and the 16 bytes of stats are allocated
+// inside the frame; the blocking read-back of the stats has synchronised when it returns.
+extern "C" int vrc_sight_field(const vrc_distance* d, const uint32_t eye[3], uint32_t radius, uint32_t lo, uint32_t hi, int flags, vrc_distance** out,
+                               vrc_sight_stats* stats)
+{
+    const char* what = "vrc_sight_field";
+    if (!d || !out || !eye) return vrc::fail(VRC_ERR_INVALID, "%s: null argument", what);
+    if (const int rc = check_sight(what, lo, hi, flags)) return rc;
+    const uint32_t S = 1u << d->depth;
+    if (eye[0] >= S || eye[1] >= S || eye[2] >= S) return vrc::fail(VRC_ERR_INVALID, "%s: eye %u %u %u outside the volume of %u^3", what, eye[0], eye[1], eye[2], S);
+    vrc_distance* f = new (std::nothrow) vrc_distance();
+    if (!f) return vrc::fail(VRC_ERR_OOM, "out of host memory");
+    f->device = d->device; f->depth = d->depth;
+    unsigned long long* d_stats = nullptr;
+    unsigned long long host[2] = {0ull, 0ull};
+    const int rc = staged_call(what, snapshot_call(d->device, VRC_MEM_DEVICE, nullptr), [&]() {
+        hipError_t e = hipMalloc((void**)&f->d_field, (size_t)4u << (3u * f->depth));
+        if (e == hipSuccess) e = hipMalloc((void**)&d_stats, sizeof host);
+        if (e == hipSuccess) e = hipMemsetAsync(d_stats, 0, sizeof host, nullptr);
+        if (e != hipSuccess) return e;
+        vrc::sight_field_run(d->d_field, d->depth, eye, radius, lo, hi, (flags & VRC_SIGHT_TOUCH) != 0, sight_strides(d, hi, flags), f->d_field, d_stats, nullptr);
+        e = hipGetLastError();
+        return e != hipSuccess ? e : hipMemcpy(host, d_stats, sizeof host, hipMemcpyDeviceToHost);
+    });
+    if (d_stats) (void)hipFree(d_stats);
+    if (rc) {
+        (void)vrc_distance_destroy(f);
+        return rc;
+    }
+    if (stats) {
+        stats->visible = host[0]; stats->reserved = 0u;
+        decode_argmax(host[1], f->depth, &stats->max_d2, stats->argmax);
+    }
+    *out = f;
+    return VRC_OK;
 }
 
 // ---- a field read at the voxels of every posed piece (the rule: include/vrc.h; the kernels: vrc_rigid.hip) ---------

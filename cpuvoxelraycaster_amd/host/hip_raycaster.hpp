@@ -352,13 +352,14 @@ private:
 // on the device, S^3 uint32 in [(x*S + y)*S + z] order, that later edits of the volume do not change.  Movable, RAII.
 // HipVoxelVolume::travelField makes the same object with the steps from the seeds in place of the squared distance
 // (vrc_travel_field): connectivity() is then 6 or 26, travelStats() holds what the call reported, tracePaths() reads routes.
+// sight() walks straight segments over either kind and visibleFrom() makes the field of what an eye sees (vrc_sight_*).
 class HipVoxelDistance {
 public:
     ~HipVoxelDistance() { vrc_distance_destroy(d_); }
-    HipVoxelDistance(HipVoxelDistance&& o) noexcept : d_(o.d_), stats_(o.stats_), travel_(o.travel_) { o.d_ = nullptr; }
+    HipVoxelDistance(HipVoxelDistance&& o) noexcept : d_(o.d_), stats_(o.stats_), travel_(o.travel_), sight_(o.sight_) { o.d_ = nullptr; }
     HipVoxelDistance& operator=(HipVoxelDistance&& o) noexcept
     {
-        if (this != &o) { vrc_distance_destroy(d_); d_ = o.d_; stats_ = o.stats_; travel_ = o.travel_; o.d_ = nullptr; }
+        if (this != &o) { vrc_distance_destroy(d_); d_ = o.d_; stats_ = o.stats_; travel_ = o.travel_; sight_ = o.sight_; o.d_ = nullptr; }
         return *this;
     }
     HipVoxelDistance(const HipVoxelDistance&) = delete;
@@ -366,6 +367,7 @@ public:
 
     const vrc_distance_stats& stats() const { return stats_; }
     const vrc_travel_stats& travelStats() const { return travel_; }      // of a travel field; zero for a Euclidean one
+    const vrc_sight_stats& sightStats() const { return sight_; }         // of a sight field (visibleFrom); zero otherwise
     int connectivity() const { return vrc_travel_connectivity(d_); }   // 6 / 26: a travel field; 0: a Euclidean one
     uint32_t depth() const { return vrc_distance_depth(d_); }
     uint64_t bytes() const { return vrc_distance_bytes(d_); }
@@ -396,15 +398,37 @@ public:
         check(vrc_travel_trace_paths(d_, n, xyz, capacity, capacity ? paths.data() : nullptr, lengths.data(), VRC_MEM_HOST, nullptr),
               "vrc_travel_trace_paths");
     }
+    // Straight walks over the field (vrc_sight_segments) for n segments (n x 6: voxel a, voxel b): a record per segment --
+    // VRC_SIGHT_CLEAR when every visited voxel has lo <= value <= hi, VRC_SIGHT_BLOCKED with the first that has not and the
+    // voxel visited before it, VRC_SIGHT_OUTSIDE for an endpoint outside the volume.  flags: VRC_SIGHT_TOUCH for the
+    // supercover, VRC_SIGHT_PLAIN to never stride.  lo = r * r + 1 on the field to the solid asks for a ball of radius r.
+    std::vector<vrc_sight> sight(const int32_t* segments, uint64_t n, uint32_t lo = 1u, uint32_t hi = VRC_DISTANCE_NONE, int flags = VRC_SIGHT_THIN) const
+    {
+        std::vector<vrc_sight> out((size_t)n);
+        check(vrc_sight_segments(d_, n, segments, lo, hi, flags, out.data(), VRC_MEM_HOST, nullptr), "vrc_sight_segments");
+        return out;
+    }
+    // What an eye at voxel `eye` sees (vrc_sight_field): a new field holding |p - eye|^2 at every voxel p within `radius` (0:
+    // no limit) whose walk from the eye is clear up to, not counting, p itself, VRC_DISTANCE_NONE elsewhere; sightStats()
+    // holds what the call reported.  One walk per voxel in range.  Synchronous.
+    HipVoxelDistance visibleFrom(const uint32_t eye[3], uint32_t radius = 0u, uint32_t lo = 1u, uint32_t hi = VRC_DISTANCE_NONE, int flags = VRC_SIGHT_THIN) const
+    {
+        vrc_distance* d = nullptr;
+        vrc_sight_stats stats{};
+        check(vrc_sight_field(d_, eye, radius, lo, hi, flags, &d, &stats), "vrc_sight_field");
+        return HipVoxelDistance(d, stats);
+    }
     vrc_distance* handle() const { return d_; }
 
 private:
     friend class HipVoxelVolume;
     HipVoxelDistance(vrc_distance* adopted, const vrc_distance_stats& stats) : d_(adopted), stats_(stats) {}
+    HipVoxelDistance(vrc_distance* adopted, const vrc_sight_stats& sight) : d_(adopted), sight_(sight) {}
     HipVoxelDistance(vrc_distance* adopted, const vrc_travel_stats& travel) : d_(adopted), travel_(travel) {}
     vrc_distance* d_ = nullptr;
     vrc_distance_stats stats_{};
     vrc_travel_stats travel_{};
+    vrc_sight_stats sight_{};
 };
 
 // The difference of two volumes (include/vrc.h: vrc_delta_diff): a snapshot on the device, one record {word, bits} per

@@ -994,6 +994,33 @@ class VoxelVolume:
             field.close()
         return None if lengths[0] == capi.VRC_DISTANCE_NONE else paths[0]
 
+    def lineOfSight(self, a, b, radius=0):
+        """Whether a ball of `radius` voxels (0: a thin ray) passes in a straight line from voxel a to voxel b without
+        touching the solid: the distance field to the solid, then VoxelDistance.sight in supercover mode with lo =
+        radius^2 + 1, the radius rule of fillSpheres.  False as well when an endpoint lies outside the volume.  For many
+        segments keep the field and call its sight()."""
+        r = self._radius(radius, "lineOfSight")
+        field = self.distanceField()
+        try:
+            rec = field.sight(a, b, lo=r * r + 1, touch=True)
+        finally:
+            field.close()
+        return bool(rec["status"][0] == capi.VRC_SIGHT_CLEAR)
+
+    def visibleFrom(self, eye, radius=0):
+        """A new volume holding the voxels an eye at voxel `eye` sees within `radius` voxels (0: no limit), the solid surface
+        voxels at the end of a clear line included: the distance field to the solid, its sight field (VoxelDistance.visibleFrom)
+        and a select of the finite values.  AND it with this volume for the visible blocks."""
+        field = self.distanceField()
+        try:
+            seen = field.visibleFrom(eye, radius)
+        finally:
+            field.close()
+        try:
+            return seen.select(0, capi.VRC_DISTANCE_NONE - 1)
+        finally:
+            seen.close()
+
     @staticmethod
     def _radius(r, what):
         r = int(r)
@@ -1764,6 +1791,40 @@ class VoxelDistance:
         check(capi.load().vrc_travel_trace_paths(self._h, n, ptr(starts_ptr), int(capacity), ptr(paths_ptr), ptr(lengths_ptr), capi.VRC_MEM_DEVICE,
                                                    ptr(stream)))
 
+    @staticmethod
+    def _sight_flags(touch, plain=False):
+        return (capi.VRC_SIGHT_TOUCH if touch else 0) | (capi.VRC_SIGHT_PLAIN if plain else 0)
+
+    def sight(self, a, b, lo=1, hi=capi.VRC_DISTANCE_NONE, touch=False, plain=False):
+        """Straight walks over the field (include/vrc.h: vrc_sight_segments): one capi.SIGHT_DTYPE record per segment from
+        voxel a[i] to voxel b[i] ((n, 3) each, or one voxel for all) -- status capi.VRC_SIGHT_CLEAR when every visited voxel has
+        lo <= value <= hi, VRC_SIGHT_BLOCKED with `at` the first that has not and `before` the voxel visited before it,
+        VRC_SIGHT_OUTSIDE for an endpoint outside the volume.  touch: the supercover, every voxel the segment touches, where
+        the default passes diagonally between two voxels.  lo = r^2 + 1 on the field to the solid asks for a ball of radius
+        r.  plain: never stride (the records are the same either way)."""
+        a, b = np.asarray(a, np.int64).reshape(-1, 3), np.asarray(b, np.int64).reshape(-1, 3)
+        n = max(len(a), len(b))
+        segments = np.empty((n, 6), np.int32)
+        segments[:, :3], segments[:, 3:] = a, b
+        out = np.zeros(n, capi.SIGHT_DTYPE)
+        check(capi.load().vrc_sight_segments(self._h, n, ptr(segments), int(lo), int(hi), self._sight_flags(touch, plain), ptr(out), capi.VRC_MEM_HOST, None))
+        return out
+
+    def sightDevice(self, n, segments_ptr, out_ptr, lo=1, hi=capi.VRC_DISTANCE_NONE, touch=False, plain=False, stream=None):
+        """the same over n x 6 int32 of segments and n 32-byte records in device memory, asynchronous on `stream`"""
+        check(capi.load().vrc_sight_segments(self._h, n, ptr(segments_ptr), int(lo), int(hi), self._sight_flags(touch, plain), ptr(out_ptr), capi.VRC_MEM_DEVICE,
+                                             ptr(stream)))
+
+    def visibleFrom(self, eye, radius=0, lo=1, hi=capi.VRC_DISTANCE_NONE, touch=False, plain=False):
+        """What an eye at voxel `eye` sees (include/vrc.h: vrc_sight_field): a new VoxelDistance holding |p - eye|^2 at every
+        voxel p within `radius` (0: no limit) whose walk from the eye is clear up to, not counting, p itself, and
+        capi.VRC_DISTANCE_NONE elsewhere; `stats` is a capi.SightStats (visible, max_d2, argmax).  One walk per voxel in
+        range.  Synchronous."""
+        eye = np.ascontiguousarray(eye, np.uint32).reshape(3)
+        handle, stats = C.c_void_p(), capi.SightStats()
+        check(capi.load().vrc_sight_field(self._h, ptr(eye), int(radius), int(lo), int(hi), self._sight_flags(touch, plain), C.byref(handle), C.byref(stats)))
+        return VoxelDistance(handle, stats, self.depth, self.device)
+
     def bytes(self):
         return int(capi.load().vrc_distance_bytes(self._h))
 
@@ -1806,6 +1867,29 @@ class VoxelDistance:
             self.close()
         except Exception:
             pass
+
+
+def smoothPath(route, field, radius=0, touch=True):
+    """Greedy string pulling of a route ((k, 3) voxels, as VoxelVolume.shortestPath or VoxelDistance.tracePaths return it)
+    over `field`, the VoxelDistance to the solid: from the anchor -- first the route's start -- one batched sight() covers
+    every later voxel of the route, the one of greatest index that a ball of `radius` reaches in a straight line becomes the
+    next waypoint and anchor, until the end is reached.  Returns the waypoints, a subsequence of the route that keeps both
+    ends.  Every leg that spans more than one step of the route is a clear segment.  Where no later voxel is reached in a
+    clear line -- the next step of the route is not clear itself: the route runs closer to a wall than `radius`, or, with
+    touch, takes a diagonal step past a corner -- that single step is kept as the leg, clear or not; check such legs with
+    sight() if the route was not made for this radius."""
+    route = np.ascontiguousarray(route, np.uint32).reshape(-1, 3)
+    r = int(radius)
+    if r < 0:
+        raise ValueError(f"smoothPath: negative radius {r}")
+    lo = min(r, 65535) ** 2 + 1
+    keep, anchor = [0], 0
+    while anchor < len(route) - 1:
+        records = field.sight(route[anchor], route[anchor + 1:], lo=lo, touch=touch)
+        clear = np.flatnonzero(records["status"] == capi.VRC_SIGHT_CLEAR)
+        anchor += int(clear[-1]) + 1 if len(clear) else 1
+        keep.append(anchor)
+    return route[keep]
 
 
 class VoxelDelta:

@@ -1150,6 +1150,73 @@ int vrc_rigid_clearance(const vrc_labels *l, const uint8_t *keep /* C bytes, NUL
                         const vrc_affine *maps /* C */, const uint32_t *boxes /* C x 6 lo,hi; NULL = all of the field */,
                         const vrc_distance *field, vrc_piece_clearance *out /* C */, int mem, void *stream);
 
+/* Line of sight and visible sets by exact voxel walks over a vrc_distance snapshot: can a projectile or an agent of radius r
+ * go from a to b in a straight line, and what does an eye or a point light at e see.  The snapshot holds both things such a
+ * query needs: it is a copy of the occupancy (D = 0 exactly on the feature set) and it holds the free radius round every voxel.
+ * Both calls take snapshots only, as vrc_rigid_clearance does: they order behind nothing.  Exact in integers.
+ *
+ * The walk from voxel a to voxel b, both inside the volume.  The segment runs from the centre of a to the centre of b; with
+ * n_c = |b_c - a_c| per axis, crossing k of axis c (k = 1..n_c) happens at t = (2k - 1) / (2 n_c).  Times are compared by
+ * cross-multiplication in integers, (2k - 1) n_d against (2j - 1) n_c, products below 2^22; no float is used anywhere.  Centres
+ * are half-integers, so the segment never lies in a face plane and ties are isolated points where it passes through an edge or
+ * a corner.  VRC_SIGHT_THIN (flags bit 0 clear): crossings of equal t are ONE diagonal step; the visited voxels are exactly
+ * those whose open cube the open segment meets, in order of t -- the travel field's convention, a diagonal step is allowed
+ * whatever lies beside it.  VRC_SIGHT_TOUCH (flags bit 0 set), the supercover: at a tie of the axis set T the walk first visits
+ * the voxels reached from the current one by advancing each non-empty proper subset of T, in ascending order of the subset's
+ * mask (bit 0 = x, 1 = y, 2 = z), then the voxel with all of T advanced; the visited voxels are exactly those whose closed
+ * cube the segment meets.  The walk visits a first, with index 0, and b last; with a == b there is one visited voxel.  The
+ * visited SET of b -> a is that of a -> b in both modes.
+ *
+ * Clear.  A voxel p is clear iff lo <= field(p) <= hi, VRC_DISTANCE_NONE compared as the plain value 0xffffffff
+ * (vrc_distance_select's convention).  A thin line of sight on the Euclidean field to the solid: lo = 1, hi = 0xffffffff.  A
+ * ball of radius r under vrc_volume_fill_spheres' radius rule: lo = r^2 + 1.  Staying inside the reached medium of a travel
+ * field: lo = 0, hi = 0xfffffffe.
+ *
+ * vrc_sight_segments writes one record per segment (segments: n x 6 int32, a then b).  status = VRC_SIGHT_BLOCKED: `at` is the
+ * first visited voxel that is not clear and `before` the voxel visited just before it, `at` itself when `at` is a;
+ * VRC_SIGHT_CLEAR: every visited voxel is clear, `at` is b and `before` the voxel visited just before b; VRC_SIGHT_OUTSIDE: an
+ * endpoint lies outside the volume, nothing is walked and every other byte is 0.  reserved = 0.  Any vrc_distance snapshot of
+ * depth 2..10 is accepted, Euclidean or travel.  mem / stream as in vrc_distance_at: VRC_MEM_HOST stages segments and records
+ * in a block of the call's own and is synchronous, VRC_MEM_DEVICE works in place and is asynchronous on `stream`.  A NULL
+ * field, NULL buffers with n > 0, lo > hi, unknown flag bits, a bad mem and an n beyond one launch are VRC_ERR_INVALID, refused
+ * before any device call; n == 0 is a no-op.  The call keeps no scratch.
+ *
+ * vrc_sight_field: what an eye sees, as a new vrc_distance snapshot of d's depth on d's device (vrc_travel_connectivity 0).
+ * The value at p is |p - eye|^2 when p is in range -- radius == 0, or |p - eye|^2 <= radius^2 -- and every voxel visited by the
+ * walk eye -> p is clear, NOT counting p itself; VRC_DISTANCE_NONE otherwise; p == eye always has the value 0.  A solid
+ * surface voxel is therefore visible when the air up to it is clear, and an eye inside a wall sees only itself.  Every
+ * accessor works on the result: vrc_distance_select(out, 0, r^2, dst, op) is "seen within r", AND-ed with the solid it is the
+ * visible blocks; vrc_rigid_clearance on it says which pieces are in view.  stats (may be NULL): visible = the number of
+ * finite values, max_d2 = the largest, argmax = the voxel of smallest dense index that holds it, reserved = 0.  Synchronous,
+ * on the NULL stream, as the other snapshot creators are; the result owns 4 bytes per voxel, 16 bytes of stats are freed
+ * before return.  The cost is ONE WALK PER VOXEL IN RANGE: S^3 walks without a radius.  NULL d or out, an eye outside the
+ * volume, lo > hi and unknown flags are VRC_ERR_INVALID.
+ *
+ * The stride.  On a field made by vrc_volume_distance_field, with hi == 0xffffffff, the walk may STRIDE: such a field is the
+ * squared distance to a set, sqrt D is 1-Lipschitz, so the value at a clear voxel bounds how far the segment can be followed
+ * without meeting a voxel below lo, and the walk jumps that far and goes on from the voxel the plain walk would be in.  The
+ * stride is an optimisation and never part of the rule: the records are byte-identical to the plain walk's (the bound and its
+ * proof, and how the kernels are built: DESIGN.md; times: README.md).  Every other snapshot -- a travel field, and a sight field,
+ * whose values are no distance to a set although its vrc_travel_connectivity is 0 too --, hi < 0xffffffff and VRC_SIGHT_PLAIN
+ * (flags bit 1: so that tests and benchmarks can compare the two on the device) always take the plain walk. */
+#define VRC_SIGHT_THIN 0
+#define VRC_SIGHT_TOUCH 1
+#define VRC_SIGHT_PLAIN 2
+#define VRC_SIGHT_CLEAR 0u
+#define VRC_SIGHT_BLOCKED 1u
+#define VRC_SIGHT_OUTSIDE 2u
+typedef struct vrc_sight {      /* 32 bytes */
+    uint32_t status;            /* VRC_SIGHT_CLEAR 0, VRC_SIGHT_BLOCKED 1, VRC_SIGHT_OUTSIDE 2 */
+    uint32_t at[3];             /* BLOCKED: the first visited voxel that is not clear; CLEAR: b */
+    uint32_t before[3];         /* the voxel visited just before `at`; `at` itself when `at` has index 0 */
+    uint32_t reserved;          /* 0 */
+} vrc_sight;
+typedef struct vrc_sight_stats { uint64_t visible; uint32_t max_d2; uint32_t argmax[3]; uint32_t reserved; } vrc_sight_stats;
+int vrc_sight_segments(const vrc_distance *d, uint64_t n, const int32_t *segments /* n x 6: a, b */,
+                       uint32_t lo, uint32_t hi, int flags, vrc_sight *out, int mem, void *stream);
+int vrc_sight_field(const vrc_distance *d, const uint32_t eye[3], uint32_t radius, uint32_t lo, uint32_t hi,
+                    int flags, vrc_distance **out, vrc_sight_stats *stats);
+
 /* Deltas: the difference of two volumes as a compact list of changed occupancy words, on the device -- the undo / redo step
  * (an undo stack of clones costs a whole occupancy per step, 16 MiB at 512^3 and 128 MiB at 1024^3, where an edit changes a
  * few hundred words), what carries an edit from the rank that made it to the replicas of the other ranks, and the answer to
